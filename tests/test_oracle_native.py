@@ -34,21 +34,33 @@ def test_restatement_matches_reference_goldens(oracle_native, scans, golden, pai
         assert np.array_equal(sha(idx[:, :lim]), golden[key + '/sha'])
 
 
-def test_restatement_matches_reference_build_on_random_clouds(oracle_native):
-    ref = oracle_native.reference()
-    if ref is None:
-        pytest.skip('oracle/_ref not built (reference tree absent)')
-    o = oracle_native.restatement()
+def random_clouds():
+    """Seeded random clouds with exact duplicates (distance ties) and their voxel sizes -> [(key, pts, lens, voxel)]."""
     rng = np.random.default_rng(0)
+    cases = []
     for n0, n1, scale in [(1, 1, 1.0), (5, 300, 3.0), (2000, 1500, 20.0), (4000, 1, 40.0)]:
         pts = (rng.standard_normal((n0 + n1, 3)) * scale).astype(np.float32)
         pts[: min(n0, 3)] = pts[0]  # duplicates -> exact distance ties
         lens = np.array([n0, n1], dtype=np.int64)
         for voxel in (0.6, 2.4):
-            po, lo = o.grid_subsampling(pts, lens, np.float32(voxel))
+            cases.append((f'{n0}_{n1}_{voxel}', pts, lens, voxel))
+    return cases
+
+
+def test_restatement_matches_reference_build_on_random_clouds(oracle_native, golden_dir):
+    """Against the reference's own build when oracle/_ref is present, and always against its outputs stored in
+    tests/golden/ref_random_clouds.npz (gen_ref_random_golden.py)."""
+    ref = oracle_native.reference()
+    stored = np.load(os.path.join(golden_dir, 'ref_random_clouds.npz'))
+    o = oracle_native.restatement()
+    for key, pts, lens, voxel in random_clouds():
+        po, lo = o.grid_subsampling(pts, lens, np.float32(voxel))
+        io = o.radius_neighbors(po, pts, lo, lens, np.float32(voxel * 2.125))
+        assert np.array_equal(lo, stored[key + '/lengths']) and np.array_equal(po, stored[key + '/points']), key
+        assert np.array_equal(io, stored[key + '/neighbors']), key
+        if ref is not None:
             pr, lr = ref.grid_subsampling(pts, lens, np.float32(voxel))
             assert np.array_equal(lo, lr) and np.array_equal(po, pr)
-            io = o.radius_neighbors(po, pts, lo, lens, np.float32(voxel * 2.125))
             ir = oracle_native.canonicalize_ties(po, pts, ref.radius_neighbors(po, pts, lo, lens, np.float32(voxel * 2.125)))
             assert np.array_equal(io, ir)
 
