@@ -408,6 +408,29 @@ int rdm_coarse_matching_features(const float* ref_feats, int64_t ld_ref, int64_t
                                  int64_t* src_idx, float* out_scores, int32_t* out_count, void* ws,
                                  size_t ws_bytes, void* stream);
 
+/* ---- evaluation: ground-truth superpoint correspondences ----------------------------------------------------
+ * Replaces get_node_correspondences (geotransformer/modules/registration/matching.py:252-350) as test.py's evaluation
+ * forward calls it (experiments/model.py:283-295, radius cfg.model.ground_truth_matching_radius = 0.6,
+ * experiments/config.py:101).  ref/src nodes [m,3] / [n,3]; patches of k <= 128 slots: with ref_knn_idx / src_knn_idx
+ * null, *_points are the gathered patch points [m*k, 3] / [n*k, 3] (the reference's knn points); otherwise *_points are
+ * the clouds' points [*_n_points, 3] and *_knn_idx the int64 [m,k] / [n,k] slot indices into them, an index outside
+ * [0, n_points) standing for the zero pad row (rdm_point_to_node's layout).  Masks (u8, 1 = valid) may be null = all
+ * valid, as the reference's None.  transform: device f32 4x4 row-major, src -> ref; pos_radius in double as the Python
+ * float it is (the sphere test uses (float)pos_radius, the point test (float)(pos_radius^2)).
+ * Outputs: the candidates with overlap > 0 in row-major (ref, src) order (torch.nonzero's): out_indices int64 [C,2],
+ * out_overlaps f32 [C], at most `capacity` rows written; counts (device int32[2]) = {C, B} (B = candidate pairs that pass
+ * the sphere test); *status (device int32, caller zeroes) = 1 when C > capacity (-> RDM_ERR_CAPACITY for the caller).
+ * Workspace: rdm_gt_node_correspondences_workspace_bytes(m, n) (about 4 B per node pair, the worst case B = m*n).
+ * m * n <= 2^31.                                                                                                      */
+size_t rdm_gt_node_correspondences_workspace_bytes(int64_t m, int64_t n);
+int rdm_gt_node_correspondences(const float* ref_nodes, int64_t m, const float* src_nodes, int64_t n,
+                                const float* ref_points, const int64_t* ref_knn_idx, int64_t ref_n_points,
+                                const float* src_points, const int64_t* src_knn_idx, int64_t src_n_points, int k,
+                                const uint8_t* ref_node_mask, const uint8_t* src_node_mask, const uint8_t* ref_knn_mask,
+                                const uint8_t* src_knn_mask, const float* transform, double pos_radius,
+                                int64_t* out_indices, float* out_overlaps, int64_t capacity, int32_t* counts,
+                                int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- a14: Sinkhorn ---------------------------------------------------------------------------------
  * Replaces LearnableLogOptimalTransport.forward (geotransformer/modules/sinkhorn/
  * learnable_sinkhorn.py:13-66): scores [batch, m, n], masks [batch, m] / [batch, n] (1 = valid),
@@ -626,6 +649,14 @@ int rdm_engine_get_tensor(rdm_engine* e, const char* name, rdm_tensor_view* out)
 int rdm_engine_export(rdm_engine* e, int n, const char* const* names, void* const* dst, void* stream);
 /* rdm_engine_get_tensor for n names at once (out[n]). */
 int rdm_engine_describe(rdm_engine* e, int n, const char* const* names, rdm_tensor_view* out);
+/* The same stage (rdm_gt_node_correspondences; experiments/model.py:283-295 -> matching.py:252-350) on the LAST run's
+ * resident superpoints, patches and fine points (rdm_engine_run / _forward / _forward_batched / the lock-step entries, per
+ * engine): no upload, no export.  transform: device f32 4x4 (src -> ref).  Writes at most `capacity` rows to out_indices
+ * (int64 [C,2]) / out_overlaps (f32 [C]); count_host[0..1] = {C, B} (host int64[2]).  Scratch comes from the engine's
+ * arena above the last run's tensors.  Synchronises `stream`; returns RDM_ERR_CAPACITY when C > capacity (nothing written
+ * past capacity) and RDM_ERR_ARG when the engine has no completed forward run (e.g. after rdm_engine_collate alone).   */
+int rdm_engine_gt_node_correspondences(rdm_engine* e, const float* transform, double pos_radius, int64_t* out_indices,
+                                       float* out_overlaps, int64_t capacity, int64_t* count_host, void* stream);
 /* Plain device-to-device copy on `stream` (lets a host without a HIP binding read arena tensors). */
 int rdm_copy_device(void* dst, const void* src, size_t bytes, void* stream);
 

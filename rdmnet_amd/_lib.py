@@ -121,6 +121,10 @@ SIGNATURES = {
     'rdm_coarse_matching_features_workspace_bytes': (c_size, [c_i64, c_i64]),
     'rdm_coarse_matching_features': (c_int, [c_void, c_i64, c_i64, c_void, c_i64, c_i64, c_i64, c_void, c_void, c_int, c_int,
                                              c_void, c_void, c_void, c_void, c_void, c_size, c_void]),
+    'rdm_gt_node_correspondences_workspace_bytes': (c_size, [c_i64, c_i64]),
+    'rdm_gt_node_correspondences': (c_int, [c_void, c_i64, c_void, c_i64, c_void, c_void, c_i64, c_void, c_void, c_i64, c_int,
+                                            c_void, c_void, c_void, c_void, c_void, ctypes.c_double, c_void, c_void, c_i64,
+                                            c_void, c_void, c_void, c_size, c_void]),
     'rdm_sinkhorn': (c_int, [c_void, c_i64, c_i64, c_i64, c_void, c_void, c_void, c_int, c_void, c_void]),
     'rdm_lgr_workspace_bytes': (c_size, [c_i64]),
     'rdm_lgr': (c_int, [c_void, c_void, c_void, c_void, c_void, c_i64, c_i64, c_f32, c_int, c_int, c_void, c_void,
@@ -151,6 +155,7 @@ SIGNATURES = {
     'rdm_engine_get_tensor': (c_int, [c_void, ctypes.c_char_p, c_void]),
     'rdm_engine_describe': (c_int, [c_void, c_int, c_void, c_void]),
     'rdm_engine_export': (c_int, [c_void, c_int, c_void, c_void, c_void]),
+    'rdm_engine_gt_node_correspondences': (c_int, [c_void, c_void, ctypes.c_double, c_void, c_void, c_i64, c_void, c_void]),
     'rdm_copy_device': (c_int, [c_void, c_void, c_size, c_void]),
 }
 

@@ -130,6 +130,17 @@ inline hipError_t set_max_dynamic_lds(const void* kernel, int bytes, std::atomic
 
 constexpr int kWave = 64;
 
+// The reference's fp32 squared distance, pairwise_distance (geotransformer/modules/ops/pairwise_distance.py:4-31):
+// d = (|x|^2 - 2*xy) + |y|^2, clamped at 1e-12, with xy = fma(x2,y2, fma(x1,y1, x0*y0)) -- the order the reference's sgemm
+// uses for k = 3 -- and xn / yn = (v0*v0 + v1*v1) + v2*v2 given by the caller.  Shared by point_to_node (matching.hip) and
+// the ground-truth superpoint correspondences (gt_node_corr.hip); never contracted, whatever the including file's setting.
+__device__ __forceinline__ float ref_sq_dist(float x0, float x1, float x2, float xn, float y0, float y1, float y2, float yn) {
+#pragma clang fp contract(off)
+  const float xy = fmaf(x2, y2, fmaf(x1, y1, x0 * y0));
+  float d = (xn - 2.f * xy) + yn;
+  return d < 1e-12f ? 1e-12f : d;
+}
+
 // element `off` of a neighbour-index table held as int64 (i32 = 0) or int32 (i32 = 1)
 __device__ __forceinline__ long long ld_index(const int64_t* p, long long off, int i32) {
   return i32 ? static_cast<long long>(reinterpret_cast<const int32_t*>(p)[off]) : static_cast<long long>(p[off]);

@@ -135,6 +135,20 @@ struct rdm_engine {
   std::vector<hipEvent_t> events;      // 3 per KPConv layer: before gather, between, after GEMM
   std::vector<rdm_kpconv_profile> prof;  // filled at the end of a run
   int prof_layers = 0;
+  // What rdm_engine_gt_node_correspondences reads: the last completed forward's superpoints, their patches (point_to_node's
+  // layout: [m, K] int64 indices into the cloud's fine points, pad = that cloud's fine-point count) and the fine points, all
+  // in the arena.  Cleared whenever the arena is rewritten; set at the end of a forward that completed.
+  struct GtInputs {
+    bool valid = false;
+    const float* nodes[2] = {nullptr, nullptr};
+    int64_t m[2] = {0, 0};
+    const float* pf[2] = {nullptr, nullptr};
+    int64_t nf[2] = {0, 0};
+    const int64_t* knn[2] = {nullptr, nullptr};
+    const uint8_t* km[2] = {nullptr, nullptr};
+    const uint8_t* nm[2] = {nullptr, nullptr};
+    int k = 0;
+  } gt;
 
   template <typename T>
   T* alloc(size_t count) {
@@ -948,6 +962,7 @@ extern "C" int rdm_engine_reserve(rdm_engine* e, size_t bytes) {
   RDM_HIP_CHECK(hipDeviceSynchronize());  // (runs of this engine may be in flight on any stream)
   e->batch.clear();
   e->arena_base = 0;
+  e->gt.valid = false;
   RDM_HIP_CHECK(hipFree(e->arena));
   e->arena = nullptr;
   e->arena_cap = bytes;
@@ -1058,6 +1073,7 @@ static int collate_batch_once(rdm_engine* e, int B, const float* const* refs, co
   const rdm_engine_config& c = e->cfg;
   e->arena_off = 0;
   e->arena_base = 0;
+  e->gt.valid = false;
   e->batch.clear();
   e->taps.clear();
   Run r;
@@ -1453,6 +1469,7 @@ static int engine_run_once(rdm_engine* e, const float* ref_points, int64_t n_ref
                            const rdm_data_dict* dd, rdm_engine_result* res, void* stream, const PairPyramid* pre) {
   const rdm_engine_config& c = e->cfg;
   e->arena_off = pre ? e->arena_base : 0;  // (a pair of a collated batch: its pyramid lies below arena_base)
+  e->gt.valid = false;
   if (!pre) {
     e->batch.clear();  // (the arena is rewritten: a collated batch is gone)
     e->arena_base = 0;
@@ -1969,6 +1986,23 @@ static int engine_run_once(rdm_engine* e, const float* ref_points, int64_t n_ref
   RDM_DUP_LOOP("p2n")
   ENG_CHECK(rdm_point_to_node_pair(pf_ref, nf_ref, nodes, m_r, pf_src, nf_src, nodes + 3 * m_r, m_s, K, r_knn, r_km, r_nm, s_knn,
                                    s_km, s_nm, p2n_status, r.ws, r.ws_bytes, r.st));  // both clouds, one set of launches
+  {  // (kept for rdm_engine_gt_node_correspondences; valid once the run completes)
+    rdm_engine::GtInputs& g = e->gt;
+    g.nodes[0] = nodes; g.nodes[1] = nodes + 3 * m_r;
+    g.m[0] = m_r; g.m[1] = m_s;
+    g.pf[0] = pf_ref; g.pf[1] = pf_src;
+    g.nf[0] = nf_ref; g.nf[1] = nf_src;
+    g.knn[0] = r_knn; g.knn[1] = s_knn;
+    g.km[0] = r_km; g.km[1] = s_km;
+    g.nm[0] = r_nm; g.nm[1] = s_nm;
+    g.k = K;
+  }
+  tap(r, "ref_node_masks", r_nm, m_r, 1, 1, 2);  // (the grouping: what the per-op mirror's taps hold under the same names)
+  tap(r, "src_node_masks", s_nm, m_s, 1, 1, 2);
+  tap(r, "ref_knn", r_knn, m_r, K, K, 1);
+  tap(r, "src_knn", s_knn, m_s, K, K, 1);
+  tap(r, "ref_knn_masks", r_km, m_r, K, K, 2);
+  tap(r, "src_knn_masks", s_km, m_s, K, K, 2);
   const int kc = c.num_correspondences;
   int64_t* r_sel = e->alloc<int64_t>(kc);
   int64_t* s_sel = e->alloc<int64_t>(kc);
@@ -2102,6 +2136,7 @@ static int engine_run_once(rdm_engine* e, const float* ref_points, int64_t n_ref
   tap(r, "src_corr_points", sc, res->n_correspondences, 3, 3, 0);
   tap(r, "corr_scores", cs, res->n_correspondences, 1, 1, 0);
   tap(r, "estimated_transform", T, 4, 4, 4, 0);
+  e->gt.valid = true;
   return RDM_OK;
 }
 
@@ -2191,6 +2226,55 @@ extern "C" int rdm_engine_export(rdm_engine* e, int n, const char* const* names,
     if (++b.n == 24) ENG_CHECK(flush());
   }
   return flush();
+}
+
+namespace rdm {
+int gt_node_correspondences_impl(const float* ref_nodes, int64_t m, const float* src_nodes, int64_t n, const float* ref_points,
+                                 const int64_t* ref_idx, int64_t ref_n_points, const float* src_points, const int64_t* src_idx,
+                                 int64_t src_n_points, int k, const uint8_t* ref_node_mask, const uint8_t* src_node_mask,
+                                 const uint8_t* ref_knn_mask, const uint8_t* src_knn_mask, const float* transform,
+                                 double pos_radius, int64_t* out_indices, float* out_overlaps, int64_t capacity, int32_t* counts,
+                                 int32_t* status, int32_t* mirror, void* ws, size_t ws_bytes, void* stream);
+}
+
+extern "C" int rdm_engine_gt_node_correspondences(rdm_engine* e, const float* transform, double pos_radius, int64_t* out_indices,
+                                                  float* out_overlaps, int64_t capacity, int64_t* count_host, void* stream) {
+  RDM_REQUIRE(e && transform && count_host, "rdm_engine_gt_node_correspondences: null pointer");
+  RDM_REQUIRE(e->gt.valid, "rdm_engine_gt_node_correspondences: the engine holds no completed forward run (its superpoints, "
+                           "patches and fine points); run rdm_engine_run / rdm_engine_forward first");
+  const rdm_engine::GtInputs& g = e->gt;
+  // scratch above the last run's tensors, released again below (the call synchronises before it returns)
+  const size_t off_before = e->arena_off;
+  const size_t ws_bytes = rdm_gt_node_correspondences_workspace_bytes(g.m[0], g.m[1]);
+  char* ws = e->alloc<char>(ws_bytes);
+  int32_t* counts = e->alloc<int32_t>(2);
+  if (ws == nullptr || counts == nullptr) {
+    e->arena_off = off_before;
+    set_error("rdm_engine_gt_node_correspondences: %zu B of scratch do not fit above the last run in the arena (%zu B)", ws_bytes,
+              e->arena_cap);
+    return RDM_ERR_WORKSPACE;
+  }
+  int32_t* mirror_dev = reinterpret_cast<int32_t*>(static_cast<char*>(e->pinned_dev) + 512);  // {C, B}
+  const int32_t* mirror = reinterpret_cast<const int32_t*>(static_cast<const char*>(e->pinned) + 512);
+  const int rc = rdm::gt_node_correspondences_impl(
+      g.nodes[0], g.m[0], g.nodes[1], g.m[1], g.pf[0], g.knn[0], g.nf[0], g.pf[1], g.knn[1], g.nf[1], g.k, g.nm[0], g.nm[1], g.km[0],
+      g.km[1], transform, pos_radius, out_indices, out_overlaps, capacity, counts, nullptr, mirror_dev, ws, ws_bytes, stream);
+  hipError_t err = hipSuccess;
+  if (rc == RDM_OK) err = hipStreamSynchronize(static_cast<hipStream_t>(stream));
+  e->arena_off = off_before;
+  if (rc != RDM_OK) return rc;
+  if (err != hipSuccess) {
+    set_error("rdm_engine_gt_node_correspondences: hipStreamSynchronize failed: %s", hipGetErrorString(err));
+    return RDM_ERR_HIP;
+  }
+  count_host[0] = mirror[0];
+  count_host[1] = mirror[1];
+  if (count_host[0] > capacity) {
+    set_error("rdm_engine_gt_node_correspondences: %lld correspondences, capacity %lld", (long long)count_host[0],
+              (long long)capacity);
+    return RDM_ERR_CAPACITY;
+  }
+  return RDM_OK;
 }
 
 extern "C" int rdm_copy_device(void* dst, const void* src, size_t bytes, void* stream) {

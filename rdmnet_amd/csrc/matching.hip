@@ -157,12 +157,7 @@ __global__ __launch_bounds__(1024) void compact_index_pair_kernel(const unsigned
 
 // ---------------------------------------------------------------------------------------------
 // point_to_node_partition (modules/ops/pointcloud_partition.py:60-107)
-__device__ __forceinline__ float ref_sq_dist(float x0, float x1, float x2, float xn, float y0, float y1,
-                                             float y2, float yn) {
-  const float xy = fmaf(x2, y2, fmaf(x1, y1, x0 * y0));
-  float d = (xn - 2.f * xy) + yn;
-  return d < 1e-12f ? 1e-12f : d;
-}
+// (ref_sq_dist, the reference's fp32 distance formula: common.h)
 
 // one thread per point: owner = argmin over nodes (first minimum), d_own = that distance
 __device__ __forceinline__ void p2n_assign_body(unsigned block_x, const float* points, int n, const float* nodes, int m, int32_t* owner,

@@ -450,6 +450,25 @@ class Engine:
         return (view(self.result.host_ref_corr_points, 3 * n).reshape(n, 3), view(self.result.host_src_corr_points, 3 * n).reshape(n, 3),
                 view(self.result.host_corr_scores, n))
 
+    def gt_node_correspondences(self, transform, pos_radius=0.6):
+        """get_node_correspondences (matching.py:252-350, experiments/model.py:283-295) on the last run's resident superpoints,
+        patches and fine points (rdm_engine_gt_node_correspondences): transform f32 [4,4] src -> ref (any device) ->
+        (corr_indices i64 [C,2], corr_overlaps f32 [C], B) with B the number of candidate patch pairs.  Synchronises the
+        current stream."""
+        T = torch.as_tensor(transform, dtype=torch.float32).to(self.device).contiguous()
+        if tuple(T.shape) != (4, 4):
+            raise RuntimeError(f'gt_node_correspondences: transform has shape {tuple(T.shape)}, expected (4, 4)')
+        m, n = int(self.result.n_ref_nodes), int(self.result.n_src_nodes)
+        cap = max(m * n, 1)  # the worst case B = M*N
+        idx = torch.empty((cap, 2), dtype=torch.int64, device=self.device)
+        ovl = torch.empty((cap,), dtype=torch.float32, device=self.device)
+        counts = (ctypes.c_int64 * 2)()
+        _lib.check(self.L.rdm_engine_gt_node_correspondences(self._h, T.data_ptr(), float(pos_radius), idx.data_ptr(),
+                                                             ovl.data_ptr(), cap, counts, _lib.stream_ptr()),
+                   'rdm_engine_gt_node_correspondences')
+        c = int(counts[0])
+        return idx[:c], ovl[:c], int(counts[1])
+
     def corr(self):
         """(ref_corr_points, src_corr_points, corr_scores) of the last run as fresh tensors."""
         n = self.result.n_correspondences

@@ -6,6 +6,7 @@ Host-side numpy, as in the reference (these run once per pair on a few hundred c
     `{seq}_{src}_{ref}.npz` per pair);
   * `compute_registration_error` & co: geotransformer/utils/registration.py:17-108;
   * `evaluate_correspondences`, `evaluate_sparse_correspondences`: registration.py:175-200, 354-402;
+  * `evaluate_coarse`: the per-pair PIR of test.py (experiments/loss.py:347-365);
   * `Summary`: the meters and report lines of experiments/eval.py:36-286 (method 'lgr' and 'svd').
 """
 import math
@@ -47,6 +48,21 @@ def save_pair_npz(output_dir, data_dict, output_dict, estimated_transform_ransac
     if 'transform' in data_dict:
         arrays['transform'] = host(data_dict['transform'])
     arrays.update(extra or {})
+    name = osp.join(output_dir, npz_file_name(data_dict['seq_id'], data_dict['src_frame'], data_dict['ref_frame']))
+    np.savez_compressed(name, **arrays)
+    return name
+
+
+# test.py:80-90: what the evaluation run stores per pair and eval.py:100-140 reads back
+TEST_NPZ_KEYS = NPZ_KEYS[:12] + ('corr_scores', 'gt_node_corr_indices', 'gt_node_corr_overlaps', 'estimated_transform')
+
+
+def save_pair_test_npz(output_dir, data_dict, output_dict):
+    """test.py:80-90: the .npz of the evaluation run, exactly its keys -- TEST_NPZ_KEYS plus the pair's `transform`."""
+    def host(v):
+        return v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)
+    arrays = {k: host(output_dict[k]) for k in TEST_NPZ_KEYS}
+    arrays['transform'] = host(data_dict['transform'])
     name = osp.join(output_dir, npz_file_name(data_dict['seq_id'], data_dict['src_frame'], data_dict['ref_frame']))
     np.savez_compressed(name, **arrays)
     return name
@@ -140,6 +156,23 @@ def evaluate_sparse_correspondences(ref_points, src_points, ref_corr_indices, sr
     ref_hit = np.any(pos, axis=1).sum() / (np.any(gt, axis=1).sum() + 1e-12)
     src_hit = np.any(pos, axis=0).sum() / (np.any(gt, axis=0).sum() + 1e-12)
     return {'precision': precision, 'recall': recall, 'hit_ratio': 0.5 * (ref_hit + src_hit)}
+
+
+def evaluate_coarse(output_dict, acceptance_overlap=0.0):
+    """Evaluator.evaluate_coarse (experiments/loss.py:347-365): the PIR test.py logs per pair -- the fraction of the predicted
+    superpoint pairs (ref/src_node_corr_indices) that are ground-truth pairs with overlap > acceptance_overlap
+    (cfg.eval.acceptance_overlap, 0.0, experiments/config.py:62).  output_dict needs ref_points_c, src_points_c,
+    ref/src_node_corr_indices and gt_node_corr_indices / gt_node_corr_overlaps; tensors or arrays.  The map and the mean are
+    fp32 as in the reference (exact: a mean of at most 2^24 zeros and ones)."""
+    def host(v):
+        return v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)
+    m, n = host(output_dict['ref_points_c']).shape[0], host(output_dict['src_points_c']).shape[0]
+    keep = host(output_dict['gt_node_corr_overlaps']) > acceptance_overlap
+    gt = host(output_dict['gt_node_corr_indices']).reshape(-1, 2)[keep]
+    gt_map = np.zeros((m, n), np.float32)
+    gt_map[gt[:, 0], gt[:, 1]] = 1.0
+    hits = gt_map[host(output_dict['ref_node_corr_indices']), host(output_dict['src_node_corr_indices'])]
+    return float(np.float32(hits.sum(dtype=np.float64)) / np.float32(hits.size)) if hits.size else float('nan')
 
 
 class Summary:

@@ -4,12 +4,16 @@ registration report, on the native engine.
     python -m rdmnet_amd.infer --infer-root /path/to/assets/pc --out out/           # the two bundled pairs
     python -m rdmnet_amd.infer --dataset-root /data/kitti --subset test --out out/ --weights rdmnet.pth.tar
     python -m rdmnet_amd.infer --synthetic 512 --no-npz                              # throughput on synthetic KITTI-shaped pairs
+    python -m rdmnet_amd.infer --dataset-root /data/kitti --gt-nodes --out out/      # test.py's evaluation run (eval.py reads out/)
     python -m torch.distributed.run --nproc-per-node 8 -m rdmnet_amd.infer ...       # pairs sharded over ranks
 
 Per pair it writes what the reference writes: one line in `<seq>_pose` and one `<seq>_<src>_<ref>.npz`
 (evaluation.save_pair_npz).  With ground truth in the loader it also prints eval.py's report lines.
 Multi-GPU: rank r takes pairs r, r+W, ... (sharding.pairs_for_rank); the only collective is the final
 gather of the per-pair records.  `--dataset mulran` switches the vote layer off as infer.py:119-120 does.
+`--gt-nodes` turns the run into test.py's (eval.sh -> experiments/test.py, the model of experiments/model.py): for every pair
+with a ground-truth `transform` the ground-truth superpoint correspondences (model.py:283-297) are computed on the GPU from
+the engine's resident tensors, the Coarse Matching meters become real, and the .npz holds exactly test.py:80-90's keys.
 """
 import argparse
 import os
@@ -37,11 +41,16 @@ class Tester:
     records, pose lines and the report come out in dataset order whatever the completion order."""
 
     def __init__(self, cfg, state, output_dir=None, save_npz=True, ransac=True, write_poses=True,
-                 pairs_in_flight=DEFAULT_PAIRS_IN_FLIGHT, wait_us=None, lockstep=None):
+                 pairs_in_flight=DEFAULT_PAIRS_IN_FLIGHT, wait_us=None, lockstep=None, gt_nodes=False):
         self.cfg, self.output_dir, self.save_npz, self.ransac = cfg, output_dir, save_npz, ransac
         self.write_poses = write_poses  # False under several ranks: rank 0 writes all poses, in pair order, at the end
+        # gt_nodes: test.py's run -- ground-truth superpoint correspondences per pair with a transform (model.py:283-297, radius
+        # cfg.model.ground_truth_matching_radius, 0.6 when absent), the coarse meters, test.py:80-90's .npz
+        self.gt_nodes = bool(gt_nodes)
+        radius = getattr(getattr(cfg, 'model', None), 'ground_truth_matching_radius', None)
+        self.gt_radius = 0.6 if radius is None else float(radius)
         self.pipeline = PairPipeline(cfg, state, pairs_in_flight=pairs_in_flight, wait_us=wait_us,
-                                     keep_taps=bool(save_npz and output_dir), lockstep=lockstep)
+                                     keep_taps=bool(save_npz and output_dir) or self.gt_nodes, lockstep=lockstep)
         self.engine = self.pipeline.engines[0]  # (the serial entry point `step` runs on this one)
         if output_dir:
             os.makedirs(output_dir, exist_ok=True)
@@ -78,6 +87,17 @@ class Tester:
                'n_corr': int(res.n_correspondences), 'ms': ms, 'transform': T}
         if 'transform' in item:  # what the pair's registration / correspondence numbers need (the engine's buffers are reused)
             rec['_measure'] = (np.asarray(item['transform'], np.float64), T) + eng.host_corr()  # (numpy copies)
+        if self.gt_nodes and 'transform' in item:  # test.py: model.py:283-297 on the engine's resident tensors, this stream
+            gt_idx, gt_ovl, _ = eng.gt_node_correspondences(np.asarray(item['transform'], np.float32), self.gt_radius)
+            m_r = int(res.n_ref_nodes)
+            t = eng.tensors(['nodes', 'ref_node_corr_indices', 'src_node_corr_indices'])  # (one batched copy)
+            nodes, r_sel, s_sel = (t[k].cpu().numpy() for k in ('nodes', 'ref_node_corr_indices', 'src_node_corr_indices'))
+            rec['_nodes'] = (nodes[:m_r], nodes[m_r:], r_sel[:, 0], s_sel[:, 0], gt_idx.cpu().numpy())
+            if self.output_dir and self.save_npz:
+                od = self.output_dict(eng, item['ref_points'].shape[0])
+                od.update(gt_node_corr_indices=gt_idx, gt_node_corr_overlaps=gt_ovl)
+                evaluation.save_pair_test_npz(self.output_dir, item, od)
+            return rec
         if self.output_dir and self.save_npz:
             od = self.output_dict(eng, item['ref_points'].shape[0])
             T_ransac = None
@@ -92,8 +112,10 @@ class Tester:
         if self.output_dir and self.write_poses:
             evaluation.append_pose(self.output_dir, rec, rec['transform'])
         args = rec.pop('_measure', None)
+        nodes = rec.pop('_nodes', None)
         if args is not None:  # 0.3 ms of host work per pair: here it does not keep a worker's stream idle
-            rec.update(self.summary.commit((rec['seq_id'], rec['src_frame'], rec['ref_frame']), self.summary.measure(*args)))
+            rec.update(self.summary.commit((rec['seq_id'], rec['src_frame'], rec['ref_frame']),
+                                           self.summary.measure(*args, nodes=nodes)))
         self.records.append(rec)
         return rec
 
@@ -140,6 +162,9 @@ def main(argv=None):
                          'rdmnet_amd.pipeline.DEFAULT_LOCKSTEP with two or more pairs in flight and no .npz outputs; 1 = one pair per engine call)')
     ap.add_argument('--no-ransac', action='store_true', help='skip the RANSAC estimate stored beside the LGR pose in the .npz')
     ap.add_argument('--quiet', action='store_true', help='no per-pair log line (the reference prints one per iteration, infer.py:62-66)')
+    ap.add_argument('--gt-nodes', action='store_true',
+                    help="test.py's evaluation run: ground-truth superpoint correspondences on the GPU for every pair with a transform "
+                         "(experiments/model.py:283-297), real Coarse Matching meters, .npz files with test.py's keys (eval.py reads them)")
     args = ap.parse_args(argv)
 
     rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
@@ -179,7 +204,7 @@ def main(argv=None):
         print(f'Data loader created: {time.time() - t0:.3f}s collapsed.')
         print(f'Calibrate neighbors: {cfg.neighbor_limits}.')
     tester = Tester(cfg, load_state(args.weights, cfg), args.out, save_npz=not args.no_npz, ransac=not args.no_ransac,
-                    write_poses=world == 1, pairs_in_flight=args.pairs_in_flight, lockstep=args.lockstep)
+                    write_poses=world == 1, pairs_in_flight=args.pairs_in_flight, lockstep=args.lockstep, gt_nodes=args.gt_nodes)
     mine = sharding.pairs_for_rank(len(data), rank, world)
     # scans are read and staged (pinned host -> HBM on a side stream) two pairs ahead of every in-flight pair
     stager = ds_mod.PairStager(data, mine, depth=2 * args.pairs_in_flight, workers=max(2, args.pairs_in_flight))
@@ -210,7 +235,7 @@ def main(argv=None):
             print('  Registration (all ranks), RR: {:.4f}, RRE: {:.3f}, RTE: {:.3f}'.format(
                 ok.mean(), allrec[ok, 5].mean() if ok.any() else 0.0, allrec[ok, 6].mean() if ok.any() else 0.0))
             if world == 1:  # correspondence-level meters (PIR / IR / FMR) are accumulated per rank only
-                for line in tester.summary.lines()[1:]:
+                for line in tester.summary.lines()[0 if args.gt_nodes else 1:]:  # (the coarse meters exist with --gt-nodes)
                     print(line)
     if dist is not None:
         dist.destroy_process_group()

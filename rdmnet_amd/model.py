@@ -586,3 +586,69 @@ class RDMNet(torch.nn.Module):
 def create_model(cfg):
     """experiments/model_infer.py:357-359."""
     return RDMNet(cfg)
+
+
+class RDMNetEval(RDMNet):
+    """experiments/model.py (the model test.py runs, eval.sh -> test.py -> eval.py): the inference forward of RDMNet plus the
+    ground-truth superpoint correspondences of model.py:283-297 -- get_node_correspondences (geotransformer/modules/
+    registration/matching.py:252-350) on the pair's superpoints, patches and `data_dict['transform']`, radius
+    cfg.model.ground_truth_matching_radius (experiments/config.py:101; 0.6 when the key is absent).  Same parameters and
+    state dict as RDMNet.  The stage runs on the engine's resident tensors (rdm_engine_gt_node_correspondences); with a `taps`
+    dictionary, on the per-op mirror's grouping.  A list of data_dicts runs the forward as one lock-step group, then the stage
+    once per pair (on each pair's engine; not as one grouped launch)."""
+
+    def __init__(self, cfg, device=None):
+        super().__init__(cfg, device)
+        radius = getattr(getattr(cfg, 'model', None), 'ground_truth_matching_radius', None)
+        self.matching_radius = 0.6 if radius is None else float(radius)
+
+    @staticmethod
+    def _check_eval(data_dict):
+        if 'transform' not in data_dict:  # model.py:114 reads it unconditionally
+            raise KeyError("transform: the evaluation model (experiments/model.py:114) needs data_dict['transform']")
+        if not data_dict.get('testing', True):
+            raise NotImplementedError("testing=False builds the training outputs of experiments/model.py -- 'mask' "
+                                      "(get_node_correspondences_disance, model.py:184) and the training n2n scores -- "
+                                      'which are not implemented')
+
+    def _transform(self, data_dict):
+        return torch.as_tensor(data_dict['transform'], dtype=torch.float32).to(self.device).contiguous()
+
+    @torch.no_grad()
+    def forward(self, data_dict, taps=None):
+        group = isinstance(data_dict, (list, tuple))
+        dicts = list(data_dict) if group else [data_dict]
+        for d in dicts:
+            self._check_eval(d)
+        if taps is not None or not self.fast_path:
+            outs = []
+            for d in dicts:
+                t = taps if taps is not None else {}
+                out = self._forward_per_op(d, t)
+                idx, ovl, _ = ops.gt_node_correspondences_indexed(
+                    out['ref_points_c'], out['src_points_c'], out['ref_points_f'], t['ref_knn'], out['src_points_f'], t['src_knn'],
+                    self._transform(d), self.matching_radius, t['ref_node_masks'], t['src_node_masks'], t['ref_knn_masks'],
+                    t['src_knn_masks'])
+                out.update(gt_node_corr_indices=idx, gt_node_corr_overlaps=ovl)
+                outs.append(out)
+            return outs if group else outs[0]
+        if group and len(dicts) > 1:
+            from . import engine as engine_mod
+            if len(dicts) > 8:
+                raise ValueError('a lock-step group carries at most 8 data_dicts')
+            engines = self._engine_group(len(dicts))
+            results = engine_mod.Engine.forward_lockstep(engines, dicts)
+            outs = [self._output_dict(e, r, d) for e, r, d in zip(engines, results, dicts)]
+        else:
+            engines = [self._engine()]
+            outs = [self._output_dict(engines[0], engines[0].forward(dicts[0]), dicts[0])]
+        for e, out, d in zip(engines, outs, dicts):
+            idx, ovl, _ = e.gt_node_correspondences(self._transform(d), self.matching_radius)
+            out.update(gt_node_corr_indices=idx, gt_node_corr_overlaps=ovl)
+        return outs if group else outs[0]
+
+
+def create_eval_model(cfg):
+    """experiments/model.py:389-391 (test.py's model): create_model's network plus gt_node_corr_indices /
+    gt_node_corr_overlaps in the output_dict."""
+    return RDMNetEval(cfg)

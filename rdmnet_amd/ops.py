@@ -549,3 +549,93 @@ def ransac_correspondences(src_corr, ref_corr, distance_threshold=0.3, ransac_n=
                                             _lib.ptr(hyp), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
                'rdm_ransac_correspondences')
     return (T, stats, rmse, hyp) if return_hypotheses else (T, stats, rmse)
+
+
+def _gt_check(t, name, shape, dtype, device):
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError(f'gt_node_correspondences: {name} must be a tensor')
+    if t.device != device:
+        raise RuntimeError(f'gt_node_correspondences: {name} is on {t.device}, expected {device}')
+    if t.dtype != dtype:
+        raise RuntimeError(f'gt_node_correspondences: {name} has dtype {t.dtype}, expected {dtype}')
+    if tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f'gt_node_correspondences: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}')
+    return t.contiguous()
+
+
+def _gt_mask(t, name, shape, device):
+    if t is None:
+        return None
+    if isinstance(t, torch.Tensor) and t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    return _gt_check(t, name, shape, torch.uint8, device)
+
+
+def _gt_call(ref_nodes, src_nodes, ref_pts, ref_idx, src_pts, src_idx, k, transform, pos_radius, masks):
+    L = _lib.lib()
+    dev, m, n = ref_nodes.device, ref_nodes.shape[0], src_nodes.shape[0]
+    cap = m * n  # the worst case B = M*N
+    idx = torch.empty((cap, 2), dtype=torch.int64, device=dev)
+    ovl = torch.empty((cap,), dtype=torch.float32, device=dev)
+    flags = torch.zeros((3,), dtype=torch.int32, device=dev)  # counts {C, B}, status
+    ws = scratch(dev, L.rdm_gt_node_correspondences_workspace_bytes(m, n))
+    _lib.check(L.rdm_gt_node_correspondences(ref_nodes.data_ptr(), m, src_nodes.data_ptr(), n, ref_pts.data_ptr(), _lib.ptr(ref_idx),
+                                             0 if ref_idx is None else ref_pts.shape[0], src_pts.data_ptr(), _lib.ptr(src_idx),
+                                             0 if src_idx is None else src_pts.shape[0], k, *[_lib.ptr(t) for t in masks],
+                                             transform.data_ptr(), float(pos_radius), idx.data_ptr(), ovl.data_ptr(), cap,
+                                             flags.data_ptr(), flags[2:].data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+               'rdm_gt_node_correspondences')
+    c, b, status = (int(v) for v in flags.cpu())
+    if status != 0:  # (cannot happen with capacity M*N)
+        raise RuntimeError('rdm_gt_node_correspondences: output capacity exceeded')
+    return idx[:c], ovl[:c], b
+
+
+def _gt_inputs(ref_nodes, src_nodes, transform):
+    if not isinstance(ref_nodes, torch.Tensor) or ref_nodes.device.type != 'cuda':
+        raise RuntimeError('gt_node_correspondences: ref_nodes must be a CUDA tensor')
+    dev = ref_nodes.device
+    m = ref_nodes.shape[0] if ref_nodes.dim() == 2 else -1
+    n = src_nodes.shape[0] if isinstance(src_nodes, torch.Tensor) and src_nodes.dim() == 2 else -1
+    if m <= 0 or n <= 0:
+        raise RuntimeError(f'gt_node_correspondences: bad node shapes {tuple(ref_nodes.shape)} / {tuple(src_nodes.shape)}')
+    return (dev, m, n, _gt_check(ref_nodes, 'ref_nodes', (m, 3), torch.float32, dev),
+            _gt_check(src_nodes, 'src_nodes', (n, 3), torch.float32, dev), _gt_check(transform, 'transform', (4, 4), torch.float32, dev))
+
+
+def gt_node_correspondences(ref_nodes, src_nodes, ref_knn_points, src_knn_points, transform, pos_radius, ref_masks=None,
+                            src_masks=None, ref_knn_masks=None, src_knn_masks=None):
+    """get_node_correspondences (geotransformer/modules/registration/matching.py:252-350) on device tensors:
+    nodes f32 [M,3] / [N,3], gathered patch points f32 [M,K,3] / [N,K,3] (K <= 128), transform f32 [4,4] (src -> ref),
+    masks bool / u8 or None (= all valid) -> (corr_indices i64 [C,2], corr_overlaps f32 [C]), the candidates with overlap > 0
+    in (ref, src) order.  Synchronises the stream once (C is data dependent)."""
+    dev, m, n, ref_nodes, src_nodes, transform = _gt_inputs(ref_nodes, src_nodes, transform)
+    k = ref_knn_points.shape[1] if isinstance(ref_knn_points, torch.Tensor) and ref_knn_points.dim() == 3 else -1
+    if not 0 < k <= 128:
+        raise RuntimeError(f'gt_node_correspondences: ref_knn_points must be [M, K, 3] with 0 < K <= 128')
+    ref_knn_points = _gt_check(ref_knn_points, 'ref_knn_points', (m, k, 3), torch.float32, dev)
+    src_knn_points = _gt_check(src_knn_points, 'src_knn_points', (n, k, 3), torch.float32, dev)
+    masks = [_gt_mask(ref_masks, 'ref_masks', (m,), dev), _gt_mask(src_masks, 'src_masks', (n,), dev),
+             _gt_mask(ref_knn_masks, 'ref_knn_masks', (m, k), dev), _gt_mask(src_knn_masks, 'src_knn_masks', (n, k), dev)]
+    idx, ovl, _ = _gt_call(ref_nodes, src_nodes, ref_knn_points, None, src_knn_points, None, k, transform, pos_radius, masks)
+    return idx, ovl
+
+
+def gt_node_correspondences_indexed(ref_nodes, src_nodes, ref_points, ref_knn_indices, src_points, src_knn_indices, transform,
+                                    pos_radius, ref_masks=None, src_masks=None, ref_knn_masks=None, src_knn_masks=None):
+    """gt_node_correspondences with the patches as point_to_node writes them: fine points f32 [n_r,3] / [n_s,3] and int64 slot
+    indices [M,K] / [N,K] into them (an index outside [0, n) is the zero pad row, model.py:268-273) -> (corr_indices,
+    corr_overlaps, B) with B the number of candidate patch pairs that passed the enclosing-sphere test."""
+    dev, m, n, ref_nodes, src_nodes, transform = _gt_inputs(ref_nodes, src_nodes, transform)
+    k = ref_knn_indices.shape[1] if isinstance(ref_knn_indices, torch.Tensor) and ref_knn_indices.dim() == 2 else -1
+    if not 0 < k <= 128:
+        raise RuntimeError(f'gt_node_correspondences: ref_knn_indices must be [M, K] with 0 < K <= 128')
+    ref_points = _gt_check(ref_points, 'ref_points', (ref_points.shape[0], 3), torch.float32, dev)
+    src_points = _gt_check(src_points, 'src_points', (src_points.shape[0], 3), torch.float32, dev)
+    if ref_points.shape[0] == 0 or src_points.shape[0] == 0:
+        raise RuntimeError('gt_node_correspondences: empty cloud')
+    ref_knn_indices = _gt_check(ref_knn_indices, 'ref_knn_indices', (m, k), torch.int64, dev)
+    src_knn_indices = _gt_check(src_knn_indices, 'src_knn_indices', (n, k), torch.int64, dev)
+    masks = [_gt_mask(ref_masks, 'ref_masks', (m,), dev), _gt_mask(src_masks, 'src_masks', (n,), dev),
+             _gt_mask(ref_knn_masks, 'ref_knn_masks', (m, k), dev), _gt_mask(src_knn_masks, 'src_knn_masks', (n, k), dev)]
+    return _gt_call(ref_nodes, src_nodes, ref_points, ref_knn_indices, src_points, src_knn_indices, k, transform, pos_radius, masks)
