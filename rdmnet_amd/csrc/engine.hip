@@ -198,15 +198,34 @@ void tap(Run& r, const char* name, const void* p, int64_t rows, int64_t cols, in
 }
 void tap(Run& r, const char* name, const Mat& m) { tap(r, name, m.p, m.rows, m.cols, m.ld, 0); }
 
+// a prepared Linear / KPConv weight; null (the error text set) when the checkpoint has none
+const Linear* lin_param(Run& r, const std::string& name) {
+  auto it = r.e->params->lin.find(name);
+  if (it != r.e->params->lin.end()) return &it->second;
+  set_error("rdm_engine: missing parameter %s", name.c_str());
+  return nullptr;
+}
+
+float* vecp(Run& r, const std::string& name) {
+  auto it = r.e->params->vec.find(name);
+  return it == r.e->params->vec.end() ? nullptr : it->second;
+}
+
+// the affine parameters <prefix>.weight, <prefix>.bias of a normalisation
+int norm_params(Run& r, const std::string& prefix, float** g, float** b) {
+  *g = vecp(r, prefix + ".weight");
+  *b = vecp(r, prefix + ".bias");
+  if (*g && *b) return RDM_OK;
+  set_error("rdm_engine: missing parameter %s.*", prefix.c_str());
+  return RDM_ERR_ARG;
+}
+
 int linear(Run& r, const std::string& name, const Mat& x, Mat& y, int act = 0, bool alloc_out = true) {
   lockstep_align();  // (lockstep.h: the pairs of a lock-step group start every layer together)
   rdm_engine* e = r.e;
-  auto it = e->params->lin.find(name);
-  if (it == e->params->lin.end()) {
-    set_error("rdm_engine: missing parameter %s", name.c_str());
-    return RDM_ERR_ARG;
-  }
-  const Linear& L = it->second;
+  const Linear* Lp = lin_param(r, name);
+  if (!Lp) return RDM_ERR_ARG;
+  const Linear& L = *Lp;
   if (alloc_out) {
     y = e->mat(x.rows, L.out);
     ENG_ALLOC(y.p);
@@ -219,12 +238,10 @@ int linear(Run& r, const std::string& name, const Mat& x, Mat& y, int act = 0, b
 int linear_pair(Run& r, const std::string& name0, const Mat& x0, Mat& y0, const std::string& name1, const Mat& x1, Mat& y1) {
   lockstep_align();  // (lockstep.h: the pairs of a lock-step group start every layer together)
   rdm_engine* e = r.e;
-  auto i0 = e->params->lin.find(name0), i1 = e->params->lin.find(name1);
-  if (i0 == e->params->lin.end() || i1 == e->params->lin.end()) {
-    set_error("rdm_engine: missing parameter %s", (i0 == e->params->lin.end() ? name0 : name1).c_str());
-    return RDM_ERR_ARG;
-  }
-  const Linear &L0 = i0->second, &L1 = i1->second;
+  const Linear* P0 = lin_param(r, name0);
+  const Linear* P1 = P0 ? lin_param(r, name1) : nullptr;
+  if (!P0 || !P1) return RDM_ERR_ARG;
+  const Linear &L0 = *P0, &L1 = *P1;
   y0 = e->mat(x0.rows, L0.out);
   y1 = e->mat(x1.rows, L1.out);
   ENG_ALLOC(y0.p); ENG_ALLOC(y1.p);
@@ -232,22 +249,13 @@ int linear_pair(Run& r, const std::string& name0, const Mat& x0, Mat& y0, const 
                    y1.ld, x1.rows, L1.out, L1.kpad, L1.bias, r.ws, r.ws_bytes, r.st);
 }
 
-float* vecp(Run& r, const std::string& name) {
-  auto it = r.e->params->vec.find(name);
-  return it == r.e->params->vec.end() ? nullptr : it->second;
-}
-
 int group_norm(Run& r, const std::string& name, const Mat& x, Mat& y, int act, const Mat* res, uint8_t* positive) {
   lockstep_align();  // (lockstep.h: the pairs of a lock-step group start every layer together)
   rdm_engine* e = r.e;
   y = e->mat(x.rows, x.cols);
   ENG_ALLOC(y.p);
-  float* g = vecp(r, name + ".norm.weight");
-  float* b = vecp(r, name + ".norm.bias");
-  if (!g || !b) {
-    set_error("rdm_engine: missing parameter %s.norm.*", name.c_str());
-    return RDM_ERR_ARG;
-  }
+  float *g, *b;
+  ENG_CHECK(norm_params(r, name + ".norm", &g, &b));
   return rdm_group_norm(x.p, x.rows, x.cols, x.ld, r.groups, g, b, 1e-5f, res ? res->p : nullptr, res ? res->ld : 0, act,
                         y.p, y.ld, positive, r.ws, r.ws_bytes, r.st);
 }
@@ -256,21 +264,14 @@ int group_norm(Run& r, const std::string& name, const Mat& x, Mat& y, int act, c
 int unary(Run& r, const std::string& name, const Mat& x, Mat& y, int act, const Mat* res, uint8_t* positive) {
   lockstep_align();  // (lockstep.h: the pairs of a lock-step group start every layer together)
   rdm_engine* e = r.e;
-  auto it = e->params->lin.find(name + ".mlp");
-  if (it == e->params->lin.end()) {
-    set_error("rdm_engine: missing parameter %s.mlp", name.c_str());
-    return RDM_ERR_ARG;
-  }
-  const Linear& L = it->second;
+  const Linear* Lp = lin_param(r, name + ".mlp");
+  if (!Lp) return RDM_ERR_ARG;
+  const Linear& L = *Lp;
   Mat t = e->mat(x.rows, L.out);
   y = e->mat(x.rows, L.out);
   ENG_ALLOC(t.p); ENG_ALLOC(y.p);
-  float* g = vecp(r, name + ".norm.norm.weight");
-  float* b = vecp(r, name + ".norm.norm.bias");
-  if (!g || !b) {
-    set_error("rdm_engine: missing parameter %s.norm.norm.*", name.c_str());
-    return RDM_ERR_ARG;
-  }
+  float *g, *b;
+  ENG_CHECK(norm_params(r, name + ".norm.norm", &g, &b));
   return rdm_linear_group_norm(x.p, x.ld, L.b, L.ldb, L.bias, nullptr, x.rows, L.out, L.kpad, r.groups, g, b, 1e-5f,
                                res ? res->p : nullptr, res ? res->ld : 0, act, t.p, t.ld, y.p, y.ld, positive, r.ws,
                                r.ws_bytes, r.st);
@@ -283,12 +284,9 @@ int decoder_stage(Run& r, const std::string& lin_name, const std::string* norm_n
                   int64_t up_ld, const Mat& skip, int64_t m, Mat& y) {
   lockstep_align();  // (lockstep.h: the pairs of a lock-step group start every layer together)
   rdm_engine* e = r.e;
-  auto it = e->params->lin.find(lin_name);
-  if (it == e->params->lin.end()) {
-    set_error("rdm_engine: missing parameter %s", lin_name.c_str());
-    return RDM_ERR_ARG;
-  }
-  const Linear& L = it->second;
+  const Linear* Lp = lin_param(r, lin_name);
+  if (!Lp) return RDM_ERR_ARG;
+  const Linear& L = *Lp;
   RDM_REQUIRE(coarse.cols + skip.cols == L.in, "rdm_engine: %s expects %lld input columns", lin_name.c_str(), (long long)L.in);
   Mat t = e->mat(m, L.out);
   ENG_ALLOC(t.p);
@@ -296,12 +294,7 @@ int decoder_stage(Run& r, const std::string& lin_name, const std::string* norm_n
   if (norm_name) {
     y = e->mat(m, L.out);
     ENG_ALLOC(y.p);
-    g = vecp(r, *norm_name + ".weight");
-    b = vecp(r, *norm_name + ".bias");
-    if (!g || !b) {
-      set_error("rdm_engine: missing parameter %s.*", norm_name->c_str());
-      return RDM_ERR_ARG;
-    }
+    ENG_CHECK(norm_params(r, *norm_name, &g, &b));
   } else {
     y = t;
   }
@@ -347,28 +340,31 @@ int kpconv(Run& r, const std::string& name, const Mat& x, const uint8_t* x_pos, 
            const Mat* pool_src = nullptr, Mat* pool_out = nullptr) {
   lockstep_align();  // (lockstep.h: the pairs of a lock-step group start every layer together)
   rdm_engine* e = r.e;
-  auto it = e->params->lin.find(name + ".weights");
-  if (it == e->params->lin.end()) {
-    set_error("rdm_engine: missing parameter %s.weights", name.c_str());
-    return RDM_ERR_ARG;
-  }
-  const Linear& W = it->second;
+  const Linear* Wp = lin_param(r, name + ".weights");
+  if (!Wp) return RDM_ERR_ARG;
+  const Linear& W = *Wp;
   const int64_t cin = x.cols, kdim = cin == 1 ? 16 : 15 * cin;
   const int i32 = t.i32 ? 1 : 0;  // the convolution kernels and the shortcut pool read `t` in its own element width
+  const int li = e->prof_layers;
+  const bool prof = e->profile && (e->profile_shapes_only ? li < 16 : 3 * li + 2 < static_cast<int>(e->events.size()));
+  auto end_profile = [&](int fused) -> int {  // the layer's last event and its record
+    ENG_CHECK(layer_event(e, 3 * li + 2, r.st));
+    rdm_kpconv_profile p;
+    p.m = q.n; p.h = t.width; p.c_in = cin; p.c_out = W.out; p.pooled_channels = pool_src ? pool_src->cols : 0;
+    p.gather_ms = p.total_ms = 0.f;
+    p.fused = fused; p.reserved = 0;
+    e->prof.push_back(p);
+    e->prof_layers++;
+    return RDM_OK;
+  };
   if (W.packed && rdm_kpconv_fused_enabled()) {
     // fine levels (c_in = 1, 32, 64): the whole convolution is one kernel, the [M, 15 C] block never leaves the CU
-    float* gam = vecp(r, norm_name + ".norm.weight");
-    float* bet = vecp(r, norm_name + ".norm.bias");
-    if (!gam || !bet) {
-      set_error("rdm_engine: missing parameter %s.norm.*", norm_name.c_str());
-      return RDM_ERR_ARG;
-    }
+    float *gam, *bet;
+    ENG_CHECK(norm_params(r, norm_name + ".norm", &gam, &bet));
     Mat conv = e->mat(q.n, W.out);
     y = e->mat(q.n, W.out);
     ENG_ALLOC(conv.p); ENG_ALLOC(y.p);
     RDM_REQUIRE(rdm_kpconv_fused_workspace_bytes(q.n, cin, W.out) <= r.ws_bytes, "rdm_engine: scratch too small");
-    const int li = e->prof_layers;
-    const bool prof = e->profile && (e->profile_shapes_only ? li < 16 : 3 * li + 2 < static_cast<int>(e->events.size()));
     if (prof) ENG_CHECK(layer_event(e, 3 * li, r.st));
     // (rdm_kpconv_fused_group_norm's two halves, so that the layer events bracket the convolution kernel alone)
     const int nblk = static_cast<int>(rdm_kpconv_fused_partial_rows(q.n, cin));
@@ -386,24 +382,13 @@ int kpconv(Run& r, const std::string& name, const Mat& x, const uint8_t* x_pos, 
       ENG_CHECK(gather_max_ordered(pool_src->p, pool_src->rows, pool_src->cols, pool_src->ld, t.idx, q.n, t.width, t.stride(),
                                    t.flags, pool_out->p, pool_out->ld, order, i32, r.st));
     }
-    if (prof) {
-      ENG_CHECK(layer_event(e, 3 * li + 2, r.st));
-      rdm_kpconv_profile p;
-      p.m = q.n; p.h = t.width; p.c_in = cin; p.c_out = W.out; p.pooled_channels = pool_src ? pool_src->cols : 0;
-      p.gather_ms = p.total_ms = 0.f;
-      p.fused = 1; p.reserved = 0;
-      e->prof.push_back(p);
-      e->prof_layers++;
-    }
-    (void)order;
+    if (prof) ENG_CHECK(end_profile(1));
     return RDM_OK;
   }
   Mat wf = e->mat(q.n, kdim);
   ENG_ALLOC(wf.p);
   float* nn = e->alloc<float>(q.n > 0 ? q.n : 1);
   ENG_ALLOC(nn);
-  const int li = e->prof_layers;
-  const bool prof = e->profile && (e->profile_shapes_only ? li < 16 : 3 * li + 2 < static_cast<int>(e->events.size()));
   if (prof) ENG_CHECK(layer_event(e, 3 * li, r.st));
   ENG_CHECK(kpconv_gather_impl(q.pts, q.n, s.pts, s.n, x.p, cin, x.ld, x_pos, t.idx, t.width, t.stride(), t.flags,
                                vecp(r, name + ".kernel_points"), sigma, wf.p, wf.ld, nn, order, i32, r.st));
@@ -424,24 +409,12 @@ int kpconv(Run& r, const std::string& name, const Mat& x, const uint8_t* x_pos, 
     ENG_CHECK(gather_max_ordered(pool_src->p, pool_src->rows, pool_src->cols, pool_src->ld, t.idx, q.n, t.width, t.stride(),
                                    t.flags, pool_out->p, pool_out->ld, order, i32, r.st));
   }
-  if (prof) {
-    ENG_CHECK(layer_event(e, 3 * li + 2, r.st));
-    rdm_kpconv_profile p;
-    p.m = q.n; p.h = t.width; p.c_in = cin; p.c_out = W.out; p.pooled_channels = pool_src ? pool_src->cols : 0;
-    p.gather_ms = p.total_ms = 0.f;
-    p.fused = 0; p.reserved = 0;
-    e->prof.push_back(p);
-    e->prof_layers++;
-  }
+  if (prof) ENG_CHECK(end_profile(0));
   // GroupNorm + LeakyReLU of the convolution output (modules.py:141-145, 205-207)
   y = e->mat(q.n, W.out);
   ENG_ALLOC(y.p);
-  float* gam = vecp(r, norm_name + ".norm.weight");
-  float* bet = vecp(r, norm_name + ".norm.bias");
-  if (!gam || !bet) {
-    set_error("rdm_engine: missing parameter %s.norm.*", norm_name.c_str());
-    return RDM_ERR_ARG;
-  }
+  float *gam, *bet;
+  ENG_CHECK(norm_params(r, norm_name + ".norm", &gam, &bet));
   return group_norm_finish(gn_partial, gn_blocks, conv.p, q.n, W.out, conv.ld, r.groups, gam, bet, 1e-5f, nullptr, 0, 2, y.p,
                            y.ld, nullptr, static_cast<char*>(r.ws) + gemm_ws + stat_bytes, r.ws_bytes - gemm_ws - stat_bytes,
                            r.st);
@@ -454,12 +427,9 @@ int kpconv(Run& r, const std::string& name, const Mat& x, const uint8_t* x_pos, 
 int linear_ln(Run& r, const std::string& lin, const std::string& norm, const Mat& x, const Mat& res, Mat& y, bool alloc_out) {
   lockstep_align();  // (lockstep.h: the pairs of a lock-step group start every layer together)
   rdm_engine* e = r.e;
-  auto it = e->params->lin.find(lin);
-  if (it == e->params->lin.end()) {
-    set_error("rdm_engine: missing parameter %s", lin.c_str());
-    return RDM_ERR_ARG;
-  }
-  const Linear& L = it->second;
+  const Linear* Lp = lin_param(r, lin);
+  if (!Lp) return RDM_ERR_ARG;
+  const Linear& L = *Lp;
   if (L.wt && L.out == 128) {
     if (alloc_out) {
       y = e->mat(x.rows, L.out);
@@ -645,11 +615,7 @@ int launch1d(const char* what, int64_t n, hipStream_t st, A... args) {
 
 // Wait for the engine's stream at a size read-back.  The runtime's synchronize busy-waits: with several pairs in
 // flight per GPU and 8 ranks per node that is 32 spinning cores; hosts with a small CPU quota poll instead.
-int wait_on(rdm_engine* e, hipStream_t st) {
-  if (lockstep_active()) {  // a pair of a lock-step group: parked until every pair of the group waits; the group waits once
-    lockstep_sync();
-    return RDM_OK;
-  }
+int wait_idle(rdm_engine* e, hipStream_t st) {
   if (e->wait_sleep_us <= 0) {
     RDM_HIP_CHECK(hipStreamSynchronize(st));
     return RDM_OK;
@@ -664,6 +630,13 @@ int wait_on(rdm_engine* e, hipStream_t st) {
     timespec ts{0, static_cast<long>(e->wait_sleep_us) * 1000};
     nanosleep(&ts, nullptr);
   }
+}
+int wait_on(rdm_engine* e, hipStream_t st) {
+  if (lockstep_active()) {  // a pair of a lock-step group: parked until every pair of the group waits; the group waits once
+    lockstep_sync();
+    return RDM_OK;
+  }
+  return wait_idle(e, st);
 }
 int wait_stream(Run& r) { return wait_on(r.e, r.st); }
 
@@ -1018,33 +991,148 @@ extern "C" int rdm_engine_get_tensor(rdm_engine* e, const char* name, rdm_tensor
   return RDM_OK;
 }
 
+namespace {
+
+// with three or more pairs sharing the GPU the tiled GEMM keeps two workgroups per CU (gemm.hip: gemm_set_lds_pad)
+struct PadGuard {
+  explicit PadGuard(unsigned b) { rdm::gemm_set_lds_pad(b); }
+  ~PadGuard() { rdm::gemm_set_lds_pad(0); }
+};
+// rdm_engine_collate: the collate alone, its stage tensors kept for this call whatever rdm_engine_keep_taps says (the setting
+// is restored afterwards)
+struct CollateOnly {
+  rdm_engine* e;
+  bool keep_before;
+  explicit CollateOnly(rdm_engine* eng) : e(eng), keep_before(eng->keep_taps) { e->keep_taps = e->collate_only = true; }
+  ~CollateOnly() { e->collate_only = false; e->keep_taps = keep_before; }
+};
+
+// ---------------------------------------------------------------- the pyramid (collate, data.py:13-77)
+// levels whose subsampling runs as the multi-launch pipeline (RDM_GS_MULTI_LEVELS, developer knob; default: the first)
+int gs_multi_levels() {
+  static const int n = [] { const char* v = ::rdm::dev_knob("RDM_GS_MULTI_LEVELS"); return v ? atoi(v) : 1; }();
+  return n;
+}
+
+// Radius searches recorded (radius_grid_query_deferred) and launched together at flush(): two launches for up to 16 searches.
+struct SearchQueue {
+  std::vector<char> buf = std::vector<char>(radius_redo_queue_bytes());
+  int queued = 0;
+  hipStream_t st;
+  explicit SearchQueue(hipStream_t s) : st(s) { radius_redo_queue_reset(buf.data()); }
+  int flush() {
+    queued = 0;
+    return radius_redo_flush(buf.data(), st);
+  }
+};
+
+// The search of level q's points in grid g (at most `limit` neighbours) into a table it allocates (int32 elements when i32),
+// with the redo flags of its second pass; `status` is the search's {max count, status} row.  A full queue (radius_neighbors.hip
+// kRedoMax) is flushed first.
+int search(rdm_engine* e, SearchQueue& sq, const Level& q, const Grid& g, float rad, int limit, bool i32, int32_t* status,
+           Table& t) {
+  if (sq.queued == 16) ENG_CHECK(sq.flush());
+  t.rows = q.n; t.width = limit; t.flags = status;
+  t.i32 = i32;
+  t.idx = reinterpret_cast<int64_t*>(e->alloc<char>(static_cast<size_t>(q.n > 0 ? q.n : 1) * limit * (i32 ? 4 : 8)));
+  ENG_ALLOC(t.idx);
+  unsigned char* redo_flags = e->alloc<unsigned char>(static_cast<size_t>(q.n > 0 ? q.n : 1));
+  ENG_ALLOC(redo_flags);
+  ++sq.queued;
+  return radius_grid_query_deferred(g.ws, g.bytes, g.n_s, q.pts, q.n, q.lengths, 2, rad, limit, t.idx, nullptr, t.flags,
+                                    t.flags + 1, redo_flags, sq.buf.data(), i32 ? 1 : 0, sq.st);
+}
+
+// The searches of a pair's collate, in the order that numbers its status rows (PairPyramid::flags, the "search_flags" stage
+// tensor): per level i the neighbours, the subsampling to level i + 1 and the up-sampling to level i - 1 (radius 2^i r_0).
+// The forward consumes column 0 of upsampling[1..3] only (nearest_upsample, functional.py:6-22) and upsampling[0] not at all
+// (backbone.py:118-151 stops at the second level): a plain run skips that search (32 000 queries, a quarter of all), keeps one
+// column of the others, and keeps the neighbour / subsampling tables, which only its own KPConv layers and shortcut pools read, in
+// 32 bits (33 MB less written and 65 MB less read per pair).  `full` (the collate API, runs that keep their stage tensors):
+// the reference's int64 tables at full width.  (in a plain run up[0] stays the default-constructed Table -- null
+// pointer, zero rows, never read -- and the status rows are numbered without the skipped search: self0 sub0 self1 sub1 self2
+// sub2 up1 ... ; the layout Engine.collate documents (rows 4 / 7 / 10 / 12 = the up-sampling tables) holds for full runs.)
+// nb0_done: the first search already ran (latency mode: on the side stream, as status row 0).
+int search_pyramid(rdm_engine* e, PairPyramid& py, bool full, bool nb0_done, SearchQueue& sq) {
+  const rdm_engine_config& c = e->cfg;
+  auto row = [&py] { return py.flags + 2 * py.calls++; };
+  float radius = c.init_radius;
+  for (int i = 0; i < 5; ++i, radius *= 2.f) {
+    const Level* lv = py.lv;
+    if (!(nb0_done && i == 0)) ENG_CHECK(search(e, sq, lv[i], py.grids[i], radius, c.neighbor_limits[i], !full, row(), py.nb[i]));
+    if (i < 4) ENG_CHECK(search(e, sq, lv[i + 1], py.grids[i], radius, c.neighbor_limits[i], !full, row(), py.sub[i]));
+    if (i > 0 && (full || i > 1))
+      ENG_CHECK(search(e, sq, lv[i - 1], py.grids[i], radius, full ? c.neighbor_limits[i] : 1, false, row(), py.up[i - 1]));
+  }
+  return RDM_OK;
+}
+
+// The level grids [first, last) of n pairs (radius r_i = 2^i r_0), eight (pair, level) items per set of launches: each item is
+// the grid of one pair's level (its own bounding box, two clouds).  They serve the searches of the collate and, through their
+// cell-sorted records, the spatial query order of the KPConv kernels and the shortcut pools.
+int build_level_grids(rdm_engine* e, PairPyramid* pys, int n, int first, int last, hipStream_t st) {
+  const float* gp[8];
+  int64_t gn[8];
+  const int64_t* gl[8];
+  float gr[8];
+  void* gw[8];
+  size_t gb[8];
+  int k = 0;
+  auto launch = [&]() -> int {
+    RDM_DUP_LOOP("rnbuild")
+    ENG_CHECK(radius_grid_build_multi(k, gp, gn, gl, 2, gr, gw, gb, st));
+    k = 0;
+    return RDM_OK;
+  };
+  for (int p = 0; p < n; ++p) {
+    float rad = e->cfg.init_radius;
+    for (int i = 0; i < last; ++i, rad *= 2.f) {
+      if (i < first) continue;
+      const Level& l = pys[p].lv[i];
+      Grid& g = pys[p].grids[i];
+      g.n_s = l.n;
+      g.bytes = rdm_radius_grid_workspace_bytes(l.n);
+      g.ws = e->alloc<char>(g.bytes);
+      ENG_ALLOC(g.ws);
+      gp[k] = l.pts; gn[k] = l.n; gl[k] = l.lengths; gr[k] = rad; gw[k] = g.ws; gb[k] = g.bytes;
+      if (++k == 8) ENG_CHECK(launch());
+    }
+  }
+  return k > 0 ? launch() : RDM_OK;
+}
+
+}  // namespace
+
 static int engine_run_once(rdm_engine* e, const float* ref_points, int64_t n_ref, const float* src_points, int64_t n_src,
                            const rdm_data_dict* dd, rdm_engine_result* res, void* stream, const PairPyramid* pre = nullptr);
 
 // The default 3 GiB arena covers pairs of ~2 x 25 k points; denser input (raw scans, KITTI-360-sized clouds)
 // grows it: on exhaustion the stream is drained, the arena doubled (288 GB of HBM leave room) and the pair
 // re-run.  An arena size chosen by the caller (rdm_engine_config.arena_bytes) is never changed.
+static bool may_grow(const rdm_engine* e, int rc) {
+  return rc == RDM_ERR_WORKSPACE && e->arena_exhausted && !e->arena_fixed && e->arena_cap < (size_t(96) << 30);
+}
+static int grow_arena(rdm_engine* e, void* stream, const char* who) {
+  RDM_HIP_CHECK(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+  RDM_HIP_CHECK(hipFree(e->arena));
+  e->arena = nullptr;
+  e->arena_cap *= 2;
+  const hipError_t err = hipMalloc(reinterpret_cast<void**>(&e->arena), e->arena_cap);
+  if (err != hipSuccess) {
+    e->arena_cap = 0;
+    set_error("%s: growing the activation arena failed: %s", who, hipGetErrorString(err));
+    return RDM_ERR_HIP;
+  }
+  return RDM_OK;
+}
 static int engine_run_growing(rdm_engine* e, const float* ref_points, int64_t n_ref, const float* src_points, int64_t n_src,
                               const rdm_data_dict* dd, rdm_engine_result* res, void* stream) {
-  // with three or more pairs sharing the GPU the tiled GEMM keeps two workgroups per CU (gemm.hip: gemm_set_lds_pad)
-  struct PadGuard {
-    explicit PadGuard(unsigned b) { rdm::gemm_set_lds_pad(b); }
-    ~PadGuard() { rdm::gemm_set_lds_pad(0); }
-  } pad_guard(e->pairs_in_flight >= 3 ? 20480u : 0u);
+  PadGuard pad_guard(e->pairs_in_flight >= 3 ? 20480u : 0u);
   for (;;) {
     e->arena_exhausted = false;
     const int rc = engine_run_once(e, ref_points, n_ref, src_points, n_src, dd, res, stream);
-    if (rc != RDM_ERR_WORKSPACE || !e->arena_exhausted || e->arena_fixed || e->arena_cap >= (size_t(96) << 30)) return rc;
-    RDM_HIP_CHECK(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    RDM_HIP_CHECK(hipFree(e->arena));
-    e->arena = nullptr;
-    e->arena_cap *= 2;
-    const hipError_t err = hipMalloc(reinterpret_cast<void**>(&e->arena), e->arena_cap);
-    if (err != hipSuccess) {
-      e->arena_cap = 0;
-      set_error("rdm_engine_run: growing the activation arena failed: %s", hipGetErrorString(err));
-      return RDM_ERR_HIP;
-    }
+    if (!may_grow(e, rc)) return rc;
+    ENG_CHECK(grow_arena(e, stream, "rdm_engine_run"));
   }
 }
 
@@ -1062,9 +1150,8 @@ extern "C" int rdm_engine_run(rdm_engine* e, const float* ref_points, int64_t n_
 // four pairs in flight it costs 0.25 ms of a pair's 1.9 ms (profiles/r04_marginal_cost.txt), and the batching lab measured the
 // class at 0.43x per pair when four pairs share its launches (profiles/r05_batch_lab.md).  Here
 //   * every subsampling launch works on 2 B clouds (one workgroup per cloud: the latency of a pair's chain now serves B),
-//   * the grids are built as (pair, level) items, eight per set of launches -- each item is exactly the grid of the pair's own
-//     collate (its own bounding box, two clouds), so records and tables come out as in a single-pair run,
-//   * the 12 searches of every pair are recorded into one queue and flushed 16 at a time (two launches per flush),
+//   * the grids are built as (pair, level) items, eight per set of launches (build_level_grids),
+//   * the 12 searches of every pair (search_pyramid, as in a plain run) are recorded into one queue and flushed 16 at a time,
 //   * the level sizes of all pairs return in one read-back.
 // What a pair's forward reads is bit for bit what its own collate would have written (integer tables, the same points, the same
 // cell-sorted records): rdm_engine_forward_batched(k) then equals rdm_engine_run on pair k.
@@ -1100,7 +1187,6 @@ static int collate_batch_once(rdm_engine* e, int B, const float* const* refs, co
   }
   int64_t* all_len = e->alloc<int64_t>(static_cast<size_t>(4) * nc);  // levels 1..4 x clouds, contiguous for one read-back
   ENG_ALLOC(all_len);
-  static const int gs_multi_levels = [] { const char* v = ::rdm::dev_knob("RDM_GS_MULTI_LEVELS"); return v ? atoi(v) : 1; }();
   float voxel = c.init_voxel_size;
   for (int i = 1; i < 5; ++i) {
     voxel *= 2.f;  // data.py:23-28
@@ -1108,7 +1194,7 @@ static int collate_batch_once(rdm_engine* e, int B, const float* const* refs, co
     len[i] = all_len + static_cast<size_t>(i - 1) * nc;
     ENG_ALLOC(pts[i]);
     ENG_CHECK(grid_subsample_mode(pts[i - 1], n_tot, len[i - 1], nc, voxel, pts[i], len[i], r.ws, r.ws_bytes, st,
-                                  i <= gs_multi_levels ? 2 : 1));
+                                  i <= gs_multi_levels() ? 2 : 1));
   }
   std::vector<int64_t> host_len(static_cast<size_t>(4) * nc);
   RDM_REQUIRE(host_len.size() * sizeof(int64_t) <= 4096, "rdm_engine_collate_batch: too many pairs for the read-back buffer");
@@ -1135,66 +1221,10 @@ static int collate_batch_once(rdm_engine* e, int B, const float* const* refs, co
       }
     }
   }
-  // the (pair, level) grids, eight items per set of launches
-  {
-    const float* gp[8];
-    int64_t gn[8];
-    const int64_t* gl[8];
-    float gr[8];
-    void* gw[8];
-    size_t gb[8];
-    int k = 0;
-    auto flush = [&]() -> int {
-      if (k > 0) ENG_CHECK(radius_grid_build_multi(k, gp, gn, gl, 2, gr, gw, gb, st));
-      k = 0;
-      return RDM_OK;
-    };
-    for (int p = 0; p < B; ++p) {
-      float rad = c.init_radius;
-      for (int i = 0; i < 5; ++i, rad *= 2.f) {
-        Grid& g = e->batch[p].grids[i];
-        g.n_s = e->batch[p].lv[i].n;
-        g.bytes = rdm_radius_grid_workspace_bytes(g.n_s);
-        g.ws = e->alloc<char>(g.bytes);
-        ENG_ALLOC(g.ws);
-        gp[k] = e->batch[p].lv[i].pts; gn[k] = g.n_s; gl[k] = e->batch[p].lv[i].lengths; gr[k] = rad; gw[k] = g.ws; gb[k] = g.bytes;
-        if (++k == 8) ENG_CHECK(flush());
-      }
-    }
-    ENG_CHECK(flush());
-  }
-  // the searches of a plain run (engine_run_once: 12 per pair, int32 tables, one column of the up-sampling tables 1..3)
-  {
-    std::vector<char> queue(radius_redo_queue_bytes());
-    radius_redo_queue_reset(queue.data());
-    int queued = 0;
-    for (int p = 0; p < B; ++p) {
-      PairPyramid& py = e->batch[p];
-      auto search = [&](const Level& q, const Grid& g, float rad, int limit, Table& t, bool i32) -> int {
-        if (queued == 16) {  // (the queue's capacity: radius_neighbors.hip kRedoMax)
-          ENG_CHECK(radius_redo_flush(queue.data(), st));
-          queued = 0;
-        }
-        t.rows = q.n; t.width = limit; t.flags = py.flags + 2 * py.calls++;
-        t.i32 = i32;
-        t.idx = reinterpret_cast<int64_t*>(e->alloc<char>(static_cast<size_t>(q.n > 0 ? q.n : 1) * limit * (i32 ? 4 : 8)));
-        ENG_ALLOC(t.idx);
-        unsigned char* redo_flags = e->alloc<unsigned char>(static_cast<size_t>(q.n > 0 ? q.n : 1));
-        ENG_ALLOC(redo_flags);
-        ++queued;
-        return radius_grid_query_deferred(g.ws, g.bytes, g.n_s, q.pts, q.n, q.lengths, 2, rad, limit, t.idx, nullptr, t.flags,
-                                          t.flags + 1, redo_flags, queue.data(), i32 ? 1 : 0, st);
-      };
-      float radius = c.init_radius;
-      for (int i = 0; i < 5; ++i) {  // (the order of engine_run_once: the status rows are numbered by it)
-        ENG_CHECK(search(py.lv[i], py.grids[i], radius, c.neighbor_limits[i], py.nb[i], true));
-        if (i < 4) ENG_CHECK(search(py.lv[i + 1], py.grids[i], radius, c.neighbor_limits[i], py.sub[i], true));
-        if (i > 1) ENG_CHECK(search(py.lv[i - 1], py.grids[i], radius, 1, py.up[i - 1], false));
-        radius *= 2.f;
-      }
-    }
-    ENG_CHECK(radius_redo_flush(queue.data(), st));
-  }
+  ENG_CHECK(build_level_grids(e, e->batch.data(), B, 0, 5, st));
+  SearchQueue sq(st);
+  for (PairPyramid& py : e->batch) ENG_CHECK(search_pyramid(e, py, false, false, sq));
+  ENG_CHECK(sq.flush());
   e->arena_base = e->arena_off;
   e->batch_n_ref.assign(n_refs, n_refs + B);
   e->batch_n_src.assign(n_srcs, n_srcs + B);
@@ -1216,17 +1246,8 @@ extern "C" int rdm_engine_collate_batch(rdm_engine* e, int n_pairs, const float*
       e->batch.clear();
       e->arena_base = 0;
     }
-    if (rc != RDM_ERR_WORKSPACE || !e->arena_exhausted || e->arena_fixed || e->arena_cap >= (size_t(96) << 30)) return rc;
-    RDM_HIP_CHECK(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    RDM_HIP_CHECK(hipFree(e->arena));
-    e->arena = nullptr;
-    e->arena_cap *= 2;
-    const hipError_t err = hipMalloc(reinterpret_cast<void**>(&e->arena), e->arena_cap);
-    if (err != hipSuccess) {
-      e->arena_cap = 0;
-      set_error("rdm_engine_collate_batch: growing the activation arena failed: %s", hipGetErrorString(err));
-      return RDM_ERR_HIP;
-    }
+    if (!may_grow(e, rc)) return rc;
+    ENG_CHECK(grow_arena(e, stream, "rdm_engine_collate_batch"));
   }
 }
 
@@ -1237,10 +1258,7 @@ extern "C" int rdm_engine_collate_batch(rdm_engine* e, int n_pairs, const float*
 extern "C" int rdm_engine_forward_batched(rdm_engine* e, int k, rdm_engine_result* res, void* stream) {
   RDM_REQUIRE(e && res, "rdm_engine_forward_batched: null pointer");
   RDM_REQUIRE(k >= 0 && k < static_cast<int>(e->batch.size()), "rdm_engine_forward_batched: no collated pair %d (rdm_engine_collate_batch first)", k);
-  struct PadGuard {
-    explicit PadGuard(unsigned b) { rdm::gemm_set_lds_pad(b); }
-    ~PadGuard() { rdm::gemm_set_lds_pad(0); }
-  } pad_guard(e->pairs_in_flight >= 3 ? 20480u : 0u);
+  PadGuard pad_guard(e->pairs_in_flight >= 3 ? 20480u : 0u);
   e->arena_exhausted = false;
   return engine_run_once(e, nullptr, e->batch_n_ref[k], nullptr, e->batch_n_src[k], nullptr, res, stream, &e->batch[k]);
 }
@@ -1251,110 +1269,60 @@ extern "C" int rdm_engine_forward_batched(rdm_engine* e, int k, rdm_engine_resul
 // all pairs goes out as one grouped launch; the four size read-backs of the pairs become four waits of the group.  Every pair gets
 // the bits of rdm_engine_run on it alone (same kernel bodies, arguments and grids).
 namespace {
-struct LockstepJob {
-  rdm_engine* const* engines;
-  const float* const* refs;
-  const int64_t* n_refs;
-  const float* const* srcs;
-  const int64_t* n_srcs;
-  rdm_engine_result* const* results;
-  void* stream;
-  bool collated;  // the pyramids of all pairs lie in engines[0]'s arena (rdm_engine_collate_batch)
-  const rdm_data_dict* const* dds;  // rdm_engine_forward_lockstep: the callers' data_dicts (the forwards alone), else null
-  bool collate_only = false;        // rdm_engine_collate_lockstep: the collates alone (full tables kept as stage tensors)
-};
-int lockstep_pair(int k, void* user) {
-  const LockstepJob& j = *static_cast<const LockstepJob*>(user);
-  rdm_engine* e = j.engines[k];
-  e->arena_exhausted = false;
-  if (j.collate_only) {  // (as rdm_engine_collate: the stage tensors of THIS call are kept whatever rdm_engine_keep_taps says)
-    const bool keep_before = e->keep_taps;
-    e->keep_taps = true;
-    e->collate_only = true;
-    const int rc = engine_run_once(e, j.refs[k], j.n_refs[k], j.srcs[k], j.n_srcs[k], nullptr, j.results[k], j.stream);
-    e->collate_only = false;
-    e->keep_taps = keep_before;
-    return rc;
-  }
-  if (j.dds) {
-    const rdm_data_dict* dd = j.dds[k];
-    return engine_run_once(e, nullptr, dd->n_ref[0], nullptr, dd->n_points[0] - dd->n_ref[0], dd, j.results[k], j.stream);
-  }
-  if (j.collated) {  // (engines 1.. read the pyramid in engines[0]'s arena and keep their activations in their own)
-    if (k > 0) {
-      e->batch.clear();
-      e->arena_base = 0;
-    }
-    return engine_run_once(e, nullptr, j.n_refs[k], nullptr, j.n_srcs[k], nullptr, j.results[k], j.stream, &j.engines[0]->batch[k]);
-  }
-  return engine_run_once(e, j.refs[k], j.n_refs[k], j.srcs[k], j.n_srcs[k], nullptr, j.results[k], j.stream);
-}
-int lockstep_wait(hipStream_t st, void* user) {
-  rdm_engine* e = static_cast<rdm_engine*>(user);
-  if (e->wait_sleep_us <= 0) {
-    RDM_HIP_CHECK(hipStreamSynchronize(st));
-    return RDM_OK;
-  }
-  for (;;) {
-    const hipError_t q = hipStreamQuery(st);
-    if (q == hipSuccess) return RDM_OK;
-    if (q != hipErrorNotReady) {
-      set_error("hipStreamQuery failed: %s", hipGetErrorString(q));
-      return RDM_ERR_HIP;
-    }
-    timespec ts{0, static_cast<long>(e->wait_sleep_us) * 1000};
-    nanosleep(&ts, nullptr);
-  }
-}
-}  // namespace
+int lockstep_wait(hipStream_t st, void* user) { return wait_idle(static_cast<rdm_engine*>(user), st); }
 
-extern "C" int rdm_engine_run_lockstep(rdm_engine* const* engines, int n_pairs, const float* const* ref_points, const int64_t* n_ref,
-                                       const float* const* src_points, const int64_t* n_src, rdm_engine_result* const* results,
-                                       int collate_batched, void* stream) {
-  RDM_REQUIRE(engines && ref_points && n_ref && src_points && n_src && results, "rdm_engine_run_lockstep: null pointer");
-  RDM_REQUIRE(n_pairs >= 1 && n_pairs <= kGroupMax, "rdm_engine_run_lockstep: 1 .. %d pairs", kGroupMax);
-  for (int k = 0; k < n_pairs; ++k) {
-    RDM_REQUIRE(engines[k] && results[k] && ref_points[k] && src_points[k] && n_ref[k] > 0 && n_src[k] > 0,
-                "rdm_engine_run_lockstep: pair %d is incomplete", k);
-    RDM_REQUIRE(engines[k]->finalized, "rdm_engine_run_lockstep: engine %d is not finalized", k);
-    for (int j = 0; j < k; ++j) RDM_REQUIRE(engines[j] != engines[k], "rdm_engine_run_lockstep: every pair needs an engine of its own");
+struct LockstepJob {  // what a lock-step entry hands lockstep_drive; k: the pair
+  const char* who;                      // the entry's name, for its error texts
+  std::function<bool(int)> has_input;   // pair k's inputs are there
+  std::function<int(int)> check;        // further checks of pair k's inputs (optional)
+  std::function<int()> prepare;         // before the group runs (optional)
+  std::function<int(int)> pair;         // pair k as a context of the group
+  std::function<int(int)> rerun;        // pair k alone after it exhausted its arena (the arena grows)
+};
+
+// The lock-step entries' common part: checks the group, runs job.pair(k) for every k as the contexts of one lock-step group on
+// `stream`, runs a pair that exhausted its (growable) arena again on its own -- in reverse order: engines[0] last, whose arena a
+// batched collate put every pair's pyramid in (they are done by then) -- and returns the first pair's error.
+int lockstep_drive(const LockstepJob& job, rdm_engine* const* engines, rdm_engine_result* const* results, int n, void* stream) {
+  const char* who = job.who;
+  RDM_REQUIRE(n >= 1 && n <= kGroupMax, "%s: 1 .. %d pairs", who, kGroupMax);
+  for (int k = 0; k < n; ++k) {
+    RDM_REQUIRE(engines[k] && results[k] && job.has_input(k), "%s: pair %d is incomplete", who, k);
+    RDM_REQUIRE(engines[k]->finalized, "%s: engine %d is not finalized", who, k);
+    for (int j = 0; j < k; ++j) RDM_REQUIRE(engines[j] != engines[k], "%s: every pair needs an engine of its own", who);
+    if (job.check) ENG_CHECK(job.check(k));
   }
-  struct PadGuard {
-    explicit PadGuard(unsigned b) { rdm::gemm_set_lds_pad(b); }
-    ~PadGuard() { rdm::gemm_set_lds_pad(0); }
-  } pad_guard(0u);  // (no GEMM residency cap: a grouped launch is wide enough to want all four workgroups per CU -- 633 against 627 pairs/s at 4 x 4)
-  // the collates of all pairs as one launch sequence on engines[0] (exact, tests/test_engine_gpu.py), then the forwards in lock step
-  bool any_taps = false;  // (an engine that keeps its stage tensors builds the reference's full tables: it collates its own pair)
-  for (int k = 0; k < n_pairs; ++k) any_taps |= engines[k]->keep_taps;
-  const bool collated = collate_batched != 0 && n_pairs > 1 && !any_taps;
-  if (collated) ENG_CHECK(rdm_engine_collate_batch(engines[0], n_pairs, ref_points, n_ref, src_points, n_src, stream));
-  LockstepJob job{engines, ref_points, n_ref, src_points, n_src, results, stream, collated, nullptr};
+  PadGuard pad_guard(0u);  // (no GEMM residency cap: a grouped launch is wide enough to want all four workgroups per CU -- 633 against 627 pairs/s at 4 x 4)
+  if (job.prepare) ENG_CHECK(job.prepare());
+  struct Ctx {
+    rdm_engine* const* engines;
+    const LockstepJob* job;
+  } ctx{engines, &job};
+  auto run_pair = [](int k, void* user) -> int {
+    const Ctx& c = *static_cast<const Ctx*>(user);
+    c.engines[k]->arena_exhausted = false;
+    return c.job->pair(k);
+  };
   int rcs[kGroupMax] = {};
-  const int wrc = lockstep_run(n_pairs, lockstep_pair, &job, static_cast<hipStream_t>(stream), lockstep_wait, engines[0], rcs);
+  const int wrc = lockstep_run(n, run_pair, &ctx, static_cast<hipStream_t>(stream), lockstep_wait, engines[0], rcs);
   if (wrc == -1) {
-    set_error("rdm_engine_run_lockstep: called from inside a lock-step group (a host thread runs one group at a time)");
+    set_error("%s: called from inside a lock-step group (a host thread runs one group at a time)", who);
     return RDM_ERR_ARG;
   }
   if (wrc == -3) {
-    set_error("rdm_engine_run_lockstep: no memory for the context stacks");
+    set_error("%s: no memory for the context stacks", who);
     return RDM_ERR_HIP;
   }
   if (wrc != 0) return wrc;  // (the group's host wait failed: the error text is the wait's)
-  // a pair that exhausted its arena runs again on its own: rdm_engine_run grows the arena (engines[0] last: that rewrites the
-  // arena the other pairs' pyramids lie in -- they are done by then)
-  for (int k = n_pairs - 1; k >= 0; --k) {
-    if (rcs[k] == RDM_ERR_WORKSPACE && engines[k]->arena_exhausted && !engines[k]->arena_fixed)
-      rcs[k] = engine_run_growing(engines[k], ref_points[k], n_ref[k], src_points[k], n_src[k], nullptr, results[k], stream);
+  for (int k = n - 1; k >= 0; --k) {
+    if (rcs[k] == RDM_ERR_WORKSPACE && engines[k]->arena_exhausted && !engines[k]->arena_fixed) rcs[k] = job.rerun(k);
   }
-  for (int k = 0; k < n_pairs; ++k)
+  for (int k = 0; k < n; ++k)
     if (rcs[k] != RDM_OK) return rcs[k];
   return RDM_OK;
 }
 
-// RDMNet.forward (model_infer.py:109-354) of n callers' data_dicts on n engines in lock step: rdm_engine_forward per pair, the
-// launches grouped as in rdm_engine_run_lockstep.  Every pair: the bits (and stage tensors, with rdm_engine_keep_taps) of
-// rdm_engine_forward on it alone.
-static int check_data_dict(const rdm_data_dict* dd, const char* who) {
+int check_data_dict(const rdm_data_dict* dd, const char* who) {
   for (int i = 0; i < 5; ++i) {
     RDM_REQUIRE(dd->points[i] && dd->lengths[i] && dd->neighbors[i] && dd->n_points[i] > 1 && dd->n_ref[i] > 0 &&
                     dd->n_ref[i] < dd->n_points[i] && dd->neighbors_width[i] > 0 && dd->neighbors_ld[i] >= dd->neighbors_width[i],
@@ -1367,41 +1335,58 @@ static int check_data_dict(const rdm_data_dict* dd, const char* who) {
   RDM_REQUIRE(dd->features && dd->features_ld >= 1, "%s: features missing", who);
   return RDM_OK;
 }
+}  // namespace
 
+extern "C" int rdm_engine_run_lockstep(rdm_engine* const* engines, int n_pairs, const float* const* ref_points, const int64_t* n_ref,
+                                       const float* const* src_points, const int64_t* n_src, rdm_engine_result* const* results,
+                                       int collate_batched, void* stream) {
+  RDM_REQUIRE(engines && ref_points && n_ref && src_points && n_src && results, "rdm_engine_run_lockstep: null pointer");
+  // the collates of all pairs as one launch sequence on engines[0] (exact, tests/test_engine_gpu.py), then the forwards in lock
+  // step; engines 1.. read their pyramid in engines[0]'s arena and keep their activations in their own
+  bool collated = false;
+  LockstepJob job;
+  job.who = "rdm_engine_run_lockstep";
+  job.has_input = [&](int k) { return ref_points[k] && src_points[k] && n_ref[k] > 0 && n_src[k] > 0; };
+  job.prepare = [&]() -> int {
+    bool any_taps = false;  // (an engine that keeps its stage tensors builds the reference's full tables: it collates its own pair)
+    for (int k = 0; k < n_pairs; ++k) any_taps |= engines[k]->keep_taps;
+    collated = collate_batched != 0 && n_pairs > 1 && !any_taps;
+    return collated ? rdm_engine_collate_batch(engines[0], n_pairs, ref_points, n_ref, src_points, n_src, stream) : RDM_OK;
+  };
+  job.pair = [&](int k) {
+    rdm_engine* e = engines[k];
+    if (!collated) return engine_run_once(e, ref_points[k], n_ref[k], src_points[k], n_src[k], nullptr, results[k], stream);
+    if (k > 0) {
+      e->batch.clear();
+      e->arena_base = 0;
+    }
+    return engine_run_once(e, nullptr, n_ref[k], nullptr, n_src[k], nullptr, results[k], stream, &engines[0]->batch[k]);
+  };
+  job.rerun = [&](int k) {
+    return engine_run_growing(engines[k], ref_points[k], n_ref[k], src_points[k], n_src[k], nullptr, results[k], stream);
+  };
+  return lockstep_drive(job, engines, results, n_pairs, stream);
+}
+
+// RDMNet.forward (model_infer.py:109-354) of n callers' data_dicts on n engines in lock step: rdm_engine_forward per pair, the
+// launches grouped as in rdm_engine_run_lockstep.  Every pair: the bits (and stage tensors, with rdm_engine_keep_taps) of
+// rdm_engine_forward on it alone.
 extern "C" int rdm_engine_forward_lockstep(rdm_engine* const* engines, int n_pairs, const rdm_data_dict* const* data,
                                            rdm_engine_result* const* results, void* stream) {
   RDM_REQUIRE(engines && data && results, "rdm_engine_forward_lockstep: null pointer");
-  RDM_REQUIRE(n_pairs >= 1 && n_pairs <= kGroupMax, "rdm_engine_forward_lockstep: 1 .. %d pairs", kGroupMax);
-  for (int k = 0; k < n_pairs; ++k) {
-    RDM_REQUIRE(engines[k] && results[k] && data[k], "rdm_engine_forward_lockstep: pair %d is incomplete", k);
-    RDM_REQUIRE(engines[k]->finalized, "rdm_engine_forward_lockstep: engine %d is not finalized", k);
-    for (int j = 0; j < k; ++j) RDM_REQUIRE(engines[j] != engines[k], "rdm_engine_forward_lockstep: every pair needs an engine of its own");
-    if (int rc = check_data_dict(data[k], "rdm_engine_forward_lockstep")) return rc;
-  }
-  struct PadGuard {
-    explicit PadGuard(unsigned b) { rdm::gemm_set_lds_pad(b); }
-    ~PadGuard() { rdm::gemm_set_lds_pad(0); }
-  } pad_guard(0u);  // (as rdm_engine_run_lockstep)
-  LockstepJob job{engines, nullptr, nullptr, nullptr, nullptr, results, stream, false, data};
-  int rcs[kGroupMax] = {};
-  const int wrc = lockstep_run(n_pairs, lockstep_pair, &job, static_cast<hipStream_t>(stream), lockstep_wait, engines[0], rcs);
-  if (wrc == -1) {
-    set_error("rdm_engine_forward_lockstep: called from inside a lock-step group (a host thread runs one group at a time)");
-    return RDM_ERR_ARG;
-  }
-  if (wrc == -3) {
-    set_error("rdm_engine_forward_lockstep: no memory for the context stacks");
-    return RDM_ERR_HIP;
-  }
-  if (wrc != 0) return wrc;
-  for (int k = n_pairs - 1; k >= 0; --k) {  // a pair that exhausted its arena runs again on its own (the arena grows)
-    if (rcs[k] == RDM_ERR_WORKSPACE && engines[k]->arena_exhausted && !engines[k]->arena_fixed)
-      rcs[k] = engine_run_growing(engines[k], nullptr, data[k]->n_ref[0], nullptr, data[k]->n_points[0] - data[k]->n_ref[0], data[k],
-                                  results[k], stream);
-  }
-  for (int k = 0; k < n_pairs; ++k)
-    if (rcs[k] != RDM_OK) return rcs[k];
-  return RDM_OK;
+  LockstepJob job;
+  job.who = "rdm_engine_forward_lockstep";
+  job.has_input = [&](int k) { return data[k] != nullptr; };
+  job.check = [&](int k) { return check_data_dict(data[k], "rdm_engine_forward_lockstep"); };
+  job.pair = [&](int k) {
+    const rdm_data_dict* dd = data[k];
+    return engine_run_once(engines[k], nullptr, dd->n_ref[0], nullptr, dd->n_points[0] - dd->n_ref[0], dd, results[k], stream);
+  };
+  job.rerun = [&](int k) {
+    const rdm_data_dict* dd = data[k];
+    return engine_run_growing(engines[k], nullptr, dd->n_ref[0], nullptr, dd->n_points[0] - dd->n_ref[0], dd, results[k], stream);
+  };
+  return lockstep_drive(job, engines, results, n_pairs, stream);
 }
 
 // The collates of n pairs (rdm_engine_collate each: full tables at the reference's widths, kept as stage tensors of the pair's
@@ -1410,32 +1395,15 @@ extern "C" int rdm_engine_collate_lockstep(rdm_engine* const* engines, int n_pai
                                            const float* const* src_points, const int64_t* n_src, rdm_engine_result* const* results,
                                            void* stream) {
   RDM_REQUIRE(engines && ref_points && n_ref && src_points && n_src && results, "rdm_engine_collate_lockstep: null pointer");
-  RDM_REQUIRE(n_pairs >= 1 && n_pairs <= kGroupMax, "rdm_engine_collate_lockstep: 1 .. %d pairs", kGroupMax);
-  for (int k = 0; k < n_pairs; ++k) {
-    RDM_REQUIRE(engines[k] && results[k] && ref_points[k] && src_points[k] && n_ref[k] > 0 && n_src[k] > 0,
-                "rdm_engine_collate_lockstep: pair %d is incomplete", k);
-    RDM_REQUIRE(engines[k]->finalized, "rdm_engine_collate_lockstep: engine %d is not finalized", k);
-    for (int j = 0; j < k; ++j) RDM_REQUIRE(engines[j] != engines[k], "rdm_engine_collate_lockstep: every pair needs an engine of its own");
-  }
-  LockstepJob job{engines, ref_points, n_ref, src_points, n_src, results, stream, false, nullptr, true};
-  int rcs[kGroupMax] = {};
-  const int wrc = lockstep_run(n_pairs, lockstep_pair, &job, static_cast<hipStream_t>(stream), lockstep_wait, engines[0], rcs);
-  if (wrc == -1) {
-    set_error("rdm_engine_collate_lockstep: called from inside a lock-step group (a host thread runs one group at a time)");
-    return RDM_ERR_ARG;
-  }
-  if (wrc == -3) {
-    set_error("rdm_engine_collate_lockstep: no memory for the context stacks");
-    return RDM_ERR_HIP;
-  }
-  if (wrc != 0) return wrc;
-  for (int k = n_pairs - 1; k >= 0; --k) {  // a pair that exhausted its arena collates again on its own (the arena grows)
-    if (rcs[k] == RDM_ERR_WORKSPACE && engines[k]->arena_exhausted && !engines[k]->arena_fixed)
-      rcs[k] = rdm_engine_collate(engines[k], ref_points[k], n_ref[k], src_points[k], n_src[k], results[k], stream);
-  }
-  for (int k = 0; k < n_pairs; ++k)
-    if (rcs[k] != RDM_OK) return rcs[k];
-  return RDM_OK;
+  LockstepJob job;
+  job.who = "rdm_engine_collate_lockstep";
+  job.has_input = [&](int k) { return ref_points[k] && src_points[k] && n_ref[k] > 0 && n_src[k] > 0; };
+  job.pair = [&](int k) {
+    CollateOnly collate_only(engines[k]);
+    return engine_run_once(engines[k], ref_points[k], n_ref[k], src_points[k], n_src[k], nullptr, results[k], stream);
+  };
+  job.rerun = [&](int k) { return rdm_engine_collate(engines[k], ref_points[k], n_ref[k], src_points[k], n_src[k], results[k], stream); };
+  return lockstep_drive(job, engines, results, n_pairs, stream);
 }
 
 // The collate alone (geotransformer/utils/data.py:13-77 on two clouds): the pyramid and its 13 searches stay in the engine's
@@ -1447,13 +1415,8 @@ extern "C" int rdm_engine_collate(rdm_engine* e, const float* ref_points, int64_
   RDM_REQUIRE(e && ref_points && src_points && res, "rdm_engine_collate: null pointer");
   RDM_REQUIRE(n_ref > 0 && n_src > 0, "rdm_engine_collate: empty cloud");
   RDM_REQUIRE(e->finalized, "rdm_engine_collate: call rdm_engine_finalize first");
-  const bool keep_before = e->keep_taps;  // the stage tensors of THIS call are kept; later runs keep what they kept before
-  e->keep_taps = true;
-  e->collate_only = true;
-  const int rc = engine_run_growing(e, ref_points, n_ref, src_points, n_src, nullptr, res, stream);
-  e->collate_only = false;
-  e->keep_taps = keep_before;
-  return rc;
+  CollateOnly collate_only(e);
+  return engine_run_growing(e, ref_points, n_ref, src_points, n_src, nullptr, res, stream);
 }
 
 // RDMNet.forward alone (experiments/model_infer.py:109-354) on a data_dict the caller collated -- with this library's
@@ -1465,399 +1428,158 @@ extern "C" int rdm_engine_forward(rdm_engine* e, const rdm_data_dict* dd, rdm_en
   return engine_run_growing(e, nullptr, dd->n_ref[0], nullptr, dd->n_points[0] - dd->n_ref[0], dd, res, stream);
 }
 
-static int engine_run_once(rdm_engine* e, const float* ref_points, int64_t n_ref, const float* src_points, int64_t n_src,
-                           const rdm_data_dict* dd, rdm_engine_result* res, void* stream, const PairPyramid* pre) {
-  const rdm_engine_config& c = e->cfg;
-  e->arena_off = pre ? e->arena_base : 0;  // (a pair of a collated batch: its pyramid lies below arena_base)
-  e->gt.valid = false;
-  if (!pre) {
-    e->batch.clear();  // (the arena is rewritten: a collated batch is gone)
-    e->arena_base = 0;
-  }
-  e->taps.clear();
-  e->prof.clear();
-  e->prof_layers = 0;
-  Run r;
-  r.e = e; r.st = static_cast<hipStream_t>(stream); r.groups = c.group_norm;
-  const int64_t n0 = n_ref + n_src;
-  // latency mode (see rdm_engine::overlap_mode); never on the legacy null stream, which every other blocking stream serialises with
-  bool overlap = !pre && !lockstep_active() && !e->collate_only && r.st != nullptr && (e->overlap_mode == 2 || (e->overlap_mode == 1 && e->pairs_in_flight == 1));
-  if (overlap) ENG_CHECK(ensure_side(e, r.st, &overlap));
-  SideGuard side_guard{e};
-  // kernel scratch: the largest consumers are the grid-subsample tables and split-K partials
-  r.ws_bytes = pre ? size_t(96) << 20
-                   : std::max<size_t>(rdm_grid_subsample_workspace_bytes(n0, 2),
-                                      std::max<size_t>(rdm_radius_neighbors_workspace_bytes(n0, n0, 2), size_t(96) << 20));
-  r.ws = e->alloc<char>(r.ws_bytes);
-  ENG_ALLOC(r.ws);
-  std::memset(res, 0, sizeof(*res));
+namespace {
 
-  Level lv[5];
-  Table nb[5], sub[4], up[4];
-  int32_t* flags = pre ? pre->flags : e->alloc<int32_t>(64);
-  ENG_ALLOC(flags);
-  // Latency mode, first half: the caller's stream runs the subsampling of levels 1-4 (a chain of one- and two-workgroup kernels,
-  // ~0.4 ms) while the side stream builds the first level's grid, searches its neighbours and runs the encoder's first two
-  // blocks (wide launches that need nothing but level 0).  No device-side dependency: taken only when the caller's stream is
-  // idle at the call (the inputs are then complete), and joined by a host wait next to the read-back of the level sizes.
-  bool overlap_l0 = false;
-  if (overlap && !dd) {  // (a hand-off event the caller just made the stream wait for -- dataset.PairStager -- takes it a few us)
-    const auto t_poll = std::chrono::steady_clock::now();
-    do {
-      overlap_l0 = hipStreamQuery(r.st) == hipSuccess;
-    } while (!overlap_l0 && std::chrono::steady_clock::now() - t_poll < std::chrono::microseconds(40));
+// ---------------------------------------------------------------- the network's stages (model_infer.py:109-354)
+struct Encoder {  // backbone.py:72-107
+  Mat x;                     // the last block's output
+  uint8_t* x_pos = nullptr;  // the input features' "row sum > 0" flags (kpconv.py:113-114)
+  Mat feats[5];              // each level's last block: the decoder's skip features
+  int blocks = 0;            // blocks issued (latency mode: 0-1 on the side stream, inside the collate)
+};
+
+int encoder_input(Run& rr, const rdm_data_dict* dd, int64_t n0, Encoder& enc) {
+  rdm_engine* e = rr.e;
+  Mat& x = enc.x;
+  if (dd) {  // data_dict['features'] (model_infer.py:113), [N0, 1]
+    x.p = const_cast<float*>(dd->features); x.rows = n0; x.cols = 1; x.ld = dd->features_ld;
+  } else {
+    x = e->mat(n0, 1);
+    ENG_ALLOC(x.p);
   }
-  Run rs = r;  // the side stream's launches of the first level
-  if (overlap_l0) {
-    rs.st = e->side;
-    rs.ws_bytes = std::max<size_t>(size_t(96) << 20, rdm_linear_group_norm_workspace_bytes(n0, 128));
-    rs.ws = e->alloc<char>(rs.ws_bytes);
-    ENG_ALLOC(rs.ws);
-  }
-  if (!pre) fill_words<int32_t>(flags, 64, 0, overlap_l0 ? rs.st : r.st);  // (the first searches write their status rows on that stream)
-  int call = pre ? pre->calls : 0;
-  Grid grids[5] = {};
-  std::vector<char> redo_queue(radius_redo_queue_bytes());
-  radius_redo_queue_reset(redo_queue.data());
-  auto build_grid = [&](const Level& s, float rad, Grid& g) -> int {
-    g.n_s = s.n;
-    g.bytes = rdm_radius_grid_workspace_bytes(s.n);
-    g.ws = e->alloc<char>(g.bytes);
-    ENG_ALLOC(g.ws);
-    return rdm_radius_grid_build(s.pts, s.n, s.lengths, 2, rad, g.ws, g.bytes, r.st);
-  };
-  auto search = [&](const Level& q, const Grid& g, float rad, int limit, Table& t, bool i32 = false, void* queue = nullptr,
-                    hipStream_t qst = nullptr) -> int {
-    t.rows = q.n; t.width = limit; t.flags = flags + 2 * call++;
-    t.i32 = i32;
-    t.idx = reinterpret_cast<int64_t*>(e->alloc<char>(static_cast<size_t>(q.n > 0 ? q.n : 1) * limit * (i32 ? 4 : 8)));
-    ENG_ALLOC(t.idx);
-    // the large-buffer second pass of all 14 searches is one launch after the loop (radius_redo_flush)
-    unsigned char* redo_flags = e->alloc<unsigned char>(static_cast<size_t>(q.n > 0 ? q.n : 1));
-    ENG_ALLOC(redo_flags);
-    return radius_grid_query_deferred(g.ws, g.bytes, g.n_s, q.pts, q.n, q.lengths, 2, rad, limit, t.idx, nullptr, t.flags,
-                                      t.flags + 1, redo_flags, queue ? queue : redo_queue.data(), i32 ? 1 : 0, qst ? qst : r.st);
-  };
-  // the five level grids with one set of launches (radius r_i = 2^i r_0): they serve the searches of the collate and, through
-  // their cell-sorted records, the spatial query order of the KPConv kernels and the shortcut pools
-  auto build_level_grids = [&](int first = 0, int last = 5, hipStream_t gst = nullptr) -> int {  // levels [first, last)
-    const float* gp[5];
-    int64_t gn[5];
-    const int64_t* gl[5];
-    float gr[5];
-    void* gw[5];
-    size_t gb[5];
-    float rad = c.init_radius;
-    int k = 0;
-    for (int i = 0; i < last; ++i, rad *= 2.f) {
-      if (i < first) continue;
-      grids[i].n_s = lv[i].n;
-      grids[i].bytes = rdm_radius_grid_workspace_bytes(lv[i].n);
-      grids[i].ws = e->alloc<char>(grids[i].bytes);
-      ENG_ALLOC(grids[i].ws);
-      gp[k] = lv[i].pts; gn[k] = lv[i].n; gl[k] = lv[i].lengths; gr[k] = rad; gw[k] = grids[i].ws; gb[k] = grids[i].bytes;
-      ++k;
-    }
-    RDM_DUP_LOOP("rnbuild")
-    ENG_CHECK(radius_grid_build_multi(k, gp, gn, gl, 2, gr, gw, gb, gst ? gst : r.st));
-    return RDM_OK;
-  };
-  // ---------------------------------------------------------------- encoder (backbone.py:72-107), as two callables: the
-  // latency mode runs the input and the first two blocks on the side stream while the deeper levels are still being subsampled
-  Mat x;
-  uint8_t* x_pos = nullptr;
-  Mat feats[5];
-  int fi = 0;
-  auto encoder_input = [&](Run& rr) -> int {
-    if (dd) {  // data_dict['features'] (model_infer.py:113), [N0, 1]
-      x.p = const_cast<float*>(dd->features); x.rows = n0; x.cols = 1; x.ld = dd->features_ld;
+  enc.x_pos = e->alloc<uint8_t>(n0);
+  ENG_ALLOC(enc.x_pos);
+  if (dd) return rdm_row_positive(x.p, n0, 1, x.ld, enc.x_pos, rr.st);
+  return launch1d<unit_features_kernel_body, unit_features_kernel>("unit_features", n0, rr.st, x.p, n0, x.ld, enc.x_pos);
+}
+
+int encoder_blocks(Run& rr, const PairPyramid& py, int b0, int b1, Encoder& enc) {
+  rdm_engine* e = rr.e;
+  const char* names[14] = {"encoder1_1", "encoder1_2", "encoder2_1", "encoder2_2", "encoder2_3", "encoder3_1", "encoder3_2",
+                           "encoder3_3", "encoder4_1", "encoder4_2", "encoder4_3", "encoder5_1", "encoder5_2", "encoder5_3"};
+  const int level[14] = {0, 0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4};
+  const bool strided[14] = {false, false, true, false, false, true, false, false, true, false, false, true, false, false};
+  Mat& x = enc.x;
+  for (int b = b0; b < b1; ++b) {
+    const std::string name = std::string("encoder.") + names[b];
+    const int lvl = level[b];
+    const Level& s = py.lv[lvl];
+    const Level& q = strided[b] ? py.lv[lvl + 1] : py.lv[lvl];
+    const Table& t = strided[b] ? py.sub[lvl] : py.nb[lvl];
+    const float sigma = e->cfg.init_sigma * static_cast<float>(1 << lvl);
+    // visit the queries in the cell order of their level's search grid: neighbouring queries share most
+    // neighbours, so gathered lines are re-used from L1 (results do not depend on the order)
+    const Grid& qg = py.grids[strided[b] ? lvl + 1 : lvl];
+    const float* order = qg.ws ? rdm_radius_grid_records(qg.ws, qg.bytes, qg.n_s) : nullptr;
+    Mat y;
+    if (b == 0) {
+      ENG_CHECK(kpconv(rr, name + ".KPConv", x, enc.x_pos, q, s, t, sigma, name + ".norm", y, order));
     } else {
-      x = e->mat(n0, 1);
-      ENG_ALLOC(x.p);
-    }
-    x_pos = e->alloc<uint8_t>(n0);
-    ENG_ALLOC(x_pos);
-    if (dd) ENG_CHECK(rdm_row_positive(x.p, n0, 1, x.ld, x_pos, rr.st));
-    else ENG_CHECK(launch1d<unit_features_kernel_body, unit_features_kernel>("unit_features", n0, rr.st, x.p, n0, x.ld, x_pos));
-    return RDM_OK;
-  };
-  auto encoder_blocks = [&](Run& rr, int b0, int b1) -> int {
-    const char* names[14] = {"encoder1_1", "encoder1_2", "encoder2_1", "encoder2_2", "encoder2_3", "encoder3_1", "encoder3_2",
-                             "encoder3_3", "encoder4_1", "encoder4_2", "encoder4_3", "encoder5_1", "encoder5_2", "encoder5_3"};
-    const int level[14] = {0, 0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4};
-    const bool strided[14] = {false, false, true, false, false, true, false, false, true, false, false, true, false, false};
-    for (int b = b0; b < b1; ++b) {
-      const std::string name = std::string("encoder.") + names[b];
-      const int lvl = level[b];
-      const Level& s = lv[lvl];
-      const Level& q = strided[b] ? lv[lvl + 1] : lv[lvl];
-      const Table& t = strided[b] ? sub[lvl] : nb[lvl];
-      const float sigma = c.init_sigma * static_cast<float>(1 << lvl);
-      // visit the queries in the cell order of their level's search grid: neighbouring queries share most
-      // neighbours, so gathered lines are re-used from L1 (results do not depend on the order)
-      const Grid& qg = grids[strided[b] ? lvl + 1 : lvl];
-      const float* order = qg.ws ? rdm_radius_grid_records(qg.ws, qg.bytes, qg.n_s) : nullptr;
-      Mat y;
-      if (b == 0) {
-        ENG_CHECK(kpconv(rr, name + ".KPConv", x, x_pos, q, s, t, sigma, name + ".norm", y, order));
+      Mat h = x;
+      uint8_t* h_pos = e->alloc<uint8_t>(x.rows > 0 ? x.rows : 1);
+      ENG_ALLOC(h_pos);
+      if (e->params->lin.count(name + ".unary1.mlp")) {
+        ENG_CHECK(unary(rr, name + ".unary1", x, h, 2, nullptr, h_pos));
       } else {
-        Mat h = x;
-        uint8_t* h_pos = e->alloc<uint8_t>(x.rows > 0 ? x.rows : 1);
-        ENG_ALLOC(h_pos);
-        if (e->params->lin.count(name + ".unary1.mlp")) {
-          ENG_CHECK(unary(rr, name + ".unary1", x, h, 2, nullptr, h_pos));
-        } else {
-          ENG_CHECK(rdm_row_positive(x.p, x.rows, x.cols, x.ld, h_pos, rr.st));
-        }
-        Mat cn;
-        Mat sc = x;
-        ENG_CHECK(kpconv(rr, name + ".KPConv", h, h_pos, q, s, t, sigma, name + ".norm_conv", cn, order,
-                         strided[b] ? &x : nullptr, strided[b] ? &sc : nullptr));
-        if (e->params->lin.count(name + ".unary_shortcut.mlp")) {
-          Mat s2;
-          ENG_CHECK(unary(rr, name + ".unary_shortcut", sc, s2, 0, nullptr, nullptr));
-          sc = s2;
-        }
-        ENG_CHECK(unary(rr, name + ".unary2", cn, y, 2, &sc, nullptr));
+        ENG_CHECK(rdm_row_positive(x.p, x.rows, x.cols, x.ld, h_pos, rr.st));
       }
-      x = y;
-      tap(r, name.c_str(), x);
-      if (b == 1 || b == 4 || b == 7 || b == 10 || b == 13) feats[fi++] = x;
-    }
-    return RDM_OK;
-  };
-  if (pre) {
-    // ------------------------------------------------------------ a pair of a collated batch (rdm_engine_collate_batch)
-    for (int i = 0; i < 5; ++i) {
-      lv[i] = pre->lv[i];
-      nb[i] = pre->nb[i];
-      grids[i] = pre->grids[i];
-      res->level_sizes[i] = lv[i].n;
-      res->level_ref_sizes[i] = lv[i].n_ref;
-      if (i < 4) {
-        sub[i] = pre->sub[i];
-        up[i] = pre->up[i];
+      Mat cn;
+      Mat sc = x;
+      ENG_CHECK(kpconv(rr, name + ".KPConv", h, h_pos, q, s, t, sigma, name + ".norm_conv", cn, order,
+                       strided[b] ? &x : nullptr, strided[b] ? &sc : nullptr));
+      if (e->params->lin.count(name + ".unary_shortcut.mlp")) {
+        Mat s2;
+        ENG_CHECK(unary(rr, name + ".unary_shortcut", sc, s2, 0, nullptr, nullptr));
+        sc = s2;
       }
+      ENG_CHECK(unary(rr, name + ".unary2", cn, y, 2, &sc, nullptr));
     }
-  } else if (dd) {
-    // ------------------------------------------------------------ the caller's data_dict (model_infer.py:113-131)
-    for (int i = 0; i < 5; ++i) {
-      lv[i].pts = const_cast<float*>(dd->points[i]);
-      lv[i].n = dd->n_points[i];
-      lv[i].n_ref = dd->n_ref[i];
-      lv[i].lengths = const_cast<int64_t*>(dd->lengths[i]);
-      res->level_sizes[i] = lv[i].n;
-      res->level_ref_sizes[i] = lv[i].n_ref;
-      nb[i].idx = const_cast<int64_t*>(dd->neighbors[i]);
-      nb[i].rows = lv[i].n; nb[i].width = dd->neighbors_width[i]; nb[i].ld = dd->neighbors_ld[i];
-      nb[i].flags = const_cast<int32_t*>(dd->neighbors_count[i]);
-    }
-    for (int i = 0; i < 4; ++i) {
-      sub[i].idx = const_cast<int64_t*>(dd->subsampling[i]);
-      sub[i].rows = lv[i + 1].n; sub[i].width = dd->subsampling_width[i]; sub[i].ld = dd->subsampling_ld[i];
-      sub[i].flags = const_cast<int32_t*>(dd->subsampling_count[i]);
-      up[i].idx = const_cast<int64_t*>(dd->upsampling[i]);
-      up[i].rows = lv[i].n; up[i].width = dd->upsampling_width[i]; up[i].ld = dd->upsampling_ld[i];
-      up[i].flags = const_cast<int32_t*>(dd->upsampling_count[i]);
-    }
-    // the caller collated (no grids of ours): build them for the spatial query order of the encoder's kernels -- the same
-    // grids the per-op mirror builds (rdmnet_amd/model.py: run_encoder), so both give the same GroupNorm partials
-    ENG_CHECK(build_level_grids());
-    if (dd->collate_status && dd->n_collate_status > 0) {  // the collate's status words join the engine's own (checked below)
-      ::rdm::launch<or_status_kernel_body, or_status_kernel, 64>(dim3(1), 0, r.st, dd->collate_status, static_cast<int>(dd->n_collate_status),
-                         flags + 2 * call + 1);
-      ENG_CHECK(launch_status("or_status_kernel"));
-      call++;
-    }
-  } else {
-  // ---------------------------------------------------------------- collate (data.py:13-77)
-  // The forward consumes column 0 of upsampling[1..3] only (nearest_upsample, functional.py:6-22) and upsampling[0] not at all
-  // (backbone.py:118-151 stops at the second level): a plain run skips that search (32 000 queries, a quarter of all) and keeps one
-  // column of the others; the collate API and runs that keep their stage tensors build the reference's full tables.
-  // (in a plain run up[0] stays the default-constructed Table -- null pointer, zero rows, never read -- and the status
-  // rows `flags` are numbered in CALL order, i.e. without the skipped search: self0 sub0 self1 sub1 self2 sub2 up1 ... ; the
-  // layout Engine.collate documents (rows 4 / 7 / 10 / 12 = the up-sampling tables) holds for runs that build all 13 tables.)
-  const bool full_up = e->keep_taps || e->collate_only;
-  // ... and keeps the neighbour / subsampling tables, which only its own KPConv layers and shortcut pools read, in 32 bits
-  // (33 MB less written and 65 MB less read per pair; the int64 layout of the reference stays wherever a table leaves the
-  // engine: stage tensors, rdm_engine_collate, rdm_engine_forward's data_dict)
-  const bool i32 = !full_up;
-  lv[0].n = n0; lv[0].n_ref = n_ref;
-  lv[0].pts = e->alloc<float>(3 * n0);
-  lv[0].lengths = e->alloc<int64_t>(2);
-  ENG_ALLOC(lv[0].pts); ENG_ALLOC(lv[0].lengths);
-  // (latency mode: each stream stacks the clouds for itself -- lv[0] is the side stream's copy, which everything but the
-  // subsampling chain reads; that chain reads the caller's stream's own)
-  float* pts0 = lv[0].pts;
-  int64_t* len0 = lv[0].lengths;
-  if (overlap_l0) {
-    pts0 = e->alloc<float>(3 * n0);
-    len0 = e->alloc<int64_t>(2);
-    ENG_ALLOC(pts0); ENG_ALLOC(len0);
+    x = y;
+    tap(rr, name.c_str(), x);
+    if (b % 3 == 1) enc.feats[b / 3] = x;  // (blocks 1, 4, 7, 10, 13)
   }
-  if (overlap_l0) side_guard.pending++;  // (from here to the join an early return waits for the side stream)
-  ENG_CHECK(launch1d<concat_points_kernel_body, concat_points_kernel>("concat_points", 3 * n0, r.st, ref_points, n_ref, src_points, n_src, pts0, len0));
-  int64_t* all_len = e->alloc<int64_t>(8);  // device lengths of levels 1..4, contiguous for one read-back
-  ENG_ALLOC(all_len);
-  float voxel = c.init_voxel_size;
-  int64_t cap = n0;
-  // levels whose subsampling runs as the multi-launch pipeline (RDM_GS_MULTI_LEVELS, developer knob; default: the first)
-  static const int gs_multi_levels = [] { const char* v = ::rdm::dev_knob("RDM_GS_MULTI_LEVELS"); return v ? atoi(v) : 1; }();
-  std::vector<char> side_queue(radius_redo_queue_bytes());
-  for (int i = 1; i < 5; ++i) {
-    voxel *= 2.f;  // data.py:23-28
-    lv[i].pts = e->alloc<float>(3 * cap);
-    lv[i].lengths = all_len + 2 * (i - 1);
-    ENG_ALLOC(lv[i].pts);
-    // level 0 -> 1 (16-20 k points per cloud): phases spread over the GPU when the clouds are large; the later levels run at
-    // capacity `cap` with a few thousand real points: the single-workgroup kernel
-    RDM_DUP_LOOP("gs")
-    ENG_CHECK(grid_subsample_mode(i == 1 ? pts0 : lv[i - 1].pts, cap, i == 1 ? len0 : lv[i - 1].lengths, 2, voxel, lv[i].pts,
-                                  lv[i].lengths, r.ws, r.ws_bytes, r.st, i <= gs_multi_levels ? 2 : 1));
-    // capacity of the next level is unknown on the host until the read-back; run it at full capacity
-    if (i == 1 && overlap_l0) {
-      // beside that chain, on the side stream: everything that needs level 0 only.  Enqueued between the chain's first level
-      // (0.18 ms of GPU time) and the rest, so that neither stream waits for the host to get to it.
-      ENG_CHECK(launch1d<concat_points_kernel_body, concat_points_kernel>("concat_points", 3 * n0, rs.st, ref_points, n_ref, src_points, n_src, lv[0].pts,
-                         lv[0].lengths));
-      ENG_CHECK(build_level_grids(0, 1, rs.st));
-      radius_redo_queue_reset(side_queue.data());
-      ENG_CHECK(search(lv[0], grids[0], c.init_radius, c.neighbor_limits[0], nb[0], i32, side_queue.data(), rs.st));
-      ENG_CHECK(radius_redo_flush(side_queue.data(), rs.st));
-      ENG_CHECK(encoder_input(rs));
-      ENG_CHECK(encoder_blocks(rs, 0, 2));
-    }
-  }
-  int64_t host_len[8];
-  // NOTE: each level was subsampled with n_points = cap (capacity): rows beyond the true count are
-  // never read because the kernels walk `lengths`.
-  ENG_CHECK(d2h(r, all_len, sizeof(host_len), host_len));
-  if (overlap_l0) {  // host-side join (the caller's stream is idle here)
-    ENG_CHECK(wait_on(e, e->side));
-    side_guard.pending--;
-  }
-  for (int i = 1; i < 5; ++i) {
-    lv[i].n_ref = host_len[2 * (i - 1)];
-    lv[i].n = host_len[2 * (i - 1)] + host_len[2 * (i - 1) + 1];
-    res->level_sizes[i] = lv[i].n;
-    res->level_ref_sizes[i] = lv[i].n_ref;
-  }
-  res->level_sizes[0] = n0;
-  res->level_ref_sizes[0] = n_ref;
+  enc.blocks = b1;
+  return RDM_OK;
+}
 
-  float radius = c.init_radius;
-  ENG_CHECK(build_level_grids(overlap_l0 ? 1 : 0, 5));
-  for (int i = 0; i < 5; ++i) {
-    if (!(overlap_l0 && i == 0)) ENG_CHECK(search(lv[i], grids[i], radius, c.neighbor_limits[i], nb[i], i32));
-    if (i < 4) ENG_CHECK(search(lv[i + 1], grids[i], radius, c.neighbor_limits[i], sub[i], i32));
-    if (i > 0 && (full_up || i > 1)) ENG_CHECK(search(lv[i - 1], grids[i], radius, full_up ? c.neighbor_limits[i] : 1, up[i - 1]));
-    radius *= 2.f;
-  }
-  ENG_CHECK(radius_redo_flush(redo_queue.data(), r.st));
-  }  // collate
-  for (int i = 0; i < 5; ++i) {
-    tap(r, ("lengths" + std::to_string(i)).c_str(), lv[i].lengths, 1, 2, 2, 1);
-    tap(r, ("points" + std::to_string(i)).c_str(), lv[i].pts, lv[i].n, 3, 3, 0);
-    tap(r, ("neighbors" + std::to_string(i)).c_str(), nb[i].idx, nb[i].rows, nb[i].width, nb[i].stride(), 1);
-    if (i < 4) {
-      tap(r, ("subsampling" + std::to_string(i)).c_str(), sub[i].idx, sub[i].rows, sub[i].width, sub[i].stride(), 1);
-      tap(r, ("upsampling" + std::to_string(i)).c_str(), up[i].idx, up[i].rows, up[i].width, up[i].stride(), 1);
-    }
-  }
+struct Coarse {  // transformer 1 and the n2p head (model_infer.py:146-160)
+  Mat buf;                // [Nc, D + 1]: the features, then the n2p logit (the decoder's coarse input)
+  Mat x;                  // buf's features
+  float* n2p = nullptr;   // sigmoid of the logit: runs that keep their stage tensors only
+};
 
-  tap(r, "search_flags", flags, 32, 2, 2, 3);  // per search: [max neighbour count, status] (int32)
-  if (e->collate_only) {
-    res->arena_used = e->arena_off;
-    return RDM_OK;
-  }
-
-  // kernel scratch of the network part, sized from the actual pyramid: Linear+GroupNorm of level l is at most
-  // lv[l].n rows x (init_dim * 2^(l+1)) columns (backbone.py:27-70); the decoder and heads are narrower
-  {
-    size_t need = r.ws_bytes;
-    for (int l = 0; l < c.num_stages; ++l)
-      need = std::max(need, rdm_linear_group_norm_workspace_bytes(lv[l].n, int64_t(128) << l));
-    if (need > r.ws_bytes) {
-      r.ws_bytes = need;
-      r.ws = e->alloc<char>(r.ws_bytes);
-      ENG_ALLOC(r.ws);
-    }
-  }
-
-  // ---------------------------------------------------------------- encoder (the callables above)
-  if (!overlap_l0) {
-    ENG_CHECK(encoder_input(r));
-    ENG_CHECK(encoder_blocks(r, 0, 14));
-  } else {
-    ENG_CHECK(encoder_blocks(r, 2, 14));  // (input and blocks 0-1 ran on the side stream beside the subsampling)
-  }
-  const int64_t Nc = lv[4].n, nc_ref = lv[4].n_ref, Nf = lv[1].n, nf_ref = lv[1].n_ref;
-  const int64_t D = c.out_dim;  // 256
-  tap(r, "feats_c_enc", feats[4]);
-
-  // ---------------------------------------------------------------- transformer #1 + heads
+int transformer1(Run& r, const PairPyramid& py, const Mat& feats4, Coarse& co) {
+  rdm_engine* e = r.e;
+  const rdm_engine_config& c = e->cfg;
+  const int64_t Nc = py.lv[4].n, D = c.out_dim;
   Mat pts_c4{e->alloc<float>(4 * (Nc > 0 ? Nc : 1)), Nc, 4, 4};
   ENG_ALLOC(pts_c4.p);
-  ENG_CHECK(launch1d<pad_points_kernel_body, pad_points_kernel>("pad_points", Nc, r.st, lv[4].pts, Nc, pts_c4.p));
-  Mat buf_c = e->mat(Nc, D + 1);
-  ENG_ALLOC(buf_c.p);
-  Mat x_c = buf_c.cols_from(0, D);
-  ENG_CHECK(thdroformer(r, "transformer", pts_c4, feats[4], nc_ref, c.num_layers, x_c));
-  tap(r, "t1", x_c);
-  Mat n2p_logit = buf_c.cols_from(D, 1);
-  ENG_CHECK(linear(r, "proj_n2p_score", x_c, n2p_logit, 0, false));
+  ENG_CHECK(launch1d<pad_points_kernel_body, pad_points_kernel>("pad_points", Nc, r.st, py.lv[4].pts, Nc, pts_c4.p));
+  co.buf = e->mat(Nc, D + 1);
+  ENG_ALLOC(co.buf.p);
+  co.x = co.buf.cols_from(0, D);
+  ENG_CHECK(thdroformer(r, "transformer", pts_c4, feats4, py.lv[4].n_ref, c.num_layers, co.x));
+  tap(r, "t1", co.x);
+  Mat n2p_logit = co.buf.cols_from(D, 1);
+  ENG_CHECK(linear(r, "proj_n2p_score", co.x, n2p_logit, 0, false));
   // The three score heads' sigmoids (and the n2n projection) feed output tensors only (model_infer.py:160-236: `n2p_scores`,
   // `p2p_scores`, `node_scores`; the n2p LOGIT is an input of the decoder and stays): a plain run, which hands out no stage
   // tensors, skips those four launches.
-  const bool want_scores = e->keep_taps;
-  float* n2p = nullptr;
-  if (want_scores) {
-    n2p = e->alloc<float>(Nc);
-    ENG_ALLOC(n2p);
-    ENG_CHECK(rdm_sigmoid_column(n2p_logit.p, n2p_logit.ld, Nc, n2p, r.st));
-    tap(r, "n2p_scores", n2p, Nc, 1, 1, 0);
+  if (e->keep_taps) {
+    co.n2p = e->alloc<float>(Nc);
+    ENG_ALLOC(co.n2p);
+    ENG_CHECK(rdm_sigmoid_column(n2p_logit.p, n2p_logit.ld, Nc, co.n2p, r.st));
+    tap(r, "n2p_scores", co.n2p, Nc, 1, 1, 0);
   }
+  return RDM_OK;
+}
 
-  // ---------------------------------------------------------------- decoder (backbone.py:118-151)
-  // Latency mode: the three wide GEMMs of the decoder run on the side stream beside the chain of small launches of the second
-  // transformer, the grouping and the coarse matching (~80 launches of a few workgroups each).  Fork and join sit at read-backs
-  // the host performs anyway (the NMS survivor counts, the coarse matching's correspondence count): once the host has seen the
-  // caller's stream idle, the side stream needs no device-side dependency on it, and the join is a host wait on the side
-  // stream next to the one on the caller's stream -- a device-side event pair between two busy streams costs ~0.15 ms per
-  // pair here (tools/overlap_probe.py, tools/xsync_probe.hip), more than the overlap wins.
-  Mat dec, feats_f;
-  float* p2p = nullptr;
-  auto run_decoder = [&](Run& rd) -> int {
-    const std::string n4 = "decoder.decoder4.norm.norm", n3 = "decoder.decoder3.norm.norm";
-    Mat l4, l3;
-    ENG_CHECK(decoder_stage(rd, "decoder.decoder4.mlp", &n4, buf_c, up[3].idx, up[3].stride(), feats[3], lv[3].n, l4));
-    ENG_CHECK(decoder_stage(rd, "decoder.decoder3.mlp", &n3, l4, up[2].idx, up[2].stride(), feats[2], lv[2].n, l3));
-    ENG_CHECK(decoder_stage(rd, "decoder.decoder2.mlp", nullptr, l3, up[1].idx, up[1].stride(), feats[1], lv[1].n, dec));
-    tap(r, "decoder", dec);
-    feats_f = dec.cols_from(0, D);
-    if (want_scores) {
-      p2p = e->alloc<float>(Nf);
-      ENG_ALLOC(p2p);
-      ENG_CHECK(rdm_sigmoid_column(dec.p + D, dec.ld, Nf, p2p, rd.st));
-      tap(r, "p2p_scores", p2p, Nf, 1, 1, 0);
+// backbone.py:118-151: dec = [fine features (D) | p2p logit] of level 1
+int decoder(Run& rd, const PairPyramid& py, const Mat& coarse, const Mat* feats, Mat& dec) {
+  rdm_engine* e = rd.e;
+  const int64_t D = e->cfg.out_dim, Nf = py.lv[1].n;
+  const std::string n4 = "decoder.decoder4.norm.norm", n3 = "decoder.decoder3.norm.norm";
+  Mat l4, l3;
+  ENG_CHECK(decoder_stage(rd, "decoder.decoder4.mlp", &n4, coarse, py.up[3].idx, py.up[3].stride(), feats[3], py.lv[3].n, l4));
+  ENG_CHECK(decoder_stage(rd, "decoder.decoder3.mlp", &n3, l4, py.up[2].idx, py.up[2].stride(), feats[2], py.lv[2].n, l3));
+  ENG_CHECK(decoder_stage(rd, "decoder.decoder2.mlp", nullptr, l3, py.up[1].idx, py.up[1].stride(), feats[1], Nf, dec));
+  tap(rd, "decoder", dec);
+  if (e->keep_taps) {
+    float* p2p = e->alloc<float>(Nf);
+    ENG_ALLOC(p2p);
+    ENG_CHECK(rdm_sigmoid_column(dec.p + D, dec.ld, Nf, p2p, rd.st));
+    tap(rd, "p2p_scores", p2p, Nf, 1, 1, 0);
+  }
+  return RDM_OK;
+}
+
+// the status words of the pair's first `calls` searches, read back: a failed search is a capacity error of the run
+int check_searches(const int32_t* host_flags, int calls) {
+  for (int i = 0; i < 2 * calls; i += 2)
+    if (host_flags[i + 1] != 0) {
+      set_error("rdm_engine_run: a radius search failed (status %d: 2 = grid built for a smaller radius)", host_flags[i + 1]);
+      return RDM_ERR_CAPACITY;
     }
-    return RDM_OK;
-  };
-  auto fork_decoder = [&]() -> int {  // after a host wait on the caller's stream: what the decoder reads was complete then, and nothing enqueued since writes it
-    Run rd = r;
-    rd.st = e->side;
-    rd.ws = nullptr; rd.ws_bytes = 0;  // (decoder_stage then takes its scratch from the arena: r.ws belongs to the caller's stream)
-    side_guard.pending++;
-    return run_decoder(rd);
-  };
-  if (!overlap) ENG_CHECK(run_decoder(r));
+  return RDM_OK;
+}
 
-  int64_t m_r = 0, m_s = 0, Mn = 0;
-  float* nodes = nullptr;
+struct Superpoints {  // the superpoints after vote and NMS, their features after transformer 2, normalised
+  int64_t m_r = 0, m_s = 0;
+  float* nodes = nullptr;  // [m_r + m_s, 3]
+  Mat feats;
+};
+
+// vote (vote.py:83-117), NMS (vote.py:13-40), the survivors' rows, transformer 2 and the normalisation.  `fork` (latency mode)
+// starts the decoder on the side stream once the host has read the NMS counts back.
+int superpoints(Run& r, const PairPyramid& py, const Coarse& co, const std::function<int()>* fork, Superpoints& sp) {
+  rdm_engine* e = r.e;
+  const rdm_engine_config& c = e->cfg;
+  const int64_t Nc = py.lv[4].n, nc_ref = py.lv[4].n_ref, D = c.out_dim;
+  const bool want_scores = e->keep_taps;
+  int64_t Mn = 0;
   Mat buf2;
   if (c.use_vote) {
-    // ---------------------------------------------------------------- vote (vote.py:83-117)
-    Mat h = x_c;
+    Mat h = co.x;
     for (int i = 0; i < c.vote_mlp_layers; ++i) {
       Mat t1, t2;
       ENG_CHECK(linear(r, "vote.mlp_modules." + std::to_string(3 * i), h, t1));
@@ -1868,9 +1590,9 @@ static int engine_run_once(rdm_engine* e, const float* ref_points, int64_t n_ref
     ENG_CHECK(linear(r, "vote.ctr_reg", h, off));
     float* shifted = e->alloc<float>(3 * (Nc > 0 ? Nc : 1));
     ENG_ALLOC(shifted);
-    ENG_CHECK(rdm_vote_shift(lv[4].pts, off.p, off.ld, Nc, c.vote_limit[0], c.vote_limit[1], c.vote_limit[2], shifted, r.st));
+    ENG_CHECK(rdm_vote_shift(py.lv[4].pts, off.p, off.ld, Nc, c.vote_limit[0], c.vote_limit[1], c.vote_limit[2], shifted, r.st));
     Mat off_f = off.cols_from(3, D), vfeats;
-    ENG_CHECK(layer_norm(r, "vote.out_proj.0", x_c, &off_f, 0, vfeats));
+    ENG_CHECK(layer_norm(r, "vote.out_proj.0", co.x, &off_f, 0, vfeats));
     tap(r, "vote_xyz", shifted, Nc, 3, 3, 0);
     tap(r, "vote_feats", vfeats);
     float* n2n = nullptr;
@@ -1882,43 +1604,40 @@ static int engine_run_once(rdm_engine* e, const float* ref_points, int64_t n_ref
       ENG_CHECK(rdm_sigmoid_column(n2n_logit.p, n2n_logit.ld, Nc, n2n, r.st));
     }
 
-    // ---------------------------------------------------------------- NMS (vote.py:13-40)
+    // NMS: a radius search among the shifted superpoints, recorded as the status row after the collate's
     Level nodes_all;
-    nodes_all.pts = shifted; nodes_all.n = Nc; nodes_all.lengths = lv[4].lengths; nodes_all.n_ref = nc_ref;
+    nodes_all.pts = shifted; nodes_all.n = Nc; nodes_all.lengths = py.lv[4].lengths; nodes_all.n_ref = nc_ref;
     Table nms_t;
     Grid nms_grid;
+    nms_grid.n_s = Nc;
+    nms_grid.bytes = rdm_radius_grid_workspace_bytes(Nc);
+    nms_grid.ws = e->alloc<char>(nms_grid.bytes);
+    ENG_ALLOC(nms_grid.ws);
     if (Nc <= 4096) {  // a few hundred superpoints: one cell per cloud (brute force) in one launch instead of the grid's seven
-      nms_grid.n_s = Nc;
-      nms_grid.bytes = rdm_radius_grid_workspace_bytes(Nc);
-      nms_grid.ws = e->alloc<char>(nms_grid.bytes);
-      ENG_ALLOC(nms_grid.ws);
-      ENG_CHECK(radius_grid_build_trivial(shifted, Nc, lv[4].lengths, 2, nms_grid.ws, nms_grid.bytes, r.st));
+      ENG_CHECK(radius_grid_build_trivial(shifted, Nc, py.lv[4].lengths, 2, nms_grid.ws, nms_grid.bytes, r.st));
     } else {
-      ENG_CHECK(build_grid(nodes_all, c.nms_radius, nms_grid));
+      ENG_CHECK(rdm_radius_grid_build(shifted, Nc, py.lv[4].lengths, 2, c.nms_radius, nms_grid.ws, nms_grid.bytes, r.st));
     }
-    ENG_CHECK(search(nodes_all, nms_grid, c.nms_radius, c.neighbor_limits[4], nms_t));
-    ENG_CHECK(radius_redo_flush(redo_queue.data(), r.st));  // (searches are recorded and run at the flush)
+    SearchQueue sq(r.st);
+    ENG_CHECK(search(e, sq, nodes_all, nms_grid, c.nms_radius, c.neighbor_limits[4], false, py.flags + 2 * py.calls, nms_t));
+    ENG_CHECK(sq.flush());
     uint8_t* keep = e->alloc<uint8_t>(Nc > 0 ? Nc : 1);
     ENG_ALLOC(keep);
     ENG_CHECK(rdm_nms(nms_t.idx, Nc, nms_t.width, nms_t.width, nms_t.flags, keep, r.st));
     tap(r, "nms_mask", keep, Nc, 1, 1, 2);
     int32_t* order = e->alloc<int32_t>(Nc > 0 ? Nc : 1);
-    int32_t* kept = flags + 60;  // [2]
+    int32_t* kept = py.flags + 60;  // [2]
     ENG_ALLOC(order);
     // both clouds' compactions in one launch, which also stores the status words into the mapped read-back buffer
-    ENG_CHECK(compact_indices_pair(keep, nc_ref, Nc, order, kept, flags, static_cast<int32_t*>(e->pinned_dev), 64, r.st));
+    ENG_CHECK(compact_indices_pair(keep, nc_ref, Nc, order, kept, py.flags, static_cast<int32_t*>(e->pinned_dev), 64, r.st));
     int32_t host_flags[64];
     ENG_CHECK(wait_stream(r));
     std::memcpy(host_flags, e->pinned, sizeof(host_flags));
-    for (int i = 0; i < 2 * call; i += 2)
-      if (host_flags[i + 1] != 0) {
-        set_error("rdm_engine_run: a radius search failed (status %d: 2 = grid built for a smaller radius)", host_flags[i + 1]);
-        return RDM_ERR_CAPACITY;
-      }
-    m_r = host_flags[60]; m_s = host_flags[61]; Mn = m_r + m_s;
-    RDM_REQUIRE(m_r > 0 && m_s > 0, "rdm_engine_run: NMS left no superpoints");
-    nodes = e->alloc<float>(3 * Mn);
-    ENG_ALLOC(nodes);
+    ENG_CHECK(check_searches(host_flags, py.calls + 1));
+    sp.m_r = host_flags[60]; sp.m_s = host_flags[61]; Mn = sp.m_r + sp.m_s;
+    RDM_REQUIRE(sp.m_r > 0 && sp.m_s > 0, "rdm_engine_run: NMS left no superpoints");
+    sp.nodes = e->alloc<float>(3 * Mn);
+    ENG_ALLOC(sp.nodes);
     Mat sel_feats = e->mat(Mn, D);
     ENG_ALLOC(sel_feats.p);
     // (the (n2p, n2n) score pairs exist only in runs that hand out stage tensors: a plain run skips the score heads, and a
@@ -1929,116 +1648,119 @@ static int engine_run_once(rdm_engine* e, const float* ref_points, int64_t n_ref
     ENG_ALLOC(nodes4.p);
     {  // the survivors' rows of every per-superpoint tensor with one launch
       SelectNodesArgs sa;
-      sa.order = order; sa.nc_ref = static_cast<int>(nc_ref); sa.m_r = static_cast<int>(m_r); sa.m_n = static_cast<int>(Mn);
-      sa.xyz = shifted; sa.feats = vfeats.p; sa.n2p = n2p; sa.n2n = n2n;
+      sa.order = order; sa.nc_ref = static_cast<int>(nc_ref); sa.m_r = static_cast<int>(sp.m_r); sa.m_n = static_cast<int>(Mn);
+      sa.xyz = shifted; sa.feats = vfeats.p; sa.n2p = co.n2p; sa.n2n = n2n;
       sa.d = static_cast<int>(D); sa.ldf = static_cast<int>(vfeats.ld); sa.ldo = static_cast<int>(sel_feats.ld);
-      sa.nodes = nodes; sa.nodes4 = nodes4.p; sa.out_feats = sel_feats.p; sa.scores = sel_scores;
+      sa.nodes = sp.nodes; sa.nodes4 = nodes4.p; sa.out_feats = sel_feats.p; sa.scores = sel_scores;
       ::rdm::launch<select_nodes_kernel_body, select_nodes_kernel, 64>(dim3(static_cast<unsigned>(Mn)), 0, r.st, sa);
       ENG_CHECK(launch_status("select_nodes_kernel"));
     }
-    tap(r, "nodes", nodes, Mn, 3, 3, 0);
+    tap(r, "nodes", sp.nodes, Mn, 3, 3, 0);
     if (want_scores) tap(r, "node_scores", sel_scores, Mn, 2, 2, 0);
 
-    // ---------------------------------------------------------------- transformer #2, normalise
+    // transformer #2 (latency mode: the decoder is forked once its first two layers are enqueued -- everything the decoder reads
+    // was complete at the read-back above, and the host's 12 launches for it then do not hold up this chain)
     buf2 = e->mat(Mn, D);
     ENG_ALLOC(buf2.p);
-    // (latency mode: the decoder is forked once the first two layers are enqueued -- everything it reads was complete at the
-    // read-back above, and the host's 12 launches for it then do not hold up this chain)
-    const std::function<int()> fork = fork_decoder;
-    ENG_CHECK(thdroformer(r, "transformer2", nodes4, sel_feats, m_r, c.num_layers2, buf2, overlap ? &fork : nullptr));
-    if (overlap && 2 * c.num_layers2 < 2) ENG_CHECK(fork_decoder());
+    ENG_CHECK(thdroformer(r, "transformer2", nodes4, sel_feats, sp.m_r, c.num_layers2, buf2, fork));
+    if (fork && 2 * c.num_layers2 < 2) ENG_CHECK((*fork)());
     tap(r, "t2", buf2);
   } else {
     // infer.py:119-120 (Mulran) switches the vote layer off and model_infer.py:179-246 then leaves the
     // superpoints undefined; defined as the un-shifted coarse points with the first transformer's features
     int32_t host_flags[64];
-    ENG_CHECK(d2h(r, flags, sizeof(host_flags), host_flags));
-    for (int i = 0; i < 2 * call; i += 2)
-      if (host_flags[i + 1] != 0) {
-        set_error("rdm_engine_run: a radius search failed (status %d: 2 = grid built for a smaller radius)", host_flags[i + 1]);
-        return RDM_ERR_CAPACITY;
-      }
-    m_r = nc_ref; m_s = Nc - nc_ref; Mn = Nc;
-    RDM_REQUIRE(m_r > 0 && m_s > 0, "rdm_engine_run: a cloud has no superpoints");
-    if (overlap) ENG_CHECK(fork_decoder());
-    nodes = const_cast<float*>(lv[4].pts);
-    buf2 = x_c;
-    tap(r, "nodes", nodes, Mn, 3, 3, 0);
+    ENG_CHECK(d2h(r, py.flags, sizeof(host_flags), host_flags));
+    ENG_CHECK(check_searches(host_flags, py.calls));
+    sp.m_r = nc_ref; sp.m_s = Nc - nc_ref; Mn = Nc;
+    RDM_REQUIRE(sp.m_r > 0 && sp.m_s > 0, "rdm_engine_run: a cloud has no superpoints");
+    if (fork) ENG_CHECK((*fork)());
+    sp.nodes = const_cast<float*>(py.lv[4].pts);
+    buf2 = co.x;
+    tap(r, "nodes", sp.nodes, Mn, 3, 3, 0);
   }
-  Mat fn = e->mat(Mn, D);
-  ENG_ALLOC(fn.p);
-  ENG_CHECK(rdm_l2_normalize(buf2.p, buf2.ld, Mn, D, fn.p, fn.ld, r.st));
-  tap(r, "feats_c", fn);
+  sp.feats = e->mat(Mn, D);
+  ENG_ALLOC(sp.feats.p);
+  ENG_CHECK(rdm_l2_normalize(buf2.p, buf2.ld, Mn, D, sp.feats.p, sp.feats.ld, r.st));
+  tap(r, "feats_c", sp.feats);
+  return RDM_OK;
+}
 
-  // ---------------------------------------------------------------- grouping + coarse matching
+struct CoarseMatching {  // the grouping (point_to_node) and the superpoint correspondences
+  int64_t *r_knn = nullptr, *s_knn = nullptr;  // [m, K] patches: indices into the cloud's fine points
+  uint8_t *r_km = nullptr, *s_km = nullptr;    // [m, K] patch masks
+  uint8_t *r_nm = nullptr, *s_nm = nullptr;    // [m] node masks
+  int64_t *r_sel = nullptr, *s_sel = nullptr;  // [num_correspondences] selected superpoint pairs (count: flags[63])
+  float* node_sc = nullptr;
+};
+
+// grouping (model_infer.py:248-268) + coarse matching (model_infer.py:270-290); the counts land in flags[62..63]
+int coarse_matching(Run& r, const PairPyramid& py, const Superpoints& sp, CoarseMatching& cm) {
+  rdm_engine* e = r.e;
+  const rdm_engine_config& c = e->cfg;
   const int K = c.points_in_patch;
-  const float* pf_ref = lv[1].pts;
-  const float* pf_src = lv[1].pts + 3 * nf_ref;
-  const int64_t nf_src = Nf - nf_ref;
-  int64_t* r_knn = e->alloc<int64_t>(m_r * K);
-  int64_t* s_knn = e->alloc<int64_t>(m_s * K);
-  uint8_t* r_km = e->alloc<uint8_t>(m_r * K);
-  uint8_t* s_km = e->alloc<uint8_t>(m_s * K);
-  uint8_t* r_nm = e->alloc<uint8_t>(m_r);
-  uint8_t* s_nm = e->alloc<uint8_t>(m_s);
-  ENG_ALLOC(r_knn); ENG_ALLOC(s_knn); ENG_ALLOC(r_km); ENG_ALLOC(s_km); ENG_ALLOC(r_nm); ENG_ALLOC(s_nm);
-  int32_t* p2n_status = flags + 62;
+  const int64_t m_r = sp.m_r, m_s = sp.m_s, D = c.out_dim;
+  const int64_t Nf = py.lv[1].n, nf_ref = py.lv[1].n_ref, nf_src = Nf - nf_ref;
+  const float* pf_ref = py.lv[1].pts;
+  const float* pf_src = py.lv[1].pts + 3 * nf_ref;
+  cm.r_knn = e->alloc<int64_t>(m_r * K);
+  cm.s_knn = e->alloc<int64_t>(m_s * K);
+  cm.r_km = e->alloc<uint8_t>(m_r * K);
+  cm.s_km = e->alloc<uint8_t>(m_s * K);
+  cm.r_nm = e->alloc<uint8_t>(m_r);
+  cm.s_nm = e->alloc<uint8_t>(m_s);
+  ENG_ALLOC(cm.r_knn); ENG_ALLOC(cm.s_knn); ENG_ALLOC(cm.r_km); ENG_ALLOC(cm.s_km); ENG_ALLOC(cm.r_nm); ENG_ALLOC(cm.s_nm);
+  int32_t* p2n_status = py.flags + 62;
   RDM_DUP_LOOP("p2n")
-  ENG_CHECK(rdm_point_to_node_pair(pf_ref, nf_ref, nodes, m_r, pf_src, nf_src, nodes + 3 * m_r, m_s, K, r_knn, r_km, r_nm, s_knn,
-                                   s_km, s_nm, p2n_status, r.ws, r.ws_bytes, r.st));  // both clouds, one set of launches
+  ENG_CHECK(rdm_point_to_node_pair(pf_ref, nf_ref, sp.nodes, m_r, pf_src, nf_src, sp.nodes + 3 * m_r, m_s, K, cm.r_knn, cm.r_km,
+                                   cm.r_nm, cm.s_knn, cm.s_km, cm.s_nm, p2n_status, r.ws, r.ws_bytes, r.st));  // both clouds, one set of launches
   {  // (kept for rdm_engine_gt_node_correspondences; valid once the run completes)
     rdm_engine::GtInputs& g = e->gt;
-    g.nodes[0] = nodes; g.nodes[1] = nodes + 3 * m_r;
+    g.nodes[0] = sp.nodes; g.nodes[1] = sp.nodes + 3 * m_r;
     g.m[0] = m_r; g.m[1] = m_s;
     g.pf[0] = pf_ref; g.pf[1] = pf_src;
     g.nf[0] = nf_ref; g.nf[1] = nf_src;
-    g.knn[0] = r_knn; g.knn[1] = s_knn;
-    g.km[0] = r_km; g.km[1] = s_km;
-    g.nm[0] = r_nm; g.nm[1] = s_nm;
+    g.knn[0] = cm.r_knn; g.knn[1] = cm.s_knn;
+    g.km[0] = cm.r_km; g.km[1] = cm.s_km;
+    g.nm[0] = cm.r_nm; g.nm[1] = cm.s_nm;
     g.k = K;
   }
-  tap(r, "ref_node_masks", r_nm, m_r, 1, 1, 2);  // (the grouping: what the per-op mirror's taps hold under the same names)
-  tap(r, "src_node_masks", s_nm, m_s, 1, 1, 2);
-  tap(r, "ref_knn", r_knn, m_r, K, K, 1);
-  tap(r, "src_knn", s_knn, m_s, K, K, 1);
-  tap(r, "ref_knn_masks", r_km, m_r, K, K, 2);
-  tap(r, "src_knn_masks", s_km, m_s, K, K, 2);
+  tap(r, "ref_node_masks", cm.r_nm, m_r, 1, 1, 2);  // (the grouping: what the per-op mirror's taps hold under the same names)
+  tap(r, "src_node_masks", cm.s_nm, m_s, 1, 1, 2);
+  tap(r, "ref_knn", cm.r_knn, m_r, K, K, 1);
+  tap(r, "src_knn", cm.s_knn, m_s, K, K, 1);
+  tap(r, "ref_knn_masks", cm.r_km, m_r, K, K, 2);
+  tap(r, "src_knn_masks", cm.s_km, m_s, K, K, 2);
   const int kc = c.num_correspondences;
-  int64_t* r_sel = e->alloc<int64_t>(kc);
-  int64_t* s_sel = e->alloc<int64_t>(kc);
-  float* node_sc = e->alloc<float>(kc);
-  int32_t* n_sel = flags + 63;
-  ENG_ALLOC(r_sel); ENG_ALLOC(s_sel); ENG_ALLOC(node_sc);
-  {
-    void* cm_ws = r.ws;
-    size_t cm_bytes = rdm_coarse_matching_features_workspace_bytes(m_r, m_s);  // 12 B per superpoint pair
-    if (cm_bytes > r.ws_bytes) {  // thousands of superpoints per cloud (very sparse input)
-      cm_ws = e->alloc<char>(cm_bytes);
-      ENG_ALLOC(cm_ws);
-    } else {
-      cm_bytes = r.ws_bytes;
-    }
-    RDM_DUP_LOOP("coarse")
-  ENG_CHECK(rdm_coarse_matching_features(fn.p, fn.ld, m_r, fn.p + m_r * fn.ld, fn.ld, m_s, D, r_nm, s_nm,
-                                           c.dual_normalization, kc, r_sel, s_sel, node_sc, n_sel, cm_ws, cm_bytes, r.st));
+  cm.r_sel = e->alloc<int64_t>(kc);
+  cm.s_sel = e->alloc<int64_t>(kc);
+  cm.node_sc = e->alloc<float>(kc);
+  int32_t* n_sel = py.flags + 63;
+  ENG_ALLOC(cm.r_sel); ENG_ALLOC(cm.s_sel); ENG_ALLOC(cm.node_sc);
+  void* cm_ws = r.ws;
+  size_t cm_bytes = rdm_coarse_matching_features_workspace_bytes(m_r, m_s);  // 12 B per superpoint pair
+  if (cm_bytes > r.ws_bytes) {  // thousands of superpoints per cloud (very sparse input)
+    cm_ws = e->alloc<char>(cm_bytes);
+    ENG_ALLOC(cm_ws);
+  } else {
+    cm_bytes = r.ws_bytes;
   }
-  int32_t tail[2];
-  ENG_CHECK(d2h(r, flags + 62, sizeof(tail), tail));
-  if (overlap) {  // host-side join: the fine features are read from here on
-    ENG_CHECK(wait_on(e, e->side));
-    side_guard.pending--;
-  }
-  if (tail[0] != 0) {
-    set_error("rdm_engine_run: a superpoint owns more than 4096 points");
-    return RDM_ERR_CAPACITY;
-  }
-  const int64_t B = tail[1];
-  RDM_REQUIRE(B > 0, "rdm_engine_run: no superpoint correspondences");
-  tap(r, "ref_node_corr_indices", r_sel, B, 1, 1, 1);
-  tap(r, "src_node_corr_indices", s_sel, B, 1, 1, 1);
-  tap(r, "node_corr_scores", node_sc, B, 1, 1, 0);
+  const Mat& fn = sp.feats;
+  RDM_DUP_LOOP("coarse")
+  ENG_CHECK(rdm_coarse_matching_features(fn.p, fn.ld, m_r, fn.p + m_r * fn.ld, fn.ld, m_s, D, cm.r_nm, cm.s_nm,
+                                         c.dual_normalization, kc, cm.r_sel, cm.s_sel, cm.node_sc, n_sel, cm_ws, cm_bytes, r.st));
+  return RDM_OK;
+}
 
-  // ---------------------------------------------------------------- patches, Sinkhorn, LGR
+// patches, Sinkhorn, LGR (model_infer.py:292-354) on the B superpoint correspondences, and the pair's result read back
+int fine_matching(Run& r, const PairPyramid& py, const Superpoints& sp, const CoarseMatching& cm, const Mat& feats_f, int64_t B,
+                  rdm_engine_result* res) {
+  rdm_engine* e = r.e;
+  const rdm_engine_config& c = e->cfg;
+  const int K = c.points_in_patch;
+  const int64_t m_r = sp.m_r, m_s = sp.m_s, D = c.out_dim;
+  const int64_t nf_ref = py.lv[1].n_ref, nf_src = py.lv[1].n - nf_ref;
+  const float* pf_ref = py.lv[1].pts;
+  const float* pf_src = py.lv[1].pts + 3 * nf_ref;
   int64_t* r_idx = e->alloc<int64_t>(B * K);
   int64_t* s_idx = e->alloc<int64_t>(B * K);
   uint8_t* r_pm = e->alloc<uint8_t>(B * K);
@@ -2048,19 +1770,19 @@ static int engine_run_once(rdm_engine* e, const float* ref_points, int64_t n_ref
   ENG_ALLOC(r_idx); ENG_ALLOC(s_idx); ENG_ALLOC(r_pm); ENG_ALLOC(s_pm); ENG_ALLOC(r_pts); ENG_ALLOC(s_pts);
   {  // the patch gathers as two launches: (knn indices, knn masks) x (ref, src), then the points x (ref, src); the patch
      // FEATURES are gathered inside the score GEMM's operand loads (rdm_patch_scores)
-    const void* x1[4] = {r_knn, s_knn, r_km, s_km};
+    const void* x1[4] = {cm.r_knn, cm.s_knn, cm.r_km, cm.s_km};
     const int64_t ns1[4] = {m_r, m_s, m_r, m_s}, w1[4] = {2 * K, 2 * K, K / 4, K / 4}, mm1[4] = {B, B, B, B};
-    const int64_t* i1[4] = {r_sel, s_sel, r_sel, s_sel};
+    const int64_t* i1[4] = {cm.r_sel, cm.s_sel, cm.r_sel, cm.s_sel};
     void* y1[4] = {r_idx, s_idx, r_pm, s_pm};
     RDM_DUP_LOOP("rows")
-  ENG_CHECK(gather_rows_multi(4, x1, ns1, w1, w1, i1, mm1, y1, w1, r.st));
+    ENG_CHECK(gather_rows_multi(4, x1, ns1, w1, w1, i1, mm1, y1, w1, r.st));
     const void* x2[2] = {pf_ref, pf_src};
     const int64_t ns2[2] = {nf_ref, nf_src}, w2[2] = {3, 3}, lx2[2] = {3, 3};
     const int64_t mm2[2] = {B * K, B * K};
     const int64_t* i2[2] = {r_idx, s_idx};
     void* y2[2] = {r_pts, s_pts};
     RDM_DUP_LOOP("rows")
-  ENG_CHECK(gather_rows_multi(2, x2, ns2, w2, lx2, i2, mm2, y2, w2, r.st));
+    ENG_CHECK(gather_rows_multi(2, x2, ns2, w2, lx2, i2, mm2, y2, w2, r.st));
   }
   float* sqrt_c = vecp(r, "__sqrt_out_dim");  // [K] x sqrt(D): the einsum's divisor (model_infer.py:311), uploaded at finalize
   float* scores = e->alloc<float>(B * K * K);
@@ -2107,8 +1829,8 @@ static int engine_run_once(rdm_engine* e, const float* ref_points, int64_t n_ref
                      reinterpret_cast<float*>(static_cast<char*>(e->pinned_dev) + 4096), static_cast<int>(e->host_corr_cap));
   ENG_CHECK(launch_status("export_result_kernel"));
   ENG_CHECK(wait_stream(r));
-  std::memcpy(tailbuf.T, r.e->pinned, 64);
-  std::memcpy(tailbuf.counts, static_cast<char*>(r.e->pinned) + 64, 12);
+  std::memcpy(tailbuf.T, e->pinned, 64);
+  std::memcpy(tailbuf.counts, static_cast<char*>(e->pinned) + 64, 12);
   std::memcpy(res->transform, tailbuf.T, 64);
   res->n_correspondences = tailbuf.counts[0];
   res->n_hypotheses = tailbuf.counts[1];
@@ -2136,6 +1858,254 @@ static int engine_run_once(rdm_engine* e, const float* ref_points, int64_t n_ref
   tap(r, "src_corr_points", sc, res->n_correspondences, 3, 3, 0);
   tap(r, "corr_scores", cs, res->n_correspondences, 1, 1, 0);
   tap(r, "estimated_transform", T, 4, 4, 4, 0);
+  return RDM_OK;
+}
+
+// ---------------------------------------------------------------- the three sources of a pair's pyramid
+// The caller's data_dict (model_infer.py:113-131): its tables, the level grids (no grids of the caller's: the spatial query
+// order of the encoder's kernels needs them -- the same grids the per-op mirror builds, rdmnet_amd/model.py: run_encoder, so
+// both give the same GroupNorm partials) and the caller's collate status words ORed into one status row.
+int pyramid_from_data_dict(Run& r, const rdm_data_dict& dd, PairPyramid& py) {
+  rdm_engine* e = r.e;
+  py.flags = e->alloc<int32_t>(64);
+  ENG_ALLOC(py.flags);
+  fill_words<int32_t>(py.flags, 64, 0, r.st);
+  auto table = [](const int64_t* idx, int64_t rows, int64_t width, int64_t ld, const int32_t* flags) {
+    Table t;
+    t.idx = const_cast<int64_t*>(idx); t.rows = rows; t.width = width; t.ld = ld; t.flags = const_cast<int32_t*>(flags);
+    return t;
+  };
+  for (int i = 0; i < 5; ++i) {
+    Level& l = py.lv[i];
+    l.pts = const_cast<float*>(dd.points[i]);
+    l.n = dd.n_points[i];
+    l.n_ref = dd.n_ref[i];
+    l.lengths = const_cast<int64_t*>(dd.lengths[i]);
+    py.nb[i] = table(dd.neighbors[i], l.n, dd.neighbors_width[i], dd.neighbors_ld[i], dd.neighbors_count[i]);
+  }
+  for (int i = 0; i < 4; ++i) {
+    py.sub[i] = table(dd.subsampling[i], py.lv[i + 1].n, dd.subsampling_width[i], dd.subsampling_ld[i], dd.subsampling_count[i]);
+    py.up[i] = table(dd.upsampling[i], py.lv[i].n, dd.upsampling_width[i], dd.upsampling_ld[i], dd.upsampling_count[i]);
+  }
+  ENG_CHECK(build_level_grids(e, &py, 1, 0, 5, r.st));
+  if (dd.collate_status && dd.n_collate_status > 0) {  // the collate's status words join the engine's own (checked with them)
+    ::rdm::launch<or_status_kernel_body, or_status_kernel, 64>(dim3(1), 0, r.st, dd.collate_status, static_cast<int>(dd.n_collate_status),
+                       py.flags + 2 * py.calls + 1);
+    ENG_CHECK(launch_status("or_status_kernel"));
+    py.calls++;
+  }
+  return RDM_OK;
+}
+
+// The engine's own collate (data.py:13-77) of [ref; src].  `overlap`: latency mode may run the first level on the side stream,
+// and with it the encoder's input and first two blocks (into `enc`).
+int collate_pair(Run& r, bool overlap, SideGuard& side_guard, const float* ref_points, int64_t n_ref, const float* src_points,
+                 int64_t n_src, PairPyramid& py, Encoder& enc) {
+  rdm_engine* e = r.e;
+  const rdm_engine_config& c = e->cfg;
+  const int64_t n0 = n_ref + n_src;
+  Level* lv = py.lv;
+  py.flags = e->alloc<int32_t>(64);
+  ENG_ALLOC(py.flags);
+  // Latency mode, first half: the caller's stream runs the subsampling of levels 1-4 (a chain of one- and two-workgroup kernels,
+  // ~0.4 ms) while the side stream builds the first level's grid, searches its neighbours and runs the encoder's first two
+  // blocks (wide launches that need nothing but level 0).  No device-side dependency: taken only when the caller's stream is
+  // idle at the call (the inputs are then complete), and joined by a host wait next to the read-back of the level sizes.
+  bool overlap_l0 = false;
+  if (overlap) {  // (a hand-off event the caller just made the stream wait for -- dataset.PairStager -- takes it a few us)
+    const auto t_poll = std::chrono::steady_clock::now();
+    do {
+      overlap_l0 = hipStreamQuery(r.st) == hipSuccess;
+    } while (!overlap_l0 && std::chrono::steady_clock::now() - t_poll < std::chrono::microseconds(40));
+  }
+  Run rs = r;  // the side stream's launches of the first level
+  if (overlap_l0) {
+    rs.st = e->side;
+    rs.ws_bytes = std::max<size_t>(size_t(96) << 20, rdm_linear_group_norm_workspace_bytes(n0, 128));
+    rs.ws = e->alloc<char>(rs.ws_bytes);
+    ENG_ALLOC(rs.ws);
+  }
+  fill_words<int32_t>(py.flags, 64, 0, overlap_l0 ? rs.st : r.st);  // (the first searches write their status rows on that stream)
+  const bool full = e->keep_taps || e->collate_only;  // the reference's tables (search_pyramid)
+  lv[0].n = n0; lv[0].n_ref = n_ref;
+  lv[0].pts = e->alloc<float>(3 * n0);
+  lv[0].lengths = e->alloc<int64_t>(2);
+  ENG_ALLOC(lv[0].pts); ENG_ALLOC(lv[0].lengths);
+  // (latency mode: each stream stacks the clouds for itself -- lv[0] is the side stream's copy, which everything but the
+  // subsampling chain reads; that chain reads the caller's stream's own)
+  float* pts0 = lv[0].pts;
+  int64_t* len0 = lv[0].lengths;
+  if (overlap_l0) {
+    pts0 = e->alloc<float>(3 * n0);
+    len0 = e->alloc<int64_t>(2);
+    ENG_ALLOC(pts0); ENG_ALLOC(len0);
+    side_guard.pending++;  // (from here to the join an early return waits for the side stream)
+  }
+  ENG_CHECK(launch1d<concat_points_kernel_body, concat_points_kernel>("concat_points", 3 * n0, r.st, ref_points, n_ref, src_points, n_src, pts0, len0));
+  int64_t* all_len = e->alloc<int64_t>(8);  // device lengths of levels 1..4, contiguous for one read-back
+  ENG_ALLOC(all_len);
+  float voxel = c.init_voxel_size;
+  const int64_t cap = n0;
+  for (int i = 1; i < 5; ++i) {
+    voxel *= 2.f;  // data.py:23-28
+    lv[i].pts = e->alloc<float>(3 * cap);
+    lv[i].lengths = all_len + 2 * (i - 1);
+    ENG_ALLOC(lv[i].pts);
+    // level 0 -> 1 (16-20 k points per cloud): phases spread over the GPU when the clouds are large; the later levels run at
+    // capacity `cap` with a few thousand real points: the single-workgroup kernel
+    RDM_DUP_LOOP("gs")
+    ENG_CHECK(grid_subsample_mode(i == 1 ? pts0 : lv[i - 1].pts, cap, i == 1 ? len0 : lv[i - 1].lengths, 2, voxel, lv[i].pts,
+                                  lv[i].lengths, r.ws, r.ws_bytes, r.st, i <= gs_multi_levels() ? 2 : 1));
+    // capacity of the next level is unknown on the host until the read-back; run it at full capacity
+    if (i == 1 && overlap_l0) {
+      // beside that chain, on the side stream: everything that needs level 0 only.  Enqueued between the chain's first level
+      // (0.18 ms of GPU time) and the rest, so that neither stream waits for the host to get to it.
+      ENG_CHECK(launch1d<concat_points_kernel_body, concat_points_kernel>("concat_points", 3 * n0, rs.st, ref_points, n_ref, src_points, n_src, lv[0].pts,
+                         lv[0].lengths));
+      ENG_CHECK(build_level_grids(e, &py, 1, 0, 1, rs.st));
+      SearchQueue side_queue(rs.st);
+      ENG_CHECK(search(e, side_queue, lv[0], py.grids[0], c.init_radius, c.neighbor_limits[0], !full, py.flags + 2 * py.calls++,
+                       py.nb[0]));
+      ENG_CHECK(side_queue.flush());
+      ENG_CHECK(encoder_input(rs, nullptr, n0, enc));
+      ENG_CHECK(encoder_blocks(rs, py, 0, 2, enc));
+    }
+  }
+  int64_t host_len[8];
+  // NOTE: each level was subsampled with n_points = cap (capacity): rows beyond the true count are
+  // never read because the kernels walk `lengths`.
+  ENG_CHECK(d2h(r, all_len, sizeof(host_len), host_len));
+  if (overlap_l0) {  // host-side join (the caller's stream is idle here)
+    ENG_CHECK(wait_on(e, e->side));
+    side_guard.pending--;
+  }
+  for (int i = 1; i < 5; ++i) {
+    lv[i].n_ref = host_len[2 * (i - 1)];
+    lv[i].n = host_len[2 * (i - 1)] + host_len[2 * (i - 1) + 1];
+  }
+  ENG_CHECK(build_level_grids(e, &py, 1, overlap_l0 ? 1 : 0, 5, r.st));
+  SearchQueue sq(r.st);
+  ENG_CHECK(search_pyramid(e, py, full, overlap_l0, sq));
+  return sq.flush();
+}
+
+void tap_pyramid(Run& r, const PairPyramid& py) {
+  for (int i = 0; i < 5; ++i) {
+    const Level& l = py.lv[i];
+    tap(r, ("lengths" + std::to_string(i)).c_str(), l.lengths, 1, 2, 2, 1);
+    tap(r, ("points" + std::to_string(i)).c_str(), l.pts, l.n, 3, 3, 0);
+    tap(r, ("neighbors" + std::to_string(i)).c_str(), py.nb[i].idx, py.nb[i].rows, py.nb[i].width, py.nb[i].stride(), 1);
+    if (i < 4) {
+      tap(r, ("subsampling" + std::to_string(i)).c_str(), py.sub[i].idx, py.sub[i].rows, py.sub[i].width, py.sub[i].stride(), 1);
+      tap(r, ("upsampling" + std::to_string(i)).c_str(), py.up[i].idx, py.up[i].rows, py.up[i].width, py.up[i].stride(), 1);
+    }
+  }
+  tap(r, "search_flags", py.flags, 32, 2, 2, 3);  // per search: [max neighbour count, status] (int32)
+}
+
+}  // namespace
+
+// One pair: its pyramid -- a slice of a collated batch (`pre`), the caller's data_dict (`dd`) or the engine's own collate --
+// then RDMNet.forward (model_infer.py:109-354) on it.
+static int engine_run_once(rdm_engine* e, const float* ref_points, int64_t n_ref, const float* src_points, int64_t n_src,
+                           const rdm_data_dict* dd, rdm_engine_result* res, void* stream, const PairPyramid* pre) {
+  const rdm_engine_config& c = e->cfg;
+  e->arena_off = pre ? e->arena_base : 0;  // (a pair of a collated batch: its pyramid lies below arena_base)
+  e->gt.valid = false;
+  if (!pre) {
+    e->batch.clear();  // (the arena is rewritten: a collated batch is gone)
+    e->arena_base = 0;
+  }
+  e->taps.clear();
+  e->prof.clear();
+  e->prof_layers = 0;
+  Run r;
+  r.e = e; r.st = static_cast<hipStream_t>(stream); r.groups = c.group_norm;
+  const int64_t n0 = n_ref + n_src;
+  // latency mode (see rdm_engine::overlap_mode); never on the legacy null stream, which every other blocking stream serialises with
+  bool overlap = !pre && !lockstep_active() && !e->collate_only && r.st != nullptr && (e->overlap_mode == 2 || (e->overlap_mode == 1 && e->pairs_in_flight == 1));
+  if (overlap) ENG_CHECK(ensure_side(e, r.st, &overlap));
+  SideGuard side_guard{e};
+  // kernel scratch: the largest consumers are the grid-subsample tables and split-K partials
+  r.ws_bytes = pre ? size_t(96) << 20
+                   : std::max<size_t>(rdm_grid_subsample_workspace_bytes(n0, 2),
+                                      std::max<size_t>(rdm_radius_neighbors_workspace_bytes(n0, n0, 2), size_t(96) << 20));
+  r.ws = e->alloc<char>(r.ws_bytes);
+  ENG_ALLOC(r.ws);
+  std::memset(res, 0, sizeof(*res));
+
+  PairPyramid py;
+  Encoder enc;
+  if (pre) py = *pre;
+  else if (dd) ENG_CHECK(pyramid_from_data_dict(r, *dd, py));
+  else ENG_CHECK(collate_pair(r, overlap, side_guard, ref_points, n_ref, src_points, n_src, py, enc));
+  for (int i = 0; i < 5; ++i) {
+    res->level_sizes[i] = py.lv[i].n;
+    res->level_ref_sizes[i] = py.lv[i].n_ref;
+  }
+  tap_pyramid(r, py);
+  if (e->collate_only) {
+    res->arena_used = e->arena_off;
+    return RDM_OK;
+  }
+
+  // kernel scratch of the network part, sized from the actual pyramid: Linear+GroupNorm of level l is at most
+  // lv[l].n rows x (init_dim * 2^(l+1)) columns (backbone.py:27-70); the decoder and heads are narrower
+  {
+    size_t need = r.ws_bytes;
+    for (int l = 0; l < c.num_stages; ++l)
+      need = std::max(need, rdm_linear_group_norm_workspace_bytes(py.lv[l].n, int64_t(128) << l));
+    if (need > r.ws_bytes) {
+      r.ws_bytes = need;
+      r.ws = e->alloc<char>(r.ws_bytes);
+      ENG_ALLOC(r.ws);
+    }
+  }
+
+  // encoder (backbone.py:72-107; latency mode: the input and blocks 0-1 ran on the side stream during the collate)
+  if (enc.blocks == 0) ENG_CHECK(encoder_input(r, dd, n0, enc));
+  ENG_CHECK(encoder_blocks(r, py, enc.blocks, 14, enc));
+  tap(r, "feats_c_enc", enc.feats[4]);
+  Coarse co;
+  ENG_CHECK(transformer1(r, py, enc.feats[4], co));
+
+  // Decoder.  Latency mode: the three wide GEMMs of the decoder run on the side stream beside the chain of small launches of the
+  // second transformer, the grouping and the coarse matching (~80 launches of a few workgroups each).  Fork and join sit at
+  // read-backs the host performs anyway (the NMS survivor counts, the coarse matching's correspondence count): once the host has
+  // seen the caller's stream idle, the side stream needs no device-side dependency on it, and the join is a host wait on the side
+  // stream next to the one on the caller's stream -- a device-side event pair between two busy streams costs ~0.15 ms per
+  // pair here (tools/overlap_probe.py, tools/xsync_probe.hip), more than the overlap wins.
+  Mat dec;
+  // (superpoints forks it after a host wait on the caller's stream: what the decoder reads was complete then, and nothing
+  // enqueued since writes it)
+  const std::function<int()> fork_decoder = [&]() -> int {
+    Run rd = r;
+    rd.st = e->side;
+    rd.ws = nullptr; rd.ws_bytes = 0;  // (decoder_stage then takes its scratch from the arena: r.ws belongs to the caller's stream)
+    side_guard.pending++;
+    return decoder(rd, py, co.buf, enc.feats, dec);
+  };
+  if (!overlap) ENG_CHECK(decoder(r, py, co.buf, enc.feats, dec));
+  Superpoints sp;
+  ENG_CHECK(superpoints(r, py, co, overlap ? &fork_decoder : nullptr, sp));
+  CoarseMatching cm;
+  ENG_CHECK(coarse_matching(r, py, sp, cm));
+  int32_t tail[2];
+  ENG_CHECK(d2h(r, py.flags + 62, sizeof(tail), tail));
+  if (overlap) {  // host-side join: the fine features are read from here on
+    ENG_CHECK(wait_on(e, e->side));
+    side_guard.pending--;
+  }
+  if (tail[0] != 0) {
+    set_error("rdm_engine_run: a superpoint owns more than 4096 points");
+    return RDM_ERR_CAPACITY;
+  }
+  const int64_t B = tail[1];
+  RDM_REQUIRE(B > 0, "rdm_engine_run: no superpoint correspondences");
+  tap(r, "ref_node_corr_indices", cm.r_sel, B, 1, 1, 1);
+  tap(r, "src_node_corr_indices", cm.s_sel, B, 1, 1, 1);
+  tap(r, "node_corr_scores", cm.node_sc, B, 1, 1, 0);
+  ENG_CHECK(fine_matching(r, py, sp, cm, dec.cols_from(0, c.out_dim), B, res));
   e->gt.valid = true;
   return RDM_OK;
 }
