@@ -434,7 +434,11 @@ int rdm_gt_node_correspondences(const float* ref_nodes, int64_t m, const float* 
 /* ---- a14: Sinkhorn ---------------------------------------------------------------------------------
  * Replaces LearnableLogOptimalTransport.forward (geotransformer/modules/sinkhorn/
  * learnable_sinkhorn.py:13-66): scores [batch, m, n], masks [batch, m] / [batch, n] (1 = valid),
- * alpha = dustbin score (device scalar), out [batch, m+1, n+1].  m, n <= 128.                     */
+ * alpha = dustbin score (device scalar), out [batch, m+1, n+1].  m, n <= 128.  Masked entries are
+ * fl(-1e12), except where a whole side of a patch is masked, which gives the reference's values:
+ * after >= 1 iteration, no valid row -> the dustbin column is -inf (every row) and the valid entries of
+ * the dustbin row are 0; no valid column -> the mirror image; neither -> NaN everywhere (-inf everywhere
+ * with iters = 0).                                                                                 */
 int rdm_sinkhorn(const float* scores, int64_t batch, int64_t m, int64_t n, const uint8_t* row_mask,
                  const uint8_t* col_mask, const float* alpha, int iters, float* out, void* stream);
 

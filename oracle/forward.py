@@ -270,21 +270,22 @@ def coarse_matching(ref_f, src_f, ref_mask, src_mask, k, dual=True):
 
 # ----------------------------------------------------------------------------- a14: Sinkhorn
 def sinkhorn(scores, row_mask, col_mask, alpha, iters):
-    """modules/sinkhorn/learnable_sinkhorn.py:13-66."""
+    """modules/sinkhorn/learnable_sinkhorn.py:13-66, in the dtype of `scores` (the reference's is fp32; alpha must match)."""
     b, m, n = scores.shape
+    dt = scores.dtype
     prm = torch.zeros(b, m + 1, dtype=torch.bool)
     prm[:, :m] = ~row_mask
     pcm = torch.zeros(b, n + 1, dtype=torch.bool)
     pcm[:, :n] = ~col_mask
     z = torch.cat([torch.cat([scores, alpha.expand(b, m, 1)], -1), alpha.expand(b, 1, n + 1)], 1)
     z = z.masked_fill(prm[:, :, None] | pcm[:, None, :], -NEG_INF)
-    nr, nc = row_mask.float().sum(1), col_mask.float().sum(1)
+    nr, nc = row_mask.to(dt).sum(1), col_mask.to(dt).sum(1)
     norm = -torch.log(nr + nc)
-    log_mu = torch.empty(b, m + 1)
+    log_mu = torch.empty(b, m + 1, dtype=dt)
     log_mu[:, :m] = norm[:, None]
     log_mu[:, m] = torch.log(nc) + norm
     log_mu[prm] = -NEG_INF
-    log_nu = torch.empty(b, n + 1)
+    log_nu = torch.empty(b, n + 1, dtype=dt)
     log_nu[:, :n] = norm[:, None]
     log_nu[:, n] = torch.log(nr) + norm
     log_nu[pcm] = -NEG_INF

@@ -277,8 +277,9 @@ __global__ void l2_normalize_kernel(const float* x, int ldx, int n, int c, float
 extern "C" int rdm_rope(float* q, int64_t ldq, float* k, int64_t ldk, const float* emb, int64_t lde,
                         int64_t n, int64_t d_model, void* stream) {
   using namespace rdm;
-  RDM_REQUIRE(q && emb && n >= 0 && d_model % 2 == 0, "rdm_rope: bad arguments");
-  if (n == 0) return RDM_OK;
+  RDM_REQUIRE(n >= 0 && d_model % 2 == 0, "rdm_rope: bad arguments");
+  if (n == 0) return RDM_OK;  // (torch hands zero-row tensors over as null pointers)
+  RDM_REQUIRE(q && emb, "rdm_rope: null pointer");
   const int pairs = static_cast<int>(d_model / 2);
   launch<rope_body, rope_kernel, 256>(dim3(ceil_div<int64_t>(n * pairs, 256)), 0, static_cast<hipStream_t>(stream), q,
                                       static_cast<int>(ldq), k, static_cast<int>(ldk), emb, static_cast<int>(lde), static_cast<int>(n), pairs);
@@ -358,8 +359,9 @@ extern "C" int rdm_attention_bf16(const float* q, int64_t ldq, const float* k, i
 extern "C" int rdm_vote_shift(const float* xyz, const float* offsets, int64_t ldo, int64_t n, float lx,
                               float ly, float lz, float* out, void* stream) {
   using namespace rdm;
-  RDM_REQUIRE(xyz && offsets && out && n >= 0, "rdm_vote_shift: bad arguments");
+  RDM_REQUIRE(n >= 0, "rdm_vote_shift: bad arguments");
   if (n == 0) return RDM_OK;
+  RDM_REQUIRE(xyz && offsets && out, "rdm_vote_shift: null pointer");
   ::rdm::launch<vote_shift_kernel_body, vote_shift_kernel, 256>(dim3(ceil_div<int64_t>(3 * n, 256)), 0, static_cast<hipStream_t>(stream), xyz, offsets, static_cast<int>(ldo), static_cast<int>(n), lx,
                      ly, lz, out);
   return launch_status("vote_shift_kernel");
@@ -367,8 +369,9 @@ extern "C" int rdm_vote_shift(const float* xyz, const float* offsets, int64_t ld
 
 extern "C" int rdm_sigmoid_column(const float* x, int64_t ldx, int64_t n, float* out, void* stream) {
   using namespace rdm;
-  RDM_REQUIRE(x && out && n >= 0, "rdm_sigmoid_column: bad arguments");
+  RDM_REQUIRE(n >= 0, "rdm_sigmoid_column: bad arguments");
   if (n == 0) return RDM_OK;
+  RDM_REQUIRE(x && out, "rdm_sigmoid_column: null pointer");
   ::rdm::launch<sigmoid_kernel_body, sigmoid_kernel, 256>(dim3(ceil_div<int64_t>(n, 256)), 0, static_cast<hipStream_t>(stream), x, static_cast<int>(ldx), static_cast<int>(n), out);
   return launch_status("sigmoid_kernel");
 }
@@ -376,8 +379,9 @@ extern "C" int rdm_sigmoid_column(const float* x, int64_t ldx, int64_t n, float*
 extern "C" int rdm_l2_normalize(const float* x, int64_t ldx, int64_t n, int64_t c, float* y, int64_t ldy,
                                 void* stream) {
   using namespace rdm;
-  RDM_REQUIRE(x && y && n >= 0 && c > 0, "rdm_l2_normalize: bad arguments");
+  RDM_REQUIRE(n >= 0 && c > 0, "rdm_l2_normalize: bad arguments");
   if (n == 0) return RDM_OK;
+  RDM_REQUIRE(x && y, "rdm_l2_normalize: null pointer");
   ::rdm::launch<l2_normalize_kernel_body, l2_normalize_kernel, 256>(dim3(ceil_div<int64_t>(n, 4)), 0, static_cast<hipStream_t>(stream), x, static_cast<int>(ldx), static_cast<int>(n),
                      static_cast<int>(c), y, static_cast<int>(ldy));
   return launch_status("l2_normalize_kernel");

@@ -7,7 +7,7 @@
 // away: in the reference they hold -1e12, so every exp() involving them underflows to exactly 0 and
 // their own potentials evaluate to exactly 0 -- dropping them changes nothing but the summation
 // order.  Masked entries of the output are written as fl(-1e12), the value the reference's
-// fp32 arithmetic produces there.
+// fp32 arithmetic produces there -- unless a whole side is masked (see sinkhorn_empty_side).
 // exp() inside the sums is the hardware exponential (__expf, arguments <= 0 after the max shift:
 // relative error <= ~1e-6 on terms that matter); log() is the accurate one.
 //   u = log_mu - logsumexp_j(Z + v)        logsumexp(x) = max + log(sum(exp(x - max)))
@@ -140,6 +140,26 @@ __device__ __forceinline__ void sinkhorn_iterate(const float* Z, int ldz, int nr
   }
 }
 
+// A patch whose rows (nr = 0) or columns (nc = 0) are all masked, as the reference evaluates it.  With nr = 0,
+// log_nu of the dustbin column is log(0) + norm = -inf, so the first iteration makes v[n] = -inf: the whole dustbin column
+// is -inf, masked rows included, and the valid entries of the dustbin row are 0 (u[m] = -(alpha + log(nc + 1)) and
+// v[j] = log((nc + 1) / nc), so alpha + u[m] + v[j] - norm = 0; the reference's fp32 gives 0.0 there too).  nc = 0
+// mirrors it.  With nr = nc = 0, norm = -log(0) = +inf: every entry is Z - inf = -inf without iterations and NaN after one
+// (log_mu[m] = log(0) + inf).  With iters = 0 and one non-empty side the common path already returns Z - norm.
+__device__ __forceinline__ void sinkhorn_empty_side(int nr, int nc, int m, int n, const unsigned char* rm, const unsigned char* cm,
+                                                    int iters, float* O) {
+  const float masked = -1.0e12f;
+  const int total = (m + 1) * (n + 1);
+  for (int t = threadIdx.x; t < total; t += 256) {
+    const int r = t / (n + 1), c = t % (n + 1);
+    float o;
+    if (nr == 0 && nc == 0) o = iters > 0 ? __builtin_nanf("") : -INFINITY;
+    else if (nr == 0) o = c == n ? -INFINITY : (r == m && cm[c] ? 0.f : masked);
+    else o = r == m ? -INFINITY : (c == n && rm[r] ? 0.f : masked);
+    O[t] = o;
+  }
+}
+
 // 256 threads.  Thread t owns row (t>>1), columns [66*(t&1), 66*(t&1)+66) of the compacted score
 // block in REGISTERS, and likewise half of column (t>>1): the 100 iterations touch LDS only for the
 // broadcast potentials u, v.  A row's two halves are combined with one lane exchange.  The entries are held as
@@ -176,6 +196,10 @@ __device__ __forceinline__ void sinkhorn_kernel_body(const dim3 blockIdx, const 
   }
   __syncthreads();
   const int nr = s_nr, nc = s_nc, R = nr + 1, C = nc + 1;
+  if ((nr == 0 || nc == 0) && (iters > 0 || nr + nc == 0)) {  // uniform over the workgroup
+    sinkhorn_empty_side(nr, nc, m, n, rm, cm, iters, O);
+    return;
+  }
   const int ldz = C | 1;
   float* Z = lds;
   const float alpha = *alpha_p;

@@ -155,8 +155,9 @@ def kpconv_fused(q_points, s_points, s_feats, s_positive, idx, kernel_points, si
 
 
 def kpconv_fused_group_norm(q_points, s_points, s_feats, s_positive, idx, kernel_points, sigma, w_packed, bias, c_out, gamma,
-                            beta, groups, *, width=None, act=ACT_LEAKY, eps=1e-5, order=None):
-    """act(GroupNorm(KPConv(...))) -- the fused convolution followed by the normalisation every backbone block applies."""
+                            beta, groups, *, width=None, act=ACT_LEAKY, eps=1e-5, order=None, return_conv=False):
+    """act(GroupNorm(KPConv(...))) -- the fused convolution followed by the normalisation every backbone block applies.
+    return_conv: also return the convolution output the normalisation read -> (y, conv)."""
     L = _lib.lib()
     m, c = q_points.shape[0], s_feats.shape[1]
     conv, y = feat_empty(m, c_out, q_points.device), feat_empty(m, c_out, q_points.device)
@@ -167,7 +168,7 @@ def kpconv_fused_group_norm(q_points, s_points, s_feats, s_positive, idx, kernel
                                              bias.data_ptr(), c_out, groups, gamma.data_ptr(), beta.data_ptr(), eps, act,
                                              conv.data_ptr(), _ld(conv), y.data_ptr(), _ld(y), ws.data_ptr(), ws.numel(),
                                              _lib.ptr(order), _lib.stream_ptr()), 'rdm_kpconv_fused_group_norm')
-    return y
+    return (y, conv) if return_conv else y
 
 
 def group_norm(x, gamma, beta, groups, *, act=ACT_NONE, residual=None, want_positive=False, eps=1e-5, form=0):

@@ -23,6 +23,20 @@ def padded(t, device='cuda'):
     return buf[:, :c]
 
 
+def kpconv_fp64(q_pts, s_pts, feats, idx, kp, sigma, W, bias):
+    """KPConv.forward (kpconv.py:79-122) in fp64: influence-weighted sum over the neighbours (index len(s_pts) = the shadow
+    point far away with zero features), contraction with W [15, c_in, c_out], division by the count of neighbours with a
+    positive feature sum (at least 1), bias."""
+    c = feats.shape[1]
+    sp = torch.cat([s_pts, torch.full((1, 3), 1e6)]).double()
+    sf = torch.cat([feats, torch.zeros(1, c)]).double()
+    rel = sp[idx] - q_pts.double()[:, None]
+    infl = torch.clamp(1 - ((rel[:, :, None] - kp.double()) ** 2).sum(-1).sqrt() / sigma, min=0)
+    wf = torch.einsum('mhk,mhc->mkc', infl, sf[idx]).reshape(idx.shape[0], 15 * c)
+    nn = torch.cat([feats.sum(1) > 0, torch.zeros(1, dtype=torch.bool)])[idx].sum(1).clamp(min=1).double()
+    return wf @ W.double().reshape(15 * c, -1) / nn[:, None] + bias.double()
+
+
 @pytest.mark.parametrize('m,k,n,trans_b', [(1, 4, 1, False), (77, 36, 33, False), (300, 128, 257, False),
                                             (2236, 1284, 1024, False), (842, 7680, 512, False),
                                             (39609, 480, 32, False), (5000, 64, 128, False),
@@ -390,14 +404,7 @@ def test_kpconv_fused_matches_reference_formula(ops, c, cout, h, m, ns):
     W = torch.randn(15, c, cout, generator=g) / np.sqrt(15 * c)
     bias = torch.randn(cout, generator=g)
     sigma = 1.7
-    sp = torch.cat([s_pts, torch.full((1, 3), 1e6)]).double()
-    sf = torch.cat([feats, torch.zeros(1, c)]).double()
-    rel = sp[idx] - q_pts.double()[:, None]
-    infl = torch.clamp(1 - ((rel[:, :, None] - kp.double()) ** 2).sum(-1).sqrt() / sigma, min=0)
-    wf = torch.einsum('mhk,mhc->mkc', infl, sf[idx]).reshape(m, 15 * c)
-    pos = (feats.sum(1) > 0)
-    nn_ref = torch.cat([pos, torch.zeros(1, dtype=torch.bool)])[idx].sum(1).clamp(min=1).double()
-    ref = wf @ W.double().reshape(15 * c, cout) / nn_ref[:, None] + bias.double()
+    ref = kpconv_fp64(q_pts, s_pts, feats, idx, kp, sigma, W, bias)
     packed = torch.from_numpy(ops.kpconv_pack_weights(W.numpy())).cuda()
     fd = padded(feats)
     args = (q_pts.cuda(), s_pts.cuda(), fd, ops.row_positive(fd), idx.cuda(), kp.cuda(), sigma, packed, bias.cuda(), cout)
