@@ -347,6 +347,23 @@ int rdm_attention_bf16(const float* q, int64_t ldq, const float* k, int64_t ldk,
 int rdm_attention_self_pair(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
                             float* out, int64_t ldo, int64_t n0, int64_t n1, int heads, int head_dim, int bf16,
                             void* stream);
+/* rdm_attention_topk: the top-k ("dynamic") attention of the second 3DRoFormer's self layers (cfg.thdroformer.k2;
+ *   rdmnet/thdroformer/thdroformer.py:20-40 with k != None): each query row keeps its `keep` (0 <= keep <= n_k) largest scores
+ *   q k^T / sqrt(head_dim) -- the same fp32 scores rdm_attention forms -- and out = softmax over the kept scores times their
+ *   v rows; the other keys get probability 0.  keep = 0 gives zero rows.  Ties: among keys whose score equals the keep-th
+ *   largest (-0 equal to +0), the lowest key indices are kept (torch.topk leaves the choice unspecified).  Any n_k (rows of
+ *   up to 2048 keys keep their scores in LDS, longer rows form them again per pass); n_q = 0 and n_k = 0 are valid.
+ *   Arguments as rdm_attention.
+ * rdm_attention_self_pair_topk: both stacked clouds in one launch, as rdm_attention_self_pair, cloud 0 keeping keep0 of its
+ *   n0 keys and cloud 1 keep1 of its n1; the bits of two rdm_attention_topk calls.
+ * rdm_topk_count: the kept count int(n * frac) of the reference -- the IEEE double product truncated (int(100 * 0.57) is 56).
+ *   Host only; the single definition the engine uses.                                                                      */
+int rdm_attention_topk(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, float* out,
+                       int64_t ldo, int64_t n_q, int64_t n_k, int64_t keep, int heads, int head_dim, void* stream);
+int rdm_attention_self_pair_topk(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                                 float* out, int64_t ldo, int64_t n0, int64_t n1, int64_t keep0, int64_t keep1, int heads,
+                                 int head_dim, void* stream);
+int64_t rdm_topk_count(int64_t n, double frac);
 
 /* ---- a8/a9 helpers ------------------------------------------------------------------------------
  * rdm_vote_shift: xyz + clamp(offset[:, :3], +-limit) (rdmnet/vote/vote.py:98-108).
@@ -641,6 +658,11 @@ int rdm_engine_set_pairs_in_flight(rdm_engine* e, int n);
  * spin kernels the first time it sees a caller stream (a few hundred microseconds, once) and stays serial where no such stream exists.
  * The reference has no counterpart (its loop is synchronous: geotransformer/engine/single_tester.py:86-134).                    */
 int rdm_engine_set_overlap(rdm_engine* e, int mode);
+/* cfg.thdroformer.k2: self layer i (0 .. n_layers - 1) of transformer #2 runs rdm_attention_self_pair_topk with
+ * keep = rdm_topk_count(n, fracs[i]) for each cloud's superpoint count n; fracs[i] < 0, layers past n_layers, transformer #1 and
+ * every cross layer stay dense.  fracs[i] must be <= 1; not with attention_bf16.  n_layers = 0 clears the setting.  Valid
+ * before or after finalize / share_params (the setting is the engine's own, not part of the shared parameters).            */
+int rdm_engine_set_attention_topk(rdm_engine* e, int n_layers, const double* fracs);
 /* Per-KPConv-layer profile of the next runs: 0 = off, 1 = HIP events around every layer's neighbourhood kernel and around the
  * whole layer (rdm_engine_get_profile: sizes + milliseconds), 2 = the layers' sizes only, no events -- for the other pairs of a
  * lock-step group whose first engine records the events: the launches (and durations) are the group's.                     */

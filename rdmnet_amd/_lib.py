@@ -105,6 +105,11 @@ SIGNATURES = {
                               c_void]),
     'rdm_attention_self_pair': (c_int, [c_void, c_i64, c_void, c_i64, c_void, c_i64, c_void, c_i64, c_i64, c_i64, c_int, c_int,
                                         c_int, c_void]),
+    'rdm_attention_topk': (c_int, [c_void, c_i64, c_void, c_i64, c_void, c_i64, c_void, c_i64, c_i64, c_i64, c_i64, c_int, c_int,
+                                   c_void]),
+    'rdm_attention_self_pair_topk': (c_int, [c_void, c_i64, c_void, c_i64, c_void, c_i64, c_void, c_i64, c_i64, c_i64, c_i64, c_i64,
+                                             c_int, c_int, c_void]),
+    'rdm_topk_count': (c_i64, [c_i64, ctypes.c_double]),
     'rdm_vote_shift': (c_int, [c_void, c_void, c_i64, c_i64, c_f32, c_f32, c_f32, c_void, c_void]),
     'rdm_sigmoid_column': (c_int, [c_void, c_i64, c_i64, c_void, c_void]),
     'rdm_l2_normalize': (c_int, [c_void, c_i64, c_i64, c_i64, c_void, c_i64, c_void]),
@@ -149,6 +154,7 @@ SIGNATURES = {
     'rdm_engine_set_wait': (c_int, [c_void, c_int]),
     'rdm_engine_set_pairs_in_flight': (c_int, [c_void, c_int]),
     'rdm_engine_set_overlap': (c_int, [c_void, c_int]),
+    'rdm_engine_set_attention_topk': (c_int, [c_void, c_int, c_void]),
     'rdm_engine_enable_profile': (c_int, [c_void, c_int]),
     'rdm_engine_get_profile': (c_int, [c_void, c_void, c_int]),
     'rdm_engine_keep_taps': (c_int, [c_void, c_int]),

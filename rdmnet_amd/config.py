@@ -1,5 +1,8 @@
 """Configuration of the inference path.  Mirrors the constants the reference reads from its
 EasyDict (experiments/config.py:84-161); only keys used by inference are kept."""
+import numbers
+
+import numpy as np
 
 
 class Cfg(dict):
@@ -35,3 +38,39 @@ def make_cfg():
     c.test = Cfg(vis=False)
     c.neighbor_limits = [65, 63, 69, 70, 81]  # calibrated on the bundled pairs (utils/data.py:195-220)
     return c
+
+
+def topk_fractions(cfg):
+    """cfg.thdroformer.k2 checked and read: None when every self layer of transformer #2 is dense (k2 None, or None in each
+    of the first num_layers2 entries), else one float per self layer, -1.0 for a dense one (the encoding of
+    rdm_engine_set_attention_topk).  A layer keeps int(n * f) keys of a cloud of n superpoints (thdroformer.py:20-40).
+    Raises ValueError naming the key for: a k2 that is not a sequence; fewer than num_layers2 entries (an IndexError in the
+    reference); an entry that is not None or a real number in [0, 1] (the reference also runs 1 < f while int(n * f) <= n,
+    which depends on the data: rejected up front here); k2 together with attention_bf16 (no top-k variant of that mode).
+    Entries past num_layers2 are ignored, as in the reference."""
+    t = cfg.thdroformer
+    k2 = t.get('k2', None)
+    if k2 is None:
+        return None
+    if isinstance(k2, (str, bytes)) or not hasattr(k2, '__len__') or not hasattr(k2, '__getitem__'):
+        raise ValueError(f'cfg.thdroformer.k2 must be None or a sequence of per-layer fractions, got {k2!r}')
+    n = int(t.num_layers2)
+    if len(k2) < n:
+        raise ValueError(f'cfg.thdroformer.k2 has {len(k2)} entries; transformer #2 has num_layers2 = {n} self layers')
+    fracs = []
+    for i in range(n):
+        f = k2[i]
+        if f is None:
+            fracs.append(-1.0)
+            continue
+        if isinstance(f, (bool, np.bool_)) or not isinstance(f, numbers.Real):
+            raise ValueError(f'cfg.thdroformer.k2[{i}] must be None or a real number in [0, 1], got {f!r}')
+        if not 0.0 <= float(f) <= 1.0:  # (also rejects NaN)
+            raise ValueError(f'cfg.thdroformer.k2[{i}] = {f!r} is outside [0, 1]')
+        fracs.append(float(f))
+    if all(f < 0 for f in fracs):
+        return None
+    if t.get('attention_bf16', False):
+        raise ValueError('cfg.thdroformer.k2 cannot be combined with cfg.thdroformer.attention_bf16 (no top-k variant of '
+                         'bf16 attention)')
+    return fracs

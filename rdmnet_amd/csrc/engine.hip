@@ -117,6 +117,9 @@ struct rdm_engine {
   std::map<std::string, rdm_tensor_view> taps;
   bool keep_taps = false;
   bool collate_only = false;  // rdm_engine_collate: stop after the pyramid and its searches
+  // rdm_engine_set_attention_topk (cfg.thdroformer.k2): per self layer of transformer #2, the fraction of each cloud's keys a
+  // query keeps (thdroformer.py:20-40); negative or past the end: dense
+  std::vector<double> topk_fracs;
   int pairs_in_flight = 1;    // rdm_engine_set_pairs_in_flight: how many pairs share the GPU (>= 3: GEMM residency capped)
   // Latency mode (rdm_engine_set_overlap): with ONE pair in flight most of the GPU idles while a chain of one-workgroup kernels
   // runs, so the engine runs the wide, independent parts of a pair (the first level's search + blocks, the decoder) on a side
@@ -472,9 +475,10 @@ int attention_tail(Run& r, const std::string& p, const Mat& hid, const Mat& x, M
 // rotary embedding and the whole tail) runs once on all rows; only the attention itself is per cloud.
 // Cross layers keep the reference's order: src attends to the UPDATED ref features (:244-245).
 // `after_two` (optional) is called once two layers have been enqueued (latency mode: the host then has enough of a lead on the
-// caller's stream to enqueue the side stream's launches without stalling it).
+// caller's stream to enqueue the side stream's launches without stalling it).  `topk` (optional, transformer #2 only): the kept
+// fraction per self layer (thdroformer.py:132-135 passes k[layer] to dynamic_attention); a negative entry or none: dense.
 int thdroformer(Run& r, const std::string& name, const Mat& pts4, const Mat& x, int64_t n0, int num_layers, Mat out,
-                const std::function<int()>* after_two = nullptr) {
+                const std::function<int()>* after_two = nullptr, const std::vector<double>* topk = nullptr) {
   rdm_engine* e = r.e;
   const int heads = e->cfg.num_heads;
   const int64_t N = x.rows, n1 = N - n0;
@@ -493,8 +497,15 @@ int thdroformer(Run& r, const std::string& name, const Mat& pts4, const Mat& x, 
       ENG_CHECK(linear(r, p + ".qkv", f, qkv));
       Mat q = qkv.cols_from(0, d), k = qkv.cols_from(d, d), v = qkv.cols_from(2 * d, d);
       ENG_CHECK(rdm_rope(q.p, q.ld, k.p, k.ld, emb.p, emb.ld, N, d, r.st));
-      ENG_CHECK(rdm_attention_self_pair(q.p, q.ld, k.p, k.ld, v.p, v.ld, hid.p, hid.ld, n0, n1, heads, hd,
-                                        e->cfg.attention_bf16 ? 1 : 0, r.st));  // both clouds, one launch
+      const size_t self_idx = static_cast<size_t>(i / 2);
+      if (topk && self_idx < topk->size() && (*topk)[self_idx] >= 0) {  // each cloud keeps int(n * f) of its own keys
+        const double f = (*topk)[self_idx];
+        ENG_CHECK(rdm_attention_self_pair_topk(q.p, q.ld, k.p, k.ld, v.p, v.ld, hid.p, hid.ld, n0, n1, rdm_topk_count(n0, f),
+                                               rdm_topk_count(n1, f), heads, hd, r.st));
+      } else {
+        ENG_CHECK(rdm_attention_self_pair(q.p, q.ld, k.p, k.ld, v.p, v.ld, hid.p, hid.ld, n0, n1, heads, hd,
+                                          e->cfg.attention_bf16 ? 1 : 0, r.st));  // both clouds, one launch
+      }
       ENG_CHECK(attention_tail(r, p, hid, f, fnew));
     } else {
       Mat q, kv1, kv0;
@@ -958,6 +969,15 @@ extern "C" int rdm_engine_set_wait(rdm_engine* e, int sleep_us) {
 extern "C" int rdm_engine_set_pairs_in_flight(rdm_engine* e, int n) {
   RDM_REQUIRE(e && n >= 1, "rdm_engine_set_pairs_in_flight: bad arguments");
   e->pairs_in_flight = n;
+  return RDM_OK;
+}
+
+extern "C" int rdm_engine_set_attention_topk(rdm_engine* e, int n_layers, const double* fracs) {
+  RDM_REQUIRE(e && n_layers >= 0 && (n_layers == 0 || fracs), "rdm_engine_set_attention_topk: bad arguments");
+  RDM_REQUIRE(n_layers == 0 || !e->cfg.attention_bf16, "rdm_engine_set_attention_topk: no top-k variant of bf16 attention");
+  for (int i = 0; i < n_layers; ++i)
+    RDM_REQUIRE(fracs[i] <= 1.0 && !std::isnan(fracs[i]), "rdm_engine_set_attention_topk: fraction %d is %g (not <= 1)", i, fracs[i]);
+  e->topk_fracs.assign(fracs, fracs + n_layers);
   return RDM_OK;
 }
 
@@ -1662,7 +1682,7 @@ int superpoints(Run& r, const PairPyramid& py, const Coarse& co, const std::func
     // was complete at the read-back above, and the host's 12 launches for it then do not hold up this chain)
     buf2 = e->mat(Mn, D);
     ENG_ALLOC(buf2.p);
-    ENG_CHECK(thdroformer(r, "transformer2", nodes4, sel_feats, sp.m_r, c.num_layers2, buf2, fork));
+    ENG_CHECK(thdroformer(r, "transformer2", nodes4, sel_feats, sp.m_r, c.num_layers2, buf2, fork, &e->topk_fracs));
     if (fork && 2 * c.num_layers2 < 2) ENG_CHECK((*fork)());
     tap(r, "t2", buf2);
   } else {

@@ -4,7 +4,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib, weights
+from . import _lib, config, weights
 
 
 class EngineConfig(ctypes.Structure):
@@ -96,9 +96,13 @@ class Engine:
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.cfg = cfg
         self._h = ctypes.c_void_p()
+        topk = config.topk_fractions(cfg)  # cfg.thdroformer.k2 (ValueError before anything is created)
         with torch.cuda.device(self.device):
             c = make_config(cfg, arena_bytes)
             _lib.check(self.L.rdm_engine_create(ctypes.byref(c), ctypes.byref(self._h)), 'rdm_engine_create')
+            if topk is not None:
+                fr = (ctypes.c_double * len(topk))(*topk)
+                _lib.check(self.L.rdm_engine_set_attention_topk(self._h, len(topk), fr), 'rdm_engine_set_attention_topk')
             if share_with is not None:
                 _lib.check(self.L.rdm_engine_share_params(self._h, share_with._h), 'rdm_engine_share_params')
             for name, shape in ({} if share_with is not None else weights.schema(cfg)).items():

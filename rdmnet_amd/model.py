@@ -12,7 +12,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import ops, weights
+from . import config, ops, weights
 from .ops import ACT_LEAKY, ACT_NONE, ACT_RELU, pad4
 
 
@@ -55,6 +55,7 @@ class RDMNet(torch.nn.Module):
         self._np_state = None  # name -> numpy float32 (what the kernels' weight preparation reads)
         self.use_vote = bool(cfg.Vote.inference_use_vote and cfg.Vote.model_use_vote)
         self.attention_bf16 = bool(getattr(cfg.thdroformer, 'attention_bf16', False))
+        self.topk2 = config.topk_fractions(cfg)  # cfg.thdroformer.k2 per self layer of transformer #2 (None: all dense)
         self._tls = threading.local()  # .profile: list -> per-KPConv-layer HIP-event records (bench.py)
         # native engines by (device, stream), least recently used first; at most `max_engines` are kept (each owns an arena of
         # >= 3 GiB of HBM): a caller that keeps creating streams recycles engines instead of accumulating them
@@ -281,10 +282,11 @@ class RDMNet(torch.nn.Module):
         h = self._linear(lin, x)
         return ops.layer_norm(h, W[norm + '.weight'], W[norm + '.bias'], residual=residual, out=out)
 
-    def _thdroformer(self, name, pts4, x, n0, num_layers, out):
+    def _thdroformer(self, name, pts4, x, n0, num_layers, out, topk=None):
         """rdmnet/thdroformer/thdroformer.py:266-347 on the STACKED [ref; src] rows (same op sequence as
         the native engine): shared-weight ops run once on all rows, attention per cloud; cross layers are
-        sequential -- src attends to the UPDATED ref features (:244-245)."""
+        sequential -- src attends to the UPDATED ref features (:244-245).  topk (transformer #2): the kept fraction per
+        self layer, negative = dense (config.topk_fractions); each cloud keeps int(n * f) of its own keys."""
         W, heads = self._w, self.cfg.thdroformer.num_heads
         N = x.shape[0]
         n1 = N - n0
@@ -298,7 +300,9 @@ class RDMNet(torch.nn.Module):
                 qkv = ops.gemm(f, W[p + '.qkv'][0], d, 3 * d, bias=W[p + '.qkv'][1])
                 q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
                 ops.rope(q, k, emb)
-                ops.attention_self_pair(q, k, v, n0, heads, out=hid, bf16=self.attention_bf16)  # both clouds, one launch
+                frac = topk[i // 2] if topk is not None else -1.0
+                keep = (ops.topk_count(n0, frac), ops.topk_count(n1, frac)) if frac >= 0 else None
+                ops.attention_self_pair(q, k, v, n0, heads, out=hid, bf16=self.attention_bf16, keep=keep)  # both clouds, one launch
                 self._attention_tail(p, hid, f, fnew)
             else:
                 q = ops.gemm(f, W[p + '.q'][0], d, d, bias=W[p + '.q'][1])
@@ -516,7 +520,7 @@ class RDMNet(torch.nn.Module):
             # transformer #2 on the surviving nodes
             buf2 = ops.feat_empty(m_r + m_s, t.output_dim, dev)
             nodes4 = self._pts4(nodes)
-            self._thdroformer('transformer2', nodes4, sel_feats, m_r, t.num_layers2, buf2)
+            self._thdroformer('transformer2', nodes4, sel_feats, m_r, t.num_layers2, buf2, topk=self.topk2)
             taps['t2_ref'], taps['t2_src'] = buf2[:m_r], buf2[m_r:]
         else:
             # infer.py:119-120 (Mulran) disables the vote layer; model_infer.py:179-246 then leaves

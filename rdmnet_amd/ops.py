@@ -313,23 +313,45 @@ def rope(q, k, emb):
                           q.shape[0], q.shape[1], _lib.stream_ptr()), 'rdm_rope')
 
 
-def attention(q, k, v, heads, out=None, bf16=False):
+def topk_count(n, frac):
+    """int(n * frac) as the library defines it (rdm_topk_count): the kept count of a top-k attention layer."""
+    return _lib.lib().rdm_topk_count(int(n), float(frac))
+
+
+def attention(q, k, v, heads, out=None, bf16=False, keep=None):
+    """softmax(q k^T / sqrt(d)) v per head; keep (0 <= keep <= len(k)): each query keeps only its `keep` largest scores
+    (rdm_attention_topk, cfg.thdroformer.k2); None: dense."""
     L = _lib.lib()
     nq, d = q.shape
     if out is None:
         out = feat_empty(nq, d, q.device)
+    if keep is not None:
+        if bf16:
+            raise ValueError('attention: no top-k variant of bf16 attention')
+        _lib.check(L.rdm_attention_topk(q.data_ptr(), _ld(q), k.data_ptr(), _ld(k), v.data_ptr(), _ld(v), out.data_ptr(), _ld(out),
+                                        nq, k.shape[0], int(keep), heads, d // heads, _lib.stream_ptr()), 'rdm_attention_topk')
+        return out
     fn = L.rdm_attention_bf16 if bf16 else L.rdm_attention
     _lib.check(fn(q.data_ptr(), _ld(q), k.data_ptr(), _ld(k), v.data_ptr(), _ld(v), out.data_ptr(), _ld(out),
                                nq, k.shape[0], heads, d // heads, _lib.stream_ptr()), 'rdm_attention')
     return out
 
 
-def attention_self_pair(q, k, v, n0, heads, out=None, bf16=False):
-    """Self-attention of two stacked clouds (rows [0, n0) and [n0, n)) in one launch; same results as two attention calls."""
+def attention_self_pair(q, k, v, n0, heads, out=None, bf16=False, keep=None):
+    """Self-attention of two stacked clouds (rows [0, n0) and [n0, n)) in one launch; same results as two attention calls.
+    keep = (keep0, keep1): top-k attention, cloud 0 keeping keep0 keys per query and cloud 1 keep1 (rdm_attention_self_pair_topk)."""
     L = _lib.lib()
     n, d = q.shape
     if out is None:
         out = feat_empty(n, d, q.device)
+    if keep is not None:
+        if bf16:
+            raise ValueError('attention_self_pair: no top-k variant of bf16 attention')
+        keep0, keep1 = keep
+        _lib.check(L.rdm_attention_self_pair_topk(q.data_ptr(), _ld(q), k.data_ptr(), _ld(k), v.data_ptr(), _ld(v), out.data_ptr(),
+                                                  _ld(out), n0, n - n0, int(keep0), int(keep1), heads, d // heads, _lib.stream_ptr()),
+                   'rdm_attention_self_pair_topk')
+        return out
     _lib.check(L.rdm_attention_self_pair(q.data_ptr(), _ld(q), k.data_ptr(), _ld(k), v.data_ptr(), _ld(v), out.data_ptr(), _ld(out),
                                          n0, n - n0, heads, d // heads, int(bf16), _lib.stream_ptr()), 'rdm_attention_self_pair')
     return out
