@@ -130,6 +130,35 @@ int rdm_ransac_correspondences(const float* src_corr, const float* ref_corr, int
                                int ransac_n, int num_iterations, uint64_t seed, float* transform, int32_t* stats,
                                float* inlier_rmse, int32_t* hyp_inliers, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- §7 ICP / pair generation: point-to-point ICP --------------------------------------------------
+ * The ground-truth refinement of preporcess/generate_kitti_pairs.py:157-172 (Open3D registration_icp,
+ * TransformationEstimationPointToPoint without scaling, ICPConvergenceCriteria; 0.5 m, up to 5000 iterations, on
+ * raw scans).  source [n_source, ld_source] / target [n_target, ld_target]: device f32, xyz in the first three
+ * columns.  pcd = init . source (float64; untouched for the identity), transformation = init, evaluate; then up to
+ * max_iteration times: update = Kabsch of the correspondences (identity without any), transformation = update .
+ * transformation, pcd = update . pcd, evaluate; stop when |d fitness| < relative_fitness and |d rmse| <
+ * relative_rmse.  Evaluate: nearest target with d2 < r2, r2 = (double)(float)(r*r), d2 = ((dx*dx)+(dy*dy))+(dz*dz) in
+ * float64 on the float32 targets, ties to the lowest index; fitness = n_corr / n_source, rmse = sqrt(err2 / n_corr).
+ * init_host: host f64[16] row-major (NULL = identity).  Outputs (device): transform f64[16], fitness_rmse f64[2] of
+ * the last evaluation, stats int32[2] = {updates applied, n_corr}; history (optional, device) f64[(max_iteration+1)
+ * x 15], record k = {fitness_k, rmse_k, n_corr_k, update_k (12, the update computed from evaluation k and applied
+ * after it; the identity in the last record, after which no update follows)}.  The host reads one int32 per 32
+ * iterations.  max_correspondence_distance <= 0 is an argument error; an empty source returns init with fitness 0;
+ * a target point that is not finite (or beyond 2^30 cells of r from the origin) is an argument error.
+ * n_source, n_target < 2^31.  Open3D is not part of the reference tree -> parity unpinned.                    */
+size_t rdm_icp_workspace_bytes(int64_t n_source, int64_t n_target);
+int rdm_icp_point_to_point(const float* source, int64_t n_source, int64_t ld_source, const float* target, int64_t n_target,
+                           int64_t ld_target, double max_correspondence_distance, const double* init_host, int max_iteration,
+                           double relative_fitness, double relative_rmse, double* transform, double* fitness_rmse,
+                           int32_t* stats, double* history, void* ws, size_t ws_bytes, void* stream);
+/* The evaluation step alone (preporcess/generate_kitti_pairs.py:157-172, inside Open3D's registration_icp; parity
+ * unpinned) on a caller's float64 query cloud pcd [n, 3] (device): idx int32[n] = nearest target with d2 < r2
+ * (lowest index among equal d2) or -1, d2 f64[n] = its squared distance (-1 where idx is -1).  Same semantics, bit for
+ * bit, as the search inside rdm_icp_point_to_point; workspace rdm_icp_workspace_bytes(0, n_target).            */
+int rdm_icp_correspondences(const double* pcd, int64_t n, const float* target, int64_t n_target, int64_t ld_target,
+                            double max_correspondence_distance, int32_t* idx, double* d2, void* ws, size_t ws_bytes,
+                            void* stream);
+
 /* ---- dense contraction ---------------------------------------------------------------------
  * C[b] = act((A[b] (m x k) * op(B[b])) / rowdiv[row] + bias[col]) in fp32 on the f32 MFMA.
  * trans_b = 0: B is [k, n] row-major (pre-transposed nn.Linear weights, KPConv weights viewed

@@ -63,6 +63,11 @@ SIGNATURES = {
     'rdm_ransac_workspace_bytes': (c_size, [c_int]),
     'rdm_ransac_correspondences': (c_int, [c_void, c_void, c_i64, c_f32, c_int, c_int, ctypes.c_uint64, c_void, c_void, c_void,
                                            c_void, c_void, c_size, c_void]),
+    'rdm_icp_workspace_bytes': (c_size, [c_i64, c_i64]),
+    'rdm_icp_point_to_point': (c_int, [c_void, c_i64, c_i64, c_void, c_i64, c_i64, ctypes.c_double, c_void, c_int, ctypes.c_double,
+                                       ctypes.c_double, c_void, c_void, c_void, c_void, c_void, c_size, c_void]),
+    'rdm_icp_correspondences': (c_int, [c_void, c_i64, c_void, c_i64, c_i64, ctypes.c_double, c_void, c_void, c_void, c_size,
+                                        c_void]),
     'rdm_neighbor_histogram': (c_int, [c_void, c_i64, c_void, c_int, c_void]),
     'rdm_radius_grid_records': (c_void, [c_void, c_size, c_i64]),
     'rdm_row_positive': (c_int, [c_void, c_i64, c_i64, c_i64, c_void, c_void]),

@@ -1,0 +1,585 @@
+// Point-to-point ICP on the GPU: the refinement of the KITTI ground-truth poses
+// (preporcess/generate_kitti_pairs.py:157-172: Open3D registration_icp, TransformationEstimationPointToPoint without
+// scaling, ICPConvergenceCriteria, 0.5 m, up to 5000 iterations, on the raw ~120 k-point scans).
+//
+// Open3D (0.11) is not under the reference tree -> PARITY UNPINNED.  Restated algorithm (RegistrationICP):
+//   pcd = init . source (float64; left as is for the identity), transformation = init, evaluate;
+//   for i < max_iteration: update = Kabsch(correspondences) (identity if there are none), transformation = update .
+//   transformation, pcd = update . pcd (incremental), evaluate; stop when |d fitness| < relative_fitness and
+//   |d rmse| < relative_rmse.
+//   Evaluate: for every pcd point the nearest target point with d2 < r2 -> fitness = n_corr / n_source,
+//   inlier_rmse = sqrt(err2 / n_corr) (both 0 without correspondences).
+// Neighbour step, defined to the bit (a float64 numpy restatement gives the same idx and d2):
+//   targets are float32 read as double, d = q - t per axis, d2 = ((dx*dx) + (dy*dy)) + (dz*dz) (never contracted),
+//   accept iff d2 < r2 with r2 = (double)(float)(r*r) (Open3D's KDTreeFlann hands FLANN a float squared radius),
+//   ties in d2 keep the lowest target index.
+// Transforms are applied as x' = ((R00*x + R01*y) + R02*z) + t0 per row, uncontracted.
+//
+// Structure:
+//   target index, once per call: cell = floor(t / h) per axis (h = sqrt(r2) (1 + 1e-6) >= the search radius) ->
+//   cell box (block slabs, one-block finalize) -> 64-bit key relative to the box -> radix sort of (key, index) ->
+//   float4 records in key order.  A query looks its 3 x 3 cell columns up by exact key (binary search of the lowest
+//   key of a column, then a forward scan): no clamping, so a query outside the box finds exactly the targets within
+//   r of it.  Every occupied cell holds its own points only, whatever the extent (the box only has to fit 2^62 cells).
+//   per iteration, with no host synchronisation: search (applies the pending update to its pcd point first; float64
+//   partials of count, err2 and the two sums to block slabs) -> one-block means -> demeaned covariance (second pass:
+//   60-80 m coordinates make the one-pass formula lose digits) -> one-block finalize (Kabsch, composition,
+//   convergence test, history record, outputs, `done`).  Every kernel of an iteration returns at once when `done` is
+//   set; the host enqueues iterations in chunks and reads `done` once per chunk.
+// Determinism: every reduction runs in a fixed order (lanes by butterfly, waves and slabs in index order); there are
+// no float atomics, so two runs give the same bits.
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "../../include/rdmnet_hip.h"
+#include "common.h"
+#include "procrustes.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+using namespace rdm;
+
+constexpr int kBlock = 256;
+constexpr int kMaxBlocks = 1024;              // slab rows: the point kernels stride over at most this many blocks
+constexpr int kChunk = 32;                    // iterations enqueued between two reads of `done`
+constexpr double kCellLimit = 1073741824.0;   // |t / h| < 2^30 for every target point
+constexpr int kRecord = 15;                   // history record: fitness, rmse, n_corr, update[12]
+
+struct Mat16 {
+  double v[16];
+};
+
+struct IcpState {
+  double T[16];   // transformation so far (row-major 4x4)
+  double U[12];   // update of the last finalize (R | t, rows), applied by the next search
+  double fitness, rmse;
+  double err2, ms[3], mt[3];
+  long long n_corr;
+  int done;       // 0 running, 1 finished, 2 bad target (non-finite point or extent beyond the cell limits)
+  int updates;
+};
+
+struct Grid {
+  long long lo[3], dims[3];  // cell box of the target (dims = 0 when it is empty)
+  double h;
+};
+
+__device__ __forceinline__ double cell_of(double x, double h) { return floor(x / h); }
+
+// Sums K doubles over the block (256 threads) in a fixed order; thread k < K returns the total of value k.
+template <int K>
+__device__ __forceinline__ double block_sum(double (&v)[K], int k) {
+  __shared__ double part[kBlock / kWave][K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) v[j] = wave_sum(v[j]);
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int j = 0; j < K; ++j) part[threadIdx.x >> 6][j] = v[j];
+  __syncthreads();
+  double s = 0.0;
+  if (k < K) {
+    s = part[0][k];
+    for (int w = 1; w < kBlock / kWave; ++w) s += part[w][k];
+  }
+  return s;
+}
+
+// Row-wise sum over `rows` slab rows of K doubles (one block): thread t takes rows t, t + 256, ... in order.
+template <int K>
+__device__ __forceinline__ double slab_sum(const double* __restrict__ slab, int rows, int k) {
+  double v[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) v[j] = 0.0;
+  for (int r = threadIdx.x; r < rows; r += kBlock)
+#pragma unroll
+    for (int j = 0; j < K; ++j) v[j] += slab[static_cast<long long>(r) * K + j];
+  return block_sum<K>(v, k);
+}
+
+__device__ __forceinline__ void apply_rt(const double* M, double& x, double& y, double& z) {
+  const double a = ((M[0] * x + M[1] * y) + M[2] * z) + M[3];
+  const double b = ((M[4] * x + M[5] * y) + M[6] * z) + M[7];
+  const double c = ((M[8] * x + M[9] * y) + M[10] * z) + M[11];
+  x = a; y = b; z = c;
+}
+
+// ---- target index --------------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(kBlock) void icp_bbox_kernel(const float* __restrict__ target, int m, long long ld, double h,
+                                                          double* __restrict__ slab) {
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, bad = 0.0;
+  for (int j = blockIdx.x * kBlock + threadIdx.x; j < m; j += gridDim.x * kBlock) {
+    for (int a = 0; a < 3; ++a) {
+      const double c = cell_of(static_cast<double>(target[j * ld + a]), h);
+      if (!(fabs(c) < kCellLimit)) bad = 1.0;  // (NaN and infinities too)
+      lo[a] = fmin(lo[a], c);
+      hi[a] = fmax(hi[a], c);
+    }
+  }
+  __shared__ double red[7][kBlock];
+  for (int a = 0; a < 3; ++a) {
+    red[a][threadIdx.x] = lo[a];
+    red[3 + a][threadIdx.x] = hi[a];
+  }
+  red[6][threadIdx.x] = bad;
+  __syncthreads();
+  if (threadIdx.x < 7) {
+    const int k = threadIdx.x;
+    double v = red[k][0];
+    for (int t = 1; t < kBlock; ++t) v = k < 3 ? fmin(v, red[k][t]) : fmax(v, red[k][t]);
+    slab[blockIdx.x * 8 + k] = v;
+  }
+}
+
+// One block: the cell box from the bbox slabs, and the state of a new call (T = init, nothing done).
+__global__ __launch_bounds__(kBlock) void icp_setup_kernel(const double* __restrict__ slab, int rows, int m, double h, Mat16 init,
+                                                           Grid* __restrict__ grid, IcpState* __restrict__ st) {
+  if (threadIdx.x != 0) return;
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  bool bad = false;
+  for (int r = 0; r < rows; ++r) {
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = fmin(lo[a], slab[r * 8 + a]);
+      hi[a] = fmax(hi[a], slab[r * 8 + 3 + a]);
+    }
+    bad = bad || slab[r * 8 + 6] != 0.0;
+  }
+  double cells = 1.0;
+  for (int a = 0; a < 3; ++a) {
+    const double d = m > 0 && !bad ? hi[a] - lo[a] + 1.0 : 0.0;
+    grid->lo[a] = m > 0 && !bad ? static_cast<long long>(lo[a]) : 0;
+    grid->dims[a] = static_cast<long long>(d);
+    cells *= d;
+  }
+  if (cells > 4611686018427387904.0) bad = true;  // keys are 64-bit: the box must fit 2^62 cells
+  grid->h = h;
+  for (int k = 0; k < 16; ++k) st->T[k] = init.v[k];
+  for (int k = 0; k < 12; ++k) st->U[k] = (k % 5 == 0) ? 1.0 : 0.0;
+  st->fitness = st->rmse = st->err2 = 0.0;
+  for (int a = 0; a < 3; ++a) st->ms[a] = st->mt[a] = 0.0;
+  st->n_corr = 0;
+  st->updates = 0;
+  st->done = bad ? 2 : 0;
+}
+
+__global__ __launch_bounds__(kBlock) void icp_key_kernel(const float* __restrict__ target, int m, long long ld,
+                                                         const Grid* __restrict__ grid, const IcpState* __restrict__ st,
+                                                         unsigned long long* __restrict__ keys, int* __restrict__ vals) {
+  const int j = blockIdx.x * kBlock + threadIdx.x;
+  if (j >= m) return;
+  unsigned long long key = 0;
+  if (st->done == 0) {
+    long long c[3];
+    for (int a = 0; a < 3; ++a)
+      c[a] = static_cast<long long>(cell_of(static_cast<double>(target[j * ld + a]), grid->h)) - grid->lo[a];
+    key = static_cast<unsigned long long>((c[0] * grid->dims[1] + c[1]) * grid->dims[2] + c[2]);
+  }
+  keys[j] = key;
+  vals[j] = j;
+}
+
+__global__ __launch_bounds__(kBlock) void icp_records_kernel(const float* __restrict__ target, int m, long long ld,
+                                                             const int* __restrict__ order, float4* __restrict__ recs) {
+  const int p = blockIdx.x * kBlock + threadIdx.x;
+  if (p >= m) return;
+  const int j = order[p];
+  recs[p] = make_float4(target[j * ld], target[j * ld + 1], target[j * ld + 2], __int_as_float(j));
+}
+
+// ---- neighbour step --------------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ int lower_bound(const unsigned long long* __restrict__ keys, int m, unsigned long long key) {
+  int lo = 0, n = m;
+  while (n > 0) {
+    const int half = n >> 1;
+    if (keys[lo + half] < key) {
+      lo += half + 1;
+      n -= half + 1;
+    } else {
+      n = half;
+    }
+  }
+  return lo;
+}
+
+// Nearest target with d2 < r2 (lowest index among equal d2), or -1; *best = its d2, *rec = its record.
+__device__ int nearest(double qx, double qy, double qz, const unsigned long long* __restrict__ keys,
+                       const float4* __restrict__ recs, int m, const Grid& g, double r2, double* best, float4* rec) {
+  int bj = -1;
+  double bd = INFINITY;
+  float4 br = make_float4(0.f, 0.f, 0.f, 0.f);
+  *best = bd;
+  *rec = br;
+  if (m == 0 || g.dims[0] == 0 || !(isfinite(qx) && isfinite(qy) && isfinite(qz))) return -1;
+  const double q[3] = {qx, qy, qz};
+  long long c[3];
+  for (int a = 0; a < 3; ++a) {
+    const double ca = cell_of(q[a], g.h) - static_cast<double>(g.lo[a]);  // exact: both are integers below 2^31
+    if (ca < -1.0 || ca > static_cast<double>(g.dims[a])) return -1;     // no occupied cell next to the query's
+    c[a] = static_cast<long long>(ca);
+  }
+  const long long z0 = c[2] - 1 < 0 ? 0 : c[2] - 1, z1 = c[2] + 1 >= g.dims[2] ? g.dims[2] - 1 : c[2] + 1;
+  if (z0 > z1) return -1;
+  for (long long x = c[0] - 1; x <= c[0] + 1; ++x) {
+    if (x < 0 || x >= g.dims[0]) continue;
+    for (long long y = c[1] - 1; y <= c[1] + 1; ++y) {
+      if (y < 0 || y >= g.dims[1]) continue;
+      const long long col = (x * g.dims[1] + y) * g.dims[2];
+      const unsigned long long khi = static_cast<unsigned long long>(col + z1);
+      for (int p = lower_bound(keys, m, static_cast<unsigned long long>(col + z0)); p < m && keys[p] <= khi; ++p) {
+        const float4 r = recs[p];
+        const double dx = qx - static_cast<double>(r.x), dy = qy - static_cast<double>(r.y),
+                     dz = qz - static_cast<double>(r.z);
+        const double d2 = ((dx * dx) + (dy * dy)) + (dz * dz);
+        const int j = __float_as_int(r.w);
+        if (d2 < r2 && (d2 < bd || (d2 == bd && j < bj))) {
+          bd = d2;
+          bj = j;
+          br = r;
+        }
+      }
+    }
+  }
+  *best = bd;
+  *rec = br;
+  return bj;
+}
+
+// pcd = init . source (or the source as is), as float64
+__global__ __launch_bounds__(kBlock) void icp_init_kernel(const float* __restrict__ source, int n, long long ld, Mat16 init,
+                                                          int apply, double* __restrict__ pcd) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  double x = source[i * ld], y = source[i * ld + 1], z = source[i * ld + 2];
+  if (apply) {
+    const double M[12] = {init.v[0], init.v[1], init.v[2], init.v[3], init.v[4], init.v[5],
+                          init.v[6], init.v[7], init.v[8], init.v[9], init.v[10], init.v[11]};
+    apply_rt(M, x, y, z);
+  }
+  pcd[3ll * i] = x;
+  pcd[3ll * i + 1] = y;
+  pcd[3ll * i + 2] = z;
+}
+
+// One evaluation: (apply the pending update to the pcd point,) search, block partials
+// {count, err2, sum pcd xyz, sum target xyz} -> slab[block][8].  d2_out: optional (-1 where there is no neighbour).
+__global__ __launch_bounds__(kBlock) void icp_search_kernel(double* __restrict__ pcd, int n, int apply,
+                                                            const unsigned long long* __restrict__ keys,
+                                                            const float4* __restrict__ recs, int m, const Grid* __restrict__ grid,
+                                                            double r2, const IcpState* __restrict__ st, int* __restrict__ idx,
+                                                            double* __restrict__ d2_out, double* __restrict__ slab) {
+  if (st->done) return;
+  const Grid g = *grid;
+  double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+    double x = pcd[3ll * i], y = pcd[3ll * i + 1], z = pcd[3ll * i + 2];
+    if (apply) {
+      apply_rt(st->U, x, y, z);
+      pcd[3ll * i] = x;
+      pcd[3ll * i + 1] = y;
+      pcd[3ll * i + 2] = z;
+    }
+    double d2;
+    float4 r;
+    const int j = nearest(x, y, z, keys, recs, m, g, r2, &d2, &r);
+    idx[i] = j;
+    if (d2_out) d2_out[i] = j >= 0 ? d2 : -1.0;
+    if (j >= 0) {
+      acc[0] += 1.0;
+      acc[1] += d2;
+      acc[2] += x;
+      acc[3] += y;
+      acc[4] += z;
+      acc[5] += static_cast<double>(r.x);
+      acc[6] += static_cast<double>(r.y);
+      acc[7] += static_cast<double>(r.z);
+    }
+  }
+  const double s = block_sum<8>(acc, threadIdx.x);
+  if (threadIdx.x < 8) slab[blockIdx.x * 8 + threadIdx.x] = s;
+}
+
+}  // namespace
+
+namespace {
+
+// One block: means of the correspondences from the search slabs.
+__global__ __launch_bounds__(kBlock) void icp_mean_kernel(const double* __restrict__ slab, int rows, IcpState* __restrict__ st) {
+  if (st->done) return;
+  const double s = slab_sum<8>(slab, rows, threadIdx.x);
+  __shared__ double tot[8];
+  if (threadIdx.x < 8) tot[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double cnt = tot[0];
+    st->n_corr = static_cast<long long>(cnt);
+    st->err2 = tot[1];
+    for (int a = 0; a < 3; ++a) {
+      st->ms[a] = cnt > 0.0 ? tot[2 + a] / cnt : 0.0;
+      st->mt[a] = cnt > 0.0 ? tot[5 + a] / cnt : 0.0;
+    }
+  }
+}
+
+// Demeaned covariance H[a][b] = sum (p - ms)_a (t - mt)_b over the correspondences -> slab[block][9].
+__global__ __launch_bounds__(kBlock) void icp_cov_kernel(const double* __restrict__ pcd, int n, const float* __restrict__ target,
+                                                         long long ld, const int* __restrict__ idx,
+                                                         const IcpState* __restrict__ st, double* __restrict__ slab) {
+  if (st->done) return;
+  const double ms[3] = {st->ms[0], st->ms[1], st->ms[2]}, mt[3] = {st->mt[0], st->mt[1], st->mt[2]};
+  double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+    const int j = idx[i];
+    if (j < 0) continue;
+    double p[3], t[3];
+    for (int a = 0; a < 3; ++a) {
+      p[a] = pcd[3ll * i + a] - ms[a];
+      t[a] = static_cast<double>(target[j * ld + a]) - mt[a];
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) acc[3 * a + b] += p[a] * t[b];
+  }
+  const double s = block_sum<9>(acc, threadIdx.x);
+  if (threadIdx.x < 9) slab[blockIdx.x * 9 + threadIdx.x] = s;
+}
+
+// One block, evaluation k: fitness / rmse, convergence test, Kabsch update, composition, history record k, outputs.
+__global__ __launch_bounds__(kBlock) void icp_finalize_kernel(const double* __restrict__ slab, int rows, IcpState* __restrict__ st,
+                                                              int k, int max_iteration, int n_source, double relative_fitness,
+                                                              double relative_rmse, double* __restrict__ history,
+                                                              double* __restrict__ transform, double* __restrict__ fit_rmse,
+                                                              int32_t* __restrict__ stats) {
+  if (st->done) return;
+  const double s = slab_sum<9>(slab, rows, threadIdx.x);
+  __shared__ double H[9];
+  if (threadIdx.x < 9) H[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const long long nc = st->n_corr;
+  const double fitness = nc > 0 ? static_cast<double>(nc) / static_cast<double>(n_source) : 0.0;
+  const double rmse = nc > 0 ? sqrt(st->err2 / static_cast<double>(nc)) : 0.0;
+  const bool converged = k > 0 && fabs(st->fitness - fitness) < relative_fitness && fabs(st->rmse - rmse) < relative_rmse;
+  const bool stop = converged || k >= max_iteration || n_source == 0;
+  st->fitness = fitness;
+  st->rmse = rmse;
+  double U[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  if (!stop) {
+    if (nc > 0) {
+      double h[9], R[9];
+      for (int q = 0; q < 9; ++q) h[q] = H[q];
+      kabsch_rotation(h, R);
+      for (int a = 0; a < 3; ++a) {
+        for (int b = 0; b < 3; ++b) U[4 * a + b] = R[3 * a + b];
+        U[4 * a + 3] = st->mt[a] - ((R[3 * a] * st->ms[0] + R[3 * a + 1] * st->ms[1]) + R[3 * a + 2] * st->ms[2]);
+      }
+    }
+    double T[16];
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 4; ++b)
+        T[4 * a + b] = ((U[4 * a] * st->T[b] + U[4 * a + 1] * st->T[4 + b]) + U[4 * a + 2] * st->T[8 + b]) + U[4 * a + 3] * st->T[12 + b];
+    for (int b = 0; b < 4; ++b) T[12 + b] = st->T[12 + b];
+    for (int q = 0; q < 16; ++q) st->T[q] = T[q];
+    st->updates = k + 1;
+  }
+  for (int q = 0; q < 12; ++q) st->U[q] = U[q];
+  if (history) {
+    double* rec = history + static_cast<long long>(k) * kRecord;
+    rec[0] = fitness;
+    rec[1] = rmse;
+    rec[2] = static_cast<double>(nc);
+    for (int q = 0; q < 12; ++q) rec[3 + q] = U[q];
+  }
+  for (int q = 0; q < 16; ++q) transform[q] = st->T[q];
+  fit_rmse[0] = fitness;
+  fit_rmse[1] = rmse;
+  stats[0] = st->updates;
+  stats[1] = static_cast<int32_t>(nc);
+  if (stop) st->done = 1;
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------
+
+int point_blocks(int64_t n) {
+  const int64_t b = (n + kBlock - 1) / kBlock;
+  return static_cast<int>(b < 1 ? 1 : (b > kMaxBlocks ? kMaxBlocks : b));
+}
+
+size_t sort_temp_bytes(int64_t m) {
+  size_t bytes = 0;
+  if (m > 0 &&
+      rocprim::radix_sort_pairs(nullptr, bytes, static_cast<const unsigned long long*>(nullptr),
+                                static_cast<unsigned long long*>(nullptr), static_cast<const int*>(nullptr),
+                                static_cast<int*>(nullptr), static_cast<unsigned>(m)) != hipSuccess)
+    return 0;
+  return bytes;
+}
+
+struct Work {
+  double* pcd;
+  int* idx;
+  double* slab;
+  double* slab_cov;
+  IcpState* st;
+  Grid* grid;
+  unsigned long long *keys_in, *keys;
+  int *vals_in, *order;
+  float4* recs;
+  void* sort_tmp;
+  size_t sort_bytes;
+};
+
+bool carve(Arena& ar, int64_t n, int64_t m, Work& w) {
+  w.pcd = ar.take<double>(static_cast<size_t>(n > 0 ? n : 1) * 3);
+  w.idx = ar.take<int>(n > 0 ? n : 1);
+  w.slab = ar.take<double>(kMaxBlocks * 8);
+  w.slab_cov = ar.take<double>(kMaxBlocks * 9);
+  w.st = ar.take<IcpState>(1);
+  w.grid = ar.take<Grid>(1);
+  const size_t mm = static_cast<size_t>(m > 0 ? m : 1);
+  w.keys_in = ar.take<unsigned long long>(mm);
+  w.keys = ar.take<unsigned long long>(mm);
+  w.vals_in = ar.take<int>(mm);
+  w.order = ar.take<int>(mm);
+  w.recs = ar.take<float4>(mm);
+  w.sort_bytes = sort_temp_bytes(m);
+  w.sort_tmp = ar.take<char>(w.sort_bytes > 0 ? w.sort_bytes : 1);
+  return ar.ok;
+}
+
+double search_r2(double r) { return static_cast<double>(static_cast<float>(r * r)); }
+
+// Target index and a fresh state (T = init).
+int build_index(const float* target, int64_t m, int64_t ld, double r2, const Mat16& init, Work& w, hipStream_t st) {
+  const double h = sqrt(r2) * (1.0 + 1e-6);
+  const int tb = point_blocks(m);
+  hipLaunchKernelGGL(icp_bbox_kernel, dim3(tb), dim3(kBlock), 0, st, target, static_cast<int>(m), static_cast<long long>(ld), h,
+                     w.slab);
+  hipLaunchKernelGGL(icp_setup_kernel, dim3(1), dim3(kBlock), 0, st, w.slab, tb, static_cast<int>(m), h, init, w.grid, w.st);
+  if (m > 0) {
+    const unsigned blocks = static_cast<unsigned>((m + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(icp_key_kernel, dim3(blocks), dim3(kBlock), 0, st, target, static_cast<int>(m), static_cast<long long>(ld),
+                       w.grid, w.st, w.keys_in, w.vals_in);
+    size_t bytes = w.sort_bytes;
+    RDM_HIP_CHECK(rocprim::radix_sort_pairs(w.sort_tmp, bytes, w.keys_in, w.keys, w.vals_in, w.order, static_cast<unsigned>(m), 0u,
+                                            64u, st));
+    hipLaunchKernelGGL(icp_records_kernel, dim3(blocks), dim3(kBlock), 0, st, target, static_cast<int>(m),
+                       static_cast<long long>(ld), w.order, w.recs);
+  }
+  return launch_status("icp target index");
+}
+
+int read_done(const IcpState* st_dev, int* done, hipStream_t st) {
+  RDM_HIP_CHECK(hipMemcpyAsync(done, &st_dev->done, sizeof(int), hipMemcpyDeviceToHost, st));
+  RDM_HIP_CHECK(hipStreamSynchronize(st));
+  return RDM_OK;
+}
+
+const Mat16 kIdentity = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
+
+}  // namespace
+
+extern "C" size_t rdm_icp_workspace_bytes(int64_t n_source, int64_t n_target) {
+  using namespace rdm;
+  Arena ar(nullptr, 0);
+  Work w;
+  carve(ar, n_source, n_target, w);
+  return ar.off;
+}
+
+extern "C" int rdm_icp_point_to_point(const float* source, int64_t n_source, int64_t ld_source, const float* target,
+                                      int64_t n_target, int64_t ld_target, double max_correspondence_distance,
+                                      const double* init_host, int max_iteration, double relative_fitness, double relative_rmse,
+                                      double* transform, double* fitness_rmse, int32_t* stats, double* history, void* ws,
+                                      size_t ws_bytes, void* stream) {
+  using namespace rdm;
+  RDM_REQUIRE(transform && fitness_rmse && stats, "rdm_icp_point_to_point: null output");
+  RDM_REQUIRE(max_correspondence_distance > 0.0, "rdm_icp_point_to_point: max_correspondence_distance must be > 0 (got %g)",
+              max_correspondence_distance);
+  RDM_REQUIRE(n_source >= 0 && n_source < (1ll << 31) && n_target >= 0 && n_target < (1ll << 31) && max_iteration >= 0 &&
+                  ld_source >= 3 && ld_target >= 3 && relative_fitness >= 0.0 && relative_rmse >= 0.0,
+              "rdm_icp_point_to_point: bad arguments");
+  RDM_REQUIRE((source || n_source == 0) && (target || n_target == 0), "rdm_icp_point_to_point: null points");
+  Mat16 init = kIdentity;
+  bool identity = true;
+  if (init_host)
+    for (int q = 0; q < 16; ++q) {
+      init.v[q] = init_host[q];
+      identity = identity && init.v[q] == kIdentity.v[q];
+    }
+  const double r2 = search_r2(max_correspondence_distance);
+  RDM_REQUIRE(r2 > 0.0 && std::isfinite(r2), "rdm_icp_point_to_point: max_correspondence_distance^2 is not a positive float");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Arena ar(ws, ws_bytes);
+  Work w;
+  if (!carve(ar, n_source, n_target, w)) {
+    set_error("rdm_icp_point_to_point: workspace too small (%zu < %zu bytes)", ws_bytes, ar.off);
+    return RDM_ERR_WORKSPACE;
+  }
+  int rc = build_index(target, n_target, ld_target, r2, init, w, st);
+  if (rc != RDM_OK) return rc;
+  const int n = static_cast<int>(n_source), m = static_cast<int>(n_target), pb = point_blocks(n_source);
+  if (n > 0)
+    hipLaunchKernelGGL(icp_init_kernel, dim3(static_cast<unsigned>((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, source, n,
+                       static_cast<long long>(ld_source), init, identity ? 0 : 1, w.pcd);
+  int done = 0;
+  for (int k = 0; k <= max_iteration && done == 0;) {
+    const int end = max_iteration - k < kChunk ? max_iteration + 1 : k + kChunk;
+    for (; k < end; ++k) {
+      hipLaunchKernelGGL(icp_search_kernel, dim3(pb), dim3(kBlock), 0, st, w.pcd, n, k > 0 ? 1 : 0, w.keys, w.recs, m, w.grid, r2,
+                         w.st, w.idx, static_cast<double*>(nullptr), w.slab);
+      hipLaunchKernelGGL(icp_mean_kernel, dim3(1), dim3(kBlock), 0, st, w.slab, pb, w.st);
+      hipLaunchKernelGGL(icp_cov_kernel, dim3(pb), dim3(kBlock), 0, st, w.pcd, n, target, static_cast<long long>(ld_target), w.idx,
+                         w.st, w.slab_cov);
+      hipLaunchKernelGGL(icp_finalize_kernel, dim3(1), dim3(kBlock), 0, st, w.slab_cov, pb, w.st, k, max_iteration, n,
+                         relative_fitness, relative_rmse, history, transform, fitness_rmse, stats);
+    }
+    rc = launch_status("rdm_icp_point_to_point");
+    if (rc != RDM_OK) return rc;
+    rc = read_done(w.st, &done, st);  // one 4-byte read-back per chunk
+    if (rc != RDM_OK) return rc;
+  }
+  if (done == 2) {
+    set_error("rdm_icp_point_to_point: a target point is not finite or lies beyond 2^30 cells of %g m from the origin",
+              sqrt(r2));
+    return RDM_ERR_ARG;
+  }
+  return RDM_OK;
+}
+
+extern "C" int rdm_icp_correspondences(const double* pcd, int64_t n, const float* target, int64_t n_target, int64_t ld_target,
+                                       double max_correspondence_distance, int32_t* idx, double* d2, void* ws, size_t ws_bytes,
+                                       void* stream) {
+  using namespace rdm;
+  RDM_REQUIRE(idx && d2, "rdm_icp_correspondences: null output");
+  RDM_REQUIRE(max_correspondence_distance > 0.0, "rdm_icp_correspondences: max_correspondence_distance must be > 0 (got %g)",
+              max_correspondence_distance);
+  RDM_REQUIRE(n >= 0 && n < (1ll << 31) && n_target >= 0 && n_target < (1ll << 31) && ld_target >= 3,
+              "rdm_icp_correspondences: bad arguments");
+  RDM_REQUIRE((pcd || n == 0) && (target || n_target == 0), "rdm_icp_correspondences: null points");
+  const double r2 = search_r2(max_correspondence_distance);
+  RDM_REQUIRE(r2 > 0.0 && std::isfinite(r2), "rdm_icp_correspondences: max_correspondence_distance^2 is not a positive float");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Arena ar(ws, ws_bytes);
+  Work w;
+  if (!carve(ar, 0, n_target, w)) {
+    set_error("rdm_icp_correspondences: workspace too small (%zu < %zu bytes)", ws_bytes, ar.off);
+    return RDM_ERR_WORKSPACE;
+  }
+  int rc = build_index(target, n_target, ld_target, r2, kIdentity, w, st);
+  if (rc != RDM_OK) return rc;
+  if (n > 0)
+    hipLaunchKernelGGL(icp_search_kernel, dim3(point_blocks(n)), dim3(kBlock), 0, st, const_cast<double*>(pcd), static_cast<int>(n),
+                       0, w.keys, w.recs, static_cast<int>(n_target), w.grid, r2, w.st, idx, d2, w.slab);
+  rc = launch_status("rdm_icp_correspondences");
+  if (rc != RDM_OK) return rc;
+  int done = 0;
+  rc = read_done(w.st, &done, st);
+  if (rc != RDM_OK) return rc;
+  if (done == 2) {
+    set_error("rdm_icp_correspondences: a target point is not finite or lies beyond 2^30 cells of %g m from the origin", sqrt(r2));
+    return RDM_ERR_ARG;
+  }
+  return RDM_OK;
+}

@@ -574,6 +574,87 @@ def ransac_correspondences(src_corr, ref_corr, distance_threshold=0.3, ransac_n=
     return (T, stats, rmse, hyp) if return_hypotheses else (T, stats, rmse)
 
 
+class RegistrationResult:
+    """Named as Open3D's: transformation (float64 [4, 4], numpy), fitness, inlier_rmse, num_correspondences (of the last
+    evaluation), iterations (updates applied) and, when asked for, history (float64 [evaluations, 15] numpy: per
+    evaluation k {fitness, rmse, n_corr, update_k as 12 row-major R|t values}; row 0 is the initial evaluation)."""
+
+    def __init__(self, transformation, fitness, inlier_rmse, num_correspondences, iterations, history=None):
+        self.transformation = transformation
+        self.fitness = fitness
+        self.inlier_rmse = inlier_rmse
+        self.num_correspondences = num_correspondences
+        self.iterations = iterations
+        self.history = history
+
+    def __repr__(self):
+        return (f'RegistrationResult(fitness={self.fitness:.6e}, inlier_rmse={self.inlier_rmse:.6e}, '
+                f'num_correspondences={self.num_correspondences}, iterations={self.iterations})')
+
+
+def _points_arg(t, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] >= 3):
+        raise ValueError(f'{name} must be a float32 CUDA tensor [N, >=3]')
+    if t.shape[0] > 0 and t.stride(1) != 1:
+        raise ValueError(f'{name} must have unit column stride')
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def icp_point_to_point(source, target, max_correspondence_distance, init=None, max_iteration=30, relative_fitness=1e-6,
+                       relative_rmse=1e-6, history=False):
+    """Open3D's registration_icp with TransformationEstimationPointToPoint (no scaling) and ICPConvergenceCriteria (the
+    defaults are Open3D's), as preporcess/generate_kitti_pairs.py:157-172 runs it, on the GPU (rdm_icp_point_to_point).
+    source / target: float32 CUDA [N, >=3] (xyz first).  init: 4x4 (anything numpy accepts), None = identity.
+    -> RegistrationResult with host values (the call ends with the read-back of its results)."""
+    import numpy as np
+    L = _lib.lib()
+    lds, ldt = _points_arg(source, 'source'), _points_arg(target, 'target')
+    if source.device != target.device:
+        raise ValueError('source and target must be on the same device')
+    if not max_correspondence_distance > 0:
+        raise ValueError(f'max_correspondence_distance must be > 0, got {max_correspondence_distance}')
+    if int(max_iteration) < 0:
+        raise ValueError(f'max_iteration must be >= 0, got {max_iteration}')
+    init64 = np.eye(4) if init is None else np.ascontiguousarray(np.asarray(init, dtype=np.float64))
+    if init64.shape != (4, 4):
+        raise ValueError(f'init must be 4x4, got {init64.shape}')
+    dev = source.device
+    out = torch.empty((20,), dtype=torch.float64, device=dev)  # transform[16], fitness, rmse, stats (2 x int32) in one read-back
+    stats = out[18:].view(torch.int32)
+    hist = torch.empty((int(max_iteration) + 1, 15), dtype=torch.float64, device=dev) if history else None
+    ws = scratch(dev, L.rdm_icp_workspace_bytes(source.shape[0], target.shape[0]))
+    _lib.check(L.rdm_icp_point_to_point(_lib.ptr(source), source.shape[0], lds, _lib.ptr(target), target.shape[0], ldt,
+                                        float(max_correspondence_distance), init64.ctypes.data, int(max_iteration),
+                                        float(relative_fitness), float(relative_rmse), out.data_ptr(), out[16:].data_ptr(),
+                                        stats.data_ptr(), _lib.ptr(hist), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+               'rdm_icp_point_to_point')
+    host = out.cpu().numpy()
+    iters, n_corr = (int(x) for x in host[18:19].view(np.int32))
+    h = hist[:iters + 1].cpu().numpy() if history else None
+    return RegistrationResult(host[:16].reshape(4, 4).copy(), float(host[16]), float(host[17]), n_corr, iters, h)
+
+
+def icp_correspondences(pcd, target, max_correspondence_distance):
+    """The evaluation step of icp_point_to_point alone: pcd float64 CUDA [N, 3] (contiguous), target float32 CUDA
+    [M, >=3] -> (idx int32 [N], -1 = none; d2 float64 [N], -1 where idx is -1), on the device."""
+    L = _lib.lib()
+    if not (isinstance(pcd, torch.Tensor) and pcd.is_cuda and pcd.dtype == torch.float64 and pcd.dim() == 2 and pcd.shape[1] == 3):
+        raise ValueError('pcd must be a float64 CUDA tensor [N, 3]')
+    pcd = pcd.contiguous()
+    ldt = _points_arg(target, 'target')
+    if not max_correspondence_distance > 0:
+        raise ValueError(f'max_correspondence_distance must be > 0, got {max_correspondence_distance}')
+    n = pcd.shape[0]
+    idx = torch.empty((max(n, 1),), dtype=torch.int32, device=pcd.device)
+    d2 = torch.empty((max(n, 1),), dtype=torch.float64, device=pcd.device)
+    ws = scratch(pcd.device, L.rdm_icp_workspace_bytes(0, target.shape[0]))
+    _lib.check(L.rdm_icp_correspondences(_lib.ptr(pcd), n, _lib.ptr(target), target.shape[0], ldt,
+                                         float(max_correspondence_distance), idx.data_ptr(), d2.data_ptr(), ws.data_ptr(),
+                                         ws.numel(), _lib.stream_ptr()),
+               'rdm_icp_correspondences')
+    return idx[:n], d2[:n]
+
+
 def _gt_check(t, name, shape, dtype, device):
     if not isinstance(t, torch.Tensor):
         raise RuntimeError(f'gt_node_correspondences: {name} must be a tensor')

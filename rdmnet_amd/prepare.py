@@ -1,0 +1,239 @@
+"""Derived KITTI trees from raw data, the two trees `dataset.OdometryKittiPairDataset` reads:
+
+  python -m rdmnet_amd.prepare downsample --dataset-root R [--sequences 0 ... 10]
+      R/sequences/%02d/velodyne/*.bin (f32 [N, 4]) -> R/downsampled_xyzi/%02d/<frame>.npy (f32 [M, 4]): centroid voxel
+      down-sampling at 0.3 m of xyz + intensity on the GPU (ops.voxel_downsample), as preporcess/downsample_pcd_kitti.py
+      does with Open3D.
+  python -m rdmnet_amd.prepare pairs --dataset-root R [--sequences 8 9 10] [--thres 10] [--max-iteration 5000]
+                                     [--distance 0.5]
+      R/poses/%02d.txt + R/calib/sequences/%02d/calib.txt + the raw scans -> R/icp{thres}/%02d: the pair lists with
+      ICP-refined poses, restating preporcess/generate_kitti_pairs.py:95-195 with the GPU ICP (ops.icp_point_to_point).
+
+Stated deviations from the reference's pair script:
+  * the pair file is written fresh; the reference appends to it (its `open(..., 'a')`), so a rerun doubles it;
+  * the odometry pose M is handed to the ICP as its `init` instead of being applied to the scan on the host first: the
+    same algorithm, only the rounding of the first transform differs (the file holds reg.transformation @ M, the
+    composition the reference's issue.md explains);
+  * where the reference would loop forever (the frame before the first far one is not a frame id), this raises.
+"""
+import argparse
+import glob
+import os
+import os.path as osp
+import queue
+import threading
+
+import numpy as np
+
+DOWNSAMPLE_VOXEL = 0.3
+WINDOW = 100  # frames looked ahead for the next pair (generate_kitti_pairs.py:131)
+
+
+def read_poses(path):
+    """R/poses/%02d.txt -> float64 [F, 4, 4] (camera-frame poses, T_w_cam0), one row per frame."""
+    rows = np.genfromtxt(path).reshape(-1, 12)
+    pos = np.zeros((rows.shape[0], 4, 4))
+    pos[:, :3, :] = rows.reshape(-1, 3, 4)
+    pos[:, 3, 3] = 1.0
+    return pos
+
+
+def read_velo2cam(path):
+    """calib.txt -> the reference's `velo2cam` (get_velo2cam): the last line whose value parses as 12 floats (Tr in a
+    KITTI odometry calib.txt) as a 4x4, TRANSPOSED, as the reference keeps it."""
+    calib = None
+    with open(path) as f:
+        for line in f:
+            if ':' not in line:
+                continue
+            try:
+                v = np.array([float(x) for x in line.split(':', 1)[1].split()])
+            except ValueError:
+                continue
+            if v.size == 12:
+                calib = v
+    if calib is None:
+        raise ValueError(f'{path}: no line with 12 values')
+    return np.vstack([calib.reshape(3, 4), [0, 0, 0, 1]]).T
+
+
+def relative_transform(velo2cam, pose0, pose1):
+    """generate_kitti_pairs.py:151-152: M maps scan `curr` (pose0) into the velodyne frame of scan `next` (pose1)."""
+    return (velo2cam @ pose0.T @ np.linalg.inv(pose1.T) @ np.linalg.inv(velo2cam)).T
+
+
+def pair_frames(frame_ids, translations, thres, window=WINDOW):
+    """The pairing loop of generate_kitti_pairs.py:124-186 -> [(curr, next)].  Frame ids index the rows of
+    `translations` directly.  From curr (the first id): the frames curr ... curr+window-1 farther than `thres` from curr;
+    none -> curr + 1; else next = (the first of them) - 1 is a pair if it is a frame id, and curr = next + 1.  The loop
+    ends when curr is not a frame id."""
+    ids = sorted(int(i) for i in frame_ids)
+    have = set(ids)
+    T = np.asarray(translations, dtype=np.float64)
+    pairs = []
+    curr = ids[0] if ids else None
+    while curr in have:
+        if curr >= T.shape[0]:
+            raise ValueError(f'frame {curr} has no pose (the pose file has {T.shape[0]} rows)')
+        dist = np.sqrt(((T[curr:curr + window] - T[curr]) ** 2).sum(-1))  # = the reference's pdist[curr][curr:curr+window]
+        far = np.where(dist > thres)[0]
+        if len(far) == 0:
+            curr += 1
+            continue
+        nxt = int(far[0]) + curr - 1
+        if nxt not in have:
+            raise ValueError(f'frame {nxt} (before the first frame farther than {thres} m from {curr}) is missing: the '
+                             'reference loops forever here')
+        pairs.append((curr, nxt))
+        curr = nxt + 1
+    return pairs
+
+
+def format_pair_line(curr, nxt, transform):
+    """One line of R/icp{thres}/%02d: `curr next` and the first three rows of the pose, '%.6f ' each (a trailing blank
+    before the newline, as the reference writes it)."""
+    v = np.asarray(transform, dtype=np.float64).reshape(-1)[:12]
+    return f'{curr} {nxt} ' + ''.join(f'{x:.6f} ' for x in v) + '\n'
+
+
+def _velodyne(root, seq):
+    return osp.join(root, 'sequences', '%02d' % seq, 'velodyne')
+
+
+def frame_ids(root, seq):
+    files = glob.glob(osp.join(_velodyne(root, seq), '*.bin'))
+    if not files:
+        raise FileNotFoundError(f'no scans under {_velodyne(root, seq)}')
+    return sorted(int(osp.basename(f)[:-4]) for f in files)
+
+
+def read_scan(root, seq, frame):
+    return np.fromfile(osp.join(_velodyne(root, seq), '%06d.bin' % frame), dtype=np.float32).reshape(-1, 4)
+
+
+def _read_ahead(load, keys, depth=2):
+    """Yields (key, load(key)) in order; a background thread reads up to `depth` items ahead."""
+    q = queue.Queue(maxsize=depth)
+    stop = threading.Event()
+
+    def work():
+        for k in keys:
+            try:
+                item = (k, load(k), None)
+            except Exception as e:  # surfaced in the consumer
+                item = (k, None, e)
+            while not stop.is_set():
+                try:
+                    q.put(item, timeout=0.1)
+                    break
+                except queue.Full:
+                    continue
+            if stop.is_set() or item[2] is not None:
+                return
+
+    t = threading.Thread(target=work, daemon=True)
+    t.start()
+    try:
+        for _ in keys:
+            k, v, err = q.get()
+            if err is not None:
+                raise err
+            yield k, v
+    finally:
+        stop.set()
+
+
+def downsample_sequence(root, seq, voxel=DOWNSAMPLE_VOXEL, log=print):
+    """R/sequences/%02d/velodyne/*.bin -> R/downsampled_xyzi/%02d/<frame>.npy (f32 [M, 4])."""
+    import torch
+    from . import ops
+    out_dir = osp.join(root, 'downsampled_xyzi', '%02d' % seq)
+    os.makedirs(out_dir, exist_ok=True)
+    ids = frame_ids(root, seq)
+    for frame, pts in _read_ahead(lambda f: read_scan(root, seq, f), ids):
+        got = ops.voxel_downsample(torch.from_numpy(pts).cuda(), voxel).cpu().numpy()
+        np.save(osp.join(out_dir, '%06d.npy' % frame), got)
+    log(f'sequence {seq:02d}: {len(ids)} scans down-sampled into {out_dir}')
+    return len(ids)
+
+
+class _RawPairs:
+    """Items for dataset.PairStager: ref_points = scan `next` (the ICP target), src_points = scan `curr` (the source)."""
+
+    def __init__(self, root, seq, pairs):
+        self.root, self.seq, self.pairs = root, seq, pairs
+
+    def __len__(self):
+        return len(self.pairs)
+
+    def __getitem__(self, i):
+        curr, nxt = self.pairs[i]
+        return {'curr': curr, 'next': nxt, 'ref_points': read_scan(self.root, self.seq, nxt)[:, :3],
+                'src_points': read_scan(self.root, self.seq, curr)[:, :3]}
+
+
+def generate_pairs(root, seq, thres=10, max_iteration=5000, distance=0.5, log=print):
+    """R/icp{thres}/%02d for one sequence (generate_kitti_pairs.py:95-195) -> [(curr, next, pose f64 [4, 4])]."""
+    from . import ops
+    from .dataset import PairStager
+    ids = frame_ids(root, seq)
+    poses = read_poses(osp.join(root, 'poses', '%02d.txt' % seq))
+    velo2cam = read_velo2cam(osp.join(root, 'calib', 'sequences', '%02d' % seq, 'calib.txt'))
+    pairs = pair_frames(ids, poses[:, :3, 3], thres)
+    out_dir = osp.join(root, 'icp%d' % thres)
+    os.makedirs(out_dir, exist_ok=True)
+    out = []
+    with open(osp.join(out_dir, '%02d' % seq), 'w') as f:
+        for item, target, source in PairStager(_RawPairs(root, seq, pairs)):
+            curr, nxt = item['curr'], item['next']
+            M = relative_transform(velo2cam, poses[curr], poses[nxt])
+            reg = ops.icp_point_to_point(source, target, distance, init=M, max_iteration=max_iteration)
+            f.write(format_pair_line(curr, nxt, reg.transformation))
+            f.flush()
+            out.append((curr, nxt, reg.transformation))
+    log(f'sequence {seq:02d}: {len(out)} pairs written to {osp.join(out_dir, "%02d" % seq)}')
+    return out
+
+
+def _parser():
+    p = argparse.ArgumentParser(prog='python -m rdmnet_amd.prepare', description=__doc__.split('\n\n')[0])
+    sub = p.add_subparsers(dest='command', required=True)
+    d = sub.add_parser('downsample', help='raw scans -> downsampled_xyzi (0.3 m voxels, xyz + intensity)')
+    d.add_argument('--dataset-root', required=True)
+    d.add_argument('--sequences', type=int, nargs='+', default=list(range(11)))
+    q = sub.add_parser('pairs', help='poses + raw scans -> icp{thres} pair lists with ICP-refined poses',
+                       description='The default sequences are the reference\'s test split.  test_data_loader calibrates its '
+                                   'neighbour limits on the train split, so a tree for it also needs --sequences 0 1 2 3 4 5.')
+    q.add_argument('--dataset-root', required=True)
+    q.add_argument('--sequences', type=int, nargs='+', default=[8, 9, 10],
+                   help='default 8 9 10 (the test split); test_data_loader also needs 0 ... 5 (it calibrates on the train split)')
+    q.add_argument('--thres', type=int, default=10, help='pair distance in metres (default 10)')
+    q.add_argument('--max-iteration', type=int, default=5000)
+    q.add_argument('--distance', type=float, default=0.5, help='ICP max correspondence distance in metres (default 0.5)')
+    return p
+
+
+def main(argv=None):
+    p = _parser()
+    a = p.parse_args(argv)
+    if any(s < 0 for s in a.sequences):
+        p.error('sequences must be >= 0')
+    if not osp.isdir(a.dataset_root):
+        p.error(f'--dataset-root {a.dataset_root} is not a directory')
+    if a.command == 'pairs':
+        if a.thres < 0:
+            p.error('--thres must be >= 0')
+        if a.max_iteration < 0:
+            p.error('--max-iteration must be >= 0')
+        if not a.distance > 0:
+            p.error('--distance must be > 0')
+        for s in a.sequences:
+            generate_pairs(a.dataset_root, s, a.thres, a.max_iteration, a.distance)
+    else:
+        for s in a.sequences:
+            downsample_sequence(a.dataset_root, s)
+    return 0
+
+
+if __name__ == '__main__':
+    raise SystemExit(main())
