@@ -11,7 +11,12 @@ whole job.  One process per GPU; pairs are sharded rank-strided with no data-pat
 one all_gather of result records at the end (RCCL).
 
   python bench.py --gpus 1 --steps 20 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 3 --full    # + the side figures, roofline passes and CPU baseline
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the result line: the side passes after
+the timed region (full tables, one pair per call, host to host, drop-in API, the one-stream roofline and latency passes),
+the real-slot counts before it and the CPU baseline run with --full only.  Their keys are null in a plain run's line.
 """
 import argparse
 import collections
@@ -191,7 +196,10 @@ def main():
     ap.add_argument('--steps', type=int, default=480)
     ap.add_argument('--warmup', type=int, default=16)
     ap.add_argument('--pairs', type=int, default=8, help='distinct synthetic pairs cycled through')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline: the real-slot counts, the side passes after the timed region\n'
+                         '(full tables, one pair per call, host to host, drop-in API, one-stream roofline and latency) and the CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--streams', type=int, default=4, help='pairs in flight per GPU (host threads, one HIP stream each)')
     ap.add_argument('--path', choices=['engine', 'python'], default='engine',
                     help='engine: one native call per pair (rdm_engine_run); python: per-op mirror (rdmnet_amd.model)')
@@ -212,15 +220,15 @@ def main():
                     help='untimed pairs run for this long before the warm-up steps so that host and GPU clocks are at their\n'
                          'steady state (a fresh box is 15-20 %% slower for its first seconds); 0 = none')
     ap.add_argument('--full-steps', type=int, default=96,
-                    help='pairs of the all-13-tables pass of the engine path after the timed region (0 = skip)')
+                    help='with --full: pairs of the all-13-tables pass of the engine path after the timed region (0 = skip)')
     ap.add_argument('--host-steps', type=int, default=96,
-                    help='pairs of the host-to-host pass that follows the timed region (0 = skip)')
+                    help='with --full: pairs of the host-to-host pass that follows the timed region (0 = skip)')
     ap.add_argument('--api-collate', choices=['native', 'python'], default='native',
                     help='collate of the drop-in-API pass: native = rdm_engine_collate (one call), python = 17 launches from Python')
     ap.add_argument('--api-steps', type=int, default=192,
-                    help='pairs of the drop-in-API pass (Python collate + model(data_dict)) after the timed region (0 = skip)')
+                    help='with --full: pairs of the drop-in-API pass (Python collate + model(data_dict)) after the timed region (0 = skip)')
     ap.add_argument('--real-slots', choices=['on', 'off'], default='on',
-                    help='on: count the real (non-padding) neighbour slots of every distinct pair before the run (8 untimed\n'
+                    help='with --full, on: count the real (non-padding) neighbour slots of every distinct pair before the run (8 untimed\n'
                          'collates) for the real-slot variant of the roofline; off: profile runs that should contain bench pairs only')
     ap.add_argument('--pin', choices=['on', 'off'], default='on',
                     help='with several ranks on one host: pin rank r to the r-th contiguous slice of the CPUs this job may use')
@@ -404,7 +412,7 @@ def main():
     # Slots of every KPConv layer's neighbour table that hold a real neighbour (the rest is padding behind them), per
     # distinct pair: the `real_slots` variant of the roofline.  Untimed; layer order = Encoder.forward (backbone.py:72-107).
     real_slots = {}
-    if args.real_slots == 'on':
+    if args.full and args.real_slots == 'on':
         for pid, (r_, s_) in enumerate(dev_pairs):
             dd = engines[0].collate(r_, s_)
             nb = [int((dd['neighbors'][l] < dd['points'][l].shape[0]).sum()) for l in range(5)]
@@ -541,7 +549,7 @@ def main():
     # never `value`: with the stage tensors kept the engine builds the reference's full tables (and every pair of a lock-step
     # group collates itself).
     full_tables = None
-    if args.path == 'engine' and args.full_steps > 0:
+    if args.full and args.path == 'engine' and args.full_steps > 0:
         def full_step(eng, i):
             eng.enable_profile(False)
             res = eng.run(*dev_tensors(i))
@@ -565,7 +573,7 @@ def main():
 
     # ---- the schedule of rounds 1-4 beside the lock-step groups: the same engines, streams and pairs, one pair per engine call
     one_by_one = None
-    if grouped and args.full_steps > 0:
+    if args.full and grouped and args.full_steps > 0:
         def single_step(eng, i):
             eng.enable_profile(False)
             res = eng.run(*dev_tensors(i))
@@ -582,7 +590,7 @@ def main():
     # in HOST memory).  Never `value`: a second, shorter region after the timed one.  Each in-flight pair copies its scans
     # from pinned host memory on its worker's stream, runs the engine, and copies the correspondences back.
     host_to_host = None
-    if args.path == 'engine' and args.host_steps > 0:
+    if args.full and args.path == 'engine' and args.host_steps > 0:
         pinned = [(torch.from_numpy(r).pin_memory(), torch.from_numpy(s_).pin_memory()) for r, s_, _ in pairs]
         staged = {}  # step -> the device copies its worker made (tensors_of runs on the worker's stream, right before the group)
 
@@ -613,7 +621,7 @@ def main():
     # reference's 31-key output_dict; in the headline's schedule a worker hands the data_dicts of the pairs it drew to ONE
     # model([data_dict, ...]) call (rdm_engine_forward_lockstep).  A second figure, never `value`.
     api = None
-    if args.api_steps > 0:
+    if args.full and args.api_steps > 0:
         if net is None:
             net = model.create_model(cfg).cuda(local_rank)
             net.load_state_dict(state)
@@ -758,7 +766,7 @@ def main():
     # engine as a user with one pair in flight gets it: latency mode on, rdm_engine_set_overlap).
     iso_prof = []
     iso_single_prof = []  # single pairs alone (one launch = one pair): the figure of rounds 1-4, whatever the timed region's schedule
-    if args.path == 'engine':
+    if args.full and args.path == 'engine':
         engines[0].set_pairs_in_flight(1)  # (these passes ARE one pair in flight: no GEMM residency cap)
         with torch.cuda.stream(streams[0] if streams[0] is not None else torch.cuda.Stream()):  # (never the null stream)
             engines[0].set_overlap(0)
@@ -919,7 +927,7 @@ def main():
                        'host_path': args.path,
                        'host_cpus_per_rank': budget, 'host_cpus_pinned': len(pinned_cpus) if pinned_cpus else None,
                        'gpu_max_hw_queues': pipeline.hw_queues(), 'clock_ramp_s': args.ramp_seconds, 'wait': 'spin' if wait_us == 0 else f'poll+sleep {wait_us}us',
-                       'parallelism': f'pairs sharded over {world} GPU(s)'},
+                       'parallelism': f'pairs sharded over {world} GPU(s)', 'full': args.full},
             'p50_ms_per_pair': float(np.median(lat)),
             'one_pair_in_flight': ({'p50_ms_per_pair': float(np.median(iso_lat)), 'pairs': len(iso_lat),
                                     'serial_p50_ms_per_pair': float(np.median(iso_serial)) if iso_serial else None,
@@ -944,7 +952,7 @@ def main():
             'roofline': roofline,
             'roofline_mfma': roofline_mfma,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             result['cpu_baseline'] = cpu_baseline(args.cache, args.pairs)
         else:
             result['cpu_baseline'] = None

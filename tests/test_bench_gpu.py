@@ -25,7 +25,7 @@ def run_bench(*args, env_extra=None, timeout=900):
 
 
 def test_two_ranks_self_spawned_on_one_device():
-    r = run_bench('--gpus', '2', '--steps', '8', '--warmup', '2', '--ramp-seconds', '0', '--streams', '2', '--pairs', '4',
+    r = run_bench('--gpus', '2', '--full', '--steps', '8', '--warmup', '2', '--ramp-seconds', '0', '--streams', '2', '--pairs', '4',
                   '--host-steps', '4', '--full-steps', '4', '--api-steps', '4', '--no-cpu-baseline', '--dist-backend', 'gloo', env_extra={'RDM_BENCH_SHARE_DEVICE': '1'})
     assert r['n_gpus'] == 2 and r['steps'] == 8 and r['scaling'] == 'weak' and r['unit'] == 'pairs/s'
     # a step = one engine call = one lock-step group of config.pairs_per_step pairs (round 5; --lockstep 1: one pair)
@@ -45,7 +45,8 @@ def test_two_ranks_self_spawned_on_one_device():
 
 
 def test_single_rank_line_has_the_contract_fields():
-    r = run_bench('--steps', '8', '--warmup', '2', '--ramp-seconds', '0', '--pairs', '2', '--host-steps', '4', '--full-steps', '4', '--api-steps', '8', '--no-cpu-baseline')
+    r = run_bench('--full', '--steps', '8', '--warmup', '2', '--ramp-seconds', '0', '--pairs', '2', '--host-steps', '4', '--full-steps', '4', '--api-steps', '8',
+                  '--no-cpu-baseline')
     assert r['config']['pairs_per_step'] >= 2 and r['config']['pairs_per_gpu'] == 8 * r['config']['pairs_per_step']
     assert r['roofline']['group_alone']['frac'] > 0 and r['roofline']['single_pair_alone']['frac'] > 0 and r['roofline']['launches'] > 0
     for key in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
@@ -71,11 +72,30 @@ def test_single_rank_line_has_the_contract_fields():
     assert r['config']['scheduler'] == 'rdmnet_amd.pipeline.PairPipeline'
 
 
+def test_plain_run_measures_the_headline_alone(tmp_path):
+    """Without --full the line keeps the headline and what the timed steps themselves recorded; the side passes, the one-stream
+    roofline and latency passes and the CPU baseline do not run, and --dump-outputs still writes the last timed step."""
+    out = tmp_path / 'dump'
+    r = run_bench('--steps', '8', '--warmup', '2', '--ramp-seconds', '0', '--pairs', '2', '--dump-outputs', str(out))
+    for key in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'dtype', 'config'):
+        assert key in r, key
+    assert r['config']['full'] is False and r['steps'] == 8 and r['warmup'] == 2 and r['unit'] == 'pairs/s' and r['higher_is_better']
+    pps = r['config']['pairs_per_step']
+    assert r['value'] > 0 and abs(r['value'] - 8 * pps / (r['ms_per_step'] * 8 / 1e3)) < 1e-6 * r['value']
+    assert r['records'] == {'gathered': 8 * pps, 'distinct_steps': 8 * pps, 'distinct_pairs': 2}
+    for key in ('one_pair_per_call', 'full_tables', 'host_to_host', 'drop_in_api', 'one_pair_in_flight', 'cpu_baseline'):
+        assert r[key] is None, key
+    rf = r['roofline']
+    assert rf['launches'] > 0 and rf['group_alone'] is None and rf['single_pair_alone'] is None and 'real_slots' not in rf
+    assert sorted(os.listdir(out)) == sorted(f'pair{k}_{name}.npy' for k in range(pps)
+                                             for name in ('transform', 'ref_corr_points', 'src_corr_points', 'corr_scores'))
+
+
 def test_single_rank_through_rccl():
     """The RCCL path on the one GPU a test box has: world size 1, backend nccl; the barriers, the record all_gather and
     the all_reduce(MAX) of the elapsed time go through the process group (the multi-GPU run's collectives,
     geotransformer/engine/base_tester.py:70-76,123-128 in the reference)."""
-    r = run_bench('--gpus', '1', '--force-dist', '--steps', '8', '--warmup', '2', '--ramp-seconds', '0', '--pairs', '2', '--host-steps', '4',
+    r = run_bench('--gpus', '1', '--force-dist', '--full', '--steps', '8', '--warmup', '2', '--ramp-seconds', '0', '--pairs', '2', '--host-steps', '4',
                   '--full-steps', '0', '--api-steps', '4', '--no-cpu-baseline', '--lockstep', '1', timeout=600)  # (one pair per call: rounds 1-4)
     assert r['config']['pairs_per_step'] == 1
     assert r['collective']['backend'] == 'nccl' and r['collective']['forced_single_rank'] and r['collective']['library'].startswith('RCCL')

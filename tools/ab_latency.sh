@@ -3,7 +3,7 @@ source "$(dirname "${BASH_SOURCE[0]}")/lab_env.sh"  # developer knobs live in th
 # prints the latency-mode p50 and the serial p50 (ms per pair) of bench.py's one-stream passes.
 N=$1; shift
 run() {
-  env $1 python bench.py --steps 24 --warmup 4 --streams 1 --ramp-seconds 1 --no-cpu-baseline --host-steps 0 --api-steps 0 --full-steps 0 --layer-events-every 0 --real-slots off 2>/dev/null | python -c "
+  env $1 python bench.py --full --steps 24 --warmup 4 --streams 1 --ramp-seconds 1 --no-cpu-baseline --host-steps 0 --api-steps 0 --full-steps 0 --layer-events-every 0 --real-slots off 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

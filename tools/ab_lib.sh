@@ -1,7 +1,7 @@
 # interleaved A/B of two builds of the library (same ABI) on one box:  bash tools/ab_lib.sh <other librdmnet_hip.so> [rounds] [streams]
 OTHER=$1; N=${2:-3}; S=${3:-4}
 run() {
-  python bench.py --streams $S --steps 320 --warmup 16 --ramp-seconds 2 --no-cpu-baseline --host-steps 0 --api-steps 0 2>/dev/null | python -c "
+  python bench.py --full --streams $S --steps 320 --warmup 16 --ramp-seconds 2 --no-cpu-baseline --host-steps 0 --api-steps 0 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

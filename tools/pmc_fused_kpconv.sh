@@ -7,7 +7,7 @@ for mode in fused default; do
   if [ $mode = fused ]; then export RDM_FUSED_KPCONV=1; else unset RDM_FUSED_KPCONV; fi
   for c in FETCH_SIZE WRITE_SIZE; do
     rm -rf $O/x_$c
-    rocprofv3 --kernel-trace --pmc $c -d $O/x_$c -- python bench.py --steps 4 --warmup 2 --ramp-seconds 0 --no-cpu-baseline --streams 1 --host-steps 0 --api-steps 0 > $O/x.log 2>&1
+    rocprofv3 --kernel-trace --pmc $c -d $O/x_$c -- python bench.py --full --steps 4 --warmup 2 --ramp-seconds 0 --no-cpu-baseline --streams 1 --host-steps 0 --api-steps 0 > $O/x.log 2>&1
   done
   python - "$(db $O/x_FETCH_SIZE)" "$(db $O/x_WRITE_SIZE)" $mode <<'PY' >> $O/r02_pmc_fused_kpconv.md
 import sqlite3, sys
