@@ -665,9 +665,10 @@ __global__ __launch_bounds__(1024) void topk_kernel(const float* s, int m, int n
 extern "C" int rdm_nms(const int64_t* idx, int64_t n, int64_t h, int64_t ldi, const int32_t* width,
                        uint8_t* keep, void* stream) {
   using namespace rdm;
-  RDM_REQUIRE(idx && keep && n >= 0 && h > 0, "rdm_nms: bad arguments");
+  RDM_REQUIRE(n >= 0, "rdm_nms: bad arguments");
+  if (n == 0) return RDM_OK;  // (before the pointer check: torch passes a null pointer for an empty table)
+  RDM_REQUIRE(idx && keep && h > 0, "rdm_nms: bad arguments");
   RDM_REQUIRE(n <= 150000, "rdm_nms: at most 150000 nodes (LDS-resident state)");
-  if (n == 0) return RDM_OK;
   ::rdm::launch<nms_kernel_body, nms_kernel, 1024>(dim3(1), static_cast<size_t>(n), static_cast<hipStream_t>(stream),
                      idx, static_cast<int>(n), static_cast<int>(h), static_cast<int>(ldi), width, keep);
   return launch_status("nms_kernel");
