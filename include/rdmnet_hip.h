@@ -500,6 +500,39 @@ int rdm_lgr(const float* log_scores, const float* ref_knn_points, const float* s
             float* src_corr, float* corr_scores, float* transform, int32_t* counts, void* ws, size_t ws_bytes,
             void* stream);
 
+/* cfg.fine_matching beyond the three keys of rdm_lgr (experiments/config.py:152-161; passed to LocalGlobalRegistration at
+ * experiments/model_infer.py:91-101).  The shipped values are {1, 0, 1, 0, 0.f, 0}.                                   */
+typedef struct rdm_fine_matching_options {
+  int32_t topk;                 /* k of both top-k selections, 1 .. side (side + 1 with use_dustbin)                    */
+  int32_t mutual;               /* 1: a correspondence needs both sides (and), 0: either (or)                           */
+  int32_t use_dustbin;          /* 1: test against the line's dustbin entry, 0: against confidence_threshold            */
+  int32_t use_global_score;     /* 1: corr_scores are multiplied by the patch's superpoint-pair score                   */
+  float confidence_threshold;   /* >= 0; read without use_dustbin only                                                  */
+  int32_t correspondence_limit; /* 0: none; L >= 1: hypotheses are scored and the pose refined on the L best-scored    */
+} rdm_fine_matching_options;
+
+/* LocalGlobalRegistration.forward with every option (local_global_registration.py:49-91 compute_correspondence_matrix,
+ * :145-202 local_to_global_registration, :229-243 forward).  (i, j) is a candidate of the ref side iff j is among the topk
+ * largest of row i of S = exp(log_scores) -- the dustbin column included with use_dustbin -- and S[i,j] exceeds the row's dustbin
+ * entry (use_dustbin) or confidence_threshold; the src side likewise over columns; `mutual` combines them; both knn masks
+ * apply.  Among equal values at a k-th boundary the lowest index is kept (torch.topk leaves it open).  corr_scores =
+ * S[i,j] (x global_scores[patch] with use_global_score, after the test).  correspondence_limit = L: if more than L
+ * correspondences exist, the local hypotheses -- still fitted on every patch with >= correspondence_threshold of ALL its
+ * correspondences -- are scored, and the pose is refined, on the L with the largest scores (lowest position among equal scores
+ * at the boundary), kept in nonzero order; the outputs still list all C, counts[0] = C.
+ * log_scores [batch, score_dim, score_dim]: score_dim = side + 1 (the Sinkhorn output; without use_dustbin only its
+ * [side, side] block is read, model_infer.py:319-320) or, without use_dustbin, side.  global_scores [batch] (may be null
+ * without use_global_score).  Outputs have capacity rdm_lgr_options_capacity = batch * min(2 topk side, side^2) rows (0 for
+ * invalid arguments, as the workspace size).  With the shipped values the result equals rdm_lgr's bit for bit.
+ * RDM_ERR_ARG for options outside the ranges above.                                                                         */
+int64_t rdm_lgr_options_capacity(int64_t batch, int64_t side, const rdm_fine_matching_options* options);
+size_t rdm_lgr_options_workspace_bytes(int64_t batch, int64_t side, const rdm_fine_matching_options* options);
+int rdm_lgr_options(const float* log_scores, int64_t score_dim, const float* ref_knn_points, const float* src_knn_points,
+                    const uint8_t* ref_knn_masks, const uint8_t* src_knn_masks, const float* global_scores, int64_t batch,
+                    int64_t side, float acceptance_radius, int correspondence_threshold, int num_refinement_steps,
+                    const rdm_fine_matching_options* options, float* ref_corr, float* src_corr, float* corr_scores,
+                    float* transform, int32_t* counts, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- native orchestration: one call per scan pair ----------------------------------------------
  * rdm_engine_run = the collate of geotransformer/utils/data.py:13-77 + RDMNet.forward of
  * experiments/model_infer.py:109-354 as a fixed sequence of the kernels above on one stream, with
@@ -692,6 +725,13 @@ int rdm_engine_set_overlap(rdm_engine* e, int mode);
  * every cross layer stay dense.  fracs[i] must be <= 1; not with attention_bf16.  n_layers = 0 clears the setting.  Valid
  * before or after finalize / share_params (the setting is the engine's own, not part of the shared parameters).            */
 int rdm_engine_set_attention_topk(rdm_engine* e, int n_layers, const double* fracs);
+/* cfg.fine_matching.{topk, mutual, use_dustbin, confidence_threshold, use_global_score, correspondence_limit}
+ * (experiments/model_infer.py:91-101, :319-329): the engine's registration then runs rdm_lgr_options -- global_scores are the
+ * superpoint-pair scores of coarse matching -- and its correspondence buffers, the mapped host buffer among them, hold
+ * num_correspondences * min(2 topk K, K^2) rows.  NULL restores rdm_lgr.  Call it after rdm_engine_create and before the
+ * engine's first run (it re-allocates the host buffer); the setting is the engine's own, not part of the shared parameters,
+ * so the engines of a lock-step group may differ in it.                                                              */
+int rdm_engine_set_fine_matching(rdm_engine* e, const rdm_fine_matching_options* options);
 /* Per-KPConv-layer profile of the next runs: 0 = off, 1 = HIP events around every layer's neighbourhood kernel and around the
  * whole layer (rdm_engine_get_profile: sizes + milliseconds), 2 = the layers' sizes only, no events -- for the other pairs of a
  * lock-step group whose first engine records the events: the launches (and durations) are the group's.                     */

@@ -14,6 +14,19 @@ c_size = ctypes.c_size_t
 
 ABI_VERSION = 2  # = RDM_ABI_VERSION of include/rdmnet_hip.h this binding was written against
 
+
+class FineMatchingOptions(ctypes.Structure):
+    """rdm_fine_matching_options (include/rdmnet_hip.h); correspondence_limit 0 = none."""
+    _fields_ = [('topk', ctypes.c_int32), ('mutual', ctypes.c_int32), ('use_dustbin', ctypes.c_int32),
+                ('use_global_score', ctypes.c_int32), ('confidence_threshold', ctypes.c_float),
+                ('correspondence_limit', ctypes.c_int32)]
+
+    @classmethod
+    def of(cls, topk=1, mutual=False, use_dustbin=True, confidence_threshold=0.0, use_global_score=False,
+           correspondence_limit=None):
+        return cls(int(topk), int(bool(mutual)), int(bool(use_dustbin)), int(bool(use_global_score)), float(confidence_threshold),
+                   0 if correspondence_limit is None else int(correspondence_limit))
+
 # name -> (restype, argtypes); mirrors include/rdmnet_hip.h one to one
 SIGNATURES = {
     'rdm_abi_version': (c_int, []),
@@ -139,6 +152,10 @@ SIGNATURES = {
     'rdm_lgr_workspace_bytes': (c_size, [c_i64]),
     'rdm_lgr': (c_int, [c_void, c_void, c_void, c_void, c_void, c_i64, c_i64, c_f32, c_int, c_int, c_void, c_void,
                         c_void, c_void, c_void, c_void, c_size, c_void]),
+    'rdm_lgr_options_capacity': (c_i64, [c_i64, c_i64, c_void]),
+    'rdm_lgr_options_workspace_bytes': (c_size, [c_i64, c_i64, c_void]),
+    'rdm_lgr_options': (c_int, [c_void, c_i64, c_void, c_void, c_void, c_void, c_void, c_i64, c_i64, c_f32, c_int, c_int, c_void,
+                                c_void, c_void, c_void, c_void, c_void, c_void, c_size, c_void]),
     'rdm_engine_create': (c_int, [c_void, c_void]),
     'rdm_engine_destroy': (None, [c_void]),
     'rdm_engine_set_param': (c_int, [c_void, ctypes.c_char_p, c_void, c_void, c_int]),
@@ -160,6 +177,7 @@ SIGNATURES = {
     'rdm_engine_set_pairs_in_flight': (c_int, [c_void, c_int]),
     'rdm_engine_set_overlap': (c_int, [c_void, c_int]),
     'rdm_engine_set_attention_topk': (c_int, [c_void, c_int, c_void]),
+    'rdm_engine_set_fine_matching': (c_int, [c_void, c_void]),
     'rdm_engine_enable_profile': (c_int, [c_void, c_int]),
     'rdm_engine_get_profile': (c_int, [c_void, c_void, c_int]),
     'rdm_engine_keep_taps': (c_int, [c_void, c_int]),

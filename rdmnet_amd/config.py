@@ -74,3 +74,47 @@ def topk_fractions(cfg):
         raise ValueError('cfg.thdroformer.k2 cannot be combined with cfg.thdroformer.attention_bf16 (no top-k variant of '
                          'bf16 attention)')
     return fracs
+
+
+FINE_MATCHING_DEFAULTS = dict(topk=1, mutual=False, use_dustbin=True, confidence_threshold=0.0, use_global_score=False,
+                              correspondence_limit=None)
+
+
+def check_fine_matching(values, points_in_patch, where='cfg.fine_matching.'):
+    """The six options in `values` (a missing one means its shipped value) checked and normalised -> dict.  Raises ValueError
+    naming the offending key, prefixed with `where`: a topk that is not an integer in [1, K] ([1, K + 1] with use_dustbin), K =
+    points_in_patch (torch.topk raises beyond that); a confidence_threshold that is not a real number >= 0 (also NaN: in the
+    reference a negative threshold matches every zero entry of the scattered matrix); a correspondence_limit that is neither
+    None nor an integer >= 1; a flag that is not a bool."""
+    o = {k: values.get(k, v) for k, v in FINE_MATCHING_DEFAULTS.items()}
+    for k in ('mutual', 'use_dustbin', 'use_global_score'):
+        if not isinstance(o[k], (bool, np.bool_)):
+            raise ValueError(f'{where}{k} must be a bool, got {o[k]!r}')
+        o[k] = bool(o[k])
+    side = int(points_in_patch) + (1 if o['use_dustbin'] else 0)
+    k = o['topk']
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, numbers.Integral) or not 1 <= int(k) <= side:
+        raise ValueError(f'{where}topk must be an integer in [1, {side}], got {k!r}')
+    o['topk'] = int(k)
+    t = o['confidence_threshold']
+    if isinstance(t, (bool, np.bool_)) or not isinstance(t, numbers.Real) or not float(t) >= 0.0:  # (also rejects NaN)
+        raise ValueError(f'{where}confidence_threshold must be a real number >= 0, got {t!r}')
+    o['confidence_threshold'] = float(t)
+    lim = o['correspondence_limit']
+    if lim is not None:
+        if isinstance(lim, (bool, np.bool_)) or not isinstance(lim, numbers.Integral) or int(lim) < 1:
+            raise ValueError(f'{where}correspondence_limit must be None or an integer >= 1, got {lim!r}')
+        o['correspondence_limit'] = int(lim)
+    return o
+
+
+def fine_matching_options(cfg):
+    """cfg.fine_matching.{topk, mutual, use_dustbin, confidence_threshold, use_global_score, correspondence_limit} checked and
+    read (local_global_registration.py:11-47; the other three keys travel in the engine configuration): None when all six hold
+    the values the reference ships -- the registration then runs its k = 1 / dustbin / non-mutual kernel -- else a dict of the
+    six (the keyword arguments of ops.lgr and _lib.FineMatchingOptions.of).  A missing key means its shipped value.
+    Raises the ValueErrors of check_fine_matching, each naming its key."""
+    o = check_fine_matching(cfg.fine_matching, cfg.model.num_points_in_patch)
+    # (confidence_threshold is not read with the dustbin: any valid value is the shipped behaviour then)
+    same = all(o[k] == v for k, v in FINE_MATCHING_DEFAULTS.items() if not (k == 'confidence_threshold' and o['use_dustbin']))
+    return None if same else o

@@ -120,6 +120,10 @@ struct rdm_engine {
   // rdm_engine_set_attention_topk (cfg.thdroformer.k2): per self layer of transformer #2, the fraction of each cloud's keys a
   // query keeps (thdroformer.py:20-40); negative or past the end: dense
   std::vector<double> topk_fracs;
+  // rdm_engine_set_fine_matching (cfg.fine_matching beyond the three keys of the configuration): the registration runs
+  // rdm_lgr_options; unset: rdm_lgr
+  bool has_fm = false;
+  rdm_fine_matching_options fm{1, 0, 1, 0, 0.f, 0};
   int pairs_in_flight = 1;    // rdm_engine_set_pairs_in_flight: how many pairs share the GPU (>= 3: GEMM residency capped)
   // Latency mode (rdm_engine_set_overlap): with ONE pair in flight most of the GPU idles while a chain of one-workgroup kernels
   // runs, so the engine runs the wide, independent parts of a pair (the first level's search + blocks, the decoder) on a side
@@ -969,6 +973,45 @@ extern "C" int rdm_engine_set_wait(rdm_engine* e, int sleep_us) {
 extern "C" int rdm_engine_set_pairs_in_flight(rdm_engine* e, int n) {
   RDM_REQUIRE(e && n >= 1, "rdm_engine_set_pairs_in_flight: bad arguments");
   e->pairs_in_flight = n;
+  return RDM_OK;
+}
+
+extern "C" int rdm_engine_set_fine_matching(rdm_engine* e, const rdm_fine_matching_options* o) {
+  RDM_REQUIRE(e, "rdm_engine_set_fine_matching: null engine");
+  if (!o) {
+    e->has_fm = false;
+    return RDM_OK;
+  }
+  const int K = std::max(e->cfg.points_in_patch, 1);
+  RDM_REQUIRE(o->topk >= 1 && o->topk <= K + (o->use_dustbin ? 1 : 0), "rdm_engine_set_fine_matching: topk = %d is outside [1, %d]",
+              o->topk, K + (o->use_dustbin ? 1 : 0));
+  RDM_REQUIRE(o->confidence_threshold >= 0.f, "rdm_engine_set_fine_matching: confidence_threshold = %g is not >= 0",
+              static_cast<double>(o->confidence_threshold));
+  RDM_REQUIRE(o->correspondence_limit >= 0, "rdm_engine_set_fine_matching: correspondence_limit = %d (0 = none, or >= 1)",
+              o->correspondence_limit);
+  // the mapped host buffer holds every correspondence of a run: min(2 topk K, K^2) per superpoint pair
+  const int64_t cap = rdm_lgr_options_capacity(std::max(e->cfg.num_correspondences, 1), K, o);
+  if (cap > e->host_corr_cap) {
+    int device = -1;
+    RDM_HIP_CHECK(hipGetDevice(&device));
+    RDM_REQUIRE(device == e->device, "rdm_engine_set_fine_matching: the engine belongs to device %d, current is %d", e->device, device);
+    void* pinned = nullptr;
+    void* pinned_dev = nullptr;
+    RDM_HIP_CHECK(hipHostMalloc(&pinned, 4096 + static_cast<size_t>(cap) * 7 * sizeof(float), hipHostMallocMapped));
+    const hipError_t err = hipHostGetDevicePointer(&pinned_dev, pinned, 0);
+    if (err != hipSuccess) {
+      (void)hipHostFree(pinned);
+      set_error("rdm_engine_set_fine_matching: hipHostGetDevicePointer failed: %s", hipGetErrorString(err));
+      return RDM_ERR_HIP;
+    }
+    RDM_HIP_CHECK(hipDeviceSynchronize());  // (nothing of this engine may still write the old buffer)
+    if (e->pinned) (void)hipHostFree(e->pinned);
+    e->pinned = pinned;
+    e->pinned_dev = pinned_dev;
+    e->host_corr_cap = cap;
+  }
+  e->fm = *o;
+  e->has_fm = true;
   return RDM_OK;
 }
 
@@ -1829,16 +1872,30 @@ int fine_matching(Run& r, const PairPyramid& py, const Superpoints& sp, const Co
   tap(r, "ref_node_corr_knn_masks", r_pm, B, K, K, 2);
   tap(r, "src_node_corr_knn_masks", s_pm, B, K, K, 2);
 
-  const int64_t ccap = B * 2 * K;
+  const int64_t ccap = e->has_fm ? rdm_lgr_options_capacity(B, K, &e->fm) : B * 2 * K;
   float* rc = e->alloc<float>(3 * ccap);
   float* sc = e->alloc<float>(3 * ccap);
   float* cs = e->alloc<float>(ccap);
   float* T = e->alloc<float>(16 + 4);  // pose and the three counters behind it: one read-back copy
   ENG_ALLOC(rc); ENG_ALLOC(sc); ENG_ALLOC(cs); ENG_ALLOC(T);
   int32_t* counts = reinterpret_cast<int32_t*>(T + 16);
-  RDM_DUP_LOOP("lgr")
-  ENG_CHECK(rdm_lgr(ms, r_pts, s_pts, r_pm, s_pm, B, K, c.acceptance_radius, c.correspondence_threshold,
-                    c.num_refinement_steps, rc, sc, cs, T, counts, r.ws, r.ws_bytes, r.st));
+  if (e->has_fm) {  // (model_infer.py:319-329: global_scores = the superpoint-pair scores; without the dustbin only the K x K block is read)
+    void* lgr_ws = r.ws;
+    size_t lgr_bytes = rdm_lgr_options_workspace_bytes(B, K, &e->fm);
+    if (lgr_bytes > r.ws_bytes) {  // (a large topk: 13 B per possible match)
+      lgr_ws = e->alloc<char>(lgr_bytes);
+      ENG_ALLOC(lgr_ws);
+    } else {
+      lgr_bytes = r.ws_bytes;
+    }
+    RDM_DUP_LOOP("lgr")
+    ENG_CHECK(rdm_lgr_options(ms, K + 1, r_pts, s_pts, r_pm, s_pm, cm.node_sc, B, K, c.acceptance_radius, c.correspondence_threshold,
+                              c.num_refinement_steps, &e->fm, rc, sc, cs, T, counts, lgr_ws, lgr_bytes, r.st));
+  } else {
+    RDM_DUP_LOOP("lgr")
+    ENG_CHECK(rdm_lgr(ms, r_pts, s_pts, r_pm, s_pm, B, K, c.acceptance_radius, c.correspondence_threshold,
+                      c.num_refinement_steps, rc, sc, cs, T, counts, r.ws, r.ws_bytes, r.st));
+  }
   struct {
     float T[16];
     int32_t counts[4];

@@ -97,12 +97,16 @@ class Engine:
         self.cfg = cfg
         self._h = ctypes.c_void_p()
         topk = config.topk_fractions(cfg)  # cfg.thdroformer.k2 (ValueError before anything is created)
+        fm = config.fine_matching_options(cfg)  # cfg.fine_matching beyond the engine configuration's three keys (likewise)
         with torch.cuda.device(self.device):
             c = make_config(cfg, arena_bytes)
             _lib.check(self.L.rdm_engine_create(ctypes.byref(c), ctypes.byref(self._h)), 'rdm_engine_create')
             if topk is not None:
                 fr = (ctypes.c_double * len(topk))(*topk)
                 _lib.check(self.L.rdm_engine_set_attention_topk(self._h, len(topk), fr), 'rdm_engine_set_attention_topk')
+            if fm is not None:
+                opt = _lib.FineMatchingOptions.of(**fm)
+                _lib.check(self.L.rdm_engine_set_fine_matching(self._h, ctypes.byref(opt)), 'rdm_engine_set_fine_matching')
             if share_with is not None:
                 _lib.check(self.L.rdm_engine_share_params(self._h, share_with._h), 'rdm_engine_share_params')
             for name, shape in ({} if share_with is not None else weights.schema(cfg)).items():

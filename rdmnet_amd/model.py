@@ -56,6 +56,7 @@ class RDMNet(torch.nn.Module):
         self.use_vote = bool(cfg.Vote.inference_use_vote and cfg.Vote.model_use_vote)
         self.attention_bf16 = bool(getattr(cfg.thdroformer, 'attention_bf16', False))
         self.topk2 = config.topk_fractions(cfg)  # cfg.thdroformer.k2 per self layer of transformer #2 (None: all dense)
+        self.fm_options = config.fine_matching_options(cfg)  # cfg.fine_matching beyond radius / threshold / steps (None: as shipped)
         self._tls = threading.local()  # .profile: list -> per-KPConv-layer HIP-event records (bench.py)
         # native engines by (device, stream), least recently used first; at most `max_engines` are kept (each owns an arena of
         # >= 3 GiB of HBM): a caller that keeps creating streams recycles engines instead of accumulating them
@@ -564,8 +565,10 @@ class RDMNet(torch.nn.Module):
         out['matching_scores'] = ms
 
         fm = cfg.fine_matching
+        # (model_infer.py:319-329: without the dustbin LGR gets the K x K block -- cut by the kernel's reads, `ms` stays whole in the
+        # output; global_scores are the superpoint-pair scores)
         rc, sc, cs, T, counts = ops.lgr(ms, r_pts, s_pts, r_pm, s_pm, fm.acceptance_radius, fm.correspondence_threshold,
-                                        fm.num_refinement_steps)
+                                        fm.num_refinement_steps, global_scores=node_scores.contiguous(), **(self.fm_options or {}))
         # sync: number of correspondences + status words (grouping capacity; the collate's 13 radius searches, whose
         # status nobody has read yet unless the collate ran with exact_shapes=True)
         cflags = data_dict.get('_flags')

@@ -4,9 +4,11 @@ Every function enqueues on the current torch stream and returns freshly allocate
 matrices are row-major with a row stride that is a multiple of 4 floats (`.stride(0)`); logical
 widths are passed explicitly where they differ.  No function here falls back to torch math.
 """
+import ctypes
+
 import torch
 
-from . import _lib
+from . import _lib, config
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 
@@ -516,22 +518,47 @@ def sinkhorn(scores, row_mask, col_mask, alpha, iters):
     return out
 
 
-def lgr(log_scores, ref_pts, src_pts, ref_mask, src_mask, radius, min_corr, steps):
-    """-> (ref_corr [cap,3], src_corr [cap,3], scores [cap], T [4,4], counts i32[3]) -- counts[0] rows are valid."""
+def lgr(log_scores, ref_pts, src_pts, ref_mask, src_mask, radius, min_corr, steps, *, topk=1, mutual=False, use_dustbin=True,
+        confidence_threshold=0.0, use_global_score=False, correspondence_limit=None, global_scores=None):
+    """-> (ref_corr [cap,3], src_corr [cap,3], scores [cap], T [4,4], counts i32[3]) -- counts[0] rows are valid.
+    The keyword arguments are cfg.fine_matching's (rdm_lgr_options; config.fine_matching_options checks them); with all of them
+    at their defaults the call is rdm_lgr.  log_scores: the Sinkhorn output [b, K+1, K+1] -- without use_dustbin only its
+    [K, K] block is read (model_infer.py:319-320), or that block itself, contiguous.  global_scores [b]: with use_global_score."""
     L = _lib.lib()
     b, side = ref_mask.shape
     dev = log_scores.device
-    cap = b * 2 * side
+    o = config.check_fine_matching(dict(topk=topk, mutual=mutual, use_dustbin=use_dustbin, confidence_threshold=confidence_threshold,
+                                        use_global_score=use_global_score, correspondence_limit=correspondence_limit), side,
+                                   where='lgr: ')  # (a ValueError names the argument: nothing is truncated to an int here)
+    opt = None
+    if (o['topk'], o['mutual'], o['use_dustbin'], o['use_global_score'], o['correspondence_limit']) != (1, False, True, False, None):
+        opt = _lib.FineMatchingOptions.of(**o)
+        cap = L.rdm_lgr_options_capacity(b, side, ctypes.byref(opt))
+        if log_scores.dim() != 3 or not log_scores.is_contiguous() or log_scores.shape[1] != log_scores.shape[2]:
+            raise ValueError(f'lgr: log_scores must be a contiguous [b, n, n] tensor, got {tuple(log_scores.shape)}')
+        if o['use_global_score'] and (global_scores is None or global_scores.dtype != torch.float32 or
+                                      not global_scores.is_contiguous() or global_scores.shape[0] < b):
+            raise ValueError(f'lgr: use_global_score needs global_scores, contiguous float32 with at least {b} entries')
+    else:
+        cap = b * 2 * side
     rc = torch.empty((cap, 3), dtype=torch.float32, device=dev)
     sc = torch.empty((cap, 3), dtype=torch.float32, device=dev)
     cs = torch.empty((cap,), dtype=torch.float32, device=dev)
     T = torch.empty((4, 4), dtype=torch.float32, device=dev)
     counts = torch.empty((3,), dtype=torch.int32, device=dev)
-    ws = scratch(dev, L.rdm_lgr_workspace_bytes(b))
-    _lib.check(L.rdm_lgr(log_scores.data_ptr(), ref_pts.data_ptr(), src_pts.data_ptr(), ref_mask.data_ptr(),
-                         src_mask.data_ptr(), b, side, float(radius), int(min_corr), int(steps), rc.data_ptr(), sc.data_ptr(),
-                         cs.data_ptr(), T.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
-               'rdm_lgr')
+    if opt is None:
+        ws = scratch(dev, L.rdm_lgr_workspace_bytes(b))
+        _lib.check(L.rdm_lgr(log_scores.data_ptr(), ref_pts.data_ptr(), src_pts.data_ptr(), ref_mask.data_ptr(),
+                             src_mask.data_ptr(), b, side, float(radius), int(min_corr), int(steps), rc.data_ptr(), sc.data_ptr(),
+                             cs.data_ptr(), T.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+                   'rdm_lgr')
+    else:
+        ws = scratch(dev, L.rdm_lgr_options_workspace_bytes(b, side, ctypes.byref(opt)))
+        _lib.check(L.rdm_lgr_options(log_scores.data_ptr(), log_scores.shape[1], ref_pts.data_ptr(), src_pts.data_ptr(),
+                                     ref_mask.data_ptr(), src_mask.data_ptr(), _lib.ptr(global_scores if o['use_global_score'] else None),
+                                     b, side, float(radius), int(min_corr), int(steps), ctypes.byref(opt), rc.data_ptr(),
+                                     sc.data_ptr(), cs.data_ptr(), T.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                                     _lib.stream_ptr()), 'rdm_lgr_options')
     return rc, sc, cs, T, counts
 
 
