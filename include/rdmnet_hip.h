@@ -755,6 +755,48 @@ int rdm_engine_gt_node_correspondences(rdm_engine* e, const float* transform, do
 /* Plain device-to-device copy on `stream` (lets a host without a HIP binding read arena tensors). */
 int rdm_copy_device(void* dst, const void* src, size_t bytes, void* stream);
 
+/* ---- §7 offline evaluator: the meters of experiments/eval.py for a batch of saved pairs ------------------------------
+ * What eval.py:100-239 computes per pair file, for P pairs per call, with a number of launches that does not depend on P
+ * (method RANSAC adds the three launches of rdm_ransac_correspondences per pair) and no host synchronisation.
+ * Packed ragged device inputs:
+ *   corr_offsets i64[P+1]; ref_corr, src_corr f32[sum C, 3]; corr_scores f32[sum C]   (pair p: rows corr_offsets[p] ..)
+ *   gt_transform f32[P,16]; est_transform f32[P,16]: input for RDM_EVAL_LGR, output for the two other methods
+ *   node_offsets i64[P+1], ref_node_corr, src_node_corr i64[sum]: the predicted superpoint pairs
+ *   gt_offsets i64[P+1], gt_node_corr i64[sum, 2]: the ground-truth superpoint pairs; node_dims i64[P,2] = {M, N}
+ * corr_offsets_host is the host's copy of corr_offsets (grid sizes, and the per-pair calls of RANSAC).
+ * Per pair: (1) options.num_corr = L > 0 and C > L: the L best-scored rows -- the first L in the order (score descending, row
+ * ascending), kept in row order (eval.py:121-125; np.argsort leaves equal scores open, here the lowest rows stay);
+ * (2) the transform: the stored one (LGR), the weighted Procrustes of the selected rows with weights s / (sum s + 1e-5) --
+ * float64 sums in a fixed order, Horn's solver (SVD, procrustes.py:6-73) --, or rdm_ransac_correspondences of the selected
+ * rows (RANSAC; every pair with options.ransac_seed); (3) registration.py:175-200,361-375 on the selected rows: src moved
+ * by gt_transform in fp32 (x r0 + y r1 + z r2 as two fma, then + t), fp32 residuals sqrt((dx dx + dy dy) + dz dz), their
+ * mean (float64 sum), the rows below acceptance_radius, 0.3 and 0.1, and `overlap`: the ref rows whose nearest moved src
+ * row (exact search) is closer than acceptance_radius; (4) registration.py:378-402: precision = predicted cells that are
+ * ground-truth cells / (predicted cells + 1e-12), cells counted once on both sides; (5) registration.py:17-108 in float64 on
+ * the fp32 matrices.  No atomics; every sum has a fixed order, so a pair's record does not depend on its batch.
+ * records: device f64 [P, RDM_EVAL_RECORD_WIDTH]: {num_corr, residual, inlier_ratio, inlier_ratio_0.3, inlier_ratio_0.1,
+ * overlap, precision, rre (degrees), rte, |d roll|, |d pitch|, |d yaw|, inliers, inliers_0.3, inliers_0.1, overlapping rows,
+ * hit cells, predicted cells, ground-truth cells, superpoint indices outside M x N (ignored; 0 for valid input)}.  A pair
+ * without correspondences has NaN in fields 1-5.                                                                          */
+#define RDM_EVAL_RECORD_WIDTH 20
+enum { RDM_EVAL_LGR = 0, RDM_EVAL_SVD = 1, RDM_EVAL_RANSAC = 2 };
+typedef struct rdm_eval_options {
+  int32_t method;             /* RDM_EVAL_* */
+  int32_t num_corr;           /* eval.py --num_corr; 0 = every correspondence */
+  double acceptance_radius;   /* cfg.eval.acceptance_radius (0.6) */
+  float ransac_distance_threshold;  /* cfg.ransac: 0.3 */
+  int32_t ransac_n;                 /*             4   */
+  int32_t ransac_iterations;        /*             50 000 */
+  int32_t reserved;
+  uint64_t ransac_seed;
+} rdm_eval_options;
+size_t rdm_eval_pairs_workspace_bytes(int64_t num_pairs, int64_t total_corr, int64_t max_corr, const rdm_eval_options* options);
+int rdm_eval_pairs(int64_t num_pairs, const int64_t* corr_offsets, const int64_t* corr_offsets_host, const float* ref_corr,
+                   const float* src_corr, const float* corr_scores, const float* gt_transform, float* est_transform,
+                   const int64_t* node_offsets, const int64_t* ref_node_corr, const int64_t* src_node_corr,
+                   const int64_t* gt_offsets, const int64_t* gt_node_corr, const int64_t* node_dims,
+                   const rdm_eval_options* options, double* records, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,29 @@ class FineMatchingOptions(ctypes.Structure):
         return cls(int(topk), int(bool(mutual)), int(bool(use_dustbin)), int(bool(use_global_score)), float(confidence_threshold),
                    0 if correspondence_limit is None else int(correspondence_limit))
 
+
+class EvalOptions(ctypes.Structure):
+    """rdm_eval_options (include/rdmnet_hip.h); num_corr 0 = every correspondence."""
+    METHODS = {'lgr': 0, 'svd': 1, 'ransac': 2}
+    _fields_ = [('method', ctypes.c_int32), ('num_corr', ctypes.c_int32), ('acceptance_radius', ctypes.c_double),
+                ('ransac_distance_threshold', ctypes.c_float), ('ransac_n', ctypes.c_int32),
+                ('ransac_iterations', ctypes.c_int32), ('reserved', ctypes.c_int32), ('ransac_seed', ctypes.c_uint64)]
+
+    @classmethod
+    def of(cls, method='lgr', num_corr=None, acceptance_radius=0.6, distance_threshold=0.3, ransac_n=4, num_iterations=50000,
+           seed=0):
+        if method not in cls.METHODS:
+            raise ValueError(f'Unsupported registration method: {method}.')
+        return cls(cls.METHODS[method], 0 if num_corr is None else int(num_corr), float(acceptance_radius),
+                   float(distance_threshold), int(ransac_n), int(num_iterations), 0, int(seed))
+
+
+EVAL_RECORD_WIDTH = 20  # = RDM_EVAL_RECORD_WIDTH
+# the fields of one record of rdm_eval_pairs, in order
+EVAL_FIELDS = ('num_corr', 'residual', 'inlier_ratio', 'inlier_ratio_0.3', 'inlier_ratio_0.1', 'overlap', 'precision', 'rre', 'rte',
+               'rx', 'ry', 'rz', 'inliers', 'inliers_0.3', 'inliers_0.1', 'overlap_rows', 'hit_cells', 'pred_cells', 'gt_cells',
+               'bad_indices')
+
 # name -> (restype, argtypes); mirrors include/rdmnet_hip.h one to one
 SIGNATURES = {
     'rdm_abi_version': (c_int, []),
@@ -186,6 +209,9 @@ SIGNATURES = {
     'rdm_engine_export': (c_int, [c_void, c_int, c_void, c_void, c_void]),
     'rdm_engine_gt_node_correspondences': (c_int, [c_void, c_void, ctypes.c_double, c_void, c_void, c_i64, c_void, c_void]),
     'rdm_copy_device': (c_int, [c_void, c_void, c_size, c_void]),
+    'rdm_eval_pairs_workspace_bytes': (c_size, [c_i64, c_i64, c_i64, c_void]),
+    'rdm_eval_pairs': (c_int, [c_i64, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void,
+                               c_void, c_void, c_void, c_void, c_void, c_size, c_void]),
 }
 
 

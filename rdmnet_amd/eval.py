@@ -1,0 +1,160 @@
+"""Offline evaluator: experiments/eval.py on the GPU.
+
+    python -m rdmnet_amd.eval --features-root DIR [--method lgr|ransac|svd] [--num_corr N] [--verbose] [--batch B]
+
+reads the pair files `python -m rdmnet_amd.infer --gt-nodes` (or the reference's test.py) wrote into DIR and prints the
+report of eval.py:248-286.  Files are ordered as eval.py:78-81 orders them, pair (seq 8, src frame 15) is skipped as in
+:94-95.  Reader threads load, decompress and pack the next batches while the current one is evaluated by
+`ops.evaluate_pairs` (one host-to-device copy, a fixed number of kernel launches and one device-to-host copy per batch).
+The `Node Detection` line prints zeros: the reference registers its meters and never updates them.
+"""
+import argparse
+import glob
+import os.path as osp
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+from . import config, evaluation
+
+METHODS = ('lgr', 'ransac', 'svd')
+NOT_BUILT = {'teaser': 'TEASER++ is not part of this project',
+             'ransac_featurematch': "the reference's evaluation loop has no branch for it (eval.py:177-219)"}
+PAIR_KEYS = ('ref_corr_points', 'src_corr_points', 'corr_scores', 'transform', 'estimated_transform', 'ref_node_corr_indices',
+             'src_node_corr_indices', 'gt_node_corr_indices')
+MAX_THREADS = 16
+# experiments/config.py: cfg.eval and cfg.ransac (a cfg that carries these sections overrides them)
+EVAL_DEFAULTS = dict(acceptance_radius=0.6, inlier_ratio_threshold=0.05, rre_threshold=5.0, rte_threshold=2.0)
+RANSAC_DEFAULTS = dict(distance_threshold=0.3, num_points=4, num_iterations=50000)
+
+
+def method_arg(value):
+    if value in NOT_BUILT:
+        raise argparse.ArgumentTypeError(f"method '{value}' is not supported: {NOT_BUILT[value]}")
+    if value not in METHODS:
+        raise argparse.ArgumentTypeError(f"invalid choice: '{value}' (choose from {', '.join(METHODS)})")
+    return value
+
+
+def make_parser():
+    parser = argparse.ArgumentParser(prog='python -m rdmnet_amd.eval', description=__doc__.split('\n\n')[0])
+    parser.add_argument('--features-root', '--features_root', required=True, help='directory of the {seq}_{src}_{ref}.npz pair files')
+    parser.add_argument('--test_epoch', default=None, type=int, help='test epoch')
+    parser.add_argument('--method', type=method_arg, default='lgr', help='registration method: ' + ', '.join(METHODS))
+    parser.add_argument('--num_corr', type=int, default=None, help='number of correspondences for registration')
+    parser.add_argument('--verbose', action='store_true', help='verbose mode')
+    parser.add_argument('--batch', type=int, default=64, help='pairs per GPU call')
+    parser.add_argument('--workers', type=int, default=8, help=f'reader threads (at most {MAX_THREADS})')
+    parser.add_argument('--seed', type=int, default=0, help='seed of --method ransac')
+    return parser
+
+
+def split_name(file_name):
+    return osp.splitext(osp.basename(file_name))[0].split('_')
+
+
+def sort_key(file_name):
+    """eval.py:80: the integers of the file name.  Names whose sequence id is not an integer (:87-90 reads those too) come
+    after the integer ones, by (sequence id, src frame, ref frame)."""
+    parts = split_name(file_name)
+    try:
+        return (0, [int(i) for i in parts], '')
+    except ValueError:
+        return (1, [int(i) for i in parts[1:]], parts[0])
+
+
+def pair_ids(file_name):
+    """eval.py:85-90 -> (seq_id, src_frame, ref_frame)."""
+    parts = split_name(file_name)
+    try:
+        seq_id, src_frame, ref_frame = [int(x) for x in parts]
+    except ValueError:
+        seq_id, src_frame, ref_frame = parts
+        src_frame, ref_frame = int(src_frame), int(ref_frame)
+    return seq_id, src_frame, ref_frame
+
+
+def list_pairs(features_root):
+    """-> (number of files, [(position from 1, file name, ids)] without the pair eval.py:94-95 drops)."""
+    names = sorted(glob.glob(osp.join(features_root, '*.npz')), key=lambda n: (sort_key(n)[0], sort_key(n)[2], sort_key(n)[1]))
+    out = []
+    for i, name in enumerate(names):
+        ids = pair_ids(name)
+        if ids[0] == 8 and ids[1] == 15:  # "delete bad data"
+            continue
+        out.append((i + 1, name, ids))
+    return len(names), out
+
+
+def load_pair(file_name):
+    with np.load(file_name) as z:
+        d = {k: z[k] for k in PAIR_KEYS}
+        d['node_dims'] = (z['ref_points_c'].shape[0], z['src_points_c'].shape[0])
+    return d
+
+
+def pair_message(position, total, ids, out):
+    """eval.py:127,170-174,238-239."""
+    m = '{}/{}, seq_id: {}, id0: {}, id1: {}'.format(position, total, *ids)
+    m += ', c_PIR: {:.3f}'.format(out['c_PIR'])
+    if 'f_IR' in out:
+        m += ', f_IR: {:.3f}, f_OV: {:.3f}, f_RS: {:.3f}, f_NU: {}'.format(out['f_IR'], out['f_OV'], out['f_RS'], out['f_NU'])
+    return m + ', r_RRE: {:.3f}, r_RTE: {:.3f}'.format(out['r_RRE'], out['r_RTE'])
+
+
+def evaluate(args, cfg=None, emit=print, timings=None):
+    """eval_one_epoch (eval.py:36-286).  Returns the Summary.  `timings` (dict) receives the seconds the main thread spent
+    waiting for packed batches ('load_wait') and inside the GPU calls ('evaluate')."""
+    import time
+    from . import ops
+    cfg = cfg or config.make_cfg()
+    ev = dict(EVAL_DEFAULTS, **cfg.get('eval', {}))
+    rs = dict(RANSAC_DEFAULTS, **cfg.get('ransac', {}))
+    summary = evaluation.Summary(ev['acceptance_radius'], ev['inlier_ratio_threshold'], ev['rre_threshold'], ev['rte_threshold'])
+    total, todo = list_pairs(args.features_root)
+    batch = max(1, int(args.batch))
+    workers = max(1, min(MAX_THREADS, int(args.workers)))
+    batches = [todo[i:i + batch] for i in range(0, len(todo), batch)]
+    t_wait = t_eval = 0.0
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        def prepare(items):  # files in parallel, then one packed buffer
+            return ops.pack_eval_pairs(list(pool.map(load_pair, [name for _, name, _ in items])))
+
+        with ThreadPoolExecutor(max_workers=1) as packer:
+            ahead = 2
+            pending = [packer.submit(prepare, b) for b in batches[:ahead]]
+            for k, items in enumerate(batches):
+                t0 = time.perf_counter()
+                packed = pending.pop(0).result()
+                if k + ahead < len(batches):
+                    pending.append(packer.submit(prepare, batches[k + ahead]))
+                t1 = time.perf_counter()
+                records, _ = ops.evaluate_pairs(packed, args.method, args.num_corr, acceptance_radius=ev['acceptance_radius'],
+                                                distance_threshold=rs['distance_threshold'], ransac_n=rs['num_points'],
+                                                num_iterations=rs['num_iterations'], seed=args.seed)
+                t2 = time.perf_counter()
+                t_wait += t1 - t0
+                t_eval += t2 - t1
+                for (position, _, ids), rec in zip(items, records):
+                    out = summary.commit_record(ids, rec)
+                    if args.verbose:
+                        emit(pair_message(position, total, ids, out))
+    if timings is not None:
+        timings.update(load_wait=t_wait, evaluate=t_eval, pairs=len(todo))
+    if args.test_epoch is not None:
+        emit(f'Epoch {args.test_epoch}, method {args.method}')
+    for line in summary.report_lines():
+        emit(line)
+    return summary
+
+
+def main(argv=None):
+    args = make_parser().parse_args(argv)
+    if not osp.isdir(args.features_root):
+        sys.exit(f'{args.features_root}: not a directory')
+    evaluate(args)
+
+
+if __name__ == '__main__':
+    main()

@@ -7,7 +7,8 @@ Host-side numpy, as in the reference (these run once per pair on a few hundred c
   * `compute_registration_error` & co: geotransformer/utils/registration.py:17-108;
   * `evaluate_correspondences`, `evaluate_sparse_correspondences`: registration.py:175-200, 354-402;
   * `evaluate_coarse`: the per-pair PIR of test.py (experiments/loss.py:347-365);
-  * `Summary`: the meters and report lines of experiments/eval.py:36-286 (method 'lgr' and 'svd').
+  * `Summary`: the meters and report lines of experiments/eval.py:36-286 (method 'lgr' and 'svd'); `commit_record` takes the
+    per-pair records of the GPU evaluator (rdmnet_amd/eval.py).
 """
 import math
 import os.path as osp
@@ -242,6 +243,27 @@ class Summary:
         """ids = (seq_id, src_frame, ref_frame).  nodes = (ref_nodes, src_nodes, ref_idx, src_idx,
         gt_node_corr_indices) enables the coarse-matching meters.  Returns the per-pair dict."""
         return self.commit(ids, self.measure(gt_transform, est_transform, ref_corr_points, src_corr_points, corr_scores, nodes))
+
+    def commit_record(self, ids, record):
+        """Adds one pair's record of ops.evaluate_pairs (rdm_eval_pairs, fields _lib.EVAL_FIELDS) to the meters: the same
+        bookkeeping as `commit` of a `measure` result with `nodes`.  Returns the per-pair dict of `update`."""
+        from ._lib import EVAL_FIELDS
+        r = dict(zip(EVAL_FIELDS, (float(v) for v in record)))
+        m = {'precision': r['precision'], 'registration': (r['rre'], r['rte'], r['rx'], r['ry'], r['rz'])}
+        if r['num_corr'] > 0:
+            m['fine'] = {k: r[k] for k in ('inlier_ratio', 'inlier_ratio_0.3', 'inlier_ratio_0.1', 'overlap', 'residual')}
+            m['fine']['num_corr'] = m['fine']['n'] = int(r['num_corr'])
+        return self.commit(ids, m)
+
+    def node_detection_line(self):
+        """eval.py:249-255.  The reference registers these four meters and never updates them: zeros unless a caller does."""
+        m = self.mean
+        return '  Node Detection, PRED_OV: {:.3f}, GT_OV: {:.3f}, PRED_T_OV: {:.3f}, GT_MAX_OV: {:.3f}'.format(
+            m('pred_overlap'), m('gt_overlap'), m('pred_true_overlap'), m('gt_max_overlap_for_each_node'))
+
+    def report_lines(self):
+        """The four report lines of eval.py:248-286, in its order."""
+        return [self.node_detection_line()] + self.lines()
 
     def lines(self):
         m = self.mean

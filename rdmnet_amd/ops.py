@@ -770,3 +770,107 @@ def gt_node_correspondences_indexed(ref_nodes, src_nodes, ref_points, ref_knn_in
     masks = [_gt_mask(ref_masks, 'ref_masks', (m,), dev), _gt_mask(src_masks, 'src_masks', (n,), dev),
              _gt_mask(ref_knn_masks, 'ref_knn_masks', (m, k), dev), _gt_mask(src_knn_masks, 'src_knn_masks', (n, k), dev)]
     return _gt_call(ref_nodes, src_nodes, ref_points, ref_knn_indices, src_points, src_knn_indices, k, transform, pos_radius, masks)
+
+
+# ---- offline evaluator (rdm_eval_pairs) ------------------------------------------------------------------------------
+
+class PackedEvalPairs:
+    """A batch of saved pairs as rdm_eval_pairs reads it: one host buffer (`buf`, uint8) holding every array at a 256-byte
+    aligned offset (`sections`: name -> (offset, dtype, shape)), so that the batch costs one host-to-device copy.  Built by
+    `pack_eval_pairs`, on any thread: nothing here touches the GPU."""
+
+    def __init__(self, buf, sections, corr_offsets, num_pairs):
+        self.buf, self.sections, self.corr_offsets, self.num_pairs = buf, sections, corr_offsets, num_pairs
+
+
+def pack_eval_pairs(pairs, pin=None):
+    """pairs: a list of dicts with the arrays of a test.py pair file (numpy or tensors): ref_corr_points, src_corr_points
+    [C, 3], corr_scores [C], transform [4, 4], estimated_transform [4, 4] (optional: identity), ref_node_corr_indices,
+    src_node_corr_indices, gt_node_corr_indices [G, 2], and the superpoint counts as ref_points_c / src_points_c (arrays, only
+    their length is used) or node_dims = (M, N).  pin: page-locked buffer (default: when a GPU is present)."""
+    import numpy as np
+
+    def host(v, dtype):
+        v = v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)
+        return np.ascontiguousarray(v, dtype=dtype)
+
+    P = len(pairs)
+    ref = [host(d['ref_corr_points'], np.float32).reshape(-1, 3) for d in pairs]
+    src = [host(d['src_corr_points'], np.float32).reshape(-1, 3) for d in pairs]
+    sc = [host(d['corr_scores'], np.float32).reshape(-1) for d in pairs]
+    rn = [host(d['ref_node_corr_indices'], np.int64).reshape(-1) for d in pairs]
+    sn = [host(d['src_node_corr_indices'], np.int64).reshape(-1) for d in pairs]
+    gn = [host(d['gt_node_corr_indices'], np.int64).reshape(-1, 2) for d in pairs]
+    for p in range(P):
+        if not (len(ref[p]) == len(src[p]) == len(sc[p])) or len(rn[p]) != len(sn[p]):
+            raise ValueError(f'pair {p}: correspondence arrays of different lengths')
+    dims = np.zeros((P, 2), np.int64)
+    for p, d in enumerate(pairs):
+        dims[p] = d['node_dims'] if 'node_dims' in d else (len(d['ref_points_c']), len(d['src_points_c']))
+    eye = np.eye(4, dtype=np.float32)
+    arrays = {
+        'corr_offsets': np.concatenate([[0], np.cumsum([len(a) for a in sc])]).astype(np.int64),
+        'node_offsets': np.concatenate([[0], np.cumsum([len(a) for a in rn])]).astype(np.int64),
+        'gt_offsets': np.concatenate([[0], np.cumsum([len(a) for a in gn])]).astype(np.int64),
+        'node_dims': dims,
+        'gt_transform': np.stack([host(d['transform'], np.float32).reshape(4, 4) for d in pairs]) if P else np.zeros((0, 4, 4), np.float32),
+        'est_transform': np.stack([host(d.get('estimated_transform', eye), np.float32).reshape(4, 4) for d in pairs])
+        if P else np.zeros((0, 4, 4), np.float32),
+        'ref_corr': np.concatenate(ref) if P else np.zeros((0, 3), np.float32),
+        'src_corr': np.concatenate(src) if P else np.zeros((0, 3), np.float32),
+        'corr_scores': np.concatenate(sc) if P else np.zeros((0,), np.float32),
+        'ref_node_corr': np.concatenate(rn) if P else np.zeros((0,), np.int64),
+        'src_node_corr': np.concatenate(sn) if P else np.zeros((0,), np.int64),
+        'gt_node_corr': np.concatenate(gn) if P else np.zeros((0, 2), np.int64),
+    }
+    sections, off = {}, 0
+    for name, a in arrays.items():
+        sections[name] = (off, a.dtype, a.shape)
+        off += (a.nbytes + 255) // 256 * 256
+    if pin is None:
+        pin = torch.cuda.is_available()
+    buf = torch.empty(max(off, 256), dtype=torch.uint8, pin_memory=bool(pin))
+    view = buf.numpy()
+    for name, a in arrays.items():
+        o = sections[name][0]
+        view[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+    return PackedEvalPairs(buf, sections, arrays['corr_offsets'], P)
+
+
+def evaluate_pairs(pairs, method='lgr', num_corr=None, *, acceptance_radius=0.6, distance_threshold=0.3, ransac_n=4,
+                   num_iterations=50000, seed=0, device=None):
+    """experiments/eval.py:100-239 for a batch of saved pairs on the GPU (rdm_eval_pairs): `pairs` is a list of per-pair dicts
+    (pack_eval_pairs) or a PackedEvalPairs.  -> (records float64 [P, EVAL_RECORD_WIDTH] numpy, fields _lib.EVAL_FIELDS;
+    transforms float32 [P, 4, 4] numpy: the registration the method used).  One host-to-device copy, a fixed number of launches,
+    one device-to-host copy (which is the only synchronisation)."""
+    import numpy as np
+    L = _lib.lib()
+    opts = _lib.EvalOptions.of(method, num_corr, acceptance_radius, distance_threshold, ransac_n, num_iterations, seed)
+    if num_corr is not None and int(num_corr) <= 0:
+        raise ValueError('num_corr must be positive')
+    packed = pairs if isinstance(pairs, PackedEvalPairs) else pack_eval_pairs(pairs)
+    P = packed.num_pairs
+    W = _lib.EVAL_RECORD_WIDTH
+    if P == 0:
+        return np.zeros((0, W), np.float64), np.zeros((0, 4, 4), np.float32)
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    with torch.cuda.device(dev):
+        d_in = packed.buf.to(dev, non_blocking=True)
+        base = d_in.data_ptr()
+        at = {name: base + o for name, (o, _, _) in packed.sections.items()}
+        offs = packed.corr_offsets
+        counts = np.diff(offs)
+        out = torch.empty(P * W * 8 + P * 64, dtype=torch.uint8, device=dev)  # records, then the transforms
+        rec_ptr, est_ptr = out.data_ptr(), out.data_ptr() + P * W * 8
+        _lib.check(L.rdm_copy_device(est_ptr, at['est_transform'], P * 64, _lib.stream_ptr()), 'rdm_copy_device')
+        ws = scratch(dev, L.rdm_eval_pairs_workspace_bytes(P, int(offs[-1]), int(counts.max()), ctypes.addressof(opts)))
+        _lib.check(L.rdm_eval_pairs(P, at['corr_offsets'], offs.ctypes.data, at['ref_corr'], at['src_corr'], at['corr_scores'],
+                                    at['gt_transform'], est_ptr, at['node_offsets'], at['ref_node_corr'], at['src_node_corr'],
+                                    at['gt_offsets'], at['gt_node_corr'], at['node_dims'], ctypes.addressof(opts), rec_ptr,
+                                    ws.data_ptr(), ws.numel(), _lib.stream_ptr()), 'rdm_eval_pairs')
+        h = out.cpu().numpy()
+    records = h[:P * W * 8].view(np.float64).reshape(P, W).copy()
+    transforms = h[P * W * 8:].view(np.float32).reshape(P, 4, 4).copy()
+    if records[:, _lib.EVAL_FIELDS.index('bad_indices')].any():
+        raise RuntimeError('rdm_eval_pairs: superpoint correspondence indices outside the pair\'s M x N nodes')
+    return records, transforms
