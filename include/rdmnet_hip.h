@@ -454,6 +454,30 @@ int rdm_coarse_matching_features(const float* ref_feats, int64_t ld_ref, int64_t
                                  int64_t* src_idx, float* out_scores, int32_t* out_count, void* ws,
                                  size_t ws_bytes, void* stream);
 
+/* ---- §7 descriptor matching: exact nearest-feature correspondences ----------------------------------------------------
+ * Replaces get_nearest_neighbor (geotransformer/utils/pointcloud.py:11-22, a cKDTree over the feature rows) as
+ * extract_corr_indices_from_feats / extract_correspondences_from_feats use it (geotransformer/utils/registration.py:222-277).
+ * a [n, c] (row stride lda), b [m, c] (row stride ldb): device f32, finite, 1 <= c <= 1024; float4 loads when c, lda, ldb are
+ * multiples of 4 and both pointers 16-byte aligned, scalar loads otherwise.  nn_ab [n] i64: for every row of a the row of b
+ * with the smallest sum_c (a_ic - b_jc)^2 EVALUATED IN FLOAT64 on the fp32 inputs, the lowest index among exactly equal
+ * distances (cKDTree leaves ties open); dist_ab [n] f32 (may be null): sqrt of that float64 sum, rounded to fp32.  With
+ * both_sides also nn_ba [m] / dist_ba [m]: the nearest row of a for every row of b.  The fp32 MFMA tiles of |a|^2 + |b|^2 -
+ * 2 a.b decide a line only where their two best candidates are further apart than twice the proven round-off bound
+ * (c + 8) 2^-24 (|a_i|^2 + max_j |b_j|^2); every other line is evaluated in float64 against every row of the other side
+ * (feature_match.hip).  No n x m matrix is written, no float atomics, results do not depend on scheduling.
+ * phase2_lines (optional, device int32[2]): the lines of a / of b that took the float64 pass.  n = 0: nothing is written
+ * (RDM_ERR_ARG with both_sides); m = 0: RDM_ERR_ARG.  n, m < 2^31 - 128, n <= 65535 * 128.  No synchronisation.
+ * rdm_feature_match_select turns the two index vectors into extract_corr_indices_from_feats' output on the device:
+ * mode 0 = (arange(n), nn_ab); 1 = mutual: the i with nn_ba[nn_ab[i]] == i, ascending, and their nn_ab; 2 = bilateral:
+ * ([arange(n), nn_ba], [nn_ab, arange(m)]).  ref_idx / src_idx i64 and dist f32 (optional; the rows' dist_ab, then dist_ba)
+ * with capacity n (n + m for mode 2); *count (device int32) = rows written.                                              */
+size_t rdm_feature_match_workspace_bytes(int64_t n, int64_t m, int both_sides);
+int rdm_feature_match(const float* a, int64_t lda, int64_t n, const float* b, int64_t ldb, int64_t m, int64_t c, int both_sides,
+                      int64_t* nn_ab, float* dist_ab, int64_t* nn_ba, float* dist_ba, int32_t* phase2_lines, void* ws,
+                      size_t ws_bytes, void* stream);
+int rdm_feature_match_select(int mode, const int64_t* nn_ab, const float* dist_ab, const int64_t* nn_ba, const float* dist_ba,
+                             int64_t n, int64_t m, int64_t* ref_idx, int64_t* src_idx, float* dist, int32_t* count, void* stream);
+
 /* ---- evaluation: ground-truth superpoint correspondences ----------------------------------------------------
  * Replaces get_node_correspondences (geotransformer/modules/registration/matching.py:252-350) as test.py's evaluation
  * forward calls it (experiments/model.py:283-295, radius cfg.model.ground_truth_matching_radius = 0.6,
@@ -752,6 +776,16 @@ int rdm_engine_describe(rdm_engine* e, int n, const char* const* names, rdm_tens
  * past capacity) and RDM_ERR_ARG when the engine has no completed forward run (e.g. after rdm_engine_collate alone).   */
 int rdm_engine_gt_node_correspondences(rdm_engine* e, const float* transform, double pos_radius, int64_t* out_indices,
                                        float* out_overlaps, int64_t capacity, int64_t* count_host, void* stream);
+/* Descriptor matching (rdm_feature_match + rdm_feature_match_select) on the LAST run's resident tensors, no upload, no export:
+ * level 0 = fine (ref/src_points_f, ref/src_feats_f: the first level's points and the decoder's features), 1 = coarse
+ * (ref/src_points_c, ref/src_feats_c: the superpoints and their normalised features); mode as rdm_feature_match_select.  All
+ * four tensors stay in the arena after a plain run, so rdm_engine_keep_taps is not needed.  Per engine after its run, also for
+ * the engines of a lock-step group (not a grouped launch).  Outputs (device, capacity rows: >= n_ref, n_ref + n_src for mode
+ * 2, else RDM_ERR_CAPACITY): ref_idx / src_idx i64, ref_points / src_points f32 [.,3] (optional), dists f32 (optional).
+ * count_host (host int64[3]) = {correspondences, lines of ref, lines of src that took the float64 pass}.  Scratch comes
+ * from the arena above the last run; synchronises `stream`; RDM_ERR_ARG without a completed forward run.                */
+int rdm_engine_feature_correspondences(rdm_engine* e, int level, int mode, int64_t* ref_idx, int64_t* src_idx, float* ref_points,
+                                       float* src_points, float* dists, int64_t capacity, int64_t* count_host, void* stream);
 /* Plain device-to-device copy on `stream` (lets a host without a HIP binding read arena tensors). */
 int rdm_copy_device(void* dst, const void* src, size_t bytes, void* stream);
 

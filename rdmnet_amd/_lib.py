@@ -208,6 +208,12 @@ SIGNATURES = {
     'rdm_engine_describe': (c_int, [c_void, c_int, c_void, c_void]),
     'rdm_engine_export': (c_int, [c_void, c_int, c_void, c_void, c_void]),
     'rdm_engine_gt_node_correspondences': (c_int, [c_void, c_void, ctypes.c_double, c_void, c_void, c_i64, c_void, c_void]),
+    'rdm_feature_match_workspace_bytes': (c_size, [c_i64, c_i64, c_int]),
+    'rdm_feature_match': (c_int, [c_void, c_i64, c_i64, c_void, c_i64, c_i64, c_i64, c_int, c_void, c_void, c_void, c_void, c_void,
+                                  c_void, c_size, c_void]),
+    'rdm_feature_match_select': (c_int, [c_int, c_void, c_void, c_void, c_void, c_i64, c_i64, c_void, c_void, c_void, c_void, c_void]),
+    'rdm_engine_feature_correspondences': (c_int, [c_void, c_int, c_int, c_void, c_void, c_void, c_void, c_void, c_i64, c_void,
+                                                   c_void]),
     'rdm_copy_device': (c_int, [c_void, c_void, c_size, c_void]),
     'rdm_eval_pairs_workspace_bytes': (c_size, [c_i64, c_i64, c_i64, c_void]),
     'rdm_eval_pairs': (c_int, [c_i64, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void,

@@ -155,6 +155,10 @@ struct rdm_engine {
     const uint8_t* km[2] = {nullptr, nullptr};
     const uint8_t* nm[2] = {nullptr, nullptr};
     int k = 0;
+    // rdm_engine_feature_correspondences: the fine (decoder) and coarse (normalised superpoint) features, rows [ref; src]
+    const float* ff = nullptr; int64_t ff_ld = 0;
+    const float* fc = nullptr; int64_t fc_ld = 0;
+    int d = 0;
   } gt;
 
   template <typename T>
@@ -2183,6 +2187,9 @@ static int engine_run_once(rdm_engine* e, const float* ref_points, int64_t n_ref
   tap(r, "src_node_corr_indices", cm.s_sel, B, 1, 1, 1);
   tap(r, "node_corr_scores", cm.node_sc, B, 1, 1, 0);
   ENG_CHECK(fine_matching(r, py, sp, cm, dec.cols_from(0, c.out_dim), B, res));
+  e->gt.ff = dec.p; e->gt.ff_ld = dec.ld;
+  e->gt.fc = sp.feats.p; e->gt.fc_ld = sp.feats.ld;
+  e->gt.d = c.out_dim;
   e->gt.valid = true;
   return RDM_OK;
 }
@@ -2321,6 +2328,70 @@ extern "C" int rdm_engine_gt_node_correspondences(rdm_engine* e, const float* tr
               (long long)capacity);
     return RDM_ERR_CAPACITY;
   }
+  return RDM_OK;
+}
+
+namespace rdm {
+int feature_match_gather_points(const float* ref_points, const float* src_points, const int64_t* ref_idx, const int64_t* src_idx,
+                                const int32_t* count, int64_t capacity, float* ref_out, float* src_out, hipStream_t st);
+}
+
+extern "C" int rdm_engine_feature_correspondences(rdm_engine* e, int level, int mode, int64_t* ref_idx, int64_t* src_idx,
+                                                  float* ref_points, float* src_points, float* dists, int64_t capacity,
+                                                  int64_t* count_host, void* stream) {
+  RDM_REQUIRE(e && ref_idx && src_idx && count_host, "rdm_engine_feature_correspondences: null pointer");
+  RDM_REQUIRE((ref_points == nullptr) == (src_points == nullptr), "rdm_engine_feature_correspondences: ref_points without src_points");
+  RDM_REQUIRE(level == 0 || level == 1, "rdm_engine_feature_correspondences: level %d (0 fine, 1 coarse)", level);
+  RDM_REQUIRE(mode >= 0 && mode <= 2, "rdm_engine_feature_correspondences: mode %d (0 nearest, 1 mutual, 2 bilateral)", mode);
+  RDM_REQUIRE(e->gt.valid, "rdm_engine_feature_correspondences: the engine holds no completed forward run (its points and "
+                           "features); run rdm_engine_run / rdm_engine_forward first");
+  const rdm_engine::GtInputs& g = e->gt;
+  const int64_t n = level == 0 ? g.nf[0] : g.m[0], m = level == 0 ? g.nf[1] : g.m[1];
+  const float* pts_r = level == 0 ? g.pf[0] : g.nodes[0];
+  const float* pts_s = level == 0 ? g.pf[1] : g.nodes[1];
+  const float* f = level == 0 ? g.ff : g.fc;
+  const int64_t ld = level == 0 ? g.ff_ld : g.fc_ld;
+  const int64_t need = mode == 2 ? n + m : n;
+  if (capacity < need) {
+    set_error("rdm_engine_feature_correspondences: capacity %lld, up to %lld correspondences", (long long)capacity, (long long)need);
+    return RDM_ERR_CAPACITY;
+  }
+  const int both = mode != 0;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // scratch above the last run's tensors, released again below (the call synchronises before it returns)
+  const size_t off_before = e->arena_off;
+  const size_t ws_bytes = rdm_feature_match_workspace_bytes(n, m, both);
+  char* ws = e->alloc<char>(ws_bytes);
+  int64_t* nn_ab = e->alloc<int64_t>(n);
+  int64_t* nn_ba = e->alloc<int64_t>(m);
+  float* d_ab = e->alloc<float>(n);
+  float* d_ba = e->alloc<float>(m);
+  int32_t* words = e->alloc<int32_t>(4);  // {count, phase-2 lines of ref, of src}
+  if (!ws || !nn_ab || !nn_ba || !d_ab || !d_ba || !words) {
+    e->arena_off = off_before;
+    set_error("rdm_engine_feature_correspondences: %zu B of scratch do not fit above the last run in the arena (%zu B)", ws_bytes,
+              e->arena_cap);
+    return RDM_ERR_WORKSPACE;
+  }
+  int rc = rdm_feature_match(f, ld, n, f + n * ld, ld, m, g.d, both, nn_ab, d_ab, nn_ba, d_ba, words + 1, ws, ws_bytes, stream);
+  if (rc == RDM_OK) rc = rdm_feature_match_select(mode, nn_ab, d_ab, nn_ba, d_ba, n, m, ref_idx, src_idx, dists, words, stream);
+  if (rc == RDM_OK && ref_points)
+    rc = rdm::feature_match_gather_points(pts_r, pts_s, ref_idx, src_idx, words, need, ref_points, src_points, st);
+  int32_t* mirror_dev = reinterpret_cast<int32_t*>(static_cast<char*>(e->pinned_dev) + 640);
+  const int32_t* mirror = reinterpret_cast<const int32_t*>(static_cast<const char*>(e->pinned) + 640);
+  if (rc == RDM_OK) {
+    rdm::copy_words(words, mirror_dev, 3, st);
+    rc = launch_status("copy_words");
+  }
+  hipError_t err = hipSuccess;
+  if (rc == RDM_OK) err = hipStreamSynchronize(st);
+  e->arena_off = off_before;
+  if (rc != RDM_OK) return rc;
+  if (err != hipSuccess) {
+    set_error("rdm_engine_feature_correspondences: hipStreamSynchronize failed: %s", hipGetErrorString(err));
+    return RDM_ERR_HIP;
+  }
+  for (int i = 0; i < 3; ++i) count_host[i] = mirror[i];
   return RDM_OK;
 }
 

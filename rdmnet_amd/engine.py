@@ -477,6 +477,43 @@ class Engine:
         c = int(counts[0])
         return idx[:c], ovl[:c], int(counts[1])
 
+    def feature_correspondences(self, level='fine', mode='nearest', return_phase2=False):
+        """The descriptor protocol (extract_correspondences_from_feats, geotransformer/utils/registration.py:222-277) on the last
+        run's resident tensors (rdm_engine_feature_correspondences), no upload: level 'fine' matches ref/src_feats_f and returns
+        points of ref/src_points_f, 'coarse' ref/src_feats_c and ref/src_points_c; mode 'nearest' | 'mutual' | 'bilateral' as
+        ops.feature_match.  -> dict(ref_corr_indices, src_corr_indices int64, ref_corr_points, src_corr_points f32 [C, 3],
+        feat_dists f32 [C]) on the device (with return_phase2 also 'phase2_lines': the lines of ref / src that took the float64
+        pass).  All four tensors survive a plain run, so keep_taps is not needed; an engine without a completed forward run
+        raises.  Synchronises the current stream."""
+        if level not in ('fine', 'coarse'):
+            raise ValueError(f"feature_correspondences: level {level!r}, expected 'fine' or 'coarse'")
+        from .ops import FEATURE_MATCH_MODES
+        if mode not in FEATURE_MATCH_MODES:
+            raise ValueError(f'feature_correspondences: mode {mode!r}, expected one of {sorted(FEATURE_MATCH_MODES)}')
+        r = self.result
+        if level == 'fine':
+            n = int(r.level_ref_sizes[1])
+            m = int(r.level_sizes[1]) - n
+        else:
+            n, m = int(r.n_ref_nodes), int(r.n_src_nodes)
+        cap = max(n + m if mode == 'bilateral' else n, 1)
+        ri = torch.empty((cap,), dtype=torch.int64, device=self.device)
+        si = torch.empty((cap,), dtype=torch.int64, device=self.device)
+        rp = torch.empty((cap, 3), dtype=torch.float32, device=self.device)
+        sp = torch.empty((cap, 3), dtype=torch.float32, device=self.device)
+        dist = torch.empty((cap,), dtype=torch.float32, device=self.device)
+        counts = (ctypes.c_int64 * 3)()
+        _lib.check(self.L.rdm_engine_feature_correspondences(self._h, 0 if level == 'fine' else 1, FEATURE_MATCH_MODES[mode],
+                                                             ri.data_ptr(), si.data_ptr(), rp.data_ptr(), sp.data_ptr(),
+                                                             dist.data_ptr(), cap, counts, _lib.stream_ptr()),
+                   'rdm_engine_feature_correspondences')
+        c = int(counts[0])
+        out = dict(ref_corr_indices=ri[:c], src_corr_indices=si[:c], ref_corr_points=rp[:c], src_corr_points=sp[:c],
+                   feat_dists=dist[:c])
+        if return_phase2:
+            out['phase2_lines'] = (int(counts[1]), int(counts[2]))
+        return out
+
     def corr(self):
         """(ref_corr_points, src_corr_points, corr_scores) of the last run as fresh tensors."""
         n = self.result.n_correspondences

@@ -1,12 +1,19 @@
 """Offline evaluator: experiments/eval.py on the GPU.
 
-    python -m rdmnet_amd.eval --features-root DIR [--method lgr|ransac|svd] [--num_corr N] [--verbose] [--batch B]
+    python -m rdmnet_amd.eval --features-root DIR [--method lgr|ransac|svd|ransac_featurematch] [--num_corr N] [--verbose] [--batch B]
 
 reads the pair files `python -m rdmnet_amd.infer --gt-nodes` (or the reference's test.py) wrote into DIR and prints the
 report of eval.py:248-286.  Files are ordered as eval.py:78-81 orders them, pair (seq 8, src frame 15) is skipped as in
 :94-95.  Reader threads load, decompress and pack the next batches while the current one is evaluated by
 `ops.evaluate_pairs` (one host-to-device copy, a fixed number of kernel launches and one device-to-host copy per batch).
 The `Node Detection` line prints zeros: the reference registers its meters and never updates them.
+
+`--method ransac_featurematch` is THIS project's definition: the reference's parser accepts the name (eval.py:30) and its loop has
+no branch for it (eval.py:177-219).  The pair is evaluated on the descriptor correspondences `infer --feature-match` stored
+(feat_ref/src_corr_points) in place of ref/src_corr_points, with score -feat_corr_dists -- so --num_corr N keeps the N smallest
+feature distances, lowest rows among equals --, the fine meters are the descriptor IR / FMR, and the pose is
+rdm_ransac_correspondences with the cfg.ransac values, as --method ransac.  Open3D's own
+registration_ransac_based_on_feature_matching (its internal KNN and checkers) is not restated.
 """
 import argparse
 import glob
@@ -18,30 +25,38 @@ import numpy as np
 
 from . import config, evaluation
 
-METHODS = ('lgr', 'ransac', 'svd')
+METHODS = ('lgr', 'ransac', 'svd')                # what the reference's evaluation loop implements (eval.py:177-219)
+OWN_METHODS = ('ransac_featurematch',)            # defined by this project; the command line takes them (main)
 NOT_BUILT = {'teaser': 'TEASER++ is not part of this project',
-             'ransac_featurematch': "the reference's evaluation loop has no branch for it (eval.py:177-219)"}
+             'ransac_featurematch': "the reference's evaluation loop has no branch for it (eval.py:177-219); this project's "
+                                    "definition is enabled by make_parser(own_methods=True), as the command line does"}
+FEATURE_KEYS = ('feat_ref_corr_points', 'feat_src_corr_points', 'feat_corr_dists')  # read by --method ransac_featurematch
 PAIR_KEYS = ('ref_corr_points', 'src_corr_points', 'corr_scores', 'transform', 'estimated_transform', 'ref_node_corr_indices',
              'src_node_corr_indices', 'gt_node_corr_indices')
+KERNEL_METHOD = {'ransac_featurematch': 'ransac'}  # (rdm_eval_pairs is unchanged: only the packed rows differ)
 MAX_THREADS = 16
 # experiments/config.py: cfg.eval and cfg.ransac (a cfg that carries these sections overrides them)
 EVAL_DEFAULTS = dict(acceptance_radius=0.6, inlier_ratio_threshold=0.05, rre_threshold=5.0, rte_threshold=2.0)
 RANSAC_DEFAULTS = dict(distance_threshold=0.3, num_points=4, num_iterations=50000)
 
 
-def method_arg(value):
+def method_arg(value, methods=METHODS):
+    if value in methods:
+        return value
     if value in NOT_BUILT:
         raise argparse.ArgumentTypeError(f"method '{value}' is not supported: {NOT_BUILT[value]}")
-    if value not in METHODS:
-        raise argparse.ArgumentTypeError(f"invalid choice: '{value}' (choose from {', '.join(METHODS)})")
-    return value
+    raise argparse.ArgumentTypeError(f"invalid choice: '{value}' (choose from {', '.join(methods)})")
 
 
-def make_parser():
+def make_parser(own_methods=False):
+    """The reference's eval.py arguments.  own_methods: --method also takes OWN_METHODS (this project's definitions of names the
+    reference advertises without implementing them); `python -m rdmnet_amd.eval` sets it."""
+    methods = METHODS + OWN_METHODS if own_methods else METHODS
     parser = argparse.ArgumentParser(prog='python -m rdmnet_amd.eval', description=__doc__.split('\n\n')[0])
     parser.add_argument('--features-root', '--features_root', required=True, help='directory of the {seq}_{src}_{ref}.npz pair files')
     parser.add_argument('--test_epoch', default=None, type=int, help='test epoch')
-    parser.add_argument('--method', type=method_arg, default='lgr', help='registration method: ' + ', '.join(METHODS))
+    parser.add_argument('--method', type=lambda v: method_arg(v, methods), default='lgr',
+                        help='registration method: ' + ', '.join(methods))
     parser.add_argument('--num_corr', type=int, default=None, help='number of correspondences for registration')
     parser.add_argument('--verbose', action='store_true', help='verbose mode')
     parser.add_argument('--batch', type=int, default=64, help='pairs per GPU call')
@@ -87,10 +102,18 @@ def list_pairs(features_root):
     return len(names), out
 
 
-def load_pair(file_name):
+def load_pair(file_name, method='lgr'):
     with np.load(file_name) as z:
         d = {k: z[k] for k in PAIR_KEYS}
         d['node_dims'] = (z['ref_points_c'].shape[0], z['src_points_c'].shape[0])
+        if method == 'ransac_featurematch':  # the stored descriptor correspondences take the place of the fine matching's
+            for k in FEATURE_KEYS:
+                if k not in z.files:
+                    raise KeyError(f"{file_name} has no '{k}': --method ransac_featurematch reads the descriptor correspondences "
+                                   "that `python -m rdmnet_amd.infer --feature-match {nearest,mutual,bilateral}` writes")
+            d['ref_corr_points'] = np.ascontiguousarray(z['feat_ref_corr_points'], np.float32)
+            d['src_corr_points'] = np.ascontiguousarray(z['feat_src_corr_points'], np.float32)
+            d['corr_scores'] = -np.ascontiguousarray(z['feat_corr_dists'], np.float32)
     return d
 
 
@@ -119,7 +142,7 @@ def evaluate(args, cfg=None, emit=print, timings=None):
     t_wait = t_eval = 0.0
     with ThreadPoolExecutor(max_workers=workers) as pool:
         def prepare(items):  # files in parallel, then one packed buffer
-            return ops.pack_eval_pairs(list(pool.map(load_pair, [name for _, name, _ in items])))
+            return ops.pack_eval_pairs(list(pool.map(lambda name: load_pair(name, args.method), [name for _, name, _ in items])))
 
         with ThreadPoolExecutor(max_workers=1) as packer:
             ahead = 2
@@ -130,7 +153,7 @@ def evaluate(args, cfg=None, emit=print, timings=None):
                 if k + ahead < len(batches):
                     pending.append(packer.submit(prepare, batches[k + ahead]))
                 t1 = time.perf_counter()
-                records, _ = ops.evaluate_pairs(packed, args.method, args.num_corr, acceptance_radius=ev['acceptance_radius'],
+                records, _ = ops.evaluate_pairs(packed, KERNEL_METHOD.get(args.method, args.method), args.num_corr, acceptance_radius=ev['acceptance_radius'],
                                                 distance_threshold=rs['distance_threshold'], ransac_n=rs['num_points'],
                                                 num_iterations=rs['num_iterations'], seed=args.seed)
                 t2 = time.perf_counter()
@@ -150,7 +173,7 @@ def evaluate(args, cfg=None, emit=print, timings=None):
 
 
 def main(argv=None):
-    args = make_parser().parse_args(argv)
+    args = make_parser(own_methods=True).parse_args(argv)
     if not osp.isdir(args.features_root):
         sys.exit(f'{args.features_root}: not a directory')
     evaluate(args)

@@ -58,12 +58,27 @@ def save_pair_npz(output_dir, data_dict, output_dict, estimated_transform_ransac
 TEST_NPZ_KEYS = NPZ_KEYS[:12] + ('corr_scores', 'gt_node_corr_indices', 'gt_node_corr_overlaps', 'estimated_transform')
 
 
-def save_pair_test_npz(output_dir, data_dict, output_dict):
-    """test.py:80-90: the .npz of the evaluation run, exactly its keys -- TEST_NPZ_KEYS plus the pair's `transform`."""
+# what `infer --feature-match` adds to a pair's file: the descriptor protocol on the fine level (ops.feature_correspondences)
+FEATURE_MATCH_KEYS = ('feat_ref_corr_indices', 'feat_src_corr_indices', 'feat_ref_corr_points', 'feat_src_corr_points',
+                      'feat_corr_dists')
+
+
+def feature_match_arrays(fm):
+    """Engine.feature_correspondences' dict -> the FEATURE_MATCH_KEYS arrays of a pair file."""
+    def host(v):
+        return v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)
+    return dict(zip(FEATURE_MATCH_KEYS, (host(fm[k]) for k in ('ref_corr_indices', 'src_corr_indices', 'ref_corr_points',
+                                                                'src_corr_points', 'feat_dists'))))
+
+
+def save_pair_test_npz(output_dir, data_dict, output_dict, extra=None):
+    """test.py:80-90: the .npz of the evaluation run, exactly its keys -- TEST_NPZ_KEYS plus the pair's `transform` (and
+    `extra`: the FEATURE_MATCH_KEYS of `infer --feature-match`)."""
     def host(v):
         return v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)
     arrays = {k: host(output_dict[k]) for k in TEST_NPZ_KEYS}
     arrays['transform'] = host(data_dict['transform'])
+    arrays.update(extra or {})
     name = osp.join(output_dir, npz_file_name(data_dict['seq_id'], data_dict['src_frame'], data_dict['ref_frame']))
     np.savez_compressed(name, **arrays)
     return name

@@ -5,6 +5,7 @@ registration report, on the native engine.
     python -m rdmnet_amd.infer --dataset-root /data/kitti --subset test --out out/ --weights rdmnet.pth.tar
     python -m rdmnet_amd.infer --synthetic 512 --no-npz                              # throughput on synthetic KITTI-shaped pairs
     python -m rdmnet_amd.infer --dataset-root /data/kitti --gt-nodes --out out/      # test.py's evaluation run (eval.py reads out/)
+    python -m rdmnet_amd.infer --infer-root /path/to/assets/pc --out out/ --feature-match mutual   # + descriptor correspondences
     python -m torch.distributed.run --nproc-per-node 8 -m rdmnet_amd.infer ...       # pairs sharded over ranks
 
 Per pair it writes what the reference writes: one line in `<seq>_pose` and one `<seq>_<src>_<ref>.npz`
@@ -14,6 +15,10 @@ gather of the per-pair records.  `--dataset mulran` switches the vote layer off 
 `--gt-nodes` turns the run into test.py's (eval.sh -> experiments/test.py, the model of experiments/model.py): for every pair
 with a ground-truth `transform` the ground-truth superpoint correspondences (model.py:283-297) are computed on the GPU from
 the engine's resident tensors, the Coarse Matching meters become real, and the .npz holds exactly test.py:80-90's keys.
+`--feature-match MODE` adds the classical descriptor protocol (extract_correspondences_from_feats,
+geotransformer/utils/registration.py:258-277, on the fine level: Engine.feature_correspondences) to every pair file --
+evaluation.FEATURE_MATCH_KEYS, what `python -m rdmnet_amd.eval --method ransac_featurematch` reads -- and, with ground truth, the
+descriptor inlier ratio to the pair's log line.
 """
 import argparse
 import os
@@ -41,12 +46,18 @@ class Tester:
     records, pose lines and the report come out in dataset order whatever the completion order."""
 
     def __init__(self, cfg, state, output_dir=None, save_npz=True, ransac=True, write_poses=True,
-                 pairs_in_flight=DEFAULT_PAIRS_IN_FLIGHT, wait_us=None, lockstep=None, gt_nodes=False):
+                 pairs_in_flight=DEFAULT_PAIRS_IN_FLIGHT, wait_us=None, lockstep=None, gt_nodes=False, feature_match=None):
         self.cfg, self.output_dir, self.save_npz, self.ransac = cfg, output_dir, save_npz, ransac
         self.write_poses = write_poses  # False under several ranks: rank 0 writes all poses, in pair order, at the end
         # gt_nodes: test.py's run -- ground-truth superpoint correspondences per pair with a transform (model.py:283-297, radius
         # cfg.model.ground_truth_matching_radius, 0.6 when absent), the coarse meters, test.py:80-90's .npz
         self.gt_nodes = bool(gt_nodes)
+        # feature_match: 'nearest' | 'mutual' | 'bilateral' -- the descriptor correspondences of the fine level per pair
+        if feature_match is not None and feature_match not in ops.FEATURE_MATCH_MODES:
+            raise ValueError(f'feature_match {feature_match!r}, expected one of {sorted(ops.FEATURE_MATCH_MODES)}')
+        self.feature_match = feature_match
+        ev = dict(cfg.get('eval', {})) if hasattr(cfg, 'get') else {}
+        self.fm_radius = float(ev.get('acceptance_radius', 0.6))
         radius = getattr(getattr(cfg, 'model', None), 'ground_truth_matching_radius', None)
         self.gt_radius = 0.6 if radius is None else float(radius)
         self.pipeline = PairPipeline(cfg, state, pairs_in_flight=pairs_in_flight, wait_us=wait_us,
@@ -87,6 +98,14 @@ class Tester:
                'n_corr': int(res.n_correspondences), 'ms': ms, 'transform': T}
         if 'transform' in item:  # what the pair's registration / correspondence numbers need (the engine's buffers are reused)
             rec['_measure'] = (np.asarray(item['transform'], np.float64), T) + eng.host_corr()  # (numpy copies)
+        extra = None
+        if self.feature_match:  # the descriptor protocol on the engine's resident fine points and features, this stream
+            extra = evaluation.feature_match_arrays(eng.feature_correspondences('fine', self.feature_match))
+            rec['n_feat_corr'] = int(extra['feat_corr_dists'].shape[0])
+            if 'transform' in item and rec['n_feat_corr'] > 0:  # evaluate_correspondences on those points (registration.py:361-375)
+                rec['feat_IR'] = float(evaluation.evaluate_correspondences(
+                    extra['feat_ref_corr_points'], extra['feat_src_corr_points'], np.asarray(item['transform'], np.float64),
+                    positive_radius=self.fm_radius)['inlier_ratio'])
         if self.gt_nodes and 'transform' in item:  # test.py: model.py:283-297 on the engine's resident tensors, this stream
             gt_idx, gt_ovl, _ = eng.gt_node_correspondences(np.asarray(item['transform'], np.float32), self.gt_radius)
             m_r = int(res.n_ref_nodes)
@@ -96,7 +115,7 @@ class Tester:
             if self.output_dir and self.save_npz:
                 od = self.output_dict(eng, item['ref_points'].shape[0])
                 od.update(gt_node_corr_indices=gt_idx, gt_node_corr_overlaps=gt_ovl)
-                evaluation.save_pair_test_npz(self.output_dir, item, od)
+                evaluation.save_pair_test_npz(self.output_dir, item, od, extra=extra)
             return rec
         if self.output_dir and self.save_npz:
             od = self.output_dict(eng, item['ref_points'].shape[0])
@@ -104,7 +123,7 @@ class Tester:
             if self.ransac:  # infer.py:75-82: distance 0.3, ransac_n 4, 50 000 iterations, on the GPU
                 T_ransac = ops.ransac_correspondences(od['src_corr_points'].contiguous(), od['ref_corr_points'].contiguous(),
                                                       0.3, 4, 50000)[0].cpu().numpy().astype(np.float64)
-            evaluation.save_pair_npz(self.output_dir, item, od, estimated_transform_ransac=T_ransac)
+            evaluation.save_pair_npz(self.output_dir, item, od, estimated_transform_ransac=T_ransac, extra=extra)
         return rec
 
     def _commit(self, rec):
@@ -134,8 +153,13 @@ class Tester:
             rec['ms'] = self.pipeline.last_stats['latency_ms'].get(i, rec['ms'])
             self._commit(rec)
             if log:
-                log('seq_id: {}, id0: {}, id1: {}, nCorr: {}'.format(rec['seq_id'], rec['ref_frame'], rec['src_frame'],
-                                                                      rec['n_corr']))
+                line = 'seq_id: {}, id0: {}, id1: {}, nCorr: {}'.format(rec['seq_id'], rec['ref_frame'], rec['src_frame'],
+                                                                        rec['n_corr'])
+                if 'n_feat_corr' in rec:  # (--feature-match)
+                    line += ', nFeatCorr: {}'.format(rec['n_feat_corr'])
+                    if 'feat_IR' in rec:
+                        line += ', feat_IR: {:.3f}'.format(rec['feat_IR'])
+                log(line)
         return self.records
 
 
@@ -165,6 +189,9 @@ def main(argv=None):
     ap.add_argument('--gt-nodes', action='store_true',
                     help="test.py's evaluation run: ground-truth superpoint correspondences on the GPU for every pair with a transform "
                          "(experiments/model.py:283-297), real Coarse Matching meters, .npz files with test.py's keys (eval.py reads them)")
+    ap.add_argument('--feature-match', choices=sorted(ops.FEATURE_MATCH_MODES), default=None,
+                    help='also match the fine-level descriptors by nearest neighbour in feature space (registration.py:222-277) and add '
+                         'feat_ref/src_corr_indices, feat_ref/src_corr_points and feat_corr_dists to every pair file')
     args = ap.parse_args(argv)
 
     rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
@@ -204,7 +231,8 @@ def main(argv=None):
         print(f'Data loader created: {time.time() - t0:.3f}s collapsed.')
         print(f'Calibrate neighbors: {cfg.neighbor_limits}.')
     tester = Tester(cfg, load_state(args.weights, cfg), args.out, save_npz=not args.no_npz, ransac=not args.no_ransac,
-                    write_poses=world == 1, pairs_in_flight=args.pairs_in_flight, lockstep=args.lockstep, gt_nodes=args.gt_nodes)
+                    write_poses=world == 1, pairs_in_flight=args.pairs_in_flight, lockstep=args.lockstep, gt_nodes=args.gt_nodes,
+                    feature_match=args.feature_match)
     mine = sharding.pairs_for_rank(len(data), rank, world)
     # scans are read and staged (pinned host -> HBM on a side stream) two pairs ahead of every in-flight pair
     stager = ds_mod.PairStager(data, mine, depth=2 * args.pairs_in_flight, workers=max(2, args.pairs_in_flight))

@@ -772,6 +772,85 @@ def gt_node_correspondences_indexed(ref_nodes, src_nodes, ref_points, ref_knn_in
     return _gt_call(ref_nodes, src_nodes, ref_points, ref_knn_indices, src_points, src_knn_indices, k, transform, pos_radius, masks)
 
 
+# ---- descriptor matching (rdm_feature_match) ---------------------------------------------------------------------------
+
+FEATURE_MATCH_MODES = {'nearest': 0, 'mutual': 1, 'bilateral': 2}
+
+
+def _fm_feats(t, name):
+    if not isinstance(t, torch.Tensor) or t.device.type != 'cuda' or t.dtype != torch.float32 or t.dim() != 2:
+        raise RuntimeError(f'feature_match: {name} must be a float32 CUDA tensor [rows, C]')
+    if (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t
+
+
+def feature_nearest(a, b, both_sides=False, return_phase2=False):
+    """rdm_feature_match: for every row of a [N, C] the index (int64 [N]) of its nearest row of b [M, C] and the distance
+    (float32 [N]) -- the float64 brute-force answer, lowest index among equal distances; with both_sides also the same for the
+    rows of b -> (nn_ab, dist_ab, nn_ba, dist_ba) (the last two None without both_sides)[, phase2_lines int32[2] device: the
+    lines of a / b that took the float64 pass].  No synchronisation."""
+    L = _lib.lib()
+    a, b = _fm_feats(a, 'a'), _fm_feats(b, 'b')
+    if a.device != b.device or a.shape[1] != b.shape[1]:
+        raise RuntimeError(f'feature_match: a {tuple(a.shape)} on {a.device} against b {tuple(b.shape)} on {b.device}')
+    dev, n, m, c = a.device, a.shape[0], b.shape[0], a.shape[1]
+    nn_ab = torch.empty((n,), dtype=torch.int64, device=dev)
+    d_ab = torch.empty((n,), dtype=torch.float32, device=dev)
+    nn_ba = torch.empty((m,), dtype=torch.int64, device=dev) if both_sides else None
+    d_ba = torch.empty((m,), dtype=torch.float32, device=dev) if both_sides else None
+    phase2 = torch.zeros((2,), dtype=torch.int32, device=dev)
+    ws = scratch(dev, L.rdm_feature_match_workspace_bytes(n, m, int(both_sides)))
+    _lib.check(L.rdm_feature_match(a.data_ptr(), a.stride(0) if n > 1 else c, n, b.data_ptr(), b.stride(0) if m > 1 else c, m, c,
+                                   int(both_sides), nn_ab.data_ptr(), d_ab.data_ptr(), _lib.ptr(nn_ba), _lib.ptr(d_ba),
+                                   phase2.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), 'rdm_feature_match')
+    return (nn_ab, d_ab, nn_ba, d_ba, phase2) if return_phase2 else (nn_ab, d_ab, nn_ba, d_ba)
+
+
+def _feature_match(ref_feats, src_feats, mutual, bilateral):
+    """-> (ref_corr_indices, src_corr_indices, feat_dists), device; one read-back (the count) under `mutual`."""
+    L = _lib.lib()
+    mode = 1 if mutual else 2 if bilateral else 0
+    ref_feats, src_feats = _fm_feats(ref_feats, 'ref_feats'), _fm_feats(src_feats, 'src_feats')
+    dev, n, m = ref_feats.device, ref_feats.shape[0], src_feats.shape[0]
+    if n == 0 and mode != 2 and m > 0:  # (bilateral has the rows of src to match, to nothing: rdm_feature_match's error)
+        return (torch.empty((0,), dtype=torch.int64, device=dev), torch.empty((0,), dtype=torch.int64, device=dev),
+                torch.empty((0,), dtype=torch.float32, device=dev))
+    nn_ab, d_ab, nn_ba, d_ba = feature_nearest(ref_feats, src_feats, both_sides=mode != 0)
+    cap = n + m if mode == 2 else n
+    ri = torch.empty((cap,), dtype=torch.int64, device=dev)
+    si = torch.empty((cap,), dtype=torch.int64, device=dev)
+    dist = torch.empty((cap,), dtype=torch.float32, device=dev)
+    count = torch.zeros((1,), dtype=torch.int32, device=dev)
+    _lib.check(L.rdm_feature_match_select(mode, nn_ab.data_ptr(), d_ab.data_ptr(), _lib.ptr(nn_ba), _lib.ptr(d_ba), n, m,
+                                          ri.data_ptr(), si.data_ptr(), dist.data_ptr(), count.data_ptr(), _lib.stream_ptr()),
+               'rdm_feature_match_select')
+    if mode == 1:
+        k = int(count.item())  # the number of mutual pairs is data dependent: the one read-back
+        ri, si, dist = ri[:k], si[:k], dist[:k]
+    return ri, si, dist
+
+
+def feature_match(ref_feats, src_feats, mutual=False, bilateral=False):
+    """extract_corr_indices_from_feats (geotransformer/utils/registration.py:222-255) on device tensors: features f32 [N, C] /
+    [M, C], 1 <= C <= 1024 -> (ref_corr_indices, src_corr_indices) int64, in the reference's order: (arange(N), nn_ref);
+    `mutual`: the i with nn_src[nn_ref[i]] == i, ascending; `bilateral` (ignored under mutual): ([arange(N), nn_src], [nn_ref,
+    arange(M)]).  Nearest = the float64 brute-force answer with the lowest index among equal distances (rdm_feature_match).
+    N = 0 gives empty outputs; M = 0 raises."""
+    return _feature_match(ref_feats, src_feats, mutual, bilateral)[:2]
+
+
+def feature_correspondences(ref_points, src_points, ref_feats, src_feats, mutual=False, bilateral=False, return_feat_dist=False):
+    """extract_correspondences_from_feats (geotransformer/utils/registration.py:258-277), plus `bilateral`:
+    -> [ref_corr_points, src_corr_points(, feat_dists)]; feat_dists = sqrt of the float64 sum of squared differences, rounded to
+    float32."""
+    ri, si, dist = _feature_match(ref_feats, src_feats, mutual, bilateral)
+    out = [ref_points[ri], src_points[si]]
+    if return_feat_dist:
+        out.append(dist)
+    return out
+
+
 # ---- offline evaluator (rdm_eval_pairs) ------------------------------------------------------------------------------
 
 class PackedEvalPairs:
