@@ -159,6 +159,29 @@ int rdm_icp_correspondences(const double* pcd, int64_t n, const float* target, i
                             double max_correspondence_distance, int32_t* idx, double* d2, void* ws, size_t ws_bytes,
                             void* stream);
 
+/* ---- ground-truth point correspondences and cloud overlap (ball_query.hip) -------------------
+ * get_correspondences and compute_overlap (geotransformer/utils/registration.py:191-216) as one fixed-radius ball query
+ * between two full clouds.  ref [n_ref, >=3] / src [n_src, >=3]: device f32, row strides ld_ref / ld_src (xyz first);
+ * transform_host: row-major float64 4x4 on the HOST, src -> ref (null: src as it is).  Points are read as double,
+ * x' = ((R00 x + R01 y) + R02 z) + t0, d2 = ((dx dx) + (dy dy)) + (dz dz) with d = ref - src', r2 = radius * radius in double,
+ * nothing contracted.  (i, j) is a correspondence iff d2 <= r2 (closed, as cKDTree's ball); a row overlaps iff the smallest
+ * d2 of its correspondences has sqrt(d2) < radius (strict, as compute_overlap).
+ * rdm_ball_count builds the cell index of the moved src cloud, counts per ref row and leaves index, counts and int64 offsets
+ * in the workspace.  Optional device outputs: ref_min_d2 f64 [n_ref] (the row's smallest d2, -1 without a correspondence),
+ * ref_hit u8 [n_ref] / src_hit u8 [n_src rounded up to a multiple of 4 bytes, 4-byte aligned] (1 iff the row appears in a
+ * correspondence).  totals_host (host int64[4], the call's one read-back, after which the stream is idle) = {C, overlapping
+ * ref rows, overlapping src rows, status}.  A point that is not finite, or a moved src point beyond 2^30 cells of `radius`
+ * from the origin, is RDM_ERR_ARG (status 2), not a fault.  radius <= 0 is an argument error.  n_ref, n_src < 2^31 - 64.
+ * rdm_ball_fill, on the SAME workspace, ref and sizes, writes out int64 [C, 2] (capacity >= C rows) in ascending (i, j) --
+ * cKDTree leaves the order inside a row open; this library defines it as ascending j.  No cap on the length of a row; no
+ * float atomics: two calls give the same counts and order.  No synchronisation in rdm_ball_fill.                          */
+size_t rdm_ball_workspace_bytes(int64_t n_ref, int64_t n_src);
+int rdm_ball_count(const float* ref, int64_t n_ref, int64_t ld_ref, const float* src, int64_t n_src, int64_t ld_src,
+                   const double* transform_host, double radius, double* ref_min_d2, uint8_t* ref_hit, uint8_t* src_hit,
+                   int64_t* totals_host, void* ws, size_t ws_bytes, void* stream);
+int rdm_ball_fill(const float* ref, int64_t n_ref, int64_t ld_ref, int64_t n_src, int64_t* out, int64_t capacity, void* ws,
+                  size_t ws_bytes, void* stream);
+
 /* ---- dense contraction ---------------------------------------------------------------------
  * C[b] = act((A[b] (m x k) * op(B[b])) / rowdiv[row] + bias[col]) in fp32 on the f32 MFMA.
  * trans_b = 0: B is [k, n] row-major (pre-transposed nn.Linear weights, KPConv weights viewed
@@ -786,6 +809,16 @@ int rdm_engine_gt_node_correspondences(rdm_engine* e, const float* transform, do
  * from the arena above the last run; synchronises `stream`; RDM_ERR_ARG without a completed forward run.                */
 int rdm_engine_feature_correspondences(rdm_engine* e, int level, int mode, int64_t* ref_idx, int64_t* src_idx, float* ref_points,
                                        float* src_points, float* dists, int64_t capacity, int64_t* count_host, void* stream);
+/* Ground-truth point correspondences (rdm_ball_count + rdm_ball_fill) on the LAST run's resident points, no upload, no export:
+ * level 0 = the full-resolution input clouds, 1 = the fine level (ref/src_points_f), 2 = the superpoints (ref/src_points_c);
+ * transform_host float64 4x4 on the host, src -> ref (null: identity).  Per engine after its run, also for the engines of a
+ * lock-step group.  The count call takes its workspace from the arena above the last run, fills totals_host (host int64[4],
+ * as rdm_ball_count) and synchronises `stream`; the fill call writes out int64 [C, 2] (device, capacity >= C rows, else
+ * RDM_ERR_CAPACITY), synchronises and releases the workspace (so does the next count call or run).  A forward that is not
+ * followed by these calls launches nothing for them.  RDM_ERR_ARG without a completed forward run / a pending count call. */
+int rdm_engine_gt_point_correspondences_count(rdm_engine* e, int level, const double* transform_host, double radius,
+                                              int64_t* totals_host, void* stream);
+int rdm_engine_gt_point_correspondences_fill(rdm_engine* e, int64_t* out, int64_t capacity, void* stream);
 /* Plain device-to-device copy on `stream` (lets a host without a HIP binding read arena tensors). */
 int rdm_copy_device(void* dst, const void* src, size_t bytes, void* stream);
 

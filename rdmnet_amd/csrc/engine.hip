@@ -159,6 +159,17 @@ struct rdm_engine {
     const float* ff = nullptr; int64_t ff_ld = 0;
     const float* fc = nullptr; int64_t fc_ld = 0;
     int d = 0;
+    // rdm_engine_gt_point_correspondences_count / _fill: the full-resolution input clouds (level 0 of the pyramid), and the
+    // count call's workspace in the arena above the last run, kept until the fill call (or the next run) releases it
+    const float* p0[2] = {nullptr, nullptr};
+    int64_t n0[2] = {0, 0};
+    struct Ball {
+      bool pending = false;
+      const float* ref = nullptr;
+      int64_t n = 0, m = 0, count = 0;
+      char* ws = nullptr;
+      size_t ws_bytes = 0, off_before = 0;
+    } ball;
   } gt;
 
   template <typename T>
@@ -2190,6 +2201,9 @@ static int engine_run_once(rdm_engine* e, const float* ref_points, int64_t n_ref
   e->gt.ff = dec.p; e->gt.ff_ld = dec.ld;
   e->gt.fc = sp.feats.p; e->gt.fc_ld = sp.feats.ld;
   e->gt.d = c.out_dim;
+  e->gt.p0[0] = py.lv[0].pts; e->gt.p0[1] = py.lv[0].pts + 3 * py.lv[0].n_ref;
+  e->gt.n0[0] = py.lv[0].n_ref; e->gt.n0[1] = py.lv[0].n - py.lv[0].n_ref;
+  e->gt.ball.pending = false;  // (a count call's workspace lay in the arena this run rewrote)
   e->gt.valid = true;
   return RDM_OK;
 }
@@ -2392,6 +2406,63 @@ extern "C" int rdm_engine_feature_correspondences(rdm_engine* e, int level, int 
     return RDM_ERR_HIP;
   }
   for (int i = 0; i < 3; ++i) count_host[i] = mirror[i];
+  return RDM_OK;
+}
+
+extern "C" int rdm_engine_gt_point_correspondences_count(rdm_engine* e, int level, const double* transform_host, double radius,
+                                                         int64_t* totals_host, void* stream) {
+  RDM_REQUIRE(e && totals_host, "rdm_engine_gt_point_correspondences_count: null pointer");
+  RDM_REQUIRE(level >= 0 && level <= 2, "rdm_engine_gt_point_correspondences_count: level %d (0 input, 1 fine, 2 coarse)", level);
+  RDM_REQUIRE(e->gt.valid, "rdm_engine_gt_point_correspondences_count: the engine holds no completed forward run (its points); "
+                           "run rdm_engine_run / rdm_engine_forward first");
+  rdm_engine::GtInputs& g = e->gt;
+  if (g.ball.pending) {  // a count call that was never filled: its workspace goes first
+    e->arena_off = g.ball.off_before;
+    g.ball.pending = false;
+  }
+  const float* ref = level == 0 ? g.p0[0] : (level == 1 ? g.pf[0] : g.nodes[0]);
+  const float* src = level == 0 ? g.p0[1] : (level == 1 ? g.pf[1] : g.nodes[1]);
+  const int64_t n = level == 0 ? g.n0[0] : (level == 1 ? g.nf[0] : g.m[0]);
+  const int64_t m = level == 0 ? g.n0[1] : (level == 1 ? g.nf[1] : g.m[1]);
+  const size_t off_before = e->arena_off;
+  const size_t ws_bytes = rdm_ball_workspace_bytes(n, m);
+  char* ws = e->alloc<char>(ws_bytes);
+  if (ws == nullptr) {
+    e->arena_off = off_before;
+    set_error("rdm_engine_gt_point_correspondences_count: %zu B of scratch do not fit above the last run in the arena (%zu B)",
+              ws_bytes, e->arena_cap);
+    return RDM_ERR_WORKSPACE;
+  }
+  const int rc = rdm_ball_count(ref, n, 3, src, m, 3, transform_host, radius, nullptr, nullptr, nullptr, totals_host, ws, ws_bytes,
+                                stream);  // (synchronises the stream)
+  if (rc != RDM_OK) {
+    e->arena_off = off_before;
+    return rc;
+  }
+  g.ball.pending = true;
+  g.ball.ref = ref; g.ball.n = n; g.ball.m = m; g.ball.count = totals_host[0];
+  g.ball.ws = ws; g.ball.ws_bytes = ws_bytes; g.ball.off_before = off_before;
+  return RDM_OK;
+}
+
+extern "C" int rdm_engine_gt_point_correspondences_fill(rdm_engine* e, int64_t* out, int64_t capacity, void* stream) {
+  RDM_REQUIRE(e, "rdm_engine_gt_point_correspondences_fill: null engine");
+  RDM_REQUIRE(e->gt.valid && e->gt.ball.pending, "rdm_engine_gt_point_correspondences_fill: no count call is pending on the last run");
+  rdm_engine::GtInputs::Ball& b = e->gt.ball;
+  if (capacity < b.count) {
+    set_error("rdm_engine_gt_point_correspondences_fill: %lld correspondences, capacity %lld", (long long)b.count, (long long)capacity);
+    return RDM_ERR_CAPACITY;
+  }
+  const int rc = rdm_ball_fill(b.ref, b.n, 3, b.m, out, capacity, b.ws, b.ws_bytes, stream);
+  hipError_t err = hipSuccess;
+  if (rc == RDM_OK) err = hipStreamSynchronize(static_cast<hipStream_t>(stream));  // (the workspace is released below)
+  e->arena_off = b.off_before;
+  b.pending = false;
+  if (rc != RDM_OK) return rc;
+  if (err != hipSuccess) {
+    set_error("rdm_engine_gt_point_correspondences_fill: hipStreamSynchronize failed: %s", hipGetErrorString(err));
+    return RDM_ERR_HIP;
+  }
   return RDM_OK;
 }
 

@@ -28,21 +28,20 @@
 //   set; the host enqueues iterations in chunks and reads `done` once per chunk.
 // Determinism: every reduction runs in a fixed order (lanes by butterfly, waves and slabs in index order); there are
 // no float atomics, so two runs give the same bits.
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include "../../include/rdmnet_hip.h"
 #include "common.h"
 #include "procrustes.h"
 
 #pragma clang fp contract(off)
 
+#include "cell_index.h"  // the target index: cell box, keys, sort, lower_bound (shared with ball_query.hip)
+
 namespace {
 using namespace rdm;
 
-constexpr int kBlock = 256;
-constexpr int kMaxBlocks = 1024;              // slab rows: the point kernels stride over at most this many blocks
+constexpr int kBlock = kCellBlock;
+constexpr int kMaxBlocks = kCellMaxBlocks;    // slab rows: the point kernels stride over at most this many blocks
 constexpr int kChunk = 32;                    // iterations enqueued between two reads of `done`
-constexpr double kCellLimit = 1073741824.0;   // |t / h| < 2^30 for every target point
 constexpr int kRecord = 15;                   // history record: fitness, rmse, n_corr, update[12]
 
 struct Mat16 {
@@ -58,13 +57,6 @@ struct IcpState {
   int done;       // 0 running, 1 finished, 2 bad target (non-finite point or extent beyond the cell limits)
   int updates;
 };
-
-struct Grid {
-  long long lo[3], dims[3];  // cell box of the target (dims = 0 when it is empty)
-  double h;
-};
-
-__device__ __forceinline__ double cell_of(double x, double h) { return floor(x / h); }
 
 // Sums K doubles over the block (256 threads) in a fixed order; thread k < K returns the total of value k.
 template <int K>
@@ -105,54 +97,11 @@ __device__ __forceinline__ void apply_rt(const double* M, double& x, double& y, 
 
 // ---- target index --------------------------------------------------------------------------------------------------
 
-__global__ __launch_bounds__(kBlock) void icp_bbox_kernel(const float* __restrict__ target, int m, long long ld, double h,
-                                                          double* __restrict__ slab) {
-  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, bad = 0.0;
-  for (int j = blockIdx.x * kBlock + threadIdx.x; j < m; j += gridDim.x * kBlock) {
-    for (int a = 0; a < 3; ++a) {
-      const double c = cell_of(static_cast<double>(target[j * ld + a]), h);
-      if (!(fabs(c) < kCellLimit)) bad = 1.0;  // (NaN and infinities too)
-      lo[a] = fmin(lo[a], c);
-      hi[a] = fmax(hi[a], c);
-    }
-  }
-  __shared__ double red[7][kBlock];
-  for (int a = 0; a < 3; ++a) {
-    red[a][threadIdx.x] = lo[a];
-    red[3 + a][threadIdx.x] = hi[a];
-  }
-  red[6][threadIdx.x] = bad;
-  __syncthreads();
-  if (threadIdx.x < 7) {
-    const int k = threadIdx.x;
-    double v = red[k][0];
-    for (int t = 1; t < kBlock; ++t) v = k < 3 ? fmin(v, red[k][t]) : fmax(v, red[k][t]);
-    slab[blockIdx.x * 8 + k] = v;
-  }
-}
-
 // One block: the cell box from the bbox slabs, and the state of a new call (T = init, nothing done).
 __global__ __launch_bounds__(kBlock) void icp_setup_kernel(const double* __restrict__ slab, int rows, int m, double h, Mat16 init,
                                                            Grid* __restrict__ grid, IcpState* __restrict__ st) {
   if (threadIdx.x != 0) return;
-  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  bool bad = false;
-  for (int r = 0; r < rows; ++r) {
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = fmin(lo[a], slab[r * 8 + a]);
-      hi[a] = fmax(hi[a], slab[r * 8 + 3 + a]);
-    }
-    bad = bad || slab[r * 8 + 6] != 0.0;
-  }
-  double cells = 1.0;
-  for (int a = 0; a < 3; ++a) {
-    const double d = m > 0 && !bad ? hi[a] - lo[a] + 1.0 : 0.0;
-    grid->lo[a] = m > 0 && !bad ? static_cast<long long>(lo[a]) : 0;
-    grid->dims[a] = static_cast<long long>(d);
-    cells *= d;
-  }
-  if (cells > 4611686018427387904.0) bad = true;  // keys are 64-bit: the box must fit 2^62 cells
-  grid->h = h;
+  const bool bad = cell_box_from_slabs(slab, rows, m, h, grid);
   for (int k = 0; k < 16; ++k) st->T[k] = init.v[k];
   for (int k = 0; k < 12; ++k) st->U[k] = (k % 5 == 0) ? 1.0 : 0.0;
   st->fitness = st->rmse = st->err2 = 0.0;
@@ -160,22 +109,6 @@ __global__ __launch_bounds__(kBlock) void icp_setup_kernel(const double* __restr
   st->n_corr = 0;
   st->updates = 0;
   st->done = bad ? 2 : 0;
-}
-
-__global__ __launch_bounds__(kBlock) void icp_key_kernel(const float* __restrict__ target, int m, long long ld,
-                                                         const Grid* __restrict__ grid, const IcpState* __restrict__ st,
-                                                         unsigned long long* __restrict__ keys, int* __restrict__ vals) {
-  const int j = blockIdx.x * kBlock + threadIdx.x;
-  if (j >= m) return;
-  unsigned long long key = 0;
-  if (st->done == 0) {
-    long long c[3];
-    for (int a = 0; a < 3; ++a)
-      c[a] = static_cast<long long>(cell_of(static_cast<double>(target[j * ld + a]), grid->h)) - grid->lo[a];
-    key = static_cast<unsigned long long>((c[0] * grid->dims[1] + c[1]) * grid->dims[2] + c[2]);
-  }
-  keys[j] = key;
-  vals[j] = j;
 }
 
 __global__ __launch_bounds__(kBlock) void icp_records_kernel(const float* __restrict__ target, int m, long long ld,
@@ -187,20 +120,6 @@ __global__ __launch_bounds__(kBlock) void icp_records_kernel(const float* __rest
 }
 
 // ---- neighbour step --------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ int lower_bound(const unsigned long long* __restrict__ keys, int m, unsigned long long key) {
-  int lo = 0, n = m;
-  while (n > 0) {
-    const int half = n >> 1;
-    if (keys[lo + half] < key) {
-      lo += half + 1;
-      n -= half + 1;
-    } else {
-      n = half;
-    }
-  }
-  return lo;
-}
 
 // Nearest target with d2 < r2 (lowest index among equal d2), or -1; *best = its d2, *rec = its record.
 __device__ int nearest(double qx, double qy, double qz, const unsigned long long* __restrict__ keys,
@@ -401,33 +320,14 @@ __global__ __launch_bounds__(kBlock) void icp_finalize_kernel(const double* __re
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
 
-int point_blocks(int64_t n) {
-  const int64_t b = (n + kBlock - 1) / kBlock;
-  return static_cast<int>(b < 1 ? 1 : (b > kMaxBlocks ? kMaxBlocks : b));
-}
-
-size_t sort_temp_bytes(int64_t m) {
-  size_t bytes = 0;
-  if (m > 0 &&
-      rocprim::radix_sort_pairs(nullptr, bytes, static_cast<const unsigned long long*>(nullptr),
-                                static_cast<unsigned long long*>(nullptr), static_cast<const int*>(nullptr),
-                                static_cast<int*>(nullptr), static_cast<unsigned>(m)) != hipSuccess)
-    return 0;
-  return bytes;
-}
-
 struct Work {
   double* pcd;
   int* idx;
   double* slab;
   double* slab_cov;
   IcpState* st;
-  Grid* grid;
-  unsigned long long *keys_in, *keys;
-  int *vals_in, *order;
+  CellIndex ci;
   float4* recs;
-  void* sort_tmp;
-  size_t sort_bytes;
 };
 
 bool carve(Arena& ar, int64_t n, int64_t m, Work& w) {
@@ -436,15 +336,8 @@ bool carve(Arena& ar, int64_t n, int64_t m, Work& w) {
   w.slab = ar.take<double>(kMaxBlocks * 8);
   w.slab_cov = ar.take<double>(kMaxBlocks * 9);
   w.st = ar.take<IcpState>(1);
-  w.grid = ar.take<Grid>(1);
-  const size_t mm = static_cast<size_t>(m > 0 ? m : 1);
-  w.keys_in = ar.take<unsigned long long>(mm);
-  w.keys = ar.take<unsigned long long>(mm);
-  w.vals_in = ar.take<int>(mm);
-  w.order = ar.take<int>(mm);
-  w.recs = ar.take<float4>(mm);
-  w.sort_bytes = sort_temp_bytes(m);
-  w.sort_tmp = ar.take<char>(w.sort_bytes > 0 ? w.sort_bytes : 1);
+  carve_cell_index(ar, m, w.ci);
+  w.recs = ar.take<float4>(static_cast<size_t>(m > 0 ? m : 1));
   return ar.ok;
 }
 
@@ -454,18 +347,14 @@ double search_r2(double r) { return static_cast<double>(static_cast<float>(r * r
 int build_index(const float* target, int64_t m, int64_t ld, double r2, const Mat16& init, Work& w, hipStream_t st) {
   const double h = sqrt(r2) * (1.0 + 1e-6);
   const int tb = point_blocks(m);
-  hipLaunchKernelGGL(icp_bbox_kernel, dim3(tb), dim3(kBlock), 0, st, target, static_cast<int>(m), static_cast<long long>(ld), h,
-                     w.slab);
-  hipLaunchKernelGGL(icp_setup_kernel, dim3(1), dim3(kBlock), 0, st, w.slab, tb, static_cast<int>(m), h, init, w.grid, w.st);
+  hipLaunchKernelGGL(cell_bbox_kernel<float>, dim3(tb), dim3(kBlock), 0, st, target, static_cast<int>(m),
+                     static_cast<long long>(ld), h, w.slab);
+  hipLaunchKernelGGL(icp_setup_kernel, dim3(1), dim3(kBlock), 0, st, w.slab, tb, static_cast<int>(m), h, init, w.ci.grid, w.st);
   if (m > 0) {
-    const unsigned blocks = static_cast<unsigned>((m + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(icp_key_kernel, dim3(blocks), dim3(kBlock), 0, st, target, static_cast<int>(m), static_cast<long long>(ld),
-                       w.grid, w.st, w.keys_in, w.vals_in);
-    size_t bytes = w.sort_bytes;
-    RDM_HIP_CHECK(rocprim::radix_sort_pairs(w.sort_tmp, bytes, w.keys_in, w.keys, w.vals_in, w.order, static_cast<unsigned>(m), 0u,
-                                            64u, st));
-    hipLaunchKernelGGL(icp_records_kernel, dim3(blocks), dim3(kBlock), 0, st, target, static_cast<int>(m),
-                       static_cast<long long>(ld), w.order, w.recs);
+    const int rc = sort_cells(target, m, ld, &w.st->done, w.ci, st);
+    if (rc != RDM_OK) return rc;
+    hipLaunchKernelGGL(icp_records_kernel, dim3(static_cast<unsigned>((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, target,
+                       static_cast<int>(m), static_cast<long long>(ld), w.ci.order, w.recs);
   }
   return launch_status("icp target index");
 }
@@ -527,7 +416,7 @@ extern "C" int rdm_icp_point_to_point(const float* source, int64_t n_source, int
   for (int k = 0; k <= max_iteration && done == 0;) {
     const int end = max_iteration - k < kChunk ? max_iteration + 1 : k + kChunk;
     for (; k < end; ++k) {
-      hipLaunchKernelGGL(icp_search_kernel, dim3(pb), dim3(kBlock), 0, st, w.pcd, n, k > 0 ? 1 : 0, w.keys, w.recs, m, w.grid, r2,
+      hipLaunchKernelGGL(icp_search_kernel, dim3(pb), dim3(kBlock), 0, st, w.pcd, n, k > 0 ? 1 : 0, w.ci.keys, w.recs, m, w.ci.grid, r2,
                          w.st, w.idx, static_cast<double*>(nullptr), w.slab);
       hipLaunchKernelGGL(icp_mean_kernel, dim3(1), dim3(kBlock), 0, st, w.slab, pb, w.st);
       hipLaunchKernelGGL(icp_cov_kernel, dim3(pb), dim3(kBlock), 0, st, w.pcd, n, target, static_cast<long long>(ld_target), w.idx,
@@ -571,7 +460,7 @@ extern "C" int rdm_icp_correspondences(const double* pcd, int64_t n, const float
   if (rc != RDM_OK) return rc;
   if (n > 0)
     hipLaunchKernelGGL(icp_search_kernel, dim3(point_blocks(n)), dim3(kBlock), 0, st, const_cast<double*>(pcd), static_cast<int>(n),
-                       0, w.keys, w.recs, static_cast<int>(n_target), w.grid, r2, w.st, idx, d2, w.slab);
+                       0, w.ci.keys, w.recs, static_cast<int>(n_target), w.ci.grid, r2, w.st, idx, d2, w.slab);
   rc = launch_status("rdm_icp_correspondences");
   if (rc != RDM_OK) return rc;
   int done = 0;

@@ -58,6 +58,7 @@ class KpconvProfile(ctypes.Structure):
 
 _DTYPES = {0: torch.float32, 1: torch.int64, 2: torch.uint8, 3: torch.int32}
 _ESIZE = {0: 4, 1: 8, 2: 1, 3: 4}
+POINT_LEVELS = {'input': 0, 'fine': 1, 'coarse': 2}  # Engine.gt_point_correspondences
 
 
 def make_config(cfg, arena_bytes=0):
@@ -512,6 +513,27 @@ class Engine:
                    feat_dists=dist[:c])
         if return_phase2:
             out['phase2_lines'] = (int(counts[1]), int(counts[2]))
+        return out
+
+    def gt_point_correspondences(self, transform, radius, level='fine'):
+        """ops.get_correspondences on the last run's resident points (rdm_engine_gt_point_correspondences_count / _fill), no upload:
+        level 'input' = the full-resolution input clouds, 'fine' = ref/src_points_f, 'coarse' = the superpoints; transform 4x4
+        src -> ref (None: identity) -> int64 [C, 2] on the device, ascending (i, j).  The points survive a plain run, so
+        keep_taps is not needed; an engine without a completed forward run raises.  Synchronises the current stream."""
+        if level not in POINT_LEVELS:
+            raise ValueError(f'gt_point_correspondences: level {level!r}, expected one of {sorted(POINT_LEVELS)}')
+        if radius is None or not radius > 0:
+            raise ValueError(f'gt_point_correspondences: radius must be > 0, got {radius}')
+        from .ops import _transform_arg
+        T = _transform_arg(transform, 'gt_point_correspondences')
+        totals = (ctypes.c_int64 * 4)()
+        _lib.check(self.L.rdm_engine_gt_point_correspondences_count(self._h, POINT_LEVELS[level], 0 if T is None else T.ctypes.data,
+                                                                    float(radius), totals, _lib.stream_ptr()),
+                   'rdm_engine_gt_point_correspondences_count')
+        c = int(totals[0])
+        out = torch.empty((c, 2), dtype=torch.int64, device=self.device)
+        _lib.check(self.L.rdm_engine_gt_point_correspondences_fill(self._h, _lib.ptr(out) if c > 0 else 0, c, _lib.stream_ptr()),
+                   'rdm_engine_gt_point_correspondences_fill')
         return out
 
     def corr(self):

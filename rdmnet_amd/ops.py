@@ -682,6 +682,83 @@ def icp_correspondences(pcd, target, max_correspondence_distance):
     return idx[:n], d2[:n]
 
 
+def _transform_arg(transform, name):
+    """None, or anything numpy / torch holds as a 4x4 -> a contiguous float64 host array (kept alive by the caller)."""
+    import numpy as np
+    if transform is None:
+        return None
+    if isinstance(transform, torch.Tensor):
+        transform = transform.detach().cpu().numpy()
+    T = np.ascontiguousarray(np.asarray(transform, dtype=np.float64))
+    if T.shape != (4, 4):
+        raise ValueError(f'{name}: transform must be 4x4, got {T.shape}')
+    return T
+
+
+def _ball_count(ref_points, src_points, transform, radius, name, want_min=False, want_hits=False):
+    """rdm_ball_count -> (totals (C, ref rows, src rows, status), ws, ref_min_d2, ref_hit, src_hit); the workspace holds the index,
+    counts and offsets rdm_ball_fill reads."""
+    if radius is None or not radius > 0:
+        raise ValueError(f'{name} must be > 0, got {radius}')
+    L = _lib.lib()
+    ldr, lds = _points_arg(ref_points, 'ref_points'), _points_arg(src_points, 'src_points')
+    if ref_points.device != src_points.device:
+        raise ValueError('ref_points and src_points must be on the same device')
+    T = _transform_arg(transform, name)
+    dev = ref_points.device
+    n, m = ref_points.shape[0], src_points.shape[0]
+    ref_min = torch.empty((max(n, 1),), dtype=torch.float64, device=dev) if want_min else None
+    ref_hit = torch.empty((max(n, 1),), dtype=torch.uint8, device=dev) if want_hits else None
+    src_hit = torch.empty((pad4(max(m, 1)),), dtype=torch.uint8, device=dev) if want_hits else None
+    # (a buffer of its own, not the shared scratch: the fill call reads it after other ops may have run)
+    ws = torch.empty((L.rdm_ball_workspace_bytes(n, m),), dtype=torch.uint8, device=dev)
+    totals = (ctypes.c_int64 * 4)()
+    _lib.check(L.rdm_ball_count(_lib.ptr(ref_points), n, ldr, _lib.ptr(src_points), m, lds, 0 if T is None else T.ctypes.data,
+                                float(radius), _lib.ptr(ref_min), _lib.ptr(ref_hit), _lib.ptr(src_hit), totals, ws.data_ptr(),
+                                ws.numel(), _lib.stream_ptr()),
+               'rdm_ball_count')
+    return tuple(int(x) for x in totals), ws, ref_min, ref_hit, src_hit
+
+
+def get_correspondences(ref_points, src_points, transform=None, matching_radius=None):
+    """get_correspondences (geotransformer/utils/registration.py:203-216) on the GPU (rdm_ball_count + rdm_ball_fill): ref_points /
+    src_points float32 CUDA [N, >=3] (xyz first, any row stride), transform 4x4 src -> ref (None: src as it is), read as float64
+    -> int64 CUDA [C, 2], every (i, j) with |ref_i - T src_j| <= matching_radius (closed, as cKDTree's ball) in ascending (i, j).
+    The only read-back is C."""
+    L = _lib.lib()
+    totals, ws, _, _, _ = _ball_count(ref_points, src_points, transform, matching_radius, 'matching_radius')
+    c = totals[0]
+    out = torch.empty((c, 2), dtype=torch.int64, device=ref_points.device)
+    if c > 0:
+        _lib.check(L.rdm_ball_fill(_lib.ptr(ref_points), ref_points.shape[0], _points_arg(ref_points, 'ref_points'),
+                                   src_points.shape[0], out.data_ptr(), c, ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+                   'rdm_ball_fill')
+    return out
+
+
+def compute_overlap(ref_points, src_points, transform=None, positive_radius=0.1, both=False):
+    """compute_overlap (geotransformer/utils/registration.py:191-197) on the GPU: the fraction of ref rows whose nearest (moved)
+    src row is closer than positive_radius (strict) -> float; both=True -> (ref side, src side), the src side being the fraction
+    of src rows whose nearest ref row is that close, from the same call.  An empty cloud gives 0.0."""
+    o_ref, o_src, _ = pair_overlap(ref_points, src_points, transform, positive_radius, 'positive_radius')
+    return (o_ref, o_src) if both else o_ref
+
+
+def pair_overlap(ref_points, src_points, transform, radius, name='radius'):
+    """One count pass (rdm_ball_count, no list) -> (compute_overlap of the ref side, of the src side, the number of
+    get_correspondences rows) at `radius`."""
+    totals, _, _, _, _ = _ball_count(ref_points, src_points, transform, radius, name)
+    n, m = ref_points.shape[0], src_points.shape[0]
+    return (totals[1] / n if n > 0 else 0.0), (totals[2] / m if m > 0 else 0.0), totals[0]
+
+
+def overlap_labels(ref_points, src_points, transform, radius):
+    """The per-point labels of loss.py:94-103,155-158 without the list: (ref_gt bool CUDA [N], src_gt bool CUDA [M]), a row being
+    true iff it appears in some correspondence of get_correspondences(ref_points, src_points, transform, radius)."""
+    _, _, _, ref_hit, src_hit = _ball_count(ref_points, src_points, transform, radius, 'radius', want_hits=True)
+    return ref_hit[:ref_points.shape[0]].bool(), src_hit[:src_points.shape[0]].bool()
+
+
 def _gt_check(t, name, shape, dtype, device):
     if not isinstance(t, torch.Tensor):
         raise RuntimeError(f'gt_node_correspondences: {name} must be a tensor')

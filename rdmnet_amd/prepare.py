@@ -9,6 +9,12 @@
       R/poses/%02d.txt + R/calib/sequences/%02d/calib.txt + the raw scans -> R/icp{thres}/%02d: the pair lists with
       ICP-refined poses, restating preporcess/generate_kitti_pairs.py:95-195 with the GPU ICP (ops.icp_point_to_point).
 
+  python -m rdmnet_amd.prepare overlap --dataset-root R [--distance 10] [--radius 0.6]
+      R/icp{distance}/%02d + R/downsampled_xyzi -> R/overlap{distance}/%02d, one line per pair of the list:
+      `frame0 frame1 overlap_ref overlap_src num_corr` -- compute_overlap both ways and the number of get_correspondences rows at
+      `radius` (geotransformer/utils/registration.py:191-216) on the GPU (ops.pair_overlap: one count pass, no list), the
+      number the reference's loop-closure protocol selects pairs by (experiments/test_batchoffline.py:246).
+
 Stated deviations from the reference's pair script:
   * the pair file is written fresh; the reference appends to it (its `open(..., 'a')`), so a rerun doubles it;
   * the odometry pose M is handed to the ICP as its `init` instead of being applied to the scan on the host first: the
@@ -195,6 +201,53 @@ def generate_pairs(root, seq, thres=10, max_iteration=5000, distance=0.5, log=pr
     return out
 
 
+class _ListedPairs:
+    """Items for dataset.PairStager: the two down-sampled scans of a pair of an icp{distance} list (frame0 = ref, frame1 = src)."""
+
+    def __init__(self, root, metadata):
+        self.root, self.metadata = root, metadata
+
+    def __len__(self):
+        return len(self.metadata)
+
+    def _scan(self, seq, frame):
+        return np.load(osp.join(self.root, 'downsampled_xyzi', '%02d' % seq, '%06d.npy' % frame))[:, :3].astype(np.float32)
+
+    def __getitem__(self, i):
+        meta = self.metadata[i]
+        return dict(meta, ref_points=self._scan(meta['seq_id'], meta['frame0']), src_points=self._scan(meta['seq_id'], meta['frame1']))
+
+
+def format_overlap_line(frame0, frame1, overlap_ref, overlap_src, num_corr):
+    return f'{frame0} {frame1} {overlap_ref:.6f} {overlap_src:.6f} {num_corr}\n'
+
+
+def listed_sequences(root, distance):
+    """The sequences that have a pair list under R/icp{distance}."""
+    files = glob.glob(osp.join(root, 'icp%d' % distance, '[0-9][0-9]'))
+    if not files:
+        raise FileNotFoundError(f'no pair lists under {osp.join(root, "icp%d" % distance)}')
+    return sorted(int(osp.basename(f)) for f in files)
+
+
+def overlap_sequence(root, seq, distance=10, radius=0.6, workers=4, log=print):
+    """R/overlap{distance}/%02d for one sequence -> [(frame0, frame1, overlap_ref, overlap_src, num_corr)].  The scans are read on
+    `workers` (at most 16) host threads while the previous pair is on the GPU (dataset.PairStager)."""
+    from . import ops
+    from .dataset import PairStager, load_kitti_gt_txt
+    metadata = load_kitti_gt_txt(osp.join(root, 'icp%d' % distance), seq)
+    out_dir = osp.join(root, 'overlap%d' % distance)
+    os.makedirs(out_dir, exist_ok=True)
+    out = []
+    with open(osp.join(out_dir, '%02d' % seq), 'w') as f:
+        for item, ref, src in PairStager(_ListedPairs(root, metadata), workers=max(1, min(int(workers), 16))):
+            o_ref, o_src, num = ops.pair_overlap(ref, src, item['transform'], radius)
+            out.append((item['frame0'], item['frame1'], o_ref, o_src, num))
+            f.write(format_overlap_line(*out[-1]))
+    log(f'sequence {seq:02d}: {len(out)} pairs written to {osp.join(out_dir, "%02d" % seq)}')
+    return out
+
+
 def _parser():
     p = argparse.ArgumentParser(prog='python -m rdmnet_amd.prepare', description=__doc__.split('\n\n')[0])
     sub = p.add_subparsers(dest='command', required=True)
@@ -210,16 +263,29 @@ def _parser():
     q.add_argument('--thres', type=int, default=10, help='pair distance in metres (default 10)')
     q.add_argument('--max-iteration', type=int, default=5000)
     q.add_argument('--distance', type=float, default=0.5, help='ICP max correspondence distance in metres (default 0.5)')
+    o = sub.add_parser('overlap', help='icp{distance} pair lists + downsampled_xyzi -> overlap{distance}: overlap and correspondences per pair')
+    o.add_argument('--dataset-root', required=True)
+    o.add_argument('--distance', type=int, default=10, help='the pair lists to read: icp{distance} (default 10)')
+    o.add_argument('--radius', type=float, default=0.6, help='matching radius in metres (default 0.6)')
+    o.add_argument('--workers', type=int, default=4, help='host threads that read scans ahead (default 4, at most 16)')
     return p
 
 
 def main(argv=None):
     p = _parser()
     a = p.parse_args(argv)
-    if any(s < 0 for s in a.sequences):
-        p.error('sequences must be >= 0')
     if not osp.isdir(a.dataset_root):
         p.error(f'--dataset-root {a.dataset_root} is not a directory')
+    if a.command == 'overlap':
+        if not a.radius > 0:
+            p.error('--radius must be > 0')
+        if not 1 <= a.workers <= 16:
+            p.error('--workers must be 1 ... 16')
+        for s in listed_sequences(a.dataset_root, a.distance):
+            overlap_sequence(a.dataset_root, s, a.distance, a.radius, a.workers)
+        return 0
+    if any(s < 0 for s in a.sequences):
+        p.error('sequences must be >= 0')
     if a.command == 'pairs':
         if a.thres < 0:
             p.error('--thres must be >= 0')
