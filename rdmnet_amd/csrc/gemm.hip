@@ -16,7 +16,6 @@
 #include "../../include/rdmnet_hip.h"
 #include <cmath>
 #include <cstdlib>
-#include <type_traits>
 
 #include "common.h"
 #include "internal.h"
@@ -29,44 +28,39 @@ using namespace rdm;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-struct GemmArgs {
-  const float* A;
-  const float* B;
-  float* C;
-  const float* bias;    // [N] or null
-  const float* rowdiv;  // [M] or null
-  int M, N, K;
-  int lda, ldb, ldc;
-  long long sa, sb, sc;  // batch strides (elements)
-  int act;               // 0 none, 1 relu, 2 leaky-relu(0.1)
-  int splits;            // split-K factor (partials go to `part`)
-  float* part;           // [batch*splits, M, N] when splits > 1
-  double* stats;         // optional GroupNorm partials [grid.y][2][N] (non split-K only)
+struct GemmArgs {  // (the defaults: one plain product -- no batch strides, epilogue operands, split-K or gathered rows)
+  const float* A = nullptr;
+  const float* B = nullptr;
+  float* C = nullptr;
+  const float* bias = nullptr;    // [N] or null
+  const float* rowdiv = nullptr;  // [M] or null
+  int M = 0, N = 0, K = 0;
+  int lda = 0, ldb = 0, ldc = 0;
+  long long sa = 0, sb = 0, sc = 0;  // batch strides (elements)
+  int act = 0;                       // 0 none, 1 relu, 2 leaky-relu(0.1)
+  int splits = 1;                    // split-K factor (partials go to `part`)
+  float* part = nullptr;             // [batch*splits, M, N] when splits > 1
+  double* stats = nullptr;           // optional GroupNorm partials [grid.y][2][N] (non split-K only)
   // CAT kernels only -- A is the decoder's [nearest_upsample(coarse) | skip] (backbone.py:118-151, functional.py:6-22)
   // without materialising it: columns k < c1 of row m are coarse[aidx[m * ldi]] (row index out of range: zeros), the rest
   // skip[m]; A = coarse, lda its row stride; c1 a multiple of the k-tile depth
-  const float* A2;
-  const int64_t* aidx;
-  int lda2, ldi, c1, n_coarse;
+  const float* A2 = nullptr;
+  const int64_t* aidx = nullptr;
+  int lda2 = 0, ldi = 0, c1 = 0, n_coarse = 0;
   // CAT + TRANS_B ("patch scores", model_infer.py:291-311): row m of batch b of A is A[aidx[b * M + m]] and row n of B is
   // B[bidx[b * N + n]] (an index outside [0, n_coarse) / [0, n_b): a zero row, as the reference's padded gather gives); tiles
   // whose rows or columns are all shadow rows are written as zeros without touching the features
-  const int64_t* bidx;
-  int n_b;
-  int xcd_tiles;  // 1: output tiles re-mapped so that an XCD (workgroup id % 8) owns whole row tiles with all their column tiles
+  const int64_t* bidx = nullptr;
+  int n_b = 0;
+  int xcd_tiles = 0;  // 1: output tiles re-mapped so that an XCD (workgroup id % 8) owns whole row tiles with all their column tiles
 #ifdef RDM_GEMM_TIMING
-  unsigned long long* clk;  // tools/gemm_phase_lab.hip: shader-clock stamps of workgroup (0,0,0), thread 0
+  unsigned long long* clk = nullptr;  // tools/gemm_phase_lab.hip: shader-clock stamps of workgroup (0,0,0), thread 0
 #endif
 };
 #ifdef RDM_GEMM_TIMING
 #define GEMM_STAMP(k) do { if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) g.clk[k] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define GEMM_STAMP(k) do { } while (0)
-#endif
-#ifdef RDM_GEMM_TIMING  // (wide form: stamps of workgroup (0,0,0), wavefront 0; per-tile stamps for the first 128 k-tiles)
-#define GEMM_WIDE_STAMP(k) do { if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0 && (k) < 392) g.clk[k] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define GEMM_WIDE_STAMP(k) do { } while (0)
 #endif
 
 __device__ __forceinline__ float apply_act(float v, int act) {
@@ -441,347 +435,6 @@ __device__ __forceinline__ void gemm_kernel_body(const dim3 blockIdx, const dim3
 template <int BM, int BN, int WM, int WN, int BK, bool TRANS_B, int PF, bool CAT = false>
 // (64-row / 128 x 32 tiles: four workgroups per CU = four wavefronts per SIMD, 128 registers each)
 __global__ __launch_bounds__(256, (BM * BN <= 64 * 64 ? 4 : 1)) void gemm_kernel(GemmArgs g) { gemm_kernel_body<BM, BN, WM, WN, BK, TRANS_B, PF, CAT>(blockIdx, gridDim, g); }
-
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The WIDE form (round 6): 128 x 128 x 32 tiles for the products with a weight matrix as B ([K, N] row-major), 2 x 2
-// wavefronts of 64 x 64 each -- FOUR 32x32 accumulators per wavefront -- and two workgroups per CU.  What it changes against
-// gemm_kernel<64, 64> (docs/EXPERIMENTS.md 5g: matrix pipe 65 % busy where the vendor library's kernel has 93 %):
-//   * operand bytes per flop through the CU's L2 port and through LDS are halved (a 64 x 64 tile at the fp32 MFMA rate asks
-//     for 16 B/clk per CU from L2, about what a CU gets);
-//   * the LDS images are stored in FRAGMENT order -- plane (k-group g of 8 k, k parity lk) x row x 4 k-steps -- so that the
-//     operands of FOUR k-steps of a 32-row fragment are ONE ds_read_b128 (16 per k-tile and wavefront instead of 64
-//     ds_read_b32 for the same 64 x 64 of output), written as ds_write_b64 (A: a row's float4 of k holds two k-steps of either
-//     parity) and ds_write_b128 (B: a thread loads the four rows k = 8 g + lk + 2 j of its four columns and stores one
-//     column's four k-steps per instruction); XOR swizzles (A: row ^ 2 g, B: n ^ ((n >> 3) & 3)) keep reads and writes
-//     conflict-free in their lane groups (MI355X_MICROARCH.md, LDS);
-//   * ONE workgroup barrier per k-tile (64 MFMAs per wavefront), placed before the tile's last k-group: the next tile's first
-//     operands are read behind it, under that group's MFMAs.
-// Same arithmetic as the 64 x 64 tile on every output element: v_mfma_f32_32x32x2_f32 over the k pairs (2 s, 2 s + 1) in
-// ascending s, the same split-K ranges (multiples of 32), the same epilogue -- and GroupNorm column partials per 64-ROW block
-// in the 64 x 64 tile's combination order (16 row classes mod 16, fp64), so the products that move to this form keep their bits.
-template <bool CAT, bool MI16 = false>
-__device__ __forceinline__ void gemm_wide_body(const dim3 blockIdx, const dim3 gridDim, GemmArgs g) {
-  (void)gridDim;
-  constexpr int BM = 128, BN = 128, BK = 32;
-  constexpr int IMG = 8 * BM * 4;  // floats of one operand image: 8 planes x 128 rows x 4 k-steps (BM == BN)
-  constexpr int CR = 64, LDC_S = BN + 4, TPR = BN / 4, RPI = 256 / TPR;  // epilogue: 64 rows per pass, 32 threads per row, 8 rows per iteration
-  static_assert(BM == BN && RPI == 8 && CR * LDC_S * 4 <= 4 * IMG * 4 && 16 * BN * 2 * 8 <= 4 * IMG * 4, "wide tile layout");
-  __shared__ __attribute__((aligned(16))) char smem[4 * IMG * 4];  // 64 KB: [A0 | A1 | B0 | B1], then the epilogue's staging
-  float* As = reinterpret_cast<float*>(smem);
-  float* Bs = As + 2 * IMG;
-  float (*Cs)[LDC_S] = reinterpret_cast<float (*)[LDC_S]>(smem);
-  double (*stat_red)[BN][2] = reinterpret_cast<double (*)[BN][2]>(smem);  // [16 row classes][BN][sum, sum of squares]
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  // MI16: the same products on v_mfma_f32_16x16x4_f32 -- like 32x32x2 an fp32 fma chain over ascending k (tools/mfma_order_probe.hip: the
-  // two instructions and the fmaf chain agree bit for bit), with a quarter of the accumulator registers moved per flop
-  constexpr int NF = MI16 ? 4 : 2;    // fragments per wavefront and operand (16 or 32 rows each)
-  constexpr int FR = MI16 ? 16 : 32;  // rows of a fragment
-  constexpr int KG = MI16 ? 16 : 8;   // k per group of four k-steps (= one ds_read_b128 per fragment)
-  constexpr int NG = BK / KG;         // k-groups per tile
-  constexpr int KL = MI16 ? 4 : 2;    // lane groups along k of one MFMA
-  const int lk = MI16 ? lane >> 4 : lane >> 5, li = MI16 ? lane & 15 : lane & 31;
-  const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-  const int batch = blockIdx.z / g.splits, split = blockIdx.z % g.splits;
-  const float* A = g.A + (CAT ? 0 : batch * g.sa);
-  const float* B = g.B + batch * g.sb;
-  const int ktiles = (g.K + BK - 1) / BK;
-  const int per = (ktiles + g.splits - 1) / g.splits;
-  const int kt0 = split * per, kt1 = min(ktiles, kt0 + per);
-  GEMM_WIDE_STAMP(0);
-
-  // ---- staging: a thread moves 4 float4 of A (rows a_row + 32 i, k = 4 a_q ..) and 4 float4 of B (rows 8 b_g + b_lk + 2 j, columns b_n4 ..)
-  const int a_q = tid & 7, a_row = tid >> 3;
-  const int b_p = tid >> 5, b_n4 = (tid & 31) * 4;
-  const int b_k = MI16 ? 16 * (b_p >> 2) + (b_p & 3) : 8 * (b_p >> 1) + (b_p & 1);  // first of the thread's four rows (stride KL)
-  float4 ra[4], rb[4];
-  const float* a_ptr[4];
-  long long cat_row[CAT ? 4 : 1];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = min(m0 + a_row + 32 * i, g.M - 1);
-    if constexpr (CAT) {
-      const long long id = g.aidx[static_cast<long long>(row) * g.ldi];
-      cat_row[i] = (id >= 0 && id < g.n_coarse) ? id : -1;
-      a_ptr[i] = A + max(cat_row[i], 0ll) * g.lda;
-    } else {
-      a_ptr[i] = A + static_cast<long long>(row) * g.lda;
-    }
-  }
-  const float* a2_ptr[CAT ? 4 : 1];
-  if constexpr (CAT) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a2_ptr[i] = g.A2 + static_cast<long long>(min(m0 + a_row + 32 * i, g.M - 1)) * g.lda2;
-  }
-  const float* b_ptr = B + min(n0 + b_n4, g.ldb - 4);
-  const bool b_col_ok = n0 + b_n4 < g.ldb;
-  auto masked = [](const float4& v, bool ok) { return make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f); };
-  auto load_a = [&](int kt, int i) {
-    const int k0 = min(kt, kt1 - 1) * BK;  // past the end: the last tile again (stored to a buffer nobody multiplies)
-    if constexpr (CAT) {  // (a k-tile lies on one side of c1: workgroup-uniform)
-      ra[i] = *reinterpret_cast<const float4*>(k0 < g.c1 ? a_ptr[i] + (k0 + 4 * a_q) : a2_ptr[i] + min(k0 - g.c1 + 4 * a_q, g.K - g.c1 - 4));
-    } else {
-      ra[i] = *reinterpret_cast<const float4*>(a_ptr[i] + min(k0 + 4 * a_q, g.K - 4));
-    }
-  };
-  auto load_b = [&](int kt, int j) {
-    const int k0 = min(kt, kt1 - 1) * BK;
-    rb[j] = *reinterpret_cast<const float4*>(b_ptr + static_cast<long long>(min(k0 + b_k + KL * j, g.K - 1)) * g.ldb);
-  };
-  // A piece i: the float4 (k = 4 q .. 4 q + 3 of one row) is k-steps j, j + 1 of parity 0 (x, z) and of parity 1 (y, w) of k-group q / 2
-  auto store_a = [&](int buf, int kt, int i) {
-    const int k0 = min(kt, kt1 - 1) * BK;
-    const int row = a_row + 32 * i;
-    bool ok = m0 + row < g.M && k0 + 4 * a_q < g.K;
-    if constexpr (CAT) ok = ok && (k0 >= g.c1 || cat_row[i] >= 0);
-    const float4 v = masked(ra[i], ok);
-    if constexpr (MI16) {  // k = 4 q + e: k-step q % 4 of lane group e of k-group q / 4 -> four planes, one float each
-      float* p = As + buf * IMG + (((a_q >> 2) * 4 * BM + row) * 4 + (a_q & 3));
-      p[0] = v.x; p[BM * 4] = v.y; p[2 * BM * 4] = v.z; p[3 * BM * 4] = v.w;
-    } else {
-      const int g2 = a_q & 6;  // 2 x the k-group
-      float* p = As + buf * IMG + ((g2 * BM + (row ^ g2)) * 4 + (a_q & 1) * 2);
-      *reinterpret_cast<float2*>(p) = make_float2(v.x, v.z);
-      *reinterpret_cast<float2*>(p + BM * 4) = make_float2(v.y, v.w);
-    }
-  };
-  // B piece c: column b_n4 + c of the thread's four rows = that column's four k-steps of plane b_p
-  auto store_b = [&](int buf, int kt, int c) {
-    const int k0 = min(kt, kt1 - 1) * BK;
-    float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float4& r = rb[j];
-      const float e = c == 0 ? r.x : (c == 1 ? r.y : (c == 2 ? r.z : r.w));
-      v[j] = (b_col_ok && k0 + b_k + KL * j < g.K) ? e : 0.f;
-    }
-    const int n = b_n4 + c;
-    *reinterpret_cast<float4*>(Bs + buf * IMG + (b_p * BN + (n ^ ((n >> 3) & 3))) * 4) = make_float4(v[0], v[1], v[2], v[3]);
-  };
-
-  const bool partial = g.splits > 1;
-  const int c4 = (tid % TPR) * 4, rsub = tid / TPR;
-  const int gcol = n0 + c4;
-  float bv[4] = {0.f, 0.f, 0.f, 0.f};
-  if (!partial && g.bias)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) bv[e] = gcol + e < g.N ? g.bias[gcol + e] : 0.f;
-
-  using Acc = typename std::conditional<MI16, f32x4_t, f32x16>::type;
-  constexpr int AR = MI16 ? 4 : 16;
-  Acc acc[NF][NF];
-#pragma unroll
-  for (int i = 0; i < NF; ++i)
-#pragma unroll
-    for (int j = 0; j < NF; ++j)
-#pragma unroll
-      for (int r = 0; r < AR; ++r) acc[i][j][r] = 0.f;
-
-  // ---- fragment reads: k-group gq of buffer buf -> four k-steps of the two A and the two B fragments of this wavefront
-  int a_frag[NF], b_frag[NF];
-#pragma unroll
-  for (int i = 0; i < NF; ++i) {
-    a_frag[i] = wm * 64 + i * FR + li;
-    const int n = wn * 64 + i * FR + li;
-    b_frag[i] = n ^ ((n >> 3) & 3);
-  }
-  float af[2][NF][4], bf[2][NF][4];  // [register set][fragment][k-step]
-  auto read_group = [&](int set, int buf, int gq) {
-    const float* ab = As + buf * IMG + (KL * gq + lk) * BM * 4;
-    const float* bb = Bs + buf * IMG + (KL * gq + lk) * BN * 4;
-#pragma unroll
-    for (int i = 0; i < NF; ++i) {
-      const float4 t = *reinterpret_cast<const float4*>(ab + ((MI16 ? a_frag[i] : a_frag[i] ^ (2 * gq)) * 4));
-      af[set][i][0] = t.x; af[set][i][1] = t.y; af[set][i][2] = t.z; af[set][i][3] = t.w;
-    }
-#pragma unroll
-    for (int j = 0; j < NF; ++j) {
-      const float4 t = *reinterpret_cast<const float4*>(bb + b_frag[j] * 4);
-      bf[set][j][0] = t.x; bf[set][j][1] = t.y; bf[set][j][2] = t.z; bf[set][j][3] = t.w;
-    }
-  };
-  // One k-group = 16 MFMAs (4 k-steps x 2 x 2 fragments; every accumulator takes its k-steps in ascending order), written as
-  // chunks of one MFMA + one piece of the tile's other work, fenced by scheduling barriers (a wavefront issues in order:
-  // everything else has to stand BETWEEN the MFMAs to run in their shadows -- gemm_kernel_body).
-  auto group = [&](int set, auto&& piece) {
-#pragma unroll
-    for (int c = 0; c < 4 * NF * NF; ++c) {
-      const int t = c / (NF * NF), i = (c / NF) % NF, j = c % NF;
-      if constexpr (MI16) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[set][i][t], bf[set][j][t], acc[i][j], 0, 0, 0);
-      else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[set][i][t], bf[set][j][t], acc[i][j], 0, 0, 0);
-      piece(c);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-#ifndef GW_ABLATE
-#define GW_ABLATE 0  // tools/gemm_wide_lab.hip: 1 = no barrier in the loop, 2 = no global loads, 4 = no LDS stores (timing probes, wrong results)
-#endif
-  auto tile = [&](int kt, int buf) {
-    GEMM_WIDE_STAMP(8 + (kt - kt0));
-    if constexpr (MI16) {  // two k-groups of 64 MFMAs (32 clocks each): stores and the other group's operands under the first, barrier, loads under the second
-      group(0, [&](int c) {
-        if (c == 0) read_group(1, buf, 1);
-        if (!(GW_ABLATE & 4)) {
-          if (c >= 2 && c <= 16 && (c & 3) == 2) store_a(buf ^ 1, kt + 1, (c - 2) >> 2);
-          if (c >= 20 && c <= 32 && (c & 3) == 0) store_b(buf ^ 1, kt + 1, (c - 20) >> 2);
-        }
-      });
-      GEMM_WIDE_STAMP(136 + (kt - kt0));
-      if (!(GW_ABLATE & 1)) lds_barrier();
-      GEMM_WIDE_STAMP(264 + (kt - kt0));
-      __builtin_amdgcn_sched_barrier(0);
-      group(1, [&](int c) {
-        if (c == 0) read_group(0, buf ^ 1, 0);
-        if (!(GW_ABLATE & 2)) {
-          if (c >= 2 && c <= 16 && (c & 3) == 2) load_a(kt + 2, (c - 2) >> 2);
-          if (c >= 20 && c <= 32 && (c & 3) == 0) load_b(kt + 2, (c - 20) >> 2);
-        }
-      });
-      return;
-    }
-    // group 0: operands in set 0; group 1's arrive; tile kt + 1 goes from the register stage into the other buffer
-    group(0, [&](int c) {
-      if (c == 0) read_group(1, buf, 1);
-      if (!(GW_ABLATE & 4)) {
-        if (c >= 1 && c <= 4) store_a(buf ^ 1, kt + 1, c - 1);
-        if (c >= 5 && c <= 8) store_b(buf ^ 1, kt + 1, c - 5);
-      }
-    });
-    // group 1: group 2's operands arrive; tile kt + 2 is requested from global memory
-    group(1, [&](int c) {
-      if (c == 0) read_group(0, buf, 2);
-      if (!(GW_ABLATE & 2)) {
-        if (c >= 1 && c <= 4) load_a(kt + 2, c - 1);
-        if (c >= 5 && c <= 8) load_b(kt + 2, c - 5);
-      }
-    });
-    group(0, [&](int c) {
-      if (c == 0) read_group(1, buf, 3);
-    });
-    GEMM_WIDE_STAMP(136 + (kt - kt0));
-    if (!(GW_ABLATE & 1)) lds_barrier();  // every wavefront has read this tile (its last operands are in registers) and written the next one
-    GEMM_WIDE_STAMP(264 + (kt - kt0));
-    __builtin_amdgcn_sched_barrier(0);
-    group(1, [&](int c) {
-      if (c == 0) read_group(0, buf ^ 1, 0);
-    });
-  };
-  if (kt0 < kt1) {  // (an empty K range -- more splits than k-tiles -- leaves the accumulators at zero)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) load_a(kt0, i);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) load_b(kt0, j);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) store_a(0, kt0, i);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) store_b(0, kt0, c);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) load_a(kt0 + 1, i);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) load_b(kt0 + 1, j);
-  }
-  lds_barrier();
-  GEMM_WIDE_STAMP(1);
-  if (kt0 < kt1) {
-    read_group(0, 0, 0);
-    for (int kt = kt0; kt < kt1; ++kt) tile(kt, (kt - kt0) & 1);
-  }
-  lds_barrier();  // (the last tile's look-ahead reads are done: the staging tile may overwrite the images)
-  GEMM_WIDE_STAMP(2);
-
-  // ---- epilogue: two passes of 64 rows through LDS into row-major float4 stores; GroupNorm partials per 64-row block
-  const bool stats = g.stats != nullptr && !partial;
-  const bool has_rd = !partial && g.rowdiv != nullptr;
-  const int act = g.act;
-  float* C = partial ? g.part + static_cast<long long>(blockIdx.z) * g.M * g.N : g.C + batch * g.sc;
-  const int ldc = partial ? g.N : g.ldc;
-  const bool vec_ok = (ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0;
-#pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {
-    if (m0 + pass * CR >= g.M) break;  // (workgroup-uniform: a 64-row block past the last row -- the 64 x 64 grid has no such block)
-    float rdv[CR / RPI];
-#pragma unroll
-    for (int it = 0; it < CR / RPI; ++it) rdv[it] = has_rd ? g.rowdiv[min(m0 + pass * CR + it * RPI + rsub, g.M - 1)] : 1.f;
-    if (wm == pass) {  // wavefront-uniform: the two wavefront rows own one pass each
-#pragma unroll
-      for (int i = 0; i < NF; ++i)
-#pragma unroll
-        for (int j = 0; j < NF; ++j)
-#pragma unroll
-          for (int r = 0; r < AR; ++r) {
-            if constexpr (MI16) Cs[i * 16 + 4 * lk + r][wn * 64 + j * 16 + li] = acc[i][j][r];
-            else Cs[i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk][wn * 64 + j * 32 + li] = acc[i][j][r];
-          }
-    }
-    lds_barrier();
-    // row class of the 64 x 64 tile's epilogue: its thread rsub16 = row % 16 sums the rows rsub16, rsub16 + 16, .. in that order
-    double cs[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}}, css[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
-#pragma unroll
-    for (int it = 0; it < CR / RPI; ++it) {
-      const int lrow = it * RPI + rsub;
-      const int row = m0 + pass * CR + lrow;
-      if (row < g.M && gcol < g.N) {
-        const float4 t = *reinterpret_cast<const float4*>(&Cs[lrow][c4]);
-        float v[4] = {t.x, t.y, t.z, t.w};
-        if (has_rd) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = v[e] / rdv[it];
-        }
-        if (!partial) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float u = v[e] + bv[e];
-            const float neg = act == 2 ? 0.1f * u : 0.f;
-            v[e] = (act != 0 && !(u > 0.f)) ? neg : u;
-          }
-        }
-        float* dst = C + static_cast<long long>(row) * ldc + gcol;
-        if (vec_ok && gcol + 3 < g.N) {
-          *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (gcol + e < g.N) dst[e] = v[e];
-        }
-        if (stats) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            cs[it & 1][e] += v[e];
-            css[it & 1][e] += static_cast<double>(v[e]) * v[e];
-          }
-        }
-      }
-    }
-    lds_barrier();  // Cs is rewritten by the statistics exchange / the next pass
-    if (stats) {
-#pragma unroll
-      for (int par = 0; par < 2; ++par)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          stat_red[par * RPI + rsub][c4 + e][0] = cs[par][e];
-          stat_red[par * RPI + rsub][c4 + e][1] = css[par][e];
-        }
-      lds_barrier();
-      if (tid < BN && n0 + tid < g.N) {
-        double a = 0.0, b = 0.0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) {
-          a += stat_red[w][tid][0];
-          b += stat_red[w][tid][1];
-        }
-        const long long blk = static_cast<long long>(blockIdx.y) * 2 + pass;
-        g.stats[(blk * 2 + 0) * g.N + n0 + tid] = a;
-        g.stats[(blk * 2 + 1) * g.N + n0 + tid] = b;
-      }
-      lds_barrier();
-    }
-  }
-  GEMM_WIDE_STAMP(3);
-}
-template <bool CAT, bool MI16 = false>
-__global__ __launch_bounds__(256, 2) void gemm_wide_kernel(GemmArgs g) { gemm_wide_body<CAT, MI16>(blockIdx, gridDim, g); }
 
 // Latency-oriented kernel for the transformer-sized products (M up to ~1k rows, K a multiple of 16):
 // one workgroup = ONE 32 x 32 output tile, its four wavefronts split K four ways, operands go straight
@@ -1241,19 +894,6 @@ void launch(const GemmArgs& g, int batches, bool trans_b, hipStream_t st) {
     ::rdm::launch<gemm_kernel_body<BM, BN, WM, WN, BK, false, PF>, gemm_kernel<BM, BN, WM, WN, BK, false, PF>, 256, (BM * BN <= 64 * 64 ? 4 : 1)>(grid, pad, st, g);
 }
 
-// the wide form (gemm_wide_kernel): B = weights [K, N], one product or a batch with strides, optionally the decoder's virtual A
-void launch_wide(const GemmArgs& g, int batches, hipStream_t st, bool mi16_form) {
-  dim3 grid(ceil_div(g.N, 128), ceil_div(g.M, 128), batches * g.splits);
-  static const bool mi16 = ::rdm::dev_knob("RDM_GEMM_WIDE_MI16") != nullptr;  // developer knob (A/B): the 16x16x4 MFMA, same bits
-  if (mi16 || mi16_form) {
-    if (g.aidx) ::rdm::launch<gemm_wide_body<true, true>, gemm_wide_kernel<true, true>, 256, 2>(grid, 0, st, g);
-    else ::rdm::launch<gemm_wide_body<false, true>, gemm_wide_kernel<false, true>, 256, 2>(grid, 0, st, g);
-    return;
-  }
-  if (g.aidx) ::rdm::launch<gemm_wide_body<true>, gemm_wide_kernel<true>, 256, 2>(grid, 0, st, g);
-  else ::rdm::launch<gemm_wide_body<false>, gemm_wide_kernel<false>, 256, 2>(grid, 0, st, g);
-}
-
 }  // namespace
 
 // Residency of the tiled GEMM for the calling thread's launches: `bytes` of unused dynamic LDS per workgroup.  A 64 x 64 tile
@@ -1274,23 +914,42 @@ namespace {
 
 thread_local int g_last_plan[4] = {0, 0, 0, 0};  // tile rows, tile columns, k-tile depth, split-K factor of the last dispatch
 
-// form (tests, A/B runs; rdm_gemm_form): 0 = the library's choice; 1 / 2 = the products the model gives to the 64 x 64 tile run on the
-// wide form instead (128 x 128 x 32 tiles; 1: v_mfma_f32_32x32x2_f32, 2: v_mfma_f32_16x16x4_f32) -- same split factor, same bits.
-int gemm_dispatch(GemmArgs g, int batches, bool trans_b, void* ws, size_t ws_bytes, int* stat_blocks, hipStream_t st, int form = 0) {
+enum Tile { T128, T64, T128x32 };
+
+// How one dense product runs: what the launch needs, and what rdm_gemm_last_plan reports.
+struct GemmPlan {
+  bool small = false;  // the 32 x 32 kernel whose four wavefronts split K (reported as bm = bn = 32, bk = K / 4, splits = 4)
+  Tile tile = T64;
+  int bm = 64, bn = 64, bk = 32;  // block tile of the launch
+  int splits = 1;                 // split-K factor
+  int exp_tile = 0;               // lab build only: experimental tile 4..7 instead of `tile`
+  int xcd_tiles = 0;              // lab build only: GemmArgs::xcd_tiles
+};
+
+// The shapes the 32 x 32 K-split kernel takes (one bias-only product with weights as B: plan_gemm, rdm::gemm_pair).
+bool small_kernel_ok(long long m, long long n, long long k) {
+  return m <= 1536 && k % 16 == 0 && k >= 64 && k <= 1024 && m * n <= 1536 * 512;
+}
+
+// Block tile of the plan's `tile`, and the k-tile depth: deep tiles for the latency-bound small configurations (a 350 x 128 x 128
+// projection is two 64-deep steps instead of eight 16-deep ones), shallow where K itself is tiny.
+//   T128:    16-deep (32-deep measured slower: LDS halves residency)
+//   T64:     32-deep k-tiles: 34 KB of LDS per block -> 4 blocks per CU (64-deep: 2); measured +2 % with 4 pairs in flight
+//            (two k-tiles of register prefetch: -3 % over the path's shapes; four: no further gain -- what bounds these tiles
+//            is the ~20 B/clk a CU draws from L2, see tools/tail_lab.hip, not the latency of one load)
+//            (gathered / concatenated operands exist in the 32-deep instantiation only; its loads clamp k to K - 4)
+void set_tile_shape(GemmPlan& p, long long k, bool gathered) {
+  p.bm = p.tile == T64 ? 64 : 128;
+  p.bn = p.tile == T128 ? 128 : (p.tile == T64 ? 64 : 32);
+  p.bk = p.tile == T128 ? 16 : ((p.tile == T64 ? (k >= 48 || gathered) : k >= 32) ? 32 : 16);
+}
+
+// Tile shape and split-K factor of a tiled product from a small cost model fitted to tools/gemm_sweep_graph.py (HIP-graph-replayed
+// timings of every product shape of the path): a block costs a fixed prologue + epilogue plus a time per 64 of K;
+// blocks run in rounds of (CUs x resident blocks); split-K adds the partial traffic and one more launch.
+// ws_cap: bytes the caller gives for split-K partials; model_cus: the CUs the model plans for.
+GemmPlan plan_tiled(const GemmArgs& g, int batches, size_t ws_cap, long long model_cus = 256) {
   const long long m = g.M, n = g.N, k = g.K;
-  const char* tune_env = ::rdm::dev_knob("RDM_GEMM_TUNE");  // developer knob, see below; any value also bypasses the small kernel
-  if (batches == 1 && !trans_b && !g.rowdiv && !g.stats && !g.aidx && m <= 1536 && k % 16 == 0 && k >= 64 && k <= 1024 &&
-      m * n <= 1536 * 512 && !(tune_env && tune_env[0] != '0')) {
-    if (stat_blocks) *stat_blocks = 0;
-    g_last_plan[0] = 32; g_last_plan[1] = 32; g_last_plan[2] = static_cast<int>(k / 4); g_last_plan[3] = 4;  // K over four wavefronts
-    RDM_DUP_LOOP("gemmsmall")
-    ::rdm::launch<gemm_small_entry, gemm_small_kernel, 256>(dim3(ceil_div<long long>(n, 32), ceil_div<long long>(m, 32)), 0, st, g);
-    return launch_status("gemm_small_kernel");
-  }
-  // Tile shape and split-K factor from a small cost model fitted to tools/gemm_sweep_graph.py (HIP-graph-replayed
-  // timings of every product shape of the path): a block costs a fixed prologue + epilogue plus a time per 64 of K;
-  // blocks run in rounds of (CUs x resident blocks); split-K adds the partial traffic and one more launch.
-  enum Tile { T128, T64, T128x32 };
   // per 64 of K a block that shares its CU with r - 1 others needs max(lat * (1 + alpha (r - 1)), MFMA time * r);
   // constants refitted by tools/gemm_model_fit.py on the sweep in tools/data/ (782 us for the path's 36 shapes against
   // 769 us for the per-shape optimum)
@@ -1298,55 +957,81 @@ int gemm_dispatch(GemmArgs g, int batches, bool trans_b, void* ws, size_t ws_byt
   static const Cand cands[3] = {{T128, 128, 128, 4.0, 2.6, 3.4, 3, 0.0}, {T64, 64, 64, 1.5, 2.2, 0.86, 4, 0.2},
                                 {T128x32, 128, 32, 3.0, 1.3, 0.86, 3, 0.0}};
   static const int split_set[8] = {1, 2, 3, 4, 6, 8, 12, 16};
-  // CUs the model plans for.  (RDM_GEMM_CUS, developer knob: with four pairs in flight a product effectively owns a
-  // quarter of the chip, tools/exp_cumask.sh.)
+  GemmPlan p;
+  double best = 1e30;
+  for (const Cand& c : cands) {
+    if (g.aidx && c.tile != T64) continue;  // the concatenating / gathering operands exist for the 64x64x32 tile only
+    if (c.tile == T128x32 && n > 64) continue;
+    if (c.tile != T128x32 && n <= 32) continue;  // a 64-wide tile would be half empty
+    if (c.tile == T128 && n < 128) continue;
+    const long long tiles = ceil_div<long long>(m, c.bm) * ceil_div<long long>(n, c.bn) * batches;
+    const int max_s = k >= 256 ? static_cast<int>(std::min<long long>(16, k / 128)) : 1;
+    for (int sp : split_set) {
+      if (sp > max_s) break;
+      if (sp > 1 && static_cast<size_t>(m) * n * sp * batches * sizeof(float) > ws_cap) break;
+      const long long blocks = tiles * sp;
+      const double k_per = static_cast<double>(k) / sp / 64.0;
+      const long long per_round = model_cus * c.resident;
+      const long long full = blocks / per_round, rem = blocks % per_round;
+      auto per_k64 = [&](double r) { return std::max(c.lat_k64_us * (1.0 + c.alpha * (r - 1.0)), c.mfma_k64_us * r); };
+      double t = full * (c.fixed_us + k_per * per_k64(c.resident));
+      if (rem) t += c.fixed_us + k_per * per_k64(static_cast<double>(ceil_div<long long>(rem, model_cus)));
+      if (sp > 1) t += 3.0 + static_cast<double>(m) * n * sp * 8.0 / 1.5e6;  // reduce launch + partial write/read
+      if (t < best) {
+        best = t;
+        p.tile = c.tile;
+        p.splits = sp;
+      }
+    }
+  }
+  if (g.aidx && g.bidx) p.splits = 1;  // (patch scores: 256 batches fill the chip; the zero-tile shortcut writes C directly)
+  set_tile_shape(p, k, g.aidx != nullptr);
+  return p;
+}
+
+// The plan of a product: a pure function of the sizes, of WHICH optional operands are present and of the workspace size.
+GemmPlan plan_gemm(const GemmArgs& g, int batches, bool trans_b, size_t ws_cap) {
+  if (batches == 1 && !trans_b && !g.rowdiv && !g.stats && !g.aidx && small_kernel_ok(g.M, g.N, g.K)) {
+    GemmPlan p;
+    p.small = true;
+    p.bm = p.bn = 32; p.bk = g.K / 4; p.splits = 4;  // K over four wavefronts
+    return p;
+  }
+  return plan_tiled(g, batches, ws_cap);
+}
+
+#ifdef RDM_DEV_KNOBS
+// Every developer knob of the dense products (lab build: librdmnet_hip_lab.so); the product library plans with plan_gemm alone.
+
+// RDM_GEMM_TUNE (tools/gemm_sweep*.py) also keeps products off the 32 x 32 kernel, unless its value starts with 0
+bool lab_tune_skips_small() {
+  const char* tune = ::rdm::dev_knob("RDM_GEMM_TUNE");
+  return tune && tune[0] != '0';
+}
+
+void lab_overrides(GemmPlan& p, const GemmArgs& g, int batches, size_t ws_cap) {
+  const long long m = g.M, n = g.N, k = g.K;
+  // RDM_GEMM_CUS: CUs the model plans for (with four pairs in flight a product effectively owns a quarter of the chip,
+  // tools/exp_cumask.sh)
   static const long long model_cus = [] {
     const char* v = ::rdm::dev_knob("RDM_GEMM_CUS");
     const long long n = v ? atoll(v) : 256;
     return n >= 8 && n <= 256 ? n : 256ll;
   }();
-  Tile tile = T64;
-  int best_s = 1;
-  {
-    double best = 1e30;
-    const size_t ws_cap = ws ? ws_bytes : 0;
-    for (const Cand& c : cands) {
-      if (g.aidx && c.tile != T64) continue;
-      if (c.tile == T128x32 && n > 64) continue;
-      if (c.tile != T128x32 && n <= 32) continue;  // a 64-wide tile would be half empty
-      if (c.tile == T128 && n < 128) continue;
-      const long long tiles = ceil_div<long long>(m, c.bm) * ceil_div<long long>(n, c.bn) * batches;
-      const int max_s = k >= 256 ? static_cast<int>(std::min<long long>(16, k / 128)) : 1;
-      for (int sp : split_set) {
-        if (sp > max_s) break;
-        if (sp > 1 && static_cast<size_t>(m) * n * sp * batches * sizeof(float) > ws_cap) break;
-        const long long blocks = tiles * sp;
-        const double k_per = static_cast<double>(k) / sp / 64.0;
-        const long long per_round = model_cus * c.resident;
-        const long long full = blocks / per_round, rem = blocks % per_round;
-        auto per_k64 = [&](double r) { return std::max(c.lat_k64_us * (1.0 + c.alpha * (r - 1.0)), c.mfma_k64_us * r); };
-        double t = full * (c.fixed_us + k_per * per_k64(c.resident));
-        if (rem) t += c.fixed_us + k_per * per_k64(static_cast<double>(ceil_div<long long>(rem, model_cus)));
-        if (sp > 1) t += 3.0 + static_cast<double>(m) * n * sp * 8.0 / 1.5e6;  // reduce launch + partial write/read
-        if (t < best) {
-          best = t;
-          tile = c.tile;
-          best_s = sp;
-        }
-      }
-    }
-  }
-  // developer knob for tuning runs (tools/gemm_sweep*.py): RDM_GEMM_TUNE="<tile 1..3>,<splits>" overrides the model
-  int force_splits = 0, exp_tile = 0;
+  if (p.small && !lab_tune_skips_small()) return;
+  if (p.small || model_cus != 256) p = plan_tiled(g, batches, ws_cap, model_cus);
+  // tuning runs (tools/gemm_sweep*.py): RDM_GEMM_TUNE="<tile 1..3>,<splits>" overrides the model; tiles 4..7 are experimental
+  // (128 x 64, 64 x 128, 128 x 128, 256 x 64; all 32-deep with two register stages)
+  int force_splits = 0;
   if (const char* tune = ::rdm::dev_knob("RDM_GEMM_TUNE")) {
     int t = 0, sp = 0;
     if (sscanf(tune, "%d,%d", &t, &sp) >= 1) {
-      if (t == 1) tile = T128;
-      else if (t == 2) tile = T64;
-      else if (t == 3) tile = T128x32;
-      else if (t >= 4 && t <= 7) exp_tile = t;  // experimental tiles, tuning runs only (see the launch below)
+      if (t == 1) p.tile = T128;
+      else if (t == 2) p.tile = T64;
+      else if (t == 3) p.tile = T128x32;
+      else if (t >= 4 && t <= 7) p.exp_tile = t;
       force_splits = sp;
-      if (t >= 1 && t <= 7 && sp == 0) best_s = 1;
+      if (t >= 1 && t <= 7 && sp == 0) p.splits = 1;
     }
   }
   // developer experiment: RDM_GEMM_BIG="<min M>[,<tile 4..7>]" runs the un-split products with at least that many rows and
@@ -1354,77 +1039,67 @@ int gemm_dispatch(GemmArgs g, int batches, bool trans_b, void* ws, size_t ws_byt
   // co-limits the 64x64 tile when several pairs share the GPU
   static const int big_min_m = [] { const char* v = ::rdm::dev_knob("RDM_GEMM_BIG"); return v ? atoi(v) : 0; }();
   static const int big_tile = [] { const char* v = ::rdm::dev_knob("RDM_GEMM_BIG"); const char* c = v ? strchr(v, ',') : nullptr; return c ? atoi(c + 1) : 6; }();
-  static const bool big_split = ::rdm::dev_knob("RDM_GEMM_BIG_SPLIT") != nullptr;  // (lab: the split-K products too -- same split factor, same bits)
-  if (big_min_m > 0 && exp_tile == 0 && m >= big_min_m && n >= 128 && (best_s == 1 || big_split) && force_splits == 0 && batches == 1)
-    exp_tile = big_tile;
-  static const bool xcd_env = ::rdm::dev_knob("RDM_GEMM_XCD") != nullptr;  // developer knob (A/B)
-  g.xcd_tiles = (xcd_env && ceil_div<long long>(n, 64) > 1 && ceil_div<long long>(m, 64) * ceil_div<long long>(n, 64) >= 64) ? 1 : 0;
+  static const bool big_split = ::rdm::dev_knob("RDM_GEMM_BIG_SPLIT") != nullptr;  // (the split-K products too -- same split factor, same bits)
+  if (big_min_m > 0 && big_tile >= 4 && big_tile <= 7 && p.exp_tile == 0 && m >= big_min_m && n >= 128 && (p.splits == 1 || big_split) && force_splits == 0 && batches == 1)
+    p.exp_tile = big_tile;
+  static const bool xcd_env = ::rdm::dev_knob("RDM_GEMM_XCD") != nullptr;  // (A/B) GemmArgs::xcd_tiles
+  p.xcd_tiles = (xcd_env && ceil_div<long long>(n, 64) > 1 && ceil_div<long long>(m, 64) * ceil_div<long long>(n, 64) >= 64) ? 1 : 0;
   if (g.aidx) {  // the concatenating / gathering operands exist for the 64x64x32 tile only
-    tile = T64;
-    exp_tile = 0;
-    if (g.bidx) best_s = 1, force_splits = 0;  // (256 batches fill the chip; the zero-tile shortcut writes C directly)
+    p.tile = T64;
+    p.exp_tile = 0;
+    if (g.bidx) p.splits = 1, force_splits = 0;
   }
-  // The wide form takes the 64 x 64 tile's products (same split factor, same 64-row statistics blocks: the same bits) when the
-  // output is at least `wide_min_n` columns wide and has enough rows to be worth 128-row tiles.
-  static const int wide_min_m = [] { const char* v = ::rdm::dev_knob("RDM_GEMM_WIDE_MIN_M"); return v ? atoi(v) : 256; }();
-  static const int wide_min_n = [] { const char* v = ::rdm::dev_knob("RDM_GEMM_WIDE_MIN_N"); return v ? atoi(v) : 128; }();
-  // Measured (round 6, docs/EXPERIMENTS.md 5h): bit-identical, half the LDS instructions and no bank conflicts, 94 % of the MFMA rate
-  // per k-tile with two workgroups per CU -- and no faster than the 64 x 64 tile, alone or in the lock-step schedule (639-641 against
-  // 638-643 pairs/s): off unless the lab build asks for it (RDM_GEMM_WIDE=1).
-  static const bool wide_knob = ::rdm::dev_knob("RDM_GEMM_WIDE") != nullptr;
-  const bool wide_off = !wide_knob && form == 0;
-  static const bool wide_force = ::rdm::dev_knob("RDM_GEMM_WIDE_FORCE") != nullptr;  // developer knob (probes): whatever tile the model chose
-  if (wide_force && !trans_b && !g.bidx && exp_tile == 0) tile = T64;
-  const bool wide = !wide_off && tile == T64 && exp_tile == 0 && !trans_b && !g.bidx && (form != 0 || (m >= wide_min_m && n >= wide_min_n));
-  int bm = tile == T64 ? 64 : 128, bn = tile == T128 ? 128 : (tile == T64 ? 64 : 32);
-  if (wide) { bm = 128; bn = 128; }
-  if (exp_tile == 4) { bm = 128; bn = 64; }
-  if (exp_tile == 5) { bm = 64; bn = 128; }
-  if (exp_tile == 6) { bm = 128; bn = 128; }
-  if (exp_tile == 7) { bm = 256; bn = 64; }
-  {
-    int sp = force_splits > 0 ? force_splits : best_s;
-    const size_t need = static_cast<size_t>(m) * n * sp * batches * sizeof(float);
-    if (sp > 1 && ws && ws_bytes >= need) {
-      g.splits = sp;
-      g.part = static_cast<float*>(ws);
-    }
+  if (force_splits > 0)  // (a forced factor whose partials do not fit the workspace: no split)
+    p.splits = (force_splits > 1 && static_cast<size_t>(m) * n * force_splits * batches * sizeof(float) <= ws_cap) ? force_splits : 1;
+  set_tile_shape(p, k, g.aidx != nullptr);
+  static const bool bk16 = ::rdm::dev_knob("RDM_GEMM_BK16") != nullptr;  // (A/B) shallow k-tiles, twice the resident workgroups
+  if (bk16 && p.tile == T64 && !g.aidx) p.bk = 16;
+  if (p.exp_tile) {
+    p.bm = p.exp_tile == 5 ? 64 : (p.exp_tile == 7 ? 256 : 128);
+    p.bn = (p.exp_tile == 5 || p.exp_tile == 6) ? 128 : 64;
+    p.bk = 32;
+  }
+}
+#endif
+
+int launch_plan(const GemmPlan& p, GemmArgs g, int batches, bool trans_b, void* ws, int* stat_blocks, hipStream_t st) {
+  const long long m = g.M, n = g.N;
+  g_last_plan[0] = p.bm; g_last_plan[1] = p.bn; g_last_plan[2] = p.bk; g_last_plan[3] = p.splits;
+  if (p.small) {
+    if (stat_blocks) *stat_blocks = 0;
+    RDM_DUP_LOOP("gemmsmall")
+    ::rdm::launch<gemm_small_entry, gemm_small_kernel, 256>(dim3(ceil_div<long long>(n, 32), ceil_div<long long>(m, 32)), 0, st, g);
+    return launch_status("gemm_small_kernel");
+  }
+  g.xcd_tiles = p.xcd_tiles;
+  if (p.splits > 1) {  // (the plan asks for no more partials than the workspace holds)
+    g.splits = p.splits;
+    g.part = static_cast<float*>(ws);
   }
   double* reduce_stats = nullptr;  // split-K: the statistics come from the reduce pass (64-row blocks)
   if (g.splits > 1) {
     if (batches == 1 && g.N % 4 == 0) reduce_stats = g.stats;
     g.stats = nullptr;
   }
-  if (stat_blocks)  // (the wide form writes the 64 x 64 tile's 64-row blocks)
-    *stat_blocks = g.stats ? static_cast<int>(ceil_div<long long>(m, wide ? 64 : bm))
+  if (stat_blocks)
+    *stat_blocks = g.stats ? static_cast<int>(ceil_div<long long>(m, p.bm))
                            : (reduce_stats ? static_cast<int>(ceil_div<long long>(m, stat_rows_per_block(n))) : 0);
-  g_last_plan[0] = bm; g_last_plan[1] = bn; g_last_plan[3] = g.splits;
-  g_last_plan[2] = wide ? 32 : (tile == T128 ? 16 : ((tile == T64 ? (k >= 48 || g.aidx) : k >= 32) ? 32 : 16));
-  // k-tile depth: deep tiles for the latency-bound small configurations (a 350 x 128 x 128 projection
-  // is two 64-deep steps instead of eight 16-deep ones), shallow where K itself is tiny
   RDM_DUP_LOOP("gemm") {
-  if (wide) launch_wide(g, batches, st, form == 2);
-  else
 #ifdef RDM_DEV_KNOBS  // the experimental tiles exist in the lab build only (RDM_GEMM_TUNE=4..7, RDM_GEMM_BIG)
-  if (exp_tile == 4) launch<128, 64, 2, 2, 32, 2>(g, batches, trans_b, st);
-  else if (exp_tile == 5) launch<64, 128, 2, 2, 32, 2>(g, batches, trans_b, st);
-  else if (exp_tile == 6) launch<128, 128, 2, 2, 32, 2>(g, batches, trans_b, st);
-  else if (exp_tile == 7) launch<256, 64, 4, 1, 32, 2>(g, batches, trans_b, st);
+  if (p.exp_tile == 4) launch<128, 64, 2, 2, 32, 2>(g, batches, trans_b, st);
+  else if (p.exp_tile == 5) launch<64, 128, 2, 2, 32, 2>(g, batches, trans_b, st);
+  else if (p.exp_tile == 6) launch<128, 128, 2, 2, 32, 2>(g, batches, trans_b, st);
+  else if (p.exp_tile == 7) launch<256, 64, 4, 1, 32, 2>(g, batches, trans_b, st);
   else
 #endif
-  switch (tile) {
-    case T128: launch<128, 128, 2, 2, 16>(g, batches, trans_b, st); break;  // 32-deep measured slower (LDS halves residency)
+  switch (p.tile) {  // (the k-tile depth is the plan's: set_tile_shape)
+    case T128: launch<128, 128, 2, 2, 16>(g, batches, trans_b, st); break;
     case T64:
-      // 32-deep k-tiles: 34 KB of LDS per block -> 4 blocks per CU (64-deep: 2); measured +2 % with 4 pairs in flight
-      // (two k-tiles of register prefetch: -3 % over the path's shapes; four: no further gain -- what bounds these tiles
-      // is the ~20 B/clk a CU draws from L2, see tools/tail_lab.hip, not the latency of one load)
-      // (gathered / concatenated operands exist in the 32-deep instantiation only; its loads clamp k to K - 4)
-      static const bool bk16 = ::rdm::dev_knob("RDM_GEMM_BK16") != nullptr;  // developer knob (A/B): shallow k-tiles, twice the resident workgroups
-      if ((k >= 48 && !bk16) || g.aidx) launch<64, 64, 2, 2, 32, 2>(g, batches, trans_b, st);
+      if (p.bk == 32) launch<64, 64, 2, 2, 32, 2>(g, batches, trans_b, st);
       else launch<64, 64, 2, 2, 16>(g, batches, trans_b, st);
       break;
     case T128x32:
-      if (k >= 32) launch<128, 32, 4, 1, 32, 2>(g, batches, trans_b, st);
+      if (p.bk == 32) launch<128, 32, 4, 1, 32, 2>(g, batches, trans_b, st);
       else launch<128, 32, 4, 1, 16>(g, batches, trans_b, st);
       break;
   }
@@ -1444,19 +1119,27 @@ int gemm_dispatch(GemmArgs g, int batches, bool trans_b, void* ws, size_t ws_byt
   return RDM_OK;
 }
 
+// Plans a product (in the lab build: lets the developer knobs change the plan) and launches it.
+int gemm_dispatch(const GemmArgs& g, int batches, bool trans_b, void* ws, size_t ws_bytes, int* stat_blocks, hipStream_t st) {
+  const size_t ws_cap = ws ? ws_bytes : 0;
+  GemmPlan p = plan_gemm(g, batches, trans_b, ws_cap);
+#ifdef RDM_DEV_KNOBS
+  lab_overrides(p, g, batches, ws_cap);
+#endif
+  return launch_plan(p, g, batches, trans_b, ws, stat_blocks, st);
+}
+
 }  // namespace
 
 int rdm::gemm_with_stats(const float* a, int64_t lda, const float* b, int64_t ldb, float* c, int64_t ldc, int64_t m,
                          int64_t n, int64_t k, const float* bias, const float* rowdiv, void* ws, size_t ws_bytes,
-                         double* gn_partial, int* gn_blocks, void* stream, int form) {
+                         double* gn_partial, int* gn_blocks, void* stream) {
   GemmArgs g;
   g.A = a; g.B = b; g.C = c; g.bias = bias; g.rowdiv = rowdiv;
   g.M = static_cast<int>(m); g.N = static_cast<int>(n); g.K = static_cast<int>(k);
   g.lda = static_cast<int>(lda); g.ldb = static_cast<int>(ldb); g.ldc = static_cast<int>(ldc);
-  g.sa = g.sb = g.sc = 0;
-  g.act = 0; g.splits = 1; g.part = nullptr; g.stats = gn_partial;
-  g.A2 = nullptr; g.aidx = nullptr; g.lda2 = g.ldi = g.c1 = g.n_coarse = 0; g.bidx = nullptr; g.n_b = 0;
-  return gemm_dispatch(g, 1, false, ws, ws_bytes, gn_blocks, static_cast<hipStream_t>(stream), form);
+  g.stats = gn_partial;
+  return gemm_dispatch(g, 1, false, ws, ws_bytes, gn_blocks, static_cast<hipStream_t>(stream));
 }
 
 // C = [nearest_upsample(coarse)[idx[:, 0]] | skip] B + bias (decoder, backbone.py:118-151) without materialising the
@@ -1465,43 +1148,37 @@ int rdm::gemm_with_stats(const float* a, int64_t lda, const float* b, int64_t ld
 int rdm::gemm_concat_with_stats(const float* coarse, int64_t ld1, int64_t c1, int64_t n_coarse, const int64_t* idx, int64_t ldi,
                                 const float* skip, int64_t ld2, int64_t c2, const float* b, int64_t ldb, float* c, int64_t ldc,
                                 int64_t m, int64_t n, const float* bias, int act, void* ws, size_t ws_bytes, double* gn_partial,
-                                int* gn_blocks, void* stream, int form) {
+                                int* gn_blocks, void* stream) {
   if (c1 % 32 != 0 || c2 % 4 != 0 || c2 < 4 || ld1 % 4 != 0 || ld2 % 4 != 0 || ldb % 4 != 0 || m <= 0 ||
       ((reinterpret_cast<uintptr_t>(coarse) | reinterpret_cast<uintptr_t>(skip) | reinterpret_cast<uintptr_t>(b)) & 15) != 0)
     return 1;
   GemmArgs g;
-  g.A = coarse; g.B = b; g.C = c; g.bias = bias; g.rowdiv = nullptr;
+  g.A = coarse; g.B = b; g.C = c; g.bias = bias;
   g.M = static_cast<int>(m); g.N = static_cast<int>(n); g.K = static_cast<int>(c1 + c2);
   g.lda = static_cast<int>(ld1); g.ldb = static_cast<int>(ldb); g.ldc = static_cast<int>(ldc);
-  g.sa = g.sb = g.sc = 0;
-  g.act = act; g.splits = 1; g.part = nullptr; g.stats = gn_partial;
+  g.act = act; g.stats = gn_partial;
   g.A2 = skip; g.aidx = idx; g.lda2 = static_cast<int>(ld2); g.ldi = static_cast<int>(ldi); g.c1 = static_cast<int>(c1);
   g.n_coarse = static_cast<int>(n_coarse);
-  g.bidx = nullptr; g.n_b = 0;
-  return gemm_dispatch(g, 1, false, ws, ws_bytes, gn_blocks, static_cast<hipStream_t>(stream), form);
+  return gemm_dispatch(g, 1, false, ws, ws_bytes, gn_blocks, static_cast<hipStream_t>(stream));
 }
-
-namespace {
-bool small_kernel_ok(long long m, long long n, long long k) {
-  return m <= 1536 && k % 16 == 0 && k >= 64 && k <= 1024 && m * n <= 1536 * 512 && !::rdm::dev_knob("RDM_GEMM_TUNE");
-}
-}  // namespace
 
 // Two bias-only products C_i = A_i B_i + bias_i in one launch when both fit the 32x32 K-split kernel (else two launches).
 int rdm::gemm_pair(const float* a0, int64_t lda0, const float* b0, int64_t ldb0, float* c0, int64_t ldc0, int64_t m0, int64_t n0,
                    int64_t k0, const float* bias0, const float* a1, int64_t lda1, const float* b1, int64_t ldb1, float* c1,
                    int64_t ldc1, int64_t m1, int64_t n1, int64_t k1, const float* bias1, void* ws, size_t ws_bytes, void* stream) {
-  if (m0 > 0 && m1 > 0 && small_kernel_ok(m0, n0, k0) && small_kernel_ok(m1, n1, k1) && lda0 % 4 == 0 && lda1 % 4 == 0 &&
-      ldb0 % 4 == 0 && ldb1 % 4 == 0 && ((reinterpret_cast<uintptr_t>(a0) | reinterpret_cast<uintptr_t>(a1)) & 15) == 0) {
+  bool small = m0 > 0 && m1 > 0 && small_kernel_ok(m0, n0, k0) && small_kernel_ok(m1, n1, k1) && lda0 % 4 == 0 && lda1 % 4 == 0 &&
+               ldb0 % 4 == 0 && ldb1 % 4 == 0 && ((reinterpret_cast<uintptr_t>(a0) | reinterpret_cast<uintptr_t>(a1)) & 15) == 0;
+#ifdef RDM_DEV_KNOBS
+  small = small && !lab_tune_skips_small();
+#endif
+  if (small) {
     GemmArgs g[2];
     const float* A[2] = {a0, a1}; const float* B[2] = {b0, b1}; float* C[2] = {c0, c1}; const float* bias[2] = {bias0, bias1};
     const int64_t M[2] = {m0, m1}, N[2] = {n0, n1}, K[2] = {k0, k1}, LA[2] = {lda0, lda1}, LB[2] = {ldb0, ldb1}, LC[2] = {ldc0, ldc1};
     for (int i = 0; i < 2; ++i) {
-      g[i].A = A[i]; g[i].B = B[i]; g[i].C = C[i]; g[i].bias = bias[i]; g[i].rowdiv = nullptr;
+      g[i].A = A[i]; g[i].B = B[i]; g[i].C = C[i]; g[i].bias = bias[i];
       g[i].M = static_cast<int>(M[i]); g[i].N = static_cast<int>(N[i]); g[i].K = static_cast<int>(K[i]);
       g[i].lda = static_cast<int>(LA[i]); g[i].ldb = static_cast<int>(LB[i]); g[i].ldc = static_cast<int>(LC[i]);
-      g[i].sa = g[i].sb = g[i].sc = 0; g[i].act = 0; g[i].splits = 1; g[i].part = nullptr; g[i].stats = nullptr;
-      g[i].A2 = nullptr; g[i].aidx = nullptr; g[i].lda2 = g[i].ldi = g[i].c1 = g[i].n_coarse = 0; g[i].bidx = nullptr; g[i].n_b = 0;
     }
     const long long gx = ceil_div<long long>(std::max(n0, n1), 32), gy = ceil_div<long long>(std::max(m0, m1), 32);
     ::rdm::launch<gemm_small_pair_entry, gemm_small_pair_kernel, 256>(dim3(gx, gy, 2), 0, static_cast<hipStream_t>(stream), g[0], g[1]);
@@ -1526,15 +1203,7 @@ extern "C" int rdm_gemm(const float* a, int64_t lda, int64_t stride_a, const flo
                         int64_t stride_b, int trans_b, float* c, int64_t ldc, int64_t stride_c,
                         int64_t m, int64_t n, int64_t k, int batches, const float* bias,
                         const float* rowdiv, int act, void* ws, size_t ws_bytes, void* stream) {
-  return rdm_gemm_form(a, lda, stride_a, b, ldb, stride_b, trans_b, c, ldc, stride_c, m, n, k, batches, bias, rowdiv, act, ws, ws_bytes, 0, stream);
-}
-
-extern "C" int rdm_gemm_form(const float* a, int64_t lda, int64_t stride_a, const float* b, int64_t ldb,
-                             int64_t stride_b, int trans_b, float* c, int64_t ldc, int64_t stride_c,
-                             int64_t m, int64_t n, int64_t k, int batches, const float* bias,
-                             const float* rowdiv, int act, void* ws, size_t ws_bytes, int form, void* stream) {
   using namespace rdm;
-  RDM_REQUIRE(form >= 0 && form <= 2, "rdm_gemm_form: unknown form %d", form);
   RDM_REQUIRE(a && b && c, "rdm_gemm: null pointer");
   RDM_REQUIRE(m >= 0 && n >= 0 && k >= 0 && batches >= 1, "rdm_gemm: bad sizes");
   if (m == 0 || n == 0) return RDM_OK;
@@ -1549,9 +1218,8 @@ extern "C" int rdm_gemm_form(const float* a, int64_t lda, int64_t stride_a, cons
   g.M = static_cast<int>(m); g.N = static_cast<int>(n); g.K = static_cast<int>(k);
   g.lda = static_cast<int>(lda); g.ldb = static_cast<int>(ldb); g.ldc = static_cast<int>(ldc);
   g.sa = stride_a; g.sb = stride_b; g.sc = stride_c;
-  g.act = act; g.splits = 1; g.part = nullptr; g.stats = nullptr;
-  g.A2 = nullptr; g.aidx = nullptr; g.lda2 = g.ldi = g.c1 = g.n_coarse = 0; g.bidx = nullptr; g.n_b = 0;
-  return gemm_dispatch(g, batches, trans_b != 0, ws, ws_bytes, nullptr, static_cast<hipStream_t>(stream), form);
+  g.act = act;
+  return gemm_dispatch(g, batches, trans_b != 0, ws, ws_bytes, nullptr, static_cast<hipStream_t>(stream));
 }
 
 // y = act(GroupNorm(x W + b [/ rowdiv]) [+ residual]): the Linear/KPConv-weight GEMM writes its
@@ -1567,17 +1235,7 @@ extern "C" int rdm_linear_group_norm(const float* x, int64_t ldx, const float* w
                                      const float* gamma, const float* beta, float eps, const float* residual,
                                      int64_t ldr, int act, float* lin_out, int64_t ld_lin, float* y, int64_t ldy,
                                      uint8_t* positive, void* ws, size_t ws_bytes, void* stream) {
-  return rdm_linear_group_norm_form(x, ldx, w, ldw, bias, rowdiv, m, n, k, groups, gamma, beta, eps, residual, ldr, act, lin_out, ld_lin, y, ldy,
-                                    positive, ws, ws_bytes, 0, stream);
-}
-
-extern "C" int rdm_linear_group_norm_form(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias,
-                                          const float* rowdiv, int64_t m, int64_t n, int64_t k, int groups,
-                                          const float* gamma, const float* beta, float eps, const float* residual,
-                                          int64_t ldr, int act, float* lin_out, int64_t ld_lin, float* y, int64_t ldy,
-                                          uint8_t* positive, void* ws, size_t ws_bytes, int form, void* stream) {
   using namespace rdm;
-  RDM_REQUIRE(form >= 0 && form <= 2, "rdm_linear_group_norm_form: unknown form %d", form);
   RDM_REQUIRE(x && w && gamma && beta && lin_out && y, "rdm_linear_group_norm: null pointer");
   RDM_REQUIRE(k % 4 == 0 && ldx % 4 == 0 && ldw % 4 == 0, "rdm_linear_group_norm: K, ldx, ldw must be multiples of 4");
   if (m == 0) return RDM_OK;
@@ -1592,7 +1250,7 @@ extern "C" int rdm_linear_group_norm_form(const float* x, int64_t ldx, const flo
     return RDM_ERR_WORKSPACE;
   }
   int nblk = 0;
-  if (int e = gemm_with_stats(x, ldx, w, ldw, lin_out, ld_lin, m, n, k, bias, rowdiv, gws, gemm_ws, partial, &nblk, stream, form))
+  if (int e = gemm_with_stats(x, ldx, w, ldw, lin_out, ld_lin, m, n, k, bias, rowdiv, gws, gemm_ws, partial, &nblk, stream))
     return e;
   return group_norm_finish(partial, nblk, lin_out, m, n, ld_lin, groups, gamma, beta, eps, residual, ldr, act, y, ldy,
                            positive, nws, gn_ws, stream);
@@ -1612,12 +1270,11 @@ extern "C" int rdm_patch_scores(const float* ref_feats, int64_t ld_ref, int64_t 
               "rdm_patch_scores: features must be 16-byte aligned");
   if (batch == 0) return RDM_OK;
   GemmArgs g;
-  g.A = ref_feats; g.B = src_feats; g.C = scores; g.bias = nullptr; g.rowdiv = rowdiv;
+  g.A = ref_feats; g.B = src_feats; g.C = scores; g.rowdiv = rowdiv;
   g.M = static_cast<int>(side); g.N = static_cast<int>(side); g.K = static_cast<int>(d);
   g.lda = static_cast<int>(ld_ref); g.ldb = static_cast<int>(ld_src); g.ldc = static_cast<int>(side);
-  g.sa = g.sb = 0; g.sc = side * side;
-  g.act = 0; g.splits = 1; g.part = nullptr; g.stats = nullptr;
-  g.A2 = nullptr; g.aidx = ref_idx; g.lda2 = g.ldi = g.c1 = 0; g.n_coarse = static_cast<int>(n_ref);
+  g.sc = side * side;
+  g.aidx = ref_idx; g.n_coarse = static_cast<int>(n_ref);
   g.bidx = src_idx; g.n_b = static_cast<int>(n_src);
   return gemm_dispatch(g, static_cast<int>(batch), true, nullptr, 0, nullptr, static_cast<hipStream_t>(stream));
 }
@@ -1635,17 +1292,7 @@ extern "C" int rdm_decoder_stage(const float* coarse, int64_t n_coarse, int64_t 
                                  const float* bias, int64_t n, int groups, const float* gamma, const float* beta, float eps,
                                  int act, float* lin_out, int64_t ld_lin, float* y, int64_t ldy, void* ws, size_t ws_bytes,
                                  void* stream) {
-  return rdm_decoder_stage_form(coarse, n_coarse, c1, ld1, idx, ldi, skip, c2, ld2, m, w, ldw, bias, n, groups, gamma, beta, eps, act, lin_out, ld_lin,
-                                y, ldy, ws, ws_bytes, 0, stream);
-}
-
-extern "C" int rdm_decoder_stage_form(const float* coarse, int64_t n_coarse, int64_t c1, int64_t ld1, const int64_t* idx, int64_t ldi,
-                                      const float* skip, int64_t c2, int64_t ld2, int64_t m, const float* w, int64_t ldw,
-                                      const float* bias, int64_t n, int groups, const float* gamma, const float* beta, float eps,
-                                      int act, float* lin_out, int64_t ld_lin, float* y, int64_t ldy, void* ws, size_t ws_bytes,
-                                      int form, void* stream) {
   using namespace rdm;
-  RDM_REQUIRE(form >= 0 && form <= 2, "rdm_decoder_stage_form: unknown form %d", form);
   RDM_REQUIRE(coarse && idx && skip && w && lin_out && (!gamma || (beta && y)), "rdm_decoder_stage: null pointer");
   RDM_REQUIRE(c1 > 0 && c2 > 0 && n > 0 && m >= 0 && ldw % 4 == 0, "rdm_decoder_stage: bad sizes");
   if (m == 0) return RDM_OK;
@@ -1666,11 +1313,11 @@ extern "C" int rdm_decoder_stage_form(const float* coarse, int64_t n_coarse, int
   int rc = 1;
   if (!no_virtual && k == kpad)
     rc = gemm_concat_with_stats(coarse, ld1, c1, n_coarse, idx, ldi, skip, ld2, c2, w, ldw, lin_out, ld_lin, m, n, bias, 0, gws,
-                                gemm_ws, gamma ? partial : nullptr, &nblk, stream, form);
+                                gemm_ws, gamma ? partial : nullptr, &nblk, stream);
   if (rc == 1) {
     if (int e = rdm_upsample_concat(coarse, n_coarse, c1, ld1, idx, ldi, skip, c2, ld2, m, cat, kpad, stream)) return e;
     rc = gemm_with_stats(cat, kpad, w, ldw, lin_out, ld_lin, m, n, kpad, bias, nullptr, gws, gemm_ws, gamma ? partial : nullptr,
-                         &nblk, stream, form);
+                         &nblk, stream);
   }
   if (rc != 0 || !gamma) return rc;
   return group_norm_finish(partial, nblk, lin_out, m, n, ld_lin, groups, gamma, beta, eps, nullptr, 0, act, y, ldy, nullptr, nws,

@@ -124,6 +124,38 @@ __device__ __forceinline__ float2 gn_scale_shift(GnFinalizeLds<COLS>& L, int col
   }
   return out;
 }
+
+// The finalize for group widths that do not divide 64 (a group then straddles the column blocks of gn_finalize_kernel; no width of
+// the path -- its groups are 1 to 64 columns wide): one thread per column adds the partials of its group's columns itself, the row
+// blocks of a column in ascending order.
+__device__ __forceinline__ void gn_finalize_any_width_kernel_body(const dim3 blockIdx, const dim3 gridDim, const double* partial, int nblk,
+                                                                  int n, int c, int groups, const float* gamma, const float* beta,
+                                                                  float eps, float* scale, float* shift) {
+  (void)gridDim;
+  const int col = blockIdx.x * 256 + threadIdx.x;
+  if (col >= c) return;
+  const int cpg = c / groups, g0 = (col / cpg) * cpg;
+  double gs = 0.0, gss = 0.0;
+  for (int k = g0; k < min(g0 + cpg, c); ++k) {
+    double a = 0.0, b = 0.0;
+    for (int blk = 0; blk < nblk; ++blk) {
+      a += partial[(static_cast<int64_t>(blk) * 2 + 0) * c + k];
+      b += partial[(static_cast<int64_t>(blk) * 2 + 1) * c + k];
+    }
+    gs += a;
+    gss += b;
+  }
+  const double cnt = static_cast<double>(n) * cpg;  // (scale and shift as in gn_scale_shift)
+  const double mean = gs / cnt;
+  double var = gss / cnt - mean * mean;
+  if (var < 0.0) var = 0.0;
+  const double gsc = 1.0 / sqrt(var + static_cast<double>(eps)) * static_cast<double>(gamma[col]);
+  scale[col] = static_cast<float>(gsc);
+  shift[col] = static_cast<float>(static_cast<double>(beta[col]) - mean * gsc);
+}
+__global__ __launch_bounds__(256) void gn_finalize_any_width_kernel(const double* partial, int nblk, int n, int c, int groups,
+                                                                    const float* gamma, const float* beta, float eps, float* scale,
+                                                                    float* shift) { gn_finalize_any_width_kernel_body(blockIdx, gridDim, partial, nblk, n, c, groups, gamma, beta, eps, scale, shift); }
 template <int COLS>
 __device__ __forceinline__ void gn_finalize_kernel_body(const dim3 blockIdx, const dim3 gridDim, const double* partial, int nblk, int n,
                                                             int c, int groups, const float* gamma,
@@ -541,8 +573,9 @@ int rdm::group_norm_finish(const double* partial_in, int nblk, const float* x, i
                       (!residual || (reinterpret_cast<uintptr_t>(residual) & 15) == 0);
   static const bool fin64 = ::rdm::dev_knob("RDM_GN_FINALIZE_64") != nullptr;  // developer knob (A/B): always 64 columns per workgroup
   const bool narrow = !fin64 && nblk >= 128 && c / groups <= 16 && 16 % (c / groups) == 0;
+  const bool whole_groups = 64 % (c / groups) == 0;  // (every group inside one 64-column block: what gn_scale_shift needs)
   // coarse levels: finalize + apply as one launch (see gn_finalize_apply_kernel); form 1 = always the separate launches
-  if (form != 1 && !narrow && !positive && vec_ok && c % 64 == 0 && n <= 4096) {
+  if (form != 1 && !narrow && !positive && vec_ok && c % 64 == 0 && n <= 4096 && whole_groups) {
     RDM_DUP_LOOP("gnfin")
     ::rdm::launch<gn_finalize_apply_kernel_body, gn_finalize_apply_kernel, 1024>(dim3(static_cast<unsigned>(c / 64), static_cast<unsigned>(ceil_div<int64_t>(n, kGnFusedRows))), 0, st, use, nblk, x, static_cast<int>(n), static_cast<int>(c), static_cast<int>(ldx), groups, gamma, beta,
                        eps, residual, static_cast<int>(ldr), act, y, static_cast<int>(ldy));
@@ -550,7 +583,10 @@ int rdm::group_norm_finish(const double* partial_in, int nblk, const float* x, i
   }
   {
     RDM_DUP_LOOP("gnfin")
-    if (narrow)
+    if (!whole_groups)
+      ::rdm::launch<gn_finalize_any_width_kernel_body, gn_finalize_any_width_kernel, 256>(dim3(ceil_div<int64_t>(c, 256)), 0, st, use, nblk,
+                         static_cast<int>(n), static_cast<int>(c), groups, gamma, beta, eps, ss, ss + c);
+    else if (narrow)
       ::rdm::launch<gn_finalize_kernel_body<16>, gn_finalize_kernel<16>, 1024>(dim3(ceil_div<int64_t>(c, 16)), 0, st, use, nblk,
                          static_cast<int>(n), static_cast<int>(c), groups, gamma, beta, eps, ss, ss + c);
     else

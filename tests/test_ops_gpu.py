@@ -14,6 +14,12 @@ def ops():
     return ops
 
 
+# Products of the path's coarse levels and edge shapes: split-K with K = 7680 / 3840 / 1920, ragged M, N and K, N = 1028 and N
+# that is no multiple of 32 (m, k, n; weights as B)
+RAGGED_AND_SPLIT_K = [(563, 7680, 512), (1310, 3840, 256), (3879, 1920, 128), (10961, 64, 256), (3879, 128, 512), (300, 36, 132),
+                      (257, 1284, 260), (129, 68, 1028), (32000, 32, 128)]
+
+
 def padded(t, device='cuda'):
     """[n, c] tensor -> device view with row stride padded to a multiple of 4 (pads zeroed)."""
     n, c = t.shape
@@ -40,7 +46,8 @@ def kpconv_fp64(q_pts, s_pts, feats, idx, kp, sigma, W, bias):
 @pytest.mark.parametrize('m,k,n,trans_b', [(1, 4, 1, False), (77, 36, 33, False), (300, 128, 257, False),
                                             (2236, 1284, 1024, False), (842, 7680, 512, False),
                                             (39609, 480, 32, False), (5000, 64, 128, False),
-                                            (332, 256, 316, True), (129, 2048, 128, False)])
+                                            (332, 256, 316, True), (129, 2048, 128, False)] +
+                         [(m, k, n, False) for m, k, n in RAGGED_AND_SPLIT_K])
 def test_gemm_matches_fp64(ops, m, k, n, trans_b):
     g = torch.Generator().manual_seed(m * 7 + n)
     a = torch.randn(m, k, generator=g)
@@ -272,7 +279,8 @@ def test_pooling_ops_are_exact(ops):
 
 @pytest.mark.parametrize('ns,m,c1,c2,n,norm', [(300, 1000, 64, 36, 128, True), (563, 1310, 257, 1024, 1024, True),
                                               (50, 1000, 32, 12, 64, True), (40, 300, 32, 4, 64, False),  # c1 + c2 < 48
-                                              (1310, 3879, 1024, 512, 512, True), (900, 2500, 512, 256, 257, False)])
+                                              (1310, 3879, 1024, 512, 512, True), (900, 2500, 512, 256, 257, False),
+                                              (100, 333, 64, 36, 132, True)])  # ragged N: 4 groups of 33 channels
 def test_decoder_stage_matches_torch(ops, ns, m, c1, c2, n, norm):
     """Decoder stage (backbone.py:118-151: nearest_upsample + cat + UnaryBlock / Linear) against torch fp64, 2e-5 of the output
     range; c1 % 32 == 0 takes the GEMM whose A tiles read the two sources directly, other widths the materialised rows --
@@ -283,30 +291,32 @@ def test_decoder_stage_matches_torch(ops, ns, m, c1, c2, n, norm):
     k = c1 + c2
     w, bias = torch.randn(k, n, generator=g) / k ** 0.5, torch.randn(n, generator=g)
     gamma, beta = torch.rand(n, generator=g) + 0.5, torch.randn(n, generator=g)
+    groups = 32 if n % 32 == 0 else 4
     a = torch.cat([torch.cat([coarse, torch.zeros(1, c1)])[idx[:, 0]], skip], 1).double()
     lin = a @ w.double() + bias.double()
-    want = F.leaky_relu(F.group_norm(lin.t()[None], 32, gamma.double(), beta.double(), 1e-5)[0].t(), 0.1) if norm else lin
+    want = F.leaky_relu(F.group_norm(lin.t()[None], groups, gamma.double(), beta.double(), 1e-5)[0].t(), 0.1) if norm else lin
     kp = (k + 3) // 4 * 4
     wp = torch.zeros(kp, n)
     wp[:k] = w
     args = (padded(coarse), idx.cuda(), padded(skip), padded(wp), n, bias.cuda())
-    got = ops.decoder_stage(*args, gamma.cuda(), beta.cuda(), 32, act=ops.ACT_LEAKY) if norm else ops.decoder_stage(*args)
+    got = ops.decoder_stage(*args, gamma.cuda(), beta.cuda(), groups, act=ops.ACT_LEAKY) if norm else ops.decoder_stage(*args)
     assert (got.cpu().double() - want).abs().max() <= 2e-5 * want.abs().max()
     cat = ops.upsample_concat(padded(coarse), idx.cuda(), padded(skip))
-    sep = (ops.linear_group_norm(cat, padded(wp), kp, n, bias.cuda(), gamma.cuda(), beta.cuda(), 32, act=ops.ACT_LEAKY) if norm
+    sep = (ops.linear_group_norm(cat, padded(wp), kp, n, bias.cuda(), gamma.cuda(), beta.cuda(), groups, act=ops.ACT_LEAKY) if norm
            else ops.gemm(cat, padded(wp), kp, n, bias=bias.cuda()))
     assert (got - sep).abs().max() <= 2e-5 * want.abs().max()
 
 
-@pytest.mark.parametrize('m,k,n', [(5000, 64, 32), (13795, 128, 256), (700, 1024, 512), (77, 36, 64)])
+@pytest.mark.parametrize('m,k,n', [(5000, 64, 32), (13795, 128, 256), (700, 1024, 512), (77, 36, 64)] + RAGGED_AND_SPLIT_K)
 def test_linear_group_norm_fused_matches_torch(ops, m, k, n):
     g = torch.Generator().manual_seed(m + n)
     x, w, bias = torch.randn(m, k, generator=g), torch.randn(k, n, generator=g) / k ** 0.5, torch.randn(n, generator=g)
     gamma, beta, res = torch.rand(n, generator=g) + 0.5, torch.randn(n, generator=g), torch.randn(m, n, generator=g)
     rowdiv = torch.randint(1, 5, (m,), generator=g).float()
+    groups = 32 if n % 32 == 0 else 4
     lin = (x.double() @ w.double()) / rowdiv.double()[:, None] + bias.double()
-    ref = F.leaky_relu(F.group_norm(lin.t()[None], 32, gamma.double(), beta.double(), 1e-5)[0].t() + res.double(), 0.1)
-    y = ops.linear_group_norm(padded(x), padded(w), k, n, bias.cuda(), gamma.cuda(), beta.cuda(), 32, rowdiv=rowdiv.cuda(),
+    ref = F.leaky_relu(F.group_norm(lin.t()[None], groups, gamma.double(), beta.double(), 1e-5)[0].t() + res.double(), 0.1)
+    y = ops.linear_group_norm(padded(x), padded(w), k, n, bias.cuda(), gamma.cuda(), beta.cuda(), groups, rowdiv=rowdiv.cuda(),
                               act=ops.ACT_LEAKY, residual=padded(res))
     assert (y.cpu().double() - ref).abs().max().item() <= 5e-5
 
@@ -512,43 +522,3 @@ def test_kpconv_gather_lds_tile_form_has_the_bits_of_the_per_neighbour_form(ops,
         a, na = ops.kpconv_gather(*args, width=cap, order=rec, form=2)
         b, nb = ops.kpconv_gather(*args, width=cap, form=1)
         assert torch.equal(a[:, :15 * c], b[:, :15 * c]) and torch.equal(na[:m], nb[:m])
-
-
-@pytest.mark.parametrize('m,k,n', [(563, 7680, 512), (1310, 3840, 256), (3879, 1920, 128), (10961, 64, 256), (3879, 128, 512), (300, 36, 132),
-                                   (257, 1284, 260), (129, 68, 1028), (32000, 32, 128)])
-def test_gemm_forms_return_the_same_bits(ops, m, k, n):
-    """Round 6: the WIDE forms of the tiled GEMM (rdm_gemm_form 1 / 2: 128 x 128 x 32 tiles with fragment-ordered LDS images, on
-    v_mfma_f32_32x32x2_f32 or v_mfma_f32_16x16x4_f32) return the bits of the library's choice (form 0: the 64 x 64 tile) -- an
-    output element is one fp32 fma chain over ascending k inside the same split-K ranges whatever the tile and the MFMA shape,
-    and the GroupNorm column partials keep their 64-row blocks and their combination order.  Products with and without split-K,
-    with bias / activation / row divisor / statistics, ragged edges in M, N and K."""
-    g = torch.Generator().manual_seed(m + k + n)
-    kp, n_p = (k + 3) // 4 * 4, (n + 3) // 4 * 4
-    a = torch.zeros(m, kp)
-    a[:, :k] = torch.randn(m, k, generator=g)
-    w = torch.zeros(kp, n_p)
-    w[:k, :n] = torch.randn(k, n, generator=g) / k ** 0.5
-    bias, gamma, beta = torch.randn(n, generator=g), torch.rand(n, generator=g) + 0.5, torch.randn(n, generator=g)
-    rowdiv = torch.randint(1, 40, (m,), generator=g).float()
-    a, w, bias, gamma, beta, rowdiv = (t.cuda() for t in (a, w, bias, gamma, beta, rowdiv))
-    groups = 32 if n % 32 == 0 else 4
-    want_plain = ops.gemm(a, w, kp, n, bias=bias, act=ops.ACT_LEAKY)
-    want_gn = ops.linear_group_norm(a, w, kp, n, bias, gamma, beta, groups, rowdiv=rowdiv, act=ops.ACT_LEAKY)
-    for form in (1, 2):
-        assert torch.equal(ops.gemm(a, w, kp, n, bias=bias, act=ops.ACT_LEAKY, form=form), want_plain), form
-        assert torch.equal(ops.linear_group_norm(a, w, kp, n, bias, gamma, beta, groups, rowdiv=rowdiv, act=ops.ACT_LEAKY, form=form), want_gn), form
-
-
-@pytest.mark.parametrize('ns,m,c1,c2,n,norm', [(1310, 3879, 1024, 512, 512, True), (900, 2500, 512, 256, 257, False), (100, 333, 64, 36, 132, True)])
-def test_decoder_stage_forms_return_the_same_bits(ops, ns, m, c1, c2, n, norm):
-    """The decoder's virtual [upsample | skip] operand on the wide forms (rdm_decoder_stage_form 1 / 2): the bits of form 0."""
-    g = torch.Generator().manual_seed(m + c1)
-    coarse, skip = torch.randn(ns, c1, generator=g).cuda(), torch.randn(m, c2, generator=g).cuda()
-    idx = torch.randint(0, ns + 3, (m, 4), generator=g).cuda()  # (rows past the coarse level: zero rows)
-    w = torch.zeros(c1 + c2, (n + 3) // 4 * 4)
-    w[:, :n] = torch.randn(c1 + c2, n, generator=g) / (c1 + c2) ** 0.5
-    w, bias, gamma, beta = w.cuda(), torch.randn(n, generator=g).cuda(), (torch.rand(n, generator=g) + 0.5).cuda(), torch.randn(n, generator=g).cuda()
-    groups = 32 if n % 32 == 0 else 4
-    run = lambda form: ops.decoder_stage(coarse, idx, skip, w, n, bias, gamma if norm else None, beta if norm else None, groups, act=ops.ACT_LEAKY, form=form)
-    want = run(0)
-    assert torch.equal(run(1), want) and torch.equal(run(2), want)

@@ -18,7 +18,7 @@ def group_launches(db, which=20):
     s, e = starts[which], starts[which + 1]
     out = []
     for i in range(s, e):
-        if re.search(r'gemm_(kernel|wide|small)|splitk', names[i]):
+        if re.search(r'gemm_(kernel|small)|splitk', names[i]):
             out.append((i - s, names[i], rows[i][3] // max(rows[i][4], 1), (rows[i][2] - rows[i][1]) / 1e3))
     return out, sum((rows[i][2] - rows[i][1]) / 1e3 for i in range(s, e)), (rows[e - 1][2] - rows[s][1]) / 1e3
 
