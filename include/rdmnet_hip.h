@@ -182,6 +182,31 @@ int rdm_ball_count(const float* ref, int64_t n_ref, int64_t ld_ref, const float*
 int rdm_ball_fill(const float* ref, int64_t n_ref, int64_t ld_ref, int64_t n_src, int64_t* out, int64_t capacity, void* ws,
                   size_t ws_bytes, void* stream);
 
+/* ---- exact cloud-to-cloud nearest neighbours: chamfer, fitness, re-alignment error (nearest.hip) ---------
+ * get_nearest_neighbor (geotransformer/utils/pointcloud.py:11-22, a cKDTree k = 1 query) and what registration.py builds on
+ * it (compute_overlap :191-197, compute_modified_chamfer_distance :155-172).  q [n_q, >=3] / s [n_s, >=3]: device f32, row
+ * strides ld_q / ld_s (xyz first); q_transform_host / s_transform_host: optional row-major float64 4x4 on the HOST, applied to
+ * the respective cloud (null: the cloud as it is).  Points are read as double, x' = ((R00 x + R01 y) + R02 z) + t0,
+ * d2 = ((dx dx) + (dy dy)) + (dz dz) with d = q' - s', nothing contracted.  Per query row: d2 f64 [n_q] (device, optional) =
+ * the smallest d2 over ALL support rows, idx i32 [n_q] (device, optional) = the LOWEST support row that attains it (cKDTree
+ * leaves equal distances open; this library defines the tie); the distance is sqrt(d2) in double.  n_s = 0: d2 = +inf and
+ * idx = n_s, as cKDTree returns; n_q = 0 is valid and empty.  cell: the edge of the index's cells (<= 0: chosen on the device,
+ * about 8 support points per cell); the result does not depend on it, nor on the path a row takes -- rows the cell search
+ * cannot settle are swept against every support row with the same expression -- and two calls give the same bits (float64
+ * sums in a fixed order, no float atomics).  totals_host (host double[5], the call's one read-back, after which the stream is
+ * idle) = {sum of sqrt(d2), rows with sqrt(d2) < radius (strict, as compute_overlap; none with radius <= 0), the sum of d2
+ * over those rows, rows that took the sweep, status}.  A point that is not finite, before or after moving, or a support point
+ * beyond 2^30 cells of `cell` from the origin, is RDM_ERR_ARG (status 2), not a fault: nothing is indexed by such a point and
+ * idx / d2 are left untouched.  n_q, n_s < 2^31 - 64.
+ * rdm_realign_error: compute_registration_rmse (registration.py:136-152), *mean_host = the mean over the rows of pts [n, >=3]
+ * of |gt p - est p| with the arithmetic above (NaN for n = 0); workspace rdm_nearest_workspace_bytes(0, 0).             */
+size_t rdm_nearest_workspace_bytes(int64_t n_q, int64_t n_s);
+int rdm_nearest(const float* q, int64_t n_q, int64_t ld_q, const float* s, int64_t n_s, int64_t ld_s,
+                const double* q_transform_host, const double* s_transform_host, double cell, double radius, int32_t* idx,
+                double* d2, double* totals_host, void* ws, size_t ws_bytes, void* stream);
+int rdm_realign_error(const float* pts, int64_t n, int64_t ld, const double* gt_host, const double* est_host, double* mean_host,
+                      void* ws, size_t ws_bytes, void* stream);
+
 /* ---- dense contraction ---------------------------------------------------------------------
  * C[b] = act((A[b] (m x k) * op(B[b])) / rowdiv[row] + bias[col]) in fp32 on the f32 MFMA.
  * trans_b = 0: B is [k, n] row-major (pre-transposed nn.Linear weights, KPConv weights viewed
@@ -799,6 +824,16 @@ int rdm_engine_feature_correspondences(rdm_engine* e, int level, int mode, int64
 int rdm_engine_gt_point_correspondences_count(rdm_engine* e, int level, const double* transform_host, double radius,
                                               int64_t* totals_host, void* stream);
 int rdm_engine_gt_point_correspondences_fill(rdm_engine* e, int64_t* out, int64_t capacity, void* stream);
+/* How well a pose aligns the LAST run's resident clouds, without ground truth (two rdm_nearest calls, no upload, no export):
+ * levels as above; transform_host float64 4x4 on the host, src -> ref (null: the run's own estimated_transform).  Both sides
+ * are measured in the ref frame: ref rows against the moved src cloud, moved src rows against the ref cloud.  out_host (host
+ * double[8]) = {ref rows with a neighbour nearer than radius, their sum of d2, the sum of all ref rows' nearest distances, the
+ * same three for the src rows, n_ref, n_src}.  Per engine after its run, also for the engines of a lock-step group; the
+ * workspace lies in the arena above the last run and is released before the call returns (a pending count call's too);
+ * synchronises `stream`.  A forward that is not followed by this call launches nothing for it.  radius <= 0 and an engine
+ * without a completed forward run are RDM_ERR_ARG.                                                                      */
+int rdm_engine_alignment_quality(rdm_engine* e, int level, const double* transform_host, double radius, double* out_host,
+                                 void* stream);
 /* Plain device-to-device copy on `stream` (lets a host without a HIP binding read arena tensors). */
 int rdm_copy_device(void* dst, const void* src, size_t bytes, void* stream);
 

@@ -170,6 +170,8 @@ struct rdm_engine {
       char* ws = nullptr;
       size_t ws_bytes = 0, off_before = 0;
     } ball;
+    // rdm_engine_alignment_quality: the run's own estimated_transform, as the result struct holds it
+    float est[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   } gt;
 
   template <typename T>
@@ -1924,6 +1926,7 @@ int fine_matching(Run& r, const PairPyramid& py, const Superpoints& sp, const Co
   std::memcpy(tailbuf.T, e->pinned, 64);
   std::memcpy(tailbuf.counts, static_cast<char*>(e->pinned) + 64, 12);
   std::memcpy(res->transform, tailbuf.T, 64);
+  std::memcpy(e->gt.est, tailbuf.T, 64);
   res->n_correspondences = tailbuf.counts[0];
   res->n_hypotheses = tailbuf.counts[1];
   res->best_hypothesis = tailbuf.counts[2];
@@ -2463,6 +2466,55 @@ extern "C" int rdm_engine_gt_point_correspondences_fill(rdm_engine* e, int64_t* 
     set_error("rdm_engine_gt_point_correspondences_fill: hipStreamSynchronize failed: %s", hipGetErrorString(err));
     return RDM_ERR_HIP;
   }
+  return RDM_OK;
+}
+
+extern "C" int rdm_engine_alignment_quality(rdm_engine* e, int level, const double* transform_host, double radius, double* out_host,
+                                            void* stream) {
+  RDM_REQUIRE(e && out_host, "rdm_engine_alignment_quality: null pointer");
+  RDM_REQUIRE(level >= 0 && level <= 2, "rdm_engine_alignment_quality: level %d (0 input, 1 fine, 2 coarse)", level);
+  RDM_REQUIRE(radius > 0.0 && std::isfinite(radius), "rdm_engine_alignment_quality: radius must be > 0 and finite (got %g)", radius);
+  RDM_REQUIRE(e->gt.valid, "rdm_engine_alignment_quality: the engine holds no completed forward run (its points); "
+                           "run rdm_engine_run / rdm_engine_forward first");
+  rdm_engine::GtInputs& g = e->gt;
+  if (g.ball.pending) {  // a count call that was never filled: its workspace goes first
+    e->arena_off = g.ball.off_before;
+    g.ball.pending = false;
+  }
+  const float* ref = level == 0 ? g.p0[0] : (level == 1 ? g.pf[0] : g.nodes[0]);
+  const float* src = level == 0 ? g.p0[1] : (level == 1 ? g.pf[1] : g.nodes[1]);
+  const int64_t n = level == 0 ? g.n0[0] : (level == 1 ? g.nf[0] : g.m[0]);
+  const int64_t m = level == 0 ? g.n0[1] : (level == 1 ? g.nf[1] : g.m[1]);
+  double own[16];
+  if (transform_host == nullptr) {  // the run's own pose
+    for (int k = 0; k < 16; ++k) own[k] = static_cast<double>(g.est[k]);
+    transform_host = own;
+  }
+  // scratch above the last run's tensors, released again below (both calls synchronise before they return)
+  const size_t off_before = e->arena_off;
+  const size_t a = rdm_nearest_workspace_bytes(n, m), b = rdm_nearest_workspace_bytes(m, n);
+  const size_t ws_bytes = a > b ? a : b;
+  char* ws = e->alloc<char>(ws_bytes);
+  if (ws == nullptr) {
+    e->arena_off = off_before;
+    set_error("rdm_engine_alignment_quality: %zu B of scratch do not fit above the last run in the arena (%zu B)", ws_bytes,
+              e->arena_cap);
+    return RDM_ERR_WORKSPACE;
+  }
+  // both sides in the ref frame: ref rows against the moved src cloud, moved src rows against the ref cloud
+  double side[2][5];
+  int rc = rdm_nearest(ref, n, 3, src, m, 3, nullptr, transform_host, 0.0, radius, nullptr, nullptr, side[0], ws, ws_bytes, stream);
+  if (rc == RDM_OK)
+    rc = rdm_nearest(src, m, 3, ref, n, 3, transform_host, nullptr, 0.0, radius, nullptr, nullptr, side[1], ws, ws_bytes, stream);
+  e->arena_off = off_before;
+  if (rc != RDM_OK) return rc;
+  for (int k = 0; k < 2; ++k) {
+    out_host[3 * k] = side[k][1];      // rows with a neighbour nearer than radius
+    out_host[3 * k + 1] = side[k][2];  // their sum of d2
+    out_host[3 * k + 2] = side[k][0];  // the sum of all nearest distances
+  }
+  out_host[6] = static_cast<double>(n);
+  out_host[7] = static_cast<double>(m);
   return RDM_OK;
 }
 

@@ -536,6 +536,25 @@ class Engine:
                    'rdm_engine_gt_point_correspondences_fill')
         return out
 
+    def alignment_quality(self, transform=None, radius=None, level='input'):
+        """ops.alignment_quality on the last run's resident points (rdm_engine_alignment_quality), no upload: levels as
+        gt_point_correspondences; transform 4x4 src -> ref (None: the run's own estimated_transform); radius None =
+        cfg.fine_matching.acceptance_radius -> dict(fitness_ref, fitness_src, inlier_rmse_ref, inlier_rmse_src, chamfer, n_ref,
+        n_src).  keep_taps is not needed; an engine without a completed forward run raises.  Synchronises the current stream."""
+        if level not in POINT_LEVELS:
+            raise ValueError(f'alignment_quality: level {level!r}, expected one of {sorted(POINT_LEVELS)}')
+        if radius is None:
+            radius = float(self.cfg.fine_matching.acceptance_radius)
+        if not radius > 0:
+            raise ValueError(f'alignment_quality: radius must be > 0, got {radius}')
+        from .ops import _transform_arg, quality_dict
+        T = _transform_arg(transform, 'alignment_quality')
+        out = (ctypes.c_double * 8)()
+        _lib.check(self.L.rdm_engine_alignment_quality(self._h, POINT_LEVELS[level], 0 if T is None else T.ctypes.data, float(radius),
+                                                       out, _lib.stream_ptr()),
+                   'rdm_engine_alignment_quality')
+        return quality_dict([float(x) for x in out])
+
     def corr(self):
         """(ref_corr_points, src_corr_points, corr_scores) of the last run as fresh tensors."""
         n = self.result.n_correspondences

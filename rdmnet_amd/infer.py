@@ -6,6 +6,7 @@ registration report, on the native engine.
     python -m rdmnet_amd.infer --synthetic 512 --no-npz                              # throughput on synthetic KITTI-shaped pairs
     python -m rdmnet_amd.infer --dataset-root /data/kitti --gt-nodes --out out/      # test.py's evaluation run (eval.py reads out/)
     python -m rdmnet_amd.infer --infer-root /path/to/assets/pc --out out/ --feature-match mutual   # + descriptor correspondences
+    python -m rdmnet_amd.infer --infer-root /path/to/assets/pc --out out/ --quality                # + fitness, inlier RMSE, chamfer
     python -m torch.distributed.run --nproc-per-node 8 -m rdmnet_amd.infer ...       # pairs sharded over ranks
 
 Per pair it writes what the reference writes: one line in `<seq>_pose` and one `<seq>_<src>_<ref>.npz`
@@ -19,6 +20,9 @@ the engine's resident tensors, the Coarse Matching meters become real, and the .
 geotransformer/utils/registration.py:258-277, on the fine level: Engine.feature_correspondences) to every pair file --
 evaluation.FEATURE_MATCH_KEYS, what `python -m rdmnet_amd.eval --method ransac_featurematch` reads -- and, with ground truth, the
 descriptor inlier ratio to the pair's log line.
+`--quality` judges every pair's pose without ground truth (Engine.alignment_quality on the resident input clouds, radius
+cfg.fine_matching.acceptance_radius): fitness and inlier RMSE of both sides and the chamfer distance go to the pair's log line and,
+as quality_* keys (ops.QUALITY_KEYS), into its .npz; every other key stays as it is.
 """
 import argparse
 import os
@@ -46,7 +50,8 @@ class Tester:
     records, pose lines and the report come out in dataset order whatever the completion order."""
 
     def __init__(self, cfg, state, output_dir=None, save_npz=True, ransac=True, write_poses=True,
-                 pairs_in_flight=DEFAULT_PAIRS_IN_FLIGHT, wait_us=None, lockstep=None, gt_nodes=False, feature_match=None):
+                 pairs_in_flight=DEFAULT_PAIRS_IN_FLIGHT, wait_us=None, lockstep=None, gt_nodes=False, feature_match=None,
+                 quality=False):
         self.cfg, self.output_dir, self.save_npz, self.ransac = cfg, output_dir, save_npz, ransac
         self.write_poses = write_poses  # False under several ranks: rank 0 writes all poses, in pair order, at the end
         # gt_nodes: test.py's run -- ground-truth superpoint correspondences per pair with a transform (model.py:283-297, radius
@@ -56,6 +61,7 @@ class Tester:
         if feature_match is not None and feature_match not in ops.FEATURE_MATCH_MODES:
             raise ValueError(f'feature_match {feature_match!r}, expected one of {sorted(ops.FEATURE_MATCH_MODES)}')
         self.feature_match = feature_match
+        self.quality = bool(quality)  # Engine.alignment_quality of every pair's own pose, on the input clouds
         ev = dict(cfg.get('eval', {})) if hasattr(cfg, 'get') else {}
         self.fm_radius = float(ev.get('acceptance_radius', 0.6))
         radius = getattr(getattr(cfg, 'model', None), 'ground_truth_matching_radius', None)
@@ -106,6 +112,10 @@ class Tester:
                 rec['feat_IR'] = float(evaluation.evaluate_correspondences(
                     extra['feat_ref_corr_points'], extra['feat_src_corr_points'], np.asarray(item['transform'], np.float64),
                     positive_radius=self.fm_radius)['inlier_ratio'])
+        if self.quality:  # fitness / inlier RMSE / chamfer of the pair's own pose on the engine's resident input clouds, this stream
+            rec['quality'] = eng.alignment_quality()
+            extra = dict(extra or {})
+            extra.update({f'quality_{k}': np.float64(rec['quality'][k]) for k in ops.QUALITY_KEYS})
         if self.gt_nodes and 'transform' in item:  # test.py: model.py:283-297 on the engine's resident tensors, this stream
             gt_idx, gt_ovl, _ = eng.gt_node_correspondences(np.asarray(item['transform'], np.float32), self.gt_radius)
             m_r = int(res.n_ref_nodes)
@@ -159,6 +169,8 @@ class Tester:
                     line += ', nFeatCorr: {}'.format(rec['n_feat_corr'])
                     if 'feat_IR' in rec:
                         line += ', feat_IR: {:.3f}'.format(rec['feat_IR'])
+                if 'quality' in rec:  # (--quality)
+                    line += ''.join(', {}: {:.4f}'.format(k, rec['quality'][k]) for k in ops.QUALITY_KEYS)
                 log(line)
         return self.records
 
@@ -192,6 +204,9 @@ def main(argv=None):
     ap.add_argument('--feature-match', choices=sorted(ops.FEATURE_MATCH_MODES), default=None,
                     help='also match the fine-level descriptors by nearest neighbour in feature space (registration.py:222-277) and add '
                          'feat_ref/src_corr_indices, feat_ref/src_corr_points and feat_corr_dists to every pair file')
+    ap.add_argument('--quality', action='store_true',
+                    help="judge every pair's pose without ground truth: fitness and inlier RMSE of both clouds and the chamfer distance "
+                         'at cfg.fine_matching.acceptance_radius, in the log line and as quality_* keys of the pair file')
     args = ap.parse_args(argv)
 
     rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
@@ -232,7 +247,7 @@ def main(argv=None):
         print(f'Calibrate neighbors: {cfg.neighbor_limits}.')
     tester = Tester(cfg, load_state(args.weights, cfg), args.out, save_npz=not args.no_npz, ransac=not args.no_ransac,
                     write_poses=world == 1, pairs_in_flight=args.pairs_in_flight, lockstep=args.lockstep, gt_nodes=args.gt_nodes,
-                    feature_match=args.feature_match)
+                    feature_match=args.feature_match, quality=args.quality)
     mine = sharding.pairs_for_rank(len(data), rank, world)
     # scans are read and staged (pinned host -> HBM on a side stream) two pairs ahead of every in-flight pair
     stager = ds_mod.PairStager(data, mine, depth=2 * args.pairs_in_flight, workers=max(2, args.pairs_in_flight))

@@ -758,6 +758,102 @@ def overlap_labels(ref_points, src_points, transform, radius):
     return ref_hit[:ref_points.shape[0]].bool(), src_hit[:src_points.shape[0]].bool()
 
 
+def _nearest(q_points, s_points, q_transform=None, s_transform=None, cell=None, radius=0.0, want_rows=True):
+    """rdm_nearest -> (idx int32 [n_q], d2 float64 [n_q] (None without want_rows), totals (sum of distances, rows nearer than
+    radius, their sum of d2, rows that took the exact sweep))."""
+    L = _lib.lib()
+    ldq, lds = _points_arg(q_points, 'q_points'), _points_arg(s_points, 's_points')
+    if q_points.device != s_points.device:
+        raise ValueError('q_points and s_points must be on the same device')
+    Tq, Ts = _transform_arg(q_transform, 'q_transform'), _transform_arg(s_transform, 's_transform')
+    dev = q_points.device
+    n, m = q_points.shape[0], s_points.shape[0]
+    idx = torch.empty((max(n, 1),), dtype=torch.int32, device=dev) if want_rows else None
+    d2 = torch.empty((max(n, 1),), dtype=torch.float64, device=dev) if want_rows else None
+    ws = scratch(dev, L.rdm_nearest_workspace_bytes(n, m))
+    totals = (ctypes.c_double * 5)()
+    _lib.check(L.rdm_nearest(_lib.ptr(q_points), n, ldq, _lib.ptr(s_points), m, lds, 0 if Tq is None else Tq.ctypes.data,
+                             0 if Ts is None else Ts.ctypes.data, 0.0 if cell is None else float(cell), float(radius),
+                             _lib.ptr(idx), _lib.ptr(d2), totals, ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+               'rdm_nearest')
+    if want_rows:
+        idx, d2 = idx[:n], d2[:n]
+    return idx, d2, (float(totals[0]), int(totals[1]), float(totals[2]), int(totals[3]))
+
+
+def get_nearest_neighbor(q_points, s_points, return_index=False, *, q_transform=None, s_transform=None, cell=None):
+    """get_nearest_neighbor (geotransformer/utils/pointcloud.py:11-22, a cKDTree k = 1 query) on the GPU (rdm_nearest): q_points /
+    s_points float32 CUDA [N, >=3] (xyz first, any row stride), read as float64; q_transform / s_transform: optional 4x4 applied
+    to the respective cloud -> float64 CUDA [n_q], the distance of every query row to its nearest support row, at any distance
+    (with return_index also int64 [n_q], the LOWEST support row at that distance; n_s = 0: inf and n_s).  cell: the edge of the
+    index's cells (None: chosen on the device); the result does not depend on it."""
+    idx, d2, _ = _nearest(q_points, s_points, q_transform, s_transform, cell)
+    dist = torch.sqrt(d2)
+    return (dist, idx.long()) if return_index else dist
+
+
+def _mean(total, n):
+    return total / n if n > 0 else float('nan')  # (numpy's mean of nothing)
+
+
+def compute_modified_chamfer_distance(raw_points, ref_points, src_points, gt_transform, est_transform):
+    """compute_modified_chamfer_distance (geotransformer/utils/registration.py:155-172, RPMNet's measure) on the GPU: the mean
+    nearest distance of est . src to raw, plus that of ref to (est . gt^-1) . raw -> float.  The composed transform is formed in
+    float64 on the host, as the reference forms it."""
+    import numpy as np
+    gt, est = _transform_arg(gt_transform, 'gt_transform'), _transform_arg(est_transform, 'est_transform')
+    composed = np.matmul(est, np.linalg.inv(gt))
+    _, _, p_q = _nearest(src_points, raw_points, q_transform=est, want_rows=False)
+    _, _, q_p = _nearest(ref_points, raw_points, s_transform=composed, want_rows=False)
+    return _mean(p_q[0], src_points.shape[0]) + _mean(q_p[0], ref_points.shape[0])
+
+
+def compute_registration_rmse(src_points, gt_transform, est_transform):
+    """compute_registration_rmse (geotransformer/utils/registration.py:136-152; the re-alignment error of Rotated 3DMatch) on the
+    GPU (rdm_realign_error): the mean over src_points of |gt p - est p| in float64 -> float."""
+    L = _lib.lib()
+    ld = _points_arg(src_points, 'src_points')
+    gt, est = _transform_arg(gt_transform, 'gt_transform'), _transform_arg(est_transform, 'est_transform')
+    if gt is None or est is None:
+        raise ValueError('compute_registration_rmse: gt_transform and est_transform must be 4x4')
+    ws = scratch(src_points.device, L.rdm_nearest_workspace_bytes(0, 0))
+    mean = ctypes.c_double()
+    _lib.check(L.rdm_realign_error(_lib.ptr(src_points), src_points.shape[0], ld, gt.ctypes.data, est.ctypes.data,
+                                   ctypes.byref(mean), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), 'rdm_realign_error')
+    return float(mean.value)
+
+
+def quality_dict(v):
+    """The eight numbers of rdm_engine_alignment_quality ({rows nearer than radius, their sum of d2, the sum of all nearest
+    distances} of the ref side and of the src side, n_ref, n_src) -> alignment_quality's dict."""
+    import math
+    n_ref, n_src = int(v[6]), int(v[7])
+    out = {}
+    for k, (side, n) in enumerate((('ref', n_ref), ('src', n_src))):
+        within, sum_d2 = v[3 * k], v[3 * k + 1]
+        out[f'fitness_{side}'] = within / n if n > 0 else 0.0
+        out[f'inlier_rmse_{side}'] = math.sqrt(sum_d2 / within) if within > 0 else 0.0
+    out['chamfer'] = _mean(v[2], n_ref) + _mean(v[5], n_src)
+    out['n_ref'], out['n_src'] = n_ref, n_src
+    return out
+
+
+QUALITY_KEYS = ('fitness_ref', 'fitness_src', 'inlier_rmse_ref', 'inlier_rmse_src', 'chamfer')
+
+
+def alignment_quality(ref_points, src_points, transform, radius):
+    """How well `transform` (4x4, src -> ref; None: identity) aligns two clouds, without ground truth: what Open3D's
+    evaluate_registration reports, for both sides, plus the chamfer distance.  Both sides are measured in the ref frame (two
+    rdm_nearest calls) -> dict(fitness_ref / fitness_src: the share of rows with a neighbour nearer than radius (strict) in the
+    other cloud; inlier_rmse_ref / inlier_rmse_src: sqrt of the mean d2 over those rows, 0 without any; chamfer: the sum of the
+    two mean nearest distances; n_ref, n_src)."""
+    if radius is None or not radius > 0:
+        raise ValueError(f'alignment_quality: radius must be > 0, got {radius}')
+    _, _, a = _nearest(ref_points, src_points, s_transform=transform, radius=radius, want_rows=False)
+    _, _, b = _nearest(src_points, ref_points, q_transform=transform, radius=radius, want_rows=False)
+    return quality_dict((float(a[1]), a[2], a[0], float(b[1]), b[2], b[0], ref_points.shape[0], src_points.shape[0]))
+
+
 def _gt_check(t, name, shape, dtype, device):
     if not isinstance(t, torch.Tensor):
         raise RuntimeError(f'gt_node_correspondences: {name} must be a tensor')
