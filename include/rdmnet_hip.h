@@ -207,6 +207,29 @@ int rdm_nearest(const float* q, int64_t n_q, int64_t ld_q, const float* s, int64
 int rdm_realign_error(const float* pts, int64_t n, int64_t ld, const double* gt_host, const double* est_host, double* mean_host,
                       void* ws, size_t ws_bytes, void* stream);
 
+/* ---- pose information matrix of an aligned pair (nearest.hip) ---------------------------------------------------------
+ * What Open3D's get_information_matrix_from_point_clouds(source, target, max_correspondence_distance, transformation) and
+ * evaluate_registration compute (Open3D is not part of the reference tree -> parity unpinned; pinned to the float64
+ * restatement tests/information_restatement.py).  q = source, s = target, transforms, reads and arithmetic exactly as
+ * rdm_nearest (one run of its move / index / shell / sweep phases).  Source row i has a correspondence (i, j) iff its nearest
+ * target row j (the lowest among equal distances) has sqrt(d2) < radius -- STRICT, the rows rdm_nearest counts in totals[1];
+ * Open3D's own comparison is library-internal, this library defines it.  With p = (x, y, z) the MOVED TARGET point s'_j, the
+ * matrix is the sum over the correspondences of g g^T for g = (0, z, -y, 1, 0, 0), (-z, 0, x, 0, 1, 0), (y, -x, 0, 0, 0, 1)
+ * (rotation first, then translation, as Open3D), evaluated in closed form from C = sum 1 (an integer), sum p and sum p p^T:
+ * rotation block tr(M) I - M, translation block C I, upper-right block [sum p]x and its transpose below.  Float64 sums in a
+ * fixed order (per thread in row order, lanes by butterfly, wavefronts and block slabs in order; the launch geometry depends
+ * on n_q only), no float atomics: two calls give the same bits, whatever `cell` and whatever path a row took.
+ * out_host (host double[40], the call's one read-back, after which the stream is idle) = {the matrix row-major [36], C, the sum
+ * of d2 over the correspondences, rows that took the sweep, status 0}.  corr_out (device, optional): int64 [C, 2] rows (i, j) in
+ * ascending i -- evaluate_registration's correspondence_set --, compacted in order on the device (no atomic counter); at most
+ * `capacity` rows are written, and C > capacity returns RDM_ERR_CAPACITY with out_host filled.  n_q = 0, n_s = 0 or no row
+ * under the radius: the zero matrix and C = 0.  radius <= 0 is RDM_ERR_ARG; so is a point that is not finite, before or after
+ * moving (or a target point beyond 2^30 cells of `cell`), with out_host and corr_out untouched.  n_q, n_s < 2^31 - 64.   */
+size_t rdm_information_workspace_bytes(int64_t n_q, int64_t n_s);
+int rdm_information_matrix(const float* q, int64_t n_q, int64_t ld_q, const float* s, int64_t n_s, int64_t ld_s,
+                           const double* q_transform_host, const double* s_transform_host, double cell, double radius,
+                           double* out_host, int64_t* corr_out, int64_t capacity, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- dense contraction ---------------------------------------------------------------------
  * C[b] = act((A[b] (m x k) * op(B[b])) / rowdiv[row] + bias[col]) in fp32 on the f32 MFMA.
  * trans_b = 0: B is [k, n] row-major (pre-transposed nn.Linear weights, KPConv weights viewed
@@ -834,6 +857,15 @@ int rdm_engine_gt_point_correspondences_fill(rdm_engine* e, int64_t* out, int64_
  * without a completed forward run are RDM_ERR_ARG.                                                                      */
 int rdm_engine_alignment_quality(rdm_engine* e, int level, const double* transform_host, double radius, double* out_host,
                                  void* stream);
+/* rdm_information_matrix on the LAST run's resident clouds (no upload, no export): levels as above; source = the src cloud moved
+ * by transform_host (float64 4x4 on the host, src -> ref; null: the run's own estimated_transform), target = the ref cloud;
+ * out_host (host double[40]), corr_out (device int64 [C, 2], rows (src row, ref row); optional) and capacity as
+ * rdm_information_matrix.  Per engine after its run, also for the engines of a lock-step group; the workspace lies in the arena
+ * above the last run and is released before the call returns (a pending count call's too); synchronises `stream`.  A forward
+ * that is not followed by this call launches nothing for it.  radius <= 0 and an engine without a completed forward run are
+ * RDM_ERR_ARG; C > capacity is RDM_ERR_CAPACITY.                                                                          */
+int rdm_engine_information_matrix(rdm_engine* e, int level, const double* transform_host, double radius, double* out_host,
+                                  int64_t* corr_out, int64_t capacity, void* stream);
 /* Plain device-to-device copy on `stream` (lets a host without a HIP binding read arena tensors). */
 int rdm_copy_device(void* dst, const void* src, size_t bytes, void* stream);
 

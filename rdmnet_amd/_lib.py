@@ -110,6 +110,9 @@ SIGNATURES = {
     'rdm_nearest': (c_int, [c_void, c_i64, c_i64, c_void, c_i64, c_i64, c_void, c_void, ctypes.c_double, ctypes.c_double, c_void,
                             c_void, c_void, c_void, c_size, c_void]),
     'rdm_realign_error': (c_int, [c_void, c_i64, c_i64, c_void, c_void, c_void, c_void, c_size, c_void]),
+    'rdm_information_workspace_bytes': (c_size, [c_i64, c_i64]),
+    'rdm_information_matrix': (c_int, [c_void, c_i64, c_i64, c_void, c_i64, c_i64, c_void, c_void, ctypes.c_double, ctypes.c_double,
+                                       c_void, c_void, c_i64, c_void, c_size, c_void]),
     'rdm_neighbor_histogram': (c_int, [c_void, c_i64, c_void, c_int, c_void]),
     'rdm_radius_grid_records': (c_void, [c_void, c_size, c_i64]),
     'rdm_row_positive': (c_int, [c_void, c_i64, c_i64, c_i64, c_void, c_void]),
@@ -219,6 +222,7 @@ SIGNATURES = {
     'rdm_engine_gt_point_correspondences_count': (c_int, [c_void, c_int, c_void, ctypes.c_double, c_void, c_void]),
     'rdm_engine_gt_point_correspondences_fill': (c_int, [c_void, c_void, c_i64, c_void]),
     'rdm_engine_alignment_quality': (c_int, [c_void, c_int, c_void, ctypes.c_double, c_void, c_void]),
+    'rdm_engine_information_matrix': (c_int, [c_void, c_int, c_void, ctypes.c_double, c_void, c_void, c_i64, c_void]),
     'rdm_copy_device': (c_int, [c_void, c_void, c_size, c_void]),
     'rdm_eval_pairs_workspace_bytes': (c_size, [c_i64, c_i64, c_i64, c_void]),
     'rdm_eval_pairs': (c_int, [c_i64, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void,

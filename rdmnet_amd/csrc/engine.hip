@@ -2518,6 +2518,44 @@ extern "C" int rdm_engine_alignment_quality(rdm_engine* e, int level, const doub
   return RDM_OK;
 }
 
+extern "C" int rdm_engine_information_matrix(rdm_engine* e, int level, const double* transform_host, double radius, double* out_host,
+                                             int64_t* corr_out, int64_t capacity, void* stream) {
+  RDM_REQUIRE(e && out_host, "rdm_engine_information_matrix: null pointer");
+  RDM_REQUIRE(level >= 0 && level <= 2, "rdm_engine_information_matrix: level %d (0 input, 1 fine, 2 coarse)", level);
+  RDM_REQUIRE(radius > 0.0 && std::isfinite(radius), "rdm_engine_information_matrix: radius must be > 0 and finite (got %g)", radius);
+  RDM_REQUIRE(e->gt.valid, "rdm_engine_information_matrix: the engine holds no completed forward run (its points); "
+                           "run rdm_engine_run / rdm_engine_forward first");
+  rdm_engine::GtInputs& g = e->gt;
+  if (g.ball.pending) {  // a count call that was never filled: its workspace goes first
+    e->arena_off = g.ball.off_before;
+    g.ball.pending = false;
+  }
+  const float* ref = level == 0 ? g.p0[0] : (level == 1 ? g.pf[0] : g.nodes[0]);
+  const float* src = level == 0 ? g.p0[1] : (level == 1 ? g.pf[1] : g.nodes[1]);
+  const int64_t n = level == 0 ? g.n0[0] : (level == 1 ? g.nf[0] : g.m[0]);
+  const int64_t m = level == 0 ? g.n0[1] : (level == 1 ? g.nf[1] : g.m[1]);
+  double own[16];
+  if (transform_host == nullptr) {  // the run's own pose
+    for (int k = 0; k < 16; ++k) own[k] = static_cast<double>(g.est[k]);
+    transform_host = own;
+  }
+  // scratch above the last run's tensors, released again below (the call synchronises before it returns)
+  const size_t off_before = e->arena_off;
+  const size_t ws_bytes = rdm_information_workspace_bytes(m, n);
+  char* ws = e->alloc<char>(ws_bytes);
+  if (ws == nullptr) {
+    e->arena_off = off_before;
+    set_error("rdm_engine_information_matrix: %zu B of scratch do not fit above the last run in the arena (%zu B)", ws_bytes,
+              e->arena_cap);
+    return RDM_ERR_WORKSPACE;
+  }
+  // source = the src cloud moved by the pose, target = the ref cloud
+  const int rc = rdm_information_matrix(src, m, 3, ref, n, 3, transform_host, nullptr, 0.0, radius, out_host, corr_out, capacity, ws,
+                                        ws_bytes, stream);
+  e->arena_off = off_before;
+  return rc;
+}
+
 extern "C" int rdm_copy_device(void* dst, const void* src, size_t bytes, void* stream) {
   RDM_REQUIRE(dst && src, "rdm_copy_device: null pointer");
   RDM_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));

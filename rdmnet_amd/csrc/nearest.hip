@@ -29,6 +29,14 @@
 // on h, on the path a row takes or on scheduling: no float atomics, two calls give the same bits.
 // A point that is not finite, before or after moving, or a support point beyond the cell limits, sets the status before
 // anything is indexed: every later kernel returns at once, the outputs stay untouched and the call returns RDM_ERR_ARG.
+//
+// rdm_information_matrix (Open3D's get_information_matrix_from_point_clouds / evaluate_registration; parity unpinned, pinned to
+// tests/information_restatement.py) runs the phases above once, q = source, s = target, and then, over the rows with
+// sqrt(d2) < radius (STRICT: the rows the reduce step counts; Open3D's own comparison is library-internal, this library defines
+// it), p = s'_idx the MOVED TARGET point: the sum of g g^T for g = (0, z, -y, 1, 0, 0), (-z, 0, x, 0, 1, 0), (y, -x, 0, 0, 0, 1)
+// in closed form -- C = sum 1 (an integer), sum p, sum p p^T: rotation block tr(M) I - M, translation block C I, upper-right
+// block [sum p]x, its transpose below -- with the reduce step's sums (info_sum_kernel, info_totals_kernel); optionally the rows
+// (i, idx[i]) in ascending i by a second ordered compaction (info_corr_kernel; no atomic counter); one read-back of 40 doubles.
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
@@ -61,6 +69,7 @@ struct Rec {  // a moved support point and its row, in key order
 struct NnState {
   int stop;         // 2: a point that is not finite, or a support point beyond the cell limits
   unsigned n_list;  // unsettled rows (written by the compaction)
+  unsigned n_corr;  // rdm_information_matrix: rows under the radius (written by its compaction)
   double radius;
 };
 
@@ -156,6 +165,7 @@ __global__ void nn_setup_kernel(const double* __restrict__ slab_s, int rows_s, i
   grid->h = h;
   st->stop = bad ? 2 : 0;
   st->n_list = 0;
+  st->n_corr = 0;
   st->radius = radius;
 }
 
@@ -370,6 +380,98 @@ __global__ void realign_totals_kernel(const double* __restrict__ slab, int rows,
   totals[1] = bad;
 }
 
+// ---- rdm_information_matrix: the 6 x 6 information matrix of the rows under the radius --------------------------------------
+// Per correspondence (i, j = idx[i]) with sqrt(d2[i]) < radius (strict; the rows nn_sum_kernel counts) and p = (x, y, z) = s'_j:
+// the closed form of sum g g^T over g = (0, z, -y, 1, 0, 0), (-z, 0, x, 0, 1, 0), (y, -x, 0, 0, 0, 1) needs C = sum 1 (an integer),
+// s = sum p, M = sum p p^T (six entries) and, for the inlier RMSE, sum d2.
+constexpr int kInfoSums = 10;  // x, y, z, xx, xy, xz, yy, yz, zz, d2
+constexpr int kInfoOut = 40;   // the read-back: the matrix row-major [36], C, sum of d2, rows that took the sweep, status
+
+// Block sums in nn_sum_kernel's order (per thread in row order, lanes by butterfly, wavefronts in order) -> slab[block][kInfoSums],
+// count[block]; within[i] = 1 iff row i has a correspondence (the compaction's flags).
+__global__ __launch_bounds__(kBlock) void info_sum_kernel(const double* __restrict__ d2, const int* __restrict__ idx, int n,
+                                                          const double* __restrict__ sm, const NnState* __restrict__ st,
+                                                          double* __restrict__ slab, long long* __restrict__ count,
+                                                          uint8_t* __restrict__ within) {
+  if (st->stop != 0) return;
+  const double r = st->radius;
+  double acc[kInfoSums];
+  for (int k = 0; k < kInfoSums; ++k) acc[k] = 0.0;
+  int c = 0;
+  for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += static_cast<long long>(gridDim.x) * kBlock) {
+    const double v = d2[i];
+    const bool in = sqrt(v) < r;  // (strict; false for d2 = +inf, so idx = n_s is never read)
+    within[i] = in ? 1 : 0;
+    if (in) {
+      const long long j = idx[i];
+      const double x = sm[3 * j], y = sm[3 * j + 1], z = sm[3 * j + 2];
+      c += 1;
+      acc[0] += x; acc[1] += y; acc[2] += z;
+      acc[3] += x * x; acc[4] += x * y; acc[5] += x * z;
+      acc[6] += y * y; acc[7] += y * z; acc[8] += z * z;
+      acc[9] += v;
+    }
+  }
+  __shared__ double red[kInfoSums][kRowsPerBlock];
+  __shared__ int red_c[kRowsPerBlock];
+  for (int k = 0; k < kInfoSums; ++k) acc[k] = wave_sum(acc[k]);
+  c = wave_sum_i(c);
+  if (lane_id() == 0) {
+    for (int k = 0; k < kInfoSums; ++k) red[k][threadIdx.x >> 6] = acc[k];
+    red_c[threadIdx.x >> 6] = c;
+  }
+  __syncthreads();
+  if (threadIdx.x < kInfoSums) {
+    double v = red[threadIdx.x][0];
+    for (int w = 1; w < kRowsPerBlock; ++w) v += red[threadIdx.x][w];
+    slab[blockIdx.x * kInfoSums + threadIdx.x] = v;
+  } else if (threadIdx.x == kInfoSums) {
+    long long v = 0;
+    for (int w = 0; w < kRowsPerBlock; ++w) v += red_c[w];
+    count[blockIdx.x] = v;
+  }
+}
+
+// One thread: the block slabs in order -> out[kInfoOut] (all zero but the status after a bad call, or without rows).
+__global__ void info_totals_kernel(const double* __restrict__ slab, const long long* __restrict__ count, int rows,
+                                   const NnState* __restrict__ st, double* __restrict__ out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double t[kInfoSums];
+  for (int k = 0; k < kInfoSums; ++k) t[k] = 0.0;
+  long long c = 0;
+  if (st->stop == 0)
+    for (int r = 0; r < rows; ++r) {
+      for (int k = 0; k < kInfoSums; ++k) t[k] += slab[r * kInfoSums + k];
+      c += count[r];
+    }
+  const double C = static_cast<double>(c), sx = t[0], sy = t[1], sz = t[2];
+  const double xx = t[3], xy = t[4], xz = t[5], yy = t[6], yz = t[7], zz = t[8];
+  const double info[36] = {yy + zz, -xy,     -xz,     0.0, -sz, sy,    //
+                           -xy,     xx + zz, -yz,     sz,  0.0, -sx,   //
+                           -xz,     -yz,     xx + yy, -sy, sx,  0.0,   //
+                           0.0,     sz,      -sy,     C,   0.0, 0.0,   //
+                           -sz,     0.0,     sx,      0.0, C,   0.0,   //
+                           sy,      -sx,     0.0,     0.0, 0.0, C};
+  for (int k = 0; k < 36; ++k) out[k] = info[k] + 0.0;  // (+ 0.0: no negative zeros)
+  out[36] = C;
+  out[37] = t[9];
+  out[38] = st->stop == 0 ? static_cast<double>(st->n_list) : 0.0;
+  out[39] = static_cast<double>(st->stop);
+}
+
+// out[k] = (i, idx[i]) for the k-th row under the radius, k < capacity (rows ascending: the compaction is stable)
+__global__ __launch_bounds__(kBlock) void info_corr_kernel(const int* __restrict__ rows, const int* __restrict__ idx,
+                                                           const NnState* __restrict__ st, long long capacity,
+                                                           long long* __restrict__ out) {
+  if (st->stop != 0) return;
+  const long long count = st->n_corr < capacity ? st->n_corr : capacity;
+  for (long long k = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; k < count; k += static_cast<long long>(gridDim.x) * kBlock) {
+    const int i = rows[k];
+    out[2 * k] = i;
+    out[2 * k + 1] = idx[i];
+  }
+}
+
 using RowIter = rocprim::counting_iterator<int>;
 
 size_t select_temp_bytes(int64_t n) {
@@ -438,6 +540,60 @@ extern "C" size_t rdm_nearest_workspace_bytes(int64_t n_q, int64_t n_s) {
   return ar.off;
 }
 
+namespace {
+
+// move, boxes, setup, the index of the moved support cloud, phase 1, the list of unsettled rows, phase 2: idx / d2 of every row
+int search(const float* q, int n, int64_t ld_q, const float* s, int m, int64_t ld_s, const double* q_transform_host,
+           const double* s_transform_host, double cell, double radius, const Work& w, int* out_idx, double* out_d2, hipStream_t st) {
+  if (n > 0)
+    hipLaunchKernelGGL(nn_move_kernel, dim3(row_blocks(n)), dim3(kBlock), 0, st, q, n, static_cast<long long>(ld_q),
+                       mat_of(q_transform_host), q_transform_host ? 1 : 0, w.qm);
+  if (m > 0)
+    hipLaunchKernelGGL(nn_move_kernel, dim3(row_blocks(m)), dim3(kBlock), 0, st, s, m, static_cast<long long>(ld_s),
+                       mat_of(s_transform_host), s_transform_host ? 1 : 0, w.sm);
+  const int qb = point_blocks(n), sb = point_blocks(m);
+  hipLaunchKernelGGL(nn_box_kernel, dim3(qb), dim3(kBlock), 0, st, w.qm, n, w.slab_q);
+  hipLaunchKernelGGL(nn_box_kernel, dim3(sb), dim3(kBlock), 0, st, w.sm, m, w.slab_s);
+  hipLaunchKernelGGL(nn_setup_kernel, dim3(1), dim3(64), 0, st, w.slab_s, sb, m, w.slab_q, qb, cell, radius, w.ci.grid, w.st);
+  if (m > 0) {
+    CellIndex ci = w.ci;
+    const int rc = sort_cells(w.sm, m, 3, &w.st->stop, ci, st);
+    if (rc != RDM_OK) return rc;
+    hipLaunchKernelGGL(nn_records_kernel, dim3(row_blocks(m)), dim3(kBlock), 0, st, w.sm, m, w.ci.order, w.st, w.recs);
+  }
+  if (n > 0) {
+    hipLaunchKernelGGL(nn_shell_kernel, dim3(static_cast<unsigned>((static_cast<int64_t>(n) + kRowsPerBlock - 1) / kRowsPerBlock)),
+                       dim3(kBlock), 0, st, w.qm, n, w.ci.keys, w.recs, m, w.ci.grid, w.st, out_idx, out_d2, w.open);
+    if (m > 0) {
+      // (after a bad call `open` holds stale flags: the list is then garbage of at most n entries, and nothing reads it)
+      size_t bytes = w.select_bytes;
+      RDM_HIP_CHECK(rocprim::select(w.select_tmp, bytes, RowIter(0), static_cast<const uint8_t*>(w.open), w.list, &w.st->n_list,
+                                    static_cast<size_t>(n), st));
+      const int64_t groups = (static_cast<int64_t>(n) + kWave - 1) / kWave;
+      hipLaunchKernelGGL(nn_sweep_kernel, dim3(static_cast<unsigned>(groups > kSweepMaxBlocks ? kSweepMaxBlocks : groups)), dim3(kBlock),
+                         0, st, w.qm, w.sm, m, w.list, w.st, out_idx, out_d2);
+    }
+  }
+  return RDM_OK;
+}
+
+struct InfoWork {
+  Work nn;
+  double* slab;
+  long long* count;
+  double* out;
+};
+
+bool carve_info(Arena& ar, int64_t n, int64_t m, InfoWork& w) {
+  carve(ar, n, m, w.nn);
+  w.slab = ar.take<double>(kCellMaxBlocks * kInfoSums);
+  w.count = ar.take<long long>(kCellMaxBlocks);
+  w.out = ar.take<double>(kInfoOut);
+  return ar.ok;
+}
+
+}  // namespace
+
 extern "C" int rdm_nearest(const float* q, int64_t n_q, int64_t ld_q, const float* s, int64_t n_s, int64_t ld_s,
                            const double* q_transform_host, const double* s_transform_host, double cell, double radius, int32_t* idx,
                            double* d2, double* totals_host, void* ws, size_t ws_bytes, void* stream) {
@@ -457,40 +613,12 @@ extern "C" int rdm_nearest(const float* q, int64_t n_q, int64_t ld_q, const floa
   const int n = static_cast<int>(n_q), m = static_cast<int>(n_s);
   int* out_idx = idx ? idx : w.idx;
   double* out_d2 = d2 ? d2 : w.d2;
-  // move, boxes, setup
-  if (n > 0)
-    hipLaunchKernelGGL(nn_move_kernel, dim3(row_blocks(n)), dim3(kBlock), 0, st, q, n, static_cast<long long>(ld_q),
-                       mat_of(q_transform_host), q_transform_host ? 1 : 0, w.qm);
-  if (m > 0)
-    hipLaunchKernelGGL(nn_move_kernel, dim3(row_blocks(m)), dim3(kBlock), 0, st, s, m, static_cast<long long>(ld_s),
-                       mat_of(s_transform_host), s_transform_host ? 1 : 0, w.sm);
-  const int qb = point_blocks(n), sb = point_blocks(m);
-  hipLaunchKernelGGL(nn_box_kernel, dim3(qb), dim3(kBlock), 0, st, w.qm, n, w.slab_q);
-  hipLaunchKernelGGL(nn_box_kernel, dim3(sb), dim3(kBlock), 0, st, w.sm, m, w.slab_s);
-  hipLaunchKernelGGL(nn_setup_kernel, dim3(1), dim3(64), 0, st, w.slab_s, sb, m, w.slab_q, qb, cell, radius, w.ci.grid, w.st);
-  // index of the moved support cloud
-  if (m > 0) {
-    const int rc = sort_cells(w.sm, m, 3, &w.st->stop, w.ci, st);
-    if (rc != RDM_OK) return rc;
-    hipLaunchKernelGGL(nn_records_kernel, dim3(row_blocks(m)), dim3(kBlock), 0, st, w.sm, m, w.ci.order, w.st, w.recs);
-  }
-  if (n > 0) {
-    // phase 1, the list of unsettled rows, phase 2
-    hipLaunchKernelGGL(nn_shell_kernel, dim3(static_cast<unsigned>((n_q + kRowsPerBlock - 1) / kRowsPerBlock)), dim3(kBlock), 0, st, w.qm,
-                       n, w.ci.keys, w.recs, m, w.ci.grid, w.st, out_idx, out_d2, w.open);
-    if (m > 0) {
-      // (after a bad call `open` holds stale flags: the list is then garbage of at most n entries, and nothing reads it)
-      size_t bytes = w.select_bytes;
-      RDM_HIP_CHECK(rocprim::select(w.select_tmp, bytes, RowIter(0), static_cast<const uint8_t*>(w.open), w.list, &w.st->n_list,
-                                    static_cast<size_t>(n), st));
-      const int64_t groups = (n_q + kWave - 1) / kWave;
-      hipLaunchKernelGGL(nn_sweep_kernel, dim3(static_cast<unsigned>(groups > kSweepMaxBlocks ? kSweepMaxBlocks : groups)), dim3(kBlock),
-                         0, st, w.qm, w.sm, m, w.list, w.st, out_idx, out_d2);
-    }
-    hipLaunchKernelGGL(nn_sum_kernel, dim3(qb), dim3(kBlock), 0, st, out_d2, n, w.st, w.slab_sum);
-  }
+  int rc = search(q, n, ld_q, s, m, ld_s, q_transform_host, s_transform_host, cell, radius, w, out_idx, out_d2, st);
+  if (rc != RDM_OK) return rc;
+  const int qb = point_blocks(n);
+  if (n > 0) hipLaunchKernelGGL(nn_sum_kernel, dim3(qb), dim3(kBlock), 0, st, out_d2, n, w.st, w.slab_sum);
   hipLaunchKernelGGL(nn_totals_kernel, dim3(1), dim3(64), 0, st, w.slab_sum, n > 0 ? qb : 0, w.st, w.totals);
-  const int rc = launch_status("rdm_nearest");
+  rc = launch_status("rdm_nearest");
   if (rc != RDM_OK) return rc;
   double host[8];
   RDM_HIP_CHECK(hipMemcpyAsync(host, w.totals, sizeof(host), hipMemcpyDeviceToHost, st));  // the call's one read-back
@@ -500,6 +628,68 @@ extern "C" int rdm_nearest(const float* q, int64_t n_q, int64_t ld_q, const floa
     set_error("rdm_nearest: a point is not finite (before or after moving), or a support point lies beyond 2^30 cells (or the "
               "box beyond 2^62 cells) of the cell edge");
     return RDM_ERR_ARG;
+  }
+  return RDM_OK;
+}
+
+extern "C" size_t rdm_information_workspace_bytes(int64_t n_q, int64_t n_s) {
+  using namespace rdm;
+  Arena ar(nullptr, 0);
+  InfoWork w;
+  carve_info(ar, n_q > 0 ? n_q : 0, n_s > 0 ? n_s : 0, w);
+  return ar.off;
+}
+
+extern "C" int rdm_information_matrix(const float* q, int64_t n_q, int64_t ld_q, const float* s, int64_t n_s, int64_t ld_s,
+                                      const double* q_transform_host, const double* s_transform_host, double cell, double radius,
+                                      double* out_host, int64_t* corr_out, int64_t capacity, void* ws, size_t ws_bytes, void* stream) {
+  using namespace rdm;
+  RDM_REQUIRE(out_host, "rdm_information_matrix: null out_host");
+  RDM_REQUIRE(sizes_ok(n_q, n_s, ld_q, ld_s), "rdm_information_matrix: bad sizes (n_q=%lld n_s=%lld; both < 2^31 - 64, row strides >= 3)",
+              (long long)n_q, (long long)n_s);
+  RDM_REQUIRE((q || n_q == 0) && (s || n_s == 0), "rdm_information_matrix: null points");
+  RDM_REQUIRE(std::isfinite(cell), "rdm_information_matrix: cell (%g) must be finite", cell);
+  RDM_REQUIRE(radius > 0.0 && std::isfinite(radius), "rdm_information_matrix: radius must be > 0 and finite (got %g)", radius);
+  RDM_REQUIRE(capacity >= 0, "rdm_information_matrix: negative capacity");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Arena ar(ws, ws_bytes);
+  InfoWork w;
+  if (!carve_info(ar, n_q, n_s, w)) {
+    set_error("rdm_information_matrix: workspace too small (%zu < %zu bytes)", ws_bytes, ar.off);
+    return RDM_ERR_WORKSPACE;
+  }
+  const int n = static_cast<int>(n_q), m = static_cast<int>(n_s);
+  int rc = search(q, n, ld_q, s, m, ld_s, q_transform_host, s_transform_host, cell, radius, w.nn, w.nn.idx, w.nn.d2, st);
+  if (rc != RDM_OK) return rc;
+  const bool rows = n > 0 && m > 0;  // (without support rows d2 = +inf: no correspondence)
+  const int qb = point_blocks(n);
+  if (rows) {
+    // (the flags of the unsettled rows and their list are read out: both buffers now serve the rows under the radius)
+    hipLaunchKernelGGL(info_sum_kernel, dim3(qb), dim3(kBlock), 0, st, w.nn.d2, w.nn.idx, n, w.nn.sm, w.nn.st, w.slab, w.count,
+                       w.nn.open);
+    if (corr_out) {
+      size_t bytes = w.nn.select_bytes;
+      RDM_HIP_CHECK(rocprim::select(w.nn.select_tmp, bytes, RowIter(0), static_cast<const uint8_t*>(w.nn.open), w.nn.list,
+                                    &w.nn.st->n_corr, static_cast<size_t>(n), st));
+      hipLaunchKernelGGL(info_corr_kernel, dim3(qb), dim3(kBlock), 0, st, w.nn.list, w.nn.idx, w.nn.st,
+                         static_cast<long long>(capacity), reinterpret_cast<long long*>(corr_out));
+    }
+  }
+  hipLaunchKernelGGL(info_totals_kernel, dim3(1), dim3(64), 0, st, w.slab, w.count, rows ? qb : 0, w.nn.st, w.out);
+  rc = launch_status("rdm_information_matrix");
+  if (rc != RDM_OK) return rc;
+  double host[kInfoOut];
+  RDM_HIP_CHECK(hipMemcpyAsync(host, w.out, sizeof(host), hipMemcpyDeviceToHost, st));  // the call's one read-back
+  RDM_HIP_CHECK(hipStreamSynchronize(st));
+  if (host[39] != 0.0) {
+    set_error("rdm_information_matrix: a point is not finite (before or after moving), or a target point lies beyond 2^30 cells "
+              "(or the box beyond 2^62 cells) of the cell edge");
+    return RDM_ERR_ARG;
+  }
+  for (int k = 0; k < kInfoOut; ++k) out_host[k] = host[k];
+  if (corr_out && host[36] > static_cast<double>(capacity)) {
+    set_error("rdm_information_matrix: %lld correspondences, capacity %lld", (long long)host[36], (long long)capacity);
+    return RDM_ERR_CAPACITY;
   }
   return RDM_OK;
 }

@@ -555,6 +555,33 @@ class Engine:
                    'rdm_engine_alignment_quality')
         return quality_dict([float(x) for x in out])
 
+    def information_matrix(self, transform=None, radius=None, level='input', return_correspondences=False):
+        """ops.information_matrix on the last run's resident points (rdm_engine_information_matrix), no upload: source = the src
+        cloud moved by transform (4x4 src -> ref; None: the run's own estimated_transform), target = the ref cloud; levels as
+        gt_point_correspondences; radius None = cfg.fine_matching.acceptance_radius -> float64 [6, 6] on the host (with
+        return_correspondences also int64 [C, 2] on the device, rows (src row, ref row) in ascending src row).  keep_taps is not
+        needed; an engine without a completed forward run raises.  Synchronises the current stream."""
+        if level not in POINT_LEVELS:
+            raise ValueError(f'information_matrix: level {level!r}, expected one of {sorted(POINT_LEVELS)}')
+        if radius is None:
+            radius = float(self.cfg.fine_matching.acceptance_radius)
+        if not radius > 0:
+            raise ValueError(f'information_matrix: radius must be > 0, got {radius}')
+        from .ops import INFORMATION_WIDTH, _transform_arg, information_result
+        T = _transform_arg(transform, 'information_matrix')
+        r = self.result
+        n_src = {'input': int(r.level_sizes[0]) - int(r.level_ref_sizes[0]), 'fine': int(r.level_sizes[1]) - int(r.level_ref_sizes[1]),
+                 'coarse': int(r.n_src_nodes)}[level]
+        cap = max(n_src, 1)  # (at most one row per src row; sizes of a run that never completed are not used: the call raises)
+        corr = torch.empty((cap, 2), dtype=torch.int64, device=self.device) if return_correspondences else None
+        host = (ctypes.c_double * INFORMATION_WIDTH)()
+        _lib.check(self.L.rdm_engine_information_matrix(self._h, POINT_LEVELS[level], 0 if T is None else T.ctypes.data, float(radius),
+                                                        host, _lib.ptr(corr), cap, _lib.stream_ptr()),
+                   'rdm_engine_information_matrix')
+        info, c, _, _, corr = information_result(host, corr)
+        self.information_corr = c  # the correspondences behind the last matrix
+        return (info, corr) if return_correspondences else info
+
     def corr(self):
         """(ref_corr_points, src_corr_points, corr_scores) of the last run as fresh tensors."""
         n = self.result.n_correspondences

@@ -7,6 +7,7 @@ registration report, on the native engine.
     python -m rdmnet_amd.infer --dataset-root /data/kitti --gt-nodes --out out/      # test.py's evaluation run (eval.py reads out/)
     python -m rdmnet_amd.infer --infer-root /path/to/assets/pc --out out/ --feature-match mutual   # + descriptor correspondences
     python -m rdmnet_amd.infer --infer-root /path/to/assets/pc --out out/ --quality                # + fitness, inlier RMSE, chamfer
+    python -m rdmnet_amd.infer --infer-root /path/to/assets/pc --out out/ --information            # + the 6 x 6 pose information matrix
     python -m torch.distributed.run --nproc-per-node 8 -m rdmnet_amd.infer ...       # pairs sharded over ranks
 
 Per pair it writes what the reference writes: one line in `<seq>_pose` and one `<seq>_<src>_<ref>.npz`
@@ -23,6 +24,10 @@ descriptor inlier ratio to the pair's log line.
 `--quality` judges every pair's pose without ground truth (Engine.alignment_quality on the resident input clouds, radius
 cfg.fine_matching.acceptance_radius): fitness and inlier RMSE of both sides and the chamfer distance go to the pair's log line and,
 as quality_* keys (ops.QUALITY_KEYS), into its .npz; every other key stays as it is.
+`--information` says how well every pair's pose is constrained, for a pose graph: Open3D's 6 x 6 information matrix of the pair
+(Engine.information_matrix on the resident input clouds, src moved by the pair's own pose against ref, radius
+cfg.fine_matching.acceptance_radius) goes into the .npz as `information` (float64 [6, 6]) with `information_corr` (int64, the
+correspondences behind it), and `info_corr: N` to the pair's log line; every other key stays as it is.
 """
 import argparse
 import os
@@ -51,7 +56,7 @@ class Tester:
 
     def __init__(self, cfg, state, output_dir=None, save_npz=True, ransac=True, write_poses=True,
                  pairs_in_flight=DEFAULT_PAIRS_IN_FLIGHT, wait_us=None, lockstep=None, gt_nodes=False, feature_match=None,
-                 quality=False):
+                 quality=False, information=False):
         self.cfg, self.output_dir, self.save_npz, self.ransac = cfg, output_dir, save_npz, ransac
         self.write_poses = write_poses  # False under several ranks: rank 0 writes all poses, in pair order, at the end
         # gt_nodes: test.py's run -- ground-truth superpoint correspondences per pair with a transform (model.py:283-297, radius
@@ -62,6 +67,7 @@ class Tester:
             raise ValueError(f'feature_match {feature_match!r}, expected one of {sorted(ops.FEATURE_MATCH_MODES)}')
         self.feature_match = feature_match
         self.quality = bool(quality)  # Engine.alignment_quality of every pair's own pose, on the input clouds
+        self.information = bool(information)  # Engine.information_matrix of every pair's own pose, on the input clouds
         ev = dict(cfg.get('eval', {})) if hasattr(cfg, 'get') else {}
         self.fm_radius = float(ev.get('acceptance_radius', 0.6))
         radius = getattr(getattr(cfg, 'model', None), 'ground_truth_matching_radius', None)
@@ -116,6 +122,11 @@ class Tester:
             rec['quality'] = eng.alignment_quality()
             extra = dict(extra or {})
             extra.update({f'quality_{k}': np.float64(rec['quality'][k]) for k in ops.QUALITY_KEYS})
+        if self.information:  # the pose information matrix of the pair on the engine's resident input clouds, this stream
+            info = eng.information_matrix()
+            rec['info_corr'] = int(eng.information_corr)
+            extra = dict(extra or {})
+            extra.update(information=info.numpy(), information_corr=np.int64(rec['info_corr']))
         if self.gt_nodes and 'transform' in item:  # test.py: model.py:283-297 on the engine's resident tensors, this stream
             gt_idx, gt_ovl, _ = eng.gt_node_correspondences(np.asarray(item['transform'], np.float32), self.gt_radius)
             m_r = int(res.n_ref_nodes)
@@ -171,6 +182,8 @@ class Tester:
                         line += ', feat_IR: {:.3f}'.format(rec['feat_IR'])
                 if 'quality' in rec:  # (--quality)
                     line += ''.join(', {}: {:.4f}'.format(k, rec['quality'][k]) for k in ops.QUALITY_KEYS)
+                if 'info_corr' in rec:  # (--information)
+                    line += ', info_corr: {}'.format(rec['info_corr'])
                 log(line)
         return self.records
 
@@ -207,6 +220,9 @@ def main(argv=None):
     ap.add_argument('--quality', action='store_true',
                     help="judge every pair's pose without ground truth: fitness and inlier RMSE of both clouds and the chamfer distance "
                          'at cfg.fine_matching.acceptance_radius, in the log line and as quality_* keys of the pair file')
+    ap.add_argument('--information', action='store_true',
+                    help="add every pair's 6 x 6 pose information matrix (Open3D's get_information_matrix_from_point_clouds at "
+                         'cfg.fine_matching.acceptance_radius, for a pose graph) to the pair file as information / information_corr')
     args = ap.parse_args(argv)
 
     rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
@@ -247,7 +263,8 @@ def main(argv=None):
         print(f'Calibrate neighbors: {cfg.neighbor_limits}.')
     tester = Tester(cfg, load_state(args.weights, cfg), args.out, save_npz=not args.no_npz, ransac=not args.no_ransac,
                     write_poses=world == 1, pairs_in_flight=args.pairs_in_flight, lockstep=args.lockstep, gt_nodes=args.gt_nodes,
-                    feature_match=args.feature_match, quality=args.quality)
+                    feature_match=args.feature_match, quality=args.quality,
+                    information=args.information)
     mine = sharding.pairs_for_rank(len(data), rank, world)
     # scans are read and staged (pinned host -> HBM on a side stream) two pairs ahead of every in-flight pair
     stager = ds_mod.PairStager(data, mine, depth=2 * args.pairs_in_flight, workers=max(2, args.pairs_in_flight))

@@ -605,8 +605,10 @@ class RegistrationResult:
     evaluation), iterations (updates applied) and, when asked for, history (float64 [evaluations, 15] numpy: per
     evaluation k {fitness, rmse, n_corr, update_k as 12 row-major R|t values}; row 0 is the initial evaluation)."""
 
-    def __init__(self, transformation, fitness, inlier_rmse, num_correspondences, iterations, history=None):
+    def __init__(self, transformation, fitness, inlier_rmse, num_correspondences, iterations, history=None,
+                 correspondence_set=None):
         self.transformation = transformation
+        self.correspondence_set = correspondence_set  # evaluate_registration: int64 CUDA [C, 2], rows (source row, target row)
         self.fitness = fitness
         self.inlier_rmse = inlier_rmse
         self.num_correspondences = num_correspondences
@@ -852,6 +854,66 @@ def alignment_quality(ref_points, src_points, transform, radius):
     _, _, a = _nearest(ref_points, src_points, s_transform=transform, radius=radius, want_rows=False)
     _, _, b = _nearest(src_points, ref_points, q_transform=transform, radius=radius, want_rows=False)
     return quality_dict((float(a[1]), a[2], a[0], float(b[1]), b[2], b[0], ref_points.shape[0], src_points.shape[0]))
+
+
+INFORMATION_WIDTH = 40  # the read-back of rdm_information_matrix: the matrix [36], C, the sum of d2, rows swept, status
+
+
+def information_result(host, corr):
+    """The read-back of rdm_information_matrix / rdm_engine_information_matrix (40 doubles) and the correspondence buffer ->
+    (information float64 [6, 6] (host tensor), C, the sum of d2 over the correspondences, rows that took the sweep, corr[:C])."""
+    info = torch.tensor([float(x) for x in host[:36]], dtype=torch.float64).reshape(6, 6)
+    c = int(host[36])
+    return info, c, float(host[37]), int(host[38]), None if corr is None else corr[:c]
+
+
+def _information(source, target, radius, s_transform=None, t_transform=None, want_corr=False, cell=None):
+    """rdm_information_matrix -> information_result's tuple; s_transform / t_transform move the source / the target cloud."""
+    if radius is None or not radius > 0:
+        raise ValueError(f'max_correspondence_distance must be > 0, got {radius}')
+    L = _lib.lib()
+    ldq, lds = _points_arg(source, 'source'), _points_arg(target, 'target')
+    if source.device != target.device:
+        raise ValueError('source and target must be on the same device')
+    Tq, Ts = _transform_arg(s_transform, 'transformation'), _transform_arg(t_transform, 'target transformation')
+    dev = source.device
+    n, m = source.shape[0], target.shape[0]
+    corr = torch.empty((max(n, 1), 2), dtype=torch.int64, device=dev) if want_corr else None  # (at most one row per source row)
+    ws = scratch(dev, L.rdm_information_workspace_bytes(n, m))
+    host = (ctypes.c_double * INFORMATION_WIDTH)()
+    _lib.check(L.rdm_information_matrix(_lib.ptr(source), n, ldq, _lib.ptr(target), m, lds, 0 if Tq is None else Tq.ctypes.data,
+                                        0 if Ts is None else Ts.ctypes.data, 0.0 if cell is None else float(cell), float(radius),
+                                        host, _lib.ptr(corr), n, ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+               'rdm_information_matrix')
+    return information_result(host, corr)
+
+
+def information_matrix(source, target, max_correspondence_distance, transformation=None, return_correspondences=False):
+    """Open3D's get_information_matrix_from_point_clouds(source, target, max_correspondence_distance, transformation) on the GPU
+    (rdm_information_matrix; parity unpinned, pinned to tests/information_restatement.py): source / target float32 CUDA [N, >=3]
+    (xyz first, any row stride), transformation 4x4 source -> target (None: the source as it is), read as float64.  A source row
+    has a correspondence iff its nearest target row (the lowest among equal distances) is nearer than
+    max_correspondence_distance (strict); the matrix sums g g^T over the target points p of the correspondences, g = (0, z, -y,
+    1, 0, 0), (-z, 0, x, 0, 1, 0), (y, -x, 0, 0, 0, 1).  -> float64 [6, 6] on the host (it arrives in the call's read-back); with
+    return_correspondences also int64 CUDA [C, 2], rows (source row, target row) in ascending source row."""
+    info, _, _, _, corr = _information(source, target, max_correspondence_distance, transformation,
+                                       want_corr=return_correspondences)
+    return (info, corr) if return_correspondences else info
+
+
+def evaluate_registration(source, target, max_correspondence_distance, transformation=None):
+    """Open3D's evaluate_registration on the GPU, from one rdm_information_matrix call: -> RegistrationResult(transformation,
+    fitness = C / n_source, inlier_rmse = sqrt(sum d2 / C) (0 without correspondences), num_correspondences = C, iterations 0)
+    with correspondence_set int64 CUDA [C, 2] and, as an extra attribute, `information` (float64 [6, 6])."""
+    import math
+    import numpy as np
+    info, c, sum_d2, _, corr = _information(source, target, max_correspondence_distance, transformation, want_corr=True)
+    n = source.shape[0]
+    T = _transform_arg(transformation, 'transformation')
+    res = RegistrationResult(np.eye(4) if T is None else T.copy(), c / n if n > 0 else 0.0, math.sqrt(sum_d2 / c) if c > 0 else 0.0,
+                             c, 0, correspondence_set=corr)
+    res.information = info
+    return res
 
 
 def _gt_check(t, name, shape, dtype, device):
