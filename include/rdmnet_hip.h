@@ -230,6 +230,49 @@ int rdm_information_matrix(const float* q, int64_t n_q, int64_t ld_q, const floa
                            const double* q_transform_host, const double* s_transform_host, double cell, double radius,
                            double* out_host, int64_t* corr_out, int64_t capacity, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- pose-graph optimisation (pose_graph.hip) ---------------------------------------------------------------------------
+ * What Open3D's global_optimization does (Open3D is not part of the reference tree -> parity unpinned; the definition is DESIGN.md
+ * section 7, pinned to the float64 restatement tests/pose_graph_restatement.py): damped Gauss-Newton on SE(3), information
+ * matrices as weights, a line process for uncertain (loop-closure) edges.  A call takes n_graphs graphs, concatenated:
+ * graph_node_offsets_host / graph_edge_offsets_host (host int64 [G + 1], from 0), nodes (device float64 [N, 16], row-major 4 x 4,
+ * the pose of scan i in the frame of its graph's node 0, which stays fixed), edges_host (host int64 [E, 2], rows (s, t), node
+ * numbers INSIDE the edge's graph), transforms (device float64 [E, 16], source-scan to target-scan coordinates: the model is
+ * X_s = X_t T), informations (device float64 [E, 36], rotation first, as rdm_information_matrix), uncertain_host (host uint8 [E]
+ * or null: no edge is uncertain).  line_process_weight mu <= 0: no line process (every weight is 1); else an uncertain edge's
+ * weight is l = (mu / (mu + r^T L r))^2 at the current poses, and it is reported as pruned when l < edge_prune_threshold at the
+ * final poses (edges are never removed).  Residual r = (Log of the rotation of E, translation of E), E = T^-1 X_t^-1 X_s; update
+ * X <- X [Exp(dw) | dt]; exact Jacobians; (H + lambda blockdiag(H)) x = -b solved per graph by one workgroup with block-Jacobi
+ * preconditioned conjugate gradients until sqrt(r^T M^-1 r) <= pcg_tolerance times its first value or pcg_max_iterations;
+ * lambda starts at 1e-6, a step is accepted iff the new cost is <= the old one (lambda / 10, at least 1e-12), else rejected
+ * (lambda * 10; above 1e12 the solve ends with stop reason 2).  Stops: 1 = the largest |entry| of the gradient of F (2 J^T L r) is
+ * <= gradient_tolerance, 2 = the relative decrease of an accepted step is <= cost_tolerance, 3 = max_iterations (accepted and
+ * rejected steps count), 4 = a graph without nodes or without edges (returned as given).  Float64, no float atomics, every sum
+ * in an order the graph alone decides: a graph's outputs are the same bits alone, in any batch, at any position, in any run.
+ * Outputs (device): nodes_out [N, 16] (may be `nodes`), weights_out [E] (optional: l at the final poses), pruned_out uint8 [E]
+ * (optional); report_host (host double [G, 8], the call's one read-back of results): {initial cost, final cost, iterations, PCG
+ * iterations in total, stop reason, status, final lambda, largest gradient entry at the last linearisation}.  RDM_ERR_ARG, with
+ * every device output untouched: an edge that joins a node to itself or names a node outside its graph, a graph above 65 536
+ * nodes or 1 048 576 edges, (status 1) an entry that is not finite, (2) an information matrix with |L_ij - L_ji| > 1e-12 max|L|,
+ * (3) a residual rotation of the GIVEN poses with cos(angle) < -0.99 (during the solve such a candidate is a rejected step),
+ * (4) a node block that is not positive definite (a node no edge reaches, an indefinite information matrix); the message names
+ * the first graph whose status is not 0.  The host reads one word every 8 iterations.  The per-graph limits are nominal: the
+ * block-Jacobi conjugate gradients need on the order of 10^4 iterations per step at 500 nodes (docs/EXPERIMENTS.md 5n), all inside one
+ * launch of one workgroup; for graphs beyond a few thousand nodes choose pcg_max_iterations accordingly.                                                                                                   */
+size_t rdm_pose_graph_workspace_bytes(int64_t n_graphs, int64_t n_nodes, int64_t n_edges);
+int rdm_pose_graph_optimize(int64_t n_graphs, const int64_t* graph_node_offsets_host, const int64_t* graph_edge_offsets_host,
+                            const double* nodes, const int64_t* edges_host, const double* transforms, const double* informations,
+                            const uint8_t* uncertain_host, double line_process_weight, double edge_prune_threshold,
+                            int max_iterations, double gradient_tolerance, double cost_tolerance, int pcg_max_iterations,
+                            double pcg_tolerance, double* nodes_out, double* weights_out, uint8_t* pruned_out, double* report_host,
+                            void* ws, size_t ws_bytes, void* stream);
+/* The kernels' per-edge arithmetic compiled for the host (all pointers host memory; no GPU needed), so that it can be held
+ * against the restatement without a device: out (double[128]) = {l, cost term, r [6], l A^T L A [36], l A^T L B [36],
+ * l B^T L B [36], l A^T L r [6], l B^T L r [6]} for one edge (A, B: the Jacobians of r with respect to the source's and the
+ * target's perturbation); RDM_ERR_ARG beyond the angle limit (r is still written).  And X [Exp(dw) | dt] -> out (double[16]). */
+int rdm_pose_graph_edge_terms_host(const double* source_pose, const double* target_pose, const double* transform,
+                                   const double* information, double line_process_weight, int uncertain, double* out);
+int rdm_pose_graph_retract_host(const double* pose, const double* delta, double* out);
+
 /* ---- dense contraction ---------------------------------------------------------------------
  * C[b] = act((A[b] (m x k) * op(B[b])) / rowdiv[row] + bias[col]) in fp32 on the f32 MFMA.
  * trans_b = 0: B is [k, n] row-major (pre-transposed nn.Linear weights, KPConv weights viewed

@@ -113,6 +113,12 @@ SIGNATURES = {
     'rdm_information_workspace_bytes': (c_size, [c_i64, c_i64]),
     'rdm_information_matrix': (c_int, [c_void, c_i64, c_i64, c_void, c_i64, c_i64, c_void, c_void, ctypes.c_double, ctypes.c_double,
                                        c_void, c_void, c_i64, c_void, c_size, c_void]),
+    'rdm_pose_graph_workspace_bytes': (c_size, [c_i64, c_i64, c_i64]),
+    'rdm_pose_graph_optimize': (c_int, [c_i64, c_void, c_void, c_void, c_void, c_void, c_void, c_void, ctypes.c_double, ctypes.c_double,
+                                        c_int, ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, c_void, c_void, c_void, c_void,
+                                        c_void, c_size, c_void]),
+    'rdm_pose_graph_edge_terms_host': (c_int, [c_void, c_void, c_void, c_void, ctypes.c_double, c_int, c_void]),
+    'rdm_pose_graph_retract_host': (c_int, [c_void, c_void, c_void]),
     'rdm_neighbor_histogram': (c_int, [c_void, c_i64, c_void, c_int, c_void]),
     'rdm_radius_grid_records': (c_void, [c_void, c_size, c_i64]),
     'rdm_row_positive': (c_int, [c_void, c_i64, c_i64, c_i64, c_void, c_void]),

@@ -916,6 +916,127 @@ def evaluate_registration(source, target, max_correspondence_distance, transform
     return res
 
 
+POSE_GRAPH_REPORT_WIDTH = 8  # per graph: initial cost, final cost, iterations, PCG iterations, stop reason, status, lambda, gradient
+POSE_GRAPH_STOP = {1: 'gradient', 2: 'cost', 3: 'max_iterations', 4: 'empty'}
+POSE_GRAPH_MAX_NODES, POSE_GRAPH_MAX_EDGES = 65536, 1048576  # per graph (rdm_pose_graph_optimize)
+
+
+class PoseGraphResult:
+    """What pose_graph_optimize returns.  nodes: float64 [N, 4, 4] and weights: float64 [E] (the line-process weights l_e at the
+    final poses; 1 for certain edges and without a line process) and pruned: bool [E] (uncertain edges with l_e <
+    edge_prune_threshold; they stay in the arrays), on the device the call ran on; per graph, as host numpy arrays [G]:
+    initial_cost, final_cost, iterations (accepted and rejected steps), pcg_iterations (in total), stop_reason (int: 1 the
+    gradient test, 2 the cost test, 3 max_iterations, 4 a graph without nodes or edges; stop_reasons has the names), damping
+    (the final lambda) and gradient_max (the largest gradient entry at the last linearisation)."""
+
+    def __init__(self, nodes, weights, pruned, report):
+        import numpy as np
+        self.nodes, self.weights, self.pruned = nodes, weights, pruned
+        rep = np.asarray(report, dtype=np.float64).reshape(-1, POSE_GRAPH_REPORT_WIDTH)
+        self.initial_cost, self.final_cost = rep[:, 0].copy(), rep[:, 1].copy()
+        self.iterations, self.pcg_iterations = rep[:, 2].astype(np.int64), rep[:, 3].astype(np.int64)
+        self.stop_reason = rep[:, 4].astype(np.int64)
+        self.stop_reasons = [POSE_GRAPH_STOP.get(int(v), 'none') for v in self.stop_reason]
+        self.damping, self.gradient_max = rep[:, 6].copy(), rep[:, 7].copy()
+
+
+def _pose_graph_connected(edges, node_offsets, edge_offsets):
+    """Union-find over every graph's edges: ValueError naming the first node that no path connects to its graph's node 0.
+    Edges whose ends are outside their graph are left to the library's own check.  Graphs without edges are returned as given
+    and are not checked."""
+    for g in range(len(node_offsets) - 1):
+        n, e0, e1 = int(node_offsets[g + 1] - node_offsets[g]), int(edge_offsets[g]), int(edge_offsets[g + 1])
+        if n == 0 or e1 == e0:
+            continue
+        parent = list(range(n))
+
+        def find(i):
+            while parent[i] != i:
+                parent[i] = parent[parent[i]]
+                i = parent[i]
+            return i
+
+        for s, t in edges[e0:e1].tolist():
+            if 0 <= s < n and 0 <= t < n:
+                a, b = find(s), find(t)
+                if a != b:
+                    parent[max(a, b)] = min(a, b)
+        for i in range(n):
+            if find(i) != 0:
+                raise ValueError(f'pose_graph_optimize: no path of edges connects node {i} of graph {g} to its node 0')
+
+
+def pose_graph_optimize(nodes, edges, transforms, informations, uncertain=None, *, line_process_weight=None,
+                        edge_prune_threshold=0.25, max_iterations=100, gradient_tolerance=1e-9, cost_tolerance=1e-12,
+                        graph_node_offsets=None, graph_edge_offsets=None, pcg_max_iterations=None, pcg_tolerance=1e-10):
+    """Pose-graph optimisation on the GPU (rdm_pose_graph_optimize; what Open3D's global_optimization does; parity unpinned,
+    the definition is DESIGN.md section 7, pinned to tests/pose_graph_restatement.py).  nodes float64 [N, 4, 4] (the pose of scan i
+    in the frame of its graph's node 0, which stays fixed), edges int64 [E, 2] rows (s, t) numbered inside their graph, transforms
+    float64 [E, 4, 4] (source-scan to target-scan coordinates -- a pair's estimated_transform with src = s, ref = t; the model is
+    X_s = X_t T), informations float64 [E, 6, 6] (rotation first, as ops.information_matrix), uncertain bool [E] (loop-closure
+    edges; None: none).  Tensors (device or host) or anything numpy holds.  A batch of graphs is concatenated, with
+    graph_node_offsets / graph_edge_offsets int64 [G + 1] (None: one graph).  line_process_weight None: every weight is 1;
+    mu > 0: uncertain edges carry l = (mu / (mu + r^T L r))^2.  pcg_max_iterations None: 60 (N - 1) + 64 of the largest graph (ten times the unknowns: in float64 the conjugate gradients
+    need a few times their exact-arithmetic count on these ill-conditioned systems; the tolerance ends them before; a graph of many
+    thousands of nodes spends that inside one kernel launch -- pass a cap of your own there).
+    -> PoseGraphResult.  ValueError for a node without a path to node 0; RuntimeError (the library's argument error, every output
+    untouched) for a self edge, an index outside its graph, a non-finite entry, an asymmetric information matrix, a graph above
+    65 536 nodes or 1 048 576 edges."""
+    import numpy as np
+    L = _lib.lib()
+    tensors = [t for t in (nodes, transforms, informations) if isinstance(t, torch.Tensor) and t.is_cuda]
+    dev = tensors[0].device if tensors else torch.device('cuda', torch.cuda.current_device())
+
+    def dev64(t, shape, name):
+        t = t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float64)))
+        t = t.detach().to(device=dev, dtype=torch.float64).contiguous()
+        if t.dim() != 3 or tuple(t.shape[1:]) != shape:
+            raise ValueError(f'pose_graph_optimize: {name} must be [*, {shape[0]}, {shape[1]}], got {tuple(t.shape)}')
+        return t
+
+    def host(t, dtype):
+        if t is None:
+            return None
+        if isinstance(t, torch.Tensor):
+            t = t.detach().cpu().numpy()
+        return np.ascontiguousarray(np.asarray(t).astype(dtype, copy=False))
+
+    X, T, Lm = dev64(nodes, (4, 4), 'nodes'), dev64(transforms, (4, 4), 'transforms'), dev64(informations, (6, 6), 'informations')
+    ed = host(edges, np.int64).reshape(-1, 2)
+    unc = host(uncertain, np.uint8)
+    n, e = X.shape[0], ed.shape[0]
+    if T.shape[0] != e or Lm.shape[0] != e or (unc is not None and unc.shape != (e,)):
+        raise ValueError('pose_graph_optimize: edges, transforms, informations and uncertain must have one row per edge')
+    if (graph_node_offsets is None) != (graph_edge_offsets is None):
+        raise ValueError('pose_graph_optimize: graph_node_offsets and graph_edge_offsets go together')
+    noff = np.array([0, n], np.int64) if graph_node_offsets is None else host(graph_node_offsets, np.int64)
+    eoff = np.array([0, e], np.int64) if graph_edge_offsets is None else host(graph_edge_offsets, np.int64)
+    if noff.ndim != 1 or noff.shape != eoff.shape or noff.shape[0] < 1 or noff[0] != 0 or eoff[0] != 0 or noff[-1] != n or eoff[-1] != e \
+            or np.any(np.diff(noff) < 0) or np.any(np.diff(eoff) < 0):
+        raise ValueError('pose_graph_optimize: offsets must be [G + 1], ascending, from 0 to the number of nodes / edges')
+    if line_process_weight is not None and not line_process_weight > 0:
+        raise ValueError(f'pose_graph_optimize: line_process_weight must be > 0 or None, got {line_process_weight}')
+    g = noff.shape[0] - 1
+    if g > 0 and np.diff(noff).max() <= POSE_GRAPH_MAX_NODES and np.diff(eoff).max() <= POSE_GRAPH_MAX_EDGES:
+        _pose_graph_connected(ed, noff, eoff)
+    if pcg_max_iterations is None:
+        pcg_max_iterations = 60 * max(int(np.diff(noff).max()) - 1 if g > 0 else 0, 0) + 64
+    out = torch.empty_like(X)
+    weights = torch.empty(e, dtype=torch.float64, device=dev)
+    pruned = torch.empty(e, dtype=torch.uint8, device=dev)
+    report = np.zeros((g, POSE_GRAPH_REPORT_WIDTH), np.float64)
+    with torch.cuda.device(dev):
+        ws = scratch(dev, L.rdm_pose_graph_workspace_bytes(g, n, e))
+        _lib.check(L.rdm_pose_graph_optimize(g, noff.ctypes.data, eoff.ctypes.data, _lib.ptr(X), ed.ctypes.data, _lib.ptr(T),
+                                             _lib.ptr(Lm), 0 if unc is None else unc.ctypes.data,
+                                             0.0 if line_process_weight is None else float(line_process_weight),
+                                             float(edge_prune_threshold), int(max_iterations), float(gradient_tolerance),
+                                             float(cost_tolerance), int(pcg_max_iterations), float(pcg_tolerance), _lib.ptr(out),
+                                             _lib.ptr(weights), _lib.ptr(pruned), report.ctypes.data, ws.data_ptr(), ws.numel(),
+                                             _lib.stream_ptr()), 'rdm_pose_graph_optimize')
+    return PoseGraphResult(out, weights, pruned.bool(), report)
+
+
 def _gt_check(t, name, shape, dtype, device):
     if not isinstance(t, torch.Tensor):
         raise RuntimeError(f'gt_node_correspondences: {name} must be a tensor')

@@ -1,0 +1,220 @@
+"""Trajectories of a run over a sequence: the reference's chaining and absolute trajectory error, and the pose graph of a run.
+
+    python -m rdmnet_amd.trajectory --features-root DIR [--optimize] [--line-process-weight MU] [--unit-information] [--out DIR]
+
+reads the `{seq}_{src}_{ref}.npz` pair files that `python -m rdmnet_amd.infer` wrote into DIR (ordered and filtered as
+`python -m rdmnet_amd.eval` reads them) and, per sequence, chains the pair poses into a trajectory as
+experiments/eval_pose_visualization_online.py:275-388 does (`cur_pose = cur_pose @ inv(est_transform)`), aligns it to the chained
+ground truth with Umeyama and prints the absolute trajectory error of :173-212.  A pair whose src frame is the previous chain
+pair's ref frame, and whose ref frame is new to the chain, continues the odometry chain (a certain edge of the pose graph; among
+several such pairs the first in file order); every other pair file of the sequence is an uncertain (loop-closure) edge between
+two frames of the chain.  With --optimize all sequences are optimised as one batch by
+`ops.pose_graph_optimize` and the report is printed for the optimised trajectory too.  Without --optimize no
+GPU is needed.  Everything here is numpy float64 on the host."""
+import argparse
+import math
+import os
+import os.path as osp
+import sys
+
+import numpy as np
+
+REFERENCE_KEYS = ('r_rmse', 'r_mean', 'rmse', 'mean')  # eval_absolute_error's dict, in its order
+
+
+def chain_poses(transforms):
+    """eval_pose_visualization_online.py:279,386-388: from the identity, cur_pose = cur_pose @ inv(est_transform) per pair, one
+    pose per pair (the identity itself is not part of the trajectory).  -> float64 [n, 4, 4]."""
+    cur = np.eye(4)
+    out = np.zeros((len(transforms), 4, 4))
+    for i, T in enumerate(transforms):
+        cur = np.matmul(cur, np.linalg.inv(np.asarray(T, dtype=np.float64)))
+        out[i] = cur
+    return out
+
+
+def umeyama_alignment(x, y, with_scale=False):
+    """eval_pose_visualization_online.py:120-171 (Umeyama 1991): x, y [m, n] point sets -> (r, t, c) with y ~ c r x + t."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    m, n = x.shape
+    mean_x, mean_y = x.mean(axis=1), y.mean(axis=1)
+    xc, yc = x - mean_x[:, None], y - mean_y[:, None]
+    sigma_x = 1.0 / n * (np.linalg.norm(xc) ** 2)
+    cov = np.zeros((m, m))
+    for i in range(n):  # (the reference adds the outer products one by one)
+        cov += np.outer(yc[:, i], xc[:, i])
+    cov = np.multiply(1.0 / n, cov)
+    u, d, v = np.linalg.svd(cov)
+    s = np.eye(m)
+    if np.linalg.det(u) * np.linalg.det(v) < 0.0:
+        s[m - 1, m - 1] = -1
+    r = u.dot(s).dot(v)
+    c = 1 / sigma_x * np.trace(np.diag(d).dot(s)) if with_scale else 1.0
+    t = mean_y - np.multiply(c, r.dot(mean_x))
+    return r, t, c
+
+
+def absolute_trajectory_error(traj, gt_traj):
+    """eval_absolute_error (eval_pose_visualization_online.py:173-212) with gt_traj_inv = inv(gt_traj) (:591): the trajectory's
+    positions are aligned to the ground truth's by umeyama_alignment (no scale), then per pose E = inv(gt) @ aligned.
+    -> dict with the reference's four keys, literally: 'mean' and 'rmse' = round(., 3) * 100 of the mean of |translation
+    component| over all 3 n components and of sqrt(sum of squared components / n) (centimetres); 'r_mean' = round(mean rotation
+    angle in degrees, 2); 'r_rmse' = round(sqrt(TRANSLATION mean square), 2) -- the reference computes the rotation mean
+    square and then takes the root of the translation's (:197-198).  Beside them: 'rotation_rmse_deg', the root of the rotation
+    mean square (rounded to 2 decimals), and 'unrounded': {'mean', 'rmse' (metres), 'r_mean', 'rotation_rmse_deg' (degrees),
+    'r_rmse' (the reference's quantity, = 'rmse')}."""
+    traj, gt_traj = np.asarray(traj, dtype=np.float64), np.asarray(gt_traj, dtype=np.float64)
+    r, t, _ = umeyama_alignment(traj[:, :3, 3].transpose((1, 0)), gt_traj[:, :3, 3].transpose((1, 0)))
+    T = np.eye(4)
+    T[:3, :3] = r
+    T[:3, 3] = t
+    err = np.matmul(np.linalg.inv(gt_traj), np.matmul(T, traj))
+    traj_error = np.abs(err[:, :3, 3])
+    mean = np.mean(traj_error)
+    mse = np.sum(traj_error ** 2) / len(traj_error)
+    rmse = np.sqrt(mse)
+    tr = err[:, 0, 0] + err[:, 1, 1] + err[:, 2, 2]
+    degrees = np.arccos(np.clip((tr - 1) / 2, -1, 1)) / math.pi * 180
+    r_mean = np.mean(degrees)
+    rot_rmse = np.sqrt(np.sum(degrees ** 2) / len(degrees))
+    return {'r_rmse': round(rmse, 2), 'r_mean': round(r_mean, 2), 'rmse': round(rmse, 3) * 100, 'mean': round(mean, 3) * 100,
+            'rotation_rmse_deg': round(rot_rmse, 2),
+            'unrounded': {'mean': float(mean), 'rmse': float(rmse), 'r_mean': float(r_mean), 'r_rmse': float(rmse),
+                          'rotation_rmse_deg': float(rot_rmse)}}
+
+
+# ---- the pose graph of a run ------------------------------------------------------------------------------------------------
+
+class TrajectoryError(Exception):
+    pass
+
+
+def read_sequences(features_root, unit_information=False):
+    """-> {seq: dict(frames [n + 1] (the chain's frames, first the first pair's src), chain [(file, T, gt, information)],
+    loops [(file, src, ref, T, information)])} in eval's file order."""
+    from . import eval as ev
+    _, todo = ev.list_pairs(features_root)
+    seqs = {}
+    for _, name, (seq, src, ref) in todo:
+        with np.load(name) as z:
+            T = np.asarray(z['estimated_transform'], dtype=np.float64)
+            gt = np.asarray(z['transform'], dtype=np.float64) if 'transform' in z.files else None
+            if unit_information:
+                info = np.eye(6)
+            elif 'information' in z.files:
+                info = np.asarray(z['information'], dtype=np.float64)
+            else:
+                raise TrajectoryError(f"{name} has no 'information': write it with `python -m rdmnet_amd.infer --information`, or "
+                                      "pass --unit-information")
+        s = seqs.setdefault(seq, dict(frames=[], chain=[], loops=[]))
+        if not s['chain'] or (src == s['frames'][-1] and ref not in s['frames']):
+            if not s['chain']:
+                s['frames'].append(src)
+            s['frames'].append(ref)
+            s['chain'].append((name, T, gt, info))
+        else:
+            s['loops'].append((name, src, ref, T, info))
+    for seq, s in seqs.items():
+        where = {f: i for i, f in reversed(list(enumerate(s['frames'])))}
+        for name, src, ref, _, _ in s['loops']:
+            for f in (src, ref):
+                if f not in where:
+                    raise TrajectoryError(f'{name}: frame {f} of sequence {seq} is not a frame of the odometry chain '
+                                          f"({s['frames'][0]} ... {s['frames'][-1]})")
+        s['where'] = where
+    return seqs
+
+
+def sequence_graph(s):
+    """Nodes 0 .. n: the chain's frames, node 0 the first pair's src at the identity, the others chained (X_ref = X_src inv(T));
+    edges (s = src node, t = ref node, T): first the chain's (certain), then the loops (uncertain).
+    -> (nodes, edges, transforms, informations, uncertain, the file name of every edge)."""
+    chained = chain_poses([T for _, T, _, _ in s['chain']])
+    nodes = np.concatenate([np.eye(4)[None], chained])
+    edges = [(i, i + 1) for i in range(len(s['chain']))] + [(s['where'][src], s['where'][ref]) for _, src, ref, _, _ in s['loops']]
+    transforms = [T for _, T, _, _ in s['chain']] + [T for _, _, _, T, _ in s['loops']]
+    infos = [L for _, _, _, L in s['chain']] + [L for _, _, _, _, L in s['loops']]
+    uncertain = [0] * len(s['chain']) + [1] * len(s['loops'])
+    names = [osp.basename(c[0]) for c in s['chain']] + [osp.basename(c[0]) for c in s['loops']]
+    keep = [k for k, (a, b) in enumerate(edges) if a != b]  # (a loop pair inside one frame constrains nothing)
+    pick = lambda v: [v[k] for k in keep]
+    return (nodes, np.asarray(pick(edges), np.int64).reshape(-1, 2), np.asarray(pick(transforms)).reshape(-1, 4, 4),
+            np.asarray(pick(infos)).reshape(-1, 6, 6), np.asarray(pick(uncertain), np.uint8), pick(names))
+
+
+def report_line(seq, what, err):
+    return f'seq {seq} {what}: ' + ', '.join(f'{k}: {err[k]}' for k in REFERENCE_KEYS) + f", rotation_rmse_deg: {err['rotation_rmse_deg']}"
+
+
+def write_kitti_poses(path, poses):
+    """One line per pose: the 12 entries of its first three rows.  The command line writes one pose per FRAME of the chain, the first
+    frame (the identity) included -- one line more than the reference's `traj` list, which the error report is computed on."""
+    with open(path, 'w') as f:
+        for X in poses:
+            f.write(' '.join(f'{v:.9e}' for v in np.asarray(X)[:3].reshape(-1)) + '\n')
+
+
+def run(args, emit=print):
+    seqs = read_sequences(args.features_root, args.unit_information)
+    graphs = {seq: sequence_graph(s) for seq, s in seqs.items()}
+    if args.out:
+        os.makedirs(args.out, exist_ok=True)
+    gts = {}
+    for seq, s in seqs.items():
+        traj = graphs[seq][0][1:]
+        if all(gt is not None for _, _, gt, _ in s['chain']):
+            gts[seq] = chain_poses([gt for _, _, gt, _ in s['chain']])
+            emit(report_line(seq, 'chained', absolute_trajectory_error(traj, gts[seq])))
+        else:
+            emit(f'seq {seq} chained: no ground truth in the pair files')
+        if args.out:
+            write_kitti_poses(osp.join(args.out, f'{seq}_chained.txt'), graphs[seq][0])
+    if not args.optimize:
+        return None
+    if not graphs:
+        raise TrajectoryError(f'{args.features_root}: no pair files to optimise')
+    from . import ops
+    order = list(graphs)
+    noff = np.cumsum([0] + [len(graphs[q][0]) for q in order])
+    eoff = np.cumsum([0] + [len(graphs[q][1]) for q in order])
+    cat = lambda k, shape: np.concatenate([graphs[q][k].reshape(shape) for q in order]) if order else np.zeros(shape[1:])
+    res = ops.pose_graph_optimize(cat(0, (-1, 4, 4)), cat(1, (-1, 2)), cat(2, (-1, 4, 4)), cat(3, (-1, 6, 6)), cat(4, (-1,)),
+                                  line_process_weight=args.line_process_weight, edge_prune_threshold=args.edge_prune_threshold,
+                                  max_iterations=args.max_iterations, graph_node_offsets=noff, graph_edge_offsets=eoff)
+    nodes, pruned = res.nodes.cpu().numpy(), res.pruned.cpu().numpy()
+    for g, seq in enumerate(order):
+        traj = nodes[noff[g] + 1:noff[g + 1]]
+        if seq in gts:
+            emit(report_line(seq, 'optimized', absolute_trajectory_error(traj, gts[seq])))
+        names = [graphs[seq][5][int(e)] for e in np.nonzero(pruned[eoff[g]:eoff[g + 1]])[0]]
+        emit(f'seq {seq} pose graph: {noff[g + 1] - noff[g]} nodes, {eoff[g + 1] - eoff[g]} edges, cost {res.initial_cost[g]:.6g} -> '
+             f'{res.final_cost[g]:.6g}, {res.iterations[g]} iterations ({res.stop_reasons[g]}), pruned edges: {names}')
+        if args.out:
+            write_kitti_poses(osp.join(args.out, f'{seq}_optimized.txt'), nodes[noff[g]:noff[g + 1]])
+    return res
+
+
+def make_parser():
+    ap = argparse.ArgumentParser(prog='python -m rdmnet_amd.trajectory', description=__doc__.split('\n\n')[0])
+    ap.add_argument('--features-root', '--features_root', required=True, help='directory of the {seq}_{src}_{ref}.npz pair files')
+    ap.add_argument('--optimize', action='store_true', help='optimise the pose graphs of all sequences on the GPU')
+    ap.add_argument('--line-process-weight', type=float, default=None, help='mu of the line process on the loop edges (default: none)')
+    ap.add_argument('--edge-prune-threshold', type=float, default=0.25)
+    ap.add_argument('--max-iterations', type=int, default=100)
+    ap.add_argument('--unit-information', action='store_true', help='use the identity as the information matrix of every pair (the files need no `information`)')
+    ap.add_argument('--out', default=None, help='directory for one KITTI-format pose file per sequence and variant')
+    return ap
+
+
+def main(argv=None):
+    args = make_parser().parse_args(argv)
+    if not osp.isdir(args.features_root):
+        sys.exit(f'{args.features_root}: not a directory')
+    try:
+        run(args)
+    except TrajectoryError as e:
+        sys.exit(str(e))
+
+
+if __name__ == '__main__':
+    main()
