@@ -257,8 +257,25 @@ int rdm_information_matrix(const float* q, int64_t n_q, int64_t ld_q, const floa
  * (4) a node block that is not positive definite (a node no edge reaches, an indefinite information matrix); the message names
  * the first graph whose status is not 0.  The host reads one word every 8 iterations.  The per-graph limits are nominal: the
  * block-Jacobi conjugate gradients need on the order of 10^4 iterations per step at 500 nodes (docs/EXPERIMENTS.md 5n), all inside one
- * launch of one workgroup; for graphs beyond a few thousand nodes choose pcg_max_iterations accordingly.                                                                                                   */
+ * launch of one workgroup; with block-Jacobi choose pcg_max_iterations accordingly for graphs beyond a few thousand nodes, or
+ * select the chain preconditioner below (7 to 17 times fewer iterations on drives with loop closures, each about 4 times as
+ * long at 500 nodes: 5o).
+ * The _pc forms take `preconditioner`: 0 block-Jacobi (what the plain forms forward, bit for bit), 1 the odometry chain, anything
+ * else RDM_ERR_ARG.  The chain preconditioner M is block tridiagonal over the free nodes 1 .. n - 1: diagonal blocks
+ * (1 + lambda) D_i (D_i the node block from all incident edges), block (i, i + 1) the sum of l A^T L B over the edges that join
+ * nodes i and i + 1 in ascending edge order (as is when the edge's source is i, transposed when it is i + 1); every other edge
+ * contributes to the diagonal only, so a graph without such pairs gets block-Jacobi again.  M is factored once per linearisation
+ * by a block Cholesky along the chain (a pivot that is not positive: status 4) and applied once per PCG iteration by two sweeps
+ * of one wavefront; the determinism guarantee above holds.  Only preconditioner 1 enlarges the workspace (36 doubles per node).
+ * Graphs whose system is far from its chain (a hub) gain nothing; the solution is the same within the tolerances.            */
 size_t rdm_pose_graph_workspace_bytes(int64_t n_graphs, int64_t n_nodes, int64_t n_edges);
+size_t rdm_pose_graph_workspace_bytes_pc(int64_t n_graphs, int64_t n_nodes, int64_t n_edges, int preconditioner);
+int rdm_pose_graph_optimize_pc(int64_t n_graphs, const int64_t* graph_node_offsets_host, const int64_t* graph_edge_offsets_host,
+                               const double* nodes, const int64_t* edges_host, const double* transforms, const double* informations,
+                               const uint8_t* uncertain_host, double line_process_weight, double edge_prune_threshold,
+                               int max_iterations, double gradient_tolerance, double cost_tolerance, int pcg_max_iterations,
+                               double pcg_tolerance, int preconditioner, double* nodes_out, double* weights_out,
+                               uint8_t* pruned_out, double* report_host, void* ws, size_t ws_bytes, void* stream);
 int rdm_pose_graph_optimize(int64_t n_graphs, const int64_t* graph_node_offsets_host, const int64_t* graph_edge_offsets_host,
                             const double* nodes, const int64_t* edges_host, const double* transforms, const double* informations,
                             const uint8_t* uncertain_host, double line_process_weight, double edge_prune_threshold,
@@ -272,6 +289,10 @@ int rdm_pose_graph_optimize(int64_t n_graphs, const int64_t* graph_node_offsets_
 int rdm_pose_graph_edge_terms_host(const double* source_pose, const double* target_pose, const double* transform,
                                    const double* information, double line_process_weight, int uncertain, double* out);
 int rdm_pose_graph_retract_host(const double* pose, const double* delta, double* out);
+/* The chain preconditioner's factor and apply functions, as the kernels run them, on the host (all pointers host memory): solves
+ * M out = rhs for the block tridiagonal M with diagonal blocks diag [n, 36] (row-major 6 x 6, the lower triangle is read) and
+ * blocks (i, i + 1) off [n - 1, 36]; rhs and out [n, 6].  RDM_ERR_ARG for a pivot that is not positive.                      */
+int rdm_pose_graph_chain_host(int64_t n, const double* diag, const double* off, const double* rhs, double* out);
 
 /* ---- dense contraction ---------------------------------------------------------------------
  * C[b] = act((A[b] (m x k) * op(B[b])) / rowdiv[row] + bias[col]) in fp32 on the f32 MFMA.

@@ -117,6 +117,11 @@ SIGNATURES = {
     'rdm_pose_graph_optimize': (c_int, [c_i64, c_void, c_void, c_void, c_void, c_void, c_void, c_void, ctypes.c_double, ctypes.c_double,
                                         c_int, ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, c_void, c_void, c_void, c_void,
                                         c_void, c_size, c_void]),
+    'rdm_pose_graph_workspace_bytes_pc': (c_size, [c_i64, c_i64, c_i64, c_int]),
+    'rdm_pose_graph_optimize_pc': (c_int, [c_i64, c_void, c_void, c_void, c_void, c_void, c_void, c_void, ctypes.c_double,
+                                           ctypes.c_double, c_int, ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, c_int,
+                                           c_void, c_void, c_void, c_void, c_void, c_size, c_void]),
+    'rdm_pose_graph_chain_host': (c_int, [c_i64, c_void, c_void, c_void, c_void]),
     'rdm_pose_graph_edge_terms_host': (c_int, [c_void, c_void, c_void, c_void, ctypes.c_double, c_int, c_void]),
     'rdm_pose_graph_retract_host': (c_int, [c_void, c_void, c_void]),
     'rdm_neighbor_histogram': (c_int, [c_void, c_i64, c_void, c_int, c_void]),

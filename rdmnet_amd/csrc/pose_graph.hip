@@ -9,7 +9,8 @@
 // alone, in any batch, at any position and from run to run.
 //
 // Per outer iteration the host launches a fixed sequence: pg_linearize_kernel (one thread per edge), pg_solve_kernel (one
-// workgroup per graph: block-Jacobi preconditioned conjugate gradients, matrix-free over the incidence lists), pg_update_kernel
+// workgroup per graph: conjugate gradients, matrix-free over the incidence lists, preconditioned by the node blocks (block-Jacobi,
+// the default) or, on request, by the exactly factored block tridiagonal part along the odometry chain), pg_update_kernel
 // (candidate poses), pg_cost_kernel (candidate cost terms), pg_step_kernel (accept / reject, damping, stopping tests) and
 // pg_commit_kernel.  All decisions are taken on the device; the host reads one word every kChunk iterations.
 #include "common.h"
@@ -420,15 +421,22 @@ __device__ __forceinline__ double block_max(double v, double* red) {
   return s;
 }
 
+__host__ __device__ __forceinline__ bool finite_value(double v) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return isfinite(v);
+#else
+  return std::isfinite(v);
+#endif
+}
 // In-place Cholesky of a symmetric 6 x 6 (lower triangle of a[36] is read and replaced by the factor).  false: not positive.
-__device__ __forceinline__ bool cholesky6(double* a) {
+__host__ __device__ __forceinline__ bool cholesky6(double* a) {
   bool ok = true;
 #pragma unroll
   for (int j = 0; j < 6; ++j) {
     double d = a[6 * j + j];
 #pragma unroll
     for (int k = 0; k < j; ++k) d -= a[6 * j + k] * a[6 * j + k];
-    if (!(d > 0.0) || !isfinite(d)) {
+    if (!(d > 0.0) || !finite_value(d)) {
       ok = false;
       d = 1.0;
     }
@@ -466,16 +474,214 @@ __device__ __forceinline__ void chol_solve6(const double* __restrict__ f, const 
   }
 }
 
-// One workgroup per graph: node blocks and gradient in incidence order, the gradient test, the damped block-Jacobi factors, then
-// preconditioned conjugate gradients on (H + lambda blockdiag(H)) x = -b with a matrix-free product.  A thread owns nodes tid,
-// tid + kBlock, ...; node 0 is fixed (its rows are left out: x_0 = 0).  D [N, 36], F [N, 21], b, x, r, z, pv, Ap [N, 6] are global.
+// ---- the odometry-chain preconditioner -----------------------------------------------------------------
+// M is block tridiagonal over the free nodes 1 .. n - 1: the damped node blocks on the diagonal, and between nodes i - 1 and i the
+// sum of the Hab blocks of the edges that join the two.  M = L L^T by a block Cholesky along the chain; kept per node are
+// G_i = L_ii^-1 (lower triangle, 21 values in row order, in the block-Jacobi factor's slot) and W_i = G_i L_{i,i-1} (6 x 6).
+// z = M^-1 r in four steps: c_i = G_i r_i (a thread per node), y_i = c_i - W_i y_{i-1} (forward sweep), q_i = y_i - W_{i+1}^T q_{i+1}
+// (backward sweep; q_i = L_ii^T z_i, so the same W serves both sweeps), z_i = G_i^T q_i (a thread per node).
+
+// One node of the factorisation.  d: the node's damped block (its lower triangle is read); m: M_{i,i-1}, or null at the chain's first
+// node; gp: G_{i-1}.  -> g = G_i and x = L_{i,i-1} = M_{i,i-1} G_{i-1}^T (zeros without m).  false: a pivot is not positive.
+__host__ __device__ __forceinline__ bool chain_factor_node(const double* d, const double* m, const double* gp, double* g, double* x) {
+  double s[36];
+#pragma unroll
+  for (int k = 0; k < 36; ++k) s[k] = d[k];
+  if (m != nullptr) {
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      double mr[6];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) mr[k] = m[6 * r + k];
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        double a = 0.0;
+#pragma unroll
+        for (int k = 0; k <= c; ++k) a += mr[k] * gp[c * (c + 1) / 2 + k];
+        x[6 * r + c] = a;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = 0; c <= r; ++c) {
+        double a = s[6 * r + c];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) a -= x[6 * r + k] * x[6 * c + k];
+        s[6 * r + c] = a;
+      }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 36; ++k) x[k] = 0.0;
+  }
+  const bool ok = cholesky6(s);
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {  // G = L^-1, column by column
+    g[j * (j + 1) / 2 + j] = 1.0 / s[6 * j + j];
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) {
+      double a = 0.0;
+#pragma unroll
+      for (int k = j; k < i; ++k) a += s[6 * i + k] * g[k * (k + 1) / 2 + j];
+      g[i * (i + 1) / 2 + j] = -a / s[6 * i + i];
+    }
+  }
+  return ok;
+}
+// w = G x (6 x 6; w may be x)
+__host__ __device__ __forceinline__ void chain_w(const double* g, const double* x, double* w) {
+  double t[36];
+#pragma unroll
+  for (int k = 0; k < 36; ++k) t[k] = x[k];
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+      double a = 0.0;
+#pragma unroll
+      for (int k = 0; k <= r; ++k) a += g[r * (r + 1) / 2 + k] * t[6 * k + c];
+      w[6 * r + c] = a;
+    }
+}
+// c = G r and z = G^T q
+__host__ __device__ __forceinline__ void chain_g_mul(const double* g, const double* r, double* c) {
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double a = 0.0;
+#pragma unroll
+    for (int k = 0; k <= i; ++k) a += g[i * (i + 1) / 2 + k] * r[k];
+    c[i] = a;
+  }
+}
+__host__ __device__ __forceinline__ void chain_gt_mul(const double* g, const double* q, double* z) {
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    double a = 0.0;
+#pragma unroll
+    for (int i = k; i < 6; ++i) a += g[i * (i + 1) / 2 + k] * q[i];
+    z[k] = a;
+  }
+}
+// One row of a sweep step: c - w . y, the six products added as three pairs (a short dependent chain, a fixed order).
+__host__ __device__ __forceinline__ double chain_row(double c, const double* w, const double* y) {
+  return c - (((w[0] * y[0] + w[1] * y[1]) + (w[2] * y[2] + w[3] * y[3])) + (w[4] * y[4] + w[5] * y[5]));
+}
+
+__device__ __forceinline__ double read_lane(double v, int lane) {  // lane: a constant
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+  return __hiloint2double(hi, lo);
+}
+
+// The two sweeps of one graph, in place on its rows of zv, by ONE wavefront (all 64 lanes call it).  Wg, zg: the graph's rows of
+// W [n, 36] and zv [n, 6].  Lane 8 k + r holds row r (sweep back: column r of the next node's W) of the k-th node of a group of
+// eight consecutive nodes; the eight steps of a group run one after the other, every lane evaluating chain_row and the step's
+// six lanes handing their results to all lanes through v_readlane (scalar registers: no LDS round trip on the dependent path);
+// the next group's rows are loaded before the current group's steps, so their latency lies under about eight steps.  A lane
+// reads back in the second sweep only what it wrote itself in the first.
+__device__ __forceinline__ void chain_sweeps(const double* __restrict__ Wg, double* __restrict__ zg, int n) {
+  const int lane = threadIdx.x & 63, k = lane >> 3, r = lane & 7;
+  const int m = n - 1, groups = (m + 7) >> 3;  // free nodes j = 0 .. m - 1 are the graph's nodes j + 1
+  if (groups == 0) return;
+  double w[6], c, wn[6], cn = 0.0, y[6];
+#pragma unroll
+  for (int q = 0; q < 6; ++q) y[q] = wn[q] = 0.0;
+  // (every lane loads from an address inside the graph, clamped, and lanes without a row take zeros when the group becomes the
+  // current one: no branch around the loads and no use of them before the steps they lie under)
+  const int rc = r < 6 ? r : 5;
+  auto load_forward = [&](int g, double* ww, double& cc) {
+    const int j = 8 * g + k;
+    const long long node = (j < m ? j : m - 1) + 1;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) ww[q] = Wg[36 * node + 6 * rc + q];
+    cc = zg[6 * node + rc];
+  };
+  auto load_backward = [&](int g, double* ww, double& cc) {
+    const int j = 8 * g + k;
+    const long long node = (j < m ? j : m - 1) + 1, next = node < m ? node + 1 : m;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) ww[q] = Wg[36 * next + 6 * q + rc];
+    cc = zg[6 * node + rc];
+  };
+  auto take = [&](int g, bool forward) {  // group g becomes the current one
+    const int j = 8 * g + k;
+    const bool on = r < 6 && j >= 0 && j < m, has_w = on && (forward || j + 1 < m);
+#pragma unroll
+    for (int q = 0; q < 6; ++q) w[q] = has_w ? wn[q] : 0.0;
+    c = on ? cn : 0.0;
+  };
+  auto steps = [&](bool forward) -> double {  // the eight nodes of a group; -> this lane's own entry
+    double mine = 0.0;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const int kk = forward ? s : 7 - s;
+      const double t = chain_row(c, w, y);
+      if (k == kk) mine = t;
+#pragma unroll
+      for (int q = 0; q < 6; ++q) y[q] = read_lane(t, 8 * kk + q);
+    }
+    return mine;
+  };
+  load_forward(0, wn, cn);
+  take(0, true);
+  for (int g = 0; g < groups; ++g) {
+    if (g + 1 < groups) load_forward(g + 1, wn, cn);
+    const double mine = steps(true);
+    const int j = 8 * g + k;
+    if (r < 6 && j < m) zg[6ll * (j + 1) + r] = mine;
+    take(g + 1, true);
+  }
+#pragma unroll
+  for (int q = 0; q < 6; ++q) y[q] = 0.0;
+  load_backward(groups - 1, wn, cn);
+  take(groups - 1, false);
+  for (int g = groups - 1; g >= 0; --g) {
+    if (g > 0) load_backward(g - 1, wn, cn);
+    const double mine = steps(false);
+    const int j = 8 * g + k;
+    if (r < 6 && j < m) zg[6ll * (j + 1) + r] = mine;
+    take(g - 1, false);
+  }
+}
+
+// The chain preconditioner after c_i = G_i r_i was written to zv by the nodes' threads: the sweeps, then z_i = G_i^T q_i into zv.
+// -> this thread's part of r^T z (its nodes in order).
+__device__ __forceinline__ double chain_finish(const double* __restrict__ F, const double* __restrict__ Wc, const double* rv,
+                                               double* zv, int n0, int n) {
+  __syncthreads();
+  if (threadIdx.x < kWave) chain_sweeps(Wc + 36ll * n0, zv + 6ll * n0, n);
+  __syncthreads();
+  double part = 0.0;
+  for (int i = threadIdx.x; i < n; i += kBlock) {
+    if (i == 0) continue;
+    const long long node = n0 + i;
+    double q[6], z[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) q[k] = zv[6 * node + k];
+    chain_gt_mul(F + 21 * node, q, z);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      zv[6 * node + k] = z[k];
+      part += rv[6 * node + k] * z[k];
+    }
+  }
+  return part;
+}
+
+enum : int { PRE_BLOCK_JACOBI = 0, PRE_CHAIN = 1 };
+
+// One workgroup per graph: node blocks and gradient in incidence order, the gradient test, the preconditioner's factors (kPre 0:
+// damped block-Jacobi; 1: the odometry chain, factored along the chain by thread 0 from blocks that 72 threads stage in LDS one
+// node ahead), then preconditioned conjugate gradients on (H + lambda blockdiag(H)) x = -b with a matrix-free product.  A thread
+// owns nodes tid, tid + kBlock, ...; node 0 is fixed (its rows are left out: x_0 = 0).  D [N, 36], F [N, 21], b, x, r, z, pv, Ap
+// [N, 6] are global, and so is Wc [N, 36] (kPre 1 only; else null).
+template <int kPre>
 __global__ __launch_bounds__(kBlock) void pg_solve_kernel(Graphs gr, Params p, GraphState* __restrict__ gs,
                                                           const double* __restrict__ Haa, const double* __restrict__ Hab,
                                                           const double* __restrict__ Hbb, const double* __restrict__ ga,
                                                           const double* __restrict__ gb, double* __restrict__ D,
                                                           double* __restrict__ F, double* __restrict__ bv, double* __restrict__ xv,
                                                           double* __restrict__ rv, double* __restrict__ zv, double* __restrict__ pv,
-                                                          const int* __restrict__ bad) {
+                                                          const int* __restrict__ bad, double* __restrict__ Wc) {
   __shared__ double red[kWaves];
   __shared__ int fail;
   const int g = blockIdx.x;
@@ -493,6 +699,11 @@ __global__ __launch_bounds__(kBlock) void pg_solve_kernel(Graphs gr, Params p, G
     for (int k = 0; k < 36; ++k) d[k] = 0.0;
 #pragma unroll
     for (int k = 0; k < 6; ++k) b[k] = 0.0;
+    [[maybe_unused]] double off[36];  // kPre 1: M_{i,i-1}, the edges that join this node and the one before it, in edge order
+    if constexpr (kPre == PRE_CHAIN) {
+#pragma unroll
+      for (int k = 0; k < 36; ++k) off[k] = 0.0;
+    }
     if (i > 0) {
       for (int q = gr.inc_off[node]; q < gr.inc_off[node + 1]; ++q) {
         const int code = gr.inc[q];
@@ -503,6 +714,21 @@ __global__ __launch_bounds__(kBlock) void pg_solve_kernel(Graphs gr, Params p, G
         for (int k = 0; k < 36; ++k) d[k] += H[k];
 #pragma unroll
         for (int k = 0; k < 6; ++k) b[k] += v[k];
+        if constexpr (kPre == PRE_CHAIN) {
+          const long long other = (code & 1) ? gr.es[e] : gr.et[e];
+          if (i > 1 && other == node - 1) {
+            const double* C = Hab + 36 * e;  // rows: the edge's source
+            if (code & 1) {
+#pragma unroll
+              for (int r = 0; r < 6; ++r)
+#pragma unroll
+                for (int c = 0; c < 6; ++c) off[6 * r + c] += C[6 * c + r];
+            } else {
+#pragma unroll
+              for (int k = 0; k < 36; ++k) off[k] += C[k];
+            }
+          }
+        }
       }
     }
 #pragma unroll
@@ -514,7 +740,10 @@ __global__ __launch_bounds__(kBlock) void pg_solve_kernel(Graphs gr, Params p, G
       xv[6 * node + k] = 0.0;
       rv[6 * node + k] = -b[k];
     }
-    if (i > 0) {
+    if constexpr (kPre == PRE_CHAIN) {
+#pragma unroll
+      for (int k = 0; k < 36; ++k) Wc[36 * node + k] = off[k];
+    } else if (i > 0) {
 #pragma unroll
       for (int k = 0; k < 36; ++k) d[k] *= 1.0 + lambda;
       if (!cholesky6(d)) fail = 1;
@@ -540,6 +769,43 @@ __global__ __launch_bounds__(kBlock) void pg_solve_kernel(Graphs gr, Params p, G
     }
     return;
   }
+  if constexpr (kPre == PRE_CHAIN) {
+    // the chain's factors: node after node by thread 0; threads 0 .. 71 fetch the next node's damped block and M_{i,i-1} meanwhile
+    __shared__ double stage[2][72];
+    const int t = threadIdx.x;
+    auto fetch = [&](int i) { return t < 36 ? (1.0 + lambda) * D[36ll * (n0 + i) + t] : Wc[36ll * (n0 + i) + t - 36]; };
+    if (t < 72 && n > 1) stage[0][t] = fetch(1);
+    double gp[21];
+#pragma unroll
+    for (int k = 0; k < 21; ++k) gp[k] = 0.0;
+    for (int i = 1; i < n; ++i) {
+      const int buf = (i - 1) & 1;
+      const bool more = t < 72 && i + 1 < n;
+      double next = 0.0;
+      if (more) next = fetch(i + 1);
+      __syncthreads();  // stage[buf] is written; stage[buf ^ 1] is read no more
+      if (t == 0) {
+        const long long node = n0 + i;
+        double gi[21], x[36];
+        if (!chain_factor_node(stage[buf], i > 1 ? stage[buf] + 36 : nullptr, gp, gi, x)) fail = 1;
+#pragma unroll
+        for (int k = 0; k < 21; ++k) F[21 * node + k] = gp[k] = gi[k];
+#pragma unroll
+        for (int k = 0; k < 36; ++k) Wc[36 * node + k] = x[k];
+      }
+      if (more) stage[buf ^ 1][t] = next;
+    }
+    __syncthreads();
+    if (fail) {
+      if (threadIdx.x == 0) {
+        gs[g].status = ST_SINGULAR;
+        gs[g].done = 1;
+      }
+      return;
+    }
+    for (int i = threadIdx.x; i < n; i += kBlock)
+      if (i > 1) chain_w(F + 21ll * (n0 + i), Wc + 36ll * (n0 + i), Wc + 36ll * (n0 + i));
+  }
   // 2. z = M^-1 r, pv = z, rz
   double part = 0.0;
   for (int i = threadIdx.x; i < n; i += kBlock) {
@@ -547,13 +813,25 @@ __global__ __launch_bounds__(kBlock) void pg_solve_kernel(Graphs gr, Params p, G
     double r[6], z[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int k = 0; k < 6; ++k) r[k] = rv[6 * node + k];
-    if (i > 0) chol_solve6(F + 21 * node, r, z);
+    if constexpr (kPre == PRE_CHAIN) {
+      if (i > 0) chain_g_mul(F + 21 * node, r, z);
+    } else {
+      if (i > 0) chol_solve6(F + 21 * node, r, z);
+    }
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
       zv[6 * node + k] = z[k];
-      pv[6 * node + k] = z[k];
-      if (i > 0) part += r[k] * z[k];
+      if constexpr (kPre != PRE_CHAIN) {
+        pv[6 * node + k] = z[k];
+        if (i > 0) part += r[k] * z[k];
+      }
     }
+  }
+  if constexpr (kPre == PRE_CHAIN) {
+    part = chain_finish(F, Wc, rv, zv, n0, n);
+    for (int i = threadIdx.x; i < n; i += kBlock)
+#pragma unroll
+      for (int k = 0; k < 6; ++k) pv[6ll * (n0 + i) + k] = zv[6ll * (n0 + i) + k];
   }
   double rz = block_sum(part, red);
   const double rz0 = rz;
@@ -620,13 +898,20 @@ __global__ __launch_bounds__(kBlock) void pg_solve_kernel(Graphs gr, Params p, G
         r[k] = rv[6 * node + k] - alpha * zv[6 * node + k];
         rv[6 * node + k] = r[k];
       }
-      if (i > 0) chol_solve6(F + 21 * node, r, z);
+      if constexpr (kPre == PRE_CHAIN) {
+        if (i > 0) chain_g_mul(F + 21 * node, r, z);
+      } else {
+        if (i > 0) chol_solve6(F + 21 * node, r, z);
+      }
 #pragma unroll
       for (int k = 0; k < 6; ++k) {
         zv[6 * node + k] = z[k];
-        if (i > 0) part += r[k] * z[k];
+        if constexpr (kPre != PRE_CHAIN) {
+          if (i > 0) part += r[k] * z[k];
+        }
       }
     }
+    if constexpr (kPre == PRE_CHAIN) part = chain_finish(F, Wc, rv, zv, n0, n);
     const double rz_new = block_sum(part, red);
     const double beta = rz_new / rz;
     rz = rz_new;
@@ -774,6 +1059,7 @@ struct Work {
   int* flags;  // bad, remaining, failed
   GraphState* gs;
   double *X, *Xc, *lw, *term, *Haa, *Hab, *Hbb, *ga, *gb, *D, *F, *bv, *xv, *rv, *zv, *pv, *report;
+  double* Wc;  // the chain preconditioner's [N, 36]; null without it
   size_t ints_bytes;  // the host-built integer tables are one upload: [node_off .. uncertain)
 };
 
@@ -791,7 +1077,7 @@ void carve_tables(Arena& ar, size_t G, size_t N, size_t E, Work& w) {
   w.ints_bytes = ar.off;
 }
 
-bool carve(Arena& ar, int64_t g, int64_t n, int64_t e, Work& w) {
+bool carve(Arena& ar, int64_t g, int64_t n, int64_t e, int preconditioner, Work& w) {
   const size_t G = static_cast<size_t>(g > 0 ? g : 1), N = static_cast<size_t>(n > 0 ? n : 1), E = static_cast<size_t>(e > 0 ? e : 1);
   carve_tables(ar, G, N, E, w);
   w.flags = ar.take<int>(4);
@@ -813,6 +1099,7 @@ bool carve(Arena& ar, int64_t g, int64_t n, int64_t e, Work& w) {
   w.zv = ar.take<double>(6 * N);
   w.pv = ar.take<double>(6 * N);
   w.report = ar.take<double>(kReport * G);
+  w.Wc = preconditioner == PRE_CHAIN ? ar.take<double>(36 * N) : nullptr;  // (last: the other slots lie where they lay)
   return ar.ok;
 }
 
@@ -840,12 +1127,56 @@ extern "C" int rdm_pose_graph_retract_host(const double* pose, const double* del
   return RDM_OK;
 }
 
-extern "C" size_t rdm_pose_graph_workspace_bytes(int64_t n_graphs, int64_t n_nodes, int64_t n_edges) {
+extern "C" int rdm_pose_graph_chain_host(int64_t n, const double* diag, const double* off, const double* rhs, double* out) {
+  using namespace rdm;
+  RDM_REQUIRE(n >= 0 && n < kMaxTotal, "rdm_pose_graph_chain_host: bad number of nodes");
+  if (n == 0) return RDM_OK;
+  RDM_REQUIRE(diag && rhs && out && (off || n == 1), "rdm_pose_graph_chain_host: null argument");
+  const size_t N = static_cast<size_t>(n);
+  std::vector<double> G(21 * N), W(36 * N), v(6 * N);
+  for (size_t i = 0; i < N; ++i) {
+    double m[36], x[36];
+    if (i > 0)  // M_{i,i-1} is the transpose of block (i - 1, i)
+      for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c) m[6 * r + c] = off[36 * (i - 1) + 6 * c + r];
+    if (!chain_factor_node(diag + 36 * i, i > 0 ? m : nullptr, i > 0 ? &G[21 * (i - 1)] : nullptr, &G[21 * i], x)) {
+      set_error("rdm_pose_graph_chain_host: the pivot of node %zu is not positive definite", i);
+      return RDM_ERR_ARG;
+    }
+    chain_w(&G[21 * i], x, &W[36 * i]);
+  }
+  double y[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (size_t i = 0; i < N; ++i) {  // c = G r, then the forward sweep
+    double c[6];
+    chain_g_mul(&G[21 * i], rhs + 6 * i, c);
+    for (int r = 0; r < 6; ++r) v[6 * i + r] = chain_row(c[r], &W[36 * i + 6 * r], y);
+    for (int r = 0; r < 6; ++r) y[r] = v[6 * i + r];
+  }
+  for (int r = 0; r < 6; ++r) y[r] = 0.0;
+  for (size_t i = N; i-- > 0;) {  // the backward sweep on q = L_ii^T z, then z = G^T q
+    double q[6];
+    for (int r = 0; r < 6; ++r) {
+      double col[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+      if (i + 1 < N)
+        for (int c = 0; c < 6; ++c) col[c] = W[36 * (i + 1) + 6 * c + r];
+      q[r] = chain_row(v[6 * i + r], col, y);
+    }
+    for (int r = 0; r < 6; ++r) y[r] = q[r];
+    chain_gt_mul(&G[21 * i], q, out + 6 * i);
+  }
+  return RDM_OK;
+}
+
+extern "C" size_t rdm_pose_graph_workspace_bytes_pc(int64_t n_graphs, int64_t n_nodes, int64_t n_edges, int preconditioner) {
   using namespace rdm;
   Arena ar(nullptr, 0);
   Work w;
-  carve(ar, n_graphs, n_nodes, n_edges, w);
+  carve(ar, n_graphs, n_nodes, n_edges, preconditioner, w);
   return ar.off;
+}
+
+extern "C" size_t rdm_pose_graph_workspace_bytes(int64_t n_graphs, int64_t n_nodes, int64_t n_edges) {
+  return rdm_pose_graph_workspace_bytes_pc(n_graphs, n_nodes, n_edges, 0);
 }
 
 extern "C" int rdm_pose_graph_optimize(int64_t n_graphs, const int64_t* graph_node_offsets_host,
@@ -855,8 +1186,23 @@ extern "C" int rdm_pose_graph_optimize(int64_t n_graphs, const int64_t* graph_no
                                        double gradient_tolerance, double cost_tolerance, int pcg_max_iterations, double pcg_tolerance,
                                        double* nodes_out, double* weights_out, uint8_t* pruned_out, double* report_host, void* ws,
                                        size_t ws_bytes, void* stream) {
+  return rdm_pose_graph_optimize_pc(n_graphs, graph_node_offsets_host, graph_edge_offsets_host, nodes, edges_host, transforms,
+                                    informations, uncertain_host, line_process_weight, edge_prune_threshold, max_iterations,
+                                    gradient_tolerance, cost_tolerance, pcg_max_iterations, pcg_tolerance, 0, nodes_out, weights_out,
+                                    pruned_out, report_host, ws, ws_bytes, stream);
+}
+
+extern "C" int rdm_pose_graph_optimize_pc(int64_t n_graphs, const int64_t* graph_node_offsets_host,
+                                          const int64_t* graph_edge_offsets_host, const double* nodes, const int64_t* edges_host,
+                                          const double* transforms, const double* informations, const uint8_t* uncertain_host,
+                                          double line_process_weight, double edge_prune_threshold, int max_iterations,
+                                          double gradient_tolerance, double cost_tolerance, int pcg_max_iterations,
+                                          double pcg_tolerance, int preconditioner, double* nodes_out, double* weights_out,
+                                          uint8_t* pruned_out, double* report_host, void* ws, size_t ws_bytes, void* stream) {
   using namespace rdm;
   const int64_t G = n_graphs;
+  RDM_REQUIRE(preconditioner == PRE_BLOCK_JACOBI || preconditioner == PRE_CHAIN,
+              "rdm_pose_graph_optimize: preconditioner %d (0: block-Jacobi, 1: the odometry chain)", preconditioner);
   RDM_REQUIRE(G >= 0 && G < kMaxTotal, "rdm_pose_graph_optimize: bad number of graphs");
   RDM_REQUIRE(G == 0 || (graph_node_offsets_host && graph_edge_offsets_host && report_host), "rdm_pose_graph_optimize: null argument");
   RDM_REQUIRE(max_iterations >= 0 && gradient_tolerance >= 0.0 && cost_tolerance >= 0.0 && pcg_max_iterations >= 0 &&
@@ -922,7 +1268,7 @@ extern "C" int rdm_pose_graph_optimize(int64_t n_graphs, const int64_t* graph_no
   hipStream_t st = static_cast<hipStream_t>(stream);
   Arena ar(ws, ws_bytes);
   Work w;
-  if (!carve(ar, G, N, E, w)) {
+  if (!carve(ar, G, N, E, preconditioner, w)) {
     set_error("rdm_pose_graph_optimize: workspace too small (%zu < %zu bytes)", ws_bytes, ar.off);
     return RDM_ERR_WORKSPACE;
   }
@@ -955,8 +1301,9 @@ extern "C" int rdm_pose_graph_optimize(int64_t n_graphs, const int64_t* graph_no
     for (; k < end; ++k) {
       hipLaunchKernelGGL(pg_linearize_kernel, dim3(blocks_for(E)), dim3(kBlock), 0, st, gr, e, w.X, transforms, informations, p, w.gs,
                          w.lw, w.Haa, w.Hab, w.Hbb, w.ga, w.gb, bad);
-      hipLaunchKernelGGL(pg_solve_kernel, dim3(static_cast<unsigned>(G)), dim3(kBlock), 0, st, gr, p, w.gs, w.Haa, w.Hab, w.Hbb, w.ga,
-                         w.gb, w.D, w.F, w.bv, w.xv, w.rv, w.zv, w.pv, bad);
+      hipLaunchKernelGGL(preconditioner == PRE_CHAIN ? pg_solve_kernel<PRE_CHAIN> : pg_solve_kernel<PRE_BLOCK_JACOBI>,
+                         dim3(static_cast<unsigned>(G)), dim3(kBlock), 0, st, gr, p, w.gs, w.Haa, w.Hab, w.Hbb, w.ga, w.gb, w.D, w.F, w.bv,
+                         w.xv, w.rv, w.zv, w.pv, bad, w.Wc);
       hipLaunchKernelGGL(pg_update_kernel, dim3(blocks_for(N)), dim3(kBlock), 0, st, gr, n, w.gs, w.X, w.xv, w.Xc, bad);
       hipLaunchKernelGGL(pg_cost_kernel, dim3(blocks_for(E)), dim3(kBlock), 0, st, gr, e, w.Xc, transforms, informations, p, w.gs, 0,
                          w.term, static_cast<double*>(nullptr), bad);

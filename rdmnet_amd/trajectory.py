@@ -1,6 +1,7 @@
 """Trajectories of a run over a sequence: the reference's chaining and absolute trajectory error, and the pose graph of a run.
 
     python -m rdmnet_amd.trajectory --features-root DIR [--optimize] [--line-process-weight MU] [--unit-information] [--out DIR]
+                                  [--preconditioner {block_jacobi,chain}]
 
 reads the `{seq}_{src}_{ref}.npz` pair files that `python -m rdmnet_amd.infer` wrote into DIR (ordered and filtered as
 `python -m rdmnet_amd.eval` reads them) and, per sequence, chains the pair poses into a trajectory as
@@ -9,7 +10,8 @@ ground truth with Umeyama and prints the absolute trajectory error of :173-212. 
 pair's ref frame, and whose ref frame is new to the chain, continues the odometry chain (a certain edge of the pose graph; among
 several such pairs the first in file order); every other pair file of the sequence is an uncertain (loop-closure) edge between
 two frames of the chain.  With --optimize all sequences are optimised as one batch by
-`ops.pose_graph_optimize` and the report is printed for the optimised trajectory too.  Without --optimize no
+`ops.pose_graph_optimize` (--preconditioner chain selects its odometry-chain preconditioner, which suits exactly
+these graphs) and the report is printed for the optimised trajectory too.  Without --optimize no
 GPU is needed.  Everything here is numpy float64 on the host."""
 import argparse
 import math
@@ -180,7 +182,8 @@ def run(args, emit=print):
     cat = lambda k, shape: np.concatenate([graphs[q][k].reshape(shape) for q in order]) if order else np.zeros(shape[1:])
     res = ops.pose_graph_optimize(cat(0, (-1, 4, 4)), cat(1, (-1, 2)), cat(2, (-1, 4, 4)), cat(3, (-1, 6, 6)), cat(4, (-1,)),
                                   line_process_weight=args.line_process_weight, edge_prune_threshold=args.edge_prune_threshold,
-                                  max_iterations=args.max_iterations, graph_node_offsets=noff, graph_edge_offsets=eoff)
+                                  max_iterations=args.max_iterations, graph_node_offsets=noff, graph_edge_offsets=eoff,
+                                  preconditioner=getattr(args, 'preconditioner', 'block_jacobi'))
     nodes, pruned = res.nodes.cpu().numpy(), res.pruned.cpu().numpy()
     for g, seq in enumerate(order):
         traj = nodes[noff[g] + 1:noff[g + 1]]
@@ -202,6 +205,8 @@ def make_parser():
     ap.add_argument('--edge-prune-threshold', type=float, default=0.25)
     ap.add_argument('--max-iterations', type=int, default=100)
     ap.add_argument('--unit-information', action='store_true', help='use the identity as the information matrix of every pair (the files need no `information`)')
+    ap.add_argument('--preconditioner', choices=('block_jacobi', 'chain'), default='block_jacobi',
+                    help='of the conjugate gradients inside --optimize: the node blocks, or the odometry chain factored exactly')
     ap.add_argument('--out', default=None, help='directory for one KITTI-format pose file per sequence and variant')
     return ap
 

@@ -3,9 +3,10 @@ odometry edges, noisy loop closures and a line process -- alone and as a batch o
 for comparison: the restatement's dense solve (tests/pose_graph_restatement.py, numpy on the threads OMP_NUM_THREADS gives it)
 and, where scipy is importable, the same damped Gauss-Newton iteration with a sparse direct solve (scipy.sparse.linalg.spsolve).
 
-  python tools/pose_graph_bench.py [--nodes 500] [--loops 40] [--batch 11] [--reps 3] [--cpu]
+  python tools/pose_graph_bench.py [--nodes 500] [--loops 40] [--batch 11] [--reps 3] [--cpu] [--preconditioner chain]
 Prints one JSON line: sizes, GPU ms per call (median; a call ends with its read-back), outer iterations, PCG iterations per outer
-iteration, and the host's ms per solve."""
+iteration, and the host's ms per solve.  --preconditioner (block_jacobi | chain) is passed to ops.pose_graph_optimize and named in
+the output; without the flag the call and the output are what they were."""
 import argparse
 import json
 import os
@@ -86,12 +87,17 @@ def main():
     ap.add_argument('--batch', type=int, default=11)
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--cpu', action='store_true', help='also time the host: the dense restatement and, with scipy, a sparse solve')
+    ap.add_argument('--preconditioner', choices=('block_jacobi', 'chain'), default=None)
     a = ap.parse_args()
     import torch
     from rdmnet_amd import ops
     import pose_graph_restatement as R
     graphs = [graph(a.nodes, a.loops, 40 + k) for k in range(a.batch)]
     out = {'nodes': a.nodes, 'edges': len(graphs[0]['edges']), 'batch': a.batch, 'line_process_weight': MU}
+    extra = {}
+    if a.preconditioner is not None:
+        out['preconditioner'] = a.preconditioner
+        extra['preconditioner'] = a.preconditioner
 
     def run(gs):
         noff = np.cumsum([0] + [len(g['nodes']) for g in gs])
@@ -99,7 +105,7 @@ def main():
         cat = {k: np.concatenate([g[k] for g in gs]) for k in ('nodes', 'edges', 'transforms', 'informations', 'uncertain')}
         dev = {k: torch.from_numpy(cat[k]).cuda() for k in ('nodes', 'transforms', 'informations')}
         call = lambda: ops.pose_graph_optimize(dev['nodes'], cat['edges'], dev['transforms'], dev['informations'], cat['uncertain'],
-                                               line_process_weight=MU, graph_node_offsets=noff, graph_edge_offsets=eoff, **TOL)
+                                               line_process_weight=MU, graph_node_offsets=noff, graph_edge_offsets=eoff, **TOL, **extra)
         res = call()  # warm-up (workspace, code objects)
         torch.cuda.synchronize()
         times = []
