@@ -293,6 +293,42 @@ int rdm_pose_graph_retract_host(const double* pose, const double* delta, double*
  * M out = rhs for the block tridiagonal M with diagonal blocks diag [n, 36] (row-major 6 x 6, the lower triangle is read) and
  * blocks (i, i + 1) off [n - 1, 36]; rhs and out [n, 6].  RDM_ERR_ARG for a pivot that is not positive.                      */
 int rdm_pose_graph_chain_host(int64_t n, const double* diag, const double* off, const double* rhs, double* out);
+/* The _ls forms take `linear_solver` after `preconditioner`: 0 conjugate gradients with that preconditioner (what the _pc forms
+ * forward, bit for bit), 1 the direct sparse solve (then `preconditioner`, pcg_max_iterations and pcg_tolerance are ignored and
+ * report entry 3 is 0), anything else RDM_ERR_ARG.  The direct solve suits a chain with loop closures: an
+ * edge is off-chain when both ends are free and more than one node apart (several between the same two nodes count once); the
+ * separator S is a vertex cover of the off-chain pairs chosen by one rule -- repeatedly the node with the most uncovered pairs,
+ * the lowest number among equals -- and kept ascending; the free nodes outside S fall into runs of consecutive numbers, block
+ * tridiagonal and uncoupled.  With A_II = L L^T along the runs: Y = L^-1 A_IS (a column block is stored from its first coupling
+ * position to its run's end), C = A_SS - Y^T Y = L_S L_S^T dense in 6 x 6 blocks, y = L^-1 r_I, x_S = C^-1 (r_S - Y^T y),
+ * x_I = L^-T (y - Y x_S).  A pivot that is not positive, in a run or in C, is status 4.  Every sum runs in an order the graph
+ * alone decides (ascending edge, node, separator index, block column), so the determinism guarantee holds.  A graph may have at
+ * most rdm_pose_graph_direct_max_separator() (256) separator nodes; above it the call is RDM_ERR_ARG, the message names the
+ * graph, the count and the limit, every output is untouched, and nothing falls back to conjugate gradients.  The direct solve's
+ * workspace depends on the structure (the separator sizes squared and the stored part of Y), so
+ * rdm_pose_graph_workspace_bytes_ls reads the edges and returns the exact size; 0 with rdm_last_error set for a graph above the
+ * limit or bad arguments; with linear_solver 0 what rdm_pose_graph_workspace_bytes_pc returns.                                  */
+size_t rdm_pose_graph_workspace_bytes_ls(int64_t n_graphs, const int64_t* graph_node_offsets_host,
+                                         const int64_t* graph_edge_offsets_host, const int64_t* edges_host, int preconditioner,
+                                         int linear_solver);
+int rdm_pose_graph_optimize_ls(int64_t n_graphs, const int64_t* graph_node_offsets_host, const int64_t* graph_edge_offsets_host,
+                               const double* nodes, const int64_t* edges_host, const double* transforms, const double* informations,
+                               const uint8_t* uncertain_host, double line_process_weight, double edge_prune_threshold,
+                               int max_iterations, double gradient_tolerance, double cost_tolerance, int pcg_max_iterations,
+                               double pcg_tolerance, int preconditioner, int linear_solver, double* nodes_out, double* weights_out,
+                               uint8_t* pruned_out, double* report_host, void* ws, size_t ws_bytes, void* stream);
+int rdm_pose_graph_direct_max_separator(void);
+/* |S| of one graph under the rule above (host only); the nodes go to out_nodes in ascending order, never past `capacity`
+ * (out_nodes may be null with capacity 0).  -1 for an edge outside the graph or a self edge.                                  */
+int64_t rdm_pose_graph_separator_host(int64_t n_nodes, int64_t n_edges, const int64_t* edges_host, int64_t* out_nodes,
+                                      int64_t capacity);
+/* The direct solve's factor, border, Schur and solve functions, as the kernels run them and in their order, on the host (all
+ * pointers host memory): solves the system with diagonal block i = diag[i] ([n_nodes, 36], the lower triangle is read) and, per
+ * edge e = (s, t), off[e] ([n_edges, 36]) added to block (s, t) with its rows belonging to s, its transpose to (t, s); rhs and
+ * out [n_nodes, 6].  Row 0 and edges that touch node 0 are ignored and out[0] = 0.  RDM_ERR_ARG ("not positive") for a failed
+ * pivot and for a separator above the limit.                                                                                   */
+int rdm_pose_graph_direct_host(int64_t n_nodes, int64_t n_edges, const int64_t* edges_host, const double* diag, const double* off,
+                               const double* rhs, double* out);
 
 /* ---- dense contraction ---------------------------------------------------------------------
  * C[b] = act((A[b] (m x k) * op(B[b])) / rowdiv[row] + bias[col]) in fp32 on the f32 MFMA.

@@ -10,13 +10,20 @@
 //
 // Per outer iteration the host launches a fixed sequence: pg_linearize_kernel (one thread per edge), pg_solve_kernel (one
 // workgroup per graph: conjugate gradients, matrix-free over the incidence lists, preconditioned by the node blocks (block-Jacobi,
-// the default) or, on request, by the exactly factored block tridiagonal part along the odometry chain), pg_update_kernel
+// the default) or, on request, by the exactly factored block tridiagonal part along the odometry chain; or, with the direct solve
+// selected, in its place pg_direct_blocks / _factor / _border / _schur / _solve_kernel: a separator of the loop closures is taken out,
+// the chain's runs between its nodes are factored exactly and the separator's dense Schur complement is factored in 6 x 6 blocks),
+// pg_update_kernel
 // (candidate poses), pg_cost_kernel (candidate cost terms), pg_step_kernel (accept / reject, damping, stopping tests) and
 // pg_commit_kernel.  All decisions are taken on the device; the host reads one word every kChunk iterations.
 #include "common.h"
 #include "../../include/rdmnet_hip.h"
 
+#include <algorithm>
 #include <cmath>
+#include <cstring>
+#include <set>
+#include <utility>
 #include <vector>
 
 namespace rdm {
@@ -668,6 +675,7 @@ __device__ __forceinline__ double chain_finish(const double* __restrict__ F, con
 }
 
 enum : int { PRE_BLOCK_JACOBI = 0, PRE_CHAIN = 1 };
+enum : int { SOLVER_PCG = 0, SOLVER_DIRECT = 1 };
 
 // One workgroup per graph: node blocks and gradient in incidence order, the gradient test, the preconditioner's factors (kPre 0:
 // damped block-Jacobi; 1: the odometry chain, factored along the chain by thread 0 from blocks that 72 threads stage in LDS one
@@ -926,6 +934,492 @@ __global__ __launch_bounds__(kBlock) void pg_solve_kernel(Graphs gr, Params p, G
   if (threadIdx.x == 0) gs[g].pcg_total += it;
 }
 
+// ---- the direct solve ----------------------------------------------------------------------------------
+// The same system without conjugate gradients.  A separator S (a vertex cover of the off-chain edges, chosen by the host) is taken
+// out; what is left falls into runs of consecutive nodes that are block tridiagonal and do not couple.  With A_II = L L^T along the
+// runs (chain_factor_node): Y = L^-1 A_IS, C = A_SS - Y^T Y = L_S L_S^T (dense, in 6 x 6 blocks), y = L^-1 r_I,
+// x_S = C^-1 (r_S - Y^T y), x_I = L^-T (y - Y x_S).  The functions below are one work item each and are compiled for the device
+// (the kernels map threads to items) and for the host (rdm_pose_graph_direct_host runs the items in order).
+constexpr int kMaxSeparator = 256;  // separator nodes per graph: the dense factor is [6 kMaxSeparator]^2
+
+struct Direct {             // the host-built plan of a call (global node, separator, run and coupling numbers) and its arrays
+  const int* sep_off;       // [G + 1] a graph's separator nodes
+  const int* sep_node;      // [S] ascending inside a graph
+  const int* run_off;       // [G + 1] a graph's runs
+  const int* run_begin;     // [R] first node
+  const int* run_len;       // [R]
+  const int* run_graph;     // [R]
+  const int* cpl_off;       // [R + 1] a run's couplings (run, separator node), ascending separator
+  const int* cpl_sep;       // [K]
+  const int* cpl_run;       // [K]
+  const int* cpl_pos;       // [K] first position of the run that an edge joins to the separator node
+  const int* cpl_y;         // [K] first 6 x 6 block of the coupling's part of Y (positions cpl_pos .. the run's end)
+  const int* ent_off;       // [K + 1] a coupling's edges, by position, then ascending
+  const int* ent_pos;       // [A]
+  const int* ent_code;      // [A] 2 * edge + side of the separator node (0: it is the source)
+  const int* sc_off;        // [S + 1] a separator node's couplings, ascending run
+  const int* sc;            // [K]
+  const long long* c_off;   // [G + 1] a graph's first block of C ([s, s] blocks, row-major; the lower triangle is used)
+  const long long* item_off;  // [G + 1] a graph's Schur items: s * s blocks and s right-hand sides
+  double* C;
+  double* Y;
+  int* fail;                // [G] a pivot was not positive
+};
+
+struct DirectSystem {       // the system: D, Hab and the incidence lists give A; rv the right-hand side
+  const int *es, *et, *inc_off, *inc;
+  const double *D, *Hab, *rv;
+  double *F, *Wc, *zv, *xv;  // G [N, 21], W [N, 36] (on entry: the chain's off-diagonal sums), y [N, 6], x [N, 6]
+};
+
+// M_{node, node-1}: the sum of the blocks of the edges that join the two, in edge order (rows: node).
+__host__ __device__ __forceinline__ void chain_off_block(const int* __restrict__ es, const int* __restrict__ et,
+                                                         const int* __restrict__ inc_off, const int* __restrict__ inc,
+                                                         const double* __restrict__ Hab, long long node, double* off) {
+#pragma unroll
+  for (int k = 0; k < 36; ++k) off[k] = 0.0;
+  for (int q = inc_off[node]; q < inc_off[node + 1]; ++q) {
+    const int code = inc[q];
+    const long long e = code >> 1;
+    const long long other = (code & 1) ? es[e] : et[e];
+    if (other != node - 1) continue;
+    const double* C = Hab + 36 * e;  // rows: the edge's source
+    if (code & 1) {
+#pragma unroll
+      for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) off[6 * r + c] += C[6 * c + r];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 36; ++k) off[k] += C[k];
+    }
+  }
+}
+
+// One run: the factors G_i and W_i = G_i L_{i,i-1} along it, and y = L^-1 r on its rows of zv.  false: a pivot is not positive.
+__host__ __device__ inline bool direct_run_factor(const Direct& dp, const DirectSystem& sy, double dscale, int run) {
+  const long long first = dp.run_begin[run];
+  const int len = dp.run_len[run];
+  bool ok = true;
+  double gp[21], y[6];
+#pragma unroll
+  for (int k = 0; k < 21; ++k) gp[k] = 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) y[k] = 0.0;
+  for (int i = 0; i < len; ++i) {
+    const long long node = first + i;
+    double d[36], m[36], gi[21], x[36];
+#pragma unroll
+    for (int k = 0; k < 36; ++k) {
+      d[k] = dscale * sy.D[36 * node + k];
+      m[k] = sy.Wc[36 * node + k];
+    }
+    if (!chain_factor_node(d, i > 0 ? m : nullptr, gp, gi, x)) ok = false;
+    chain_w(gi, x, x);
+    double r[6], c[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) r[k] = sy.rv[6 * node + k];
+    chain_g_mul(gi, r, c);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) r[k] = chain_row(c[k], x + 6 * k, y);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) sy.zv[6 * node + k] = y[k] = r[k];
+#pragma unroll
+    for (int k = 0; k < 21; ++k) sy.F[21 * node + k] = gp[k] = gi[k];
+#pragma unroll
+    for (int k = 0; k < 36; ++k) sy.Wc[36 * node + k] = x[k];
+  }
+  return ok;
+}
+
+// One column (of the separator node's six) of one coupling: the run's forward sweep from the coupling's first position.
+__host__ __device__ inline void direct_border_column(const Direct& dp, const DirectSystem& sy, int cpl, int col) {
+  const int run = dp.cpl_run[cpl], p = dp.cpl_pos[cpl], len = dp.run_len[run];
+  const long long first = dp.run_begin[run];
+  double* Yc = dp.Y + 36ll * dp.cpl_y[cpl];
+  int q = dp.ent_off[cpl];
+  const int qe = dp.ent_off[cpl + 1];
+  double y[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) y[k] = 0.0;
+  for (int pos = p; pos < len; ++pos) {
+    const long long node = first + pos;
+    double a[6], c[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) a[k] = 0.0;
+    for (; q < qe && dp.ent_pos[q] == pos; ++q) {  // block (node, separator node) of A, this column
+      const int code = dp.ent_code[q];
+      const double* H = sy.Hab + 36ll * (code >> 1);
+      if (code & 1) {  // the separator node is the target: the rows of Hab are this node's
+#pragma unroll
+        for (int r = 0; r < 6; ++r) a[r] += H[6 * r + col];
+      } else {
+#pragma unroll
+        for (int r = 0; r < 6; ++r) a[r] += H[6 * col + r];
+      }
+    }
+    chain_g_mul(sy.F + 21 * node, a, c);
+#pragma unroll
+    for (int r = 0; r < 6; ++r) a[r] = chain_row(c[r], sy.Wc + 36 * node + 6 * r, y);
+#pragma unroll
+    for (int r = 0; r < 6; ++r) Yc[36ll * (pos - p) + 6 * r + col] = y[r] = a[r];
+  }
+}
+
+// Block (u, v), v <= u, of C = A_SS - Y^T Y of graph g (s separator nodes): the nodes' own block or the edges that join them in
+// edge order, then the runs both touch in ascending order, every position both columns cover, one position after the other.
+__host__ __device__ inline void direct_schur_block(const Direct& dp, const DirectSystem& sy, double dscale, int g, int s, int u, int v) {
+  const int su = dp.sep_off[g] + u, sv = dp.sep_off[g] + v;
+  const long long a = dp.sep_node[su], b = dp.sep_node[sv];
+  double acc[36];
+  if (u == v) {
+#pragma unroll
+    for (int k = 0; k < 36; ++k) acc[k] = dscale * sy.D[36 * a + k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 36; ++k) acc[k] = 0.0;
+    for (int q = sy.inc_off[a]; q < sy.inc_off[a + 1]; ++q) {
+      const int code = sy.inc[q];
+      const long long e = code >> 1;
+      if (((code & 1) ? sy.es[e] : sy.et[e]) != b) continue;
+      const double* H = sy.Hab + 36 * e;
+      if (code & 1) {
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+          for (int c = 0; c < 6; ++c) acc[6 * r + c] += H[6 * c + r];
+      } else {
+#pragma unroll
+        for (int k = 0; k < 36; ++k) acc[k] += H[k];
+      }
+    }
+  }
+  int i = dp.sc_off[su], j = dp.sc_off[sv];
+  const int ie = dp.sc_off[su + 1], je = dp.sc_off[sv + 1];
+  while (i < ie && j < je) {
+    const int ci = dp.sc[i], cj = dp.sc[j], ri = dp.cpl_run[ci], rj = dp.cpl_run[cj];
+    if (ri < rj) {
+      ++i;
+    } else if (rj < ri) {
+      ++j;
+    } else {
+      const int pi = dp.cpl_pos[ci], pj = dp.cpl_pos[cj], p = pi > pj ? pi : pj, len = dp.run_len[ri];
+      const double* Yu = dp.Y + 36ll * (dp.cpl_y[ci] + (p - pi));
+      const double* Yv = dp.Y + 36ll * (dp.cpl_y[cj] + (p - pj));
+      for (int pos = p; pos < len; ++pos, Yu += 36, Yv += 36) {
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+          for (int c = 0; c < 6; ++c) {
+            double t = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) t += Yu[6 * k + r] * Yv[6 * k + c];
+            acc[6 * r + c] -= t;
+          }
+      }
+      ++i;
+      ++j;
+    }
+  }
+  double* out = dp.C + 36ll * (dp.c_off[g] + static_cast<long long>(u) * s + v);
+#pragma unroll
+  for (int k = 0; k < 36; ++k) out[k] = acc[k];
+}
+
+// Rows u of r_S - Y^T y, into the separator node's rows of xv.
+__host__ __device__ inline void direct_schur_rhs(const Direct& dp, const DirectSystem& sy, int g, int u) {
+  const int su = dp.sep_off[g] + u;
+  const long long a = dp.sep_node[su];
+  double acc[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) acc[k] = sy.rv[6 * a + k];
+  for (int i = dp.sc_off[su]; i < dp.sc_off[su + 1]; ++i) {
+    const int c = dp.sc[i], run = dp.cpl_run[c], p = dp.cpl_pos[c], len = dp.run_len[run];
+    const double* Yu = dp.Y + 36ll * dp.cpl_y[c];
+    const double* y = sy.zv + 6ll * (dp.run_begin[run] + p);
+    for (int pos = p; pos < len; ++pos, Yu += 36, y += 6) {
+#pragma unroll
+      for (int r = 0; r < 6; ++r) {
+        double t = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) t += Yu[6 * k + r] * y[k];
+        acc[r] -= t;
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) sy.xv[6 * a + k] = acc[k];
+}
+
+// The dense factor's three block operations (right-looking, column k): the pivot is cholesky6; a panel block B <- B L_kk^-T; a
+// trailing block C_ij <- C_ij - L_ik L_jk^T.  A block of C sees its updates in ascending k, whoever applies them.
+__host__ __device__ __forceinline__ void dense_panel_block(const double* l, double* b) {
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+      double v = b[6 * r + c];
+#pragma unroll
+      for (int k = 0; k < c; ++k) v -= b[6 * r + k] * l[6 * c + k];
+      b[6 * r + c] = v / l[6 * c + c];
+    }
+}
+__host__ __device__ __forceinline__ void dense_trailing_block(const double* __restrict__ li, const double* __restrict__ lj, double* c) {
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+      double t = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) t += li[6 * r + k] * lj[6 * q + k];
+      c[6 * r + q] -= t;
+    }
+}
+// z <- L^-1 z and z <- L^-T z with the lower triangle of a 6 x 6 block; r <- r - B z and r <- r - B^T z
+__host__ __device__ __forceinline__ void dense_lower_solve(const double* l, double* z) {
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double v = z[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) v -= l[6 * i + k] * z[k];
+    z[i] = v / l[6 * i + i];
+  }
+}
+__host__ __device__ __forceinline__ void dense_upper_solve(const double* l, double* z) {
+#pragma unroll
+  for (int i = 5; i >= 0; --i) {
+    double v = z[i];
+#pragma unroll
+    for (int k = i + 1; k < 6; ++k) v -= l[6 * k + i] * z[k];
+    z[i] = v / l[6 * i + i];
+  }
+}
+__host__ __device__ __forceinline__ void dense_sub_mul(const double* b, const double* z, double* r, bool transposed) {
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double t = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) t += (transposed ? b[6 * k + i] : b[6 * i + k]) * z[k];
+    r[i] -= t;
+  }
+}
+
+// One run, backwards: x_I = L^-T (y - Y x_S) into its rows of xv; the separator nodes' rows of xv hold x_S.  A position's couplings
+// are taken in ascending separator order.
+__host__ __device__ inline void direct_run_back(const Direct& dp, const DirectSystem& sy, int run) {
+  const long long first = dp.run_begin[run];
+  const int len = dp.run_len[run];
+  double y[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) y[k] = 0.0;
+  for (int pos = len - 1; pos >= 0; --pos) {
+    const long long node = first + pos;
+    double t[6], q[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) t[k] = sy.zv[6 * node + k];
+    for (int c = dp.cpl_off[run]; c < dp.cpl_off[run + 1]; ++c) {
+      const int p = dp.cpl_pos[c];
+      if (pos < p) continue;
+      dense_sub_mul(dp.Y + 36ll * (dp.cpl_y[c] + (pos - p)), sy.xv + 6ll * dp.sep_node[dp.cpl_sep[c]], t, false);
+    }
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      double col[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+      if (pos + 1 < len) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) col[c] = sy.Wc[36 * (node + 1) + 6 * c + r];
+      }
+      q[r] = chain_row(t[r], col, y);
+    }
+#pragma unroll
+    for (int r = 0; r < 6; ++r) y[r] = q[r];
+    chain_gt_mul(sy.F + 21 * node, q, t);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) sy.xv[6 * node + k] = t[k];
+  }
+}
+
+// One workgroup per graph: what phase 1 of pg_solve_kernel<PRE_CHAIN> leaves -- node blocks D, gradient b, x = 0, r = -b, the
+// chain's off-diagonal sums in Wc, the gradient test -- in the same order of sums.
+__global__ __launch_bounds__(kBlock) void pg_direct_blocks_kernel(Graphs gr, Params p, GraphState* __restrict__ gs,
+                                                                  const double* __restrict__ Haa, const double* __restrict__ Hab,
+                                                                  const double* __restrict__ Hbb, const double* __restrict__ ga,
+                                                                  const double* __restrict__ gb, double* __restrict__ D,
+                                                                  double* __restrict__ bv, double* __restrict__ xv,
+                                                                  double* __restrict__ rv, double* __restrict__ Wc,
+                                                                  int* __restrict__ fail, const int* __restrict__ bad) {
+  __shared__ double red[kWaves];
+  const int g = blockIdx.x;
+  if (*bad != 0 || gs[g].done) return;  // (uniform over the workgroup)
+  const int n0 = gr.node_off[g], n = gr.node_off[g + 1] - n0;
+  if (threadIdx.x == 0) fail[g] = 0;
+  double gmax = 0.0;
+  for (int i = threadIdx.x; i < n; i += kBlock) {
+    const long long node = n0 + i;
+    double d[36], b[6];
+#pragma unroll
+    for (int k = 0; k < 36; ++k) d[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) b[k] = 0.0;
+    if (i > 0) {
+      for (int q = gr.inc_off[node]; q < gr.inc_off[node + 1]; ++q) {
+        const int code = gr.inc[q];
+        const long long e = code >> 1;
+        const double* H = (code & 1) ? Hbb + 36 * e : Haa + 36 * e;
+        const double* v = (code & 1) ? gb + 6 * e : ga + 6 * e;
+#pragma unroll
+        for (int k = 0; k < 36; ++k) d[k] += H[k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) b[k] += v[k];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 36; ++k) D[36 * node + k] = d[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      bv[6 * node + k] = b[k];
+      gmax = fmax(gmax, fabs(2.0 * b[k]));  // the gradient of F is 2 b
+      xv[6 * node + k] = 0.0;
+      rv[6 * node + k] = -b[k];
+    }
+    if (i > 1) {
+      chain_off_block(gr.es, gr.et, gr.inc_off, gr.inc, Hab, node, d);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 36; ++k) d[k] = 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 36; ++k) Wc[36 * node + k] = d[k];
+  }
+  gmax = block_max(gmax, red);
+  if (threadIdx.x == 0) {
+    gs[g].grad_max = gmax;
+    if (gmax <= p.gtol) {
+      gs[g].stop = STOP_GRADIENT;
+      gs[g].done = 1;
+    }
+  }
+}
+
+// One thread per run of the call.
+__global__ __launch_bounds__(kWave) void pg_direct_factor_kernel(Direct dp, DirectSystem sy, int runs, const GraphState* __restrict__ gs,
+                                                                 const int* __restrict__ bad) {
+  const int run = blockIdx.x * kWave + threadIdx.x;
+  if (run >= runs || *bad != 0) return;
+  const int g = dp.run_graph[run];
+  if (gs[g].done) return;
+  if (!direct_run_factor(dp, sy, 1.0 + gs[g].lambda, run)) dp.fail[g] = 1;  // (every writer writes 1)
+}
+
+// One thread per coupling and column.
+__global__ __launch_bounds__(kBlock) void pg_direct_border_kernel(Direct dp, DirectSystem sy, int couplings,
+                                                                  const GraphState* __restrict__ gs, const int* __restrict__ bad) {
+  const int t = blockIdx.x * kBlock + threadIdx.x, cpl = t / 6;
+  if (cpl >= couplings || *bad != 0) return;
+  if (gs[dp.run_graph[dp.cpl_run[cpl]]].done) return;
+  direct_border_column(dp, sy, cpl, t - 6 * cpl);
+}
+
+// One thread per Schur item: a graph's s * s blocks (those above the diagonal do nothing) and s right-hand sides.
+__global__ __launch_bounds__(kBlock) void pg_direct_schur_kernel(Direct dp, DirectSystem sy, int g_total, long long items,
+                                                                 const GraphState* __restrict__ gs, const int* __restrict__ bad) {
+  const long long t = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
+  if (t >= items || *bad != 0) return;
+  int lo = 0, hi = g_total;  // the graph whose items hold t
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (dp.item_off[mid] <= t) lo = mid; else hi = mid;
+  }
+  const int g = lo;
+  if (gs[g].done) return;
+  const int s = dp.sep_off[g + 1] - dp.sep_off[g];
+  const int q = static_cast<int>(t - dp.item_off[g]);
+  if (q >= s * s) {
+    direct_schur_rhs(dp, sy, g, q - s * s);
+    return;
+  }
+  const int u = q / s, v = q - u * s;
+  if (v <= u) direct_schur_block(dp, sy, 1.0 + gs[g].lambda, g, s, u, v);
+}
+
+// One workgroup per graph: C = L_S L_S^T in place (column after column: every thread factors the pivot for itself, a block row of
+// the panel per thread, the trailing blocks dealt out by number), x_S by substitution with the right-hand side in LDS, then the
+// graph's runs backwards, a run per thread.  A pivot that is not positive, here or in a run, ends the graph (ST_SINGULAR).
+__global__ __launch_bounds__(kBlock) void pg_direct_solve_kernel(Direct dp, DirectSystem sy, GraphState* __restrict__ gs,
+                                                                 const int* __restrict__ bad) {
+  __shared__ double rs[6 * kMaxSeparator];
+  __shared__ int fail;
+  const int g = blockIdx.x, tid = threadIdx.x;
+  if (*bad != 0 || gs[g].done) return;  // (uniform over the workgroup)
+  const int s0 = dp.sep_off[g], s = dp.sep_off[g + 1] - s0;
+  double* C = dp.C + 36ll * dp.c_off[g];
+  if (tid == 0) fail = dp.fail[g];
+  for (int u = tid; u < s; u += kBlock)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) rs[6 * u + k] = sy.xv[6ll * dp.sep_node[s0 + u] + k];
+  __syncthreads();
+  for (int k = 0; k < s; ++k) {
+    double l[36];
+    double* pivot = C + 36ll * (static_cast<long long>(k) * s + k);
+#pragma unroll
+    for (int q = 0; q < 36; ++q) l[q] = pivot[q];
+    const bool ok = cholesky6(l);
+    __syncthreads();  // every thread has read the pivot
+    if (tid == 0) {
+      if (!ok) fail = 1;
+#pragma unroll
+      for (int q = 0; q < 36; ++q) pivot[q] = l[q];
+    }
+    for (int i = k + 1 + tid; i < s; i += kBlock) {
+      double b[36];
+      double* B = C + 36ll * (static_cast<long long>(i) * s + k);
+#pragma unroll
+      for (int q = 0; q < 36; ++q) b[q] = B[q];
+      dense_panel_block(l, b);
+#pragma unroll
+      for (int q = 0; q < 36; ++q) B[q] = b[q];
+    }
+    __syncthreads();
+    const int m = s - k - 1;
+    for (int idx = tid; idx < m * m; idx += kBlock) {
+      const int i = k + 1 + idx / m, j = k + 1 + idx % m;
+      if (j > i) continue;
+      double c[36];
+      double* Cij = C + 36ll * (static_cast<long long>(i) * s + j);
+#pragma unroll
+      for (int q = 0; q < 36; ++q) c[q] = Cij[q];
+      dense_trailing_block(C + 36ll * (static_cast<long long>(i) * s + k), C + 36ll * (static_cast<long long>(j) * s + k), c);
+#pragma unroll
+      for (int q = 0; q < 36; ++q) Cij[q] = c[q];
+    }
+    __syncthreads();
+  }
+  if (fail) {  // (uniform: written before barriers that every thread passed)
+    if (tid == 0) {
+      gs[g].status = ST_SINGULAR;
+      gs[g].done = 1;
+    }
+    return;
+  }
+  for (int k = 0; k < s; ++k) {  // L_S z = r_S
+    if (tid == 0) dense_lower_solve(C + 36ll * (static_cast<long long>(k) * s + k), rs + 6 * k);
+    __syncthreads();
+    for (int i = k + 1 + tid; i < s; i += kBlock) dense_sub_mul(C + 36ll * (static_cast<long long>(i) * s + k), rs + 6 * k, rs + 6 * i, false);
+    __syncthreads();
+  }
+  for (int k = s - 1; k >= 0; --k) {  // L_S^T x_S = z
+    if (tid == 0) dense_upper_solve(C + 36ll * (static_cast<long long>(k) * s + k), rs + 6 * k);
+    __syncthreads();
+    for (int j = tid; j < k; j += kBlock) dense_sub_mul(C + 36ll * (static_cast<long long>(k) * s + j), rs + 6 * k, rs + 6 * j, true);
+    __syncthreads();
+  }
+  for (int u = tid; u < s; u += kBlock)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) sy.xv[6ll * dp.sep_node[s0 + u] + k] = rs[6 * u + k];
+  __syncthreads();
+  for (int run = dp.run_off[g] + tid; run < dp.run_off[g + 1]; run += kBlock) direct_run_back(dp, sy, run);
+}
+
 // One thread per node: candidate pose Xc = X [Exp(dw) | dt]; node 0 of a graph keeps its pose.
 __global__ __launch_bounds__(kBlock) void pg_update_kernel(Graphs gr, int n_total, const GraphState* __restrict__ gs,
                                                            const double* __restrict__ X, const double* __restrict__ xv,
@@ -1077,9 +1571,223 @@ void carve_tables(Arena& ar, size_t G, size_t N, size_t E, Work& w) {
   w.ints_bytes = ar.off;
 }
 
-bool carve(Arena& ar, int64_t g, int64_t n, int64_t e, int preconditioner, Work& w) {
+unsigned blocks_for(int64_t n) { return static_cast<unsigned>(((n > 0 ? n : 1) + kBlock - 1) / kBlock); }  // (n < 2^35: < 2^27 blocks)
+
+// ---- the direct solve's plan (host) ------------------------------------------------------------------------------------------
+
+// The separator of one graph: a vertex cover of the pairs of free nodes that an edge joins and that are not
+// neighbours on the chain, chosen greedily -- the node with the most uncovered pairs, the lowest number among equals -- and returned
+// in ascending order.  ends(e, s, t) gives edge e's ends inside the graph (already checked).
+template <typename Ends>
+void choose_separator(int64_t n, int64_t ne, Ends ends, std::vector<int>& S) {
+  S.clear();
+  std::vector<std::pair<int, int>> pairs;
+  for (int64_t e = 0; e < ne; ++e) {
+    int64_t s, t;
+    ends(e, s, t);
+    if (s == 0 || t == 0 || s - t == 1 || t - s == 1 || s == t) continue;
+    pairs.emplace_back(static_cast<int>(std::min(s, t)), static_cast<int>(std::max(s, t)));
+  }
+  std::sort(pairs.begin(), pairs.end());
+  pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+  if (pairs.empty()) return;
+  const size_t P = pairs.size();
+  std::vector<int> off(static_cast<size_t>(n) + 1, 0), count(static_cast<size_t>(n), 0);
+  for (const auto& p : pairs) {
+    off[p.first + 1] += 1;
+    off[p.second + 1] += 1;
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    count[i] = off[i + 1];
+    off[i + 1] += off[i];
+  }
+  std::vector<int> adj(2 * P), fill(off.begin(), off.end() - 1);
+  for (size_t k = 0; k < P; ++k) {
+    adj[fill[pairs[k].first]++] = static_cast<int>(k);
+    adj[fill[pairs[k].second]++] = static_cast<int>(k);
+  }
+  std::set<std::pair<int, int>> order;  // (-uncovered pairs, node): the first is the next choice
+  for (int64_t i = 0; i < n; ++i)
+    if (count[i] > 0) order.emplace(-count[i], static_cast<int>(i));
+  std::vector<char> covered(P, 0);
+  while (!order.empty()) {
+    const int node = order.begin()->second;
+    order.erase(order.begin());
+    S.push_back(node);
+    for (int q = off[node]; q < off[node + 1]; ++q) {
+      const int k = adj[q];
+      if (covered[k]) continue;
+      covered[k] = 1;
+      const int other = pairs[k].first == node ? pairs[k].second : pairs[k].first;
+      order.erase({-count[other], other});
+      if (--count[other] > 0) order.emplace(-count[other], other);
+    }
+    count[node] = 0;
+  }
+  std::sort(S.begin(), S.end());
+}
+
+struct DirectPlan {  // Direct's tables on the host
+  std::vector<int> sep_off, sep_node, run_off, run_begin, run_len, run_graph, cpl_off, cpl_sep, cpl_run, cpl_pos, cpl_y, ent_off, ent_pos,
+      ent_code, sc_off, sc;
+  std::vector<long long> c_off, item_off;
+  long long y_blocks = 0;
+};
+
+// The plan of a call from its tables (global node numbers; inc in ascending edge order).  false, with the error set: a graph's
+// separator is above the cap, or Y is too large to index.
+bool build_direct_plan(int64_t G, const int* node_off, const int* edge_off, const int* es, const int* et, const int* inc_off,
+                       const int* inc, DirectPlan& pl, const char* who) {
+  pl = DirectPlan();
+  pl.sep_off.push_back(0);
+  pl.run_off.push_back(0);
+  pl.cpl_off.push_back(0);
+  pl.sc_off.push_back(0);
+  pl.c_off.push_back(0);
+  pl.item_off.push_back(0);
+  std::vector<int> S, node_sep, node_run;
+  struct Entry {
+    int run, sep, pos, code;
+    bool operator<(const Entry& o) const {
+      return run != o.run ? run < o.run : sep != o.sep ? sep < o.sep : pos != o.pos ? pos < o.pos : code < o.code;
+    }
+  };
+  std::vector<Entry> entries;
+  for (int64_t g = 0; g < G; ++g) {
+    const int n0 = node_off[g], n = node_off[g + 1] - n0, e0 = edge_off[g], ne = edge_off[g + 1] - e0;
+    choose_separator(n, ne, [&](int64_t e, int64_t& s, int64_t& t) { s = es[e0 + e] - n0; t = et[e0 + e] - n0; }, S);
+    if (static_cast<int>(S.size()) > kMaxSeparator) {
+      set_error("%s: graph %lld needs %zu separator nodes for the direct solve; the limit is %d (use the conjugate gradients)", who,
+                static_cast<long long>(g), S.size(), kMaxSeparator);
+      return false;
+    }
+    const int s = static_cast<int>(S.size()), sep0 = static_cast<int>(pl.sep_node.size()), run0 = static_cast<int>(pl.run_begin.size());
+    node_sep.assign(static_cast<size_t>(n > 0 ? n : 1), -1);
+    node_run.assign(static_cast<size_t>(n > 0 ? n : 1), -1);
+    for (int u = 0; u < s; ++u) {
+      node_sep[S[u]] = sep0 + u;
+      pl.sep_node.push_back(n0 + S[u]);
+    }
+    for (int i = 1; i < n; ++i) {
+      if (node_sep[i] >= 0) continue;
+      if (i == 1 || node_sep[i - 1] >= 0) {
+        pl.run_begin.push_back(n0 + i);
+        pl.run_len.push_back(0);
+        pl.run_graph.push_back(static_cast<int>(g));
+      }
+      node_run[i] = static_cast<int>(pl.run_begin.size()) - 1;
+      pl.run_len.back() += 1;
+    }
+    // couplings: the edges of every separator node whose other end lies in a run
+    entries.clear();
+    for (int u = 0; u < s; ++u) {
+      const int a = n0 + S[u];
+      for (int q = inc_off[a]; q < inc_off[a + 1]; ++q) {
+        const int code = inc[q], e = code >> 1, b = ((code & 1) ? es[e] : et[e]) - n0;
+        if (b == 0 || node_run[b] < 0) continue;
+        entries.push_back({node_run[b], sep0 + u, n0 + b - pl.run_begin[node_run[b]], code});
+      }
+    }
+    std::sort(entries.begin(), entries.end());
+    const int cpl0 = static_cast<int>(pl.cpl_sep.size());
+    size_t k = 0;
+    for (int run = run0; run < static_cast<int>(pl.run_begin.size()); ++run) {
+      for (; k < entries.size() && entries[k].run == run; ++k) {
+        const Entry& en = entries[k];
+        if (k == 0 || entries[k - 1].run != en.run || entries[k - 1].sep != en.sep) {  // a new coupling; its first entry has its first position
+          pl.ent_off.push_back(static_cast<int>(pl.ent_pos.size()));
+          pl.cpl_sep.push_back(en.sep);
+          pl.cpl_run.push_back(run);
+          pl.cpl_pos.push_back(en.pos);
+          pl.cpl_y.push_back(static_cast<int>(pl.y_blocks));
+          pl.y_blocks += pl.run_len[run] - en.pos;
+          if (pl.y_blocks > (1ll << 31) - 64) {
+            set_error("%s: the border of the direct solve is too large to index (graph %lld)", who, static_cast<long long>(g));
+            return false;
+          }
+        }
+        pl.ent_pos.push_back(en.pos);
+        pl.ent_code.push_back(en.code);
+      }
+      pl.cpl_off.push_back(static_cast<int>(pl.cpl_sep.size()));
+    }
+    // a separator node's couplings, ascending run (the couplings are numbered by run, then separator node)
+    std::vector<int> cnt(static_cast<size_t>(s) + 1, 0);
+    for (size_t c = cpl0; c < pl.cpl_sep.size(); ++c) cnt[pl.cpl_sep[c] - sep0 + 1] += 1;
+    for (int u = 0; u < s; ++u) cnt[u + 1] += cnt[u];
+    const int sc0 = static_cast<int>(pl.sc.size());
+    pl.sc.resize(pl.sc.size() + (pl.cpl_sep.size() - cpl0));
+    for (int u = 0; u < s; ++u) pl.sc_off.push_back(sc0 + cnt[u + 1]);
+    for (size_t c = cpl0; c < pl.cpl_sep.size(); ++c) pl.sc[sc0 + cnt[pl.cpl_sep[c] - sep0]++] = static_cast<int>(c);
+    pl.sep_off.push_back(static_cast<int>(pl.sep_node.size()));
+    pl.run_off.push_back(static_cast<int>(pl.run_begin.size()));
+    pl.c_off.push_back(pl.c_off.back() + static_cast<long long>(s) * s);
+    pl.item_off.push_back(pl.item_off.back() + static_cast<long long>(s) * s + s);
+  }
+  pl.ent_off.push_back(static_cast<int>(pl.ent_pos.size()));  // (a coupling's entries end where the next one's begin)
+  return true;
+}
+
+// Direct's tables in the workspace, behind the other host-built tables and uploaded with them.
+void carve_direct_tables(Arena& ar, const DirectPlan& pl, Work& w, Direct& d) {
+  auto ints = [&](const std::vector<int>& v) { return ar.take<int>(v.size() > 0 ? v.size() : 1); };
+  d.sep_off = ints(pl.sep_off);
+  d.sep_node = ints(pl.sep_node);
+  d.run_off = ints(pl.run_off);
+  d.run_begin = ints(pl.run_begin);
+  d.run_len = ints(pl.run_len);
+  d.run_graph = ints(pl.run_graph);
+  d.cpl_off = ints(pl.cpl_off);
+  d.cpl_sep = ints(pl.cpl_sep);
+  d.cpl_run = ints(pl.cpl_run);
+  d.cpl_pos = ints(pl.cpl_pos);
+  d.cpl_y = ints(pl.cpl_y);
+  d.ent_off = ints(pl.ent_off);
+  d.ent_pos = ints(pl.ent_pos);
+  d.ent_code = ints(pl.ent_code);
+  d.sc_off = ints(pl.sc_off);
+  d.sc = ints(pl.sc);
+  d.c_off = ar.take<long long>(pl.c_off.size());
+  d.item_off = ar.take<long long>(pl.item_off.size());
+  w.ints_bytes = ar.off;
+}
+void carve_direct_arrays(Arena& ar, const DirectPlan& pl, size_t G, Direct& d) {
+  d.C = ar.take<double>(36 * static_cast<size_t>(pl.c_off.back() > 0 ? pl.c_off.back() : 1));
+  d.Y = ar.take<double>(36 * static_cast<size_t>(pl.y_blocks > 0 ? pl.y_blocks : 1));
+  d.fail = ar.take<int>(G);
+}
+// The plan's tables into a host buffer laid out as carve_direct_tables lays the workspace out (h: the same carve on that buffer).
+void fill_direct_tables(const DirectPlan& pl, const Direct& h) {
+  auto put = [](const void* dst, const auto& v) {
+    if (!v.empty()) memcpy(const_cast<void*>(dst), v.data(), v.size() * sizeof(v[0]));
+  };
+  put(h.sep_off, pl.sep_off);
+  put(h.sep_node, pl.sep_node);
+  put(h.run_off, pl.run_off);
+  put(h.run_begin, pl.run_begin);
+  put(h.run_len, pl.run_len);
+  put(h.run_graph, pl.run_graph);
+  put(h.cpl_off, pl.cpl_off);
+  put(h.cpl_sep, pl.cpl_sep);
+  put(h.cpl_run, pl.cpl_run);
+  put(h.cpl_pos, pl.cpl_pos);
+  put(h.cpl_y, pl.cpl_y);
+  put(h.ent_off, pl.ent_off);
+  put(h.ent_pos, pl.ent_pos);
+  put(h.ent_code, pl.ent_code);
+  put(h.sc_off, pl.sc_off);
+  put(h.sc, pl.sc);
+  put(h.c_off, pl.c_off);
+  put(h.item_off, pl.item_off);
+}
+
+
+// plan: the direct solve's (null: conjugate gradients, and the layout is what it was)
+bool carve(Arena& ar, int64_t g, int64_t n, int64_t e, int preconditioner, Work& w, const DirectPlan* plan = nullptr,
+           Direct* direct = nullptr) {
   const size_t G = static_cast<size_t>(g > 0 ? g : 1), N = static_cast<size_t>(n > 0 ? n : 1), E = static_cast<size_t>(e > 0 ? e : 1);
   carve_tables(ar, G, N, E, w);
+  if (plan) carve_direct_tables(ar, *plan, w, *direct);
   w.flags = ar.take<int>(4);
   w.gs = ar.take<GraphState>(G);
   w.X = ar.take<double>(16 * N);
@@ -1099,11 +1807,92 @@ bool carve(Arena& ar, int64_t g, int64_t n, int64_t e, int preconditioner, Work&
   w.zv = ar.take<double>(6 * N);
   w.pv = ar.take<double>(6 * N);
   w.report = ar.take<double>(kReport * G);
-  w.Wc = preconditioner == PRE_CHAIN ? ar.take<double>(36 * N) : nullptr;  // (last: the other slots lie where they lay)
+  w.Wc = preconditioner == PRE_CHAIN || plan ? ar.take<double>(36 * N) : nullptr;  // (last: the other slots lie where they lay)
+  if (plan) carve_direct_arrays(ar, *plan, G, *direct);
   return ar.ok;
 }
 
-unsigned blocks_for(int64_t n) { return static_cast<unsigned>(((n > 0 ? n : 1) + kBlock - 1) / kBlock); }  // (n < 2^35: < 2^27 blocks)
+
+// The offsets of a call's graphs.
+int check_graphs(int64_t G, const int64_t* graph_node_offsets_host, const int64_t* graph_edge_offsets_host) {
+  RDM_REQUIRE(graph_node_offsets_host[0] == 0 && graph_edge_offsets_host[0] == 0, "rdm_pose_graph_optimize: offsets must begin at 0");
+  for (int64_t g = 0; g < G; ++g) {
+    const int64_t n = graph_node_offsets_host[g + 1] - graph_node_offsets_host[g];
+    const int64_t e = graph_edge_offsets_host[g + 1] - graph_edge_offsets_host[g];
+    RDM_REQUIRE(n >= 0 && e >= 0, "rdm_pose_graph_optimize: offsets of graph %lld decrease", static_cast<long long>(g));
+    RDM_REQUIRE(n <= kMaxNodes && e <= kMaxEdges,
+                "rdm_pose_graph_optimize: graph %lld has %lld nodes and %lld edges; the limits are %lld and %lld per graph",
+                static_cast<long long>(g), static_cast<long long>(n), static_cast<long long>(e), static_cast<long long>(kMaxNodes),
+                static_cast<long long>(kMaxEdges));
+  }
+  const int64_t N = graph_node_offsets_host[G], E = graph_edge_offsets_host[G];
+  RDM_REQUIRE(N < kMaxTotal && E < kMaxTotal / 2, "rdm_pose_graph_optimize: too many nodes or edges in one call");
+  return RDM_OK;
+}
+
+// The integer tables (t: carve_tables on a zeroed host buffer): global node ids, graph of every node / edge, incidence lists by a
+// counting sort.
+int fill_tables(int64_t G, const int64_t* graph_node_offsets_host, const int64_t* graph_edge_offsets_host, const int64_t* edges_host,
+                const uint8_t* uncertain_host, const Work& t) {
+  const int64_t N = graph_node_offsets_host[G], E = graph_edge_offsets_host[G];
+  int *node_off = t.node_off, *edge_off = t.edge_off, *edge_graph = t.edge_graph, *node_graph = t.node_graph, *es = t.es, *et = t.et;
+  int *inc_off = t.inc_off, *inc = t.inc;
+  uint8_t* unc = t.uncertain;
+  for (int64_t g = 0; g <= G; ++g) {
+    node_off[g] = static_cast<int>(graph_node_offsets_host[g]);
+    edge_off[g] = static_cast<int>(graph_edge_offsets_host[g]);
+  }
+  for (int64_t i = 0; i <= N; ++i) inc_off[i] = 0;
+  for (int64_t g = 0; g < G; ++g) {
+    const int64_t n = node_off[g + 1] - node_off[g];
+    for (int64_t i = node_off[g]; i < node_off[g + 1]; ++i) node_graph[i] = static_cast<int>(g);
+    for (int64_t e = edge_off[g]; e < edge_off[g + 1]; ++e) {
+      const int64_t s = edges_host[2 * e], t = edges_host[2 * e + 1];
+      RDM_REQUIRE(s >= 0 && s < n && t >= 0 && t < n, "rdm_pose_graph_optimize: edge %lld (%lld, %lld) is outside graph %lld of %lld nodes",
+                  static_cast<long long>(e), static_cast<long long>(s), static_cast<long long>(t), static_cast<long long>(g),
+                  static_cast<long long>(n));
+      RDM_REQUIRE(s != t, "rdm_pose_graph_optimize: edge %lld joins node %lld to itself", static_cast<long long>(e),
+                  static_cast<long long>(s));
+      edge_graph[e] = static_cast<int>(g);
+      es[e] = static_cast<int>(node_off[g] + s);
+      et[e] = static_cast<int>(node_off[g] + t);
+      inc_off[es[e] + 1] += 1;
+      inc_off[et[e] + 1] += 1;
+      unc[e] = uncertain_host ? (uncertain_host[e] != 0 ? 1 : 0) : 0;
+    }
+  }
+  for (int64_t i = 0; i < N; ++i) inc_off[i + 1] += inc_off[i];
+  std::vector<int> fill(inc_off, inc_off + N);
+  for (int64_t e = 0; e < E; ++e) {  // ascending edge order per node
+    inc[fill[es[e]]++] = static_cast<int>(2 * e);
+    inc[fill[et[e]]++] = static_cast<int>(2 * e + 1);
+  }
+  return RDM_OK;
+}
+
+// The host-built tables of a call in one buffer laid out as the workspace's first part; with `plan`, the direct solve's behind them.
+int build_host_tables(int64_t G, const int64_t* graph_node_offsets_host, const int64_t* graph_edge_offsets_host,
+                      const int64_t* edges_host, const uint8_t* uncertain_host, std::vector<char>& host, DirectPlan* plan) {
+  const int64_t N = graph_node_offsets_host[G], E = graph_edge_offsets_host[G];
+  const size_t Gs = static_cast<size_t>(G), Ns = static_cast<size_t>(N > 0 ? N : 1), Es = static_cast<size_t>(E > 0 ? E : 1);
+  Arena sizes(nullptr, 0);
+  Work t;
+  carve_tables(sizes, Gs, Ns, Es, t);
+  host.assign(sizes.off, 0);
+  Arena har(host.data(), host.size());
+  carve_tables(har, Gs, Ns, Es, t);
+  const int rc = fill_tables(G, graph_node_offsets_host, graph_edge_offsets_host, edges_host, uncertain_host, t);
+  if (rc != RDM_OK || plan == nullptr) return rc;
+  if (!build_direct_plan(G, t.node_off, t.edge_off, t.es, t.et, t.inc_off, t.inc, *plan, "rdm_pose_graph_optimize")) return RDM_ERR_ARG;
+  Direct d;
+  carve_direct_tables(sizes, *plan, t, d);
+  host.resize(sizes.off, 0);
+  Arena all(host.data(), host.size());
+  carve_tables(all, Gs, Ns, Es, t);
+  carve_direct_tables(all, *plan, t, d);
+  fill_direct_tables(*plan, d);
+  return RDM_OK;
+}
 
 }  // namespace
 }  // namespace rdm
@@ -1167,6 +1956,135 @@ extern "C" int rdm_pose_graph_chain_host(int64_t n, const double* diag, const do
   return RDM_OK;
 }
 
+extern "C" int rdm_pose_graph_direct_max_separator(void) { return rdm::kMaxSeparator; }
+
+extern "C" int64_t rdm_pose_graph_separator_host(int64_t n_nodes, int64_t n_edges, const int64_t* edges_host, int64_t* out_nodes,
+                                                 int64_t capacity) {
+  using namespace rdm;
+  if (n_nodes < 0 || n_edges < 0 || (n_edges > 0 && edges_host == nullptr) || n_nodes > kMaxTotal) return -1;
+  for (int64_t e = 0; e < n_edges; ++e) {
+    const int64_t s = edges_host[2 * e], t = edges_host[2 * e + 1];
+    if (s < 0 || s >= n_nodes || t < 0 || t >= n_nodes || s == t) return -1;
+  }
+  std::vector<int> S;
+  choose_separator(n_nodes, n_edges, [&](int64_t e, int64_t& s, int64_t& t) { s = edges_host[2 * e]; t = edges_host[2 * e + 1]; }, S);
+  for (size_t k = 0; k < S.size() && static_cast<int64_t>(k) < capacity && out_nodes != nullptr; ++k) out_nodes[k] = S[k];
+  return static_cast<int64_t>(S.size());
+}
+
+extern "C" int rdm_pose_graph_direct_host(int64_t n_nodes, int64_t n_edges, const int64_t* edges_host, const double* diag,
+                                          const double* off, const double* rhs, double* out) {
+  using namespace rdm;
+  RDM_REQUIRE(n_nodes >= 0 && n_nodes <= kMaxNodes && n_edges >= 0 && n_edges <= kMaxEdges, "rdm_pose_graph_direct_host: bad sizes");
+  if (n_nodes == 0) return RDM_OK;
+  RDM_REQUIRE(diag && rhs && out && ((edges_host && off) || n_edges == 0), "rdm_pose_graph_direct_host: null argument");
+  const int64_t noff[2] = {0, n_nodes}, eoff[2] = {0, n_edges};
+  std::vector<char> host;
+  DirectPlan plan;
+  {  // the tables of a one-graph call; edges that touch node 0 stay out of the incidence lists (they hold no block of the system)
+    Arena sizes(nullptr, 0);
+    Work t;
+    carve_tables(sizes, 1, static_cast<size_t>(n_nodes), static_cast<size_t>(n_edges > 0 ? n_edges : 1), t);
+    host.assign(sizes.off, 0);
+  }
+  Arena har(host.data(), host.size());
+  Work t;
+  carve_tables(har, 1, static_cast<size_t>(n_nodes), static_cast<size_t>(n_edges > 0 ? n_edges : 1), t);
+  int rc = fill_tables(1, noff, eoff, edges_host, nullptr, t);
+  if (rc != RDM_OK) return rc;
+  {
+    int kept = 0;
+    std::vector<int> inc_off(static_cast<size_t>(n_nodes) + 1, 0);
+    for (int64_t i = 0; i < n_nodes; ++i) {
+      inc_off[i] = kept;
+      for (int q = t.inc_off[i]; q < t.inc_off[i + 1]; ++q) {
+        const int e = t.inc[q] >> 1;
+        if (t.es[e] != 0 && t.et[e] != 0) t.inc[kept++] = t.inc[q];
+      }
+    }
+    inc_off[n_nodes] = kept;
+    for (int64_t i = 0; i <= n_nodes; ++i) t.inc_off[i] = inc_off[i];
+  }
+  if (!build_direct_plan(1, t.node_off, t.edge_off, t.es, t.et, t.inc_off, t.inc, plan, "rdm_pose_graph_direct_host")) return RDM_ERR_ARG;
+  const size_t N = static_cast<size_t>(n_nodes);
+  std::vector<double> F(21 * N), Wc(36 * N, 0.0), zv(6 * N, 0.0), xv(6 * N, 0.0), C(36 * static_cast<size_t>(plan.c_off.back()) + 36),
+      Y(36 * static_cast<size_t>(plan.y_blocks) + 36);
+  int fail = 0;
+  auto data = [](const auto& v) { return v.empty() ? nullptr : v.data(); };
+  const Direct dp = {data(plan.sep_off), data(plan.sep_node), data(plan.run_off), data(plan.run_begin), data(plan.run_len),
+                     data(plan.run_graph), data(plan.cpl_off), data(plan.cpl_sep), data(plan.cpl_run), data(plan.cpl_pos),
+                     data(plan.cpl_y), data(plan.ent_off), data(plan.ent_pos), data(plan.ent_code), data(plan.sc_off), data(plan.sc),
+                     data(plan.c_off), data(plan.item_off), C.data(), Y.data(), &fail};
+  const DirectSystem sy = {t.es, t.et, t.inc_off, t.inc, diag, off, rhs, F.data(), Wc.data(), zv.data(), xv.data()};
+  for (int64_t i = 2; i < n_nodes; ++i) chain_off_block(t.es, t.et, t.inc_off, t.inc, off, i, &Wc[36 * i]);
+  const int runs = static_cast<int>(plan.run_begin.size()), couplings = static_cast<int>(plan.cpl_sep.size()), s = plan.sep_off[1];
+  for (int run = 0; run < runs; ++run)
+    if (!direct_run_factor(dp, sy, 1.0, run)) {
+      set_error("rdm_pose_graph_direct_host: a pivot of the run that begins at node %d is not positive definite", plan.run_begin[run]);
+      return RDM_ERR_ARG;
+    }
+  for (int c = 0; c < couplings; ++c)
+    for (int col = 0; col < 6; ++col) direct_border_column(dp, sy, c, col);
+  for (int u = 0; u < s; ++u)
+    for (int v = 0; v <= u; ++v) direct_schur_block(dp, sy, 1.0, 0, s, u, v);
+  for (int u = 0; u < s; ++u) direct_schur_rhs(dp, sy, 0, u);
+  std::vector<double> rs(6 * static_cast<size_t>(s) + 6);
+  for (int u = 0; u < s; ++u)
+    for (int k = 0; k < 6; ++k) rs[6 * u + k] = xv[6 * plan.sep_node[u] + k];
+  auto block = [&](int i, int j) { return C.data() + 36 * (static_cast<size_t>(i) * s + j); };
+  for (int k = 0; k < s; ++k) {  // the dense factor, column after column
+    if (!cholesky6(block(k, k))) {
+      set_error("rdm_pose_graph_direct_host: the Schur complement's pivot of node %d is not positive definite", plan.sep_node[k]);
+      return RDM_ERR_ARG;
+    }
+    for (int i = k + 1; i < s; ++i) dense_panel_block(block(k, k), block(i, k));
+    for (int i = k + 1; i < s; ++i)
+      for (int j = k + 1; j <= i; ++j) dense_trailing_block(block(i, k), block(j, k), block(i, j));
+  }
+  for (int k = 0; k < s; ++k) {
+    dense_lower_solve(block(k, k), &rs[6 * k]);
+    for (int i = k + 1; i < s; ++i) dense_sub_mul(block(i, k), &rs[6 * k], &rs[6 * i], false);
+  }
+  for (int k = s - 1; k >= 0; --k) {
+    dense_upper_solve(block(k, k), &rs[6 * k]);
+    for (int j = 0; j < k; ++j) dense_sub_mul(block(k, j), &rs[6 * k], &rs[6 * j], true);
+  }
+  for (int u = 0; u < s; ++u)
+    for (int k = 0; k < 6; ++k) xv[6 * plan.sep_node[u] + k] = rs[6 * u + k];
+  for (int run = 0; run < runs; ++run) direct_run_back(dp, sy, run);
+  for (int k = 0; k < 6; ++k) xv[k] = 0.0;
+  memcpy(out, xv.data(), sizeof(double) * 6 * N);
+  return RDM_OK;
+}
+
+extern "C" size_t rdm_pose_graph_workspace_bytes_ls(int64_t n_graphs, const int64_t* graph_node_offsets_host,
+                                                    const int64_t* graph_edge_offsets_host, const int64_t* edges_host, int preconditioner,
+                                                    int linear_solver) {
+  using namespace rdm;
+  auto checked = [&]() -> int {
+    RDM_REQUIRE(linear_solver == SOLVER_PCG || linear_solver == SOLVER_DIRECT,
+                "rdm_pose_graph_workspace_bytes_ls: linear_solver %d (0: conjugate gradients, 1: direct)", linear_solver);
+    RDM_REQUIRE(n_graphs >= 0 && n_graphs < kMaxTotal && graph_node_offsets_host && graph_edge_offsets_host,
+                "rdm_pose_graph_workspace_bytes_ls: bad number of graphs or null offsets");
+    return check_graphs(n_graphs, graph_node_offsets_host, graph_edge_offsets_host);
+  };
+  if (checked() != RDM_OK) return 0;
+  const int64_t N = graph_node_offsets_host[n_graphs], E = graph_edge_offsets_host[n_graphs];
+  if (linear_solver == SOLVER_PCG) return rdm_pose_graph_workspace_bytes_pc(n_graphs, N, E, preconditioner);
+  if (E > 0 && edges_host == nullptr) {
+    set_error("rdm_pose_graph_workspace_bytes_ls: null edges");
+    return 0;
+  }
+  std::vector<char> host;
+  DirectPlan plan;
+  if (build_host_tables(n_graphs, graph_node_offsets_host, graph_edge_offsets_host, edges_host, nullptr, host, &plan) != RDM_OK) return 0;
+  Arena ar(nullptr, 0);
+  Work w;
+  Direct dp;
+  carve(ar, n_graphs, N, E, PRE_BLOCK_JACOBI, w, &plan, &dp);
+  return ar.off;
+}
+
 extern "C" size_t rdm_pose_graph_workspace_bytes_pc(int64_t n_graphs, int64_t n_nodes, int64_t n_edges, int preconditioner) {
   using namespace rdm;
   Arena ar(nullptr, 0);
@@ -1199,8 +2117,26 @@ extern "C" int rdm_pose_graph_optimize_pc(int64_t n_graphs, const int64_t* graph
                                           double gradient_tolerance, double cost_tolerance, int pcg_max_iterations,
                                           double pcg_tolerance, int preconditioner, double* nodes_out, double* weights_out,
                                           uint8_t* pruned_out, double* report_host, void* ws, size_t ws_bytes, void* stream) {
+  return rdm_pose_graph_optimize_ls(n_graphs, graph_node_offsets_host, graph_edge_offsets_host, nodes, edges_host, transforms,
+                                    informations, uncertain_host, line_process_weight, edge_prune_threshold, max_iterations,
+                                    gradient_tolerance, cost_tolerance, pcg_max_iterations, pcg_tolerance, preconditioner, 0, nodes_out,
+                                    weights_out, pruned_out, report_host, ws, ws_bytes, stream);
+}
+
+extern "C" int rdm_pose_graph_optimize_ls(int64_t n_graphs, const int64_t* graph_node_offsets_host,
+                                          const int64_t* graph_edge_offsets_host, const double* nodes, const int64_t* edges_host,
+                                          const double* transforms, const double* informations, const uint8_t* uncertain_host,
+                                          double line_process_weight, double edge_prune_threshold, int max_iterations,
+                                          double gradient_tolerance, double cost_tolerance, int pcg_max_iterations,
+                                          double pcg_tolerance, int preconditioner, int linear_solver, double* nodes_out,
+                                          double* weights_out, uint8_t* pruned_out, double* report_host, void* ws, size_t ws_bytes,
+                                          void* stream) {
   using namespace rdm;
   const int64_t G = n_graphs;
+  RDM_REQUIRE(linear_solver == SOLVER_PCG || linear_solver == SOLVER_DIRECT,
+              "rdm_pose_graph_optimize: linear_solver %d (0: conjugate gradients, 1: direct)", linear_solver);
+  const bool direct = linear_solver == SOLVER_DIRECT;
+  if (direct) preconditioner = PRE_BLOCK_JACOBI;  // (ignored)
   RDM_REQUIRE(preconditioner == PRE_BLOCK_JACOBI || preconditioner == PRE_CHAIN,
               "rdm_pose_graph_optimize: preconditioner %d (0: block-Jacobi, 1: the odometry chain)", preconditioner);
   RDM_REQUIRE(G >= 0 && G < kMaxTotal, "rdm_pose_graph_optimize: bad number of graphs");
@@ -1210,65 +2146,21 @@ extern "C" int rdm_pose_graph_optimize_pc(int64_t n_graphs, const int64_t* graph
                   std::isfinite(edge_prune_threshold),
               "rdm_pose_graph_optimize: bad options");
   if (G == 0) return RDM_OK;
-  RDM_REQUIRE(graph_node_offsets_host[0] == 0 && graph_edge_offsets_host[0] == 0, "rdm_pose_graph_optimize: offsets must begin at 0");
-  for (int64_t g = 0; g < G; ++g) {
-    const int64_t n = graph_node_offsets_host[g + 1] - graph_node_offsets_host[g];
-    const int64_t e = graph_edge_offsets_host[g + 1] - graph_edge_offsets_host[g];
-    RDM_REQUIRE(n >= 0 && e >= 0, "rdm_pose_graph_optimize: offsets of graph %lld decrease", static_cast<long long>(g));
-    RDM_REQUIRE(n <= kMaxNodes && e <= kMaxEdges,
-                "rdm_pose_graph_optimize: graph %lld has %lld nodes and %lld edges; the limits are %lld and %lld per graph",
-                static_cast<long long>(g), static_cast<long long>(n), static_cast<long long>(e), static_cast<long long>(kMaxNodes),
-                static_cast<long long>(kMaxEdges));
-  }
+  int rc = check_graphs(G, graph_node_offsets_host, graph_edge_offsets_host);
+  if (rc != RDM_OK) return rc;
   const int64_t N = graph_node_offsets_host[G], E = graph_edge_offsets_host[G];
-  RDM_REQUIRE(N < kMaxTotal && E < kMaxTotal / 2, "rdm_pose_graph_optimize: too many nodes or edges in one call");
   RDM_REQUIRE((nodes && nodes_out) || N == 0, "rdm_pose_graph_optimize: null nodes");
   RDM_REQUIRE((edges_host && transforms && informations) || E == 0, "rdm_pose_graph_optimize: null edges");
-  // the integer tables: global node ids, graph of every node / edge, incidence lists by a counting sort
-  Arena sizes(nullptr, 0);
-  Work t;
-  carve_tables(sizes, G, N > 0 ? N : 1, E > 0 ? E : 1, t);
-  std::vector<char> host(sizes.off, 0);
-  Arena har(host.data(), host.size());
-  carve_tables(har, G, N > 0 ? N : 1, E > 0 ? E : 1, t);
-  int *node_off = t.node_off, *edge_off = t.edge_off, *edge_graph = t.edge_graph, *node_graph = t.node_graph, *es = t.es, *et = t.et;
-  int *inc_off = t.inc_off, *inc = t.inc;
-  uint8_t* unc = t.uncertain;
-  for (int64_t g = 0; g <= G; ++g) {
-    node_off[g] = static_cast<int>(graph_node_offsets_host[g]);
-    edge_off[g] = static_cast<int>(graph_edge_offsets_host[g]);
-  }
-  for (int64_t i = 0; i <= N; ++i) inc_off[i] = 0;
-  for (int64_t g = 0; g < G; ++g) {
-    const int64_t n = node_off[g + 1] - node_off[g];
-    for (int64_t i = node_off[g]; i < node_off[g + 1]; ++i) node_graph[i] = static_cast<int>(g);
-    for (int64_t e = edge_off[g]; e < edge_off[g + 1]; ++e) {
-      const int64_t s = edges_host[2 * e], t = edges_host[2 * e + 1];
-      RDM_REQUIRE(s >= 0 && s < n && t >= 0 && t < n, "rdm_pose_graph_optimize: edge %lld (%lld, %lld) is outside graph %lld of %lld nodes",
-                  static_cast<long long>(e), static_cast<long long>(s), static_cast<long long>(t), static_cast<long long>(g),
-                  static_cast<long long>(n));
-      RDM_REQUIRE(s != t, "rdm_pose_graph_optimize: edge %lld joins node %lld to itself", static_cast<long long>(e),
-                  static_cast<long long>(s));
-      edge_graph[e] = static_cast<int>(g);
-      es[e] = static_cast<int>(node_off[g] + s);
-      et[e] = static_cast<int>(node_off[g] + t);
-      inc_off[es[e] + 1] += 1;
-      inc_off[et[e] + 1] += 1;
-      unc[e] = uncertain_host ? (uncertain_host[e] != 0 ? 1 : 0) : 0;
-    }
-  }
-  for (int64_t i = 0; i < N; ++i) inc_off[i + 1] += inc_off[i];
-  {
-    std::vector<int> fill(inc_off, inc_off + N);
-    for (int64_t e = 0; e < E; ++e) {  // ascending edge order per node
-      inc[fill[es[e]]++] = static_cast<int>(2 * e);
-      inc[fill[et[e]]++] = static_cast<int>(2 * e + 1);
-    }
-  }
+  // the integer tables, and with the direct solve its separators, runs and coupling lists behind them
+  std::vector<char> host;
+  DirectPlan plan;
+  rc = build_host_tables(G, graph_node_offsets_host, graph_edge_offsets_host, edges_host, uncertain_host, host, direct ? &plan : nullptr);
+  if (rc != RDM_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   Arena ar(ws, ws_bytes);
   Work w;
-  if (!carve(ar, G, N, E, preconditioner, w)) {
+  Direct dp;
+  if (!carve(ar, G, N, E, preconditioner, w, direct ? &plan : nullptr, &dp)) {
     set_error("rdm_pose_graph_optimize: workspace too small (%zu < %zu bytes)", ws_bytes, ar.off);
     return RDM_ERR_WORKSPACE;
   }
@@ -1286,6 +2178,9 @@ extern "C" int rdm_pose_graph_optimize_pc(int64_t n_graphs, const int64_t* graph
   int *bad = w.flags, *remaining = w.flags + 1, *failed = w.flags + 2;
   const int n = static_cast<int>(N), e = static_cast<int>(E), g = static_cast<int>(G);
   const int64_t widest = std::max<int64_t>(std::max<int64_t>(16 * N, E), G);
+  const DirectSystem sy = {w.es, w.et, w.inc_off, w.inc, w.D, w.Hab, w.rv, w.F, w.Wc, w.zv, w.xv};
+  const int runs = direct ? static_cast<int>(plan.run_begin.size()) : 0, couplings = direct ? static_cast<int>(plan.cpl_sep.size()) : 0;
+  const long long items = direct ? plan.item_off.back() : 0;
   fill_words<int>(w.flags, 4, 0, st);
   hipLaunchKernelGGL(pg_init_kernel, dim3(blocks_for(widest)), dim3(kBlock), 0, st, nodes, n, w.X, w.Xc, w.gs, g, w.node_off, w.edge_off);
   hipLaunchKernelGGL(pg_check_kernel, dim3(blocks_for(std::max(N, E))), dim3(kBlock), 0, st, gr, nodes, n, transforms, informations, e,
@@ -1293,7 +2188,7 @@ extern "C" int rdm_pose_graph_optimize_pc(int64_t n_graphs, const int64_t* graph
   hipLaunchKernelGGL(pg_cost_kernel, dim3(blocks_for(E)), dim3(kBlock), 0, st, gr, e, w.X, transforms, informations, p, w.gs, 0, w.term,
                      w.lw, bad);
   hipLaunchKernelGGL(pg_step_kernel, dim3(1), dim3(kBlock), 0, st, gr, g, p, 0, w.term, w.gs, remaining, bad);
-  int rc = launch_status("rdm_pose_graph_optimize (setup)");
+  rc = launch_status("rdm_pose_graph_optimize (setup)");
   if (rc != RDM_OK) return rc;
   int left = 1;
   for (int k = 0; k < max_iterations && left > 0;) {
@@ -1301,9 +2196,21 @@ extern "C" int rdm_pose_graph_optimize_pc(int64_t n_graphs, const int64_t* graph
     for (; k < end; ++k) {
       hipLaunchKernelGGL(pg_linearize_kernel, dim3(blocks_for(E)), dim3(kBlock), 0, st, gr, e, w.X, transforms, informations, p, w.gs,
                          w.lw, w.Haa, w.Hab, w.Hbb, w.ga, w.gb, bad);
-      hipLaunchKernelGGL(preconditioner == PRE_CHAIN ? pg_solve_kernel<PRE_CHAIN> : pg_solve_kernel<PRE_BLOCK_JACOBI>,
-                         dim3(static_cast<unsigned>(G)), dim3(kBlock), 0, st, gr, p, w.gs, w.Haa, w.Hab, w.Hbb, w.ga, w.gb, w.D, w.F, w.bv,
-                         w.xv, w.rv, w.zv, w.pv, bad, w.Wc);
+      if (direct) {
+        hipLaunchKernelGGL(pg_direct_blocks_kernel, dim3(static_cast<unsigned>(G)), dim3(kBlock), 0, st, gr, p, w.gs, w.Haa, w.Hab, w.Hbb,
+                           w.ga, w.gb, w.D, w.bv, w.xv, w.rv, w.Wc, dp.fail, bad);
+        if (runs > 0)
+          hipLaunchKernelGGL(pg_direct_factor_kernel, dim3((runs + kWave - 1) / kWave), dim3(kWave), 0, st, dp, sy, runs, w.gs, bad);
+        if (couplings > 0)
+          hipLaunchKernelGGL(pg_direct_border_kernel, dim3(blocks_for(6ll * couplings)), dim3(kBlock), 0, st, dp, sy, couplings, w.gs, bad);
+        if (items > 0)
+          hipLaunchKernelGGL(pg_direct_schur_kernel, dim3(blocks_for(items)), dim3(kBlock), 0, st, dp, sy, g, items, w.gs, bad);
+        hipLaunchKernelGGL(pg_direct_solve_kernel, dim3(static_cast<unsigned>(G)), dim3(kBlock), 0, st, dp, sy, w.gs, bad);
+      } else {
+        hipLaunchKernelGGL(preconditioner == PRE_CHAIN ? pg_solve_kernel<PRE_CHAIN> : pg_solve_kernel<PRE_BLOCK_JACOBI>,
+                           dim3(static_cast<unsigned>(G)), dim3(kBlock), 0, st, gr, p, w.gs, w.Haa, w.Hab, w.Hbb, w.ga, w.gb, w.D, w.F,
+                           w.bv, w.xv, w.rv, w.zv, w.pv, bad, w.Wc);
+      }
       hipLaunchKernelGGL(pg_update_kernel, dim3(blocks_for(N)), dim3(kBlock), 0, st, gr, n, w.gs, w.X, w.xv, w.Xc, bad);
       hipLaunchKernelGGL(pg_cost_kernel, dim3(blocks_for(E)), dim3(kBlock), 0, st, gr, e, w.Xc, transforms, informations, p, w.gs, 0,
                          w.term, static_cast<double*>(nullptr), bad);

@@ -920,6 +920,7 @@ POSE_GRAPH_REPORT_WIDTH = 8  # per graph: initial cost, final cost, iterations, 
 POSE_GRAPH_STOP = {1: 'gradient', 2: 'cost', 3: 'max_iterations', 4: 'empty'}
 POSE_GRAPH_MAX_NODES, POSE_GRAPH_MAX_EDGES = 65536, 1048576  # per graph (rdm_pose_graph_optimize)
 POSE_GRAPH_PRECONDITIONERS = {'block_jacobi': 0, 'chain': 1}  # rdm_pose_graph_optimize_pc's `preconditioner`
+POSE_GRAPH_LINEAR_SOLVERS = {'pcg': 0, 'direct': 1}  # rdm_pose_graph_optimize_ls's `linear_solver`
 
 
 class PoseGraphResult:
@@ -970,7 +971,7 @@ def _pose_graph_connected(edges, node_offsets, edge_offsets):
 def pose_graph_optimize(nodes, edges, transforms, informations, uncertain=None, *, line_process_weight=None,
                         edge_prune_threshold=0.25, max_iterations=100, gradient_tolerance=1e-9, cost_tolerance=1e-12,
                         graph_node_offsets=None, graph_edge_offsets=None, pcg_max_iterations=None, pcg_tolerance=1e-10,
-                        preconditioner='block_jacobi'):
+                        preconditioner='block_jacobi', linear_solver='pcg'):
     """Pose-graph optimisation on the GPU (rdm_pose_graph_optimize; what Open3D's global_optimization does; parity unpinned,
     the definition is DESIGN.md section 7, pinned to tests/pose_graph_restatement.py).  nodes float64 [N, 4, 4] (the pose of scan i
     in the frame of its graph's node 0, which stays fixed), edges int64 [E, 2] rows (s, t) numbered inside their graph, transforms
@@ -984,7 +985,12 @@ def pose_graph_optimize(nodes, edges, transforms, informations, uncertain=None, 
     DESIGN.md section 7).  preconditioner: 'block_jacobi' (the default: the node blocks) or 'chain' (the block tridiagonal part of
     the system along the odometry chain, nodes i and i + 1, factored exactly: 7 to 17 times fewer conjugate-gradient iterations
     on drives with loop closures, each one longer -- docs/EXPERIMENTS.md 5o; same minimum within the tolerances, other bits); any
-    other string is a ValueError.
+    other string is a ValueError.  linear_solver: 'pcg' (the default: the conjugate gradients above) or 'direct' (a direct sparse
+    solve for a chain with loop closures, DESIGN.md section 7: one end of every off-chain edge is taken out, the rest is factored
+    exactly along the chain, and the separator's dense Schur complement is factored in 6 x 6 blocks; preconditioner,
+    pcg_max_iterations and pcg_tolerance are ignored and pcg_iterations is 0; a graph may need at most 256 separator nodes
+    (rdm_pose_graph_direct_max_separator) -- above that the call is a RuntimeError naming the graph and the count, and nothing falls
+    back to the conjugate gradients); any other string is a ValueError.
     -> PoseGraphResult.  ValueError for a node without a path to node 0; RuntimeError (the library's argument error, every output
     untouched) for a self edge, an index outside its graph, a non-finite entry, an asymmetric information matrix, a graph above
     65 536 nodes or 1 048 576 edges."""
@@ -992,6 +998,9 @@ def pose_graph_optimize(nodes, edges, transforms, informations, uncertain=None, 
     if preconditioner not in POSE_GRAPH_PRECONDITIONERS:
         raise ValueError(f'pose_graph_optimize: preconditioner must be one of {sorted(POSE_GRAPH_PRECONDITIONERS)}, got {preconditioner!r}')
     pre = POSE_GRAPH_PRECONDITIONERS[preconditioner]
+    if linear_solver not in POSE_GRAPH_LINEAR_SOLVERS:
+        raise ValueError(f'pose_graph_optimize: linear_solver must be one of {sorted(POSE_GRAPH_LINEAR_SOLVERS)}, got {linear_solver!r}')
+    solver = POSE_GRAPH_LINEAR_SOLVERS[linear_solver]
     L = _lib.lib()
     tensors = [t for t in (nodes, transforms, informations) if isinstance(t, torch.Tensor) and t.is_cuda]
     dev = tensors[0].device if tensors else torch.device('cuda', torch.cuda.current_device())
@@ -1035,12 +1044,17 @@ def pose_graph_optimize(nodes, edges, transforms, informations, uncertain=None, 
     pruned = torch.empty(e, dtype=torch.uint8, device=dev)
     report = np.zeros((g, POSE_GRAPH_REPORT_WIDTH), np.float64)
     with torch.cuda.device(dev):
-        ws = scratch(dev, L.rdm_pose_graph_workspace_bytes_pc(g, n, e, pre))
-        _lib.check(L.rdm_pose_graph_optimize_pc(g, noff.ctypes.data, eoff.ctypes.data, _lib.ptr(X), ed.ctypes.data, _lib.ptr(T),
+        size = L.rdm_pose_graph_workspace_bytes_ls(g, noff.ctypes.data, eoff.ctypes.data, ed.ctypes.data, pre, solver)
+        if size == 0 and solver == 0:  # (offsets the library refuses: the call below reports them, as it always did)
+            size = L.rdm_pose_graph_workspace_bytes_pc(g, n, e, pre)
+        elif size == 0:  # (an edge outside its graph, a graph above a limit: the library's message, before any GPU work)
+            _lib.check(-1, 'rdm_pose_graph_optimize')
+        ws = scratch(dev, size)
+        _lib.check(L.rdm_pose_graph_optimize_ls(g, noff.ctypes.data, eoff.ctypes.data, _lib.ptr(X), ed.ctypes.data, _lib.ptr(T),
                                                 _lib.ptr(Lm), 0 if unc is None else unc.ctypes.data,
                                                 0.0 if line_process_weight is None else float(line_process_weight),
                                                 float(edge_prune_threshold), int(max_iterations), float(gradient_tolerance),
-                                                float(cost_tolerance), int(pcg_max_iterations), float(pcg_tolerance), pre,
+                                                float(cost_tolerance), int(pcg_max_iterations), float(pcg_tolerance), pre, solver,
                                                 _lib.ptr(out), _lib.ptr(weights), _lib.ptr(pruned), report.ctypes.data,
                                                 ws.data_ptr(), ws.numel(), _lib.stream_ptr()), 'rdm_pose_graph_optimize')
     return PoseGraphResult(out, weights, pruned.bool(), report)

@@ -1,7 +1,7 @@
 """Trajectories of a run over a sequence: the reference's chaining and absolute trajectory error, and the pose graph of a run.
 
     python -m rdmnet_amd.trajectory --features-root DIR [--optimize] [--line-process-weight MU] [--unit-information] [--out DIR]
-                                  [--preconditioner {block_jacobi,chain}]
+                                  [--preconditioner {block_jacobi,chain}] [--linear-solver {pcg,direct}]
 
 reads the `{seq}_{src}_{ref}.npz` pair files that `python -m rdmnet_amd.infer` wrote into DIR (ordered and filtered as
 `python -m rdmnet_amd.eval` reads them) and, per sequence, chains the pair poses into a trajectory as
@@ -11,7 +11,7 @@ pair's ref frame, and whose ref frame is new to the chain, continues the odometr
 several such pairs the first in file order); every other pair file of the sequence is an uncertain (loop-closure) edge between
 two frames of the chain.  With --optimize all sequences are optimised as one batch by
 `ops.pose_graph_optimize` (--preconditioner chain selects its odometry-chain preconditioner, which suits exactly
-these graphs) and the report is printed for the optimised trajectory too.  Without --optimize no
+these graphs; --linear-solver direct its direct sparse solve in place of the conjugate gradients) and the report is printed for the optimised trajectory too.  Without --optimize no
 GPU is needed.  Everything here is numpy float64 on the host."""
 import argparse
 import math
@@ -183,7 +183,8 @@ def run(args, emit=print):
     res = ops.pose_graph_optimize(cat(0, (-1, 4, 4)), cat(1, (-1, 2)), cat(2, (-1, 4, 4)), cat(3, (-1, 6, 6)), cat(4, (-1,)),
                                   line_process_weight=args.line_process_weight, edge_prune_threshold=args.edge_prune_threshold,
                                   max_iterations=args.max_iterations, graph_node_offsets=noff, graph_edge_offsets=eoff,
-                                  preconditioner=getattr(args, 'preconditioner', 'block_jacobi'))
+                                  preconditioner=getattr(args, 'preconditioner', 'block_jacobi'),
+                                  linear_solver=getattr(args, 'linear_solver', 'pcg'))
     nodes, pruned = res.nodes.cpu().numpy(), res.pruned.cpu().numpy()
     for g, seq in enumerate(order):
         traj = nodes[noff[g] + 1:noff[g + 1]]
@@ -207,6 +208,8 @@ def make_parser():
     ap.add_argument('--unit-information', action='store_true', help='use the identity as the information matrix of every pair (the files need no `information`)')
     ap.add_argument('--preconditioner', choices=('block_jacobi', 'chain'), default='block_jacobi',
                     help='of the conjugate gradients inside --optimize: the node blocks, or the odometry chain factored exactly')
+    ap.add_argument('--linear-solver', choices=('pcg', 'direct'), default='pcg',
+                    help='of --optimize: conjugate gradients, or the direct sparse solve for a chain with loop closures')
     ap.add_argument('--out', default=None, help='directory for one KITTI-format pose file per sequence and variant')
     return ap
 

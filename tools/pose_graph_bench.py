@@ -4,9 +4,10 @@ for comparison: the restatement's dense solve (tests/pose_graph_restatement.py, 
 and, where scipy is importable, the same damped Gauss-Newton iteration with a sparse direct solve (scipy.sparse.linalg.spsolve).
 
   python tools/pose_graph_bench.py [--nodes 500] [--loops 40] [--batch 11] [--reps 3] [--cpu] [--preconditioner chain]
+                                     [--linear-solver direct]
 Prints one JSON line: sizes, GPU ms per call (median; a call ends with its read-back), outer iterations, PCG iterations per outer
 iteration, and the host's ms per solve.  --preconditioner (block_jacobi | chain) is passed to ops.pose_graph_optimize and named in
-the output; without the flag the call and the output are what they were."""
+the output; without the flag the call and the output are what they were.  --linear-solver (pcg | direct) likewise."""
 import argparse
 import json
 import os
@@ -88,6 +89,7 @@ def main():
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--cpu', action='store_true', help='also time the host: the dense restatement and, with scipy, a sparse solve')
     ap.add_argument('--preconditioner', choices=('block_jacobi', 'chain'), default=None)
+    ap.add_argument('--linear-solver', choices=('pcg', 'direct'), default=None)
     a = ap.parse_args()
     import torch
     from rdmnet_amd import ops
@@ -98,6 +100,9 @@ def main():
     if a.preconditioner is not None:
         out['preconditioner'] = a.preconditioner
         extra['preconditioner'] = a.preconditioner
+    if a.linear_solver is not None:
+        out['linear_solver'] = a.linear_solver
+        extra['linear_solver'] = a.linear_solver
 
     def run(gs):
         noff = np.cumsum([0] + [len(g['nodes']) for g in gs])
