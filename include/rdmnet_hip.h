@@ -1011,6 +1011,43 @@ int rdm_eval_pairs(int64_t num_pairs, const int64_t* corr_offsets, const int64_t
                    const int64_t* gt_offsets, const int64_t* gt_node_corr, const int64_t* node_dims,
                    const rdm_eval_options* options, double* records, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- §7 robust pose from correspondences: maximum clique and truncated least squares (robust.hip) ---------------------
+ * The estimator experiments/eval.py:198-219 names `teaser`.  The library it calls is not part of the reference tree ->
+ * parity unpinned; this is the project's own definition after the published algorithm, pinned to the
+ * float64 restatement tests/robust_restatement.py.  src_corr / ref_corr: device f32 [n_corr, 3], the pose moves src onto ref;
+ * n_corr <= RDM_ROBUST_MAX_CORR, above it RDM_ERR_CAPACITY.  All arithmetic is float64 on the fp32 inputs, uncontracted, every
+ * sum in a fixed order, no float atomics: two calls give the same bits.
+ *   (1) graph: rows i != j are adjacent iff |sqrt((dx dx + dy dy) + dz dz)(src_j - src_i) - the same of ref| <= 2 noise_bound
+ *       sqrt(cbar2); a row with a non-finite value is adjacent to nothing.  degree int32[n_corr].
+ *   (2) core int32[n_corr]: the k-core numbers of the graph.
+ *   (3) selection: RDM_ROBUST_CLIQUE -- of all maximum cliques the one whose ascending row list is lexicographically smallest;
+ *       one depth-first subproblem per lowest row, each limited to max_clique_nodes search nodes (<= 0: the default,
+ *       rdm_robust_default_clique_nodes()); when a subproblem runs out, the best clique found is returned with exact = 0 (still
+ *       a deterministic result).  RDM_ROBUST_KCORE -- the rows of maximum core number.  RDM_ROBUST_NONE -- all rows.
+ *   (4) rotation: GNC-TLS over the pairs p < q of the K selected rows, a = src_q - src_p, b = ref_q - ref_p, n2 = (2 noise_bound)^2
+ *       cbar2, weights 1 at first; per iteration R = Horn's rotation of sum w a b^T, r2 = |b - R a|^2, first iteration mu = 1 /
+ *       (2 max r2 / n2 - 1) (mu <= 0: stop), th1 = (mu+1)/mu n2, th2 = mu/(mu+1) n2, cost = sum w r2 (old weights), w = 0 for
+ *       r2 >= th1, 1 for r2 <= th2, else sqrt(n2 mu (mu+1) / r2) - mu; stop when |cost - previous| < cost_threshold (not on the
+ *       first iteration) or after max_iterations; mu *= gnc_factor.  The device decides; the host reads one int32 per 16
+ *       iterations.
+ *   (5) translation, per axis: x_k = (ref_k - R src_k)[axis], c = noise_bound sqrt(cbar2), h = the sorted 2K values x_k -+ c; for
+ *       every midpoint m of consecutive h: S = {k : |x_k - m| <= c} (empty: skipped), est = mean of S, cost = sum_S (x_k - est)^2
+ *       + (K - |S|) c^2; the est of least cost, the lowest midpoint among equals.
+ * Outputs (device): transform f64[16] row-major with bottom row 0 0 0 1 (eval.py:217 writes 1 1 1 0 there; nothing reads it);
+ * stats int32[RDM_ROBUST_STATS] = {K, valid, exact, GNC iterations, translation inliers (rows within c on all three axes),
+ * graph edges}; selected int32[n_corr]: the K rows ascending, then -1; weights (optional) f64[weights_capacity]: the final
+ * weight of pair (p, q) of the selected rows at p K - p (p + 1) / 2 + q - p - 1 (pairs beyond the capacity are not written);
+ * degree, core (optional).  K < 3: valid = 0 and the identity.  n_corr = 0 launches nothing but the output fill.            */
+#define RDM_ROBUST_MAX_CORR 16384
+#define RDM_ROBUST_STATS 6
+enum { RDM_ROBUST_CLIQUE = 0, RDM_ROBUST_KCORE = 1, RDM_ROBUST_NONE = 2 };
+int64_t rdm_robust_default_clique_nodes(void);
+size_t rdm_robust_registration_workspace_bytes(int64_t n_corr, int inlier_selection);
+int rdm_robust_registration(const float* src_corr, const float* ref_corr, int64_t n_corr, double noise_bound, double cbar2,
+                            double gnc_factor, int max_iterations, double cost_threshold, int inlier_selection,
+                            int64_t max_clique_nodes, double* transform, int32_t* stats, int32_t* selected, double* weights,
+                            int64_t weights_capacity, int32_t* degree, int32_t* core, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

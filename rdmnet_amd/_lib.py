@@ -44,6 +44,10 @@ class EvalOptions(ctypes.Structure):
                    float(distance_threshold), int(ransac_n), int(num_iterations), 0, int(seed))
 
 
+ROBUST_SELECTIONS = {'clique': 0, 'kcore': 1, 'none': 2}  # RDM_ROBUST_*
+ROBUST_MAX_CORR = 16384  # = RDM_ROBUST_MAX_CORR
+ROBUST_STATS = ('num_selected', 'valid', 'exact', 'iterations', 'translation_inliers', 'edges')  # rdm_robust_registration's stats
+
 EVAL_RECORD_WIDTH = 20  # = RDM_EVAL_RECORD_WIDTH
 # the fields of one record of rdm_eval_pairs, in order
 EVAL_FIELDS = ('num_corr', 'residual', 'inlier_ratio', 'inlier_ratio_0.3', 'inlier_ratio_0.1', 'overlap', 'precision', 'rre', 'rte',
@@ -245,6 +249,11 @@ SIGNATURES = {
     'rdm_eval_pairs_workspace_bytes': (c_size, [c_i64, c_i64, c_i64, c_void]),
     'rdm_eval_pairs': (c_int, [c_i64, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void,
                                c_void, c_void, c_void, c_void, c_void, c_size, c_void]),
+    'rdm_robust_default_clique_nodes': (c_i64, []),
+    'rdm_robust_registration_workspace_bytes': (c_size, [c_i64, c_int]),
+    'rdm_robust_registration': (c_int, [c_void, c_void, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int,
+                                        ctypes.c_double, c_int, c_i64, c_void, c_void, c_void, c_void, c_i64, c_void, c_void,
+                                        c_void, c_size, c_void]),
 }
 
 

@@ -1,6 +1,7 @@
 """Offline evaluator: experiments/eval.py on the GPU.
 
-    python -m rdmnet_amd.eval --features-root DIR [--method lgr|ransac|svd|ransac_featurematch] [--num_corr N] [--verbose] [--batch B]
+    python -m rdmnet_amd.eval --features-root DIR [--method lgr|ransac|svd|ransac_featurematch|robust] [--num_corr N] [--verbose]
+                              [--batch B] [--noise-bound B] [--inlier-selection clique|kcore|none]
 
 reads the pair files `python -m rdmnet_amd.infer --gt-nodes` (or the reference's test.py) wrote into DIR and prints the
 report of eval.py:248-286.  Files are ordered as eval.py:78-81 orders them, pair (seq 8, src frame 15) is skipped as in
@@ -14,6 +15,13 @@ no branch for it (eval.py:177-219).  The pair is evaluated on the descriptor cor
 feature distances, lowest rows among equals --, the fine meters are the descriptor IR / FMR, and the pose is
 rdm_ransac_correspondences with the cfg.ransac values, as --method ransac.  Open3D's own
 registration_ransac_based_on_feature_matching (its internal KNN and checkers) is not restated.
+
+`--method robust` is THIS project's definition of the estimator eval.py:198-219 calls `teaser` (maximum clique
+of the compatibility graph, GNC-TLS rotation, truncated-least-squares translation; the library eval.py imports is not part of
+the reference tree, and the name `teaser` stays rejected).  The host selects the --num_corr rows by rdm_eval_pairs' own rule
+(score descending, row ascending, the first N, kept in row order), `ops.robust_registration` runs once per pair with
+--noise-bound (default 0.01, eval.py:200) and --inlier-selection, and the pairs are then evaluated as --method lgr with the
+computed transforms in place of the stored ones.
 """
 import argparse
 import glob
@@ -27,13 +35,15 @@ from . import config, evaluation
 
 METHODS = ('lgr', 'ransac', 'svd')                # what the reference's evaluation loop implements (eval.py:177-219)
 OWN_METHODS = ('ransac_featurematch',)            # defined by this project; the command line takes them (main)
-NOT_BUILT = {'teaser': 'TEASER++ is not part of this project',
+ROBUST_METHODS = ('robust',)                      # this project's maximum-clique / GNC-TLS estimator (ops.robust_registration)
+NOT_BUILT = {'teaser': "TEASER++ is not part of this project; its algorithm, as this project defines it, is --method robust",
+             'robust': 'this project\'s own estimator is enabled by make_parser(own_methods=True), as the command line does',
              'ransac_featurematch': "the reference's evaluation loop has no branch for it (eval.py:177-219); this project's "
                                     "definition is enabled by make_parser(own_methods=True), as the command line does"}
 FEATURE_KEYS = ('feat_ref_corr_points', 'feat_src_corr_points', 'feat_corr_dists')  # read by --method ransac_featurematch
 PAIR_KEYS = ('ref_corr_points', 'src_corr_points', 'corr_scores', 'transform', 'estimated_transform', 'ref_node_corr_indices',
              'src_node_corr_indices', 'gt_node_corr_indices')
-KERNEL_METHOD = {'ransac_featurematch': 'ransac'}  # (rdm_eval_pairs is unchanged: only the packed rows differ)
+KERNEL_METHOD = {'ransac_featurematch': 'ransac', 'robust': 'lgr'}  # (rdm_eval_pairs is unchanged: only the packed rows differ)
 MAX_THREADS = 16
 # experiments/config.py: cfg.eval and cfg.ransac (a cfg that carries these sections overrides them)
 EVAL_DEFAULTS = dict(acceptance_radius=0.6, inlier_ratio_threshold=0.05, rre_threshold=5.0, rte_threshold=2.0)
@@ -51,7 +61,7 @@ def method_arg(value, methods=METHODS):
 def make_parser(own_methods=False):
     """The reference's eval.py arguments.  own_methods: --method also takes OWN_METHODS (this project's definitions of names the
     reference advertises without implementing them); `python -m rdmnet_amd.eval` sets it."""
-    methods = METHODS + OWN_METHODS if own_methods else METHODS
+    methods = METHODS + OWN_METHODS + ROBUST_METHODS if own_methods else METHODS
     parser = argparse.ArgumentParser(prog='python -m rdmnet_amd.eval', description=__doc__.split('\n\n')[0])
     parser.add_argument('--features-root', '--features_root', required=True, help='directory of the {seq}_{src}_{ref}.npz pair files')
     parser.add_argument('--test_epoch', default=None, type=int, help='test epoch')
@@ -62,6 +72,10 @@ def make_parser(own_methods=False):
     parser.add_argument('--batch', type=int, default=64, help='pairs per GPU call')
     parser.add_argument('--workers', type=int, default=8, help=f'reader threads (at most {MAX_THREADS})')
     parser.add_argument('--seed', type=int, default=0, help='seed of --method ransac')
+    if own_methods:
+        parser.add_argument('--noise-bound', '--noise_bound', type=float, default=0.01, help='noise bound of --method robust')
+        parser.add_argument('--inlier-selection', '--inlier_selection', choices=('clique', 'kcore', 'none'), default='clique',
+                            help='inlier selection of --method robust')
     return parser
 
 
@@ -117,6 +131,33 @@ def load_pair(file_name, method='lgr'):
     return d
 
 
+def select_rows(scores, num_corr):
+    """rdm_eval_pairs' rule for --num_corr L on the host: the first L rows in the order (score descending, row ascending), kept
+    in row order; every row for L None or C <= L."""
+    scores = np.asarray(scores, np.float32).reshape(-1)
+    if num_corr is None or len(scores) <= num_corr:
+        return np.arange(len(scores))
+    order = np.lexsort((np.arange(len(scores)), -scores.astype(np.float64)))  # last key first: score, then row
+    return np.sort(order[:num_corr])
+
+
+def robust_transforms(pairs, num_corr=None, noise_bound=0.01, inlier_selection='clique', results=None):
+    """One ops.robust_registration per pair dict (load_pair) on its --num_corr rows -> float32 [P, 4, 4].  results (list):
+    receives the RobustResult of every pair."""
+    import torch
+    from . import ops
+    out = np.zeros((len(pairs), 4, 4), np.float32)
+    for p, d in enumerate(pairs):
+        rows = select_rows(d['corr_scores'], num_corr)
+        src = torch.from_numpy(np.ascontiguousarray(np.asarray(d['src_corr_points'], np.float32).reshape(-1, 3)[rows])).cuda()
+        ref = torch.from_numpy(np.ascontiguousarray(np.asarray(d['ref_corr_points'], np.float32).reshape(-1, 3)[rows])).cuda()
+        res = ops.robust_registration(src, ref, noise_bound=noise_bound, inlier_selection=inlier_selection)
+        out[p] = res.transformation.astype(np.float32)
+        if results is not None:
+            results.append(res)
+    return out
+
+
 def pair_message(position, total, ids, out):
     """eval.py:127,170-174,238-239."""
     m = '{}/{}, seq_id: {}, id0: {}, id1: {}'.format(position, total, *ids)
@@ -126,9 +167,10 @@ def pair_message(position, total, ids, out):
     return m + ', r_RRE: {:.3f}, r_RTE: {:.3f}'.format(out['r_RRE'], out['r_RTE'])
 
 
-def evaluate(args, cfg=None, emit=print, timings=None):
+def evaluate(args, cfg=None, emit=print, timings=None, collect=None):
     """eval_one_epoch (eval.py:36-286).  Returns the Summary.  `timings` (dict) receives the seconds the main thread spent
-    waiting for packed batches ('load_wait') and inside the GPU calls ('evaluate')."""
+    waiting for packed batches ('load_wait') and inside the GPU calls ('evaluate'); `collect` (list) receives per pair
+    (ids, record, the transform the record was computed with)."""
     import time
     from . import ops
     cfg = cfg or config.make_cfg()
@@ -142,25 +184,32 @@ def evaluate(args, cfg=None, emit=print, timings=None):
     t_wait = t_eval = 0.0
     with ThreadPoolExecutor(max_workers=workers) as pool:
         def prepare(items):  # files in parallel, then one packed buffer
-            return ops.pack_eval_pairs(list(pool.map(lambda name: load_pair(name, args.method), [name for _, name, _ in items])))
+            pairs = list(pool.map(lambda name: load_pair(name, args.method), [name for _, name, _ in items]))
+            return (pairs if args.method in ROBUST_METHODS else None), ops.pack_eval_pairs(pairs)
 
         with ThreadPoolExecutor(max_workers=1) as packer:
             ahead = 2
             pending = [packer.submit(prepare, b) for b in batches[:ahead]]
             for k, items in enumerate(batches):
                 t0 = time.perf_counter()
-                packed = pending.pop(0).result()
+                pairs, packed = pending.pop(0).result()
                 if k + ahead < len(batches):
                     pending.append(packer.submit(prepare, batches[k + ahead]))
                 t1 = time.perf_counter()
-                records, _ = ops.evaluate_pairs(packed, KERNEL_METHOD.get(args.method, args.method), args.num_corr, acceptance_radius=ev['acceptance_radius'],
+                if pairs is not None:  # --method robust: the computed transforms take the place of the stored ones
+                    est = robust_transforms(pairs, args.num_corr, args.noise_bound, args.inlier_selection)
+                    o, dtype, shape = packed.sections['est_transform']
+                    packed.buf.numpy()[o:o + est.nbytes] = est.reshape(-1).view(np.uint8)
+                records, used = ops.evaluate_pairs(packed, KERNEL_METHOD.get(args.method, args.method), args.num_corr, acceptance_radius=ev['acceptance_radius'],
                                                 distance_threshold=rs['distance_threshold'], ransac_n=rs['num_points'],
                                                 num_iterations=rs['num_iterations'], seed=args.seed)
                 t2 = time.perf_counter()
                 t_wait += t1 - t0
                 t_eval += t2 - t1
-                for (position, _, ids), rec in zip(items, records):
+                for k2, ((position, _, ids), rec) in enumerate(zip(items, records)):
                     out = summary.commit_record(ids, rec)
+                    if collect is not None:
+                        collect.append((ids, rec, used[k2]))
                     if args.verbose:
                         emit(pair_message(position, total, ids, out))
     if timings is not None:

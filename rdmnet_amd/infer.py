@@ -8,6 +8,7 @@ registration report, on the native engine.
     python -m rdmnet_amd.infer --infer-root /path/to/assets/pc --out out/ --feature-match mutual   # + descriptor correspondences
     python -m rdmnet_amd.infer --infer-root /path/to/assets/pc --out out/ --quality                # + fitness, inlier RMSE, chamfer
     python -m rdmnet_amd.infer --infer-root /path/to/assets/pc --out out/ --information            # + the 6 x 6 pose information matrix
+    python -m rdmnet_amd.infer --infer-root /path/to/assets/pc --out out/ --robust                 # + the maximum-clique / GNC-TLS pose
     python -m torch.distributed.run --nproc-per-node 8 -m rdmnet_amd.infer ...       # pairs sharded over ranks
 
 Per pair it writes what the reference writes: one line in `<seq>_pose` and one `<seq>_<src>_<ref>.npz`
@@ -28,6 +29,10 @@ as quality_* keys (ops.QUALITY_KEYS), into its .npz; every other key stays as it
 (Engine.information_matrix on the resident input clouds, src moved by the pair's own pose against ref, radius
 cfg.fine_matching.acceptance_radius) goes into the .npz as `information` (float64 [6, 6]) with `information_corr` (int64, the
 correspondences behind it), and `info_corr: N` to the pair's log line; every other key stays as it is.
+`--robust` adds an outlier-robust pose of every pair from its fine correspondences (ops.robust_registration: maximum clique of
+the compatibility graph, GNC-TLS rotation, truncated-least-squares translation; --noise-bound, default 0.01, eval.py:200; the
+16384 best-scored rows when there are more) to the .npz as `estimated_transform_robust` (float64 [4, 4]), and `robust_K` (rows it
+was estimated from), `robust_exact` and, with ground truth, the pose's RRE / RTE to the pair's log line; every other key stays.
 """
 import argparse
 import os
@@ -37,7 +42,7 @@ import time
 import numpy as np
 import torch
 
-from . import config, dataset as ds_mod, evaluation, ops, sharding, weights
+from . import _lib, config, dataset as ds_mod, evaluation, ops, sharding, weights
 from .pipeline import DEFAULT_PAIRS_IN_FLIGHT, PairPipeline, pin_rank
 
 
@@ -56,7 +61,7 @@ class Tester:
 
     def __init__(self, cfg, state, output_dir=None, save_npz=True, ransac=True, write_poses=True,
                  pairs_in_flight=DEFAULT_PAIRS_IN_FLIGHT, wait_us=None, lockstep=None, gt_nodes=False, feature_match=None,
-                 quality=False, information=False):
+                 quality=False, information=False, robust=False, noise_bound=0.01):
         self.cfg, self.output_dir, self.save_npz, self.ransac = cfg, output_dir, save_npz, ransac
         self.write_poses = write_poses  # False under several ranks: rank 0 writes all poses, in pair order, at the end
         # gt_nodes: test.py's run -- ground-truth superpoint correspondences per pair with a transform (model.py:283-297, radius
@@ -68,6 +73,7 @@ class Tester:
         self.feature_match = feature_match
         self.quality = bool(quality)  # Engine.alignment_quality of every pair's own pose, on the input clouds
         self.information = bool(information)  # Engine.information_matrix of every pair's own pose, on the input clouds
+        self.robust, self.noise_bound = bool(robust), float(noise_bound)  # ops.robust_registration on the fine correspondences
         ev = dict(cfg.get('eval', {})) if hasattr(cfg, 'get') else {}
         self.fm_radius = float(ev.get('acceptance_radius', 0.6))
         radius = getattr(getattr(cfg, 'model', None), 'ground_truth_matching_radius', None)
@@ -127,6 +133,19 @@ class Tester:
             rec['info_corr'] = int(eng.information_corr)
             extra = dict(extra or {})
             extra.update(information=info.numpy(), information_corr=np.int64(rec['info_corr']))
+        if self.robust:  # the outlier-robust pose from the pair's fine correspondences, this stream
+            rc, sc, cs = eng.corr()
+            if rc.shape[0] > _lib.ROBUST_MAX_CORR:  # the graph's capacity: the best-scored rows, as eval.py --num_corr selects
+                from .eval import select_rows
+                rows = torch.from_numpy(select_rows(cs.cpu().numpy(), _lib.ROBUST_MAX_CORR)).to(rc.device)
+                rc, sc = rc[rows], sc[rows]
+            rb = ops.robust_registration(sc.contiguous(), rc.contiguous(), noise_bound=self.noise_bound)
+            rec['robust_K'], rec['robust_exact'] = rb.num_selected, rb.exact
+            if 'transform' in item:
+                rec['robust_RRE'], rec['robust_RTE'] = (float(v) for v in evaluation.compute_registration_error(
+                    np.asarray(item['transform'], np.float64), rb.transformation)[:2])
+            extra = dict(extra or {})
+            extra.update(estimated_transform_robust=rb.transformation)
         if self.gt_nodes and 'transform' in item:  # test.py: model.py:283-297 on the engine's resident tensors, this stream
             gt_idx, gt_ovl, _ = eng.gt_node_correspondences(np.asarray(item['transform'], np.float32), self.gt_radius)
             m_r = int(res.n_ref_nodes)
@@ -184,6 +203,10 @@ class Tester:
                     line += ''.join(', {}: {:.4f}'.format(k, rec['quality'][k]) for k in ops.QUALITY_KEYS)
                 if 'info_corr' in rec:  # (--information)
                     line += ', info_corr: {}'.format(rec['info_corr'])
+                if 'robust_K' in rec:  # (--robust)
+                    line += ', robust_K: {}, robust_exact: {}'.format(rec['robust_K'], rec['robust_exact'])
+                    if 'robust_RRE' in rec:
+                        line += ', robust_RRE: {:.3f}, robust_RTE: {:.3f}'.format(rec['robust_RRE'], rec['robust_RTE'])
                 log(line)
         return self.records
 
@@ -223,6 +246,10 @@ def main(argv=None):
     ap.add_argument('--information', action='store_true',
                     help="add every pair's 6 x 6 pose information matrix (Open3D's get_information_matrix_from_point_clouds at "
                          'cfg.fine_matching.acceptance_radius, for a pose graph) to the pair file as information / information_corr')
+    ap.add_argument('--robust', action='store_true',
+                    help="add every pair's outlier-robust pose from its fine correspondences (maximum clique, GNC-TLS rotation, "
+                         'truncated-least-squares translation) to the pair file as estimated_transform_robust')
+    ap.add_argument('--noise-bound', '--noise_bound', type=float, default=0.01, help='noise bound of --robust (eval.py:200)')
     args = ap.parse_args(argv)
 
     rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
@@ -264,7 +291,7 @@ def main(argv=None):
     tester = Tester(cfg, load_state(args.weights, cfg), args.out, save_npz=not args.no_npz, ransac=not args.no_ransac,
                     write_poses=world == 1, pairs_in_flight=args.pairs_in_flight, lockstep=args.lockstep, gt_nodes=args.gt_nodes,
                     feature_match=args.feature_match, quality=args.quality,
-                    information=args.information)
+                    information=args.information, robust=args.robust, noise_bound=args.noise_bound)
     mine = sharding.pairs_for_rank(len(data), rank, world)
     # scans are read and staged (pinned host -> HBM on a side stream) two pairs ahead of every in-flight pair
     stager = ds_mod.PairStager(data, mine, depth=2 * args.pairs_in_flight, workers=max(2, args.pairs_in_flight))

@@ -600,6 +600,71 @@ def ransac_correspondences(src_corr, ref_corr, distance_threshold=0.3, ransac_n=
     return (T, stats, rmse, hyp) if return_hypotheses else (T, stats, rmse)
 
 
+class RobustResult:
+    """rdm_robust_registration's outputs on the host: transformation (float64 [4, 4] numpy, src -> ref, bottom row 0 0 0 1),
+    selected (int64 numpy [K]: the rows the pose was estimated from, ascending), the stats by name (num_selected, valid, exact,
+    iterations, translation_inliers, edges) and, when asked for, weights (float64 numpy [K (K - 1) / 2]: the final GNC weight
+    of pair (p, q) of the selected rows at p K - p (p + 1) / 2 + q - p - 1), degree and core (int32 numpy [C])."""
+
+    def __init__(self, transformation, selected, stats, weights=None, degree=None, core=None):
+        self.transformation, self.selected, self.weights, self.degree, self.core = transformation, selected, weights, degree, core
+        for name, v in zip(_lib.ROBUST_STATS, stats):
+            setattr(self, name, int(v))
+
+    def __repr__(self):
+        return (f'RobustResult(num_selected={self.num_selected}, valid={self.valid}, exact={self.exact}, '
+                f'iterations={self.iterations}, translation_inliers={self.translation_inliers}, edges={self.edges})')
+
+
+def robust_registration(src_corr, ref_corr, noise_bound=0.01, cbar2=1.0, gnc_factor=1.4, max_iterations=100, cost_threshold=1e-12,
+                        inlier_selection='clique', max_clique_nodes=None, return_weights=False, return_graph=False):
+    """Outlier-robust pose from correspondences (rdm_robust_registration; DESIGN.md section 7: compatibility graph, maximum
+    clique, GNC-TLS rotation, truncated-least-squares translation -- the estimator experiments/eval.py:198-219 names `teaser`,
+    this project's own definition).  src_corr / ref_corr: float32 CUDA [C, 3], C <= 16384, the pose moves src onto ref; the
+    defaults are eval.py:199-206's.  inlier_selection: 'clique', 'kcore' or 'none'; max_clique_nodes: search nodes per
+    subproblem (None: the library's default).  -> RobustResult (the call ends with the read-back of its results)."""
+    import numpy as np
+    L = _lib.lib()
+    for t, name in ((src_corr, 'src_corr'), (ref_corr, 'ref_corr')):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 3):
+            raise ValueError(f'{name} must be a float32 CUDA tensor [C, 3]')
+    if src_corr.shape != ref_corr.shape or src_corr.device != ref_corr.device:
+        raise ValueError('src_corr and ref_corr must have the same shape and device')
+    if inlier_selection not in _lib.ROBUST_SELECTIONS:
+        raise ValueError(f"inlier_selection must be one of {', '.join(_lib.ROBUST_SELECTIONS)}, got {inlier_selection!r}")
+    if not (noise_bound > 0 and cbar2 > 0 and gnc_factor > 1 and int(max_iterations) >= 1 and cost_threshold >= 0):
+        raise ValueError('noise_bound and cbar2 must be > 0, gnc_factor > 1, max_iterations >= 1, cost_threshold >= 0')
+    if max_clique_nodes is not None and int(max_clique_nodes) < 1:
+        raise ValueError(f'max_clique_nodes must be >= 1 (or None for the default), got {max_clique_nodes}')
+    src_corr, ref_corr = src_corr.contiguous(), ref_corr.contiguous()
+    C, dev = src_corr.shape[0], src_corr.device
+    mode = _lib.ROBUST_SELECTIONS[inlier_selection]
+    n_stats = len(_lib.ROBUST_STATS)
+    # transform f64[16], then int32: stats, selected[C], degree[C], core[C] -- one read-back
+    out = torch.empty((16 * 2 + n_stats + 3 * C + 2,), dtype=torch.int32, device=dev)
+    ints = out[32:]
+    stats, selected, degree, core = ints[:n_stats], ints[n_stats:n_stats + C], ints[n_stats + C:n_stats + 2 * C], ints[n_stats + 2 * C:]
+    cap = C * (C - 1) // 2 if return_weights else 0
+    weights = torch.zeros((max(cap, 1),), dtype=torch.float64, device=dev) if return_weights else None
+    ws_bytes = L.rdm_robust_registration_workspace_bytes(min(C, _lib.ROBUST_MAX_CORR), mode)
+    ws = scratch(dev, ws_bytes)
+    _lib.check(L.rdm_robust_registration(src_corr.data_ptr(), ref_corr.data_ptr(), C, float(noise_bound), float(cbar2),
+                                         float(gnc_factor), int(max_iterations), float(cost_threshold), mode,
+                                         0 if max_clique_nodes is None else int(max_clique_nodes), out.data_ptr(), stats.data_ptr(),
+                                         selected.data_ptr(), _lib.ptr(weights), cap, degree.data_ptr(), core.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+               'rdm_robust_registration')
+    host = out.cpu().numpy()
+    st = host[32:32 + n_stats]
+    K = int(st[0])
+    hi = host[32 + n_stats:]
+    w = None
+    if return_weights:
+        w = weights[:K * (K - 1) // 2].cpu().numpy() if st[1] else np.zeros(0)
+    return RobustResult(host[:32].view(np.float64).reshape(4, 4).copy(), hi[:K].astype(np.int64), st, w,
+                        hi[C:2 * C].copy() if return_graph else None, hi[2 * C:3 * C].copy() if return_graph else None)
+
+
 class RegistrationResult:
     """Named as Open3D's: transformation (float64 [4, 4], numpy), fitness, inlier_rmse, num_correspondences (of the last
     evaluation), iterations (updates applied) and, when asked for, history (float64 [evaluations, 15] numpy: per
