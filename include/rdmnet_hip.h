@@ -1048,6 +1048,42 @@ int rdm_robust_registration(const float* src_corr, const float* ref_corr, int64_
                             int64_t max_clique_nodes, double* transform, int32_t* stats, int32_t* selected, double* weights,
                             int64_t weights_capacity, int32_t* degree, int32_t* core, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- §7 loop-closure detection: Scan Context descriptors and exhaustive search (scan_context.hip) ----------------------
+ * Kim & Kim, "Scan Context", IROS 2018.  Not in the reference tree -> parity unpinned; the project's own definition (DESIGN.md
+ * section 7), pinned to the float64 restatement tests/scan_context_restatement.py.  1 <= n_rings, n_sectors <=
+ * RDM_SCAN_CONTEXT_MAX_DIM; outside that every function here returns RDM_ERR_ARG (the workspace functions 0).
+ * Descriptor of a cloud: D f32 [n_rings, n_sectors].  Per point, in float64 on the fp32 coordinates: r = sqrt(x x + y y); the
+ * point is skipped if x, y or z is not finite, r == 0 or r > max_range; ring = min(floor(r / max_range n_rings), n_rings - 1);
+ * theta = atan2(y, x) (+ 2 pi if negative), sector = min(floor(theta / (2 pi) n_sectors), n_sectors - 1); value = the fp32 sum
+ * z + (float)lidar_height.  A bin holds the maximum value of its points (negative values included), 0 without a point.
+ * Integer atomic max on order-preserving keys: independent of the order of the points, two calls give the same bits.
+ * rdm_scan_context: points device f32 [n_points, ld >= 3]; offsets device int64 [n_scans + 1], scan s is rows
+ * offsets[s] .. offsets[s + 1] (clamped to [0, n_points]; empty scans allowed); n_scans <= 65535.  Outputs (device, desc or the
+ * other two may be null): desc f32 [n_scans, n_rings, n_sectors]; desc_norm f32 [n_scans, n_rings, RDM_SCAN_CONTEXT_LD]: every
+ * column divided by its 2-norm (float64 sum of squares, one rounding), 0 in columns of norm 0 and in the pad columns; valid
+ * uint64 [n_scans]: bit j = column j has a norm > 0.
+ * Distance of descriptors Q, C: for shift n in [0, n_sectors) query column j meets candidate column (j - n) mod n_sectors;
+ * d_n = 1 - (sum of the cosines of the cnt_n column pairs valid on both sides) / cnt_n, 1 when cnt_n = 0; d = min_n d_n, shift
+ * = the lowest n that attains it (a query that is the candidate rotated by +a about z has shift ~ a n_sectors / 360 deg).
+ * fp32: per ring the 64 products of a row are summed in column order, the ring sums are added in ring order.
+ * rdm_scan_context_distance: q_desc / c_desc device f32 raw descriptors [n_q | n_c, n_rings, n_sectors] (normalised into the
+ * workspace; the same pointer and count on both sides: once); n_c <= 2^26 (RDM_ERR_CAPACITY above), n_q <= 65535 x 16.
+ * Query i has the global index q_base + i, candidate j c_base + j; j is eligible for i iff (q_base + i) - (c_base + j) >=
+ * exclude_recent (negative: every candidate is).  best_distance f32 / best_index int32 / best_shift int32 [n_q]: the eligible
+ * candidate of lowest d, the lowest candidate among equals, and its shift; (+inf, -1, -1) without an eligible candidate.
+ * dist f32 / shift int32 [n_q, n_c] (both or neither; for tests and small problems): every pair, eligible or not; the best
+ * values are the same bits with and without them.  No float atomics: the per-query merge is a 64-bit integer atomic min.  */
+#define RDM_SCAN_CONTEXT_MAX_DIM 64
+#define RDM_SCAN_CONTEXT_LD 64
+size_t rdm_scan_context_workspace_bytes(int64_t n_scans, int n_rings, int n_sectors);
+int rdm_scan_context(const float* points, int64_t ld, int64_t n_points, const int64_t* offsets, int64_t n_scans, int n_rings,
+                     int n_sectors, double max_range, double lidar_height, float* desc, float* desc_norm, uint64_t* valid, void* ws,
+                     size_t ws_bytes, void* stream);
+size_t rdm_scan_context_distance_workspace_bytes(int64_t n_q, int64_t n_c, int n_rings, int n_sectors);
+int rdm_scan_context_distance(const float* q_desc, int64_t n_q, const float* c_desc, int64_t n_c, int n_rings, int n_sectors,
+                              int64_t q_base, int64_t c_base, int64_t exclude_recent, float* best_distance, int32_t* best_index,
+                              int32_t* best_shift, float* dist, int32_t* shift, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

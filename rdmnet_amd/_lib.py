@@ -48,6 +48,9 @@ ROBUST_SELECTIONS = {'clique': 0, 'kcore': 1, 'none': 2}  # RDM_ROBUST_*
 ROBUST_MAX_CORR = 16384  # = RDM_ROBUST_MAX_CORR
 ROBUST_STATS = ('num_selected', 'valid', 'exact', 'iterations', 'translation_inliers', 'edges')  # rdm_robust_registration's stats
 
+SCAN_CONTEXT_MAX_DIM = 64  # = RDM_SCAN_CONTEXT_MAX_DIM: n_rings, n_sectors <= this
+SCAN_CONTEXT_LD = 64  # = RDM_SCAN_CONTEXT_LD: columns of a row of the normalised descriptors
+
 EVAL_RECORD_WIDTH = 20  # = RDM_EVAL_RECORD_WIDTH
 # the fields of one record of rdm_eval_pairs, in order
 EVAL_FIELDS = ('num_corr', 'residual', 'inlier_ratio', 'inlier_ratio_0.3', 'inlier_ratio_0.1', 'overlap', 'precision', 'rre', 'rte',
@@ -254,6 +257,12 @@ SIGNATURES = {
     'rdm_robust_registration': (c_int, [c_void, c_void, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int,
                                         ctypes.c_double, c_int, c_i64, c_void, c_void, c_void, c_void, c_i64, c_void, c_void,
                                         c_void, c_size, c_void]),
+    'rdm_scan_context_workspace_bytes': (c_size, [c_i64, c_int, c_int]),
+    'rdm_scan_context': (c_int, [c_void, c_i64, c_i64, c_void, c_i64, c_int, c_int, ctypes.c_double, ctypes.c_double, c_void, c_void,
+                                 c_void, c_void, c_size, c_void]),
+    'rdm_scan_context_distance_workspace_bytes': (c_size, [c_i64, c_i64, c_int, c_int]),
+    'rdm_scan_context_distance': (c_int, [c_void, c_i64, c_void, c_i64, c_int, c_int, c_i64, c_i64, c_i64, c_void, c_void, c_void,
+                                          c_void, c_void, c_void, c_size, c_void]),
 }
 
 

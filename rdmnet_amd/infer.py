@@ -9,6 +9,7 @@ registration report, on the native engine.
     python -m rdmnet_amd.infer --infer-root /path/to/assets/pc --out out/ --quality                # + fitness, inlier RMSE, chamfer
     python -m rdmnet_amd.infer --infer-root /path/to/assets/pc --out out/ --information            # + the 6 x 6 pose information matrix
     python -m rdmnet_amd.infer --infer-root /path/to/assets/pc --out out/ --robust                 # + the maximum-clique / GNC-TLS pose
+    python -m rdmnet_amd.infer --dataset-root /data/kitti --pair-lists loops --information --out out/   # the loop pairs of `prepare loops`
     python -m torch.distributed.run --nproc-per-node 8 -m rdmnet_amd.infer ...       # pairs sharded over ranks
 
 Per pair it writes what the reference writes: one line in `<seq>_pose` and one `<seq>_<src>_<ref>.npz`
@@ -33,6 +34,9 @@ correspondences behind it), and `info_corr: N` to the pair's log line; every oth
 the compatibility graph, GNC-TLS rotation, truncated-least-squares translation; --noise-bound, default 0.01, eval.py:200; the
 16384 best-scored rows when there are more) to the .npz as `estimated_transform_robust` (float64 [4, 4]), and `robust_K` (rows it
 was estimated from), `robust_exact` and, with ground truth, the pose's RRE / RTE to the pair's log line; every other key stays.
+`--pair-lists NAME [--sequences ...]` takes the pairs from the lists R/NAME/%02d (the format of icp10: `src ref` + the pose) instead
+of icp10 and --subset: with `loops`, the loop closures `python -m rdmnet_amd.prepare loops` detected, whose pair files
+`python -m rdmnet_amd.trajectory --optimize` takes as loop edges.
 """
 import argparse
 import os
@@ -211,7 +215,22 @@ class Tester:
         return self.records
 
 
-def main(argv=None):
+def pair_list_metadata(dataset_root, name, sequences=None):
+    """The dataset metadata of the pair lists R/NAME/%02d (dataset.load_kitti_gt_txt: `src ref` + 12 pose values per line, e.g.
+    what `prepare loops` writes under R/loops) -> (metadata, sequences).  sequences None: every list under R/NAME."""
+    import glob
+    folder = os.path.join(dataset_root, name)
+    if sequences is None:
+        sequences = sorted(int(os.path.basename(f)) for f in glob.glob(os.path.join(folder, '[0-9][0-9]')))
+        if not sequences:
+            raise FileNotFoundError(f'no pair lists under {folder}')
+    metadata = []
+    for seq in sequences:
+        metadata += ds_mod.load_kitti_gt_txt(folder, int(seq))
+    return metadata, [int(s) for s in sequences]
+
+
+def make_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--infer-root', default=None, help="directory with %%06d.npy scans of the 'infer' subset (assets/pc)")
     ap.add_argument('--dataset-root', default=None, help='KITTI-style root (icp10/<seq> lists + downsampled_xyzi/)')
@@ -250,7 +269,20 @@ def main(argv=None):
                     help="add every pair's outlier-robust pose from its fine correspondences (maximum clique, GNC-TLS rotation, "
                          'truncated-least-squares translation) to the pair file as estimated_transform_robust')
     ap.add_argument('--noise-bound', '--noise_bound', type=float, default=0.01, help='noise bound of --robust (eval.py:200)')
+    ap.add_argument('--pair-lists', default=None, metavar='NAME',
+                    help='with --dataset-root: the pairs of the lists R/NAME/%%02d instead of icp10 and --subset, e.g. `loops` (what '
+                         '`python -m rdmnet_amd.prepare loops` writes); the pair files are the loop edges trajectory --optimize takes')
+    ap.add_argument('--sequences', type=int, nargs='+', default=None, help='the sequences of --pair-lists (default: every list there)')
+    return ap
+
+
+def main(argv=None):
+    ap = make_parser()
     args = ap.parse_args(argv)
+    if (args.pair_lists or args.sequences) and not (args.pair_lists and args.dataset_root):
+        ap.error('--pair-lists needs --dataset-root, --sequences needs --pair-lists')
+    if args.pair_lists and (args.infer_root or args.synthetic > 0):
+        ap.error('--pair-lists cannot be combined with --infer-root or --synthetic (they would take the pairs from elsewhere)')
 
     rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
     local_rank, local_world = int(os.environ.get('LOCAL_RANK', 0)), int(os.environ.get('LOCAL_WORLD_SIZE', world))
@@ -273,6 +305,10 @@ def main(argv=None):
         calib = base
     elif args.infer_root:
         data = ds_mod.OdometryKittiPairDataset('.', 'infer', infer_root=args.infer_root)
+        calib = data
+    elif args.dataset_root and args.pair_lists:
+        metadata, _ = pair_list_metadata(args.dataset_root, args.pair_lists, args.sequences)
+        data = ds_mod.OdometryKittiPairDataset(args.dataset_root, 'test', metadata=metadata)  # (any subset but 'infer': the lists' poses are used)
         calib = data
     elif args.dataset_root:
         data = ds_mod.OdometryKittiPairDataset(args.dataset_root, args.subset)

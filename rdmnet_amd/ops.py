@@ -665,6 +665,127 @@ def robust_registration(src_corr, ref_corr, noise_bound=0.01, cbar2=1.0, gnc_fac
                         hi[C:2 * C].copy() if return_graph else None, hi[2 * C:3 * C].copy() if return_graph else None)
 
 
+# ---- loop-closure detection: Scan Context (rdm_scan_context, rdm_scan_context_distance) ------------------------------------
+
+SCAN_CONTEXT_DEFAULTS = dict(n_rings=20, n_sectors=60, max_range=80.0, lidar_height=2.0)
+
+
+def _sc_dims(n_rings, n_sectors):
+    n_rings, n_sectors = int(n_rings), int(n_sectors)
+    if not (1 <= n_rings <= _lib.SCAN_CONTEXT_MAX_DIM and 1 <= n_sectors <= _lib.SCAN_CONTEXT_MAX_DIM):
+        raise ValueError(f'n_rings and n_sectors must be 1 ... {_lib.SCAN_CONTEXT_MAX_DIM}, got {n_rings} and {n_sectors}')
+    return n_rings, n_sectors
+
+
+def scan_context(clouds, offsets=None, *, n_rings=20, n_sectors=60, max_range=80.0, lidar_height=2.0, return_normalised=False):
+    """Scan Context place descriptors (rdm_scan_context) of a batch of clouds.  clouds: a list of float32
+    CUDA tensors [N_i, >=3] (empty ones allowed), or one packed float32 CUDA tensor [N, ld >= 3] with `offsets` (int64
+    [n + 1], host or device: cloud i is rows offsets[i] .. offsets[i + 1]).  -> float32 CUDA [n, n_rings, n_sectors]; with
+    return_normalised also the column-normalised form float32 [n, n_rings, 64] and the valid-column masks int64 [n] (bit j =
+    column j has a point).  A bin is the maximum z + lidar_height of its points and does not depend on their order.  The
+    packed form with device offsets enqueues two launches and nothing else; the list form first concatenates the clouds' xyz
+    columns on the device (one extra copy of all points; a single cloud is used as it is) and copies the host-built offsets to
+    the device, as host offsets in the packed form are.  The stream is never waited for."""
+    L = _lib.lib()
+    n_rings, n_sectors = _sc_dims(n_rings, n_sectors)
+    if not (float(max_range) > 0 and float(max_range) < float('inf')):
+        raise ValueError(f'max_range must be positive and finite, got {max_range}')
+    if offsets is None:
+        if not isinstance(clouds, (list, tuple)):
+            raise ValueError('scan_context: clouds must be a list of tensors, or a packed tensor with offsets')
+        for i, t in enumerate(clouds):
+            _points_arg(t, f'clouds[{i}]')
+        if len({t.device for t in clouds}) > 1:
+            raise ValueError('scan_context: the clouds are on different devices')
+        if not clouds:
+            raise ValueError('scan_context: an empty list of clouds has no device; pass a packed tensor with offsets')
+        counts = [int(t.shape[0]) for t in clouds]
+        points = clouds[0] if len(clouds) == 1 else torch.cat([t[:, :3] for t in clouds])
+        offsets = torch.tensor([0] + counts, dtype=torch.int64).cumsum(0)
+    else:
+        points = clouds
+        _points_arg(points, 'clouds')
+        if not (isinstance(offsets, torch.Tensor) and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.numel() >= 1):
+            raise ValueError('offsets must be an int64 tensor [n + 1]')
+    dev = points.device
+    n = offsets.numel() - 1
+    if n > 65535:
+        raise ValueError(f'scan_context: {n} clouds, a call takes at most 65535')
+    offsets = offsets.to(dev).contiguous()
+    ld = points.stride(0) if points.shape[0] > 1 else points.shape[1]
+    desc = torch.empty((n, n_rings, n_sectors), dtype=torch.float32, device=dev)
+    norm = torch.empty((n, n_rings, _lib.SCAN_CONTEXT_LD), dtype=torch.float32, device=dev) if return_normalised else None
+    valid = torch.empty((n,), dtype=torch.int64, device=dev) if return_normalised else None
+    with torch.cuda.device(dev):
+        ws = scratch(dev, L.rdm_scan_context_workspace_bytes(n, n_rings, n_sectors))
+        _lib.check(L.rdm_scan_context(points.data_ptr(), ld, points.shape[0], offsets.data_ptr(), n, n_rings, n_sectors,
+                                      float(max_range), float(lidar_height), desc.data_ptr(), _lib.ptr(norm), _lib.ptr(valid),
+                                      ws.data_ptr(), ws.numel(), _lib.stream_ptr()), 'rdm_scan_context')
+    return (desc, norm, valid) if return_normalised else desc
+
+
+class ScanContextSearch:
+    """rdm_scan_context_distance's outputs, CUDA tensors: per query `distance` (float32 [n_q]), `index` (int32: the eligible
+    candidate of lowest distance, the lowest among equals; -1 without one, then distance = +inf) and `shift` (int32: that
+    candidate's column shift; -1); with full=True also `distances` (float32 [n_q, n_c]) and `shifts` (int32 [n_q, n_c]) of every
+    pair, eligible or not."""
+
+    def __init__(self, distance, index, shift, distances=None, shifts=None):
+        self.distance, self.index, self.shift, self.distances, self.shifts = distance, index, shift, distances, shifts
+
+    def __repr__(self):
+        return f'ScanContextSearch(queries={self.distance.shape[0]}, full={self.distances is not None})'
+
+
+def _sc_desc(t, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3):
+        raise ValueError(f'{name} must be a float32 CUDA tensor [n, n_rings, n_sectors]')
+    if not t.is_contiguous():
+        raise ValueError(f'{name} must be contiguous')
+    return t
+
+
+def scan_context_distance(q_desc, c_desc, *, q_base=0, c_base=0, exclude_recent=50, full=False):
+    """Exhaustive Scan Context search (rdm_scan_context_distance): every query descriptor against every candidate under every
+    column shift.  q_desc / c_desc: float32 CUDA [n_q | n_c, n_rings, n_sectors] (ops.scan_context).  Query i is frame q_base +
+    i, candidate j frame c_base + j; j is eligible for i iff (q_base + i) - (c_base + j) >= exclude_recent (negative: all
+    are).  -> ScanContextSearch.  No synchronisation."""
+    L = _lib.lib()
+    q_desc, c_desc = _sc_desc(q_desc, 'q_desc'), _sc_desc(c_desc, 'c_desc')
+    if q_desc.device != c_desc.device or q_desc.shape[1:] != c_desc.shape[1:]:
+        raise ValueError(f'scan_context_distance: q_desc {tuple(q_desc.shape)} on {q_desc.device} against c_desc '
+                         f'{tuple(c_desc.shape)} on {c_desc.device}')
+    n_rings, n_sectors = _sc_dims(q_desc.shape[1], q_desc.shape[2])
+    dev, n_q, n_c = q_desc.device, q_desc.shape[0], c_desc.shape[0]
+    best = torch.empty((3, max(n_q, 1)), dtype=torch.int32, device=dev)  # distance bits, index, shift
+    distance, index, shift = best[0, :n_q].view(torch.float32), best[1, :n_q], best[2, :n_q]
+    dists = torch.empty((n_q, n_c), dtype=torch.float32, device=dev) if full else None
+    shifts = torch.empty((n_q, n_c), dtype=torch.int32, device=dev) if full else None
+    with torch.cuda.device(dev):
+        nbytes = L.rdm_scan_context_distance_workspace_bytes(n_q, n_c, n_rings, n_sectors)
+        if nbytes == 0:
+            raise ValueError(f'scan_context_distance: {n_c} candidates, a call takes at most 2^26')
+        ws = scratch(dev, nbytes)
+        _lib.check(L.rdm_scan_context_distance(q_desc.data_ptr(), n_q, c_desc.data_ptr(), n_c, n_rings, n_sectors, int(q_base),
+                                               int(c_base), int(exclude_recent), distance.data_ptr(), index.data_ptr(),
+                                               shift.data_ptr(), _lib.ptr(dists), _lib.ptr(shifts), ws.data_ptr(), ws.numel(),
+                                               _lib.stream_ptr()), 'rdm_scan_context_distance')
+    return ScanContextSearch(distance, index, shift, dists, shifts)
+
+
+def detect_loops(descriptors, threshold=0.13, exclude_recent=50):
+    """Loop closures of one sequence: every descriptor (float32 CUDA [n, n_rings, n_sectors], frame order) against every
+    earlier one that is at least `exclude_recent` frames older; a loop is accepted iff its distance < threshold.  -> host
+    arrays (query int64, candidate int64, distance float32, shift int64, yaw_deg float64), in query order; yaw_deg = shift x 360
+    / n_sectors is the rotation about z that takes the candidate scan to the query scan.  One read-back."""
+    import numpy as np
+    res = scan_context_distance(descriptors, descriptors, exclude_recent=exclude_recent)
+    host = torch.stack([res.distance.view(torch.int32), res.index, res.shift]).cpu().numpy()
+    dist, index, shift = host[0].view(np.float32), host[1].astype(np.int64), host[2].astype(np.int64)
+    query = np.nonzero((index >= 0) & (dist.astype(np.float64) < float(threshold)))[0].astype(np.int64)
+    return (query, index[query], dist[query].copy(), shift[query], shift[query] * (360.0 / descriptors.shape[2]))
+
+
 class RegistrationResult:
     """Named as Open3D's: transformation (float64 [4, 4], numpy), fitness, inlier_rmse, num_correspondences (of the last
     evaluation), iterations (updates applied) and, when asked for, history (float64 [evaluations, 15] numpy: per

@@ -15,6 +15,16 @@
       `radius` (geotransformer/utils/registration.py:191-216) on the GPU (ops.pair_overlap: one count pass, no list), the
       number the reference's loop-closure protocol selects pairs by (experiments/test_batchoffline.py:246).
 
+  python -m rdmnet_amd.prepare loops --dataset-root R [--sequences 0 ... 10] [--threshold 0.13] [--exclude-recent 50] [--raw]
+                                     [--batch 64]
+      R/downsampled_xyzi/%02d/*.npy (the tree `infer` reads; --raw: R/sequences/%02d/velodyne/*.bin) -> R/loops/%02d and
+      R/loops/%02d.scores: loop-closure detection.  One Scan Context descriptor per scan (ops.scan_context, in batches), every scan
+      against every scan at least --exclude-recent frames older under all column shifts on the GPU (ops.detect_loops: exhaustive,
+      no prefilter); a loop is accepted below --threshold.  R/loops/%02d has the format of icp10, `query candidate` + the pose
+      that maps the query scan into the candidate's frame, so `infer --pair-lists loops` reads it (src = query, ref = candidate):
+      the ground-truth pose when R/poses/%02d.txt and the calib file exist, else the yaw-only guess Rz(-shift 360 / 60 deg).
+      R/loops/%02d.scores: `query candidate distance shift yaw_deg` per loop.  Not in the reference.
+
 Stated deviations from the reference's pair script:
   * the pair file is written fresh; the reference appends to it (its `open(..., 'a')`), so a rerun doubles it;
   * the odometry pose M is handed to the ICP as its `init` instead of being applied to the scan on the host first: the
@@ -248,6 +258,98 @@ def overlap_sequence(root, seq, distance=10, radius=0.6, workers=4, log=print):
     return out
 
 
+LOOP_DEFAULTS = dict(threshold=0.13, exclude_recent=50, batch=64)
+LOOP_SECTORS = 60  # ops.scan_context's default n_sectors: one column shift is 6 degrees
+
+
+def scan_list(root, seq, raw=False):
+    """[(frame, path)] of a sequence in frame order: R/downsampled_xyzi/%02d/*.npy, or with `raw` R/sequences/%02d/velodyne/*.bin."""
+    folder = _velodyne(root, seq) if raw else osp.join(root, 'downsampled_xyzi', '%02d' % seq)
+    ext = '.bin' if raw else '.npy'
+    files = glob.glob(osp.join(folder, '*' + ext))
+    if not files:
+        raise FileNotFoundError(f'no scans under {folder}')
+    return sorted((int(osp.basename(f)[:-len(ext)]), f) for f in files)
+
+
+def load_scan_xyz(path):
+    """One scan of either tree -> f32 [N, 3]."""
+    pts = np.fromfile(path, dtype=np.float32).reshape(-1, 4) if path.endswith('.bin') else np.load(path)
+    return np.ascontiguousarray(pts[:, :3], dtype=np.float32)
+
+
+def yaw_transform(shift, n_sectors=LOOP_SECTORS):
+    """The yaw-only pose guess of a loop: the query scan is the candidate turned by +shift sectors about z, so Rz(-shift 360 /
+    n_sectors degrees) maps the query into the candidate's frame."""
+    a = -2.0 * np.pi * shift / n_sectors
+    T = np.eye(4)
+    T[:2, :2] = [[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]]
+    return T
+
+
+def loop_ground_truth(root, seq):
+    """(velo2cam, poses) when R/poses/%02d.txt and R/calib/sequences/%02d/calib.txt exist, else None."""
+    poses, calib = osp.join(root, 'poses', '%02d.txt' % seq), osp.join(root, 'calib', 'sequences', '%02d' % seq, 'calib.txt')
+    if not (osp.isfile(poses) and osp.isfile(calib)):
+        return None
+    return read_velo2cam(calib), read_poses(poses)
+
+
+def loop_transform(gt, query, candidate, shift, n_sectors=LOOP_SECTORS):
+    """The pose written for a loop (frame ids): relative_transform of the ground truth (query -> candidate), else yaw_transform."""
+    if gt is None:
+        return yaw_transform(shift, n_sectors)
+    velo2cam, poses = gt
+    if max(query, candidate) >= poses.shape[0]:
+        raise ValueError(f'frame {max(query, candidate)} has no pose (the pose file has {poses.shape[0]} rows)')
+    return relative_transform(velo2cam, poses[query], poses[candidate])
+
+
+def format_score_line(query, candidate, distance, shift, yaw_deg):
+    return f'{query} {candidate} {distance:.6f} {shift} {yaw_deg:.1f}\n'
+
+
+def sequence_descriptors(root, seq, raw=False, batch=LOOP_DEFAULTS['batch']):
+    """-> (frame ids, descriptors float32 CUDA [F, 20, 60]): the scans are read `batch` at a time on a background thread while the
+    previous batch is on the GPU; a batch is one host-to-device copy and one ops.scan_context call."""
+    import torch
+    from . import ops
+    scans = scan_list(root, seq, raw)
+    batches = [tuple(scans[i:i + batch]) for i in range(0, len(scans), batch)]
+
+    def load(group):
+        clouds = [load_scan_xyz(path) for _, path in group]
+        offsets = np.concatenate([[0], np.cumsum([len(c) for c in clouds])]).astype(np.int64)
+        return np.concatenate(clouds) if clouds else np.zeros((0, 3), np.float32), offsets
+
+    out = []
+    for _, (points, offsets) in _read_ahead(load, batches):
+        out.append(ops.scan_context(torch.from_numpy(points).cuda(), torch.from_numpy(offsets)))
+    return [f for f, _ in scans], torch.cat(out)
+
+
+def detect_sequence_loops(root, seq, threshold=LOOP_DEFAULTS['threshold'], exclude_recent=LOOP_DEFAULTS['exclude_recent'], raw=False,
+                          batch=LOOP_DEFAULTS['batch'], log=print):
+    """R/loops/%02d and R/loops/%02d.scores for one sequence -> [(query, candidate, distance, shift, yaw_deg)] (frame ids).  Scans
+    are compared by their position in frame order, which is the frame id in a complete sequence."""
+    from . import ops
+    ids, desc = sequence_descriptors(root, seq, raw, batch)
+    loops = list(zip(*ops.detect_loops(desc, threshold, exclude_recent)))
+    gt = loop_ground_truth(root, seq)
+    out_dir = osp.join(root, 'loops')
+    os.makedirs(out_dir, exist_ok=True)
+    out = []
+    with open(osp.join(out_dir, '%02d' % seq), 'w') as f, open(osp.join(out_dir, '%02d.scores' % seq), 'w') as g:
+        for q, c, d, s, yaw in loops:
+            query, cand = ids[int(q)], ids[int(c)]
+            out.append((query, cand, float(d), int(s), float(yaw)))
+            f.write(format_pair_line(query, cand, loop_transform(gt, query, cand, int(s), desc.shape[2])))
+            g.write(format_score_line(*out[-1]))
+    log(f'sequence {seq:02d}: {len(ids)} scans, {len(out)} loops written to {osp.join(out_dir, "%02d" % seq)} with '
+        + ('ground-truth poses' if gt is not None else 'yaw-only pose guesses (no poses / calib file)'))
+    return out
+
+
 def _parser():
     p = argparse.ArgumentParser(prog='python -m rdmnet_amd.prepare', description=__doc__.split('\n\n')[0])
     sub = p.add_subparsers(dest='command', required=True)
@@ -268,6 +370,14 @@ def _parser():
     o.add_argument('--distance', type=int, default=10, help='the pair lists to read: icp{distance} (default 10)')
     o.add_argument('--radius', type=float, default=0.6, help='matching radius in metres (default 0.6)')
     o.add_argument('--workers', type=int, default=4, help='host threads that read scans ahead (default 4, at most 16)')
+    lp = sub.add_parser('loops', help='scans -> loops/%%02d pair lists: Scan Context loop-closure detection, exhaustive on the GPU')
+    lp.add_argument('--dataset-root', required=True)
+    lp.add_argument('--sequences', type=int, nargs='+', default=list(range(11)))
+    lp.add_argument('--threshold', type=float, default=LOOP_DEFAULTS['threshold'], help='a loop is accepted below this distance (default 0.13)')
+    lp.add_argument('--exclude-recent', type=int, default=LOOP_DEFAULTS['exclude_recent'],
+                    help='a candidate is at least this many frames older than its query (default 50; negative: any frame)')
+    lp.add_argument('--raw', action='store_true', help='read sequences/%%02d/velodyne/*.bin instead of downsampled_xyzi/%%02d/*.npy')
+    lp.add_argument('--batch', type=int, default=LOOP_DEFAULTS['batch'], help='scans per descriptor call (default 64)')
     return p
 
 
@@ -286,6 +396,14 @@ def main(argv=None):
         return 0
     if any(s < 0 for s in a.sequences):
         p.error('sequences must be >= 0')
+    if a.command == 'loops':
+        if not a.threshold > 0:
+            p.error('--threshold must be > 0')
+        if not 1 <= a.batch <= 65535:
+            p.error('--batch must be 1 ... 65535')
+        for s in a.sequences:
+            detect_sequence_loops(a.dataset_root, s, a.threshold, a.exclude_recent, a.raw, a.batch)
+        return 0
     if a.command == 'pairs':
         if a.thres < 0:
             p.error('--thres must be >= 0')
