@@ -1084,6 +1084,51 @@ int rdm_scan_context_distance(const float* q_desc, int64_t n_q, const float* c_d
                               int64_t q_base, int64_t c_base, int64_t exclude_recent, float* best_distance, int32_t* best_index,
                               int32_t* best_shift, float* dist, int32_t* shift, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- §7 voxel map: the scans of a sequence fused under its trajectory (voxel_map.hip) -----------------------------------
+ * Not in the reference tree -> parity unpinned; the project's own definition, pinned bit for bit to the
+ * NumPy restatement tests/voxel_map_restatement.py.  A map has a voxel size `voxel` (> 0), C = `channels` (3 ... 8: xyz and C - 3
+ * attributes) and F = RDM_VOXEL_MAP_FRAC_BITS fractional bits.  Per point p (fp32 row) of a scan with pose X (f64 [4, 4] row-major,
+ * world = X p), everything in float64 without contraction:
+ *   gate      r2 = (x x + y y) + z z in the sensor frame; a row with a non-finite value among its C is counted in
+ *             skipped_nonfinite, else one without min_range^2 <= r2 <= max_range^2 in skipped_range;
+ *   transform w_d = ((X[d][0] x + X[d][1] y) + X[d][2] z) + X[d][3];
+ *   quantise  Q_d = (int64) floor(w_d / voxel 2^F), cell_d = Q_d >> F (cell c covers [c voxel, (c + 1) voxel), anchored at the
+ *             world origin); A_k = llrint(v_k 2^F) for the attributes; a point with a cell outside [-2^20, 2^20) (a non-finite w_d
+ *             included) or |v_k| >= 2^20 is counted in out_of_extent;
+ *   add       into the voxel of key ((cell_x + 2^20) << 42) | ((cell_y + 2^20) << 21) | (cell_z + 2^20): a uint32 count and C
+ *             int64 sums of Q_d / A_k, by integer atomic adds -- the map is a function of the SET of integrated points: the order
+ *             of the scans, the batching, the schedule and the run do not change one bit.  (A count wraps at 2^32 points.)
+ * The map lives in ONE caller-owned device block of rdm_voxel_map_bytes(capacity, channels) bytes (0 for a bad shape): capacity
+ * a power of two in [64, 2^30]; six uint64 counters {occupied, integrated, skipped_nonfinite, skipped_range, out_of_extent,
+ * dropped_full}, then keys uint64 [S] (all ones = empty), counts uint32 [S], sums int64 [C][S] (each 256-byte aligned): open
+ * addressing, linear probing from the home slot fmix64(key) & (S - 1) (MurmurHash3's 64-bit finaliser), 12 + 8 C bytes a slot.  Every function takes (map, map_bytes, capacity, channels) and checks them.
+ * rdm_voxel_map_reset empties the map (a fresh block must be reset).  rdm_voxel_map_integrate: one launch for a packed batch --
+ * points device f32 [total, ld >= C], offsets device int64 [n_scans + 1] (scan s = rows offsets[s] .. offsets[s + 1], ascending,
+ * clamped to [0, total]; empty scans and n_scans = 0 are valid), poses device f64 [n_scans, 16].  The probe is bounded: a point
+ * that finds neither its key nor an empty slot in one full cycle is counted in dropped_full and changes nothing else, so a key
+ * is stored with all of its points or not at all (slots only go from empty to a key, so a key that found the table full finds it
+ * full ever after; callers keep capacity >= 2 (occupied + batch)).  rdm_voxel_map_rehash: resets new_map (another block,
+ * new_capacity >= old_capacity) and moves every occupied slot and the counters into it.  rdm_voxel_map_stats: the six counters
+ * to HOST memory; waits for the stream.  rdm_voxel_map_extract: the voxels with count >= min_points in ascending key order --
+ * points f32 [max_rows, C]: (float)((double)sum / (double)count / 2^F voxel) for xyz, the same without voxel for the attributes;
+ * counts int32 [max_rows]; cells int32 [max_rows, 3]; *n_rows (device int64) = the number of such voxels, of which the first
+ * min(*n_rows, max_rows) are written.  No float atomics and no unbounded loop anywhere.                                        */
+#define RDM_VOXEL_MAP_FRAC_BITS 20
+#define RDM_VOXEL_MAP_MAX_CHANNELS 8
+#define RDM_VOXEL_MAP_STATS 6
+size_t rdm_voxel_map_bytes(int64_t capacity, int channels);
+int rdm_voxel_map_reset(void* map, size_t map_bytes, int64_t capacity, int channels, void* stream);
+int rdm_voxel_map_integrate(void* map, size_t map_bytes, int64_t capacity, int channels, double voxel, const float* points, int64_t ld,
+                            int64_t total, const int64_t* offsets, const double* poses, int64_t n_scans, double min_range,
+                            double max_range, void* stream);
+int rdm_voxel_map_rehash(const void* old_map, size_t old_bytes, int64_t old_capacity, void* new_map, size_t new_bytes,
+                         int64_t new_capacity, int channels, void* stream);
+int rdm_voxel_map_stats(const void* map, size_t map_bytes, int64_t capacity, int channels, uint64_t* stats, void* stream);
+size_t rdm_voxel_map_extract_workspace_bytes(int64_t capacity);
+int rdm_voxel_map_extract(const void* map, size_t map_bytes, int64_t capacity, int channels, double voxel, int64_t min_points,
+                          float* points, int32_t* counts, int32_t* cells, int64_t max_rows, int64_t* n_rows, void* ws, size_t ws_bytes,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

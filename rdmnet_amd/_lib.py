@@ -51,7 +51,12 @@ ROBUST_STATS = ('num_selected', 'valid', 'exact', 'iterations', 'translation_inl
 SCAN_CONTEXT_MAX_DIM = 64  # = RDM_SCAN_CONTEXT_MAX_DIM: n_rings, n_sectors <= this
 SCAN_CONTEXT_LD = 64  # = RDM_SCAN_CONTEXT_LD: columns of a row of the normalised descriptors
 
-EVAL_RECORD_WIDTH = 20  # = RDM_EVAL_RECORD_WIDTH
+VOXEL_MAP_FRAC_BITS = 20  # = RDM_VOXEL_MAP_FRAC_BITS
+VOXEL_MAP_MAX_CHANNELS = 8  # = RDM_VOXEL_MAP_MAX_CHANNELS
+# rdm_voxel_map_stats' counters, in order (RDM_VOXEL_MAP_STATS of them)
+VOXEL_MAP_STATS = ('occupied', 'integrated', 'skipped_nonfinite', 'skipped_range', 'out_of_extent', 'dropped_full')
+
+EVAL_RECORD_WIDTH = 20 # = RDM_EVAL_RECORD_WIDTH
 # the fields of one record of rdm_eval_pairs, in order
 EVAL_FIELDS = ('num_corr', 'residual', 'inlier_ratio', 'inlier_ratio_0.3', 'inlier_ratio_0.1', 'overlap', 'precision', 'rre', 'rte',
                'rx', 'ry', 'rz', 'inliers', 'inliers_0.3', 'inliers_0.1', 'overlap_rows', 'hit_cells', 'pred_cells', 'gt_cells',
@@ -263,6 +268,15 @@ SIGNATURES = {
     'rdm_scan_context_distance_workspace_bytes': (c_size, [c_i64, c_i64, c_int, c_int]),
     'rdm_scan_context_distance': (c_int, [c_void, c_i64, c_void, c_i64, c_int, c_int, c_i64, c_i64, c_i64, c_void, c_void, c_void,
                                           c_void, c_void, c_void, c_size, c_void]),
+    'rdm_voxel_map_bytes': (c_size, [c_i64, c_int]),
+    'rdm_voxel_map_reset': (c_int, [c_void, c_size, c_i64, c_int, c_void]),
+    'rdm_voxel_map_integrate': (c_int, [c_void, c_size, c_i64, c_int, ctypes.c_double, c_void, c_i64, c_i64, c_void, c_void, c_i64,
+                                        ctypes.c_double, ctypes.c_double, c_void]),
+    'rdm_voxel_map_rehash': (c_int, [c_void, c_size, c_i64, c_void, c_size, c_i64, c_int, c_void]),
+    'rdm_voxel_map_stats': (c_int, [c_void, c_size, c_i64, c_int, c_void, c_void]),
+    'rdm_voxel_map_extract_workspace_bytes': (c_size, [c_i64]),
+    'rdm_voxel_map_extract': (c_int, [c_void, c_size, c_i64, c_int, ctypes.c_double, c_i64, c_void, c_void, c_void, c_i64, c_void,
+                                      c_void, c_size, c_void]),
 }
 
 

@@ -1,0 +1,384 @@
+// Voxel map: the scans of a sequence fused under its trajectory into one persistent hash table in world coordinates
+// (include/rdmnet_hip.h, "voxel map").  The project's own definition, pinned bit for bit to the NumPy
+// restatement tests/voxel_map_restatement.py.
+//
+// Table: open addressing with linear probing over a power-of-two number of slots, structure of arrays behind a block of six
+// uint64 counters: keys uint64 [S] (all ones = empty), counts uint32 [S], C planes of int64 sums [C][S]; 12 + 8 C bytes a slot.
+// A key is the three cells + 2^20 at 21 bits each, so it never equals the empty word.  Slots only ever go from empty to a key
+// (one 64-bit compare-and-swap), which is what makes the lock-free insert exact: the first slot of a key's probe sequence that
+// is empty or holds the key is the same for every thread that looks for it, whenever it looks.
+//
+// Integrate: one thread per point.  The point's scan is found by a bisection of the offsets (17 steps at 65 536 scans), the
+// pose is read from the device, the transform and the quantisation are float64 with the restatement's association and no
+// contraction, and the point lands in its voxel as one uint32 and C int64 atomic adds of fixed-point values: integer sums are
+// associative, so the map depends on the set of points and on nothing else.  No merge of equal keys inside a wavefront
+// before the atomics: the plain form is the one that was measured (docs/EXPERIMENTS.md).  The probe is bounded by the capacity;
+// a point that finds neither its key nor an empty slot in one full cycle is counted in dropped_full and touches nothing.
+//
+// Extract: slot -> (key or all ones, slot), one radix sort of the S pairs (the unselected sort to the end; no read-back of
+// the count is needed before the sort), then one thread per selected row.
+#include <cmath>
+
+#include "../../include/rdmnet_hip.h"
+#include "cell_index.h"
+#include "common.h"
+
+namespace rdm {
+namespace {
+
+constexpr int kFrac = RDM_VOXEL_MAP_FRAC_BITS;
+constexpr int kMaxC = RDM_VOXEL_MAP_MAX_CHANNELS;
+constexpr int kStats = RDM_VOXEL_MAP_STATS;
+constexpr int kBlock = 256;
+constexpr unsigned kMaxBlocks = 1u << 20;  // the point and slot kernels stride over at most this many blocks
+constexpr unsigned long long kEmpty = ~0ull;
+constexpr long long kHalf = 1ll << 20;               // cells lie in [-2^20, 2^20)
+constexpr double kScale = 1048576.0;                 // 2^kFrac
+constexpr double kQLimit = 1099511627776.0;          // 2^40 = 2^20 cells of 2^20 steps
+constexpr int64_t kMaxCapacity = int64_t(1) << 30;   // slots are sorted as int32 values under a 32-bit count
+static_assert(kFrac == 20, "the key layout and kQLimit assume 20 fractional bits");
+
+enum { kOccupied = 0, kIntegrated, kNonfinite, kRange, kExtent, kDropped };
+
+struct Table {
+  unsigned long long* counters;  // [kStats]
+  unsigned long long* keys;      // [S]
+  uint32_t* counts;              // [S]
+  unsigned long long* sums;      // [C][S], two's-complement int64
+};
+
+bool shape_ok(int64_t capacity, int channels) {
+  return capacity >= 64 && capacity <= kMaxCapacity && (capacity & (capacity - 1)) == 0 && channels >= 3 && channels <= kMaxC;
+}
+
+bool carve(Arena& ar, int64_t capacity, int channels, Table& t) {
+  const size_t s = static_cast<size_t>(capacity);
+  t.counters = ar.take<unsigned long long>(kStats);
+  t.keys = ar.take<unsigned long long>(s);
+  t.counts = ar.take<uint32_t>(s);
+  t.sums = ar.take<unsigned long long>(s * channels);
+  return ar.ok;
+}
+
+__device__ __forceinline__ unsigned long long mix(unsigned long long k) {  // the 64-bit finaliser of MurmurHash3
+  k ^= k >> 33;
+  k *= 0xff51afd7ed558ccdull;
+  k ^= k >> 33;
+  k *= 0xc4ceb9fe1a85ec53ull;
+  k ^= k >> 33;
+  return k;
+}
+
+// The slot of `key`, claimed if it is new (*claimed = 1), or -1 after one full cycle without the key or an empty slot.
+__device__ __forceinline__ long long find_or_claim(unsigned long long* __restrict__ keys, long long capacity, unsigned long long key,
+                                                   int* claimed) {
+  const unsigned long long mask = static_cast<unsigned long long>(capacity) - 1ull;
+  unsigned long long slot = mix(key) & mask;
+  *claimed = 0;
+  for (long long probe = 0; probe < capacity; ++probe) {
+    unsigned long long k = ld_agent(keys + slot);
+    if (k == kEmpty) {
+      k = atomicCAS(keys + slot, kEmpty, key);
+      if (k == kEmpty) {
+        *claimed = 1;
+        return static_cast<long long>(slot);
+      }
+    }
+    if (k == key) return static_cast<long long>(slot);
+    slot = (slot + 1ull) & mask;
+  }
+  return -1;
+}
+
+__global__ void __launch_bounds__(kBlock) reset_kernel(Table t, long long capacity, int channels) {
+  const long long stride = static_cast<long long>(gridDim.x) * kBlock;
+  const long long first = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
+  if (first < kStats) t.counters[first] = 0ull;
+  for (long long i = first; i < capacity; i += stride) {
+    t.keys[i] = kEmpty;
+    t.counts[i] = 0u;
+    for (int c = 0; c < channels; ++c) t.sums[c * capacity + i] = 0ull;
+  }
+}
+
+// the number of offsets[1 .. n_scans] that are <= i: the scan of row i when offsets ascend (empty scans are passed over)
+__device__ __forceinline__ long long scan_of(const int64_t* __restrict__ offsets, long long n_scans, long long i) {
+  long long lo = 0, n = n_scans;
+  while (n > 0) {
+    const long long half = n >> 1;
+    if (offsets[lo + half + 1] <= i) {
+      lo += half + 1;
+      n -= half + 1;
+    } else {
+      n = half;
+    }
+  }
+  return lo;
+}
+
+__global__ void __launch_bounds__(kBlock) integrate_kernel(Table t, long long capacity, int channels, double voxel,
+                                                           const float* __restrict__ points, long long ld, long long total,
+                                                           const int64_t* __restrict__ offsets, const double* __restrict__ poses,
+                                                           long long n_scans, double lo2, double hi2) {
+#pragma clang fp contract(off)
+  __shared__ unsigned int tally[kStats];
+  if (threadIdx.x < kStats) tally[threadIdx.x] = 0u;
+  __syncthreads();
+  const long long stride = static_cast<long long>(gridDim.x) * kBlock;
+  long long begin = offsets[0], end = offsets[n_scans];
+  begin = begin < 0 ? 0 : begin;
+  end = end > total ? total : end;  // (a bad offsets array reads nothing outside the batch)
+  for (long long i = begin + static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < end; i += stride) {
+    const float* p = points + i * ld;
+    float v[kMaxC];
+    bool finite = true;
+    for (int c = 0; c < kMaxC; ++c) {
+      v[c] = c < channels ? p[c] : 0.f;
+      finite = finite && isfinite(v[c]);
+    }
+    if (!finite) {
+      atomicAdd(&tally[kNonfinite], 1u);
+      continue;
+    }
+    const double x = v[0], y = v[1], z = v[2];
+    const double r2 = (x * x + y * y) + z * z;
+    if (!(lo2 <= r2 && r2 <= hi2)) {
+      atomicAdd(&tally[kRange], 1u);
+      continue;
+    }
+    const long long scan = scan_of(offsets, n_scans, i);
+    if (scan >= n_scans) continue;  // (offsets that do not ascend)
+    const double* X = poses + scan * 16;
+    long long q[kMaxC];
+    bool inside = true;
+    unsigned long long key = 0ull;
+    for (int d = 0; d < 3; ++d) {
+      const double w = ((X[4 * d] * x + X[4 * d + 1] * y) + X[4 * d + 2] * z) + X[4 * d + 3];
+      const double f = floor(w / voxel * kScale);
+      const bool ok = f >= -kQLimit && f < kQLimit;  // (NaN and infinities fail)
+      inside = inside && ok;
+      q[d] = ok ? static_cast<long long>(f) : 0ll;
+      key = (key << 21) | static_cast<unsigned long long>((q[d] >> kFrac) + kHalf);
+    }
+    for (int c = 3; c < kMaxC; ++c) {
+      const double a = v[c];
+      inside = inside && fabs(a) < kScale;
+      q[c] = llrint(a * kScale);  // (finite; used only when inside)
+    }
+    if (!inside) {
+      atomicAdd(&tally[kExtent], 1u);
+      continue;
+    }
+    int claimed;
+    const long long slot = find_or_claim(t.keys, capacity, key, &claimed);
+    if (slot < 0) {
+      atomicAdd(&tally[kDropped], 1u);
+      continue;
+    }
+    if (claimed) atomicAdd(&tally[kOccupied], 1u);
+    atomicAdd(&tally[kIntegrated], 1u);
+    atomicAdd(t.counts + slot, 1u);
+    for (int c = 0; c < kMaxC; ++c)
+      if (c < channels) atomicAdd(t.sums + c * capacity + slot, static_cast<unsigned long long>(q[c]));
+  }
+  __syncthreads();
+  if (threadIdx.x < kStats && tally[threadIdx.x] != 0u)
+    atomicAdd(t.counters + threadIdx.x, static_cast<unsigned long long>(tally[threadIdx.x]));
+}
+
+// Every occupied slot of `a` into `b` (reset before): the keys are distinct, so a slot is claimed once and filled with plain stores.
+__global__ void __launch_bounds__(kBlock) rehash_kernel(Table a, long long cap_a, Table b, long long cap_b, int channels) {
+  const long long stride = static_cast<long long>(gridDim.x) * kBlock;
+  const long long first = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
+  if (first < kStats) b.counters[first] = a.counters[first];
+  for (long long i = first; i < cap_a; i += stride) {
+    const unsigned long long key = a.keys[i];
+    if (key == kEmpty) continue;
+    int claimed;
+    const long long slot = find_or_claim(b.keys, cap_b, key, &claimed);
+    if (slot < 0 || !claimed) continue;  // (cap_b >= cap_a and distinct keys: not reached)
+    b.counts[slot] = a.counts[i];
+    for (int c = 0; c < channels; ++c) b.sums[c * cap_b + slot] = a.sums[c * cap_a + i];
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) select_kernel(Table t, long long capacity, unsigned int min_points,
+                                                        unsigned long long* __restrict__ keys, int* __restrict__ slots,
+                                                        unsigned long long* __restrict__ n_rows) {
+  __shared__ unsigned int picked;
+  if (threadIdx.x == 0) picked = 0u;
+  __syncthreads();
+  const long long stride = static_cast<long long>(gridDim.x) * kBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < capacity; i += stride) {
+    const unsigned long long key = t.keys[i];
+    const bool take = key != kEmpty && t.counts[i] >= min_points;
+    keys[i] = take ? key : kEmpty;
+    slots[i] = static_cast<int>(i);
+    if (take) atomicAdd(&picked, 1u);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && picked != 0u) atomicAdd(n_rows, static_cast<unsigned long long>(picked));
+}
+
+__global__ void __launch_bounds__(kBlock) emit_kernel(Table t, long long capacity, int channels, double voxel,
+                                                      const unsigned long long* __restrict__ keys, const int* __restrict__ slots,
+                                                      const unsigned long long* __restrict__ n_sel, long long max_rows,
+                                                      float* __restrict__ points, int32_t* __restrict__ counts,
+                                                      int32_t* __restrict__ cells, int64_t* __restrict__ n_rows) {
+#pragma clang fp contract(off)
+  const long long stride = static_cast<long long>(gridDim.x) * kBlock;
+  const long long first = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
+  const long long m = static_cast<long long>(*n_sel);
+  if (first == 0) *n_rows = m;
+  const long long rows = m < max_rows ? m : max_rows;
+  for (long long r = first; r < rows; r += stride) {
+    const unsigned long long key = keys[r];
+    const long long slot = slots[r];
+    const uint32_t n = t.counts[slot];
+    counts[r] = static_cast<int32_t>(n);
+    for (int d = 0; d < 3; ++d) cells[3 * r + d] = static_cast<int32_t>(static_cast<long long>((key >> (21 * (2 - d))) & 0x1fffffull) - kHalf);
+    for (int c = 0; c < channels; ++c) {
+      const double mean = static_cast<double>(static_cast<long long>(t.sums[c * capacity + slot])) / static_cast<double>(n) / kScale;
+      points[r * channels + c] = static_cast<float>(c < 3 ? mean * voxel : mean);
+    }
+  }
+}
+
+unsigned blocks_for(int64_t n) {
+  const int64_t b = (n + kBlock - 1) / kBlock;
+  return static_cast<unsigned>(b < 1 ? 1 : (b > static_cast<int64_t>(kMaxBlocks) ? kMaxBlocks : b));
+}
+
+struct ExtractWork {
+  unsigned long long *keys_in, *keys, *n_sel;
+  int *slots_in, *slots;
+  void* sort_tmp;
+  size_t sort_bytes;
+};
+
+bool carve_extract(Arena& ar, int64_t capacity, ExtractWork& w) {
+  const size_t s = static_cast<size_t>(capacity);
+  w.n_sel = ar.take<unsigned long long>(1);
+  w.keys_in = ar.take<unsigned long long>(s);
+  w.keys = ar.take<unsigned long long>(s);
+  w.slots_in = ar.take<int>(s);
+  w.slots = ar.take<int>(s);
+  w.sort_bytes = sort_temp_bytes(capacity);
+  w.sort_tmp = ar.take<char>(w.sort_bytes > 0 ? w.sort_bytes : 1);
+  return ar.ok;
+}
+
+// the table of a caller's block, or the error code after set_error
+int open_table(const char* what, void* map, size_t map_bytes, int64_t capacity, int channels, Table& t) {
+  RDM_REQUIRE(shape_ok(capacity, channels),
+              "%s: capacity must be a power of two in [64, 2^30] and channels 3 ... %d, got %lld and %d", what, kMaxC,
+              static_cast<long long>(capacity), channels);
+  RDM_REQUIRE(map != nullptr, "%s: null map", what);
+  Arena ar(map, map_bytes);
+  if (!carve(ar, capacity, channels, t)) {
+    set_error("%s: the map block is too small (%zu < %zu bytes)", what, map_bytes, ar.off);
+    return RDM_ERR_WORKSPACE;
+  }
+  return RDM_OK;
+}
+
+}  // namespace
+}  // namespace rdm
+
+extern "C" size_t rdm_voxel_map_bytes(int64_t capacity, int channels) {
+  using namespace rdm;
+  if (!shape_ok(capacity, channels)) return 0;
+  Arena ar(nullptr, 0);
+  Table t;
+  carve(ar, capacity, channels, t);
+  return ar.off;
+}
+
+extern "C" int rdm_voxel_map_reset(void* map, size_t map_bytes, int64_t capacity, int channels, void* stream) {
+  using namespace rdm;
+  Table t;
+  if (const int rc = open_table("rdm_voxel_map_reset", map, map_bytes, capacity, channels, t)) return rc;
+  hipLaunchKernelGGL(reset_kernel, dim3(blocks_for(capacity)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), t,
+                     static_cast<long long>(capacity), channels);
+  return launch_status("rdm_voxel_map_reset");
+}
+
+extern "C" int rdm_voxel_map_integrate(void* map, size_t map_bytes, int64_t capacity, int channels, double voxel, const float* points,
+                                       int64_t ld, int64_t total, const int64_t* offsets, const double* poses, int64_t n_scans,
+                                       double min_range, double max_range, void* stream) {
+  using namespace rdm;
+  Table t;
+  if (const int rc = open_table("rdm_voxel_map_integrate", map, map_bytes, capacity, channels, t)) return rc;
+  RDM_REQUIRE(voxel > 0.0 && std::isfinite(voxel), "rdm_voxel_map_integrate: voxel must be positive and finite");
+  RDM_REQUIRE(n_scans >= 0 && total >= 0 && ld >= channels, "rdm_voxel_map_integrate: bad sizes (ld must be >= channels)");
+  RDM_REQUIRE(min_range >= 0.0 && max_range >= min_range, "rdm_voxel_map_integrate: need 0 <= min_range <= max_range");
+  if (n_scans == 0 || total == 0) return RDM_OK;
+  RDM_REQUIRE(points && offsets && poses, "rdm_voxel_map_integrate: null argument");
+  hipLaunchKernelGGL(integrate_kernel, dim3(blocks_for(total)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), t,
+                     static_cast<long long>(capacity), channels, voxel, points, static_cast<long long>(ld),
+                     static_cast<long long>(total), offsets, poses, static_cast<long long>(n_scans), min_range * min_range,
+                     max_range * max_range);
+  return launch_status("rdm_voxel_map_integrate");
+}
+
+extern "C" int rdm_voxel_map_rehash(const void* old_map, size_t old_bytes, int64_t old_capacity, void* new_map, size_t new_bytes,
+                                    int64_t new_capacity, int channels, void* stream) {
+  using namespace rdm;
+  Table a, b;
+  if (const int rc = open_table("rdm_voxel_map_rehash (old)", const_cast<void*>(old_map), old_bytes, old_capacity, channels, a)) return rc;
+  if (const int rc = open_table("rdm_voxel_map_rehash (new)", new_map, new_bytes, new_capacity, channels, b)) return rc;
+  RDM_REQUIRE(new_capacity >= old_capacity && new_map != old_map, "rdm_voxel_map_rehash: the new map must be another block of at least the old capacity");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(reset_kernel, dim3(blocks_for(new_capacity)), dim3(kBlock), 0, s, b, static_cast<long long>(new_capacity), channels);
+  hipLaunchKernelGGL(rehash_kernel, dim3(blocks_for(old_capacity)), dim3(kBlock), 0, s, a, static_cast<long long>(old_capacity), b,
+                     static_cast<long long>(new_capacity), channels);
+  return launch_status("rdm_voxel_map_rehash");
+}
+
+extern "C" int rdm_voxel_map_stats(const void* map, size_t map_bytes, int64_t capacity, int channels, uint64_t* stats, void* stream) {
+  using namespace rdm;
+  Table t;
+  if (const int rc = open_table("rdm_voxel_map_stats", const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
+  RDM_REQUIRE(stats != nullptr, "rdm_voxel_map_stats: null stats");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  RDM_HIP_CHECK(hipMemcpyAsync(stats, t.counters, kStats * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  RDM_HIP_CHECK(hipStreamSynchronize(s));
+  return RDM_OK;
+}
+
+extern "C" size_t rdm_voxel_map_extract_workspace_bytes(int64_t capacity) {
+  using namespace rdm;
+  if (!shape_ok(capacity, 3)) return 0;
+  Arena ar(nullptr, 0);
+  ExtractWork w;
+  carve_extract(ar, capacity, w);
+  return ar.off;
+}
+
+extern "C" int rdm_voxel_map_extract(const void* map, size_t map_bytes, int64_t capacity, int channels, double voxel,
+                                     int64_t min_points, float* points, int32_t* counts, int32_t* cells, int64_t max_rows,
+                                     int64_t* n_rows, void* ws, size_t ws_bytes, void* stream) {
+  using namespace rdm;
+  Table t;
+  if (const int rc = open_table("rdm_voxel_map_extract", const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
+  RDM_REQUIRE(voxel > 0.0 && std::isfinite(voxel), "rdm_voxel_map_extract: voxel must be positive and finite");
+  RDM_REQUIRE(min_points >= 0 && max_rows >= 0 && n_rows != nullptr, "rdm_voxel_map_extract: bad min_points, max_rows or null n_rows");
+  RDM_REQUIRE(max_rows == 0 || (points && counts && cells), "rdm_voxel_map_extract: null output");
+  Arena ar(ws, ws_bytes);
+  ExtractWork w;
+  if (!carve_extract(ar, capacity, w)) {
+    set_error("rdm_voxel_map_extract: workspace too small (%zu < %zu bytes)", ws_bytes, ar.off);
+    return RDM_ERR_WORKSPACE;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned int least = min_points > 0xffffffffll ? 0xffffffffu : static_cast<unsigned int>(min_points);
+  fill_words<unsigned long long>(w.n_sel, 1, 0ull, s);
+  hipLaunchKernelGGL(select_kernel, dim3(blocks_for(capacity)), dim3(kBlock), 0, s, t, static_cast<long long>(capacity), least, w.keys_in,
+                     w.slots_in, w.n_sel);
+  size_t bytes = w.sort_bytes;
+  RDM_HIP_CHECK(rocprim::radix_sort_pairs(w.sort_tmp, bytes, w.keys_in, w.keys, w.slots_in, w.slots, static_cast<unsigned>(capacity), 0u,
+                                          64u, s));
+  hipLaunchKernelGGL(emit_kernel, dim3(blocks_for(max_rows)), dim3(kBlock), 0, s, t, static_cast<long long>(capacity), channels, voxel,
+                     w.keys, w.slots, w.n_sel, static_cast<long long>(max_rows), points, counts, cells, n_rows);
+  return launch_status("rdm_voxel_map_extract");
+}

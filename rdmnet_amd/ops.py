@@ -786,6 +786,151 @@ def detect_loops(descriptors, threshold=0.13, exclude_recent=50):
     return (query, index[query], dist[query].copy(), shift[query], shift[query] * (360.0 / descriptors.shape[2]))
 
 
+# ---- voxel map: the scans of a sequence fused under its trajectory (rdm_voxel_map_*) ----------------------------------------
+
+class VoxelMap:
+    """A persistent voxel map in world coordinates on the GPU (rdm_voxel_map_*): scans are moved by their
+    poses and fused into per-voxel means.  voxel: edge in metres (cell c covers [c voxel, (c + 1) voxel), anchored at the world
+    origin); channels C = 3 ... 8: xyz and C - 3 attributes (4: intensity); capacity: the table's first size, a power of two >= 64
+    -- it grows by itself.  Per voxel a count and C int64 sums of 20-bit fixed-point values under integer atomic adds, so the
+    map depends on the set of integrated points only: the order of the scans, the batching and the run do not change one bit
+    of what `extract` returns."""
+
+    def __init__(self, voxel, channels=4, capacity=1 << 20, device='cuda'):
+        voxel, channels, capacity = float(voxel), int(channels), int(capacity)
+        if not (voxel > 0 and voxel < float('inf')):
+            raise ValueError(f'voxel must be positive and finite, got {voxel}')
+        if not 3 <= channels <= _lib.VOXEL_MAP_MAX_CHANNELS:
+            raise ValueError(f'channels must be 3 ... {_lib.VOXEL_MAP_MAX_CHANNELS}, got {channels}')
+        if capacity < 64 or capacity & (capacity - 1) or _lib.lib().rdm_voxel_map_bytes(capacity, channels) == 0:
+            raise ValueError(f'capacity must be a power of two in [64, 2^30], got {capacity}')
+        self.voxel, self.channels = voxel, channels
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise ValueError(f'VoxelMap needs a CUDA device, got {self.device}')
+        if self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        self.capacity, self._buf = capacity, self._alloc(capacity)
+        self.reset()
+
+    def _alloc(self, capacity):
+        return torch.empty((_lib.lib().rdm_voxel_map_bytes(capacity, self.channels),), dtype=torch.uint8, device=self.device)
+
+    def _head(self):
+        return self._buf.data_ptr(), self._buf.numel(), self.capacity, self.channels
+
+    def reset(self):
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().rdm_voxel_map_reset(*self._head(), _lib.stream_ptr()), 'rdm_voxel_map_reset')
+        self._bound = 0  # occupied <= _bound: spares the read-back of `occupied` while the table is certainly large enough
+
+    def stats(self):
+        """{occupied, integrated, skipped_nonfinite, skipped_range, out_of_extent, dropped_full}; waits for the stream."""
+        host = (ctypes.c_uint64 * len(_lib.VOXEL_MAP_STATS))()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().rdm_voxel_map_stats(*self._head(), ctypes.addressof(host), _lib.stream_ptr()), 'rdm_voxel_map_stats')
+        out = dict(zip(_lib.VOXEL_MAP_STATS, (int(v) for v in host)))
+        self._bound = out['occupied']
+        return out
+
+    def __len__(self):
+        return self.stats()['occupied']
+
+    def _reserve(self, n_points):
+        """capacity >= 2 (occupied + the batch's points) before a batch, so that through this class nothing is ever dropped."""
+        if 2 * (self._bound + n_points) > self.capacity:
+            need = 2 * (self.stats()['occupied'] + n_points)
+            if need > self.capacity:
+                capacity = self.capacity
+                while capacity < need:
+                    capacity *= 2
+                if _lib.lib().rdm_voxel_map_bytes(capacity, self.channels) == 0:
+                    raise RuntimeError(f'VoxelMap: {need // 2} voxels need more than 2^30 slots')
+                new = self._alloc(capacity)
+                with torch.cuda.device(self.device):
+                    _lib.check(_lib.lib().rdm_voxel_map_rehash(self._buf.data_ptr(), self._buf.numel(), self.capacity, new.data_ptr(),
+                                                               new.numel(), capacity, self.channels, _lib.stream_ptr()),
+                               'rdm_voxel_map_rehash')
+                self.capacity, self._buf = capacity, new  # (the old block is freed in stream order by the caching allocator)
+        self._bound += n_points
+
+    def integrate(self, clouds, poses, min_range=0.0, max_range=float('inf')):
+        """clouds: a list of float32 CUDA tensors [N_i, >= C] (empty ones allowed), or a pair (points float32 CUDA [N, ld >= C],
+        offsets int64 [n + 1], host or device: scan i is rows offsets[i] .. offsets[i + 1]).  poses: [n, 4, 4] finite, anything
+        numpy or torch holds (world = pose @ point).  A point is integrated iff its C values are finite and min_range <= its range
+        in the sensor frame <= max_range.  -> self.  The list form concatenates the clouds' first C columns on the device."""
+        import numpy as np
+        C = self.channels
+        if isinstance(clouds, tuple) and len(clouds) == 2 and isinstance(clouds[1], torch.Tensor) and clouds[1].dtype == torch.int64:
+            points, offsets = clouds
+            if not (offsets.dim() == 1 and offsets.numel() >= 1):
+                raise ValueError('offsets must be an int64 tensor [n + 1]')
+            named = [(points, 'points')]
+        elif isinstance(clouds, (list, tuple)):
+            named = [(t, f'clouds[{i}]') for i, t in enumerate(clouds)]
+            points = offsets = None
+        else:
+            raise ValueError('VoxelMap.integrate: clouds must be a list of tensors, or (points, offsets)')
+        for t, name in named:
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] >= C):
+                raise ValueError(f'{name} must be a float32 CUDA tensor [N, >={C}] (the map has {C} channels)')
+            if t.shape[0] > 0 and t.stride(1) != 1:
+                raise ValueError(f'{name} must have unit column stride')
+            if t.device != self.device:
+                raise ValueError(f'{name} is on {t.device}, the map on {self.device}')
+        if offsets is None:
+            counts = [int(t.shape[0]) for t, _ in named]
+            offsets = torch.tensor([0] + counts, dtype=torch.int64).cumsum(0)
+            if len(named) == 1:
+                points = named[0][0]
+            elif named:
+                points = torch.cat([t[:, :C] for t, _ in named])
+        n = offsets.numel() - 1
+        if isinstance(poses, torch.Tensor):
+            poses = poses.detach().cpu().numpy()
+        X = np.ascontiguousarray(np.asarray(poses, dtype=np.float64))
+        if X.shape == (4, 4) and n == 1:
+            X = X[None]
+        if X.size == 0 and n == 0:
+            X = X.reshape(0, 4, 4)
+        if X.shape != (n, 4, 4):
+            raise ValueError(f'poses must be [{n}, 4, 4] (one 4x4 per scan), got {X.shape}')
+        if not np.isfinite(X).all():
+            raise ValueError('poses must be finite')
+        lo, hi = float(min_range), float(max_range)
+        if not 0.0 <= lo <= hi:
+            raise ValueError(f'need 0 <= min_range <= max_range, got {min_range} and {max_range}')
+        if n == 0 or points is None or points.shape[0] == 0:
+            return self
+        total = int(points.shape[0])
+        ld = points.stride(0) if total > 1 else points.shape[1]
+        self._reserve(total)
+        with torch.cuda.device(self.device):
+            offsets = offsets.to(self.device).contiguous()
+            X = torch.from_numpy(X).to(self.device)
+            _lib.check(_lib.lib().rdm_voxel_map_integrate(*self._head(), self.voxel, points.data_ptr(), ld, total, offsets.data_ptr(),
+                                                          X.data_ptr(), n, lo, hi, _lib.stream_ptr()), 'rdm_voxel_map_integrate')
+        return self
+
+    def extract(self, min_points=1):
+        """-> (points float32 [M, C], counts int32 [M], cells int32 [M, 3]) on the device: the voxels with at least min_points
+        points in ascending order of (cell x, cell y, cell z); points = the per-voxel means.  Two read-backs (sizes)."""
+        L = _lib.lib()
+        rows = self.stats()['occupied']
+        C, dev = self.channels, self.device
+        points = torch.empty((max(rows, 1), C), dtype=torch.float32, device=dev)
+        ints = torch.empty((max(rows, 1), 4), dtype=torch.int32, device=dev)  # counts, then cells
+        counts, cells = ints.view(-1)[:max(rows, 1)], ints.view(-1)[max(rows, 1):].view(-1, 3)
+        n_rows = torch.zeros((1,), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            ws = scratch(dev, L.rdm_voxel_map_extract_workspace_bytes(self.capacity))
+            _lib.check(L.rdm_voxel_map_extract(*self._head(), self.voxel, int(min_points), points.data_ptr(), counts.data_ptr(),
+                                               cells.data_ptr(), rows, n_rows.data_ptr(), ws.data_ptr(), ws.numel(),
+                                               _lib.stream_ptr()), 'rdm_voxel_map_extract')
+        m = int(n_rows.item())
+        return points[:m], counts[:m], cells[:m]
+
+
 class RegistrationResult:
     """Named as Open3D's: transformation (float64 [4, 4], numpy), fitness, inlier_rmse, num_correspondences (of the last
     evaluation), iterations (updates applied) and, when asked for, history (float64 [evaluations, 15] numpy: per

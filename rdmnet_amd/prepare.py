@@ -272,10 +272,23 @@ def scan_list(root, seq, raw=False):
     return sorted((int(osp.basename(f)[:-len(ext)]), f) for f in files)
 
 
+def load_scan(path):
+    """One scan of either tree with all its columns -> f32 [N, 4] (xyz + intensity; a .npy may hold other widths)."""
+    pts = np.fromfile(path, dtype=np.float32).reshape(-1, 4) if path.endswith('.bin') else np.load(path)
+    return np.ascontiguousarray(pts, dtype=np.float32)
+
+
 def load_scan_xyz(path):
     """One scan of either tree -> f32 [N, 3]."""
     pts = np.fromfile(path, dtype=np.float32).reshape(-1, 4) if path.endswith('.bin') else np.load(path)
     return np.ascontiguousarray(pts[:, :3], dtype=np.float32)
+
+
+def scan_path(root, seq, frame, raw=False):
+    """The file of one frame: R/downsampled_xyzi/%02d/%06d.npy, or with `raw` R/sequences/%02d/velodyne/%06d.bin."""
+    if raw:
+        return osp.join(_velodyne(root, seq), '%06d.bin' % frame)
+    return osp.join(root, 'downsampled_xyzi', '%02d' % seq, '%06d.npy' % frame)
 
 
 def yaw_transform(shift, n_sectors=LOOP_SECTORS):

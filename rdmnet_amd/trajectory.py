@@ -2,6 +2,8 @@
 
     python -m rdmnet_amd.trajectory --features-root DIR [--optimize] [--line-process-weight MU] [--unit-information] [--out DIR]
                                   [--preconditioner {block_jacobi,chain}] [--linear-solver {pcg,direct}]
+                                  [--map-scans DATASET_ROOT [--map-raw] [--map-voxel 0.3] [--map-min-points 1]
+                                   [--map-range LO HI] [--map-batch 64]]
 
 reads the `{seq}_{src}_{ref}.npz` pair files that `python -m rdmnet_amd.infer` wrote into DIR (ordered and filtered as
 `python -m rdmnet_amd.eval` reads them) and, per sequence, chains the pair poses into a trajectory as
@@ -12,7 +14,10 @@ several such pairs the first in file order); every other pair file of the sequen
 two frames of the chain.  With --optimize all sequences are optimised as one batch by
 `ops.pose_graph_optimize` (--preconditioner chain selects its odometry-chain preconditioner, which suits exactly
 these graphs; --linear-solver direct its direct sparse solve in place of the conjugate gradients) and the report is printed for the optimised trajectory too.  Without --optimize no
-GPU is needed.  Everything here is numpy float64 on the host."""
+GPU is needed.  Everything here is numpy float64 on the host.  With --map-scans (and --out) the scans of every sequence's chain
+frames are fused under the chained -- and with --optimize also the optimised -- poses into a voxel map on the GPU (`build_map`,
+`ops.VoxelMap`) and written as `{seq}_{variant}_map.npy`; a better trajectory puts the same surfaces into
+fewer voxels, so voxels and points per voxel of the two variants are a check of --optimize that needs no ground truth."""
 import argparse
 import math
 import os
@@ -156,9 +161,92 @@ def write_kitti_poses(path, poses):
             f.write(' '.join(f'{v:.9e}' for v in np.asarray(X)[:3].reshape(-1)) + '\n')
 
 
+# ---- the map of a run ------------------------------------------------------------------------------------------------------
+
+MAP_DEFAULTS = dict(voxel=0.3, min_points=1, batch=64)
+
+
+def build_map(paths, poses, voxel=MAP_DEFAULTS['voxel'], channels=None, min_range=0.0, max_range=math.inf, batch=MAP_DEFAULTS['batch'],
+              capacity=1 << 20, device='cuda'):
+    """The scans `paths` (.npy float32 [N, C] or KITTI .bin [N, 4], read by prepare.load_scan) under `poses` ([n, 4, 4], world =
+    pose @ point) fused into an ops.VoxelMap.  channels None: the columns of the first scan (at most 8).  `batch` scans are read on
+    a background thread while the previous batch is on the GPU; a batch is one host-to-device copy and one integrate call.  A
+    missing file is a TrajectoryError that names it (checked before anything is read)."""
+    paths = list(paths)
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    if len(paths) != len(poses):
+        raise ValueError(f'build_map: {len(paths)} scans and {len(poses)} poses')
+    if int(batch) < 1:
+        raise ValueError(f'build_map: batch must be >= 1, got {batch}')
+    for path in paths:
+        if not osp.isfile(path):
+            raise TrajectoryError(f'{path}: no such scan file')
+    import torch
+    from . import ops, prepare
+    groups = [(i, min(i + int(batch), len(paths))) for i in range(0, len(paths), int(batch))]
+
+    def load(group):
+        clouds = [prepare.load_scan(paths[k]) for k in range(*group)]
+        for k, c in zip(range(*group), clouds):
+            if c.ndim != 2 or c.shape[1] != clouds[0].shape[-1]:
+                raise TrajectoryError(f'{paths[k]}: shape {c.shape}, expected [N, {clouds[0].shape[-1]}] as the scans of its batch')
+        offsets = np.concatenate([[0], np.cumsum([len(c) for c in clouds])]).astype(np.int64)
+        return np.concatenate(clouds), offsets
+
+    vmap = None
+    for group, (points, offsets) in prepare._read_ahead(load, groups):
+        if vmap is None:
+            width = points.shape[1] if channels is None else int(channels)
+            vmap = ops.VoxelMap(voxel, channels=min(width, 8), capacity=capacity, device=device)
+        if points.shape[1] < vmap.channels:
+            raise TrajectoryError(f'{paths[group[0]]}: {points.shape[1]} columns, the map has {vmap.channels} channels')
+        vmap.integrate((torch.from_numpy(points).to(vmap.device), torch.from_numpy(offsets)), poses[group[0]:group[1]], min_range,
+                       max_range)
+    if vmap is None:
+        vmap = ops.VoxelMap(voxel, channels=4 if channels is None else int(channels), capacity=capacity, device=device)
+    return vmap
+
+
+def map_line(seq, what, voxel, voxels, points, stats):
+    per = f'{points / voxels:.2f}' if voxels else 'no'
+    return (f'seq {seq} {what} map: {voxels} voxels at {voxel:g} m, {points} points, {per} points per voxel, skipped: '
+            f"{stats['skipped_nonfinite']} non-finite, {stats['skipped_range']} out of range, {stats['out_of_extent']} out of extent")
+
+
+def write_map(args, seq, what, paths, poses, emit):
+    lo, hi = args.map_range if args.map_range else (0.0, math.inf)
+    vmap = build_map(paths, poses, voxel=args.map_voxel, min_range=lo, max_range=hi, batch=args.map_batch)
+    points, counts, _ = vmap.extract(args.map_min_points)
+    points, counts = points.cpu().numpy(), counts.cpu().numpy()
+    np.save(osp.join(args.out, f'{seq}_{what}_map.npy'), np.concatenate([points, counts[:, None].astype(np.float32)], 1))
+    emit(map_line(seq, what, args.map_voxel, len(counts), int(counts.sum(dtype=np.int64)), vmap.stats()))
+
+
+def map_paths(args, seqs):
+    """{seq: the scan file of every chain frame}, after the checks that need no GPU."""
+    if not getattr(args, 'map_scans', None):
+        return None
+    if not args.out:
+        raise TrajectoryError('--map-scans needs --out (the directory the maps are written to)')
+    if not (args.map_voxel > 0 and math.isfinite(args.map_voxel)) or args.map_min_points < 1 or args.map_batch < 1:
+        raise TrajectoryError('--map-voxel must be > 0, --map-min-points and --map-batch >= 1')
+    if args.map_range and not 0.0 <= args.map_range[0] <= args.map_range[1]:
+        raise TrajectoryError(f'--map-range LO HI needs 0 <= LO <= HI, got {args.map_range[0]} {args.map_range[1]}')
+    from . import prepare
+    out = {}
+    for seq, s in seqs.items():
+        out[seq] = [prepare.scan_path(args.map_scans, seq, f, args.map_raw) for f in s['frames']]
+        for path in out[seq]:
+            if not osp.isfile(path):
+                raise TrajectoryError(f'{path}: no such scan file (frame of sequence {seq}; --map-scans {args.map_scans}'
+                                      + ('' if args.map_raw else ', --map-raw reads sequences/%02d/velodyne/*.bin') + ')')
+    return out
+
+
 def run(args, emit=print):
     seqs = read_sequences(args.features_root, args.unit_information)
     graphs = {seq: sequence_graph(s) for seq, s in seqs.items()}
+    scans = map_paths(args, seqs)
     if args.out:
         os.makedirs(args.out, exist_ok=True)
     gts = {}
@@ -171,6 +259,8 @@ def run(args, emit=print):
             emit(f'seq {seq} chained: no ground truth in the pair files')
         if args.out:
             write_kitti_poses(osp.join(args.out, f'{seq}_chained.txt'), graphs[seq][0])
+        if scans:
+            write_map(args, seq, 'chained', scans[seq], graphs[seq][0], emit)
     if not args.optimize:
         return None
     if not graphs:
@@ -195,6 +285,8 @@ def run(args, emit=print):
              f'{res.final_cost[g]:.6g}, {res.iterations[g]} iterations ({res.stop_reasons[g]}), pruned edges: {names}')
         if args.out:
             write_kitti_poses(osp.join(args.out, f'{seq}_optimized.txt'), nodes[noff[g]:noff[g + 1]])
+        if scans:
+            write_map(args, seq, 'optimized', scans[seq], nodes[noff[g]:noff[g + 1]], emit)
     return res
 
 
@@ -211,6 +303,16 @@ def make_parser():
     ap.add_argument('--linear-solver', choices=('pcg', 'direct'), default='pcg',
                     help='of --optimize: conjugate gradients, or the direct sparse solve for a chain with loop closures')
     ap.add_argument('--out', default=None, help='directory for one KITTI-format pose file per sequence and variant')
+    ap.add_argument('--map-scans', default=None, metavar='DATASET_ROOT',
+                    help='fuse the scans of every chain frame under each trajectory into a voxel map on the GPU, written to --out as '
+                         '{seq}_{variant}_map.npy (float32 [M, C + 1]: the per-voxel means, then the count); reads '
+                         'DATASET_ROOT/downsampled_xyzi/%%02d/%%06d.npy')
+    ap.add_argument('--map-raw', action='store_true', help='read DATASET_ROOT/sequences/%%02d/velodyne/%%06d.bin instead')
+    ap.add_argument('--map-voxel', type=float, default=MAP_DEFAULTS['voxel'], help='voxel edge in metres')
+    ap.add_argument('--map-min-points', type=int, default=MAP_DEFAULTS['min_points'], help='write the voxels with at least this many points')
+    ap.add_argument('--map-range', type=float, nargs=2, default=None, metavar=('LO', 'HI'),
+                    help='integrate the points whose range in the sensor frame is within [LO, HI] metres (default: all)')
+    ap.add_argument('--map-batch', type=int, default=MAP_DEFAULTS['batch'], help='scans per host-to-device copy and integrate call')
     return ap
 
 

@@ -1,0 +1,168 @@
+"""Times the voxel map (ops.VoxelMap) on synthetic scans along a synthetic drive.
+
+  python tools/map_bench.py [--frames 256] [--points 120000 | 18000] [--reps 3] [--batch 64] [--voxel 0.3] [--cpu] [--cpu-frames 8]
+Prints one JSON line per case:
+  * integrate: --frames scans of --points points (120 000: a raw scan; 18 000: a down-sampled one), xyz + intensity, integrated in
+    batches of --batch from device memory into a table created large enough (no growth inside the timing); device time between
+    two events, median of --reps; points/s, the bytes/s of integer atomic adds that implies ((8 C + 4) B a point: C int64 sums and
+    a uint32 count), that rate as a fraction of the 1.3 TB/s the chip sustains for fp32 atomic adds, and the bytes/s of points read;
+  * host copy: one batch from pageable and from pinned host memory to the device, points/s -- what the command line, which reads
+    its scans from disk through host memory, is bound by at the latest;
+  * extract: ms for the voxels of that map (select, radix sort of the slots, emit), and the voxels per second;
+  * rehash: ms for one rdm_voxel_map_rehash of that map into a table of twice the capacity;
+  * with --cpu: the NumPy restatement (tests/voxel_map_restatement.py) on the first --cpu-frames scans, its points/s, and whether the
+    GPU's map of the same scans equals it bit for bit."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
+
+FLOAT_ATOMIC_BYTES_PER_S = 1.3e12  # the chip-wide rate of fp32 atomic adds
+
+
+def timed(fn, reps):
+    """Median device time in ms of fn() between two events, after one warm-up call."""
+    import torch
+    fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn()
+        b.record()
+        torch.cuda.synchronize()
+        times.append(a.elapsed_time(b))
+    return float(np.median(times)), out
+
+
+def synthetic_scans(frames, points, seed=0):
+    """-> float32 CUDA [frames * points, 4] in the sensor frame: a ground plane at z = -1.7 m with structures up to 4 m on 30 % of
+    the points, denser near the sensor (r = 2 + 78 u^2 m), intensity in [0, 1).  Generated on the device."""
+    import torch
+    g = torch.Generator(device='cuda').manual_seed(seed)
+    n = frames * points
+    u = torch.rand((n, 5), generator=g, device='cuda')
+    r = 2.0 + 78.0 * u[:, 0] ** 2
+    th = 2.0 * np.pi * u[:, 1]
+    z = -1.7 + 0.05 * (u[:, 2] - 0.5) + (u[:, 3] < 0.3) * 4.0 * u[:, 2]
+    return torch.stack([r * torch.cos(th), r * torch.sin(th), z, u[:, 4]], 1).contiguous()
+
+
+def drive(frames, step=1.0):
+    """One pose per frame: `step` metres forward per frame along a heading that turns slowly, with a little roll."""
+    poses = np.zeros((frames, 4, 4))
+    x = y = 0.0
+    for k in range(frames):
+        yaw = 0.6 * np.sin(k / 80.0)
+        roll = 0.01 * np.sin(k / 7.0)
+        Rz = np.array([[np.cos(yaw), -np.sin(yaw), 0], [np.sin(yaw), np.cos(yaw), 0], [0, 0, 1]])
+        Rx = np.array([[1, 0, 0], [0, np.cos(roll), -np.sin(roll)], [0, np.sin(roll), np.cos(roll)]])
+        poses[k, :3, :3] = Rz @ Rx
+        poses[k, :3, 3] = [x, y, 0.02 * k]
+        poses[k, 3, 3] = 1.0
+        x += step * np.cos(yaw)
+        y += step * np.sin(yaw)
+    return poses
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--frames', type=int, default=256)
+    ap.add_argument('--points', type=int, default=120000, help='points per scan: 120000 (raw) or 18000 (down-sampled)')
+    ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--batch', type=int, default=64, help='scans per integrate call')
+    ap.add_argument('--voxel', type=float, default=0.3)
+    ap.add_argument('--cpu', action='store_true', help='also time the NumPy restatement and compare the maps bit for bit')
+    ap.add_argument('--cpu-frames', type=int, default=8)
+    a = ap.parse_args(argv)
+    import torch
+    from rdmnet_amd import _lib, ops
+    assert torch.cuda.is_available(), 'map_bench needs a GPU'
+    C = 4
+    cloud, poses = synthetic_scans(a.frames, a.points), drive(a.frames)
+    total = a.frames * a.points
+    capacity = 1 << max(int(np.ceil(np.log2(2 * total))), 6)  # what VoxelMap itself would grow to at the latest
+    capacity = min(capacity, 1 << 28)
+    vmap = ops.VoxelMap(a.voxel, channels=C, capacity=capacity)
+    batches = []
+    for lo in range(0, a.frames, a.batch):
+        hi = min(lo + a.batch, a.frames)
+        batches.append((cloud[lo * a.points:hi * a.points], (torch.arange(hi - lo + 1, dtype=torch.int64) * a.points).cuda(),
+                        torch.from_numpy(poses[lo:hi])))
+
+    def integrate():
+        vmap.reset()
+        for pts, off, X in batches:
+            vmap.integrate((pts, off), X)
+        return vmap
+
+    def reset_only():
+        vmap.reset()
+
+    ms_reset, _ = timed(reset_only, a.reps)
+    ms_all, _ = timed(integrate, a.reps)
+    ms = ms_all - ms_reset
+    st = vmap.stats()
+    assert vmap.capacity == capacity and st['dropped_full'] == 0
+    pps = total / ms * 1e3
+    print(json.dumps({'case': 'integrate', 'frames': a.frames, 'points_per_scan': a.points, 'batch': a.batch, 'voxel': a.voxel,
+                      'capacity': capacity, 'ms': round(ms, 3), 'ms_reset_excluded': round(ms_reset, 3), 'points_per_s': round(pps),
+                      'atomic_bytes_per_s': round(pps * (8 * C + 4)),
+                      'fraction_of_float_atomic_rate': round(pps * (8 * C + 4) / FLOAT_ATOMIC_BYTES_PER_S, 4),
+                      'read_bytes_per_s': round(pps * 4 * C), 'voxels': st['occupied'],
+                      'points_per_voxel': round(st['integrated'] / max(st['occupied'], 1), 2), 'stats': st}))
+
+    host = cloud[:min(a.batch, a.frames) * a.points].cpu().numpy()
+    pinned = torch.from_numpy(host).pin_memory()
+    for name, src in (('pageable', torch.from_numpy(host)), ('pinned', pinned)):
+        t = []
+        for _ in range(a.reps + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            src.cuda()
+            torch.cuda.synchronize()
+            t.append(time.perf_counter() - t0)
+        s = float(np.median(t[1:]))
+        print(json.dumps({'case': 'host copy', 'memory': name, 'points': len(host), 'ms': round(s * 1e3, 3),
+                          'points_per_s': round(len(host) / s), 'GB_per_s': round(host.nbytes / s / 1e9, 2),
+                          'integrate_over_copy': round(pps / (len(host) / s), 2)}))
+
+    ms_x, out = timed(lambda: vmap.extract(), a.reps)
+    print(json.dumps({'case': 'extract', 'capacity': capacity, 'voxels': int(out[0].shape[0]), 'ms': round(ms_x, 3),
+                      'voxels_per_s': round(out[0].shape[0] / ms_x * 1e3)}))
+
+    L = _lib.lib()
+    if L.rdm_voxel_map_bytes(2 * capacity, C):
+        new = torch.empty((L.rdm_voxel_map_bytes(2 * capacity, C),), dtype=torch.uint8, device='cuda')
+        ms_r, _ = timed(lambda: _lib.check(L.rdm_voxel_map_rehash(vmap._buf.data_ptr(), vmap._buf.numel(), capacity, new.data_ptr(),
+                                                                  new.numel(), 2 * capacity, C, _lib.stream_ptr()), 'rehash'), a.reps)
+        print(json.dumps({'case': 'rehash', 'from': capacity, 'to': 2 * capacity, 'voxels': st['occupied'], 'ms': round(ms_r, 3)}))
+        del new
+
+    if a.cpu:
+        import voxel_map_restatement as VM
+        m = min(a.cpu_frames, a.frames)
+        clouds = [cloud[k * a.points:(k + 1) * a.points].cpu().numpy() for k in range(m)]
+        t0 = time.perf_counter()
+        ref = VM.build(clouds, poses[:m], a.voxel, C)
+        want = ref.extract()
+        cpu_s = time.perf_counter() - t0
+        small = ops.VoxelMap(a.voxel, channels=C).integrate([cloud[k * a.points:(k + 1) * a.points] for k in range(m)], poses[:m])
+        got = [t.cpu().numpy() for t in small.extract()]
+        same = all(np.array_equal(g.view(np.uint32) if g.dtype == np.float32 else g, w.view(np.uint32) if w.dtype == np.float32 else w)
+                   for g, w in zip(got, want)) and small.stats() == ref.stats()
+        print(json.dumps({'case': 'cpu restatement', 'frames': m, 'points': m * a.points, 'cpu_s': round(cpu_s, 3),
+                          'cpu_points_per_s': round(m * a.points / cpu_s), 'gpu_points_per_s': round(pps),
+                          'gpu_over_cpu': round(pps / (m * a.points / cpu_s), 1), 'voxels': len(want[0]), 'bit_equal': bool(same)}))
+    return 0
+
+
+if __name__ == '__main__':
+    raise SystemExit(main())
