@@ -458,7 +458,13 @@ int rdm_patch_scores(const float* ref_feats, int64_t ld_ref, int64_t n_ref, cons
  *   y = act(GroupNorm([coarse[idx[:, 0]] | skip] W + bias))        gamma != NULL (lin_out: scratch for the pre-norm rows)
  *   lin_out = [coarse[idx[:, 0]] | skip] W + bias                  gamma == NULL
  * idx [m, ldi] is the upsampling table (column 0 used; an index outside [0, n_coarse) gives a zero row); W [pad4(c1+c2), n pad]
- * as rdm_gemm's B.  When c1 is a multiple of 32 the concatenated rows exist only inside the GEMM's operand tiles. */
+ * as rdm_gemm's B.  Three routes, chosen from the sizes alone:
+ *   - c1 no multiple of 32 (or c1 + c2 no multiple of 4): the rows are concatenated into the workspace, then the plain product;
+ *   - else, when the product runs un-split (rdm_gemm_last_plan) and n_coarse < m: coarse W[0:c1] is formed once per COARSE row
+ *     (into the same workspace region) and the product of skip with W[c1:] starts its accumulators from that row of it;
+ *   - else the concatenated rows exist only inside the GEMM's operand tiles.
+ * An output element is one fp32 fma chain over ascending k from +0 on every route, and after its first c1 steps that chain holds
+ * coarse[idx[m]] W[0:c1, n] whichever fine row m runs it: for one tile shape and split-K factor the routes return the same bits. */
 size_t rdm_decoder_stage_workspace_bytes(int64_t m, int64_t n, int64_t k);
 int rdm_decoder_stage(const float* coarse, int64_t n_coarse, int64_t c1, int64_t ld1, const int64_t* idx, int64_t ldi,
                       const float* skip, int64_t c2, int64_t ld2, int64_t m, const float* w, int64_t ldw, const float* bias,

@@ -303,15 +303,19 @@ int unary(Run& r, const std::string& name, const Mat& x, Mat& y, int act, const 
 
 // Decoder stage (backbone.py:118-151): Linear [+ GroupNorm + LeakyReLU] of [nearest_upsample(coarse) | skip]; the GEMM forms the
 // concatenated rows in its A-tile loads when the widths allow it (rdm_decoder_stage) -- the [M, c1 + c2] tensor (33 MB at the
-// finest decoder level) is then neither written nor re-read.
+// finest decoder level) is then neither written nor re-read.  n_cols > 0: the caller reads the first n_cols output columns only
+// (rdm::decoder_stage_cols: an un-split product then leaves the other column tiles out; y keeps the layer's full shape).
 int decoder_stage(Run& r, const std::string& lin_name, const std::string* norm_name, const Mat& coarse, const int64_t* up_idx,
-                  int64_t up_ld, const Mat& skip, int64_t m, Mat& y) {
+                  int64_t up_ld, const Mat& skip, int64_t m, Mat& y, int64_t n_cols = 0) {
   lockstep_align();  // (lockstep.h: the pairs of a lock-step group start every layer together)
   rdm_engine* e = r.e;
   const Linear* Lp = lin_param(r, lin_name);
   if (!Lp) return RDM_ERR_ARG;
   const Linear& L = *Lp;
   RDM_REQUIRE(coarse.cols + skip.cols == L.in, "rdm_engine: %s expects %lld input columns", lin_name.c_str(), (long long)L.in);
+  RDM_REQUIRE(n_cols >= 0 && n_cols <= L.out && (n_cols == 0 || !norm_name), "rdm_engine: %s cannot compute %lld of its columns",
+              lin_name.c_str(), (long long)n_cols);
+  const int64_t n = n_cols > 0 ? n_cols : L.out;
   Mat t = e->mat(m, L.out);
   ENG_ALLOC(t.p);
   float *g = nullptr, *b = nullptr;
@@ -330,9 +334,9 @@ int decoder_stage(Run& r, const std::string& lin_name, const std::string* norm_n
     ENG_ALLOC(ws);
     ws_bytes = need;
   }
-  return rdm_decoder_stage(coarse.p, coarse.rows, coarse.cols, coarse.ld, up_idx, up_ld, skip.p, skip.cols, skip.ld, m, L.b, L.ldb,
-                           L.bias, L.out, r.groups, g, b, 1e-5f, 2, t.p, t.ld, norm_name ? y.p : nullptr, norm_name ? y.ld : 0, ws,
-                           ws_bytes, r.st);
+  return rdm::decoder_stage_cols(coarse.p, coarse.rows, coarse.cols, coarse.ld, up_idx, up_ld, skip.p, skip.cols, skip.ld, m, L.b,
+                                 L.ldb, L.bias, L.out, n, r.groups, g, b, 1e-5f, 2, t.p, t.ld, norm_name ? y.p : nullptr,
+                                 norm_name ? y.ld : 0, ws, ws_bytes, r.st);
 }
 
 int layer_norm(Run& r, const std::string& name, const Mat& x, const Mat* res, int act, Mat& y, bool alloc_out = true) {
@@ -1622,7 +1626,10 @@ int decoder(Run& rd, const PairPyramid& py, const Mat& coarse, const Mat* feats,
   Mat l4, l3;
   ENG_CHECK(decoder_stage(rd, "decoder.decoder4.mlp", &n4, coarse, py.up[3].idx, py.up[3].stride(), feats[3], py.lv[3].n, l4));
   ENG_CHECK(decoder_stage(rd, "decoder.decoder3.mlp", &n3, l4, py.up[2].idx, py.up[2].stride(), feats[2], py.lv[2].n, l3));
-  ENG_CHECK(decoder_stage(rd, "decoder.decoder2.mlp", nullptr, l3, py.up[1].idx, py.up[1].stride(), feats[1], Nf, dec));
+  // (column D, the p2p logit, is read by runs that keep their stage tensors only -- below --; the fine matching takes the first D
+  // columns: a plain run does not compute a fifth 64-column tile for that one column)
+  ENG_CHECK(decoder_stage(rd, "decoder.decoder2.mlp", nullptr, l3, py.up[1].idx, py.up[1].stride(), feats[1], Nf, dec,
+                          e->keep_taps ? 0 : D));
   tap(rd, "decoder", dec);
   if (e->keep_taps) {
     float* p2p = e->alloc<float>(Nf);

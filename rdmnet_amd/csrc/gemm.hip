@@ -52,6 +52,13 @@ struct GemmArgs {  // (the defaults: one plain product -- no batch strides, epil
   // whose rows or columns are all shadow rows are written as zeros without touching the features
   const int64_t* bidx = nullptr;
   int n_b = 0;
+  // SEED kernels only -- the accumulators of row m start from seed[sidx[m * ldsi]] (columns as C's) instead of zero; a row index
+  // outside [0, n_seed), a row >= M or a column >= N starts from +0.  With seed = coarse W[0:c1] and A = skip, B = W[c1:] an
+  // output element runs the fma chain of the CAT product (whose first c1 steps are the same for every row with one parent);
+  // un-split products only
+  const float* seed = nullptr;
+  const int64_t* sidx = nullptr;
+  int ld_seed = 0, ldsi = 0, n_seed = 0;
   int xcd_tiles = 0;  // 1: output tiles re-mapped so that an XCD (workgroup id % 8) owns whole row tiles with all their column tiles
 #ifdef RDM_GEMM_TIMING
   unsigned long long* clk = nullptr;  // tools/gemm_phase_lab.hip: shader-clock stamps of workgroup (0,0,0), thread 0
@@ -72,11 +79,12 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 // PF = global->register prefetch depth in K tiles (the loop barriers order LDS only, so the stages really stay in
 // flight): the skinny products of this path run a handful of blocks per CU and a block covers part of the load
 // latency itself.
-template <int BM, int BN, int WM, int WN, int BK, bool TRANS_B, int PF, bool CAT = false>
+template <int BM, int BN, int WM, int WN, int BK, bool TRANS_B, int PF, bool CAT = false, bool SEED = false>
 __device__ __forceinline__ void gemm_kernel_body(const dim3 blockIdx, const dim3 gridDim, GemmArgs g) {
   (void)blockIdx; (void)gridDim;
   constexpr int TM = BM / WM, TN = BN / WN, FM = TM / 32, FN = TN / 32;
   static_assert(WM * WN == 4 && TM % 32 == 0 && TN % 32 == 0, "bad tile");
+  static_assert(!SEED || (!CAT && !TRANS_B), "seeded accumulators: plain operands only");
   // transposed-staged tiles use an odd row stride (scalar LDS writes of one k-column hit distinct
   // banks); the row-major B tile is written as float4 and keeps a 16-byte-aligned stride
   constexpr int LDA_S = BM + 1, LDB_S = TRANS_B ? BN + 1 : BN + 4;
@@ -264,6 +272,7 @@ __device__ __forceinline__ void gemm_kernel_body(const dim3 blockIdx, const dim3
 #pragma unroll
   for (int q = 0; q < BM / RPI; ++q) rdv[q] = (!partial && g.rowdiv) ? g.rowdiv[min(m0 + q * RPI + rsub, g.M - 1)] : 1.f;
 
+  const int lk = lane >> 5, li = lane & 31;
   f32x16 acc[FM][FN];
 #pragma unroll
   for (int i = 0; i < FM; ++i)
@@ -271,8 +280,19 @@ __device__ __forceinline__ void gemm_kernel_body(const dim3 blockIdx, const dim3
     for (int j = 0; j < FN; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int lk = lane >> 5, li = lane & 31;
+  // SEED: the seed row of each accumulator row of this lane (the fragment layout the epilogue unpacks), -1 = start from +0;
+  // requested here, in front of the first tiles' loads, so that the seed loads below find them arrived
+  long long seed_row[SEED ? FM : 1][SEED ? 16 : 1];
+  if constexpr (SEED) {
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = m0 + wm * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+        const long long id = g.sidx[static_cast<long long>(min(row, g.M - 1)) * g.ldsi];
+        seed_row[i][r] = (row < g.M && id >= 0 && id < g.n_seed) ? id : -1;
+      }
+  }
   // One k-tile in two halves (round 5).  The operands of a half live in registers one half-step ahead: while the MFMAs of the
   // tile's FIRST half run, its second half is read from LDS (and the next tile goes from the register stage into the other LDS
   // buffer, the tile after it from global memory into the free stage); after the barrier that publishes that buffer, the first
@@ -328,6 +348,21 @@ __device__ __forceinline__ void gemm_kernel_body(const dim3 blockIdx, const dim3
   if (kt0 < kt1) {  // (an empty K range -- more splits than k-tiles -- leaves the accumulators at zero)
     load_tiles(ra0, rb0, kt0);
     if constexpr (PF == 2) load_tiles(ra1, rb1, kt0 + 1);
+    // (SEED: once per workgroup, 16 KB; a seeded product is un-split with K >= 4, so its K range is never empty.  Behind the
+    // tiles' loads in program order: the seeds arrive while the first tile goes to LDS)
+    if constexpr (SEED) {
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) {
+          const int col = n0 + wn * TN + j * 32 + li;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {  // (unconditional loads from clamped, always valid addresses)
+            const float v = g.seed[max(seed_row[i][r], 0ll) * g.ld_seed + min(col, g.N - 1)];
+            acc[i][j][r] = (seed_row[i][r] >= 0 && col < g.N) ? v : 0.f;
+          }
+        }
+    }
     store_tiles(ra0, rb0, 0, kt0);
   }
   lds_barrier();
@@ -432,9 +467,9 @@ __device__ __forceinline__ void gemm_kernel_body(const dim3 blockIdx, const dim3
   }
   GEMM_STAMP(3);
 }
-template <int BM, int BN, int WM, int WN, int BK, bool TRANS_B, int PF, bool CAT = false>
+template <int BM, int BN, int WM, int WN, int BK, bool TRANS_B, int PF, bool CAT = false, bool SEED = false>
 // (64-row / 128 x 32 tiles: four workgroups per CU = four wavefronts per SIMD, 128 registers each)
-__global__ __launch_bounds__(256, (BM * BN <= 64 * 64 ? 4 : 1)) void gemm_kernel(GemmArgs g) { gemm_kernel_body<BM, BN, WM, WN, BK, TRANS_B, PF, CAT>(blockIdx, gridDim, g); }
+__global__ __launch_bounds__(256, (BM * BN <= 64 * 64 ? 4 : 1)) void gemm_kernel(GemmArgs g) { gemm_kernel_body<BM, BN, WM, WN, BK, TRANS_B, PF, CAT, SEED>(blockIdx, gridDim, g); }
 
 // Latency-oriented kernel for the transformer-sized products (M up to ~1k rows, K a multiple of 16):
 // one workgroup = ONE 32 x 32 output tile, its four wavefronts split K four ways, operands go straight
@@ -887,6 +922,10 @@ void launch(const GemmArgs& g, int batches, bool trans_b, hipStream_t st) {
       ::rdm::launch<gemm_kernel_body<BM, BN, WM, WN, BK, false, PF, true>, gemm_kernel<BM, BN, WM, WN, BK, false, PF, true>, 256, (BM * BN <= 64 * 64 ? 4 : 1)>(grid, pad, st, g);
       return;
     }
+    if (g.seed) {  // accumulators seeded with the coarse half of the decoder's product
+      ::rdm::launch<gemm_kernel_body<BM, BN, WM, WN, BK, false, PF, false, true>, gemm_kernel<BM, BN, WM, WN, BK, false, PF, false, true>, 256, (BM * BN <= 64 * 64 ? 4 : 1)>(grid, pad, st, g);
+      return;
+    }
   }
   if (trans_b)
     ::rdm::launch<gemm_kernel_body<BM, BN, WM, WN, BK, true, PF>, gemm_kernel<BM, BN, WM, WN, BK, true, PF>, 256, (BM * BN <= 64 * 64 ? 4 : 1)>(grid, pad, st, g);
@@ -1065,6 +1104,10 @@ void lab_overrides(GemmPlan& p, const GemmArgs& g, int batches, size_t ws_cap) {
 int launch_plan(const GemmPlan& p, GemmArgs g, int batches, bool trans_b, void* ws, int* stat_blocks, hipStream_t st) {
   const long long m = g.M, n = g.N;
   g_last_plan[0] = p.bm; g_last_plan[1] = p.bn; g_last_plan[2] = p.bk; g_last_plan[3] = p.splits;
+  if (g.seed && (p.small || p.exp_tile || p.tile != T64 || p.bk != 32 || p.splits != 1 || batches != 1 || trans_b || g.aidx)) {
+    set_error("gemm: seeded accumulators exist for the un-split 64 x 64 x 32 tile only");
+    return RDM_ERR_ARG;
+  }
   if (p.small) {
     if (stat_blocks) *stat_blocks = 0;
     RDM_DUP_LOOP("gemmsmall")
@@ -1145,10 +1188,24 @@ int rdm::gemm_with_stats(const float* a, int64_t lda, const float* b, int64_t ld
 // C = [nearest_upsample(coarse)[idx[:, 0]] | skip] B + bias (decoder, backbone.py:118-151) without materialising the
 // concatenation: the GEMM's A tiles come from the two sources directly.  c1 (columns of coarse) must be a multiple of 32
 // and c1 + c2 the padded K of B; otherwise returns 1 and the caller concatenates (rdm_upsample_concat) as before.
+//
+// Two routes, same bits.  An output element is one fp32 fma chain over ascending k from +0, and the coarse columns come first:
+// after its first c1 steps the chain of (m, n) holds exactly the complete chain of coarse[idx[m]] . B[0:c1, n] -- the same
+// value for every fine row with that parent (+0 for a shadow row).  When the concatenated product would run un-split, there are
+// fewer coarse rows than fine rows and `pbuf` holds it, P = coarse B[0:c1] [n_coarse, n] is therefore formed ONCE per coarse row
+// (un-split, no bias / activation / statistics; its tile is free) and the product over the skip half alone, on the same
+// 64 x 64 x 32 tile, starts its accumulators from P[idx[m]] (GemmArgs::seed): every element runs the fma sequence of the
+// concatenated product, the epilogue (bias, GroupNorm partials per 64-row block) is that launch's own.  Both launches are
+// un-split by construction, not by the cost model (which would plan K = c2 on its own terms).  Otherwise: the concatenated
+// product, as planned.
+//
+// n_need <= n: the columns the caller reads.  The product is PLANNED with all n columns (the split-K factor is part of the bits);
+// an un-split product then computes its first n_need columns only (whole column tiles less, the same chain per element), a
+// split-K one all n as ever.
 int rdm::gemm_concat_with_stats(const float* coarse, int64_t ld1, int64_t c1, int64_t n_coarse, const int64_t* idx, int64_t ldi,
                                 const float* skip, int64_t ld2, int64_t c2, const float* b, int64_t ldb, float* c, int64_t ldc,
-                                int64_t m, int64_t n, const float* bias, int act, void* ws, size_t ws_bytes, double* gn_partial,
-                                int* gn_blocks, void* stream) {
+                                int64_t m, int64_t n, int64_t n_need, const float* bias, int act, float* pbuf, size_t pbuf_floats,
+                                void* ws, size_t ws_bytes, double* gn_partial, int* gn_blocks, void* stream) {
   if (c1 % 32 != 0 || c2 % 4 != 0 || c2 < 4 || ld1 % 4 != 0 || ld2 % 4 != 0 || ldb % 4 != 0 || m <= 0 ||
       ((reinterpret_cast<uintptr_t>(coarse) | reinterpret_cast<uintptr_t>(skip) | reinterpret_cast<uintptr_t>(b)) & 15) != 0)
     return 1;
@@ -1159,7 +1216,34 @@ int rdm::gemm_concat_with_stats(const float* coarse, int64_t ld1, int64_t c1, in
   g.act = act; g.stats = gn_partial;
   g.A2 = skip; g.aidx = idx; g.lda2 = static_cast<int>(ld2); g.ldi = static_cast<int>(ldi); g.c1 = static_cast<int>(c1);
   g.n_coarse = static_cast<int>(n_coarse);
-  return gemm_dispatch(g, 1, false, ws, ws_bytes, gn_blocks, static_cast<hipStream_t>(stream));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t ws_cap = ws ? ws_bytes : 0;
+  GemmPlan p = plan_gemm(g, 1, false, ws_cap);
+#ifdef RDM_DEV_KNOBS
+  lab_overrides(p, g, 1, ws_cap);
+#endif
+  if (p.splits == 1) n = n_need;  // (un-split: the column tiles the caller does not read are left out)
+  g.N = static_cast<int>(n);
+  const int64_t ldp = (n + 3) / 4 * 4;
+  const bool seeded = p.splits == 1 && p.tile == T64 && p.bk == 32 && p.exp_tile == 0 && n_coarse > 0 && n_coarse < m &&
+                      pbuf && static_cast<size_t>(n_coarse) * ldp <= pbuf_floats && (reinterpret_cast<uintptr_t>(pbuf) & 15) == 0;
+  if (!seeded) return launch_plan(p, g, 1, false, ws, gn_blocks, st);
+  GemmArgs gp;  // P = coarse B[0:c1]
+  gp.A = coarse; gp.B = b; gp.C = pbuf;
+  gp.M = static_cast<int>(n_coarse); gp.N = static_cast<int>(n); gp.K = static_cast<int>(c1);
+  gp.lda = static_cast<int>(ld1); gp.ldb = static_cast<int>(ldb); gp.ldc = static_cast<int>(ldp);
+  const GemmPlan pp = plan_tiled(gp, 1, 0);  // (no room for partials: the model chooses the tile of an un-split product)
+  if (int e = launch_plan(pp, gp, 1, false, nullptr, nullptr, st)) return e;
+  GemmArgs gs;  // C = skip B[c1:] on top of P[idx]
+  gs.A = skip; gs.B = b + c1 * ldb; gs.C = c; gs.bias = bias;
+  gs.M = static_cast<int>(m); gs.N = static_cast<int>(n); gs.K = static_cast<int>(c2);
+  gs.lda = static_cast<int>(ld2); gs.ldb = static_cast<int>(ldb); gs.ldc = static_cast<int>(ldc);
+  gs.act = act; gs.stats = gn_partial;
+  gs.seed = pbuf; gs.ld_seed = static_cast<int>(ldp); gs.sidx = idx; gs.ldsi = static_cast<int>(ldi); gs.n_seed = static_cast<int>(n_coarse);
+  GemmPlan ps;  // the tile of the concatenated product, one pass over K
+  ps.tile = T64; ps.splits = 1;
+  set_tile_shape(ps, c2, true);
+  return launch_plan(ps, gs, 1, false, nullptr, gn_blocks, st);
 }
 
 // Two bias-only products C_i = A_i B_i + bias_i in one launch when both fit the 32x32 K-split kernel (else two launches).
@@ -1282,7 +1366,9 @@ extern "C" int rdm_patch_scores(const float* ref_feats, int64_t ld_ref, int64_t 
 // Decoder stage (experiments/backbone.py:118-151): y = act(GroupNorm([nearest_upsample(coarse) | skip] W + b)), or the plain
 // Linear into lin_out when gamma is null (decoder2).  The concatenated rows are formed inside the GEMM's A-tile loads when
 // c1 is a multiple of 32 (gemm_concat_with_stats); other widths (the 257-column coarse tensor of decoder4) go through
-// rdm_upsample_concat into the workspace first.
+// rdm_upsample_concat into the workspace first.  On the first route, a stage with fewer coarse than fine rows whose product
+// runs un-split multiplies the coarse rows once (into the workspace region the second route concatenates into) and seeds the
+// skip half's product with them: the same fma chain per element, so all routes of one tile and split factor give the same bits.
 extern "C" size_t rdm_decoder_stage_workspace_bytes(int64_t m, int64_t n, int64_t k) {
   return rdm_linear_group_norm_workspace_bytes(m, n) + rdm::align_up(static_cast<size_t>(m > 0 ? m : 1) * ((k + 3) / 4 * 4) * sizeof(float));
 }
@@ -1292,9 +1378,19 @@ extern "C" int rdm_decoder_stage(const float* coarse, int64_t n_coarse, int64_t 
                                  const float* bias, int64_t n, int groups, const float* gamma, const float* beta, float eps,
                                  int act, float* lin_out, int64_t ld_lin, float* y, int64_t ldy, void* ws, size_t ws_bytes,
                                  void* stream) {
-  using namespace rdm;
+  return rdm::decoder_stage_cols(coarse, n_coarse, c1, ld1, idx, ldi, skip, c2, ld2, m, w, ldw, bias, n, n, groups, gamma, beta, eps,
+                                 act, lin_out, ld_lin, y, ldy, ws, ws_bytes, stream);
+}
+
+// rdm_decoder_stage of which the caller reads the first n_need columns only (a plain Linear: gamma null when n_need < n): same
+// plan, same bits in those columns; the others are written or not (gemm_concat_with_stats).
+int rdm::decoder_stage_cols(const float* coarse, int64_t n_coarse, int64_t c1, int64_t ld1, const int64_t* idx, int64_t ldi,
+                            const float* skip, int64_t c2, int64_t ld2, int64_t m, const float* w, int64_t ldw, const float* bias,
+                            int64_t n, int64_t n_need, int groups, const float* gamma, const float* beta, float eps, int act,
+                            float* lin_out, int64_t ld_lin, float* y, int64_t ldy, void* ws, size_t ws_bytes, void* stream) {
   RDM_REQUIRE(coarse && idx && skip && w && lin_out && (!gamma || (beta && y)), "rdm_decoder_stage: null pointer");
   RDM_REQUIRE(c1 > 0 && c2 > 0 && n > 0 && m >= 0 && ldw % 4 == 0, "rdm_decoder_stage: bad sizes");
+  RDM_REQUIRE(n_need == n || (n_need > 0 && n_need < n && !gamma), "rdm_decoder_stage: %lld of %lld columns", (long long)n_need, (long long)n);
   if (m == 0) return RDM_OK;
   const int64_t k = c1 + c2, kpad = (k + 3) / 4 * 4;
   static const bool no_virtual = ::rdm::dev_knob("RDM_NO_VIRTUAL_CONCAT") != nullptr;  // developer knob: always materialise
@@ -1312,8 +1408,8 @@ extern "C" int rdm_decoder_stage(const float* coarse, int64_t n_coarse, int64_t 
   int nblk = 0;
   int rc = 1;
   if (!no_virtual && k == kpad)
-    rc = gemm_concat_with_stats(coarse, ld1, c1, n_coarse, idx, ldi, skip, ld2, c2, w, ldw, lin_out, ld_lin, m, n, bias, 0, gws,
-                                gemm_ws, gamma ? partial : nullptr, &nblk, stream);
+    rc = gemm_concat_with_stats(coarse, ld1, c1, n_coarse, idx, ldi, skip, ld2, c2, w, ldw, lin_out, ld_lin, m, n, n_need, bias, 0, cat,
+                                static_cast<size_t>(m) * kpad, gws, gemm_ws, gamma ? partial : nullptr, &nblk, stream);
   if (rc == 1) {
     if (int e = rdm_upsample_concat(coarse, n_coarse, c1, ld1, idx, ldi, skip, c2, ld2, m, cat, kpad, stream)) return e;
     rc = gemm_with_stats(cat, kpad, w, ldw, lin_out, ld_lin, m, n, kpad, bias, nullptr, gws, gemm_ws, gamma ? partial : nullptr,

@@ -15,11 +15,20 @@ int gemm_with_stats(const float* a, int64_t lda, const float* b, int64_t ldb, fl
 
 // gemm_with_stats with A = [coarse[idx[:, 0]] | skip] formed inside the kernel (the decoder's upsample + concatenation,
 // backbone.py:118-151); returns 1 (nothing launched) when the shapes need the materialised concatenation instead.
+// pbuf [pbuf_floats] (16-byte aligned, may be null): room for coarse B[0:c1] [n_coarse, pad4(n)], which lets an un-split product
+// with n_coarse < m multiply the coarse rows once and seed the skip half's product with them (same bits: gemm.hip).
+// n_need <= n: the columns the caller reads; the product is planned with n columns, and an un-split one computes n_need of them.
 void gemm_set_lds_pad(unsigned bytes);
 int gemm_concat_with_stats(const float* coarse, int64_t ld1, int64_t c1, int64_t n_coarse, const int64_t* idx, int64_t ldi,
                            const float* skip, int64_t ld2, int64_t c2, const float* b, int64_t ldb, float* c, int64_t ldc,
-                           int64_t m, int64_t n, const float* bias, int act, void* ws, size_t ws_bytes, double* gn_partial,
-                           int* gn_blocks, void* stream);
+                           int64_t m, int64_t n, int64_t n_need, const float* bias, int act, float* pbuf, size_t pbuf_floats,
+                           void* ws, size_t ws_bytes, double* gn_partial, int* gn_blocks, void* stream);
+// rdm_decoder_stage (include/rdmnet_hip.h) of which the caller reads the first n_need columns only (gamma null when n_need < n):
+// those columns hold the bits of the full call; the others are written only where the product runs split-K.
+int decoder_stage_cols(const float* coarse, int64_t n_coarse, int64_t c1, int64_t ld1, const int64_t* idx, int64_t ldi,
+                       const float* skip, int64_t c2, int64_t ld2, int64_t m, const float* w, int64_t ldw, const float* bias,
+                       int64_t n, int64_t n_need, int groups, const float* gamma, const float* beta, float eps, int act,
+                       float* lin_out, int64_t ld_lin, float* y, int64_t ldy, void* ws, size_t ws_bytes, void* stream);
 
 // Two independent products C_i = A_i B_i + bias_i (rdm_gemm semantics, no activation) in one launch when both are
 // transformer-sized; otherwise two rdm_gemm calls.
