@@ -1135,6 +1135,44 @@ int rdm_voxel_map_extract(const void* map, size_t map_bytes, int64_t capacity, i
                           float* points, int32_t* counts, int32_t* cells, int64_t max_rows, int64_t* n_rows, void* ws, size_t ws_bytes,
                           void* stream);
 
+/* ---- §7 voxel moments: per-voxel Gaussians of the voxel map (voxel_map.hip) ---------------------------------------------------
+ * Not in the reference tree -> parity unpinned; the project's own definition, pinned to the NumPy restatement
+ * tests/voxel_moments_restatement.py.  For a point that the map integrates, with Q_d and cell_d as above (the same gates,
+ * transform and quantisation), the local coordinate is u_d = (Q_d - (cell_d << F)) >> RDM_VOXEL_MOMENTS_SHIFT, in [0, 4096): 12
+ * bits, a resolution of voxel / 4096.  The point adds RDM_VOXEL_MOMENTS_PLANES non-negative integers to its voxel, in this order:
+ * u_x, u_y, u_z, u_x u_x, u_x u_y, u_x u_z, u_y u_y, u_y u_z, u_z u_z.  The sums stay below 2^56 for any uint32 count, so the int64
+ * integer atomic adds are exact and the moments, like the map, depend on the SET of integrated points only.
+ * A moments block is a second caller-owned device block of rdm_voxel_moments_bytes(capacity) bytes (0 for a bad capacity) beside
+ * the map block: nine int64 sums per slot, addressed by the map's slot index (a slot's nine sums are 72 consecutive bytes).
+ * rdm_voxel_moments_reset zeroes it (a fresh block must be reset, together with its map).  rdm_voxel_map_integrate_moments is
+ * rdm_voxel_map_integrate plus the block: ONE pass, the map's own adds and the nine moment adds go into the same slot; the
+ * gates, the six counters and the treatment of a full table are those of rdm_voxel_map_integrate, and a dropped point adds
+ * nothing anywhere.  A map must be integrated through one of the two functions throughout.  rdm_voxel_moments_rehash runs AFTER
+ * rdm_voxel_map_rehash(old_map -> new_map) on the same stream: it zeroes new_moments and, for every occupied slot of old_map,
+ * looks the key up in new_map (without claiming) and copies the nine sums.  rdm_voxel_map_extract_moments: selection, order,
+ * min_points, max_rows, *n_rows and the workspace (rdm_voxel_map_extract_workspace_bytes) are those of rdm_voxel_map_extract,
+ * so its rows are the rows of that call; per row, in float64 with this association and no contraction:
+ *   n = (double)count, m_a = S_a / n, s = voxel / 4096.0, s2 = s s, cov_ab = (S_ab / n - m_a m_b) s2
+ * -- the population covariance in m^2, no clamp.  Outputs: sums int64 [max_rows, 9] (may be null), cov f64 [max_rows, 6] (xx, xy,
+ * xz, yy, yz, zz), eigenvalues f64 [max_rows, 3] ascending, normals f64 [max_rows, 3]: the unit eigenvector of the smallest
+ * eigenvalue, signed so that its component of largest magnitude is positive (on a tie the lowest axis decides).  The solver is a
+ * float64 cyclic Jacobi with a fixed number of sweeps, one voxel per thread (the trigonometric closed form loses the small
+ * eigenvalue of a planar voxel).                                                                                               */
+#define RDM_VOXEL_MOMENTS_PLANES 9
+#define RDM_VOXEL_MOMENTS_SHIFT 8
+size_t rdm_voxel_moments_bytes(int64_t capacity);
+int rdm_voxel_moments_reset(void* moments, size_t moments_bytes, int64_t capacity, void* stream);
+int rdm_voxel_map_integrate_moments(void* map, size_t map_bytes, int64_t capacity, int channels, double voxel, const float* points,
+                                    int64_t ld, int64_t total, const int64_t* offsets, const double* poses, int64_t n_scans,
+                                    double min_range, double max_range, void* moments, size_t moments_bytes, void* stream);
+int rdm_voxel_moments_rehash(const void* old_map, size_t old_bytes, int64_t old_capacity, const void* old_moments,
+                             size_t old_moments_bytes, const void* new_map, size_t new_bytes, int64_t new_capacity, void* new_moments,
+                             size_t new_moments_bytes, int channels, void* stream);
+int rdm_voxel_map_extract_moments(const void* map, size_t map_bytes, int64_t capacity, int channels, const void* moments,
+                                  size_t moments_bytes, double voxel, int64_t min_points, int64_t* sums, double* cov,
+                                  double* eigenvalues, double* normals, int64_t max_rows, int64_t* n_rows, void* ws, size_t ws_bytes,
+                                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,7 @@ VOXEL_MAP_FRAC_BITS = 20  # = RDM_VOXEL_MAP_FRAC_BITS
 VOXEL_MAP_MAX_CHANNELS = 8  # = RDM_VOXEL_MAP_MAX_CHANNELS
 # rdm_voxel_map_stats' counters, in order (RDM_VOXEL_MAP_STATS of them)
 VOXEL_MAP_STATS = ('occupied', 'integrated', 'skipped_nonfinite', 'skipped_range', 'out_of_extent', 'dropped_full')
+VOXEL_MOMENTS_PLANES = 9  # = RDM_VOXEL_MOMENTS_PLANES: u_x, u_y, u_z, then u_a u_b for ab = xx, xy, xz, yy, yz, zz
 
 EVAL_RECORD_WIDTH = 20 # = RDM_EVAL_RECORD_WIDTH
 # the fields of one record of rdm_eval_pairs, in order
@@ -277,6 +278,13 @@ SIGNATURES = {
     'rdm_voxel_map_extract_workspace_bytes': (c_size, [c_i64]),
     'rdm_voxel_map_extract': (c_int, [c_void, c_size, c_i64, c_int, ctypes.c_double, c_i64, c_void, c_void, c_void, c_i64, c_void,
                                       c_void, c_size, c_void]),
+    'rdm_voxel_moments_bytes': (c_size, [c_i64]),
+    'rdm_voxel_moments_reset': (c_int, [c_void, c_size, c_i64, c_void]),
+    'rdm_voxel_map_integrate_moments': (c_int, [c_void, c_size, c_i64, c_int, ctypes.c_double, c_void, c_i64, c_i64, c_void, c_void,
+                                                c_i64, ctypes.c_double, ctypes.c_double, c_void, c_size, c_void]),
+    'rdm_voxel_moments_rehash': (c_int, [c_void, c_size, c_i64, c_void, c_size, c_void, c_size, c_i64, c_void, c_size, c_int, c_void]),
+    'rdm_voxel_map_extract_moments': (c_int, [c_void, c_size, c_i64, c_int, c_void, c_size, ctypes.c_double, c_i64, c_void, c_void,
+                                              c_void, c_void, c_i64, c_void, c_void, c_size, c_void]),
 }
 
 

@@ -17,6 +17,12 @@
 //
 // Extract: slot -> (key or all ones, slot), one radix sort of the S pairs (the unselected sort to the end; no read-back of
 // the count is needed before the sort), then one thread per selected row.
+//
+// Moments (include/rdmnet_hip.h, "voxel moments"; tests/voxel_moments_restatement.py): a second caller-owned block of nine int64
+// sums per slot, addressed by the map's slot index -- the first and second moments of the 12-bit local coordinates u_d, so every
+// voxel gets a mean, a covariance and a normal.  integrate_moments_kernel is the integrate kernel with nine more integer adds into
+// the slot that find_or_claim returned; the plain kernel is the same body with that block compiled out.  Extraction shares the
+// selection and the sort and solves the 3 x 3 symmetric eigenproblem per row with a float64 cyclic Jacobi of kSweeps sweeps.
 #include <cmath>
 
 #include "../../include/rdmnet_hip.h"
@@ -37,6 +43,11 @@ constexpr double kScale = 1048576.0;                 // 2^kFrac
 constexpr double kQLimit = 1099511627776.0;          // 2^40 = 2^20 cells of 2^20 steps
 constexpr int64_t kMaxCapacity = int64_t(1) << 30;   // slots are sorted as int32 values under a 32-bit count
 static_assert(kFrac == 20, "the key layout and kQLimit assume 20 fractional bits");
+constexpr int kPlanes = RDM_VOXEL_MOMENTS_PLANES;   // u_x, u_y, u_z, then u_a u_b for ab = xx, xy, xz, yy, yz, zz
+constexpr int kMomShift = RDM_VOXEL_MOMENTS_SHIFT;  // u_d = (Q_d - (cell_d << kFrac)) >> kMomShift: 12 bits
+constexpr double kMomSteps = 4096.0;                // 2^(kFrac - kMomShift) steps of u_d per voxel edge
+constexpr int kSweeps = 8;                          // cyclic Jacobi sweeps (a 3 x 3 symmetric matrix converges in 4 to 5)
+static_assert(kPlanes == 9 && kFrac - kMomShift == 12, "nine sums of 12-bit local coordinates");
 
 enum { kOccupied = 0, kIntegrated, kNonfinite, kRange, kExtent, kDropped };
 
@@ -90,6 +101,18 @@ __device__ __forceinline__ long long find_or_claim(unsigned long long* __restric
   return -1;
 }
 
+// Sum k of a slot in the moments block.  Slot-major: a slot's nine sums are 72 consecutive bytes, so a point's nine adds fall
+// into two (at most three) 64-byte lines.  -DRDM_VOXEL_MOMENTS_PLANE_MAJOR builds the [9][S] layout of the table's own sums, for the
+// comparison in docs/EXPERIMENTS.md; nothing outside this function knows the layout.
+__device__ __forceinline__ long long moment_at(long long slot, int k, long long capacity) {
+#ifdef RDM_VOXEL_MOMENTS_PLANE_MAJOR
+  return k * capacity + slot;
+#else
+  (void)capacity;
+  return slot * kPlanes + k;
+#endif
+}
+
 __global__ void __launch_bounds__(kBlock) reset_kernel(Table t, long long capacity, int channels) {
   const long long stride = static_cast<long long>(gridDim.x) * kBlock;
   const long long first = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
@@ -116,10 +139,13 @@ __device__ __forceinline__ long long scan_of(const int64_t* __restrict__ offsets
   return lo;
 }
 
-__global__ void __launch_bounds__(kBlock) integrate_kernel(Table t, long long capacity, int channels, double voxel,
-                                                           const float* __restrict__ points, long long ld, long long total,
-                                                           const int64_t* __restrict__ offsets, const double* __restrict__ poses,
-                                                           long long n_scans, double lo2, double hi2) {
+// The body of both integrate kernels.  kMoments = false is the plain integrate: `moments` is unused and every moments statement
+// is compiled out.
+template <bool kMoments>
+__device__ __forceinline__ void integrate_points(Table t, unsigned long long* __restrict__ moments, long long capacity, int channels,
+                                                 double voxel, const float* __restrict__ points, long long ld, long long total,
+                                                 const int64_t* __restrict__ offsets, const double* __restrict__ poses,
+                                                 long long n_scans, double lo2, double hi2) {
 #pragma clang fp contract(off)
   __shared__ unsigned int tally[kStats];
   if (threadIdx.x < kStats) tally[threadIdx.x] = 0u;
@@ -180,10 +206,65 @@ __global__ void __launch_bounds__(kBlock) integrate_kernel(Table t, long long ca
     atomicAdd(t.counts + slot, 1u);
     for (int c = 0; c < kMaxC; ++c)
       if (c < channels) atomicAdd(t.sums + c * capacity + slot, static_cast<unsigned long long>(q[c]));
+    if constexpr (kMoments) {
+      unsigned long long u[3];
+      for (int d = 0; d < 3; ++d) u[d] = static_cast<unsigned long long>((q[d] - ((q[d] >> kFrac) << kFrac)) >> kMomShift);
+      int k = 0;
+      for (int d = 0; d < 3; ++d) atomicAdd(moments + moment_at(slot, k++, capacity), u[d]);
+      for (int a = 0; a < 3; ++a)
+        for (int b = a; b < 3; ++b) atomicAdd(moments + moment_at(slot, k++, capacity), u[a] * u[b]);
+    }
   }
   __syncthreads();
   if (threadIdx.x < kStats && tally[threadIdx.x] != 0u)
     atomicAdd(t.counters + threadIdx.x, static_cast<unsigned long long>(tally[threadIdx.x]));
+}
+
+__global__ void __launch_bounds__(kBlock) integrate_kernel(Table t, long long capacity, int channels, double voxel,
+                                                           const float* __restrict__ points, long long ld, long long total,
+                                                           const int64_t* __restrict__ offsets, const double* __restrict__ poses,
+                                                           long long n_scans, double lo2, double hi2) {
+  integrate_points<false>(t, nullptr, capacity, channels, voxel, points, ld, total, offsets, poses, n_scans, lo2, hi2);
+}
+
+__global__ void __launch_bounds__(kBlock) integrate_moments_kernel(Table t, unsigned long long* __restrict__ moments, long long capacity,
+                                                                   int channels, double voxel, const float* __restrict__ points,
+                                                                   long long ld, long long total, const int64_t* __restrict__ offsets,
+                                                                   const double* __restrict__ poses, long long n_scans, double lo2,
+                                                                   double hi2) {
+  integrate_points<true>(t, moments, capacity, channels, voxel, points, ld, total, offsets, poses, n_scans, lo2, hi2);
+}
+
+__global__ void __launch_bounds__(kBlock) moments_reset_kernel(unsigned long long* __restrict__ moments, long long words) {
+  const long long stride = static_cast<long long>(gridDim.x) * kBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < words; i += stride) moments[i] = 0ull;
+}
+
+// The slot of `key` in a table that is not being written, or -1: the probe ends at the key, at an empty slot or after one cycle.
+__device__ __forceinline__ long long find(const unsigned long long* __restrict__ keys, long long capacity, unsigned long long key) {
+  const unsigned long long mask = static_cast<unsigned long long>(capacity) - 1ull;
+  unsigned long long slot = mix(key) & mask;
+  for (long long probe = 0; probe < capacity; ++probe) {
+    const unsigned long long k = keys[slot];
+    if (k == key) return static_cast<long long>(slot);
+    if (k == kEmpty) return -1;
+    slot = (slot + 1ull) & mask;
+  }
+  return -1;
+}
+
+// After rehash_kernel moved the table `a` into `b`: the nine sums of every occupied slot of `a` into the slot its key has in `b`
+// (`mb` zeroed before; the keys are distinct, so plain stores).
+__global__ void __launch_bounds__(kBlock) moments_rehash_kernel(Table a, const unsigned long long* __restrict__ ma, long long cap_a,
+                                                                Table b, unsigned long long* __restrict__ mb, long long cap_b) {
+  const long long stride = static_cast<long long>(gridDim.x) * kBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < cap_a; i += stride) {
+    const unsigned long long key = a.keys[i];
+    if (key == kEmpty) continue;
+    const long long slot = find(b.keys, cap_b, key);
+    if (slot < 0) continue;  // (a key that the map's rehash did not move: not reached after rdm_voxel_map_rehash)
+    for (int k = 0; k < kPlanes; ++k) mb[moment_at(slot, k, cap_b)] = ma[moment_at(i, k, cap_a)];
+  }
 }
 
 // Every occupied slot of `a` into `b` (reset before): the keys are distinct, so a slot is claimed once and filled with plain stores.
@@ -244,6 +325,92 @@ __global__ void __launch_bounds__(kBlock) emit_kernel(Table t, long long capacit
   }
 }
 
+// Eigenvalues (ascending) and the unit eigenvector of the smallest one of the symmetric matrix {xx, xy, xz, yy, yz, zz}: cyclic
+// Jacobi, kSweeps sweeps over (0,1), (0,2), (1,2) with Rutishauser's update.  A rotation whose off-diagonal entry is already zero
+// is passed over, so a diagonal matrix (a single point: all zeros) comes back as it is.  No trigonometric closed form: that loses
+// the small eigenvalue of a planar voxel to cancellation.
+__device__ __forceinline__ void jacobi3(const double* __restrict__ cov, double* __restrict__ eig, double* __restrict__ normal) {
+  double a[3][3] = {{cov[0], cov[1], cov[2]}, {cov[1], cov[3], cov[4]}, {cov[2], cov[4], cov[5]}};
+  double v[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+  for (int sweep = 0; sweep < kSweeps; ++sweep) {
+#pragma unroll
+    for (int pair = 0; pair < 3; ++pair) {
+      const int p = pair == 2 ? 1 : 0, q = pair == 0 ? 1 : 2, r = 3 - p - q;
+      const double apq = a[p][q];
+      if (apq == 0.0) continue;
+      const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
+      const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));  // (theta = +-inf: t = 0)
+      const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, tau = s / (1.0 + c);
+      a[p][p] -= t * apq;
+      a[q][q] += t * apq;
+      a[p][q] = a[q][p] = 0.0;
+      const double arp = a[r][p], arq = a[r][q];
+      a[r][p] = a[p][r] = arp - s * (arq + tau * arp);
+      a[r][q] = a[q][r] = arq + s * (arp - tau * arq);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const double vkp = v[k][p], vkq = v[k][q];
+        v[k][p] = vkp - s * (vkq + tau * vkp);
+        v[k][q] = vkq + s * (vkp - tau * vkq);
+      }
+    }
+  }
+  // ascending, ties in index order
+  int i0 = 0, i1 = 1, i2 = 2;
+  if (a[i1][i1] < a[i0][i0]) { const int x = i0; i0 = i1; i1 = x; }
+  if (a[i2][i2] < a[i1][i1]) { const int x = i1; i1 = i2; i2 = x; }
+  if (a[i1][i1] < a[i0][i0]) { const int x = i0; i0 = i1; i1 = x; }
+  eig[0] = a[i0][i0];
+  eig[1] = a[i1][i1];
+  eig[2] = a[i2][i2];
+  double n[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) n[k] = i0 == 0 ? v[k][0] : (i0 == 1 ? v[k][1] : v[k][2]);
+  const double len = sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+  int big = 0;  // the component of largest magnitude is positive; on a tie the lowest axis decides
+  if (fabs(n[1]) > fabs(n[big])) big = 1;
+  if (fabs(n[2]) > fabs(n[big])) big = 2;
+  const double sign = (big == 0 ? n[0] : (big == 1 ? n[1] : n[2])) < 0.0 ? -1.0 : 1.0;
+  for (int k = 0; k < 3; ++k) normal[k] = sign * n[k] / len;
+}
+
+__global__ void __launch_bounds__(kBlock) emit_moments_kernel(Table t, const unsigned long long* __restrict__ moments, long long capacity,
+                                                              double voxel, const int* __restrict__ slots,
+                                                              const unsigned long long* __restrict__ n_sel, long long max_rows,
+                                                              int64_t* __restrict__ sums, double* __restrict__ cov,
+                                                              double* __restrict__ eigenvalues, double* __restrict__ normals,
+                                                              int64_t* __restrict__ n_rows) {
+#pragma clang fp contract(off)
+  const long long stride = static_cast<long long>(gridDim.x) * kBlock;
+  const long long first = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
+  const long long m = static_cast<long long>(*n_sel);
+  if (first == 0) *n_rows = m;
+  const long long rows = m < max_rows ? m : max_rows;
+  const double s = voxel / kMomSteps, s2 = s * s;
+  for (long long r = first; r < rows; r += stride) {
+    const long long slot = slots[r];
+    const double n = static_cast<double>(t.counts[slot]);
+    double S[kPlanes];
+    for (int k = 0; k < kPlanes; ++k) {
+      const long long v = static_cast<long long>(moments[moment_at(slot, k, capacity)]);
+      if (sums != nullptr) sums[r * kPlanes + k] = v;
+      S[k] = static_cast<double>(v);
+    }
+    const double mean[3] = {S[0] / n, S[1] / n, S[2] / n};
+    double c[6];
+    int k = 0;
+    for (int a = 0; a < 3; ++a)
+      for (int b = a; b < 3; ++b, ++k) c[k] = (S[3 + k] / n - mean[a] * mean[b]) * s2;
+    double eig[3], normal[3];
+    jacobi3(c, eig, normal);
+    for (k = 0; k < 6; ++k) cov[r * 6 + k] = c[k];
+    for (k = 0; k < 3; ++k) {
+      eigenvalues[r * 3 + k] = eig[k];
+      normals[r * 3 + k] = normal[k];
+    }
+  }
+}
+
 unsigned blocks_for(int64_t n) {
   const int64_t b = (n + kBlock - 1) / kBlock;
   return static_cast<unsigned>(b < 1 ? 1 : (b > static_cast<int64_t>(kMaxBlocks) ? kMaxBlocks : b));
@@ -277,6 +444,19 @@ int open_table(const char* what, void* map, size_t map_bytes, int64_t capacity, 
   Arena ar(map, map_bytes);
   if (!carve(ar, capacity, channels, t)) {
     set_error("%s: the map block is too small (%zu < %zu bytes)", what, map_bytes, ar.off);
+    return RDM_ERR_WORKSPACE;
+  }
+  return RDM_OK;
+}
+
+
+// the moments block of a caller, or the error code after set_error
+int open_moments(const char* what, void* moments, size_t moments_bytes, int64_t capacity, unsigned long long*& m) {
+  RDM_REQUIRE(moments != nullptr, "%s: null moments block", what);
+  Arena ar(moments, moments_bytes);
+  m = ar.take<unsigned long long>(static_cast<size_t>(capacity) * kPlanes);
+  if (!ar.ok) {
+    set_error("%s: the moments block is too small (%zu < %zu bytes)", what, moments_bytes, ar.off);
     return RDM_ERR_WORKSPACE;
   }
   return RDM_OK;
@@ -381,4 +561,97 @@ extern "C" int rdm_voxel_map_extract(const void* map, size_t map_bytes, int64_t 
   hipLaunchKernelGGL(emit_kernel, dim3(blocks_for(max_rows)), dim3(kBlock), 0, s, t, static_cast<long long>(capacity), channels, voxel,
                      w.keys, w.slots, w.n_sel, static_cast<long long>(max_rows), points, counts, cells, n_rows);
   return launch_status("rdm_voxel_map_extract");
+}
+
+// ---- voxel moments ------------------------------------------------------------------------------------------------------------
+
+extern "C" size_t rdm_voxel_moments_bytes(int64_t capacity) {
+  using namespace rdm;
+  if (!shape_ok(capacity, 3)) return 0;
+  Arena ar(nullptr, 0);
+  ar.take<unsigned long long>(static_cast<size_t>(capacity) * kPlanes);
+  return ar.off;
+}
+
+extern "C" int rdm_voxel_moments_reset(void* moments, size_t moments_bytes, int64_t capacity, void* stream) {
+  using namespace rdm;
+  RDM_REQUIRE(shape_ok(capacity, 3), "rdm_voxel_moments_reset: capacity must be a power of two in [64, 2^30], got %lld",
+              static_cast<long long>(capacity));
+  unsigned long long* m;
+  if (const int rc = open_moments("rdm_voxel_moments_reset", moments, moments_bytes, capacity, m)) return rc;
+  hipLaunchKernelGGL(moments_reset_kernel, dim3(blocks_for(capacity * kPlanes)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), m,
+                     static_cast<long long>(capacity) * kPlanes);
+  return launch_status("rdm_voxel_moments_reset");
+}
+
+extern "C" int rdm_voxel_map_integrate_moments(void* map, size_t map_bytes, int64_t capacity, int channels, double voxel,
+                                               const float* points, int64_t ld, int64_t total, const int64_t* offsets,
+                                               const double* poses, int64_t n_scans, double min_range, double max_range, void* moments,
+                                               size_t moments_bytes, void* stream) {
+  using namespace rdm;
+  Table t;
+  unsigned long long* m;
+  if (const int rc = open_table("rdm_voxel_map_integrate_moments", map, map_bytes, capacity, channels, t)) return rc;
+  if (const int rc = open_moments("rdm_voxel_map_integrate_moments", moments, moments_bytes, capacity, m)) return rc;
+  RDM_REQUIRE(voxel > 0.0 && std::isfinite(voxel), "rdm_voxel_map_integrate_moments: voxel must be positive and finite");
+  RDM_REQUIRE(n_scans >= 0 && total >= 0 && ld >= channels, "rdm_voxel_map_integrate_moments: bad sizes (ld must be >= channels)");
+  RDM_REQUIRE(min_range >= 0.0 && max_range >= min_range, "rdm_voxel_map_integrate_moments: need 0 <= min_range <= max_range");
+  if (n_scans == 0 || total == 0) return RDM_OK;
+  RDM_REQUIRE(points && offsets && poses, "rdm_voxel_map_integrate_moments: null argument");
+  hipLaunchKernelGGL(integrate_moments_kernel, dim3(blocks_for(total)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), t, m,
+                     static_cast<long long>(capacity), channels, voxel, points, static_cast<long long>(ld),
+                     static_cast<long long>(total), offsets, poses, static_cast<long long>(n_scans), min_range * min_range,
+                     max_range * max_range);
+  return launch_status("rdm_voxel_map_integrate_moments");
+}
+
+extern "C" int rdm_voxel_moments_rehash(const void* old_map, size_t old_bytes, int64_t old_capacity, const void* old_moments,
+                                        size_t old_moments_bytes, const void* new_map, size_t new_bytes, int64_t new_capacity,
+                                        void* new_moments, size_t new_moments_bytes, int channels, void* stream) {
+  using namespace rdm;
+  Table a, b;
+  unsigned long long *ma, *mb;
+  if (const int rc = open_table("rdm_voxel_moments_rehash (old)", const_cast<void*>(old_map), old_bytes, old_capacity, channels, a)) return rc;
+  if (const int rc = open_table("rdm_voxel_moments_rehash (new)", const_cast<void*>(new_map), new_bytes, new_capacity, channels, b)) return rc;
+  if (const int rc = open_moments("rdm_voxel_moments_rehash (old)", const_cast<void*>(old_moments), old_moments_bytes, old_capacity, ma)) return rc;
+  if (const int rc = open_moments("rdm_voxel_moments_rehash (new)", new_moments, new_moments_bytes, new_capacity, mb)) return rc;
+  RDM_REQUIRE(new_capacity >= old_capacity && new_map != old_map && new_moments != old_moments,
+              "rdm_voxel_moments_rehash: the new map and moments must be other blocks of at least the old capacity");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(moments_reset_kernel, dim3(blocks_for(new_capacity * kPlanes)), dim3(kBlock), 0, s, mb,
+                     static_cast<long long>(new_capacity) * kPlanes);
+  hipLaunchKernelGGL(moments_rehash_kernel, dim3(blocks_for(old_capacity)), dim3(kBlock), 0, s, a, ma, static_cast<long long>(old_capacity),
+                     b, mb, static_cast<long long>(new_capacity));
+  return launch_status("rdm_voxel_moments_rehash");
+}
+
+extern "C" int rdm_voxel_map_extract_moments(const void* map, size_t map_bytes, int64_t capacity, int channels, const void* moments,
+                                             size_t moments_bytes, double voxel, int64_t min_points, int64_t* sums, double* cov,
+                                             double* eigenvalues, double* normals, int64_t max_rows, int64_t* n_rows, void* ws,
+                                             size_t ws_bytes, void* stream) {
+  using namespace rdm;
+  Table t;
+  unsigned long long* m;
+  if (const int rc = open_table("rdm_voxel_map_extract_moments", const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
+  if (const int rc = open_moments("rdm_voxel_map_extract_moments", const_cast<void*>(moments), moments_bytes, capacity, m)) return rc;
+  RDM_REQUIRE(voxel > 0.0 && std::isfinite(voxel), "rdm_voxel_map_extract_moments: voxel must be positive and finite");
+  RDM_REQUIRE(min_points >= 0 && max_rows >= 0 && n_rows != nullptr, "rdm_voxel_map_extract_moments: bad min_points, max_rows or null n_rows");
+  RDM_REQUIRE(max_rows == 0 || (cov && eigenvalues && normals), "rdm_voxel_map_extract_moments: null output");
+  Arena ar(ws, ws_bytes);
+  ExtractWork w;
+  if (!carve_extract(ar, capacity, w)) {
+    set_error("rdm_voxel_map_extract_moments: workspace too small (%zu < %zu bytes)", ws_bytes, ar.off);
+    return RDM_ERR_WORKSPACE;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned int least = min_points > 0xffffffffll ? 0xffffffffu : static_cast<unsigned int>(min_points);
+  fill_words<unsigned long long>(w.n_sel, 1, 0ull, s);
+  hipLaunchKernelGGL(select_kernel, dim3(blocks_for(capacity)), dim3(kBlock), 0, s, t, static_cast<long long>(capacity), least, w.keys_in,
+                     w.slots_in, w.n_sel);
+  size_t bytes = w.sort_bytes;
+  RDM_HIP_CHECK(rocprim::radix_sort_pairs(w.sort_tmp, bytes, w.keys_in, w.keys, w.slots_in, w.slots, static_cast<unsigned>(capacity), 0u,
+                                          64u, s));
+  hipLaunchKernelGGL(emit_moments_kernel, dim3(blocks_for(max_rows)), dim3(kBlock), 0, s, t, m, static_cast<long long>(capacity), voxel,
+                     w.slots, w.n_sel, static_cast<long long>(max_rows), sums, cov, eigenvalues, normals, n_rows);
+  return launch_status("rdm_voxel_map_extract_moments");
 }

@@ -794,9 +794,11 @@ class VoxelMap:
     origin); channels C = 3 ... 8: xyz and C - 3 attributes (4: intensity); capacity: the table's first size, a power of two >= 64
     -- it grows by itself.  Per voxel a count and C int64 sums of 20-bit fixed-point values under integer atomic adds, so the
     map depends on the set of integrated points only: the order of the scans, the batching and the run do not change one bit
-    of what `extract` returns."""
+    of what `extract` returns.  moments=True keeps nine more int64 sums per voxel in a second block (rdm_voxel_moments_*: the first
+    and second moments of the 12-bit local coordinates), which give every voxel a mean, a covariance and a normal --
+    `extract_moments` -- and the map a sharpness report -- `sharpness`; `extract` and `stats` are the same bytes either way."""
 
-    def __init__(self, voxel, channels=4, capacity=1 << 20, device='cuda'):
+    def __init__(self, voxel, channels=4, capacity=1 << 20, device='cuda', moments=False):
         voxel, channels, capacity = float(voxel), int(channels), int(capacity)
         if not (voxel > 0 and voxel < float('inf')):
             raise ValueError(f'voxel must be positive and finite, got {voxel}')
@@ -810,11 +812,16 @@ class VoxelMap:
             raise ValueError(f'VoxelMap needs a CUDA device, got {self.device}')
         if self.device.index is None:
             self.device = torch.device('cuda', torch.cuda.current_device())
+        self.moments = bool(moments)
         self.capacity, self._buf = capacity, self._alloc(capacity)
+        self._mom = self._alloc_moments(capacity) if self.moments else None
         self.reset()
 
     def _alloc(self, capacity):
         return torch.empty((_lib.lib().rdm_voxel_map_bytes(capacity, self.channels),), dtype=torch.uint8, device=self.device)
+
+    def _alloc_moments(self, capacity):
+        return torch.empty((_lib.lib().rdm_voxel_moments_bytes(capacity),), dtype=torch.uint8, device=self.device)
 
     def _head(self):
         return self._buf.data_ptr(), self._buf.numel(), self.capacity, self.channels
@@ -822,6 +829,9 @@ class VoxelMap:
     def reset(self):
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().rdm_voxel_map_reset(*self._head(), _lib.stream_ptr()), 'rdm_voxel_map_reset')
+            if self.moments:
+                _lib.check(_lib.lib().rdm_voxel_moments_reset(self._mom.data_ptr(), self._mom.numel(), self.capacity, _lib.stream_ptr()),
+                           'rdm_voxel_moments_reset')
         self._bound = 0  # occupied <= _bound: spares the read-back of `occupied` while the table is certainly large enough
 
     def stats(self):
@@ -851,6 +861,13 @@ class VoxelMap:
                     _lib.check(_lib.lib().rdm_voxel_map_rehash(self._buf.data_ptr(), self._buf.numel(), self.capacity, new.data_ptr(),
                                                                new.numel(), capacity, self.channels, _lib.stream_ptr()),
                                'rdm_voxel_map_rehash')
+                    if self.moments:
+                        mom = self._alloc_moments(capacity)
+                        _lib.check(_lib.lib().rdm_voxel_moments_rehash(self._buf.data_ptr(), self._buf.numel(), self.capacity,
+                                                                       self._mom.data_ptr(), self._mom.numel(), new.data_ptr(), new.numel(),
+                                                                       capacity, mom.data_ptr(), mom.numel(), self.channels,
+                                                                       _lib.stream_ptr()), 'rdm_voxel_moments_rehash')
+                        self._mom = mom
                 self.capacity, self._buf = capacity, new  # (the old block is freed in stream order by the caching allocator)
         self._bound += n_points
 
@@ -908,8 +925,14 @@ class VoxelMap:
         with torch.cuda.device(self.device):
             offsets = offsets.to(self.device).contiguous()
             X = torch.from_numpy(X).to(self.device)
-            _lib.check(_lib.lib().rdm_voxel_map_integrate(*self._head(), self.voxel, points.data_ptr(), ld, total, offsets.data_ptr(),
-                                                          X.data_ptr(), n, lo, hi, _lib.stream_ptr()), 'rdm_voxel_map_integrate')
+            if self.moments:
+                _lib.check(_lib.lib().rdm_voxel_map_integrate_moments(*self._head(), self.voxel, points.data_ptr(), ld, total,
+                                                                      offsets.data_ptr(), X.data_ptr(), n, lo, hi, self._mom.data_ptr(),
+                                                                      self._mom.numel(), _lib.stream_ptr()),
+                           'rdm_voxel_map_integrate_moments')
+            else:
+                _lib.check(_lib.lib().rdm_voxel_map_integrate(*self._head(), self.voxel, points.data_ptr(), ld, total, offsets.data_ptr(),
+                                                              X.data_ptr(), n, lo, hi, _lib.stream_ptr()), 'rdm_voxel_map_integrate')
         return self
 
     def extract(self, min_points=1):
@@ -929,6 +952,55 @@ class VoxelMap:
                                                _lib.stream_ptr()), 'rdm_voxel_map_extract')
         m = int(n_rows.item())
         return points[:m], counts[:m], cells[:m]
+
+    def _need_moments(self, what):
+        if not self.moments:
+            raise ValueError(f'VoxelMap.{what} needs a map created with moments=True')
+
+    def extract_moments(self, min_points=1):
+        """-> (sums int64 [M, 9], cov float64 [M, 6], eigenvalues float64 [M, 3], normals float64 [M, 3]) on the device, row-aligned
+        with extract(min_points).  sums: of u_x, u_y, u_z, u_x u_x, u_x u_y, u_x u_z, u_y u_y, u_y u_z, u_z u_z over the voxel's points,
+        u = the 12-bit local coordinate; cov: the population covariance in m^2 (xx, xy, xz, yy, yz, zz); eigenvalues ascending; normals:
+        the unit eigenvector of the smallest, its component of largest magnitude positive.  Two read-backs (sizes)."""
+        self._need_moments('extract_moments')
+        L = _lib.lib()
+        rows = self.stats()['occupied']
+        dev, P = self.device, _lib.VOXEL_MOMENTS_PLANES
+        sums = torch.empty((max(rows, 1), P), dtype=torch.int64, device=dev)
+        real = torch.empty((max(rows, 1), 12), dtype=torch.float64, device=dev)  # cov, eigenvalues, normals
+        cov, eig, normals = (real.view(-1)[a * max(rows, 1):b * max(rows, 1)].view(max(rows, 1), b - a) for a, b in ((0, 6), (6, 9), (9, 12)))
+        n_rows = torch.zeros((1,), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            ws = scratch(dev, L.rdm_voxel_map_extract_workspace_bytes(self.capacity))
+            _lib.check(L.rdm_voxel_map_extract_moments(*self._head(), self._mom.data_ptr(), self._mom.numel(), self.voxel, int(min_points),
+                                                       sums.data_ptr(), cov.data_ptr(), eig.data_ptr(), normals.data_ptr(), rows,
+                                                       n_rows.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+                       'rdm_voxel_map_extract_moments')
+        m = int(n_rows.item())
+        return sums[:m], cov[:m], eig[:m], normals[:m]
+
+    def sharpness(self, min_points=4):
+        """The ground-truth-free map report over the voxels with at least min_points points (4: the smallest count at which a
+        3 x 3 population covariance can have full rank) -> dict: voxels (all occupied), qualified (count >= min_points), degenerate
+        (qualified without smallest eigenvalue > 0), plane_thickness = sqrt(mean(max(l0, 0))) in metres over the qualified, entropy =
+        the mean of 0.5 ln((2 pi e)^3 l0 l1 l2) over the qualified that are not degenerate (mean plane variance and mean map entropy
+        after Razlaw et al. and Droeschel & Behnke).  Lower is sharper for both; nan where there is no voxel to average.  Reduced on
+        the device; one read-back beside extract_moments'."""
+        import math
+        self._need_moments('sharpness')
+        if int(min_points) < 1:
+            raise ValueError(f'min_points must be >= 1, got {min_points}')
+        eig = self.extract_moments(min_points)[2]
+        voxels, qualified = self._bound, int(eig.shape[0])  # (extract_moments has just read `occupied`)
+        full = eig[:, 0] > 0
+        k = (2.0 * math.pi * math.e) ** 3
+        product = torch.where(full, k * eig[:, 0] * eig[:, 1] * eig[:, 2], 1.0)  # (ln 1 = 0 for the degenerate: no gather, no read-back)
+        out = torch.stack([full.sum().double(), eig[:, 0].clamp_min(0.0).sum(), (0.5 * torch.log(product)).sum()])
+        n_full, thick, ent = out.cpu().tolist()
+        n_full = int(n_full)
+        return dict(voxels=voxels, qualified=qualified, degenerate=qualified - n_full,
+                    plane_thickness=math.sqrt(thick / qualified) if qualified else float('nan'),
+                    entropy=ent / n_full if n_full else float('nan'))
 
 
 class RegistrationResult:

@@ -3,7 +3,7 @@
     python -m rdmnet_amd.trajectory --features-root DIR [--optimize] [--line-process-weight MU] [--unit-information] [--out DIR]
                                   [--preconditioner {block_jacobi,chain}] [--linear-solver {pcg,direct}]
                                   [--map-scans DATASET_ROOT [--map-raw] [--map-voxel 0.3] [--map-min-points 1]
-                                   [--map-range LO HI] [--map-batch 64]]
+                                   [--map-range LO HI] [--map-batch 64] [--map-sharpness [--map-sharpness-min-points 4]]]
 
 reads the `{seq}_{src}_{ref}.npz` pair files that `python -m rdmnet_amd.infer` wrote into DIR (ordered and filtered as
 `python -m rdmnet_amd.eval` reads them) and, per sequence, chains the pair poses into a trajectory as
@@ -17,7 +17,11 @@ these graphs; --linear-solver direct its direct sparse solve in place of the con
 GPU is needed.  Everything here is numpy float64 on the host.  With --map-scans (and --out) the scans of every sequence's chain
 frames are fused under the chained -- and with --optimize also the optimised -- poses into a voxel map on the GPU (`build_map`,
 `ops.VoxelMap`) and written as `{seq}_{variant}_map.npy`; a better trajectory puts the same surfaces into
-fewer voxels, so voxels and points per voxel of the two variants are a check of --optimize that needs no ground truth."""
+fewer voxels, so voxels and points per voxel of the two variants are a check of --optimize that needs no ground truth.  The
+count is blind to small pose errors (they thicken the surfaces inside the voxels long before they spill into new ones), so with
+--map-sharpness the map also keeps per-voxel second moments and every `map:` line is followed by a `sharpness:` line: the mean
+plane thickness (root of the mean smallest covariance eigenvalue) and the mean map entropy over the voxels with at least
+--map-sharpness-min-points points; lower is sharper for both."""
 import argparse
 import math
 import os
@@ -163,15 +167,15 @@ def write_kitti_poses(path, poses):
 
 # ---- the map of a run ------------------------------------------------------------------------------------------------------
 
-MAP_DEFAULTS = dict(voxel=0.3, min_points=1, batch=64)
+MAP_DEFAULTS = dict(voxel=0.3, min_points=1, batch=64, sharpness_min_points=4)
 
 
 def build_map(paths, poses, voxel=MAP_DEFAULTS['voxel'], channels=None, min_range=0.0, max_range=math.inf, batch=MAP_DEFAULTS['batch'],
-              capacity=1 << 20, device='cuda'):
+              capacity=1 << 20, device='cuda', moments=False):
     """The scans `paths` (.npy float32 [N, C] or KITTI .bin [N, 4], read by prepare.load_scan) under `poses` ([n, 4, 4], world =
     pose @ point) fused into an ops.VoxelMap.  channels None: the columns of the first scan (at most 8).  `batch` scans are read on
-    a background thread while the previous batch is on the GPU; a batch is one host-to-device copy and one integrate call.  A
-    missing file is a TrajectoryError that names it (checked before anything is read)."""
+    a background thread while the previous batch is on the GPU; a batch is one host-to-device copy and one integrate call.
+    moments: keep the per-voxel second moments too (ops.VoxelMap(moments=True): extract_moments, sharpness).  A missing file is a TrajectoryError that names it (checked before anything is read)."""
     paths = list(paths)
     poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
     if len(paths) != len(poses):
@@ -197,13 +201,13 @@ def build_map(paths, poses, voxel=MAP_DEFAULTS['voxel'], channels=None, min_rang
     for group, (points, offsets) in prepare._read_ahead(load, groups):
         if vmap is None:
             width = points.shape[1] if channels is None else int(channels)
-            vmap = ops.VoxelMap(voxel, channels=min(width, 8), capacity=capacity, device=device)
+            vmap = ops.VoxelMap(voxel, channels=min(width, 8), capacity=capacity, device=device, moments=moments)
         if points.shape[1] < vmap.channels:
             raise TrajectoryError(f'{paths[group[0]]}: {points.shape[1]} columns, the map has {vmap.channels} channels')
         vmap.integrate((torch.from_numpy(points).to(vmap.device), torch.from_numpy(offsets)), poses[group[0]:group[1]], min_range,
                        max_range)
     if vmap is None:
-        vmap = ops.VoxelMap(voxel, channels=4 if channels is None else int(channels), capacity=capacity, device=device)
+        vmap = ops.VoxelMap(voxel, channels=4 if channels is None else int(channels), capacity=capacity, device=device, moments=moments)
     return vmap
 
 
@@ -213,19 +217,33 @@ def map_line(seq, what, voxel, voxels, points, stats):
             f"{stats['skipped_nonfinite']} non-finite, {stats['skipped_range']} out of range, {stats['out_of_extent']} out of extent")
 
 
+def sharpness_line(seq, what, min_points, report):
+    return (f"seq {seq} {what} sharpness: {report['qualified']} of {report['voxels']} voxels with >= {min_points} points, plane thickness "
+            f"{report['plane_thickness'] * 1e3:.3f} mm, entropy {report['entropy']:.4f} ({report['degenerate']} degenerate)")
+
+
 def write_map(args, seq, what, paths, poses, emit):
     lo, hi = args.map_range if args.map_range else (0.0, math.inf)
-    vmap = build_map(paths, poses, voxel=args.map_voxel, min_range=lo, max_range=hi, batch=args.map_batch)
+    sharpness = bool(getattr(args, 'map_sharpness', False))
+    vmap = build_map(paths, poses, voxel=args.map_voxel, min_range=lo, max_range=hi, batch=args.map_batch, moments=sharpness)
     points, counts, _ = vmap.extract(args.map_min_points)
     points, counts = points.cpu().numpy(), counts.cpu().numpy()
     np.save(osp.join(args.out, f'{seq}_{what}_map.npy'), np.concatenate([points, counts[:, None].astype(np.float32)], 1))
     emit(map_line(seq, what, args.map_voxel, len(counts), int(counts.sum(dtype=np.int64)), vmap.stats()))
+    if sharpness:
+        emit(sharpness_line(seq, what, args.map_sharpness_min_points, vmap.sharpness(args.map_sharpness_min_points)))
 
 
 def map_paths(args, seqs):
     """{seq: the scan file of every chain frame}, after the checks that need no GPU."""
     if not getattr(args, 'map_scans', None):
+        if getattr(args, 'map_sharpness', False):
+            raise TrajectoryError('--map-sharpness needs --map-scans (the report is taken over the map of the scans)')
+        if getattr(args, 'map_sharpness_min_points', None) not in (None, MAP_DEFAULTS['sharpness_min_points']):
+            raise TrajectoryError('--map-sharpness-min-points needs --map-scans and --map-sharpness')
         return None
+    if getattr(args, 'map_sharpness', False) and args.map_sharpness_min_points < 2:
+        raise TrajectoryError(f'--map-sharpness-min-points must be >= 2 (a covariance needs two points), got {args.map_sharpness_min_points}')
     if not args.out:
         raise TrajectoryError('--map-scans needs --out (the directory the maps are written to)')
     if not (args.map_voxel > 0 and math.isfinite(args.map_voxel)) or args.map_min_points < 1 or args.map_batch < 1:
@@ -313,6 +331,11 @@ def make_parser():
     ap.add_argument('--map-range', type=float, nargs=2, default=None, metavar=('LO', 'HI'),
                     help='integrate the points whose range in the sensor frame is within [LO, HI] metres (default: all)')
     ap.add_argument('--map-batch', type=int, default=MAP_DEFAULTS['batch'], help='scans per host-to-device copy and integrate call')
+    ap.add_argument('--map-sharpness', action='store_true',
+                    help='keep per-voxel second moments and print, after every map line, the mean plane thickness and the mean map '
+                         'entropy of that map (needs --map-scans); lower is sharper')
+    ap.add_argument('--map-sharpness-min-points', type=int, default=MAP_DEFAULTS['sharpness_min_points'], metavar='N',
+                    help='take the sharpness report over the voxels with at least N >= 2 points')
     return ap
 
 

@@ -1,6 +1,7 @@
 """Times the voxel map (ops.VoxelMap) on synthetic scans along a synthetic drive.
 
   python tools/map_bench.py [--frames 256] [--points 120000 | 18000] [--reps 3] [--batch 64] [--voxel 0.3] [--cpu] [--cpu-frames 8]
+                              [--moments]
 Prints one JSON line per case:
   * integrate: --frames scans of --points points (120 000: a raw scan; 18 000: a down-sampled one), xyz + intensity, integrated in
     batches of --batch from device memory into a table created large enough (no growth inside the timing); device time between
@@ -10,6 +11,9 @@ Prints one JSON line per case:
     its scans from disk through host memory, is bound by at the latest;
   * extract: ms for the voxels of that map (select, radix sort of the slots, emit), and the voxels per second;
   * rehash: ms for one rdm_voxel_map_rehash of that map into a table of twice the capacity;
+  * with --moments: the same integrate into a map with the nine second-moment sums beside it (ops.VoxelMap(moments=True): 14 integer
+    atomic adds a point instead of 5, (8 C + 4 + 72) B), its points/s and the ratio to the plain integrate of the same run, and
+    the ms of extract_moments (select, sort, covariance and the Jacobi eigen-solver per voxel);
   * with --cpu: the NumPy restatement (tests/voxel_map_restatement.py) on the first --cpu-frames scans, its points/s, and whether the
     GPU's map of the same scans equals it bit for bit."""
 import argparse
@@ -79,6 +83,7 @@ def main(argv=None):
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--batch', type=int, default=64, help='scans per integrate call')
     ap.add_argument('--voxel', type=float, default=0.3)
+    ap.add_argument('--moments', action='store_true', help='also time integrate and extract with the per-voxel second moments')
     ap.add_argument('--cpu', action='store_true', help='also time the NumPy restatement and compare the maps bit for bit')
     ap.add_argument('--cpu-frames', type=int, default=8)
     a = ap.parse_args(argv)
@@ -118,6 +123,29 @@ def main(argv=None):
                       'fraction_of_float_atomic_rate': round(pps * (8 * C + 4) / FLOAT_ATOMIC_BYTES_PER_S, 4),
                       'read_bytes_per_s': round(pps * 4 * C), 'voxels': st['occupied'],
                       'points_per_voxel': round(st['integrated'] / max(st['occupied'], 1), 2), 'stats': st}))
+
+    if a.moments:
+        mmap = ops.VoxelMap(a.voxel, channels=C, capacity=capacity, moments=True)
+
+        def integrate_moments():
+            mmap.reset()
+            for pts, off, X in batches:
+                mmap.integrate((pts, off), X)
+            return mmap
+
+        ms_mreset, _ = timed(mmap.reset, a.reps)
+        ms_mall, _ = timed(integrate_moments, a.reps)
+        ms_m = ms_mall - ms_mreset
+        assert mmap.capacity == capacity and mmap.stats() == st
+        pps_m = total / ms_m * 1e3
+        print(json.dumps({'case': 'integrate with moments', 'ms': round(ms_m, 3), 'ms_reset_excluded': round(ms_mreset, 3),
+                          'points_per_s': round(pps_m), 'over_plain_integrate': round(pps_m / pps, 3),
+                          'atomic_bytes_per_s': round(pps_m * (8 * C + 4 + 72)),
+                          'fraction_of_float_atomic_rate': round(pps_m * (8 * C + 4 + 72) / FLOAT_ATOMIC_BYTES_PER_S, 4)}))
+        ms_xm, out_m = timed(lambda: mmap.extract_moments(), a.reps)
+        print(json.dumps({'case': 'extract_moments', 'capacity': capacity, 'voxels': int(out_m[0].shape[0]), 'ms': round(ms_xm, 3),
+                          'voxels_per_s': round(out_m[0].shape[0] / ms_xm * 1e3), 'sharpness': mmap.sharpness()}))
+        del mmap, out_m
 
     host = cloud[:min(a.batch, a.frames) * a.points].cpu().numpy()
     pinned = torch.from_numpy(host).pin_memory()
