@@ -45,12 +45,6 @@ struct TopkArgs {
   int seg0_blocks, row1, nq1, nk1, keep1;
 };
 
-// fp32 -> uint32 whose unsigned order is the order of the floats (finite inputs; -0 and +0 map to the same key)
-__device__ __forceinline__ uint32_t order_key(float f) {
-  const uint32_t u = __float_as_uint(f + 0.0f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __device__ __forceinline__ void attention_topk_body(const dim3 blockIdx, const dim3 gridDim, TopkArgs a_in) {
   (void)gridDim;
   TopkArgs a = a_in;
@@ -146,7 +140,7 @@ __device__ __forceinline__ void attention_topk_body(const dim3 blockIdx, const d
       for (int k0 = wave * 16; k0 < nk; k0 += 64) {
         const f32x4 s = scores(k0);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) c += (k0 + 4 * g + r < nk && (order_key(s[r]) & hi) == cand) ? 1 : 0;
+        for (int r = 0; r < 4; ++r) c += (k0 + 4 * g + r < nk && (order_key(s[r] + 0.0f) & hi) == cand) ? 1 : 0;
       }
       c = total(c);
       if (c >= need) T = cand;
@@ -157,7 +151,7 @@ __device__ __forceinline__ void attention_topk_body(const dim3 blockIdx, const d
     for (int k0 = wave * 16; k0 < nk; k0 += 64) {
       const f32x4 s = scores(k0);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) c += (k0 + 4 * g + r < nk && order_key(s[r]) == T) ? 1 : 0;
+      for (int r = 0; r < 4; ++r) c += (k0 + 4 * g + r < nk && order_key(s[r] + 0.0f) == T) ? 1 : 0;
     }
     const int n_eq = total(c);
     if (__syncthreads_or(need < n_eq)) {  // some query cuts its ties: find the need-th of them in index order
@@ -172,7 +166,7 @@ __device__ __forceinline__ void attention_topk_body(const dim3 blockIdx, const d
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int j = k0 + 4 * g + r;
-            cc += (j < nk && j >= lim && j < cand && order_key(s[r]) == T) ? 1 : 0;
+            cc += (j < nk && j >= lim && j < cand && order_key(s[r] + 0.0f) == T) ? 1 : 0;
           }
         }
         cc = total(cc);
@@ -200,7 +194,7 @@ __device__ __forceinline__ void attention_topk_body(const dim3 blockIdx, const d
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int j = k0 + 4 * g + r;
-      const uint32_t key = order_key(s[r]);
+      const uint32_t key = order_key(s[r] + 0.0f);
       const bool kept = j < nk && (key > T || (key == T && j <= J));
       p[r] = kept ? expf(s[r] - mx) : 0.f;
       lsum += p[r];

@@ -2,18 +2,16 @@
 // (geotransformer/utils/registration.py:191-216, a cKDTree ball query / nearest neighbour between two full clouds) as one
 // fixed-radius ball query on the GPU.
 //
-// Definition, to the bit (tests/pair_overlap_restatement.py is the float64 numpy restatement):
-//   points are fp32 read as double; the transform is a row-major float64 4x4 (null: src as it is);
-//   x' = ((R00*x + R01*y) + R02*z) + t0 per row;  d = ref - src' per axis;  d2 = ((dx*dx) + (dy*dy)) + (dz*dz), never
-//   contracted;  r2 = r*r in double (NOT icp.hip's float-rounded r2);
+// Definition, to the bit (x', d2 and ties: cell_index.h; tests/pair_overlap_restatement.py is the float64 numpy restatement):
+//   the transform moves src (null: src as it is);  d = ref - src' per axis;  r2 = r*r in double (NOT icp.hip's float-rounded r2);
 //   (i, j) is a correspondence iff d2 <= r2 (cKDTree's ball is closed); the list is int64 [C, 2] in ascending (i, j) -- cKDTree
 //   leaves the order inside a row open, this library defines it as ascending j;
 //   a row overlaps iff the smallest d2 of its correspondences satisfies sqrt(d2) < r (compute_overlap's comparison is strict;
 //   a row without a correspondence has no point of the other cloud within r, so it does not overlap).
 //
 // Structure:
-//   index of the MOVED src cloud, once per call (cell_index.h, shared with icp.hip): cell edge h = r (1 + 1e-6) >= r, records
-//   {x', y', z', j} in key order.  A ref row finds its candidates in the 3 x 3 cell columns around its own cell, by exact key.
+//   index of the MOVED src cloud, once per call (cell_index.h): cell edge h = r (1 + 1e-6) >= r.  A ref row finds its
+//   candidates in the 3 x 3 cell columns around its own cell, by exact key.
 //   pass 1 (ball_count_kernel), one wavefront per ref row: lanes 0..8 bisect one column each, then the wave walks the nine
 //   candidate ranges 64 records at a time -> count, smallest d2 (-1 if none), and per src row found a hit byte (d2 <= r2) and a
 //   near byte (sqrt(d2) < r), plain stores of 1 (all writers write the same value).
@@ -42,15 +40,6 @@ using namespace rdm;
 constexpr int kBlock = kCellBlock;
 constexpr int kRowsPerBlock = kBlock / kWave;  // ref rows (wavefronts) per workgroup
 
-struct Mat16 {
-  double v[16];
-};
-
-struct Rec {  // a moved src point and its row, in key order
-  double x, y, z;
-  long long j;
-};
-
 struct BallState {
   double r, r2;
   int stop;     // 2: a bad src cloud (cell_index.h), set by the setup kernel before anything reads the index
@@ -61,23 +50,6 @@ struct ToLong {
   __host__ __device__ long long operator()(int v) const { return static_cast<long long>(v); }
 };
 using CountIter = rocprim::transform_iterator<const int*, ToLong, long long>;
-
-// moved[j] = T . src[j] (or src[j] as it is), float64
-__global__ __launch_bounds__(kBlock) void ball_move_kernel(const float* __restrict__ src, int m, long long ld, Mat16 T, int apply,
-                                                           double* __restrict__ moved) {
-  const int j = blockIdx.x * kBlock + threadIdx.x;
-  if (j >= m) return;
-  double x = src[j * ld], y = src[j * ld + 1], z = src[j * ld + 2];
-  if (apply) {
-    const double a = ((T.v[0] * x + T.v[1] * y) + T.v[2] * z) + T.v[3];
-    const double b = ((T.v[4] * x + T.v[5] * y) + T.v[6] * z) + T.v[7];
-    const double c = ((T.v[8] * x + T.v[9] * y) + T.v[10] * z) + T.v[11];
-    x = a; y = b; z = c;
-  }
-  moved[3ll * j] = x;
-  moved[3ll * j + 1] = y;
-  moved[3ll * j + 2] = z;
-}
 
 // One thread: the cell box of the moved cloud, the state of a new call, zeroed totals.
 __global__ void ball_setup_kernel(const double* __restrict__ slab, int rows, int m, double h, double r, Grid* __restrict__ grid,
@@ -91,14 +63,6 @@ __global__ void ball_setup_kernel(const double* __restrict__ slab, int rows, int
   for (int k = 0; k < 4; ++k) totals[k] = 0;
 }
 
-__global__ __launch_bounds__(kBlock) void ball_records_kernel(const double* __restrict__ moved, int m, const int* __restrict__ order,
-                                                              Rec* __restrict__ recs) {
-  const int p = blockIdx.x * kBlock + threadIdx.x;
-  if (p >= m) return;
-  const int j = order[p];
-  recs[p] = Rec{moved[3ll * j], moved[3ll * j + 1], moved[3ll * j + 2], static_cast<long long>(j)};
-}
-
 // The candidate ranges of one ref row, wave-wide: lane c < 9 holds [begin, end) of cell column c (x-major, so ascending keys);
 // every other lane, and a column outside the box, an empty range.  Returns false when the row is not finite.
 __device__ __forceinline__ bool column_ranges(double qx, double qy, double qz, const unsigned long long* __restrict__ keys, int m,
@@ -107,24 +71,16 @@ __device__ __forceinline__ bool column_ranges(double qx, double qy, double qz, c
   if (!(isfinite(qx) && isfinite(qy) && isfinite(qz))) return false;
   if (m == 0 || g.dims[0] == 0 || lane >= 9) return true;
   const double q[3] = {qx, qy, qz};
-  long long c[3];
-  for (int a = 0; a < 3; ++a) {
-    const double ca = cell_of(q[a], g.h) - static_cast<double>(g.lo[a]);  // (exact while the row is within 2^52 cells; beyond: no neighbour)
-    if (!(ca >= -1.0 && ca <= static_cast<double>(g.dims[a]))) return true;  // no occupied cell next to the row's
-    c[a] = static_cast<long long>(ca);
-  }
-  const long long z0 = c[2] - 1 < 0 ? 0 : c[2] - 1, z1 = c[2] + 1 >= g.dims[2] ? g.dims[2] - 1 : c[2] + 1;
+  long long c[3], z0, z1;
+  if (!query_cell(q, g, 1, c)) return true;  // no occupied cell next to the row's
+  const bool some = ring_heights(g, c[2], 1, &z0, &z1);
   const long long x = c[0] - 1 + lane / 3, y = c[1] - 1 + lane % 3;
-  if (z0 > z1 || x < 0 || x >= g.dims[0] || y < 0 || y >= g.dims[1]) return true;
-  const long long col = (x * g.dims[1] + y) * g.dims[2];
-  *begin = lower_bound(keys, m, static_cast<unsigned long long>(col + z0));
-  *end = lower_bound(keys, m, static_cast<unsigned long long>(col + z1 + 1));
+  if (!some || x < 0 || x >= g.dims[0] || y < 0 || y >= g.dims[1]) return true;
+  unsigned long long klo, khi;
+  column_keys(g, x, y, z0, z1, &klo, &khi);
+  *begin = lower_bound(keys, m, klo);
+  *end = lower_bound(keys, m, khi + 1);
   return true;
-}
-
-__device__ __forceinline__ double sq_dist(double qx, double qy, double qz, const Rec& s) {
-  const double dx = qx - s.x, dy = qy - s.y, dz = qz - s.z;
-  return ((dx * dx) + (dy * dy)) + (dz * dz);
 }
 
 // Pass 1: one wavefront per ref row.
@@ -152,7 +108,7 @@ __global__ __launch_bounds__(kBlock) void ball_count_kernel(const float* __restr
         bool hit = false;
         if (p < e) {
           const Rec s = recs[p];
-          const double d2 = sq_dist(qx, qy, qz, s);
+          const double d2 = sq_dist(qx, qy, qz, s.x, s.y, s.z);
           hit = d2 <= r2;
           if (hit) {
             best = fmin(best, d2);
@@ -227,7 +183,7 @@ __global__ __launch_bounds__(kWave) void ball_fill_kernel(const float* __restric
         long long j = 0;
         if (p < e) {
           const Rec s = recs[p];
-          hit = sq_dist(qx, qy, qz, s) <= r2;
+          hit = sq_dist(qx, qy, qz, s.x, s.y, s.z) <= r2;
           j = s.j;
         }
         const unsigned long long bal = __ballot(hit);
@@ -319,25 +275,20 @@ extern "C" int rdm_ball_count(const float* ref, int64_t n_ref, int64_t ld_ref, c
     set_error("rdm_ball_count: workspace too small (%zu < %zu bytes)", ws_bytes, ar.off);
     return RDM_ERR_WORKSPACE;
   }
-  Mat16 T = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
-  if (transform_host)
-    for (int q = 0; q < 16; ++q) T.v[q] = transform_host[q];
   const int n = static_cast<int>(n_ref), m = static_cast<int>(n_src);
   const double h = radius * (1.0 + 1e-6);
   if (!src_hit) src_hit = w.src_hit;
   if (!ref_min_d2) ref_min_d2 = w.min_d2;
   // index of the moved src cloud
   if (m > 0)
-    hipLaunchKernelGGL(ball_move_kernel, dim3(static_cast<unsigned>((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, src, m,
-                       static_cast<long long>(ld_src), T, transform_host ? 1 : 0, w.moved);
+    hipLaunchKernelGGL(cell_move_kernel<float>, dim3(static_cast<unsigned>((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, src, m,
+                       static_cast<long long>(ld_src), mat_of(transform_host), transform_host ? 1 : 0, w.moved);
   const int tb = point_blocks(m);
   hipLaunchKernelGGL(cell_bbox_kernel<double>, dim3(tb), dim3(kBlock), 0, st, w.moved, m, 3ll, h, w.slab);
   hipLaunchKernelGGL(ball_setup_kernel, dim3(1), dim3(64), 0, st, w.slab, tb, m, h, radius, w.ci.grid, w.st, w.totals);
   if (m > 0) {
-    const int rc = sort_cells(w.moved, m, 3, &w.st->stop, w.ci, st);
+    const int rc = index_cells(w.moved, m, &w.st->stop, w.ci, w.recs, st);
     if (rc != RDM_OK) return rc;
-    hipLaunchKernelGGL(ball_records_kernel, dim3(static_cast<unsigned>((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, w.moved, m,
-                       w.ci.order, w.recs);
     fill_words(reinterpret_cast<uint32_t*>(src_hit), (static_cast<int64_t>(m) + 3) / 4, 0u, st);  // (callers' buffers hold align_up(m, 4) bytes)
     fill_words(reinterpret_cast<uint32_t*>(w.src_near), (static_cast<int64_t>(m) + 3) / 4, 0u, st);
   }

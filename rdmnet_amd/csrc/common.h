@@ -193,6 +193,34 @@ __device__ __forceinline__ int wave_sum_i(int v) {
   return v;
 }
 
+// Sums K doubles over a block of THREADS threads in a fixed order: lanes by butterfly, lane 0 of each wavefront stores, one
+// barrier, then thread k < K starts from wavefront 0's partial and adds wavefronts 1, 2, ... in order.  Returns the total of
+// value k to thread k < K (0 to the others).  The barrier also orders what the caller stored to LDS before the call.
+template <int K, int THREADS>
+__device__ __forceinline__ double block_sum(double (&v)[K], int k) {
+  __shared__ double part[K][THREADS / kWave];
+#pragma unroll
+  for (int j = 0; j < K; ++j) v[j] = wave_sum(v[j]);
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int j = 0; j < K; ++j) part[j][threadIdx.x >> 6] = v[j];
+  __syncthreads();
+  double s = 0.0;
+  if (k < K) {
+    s = part[k][0];
+    for (int w = 1; w < THREADS / kWave; ++w) s += part[k][w];
+  }
+  return s;
+}
+
+// fp32 -> uint32 whose unsigned order is the order of the floats (negative values included; -0 sorts below +0, pass f + 0.0f
+// to merge them; never 0 for a non-NaN value), and its inverse.
+__device__ __forceinline__ uint32_t order_key(float f) {
+  const uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_value(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
 // Small device-side fills and copies.  The runtime's hipMemsetAsync / hipMemcpyAsync go through blit kernels
 // with extra barrier packets and host-side bookkeeping; with several pairs in flight per GPU those cost
 // noticeably more than a plain kernel launch, so the hot path uses these instead.

@@ -35,12 +35,6 @@ __device__ __forceinline__ int selected_rows(const int64_t* corr_offsets, int p,
   return (limit > 0 && c > limit) ? limit : c;
 }
 
-// order-preserving uint32 key of a float (lgr.hip: lgr_key)
-__device__ __forceinline__ unsigned score_key(float v) {
-  const unsigned u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // ------------------------------------------------------------------------------------------------------------ select
 // eval.py:121-125 per pair segment.  C > L: the first L rows in the order (score descending, row ascending), written in row
 // order to the head of the pair's segment of sel_* (same offsets as the inputs).  An 8-bit radix select on the keys finds the
@@ -74,7 +68,7 @@ __global__ __launch_bounds__(kSelectThreads) void eval_select_kernel(const int64
         const int i = i0 + lane;
         unsigned digit = 256u;  // no candidate
         if (i < C) {
-          const unsigned key = score_key(sc[i]);
+          const unsigned key = order_key(sc[i]);
           if ((key & above) == prefix) digit = (key >> shift) & 255u;
         }
         // lanes with the same digit: the lowest of them adds the group's size to the wave's own row
@@ -127,7 +121,7 @@ __global__ __launch_bounds__(kSelectThreads) void eval_select_kernel(const int64
     const int i = i0 + tid;
     bool g = false, e = false;
     if (i < C) {
-      const unsigned key = score_key(sc[i]);
+      const unsigned key = order_key(sc[i]);
       g = all || key > prefix;
       e = !all && key == prefix;
     }

@@ -9,18 +9,13 @@
 //   |d rmse| < relative_rmse.
 //   Evaluate: for every pcd point the nearest target point with d2 < r2 -> fitness = n_corr / n_source,
 //   inlier_rmse = sqrt(err2 / n_corr) (both 0 without correspondences).
-// Neighbour step, defined to the bit (a float64 numpy restatement gives the same idx and d2):
-//   targets are float32 read as double, d = q - t per axis, d2 = ((dx*dx) + (dy*dy)) + (dz*dz) (never contracted),
-//   accept iff d2 < r2 with r2 = (double)(float)(r*r) (Open3D's KDTreeFlann hands FLANN a float squared radius),
-//   ties in d2 keep the lowest target index.
-// Transforms are applied as x' = ((R00*x + R01*y) + R02*z) + t0 per row, uncontracted.
+// Neighbour step, defined to the bit in cell_index.h (tests/icp_restatement.py gives the same idx and d2): accept iff
+//   d2 < r2 with r2 = (double)(float)(r*r) (Open3D's KDTreeFlann hands FLANN a float squared radius).
 //
 // Structure:
-//   target index, once per call: cell = floor(t / h) per axis (h = sqrt(r2) (1 + 1e-6) >= the search radius) ->
-//   cell box (block slabs, one-block finalize) -> 64-bit key relative to the box -> radix sort of (key, index) ->
-//   float4 records in key order.  A query looks its 3 x 3 cell columns up by exact key (binary search of the lowest
-//   key of a column, then a forward scan): no clamping, so a query outside the box finds exactly the targets within
-//   r of it.  Every occupied cell holds its own points only, whatever the extent (the box only has to fit 2^62 cells).
+//   target index, once per call (cell_index.h): cell edge h = sqrt(r2) (1 + 1e-6) >= the search radius; the records are the
+//   raw fp32 targets as float4 {x, y, z, bits of j} in key order.  A query looks its 3 x 3 cell columns up by exact key
+//   (binary search of the lowest key of a column, then a forward scan).
 //   per iteration, with no host synchronisation: search (applies the pending update to its pcd point first; float64
 //   partials of count, err2 and the two sums to block slabs) -> one-block means -> demeaned covariance (second pass:
 //   60-80 m coordinates make the one-pass formula lose digits) -> one-block finalize (Kabsch, composition,
@@ -34,7 +29,7 @@
 
 #pragma clang fp contract(off)
 
-#include "cell_index.h"  // the target index: cell box, keys, sort, lower_bound (shared with ball_query.hip)
+#include "cell_index.h"
 
 namespace {
 using namespace rdm;
@@ -43,10 +38,6 @@ constexpr int kBlock = kCellBlock;
 constexpr int kMaxBlocks = kCellMaxBlocks;    // slab rows: the point kernels stride over at most this many blocks
 constexpr int kChunk = 32;                    // iterations enqueued between two reads of `done`
 constexpr int kRecord = 15;                   // history record: fitness, rmse, n_corr, update[12]
-
-struct Mat16 {
-  double v[16];
-};
 
 struct IcpState {
   double T[16];   // transformation so far (row-major 4x4)
@@ -58,24 +49,6 @@ struct IcpState {
   int updates;
 };
 
-// Sums K doubles over the block (256 threads) in a fixed order; thread k < K returns the total of value k.
-template <int K>
-__device__ __forceinline__ double block_sum(double (&v)[K], int k) {
-  __shared__ double part[kBlock / kWave][K];
-#pragma unroll
-  for (int j = 0; j < K; ++j) v[j] = wave_sum(v[j]);
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int j = 0; j < K; ++j) part[threadIdx.x >> 6][j] = v[j];
-  __syncthreads();
-  double s = 0.0;
-  if (k < K) {
-    s = part[0][k];
-    for (int w = 1; w < kBlock / kWave; ++w) s += part[w][k];
-  }
-  return s;
-}
-
 // Row-wise sum over `rows` slab rows of K doubles (one block): thread t takes rows t, t + 256, ... in order.
 template <int K>
 __device__ __forceinline__ double slab_sum(const double* __restrict__ slab, int rows, int k) {
@@ -85,14 +58,7 @@ __device__ __forceinline__ double slab_sum(const double* __restrict__ slab, int 
   for (int r = threadIdx.x; r < rows; r += kBlock)
 #pragma unroll
     for (int j = 0; j < K; ++j) v[j] += slab[static_cast<long long>(r) * K + j];
-  return block_sum<K>(v, k);
-}
-
-__device__ __forceinline__ void apply_rt(const double* M, double& x, double& y, double& z) {
-  const double a = ((M[0] * x + M[1] * y) + M[2] * z) + M[3];
-  const double b = ((M[4] * x + M[5] * y) + M[6] * z) + M[7];
-  const double c = ((M[8] * x + M[9] * y) + M[10] * z) + M[11];
-  x = a; y = b; z = c;
+  return block_sum<K, kBlock>(v, k);
 }
 
 // ---- target index --------------------------------------------------------------------------------------------------
@@ -132,24 +98,18 @@ __device__ int nearest(double qx, double qy, double qz, const unsigned long long
   if (m == 0 || g.dims[0] == 0 || !(isfinite(qx) && isfinite(qy) && isfinite(qz))) return -1;
   const double q[3] = {qx, qy, qz};
   long long c[3];
-  for (int a = 0; a < 3; ++a) {
-    const double ca = cell_of(q[a], g.h) - static_cast<double>(g.lo[a]);  // exact: both are integers below 2^31
-    if (ca < -1.0 || ca > static_cast<double>(g.dims[a])) return -1;     // no occupied cell next to the query's
-    c[a] = static_cast<long long>(ca);
-  }
-  const long long z0 = c[2] - 1 < 0 ? 0 : c[2] - 1, z1 = c[2] + 1 >= g.dims[2] ? g.dims[2] - 1 : c[2] + 1;
-  if (z0 > z1) return -1;
+  if (!query_cell(q, g, 1, c)) return -1;
+  long long z0, z1;
+  if (!ring_heights(g, c[2], 1, &z0, &z1)) return -1;
   for (long long x = c[0] - 1; x <= c[0] + 1; ++x) {
     if (x < 0 || x >= g.dims[0]) continue;
     for (long long y = c[1] - 1; y <= c[1] + 1; ++y) {
       if (y < 0 || y >= g.dims[1]) continue;
-      const long long col = (x * g.dims[1] + y) * g.dims[2];
-      const unsigned long long khi = static_cast<unsigned long long>(col + z1);
-      for (int p = lower_bound(keys, m, static_cast<unsigned long long>(col + z0)); p < m && keys[p] <= khi; ++p) {
+      unsigned long long klo, khi;
+      column_keys(g, x, y, z0, z1, &klo, &khi);
+      for (int p = lower_bound(keys, m, klo); p < m && keys[p] <= khi; ++p) {
         const float4 r = recs[p];
-        const double dx = qx - static_cast<double>(r.x), dy = qy - static_cast<double>(r.y),
-                     dz = qz - static_cast<double>(r.z);
-        const double d2 = ((dx * dx) + (dy * dy)) + (dz * dz);
+        const double d2 = sq_dist(qx, qy, qz, static_cast<double>(r.x), static_cast<double>(r.y), static_cast<double>(r.z));
         const int j = __float_as_int(r.w);
         if (d2 < r2 && (d2 < bd || (d2 == bd && j < bj))) {
           bd = d2;
@@ -162,22 +122,6 @@ __device__ int nearest(double qx, double qy, double qz, const unsigned long long
   *best = bd;
   *rec = br;
   return bj;
-}
-
-// pcd = init . source (or the source as is), as float64
-__global__ __launch_bounds__(kBlock) void icp_init_kernel(const float* __restrict__ source, int n, long long ld, Mat16 init,
-                                                          int apply, double* __restrict__ pcd) {
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  double x = source[i * ld], y = source[i * ld + 1], z = source[i * ld + 2];
-  if (apply) {
-    const double M[12] = {init.v[0], init.v[1], init.v[2], init.v[3], init.v[4], init.v[5],
-                          init.v[6], init.v[7], init.v[8], init.v[9], init.v[10], init.v[11]};
-    apply_rt(M, x, y, z);
-  }
-  pcd[3ll * i] = x;
-  pcd[3ll * i + 1] = y;
-  pcd[3ll * i + 2] = z;
 }
 
 // One evaluation: (apply the pending update to the pcd point,) search, block partials
@@ -193,7 +137,7 @@ __global__ __launch_bounds__(kBlock) void icp_search_kernel(double* __restrict__
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
     double x = pcd[3ll * i], y = pcd[3ll * i + 1], z = pcd[3ll * i + 2];
     if (apply) {
-      apply_rt(st->U, x, y, z);
+      move_row(st->U, x, y, z);
       pcd[3ll * i] = x;
       pcd[3ll * i + 1] = y;
       pcd[3ll * i + 2] = z;
@@ -214,13 +158,9 @@ __global__ __launch_bounds__(kBlock) void icp_search_kernel(double* __restrict__
       acc[7] += static_cast<double>(r.z);
     }
   }
-  const double s = block_sum<8>(acc, threadIdx.x);
+  const double s = block_sum<8, kBlock>(acc, threadIdx.x);
   if (threadIdx.x < 8) slab[blockIdx.x * 8 + threadIdx.x] = s;
 }
-
-}  // namespace
-
-namespace {
 
 // One block: means of the correspondences from the search slabs.
 __global__ __launch_bounds__(kBlock) void icp_mean_kernel(const double* __restrict__ slab, int rows, IcpState* __restrict__ st) {
@@ -260,7 +200,7 @@ __global__ __launch_bounds__(kBlock) void icp_cov_kernel(const double* __restric
 #pragma unroll
       for (int b = 0; b < 3; ++b) acc[3 * a + b] += p[a] * t[b];
   }
-  const double s = block_sum<9>(acc, threadIdx.x);
+  const double s = block_sum<9, kBlock>(acc, threadIdx.x);
   if (threadIdx.x < 9) slab[blockIdx.x * 9 + threadIdx.x] = s;
 }
 
@@ -365,8 +305,6 @@ int read_done(const IcpState* st_dev, int* done, hipStream_t st) {
   return RDM_OK;
 }
 
-const Mat16 kIdentity = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
-
 }  // namespace
 
 extern "C" size_t rdm_icp_workspace_bytes(int64_t n_source, int64_t n_target) {
@@ -390,13 +328,9 @@ extern "C" int rdm_icp_point_to_point(const float* source, int64_t n_source, int
                   ld_source >= 3 && ld_target >= 3 && relative_fitness >= 0.0 && relative_rmse >= 0.0,
               "rdm_icp_point_to_point: bad arguments");
   RDM_REQUIRE((source || n_source == 0) && (target || n_target == 0), "rdm_icp_point_to_point: null points");
-  Mat16 init = kIdentity;
+  const Mat16 init = mat_of(init_host), eye = mat_of(nullptr);
   bool identity = true;
-  if (init_host)
-    for (int q = 0; q < 16; ++q) {
-      init.v[q] = init_host[q];
-      identity = identity && init.v[q] == kIdentity.v[q];
-    }
+  for (int q = 0; q < 16; ++q) identity = identity && init.v[q] == eye.v[q];
   const double r2 = search_r2(max_correspondence_distance);
   RDM_REQUIRE(r2 > 0.0 && std::isfinite(r2), "rdm_icp_point_to_point: max_correspondence_distance^2 is not a positive float");
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -410,8 +344,8 @@ extern "C" int rdm_icp_point_to_point(const float* source, int64_t n_source, int
   if (rc != RDM_OK) return rc;
   const int n = static_cast<int>(n_source), m = static_cast<int>(n_target), pb = point_blocks(n_source);
   if (n > 0)
-    hipLaunchKernelGGL(icp_init_kernel, dim3(static_cast<unsigned>((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, source, n,
-                       static_cast<long long>(ld_source), init, identity ? 0 : 1, w.pcd);
+    hipLaunchKernelGGL(cell_move_kernel<float>, dim3(static_cast<unsigned>((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, source, n,
+                       static_cast<long long>(ld_source), init, identity ? 0 : 1, w.pcd);  // pcd = init . source (or the source as is)
   int done = 0;
   for (int k = 0; k <= max_iteration && done == 0;) {
     const int end = max_iteration - k < kChunk ? max_iteration + 1 : k + kChunk;
@@ -456,7 +390,7 @@ extern "C" int rdm_icp_correspondences(const double* pcd, int64_t n, const float
     set_error("rdm_icp_correspondences: workspace too small (%zu < %zu bytes)", ws_bytes, ar.off);
     return RDM_ERR_WORKSPACE;
   }
-  int rc = build_index(target, n_target, ld_target, r2, kIdentity, w, st);
+  int rc = build_index(target, n_target, ld_target, r2, mat_of(nullptr), w, st);
   if (rc != RDM_OK) return rc;
   if (n > 0)
     hipLaunchKernelGGL(icp_search_kernel, dim3(point_blocks(n)), dim3(kBlock), 0, st, const_cast<double*>(pcd), static_cast<int>(n),

@@ -156,12 +156,6 @@ __global__ __launch_bounds__(256) void lgr_extract_kernel(const float* log_score
                                                           const unsigned char* src_mask, LgrBuffers w) { lgr_extract_kernel_body(blockIdx, gridDim, log_scores, side, ref_mask, src_mask, w); }
 
 // ------------------------------------------------------------------------------------------ extract, every option
-// order-preserving uint32 key of a float (as attention_topk.hip): the limit's radix select
-__device__ __forceinline__ unsigned lgr_key(float v) {
-  const unsigned u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // The k-th element (1 <= k < n) of a staged line base[0], base[stride], .. in the order (value descending, index ascending)
 // -- torch.topk's set with the lowest index kept among equal values at the boundary: element (v, j) of the line is among the
 // k first iff v > t or (v == t and j <= jt).  One thread per line, k passes, each the first maximum behind the previous pick
@@ -374,7 +368,7 @@ __device__ __forceinline__ void lgr_limit_kernel_body(const dim3 blockIdx, const
       __syncthreads();
       const unsigned above = shift == 24 ? 0u : ~0u << (shift + 8);
       for (int i = tid; i < C; i += kLimitThreads) {
-        const unsigned key = lgr_key(scores[i]);
+        const unsigned key = order_key(scores[i]);
         if ((key & above) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1);
       }
       __syncthreads();
@@ -411,7 +405,7 @@ __device__ __forceinline__ void lgr_limit_kernel_body(const dim3 blockIdx, const
     const int i = i0 + tid;
     bool g = false, e = false;
     if (i < C) {
-      const unsigned key = lgr_key(scores[i]);
+      const unsigned key = order_key(scores[i]);
       g = all || key > prefix;
       e = !all && key == prefix;
     }

@@ -2,9 +2,8 @@
 // query) and what the reference builds on it -- compute_overlap, compute_modified_chamfer_distance, compute_registration_rmse
 // (geotransformer/utils/registration.py:136-197) -- plus the fitness / inlier RMSE of a pose.
 //
-// Definition, to the bit (tests/nearest_restatement.py is the float64 numpy restatement):
-//   q [n_q, >=3] / s [n_s, >=3] are fp32 read as double; each cloud has an optional row-major float64 4x4 transform;
-//   x' = ((R00*x + R01*y) + R02*z) + t0 per row;  d = q' - s' per axis;  d2 = ((dx*dx) + (dy*dy)) + (dz*dz), never contracted;
+// Definition, to the bit (x', d2 and ties: cell_index.h; tests/nearest_restatement.py is the float64 numpy restatement):
+//   q [n_q, >=3] / s [n_s, >=3]; each cloud has an optional transform;  d = q' - s' per axis;
 //   d2[i] = the smallest d2 over ALL support rows, idx[i] = the LOWEST support row that attains it (cKDTree leaves equal
 //   distances open; this library defines the tie);  the distance is sqrt(d2) in double;  n_s = 0 gives d2 = +inf, idx = n_s.
 //
@@ -12,7 +11,7 @@
 //   move: q' and s' as float64 [n, 3] (the identity copies); per-block slabs of the coordinate box and a non-finite flag.
 //   setup (one thread): the cell edge h -- the caller's, or (cell <= 0) the edge of a cube that holds about 8 support points at
 //   uniform density over the box, raised so that the box stays under cell_index.h's limits -- and the cell box of s'.
-//   index: cell_index.h over s' (keys, radix sort), records {x', y', z', j} in key order.
+//   index: cell_index.h over s'.
 //   phase 1 (nn_shell_kernel), one wavefront per query row: the 3 x 3 cell columns around the query's cell (lanes bisect one
 //   column each, the wave walks the ranges 64 records at a time), then the 5 x 5 columns; smallest (d2, j) by wave butterfly.
 //   The row is SETTLED when d2 < reach^2, reach = the distance from the query to the nearest face of the cube of cells searched
@@ -57,38 +56,12 @@ constexpr int kTile = 1024;                    // phase 2: support rows per LDS 
 constexpr int kSweepMaxBlocks = 8192;
 constexpr double kMargin = 3.5527136788005009e-15;  // 2^-48
 
-struct Mat16 {
-  double v[16];
-};
-
-struct Rec {  // a moved support point and its row, in key order
-  double x, y, z;
-  long long j;
-};
-
 struct NnState {
   int stop;         // 2: a point that is not finite, or a support point beyond the cell limits
   unsigned n_list;  // unsettled rows (written by the compaction)
   unsigned n_corr;  // rdm_information_matrix: rows under the radius (written by its compaction)
   double radius;
 };
-
-// moved[j] = T . pts[j] (or pts[j] as it is), float64
-__global__ __launch_bounds__(kBlock) void nn_move_kernel(const float* __restrict__ pts, int n, long long ld, Mat16 T, int apply,
-                                                         double* __restrict__ moved) {
-  const long long j = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
-  if (j >= n) return;
-  double x = pts[j * ld], y = pts[j * ld + 1], z = pts[j * ld + 2];
-  if (apply) {
-    const double a = ((T.v[0] * x + T.v[1] * y) + T.v[2] * z) + T.v[3];
-    const double b = ((T.v[4] * x + T.v[5] * y) + T.v[6] * z) + T.v[7];
-    const double c = ((T.v[8] * x + T.v[9] * y) + T.v[10] * z) + T.v[11];
-    x = a; y = b; z = c;
-  }
-  moved[3 * j] = x;
-  moved[3 * j + 1] = y;
-  moved[3 * j + 2] = z;
-}
 
 // Per block: lowest and highest coordinate per axis and a bad flag (a non-finite coordinate) -> slab[block][8].
 __global__ __launch_bounds__(kBlock) void nn_box_kernel(const double* __restrict__ moved, int n, double* __restrict__ slab) {
@@ -101,19 +74,7 @@ __global__ __launch_bounds__(kBlock) void nn_box_kernel(const double* __restrict
       hi[a] = fmax(hi[a], v);
     }
   }
-  __shared__ double red[7][kBlock];
-  for (int a = 0; a < 3; ++a) {
-    red[a][threadIdx.x] = lo[a];
-    red[3 + a][threadIdx.x] = hi[a];
-  }
-  red[6][threadIdx.x] = bad;
-  __syncthreads();
-  if (threadIdx.x < 7) {
-    const int k = threadIdx.x;
-    double v = red[k][0];
-    for (int t = 1; t < kBlock; ++t) v = k < 3 ? fmin(v, red[k][t]) : fmax(v, red[k][t]);
-    slab[blockIdx.x * 8 + k] = v;
-  }
+  block_box(lo, hi, bad, slab);
 }
 
 // One thread: the status of a new call, the cell edge and the cell box of the moved support cloud.
@@ -169,19 +130,6 @@ __global__ void nn_setup_kernel(const double* __restrict__ slab_s, int rows_s, i
   st->radius = radius;
 }
 
-__global__ __launch_bounds__(kBlock) void nn_records_kernel(const double* __restrict__ moved, int m, const int* __restrict__ order,
-                                                            const NnState* __restrict__ st, Rec* __restrict__ recs) {
-  const long long p = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
-  if (p >= m || st->stop != 0) return;
-  const long long j = order[p];
-  recs[p] = Rec{moved[3 * j], moved[3 * j + 1], moved[3 * j + 2], j};
-}
-
-__device__ __forceinline__ double sq_dist(double qx, double qy, double qz, double sx, double sy, double sz) {
-  const double dx = qx - sx, dy = qy - sy, dz = qz - sz;
-  return ((dx * dx) + (dy * dy)) + (dz * dz);
-}
-
 // the smaller of two candidates by (d2, row)
 __device__ __forceinline__ void take(double& bd, int& bi, double d, int i) {
   if (d < bd || (d == bd && i < bi)) {
@@ -205,22 +153,19 @@ __global__ __launch_bounds__(kBlock) void nn_shell_kernel(const double* __restri
     const Grid g = *grid;
     const double q[3] = {qm[3 * i], qm[3 * i + 1], qm[3 * i + 2]};
     long long c[3] = {0, 0, 0};
-    bool inside = true;
-    for (int a = 0; a < 3; ++a) {
-      const double ca = cell_of(q[a], g.h) - static_cast<double>(g.lo[a]);
-      if (ca >= 0.0 && ca < static_cast<double>(g.dims[a])) c[a] = static_cast<long long>(ca);
-      else inside = false;
-    }
+    const bool inside = query_cell(q, g, 0, c);
     for (int rho = 1; rho <= kRings && inside && !settled; ++rho) {  // (wave-uniform)
       const int w = 2 * rho + 1;
       int begin = 0, end = 0;
       if (lane < w * w) {  // lane -> one cell column (x-major, so ascending keys)
         const long long x = c[0] - rho + lane / w, y = c[1] - rho + lane % w;
-        const long long z0 = c[2] - rho < 0 ? 0 : c[2] - rho, z1 = c[2] + rho >= g.dims[2] ? g.dims[2] - 1 : c[2] + rho;
+        long long z0, z1;
+        ring_heights(g, c[2], rho, &z0, &z1);  // (never empty: the query's cell is inside)
         if (x >= 0 && x < g.dims[0] && y >= 0 && y < g.dims[1]) {
-          const long long col = (x * g.dims[1] + y) * g.dims[2];
-          begin = lower_bound(keys, m, static_cast<unsigned long long>(col + z0));
-          end = lower_bound(keys, m, static_cast<unsigned long long>(col + z1 + 1));
+          unsigned long long klo, khi;
+          column_keys(g, x, y, z0, z1, &klo, &khi);
+          begin = lower_bound(keys, m, klo);
+          end = lower_bound(keys, m, khi + 1);
         }
       }
       for (int cc = 0; cc < w * w; ++cc) {
@@ -302,24 +247,11 @@ __global__ __launch_bounds__(kBlock) void nn_sweep_kernel(const double* __restri
   }
 }
 
-// Block sums of up to three float64 terms in a fixed order -> slab[block][4]: per thread in row order, lanes by butterfly,
-// wavefronts in order.
+// Block sums of three float64 terms in a fixed order (common.h: block_sum) -> slab[block][4]
 __device__ __forceinline__ void block_sums(double a, double b, double c, double* __restrict__ slab) {
-  __shared__ double red[3][kRowsPerBlock];
-  a = wave_sum(a);
-  b = wave_sum(b);
-  c = wave_sum(c);
-  if (lane_id() == 0) {
-    red[0][threadIdx.x >> 6] = a;
-    red[1][threadIdx.x >> 6] = b;
-    red[2][threadIdx.x >> 6] = c;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double v = red[threadIdx.x][0];
-    for (int w = 1; w < kRowsPerBlock; ++w) v += red[threadIdx.x][w];
-    slab[blockIdx.x * 4 + threadIdx.x] = v;
-  }
+  double v[3] = {a, b, c};
+  const double s = block_sum<3, kBlock>(v, threadIdx.x);
+  if (threadIdx.x < 3) slab[blockIdx.x * 4 + threadIdx.x] = s;
 }
 
 __global__ __launch_bounds__(kBlock) void nn_sum_kernel(const double* __restrict__ d2, int n, const NnState* __restrict__ st,
@@ -357,11 +289,9 @@ __global__ __launch_bounds__(kBlock) void realign_kernel(const float* __restrict
   double sum = 0.0, bad = 0.0;
   for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += static_cast<long long>(gridDim.x) * kBlock) {
     const double x = pts[i * ld], y = pts[i * ld + 1], z = pts[i * ld + 2];
-    double g[3], e[3];
-    for (int a = 0; a < 3; ++a) {
-      g[a] = ((G.v[4 * a] * x + G.v[4 * a + 1] * y) + G.v[4 * a + 2] * z) + G.v[4 * a + 3];
-      e[a] = ((E.v[4 * a] * x + E.v[4 * a + 1] * y) + E.v[4 * a + 2] * z) + E.v[4 * a + 3];
-    }
+    double g[3] = {x, y, z}, e[3] = {x, y, z};
+    move_row(G.v, g[0], g[1], g[2]);
+    move_row(E.v, e[0], e[1], e[2]);
     const double d = sqrt(sq_dist(g[0], g[1], g[2], e[0], e[1], e[2]));
     if (!isfinite(d)) bad = 1.0;  // (a non-finite point or transform)
     else sum += d;
@@ -412,19 +342,12 @@ __global__ __launch_bounds__(kBlock) void info_sum_kernel(const double* __restri
       acc[9] += v;
     }
   }
-  __shared__ double red[kInfoSums][kRowsPerBlock];
   __shared__ int red_c[kRowsPerBlock];
-  for (int k = 0; k < kInfoSums; ++k) acc[k] = wave_sum(acc[k]);
   c = wave_sum_i(c);
-  if (lane_id() == 0) {
-    for (int k = 0; k < kInfoSums; ++k) red[k][threadIdx.x >> 6] = acc[k];
-    red_c[threadIdx.x >> 6] = c;
-  }
-  __syncthreads();
+  if (lane_id() == 0) red_c[threadIdx.x >> 6] = c;
+  const double sum = block_sum<kInfoSums, kBlock>(acc, threadIdx.x);  // (synchronises)
   if (threadIdx.x < kInfoSums) {
-    double v = red[threadIdx.x][0];
-    for (int w = 1; w < kRowsPerBlock; ++w) v += red[threadIdx.x][w];
-    slab[blockIdx.x * kInfoSums + threadIdx.x] = v;
+    slab[blockIdx.x * kInfoSums + threadIdx.x] = sum;
   } else if (threadIdx.x == kInfoSums) {
     long long v = 0;
     for (int w = 0; w < kRowsPerBlock; ++w) v += red_c[w];
@@ -521,13 +444,6 @@ bool sizes_ok(int64_t n, int64_t m, int64_t ld_q, int64_t ld_s) {
   return n >= 0 && n < (1ll << 31) - 64 && m >= 0 && m < (1ll << 31) - 64 && ld_q >= 3 && ld_s >= 3;
 }
 
-Mat16 mat_of(const double* host) {
-  Mat16 T = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
-  if (host)
-    for (int k = 0; k < 16; ++k) T.v[k] = host[k];
-  return T;
-}
-
 unsigned row_blocks(int64_t n) { return static_cast<unsigned>((n + kBlock - 1) / kBlock); }
 
 }  // namespace
@@ -546,10 +462,10 @@ namespace {
 int search(const float* q, int n, int64_t ld_q, const float* s, int m, int64_t ld_s, const double* q_transform_host,
            const double* s_transform_host, double cell, double radius, const Work& w, int* out_idx, double* out_d2, hipStream_t st) {
   if (n > 0)
-    hipLaunchKernelGGL(nn_move_kernel, dim3(row_blocks(n)), dim3(kBlock), 0, st, q, n, static_cast<long long>(ld_q),
+    hipLaunchKernelGGL(cell_move_kernel<float>, dim3(row_blocks(n)), dim3(kBlock), 0, st, q, n, static_cast<long long>(ld_q),
                        mat_of(q_transform_host), q_transform_host ? 1 : 0, w.qm);
   if (m > 0)
-    hipLaunchKernelGGL(nn_move_kernel, dim3(row_blocks(m)), dim3(kBlock), 0, st, s, m, static_cast<long long>(ld_s),
+    hipLaunchKernelGGL(cell_move_kernel<float>, dim3(row_blocks(m)), dim3(kBlock), 0, st, s, m, static_cast<long long>(ld_s),
                        mat_of(s_transform_host), s_transform_host ? 1 : 0, w.sm);
   const int qb = point_blocks(n), sb = point_blocks(m);
   hipLaunchKernelGGL(nn_box_kernel, dim3(qb), dim3(kBlock), 0, st, w.qm, n, w.slab_q);
@@ -557,9 +473,8 @@ int search(const float* q, int n, int64_t ld_q, const float* s, int m, int64_t l
   hipLaunchKernelGGL(nn_setup_kernel, dim3(1), dim3(64), 0, st, w.slab_s, sb, m, w.slab_q, qb, cell, radius, w.ci.grid, w.st);
   if (m > 0) {
     CellIndex ci = w.ci;
-    const int rc = sort_cells(w.sm, m, 3, &w.st->stop, ci, st);
+    const int rc = index_cells(w.sm, m, &w.st->stop, ci, w.recs, st);
     if (rc != RDM_OK) return rc;
-    hipLaunchKernelGGL(nn_records_kernel, dim3(row_blocks(m)), dim3(kBlock), 0, st, w.sm, m, w.ci.order, w.st, w.recs);
   }
   if (n > 0) {
     hipLaunchKernelGGL(nn_shell_kernel, dim3(static_cast<unsigned>((static_cast<int64_t>(n) + kRowsPerBlock - 1) / kRowsPerBlock)),

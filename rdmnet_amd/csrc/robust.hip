@@ -382,22 +382,6 @@ __device__ __forceinline__ double weight_of(const RobustState& s, double n2, con
   return sqrt(((n2 * s.muw) * (s.muw + 1.0)) / r2) - s.muw;
 }
 
-template <int N>
-__device__ __forceinline__ void block_slab(double (&v)[N], double* __restrict__ slab_row) {
-  __shared__ double part[kBlock / kWave][N];
-#pragma unroll
-  for (int j = 0; j < N; ++j) v[j] = wave_sum(v[j]);
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int j = 0; j < N; ++j) part[threadIdx.x >> 6][j] = v[j];
-  __syncthreads();
-  if (threadIdx.x < N) {
-    double s = part[0][threadIdx.x];
-    for (int w = 1; w < kBlock / kWave; ++w) s += part[w][threadIdx.x];
-    slab_row[threadIdx.x] = s;
-  }
-}
-
 // H[a][b] = sum w a_a b_b over the pairs: block x takes p = x, x + gridDim, ..., its threads q = p + 1 + t, ... -> slab[block][9]
 __global__ __launch_bounds__(kBlock) void gnc_sum_kernel(const float* __restrict__ src, const float* __restrict__ ref,
                                                          const int32_t* __restrict__ sel, double n2,
@@ -416,7 +400,8 @@ __global__ __launch_bounds__(kBlock) void gnc_sum_kernel(const float* __restrict
         for (int b = 0; b < 3; ++b) acc[3 * a + b] += (w * m.a[a]) * m.b[b];
     }
   }
-  block_slab<9>(acc, slab + blockIdx.x * 9);
+  const double sum = block_sum<9, kBlock>(acc, threadIdx.x);
+  if (threadIdx.x < 9) slab[blockIdx.x * 9 + threadIdx.x] = sum;
 }
 
 // One thread: the slabs in order -> Horn's rotation.
@@ -453,8 +438,9 @@ __global__ __launch_bounds__(kBlock) void gnc_residual_kernel(const float* __res
   __shared__ double s_mx[kBlock / kWave];
   mx = wave_max_d(mx);
   if ((threadIdx.x & 63) == 0) s_mx[threadIdx.x >> 6] = mx;
-  block_slab<1>(acc, slab + blockIdx.x * 2);  // (synchronises)
+  const double cost = block_sum<1, kBlock>(acc, threadIdx.x);  // (synchronises)
   if (threadIdx.x == 0) {
+    slab[blockIdx.x * 2] = cost;
     double m2 = s_mx[0];
     for (int w = 1; w < kBlock / kWave; ++w) m2 = s_mx[w] > m2 ? s_mx[w] : m2;
     slab[blockIdx.x * 2 + 1] = m2;

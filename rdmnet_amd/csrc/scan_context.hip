@@ -40,13 +40,6 @@ constexpr int kIndexBits = 26, kShiftBits = 6;
 constexpr int64_t kMaxCandidates = int64_t(1) << kIndexBits;
 static_assert(kLd == kMaxDim && kMaxDim == kWave, "lane = shift and one zero-padded row per ring");
 
-// fp32 -> unsigned key with the order of the floats (negative values included); never 0 for a non-NaN value
-__device__ __forceinline__ uint32_t order_key(float v) {
-  const uint32_t b = __float_as_uint(v);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_value(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
 __device__ __forceinline__ bool valid_dims(int n_rings, int n_sectors) {
   return n_rings >= 1 && n_rings <= kMaxDim && n_sectors >= 1 && n_sectors <= kMaxDim;
 }

@@ -26,20 +26,12 @@ constexpr unsigned long long kEmptyKey = ~0ull;
 constexpr int kScanBlock = 1024;
 constexpr int kScanItems = 4;  // per thread -> 4096 items per block
 
-__device__ __forceinline__ unsigned ordered(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float unordered(unsigned o) {
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-
 __global__ __launch_bounds__(256) void vd_bbox_kernel(const float* __restrict__ pts, int64_t n, int ld,
                                                        unsigned* __restrict__ min_ord) {
   __shared__ unsigned red[4][3];
   unsigned lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += 256ll * gridDim.x)
-    for (int d = 0; d < 3; ++d) lo[d] = min(lo[d], ordered(pts[i * ld + d]));
+    for (int d = 0; d < 3; ++d) lo[d] = min(lo[d], order_key(pts[i * ld + d]));
   for (int d = 0; d < 3; ++d)
     for (int o = 32; o > 0; o >>= 1) lo[d] = min(lo[d], static_cast<unsigned>(__shfl_xor(static_cast<int>(lo[d]), o, 64)));
   if ((threadIdx.x & 63) == 0)
@@ -60,7 +52,7 @@ __global__ __launch_bounds__(256) void vd_key_kernel(const float* __restrict__ p
   if (i >= n) return;
   unsigned long long key = 0;
   for (int d = 0; d < 3; ++d) {
-    const double lo = static_cast<double>(unordered(min_ord[d])) - voxel * 0.5;
+    const double lo = static_cast<double>(key_value(min_ord[d])) - voxel * 0.5;
     const double c = floor((static_cast<double>(pts[i * ld + d]) - lo) / voxel);
     if (!(c >= 0.0 && c < 2097152.0)) {  // 21 bits per axis
       atomicExch(status, 1);

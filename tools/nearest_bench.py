@@ -3,9 +3,11 @@
 points, tools/icp_bench.py's generator), both directions at the automatic cell, and, for comparison, scipy's cKDTree k = 1
 query -- what the reference's get_nearest_neighbor calls -- on the same float64 points with 16 host threads.  The src_to_ref
 side is also timed as rdm_information_matrix (ops.information_matrix at 0.6 m with the correspondence set: the same search plus the
-reduction and the compaction) and, with --cpu, as its float64 host restatement on the cKDTree query.
+reduction and the compaction) and, with --cpu, as its float64 host restatement on the cKDTree query.  --ball adds the ball
+query on the same clouds (rdm_ball_count / rdm_ball_fill): ops.pair_overlap (the count pass) and ops.get_correspondences (count and
+list) at 0.6 m.
 
-  python tools/nearest_bench.py [--reps 5] [--cpu]
+  python tools/nearest_bench.py [--reps 5] [--cpu] [--ball]
   rocprofv3 --kernel-trace --stats -d <dir> -- python tools/nearest_bench.py --reps 1      # per-kernel times, a run of its own
 Prints one JSON line per pair: sizes, the share of rows that took the exact sweep, GPU ms per call (median), cKDTree ms (--cpu)."""
 RADIUS = 0.6  # cfg.fine_matching.acceptance_radius
@@ -33,6 +35,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--cpu', action='store_true', help="also time scipy's cKDTree (build + k = 1 query, 16 threads)")
+    ap.add_argument('--ball', action='store_true', help='also time the ball query: pair_overlap and get_correspondences at 0.6 m')
     a = ap.parse_args()
     import torch
     from rdmnet_amd import ops
@@ -58,6 +61,19 @@ def main():
             times.append((time.perf_counter() - t0) * 1e3)
         out['information'] = {'gpu_ms': float(np.median(times)), 'gpu_ms_all': times, 'C': int(corr.shape[0]),
                               'over_nearest': float(np.median(times)) / out['src_to_ref']['gpu_ms']}
+        if a.ball:
+            for key, call in (('pair_overlap', lambda: ops.pair_overlap(r, s, T, RADIUS)),
+                              ('get_correspondences', lambda: ops.get_correspondences(r, s, T, RADIUS))):
+                res = call()  # warm-up
+                torch.cuda.synchronize()
+                times = []
+                for _ in range(a.reps):
+                    t0 = time.perf_counter()
+                    call()
+                    torch.cuda.synchronize()  # (the list is filled after the count's read-back)
+                    times.append((time.perf_counter() - t0) * 1e3)
+                out[key] = {'gpu_ms': float(np.median(times)), 'gpu_ms_all': times,
+                            'C': int(res[2] if key == 'pair_overlap' else res.shape[0])}
         if a.cpu:
             import nearest_restatement as R
             from scipy.spatial import cKDTree
