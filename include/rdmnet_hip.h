@@ -1173,6 +1173,44 @@ int rdm_voxel_map_extract_moments(const void* map, size_t map_bytes, int64_t cap
                                   double* eigenvalues, double* normals, int64_t max_rows, int64_t* n_rows, void* ws, size_t ws_bytes,
                                   void* stream);
 
+/* ---- §7 voxel map registration: scans against the per-voxel Gaussians (voxel_map.hip) ---------------------------------------------
+ * Point-to-distribution registration (the NDT / voxelised-GICP family) of a packed batch of scans against a map with moments.  Not in
+ * the reference tree -> parity unpinned; the project's own definition, pinned to the NumPy restatement
+ * tests/voxel_register_restatement.py.  The map and the moments block are only read.  points / offsets / poses are those of
+ * rdm_voxel_map_integrate (ld >= channels; poses: the initial pose X_s of every scan).  Parameters: sigma > 0 (metres: the isotropic
+ * noise of a scan point), min_points >= 1, neighbors 1 or 7, max_iteration >= 0, rot_eps >= 0, trans_eps >= 0, min_range, max_range.
+ * One evaluation of scan s at the pose X = (R, t), everything in float64 without contraction:
+ *   gate      each row as rdm_voxel_map_integrate does (non-finite values, then range), w = X p with its association, Q_d and cell_d
+ *             by its quantisation; a point the map would count in out_of_extent is dropped;
+ *   visit     the voxels cell + o for o = (0,0,0), (-1,0,0), (+1,0,0), (0,-1,0), (0,+1,0), (0,0,-1), (0,0,+1) (neighbors = 1: the
+ *             first only), passing over a cell outside [-2^20, 2^20); a voxel takes part if its key is in the table and its count
+ *             n >= min_points;
+ *   per pair  mu_d = ((double)sum_d / n) / 2^F voxel; Sigma = the covariance of rdm_voxel_map_extract_moments (its formula, from
+ *             the nine sums) + sigma^2 on the diagonal; M = Sigma^-1 (here: cofactors over the determinant); r = w - mu, q = w - t,
+ *             J = [-[q]x | I3] (3 x 6, rotation first);
+ *   totals    H += J^T M J, g += J^T M r, cost += r^T M r, n_corr += 1.
+ * Iteration: (1) evaluate at X and record the outputs; (2) if max_iteration updates are applied, stop with status 0; (3) solve
+ * H delta = -g by a float64 Cholesky without pivoting; (4) if n_corr = 0 or a pivot is <= 0 or not finite, stop with status 2
+ * (degenerate: the pose is the one just evaluated); (5) else with delta = (omega, v): R <- Exp(omega) R (Rodrigues), t <- t + v --
+ * a perturbation about the sensor's position, so a map far from the origin is as well conditioned as one at it; (6) if |omega| <
+ * rot_eps and |v| < trans_eps, evaluate once more at the new pose and stop with status 1; (7) else continue.  The outputs always
+ * describe the returned pose; max_iteration = 0 is the evaluation alone.
+ * Outputs per scan (device): transforms f64 [n, 16]; hessians f64 [n, 36] (H: the information of the pose in the (omega, v)
+ * parametrisation, usable as a scan-to-map edge weight); gradients f64 [n, 6]; costs f64 [n]; stats int64 [n, 4] = {updates
+ * applied, n_corr, points that passed the gates, status}.  n_scans = 0 (nothing is written) and empty scans (status 2, or 0 with
+ * max_iteration = 0) are valid; n_scans <= 2^20.  A null or short moments block, sigma <= 0, neighbors not 1 or 7 and negative
+ * tolerances or counts are RDM_ERR_ARG; a workspace below rdm_voxel_map_register_workspace_bytes(n_scans) is RDM_ERR_WORKSPACE.
+ * An iteration is two launches: a fixed number of workgroups per scan, each thread striding over rows by their index within the
+ * scan and the sums reduced in a fixed order, then one workgroup per scan that adds the slab rows in index order.  No float
+ * atomics: two runs give the same bits, and a scan's result does not depend on the rest of the batch, on the capacity or on the
+ * order in which the map was integrated.  The host reads one word per chunk of iterations and returns when every scan stopped. */
+size_t rdm_voxel_map_register_workspace_bytes(int64_t n_scans);
+int rdm_voxel_map_register(const void* map, size_t map_bytes, int64_t capacity, int channels, const void* moments, size_t moments_bytes,
+                           double voxel, const float* points, int64_t ld, int64_t total, const int64_t* offsets, const double* poses,
+                           int64_t n_scans, double min_range, double max_range, double sigma, int64_t min_points, int neighbors,
+                           int max_iteration, double rot_eps, double trans_eps, double* transforms, double* hessians, double* gradients,
+                           double* costs, int64_t* stats, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -462,6 +462,284 @@ int open_moments(const char* what, void* moments, size_t moments_bytes, int64_t 
   return RDM_OK;
 }
 
+// ---- scan-to-map registration (include/rdmnet_hip.h, "voxel map registration"; tests/voxel_register_restatement.py) --------------
+//
+// An iteration is two launches.  register_accumulate_kernel: kRegGroups workgroups per scan; row j of a scan goes to thread
+// j mod (kRegGroups kBlock) of the scan's threads, whatever else the batch holds, so a scan's sums are the same wherever it stands.
+// A thread keeps the upper triangle of H (21), g (6), the cost and two counts, block_sum adds them in a fixed order and one slab row
+// per workgroup is written.  register_finalize_kernel: one workgroup per scan adds the scan's slab rows in index order, thread 0
+// factors H, moves the pose, tests convergence and writes the outputs.  No float atomics; the table is only read.
+
+constexpr int kRegGroups = 64;   // workgroups per scan
+constexpr int kRegSums = 30;     // H upper triangle, g, cost, then n_corr and the gated points (integers, exact in a double)
+constexpr int kRegRow = 32;      // doubles per slab row
+constexpr int kRegChunk = 8;     // evaluations enqueued between two reads of `running`
+constexpr int64_t kMaxRegScans = int64_t(1) << 20;  // kRegGroups workgroups each in one grid
+
+struct RegState {
+  double X[16];  // the pose of the next evaluation
+  int updates;   // applied so far
+  int last;      // the next evaluation is the one after convergence
+  int done;
+  int pad;
+};
+
+struct RegWork {
+  RegState* st;  // [n_scans]
+  double* slab;  // [n_scans][kRegGroups][kRegRow]
+  int* running;  // scans that are not done
+};
+
+bool carve_register(Arena& ar, int64_t n_scans, RegWork& w) {
+  const size_t n = static_cast<size_t>(n_scans > 0 ? n_scans : 1);
+  w.running = ar.take<int>(1);
+  w.st = ar.take<RegState>(n);
+  w.slab = ar.take<double>(n * kRegGroups * kRegRow);
+  return ar.ok;
+}
+
+__global__ void __launch_bounds__(kBlock) register_init_kernel(const double* __restrict__ poses, long long n_scans, RegWork w) {
+  const long long s = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
+  if (s == 0) *w.running = static_cast<int>(n_scans);
+  if (s >= n_scans) return;
+  RegState& st = w.st[s];
+  for (int k = 0; k < 16; ++k) st.X[k] = poses[s * 16 + k];
+  st.updates = 0;
+  st.last = 0;
+  st.done = 0;
+  st.pad = 0;
+}
+
+__global__ void __launch_bounds__(kBlock) register_accumulate_kernel(Table t, const unsigned long long* __restrict__ moments,
+                                                                     long long capacity, int channels, double voxel,
+                                                                     const float* __restrict__ points, long long ld, long long total,
+                                                                     const int64_t* __restrict__ offsets, double lo2, double hi2,
+                                                                     double sigma2, unsigned int min_points, int neighbors, RegWork w) {
+#pragma clang fp contract(off)
+  const long long scan = blockIdx.x / kRegGroups;
+  const int group = blockIdx.x % kRegGroups;
+  const RegState& st = w.st[scan];
+  if (st.done) return;
+  double X[12];
+  for (int k = 0; k < 12; ++k) X[k] = st.X[k];
+  long long begin = offsets[scan], end = offsets[scan + 1];
+  begin = begin < 0 ? 0 : begin;
+  end = end > total ? total : end;
+  double acc[kRegSums];
+#pragma unroll
+  for (int k = 0; k < kRegSums; ++k) acc[k] = 0.0;
+  int n_corr = 0, n_pass = 0;
+  const double s = voxel / kMomSteps, s2 = s * s;
+  for (long long i = begin + group * kBlock + threadIdx.x; i < end; i += static_cast<long long>(kRegGroups) * kBlock) {
+    const float* p = points + i * ld;
+    bool finite = true, inside = true;
+    for (int c = 0; c < kMaxC; ++c) {
+      const float v = c < channels ? p[c] : 0.f;
+      finite = finite && isfinite(v);
+      if (c >= 3) inside = inside && fabs(static_cast<double>(v)) < kScale;
+    }
+    if (!finite) continue;
+    const double x = p[0], y = p[1], z = p[2];
+    const double r2 = (x * x + y * y) + z * z;
+    if (!(lo2 <= r2 && r2 <= hi2)) continue;
+    double wd[3];
+    long long cell[3];
+    for (int d = 0; d < 3; ++d) {
+      wd[d] = ((X[4 * d] * x + X[4 * d + 1] * y) + X[4 * d + 2] * z) + X[4 * d + 3];
+      const double f = floor(wd[d] / voxel * kScale);
+      const bool ok = f >= -kQLimit && f < kQLimit;  // (NaN and infinities fail)
+      inside = inside && ok;
+      cell[d] = (ok ? static_cast<long long>(f) : 0ll) >> kFrac;
+    }
+    if (!inside) continue;
+    ++n_pass;
+    const double q0 = wd[0] - X[3], q1 = wd[1] - X[7], q2 = wd[2] - X[11];
+    for (int o = 0; o < neighbors; ++o) {  // (0,0,0), (-1,0,0), (+1,0,0), (0,-1,0), (0,+1,0), (0,0,-1), (0,0,+1)
+      long long c[3] = {cell[0], cell[1], cell[2]};
+      if (o > 0) c[(o - 1) >> 1] += (o & 1) ? -1 : 1;
+      if (c[0] < -kHalf || c[0] >= kHalf || c[1] < -kHalf || c[1] >= kHalf || c[2] < -kHalf || c[2] >= kHalf) continue;
+      const unsigned long long key = (static_cast<unsigned long long>(c[0] + kHalf) << 42) |
+                                     (static_cast<unsigned long long>(c[1] + kHalf) << 21) | static_cast<unsigned long long>(c[2] + kHalf);
+      const long long slot = find(t.keys, capacity, key);
+      if (slot < 0) continue;
+      const uint32_t count = t.counts[slot];
+      if (count < min_points) continue;
+      const double n = static_cast<double>(count);
+      double S[kPlanes];
+#pragma unroll
+      for (int k = 0; k < kPlanes; ++k) S[k] = static_cast<double>(static_cast<long long>(moments[moment_at(slot, k, capacity)]));
+      double r[3];
+#pragma unroll
+      for (int d = 0; d < 3; ++d)
+        r[d] = wd[d] - static_cast<double>(static_cast<long long>(t.sums[d * capacity + slot])) / n / kScale * voxel;
+      const double m0 = S[0] / n, m1 = S[1] / n, m2 = S[2] / n;
+      const double a00 = (S[3] / n - m0 * m0) * s2 + sigma2, a01 = (S[4] / n - m0 * m1) * s2, a02 = (S[5] / n - m0 * m2) * s2;
+      const double a11 = (S[6] / n - m1 * m1) * s2 + sigma2, a12 = (S[7] / n - m1 * m2) * s2, a22 = (S[8] / n - m2 * m2) * s2 + sigma2;
+      // M = the inverse of the symmetric matrix a: cofactors over the determinant
+      const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
+      const double c11 = a00 * a22 - a02 * a02, c12 = a01 * a02 - a00 * a12, c22 = a00 * a11 - a01 * a01;
+      const double det = (a00 * c00 + a01 * c01) + a02 * c02;
+      const double M[3][3] = {{c00 / det, c01 / det, c02 / det}, {c01 / det, c11 / det, c12 / det}, {c02 / det, c12 / det, c22 / det}};
+      double Mr[3];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) Mr[d] = (M[d][0] * r[0] + M[d][1] * r[1]) + M[d][2] * r[2];
+      // B = [q]x M = (J's rotation block)^T M; H = [[-B [q]x, B], [B^T, M]], g = (q x Mr, Mr)
+      double B[3][3];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        B[0][j] = q1 * M[2][j] - q2 * M[1][j];
+        B[1][j] = q2 * M[0][j] - q0 * M[2][j];
+        B[2][j] = q0 * M[1][j] - q1 * M[0][j];
+      }
+      double Hrr[3][3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        Hrr[a][0] = B[a][2] * q1 - B[a][1] * q2;
+        Hrr[a][1] = B[a][0] * q2 - B[a][2] * q0;
+        Hrr[a][2] = B[a][1] * q0 - B[a][0] * q1;
+      }
+      int k = 0;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int b = a; b < 3; ++b) acc[k++] += Hrr[a][b];
+#pragma unroll
+        for (int b = 0; b < 3; ++b) acc[k++] += B[a][b];
+      }
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = a; b < 3; ++b) acc[k++] += M[a][b];
+      acc[21] += q1 * Mr[2] - q2 * Mr[1];
+      acc[22] += q2 * Mr[0] - q0 * Mr[2];
+      acc[23] += q0 * Mr[1] - q1 * Mr[0];
+      acc[24] += Mr[0];
+      acc[25] += Mr[1];
+      acc[26] += Mr[2];
+      acc[27] += (r[0] * Mr[0] + r[1] * Mr[1]) + r[2] * Mr[2];
+      ++n_corr;
+    }
+  }
+  acc[28] = static_cast<double>(n_corr);
+  acc[29] = static_cast<double>(n_pass);
+  const double sum = block_sum<kRegSums, kBlock>(acc, threadIdx.x);
+  if (threadIdx.x < kRegSums) w.slab[(scan * kRegGroups + group) * kRegRow + threadIdx.x] = sum;
+}
+
+// Exp(omega) by Rodrigues' formula: I + a [omega]x + b [omega]x^2, a = sin(th) / th, b = (1 - cos(th)) / th^2 (their series below 1e-4).
+__device__ __forceinline__ void rodrigues(const double* __restrict__ om, double (&E)[3][3]) {
+  const double th2 = (om[0] * om[0] + om[1] * om[1]) + om[2] * om[2];
+  const double th = sqrt(th2);
+  double a, b;
+  if (th < 1e-4) {
+    a = 1.0 - th2 / 6.0;
+    b = 0.5 - th2 / 24.0;
+  } else {
+    a = sin(th) / th;
+    b = (1.0 - cos(th)) / th2;
+  }
+  const double K[3][3] = {{0.0, -om[2], om[1]}, {om[2], 0.0, -om[0]}, {-om[1], om[0], 0.0}};
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double kk = (K[i][0] * K[0][j] + K[i][1] * K[1][j]) + K[i][2] * K[2][j];
+      E[i][j] = ((i == j ? 1.0 : 0.0) + a * K[i][j]) + b * kk;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) register_finalize_kernel(RegWork w, int max_iteration, double rot_eps, double trans_eps,
+                                                                   double* __restrict__ transforms, double* __restrict__ hessians,
+                                                                   double* __restrict__ gradients, double* __restrict__ costs,
+                                                                   int64_t* __restrict__ stats) {
+#pragma clang fp contract(off)
+  const long long scan = blockIdx.x;
+  RegState& st = w.st[scan];
+  if (st.done) return;
+  __shared__ double tot[kRegSums];
+  if (threadIdx.x < kRegSums) {
+    const double* rows = w.slab + scan * kRegGroups * kRegRow + threadIdx.x;
+    double sum = rows[0];
+    for (int g = 1; g < kRegGroups; ++g) sum += rows[g * kRegRow];
+    tot[threadIdx.x] = sum;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double H[6][6], g[6];
+  int k = 0;
+  for (int a = 0; a < 3; ++a) {
+    for (int b = a; b < 3; ++b) H[a][b] = H[b][a] = tot[k++];
+    for (int b = 0; b < 3; ++b) H[a][3 + b] = H[3 + b][a] = tot[k++];
+  }
+  for (int a = 0; a < 3; ++a)
+    for (int b = a; b < 3; ++b) H[3 + a][3 + b] = H[3 + b][3 + a] = tot[k++];
+  for (int a = 0; a < 6; ++a) g[a] = tot[21 + a];
+  const long long n_corr = static_cast<long long>(tot[28]), n_pass = static_cast<long long>(tot[29]);
+  // the outputs describe the pose just evaluated
+  for (int q = 0; q < 16; ++q) transforms[scan * 16 + q] = st.X[q];
+  for (int a = 0; a < 6; ++a) {
+    for (int b = 0; b < 6; ++b) hessians[scan * 36 + a * 6 + b] = H[a][b];
+    gradients[scan * 6 + a] = g[a];
+  }
+  costs[scan] = tot[27];
+  int status = -1;  // running
+  if (st.last) {
+    status = 1;
+  } else if (st.updates >= max_iteration) {
+    status = 0;
+  } else {
+    // H = L L^T without pivoting, L y = -g, L^T delta = y
+    double L[6][6], y[6], delta[6];
+    bool good = n_corr > 0;
+    for (int j = 0; j < 6 && good; ++j) {
+      double d = H[j][j];
+      for (int q = 0; q < j; ++q) d -= L[j][q] * L[j][q];
+      if (!(d > 0.0) || !isfinite(d)) {
+        good = false;
+        break;
+      }
+      L[j][j] = sqrt(d);
+      for (int i = j + 1; i < 6; ++i) {
+        double v = H[i][j];
+        for (int q = 0; q < j; ++q) v -= L[i][q] * L[j][q];
+        L[i][j] = v / L[j][j];
+      }
+    }
+    if (!good) {
+      status = 2;
+    } else {
+      for (int i = 0; i < 6; ++i) {
+        double v = -g[i];
+        for (int q = 0; q < i; ++q) v -= L[i][q] * y[q];
+        y[i] = v / L[i][i];
+      }
+      for (int i = 5; i >= 0; --i) {
+        double v = y[i];
+        for (int q = i + 1; q < 6; ++q) v -= L[q][i] * delta[q];
+        delta[i] = v / L[i][i];
+      }
+      double E[3][3], R[3][3];
+      rodrigues(delta, E);
+      for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) R[i][j] = (E[i][0] * st.X[j] + E[i][1] * st.X[4 + j]) + E[i][2] * st.X[8 + j];
+      for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) st.X[4 * i + j] = R[i][j];
+        st.X[4 * i + 3] = st.X[4 * i + 3] + delta[3 + i];
+      }
+      st.updates += 1;
+      const double rot = sqrt((delta[0] * delta[0] + delta[1] * delta[1]) + delta[2] * delta[2]);
+      const double trans = sqrt((delta[3] * delta[3] + delta[4] * delta[4]) + delta[5] * delta[5]);
+      if (rot < rot_eps && trans < trans_eps) st.last = 1;
+    }
+  }
+  stats[scan * 4 + 0] = st.updates;
+  stats[scan * 4 + 1] = n_corr;
+  stats[scan * 4 + 2] = n_pass;
+  stats[scan * 4 + 3] = status;
+  if (status >= 0) {
+    st.done = 1;
+    atomicSub(w.running, 1);
+  }
+}
+
 }  // namespace
 }  // namespace rdm
 
@@ -654,4 +932,66 @@ extern "C" int rdm_voxel_map_extract_moments(const void* map, size_t map_bytes, 
   hipLaunchKernelGGL(emit_moments_kernel, dim3(blocks_for(max_rows)), dim3(kBlock), 0, s, t, m, static_cast<long long>(capacity), voxel,
                      w.slots, w.n_sel, static_cast<long long>(max_rows), sums, cov, eigenvalues, normals, n_rows);
   return launch_status("rdm_voxel_map_extract_moments");
+}
+
+// ---- voxel map registration ---------------------------------------------------------------------------------------------------
+
+extern "C" size_t rdm_voxel_map_register_workspace_bytes(int64_t n_scans) {
+  using namespace rdm;
+  if (n_scans < 0 || n_scans > kMaxRegScans) return 0;
+  Arena ar(nullptr, 0);
+  RegWork w;
+  carve_register(ar, n_scans, w);
+  return ar.off;
+}
+
+extern "C" int rdm_voxel_map_register(const void* map, size_t map_bytes, int64_t capacity, int channels, const void* moments,
+                                      size_t moments_bytes, double voxel, const float* points, int64_t ld, int64_t total,
+                                      const int64_t* offsets, const double* poses, int64_t n_scans, double min_range, double max_range,
+                                      double sigma, int64_t min_points, int neighbors, int max_iteration, double rot_eps,
+                                      double trans_eps, double* transforms, double* hessians, double* gradients, double* costs,
+                                      int64_t* stats, void* ws, size_t ws_bytes, void* stream) {
+  using namespace rdm;
+  Table t;
+  if (const int rc = open_table("rdm_voxel_map_register", const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
+  RDM_REQUIRE(moments != nullptr, "rdm_voxel_map_register: null moments block");
+  RDM_REQUIRE(moments_bytes >= rdm_voxel_moments_bytes(capacity), "rdm_voxel_map_register: the moments block is too small (%zu < %zu bytes)",
+              moments_bytes, rdm_voxel_moments_bytes(capacity));
+  RDM_REQUIRE(voxel > 0.0 && std::isfinite(voxel), "rdm_voxel_map_register: voxel must be positive and finite");
+  RDM_REQUIRE(n_scans >= 0 && n_scans <= kMaxRegScans && total >= 0 && ld >= channels,
+              "rdm_voxel_map_register: bad sizes (ld must be >= channels, n_scans <= 2^20)");
+  RDM_REQUIRE(min_range >= 0.0 && max_range >= min_range, "rdm_voxel_map_register: need 0 <= min_range <= max_range");
+  RDM_REQUIRE(sigma > 0.0 && std::isfinite(sigma), "rdm_voxel_map_register: sigma must be positive and finite (got %g)", sigma);
+  RDM_REQUIRE(neighbors == 1 || neighbors == 7, "rdm_voxel_map_register: neighbors must be 1 or 7 (got %d)", neighbors);
+  RDM_REQUIRE(min_points >= 1 && max_iteration >= 0 && rot_eps >= 0.0 && trans_eps >= 0.0,
+              "rdm_voxel_map_register: need min_points >= 1, max_iteration >= 0, rot_eps >= 0 and trans_eps >= 0");
+  Arena ar(ws, ws_bytes);
+  RegWork w;
+  if (!carve_register(ar, n_scans, w)) {
+    set_error("rdm_voxel_map_register: workspace too small (%zu < %zu bytes)", ws_bytes, ar.off);
+    return RDM_ERR_WORKSPACE;
+  }
+  if (n_scans == 0) return RDM_OK;
+  RDM_REQUIRE((points || total == 0) && offsets && poses, "rdm_voxel_map_register: null argument");
+  RDM_REQUIRE(transforms && hessians && gradients && costs && stats, "rdm_voxel_map_register: null output");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned long long* m = static_cast<const unsigned long long*>(moments);
+  const unsigned int least = min_points > 0xffffffffll ? 0xffffffffu : static_cast<unsigned int>(min_points);
+  hipLaunchKernelGGL(register_init_kernel, dim3(blocks_for(n_scans)), dim3(kBlock), 0, s, poses, static_cast<long long>(n_scans), w);
+  int running = 1;
+  for (int k = 0; k <= max_iteration && running > 0;) {
+    const int end = max_iteration - k < kRegChunk ? max_iteration + 1 : k + kRegChunk;
+    for (; k < end; ++k) {
+      hipLaunchKernelGGL(register_accumulate_kernel, dim3(static_cast<unsigned>(n_scans * kRegGroups)), dim3(kBlock), 0, s, t, m,
+                         static_cast<long long>(capacity), channels, voxel, points, static_cast<long long>(ld),
+                         static_cast<long long>(total), offsets, min_range * min_range, max_range * max_range, sigma * sigma, least,
+                         neighbors, w);
+      hipLaunchKernelGGL(register_finalize_kernel, dim3(static_cast<unsigned>(n_scans)), dim3(kBlock), 0, s, w, max_iteration, rot_eps,
+                         trans_eps, transforms, hessians, gradients, costs, stats);
+    }
+    if (const int rc = launch_status("rdm_voxel_map_register")) return rc;
+    RDM_HIP_CHECK(hipMemcpyAsync(&running, w.running, sizeof(int), hipMemcpyDeviceToHost, s));  // one 4-byte read-back per chunk
+    RDM_HIP_CHECK(hipStreamSynchronize(s));
+  }
+  return RDM_OK;
 }

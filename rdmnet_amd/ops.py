@@ -871,11 +871,8 @@ class VoxelMap:
                 self.capacity, self._buf = capacity, new  # (the old block is freed in stream order by the caching allocator)
         self._bound += n_points
 
-    def integrate(self, clouds, poses, min_range=0.0, max_range=float('inf')):
-        """clouds: a list of float32 CUDA tensors [N_i, >= C] (empty ones allowed), or a pair (points float32 CUDA [N, ld >= C],
-        offsets int64 [n + 1], host or device: scan i is rows offsets[i] .. offsets[i + 1]).  poses: [n, 4, 4] finite, anything
-        numpy or torch holds (world = pose @ point).  A point is integrated iff its C values are finite and min_range <= its range
-        in the sensor frame <= max_range.  -> self.  The list form concatenates the clouds' first C columns on the device."""
+    def _packed(self, what, clouds, poses, min_range, max_range):
+        """The argument checks of integrate and register -> (points or None, offsets, n, poses float64 numpy [n, 4, 4], lo, hi)."""
         import numpy as np
         C = self.channels
         if isinstance(clouds, tuple) and len(clouds) == 2 and isinstance(clouds[1], torch.Tensor) and clouds[1].dtype == torch.int64:
@@ -887,7 +884,7 @@ class VoxelMap:
             named = [(t, f'clouds[{i}]') for i, t in enumerate(clouds)]
             points = offsets = None
         else:
-            raise ValueError('VoxelMap.integrate: clouds must be a list of tensors, or (points, offsets)')
+            raise ValueError(f'VoxelMap.{what}: clouds must be a list of tensors, or (points, offsets)')
         for t, name in named:
             if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] >= C):
                 raise ValueError(f'{name} must be a float32 CUDA tensor [N, >={C}] (the map has {C} channels)')
@@ -917,6 +914,14 @@ class VoxelMap:
         lo, hi = float(min_range), float(max_range)
         if not 0.0 <= lo <= hi:
             raise ValueError(f'need 0 <= min_range <= max_range, got {min_range} and {max_range}')
+        return points, offsets, n, X, lo, hi
+
+    def integrate(self, clouds, poses, min_range=0.0, max_range=float('inf')):
+        """clouds: a list of float32 CUDA tensors [N_i, >= C] (empty ones allowed), or a pair (points float32 CUDA [N, ld >= C],
+        offsets int64 [n + 1], host or device: scan i is rows offsets[i] .. offsets[i + 1]).  poses: [n, 4, 4] finite, anything
+        numpy or torch holds (world = pose @ point).  A point is integrated iff its C values are finite and min_range <= its range
+        in the sensor frame <= max_range.  -> self.  The list form concatenates the clouds' first C columns on the device."""
+        points, offsets, n, X, lo, hi = self._packed('integrate', clouds, poses, min_range, max_range)
         if n == 0 or points is None or points.shape[0] == 0:
             return self
         total = int(points.shape[0])
@@ -1001,6 +1006,66 @@ class VoxelMap:
         return dict(voxels=voxels, qualified=qualified, degenerate=qualified - n_full,
                     plane_thickness=math.sqrt(thick / qualified) if qualified else float('nan'),
                     entropy=ent / n_full if n_full else float('nan'))
+
+    def register(self, clouds, poses, *, sigma=0.02, min_points=4, neighbors=1, max_iteration=30, rot_eps=1e-5, trans_eps=1e-4,
+                 min_range=0.0, max_range=float('inf')):
+        """Scan-to-map registration on the per-voxel Gaussians (rdm_voxel_map_register): every scan of the batch
+        is registered, from its initial pose, against this map -- point-to-distribution, the NDT / voxelised-GICP family.  clouds,
+        poses, min_range, max_range: as `integrate` takes them (poses: the initial poses).  sigma: the isotropic noise of a scan point
+        in metres, added to every voxel's covariance; a voxel takes part with at least min_points points; neighbors 1 (the point's own
+        voxel) or 7 (and its six face neighbours: a wider basin, less accurate from a small error); at most max_iteration Gauss-Newton
+        updates, until one is below rot_eps (rad) and trans_eps (m).  The map is only read.  -> MapRegistrationResult (device
+        tensors).  One 4-byte read-back per eight iterations."""
+        self._need_moments('register')
+        points, offsets, n, X, lo, hi = self._packed('register', clouds, poses, min_range, max_range)
+        sigma, rot_eps, trans_eps = float(sigma), float(rot_eps), float(trans_eps)
+        min_points, neighbors, max_iteration = int(min_points), int(neighbors), int(max_iteration)
+        if not (sigma > 0 and sigma < float('inf')):
+            raise ValueError(f'sigma must be positive and finite, got {sigma}')
+        if neighbors not in (1, 7):
+            raise ValueError(f'neighbors must be 1 or 7, got {neighbors}')
+        if min_points < 1 or max_iteration < 0 or not rot_eps >= 0 or not trans_eps >= 0:
+            raise ValueError('need min_points >= 1, max_iteration >= 0, rot_eps >= 0 and trans_eps >= 0')
+        L, dev = _lib.lib(), self.device
+        real = torch.zeros((n, 59), dtype=torch.float64, device=dev)  # transforms, hessians, gradients, costs
+        stats = torch.zeros((n, 4), dtype=torch.int64, device=dev)
+        T, H, g, cost = (real.view(-1)[a * n:b * n].view(n, b - a) for a, b in ((0, 16), (16, 52), (52, 58), (58, 59)))
+        if n > 0:
+            if points is None or points.shape[0] == 0:
+                points = torch.zeros((1, self.channels), dtype=torch.float32, device=dev)
+                total, ld = 0, self.channels
+            else:
+                total = int(points.shape[0])
+                ld = points.stride(0) if total > 1 else points.shape[1]
+            with torch.cuda.device(dev):
+                offsets = offsets.to(dev).contiguous()
+                Xd = torch.from_numpy(X).to(dev)
+                ws = scratch(dev, L.rdm_voxel_map_register_workspace_bytes(n))
+                _lib.check(L.rdm_voxel_map_register(*self._head(), self._mom.data_ptr(), self._mom.numel(), self.voxel, points.data_ptr(), ld,
+                                                    total, offsets.data_ptr(), Xd.data_ptr(), n, lo, hi, sigma, min_points, neighbors,
+                                                    max_iteration, rot_eps, trans_eps, T.data_ptr(), H.data_ptr(), g.data_ptr(),
+                                                    cost.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+                           'rdm_voxel_map_register')
+        return MapRegistrationResult(T.view(n, 4, 4), H.view(n, 6, 6), g, cost.view(n), stats[:, 0], stats[:, 1], stats[:, 2], stats[:, 3])
+
+
+class MapRegistrationResult:
+    """What VoxelMap.register returns, device tensors with one row per scan: transformations float64 [n, 4, 4] (the refined poses),
+    information float64 [n, 6, 6] (H = the sum of J^T M J at the returned pose, rotation first: usable as the weight of a scan-to-map
+    edge), gradient float64 [n, 6], cost float64 [n] (the sum of r^T M r), and int64 [n] each: iterations (updates applied),
+    num_correspondences (point-voxel pairs of the last evaluation), num_points (rows that passed the gates) and status (STATUS)."""
+    STATUS = ('max_iteration', 'converged', 'degenerate')
+
+    def __init__(self, transformations, information, gradient, cost, iterations, num_correspondences, num_points, status):
+        self.transformations, self.information, self.gradient, self.cost = transformations, information, gradient, cost
+        self.iterations, self.num_correspondences, self.num_points, self.status = iterations, num_correspondences, num_points, status
+
+    def __repr__(self):
+        rows = torch.stack([self.iterations, self.num_correspondences, self.num_points, self.status]).cpu().tolist()
+        cost = self.cost.cpu().tolist()
+        return 'MapRegistrationResult(' + '; '.join(
+            f'{k}: {self.STATUS[s] if 0 <= s < 3 else s} after {i} updates, {c} correspondences of {p} points, cost {v:.6g}'
+            for k, (i, c, p, s, v) in enumerate(zip(*rows, cost))) + ')'
 
 
 class RegistrationResult:

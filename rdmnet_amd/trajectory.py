@@ -3,7 +3,8 @@
     python -m rdmnet_amd.trajectory --features-root DIR [--optimize] [--line-process-weight MU] [--unit-information] [--out DIR]
                                   [--preconditioner {block_jacobi,chain}] [--linear-solver {pcg,direct}]
                                   [--map-scans DATASET_ROOT [--map-raw] [--map-voxel 0.3] [--map-min-points 1]
-                                   [--map-range LO HI] [--map-batch 64] [--map-sharpness [--map-sharpness-min-points 4]]]
+                                   [--map-range LO HI] [--map-batch 64] [--map-sharpness [--map-sharpness-min-points 4]]
+                                   [--map-refine [--map-refine-sigma 0.02] [--map-refine-neighbors {1,7}] [--map-refine-iterations 30]]]
 
 reads the `{seq}_{src}_{ref}.npz` pair files that `python -m rdmnet_amd.infer` wrote into DIR (ordered and filtered as
 `python -m rdmnet_amd.eval` reads them) and, per sequence, chains the pair poses into a trajectory as
@@ -21,7 +22,10 @@ fewer voxels, so voxels and points per voxel of the two variants are a check of 
 count is blind to small pose errors (they thicken the surfaces inside the voxels long before they spill into new ones), so with
 --map-sharpness the map also keeps per-voxel second moments and every `map:` line is followed by a `sharpness:` line: the mean
 plane thickness (root of the mean smallest covariance eigenvalue) and the mean map entropy over the voxels with at least
---map-sharpness-min-points points; lower is sharper for both."""
+--map-sharpness-min-points points; lower is sharper for both.  With --map-refine the per-voxel Gaussians are also used to improve
+the poses: every frame is registered against the map of the frames before it (`ops.VoxelMap.register`: point-to-distribution, the
+NDT / voxelised-GICP family) and then fused into that map -- `refine_against_map` -- from the optimised poses with --optimize, else
+the chained ones; the result is a third variant, `refined`, with its own error, pose file, map and sharpness lines."""
 import argparse
 import math
 import os
@@ -168,6 +172,7 @@ def write_kitti_poses(path, poses):
 # ---- the map of a run ------------------------------------------------------------------------------------------------------
 
 MAP_DEFAULTS = dict(voxel=0.3, min_points=1, batch=64, sharpness_min_points=4)
+REFINE_DEFAULTS = dict(sigma=0.02, neighbors=1, iterations=30, min_points=4)
 
 
 def build_map(paths, poses, voxel=MAP_DEFAULTS['voxel'], channels=None, min_range=0.0, max_range=math.inf, batch=MAP_DEFAULTS['batch'],
@@ -222,10 +227,61 @@ def sharpness_line(seq, what, min_points, report):
             f"{report['plane_thickness'] * 1e3:.3f} mm, entropy {report['entropy']:.4f} ({report['degenerate']} degenerate)")
 
 
-def write_map(args, seq, what, paths, poses, emit):
+def refine_against_map(paths, poses, voxel=MAP_DEFAULTS['voxel'], channels=None, min_range=0.0, max_range=math.inf,
+                       sigma=REFINE_DEFAULTS['sigma'], neighbors=REFINE_DEFAULTS['neighbors'], max_iteration=REFINE_DEFAULTS['iterations'],
+                       min_points=REFINE_DEFAULTS['min_points'], capacity=1 << 20, device='cuda'):
+    """Sequential scan-to-map refinement of the trajectory `poses` ([n, 4, 4]) of the scans `paths` (as build_map reads them): frame
+    0 keeps its pose and is integrated into a map with moments; every later frame k starts from refined[k - 1] inv(poses[k - 1])
+    poses[k] -- the previous frame's correction carried forward --, is registered against the map so far (ops.VoxelMap.register)
+    and integrated under the result.  A degenerate frame (status 2: no correspondence, or a singular system) keeps its initial
+    pose.  The scans are read on a background thread, one ahead.  -> (refined float64 [n, 4, 4], the ops.VoxelMap of all frames
+    under the refined poses, dict(frames, iterations [n], correspondences [n], status [n], degenerate)); frame 0 has status -1."""
+    paths = list(paths)
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    if len(paths) != len(poses):
+        raise ValueError(f'refine_against_map: {len(paths)} scans and {len(poses)} poses')
+    for path in paths:
+        if not osp.isfile(path):
+            raise TrajectoryError(f'{path}: no such scan file')
+    import torch
+    from . import ops, prepare
+    refined = poses.copy()
+    n = len(paths)
+    iterations, corr, status = np.zeros(n, np.int64), np.zeros(n, np.int64), np.full(n, -1, np.int64)
+    vmap = None
+    for k, cloud in prepare._read_ahead(lambda k: prepare.load_scan(paths[k]), list(range(n))):
+        if cloud.ndim != 2 or cloud.shape[1] < 3:
+            raise TrajectoryError(f'{paths[k]}: shape {cloud.shape}, expected [N, >= 3]')
+        if vmap is None:
+            width = cloud.shape[1] if channels is None else int(channels)
+            vmap = ops.VoxelMap(voxel, channels=min(width, 8), capacity=capacity, device=device, moments=True)
+        if cloud.shape[1] < vmap.channels:
+            raise TrajectoryError(f'{paths[k]}: {cloud.shape[1]} columns, the map has {vmap.channels} channels')
+        points = torch.from_numpy(np.ascontiguousarray(cloud)).to(vmap.device)
+        if k > 0:
+            init = refined[k - 1] @ np.linalg.inv(poses[k - 1]) @ poses[k]
+            res = vmap.register([points], init[None], sigma=sigma, min_points=min_points, neighbors=neighbors, max_iteration=max_iteration,
+                                min_range=min_range, max_range=max_range)
+            iterations[k], corr[k], status[k] = torch.stack([res.iterations, res.num_correspondences, res.status]).cpu().numpy()[:, 0]
+            refined[k] = init if status[k] == 2 else res.transformations[0].cpu().numpy()
+        vmap.integrate([points], refined[k][None], min_range, max_range)
+    if vmap is None:
+        vmap = ops.VoxelMap(voxel, channels=4 if channels is None else int(channels), capacity=capacity, device=device, moments=True)
+    return refined, vmap, dict(frames=n, iterations=iterations, correspondences=corr, status=status, degenerate=int((status == 2).sum()))
+
+
+def refine_line(seq, stats):
+    moved = max(stats['frames'] - 1, 1)
+    return (f"seq {seq} refined against the map: {stats['frames']} frames, {stats['iterations'].sum() / moved:.2f} iterations and "
+            f"{stats['correspondences'].sum() / moved:.0f} correspondences per frame, {stats['degenerate']} degenerate frames")
+
+
+def write_map(args, seq, what, paths, poses, emit, vmap=None):
+    """vmap: the map of these scans under these poses when the caller has built it already (the refinement's)."""
     lo, hi = args.map_range if args.map_range else (0.0, math.inf)
     sharpness = bool(getattr(args, 'map_sharpness', False))
-    vmap = build_map(paths, poses, voxel=args.map_voxel, min_range=lo, max_range=hi, batch=args.map_batch, moments=sharpness)
+    if vmap is None:
+        vmap = build_map(paths, poses, voxel=args.map_voxel, min_range=lo, max_range=hi, batch=args.map_batch, moments=sharpness)
     points, counts, _ = vmap.extract(args.map_min_points)
     points, counts = points.cpu().numpy(), counts.cpu().numpy()
     np.save(osp.join(args.out, f'{seq}_{what}_map.npy'), np.concatenate([points, counts[:, None].astype(np.float32)], 1))
@@ -236,6 +292,15 @@ def write_map(args, seq, what, paths, poses, emit):
 
 def map_paths(args, seqs):
     """{seq: the scan file of every chain frame}, after the checks that need no GPU."""
+    refine = bool(getattr(args, 'map_refine', False))
+    if refine and not (getattr(args, 'map_scans', None) and args.out):
+        raise TrajectoryError('--map-refine needs --map-scans and --out (the frames are registered against the map of the scans)')
+    if not refine:
+        for flag, key in (('--map-refine-sigma', 'sigma'), ('--map-refine-neighbors', 'neighbors'), ('--map-refine-iterations', 'iterations')):
+            if getattr(args, 'map_refine_' + key, None) not in (None, REFINE_DEFAULTS[key]):
+                raise TrajectoryError(f'{flag} needs --map-refine')
+    elif not (args.map_refine_sigma > 0 and math.isfinite(args.map_refine_sigma)) or args.map_refine_iterations < 0:
+        raise TrajectoryError('--map-refine-sigma must be > 0 and --map-refine-iterations >= 0')
     if not getattr(args, 'map_scans', None):
         if getattr(args, 'map_sharpness', False):
             raise TrajectoryError('--map-sharpness needs --map-scans (the report is taken over the map of the scans)')
@@ -279,7 +344,22 @@ def run(args, emit=print):
             write_kitti_poses(osp.join(args.out, f'{seq}_chained.txt'), graphs[seq][0])
         if scans:
             write_map(args, seq, 'chained', scans[seq], graphs[seq][0], emit)
+
+    def refine(seq, base):
+        lo, hi = args.map_range if args.map_range else (0.0, math.inf)
+        refined, vmap, stats = refine_against_map(scans[seq], base, voxel=args.map_voxel, min_range=lo, max_range=hi,
+                                                  sigma=args.map_refine_sigma, neighbors=args.map_refine_neighbors,
+                                                  max_iteration=args.map_refine_iterations)
+        if seq in gts:
+            emit(report_line(seq, 'refined', absolute_trajectory_error(refined[1:], gts[seq])))
+        emit(refine_line(seq, stats))
+        write_kitti_poses(osp.join(args.out, f'{seq}_refined.txt'), refined)
+        write_map(args, seq, 'refined', scans[seq], refined, emit, vmap=vmap)
+
     if not args.optimize:
+        if getattr(args, 'map_refine', False):
+            for seq in seqs:
+                refine(seq, graphs[seq][0])
         return None
     if not graphs:
         raise TrajectoryError(f'{args.features_root}: no pair files to optimise')
@@ -305,6 +385,8 @@ def run(args, emit=print):
             write_kitti_poses(osp.join(args.out, f'{seq}_optimized.txt'), nodes[noff[g]:noff[g + 1]])
         if scans:
             write_map(args, seq, 'optimized', scans[seq], nodes[noff[g]:noff[g + 1]], emit)
+        if getattr(args, 'map_refine', False):
+            refine(seq, nodes[noff[g]:noff[g + 1]])
     return res
 
 
@@ -336,6 +418,15 @@ def make_parser():
                          'entropy of that map (needs --map-scans); lower is sharper')
     ap.add_argument('--map-sharpness-min-points', type=int, default=MAP_DEFAULTS['sharpness_min_points'], metavar='N',
                     help='take the sharpness report over the voxels with at least N >= 2 points')
+    ap.add_argument('--map-refine', action='store_true',
+                    help='register every frame against the voxel map of the frames before it and fuse it under the result: a third '
+                         'variant, `refined`, from the optimised poses with --optimize, else the chained (needs --map-scans and --out)')
+    ap.add_argument('--map-refine-sigma', type=float, default=REFINE_DEFAULTS['sigma'], metavar='S',
+                    help='the noise of a scan point in metres, added to every voxel covariance')
+    ap.add_argument('--map-refine-neighbors', type=int, choices=(1, 7), default=REFINE_DEFAULTS['neighbors'],
+                    help="a point is matched to its own voxel (1) or to it and its six face neighbours (7: a wider basin)")
+    ap.add_argument('--map-refine-iterations', type=int, default=REFINE_DEFAULTS['iterations'], metavar='N',
+                    help='at most N Gauss-Newton updates per frame')
     return ap
 
 

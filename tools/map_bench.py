@@ -1,7 +1,7 @@
 """Times the voxel map (ops.VoxelMap) on synthetic scans along a synthetic drive.
 
   python tools/map_bench.py [--frames 256] [--points 120000 | 18000] [--reps 3] [--batch 64] [--voxel 0.3] [--cpu] [--cpu-frames 8]
-                              [--moments]
+                              [--moments] [--register]
 Prints one JSON line per case:
   * integrate: --frames scans of --points points (120 000: a raw scan; 18 000: a down-sampled one), xyz + intensity, integrated in
     batches of --batch from device memory into a table created large enough (no growth inside the timing); device time between
@@ -14,6 +14,12 @@ Prints one JSON line per case:
   * with --moments: the same integrate into a map with the nine second-moment sums beside it (ops.VoxelMap(moments=True): 14 integer
     atomic adds a point instead of 5, (8 C + 4 + 72) B), its points/s and the ratio to the plain integrate of the same run, and
     the ms of extract_moments (select, sort, covariance and the Jacobi eigen-solver per voxel);
+  * with --register (and nothing else of the above): the scan-to-map registration (ops.VoxelMap.register) at neighbors 1 and 7 for both
+    scan shapes (120 000 and 18 000 points), against the map with moments of min(--frames, 64) scans, from poses 5 cm / 5 mrad off: ms
+    per evaluation (max_iteration = 0, one scan), ms per full registration of one scan and of a batch of 64 scans (default
+    tolerances), the point-voxel pairs per second of the evaluation, and ms per iteration (accumulate + finalize launches) from runs
+    of 4 and 12 forced updates of the batch; with --cpu also the seconds of one evaluation by tests/voxel_register_restatement.py
+    and whether its counts equal the GPU's;
   * with --cpu: the NumPy restatement (tests/voxel_map_restatement.py) on the first --cpu-frames scans, its points/s, and whether the
     GPU's map of the same scans equals it bit for bit."""
 import argparse
@@ -76,6 +82,55 @@ def drive(frames, step=1.0):
     return poses
 
 
+def register_cases(a):
+    import torch
+    from rdmnet_amd import ops
+    rng = np.random.default_rng(0)
+    frames = max(min(a.frames, 64), 1)
+    for points in (120000, 18000):
+        cloud, poses = synthetic_scans(frames, points), drive(frames)
+        clouds = [cloud[k * points:(k + 1) * points] for k in range(frames)]
+        vmap = ops.VoxelMap(a.voxel, channels=4, capacity=1 << 24, moments=True).integrate(clouds, poses)
+        off = poses.copy()
+        for X in off:
+            w = rng.normal(0.0, 0.005, 3)
+            K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+            X[:3, :3] = (np.eye(3) + K + 0.5 * K @ K) @ X[:3, :3]
+            X[:3, 3] += rng.normal(0.0, 0.05, 3)
+        batch = [clouds[k % frames] for k in range(64)]
+        Xb = np.stack([off[k % frames] for k in range(64)])
+        for neighbors in (1, 7):
+            kw = dict(neighbors=neighbors)
+            ms_eval, ev = timed(lambda: vmap.register(clouds[:1], off[:1], max_iteration=0, **kw), a.reps)
+            ms_one, one = timed(lambda: vmap.register(clouds[:1], off[:1], **kw), a.reps)
+            ms_batch, many = timed(lambda: vmap.register(batch, Xb, **kw), a.reps)
+            ms_4, _ = timed(lambda: vmap.register(batch, Xb, max_iteration=4, rot_eps=0.0, trans_eps=0.0, **kw), a.reps)
+            ms_12, _ = timed(lambda: vmap.register(batch, Xb, max_iteration=12, rot_eps=0.0, trans_eps=0.0, **kw), a.reps)
+            pairs = int(ev.num_correspondences[0])
+            line = {'case': 'register', 'points_per_scan': points, 'neighbors': neighbors, 'voxel': a.voxel, 'map_frames': frames,
+                    'voxels': len(vmap), 'ms_per_evaluation': round(ms_eval, 3), 'pairs_per_evaluation': pairs,
+                    'pairs_per_s': round(pairs / ms_eval * 1e3), 'ms_one_scan': round(ms_one, 3), 'iterations_one_scan': int(one.iterations[0]),
+                    'status_one_scan': int(one.status[0]), 'ms_batch_of_64': round(ms_batch, 3),
+                    'mean_iterations_batch': round(float(many.iterations.double().mean()), 2),
+                    'converged_in_batch': int((many.status == 1).sum()),
+                    'ms_per_iteration_batch_of_64': round((ms_12 - ms_4) / 8.0, 4),
+                    'pairs_per_s_batch': round(float(many.num_correspondences.sum()) / ((ms_12 - ms_4) / 8.0) * 1e3)}
+            if a.cpu:
+                import voxel_moments_restatement as MR
+                import voxel_register_restatement as RR
+                m = min(a.cpu_frames, frames)
+                table = MR.build([c.cpu().numpy() for c in clouds[:m]], poses[:m], a.voxel, 4)
+                small = ops.VoxelMap(a.voxel, channels=4, moments=True).integrate(clouds[:m], poses[:m])
+                got = small.register(clouds[:1], off[:1], max_iteration=0, **kw)
+                t0 = time.perf_counter()
+                e = RR.evaluate(table, clouds[0].cpu().numpy(), off[0], 0.02, 4, neighbors)
+                line.update(cpu_s_per_evaluation=round(time.perf_counter() - t0, 4), cpu_map_frames=m,
+                            counts_equal=bool(int(got.num_correspondences[0]) == e['n_corr'] and int(got.num_points[0]) == e['n_points']))
+            print(json.dumps(line), flush=True)
+        del vmap
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--frames', type=int, default=256)
@@ -84,12 +139,15 @@ def main(argv=None):
     ap.add_argument('--batch', type=int, default=64, help='scans per integrate call')
     ap.add_argument('--voxel', type=float, default=0.3)
     ap.add_argument('--moments', action='store_true', help='also time integrate and extract with the per-voxel second moments')
+    ap.add_argument('--register', action='store_true', help='time the scan-to-map registration and nothing else')
     ap.add_argument('--cpu', action='store_true', help='also time the NumPy restatement and compare the maps bit for bit')
     ap.add_argument('--cpu-frames', type=int, default=8)
     a = ap.parse_args(argv)
     import torch
     from rdmnet_amd import _lib, ops
     assert torch.cuda.is_available(), 'map_bench needs a GPU'
+    if a.register:
+        return register_cases(a)
     C = 4
     cloud, poses = synthetic_scans(a.frames, a.points), drive(a.frames)
     total = a.frames * a.points
