@@ -20,9 +20,14 @@
 //
 // Moments (include/rdmnet_hip.h, "voxel moments"; tests/voxel_moments_restatement.py): a second caller-owned block of nine int64
 // sums per slot, addressed by the map's slot index -- the first and second moments of the 12-bit local coordinates u_d, so every
-// voxel gets a mean, a covariance and a normal.  integrate_moments_kernel is the integrate kernel with nine more integer adds into
-// the slot that find_or_claim returned; the plain kernel is the same body with that block compiled out.  Extraction shares the
+// voxel gets a mean, a covariance and a normal.  integrate_kernel<true> is the integrate kernel with nine more integer adds into
+// the slot that find_or_claim returned; integrate_kernel<false>, the plain one, is the same body with that block compiled out.  Extraction shares the
 // selection and the sort and solves the 3 x 3 symmetric eigenproblem per row with a float64 cyclic Jacobi of kSweeps sweeps.
+//
+// Three pinned definitions are written once: the point gate (gate_sensor, gate_world; integrate and register), the key (pack_key,
+// key_cell; integrate, register, extract) and the voxel Gaussian (voxel_gaussian; both extracts and register).  `#pragma clang fp
+// contract(off)` is lexical and does not follow an inlined callee: every helper with pinned arithmetic opens with it itself, and
+// jacobi3 and rodrigues, which stand outside any such block, stay there.
 #include <cmath>
 
 #include "../../include/rdmnet_hip.h"
@@ -124,6 +129,81 @@ __global__ void __launch_bounds__(kBlock) reset_kernel(Table t, long long capaci
   }
 }
 
+// The key of a cell: the three cells + 2^20 at 21 bits each, x highest, so keys ascend with (cell x, cell y, cell z).
+__device__ __forceinline__ unsigned long long pack_key(long long cx, long long cy, long long cz) {
+  return (static_cast<unsigned long long>(cx + kHalf) << 42) | (static_cast<unsigned long long>(cy + kHalf) << 21) |
+         static_cast<unsigned long long>(cz + kHalf);
+}
+
+__device__ __forceinline__ long long key_cell(unsigned long long key, int d) {
+  return static_cast<long long>((key >> (21 * (2 - d))) & 0x1fffffull) - kHalf;
+}
+
+// The point gate of integrate and register, in two steps so that a row's pose can be looked up behind the sensor-frame verdicts.  A
+// verdict is the counter that integrate tallies the row in.  Sensor frame: the row's values into v (zeros beyond `channels`) ->
+// kNonfinite, kRange (lo2 <= |xyz|^2 <= hi2 fails) or kPass.
+constexpr int kPass = kIntegrated;
+__device__ __forceinline__ int gate_sensor(const float* __restrict__ p, int channels, double lo2, double hi2, float (&v)[kMaxC]) {
+#pragma clang fp contract(off)
+  bool finite = true;
+  for (int c = 0; c < kMaxC; ++c) {
+    v[c] = c < channels ? p[c] : 0.f;
+    finite = finite && isfinite(v[c]);
+  }
+  if (!finite) return kNonfinite;
+  const double x = v[0], y = v[1], z = v[2];
+  const double r2 = (x * x + y * y) + z * z;
+  return lo2 <= r2 && r2 <= hi2 ? kPass : kRange;
+}
+
+// World frame, after kPass above: wd = X v (X: the first 12 doubles of a row-major 4 x 4) with the restatement's association, q = the
+// fixed-point coordinates and attributes (meaningful on kPass) -> kExtent (a cell outside [-2^20, 2^20) or |attribute| >= 2^20) or kPass.
+__device__ __forceinline__ int gate_world(const float (&v)[kMaxC], const double* __restrict__ X, double voxel, double (&wd)[3],
+                                          long long (&q)[kMaxC]) {
+#pragma clang fp contract(off)
+  const double x = v[0], y = v[1], z = v[2];
+  bool inside = true;
+  for (int d = 0; d < 3; ++d) {
+    wd[d] = ((X[4 * d] * x + X[4 * d + 1] * y) + X[4 * d + 2] * z) + X[4 * d + 3];
+    const double f = floor(wd[d] / voxel * kScale);
+    const bool ok = f >= -kQLimit && f < kQLimit;  // (NaN and infinities fail)
+    inside = inside && ok;
+    q[d] = ok ? static_cast<long long>(f) : 0ll;
+  }
+  for (int c = 3; c < kMaxC; ++c) {
+    const double a = v[c];
+    inside = inside && fabs(a) < kScale;
+    q[c] = llrint(a * kScale);  // (finite)
+  }
+  return inside ? kPass : kExtent;
+}
+
+// The Gaussian of an occupied slot: the count, the world mean of the three coordinate sums in metres and, with kCov, the population
+// covariance {xx, xy, xz, yy, yz, zz} in m^2 from the slot's nine moments.
+struct Gaussian {
+  uint32_t count;
+  double mean[3], cov[6];
+};
+
+template <bool kCov>
+__device__ __forceinline__ Gaussian voxel_gaussian(const Table& t, const unsigned long long* __restrict__ moments, long long capacity,
+                                                   double voxel, long long slot) {
+#pragma clang fp contract(off)
+  Gaussian g;
+  g.count = t.counts[slot];
+  const double n = static_cast<double>(g.count);
+  for (int d = 0; d < 3; ++d) g.mean[d] = static_cast<double>(static_cast<long long>(t.sums[d * capacity + slot])) / n / kScale * voxel;
+  if constexpr (kCov) {
+    const double s = voxel / kMomSteps, s2 = s * s;
+    double S[kPlanes];
+    for (int k = 0; k < kPlanes; ++k) S[k] = static_cast<double>(static_cast<long long>(moments[moment_at(slot, k, capacity)]));
+    const double m[3] = {S[0] / n, S[1] / n, S[2] / n};
+    for (int a = 0, k = 0; a < 3; ++a)
+      for (int b = a; b < 3; ++b, ++k) g.cov[k] = (S[3 + k] / n - m[a] * m[b]) * s2;
+  }
+  return g;
+}
+
 // the number of offsets[1 .. n_scans] that are <= i: the scan of row i when offsets ascend (empty scans are passed over)
 __device__ __forceinline__ long long scan_of(const int64_t* __restrict__ offsets, long long n_scans, long long i) {
   long long lo = 0, n = n_scans;
@@ -139,13 +219,12 @@ __device__ __forceinline__ long long scan_of(const int64_t* __restrict__ offsets
   return lo;
 }
 
-// The body of both integrate kernels.  kMoments = false is the plain integrate: `moments` is unused and every moments statement
-// is compiled out.
+// Both integrate kernels.  kMoments = false is the plain integrate: `moments` is unused and every moments statement is compiled out.
 template <bool kMoments>
-__device__ __forceinline__ void integrate_points(Table t, unsigned long long* __restrict__ moments, long long capacity, int channels,
-                                                 double voxel, const float* __restrict__ points, long long ld, long long total,
-                                                 const int64_t* __restrict__ offsets, const double* __restrict__ poses,
-                                                 long long n_scans, double lo2, double hi2) {
+__global__ void __launch_bounds__(kBlock) integrate_kernel(Table t, unsigned long long* __restrict__ moments, long long capacity,
+                                                           int channels, double voxel, const float* __restrict__ points, long long ld,
+                                                           long long total, const int64_t* __restrict__ offsets,
+                                                           const double* __restrict__ poses, long long n_scans, double lo2, double hi2) {
 #pragma clang fp contract(off)
   __shared__ unsigned int tally[kStats];
   if (threadIdx.x < kStats) tally[threadIdx.x] = 0u;
@@ -155,48 +234,21 @@ __device__ __forceinline__ void integrate_points(Table t, unsigned long long* __
   begin = begin < 0 ? 0 : begin;
   end = end > total ? total : end;  // (a bad offsets array reads nothing outside the batch)
   for (long long i = begin + static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < end; i += stride) {
-    const float* p = points + i * ld;
     float v[kMaxC];
-    bool finite = true;
-    for (int c = 0; c < kMaxC; ++c) {
-      v[c] = c < channels ? p[c] : 0.f;
-      finite = finite && isfinite(v[c]);
-    }
-    if (!finite) {
-      atomicAdd(&tally[kNonfinite], 1u);
-      continue;
-    }
-    const double x = v[0], y = v[1], z = v[2];
-    const double r2 = (x * x + y * y) + z * z;
-    if (!(lo2 <= r2 && r2 <= hi2)) {
-      atomicAdd(&tally[kRange], 1u);
-      continue;
-    }
-    const long long scan = scan_of(offsets, n_scans, i);
-    if (scan >= n_scans) continue;  // (offsets that do not ascend)
-    const double* X = poses + scan * 16;
+    double wd[3];
     long long q[kMaxC];
-    bool inside = true;
-    unsigned long long key = 0ull;
-    for (int d = 0; d < 3; ++d) {
-      const double w = ((X[4 * d] * x + X[4 * d + 1] * y) + X[4 * d + 2] * z) + X[4 * d + 3];
-      const double f = floor(w / voxel * kScale);
-      const bool ok = f >= -kQLimit && f < kQLimit;  // (NaN and infinities fail)
-      inside = inside && ok;
-      q[d] = ok ? static_cast<long long>(f) : 0ll;
-      key = (key << 21) | static_cast<unsigned long long>((q[d] >> kFrac) + kHalf);
+    int verdict = gate_sensor(points + i * ld, channels, lo2, hi2, v);
+    if (verdict == kPass) {
+      const long long scan = scan_of(offsets, n_scans, i);
+      if (scan >= n_scans) continue;  // (offsets that do not ascend)
+      verdict = gate_world(v, poses + scan * 16, voxel, wd, q);
     }
-    for (int c = 3; c < kMaxC; ++c) {
-      const double a = v[c];
-      inside = inside && fabs(a) < kScale;
-      q[c] = llrint(a * kScale);  // (finite; used only when inside)
-    }
-    if (!inside) {
-      atomicAdd(&tally[kExtent], 1u);
+    if (verdict != kPass) {
+      atomicAdd(&tally[verdict], 1u);
       continue;
     }
     int claimed;
-    const long long slot = find_or_claim(t.keys, capacity, key, &claimed);
+    const long long slot = find_or_claim(t.keys, capacity, pack_key(q[0] >> kFrac, q[1] >> kFrac, q[2] >> kFrac), &claimed);
     if (slot < 0) {
       atomicAdd(&tally[kDropped], 1u);
       continue;
@@ -218,21 +270,6 @@ __device__ __forceinline__ void integrate_points(Table t, unsigned long long* __
   __syncthreads();
   if (threadIdx.x < kStats && tally[threadIdx.x] != 0u)
     atomicAdd(t.counters + threadIdx.x, static_cast<unsigned long long>(tally[threadIdx.x]));
-}
-
-__global__ void __launch_bounds__(kBlock) integrate_kernel(Table t, long long capacity, int channels, double voxel,
-                                                           const float* __restrict__ points, long long ld, long long total,
-                                                           const int64_t* __restrict__ offsets, const double* __restrict__ poses,
-                                                           long long n_scans, double lo2, double hi2) {
-  integrate_points<false>(t, nullptr, capacity, channels, voxel, points, ld, total, offsets, poses, n_scans, lo2, hi2);
-}
-
-__global__ void __launch_bounds__(kBlock) integrate_moments_kernel(Table t, unsigned long long* __restrict__ moments, long long capacity,
-                                                                   int channels, double voxel, const float* __restrict__ points,
-                                                                   long long ld, long long total, const int64_t* __restrict__ offsets,
-                                                                   const double* __restrict__ poses, long long n_scans, double lo2,
-                                                                   double hi2) {
-  integrate_points<true>(t, moments, capacity, channels, voxel, points, ld, total, offsets, poses, n_scans, lo2, hi2);
 }
 
 __global__ void __launch_bounds__(kBlock) moments_reset_kernel(unsigned long long* __restrict__ moments, long long words) {
@@ -313,15 +350,16 @@ __global__ void __launch_bounds__(kBlock) emit_kernel(Table t, long long capacit
   if (first == 0) *n_rows = m;
   const long long rows = m < max_rows ? m : max_rows;
   for (long long r = first; r < rows; r += stride) {
-    const unsigned long long key = keys[r];
     const long long slot = slots[r];
-    const uint32_t n = t.counts[slot];
-    counts[r] = static_cast<int32_t>(n);
-    for (int d = 0; d < 3; ++d) cells[3 * r + d] = static_cast<int32_t>(static_cast<long long>((key >> (21 * (2 - d))) & 0x1fffffull) - kHalf);
-    for (int c = 0; c < channels; ++c) {
-      const double mean = static_cast<double>(static_cast<long long>(t.sums[c * capacity + slot])) / static_cast<double>(n) / kScale;
-      points[r * channels + c] = static_cast<float>(c < 3 ? mean * voxel : mean);
+    const Gaussian g = voxel_gaussian<false>(t, nullptr, capacity, voxel, slot);
+    counts[r] = static_cast<int32_t>(g.count);
+    for (int d = 0; d < 3; ++d) {
+      cells[3 * r + d] = static_cast<int32_t>(key_cell(keys[r], d));
+      points[r * channels + d] = static_cast<float>(g.mean[d]);
     }
+    for (int c = 3; c < channels; ++c)  // an attribute's mean is not scaled by the voxel
+      points[r * channels + c] =
+          static_cast<float>(static_cast<double>(static_cast<long long>(t.sums[c * capacity + slot])) / static_cast<double>(g.count) / kScale);
   }
 }
 
@@ -386,25 +424,15 @@ __global__ void __launch_bounds__(kBlock) emit_moments_kernel(Table t, const uns
   const long long m = static_cast<long long>(*n_sel);
   if (first == 0) *n_rows = m;
   const long long rows = m < max_rows ? m : max_rows;
-  const double s = voxel / kMomSteps, s2 = s * s;
   for (long long r = first; r < rows; r += stride) {
     const long long slot = slots[r];
-    const double n = static_cast<double>(t.counts[slot]);
-    double S[kPlanes];
-    for (int k = 0; k < kPlanes; ++k) {
-      const long long v = static_cast<long long>(moments[moment_at(slot, k, capacity)]);
-      if (sums != nullptr) sums[r * kPlanes + k] = v;
-      S[k] = static_cast<double>(v);
-    }
-    const double mean[3] = {S[0] / n, S[1] / n, S[2] / n};
-    double c[6];
-    int k = 0;
-    for (int a = 0; a < 3; ++a)
-      for (int b = a; b < 3; ++b, ++k) c[k] = (S[3 + k] / n - mean[a] * mean[b]) * s2;
+    if (sums != nullptr)
+      for (int k = 0; k < kPlanes; ++k) sums[r * kPlanes + k] = static_cast<long long>(moments[moment_at(slot, k, capacity)]);
+    const Gaussian g = voxel_gaussian<true>(t, moments, capacity, voxel, slot);
     double eig[3], normal[3];
-    jacobi3(c, eig, normal);
-    for (k = 0; k < 6; ++k) cov[r * 6 + k] = c[k];
-    for (k = 0; k < 3; ++k) {
+    jacobi3(g.cov, eig, normal);
+    for (int k = 0; k < 6; ++k) cov[r * 6 + k] = g.cov[k];
+    for (int k = 0; k < 3; ++k) {
       eigenvalues[r * 3 + k] = eig[k];
       normals[r * 3 + k] = normal[k];
     }
@@ -449,15 +477,15 @@ int open_table(const char* what, void* map, size_t map_bytes, int64_t capacity, 
   return RDM_OK;
 }
 
-
-// the moments block of a caller, or the error code after set_error
-int open_moments(const char* what, void* moments, size_t moments_bytes, int64_t capacity, unsigned long long*& m) {
+// the moments block of a caller, or the error code after set_error (`too_small`: the code for a block that is too small)
+int open_moments(const char* what, const void* moments, size_t moments_bytes, int64_t capacity, unsigned long long*& m,
+                 int too_small = RDM_ERR_WORKSPACE) {
   RDM_REQUIRE(moments != nullptr, "%s: null moments block", what);
-  Arena ar(moments, moments_bytes);
+  Arena ar(const_cast<void*>(moments), moments_bytes);
   m = ar.take<unsigned long long>(static_cast<size_t>(capacity) * kPlanes);
   if (!ar.ok) {
     set_error("%s: the moments block is too small (%zu < %zu bytes)", what, moments_bytes, ar.off);
-    return RDM_ERR_WORKSPACE;
+    return too_small;
   }
   return RDM_OK;
 }
@@ -529,52 +557,23 @@ __global__ void __launch_bounds__(kBlock) register_accumulate_kernel(Table t, co
 #pragma unroll
   for (int k = 0; k < kRegSums; ++k) acc[k] = 0.0;
   int n_corr = 0, n_pass = 0;
-  const double s = voxel / kMomSteps, s2 = s * s;
   for (long long i = begin + group * kBlock + threadIdx.x; i < end; i += static_cast<long long>(kRegGroups) * kBlock) {
-    const float* p = points + i * ld;
-    bool finite = true, inside = true;
-    for (int c = 0; c < kMaxC; ++c) {
-      const float v = c < channels ? p[c] : 0.f;
-      finite = finite && isfinite(v);
-      if (c >= 3) inside = inside && fabs(static_cast<double>(v)) < kScale;
-    }
-    if (!finite) continue;
-    const double x = p[0], y = p[1], z = p[2];
-    const double r2 = (x * x + y * y) + z * z;
-    if (!(lo2 <= r2 && r2 <= hi2)) continue;
+    float v[kMaxC];
     double wd[3];
-    long long cell[3];
-    for (int d = 0; d < 3; ++d) {
-      wd[d] = ((X[4 * d] * x + X[4 * d + 1] * y) + X[4 * d + 2] * z) + X[4 * d + 3];
-      const double f = floor(wd[d] / voxel * kScale);
-      const bool ok = f >= -kQLimit && f < kQLimit;  // (NaN and infinities fail)
-      inside = inside && ok;
-      cell[d] = (ok ? static_cast<long long>(f) : 0ll) >> kFrac;
-    }
-    if (!inside) continue;
+    long long fixed[kMaxC];
+    if (gate_sensor(points + i * ld, channels, lo2, hi2, v) != kPass || gate_world(v, X, voxel, wd, fixed) != kPass) continue;
     ++n_pass;
+    const long long cell[3] = {fixed[0] >> kFrac, fixed[1] >> kFrac, fixed[2] >> kFrac};
     const double q0 = wd[0] - X[3], q1 = wd[1] - X[7], q2 = wd[2] - X[11];
     for (int o = 0; o < neighbors; ++o) {  // (0,0,0), (-1,0,0), (+1,0,0), (0,-1,0), (0,+1,0), (0,0,-1), (0,0,+1)
       long long c[3] = {cell[0], cell[1], cell[2]};
       if (o > 0) c[(o - 1) >> 1] += (o & 1) ? -1 : 1;
       if (c[0] < -kHalf || c[0] >= kHalf || c[1] < -kHalf || c[1] >= kHalf || c[2] < -kHalf || c[2] >= kHalf) continue;
-      const unsigned long long key = (static_cast<unsigned long long>(c[0] + kHalf) << 42) |
-                                     (static_cast<unsigned long long>(c[1] + kHalf) << 21) | static_cast<unsigned long long>(c[2] + kHalf);
-      const long long slot = find(t.keys, capacity, key);
-      if (slot < 0) continue;
-      const uint32_t count = t.counts[slot];
-      if (count < min_points) continue;
-      const double n = static_cast<double>(count);
-      double S[kPlanes];
-#pragma unroll
-      for (int k = 0; k < kPlanes; ++k) S[k] = static_cast<double>(static_cast<long long>(moments[moment_at(slot, k, capacity)]));
-      double r[3];
-#pragma unroll
-      for (int d = 0; d < 3; ++d)
-        r[d] = wd[d] - static_cast<double>(static_cast<long long>(t.sums[d * capacity + slot])) / n / kScale * voxel;
-      const double m0 = S[0] / n, m1 = S[1] / n, m2 = S[2] / n;
-      const double a00 = (S[3] / n - m0 * m0) * s2 + sigma2, a01 = (S[4] / n - m0 * m1) * s2, a02 = (S[5] / n - m0 * m2) * s2;
-      const double a11 = (S[6] / n - m1 * m1) * s2 + sigma2, a12 = (S[7] / n - m1 * m2) * s2, a22 = (S[8] / n - m2 * m2) * s2 + sigma2;
+      const long long slot = find(t.keys, capacity, pack_key(c[0], c[1], c[2]));
+      if (slot < 0 || t.counts[slot] < min_points) continue;
+      const Gaussian G = voxel_gaussian<true>(t, moments, capacity, voxel, slot);
+      const double r[3] = {wd[0] - G.mean[0], wd[1] - G.mean[1], wd[2] - G.mean[2]};
+      const double a00 = G.cov[0] + sigma2, a01 = G.cov[1], a02 = G.cov[2], a11 = G.cov[3] + sigma2, a12 = G.cov[4], a22 = G.cov[5] + sigma2;
       // M = the inverse of the symmetric matrix a: cofactors over the determinant
       const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
       const double c11 = a00 * a22 - a02 * a02, c12 = a01 * a02 - a00 * a12, c22 = a00 * a11 - a01 * a01;
@@ -740,6 +739,64 @@ __global__ void __launch_bounds__(kBlock) register_finalize_kernel(RegWork w, in
   }
 }
 
+// ---- what the entry points share -----------------------------------------------------------------------------------------------
+
+// The batch arguments of integrate and register, or the error code after set_error.  max_scans: kMaxRegScans or no limit; empty_runs:
+// the entry point launches for n_scans > 0 even when the batch has no rows, so it reads offsets and poses then too.
+int check_batch(const char* what, double voxel, int channels, const float* points, int64_t ld, int64_t total, const int64_t* offsets,
+                const double* poses, int64_t n_scans, int64_t max_scans, bool empty_runs, double min_range, double max_range) {
+  RDM_REQUIRE(voxel > 0.0 && std::isfinite(voxel), "%s: voxel must be positive and finite", what);
+  RDM_REQUIRE(n_scans >= 0 && n_scans <= max_scans && total >= 0 && ld >= channels, "%s: bad sizes (ld must be >= channels%s)", what,
+              max_scans == kMaxRegScans ? ", n_scans <= 2^20" : "");
+  RDM_REQUIRE(min_range >= 0.0 && max_range >= min_range, "%s: need 0 <= min_range <= max_range", what);
+  const bool rows = n_scans > 0 && total > 0, scans = rows || (empty_runs && n_scans > 0);
+  RDM_REQUIRE((!rows || points) && (!scans || (offsets && poses)), "%s: null argument", what);
+  return RDM_OK;
+}
+
+// rdm_voxel_map_integrate (want_moments = false: `moments` is not looked at) and rdm_voxel_map_integrate_moments
+int integrate(const char* what, void* map, size_t map_bytes, int64_t capacity, int channels, double voxel, const float* points, int64_t ld,
+              int64_t total, const int64_t* offsets, const double* poses, int64_t n_scans, double min_range, double max_range,
+              bool want_moments, void* moments, size_t moments_bytes, void* stream) {
+  Table t;
+  unsigned long long* m = nullptr;
+  if (const int rc = open_table(what, map, map_bytes, capacity, channels, t)) return rc;
+  if (want_moments)
+    if (const int rc = open_moments(what, moments, moments_bytes, capacity, m)) return rc;
+  if (const int rc = check_batch(what, voxel, channels, points, ld, total, offsets, poses, n_scans, INT64_MAX, false, min_range, max_range))
+    return rc;
+  if (n_scans == 0 || total == 0) return RDM_OK;
+  hipLaunchKernelGGL(want_moments ? integrate_kernel<true> : integrate_kernel<false>, dim3(blocks_for(total)), dim3(kBlock), 0,
+                     static_cast<hipStream_t>(stream), t, m, capacity, channels, voxel, points, ld, total, offsets, poses, n_scans,
+                     min_range * min_range, max_range * max_range);
+  return launch_status(what);
+}
+
+unsigned int least_points(int64_t min_points) {  // (counts are uint32)
+  return min_points > 0xffffffffll ? 0xffffffffu : static_cast<unsigned int>(min_points);
+}
+
+// What both extracts do before they emit: the argument checks (outputs_ok: the entry point's own outputs are there), then the slots
+// with at least min_points points selected and sorted by key -> w.keys, w.slots and their number *w.n_sel on the device.
+int select_sorted(const char* what, const Table& t, int64_t capacity, double voxel, int64_t min_points, int64_t max_rows,
+                  const int64_t* n_rows, bool outputs_ok, void* ws, size_t ws_bytes, hipStream_t s, ExtractWork& w) {
+  RDM_REQUIRE(voxel > 0.0 && std::isfinite(voxel), "%s: voxel must be positive and finite", what);
+  RDM_REQUIRE(min_points >= 0 && max_rows >= 0 && n_rows != nullptr, "%s: bad min_points, max_rows or null n_rows", what);
+  RDM_REQUIRE(outputs_ok, "%s: null output", what);
+  Arena ar(ws, ws_bytes);
+  if (!carve_extract(ar, capacity, w)) {
+    set_error("%s: workspace too small (%zu < %zu bytes)", what, ws_bytes, ar.off);
+    return RDM_ERR_WORKSPACE;
+  }
+  fill_words<unsigned long long>(w.n_sel, 1, 0ull, s);
+  hipLaunchKernelGGL(select_kernel, dim3(blocks_for(capacity)), dim3(kBlock), 0, s, t, static_cast<long long>(capacity),
+                     least_points(min_points), w.keys_in, w.slots_in, w.n_sel);
+  size_t bytes = w.sort_bytes;
+  RDM_HIP_CHECK(rocprim::radix_sort_pairs(w.sort_tmp, bytes, w.keys_in, w.keys, w.slots_in, w.slots, static_cast<unsigned>(capacity), 0u,
+                                          64u, s));
+  return RDM_OK;
+}
+
 }  // namespace
 }  // namespace rdm
 
@@ -764,19 +821,8 @@ extern "C" int rdm_voxel_map_reset(void* map, size_t map_bytes, int64_t capacity
 extern "C" int rdm_voxel_map_integrate(void* map, size_t map_bytes, int64_t capacity, int channels, double voxel, const float* points,
                                        int64_t ld, int64_t total, const int64_t* offsets, const double* poses, int64_t n_scans,
                                        double min_range, double max_range, void* stream) {
-  using namespace rdm;
-  Table t;
-  if (const int rc = open_table("rdm_voxel_map_integrate", map, map_bytes, capacity, channels, t)) return rc;
-  RDM_REQUIRE(voxel > 0.0 && std::isfinite(voxel), "rdm_voxel_map_integrate: voxel must be positive and finite");
-  RDM_REQUIRE(n_scans >= 0 && total >= 0 && ld >= channels, "rdm_voxel_map_integrate: bad sizes (ld must be >= channels)");
-  RDM_REQUIRE(min_range >= 0.0 && max_range >= min_range, "rdm_voxel_map_integrate: need 0 <= min_range <= max_range");
-  if (n_scans == 0 || total == 0) return RDM_OK;
-  RDM_REQUIRE(points && offsets && poses, "rdm_voxel_map_integrate: null argument");
-  hipLaunchKernelGGL(integrate_kernel, dim3(blocks_for(total)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), t,
-                     static_cast<long long>(capacity), channels, voxel, points, static_cast<long long>(ld),
-                     static_cast<long long>(total), offsets, poses, static_cast<long long>(n_scans), min_range * min_range,
-                     max_range * max_range);
-  return launch_status("rdm_voxel_map_integrate");
+  return rdm::integrate("rdm_voxel_map_integrate", map, map_bytes, capacity, channels, voxel, points, ld, total, offsets, poses, n_scans,
+                        min_range, max_range, false, nullptr, 0, stream);
 }
 
 extern "C" int rdm_voxel_map_rehash(const void* old_map, size_t old_bytes, int64_t old_capacity, void* new_map, size_t new_bytes,
@@ -819,23 +865,11 @@ extern "C" int rdm_voxel_map_extract(const void* map, size_t map_bytes, int64_t 
   using namespace rdm;
   Table t;
   if (const int rc = open_table("rdm_voxel_map_extract", const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
-  RDM_REQUIRE(voxel > 0.0 && std::isfinite(voxel), "rdm_voxel_map_extract: voxel must be positive and finite");
-  RDM_REQUIRE(min_points >= 0 && max_rows >= 0 && n_rows != nullptr, "rdm_voxel_map_extract: bad min_points, max_rows or null n_rows");
-  RDM_REQUIRE(max_rows == 0 || (points && counts && cells), "rdm_voxel_map_extract: null output");
-  Arena ar(ws, ws_bytes);
-  ExtractWork w;
-  if (!carve_extract(ar, capacity, w)) {
-    set_error("rdm_voxel_map_extract: workspace too small (%zu < %zu bytes)", ws_bytes, ar.off);
-    return RDM_ERR_WORKSPACE;
-  }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const unsigned int least = min_points > 0xffffffffll ? 0xffffffffu : static_cast<unsigned int>(min_points);
-  fill_words<unsigned long long>(w.n_sel, 1, 0ull, s);
-  hipLaunchKernelGGL(select_kernel, dim3(blocks_for(capacity)), dim3(kBlock), 0, s, t, static_cast<long long>(capacity), least, w.keys_in,
-                     w.slots_in, w.n_sel);
-  size_t bytes = w.sort_bytes;
-  RDM_HIP_CHECK(rocprim::radix_sort_pairs(w.sort_tmp, bytes, w.keys_in, w.keys, w.slots_in, w.slots, static_cast<unsigned>(capacity), 0u,
-                                          64u, s));
+  ExtractWork w;
+  if (const int rc = select_sorted("rdm_voxel_map_extract", t, capacity, voxel, min_points, max_rows, n_rows,
+                                   max_rows == 0 || (points && counts && cells), ws, ws_bytes, s, w))
+    return rc;
   hipLaunchKernelGGL(emit_kernel, dim3(blocks_for(max_rows)), dim3(kBlock), 0, s, t, static_cast<long long>(capacity), channels, voxel,
                      w.keys, w.slots, w.n_sel, static_cast<long long>(max_rows), points, counts, cells, n_rows);
   return launch_status("rdm_voxel_map_extract");
@@ -866,21 +900,8 @@ extern "C" int rdm_voxel_map_integrate_moments(void* map, size_t map_bytes, int6
                                                const float* points, int64_t ld, int64_t total, const int64_t* offsets,
                                                const double* poses, int64_t n_scans, double min_range, double max_range, void* moments,
                                                size_t moments_bytes, void* stream) {
-  using namespace rdm;
-  Table t;
-  unsigned long long* m;
-  if (const int rc = open_table("rdm_voxel_map_integrate_moments", map, map_bytes, capacity, channels, t)) return rc;
-  if (const int rc = open_moments("rdm_voxel_map_integrate_moments", moments, moments_bytes, capacity, m)) return rc;
-  RDM_REQUIRE(voxel > 0.0 && std::isfinite(voxel), "rdm_voxel_map_integrate_moments: voxel must be positive and finite");
-  RDM_REQUIRE(n_scans >= 0 && total >= 0 && ld >= channels, "rdm_voxel_map_integrate_moments: bad sizes (ld must be >= channels)");
-  RDM_REQUIRE(min_range >= 0.0 && max_range >= min_range, "rdm_voxel_map_integrate_moments: need 0 <= min_range <= max_range");
-  if (n_scans == 0 || total == 0) return RDM_OK;
-  RDM_REQUIRE(points && offsets && poses, "rdm_voxel_map_integrate_moments: null argument");
-  hipLaunchKernelGGL(integrate_moments_kernel, dim3(blocks_for(total)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), t, m,
-                     static_cast<long long>(capacity), channels, voxel, points, static_cast<long long>(ld),
-                     static_cast<long long>(total), offsets, poses, static_cast<long long>(n_scans), min_range * min_range,
-                     max_range * max_range);
-  return launch_status("rdm_voxel_map_integrate_moments");
+  return rdm::integrate("rdm_voxel_map_integrate_moments", map, map_bytes, capacity, channels, voxel, points, ld, total, offsets, poses,
+                        n_scans, min_range, max_range, true, moments, moments_bytes, stream);
 }
 
 extern "C" int rdm_voxel_moments_rehash(const void* old_map, size_t old_bytes, int64_t old_capacity, const void* old_moments,
@@ -911,24 +932,12 @@ extern "C" int rdm_voxel_map_extract_moments(const void* map, size_t map_bytes, 
   Table t;
   unsigned long long* m;
   if (const int rc = open_table("rdm_voxel_map_extract_moments", const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
-  if (const int rc = open_moments("rdm_voxel_map_extract_moments", const_cast<void*>(moments), moments_bytes, capacity, m)) return rc;
-  RDM_REQUIRE(voxel > 0.0 && std::isfinite(voxel), "rdm_voxel_map_extract_moments: voxel must be positive and finite");
-  RDM_REQUIRE(min_points >= 0 && max_rows >= 0 && n_rows != nullptr, "rdm_voxel_map_extract_moments: bad min_points, max_rows or null n_rows");
-  RDM_REQUIRE(max_rows == 0 || (cov && eigenvalues && normals), "rdm_voxel_map_extract_moments: null output");
-  Arena ar(ws, ws_bytes);
-  ExtractWork w;
-  if (!carve_extract(ar, capacity, w)) {
-    set_error("rdm_voxel_map_extract_moments: workspace too small (%zu < %zu bytes)", ws_bytes, ar.off);
-    return RDM_ERR_WORKSPACE;
-  }
+  if (const int rc = open_moments("rdm_voxel_map_extract_moments", moments, moments_bytes, capacity, m)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const unsigned int least = min_points > 0xffffffffll ? 0xffffffffu : static_cast<unsigned int>(min_points);
-  fill_words<unsigned long long>(w.n_sel, 1, 0ull, s);
-  hipLaunchKernelGGL(select_kernel, dim3(blocks_for(capacity)), dim3(kBlock), 0, s, t, static_cast<long long>(capacity), least, w.keys_in,
-                     w.slots_in, w.n_sel);
-  size_t bytes = w.sort_bytes;
-  RDM_HIP_CHECK(rocprim::radix_sort_pairs(w.sort_tmp, bytes, w.keys_in, w.keys, w.slots_in, w.slots, static_cast<unsigned>(capacity), 0u,
-                                          64u, s));
+  ExtractWork w;
+  if (const int rc = select_sorted("rdm_voxel_map_extract_moments", t, capacity, voxel, min_points, max_rows, n_rows,
+                                   max_rows == 0 || (cov && eigenvalues && normals), ws, ws_bytes, s, w))
+    return rc;
   hipLaunchKernelGGL(emit_moments_kernel, dim3(blocks_for(max_rows)), dim3(kBlock), 0, s, t, m, static_cast<long long>(capacity), voxel,
                      w.slots, w.n_sel, static_cast<long long>(max_rows), sums, cov, eigenvalues, normals, n_rows);
   return launch_status("rdm_voxel_map_extract_moments");
@@ -952,15 +961,13 @@ extern "C" int rdm_voxel_map_register(const void* map, size_t map_bytes, int64_t
                                       double trans_eps, double* transforms, double* hessians, double* gradients, double* costs,
                                       int64_t* stats, void* ws, size_t ws_bytes, void* stream) {
   using namespace rdm;
+  const char* what = "rdm_voxel_map_register";
   Table t;
-  if (const int rc = open_table("rdm_voxel_map_register", const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
-  RDM_REQUIRE(moments != nullptr, "rdm_voxel_map_register: null moments block");
-  RDM_REQUIRE(moments_bytes >= rdm_voxel_moments_bytes(capacity), "rdm_voxel_map_register: the moments block is too small (%zu < %zu bytes)",
-              moments_bytes, rdm_voxel_moments_bytes(capacity));
-  RDM_REQUIRE(voxel > 0.0 && std::isfinite(voxel), "rdm_voxel_map_register: voxel must be positive and finite");
-  RDM_REQUIRE(n_scans >= 0 && n_scans <= kMaxRegScans && total >= 0 && ld >= channels,
-              "rdm_voxel_map_register: bad sizes (ld must be >= channels, n_scans <= 2^20)");
-  RDM_REQUIRE(min_range >= 0.0 && max_range >= min_range, "rdm_voxel_map_register: need 0 <= min_range <= max_range");
+  unsigned long long* m;
+  if (const int rc = open_table(what, const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
+  if (const int rc = open_moments(what, moments, moments_bytes, capacity, m, RDM_ERR_ARG)) return rc;
+  if (const int rc = check_batch(what, voxel, channels, points, ld, total, offsets, poses, n_scans, kMaxRegScans, true, min_range, max_range))
+    return rc;
   RDM_REQUIRE(sigma > 0.0 && std::isfinite(sigma), "rdm_voxel_map_register: sigma must be positive and finite (got %g)", sigma);
   RDM_REQUIRE(neighbors == 1 || neighbors == 7, "rdm_voxel_map_register: neighbors must be 1 or 7 (got %d)", neighbors);
   RDM_REQUIRE(min_points >= 1 && max_iteration >= 0 && rot_eps >= 0.0 && trans_eps >= 0.0,
@@ -972,11 +979,9 @@ extern "C" int rdm_voxel_map_register(const void* map, size_t map_bytes, int64_t
     return RDM_ERR_WORKSPACE;
   }
   if (n_scans == 0) return RDM_OK;
-  RDM_REQUIRE((points || total == 0) && offsets && poses, "rdm_voxel_map_register: null argument");
   RDM_REQUIRE(transforms && hessians && gradients && costs && stats, "rdm_voxel_map_register: null output");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const unsigned long long* m = static_cast<const unsigned long long*>(moments);
-  const unsigned int least = min_points > 0xffffffffll ? 0xffffffffu : static_cast<unsigned int>(min_points);
+  const unsigned int least = least_points(min_points);
   hipLaunchKernelGGL(register_init_kernel, dim3(blocks_for(n_scans)), dim3(kBlock), 0, s, poses, static_cast<long long>(n_scans), w);
   int running = 1;
   for (int k = 0; k <= max_iteration && running > 0;) {

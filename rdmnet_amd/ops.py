@@ -916,6 +916,17 @@ class VoxelMap:
             raise ValueError(f'need 0 <= min_range <= max_range, got {min_range} and {max_range}')
         return points, offsets, n, X, lo, hi
 
+    def _on_device(self, points, offsets, X):
+        """_packed's points, offsets and poses as the C calls take them -> (points, ld, total, offsets and poses on the device).  A batch
+        without rows gets one placeholder row and total = 0."""
+        if points is None or points.shape[0] == 0:
+            points, total, ld = torch.zeros((1, self.channels), dtype=torch.float32, device=self.device), 0, self.channels
+        else:
+            total = int(points.shape[0])
+            ld = points.stride(0) if total > 1 else points.shape[1]
+        with torch.cuda.device(self.device):
+            return points, ld, total, offsets.to(self.device).contiguous(), torch.from_numpy(X).to(self.device)
+
     def integrate(self, clouds, poses, min_range=0.0, max_range=float('inf')):
         """clouds: a list of float32 CUDA tensors [N_i, >= C] (empty ones allowed), or a pair (points float32 CUDA [N, ld >= C],
         offsets int64 [n + 1], host or device: scan i is rows offsets[i] .. offsets[i + 1]).  poses: [n, 4, 4] finite, anything
@@ -924,39 +935,41 @@ class VoxelMap:
         points, offsets, n, X, lo, hi = self._packed('integrate', clouds, poses, min_range, max_range)
         if n == 0 or points is None or points.shape[0] == 0:
             return self
-        total = int(points.shape[0])
-        ld = points.stride(0) if total > 1 else points.shape[1]
+        points, ld, total, offsets, X = self._on_device(points, offsets, X)
         self._reserve(total)
+        name = 'rdm_voxel_map_integrate' + ('_moments' if self.moments else '')
+        block = (self._mom.data_ptr(), self._mom.numel()) if self.moments else ()
         with torch.cuda.device(self.device):
-            offsets = offsets.to(self.device).contiguous()
-            X = torch.from_numpy(X).to(self.device)
-            if self.moments:
-                _lib.check(_lib.lib().rdm_voxel_map_integrate_moments(*self._head(), self.voxel, points.data_ptr(), ld, total,
-                                                                      offsets.data_ptr(), X.data_ptr(), n, lo, hi, self._mom.data_ptr(),
-                                                                      self._mom.numel(), _lib.stream_ptr()),
-                           'rdm_voxel_map_integrate_moments')
-            else:
-                _lib.check(_lib.lib().rdm_voxel_map_integrate(*self._head(), self.voxel, points.data_ptr(), ld, total, offsets.data_ptr(),
-                                                              X.data_ptr(), n, lo, hi, _lib.stream_ptr()), 'rdm_voxel_map_integrate')
+            _lib.check(getattr(_lib.lib(), name)(*self._head(), self.voxel, points.data_ptr(), ld, total, offsets.data_ptr(), X.data_ptr(),
+                                                 n, lo, hi, *block, _lib.stream_ptr()), name)
         return self
 
     def extract(self, min_points=1):
         """-> (points float32 [M, C], counts int32 [M], cells int32 [M, 3]) on the device: the voxels with at least min_points
         points in ascending order of (cell x, cell y, cell z); points = the per-voxel means.  Two read-backs (sizes)."""
+        points, counts, cells = self._extract('rdm_voxel_map_extract', min_points, ((torch.float32, (self.channels,)), (torch.int32, (1, 3))))
+        return points, counts.view(-1), cells
+
+    def _extract(self, name, min_points, blocks, *block_args):
+        """The frame of both extracts: reads `occupied`, makes one allocation per (dtype, widths) of `blocks` and cuts it into one
+        [occupied, width] output per width, calls `name` (block_args: what it takes between the map and the voxel), reads the number
+        of rows it wrote and slices the outputs to it."""
         L = _lib.lib()
         rows = self.stats()['occupied']
-        C, dev = self.channels, self.device
-        points = torch.empty((max(rows, 1), C), dtype=torch.float32, device=dev)
-        ints = torch.empty((max(rows, 1), 4), dtype=torch.int32, device=dev)  # counts, then cells
-        counts, cells = ints.view(-1)[:max(rows, 1)], ints.view(-1)[max(rows, 1):].view(-1, 3)
+        R, dev = max(rows, 1), self.device
+        outs = []
+        for dtype, widths in blocks:
+            flat, lo = torch.empty((R * sum(widths),), dtype=dtype, device=dev), 0
+            for w in widths:
+                outs.append(flat[lo * R:(lo + w) * R].view(R, w))
+                lo += w
         n_rows = torch.zeros((1,), dtype=torch.int64, device=dev)
         with torch.cuda.device(dev):
             ws = scratch(dev, L.rdm_voxel_map_extract_workspace_bytes(self.capacity))
-            _lib.check(L.rdm_voxel_map_extract(*self._head(), self.voxel, int(min_points), points.data_ptr(), counts.data_ptr(),
-                                               cells.data_ptr(), rows, n_rows.data_ptr(), ws.data_ptr(), ws.numel(),
-                                               _lib.stream_ptr()), 'rdm_voxel_map_extract')
+            _lib.check(getattr(L, name)(*self._head(), *block_args, self.voxel, int(min_points), *(t.data_ptr() for t in outs), rows,
+                                        n_rows.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), name)
         m = int(n_rows.item())
-        return points[:m], counts[:m], cells[:m]
+        return tuple(t[:m] for t in outs)
 
     def _need_moments(self, what):
         if not self.moments:
@@ -968,21 +981,8 @@ class VoxelMap:
         u = the 12-bit local coordinate; cov: the population covariance in m^2 (xx, xy, xz, yy, yz, zz); eigenvalues ascending; normals:
         the unit eigenvector of the smallest, its component of largest magnitude positive.  Two read-backs (sizes)."""
         self._need_moments('extract_moments')
-        L = _lib.lib()
-        rows = self.stats()['occupied']
-        dev, P = self.device, _lib.VOXEL_MOMENTS_PLANES
-        sums = torch.empty((max(rows, 1), P), dtype=torch.int64, device=dev)
-        real = torch.empty((max(rows, 1), 12), dtype=torch.float64, device=dev)  # cov, eigenvalues, normals
-        cov, eig, normals = (real.view(-1)[a * max(rows, 1):b * max(rows, 1)].view(max(rows, 1), b - a) for a, b in ((0, 6), (6, 9), (9, 12)))
-        n_rows = torch.zeros((1,), dtype=torch.int64, device=dev)
-        with torch.cuda.device(dev):
-            ws = scratch(dev, L.rdm_voxel_map_extract_workspace_bytes(self.capacity))
-            _lib.check(L.rdm_voxel_map_extract_moments(*self._head(), self._mom.data_ptr(), self._mom.numel(), self.voxel, int(min_points),
-                                                       sums.data_ptr(), cov.data_ptr(), eig.data_ptr(), normals.data_ptr(), rows,
-                                                       n_rows.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
-                       'rdm_voxel_map_extract_moments')
-        m = int(n_rows.item())
-        return sums[:m], cov[:m], eig[:m], normals[:m]
+        return self._extract('rdm_voxel_map_extract_moments', min_points,
+                             ((torch.int64, (_lib.VOXEL_MOMENTS_PLANES,)), (torch.float64, (6, 3, 3))), self._mom.data_ptr(), self._mom.numel())
 
     def sharpness(self, min_points=4):
         """The ground-truth-free map report over the voxels with at least min_points points (4: the smallest count at which a
@@ -1031,15 +1031,8 @@ class VoxelMap:
         stats = torch.zeros((n, 4), dtype=torch.int64, device=dev)
         T, H, g, cost = (real.view(-1)[a * n:b * n].view(n, b - a) for a, b in ((0, 16), (16, 52), (52, 58), (58, 59)))
         if n > 0:
-            if points is None or points.shape[0] == 0:
-                points = torch.zeros((1, self.channels), dtype=torch.float32, device=dev)
-                total, ld = 0, self.channels
-            else:
-                total = int(points.shape[0])
-                ld = points.stride(0) if total > 1 else points.shape[1]
+            points, ld, total, offsets, Xd = self._on_device(points, offsets, X)
             with torch.cuda.device(dev):
-                offsets = offsets.to(dev).contiguous()
-                Xd = torch.from_numpy(X).to(dev)
                 ws = scratch(dev, L.rdm_voxel_map_register_workspace_bytes(n))
                 _lib.check(L.rdm_voxel_map_register(*self._head(), self._mom.data_ptr(), self._mom.numel(), self.voxel, points.data_ptr(), ld,
                                                     total, offsets.data_ptr(), Xd.data_ptr(), n, lo, hi, sigma, min_points, neighbors,

@@ -234,6 +234,32 @@ def test_non_finite_and_range_gated_rows_are_passed_over(ops):
     assert np.isfinite(res.cost.cpu().numpy()).all() and np.isfinite(res.information.cpu().numpy()).all()
 
 
+def test_register_counts_the_points_that_integrate_keeps(ops):
+    """The 16 special rows of test_voxel_map_gpu (non-finite values, the gate boundaries, the attribute limit, the extent) as one scan
+    under three poses and two range gates: the registration's num_points, the `integrated` counter of a fresh plain map and of a
+    fresh map with moments, and both restatements' counts are one number, and that number is the literal one."""
+    import voxel_map_restatement as VM
+    from test_voxel_map import random_pose
+    from test_voxel_map_gpu import special_rows
+    rows = special_rows()
+    far = np.eye(4)
+    far[0, 3] = 314572.8 - 50.0
+    poses = (np.eye(4), far, random_pose(np.random.default_rng(2), 100.0))
+    gates = ((0.0, np.inf), (5.0, 80.0))
+    want = iter((10, 8, 9, 7, 10, 8))
+    table = MR.build([rows], [np.eye(4)], 0.3, 4)
+    against = ops.VoxelMap(0.3, channels=4, capacity=64, moments=True).integrate([cuda(rows)], np.eye(4)[None])
+    for X in poses:
+        for lo, hi in gates:
+            n = next(want)
+            assert len(VM.quantise(rows, X, 0.3, 4, lo, hi)[0]) == n and len(RR.world_points(table, rows, X, lo, hi)[0]) == n
+            res = against.register([cuda(rows)], X[None], max_iteration=0, min_range=lo, max_range=hi)
+            assert res.num_points.tolist() == [n]
+            for moments in (False, True):
+                fresh = ops.VoxelMap(0.3, channels=4, capacity=64, moments=moments).integrate([cuda(rows)], X[None], lo, hi)
+                assert fresh.stats()['integrated'] == n, (moments, lo, hi)
+
+
 def test_status_converged_and_max_iteration_and_the_map_is_only_read(ops):
     clouds, _, _, _ = scene()
     vmap = shared_map(ops, 1.0)

@@ -1,8 +1,9 @@
 """Times the voxel map (ops.VoxelMap) on synthetic scans along a synthetic drive.
 
   python tools/map_bench.py [--frames 256] [--points 120000 | 18000] [--reps 3] [--batch 64] [--voxel 0.3] [--cpu] [--cpu-frames 8]
-                              [--moments] [--register]
-Prints one JSON line per case:
+                              [--moments] [--register] [--digest]
+With --digest (and nothing else): no timing, one sha1 line per output of the voxel map on the bundled scans (see digest()), for
+comparing the bits of two builds of the library.  Otherwise prints one JSON line per case:
   * integrate: --frames scans of --points points (120 000: a raw scan; 18 000: a down-sampled one), xyz + intensity, integrated in
     batches of --batch from device memory into a table created large enough (no growth inside the timing); device time between
     two events, median of --reps; points/s, the bytes/s of integer atomic adds that implies ((8 C + 4) B a point: C int64 sums and
@@ -82,6 +83,56 @@ def drive(frames, step=1.0):
     return poses
 
 
+def off_poses(poses, rng):
+    """The poses 5 mrad / 5 cm (one sigma per axis) off."""
+    off = poses.copy()
+    for X in off:
+        w = rng.normal(0.0, 0.005, 3)
+        K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+        X[:3, :3] = (np.eye(3) + K + 0.5 * K @ K) @ X[:3, :3]
+        X[:3, 3] += rng.normal(0.0, 0.05, 3)
+    return off
+
+
+def digest():
+    """One `sha1  what` line over the raw bytes of everything the voxel map returns for the three bundled scans (tests/golden/scans.npz
+    with the intensity column of the tests) under three seeded poses: stats, extract and extract_moments of maps that grow from 1024
+    slots at voxel 0.3 and 0.05, with and without moments, and every field of register at neighbors 1 and 7, as one batch of three
+    and as three calls of one.  Two libraries (RDM_LIB_PATH) compute the same bits iff they print the same lines."""
+    import hashlib
+    import torch
+    from rdmnet_amd import ops
+    from test_voxel_map import random_pose, with_attribute
+    scans = np.load(os.path.join(ROOT, 'tests', 'golden', 'scans.npz'))
+    clouds = [torch.from_numpy(with_attribute(scans[k], i)).cuda() for i, k in enumerate(('s000000', 's000004', 's000007'))]
+    rng = np.random.default_rng(11)
+    poses = np.stack([random_pose(rng) for _ in clouds])
+
+    def line(what, tensors):
+        h = hashlib.sha1()
+        for t in tensors:
+            h.update(t.cpu().contiguous().numpy().tobytes())
+        print(f'{h.hexdigest()}  {what}', flush=True)
+
+    for voxel in (0.3, 0.05):
+        for moments in (True, False):
+            vmap = ops.VoxelMap(voxel, channels=4, capacity=1024, moments=moments).integrate(clouds, poses)
+            name = f'voxel {voxel} moments {int(moments)}'
+            line(f'{name} stats', [torch.tensor(list(vmap.stats().values()), dtype=torch.int64)])
+            line(f'{name} extract', vmap.extract())
+            if moments:
+                line(f'{name} extract_moments', vmap.extract_moments())
+    vmap = ops.VoxelMap(0.3, channels=4, capacity=1024, moments=True).integrate(clouds, poses)
+    off = off_poses(poses, np.random.default_rng(0))
+    for neighbors in (1, 7):
+        runs = [vmap.register(clouds, off, neighbors=neighbors, max_iteration=5)]
+        runs += [vmap.register(clouds[k:k + 1], off[k:k + 1], neighbors=neighbors, max_iteration=5) for k in range(3)]
+        for what, res in zip(('batch of 3', 'scan 0', 'scan 1', 'scan 2'), runs):
+            line(f'register neighbors {neighbors} {what}', [res.transformations, res.information, res.gradient, res.cost, res.iterations,
+                                                            res.num_correspondences, res.num_points, res.status])
+    return 0
+
+
 def register_cases(a):
     import torch
     from rdmnet_amd import ops
@@ -91,12 +142,7 @@ def register_cases(a):
         cloud, poses = synthetic_scans(frames, points), drive(frames)
         clouds = [cloud[k * points:(k + 1) * points] for k in range(frames)]
         vmap = ops.VoxelMap(a.voxel, channels=4, capacity=1 << 24, moments=True).integrate(clouds, poses)
-        off = poses.copy()
-        for X in off:
-            w = rng.normal(0.0, 0.005, 3)
-            K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
-            X[:3, :3] = (np.eye(3) + K + 0.5 * K @ K) @ X[:3, :3]
-            X[:3, 3] += rng.normal(0.0, 0.05, 3)
+        off = off_poses(poses, rng)
         batch = [clouds[k % frames] for k in range(64)]
         Xb = np.stack([off[k % frames] for k in range(64)])
         for neighbors in (1, 7):
@@ -140,12 +186,15 @@ def main(argv=None):
     ap.add_argument('--voxel', type=float, default=0.3)
     ap.add_argument('--moments', action='store_true', help='also time integrate and extract with the per-voxel second moments')
     ap.add_argument('--register', action='store_true', help='time the scan-to-map registration and nothing else')
+    ap.add_argument('--digest', action='store_true', help='print the sha1 lines of the bundled scans\' maps and registrations and nothing else')
     ap.add_argument('--cpu', action='store_true', help='also time the NumPy restatement and compare the maps bit for bit')
     ap.add_argument('--cpu-frames', type=int, default=8)
     a = ap.parse_args(argv)
     import torch
     from rdmnet_amd import _lib, ops
     assert torch.cuda.is_available(), 'map_bench needs a GPU'
+    if a.digest:
+        return digest()
     if a.register:
         return register_cases(a)
     C = 4
