@@ -16,6 +16,11 @@
 // pg_update_kernel
 // (candidate poses), pg_cost_kernel (candidate cost terms), pg_step_kernel (accept / reject, damping, stopping tests) and
 // pg_commit_kernel.  All decisions are taken on the device; the host reads one word every kChunk iterations.
+//
+// Every sum has ONE place: assemble_nodes (node blocks, gradient and the chain's off-diagonal sums, for pg_solve_kernel and
+// pg_direct_blocks_kernel), add_block and block_mul (a sum of Hab blocks or their transposes; t = B z or B^T z), precondition<kPre>
+// (z = M^-1 r, before the conjugate-gradient loop and in it), direct_run_factor / direct_run_back (a run of the direct solve, and the
+// whole chain of rdm_pose_graph_chain_host).  The fixed order above holds because there is no second copy to edit another way.
 #include "common.h"
 #include "../../include/rdmnet_hip.h"
 
@@ -23,6 +28,7 @@
 #include <cmath>
 #include <cstring>
 #include <set>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -311,6 +317,17 @@ struct Graphs {            // device arrays of the call
   const int* inc;          // [2 E]
 };
 
+// A workgroup has nothing to do for its graph g: the input check refused the call, or the graph is done.  (The kernels that map
+// threads to edges, nodes, runs or couplings test *bad before they look their graph up.)
+__device__ __forceinline__ bool skip(const GraphState* gs, int g, const int* bad) { return *bad != 0 || gs[g].done; }
+// Graph g ends with a failure, by a whole workgroup.
+__device__ __forceinline__ void end_graph(GraphState* gs, int g, int status) {
+  if (threadIdx.x == 0) {
+    gs[g].status = status;
+    gs[g].done = 1;
+  }
+}
+
 // Inputs: every entry finite, information matrices symmetric.  One flag for the call, and the cause in the status of the graph that
 // holds the entry (after pg_init_kernel).
 __global__ __launch_bounds__(kBlock) void pg_check_kernel(Graphs gr, const double* __restrict__ nodes, int n,
@@ -481,6 +498,38 @@ __device__ __forceinline__ void chol_solve6(const double* __restrict__ f, const 
   }
 }
 
+// The two operations on an edge's 6 x 6 block Hab, whose rows are the edge's source: every sum over such blocks goes through them, so
+// that it has one order and one shape wherever it is formed.
+// acc += H, or acc += H^T for the end of the edge that is its target.
+__host__ __device__ __forceinline__ void add_block(double* acc, const double* H, bool transposed) {
+  if (transposed) {
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) acc[6 * r + c] += H[6 * c + r];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 36; ++k) acc[k] += H[k];
+  }
+}
+// t = B z, or t = B^T z: every entry from 0.0 in ascending k.  The caller adds or subtracts t as a step of its own.
+__host__ __device__ __forceinline__ void block_mul(const double* B, const double* z, bool transposed, double* t) {
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double a = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) a += (transposed ? B[6 * k + i] : B[6 * i + k]) * z[k];
+    t[i] = a;
+  }
+}
+// r <- r - B z and r <- r - B^T z (r is neither B nor z)
+__host__ __device__ __forceinline__ void dense_sub_mul(const double* b, const double* z, double* r, bool transposed) {
+  double t[6];
+  block_mul(b, z, transposed, t);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) r[i] -= t[i];
+}
+
 // ---- the odometry-chain preconditioner -----------------------------------------------------------------
 // M is block tridiagonal over the free nodes 1 .. n - 1: the damped node blocks on the diagonal, and between nodes i - 1 and i the
 // sum of the Hab blocks of the edges that join the two.  M = L L^T by a block Cholesky along the chain; kept per node are
@@ -572,6 +621,19 @@ __host__ __device__ __forceinline__ void chain_gt_mul(const double* g, const dou
 // One row of a sweep step: c - w . y, the six products added as three pairs (a short dependent chain, a fixed order).
 __host__ __device__ __forceinline__ double chain_row(double c, const double* w, const double* y) {
   return c - (((w[0] * y[0] + w[1] * y[1]) + (w[2] * y[2] + w[3] * y[3])) + (w[4] * y[4] + w[5] * y[5]));
+}
+// M_{node, node-1}: the sum of the blocks of the edges that join the two, in edge order (rows: node).
+__host__ __device__ __forceinline__ void chain_off_block(const int* __restrict__ es, const int* __restrict__ et,
+                                                         const int* __restrict__ inc_off, const int* __restrict__ inc,
+                                                         const double* __restrict__ Hab, long long node, double* off) {
+#pragma unroll
+  for (int k = 0; k < 36; ++k) off[k] = 0.0;
+  for (int q = inc_off[node]; q < inc_off[node + 1]; ++q) {
+    const int code = inc[q];
+    const long long e = code >> 1;
+    const long long other = (code & 1) ? es[e] : et[e];
+    if (other == node - 1) add_block(off, Hab + 36 * e, code & 1);
+  }
 }
 
 __device__ __forceinline__ double read_lane(double v, int lane) {  // lane: a constant
@@ -677,6 +739,100 @@ __device__ __forceinline__ double chain_finish(const double* __restrict__ F, con
 enum : int { PRE_BLOCK_JACOBI = 0, PRE_CHAIN = 1 };
 enum : int { SOLVER_PCG = 0, SOLVER_DIRECT = 1 };
 
+// The node assembly, for the calling thread's nodes tid, tid + kBlock, ... of the graph at n0 with n nodes: D = the sum of the node's
+// Haa / Hbb blocks and b = the sum of its ga / gb over the incidence list in ascending order (zeros for the fixed node 0), written with
+// x = 0 and r = -b; with kOff, the chain's off-diagonal sum M_{i,i-1} into Wc by a second pass over the list (zeros for i <= 1).
+// -> the thread's gradient maximum.
+template <bool kOff>
+__device__ __forceinline__ double assemble_nodes(const Graphs& gr, int n0, int n, const double* __restrict__ Haa,
+                                                 const double* __restrict__ Hab, const double* __restrict__ Hbb,
+                                                 const double* __restrict__ ga, const double* __restrict__ gb, double* __restrict__ D,
+                                                 double* __restrict__ bv, double* __restrict__ xv, double* __restrict__ rv,
+                                                 double* __restrict__ Wc) {
+  double gmax = 0.0;
+  for (int i = threadIdx.x; i < n; i += kBlock) {
+    const long long node = n0 + i;
+    double d[36], b[6];
+#pragma unroll
+    for (int k = 0; k < 36; ++k) d[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) b[k] = 0.0;
+    if (i > 0) {
+      for (int q = gr.inc_off[node]; q < gr.inc_off[node + 1]; ++q) {
+        const int code = gr.inc[q];
+        const long long e = code >> 1;
+        const double* H = (code & 1) ? Hbb + 36 * e : Haa + 36 * e;
+        const double* v = (code & 1) ? gb + 6 * e : ga + 6 * e;
+#pragma unroll
+        for (int k = 0; k < 36; ++k) d[k] += H[k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) b[k] += v[k];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 36; ++k) D[36 * node + k] = d[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      bv[6 * node + k] = b[k];
+      gmax = fmax(gmax, fabs(2.0 * b[k]));  // the gradient of F is 2 b
+      xv[6 * node + k] = 0.0;
+      rv[6 * node + k] = -b[k];
+    }
+    if constexpr (kOff) {
+      if (i > 1) {
+        chain_off_block(gr.es, gr.et, gr.inc_off, gr.inc, Hab, node, d);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 36; ++k) d[k] = 0.0;
+      }
+#pragma unroll
+      for (int k = 0; k < 36; ++k) Wc[36 * node + k] = d[k];
+    }
+  }
+  return gmax;
+}
+
+// The gradient test on the workgroup's gradient maximum.  -> it ends the graph (the same in every thread).
+__device__ __forceinline__ bool gradient_stop(GraphState* gs, int g, double gmax, double gtol) {
+  if (threadIdx.x == 0) {
+    gs[g].grad_max = gmax;
+    if (gmax <= gtol) {
+      gs[g].stop = STOP_GRADIENT;
+      gs[g].done = 1;
+    }
+  }
+  return gmax <= gtol;
+}
+
+// z = M^-1 r for the calling thread's nodes, into zv (zeros for node 0).  kPre 0: the nodes' factored blocks; 1: c = G r per node, then
+// the sweeps and z = G^T q by chain_finish (whose barriers every thread of the workgroup passes).  -> this thread's part of r^T z, its
+// nodes in order.
+template <int kPre>
+__device__ __forceinline__ double precondition(const double* __restrict__ F, const double* __restrict__ Wc, const double* rv, double* zv,
+                                               int n0, int n) {
+  double part = 0.0;
+  for (int i = threadIdx.x; i < n; i += kBlock) {
+    const long long node = n0 + i;
+    double r[6], z[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < 6; ++k) r[k] = rv[6 * node + k];
+    if constexpr (kPre == PRE_CHAIN) {
+      if (i > 0) chain_g_mul(F + 21 * node, r, z);
+    } else {
+      if (i > 0) chol_solve6(F + 21 * node, r, z);
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      zv[6 * node + k] = z[k];
+      if constexpr (kPre != PRE_CHAIN) {
+        if (i > 0) part += r[k] * z[k];
+      }
+    }
+  }
+  if constexpr (kPre == PRE_CHAIN) part = chain_finish(F, Wc, rv, zv, n0, n);
+  return part;
+}
+
 // One workgroup per graph: node blocks and gradient in incidence order, the gradient test, the preconditioner's factors (kPre 0:
 // damped block-Jacobi; 1: the odometry chain, factored along the chain by thread 0 from blocks that 72 threads stage in LDS one
 // node ahead), then preconditioned conjugate gradients on (H + lambda blockdiag(H)) x = -b with a matrix-free product.  A thread
@@ -693,65 +849,20 @@ __global__ __launch_bounds__(kBlock) void pg_solve_kernel(Graphs gr, Params p, G
   __shared__ double red[kWaves];
   __shared__ int fail;
   const int g = blockIdx.x;
-  if (*bad != 0 || gs[g].done) return;  // (uniform over the workgroup)
+  if (skip(gs, g, bad)) return;  // (uniform over the workgroup)
   const int n0 = gr.node_off[g], n = gr.node_off[g + 1] - n0;
   const double lambda = gs[g].lambda;
   if (threadIdx.x == 0) fail = 0;
   __syncthreads();
   // 1. blocks, gradient, factors
-  double gmax = 0.0;
-  for (int i = threadIdx.x; i < n; i += kBlock) {
-    const long long node = n0 + i;
-    double d[36], b[6];
+  double gmax = assemble_nodes<kPre == PRE_CHAIN>(gr, n0, n, Haa, Hab, Hbb, ga, gb, D, bv, xv, rv, Wc);
+  if constexpr (kPre == PRE_BLOCK_JACOBI) {
+    for (int i = threadIdx.x; i < n; i += kBlock) {
+      if (i == 0) continue;
+      const long long node = n0 + i;
+      double d[36];  // (the thread's own writes of D)
 #pragma unroll
-    for (int k = 0; k < 36; ++k) d[k] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) b[k] = 0.0;
-    [[maybe_unused]] double off[36];  // kPre 1: M_{i,i-1}, the edges that join this node and the one before it, in edge order
-    if constexpr (kPre == PRE_CHAIN) {
-#pragma unroll
-      for (int k = 0; k < 36; ++k) off[k] = 0.0;
-    }
-    if (i > 0) {
-      for (int q = gr.inc_off[node]; q < gr.inc_off[node + 1]; ++q) {
-        const int code = gr.inc[q];
-        const long long e = code >> 1;
-        const double* H = (code & 1) ? Hbb + 36 * e : Haa + 36 * e;
-        const double* v = (code & 1) ? gb + 6 * e : ga + 6 * e;
-#pragma unroll
-        for (int k = 0; k < 36; ++k) d[k] += H[k];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) b[k] += v[k];
-        if constexpr (kPre == PRE_CHAIN) {
-          const long long other = (code & 1) ? gr.es[e] : gr.et[e];
-          if (i > 1 && other == node - 1) {
-            const double* C = Hab + 36 * e;  // rows: the edge's source
-            if (code & 1) {
-#pragma unroll
-              for (int r = 0; r < 6; ++r)
-#pragma unroll
-                for (int c = 0; c < 6; ++c) off[6 * r + c] += C[6 * c + r];
-            } else {
-#pragma unroll
-              for (int k = 0; k < 36; ++k) off[k] += C[k];
-            }
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 36; ++k) D[36 * node + k] = d[k];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      bv[6 * node + k] = b[k];
-      gmax = fmax(gmax, fabs(2.0 * b[k]));  // the gradient of F is 2 b
-      xv[6 * node + k] = 0.0;
-      rv[6 * node + k] = -b[k];
-    }
-    if constexpr (kPre == PRE_CHAIN) {
-#pragma unroll
-      for (int k = 0; k < 36; ++k) Wc[36 * node + k] = off[k];
-    } else if (i > 0) {
+      for (int k = 0; k < 36; ++k) d[k] = D[36 * node + k];
 #pragma unroll
       for (int k = 0; k < 36; ++k) d[k] *= 1.0 + lambda;
       if (!cholesky6(d)) fail = 1;
@@ -763,20 +874,10 @@ __global__ __launch_bounds__(kBlock) void pg_solve_kernel(Graphs gr, Params p, G
   }
   gmax = block_max(gmax, red);
   if (fail) {  // (block_max's barriers order the writes of `fail`)
-    if (threadIdx.x == 0) {
-      gs[g].status = ST_SINGULAR;
-      gs[g].done = 1;
-    }
+    end_graph(gs, g, ST_SINGULAR);
     return;
   }
-  if (threadIdx.x == 0) gs[g].grad_max = gmax;
-  if (gmax <= p.gtol) {
-    if (threadIdx.x == 0) {
-      gs[g].stop = STOP_GRADIENT;
-      gs[g].done = 1;
-    }
-    return;
-  }
+  if (gradient_stop(gs, g, gmax, p.gtol)) return;
   if constexpr (kPre == PRE_CHAIN) {
     // the chain's factors: node after node by thread 0; threads 0 .. 71 fetch the next node's damped block and M_{i,i-1} meanwhile
     __shared__ double stage[2][72];
@@ -805,42 +906,17 @@ __global__ __launch_bounds__(kBlock) void pg_solve_kernel(Graphs gr, Params p, G
     }
     __syncthreads();
     if (fail) {
-      if (threadIdx.x == 0) {
-        gs[g].status = ST_SINGULAR;
-        gs[g].done = 1;
-      }
+      end_graph(gs, g, ST_SINGULAR);
       return;
     }
     for (int i = threadIdx.x; i < n; i += kBlock)
       if (i > 1) chain_w(F + 21ll * (n0 + i), Wc + 36ll * (n0 + i), Wc + 36ll * (n0 + i));
   }
   // 2. z = M^-1 r, pv = z, rz
-  double part = 0.0;
-  for (int i = threadIdx.x; i < n; i += kBlock) {
-    const long long node = n0 + i;
-    double r[6], z[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double part = precondition<kPre>(F, Wc, rv, zv, n0, n);
+  for (int i = threadIdx.x; i < n; i += kBlock)
 #pragma unroll
-    for (int k = 0; k < 6; ++k) r[k] = rv[6 * node + k];
-    if constexpr (kPre == PRE_CHAIN) {
-      if (i > 0) chain_g_mul(F + 21 * node, r, z);
-    } else {
-      if (i > 0) chol_solve6(F + 21 * node, r, z);
-    }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      zv[6 * node + k] = z[k];
-      if constexpr (kPre != PRE_CHAIN) {
-        pv[6 * node + k] = z[k];
-        if (i > 0) part += r[k] * z[k];
-      }
-    }
-  }
-  if constexpr (kPre == PRE_CHAIN) {
-    part = chain_finish(F, Wc, rv, zv, n0, n);
-    for (int i = threadIdx.x; i < n; i += kBlock)
-#pragma unroll
-      for (int k = 0; k < 6; ++k) pv[6ll * (n0 + i) + k] = zv[6ll * (n0 + i) + k];
-  }
+    for (int k = 0; k < 6; ++k) pv[6ll * (n0 + i) + k] = zv[6ll * (n0 + i) + k];
   double rz = block_sum(part, red);
   const double rz0 = rz;
   int it = 0;
@@ -852,40 +928,22 @@ __global__ __launch_bounds__(kBlock) void pg_solve_kernel(Graphs gr, Params p, G
       const long long node = n0 + i;
       double y[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
       if (i > 0) {
-        double x[6];
+        double x[6], t[6];
 #pragma unroll
         for (int k = 0; k < 6; ++k) x[k] = pv[6 * node + k];
-        const double* d = D + 36 * node;
+        block_mul(D + 36 * node, x, false, t);
 #pragma unroll
-        for (int r = 0; r < 6; ++r) {
-          double a = 0.0;
-#pragma unroll
-          for (int c = 0; c < 6; ++c) a += d[6 * r + c] * x[c];
-          y[r] = (1.0 + lambda) * a;
-        }
+        for (int r = 0; r < 6; ++r) y[r] = (1.0 + lambda) * t[r];
         for (int q = gr.inc_off[node]; q < gr.inc_off[node + 1]; ++q) {
           const int code = gr.inc[q];
           const long long e = code >> 1;
-          const double* H = Hab + 36 * e;
           if (code & 1) {  // this node is the target: Hab^T p_source
-            const double* o = pv + 6ll * gr.es[e];
-#pragma unroll
-            for (int r = 0; r < 6; ++r) {
-              double a = 0.0;
-#pragma unroll
-              for (int c = 0; c < 6; ++c) a += H[6 * c + r] * o[c];
-              y[r] += a;
-            }
+            block_mul(Hab + 36 * e, pv + 6ll * gr.es[e], true, t);
           } else {
-            const double* o = pv + 6ll * gr.et[e];
-#pragma unroll
-            for (int r = 0; r < 6; ++r) {
-              double a = 0.0;
-#pragma unroll
-              for (int c = 0; c < 6; ++c) a += H[6 * r + c] * o[c];
-              y[r] += a;
-            }
+            block_mul(Hab + 36 * e, pv + 6ll * gr.et[e], false, t);
           }
+#pragma unroll
+          for (int r = 0; r < 6; ++r) y[r] += t[r];
         }
 #pragma unroll
         for (int k = 0; k < 6; ++k) part += x[k] * y[k];
@@ -896,31 +954,15 @@ __global__ __launch_bounds__(kBlock) void pg_solve_kernel(Graphs gr, Params p, G
     const double pAp = block_sum(part, red);
     if (!(pAp > 0.0)) break;
     const double alpha = rz / pAp;
-    part = 0.0;
     for (int i = threadIdx.x; i < n; i += kBlock) {
       const long long node = n0 + i;
-      double r[6], z[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll
       for (int k = 0; k < 6; ++k) {
         xv[6 * node + k] += alpha * pv[6 * node + k];
-        r[k] = rv[6 * node + k] - alpha * zv[6 * node + k];
-        rv[6 * node + k] = r[k];
-      }
-      if constexpr (kPre == PRE_CHAIN) {
-        if (i > 0) chain_g_mul(F + 21 * node, r, z);
-      } else {
-        if (i > 0) chol_solve6(F + 21 * node, r, z);
-      }
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        zv[6 * node + k] = z[k];
-        if constexpr (kPre != PRE_CHAIN) {
-          if (i > 0) part += r[k] * z[k];
-        }
+        rv[6 * node + k] = rv[6 * node + k] - alpha * zv[6 * node + k];
       }
     }
-    if constexpr (kPre == PRE_CHAIN) part = chain_finish(F, Wc, rv, zv, n0, n);
-    const double rz_new = block_sum(part, red);
+    const double rz_new = block_sum(precondition<kPre>(F, Wc, rv, zv, n0, n), red);
     const double beta = rz_new / rz;
     rz = rz_new;
     for (int i = threadIdx.x; i < n; i += kBlock) {
@@ -972,32 +1014,11 @@ struct DirectSystem {       // the system: D, Hab and the incidence lists give A
   double *F, *Wc, *zv, *xv;  // G [N, 21], W [N, 36] (on entry: the chain's off-diagonal sums), y [N, 6], x [N, 6]
 };
 
-// M_{node, node-1}: the sum of the blocks of the edges that join the two, in edge order (rows: node).
-__host__ __device__ __forceinline__ void chain_off_block(const int* __restrict__ es, const int* __restrict__ et,
-                                                         const int* __restrict__ inc_off, const int* __restrict__ inc,
-                                                         const double* __restrict__ Hab, long long node, double* off) {
-#pragma unroll
-  for (int k = 0; k < 36; ++k) off[k] = 0.0;
-  for (int q = inc_off[node]; q < inc_off[node + 1]; ++q) {
-    const int code = inc[q];
-    const long long e = code >> 1;
-    const long long other = (code & 1) ? es[e] : et[e];
-    if (other != node - 1) continue;
-    const double* C = Hab + 36 * e;  // rows: the edge's source
-    if (code & 1) {
-#pragma unroll
-      for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) off[6 * r + c] += C[6 * c + r];
-    } else {
-#pragma unroll
-      for (int k = 0; k < 36; ++k) off[k] += C[k];
-    }
-  }
-}
-
-// One run: the factors G_i and W_i = G_i L_{i,i-1} along it, and y = L^-1 r on its rows of zv.  false: a pivot is not positive.
-__host__ __device__ inline bool direct_run_factor(const Direct& dp, const DirectSystem& sy, double dscale, int run) {
+// One run: the factors G_i and W_i = G_i L_{i,i-1} along it, and y = L^-1 r on its rows of zv.  false: a pivot is not positive.  With
+// failed_at (the host's callers that name the node) the run ends at that position, which is written there; without it (the
+// kernel) the run is factored to its end.
+__host__ __device__ inline bool direct_run_factor(const Direct& dp, const DirectSystem& sy, double dscale, int run,
+                                                  int* failed_at = nullptr) {
   const long long first = dp.run_begin[run];
   const int len = dp.run_len[run];
   bool ok = true;
@@ -1014,7 +1035,13 @@ __host__ __device__ inline bool direct_run_factor(const Direct& dp, const Direct
       d[k] = dscale * sy.D[36 * node + k];
       m[k] = sy.Wc[36 * node + k];
     }
-    if (!chain_factor_node(d, i > 0 ? m : nullptr, gp, gi, x)) ok = false;
+    if (!chain_factor_node(d, i > 0 ? m : nullptr, gp, gi, x)) {
+      ok = false;
+      if (failed_at != nullptr) {
+        *failed_at = i;
+        return false;
+      }
+    }
     chain_w(gi, x, x);
     double r[6], c[6];
 #pragma unroll
@@ -1081,17 +1108,7 @@ __host__ __device__ inline void direct_schur_block(const Direct& dp, const Direc
     for (int q = sy.inc_off[a]; q < sy.inc_off[a + 1]; ++q) {
       const int code = sy.inc[q];
       const long long e = code >> 1;
-      if (((code & 1) ? sy.es[e] : sy.et[e]) != b) continue;
-      const double* H = sy.Hab + 36 * e;
-      if (code & 1) {
-#pragma unroll
-        for (int r = 0; r < 6; ++r)
-#pragma unroll
-          for (int c = 0; c < 6; ++c) acc[6 * r + c] += H[6 * c + r];
-      } else {
-#pragma unroll
-        for (int k = 0; k < 36; ++k) acc[k] += H[k];
-      }
+      if (((code & 1) ? sy.es[e] : sy.et[e]) == b) add_block(acc, sy.Hab + 36 * e, code & 1);
     }
   }
   int i = dp.sc_off[su], j = dp.sc_off[sv];
@@ -1137,15 +1154,7 @@ __host__ __device__ inline void direct_schur_rhs(const Direct& dp, const DirectS
     const int c = dp.sc[i], run = dp.cpl_run[c], p = dp.cpl_pos[c], len = dp.run_len[run];
     const double* Yu = dp.Y + 36ll * dp.cpl_y[c];
     const double* y = sy.zv + 6ll * (dp.run_begin[run] + p);
-    for (int pos = p; pos < len; ++pos, Yu += 36, y += 6) {
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) t += Yu[6 * k + r] * y[k];
-        acc[r] -= t;
-      }
-    }
+    for (int pos = p; pos < len; ++pos, Yu += 36, y += 6) dense_sub_mul(Yu, y, acc, true);
   }
 #pragma unroll
   for (int k = 0; k < 6; ++k) sy.xv[6 * a + k] = acc[k];
@@ -1175,7 +1184,7 @@ __host__ __device__ __forceinline__ void dense_trailing_block(const double* __re
       c[6 * r + q] -= t;
     }
 }
-// z <- L^-1 z and z <- L^-T z with the lower triangle of a 6 x 6 block; r <- r - B z and r <- r - B^T z
+// z <- L^-1 z and z <- L^-T z with the lower triangle of a 6 x 6 block (r <- r - B z and r <- r - B^T z: dense_sub_mul)
 __host__ __device__ __forceinline__ void dense_lower_solve(const double* l, double* z) {
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
@@ -1192,15 +1201,6 @@ __host__ __device__ __forceinline__ void dense_upper_solve(const double* l, doub
 #pragma unroll
     for (int k = i + 1; k < 6; ++k) v -= l[6 * k + i] * z[k];
     z[i] = v / l[6 * i + i];
-  }
-}
-__host__ __device__ __forceinline__ void dense_sub_mul(const double* b, const double* z, double* r, bool transposed) {
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) t += (transposed ? b[6 * k + i] : b[6 * i + k]) * z[k];
-    r[i] -= t;
   }
 }
 
@@ -1240,7 +1240,7 @@ __host__ __device__ inline void direct_run_back(const Direct& dp, const DirectSy
 }
 
 // One workgroup per graph: what phase 1 of pg_solve_kernel<PRE_CHAIN> leaves -- node blocks D, gradient b, x = 0, r = -b, the
-// chain's off-diagonal sums in Wc, the gradient test -- in the same order of sums.
+// chain's off-diagonal sums in Wc (assemble_nodes, the same function), the gradient test.
 __global__ __launch_bounds__(kBlock) void pg_direct_blocks_kernel(Graphs gr, Params p, GraphState* __restrict__ gs,
                                                                   const double* __restrict__ Haa, const double* __restrict__ Hab,
                                                                   const double* __restrict__ Hbb, const double* __restrict__ ga,
@@ -1250,55 +1250,11 @@ __global__ __launch_bounds__(kBlock) void pg_direct_blocks_kernel(Graphs gr, Par
                                                                   int* __restrict__ fail, const int* __restrict__ bad) {
   __shared__ double red[kWaves];
   const int g = blockIdx.x;
-  if (*bad != 0 || gs[g].done) return;  // (uniform over the workgroup)
+  if (skip(gs, g, bad)) return;  // (uniform over the workgroup)
   const int n0 = gr.node_off[g], n = gr.node_off[g + 1] - n0;
   if (threadIdx.x == 0) fail[g] = 0;
-  double gmax = 0.0;
-  for (int i = threadIdx.x; i < n; i += kBlock) {
-    const long long node = n0 + i;
-    double d[36], b[6];
-#pragma unroll
-    for (int k = 0; k < 36; ++k) d[k] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) b[k] = 0.0;
-    if (i > 0) {
-      for (int q = gr.inc_off[node]; q < gr.inc_off[node + 1]; ++q) {
-        const int code = gr.inc[q];
-        const long long e = code >> 1;
-        const double* H = (code & 1) ? Hbb + 36 * e : Haa + 36 * e;
-        const double* v = (code & 1) ? gb + 6 * e : ga + 6 * e;
-#pragma unroll
-        for (int k = 0; k < 36; ++k) d[k] += H[k];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) b[k] += v[k];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 36; ++k) D[36 * node + k] = d[k];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      bv[6 * node + k] = b[k];
-      gmax = fmax(gmax, fabs(2.0 * b[k]));  // the gradient of F is 2 b
-      xv[6 * node + k] = 0.0;
-      rv[6 * node + k] = -b[k];
-    }
-    if (i > 1) {
-      chain_off_block(gr.es, gr.et, gr.inc_off, gr.inc, Hab, node, d);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 36; ++k) d[k] = 0.0;
-    }
-#pragma unroll
-    for (int k = 0; k < 36; ++k) Wc[36 * node + k] = d[k];
-  }
-  gmax = block_max(gmax, red);
-  if (threadIdx.x == 0) {
-    gs[g].grad_max = gmax;
-    if (gmax <= p.gtol) {
-      gs[g].stop = STOP_GRADIENT;
-      gs[g].done = 1;
-    }
-  }
+  const double gmax = assemble_nodes<true>(gr, n0, n, Haa, Hab, Hbb, ga, gb, D, bv, xv, rv, Wc);
+  gradient_stop(gs, g, block_max(gmax, red), p.gtol);
 }
 
 // One thread per run of the call.
@@ -1350,7 +1306,7 @@ __global__ __launch_bounds__(kBlock) void pg_direct_solve_kernel(Direct dp, Dire
   __shared__ double rs[6 * kMaxSeparator];
   __shared__ int fail;
   const int g = blockIdx.x, tid = threadIdx.x;
-  if (*bad != 0 || gs[g].done) return;  // (uniform over the workgroup)
+  if (skip(gs, g, bad)) return;  // (uniform over the workgroup)
   const int s0 = dp.sep_off[g], s = dp.sep_off[g + 1] - s0;
   double* C = dp.C + 36ll * dp.c_off[g];
   if (tid == 0) fail = dp.fail[g];
@@ -1395,10 +1351,7 @@ __global__ __launch_bounds__(kBlock) void pg_direct_solve_kernel(Direct dp, Dire
     __syncthreads();
   }
   if (fail) {  // (uniform: written before barriers that every thread passed)
-    if (tid == 0) {
-      gs[g].status = ST_SINGULAR;
-      gs[g].done = 1;
-    }
+    end_graph(gs, g, ST_SINGULAR);
     return;
   }
   for (int k = 0; k < s; ++k) {  // L_S z = r_S
@@ -1558,7 +1511,8 @@ struct Work {
 };
 
 // The host-built tables; they lie first in the workspace, in one piece, so that the host fills a buffer of the same layout.
-void carve_tables(Arena& ar, size_t G, size_t N, size_t E, Work& w) {
+void carve_tables(Arena& ar, int64_t g, int64_t n, int64_t e, Work& w) {
+  const size_t G = static_cast<size_t>(g > 0 ? g : 1), N = static_cast<size_t>(n > 0 ? n : 1), E = static_cast<size_t>(e > 0 ? e : 1);
   w.node_off = ar.take<int>(G + 1);
   w.edge_off = ar.take<int>(G + 1);
   w.edge_graph = ar.take<int>(E);
@@ -1633,6 +1587,27 @@ struct DirectPlan {  // Direct's tables on the host
   std::vector<long long> c_off, item_off;
   long long y_blocks = 0;
 };
+
+// The ONE list of the tables (plan member, Direct member), in the order in which they lie in the workspace: the carve, the fill
+// and the host's view of a plan all walk it, so a table is named here and in the two structs and nowhere else.
+template <typename T>
+struct DirectTable {
+  std::vector<T> DirectPlan::*plan;
+  const T* Direct::*table;
+};
+constexpr DirectTable<int> kDirectInts[] = {
+    {&DirectPlan::sep_off, &Direct::sep_off},     {&DirectPlan::sep_node, &Direct::sep_node},   {&DirectPlan::run_off, &Direct::run_off},
+    {&DirectPlan::run_begin, &Direct::run_begin}, {&DirectPlan::run_len, &Direct::run_len},     {&DirectPlan::run_graph, &Direct::run_graph},
+    {&DirectPlan::cpl_off, &Direct::cpl_off},     {&DirectPlan::cpl_sep, &Direct::cpl_sep},     {&DirectPlan::cpl_run, &Direct::cpl_run},
+    {&DirectPlan::cpl_pos, &Direct::cpl_pos},     {&DirectPlan::cpl_y, &Direct::cpl_y},         {&DirectPlan::ent_off, &Direct::ent_off},
+    {&DirectPlan::ent_pos, &Direct::ent_pos},     {&DirectPlan::ent_code, &Direct::ent_code},   {&DirectPlan::sc_off, &Direct::sc_off},
+    {&DirectPlan::sc, &Direct::sc}};
+constexpr DirectTable<long long> kDirectLongs[] = {{&DirectPlan::c_off, &Direct::c_off}, {&DirectPlan::item_off, &Direct::item_off}};
+template <typename Visit>
+void for_each_direct_table(const DirectPlan& pl, Direct& d, Visit visit) {  // visit(the plan's vector, Direct's pointer to the table)
+  for (const auto& t : kDirectInts) visit(pl.*t.plan, d.*t.table);
+  for (const auto& t : kDirectLongs) visit(pl.*t.plan, d.*t.table);
+}
 
 // The plan of a call from its tables (global node numbers; inc in ascending edge order).  false, with the error set: a graph's
 // separator is above the cap, or Y is too large to index.
@@ -1730,25 +1705,9 @@ bool build_direct_plan(int64_t G, const int* node_off, const int* edge_off, cons
 
 // Direct's tables in the workspace, behind the other host-built tables and uploaded with them.
 void carve_direct_tables(Arena& ar, const DirectPlan& pl, Work& w, Direct& d) {
-  auto ints = [&](const std::vector<int>& v) { return ar.take<int>(v.size() > 0 ? v.size() : 1); };
-  d.sep_off = ints(pl.sep_off);
-  d.sep_node = ints(pl.sep_node);
-  d.run_off = ints(pl.run_off);
-  d.run_begin = ints(pl.run_begin);
-  d.run_len = ints(pl.run_len);
-  d.run_graph = ints(pl.run_graph);
-  d.cpl_off = ints(pl.cpl_off);
-  d.cpl_sep = ints(pl.cpl_sep);
-  d.cpl_run = ints(pl.cpl_run);
-  d.cpl_pos = ints(pl.cpl_pos);
-  d.cpl_y = ints(pl.cpl_y);
-  d.ent_off = ints(pl.ent_off);
-  d.ent_pos = ints(pl.ent_pos);
-  d.ent_code = ints(pl.ent_code);
-  d.sc_off = ints(pl.sc_off);
-  d.sc = ints(pl.sc);
-  d.c_off = ar.take<long long>(pl.c_off.size());
-  d.item_off = ar.take<long long>(pl.item_off.size());
+  for_each_direct_table(pl, d, [&](const auto& v, auto& table) {
+    table = ar.take<typename std::decay_t<decltype(v)>::value_type>(v.size() > 0 ? v.size() : 1);
+  });
   w.ints_bytes = ar.off;
 }
 void carve_direct_arrays(Arena& ar, const DirectPlan& pl, size_t G, Direct& d) {
@@ -1757,36 +1716,17 @@ void carve_direct_arrays(Arena& ar, const DirectPlan& pl, size_t G, Direct& d) {
   d.fail = ar.take<int>(G);
 }
 // The plan's tables into a host buffer laid out as carve_direct_tables lays the workspace out (h: the same carve on that buffer).
-void fill_direct_tables(const DirectPlan& pl, const Direct& h) {
-  auto put = [](const void* dst, const auto& v) {
-    if (!v.empty()) memcpy(const_cast<void*>(dst), v.data(), v.size() * sizeof(v[0]));
-  };
-  put(h.sep_off, pl.sep_off);
-  put(h.sep_node, pl.sep_node);
-  put(h.run_off, pl.run_off);
-  put(h.run_begin, pl.run_begin);
-  put(h.run_len, pl.run_len);
-  put(h.run_graph, pl.run_graph);
-  put(h.cpl_off, pl.cpl_off);
-  put(h.cpl_sep, pl.cpl_sep);
-  put(h.cpl_run, pl.cpl_run);
-  put(h.cpl_pos, pl.cpl_pos);
-  put(h.cpl_y, pl.cpl_y);
-  put(h.ent_off, pl.ent_off);
-  put(h.ent_pos, pl.ent_pos);
-  put(h.ent_code, pl.ent_code);
-  put(h.sc_off, pl.sc_off);
-  put(h.sc, pl.sc);
-  put(h.c_off, pl.c_off);
-  put(h.item_off, pl.item_off);
+void fill_direct_tables(const DirectPlan& pl, Direct h) {  // (h by value: the walk hands out its pointers, which are not changed)
+  for_each_direct_table(pl, h, [](const auto& v, auto& table) {
+    if (!v.empty()) memcpy(const_cast<void*>(static_cast<const void*>(table)), v.data(), v.size() * sizeof(v[0]));
+  });
 }
-
 
 // plan: the direct solve's (null: conjugate gradients, and the layout is what it was)
 bool carve(Arena& ar, int64_t g, int64_t n, int64_t e, int preconditioner, Work& w, const DirectPlan* plan = nullptr,
            Direct* direct = nullptr) {
   const size_t G = static_cast<size_t>(g > 0 ? g : 1), N = static_cast<size_t>(n > 0 ? n : 1), E = static_cast<size_t>(e > 0 ? e : 1);
-  carve_tables(ar, G, N, E, w);
+  carve_tables(ar, g, n, e, w);
   if (plan) carve_direct_tables(ar, *plan, w, *direct);
   w.flags = ar.take<int>(4);
   w.gs = ar.take<GraphState>(G);
@@ -1870,26 +1810,39 @@ int fill_tables(int64_t G, const int64_t* graph_node_offsets_host, const int64_t
   return RDM_OK;
 }
 
+// `host` grown (with zeros; what it holds stays) to what layout(Arena&) carves, and carved: once on a null arena for the size, then
+// on the buffer.
+template <typename Layout>
+void carve_host(std::vector<char>& host, Layout layout) {
+  Arena sizes(nullptr, 0);
+  layout(sizes);
+  host.resize(sizes.off, 0);
+  Arena ar(host.data(), host.size());
+  layout(ar);
+}
+
+// The integer tables of a call, filled, in a host buffer laid out as the workspace's first part; t: their view on `host`.
+int fill_host_tables(int64_t G, const int64_t* graph_node_offsets_host, const int64_t* graph_edge_offsets_host,
+                     const int64_t* edges_host, const uint8_t* uncertain_host, std::vector<char>& host, Work& t) {
+  const int64_t N = graph_node_offsets_host[G], E = graph_edge_offsets_host[G];
+  host.clear();
+  carve_host(host, [&](Arena& ar) { carve_tables(ar, G, N, E, t); });
+  return fill_tables(G, graph_node_offsets_host, graph_edge_offsets_host, edges_host, uncertain_host, t);
+}
+
 // The host-built tables of a call in one buffer laid out as the workspace's first part; with `plan`, the direct solve's behind them.
 int build_host_tables(int64_t G, const int64_t* graph_node_offsets_host, const int64_t* graph_edge_offsets_host,
                       const int64_t* edges_host, const uint8_t* uncertain_host, std::vector<char>& host, DirectPlan* plan) {
-  const int64_t N = graph_node_offsets_host[G], E = graph_edge_offsets_host[G];
-  const size_t Gs = static_cast<size_t>(G), Ns = static_cast<size_t>(N > 0 ? N : 1), Es = static_cast<size_t>(E > 0 ? E : 1);
-  Arena sizes(nullptr, 0);
   Work t;
-  carve_tables(sizes, Gs, Ns, Es, t);
-  host.assign(sizes.off, 0);
-  Arena har(host.data(), host.size());
-  carve_tables(har, Gs, Ns, Es, t);
-  const int rc = fill_tables(G, graph_node_offsets_host, graph_edge_offsets_host, edges_host, uncertain_host, t);
+  const int rc = fill_host_tables(G, graph_node_offsets_host, graph_edge_offsets_host, edges_host, uncertain_host, host, t);
   if (rc != RDM_OK || plan == nullptr) return rc;
   if (!build_direct_plan(G, t.node_off, t.edge_off, t.es, t.et, t.inc_off, t.inc, *plan, "rdm_pose_graph_optimize")) return RDM_ERR_ARG;
+  const int64_t N = graph_node_offsets_host[G], E = graph_edge_offsets_host[G];
   Direct d;
-  carve_direct_tables(sizes, *plan, t, d);
-  host.resize(sizes.off, 0);
-  Arena all(host.data(), host.size());
-  carve_tables(all, Gs, Ns, Es, t);
-  carve_direct_tables(all, *plan, t, d);
+  carve_host(host, [&](Arena& ar) {  // (the filled tables lie first and stay)
+    carve_tables(ar, G, N, E, t);
+    carve_direct_tables(ar, *plan, t, d);
+  });
   fill_direct_tables(*plan, d);
   return RDM_OK;
 }
@@ -1921,38 +1874,30 @@ extern "C" int rdm_pose_graph_chain_host(int64_t n, const double* diag, const do
   RDM_REQUIRE(n >= 0 && n < kMaxTotal, "rdm_pose_graph_chain_host: bad number of nodes");
   if (n == 0) return RDM_OK;
   RDM_REQUIRE(diag && rhs && out && (off || n == 1), "rdm_pose_graph_chain_host: null argument");
+  // the chain is one run of the direct solve without a separator: nodes 0 .. n - 1, no coupling
   const size_t N = static_cast<size_t>(n);
-  std::vector<double> G(21 * N), W(36 * N), v(6 * N);
-  for (size_t i = 0; i < N; ++i) {
-    double m[36], x[36];
-    if (i > 0)  // M_{i,i-1} is the transpose of block (i - 1, i)
-      for (int r = 0; r < 6; ++r)
-        for (int c = 0; c < 6; ++c) m[6 * r + c] = off[36 * (i - 1) + 6 * c + r];
-    if (!chain_factor_node(diag + 36 * i, i > 0 ? m : nullptr, i > 0 ? &G[21 * (i - 1)] : nullptr, &G[21 * i], x)) {
-      set_error("rdm_pose_graph_chain_host: the pivot of node %zu is not positive definite", i);
-      return RDM_ERR_ARG;
-    }
-    chain_w(&G[21 * i], x, &W[36 * i]);
+  std::vector<double> F(21 * N), Wc(36 * N, 0.0), zv(6 * N);
+  for (size_t i = 1; i < N; ++i)  // M_{i,i-1} is the transpose of block (i - 1, i)
+    for (int r = 0; r < 6; ++r)
+      for (int c = 0; c < 6; ++c) Wc[36 * i + 6 * r + c] = off[36 * (i - 1) + 6 * c + r];
+  const int run_begin = 0, run_len = static_cast<int>(n), cpl_off[2] = {0, 0};
+  Direct dp = {};
+  dp.run_begin = &run_begin;
+  dp.run_len = &run_len;
+  dp.cpl_off = cpl_off;
+  DirectSystem sy = {};
+  sy.D = diag;
+  sy.rv = rhs;
+  sy.F = F.data();
+  sy.Wc = Wc.data();
+  sy.zv = zv.data();
+  sy.xv = out;
+  int failed = -1;
+  if (!direct_run_factor(dp, sy, 1.0, 0, &failed)) {
+    set_error("rdm_pose_graph_chain_host: the pivot of node %d is not positive definite", failed);
+    return RDM_ERR_ARG;
   }
-  double y[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (size_t i = 0; i < N; ++i) {  // c = G r, then the forward sweep
-    double c[6];
-    chain_g_mul(&G[21 * i], rhs + 6 * i, c);
-    for (int r = 0; r < 6; ++r) v[6 * i + r] = chain_row(c[r], &W[36 * i + 6 * r], y);
-    for (int r = 0; r < 6; ++r) y[r] = v[6 * i + r];
-  }
-  for (int r = 0; r < 6; ++r) y[r] = 0.0;
-  for (size_t i = N; i-- > 0;) {  // the backward sweep on q = L_ii^T z, then z = G^T q
-    double q[6];
-    for (int r = 0; r < 6; ++r) {
-      double col[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-      if (i + 1 < N)
-        for (int c = 0; c < 6; ++c) col[c] = W[36 * (i + 1) + 6 * c + r];
-      q[r] = chain_row(v[6 * i + r], col, y);
-    }
-    for (int r = 0; r < 6; ++r) y[r] = q[r];
-    chain_gt_mul(&G[21 * i], q, out + 6 * i);
-  }
+  direct_run_back(dp, sy, 0);
   return RDM_OK;
 }
 
@@ -1981,18 +1926,10 @@ extern "C" int rdm_pose_graph_direct_host(int64_t n_nodes, int64_t n_edges, cons
   const int64_t noff[2] = {0, n_nodes}, eoff[2] = {0, n_edges};
   std::vector<char> host;
   DirectPlan plan;
-  {  // the tables of a one-graph call; edges that touch node 0 stay out of the incidence lists (they hold no block of the system)
-    Arena sizes(nullptr, 0);
-    Work t;
-    carve_tables(sizes, 1, static_cast<size_t>(n_nodes), static_cast<size_t>(n_edges > 0 ? n_edges : 1), t);
-    host.assign(sizes.off, 0);
-  }
-  Arena har(host.data(), host.size());
   Work t;
-  carve_tables(har, 1, static_cast<size_t>(n_nodes), static_cast<size_t>(n_edges > 0 ? n_edges : 1), t);
-  int rc = fill_tables(1, noff, eoff, edges_host, nullptr, t);
+  const int rc = fill_host_tables(1, noff, eoff, edges_host, nullptr, host, t);
   if (rc != RDM_OK) return rc;
-  {
+  {  // edges that touch node 0 stay out of the incidence lists (they hold no block of the system)
     int kept = 0;
     std::vector<int> inc_off(static_cast<size_t>(n_nodes) + 1, 0);
     for (int64_t i = 0; i < n_nodes; ++i) {
@@ -2010,11 +1947,11 @@ extern "C" int rdm_pose_graph_direct_host(int64_t n_nodes, int64_t n_edges, cons
   std::vector<double> F(21 * N), Wc(36 * N, 0.0), zv(6 * N, 0.0), xv(6 * N, 0.0), C(36 * static_cast<size_t>(plan.c_off.back()) + 36),
       Y(36 * static_cast<size_t>(plan.y_blocks) + 36);
   int fail = 0;
-  auto data = [](const auto& v) { return v.empty() ? nullptr : v.data(); };
-  const Direct dp = {data(plan.sep_off), data(plan.sep_node), data(plan.run_off), data(plan.run_begin), data(plan.run_len),
-                     data(plan.run_graph), data(plan.cpl_off), data(plan.cpl_sep), data(plan.cpl_run), data(plan.cpl_pos),
-                     data(plan.cpl_y), data(plan.ent_off), data(plan.ent_pos), data(plan.ent_code), data(plan.sc_off), data(plan.sc),
-                     data(plan.c_off), data(plan.item_off), C.data(), Y.data(), &fail};
+  Direct dp = {};
+  for_each_direct_table(plan, dp, [](const auto& v, auto& table) { table = v.empty() ? nullptr : v.data(); });
+  dp.C = C.data();
+  dp.Y = Y.data();
+  dp.fail = &fail;
   const DirectSystem sy = {t.es, t.et, t.inc_off, t.inc, diag, off, rhs, F.data(), Wc.data(), zv.data(), xv.data()};
   for (int64_t i = 2; i < n_nodes; ++i) chain_off_block(t.es, t.et, t.inc_off, t.inc, off, i, &Wc[36 * i]);
   const int runs = static_cast<int>(plan.run_begin.size()), couplings = static_cast<int>(plan.cpl_sep.size()), s = plan.sep_off[1];

@@ -153,25 +153,34 @@ def test_drive_with_loops_needs_a_quarter_of_the_iterations(mu):
 
 # ---- 7. direction and multiplicity ----------------------------------------------------------------------------------------------
 
-def test_edge_direction_and_doubled_pairs():
+def six_node_case():
     """Six nodes; the odometry edges alternate (i + 1, i) and (i, i + 1), the pair 2 - 3 carries two more edges, one in each direction,
     and one loop edge joins 5 and 1 (off the chain: diagonal only)."""
     rng = np.random.default_rng(12)
     edges = [(1, 0), (1, 2), (3, 2), (3, 4), (5, 4), (2, 3), (3, 2), (5, 1)]
-    c = cases.make([cases.random_pose(rng) for _ in range(6)], edges, rng)
-    res = solve(c, max_iterations=10, gradient_tolerance=0.0, cost_tolerance=0.0, preconditioner='chain')
+    return cases.make([cases.random_pose(rng) for _ in range(6)], edges, rng)
+
+
+@pytest.mark.parametrize('how', [dict(preconditioner='chain'), dict(linear_solver='direct')], ids=['chain', 'direct'])
+def test_edge_direction_and_doubled_pairs(how):
+    """six_node_case() under the chain preconditioner and under the direct solve, which add the same blocks by the same function."""
+    c = six_node_case()
+    res = solve(c, max_iterations=10, gradient_tolerance=0.0, cost_tolerance=0.0, **how)
     ang, tra = R.pose_errors(res.nodes.cpu().numpy(), c['truth'])
     print('angle', ang, 'translation', tra, 'iterations', res.iterations[0], 'pcg', res.pcg_iterations[0])
     assert ang <= POSE_BOUND and tra <= POSE_BOUND
     # without the loop edge M is the system, so (as on tree()) the conjugate gradients end after one iteration, two with rounding;
     # a block transposed the wrong way or a doubled edge left out would leave them the difference to work off
-    keep = np.arange(len(edges)) != 7
+    keep = np.arange(len(c['edges'])) != 7
     d = dict(c, edges=c['edges'][keep], transforms=c['transforms'][keep], informations=c['informations'][keep], uncertain=c['uncertain'][keep])
-    res = solve(d, max_iterations=10, gradient_tolerance=0.0, cost_tolerance=0.0, preconditioner='chain')
+    res = solve(d, max_iterations=10, gradient_tolerance=0.0, cost_tolerance=0.0, **how)
     ang, tra = R.pose_errors(res.nodes.cpu().numpy(), c['truth'])
     print('without the loop edge: angle', ang, 'translation', tra, 'iterations', res.iterations[0], 'pcg', res.pcg_iterations[0])
     assert ang <= POSE_BOUND and tra <= POSE_BOUND
-    assert res.iterations[0] > 0 and res.pcg_iterations[0] <= 2 * res.iterations[0]
+    if 'preconditioner' in how:
+        assert res.iterations[0] > 0 and res.pcg_iterations[0] <= 2 * res.iterations[0]
+    else:
+        assert res.iterations[0] > 0 and res.pcg_iterations[0] == 0
 
 
 # ---- 8. batch invariance --------------------------------------------------------------------------------------------------------

@@ -224,6 +224,8 @@ SHAPES = {
     'separator at the last node': (8, [(7, 2), (7, 4)], [7]),
     'adjacent separators': (14, [(3, 6), (3, 8), (4, 10), (4, 12)], [3, 4]),
     'chord between separators': (14, [(3, 6), (3, 8), (10, 5), (10, 12), (3, 10)], [3, 10]),
+    # (random_system stores the two (3, 10) chords as (10, 3) and (3, 10): both transposition conventions in one Schur block)
+    'double edge between separators': (14, [(3, 6), (3, 8), (10, 5), (10, 12), (3, 10), (3, 10)], [3, 10]),
     'three chords into three runs': (16, [(4, 1), (4, 7), (12, 9), (12, 15), (8, 2), (8, 6), (8, 10), (8, 14)], [4, 8, 12]),
     'two chords into one run': (12, [(2, 6), (2, 9)], [2]),
     'double edge on a chord': (10, [(2, 6), (2, 6)], [2]),

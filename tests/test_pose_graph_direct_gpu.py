@@ -157,6 +157,7 @@ SHAPES = {
     'separator at the last node': (8, [(7, 2), (7, 4)]),
     'adjacent separators': (14, [(3, 6), (3, 8), (4, 10), (4, 12)]),
     'chord between separators': (14, [(3, 6), (3, 8), (10, 5), (10, 12), (3, 10)]),
+    'double edge between separators': (14, [(3, 6), (3, 8), (10, 5), (10, 12), (3, 10), (3, 10)]),
     'run of one node': (12, [(3, 7), (3, 9), (5, 1), (5, 11)]),
     'chain of 300 with one chord': (300, [(10, 290)]),
 }

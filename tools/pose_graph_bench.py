@@ -4,11 +4,14 @@ for comparison: the restatement's dense solve (tests/pose_graph_restatement.py, 
 and, where scipy is importable, the same damped Gauss-Newton iteration with a sparse direct solve (scipy.sparse.linalg.spsolve).
 
   python tools/pose_graph_bench.py [--nodes 500] [--loops 40] [--batch 11] [--reps 3] [--cpu] [--preconditioner chain]
-                                     [--linear-solver direct]
-Prints one JSON line: sizes, GPU ms per call (median; a call ends with its read-back), outer iterations, PCG iterations per outer
+                                     [--linear-solver direct] [--digest host | gpu]
+With --digest (and nothing else): no timing, one sha1 line per result of the library's host entry points (host: no GPU needed, see
+digest_host()) or of the GPU solves of the test graphs (gpu, see digest_gpu()), for comparing the bits of two builds of the library
+(RDM_LIB_PATH).  Otherwise prints one JSON line: sizes, GPU ms per call (median; a call ends with its read-back), outer iterations, PCG iterations per outer
 iteration, and the host's ms per solve.  --preconditioner (block_jacobi | chain) is passed to ops.pose_graph_optimize and named in
 the output; without the flag the call and the output are what they were.  --linear-solver (pcg | direct) likewise."""
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -81,8 +84,112 @@ def sparse_solve(R, c, max_iterations=TOL['max_iterations']):
     return F, steps
 
 
+def sha1_line(what, arrays):
+    h = hashlib.sha1()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    print(f'{h.hexdigest()}  {what}', flush=True)
+
+
+def digest_host():
+    """One `sha1  what` line over the raw bytes that the library's host entry points return (no GPU): the chain solve on
+    chain_system of tests/test_pose_graph_chain.py, the direct solve and the separator on every shape of
+    tests/test_pose_graph_direct.py, the edge terms and the retraction on cases.noisy(), and the three workspace sizes."""
+    import ctypes
+    import pose_graph_cases as cases
+    import test_pose_graph_chain as tc
+    import test_pose_graph_direct as td
+    from rdmnet_amd import _lib
+    L = _lib.lib()
+    for n in (1, 2, 3, 50, 300):
+        diag, off, _ = tc.chain_system(n, seed=100 + n)
+        rhs = np.ascontiguousarray(np.random.default_rng(n).normal(size=(n, 6)) * 100.0)
+        rc, out = tc.chain_host(diag, off, rhs)
+        sha1_line(f'chain_host n {n} rc {rc}', [out])
+    for name, (n, chords, _) in td.SHAPES.items():
+        edges, diag, off, rhs = td.random_system(n, chords, seed=200 + n + len(chords))
+        rc, out = td.direct_host(n, edges, diag, off, rhs)
+        sha1_line(f'direct_host {name} rc {rc}', [out])
+        size, sep = td.separator(n, edges)
+        sha1_line(f'separator_host {name} size {size}', [sep])
+    c = cases.noisy()
+    terms = np.zeros((len(c['edges']), 128))
+    for e, (s, t) in enumerate(c['edges'].tolist()):
+        Xs, Xt, T, Lm = (np.ascontiguousarray(a, dtype=np.float64) for a in (c['nodes'][s], c['nodes'][t], c['transforms'][e],
+                                                                              c['informations'][e]))
+        rc = L.rdm_pose_graph_edge_terms_host(Xs.ctypes.data, Xt.ctypes.data, T.ctypes.data, Lm.ctypes.data, ctypes.c_double(MU),
+                                              int(c['uncertain'][e]), terms[e].ctypes.data)
+        assert rc == 0
+    sha1_line('edge_terms_host noisy', [terms])
+    rng = np.random.default_rng(0)
+    moved = np.zeros_like(c['nodes'])
+    for i, X in enumerate(c['nodes']):
+        d = np.ascontiguousarray(rng.normal(size=6) * (0.01 if i % 2 else 1.0))  # (both branches of the series)
+        assert L.rdm_pose_graph_retract_host(np.ascontiguousarray(X).ctypes.data, d.ctypes.data, moved[i].ctypes.data) == 0
+    sha1_line('retract_host noisy', [moved])
+    for G, N, E in ((1, 1, 0), (1, 2, 1), (3, 700, 760), (11, 5500, 5929)):
+        # G chains of N / G nodes (the first ones one longer), the other edges as chords (s, s - 2 - k) dealt out in turn
+        sizes = [N // G + (1 if g < N % G else 0) for g in range(G)]
+        extra = [(E - (N - G)) // G + (1 if g < (E - (N - G)) % G else 0) for g in range(G)]
+        edges = [[(i + 1, i) for i in range(n - 1)] + [(n - 1 - 3 * k, n - 3 - 4 * k) for k in range(x)] for n, x in zip(sizes, extra)]
+        noff = np.cumsum([0] + sizes).astype(np.int64)
+        eoff = np.cumsum([0] + [len(e) for e in edges]).astype(np.int64)
+        assert noff[-1] == N and eoff[-1] == E
+        ed = np.array([p for e in edges for p in e], np.int64).reshape(-1, 2)
+        got = [L.rdm_pose_graph_workspace_bytes(G, N, E)]
+        got += [L.rdm_pose_graph_workspace_bytes_pc(G, N, E, pre) for pre in (0, 1)]
+        got += [L.rdm_pose_graph_workspace_bytes_ls(G, noff.ctypes.data, eoff.ctypes.data, ed.ctypes.data, pre, solver)
+                for pre in (0, 1) for solver in (0, 1)]
+        assert all(v > 0 for v in got), got
+        sha1_line(f'workspace_bytes G {G} N {N} E {E}', [np.array(got, np.uint64)])
+
+
+def digest_gpu():
+    """One `sha1  what` line over nodes, weights, pruned and the report of ops.pose_graph_optimize for the graphs of the GPU tests
+    (every consistent case, noisy() with and without a gross edge, the 150-scan drive with and without a line process, the six-node
+    case of mixed directions and doubled pairs, and the one-node, two-node, 60-node batch), each under block-Jacobi PCG, chain PCG
+    and the direct solve, alone and as one batch of all of them.  Two libraries (RDM_LIB_PATH) compute the same bits iff they print
+    the same lines."""
+    import torch
+    import pose_graph_cases as cases
+    import test_pose_graph_chain_gpu as tg
+    import test_pose_graph_direct_gpu as tdg
+    from rdmnet_amd import ops
+    ten = dict(max_iterations=10, gradient_tolerance=0.0, cost_tolerance=0.0)
+    tol = dict(gradient_tolerance=1e-9, cost_tolerance=1e-12)
+    one = {k: cases.consistent('pair')[k][:1] if k == 'nodes' else cases.consistent('pair')[k][:0] for k in tg.KEYS}
+    drive = tdg.drive()
+    runs = [(name, [cases.consistent(name)], ten) for name in cases.CONSISTENT]
+    runs += [('noisy', [cases.noisy()], dict(line_process_weight=MU, **tol)),
+             ('noisy gross 3', [cases.noisy(gross=3)], dict(line_process_weight=MU, **tol)),
+             ('drive 150', [drive], dict(max_iterations=30, **tol)),
+             ('drive 150 mu', [drive], dict(line_process_weight=MU, max_iterations=30, **tol)),
+             ('six nodes', [tg.six_node_case()], ten),
+             ('sizes 1, 2, 60', [one, cases.consistent('pair'), cases.noisy()], tol)]
+    everything = [g for name, graphs, _ in runs if name != 'drive 150 mu' for g in graphs]
+    runs += [('all', everything, dict(max_iterations=30, **tol)), ('all mu', everything, dict(line_process_weight=MU, max_iterations=30, **tol))]
+    solvers = (('block_jacobi', dict(preconditioner='block_jacobi')), ('chain', dict(preconditioner='chain')),
+               ('direct', dict(linear_solver='direct')))
+    fields = ('initial_cost', 'final_cost', 'iterations', 'pcg_iterations', 'stop_reason', 'damping', 'gradient_max')
+    for name, graphs, kw in runs:
+        noff = np.cumsum([0] + [len(g['nodes']) for g in graphs])
+        eoff = np.cumsum([0] + [len(g['edges']) for g in graphs])
+        cat = {k: np.concatenate([g[k] for g in graphs]) for k in tg.KEYS}
+        for solver, extra in solvers:
+            res = ops.pose_graph_optimize(torch.from_numpy(cat['nodes']).cuda(), cat['edges'], torch.from_numpy(cat['transforms']).cuda(),
+                                          torch.from_numpy(cat['informations']).cuda(), cat['uncertain'], graph_node_offsets=noff,
+                                          graph_edge_offsets=eoff, **kw, **extra)
+            nodes, weights, pruned = res.nodes.cpu().numpy(), res.weights.cpu().numpy(), res.pruned.cpu().numpy()
+            for k in range(len(graphs)):
+                report = np.array([getattr(res, f)[k] for f in fields], np.float64)
+                sha1_line(f'{name} graph {k} {solver} steps {res.iterations[k]} pcg {res.pcg_iterations[k]}',
+                          [nodes[noff[k]:noff[k + 1]], weights[eoff[k]:eoff[k + 1]], pruned[eoff[k]:eoff[k + 1]], report])
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--digest', choices=('host', 'gpu'), default=None,
+                    help='no timing: the sha1 lines of the host entry points (no GPU needed) or of the GPU solves')
     ap.add_argument('--nodes', type=int, default=500)
     ap.add_argument('--loops', type=int, default=40)
     ap.add_argument('--batch', type=int, default=11)
@@ -91,6 +198,8 @@ def main():
     ap.add_argument('--preconditioner', choices=('block_jacobi', 'chain'), default=None)
     ap.add_argument('--linear-solver', choices=('pcg', 'direct'), default=None)
     a = ap.parse_args()
+    if a.digest is not None:
+        return digest_host() if a.digest == 'host' else digest_gpu()
     import torch
     from rdmnet_amd import ops
     import pose_graph_restatement as R
