@@ -46,9 +46,6 @@ __device__ __forceinline__ void rope_body(const dim3 blockIdx, const dim3 gridDi
     b[1] = k1 * c + k0 * s;
   }
 }
-__global__ __launch_bounds__(256) void rope_kernel(float* q, int ldq, float* k, int ldk, const float* emb, int lde, int n, int pairs) {
-  rope_body(blockIdx, gridDim, q, ldq, k, ldk, emb, lde, n, pairs);
-}
 
 struct AttnArgs {
   const float* q;
@@ -224,8 +221,6 @@ __device__ __forceinline__ void attention_body(const dim3 blockIdx, const dim3 g
       *reinterpret_cast<float2*>(a.out + static_cast<int64_t>(qi) * a.ldo + hoff + dd) = make_float2(a0 / lt, a1 / lt);
   }
 }
-template <bool BF16>
-__global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) { attention_body<BF16>(blockIdx, gridDim, a); }
 
 // vote.py:98-108: xyz + clamp(offset, -limit, +limit)
 __device__ __forceinline__ void vote_shift_kernel_body(const dim3 blockIdx, const dim3 gridDim, const float* xyz, const float* off, int ldo, int n, float lx, float ly,
@@ -240,8 +235,6 @@ __device__ __forceinline__ void vote_shift_kernel_body(const dim3 blockIdx, cons
   o = o < -lim ? -lim : o;
   out[i] = xyz[i] + o;
 }
-__global__ void vote_shift_kernel(const float* xyz, const float* off, int ldo, int n, float lx, float ly,
-                                  float lz, float* out) { vote_shift_kernel_body(blockIdx, gridDim, xyz, off, ldo, n, lx, ly, lz, out); }
 
 
 // sigmoid + clamp[0,1] of a strided column (model_infer.py:161-162, 171-172, 199-202)
@@ -252,7 +245,6 @@ __device__ __forceinline__ void sigmoid_kernel_body(const dim3 blockIdx, const d
   float s = 1.0f / (1.0f + expf(-x[static_cast<int64_t>(i) * ldx]));
   out[i] = fminf(fmaxf(s, 0.f), 1.f);
 }
-__global__ void sigmoid_kernel(const float* x, int ldx, int n, float* out) { sigmoid_kernel_body(blockIdx, gridDim, x, ldx, n, out); }
 
 
 // F.normalize(p=2, dim=1) (model_infer.py:248-249); one wavefront per row
@@ -269,7 +261,6 @@ __device__ __forceinline__ void l2_normalize_kernel_body(const dim3 blockIdx, co
   const float nrm = fmaxf(__fsqrt_rn(wave_sum(s)), 1e-12f);
   for (int i = lane; i < c; i += 64) y[static_cast<int64_t>(row) * ldy + i] = x[static_cast<int64_t>(row) * ldx + i] / nrm;
 }
-__global__ void l2_normalize_kernel(const float* x, int ldx, int n, int c, float* y, int ldy) { l2_normalize_kernel_body(blockIdx, gridDim, x, ldx, n, c, y, ldy); }
 
 
 }  // namespace
@@ -281,7 +272,7 @@ extern "C" int rdm_rope(float* q, int64_t ldq, float* k, int64_t ldk, const floa
   if (n == 0) return RDM_OK;  // (torch hands zero-row tensors over as null pointers)
   RDM_REQUIRE(q && emb, "rdm_rope: null pointer");
   const int pairs = static_cast<int>(d_model / 2);
-  launch<rope_body, rope_kernel, 256>(dim3(ceil_div<int64_t>(n * pairs, 256)), 0, static_cast<hipStream_t>(stream), q,
+  launch<rope_body, 256>(dim3(ceil_div<int64_t>(n * pairs, 256)), 0, static_cast<hipStream_t>(stream), q,
                                       static_cast<int>(ldq), k, static_cast<int>(ldk), emb, static_cast<int>(lde), static_cast<int>(n), pairs);
   return launch_status("rope_kernel");
 }
@@ -305,9 +296,9 @@ static int attention_launch(const float* q, int64_t ldq, const float* k, int64_t
   const dim3 grid(ceil_div<int64_t>(n_q, 16), heads);
   RDM_DUP_LOOP("attn")
   if (bf16)
-    launch<attention_body<true>, attention_kernel<true>, 256>(grid, 0, static_cast<hipStream_t>(stream), a);
+    launch<attention_body<true>, 256>(grid, 0, static_cast<hipStream_t>(stream), a);
   else
-    launch<attention_body<false>, attention_kernel<false>, 256>(grid, 0, static_cast<hipStream_t>(stream), a);
+    launch<attention_body<false>, 256>(grid, 0, static_cast<hipStream_t>(stream), a);
   return launch_status("attention_kernel");
 }
 
@@ -344,9 +335,9 @@ extern "C" int rdm_attention_self_pair(const float* q, int64_t ldq, const float*
   const dim3 grid(a.seg0_blocks + ceil_div<int64_t>(n1, 16), heads);
   RDM_DUP_LOOP("attn")
   if (bf16)
-    launch<attention_body<true>, attention_kernel<true>, 256>(grid, 0, static_cast<hipStream_t>(stream), a);
+    launch<attention_body<true>, 256>(grid, 0, static_cast<hipStream_t>(stream), a);
   else
-    launch<attention_body<false>, attention_kernel<false>, 256>(grid, 0, static_cast<hipStream_t>(stream), a);
+    launch<attention_body<false>, 256>(grid, 0, static_cast<hipStream_t>(stream), a);
   return launch_status("attention_kernel");
 }
 
@@ -362,7 +353,7 @@ extern "C" int rdm_vote_shift(const float* xyz, const float* offsets, int64_t ld
   RDM_REQUIRE(n >= 0, "rdm_vote_shift: bad arguments");
   if (n == 0) return RDM_OK;
   RDM_REQUIRE(xyz && offsets && out, "rdm_vote_shift: null pointer");
-  ::rdm::launch<vote_shift_kernel_body, vote_shift_kernel, 256>(dim3(ceil_div<int64_t>(3 * n, 256)), 0, static_cast<hipStream_t>(stream), xyz, offsets, static_cast<int>(ldo), static_cast<int>(n), lx,
+  ::rdm::launch<vote_shift_kernel_body, 256>(dim3(ceil_div<int64_t>(3 * n, 256)), 0, static_cast<hipStream_t>(stream), xyz, offsets, static_cast<int>(ldo), static_cast<int>(n), lx,
                      ly, lz, out);
   return launch_status("vote_shift_kernel");
 }
@@ -372,7 +363,7 @@ extern "C" int rdm_sigmoid_column(const float* x, int64_t ldx, int64_t n, float*
   RDM_REQUIRE(n >= 0, "rdm_sigmoid_column: bad arguments");
   if (n == 0) return RDM_OK;
   RDM_REQUIRE(x && out, "rdm_sigmoid_column: null pointer");
-  ::rdm::launch<sigmoid_kernel_body, sigmoid_kernel, 256>(dim3(ceil_div<int64_t>(n, 256)), 0, static_cast<hipStream_t>(stream), x, static_cast<int>(ldx), static_cast<int>(n), out);
+  ::rdm::launch<sigmoid_kernel_body, 256>(dim3(ceil_div<int64_t>(n, 256)), 0, static_cast<hipStream_t>(stream), x, static_cast<int>(ldx), static_cast<int>(n), out);
   return launch_status("sigmoid_kernel");
 }
 
@@ -382,7 +373,7 @@ extern "C" int rdm_l2_normalize(const float* x, int64_t ldx, int64_t n, int64_t 
   RDM_REQUIRE(n >= 0 && c > 0, "rdm_l2_normalize: bad arguments");
   if (n == 0) return RDM_OK;
   RDM_REQUIRE(x && y, "rdm_l2_normalize: null pointer");
-  ::rdm::launch<l2_normalize_kernel_body, l2_normalize_kernel, 256>(dim3(ceil_div<int64_t>(n, 4)), 0, static_cast<hipStream_t>(stream), x, static_cast<int>(ldx), static_cast<int>(n),
+  ::rdm::launch<l2_normalize_kernel_body, 256>(dim3(ceil_div<int64_t>(n, 4)), 0, static_cast<hipStream_t>(stream), x, static_cast<int>(ldx), static_cast<int>(n),
                      static_cast<int>(c), y, static_cast<int>(ldy));
   return launch_status("l2_normalize_kernel");
 }

@@ -228,7 +228,6 @@ __device__ __forceinline__ void attention_topk_body(const dim3 blockIdx, const d
       *reinterpret_cast<float2*>(a.out + static_cast<int64_t>(qi) * a.ldo + hoff + dd) = make_float2(a0 / lt, a1 / lt);
   }
 }
-__global__ __launch_bounds__(256) void attention_topk_kernel(TopkArgs a) { attention_topk_body(blockIdx, gridDim, a); }
 
 // Fills the segment-independent fields, sizes the staged tile for the largest segment that stages, and launches.
 int topk_launch(TopkArgs a, int64_t blocks, int heads, hipStream_t stream) {
@@ -238,12 +237,8 @@ int topk_launch(TopkArgs a, int64_t blocks, int heads, hipStream_t stream) {
   for (const int64_t n : {int64_t(a.nk), int64_t(a.seg0_blocks > 0 ? a.nk1 : 0)})
     if (n <= kStageKeys && n > staged) staged = n;
   const size_t lds = kPartialBytes + static_cast<size_t>(ceil_div<int64_t>(staged, 16)) * 64 * sizeof(f32x4);
-  if (lds > 32768) {  // (dynamic + static LDS beyond 64 KB needs the attribute: set from 32 KB of dynamic LDS up, per device)
-    static std::atomic<uint64_t> done{0};
-    RDM_HIP_CHECK(set_max_dynamic_lds(reinterpret_cast<const void*>(attention_topk_kernel), 160 * 1024 - 4096, done));
-  }
   const dim3 grid(static_cast<unsigned>(blocks), heads);
-  launch<attention_topk_body, attention_topk_kernel, 256>(grid, lds, stream, a);
+  launch<attention_topk_body, 256>(grid, lds, stream, a);
   return launch_status("attention_topk_kernel");
 }
 

@@ -40,8 +40,9 @@ void set_error(const char* fmt, ...);
     }                                     \
   } while (0)
 
-// Set by rdm::launch (lockstep.h) when the grouped launch that carried the calling context's record failed: the error text is the
-// grouped launch's; the context's next launch_status() reports it (contexts of a lock-step group share their host thread, but a
+// Set by rdm::launch (lockstep.h) when the grouped launch that carried the calling context's record failed, or when its own
+// kernel's dynamic-LDS limit could not be raised (the launch is then skipped): the error text is that failure's; the context's
+// next launch_status() reports it (contexts of a lock-step group share their host thread, but a
 // context calls launch_status right after its launch returns, before any other context runs).
 inline thread_local bool t_launch_failed = false;
 

@@ -558,7 +558,6 @@ __device__ __forceinline__ void pad_points_kernel_body(const dim3 blockIdx, cons
   out[4 * i + 2] = p[3 * i + 2];
   out[4 * i + 3] = 0.f;
 }
-__global__ void pad_points_kernel(const float* p, int64_t n, float* out) { pad_points_kernel_body(blockIdx, gridDim, p, n, out); }
 
 __global__ void fill_kernel(float* p, int64_t n, float v) {
   const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
@@ -572,7 +571,6 @@ __device__ __forceinline__ void unit_features_kernel_body(const dim3 blockIdx, c
   for (int64_t c = 0; c < ld; ++c) x[i * ld + c] = 1.0f;  // (the pad columns as the separate fill wrote them)
   positive[i] = 1;
 }
-__global__ void unit_features_kernel(float* x, int64_t n, int64_t ld, uint8_t* positive) { unit_features_kernel_body(blockIdx, gridDim, x, n, ld, positive); }
 
 // The NMS survivors' rows (vote.py:36-40 boolean-mask selects; model_infer.py:206-216): nodes, their zero-padded [n,4]
 // copy for the positional Linear, features and the (n2p, n2n) score pairs -- one launch instead of seven gathers.
@@ -601,7 +599,6 @@ __device__ __forceinline__ void select_nodes_kernel_body(const dim3 blockIdx, co
   }
   for (int c = t; c < a.ldo; c += 64) a.out_feats[static_cast<int64_t>(j) * a.ldo + c] = c < a.d ? a.feats[static_cast<int64_t>(src) * a.ldf + c] : 0.f;
 }
-__global__ __launch_bounds__(64) void select_nodes_kernel(SelectNodesArgs a) { select_nodes_kernel_body(blockIdx, gridDim, a); }
 
 __device__ __forceinline__ void concat_points_kernel_body(const dim3 blockIdx, const dim3 gridDim, const float* a, int64_t na, const float* b, int64_t nb, float* out, int64_t* lengths) {
   (void)blockIdx; (void)gridDim;
@@ -613,21 +610,17 @@ __device__ __forceinline__ void concat_points_kernel_body(const dim3 blockIdx, c
   if (i < 3 * na) out[i] = a[i];
   else if (i < 3 * (na + nb)) out[i] = b[i - 3 * na];
 }
-__global__ void concat_points_kernel(const float* a, int64_t na, const float* b, int64_t nb, float* out, int64_t* lengths) { concat_points_kernel_body(blockIdx, gridDim, a, na, b, nb, out, lengths); }
 
 
 // The host half of a pair's result in one launch: pose + counters (19 words) and the first n correspondences
 // ([ref points 3n | src points 3n | scores n]) go straight into the mapped pinned buffer.
-__device__ __forceinline__ void export_result_kernel_body(const dim3 blockIdx, const dim3 gridDim, const float* T, const float* rc, const float* sc, const float* cs,
+__global__ __launch_bounds__(256) void export_result_kernel(const float* T, const float* rc, const float* sc, const float* cs,
                                                             uint32_t* head, float* corr, int cap) {
-  (void)blockIdx; (void)gridDim;
   const int n = min(reinterpret_cast<const int32_t*>(T)[16], cap);
   const int tid = blockIdx.x * 256 + threadIdx.x, nt = gridDim.x * 256;
   if (tid < 19) head[tid] = reinterpret_cast<const uint32_t*>(T)[tid];
   for (int i = tid; i < 7 * n; i += nt) corr[i] = i < 3 * n ? rc[i] : (i < 6 * n ? sc[i - 3 * n] : cs[i - 6 * n]);
 }
-__global__ __launch_bounds__(256) void export_result_kernel(const float* T, const float* rc, const float* sc, const float* cs,
-                                                            uint32_t* head, float* corr, int cap) { export_result_kernel_body(blockIdx, gridDim, T, rc, sc, cs, head, corr, cap); }
 
 
 // dst = OR of the status words of n {max count, status} pairs (one wavefront)
@@ -639,13 +632,12 @@ __device__ __forceinline__ void or_status_kernel_body(const dim3 blockIdx, const
   for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
   if (threadIdx.x == 0) *dst = v;
 }
-__global__ __launch_bounds__(64) void or_status_kernel(const int32_t* pairs, int n, int32_t* dst) { or_status_kernel_body(blockIdx, gridDim, pairs, n, dst); }
 
 
-template <auto Body, auto Kernel, typename... A>
+template <auto Body, typename... A>
 int launch1d(const char* what, int64_t n, hipStream_t st, A... args) {
   if (n <= 0) return RDM_OK;
-  ::rdm::launch<Body, Kernel, 256>(dim3(static_cast<unsigned>(ceil_div<int64_t>(n, 256))), 0, st, args...);
+  ::rdm::launch<Body, 256>(dim3(static_cast<unsigned>(ceil_div<int64_t>(n, 256))), 0, st, args...);
   return launch_status(what);
 }
 
@@ -1264,7 +1256,7 @@ static int collate_batch_once(rdm_engine* e, int B, const float* const* refs, co
   {
     int64_t base = 0;
     for (int p = 0; p < B; ++p) {
-      ENG_CHECK(launch1d<concat_points_kernel_body, concat_points_kernel>("concat_points", 3 * (n_refs[p] + n_srcs[p]), st, refs[p], n_refs[p], srcs[p], n_srcs[p],
+      ENG_CHECK(launch1d<concat_points_kernel_body>("concat_points", 3 * (n_refs[p] + n_srcs[p]), st, refs[p], n_refs[p], srcs[p], n_srcs[p],
                          pts[0] + 3 * base, len[0] + 2 * p));
       base += n_refs[p] + n_srcs[p];
     }
@@ -1534,7 +1526,7 @@ int encoder_input(Run& rr, const rdm_data_dict* dd, int64_t n0, Encoder& enc) {
   enc.x_pos = e->alloc<uint8_t>(n0);
   ENG_ALLOC(enc.x_pos);
   if (dd) return rdm_row_positive(x.p, n0, 1, x.ld, enc.x_pos, rr.st);
-  return launch1d<unit_features_kernel_body, unit_features_kernel>("unit_features", n0, rr.st, x.p, n0, x.ld, enc.x_pos);
+  return launch1d<unit_features_kernel_body>("unit_features", n0, rr.st, x.p, n0, x.ld, enc.x_pos);
 }
 
 int encoder_blocks(Run& rr, const PairPyramid& py, int b0, int b1, Encoder& enc) {
@@ -1598,7 +1590,7 @@ int transformer1(Run& r, const PairPyramid& py, const Mat& feats4, Coarse& co) {
   const int64_t Nc = py.lv[4].n, D = c.out_dim;
   Mat pts_c4{e->alloc<float>(4 * (Nc > 0 ? Nc : 1)), Nc, 4, 4};
   ENG_ALLOC(pts_c4.p);
-  ENG_CHECK(launch1d<pad_points_kernel_body, pad_points_kernel>("pad_points", Nc, r.st, py.lv[4].pts, Nc, pts_c4.p));
+  ENG_CHECK(launch1d<pad_points_kernel_body>("pad_points", Nc, r.st, py.lv[4].pts, Nc, pts_c4.p));
   co.buf = e->mat(Nc, D + 1);
   ENG_ALLOC(co.buf.p);
   co.x = co.buf.cols_from(0, D);
@@ -1739,7 +1731,7 @@ int superpoints(Run& r, const PairPyramid& py, const Coarse& co, const std::func
       sa.xyz = shifted; sa.feats = vfeats.p; sa.n2p = co.n2p; sa.n2n = n2n;
       sa.d = static_cast<int>(D); sa.ldf = static_cast<int>(vfeats.ld); sa.ldo = static_cast<int>(sel_feats.ld);
       sa.nodes = sp.nodes; sa.nodes4 = nodes4.p; sa.out_feats = sel_feats.p; sa.scores = sel_scores;
-      ::rdm::launch<select_nodes_kernel_body, select_nodes_kernel, 64>(dim3(static_cast<unsigned>(Mn)), 0, r.st, sa);
+      ::rdm::launch<select_nodes_kernel_body, 64>(dim3(static_cast<unsigned>(Mn)), 0, r.st, sa);
       ENG_CHECK(launch_status("select_nodes_kernel"));
     }
     tap(r, "nodes", sp.nodes, Mn, 3, 3, 0);
@@ -1991,7 +1983,7 @@ int pyramid_from_data_dict(Run& r, const rdm_data_dict& dd, PairPyramid& py) {
   }
   ENG_CHECK(build_level_grids(e, &py, 1, 0, 5, r.st));
   if (dd.collate_status && dd.n_collate_status > 0) {  // the collate's status words join the engine's own (checked with them)
-    ::rdm::launch<or_status_kernel_body, or_status_kernel, 64>(dim3(1), 0, r.st, dd.collate_status, static_cast<int>(dd.n_collate_status),
+    ::rdm::launch<or_status_kernel_body, 64>(dim3(1), 0, r.st, dd.collate_status, static_cast<int>(dd.n_collate_status),
                        py.flags + 2 * py.calls + 1);
     ENG_CHECK(launch_status("or_status_kernel"));
     py.calls++;
@@ -2043,7 +2035,7 @@ int collate_pair(Run& r, bool overlap, SideGuard& side_guard, const float* ref_p
     ENG_ALLOC(pts0); ENG_ALLOC(len0);
     side_guard.pending++;  // (from here to the join an early return waits for the side stream)
   }
-  ENG_CHECK(launch1d<concat_points_kernel_body, concat_points_kernel>("concat_points", 3 * n0, r.st, ref_points, n_ref, src_points, n_src, pts0, len0));
+  ENG_CHECK(launch1d<concat_points_kernel_body>("concat_points", 3 * n0, r.st, ref_points, n_ref, src_points, n_src, pts0, len0));
   int64_t* all_len = e->alloc<int64_t>(8);  // device lengths of levels 1..4, contiguous for one read-back
   ENG_ALLOC(all_len);
   float voxel = c.init_voxel_size;
@@ -2062,7 +2054,7 @@ int collate_pair(Run& r, bool overlap, SideGuard& side_guard, const float* ref_p
     if (i == 1 && overlap_l0) {
       // beside that chain, on the side stream: everything that needs level 0 only.  Enqueued between the chain's first level
       // (0.18 ms of GPU time) and the rest, so that neither stream waits for the host to get to it.
-      ENG_CHECK(launch1d<concat_points_kernel_body, concat_points_kernel>("concat_points", 3 * n0, rs.st, ref_points, n_ref, src_points, n_src, lv[0].pts,
+      ENG_CHECK(launch1d<concat_points_kernel_body>("concat_points", 3 * n0, rs.st, ref_points, n_ref, src_points, n_src, lv[0].pts,
                          lv[0].lengths));
       ENG_CHECK(build_level_grids(e, &py, 1, 0, 1, rs.st));
       SearchQueue side_queue(rs.st);

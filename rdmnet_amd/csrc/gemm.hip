@@ -467,9 +467,6 @@ __device__ __forceinline__ void gemm_kernel_body(const dim3 blockIdx, const dim3
   }
   GEMM_STAMP(3);
 }
-template <int BM, int BN, int WM, int WN, int BK, bool TRANS_B, int PF, bool CAT = false, bool SEED = false>
-// (64-row / 128 x 32 tiles: four workgroups per CU = four wavefronts per SIMD, 128 registers each)
-__global__ __launch_bounds__(256, (BM * BN <= 64 * 64 ? 4 : 1)) void gemm_kernel(GemmArgs g) { gemm_kernel_body<BM, BN, WM, WN, BK, TRANS_B, PF, CAT, SEED>(blockIdx, gridDim, g); }
 
 // Latency-oriented kernel for the transformer-sized products (M up to ~1k rows, K a multiple of 16):
 // one workgroup = ONE 32 x 32 output tile, its four wavefronts split K four ways, operands go straight
@@ -526,7 +523,6 @@ __device__ __forceinline__ void gemm_small_entry(const dim3 blockIdx, const dim3
   __shared__ float red[4][32][33];
   gemm_small_body(blockIdx, g, red);
 }
-__global__ __launch_bounds__(256) void gemm_small_kernel(GemmArgs g) { gemm_small_entry(blockIdx, gridDim, g); }
 // two independent products in one launch (blockIdx.z): the q and the k|v projection of a cross-attention layer
 __device__ __forceinline__ void gemm_small_pair_entry(const dim3 blockIdx, const dim3 gridDim, GemmArgs g0, GemmArgs g1) {
   (void)gridDim;
@@ -535,7 +531,6 @@ __device__ __forceinline__ void gemm_small_pair_entry(const dim3 blockIdx, const
   if (static_cast<int>(blockIdx.y) * 32 >= g.M || static_cast<int>(blockIdx.x) * 32 >= g.N) return;  // whole workgroup
   gemm_small_body(blockIdx, g, red);
 }
-__global__ __launch_bounds__(256) void gemm_small_pair_kernel(GemmArgs g0, GemmArgs g1) { gemm_small_pair_entry(blockIdx, gridDim, g0, g1); }
 
 // y = act(LayerNorm(x W + bias + residual)) for the transformer width (N = 128) in ONE launch: a workgroup owns
 // 16 complete rows (wavefront w the columns 32w..32w+31 over the whole K on the 16x16x4 MFMA, operands straight from
@@ -626,7 +621,6 @@ __device__ __forceinline__ void linear_ln128_body(const dim3 blockIdx, const dim
     a.out[static_cast<long long>(row) * a.ldo + c1] = o1;
   }
 }
-__global__ __launch_bounds__(256) void linear_ln128_kernel(LinLnArgs a) { linear_ln128_body(blockIdx, gridDim, a); }
 
 // Everything of an attention layer after softmax(QK^T)V in ONE launch (thdroformer.py:142-173,
 // vanilla_transformer.py:69-103, output_layer.py:6-21), at the transformer width 128 with a 256-wide FFN:
@@ -802,8 +796,6 @@ __device__ __forceinline__ void attention_tail128_body(const dim3 blockIdx, cons
     if (row < a.M) a.out[static_cast<long long>(row) * a.ldo + c] = o[r];
   }
 }
-template <bool PACKED>
-__global__ __launch_bounds__(512) void attention_tail128_kernel(TailArgs a) { attention_tail128_body<PACKED>(blockIdx, gridDim, a); }
 
 // The tail's weights in operand order (TailArgs::packed): one thread per float4.
 __global__ void attention_tail_pack_kernel(const float* wo, int ldwo, const float* w1, int ldw1, const float* w2, int ldw2, float4* out) {
@@ -841,7 +833,6 @@ __device__ __forceinline__ void splitk_reduce_kernel_body(const dim3 blockIdx, c
     g.C[b * g.sc + static_cast<long long>(m) * g.ldc + n] = apply_act(v, g.act);
   }
 }
-__global__ void splitk_reduce_kernel(GemmArgs g, int batches) { splitk_reduce_kernel_body(blockIdx, gridDim, g, batches); }
 
 
 // Split-K reduce that also emits the GroupNorm column partials of its row block (layout of gn_partial_kernel
@@ -902,7 +893,6 @@ __device__ __forceinline__ void splitk_reduce_stats_kernel_body(const dim3 block
     stats[(static_cast<long long>(blockIdx.x) * 2 + 1) * g.N + col] = b;
   }
 }
-__global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(GemmArgs g, double* stats) { splitk_reduce_stats_kernel_body(blockIdx, gridDim, g, stats); }
 
 
 thread_local unsigned g_lds_pad = 0;  // see rdm::gemm_set_lds_pad
@@ -910,27 +900,29 @@ thread_local unsigned g_lds_pad = 0;  // see rdm::gemm_set_lds_pad
 template <int BM, int BN, int WM, int WN, int BK, int PF = 1>
 void launch(const GemmArgs& g, int batches, bool trans_b, hipStream_t st) {
   dim3 grid(ceil_div(g.N, BN), ceil_div(g.M, BM), batches * g.splits);
+  // (64-row / 128 x 32 tiles: four workgroups per CU = four wavefronts per SIMD, 128 registers each)
+  constexpr int kMinWaves = BM * BN <= 64 * 64 ? 4 : 1;
   // unused dynamic LDS per workgroup = fewer GEMM workgroups per CU (rdm::gemm_set_lds_pad; lab build: RDM_GEMM_LDS_PAD=<bytes>)
   static const int pad_env = [] { const char* v = ::rdm::dev_knob("RDM_GEMM_LDS_PAD"); return v ? atoi(v) : -1; }();
   const unsigned pad = pad_env >= 0 ? static_cast<unsigned>(pad_env) : g_lds_pad;
   if constexpr (BM == 64 && BN == 64 && BK == 32 && PF == 2) {
     if (g.aidx && g.bidx) {  // gathered rows on both sides (patch scores)
-      ::rdm::launch<gemm_kernel_body<BM, BN, WM, WN, BK, true, PF, true>, gemm_kernel<BM, BN, WM, WN, BK, true, PF, true>, 256, (BM * BN <= 64 * 64 ? 4 : 1)>(grid, pad, st, g);
+      ::rdm::launch<gemm_kernel_body<BM, BN, WM, WN, BK, true, PF, true>, 256, kMinWaves>(grid, pad, st, g);
       return;
     }
     if (g.aidx) {  // virtual [upsample | skip] A operand
-      ::rdm::launch<gemm_kernel_body<BM, BN, WM, WN, BK, false, PF, true>, gemm_kernel<BM, BN, WM, WN, BK, false, PF, true>, 256, (BM * BN <= 64 * 64 ? 4 : 1)>(grid, pad, st, g);
+      ::rdm::launch<gemm_kernel_body<BM, BN, WM, WN, BK, false, PF, true>, 256, kMinWaves>(grid, pad, st, g);
       return;
     }
     if (g.seed) {  // accumulators seeded with the coarse half of the decoder's product
-      ::rdm::launch<gemm_kernel_body<BM, BN, WM, WN, BK, false, PF, false, true>, gemm_kernel<BM, BN, WM, WN, BK, false, PF, false, true>, 256, (BM * BN <= 64 * 64 ? 4 : 1)>(grid, pad, st, g);
+      ::rdm::launch<gemm_kernel_body<BM, BN, WM, WN, BK, false, PF, false, true>, 256, kMinWaves>(grid, pad, st, g);
       return;
     }
   }
   if (trans_b)
-    ::rdm::launch<gemm_kernel_body<BM, BN, WM, WN, BK, true, PF>, gemm_kernel<BM, BN, WM, WN, BK, true, PF>, 256, (BM * BN <= 64 * 64 ? 4 : 1)>(grid, pad, st, g);
+    ::rdm::launch<gemm_kernel_body<BM, BN, WM, WN, BK, true, PF>, 256, kMinWaves>(grid, pad, st, g);
   else
-    ::rdm::launch<gemm_kernel_body<BM, BN, WM, WN, BK, false, PF>, gemm_kernel<BM, BN, WM, WN, BK, false, PF>, 256, (BM * BN <= 64 * 64 ? 4 : 1)>(grid, pad, st, g);
+    ::rdm::launch<gemm_kernel_body<BM, BN, WM, WN, BK, false, PF>, 256, kMinWaves>(grid, pad, st, g);
 }
 
 }  // namespace
@@ -1111,7 +1103,7 @@ int launch_plan(const GemmPlan& p, GemmArgs g, int batches, bool trans_b, void* 
   if (p.small) {
     if (stat_blocks) *stat_blocks = 0;
     RDM_DUP_LOOP("gemmsmall")
-    ::rdm::launch<gemm_small_entry, gemm_small_kernel, 256>(dim3(ceil_div<long long>(n, 32), ceil_div<long long>(m, 32)), 0, st, g);
+    ::rdm::launch<gemm_small_entry, 256>(dim3(ceil_div<long long>(n, 32), ceil_div<long long>(m, 32)), 0, st, g);
     return launch_status("gemm_small_kernel");
   }
   g.xcd_tiles = p.xcd_tiles;
@@ -1150,13 +1142,13 @@ int launch_plan(const GemmPlan& p, GemmArgs g, int batches, bool trans_b, void* 
   if (int e = launch_status("gemm_kernel")) return e;
   if (g.splits > 1 && reduce_stats) {
     RDM_DUP_LOOP("splitk")
-    ::rdm::launch<splitk_reduce_stats_kernel_body, splitk_reduce_stats_kernel, 256>(dim3(ceil_div<long long>(m, stat_rows_per_block(n)), ceil_div<long long>(n, 256)), 0, st, g, reduce_stats);
+    ::rdm::launch<splitk_reduce_stats_kernel_body, 256>(dim3(ceil_div<long long>(m, stat_rows_per_block(n)), ceil_div<long long>(n, 256)), 0, st, g, reduce_stats);
     return launch_status("splitk_reduce_stats_kernel");
   }
   if (g.splits > 1) {
     const long long total = static_cast<long long>(batches) * m * n;
     const int blocks = static_cast<int>(std::min<long long>(ceil_div<long long>(total, 256), 2048));
-    ::rdm::launch<splitk_reduce_kernel_body, splitk_reduce_kernel, 256>(dim3(blocks), 0, st, g, batches);
+    ::rdm::launch<splitk_reduce_kernel_body, 256>(dim3(blocks), 0, st, g, batches);
     return launch_status("splitk_reduce_kernel");
   }
   return RDM_OK;
@@ -1265,7 +1257,7 @@ int rdm::gemm_pair(const float* a0, int64_t lda0, const float* b0, int64_t ldb0,
       g[i].lda = static_cast<int>(LA[i]); g[i].ldb = static_cast<int>(LB[i]); g[i].ldc = static_cast<int>(LC[i]);
     }
     const long long gx = ceil_div<long long>(std::max(n0, n1), 32), gy = ceil_div<long long>(std::max(m0, m1), 32);
-    ::rdm::launch<gemm_small_pair_entry, gemm_small_pair_kernel, 256>(dim3(gx, gy, 2), 0, static_cast<hipStream_t>(stream), g[0], g[1]);
+    ::rdm::launch<gemm_small_pair_entry, 256>(dim3(gx, gy, 2), 0, static_cast<hipStream_t>(stream), g[0], g[1]);
     return launch_status("gemm_small_pair_kernel");
   }
   if (m0 > 0)
@@ -1437,7 +1429,7 @@ extern "C" int rdm_linear_layer_norm(const float* x, int64_t ldx, const float* w
   a.A = x; a.B = w; a.bias = bias; a.res = residual; a.gamma = gamma; a.beta = beta; a.out = y;
   a.M = static_cast<int>(m); a.K = static_cast<int>(k); a.lda = static_cast<int>(ldx); a.ldb = static_cast<int>(ldw);
   a.ldr = static_cast<int>(ldr); a.ldo = static_cast<int>(ldy); a.act = act; a.eps = eps;
-  ::rdm::launch<linear_ln128_body, linear_ln128_kernel, 256>(dim3(static_cast<unsigned>(ceil_div<int64_t>(m, 16))), 0, static_cast<hipStream_t>(stream), a);
+  ::rdm::launch<linear_ln128_body, 256>(dim3(static_cast<unsigned>(ceil_div<int64_t>(m, 16))), 0, static_cast<hipStream_t>(stream), a);
   return launch_status("linear_ln128_kernel");
 }
 
@@ -1465,7 +1457,7 @@ extern "C" int rdm_attention_tail(const float* hidden, int64_t ld_hidden, const 
   a.ldw1 = static_cast<int>(ld_w1); a.ldw2 = static_cast<int>(ld_w2); a.eps = eps;
   a.packed = nullptr;
   RDM_DUP_LOOP("tail")
-  ::rdm::launch<attention_tail128_body<false>, attention_tail128_kernel<false>, 512>(dim3(static_cast<unsigned>(ceil_div<int64_t>(m, 16))), 0, static_cast<hipStream_t>(stream), a);
+  ::rdm::launch<attention_tail128_body<false>, 512>(dim3(static_cast<unsigned>(ceil_div<int64_t>(m, 16))), 0, static_cast<hipStream_t>(stream), a);
   return launch_status("attention_tail128_kernel");
 }
 
@@ -1502,7 +1494,7 @@ extern "C" int rdm_attention_tail_packed(const float* hidden, int64_t ld_hidden,
   a.ldx = static_cast<int>(ldx); a.ldo = static_cast<int>(ld_out); a.ldwo = a.ldw1 = a.ldw2 = 0; a.eps = eps;
   a.packed = reinterpret_cast<const float4*>(packed);
   RDM_DUP_LOOP("tail")
-  ::rdm::launch<attention_tail128_body<true>, attention_tail128_kernel<true>, 512>(dim3(static_cast<unsigned>(ceil_div<int64_t>(m, 16))), 0, static_cast<hipStream_t>(stream), a);
+  ::rdm::launch<attention_tail128_body<true>, 512>(dim3(static_cast<unsigned>(ceil_div<int64_t>(m, 16))), 0, static_cast<hipStream_t>(stream), a);
   return launch_status("attention_tail128_kernel");
 }
 

@@ -194,8 +194,6 @@ __device__ __forceinline__ void kpconv_gather_kernel_body(const dim3 blockIdx, c
   if (lane == 0 && slice == 0) a.nn[m] = static_cast<float>(positives > 1 ? positives : 1);
   }  // unit loop
 }
-template <int VEC, int U, int SPLIT, int PF>
-__global__ __launch_bounds__(64 * kWaves) void kpconv_gather_kernel(KpArgs a) { kpconv_gather_kernel_body<VEC, U, SPLIT, PF>(blockIdx, gridDim, a); }
 
 
 // First layer (C_in = 1, features == 1 for every real point, reference dataset.py:187-188 and
@@ -259,7 +257,6 @@ __device__ __forceinline__ void kpconv_gather_c1_kernel_body(const dim3 blockIdx
     }
   }
 }
-__global__ __launch_bounds__(64 * kWaves) void kpconv_gather_c1_kernel(KpArgs a) { kpconv_gather_c1_kernel_body(blockIdx, gridDim, a); }
 
 
 // 1 iff the row sum is positive (kpconv.py:113-114); one wavefront per row, fixed summation order.
@@ -273,7 +270,6 @@ __device__ __forceinline__ void row_positive_kernel_body(const dim3 blockIdx, co
   s = wave_sum(s);
   if (lane == 0) out[row] = s > 0.f ? 1 : 0;
 }
-__global__ void row_positive_kernel(const float* x, int n, int c, int ld, unsigned char* out) { row_positive_kernel_body(blockIdx, gridDim, x, n, c, ld, out); }
 
 
 }  // namespace
@@ -283,7 +279,7 @@ extern "C" int rdm_row_positive(const float* x, int64_t n, int64_t c, int64_t ld
   using namespace rdm;
   RDM_REQUIRE(x && out && n >= 0 && c > 0, "rdm_row_positive: bad arguments");
   if (n == 0) return RDM_OK;
-  ::rdm::launch<row_positive_kernel_body, row_positive_kernel, 256>(dim3(ceil_div<int64_t>(n, 4)), 0, static_cast<hipStream_t>(stream), x, static_cast<int>(n), static_cast<int>(c),
+  ::rdm::launch<row_positive_kernel_body, 256>(dim3(ceil_div<int64_t>(n, 4)), 0, static_cast<hipStream_t>(stream), x, static_cast<int>(n), static_cast<int>(c),
                      static_cast<int>(ld), out);
   return launch_status("row_positive_kernel");
 }
@@ -335,15 +331,15 @@ int rdm::kpconv_gather_impl(const float* q_points, int64_t m, const float* s_poi
   // fills from L2 (feature row + point + flag per neighbour), not by the dependent-load chain.
   RDM_DUP_LOOP("gather")
   switch (c) {
-    case 1: ::rdm::launch<kpconv_gather_c1_kernel_body, kpconv_gather_c1_kernel, 64 * kWaves>(dim3(ceil_div<int64_t>(m, kWaves)), 0, st, a); break;
-    case 32: ::rdm::launch<kpconv_gather_kernel_body<2, 1, 1, 4>, kpconv_gather_kernel<2, 1, 1, 4>, 64 * kWaves>(grid(1), 0, st, a); break;
-    case 64: ::rdm::launch<kpconv_gather_kernel_body<4, 1, 1, 4>, kpconv_gather_kernel<4, 1, 1, 4>, 64 * kWaves>(grid(1), 0, st, a); break;
-    case 128: ::rdm::launch<kpconv_gather_kernel_body<4, 1, 2, 4>, kpconv_gather_kernel<4, 1, 2, 4>, 64 * kWaves>(grid(2), 0, st, a); break;
-    case 256: ::rdm::launch<kpconv_gather_kernel_body<4, 1, 4, 4>, kpconv_gather_kernel<4, 1, 4, 4>, 64 * kWaves>(grid(4), 0, st, a); break;
-    case 512: ::rdm::launch<kpconv_gather_kernel_body<4, 2, 4, 2>, kpconv_gather_kernel<4, 2, 4, 2>, 64 * kWaves>(grid(4), 0, st, a); break;
+    case 1: ::rdm::launch<kpconv_gather_c1_kernel_body, 64 * kWaves>(dim3(ceil_div<int64_t>(m, kWaves)), 0, st, a); break;
+    case 32: ::rdm::launch<kpconv_gather_kernel_body<2, 1, 1, 4>, 64 * kWaves>(grid(1), 0, st, a); break;
+    case 64: ::rdm::launch<kpconv_gather_kernel_body<4, 1, 1, 4>, 64 * kWaves>(grid(1), 0, st, a); break;
+    case 128: ::rdm::launch<kpconv_gather_kernel_body<4, 1, 2, 4>, 64 * kWaves>(grid(2), 0, st, a); break;
+    case 256: ::rdm::launch<kpconv_gather_kernel_body<4, 1, 4, 4>, 64 * kWaves>(grid(4), 0, st, a); break;
+    case 512: ::rdm::launch<kpconv_gather_kernel_body<4, 2, 4, 2>, 64 * kWaves>(grid(4), 0, st, a); break;
     default:  // any other multiple of 32 (the backbone's widths are 32 * 2^k; the reference takes any init_dim): 32-channel slices
       a.split = static_cast<int>(c / 32);
-      ::rdm::launch<kpconv_gather_kernel_body<2, 1, 0, 4>, kpconv_gather_kernel<2, 1, 0, 4>, 64 * kWaves>(grid(a.split), 0, st, a);
+      ::rdm::launch<kpconv_gather_kernel_body<2, 1, 0, 4>, 64 * kWaves>(grid(a.split), 0, st, a);
       break;
   }
   return launch_status("kpconv_gather_kernel");

@@ -20,7 +20,6 @@
 // scan pair at the same pairs/s; the engine's default for these layers since round 3.  The kernel's time is the sum of its
 // phases' L2 -> CU traffic (neighbour lines + W re-read per 16 queries: tools/kpconv_bench.py, tools/lab/kpconv_fused_pc.hip
 // for the producer / consumer variant that overlaps the phases and measured the same).
-#include <atomic>
 #include <cstdlib>
 
 #include "../../include/rdmnet_hip.h"
@@ -264,8 +263,6 @@ __device__ __forceinline__ void kpconv_fused_kernel_body(const dim3 blockIdx, co
     }
   }
 }
-template <int C, int QB, int NW, int ITERS>
-__global__ __launch_bounds__(64 * NW) void kpconv_fused_kernel(FusedArgs a) { kpconv_fused_kernel_body<C, QB, NW, ITERS>(blockIdx, gridDim, a); }
 
 
 // ---- C_in in {32, 64}, neighbour rows of at most 128 slots: the support rows of a block of queries staged ONCE in LDS
@@ -740,8 +737,6 @@ __device__ __forceinline__ void kpconv_tile_kernel_body(const dim3 blockIdx, con
   if (threadIdx.x == 0 && rdm_tile_clk) rdm_tile_clk[tl_blk * 8 + 7] = n_slots + ((wall_clock64() - tl_rt0) << 16);  // (100 MHz clock)
 #endif
 }
-template <int C, bool GATHER = false>
-__global__ __launch_bounds__(64 * TileCfg<C>::NW, (C == 32 && TileCfg<C>::NW == 8 ? 3 : 2) * TileCfg<C>::NW / 4) void kpconv_tile_kernel(FusedArgs a, const float4* __restrict__ order, int xcd_ranges) { kpconv_tile_kernel_body<C, GATHER>(blockIdx, gridDim, a, order, xcd_ranges); }
 
 
 // (Round 5 measured a rewrite of this kernel -- a wavefront's queries software-pipelined (index row of query t + 2 and the two
@@ -834,7 +829,6 @@ __device__ __forceinline__ void kpconv_fused_c1_kernel_body(const dim3 blockIdx,
     }
   }
 }
-__global__ __launch_bounds__(64 * kC1Waves) void kpconv_fused_c1_kernel(FusedArgs a) { kpconv_fused_c1_kernel_body(blockIdx, gridDim, a); }
 
 
 template <int C, int QB, int NW>
@@ -905,11 +899,9 @@ int rdm::kpconv_tile_gather(const float* q_points, int64_t m, const float* s_poi
   a.M = static_cast<int>(m); a.Ns = static_cast<int>(n_s); a.H = static_cast<int>(h);
   a.ldf = static_cast<int>(ldf); a.ldi = static_cast<int>(ldi); a.ldo = static_cast<int>(ldw); a.sigma = sigma;
   a.ctot = static_cast<int>(c); a.nn = nn;
-  static std::atomic<uint64_t> gattr{0};
-  RDM_HIP_CHECK(set_max_dynamic_lds(reinterpret_cast<const void*>(kpconv_tile_kernel<64, true>), static_cast<int>(TileLds<64>::bytes), gattr));
   const dim3 grid(static_cast<unsigned>(ceil_div<int64_t>(m, kTileQB)), static_cast<unsigned>(c / 64));
   RDM_DUP_LOOP("gather")
-  ::rdm::launch<kpconv_tile_kernel_body<64, true>, kpconv_tile_kernel<64, true>, 64 * TileCfg<64>::NW, 2 * TileCfg<64>::NW / 4>(grid, TileLds<64>::bytes, static_cast<hipStream_t>(stream), a,
+  ::rdm::launch<kpconv_tile_kernel_body<64, true>, 64 * TileCfg<64>::NW, 2 * TileCfg<64>::NW / 4>(grid, TileLds<64>::bytes, static_cast<hipStream_t>(stream), a,
                      reinterpret_cast<const float4*>(order_records), 1);
   return launch_status("kpconv_tile_kernel<64, gather>");
 }
@@ -992,33 +984,24 @@ int rdm::kpconv_fused_impl(const float* q_points, int64_t m, const float* s_poin
     // and gathers of a wavefront's four queries requested together -- 30.4 us; round 5: halving the instruction count and
     // pipelining the queries buys 15 %, four queries per pipeline stage lose it again: the address processing of the
     // scattered gathers bounds the kernel, see the note above kpconv_fused_c1_kernel)
-    ::rdm::launch<kpconv_fused_c1_kernel_body, kpconv_fused_c1_kernel, 64 * kC1Waves>(dim3(blocks), 0, st, a);
+    ::rdm::launch<kpconv_fused_c1_kernel_body, 64 * kC1Waves>(dim3(blocks), 0, st, a);
     continue;
   }
   if (use_tile(c, h, m, n_s, order_records != nullptr, form)) {  // the support rows of 16 cell-ordered queries staged once in LDS
-    static std::atomic<uint64_t> tattr32{0}, tattr64{0};
     const float4* order = reinterpret_cast<const float4*>(order_records);
     const int xcd_ranges = form == 3 ? 0 : 1;  // (form 3, lab: block ids in dispatch order, as in round 4)
-    if (c == 32) {
-      RDM_HIP_CHECK(set_max_dynamic_lds(reinterpret_cast<const void*>(kpconv_tile_kernel<32>), static_cast<int>(TileLds<32>::bytes), tattr32));
-      ::rdm::launch<kpconv_tile_kernel_body<32>, kpconv_tile_kernel<32>, 64 * TileCfg<32>::NW, (TileCfg<32>::NW == 8 ? 3 : 2) * TileCfg<32>::NW / 4>(dim3(blocks), TileLds<32>::bytes, st, a, order, xcd_ranges);
-    } else {
-      RDM_HIP_CHECK(set_max_dynamic_lds(reinterpret_cast<const void*>(kpconv_tile_kernel<64>), static_cast<int>(TileLds<64>::bytes), tattr64));
-      ::rdm::launch<kpconv_tile_kernel_body<64>, kpconv_tile_kernel<64>, 64 * TileCfg<64>::NW, 2 * TileCfg<64>::NW / 4>(dim3(blocks), TileLds<64>::bytes, st, a, order, xcd_ranges);
-    }
+    if (c == 32)
+      ::rdm::launch<kpconv_tile_kernel_body<32>, 64 * TileCfg<32>::NW, (TileCfg<32>::NW == 8 ? 3 : 2) * TileCfg<32>::NW / 4>(dim3(blocks), TileLds<32>::bytes, st, a, order, xcd_ranges);
+    else
+      ::rdm::launch<kpconv_tile_kernel_body<64>, 64 * TileCfg<64>::NW, 2 * TileCfg<64>::NW / 4>(dim3(blocks), TileLds<64>::bytes, st, a, order, xcd_ranges);
     continue;
   }
-  // (the C = 64 instance needs > 64 KB of dynamic LDS: the attribute is set once per device)
-  static std::atomic<uint64_t> attr32{0}, attr64{0};
-  RDM_HIP_CHECK(set_max_dynamic_lds(reinterpret_cast<const void*>(kpconv_fused_kernel<32, kQb32, kNw32, kIters32>),
-                                    static_cast<int>(fused_lds_bytes<32, kQb32, kNw32>()), attr32));
-  RDM_HIP_CHECK(set_max_dynamic_lds(reinterpret_cast<const void*>(kpconv_fused_kernel<64, kQb64, kNw64, kIters64>),
-                                    static_cast<int>(fused_lds_bytes<64, kQb64, kNw64>()), attr64));
+  // (the C = 64 instance needs > 64 KB of dynamic LDS: the launch raises the limit)
   const size_t lds32 = fused_lds_bytes<32, kQb32, kNw32>(), lds64 = fused_lds_bytes<64, kQb64, kNw64>();
   if (c == 32)
-    ::rdm::launch<kpconv_fused_kernel_body<32, kQb32, kNw32, kIters32>, kpconv_fused_kernel<32, kQb32, kNw32, kIters32>, 64 * kNw32>(dim3(blocks), lds32, st, a);
+    ::rdm::launch<kpconv_fused_kernel_body<32, kQb32, kNw32, kIters32>, 64 * kNw32>(dim3(blocks), lds32, st, a);
   else
-    ::rdm::launch<kpconv_fused_kernel_body<64, kQb64, kNw64, kIters64>, kpconv_fused_kernel<64, kQb64, kNw64, kIters64>, 64 * kNw64>(dim3(blocks), lds64, st, a);
+    ::rdm::launch<kpconv_fused_kernel_body<64, kQb64, kNw64, kIters64>, 64 * kNw64>(dim3(blocks), lds64, st, a);
   }
   return launch_status("kpconv_fused_kernel");
 }

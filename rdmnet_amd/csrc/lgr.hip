@@ -151,9 +151,6 @@ __device__ __forceinline__ void lgr_extract_kernel_body(const dim3 blockIdx, con
       }
   }
 }
-__global__ __launch_bounds__(256) void lgr_extract_kernel(const float* log_scores, int side,
-                                                          const unsigned char* ref_mask,
-                                                          const unsigned char* src_mask, LgrBuffers w) { lgr_extract_kernel_body(blockIdx, gridDim, log_scores, side, ref_mask, src_mask, w); }
 
 // ------------------------------------------------------------------------------------------ extract, every option
 // The k-th element (1 <= k < n) of a staged line base[0], base[stride], .. in the order (value descending, index ascending)
@@ -189,7 +186,7 @@ __device__ __forceinline__ void lgr_extract_topk_kernel_body(const dim3 blockIdx
                                                                int side, const unsigned char* ref_mask, const unsigned char* src_mask,
                                                                const float* global_scores, LgrSelect o, LgrBuffers w) {
   (void)blockIdx; (void)gridDim;
-  extern __shared__ float S[];  // compacted [(nr+D)][(nc+D)], D = 1 with the dustbin, row stride ldc (odd); static LDS stays < 4 KB (set_max_dynamic_lds)
+  extern __shared__ float S[];  // compacted [(nr+D)][(nc+D)], D = 1 with the dustbin, row stride ldc (odd); static LDS stays < 4 KB (rdm::kMaxDynamicLds)
   __shared__ int rows[kSide + 1], cols[kSide + 1];  // original index of every compacted line, dustbin (= side) last
   __shared__ float rowt[kSide], colt[kSide];        // a line's k-th value and its index (lgr_kth)
   __shared__ int rowj[kSide], colj[kSide];
@@ -272,10 +269,6 @@ __device__ __forceinline__ void lgr_extract_topk_kernel_body(const dim3 blockIdx
       }
   }
 }
-__global__ __launch_bounds__(256) void lgr_extract_topk_kernel(const float* log_scores, int n1, int side, const unsigned char* ref_mask,
-                                                               const unsigned char* src_mask, const float* global_scores, LgrSelect o,
-                                                               LgrBuffers w) { lgr_extract_topk_kernel_body(blockIdx, gridDim, log_scores, n1, side, ref_mask, src_mask, global_scores, o, w); }
-
 
 // ------------------------------------------------------------------------------------------ layout
 // One wavefront: exclusive prefix of the per-patch correspondence counts (= offsets in nonzero order) and the
@@ -321,8 +314,6 @@ __device__ __forceinline__ void lgr_layout_kernel_body(const dim3 blockIdx, cons
     w.meta[2] = -1;
   }
 }
-__global__ __launch_bounds__(64) void lgr_layout_kernel(int batch, int min_corr, LgrBuffers w) { lgr_layout_kernel_body(blockIdx, gridDim, batch, min_corr, w); }
-
 
 __device__ __forceinline__ void lgr_gather_kernel_body(const dim3 blockIdx, const dim3 gridDim, const float* ref_knn, const float* src_knn, int side, LgrBuffers w,
                                   float* ref_corr, float* src_corr, float* corr_scores) {
@@ -340,9 +331,6 @@ __device__ __forceinline__ void lgr_gather_kernel_body(const dim3 blockIdx, cons
     corr_scores[off + t] = w.local_s[o];
   }
 }
-__global__ void lgr_gather_kernel(const float* ref_knn, const float* src_knn, int side, LgrBuffers w,
-                                  float* ref_corr, float* src_corr, float* corr_scores) { lgr_gather_kernel_body(blockIdx, gridDim, ref_knn, src_knn, side, w, ref_corr, src_corr, corr_scores); }
-
 
 // ------------------------------------------------------------------------------------------ limit
 // correspondence_limit = L (:152-160): the verification set is the L best-scored of the C correspondences -- the first L in the
@@ -441,9 +429,6 @@ __device__ __forceinline__ void lgr_limit_kernel_body(const dim3 blockIdx, const
   }
   if (tid == 0) w.meta[3] = all ? C : limit;
 }
-__global__ __launch_bounds__(kLimitThreads) void lgr_limit_kernel(const float* ref_corr, const float* src_corr, const float* scores,
-                                                                  int limit, LgrBuffers w) { lgr_limit_kernel_body(blockIdx, gridDim, ref_corr, src_corr, scores, limit, w); }
-
 
 // ------------------------------------------------------------------------------------------ Procrustes
 // Sum N values per thread over the block (fixed order); red must hold N * 16 doubles.
@@ -574,10 +559,6 @@ __device__ __forceinline__ void lgr_local_kernel_body(const dim3 blockIdx, const
   __syncthreads();
   if (threadIdx.x == 0) w.chunk_inliers[chunk] = cnt_sh;
 }
-__global__ __launch_bounds__(256) void lgr_local_kernel(const float* ref_corr, const float* src_corr,
-                                                        const float* scores, float radius, LgrBuffers w) { lgr_local_kernel_body(blockIdx, gridDim, ref_corr, src_corr, scores, radius, w); }
-
-
 // single block: pick the hypothesis, refine globally
 constexpr int kRefineStage = 4608;  // correspondences staged in LDS: 4608 * 29 B = 131 KB
 __device__ __forceinline__ void lgr_refine_kernel_body(const dim3 blockIdx, const dim3 gridDim, const float* ref_corr, const float* src_corr,
@@ -646,12 +627,6 @@ __device__ __forceinline__ void lgr_refine_kernel_body(const dim3 blockIdx, cons
     counts[2] = best_out;
   }
 }
-__global__ __launch_bounds__(256) void lgr_refine_kernel(const float* ref_corr, const float* src_corr,
-                                                          const float* scores, float radius, int steps,
-                                                          LgrBuffers w, unsigned char* gate, float* out_T,
-                                                          int32_t* counts) { lgr_refine_kernel_body(blockIdx, gridDim, ref_corr, src_corr, scores, radius, steps, w, gate, out_T, counts); }
-
-
 }  // namespace
 
 namespace {
@@ -719,26 +694,22 @@ int lgr_run(const char* who, const float* log_scores, int64_t score_dim, const f
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int S = static_cast<int>(side), B = static_cast<int>(batch);
   const size_t lds = sizeof(float) * (S + 1) * ((S + 1) | 1);
-  static std::atomic<uint64_t> attr_extract{0}, attr_topk{0}, attr_refine{0};  // per device (rdm::set_max_dynamic_lds)
-  RDM_HIP_CHECK(set_max_dynamic_lds(reinterpret_cast<const void*>(lgr_refine_kernel), 160 * 1024 - 4096, attr_refine));
   if (opt) {
     const LgrSelect sel{opt->topk, opt->mutual != 0, opt->use_dustbin != 0, opt->use_global_score != 0, opt->confidence_threshold};
-    RDM_HIP_CHECK(set_max_dynamic_lds(reinterpret_cast<const void*>(lgr_extract_topk_kernel), 160 * 1024 - 4096, attr_topk));
-    ::rdm::launch<lgr_extract_topk_kernel_body, lgr_extract_topk_kernel, 256>(dim3(B), lds, st, log_scores, static_cast<int>(score_dim), S,
+    ::rdm::launch<lgr_extract_topk_kernel_body, 256>(dim3(B), lds, st, log_scores, static_cast<int>(score_dim), S,
                        ref_knn_masks, src_knn_masks, global_scores, sel, w);
   } else {
-    RDM_HIP_CHECK(set_max_dynamic_lds(reinterpret_cast<const void*>(lgr_extract_kernel), 160 * 1024 - 4096, attr_extract));
-    ::rdm::launch<lgr_extract_kernel_body, lgr_extract_kernel, 256>(dim3(B), lds, st, log_scores, S, ref_knn_masks, src_knn_masks, w);
+    ::rdm::launch<lgr_extract_kernel_body, 256>(dim3(B), lds, st, log_scores, S, ref_knn_masks, src_knn_masks, w);
   }
-  ::rdm::launch<lgr_layout_kernel_body, lgr_layout_kernel, 64>(dim3(1), 0, st, B, correspondence_threshold, w);
-  ::rdm::launch<lgr_gather_kernel_body, lgr_gather_kernel, 64>(dim3(B), 0, st, ref_knn_points, src_knn_points, S, w, ref_corr,
+  ::rdm::launch<lgr_layout_kernel_body, 64>(dim3(1), 0, st, B, correspondence_threshold, w);
+  ::rdm::launch<lgr_gather_kernel_body, 64>(dim3(B), 0, st, ref_knn_points, src_knn_points, S, w, ref_corr,
                      src_corr, corr_scores);
   if (w.ver_s)
-    ::rdm::launch<lgr_limit_kernel_body, lgr_limit_kernel, kLimitThreads>(dim3(1), 0, st, ref_corr, src_corr, corr_scores,
+    ::rdm::launch<lgr_limit_kernel_body, kLimitThreads>(dim3(1), 0, st, ref_corr, src_corr, corr_scores,
                        opt->correspondence_limit, w);
-  ::rdm::launch<lgr_local_kernel_body, lgr_local_kernel, 256>(dim3(B), 0, st, ref_corr, src_corr, corr_scores, acceptance_radius, w);
+  ::rdm::launch<lgr_local_kernel_body, 256>(dim3(B), 0, st, ref_corr, src_corr, corr_scores, acceptance_radius, w);
   // (with a limit the refinement runs on the verification set; counts[0] stays the number of ALL correspondences)
-  ::rdm::launch<lgr_refine_kernel_body, lgr_refine_kernel, 256>(dim3(1), kRefineStage * 29 + 64, st, w.ver_s ? w.ver_ref : ref_corr,
+  ::rdm::launch<lgr_refine_kernel_body, 256>(dim3(1), kRefineStage * 29 + 64, st, w.ver_s ? w.ver_ref : ref_corr,
                      w.ver_s ? w.ver_src : src_corr, w.ver_s ? w.ver_s : corr_scores, acceptance_radius, num_refinement_steps, w, gate,
                      transform, counts);
   return launch_status("lgr kernels");

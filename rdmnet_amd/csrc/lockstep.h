@@ -12,9 +12,11 @@
 // launch has been issued, so a pair's launches keep their order on the stream.  A host wait (size read-back) parks the context until
 // every running context waits; the scheduler then waits for the stream once.
 //
-// Converting a kernel: its body becomes `__device__ void name_body(const dim3 blockIdx, const dim3 gridDim, params...)` (the two
-// names shadow the built-ins, the body's text does not change), `__global__ name(params...)` calls it, and the launch site says
-// rdm::launch<name_body, name, THREADS[, MIN_WAVES]>(grid, lds_bytes, stream, args...).
+// Converting a kernel: write its body as `__device__ void name_body(const dim3 blockIdx, const dim3 gridDim, params...)` (the two
+// names shadow the built-ins, the body's text does not change) and launch it with
+// rdm::launch<name_body, THREADS[, MIN_WAVES]>(grid, lds_bytes, stream, args...).  Both kernels that run the body are generated
+// here under those launch bounds -- entry_kernel for a launch of its own, grouped_kernel for a group's -- and the launch raises
+// the dynamic-LDS limit of whichever it issues (kMaxDynamicLds): a launch site keeps neither a __global__ nor an attribute call.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -108,12 +110,38 @@ template <class F, class H, class... T, class... U> inline void apply_host(F&& f
   apply_host(static_cast<F&&>(f), p.tail, u..., p.head);
 }
 
-template <auto Body, auto Kernel, int THREADS, int MINW, class... P>
+// The single launch of a body: the kernel the launch sites used to write by hand.
+template <auto Body, int THREADS, int MINW, class... P>
+__global__ __launch_bounds__(THREADS, MINW) void entry_kernel(P... p) { Body(blockIdx, gridDim, p...); }
+
+// Dynamic + static LDS beyond 64 KB needs the attribute on the instantiation that is launched, per device: set from 32 KB of
+// dynamic LDS up (static LDS of every converted body stays below that), to all of a workgroup's 160 KB but a 4 KB static share.
+constexpr size_t kDynamicLdsDefault = 32768;
+constexpr int kMaxDynamicLds = 160 * 1024 - 4096;
+template <auto Kernel> inline int raise_lds_limit(size_t lds) {
+  if (lds <= kDynamicLdsDefault) return 0;
+  static std::atomic<uint64_t> done{0};  // per instantiation and device (set_max_dynamic_lds)
+  const hipError_t err = set_max_dynamic_lds(reinterpret_cast<const void*>(Kernel), kMaxDynamicLds, done);
+  if (err == hipSuccess) return 0;
+  set_error("launch: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(err));
+  return RDM_ERR_HIP;
+}
+// Issues the body's own kernel (the launch outside a group, and a group's launch that found no partner); 0 or RDM_ERR_HIP
+template <auto Body, int THREADS, int MINW, class... P>
+inline int issue_entry(dim3 grid, size_t lds, hipStream_t st, P... a) {
+  if (int rc = raise_lds_limit<entry_kernel<Body, THREADS, MINW, P...>>(lds)) return rc;
+  hipLaunchKernelGGL((entry_kernel<Body, THREADS, MINW, P...>), grid, dim3(THREADS), lds, st, a...);
+  return 0;
+}
+
+template <auto Body, int THREADS, int MINW, class... P>
 int fire_records(const LaunchRecord* const* recs, int n) {
   if (n == 1) {
     ArgPack<P...> a;
     std::memcpy(&a, recs[0]->args, sizeof(a));
-    apply_host([&](auto... x) { hipLaunchKernelGGL(Kernel, recs[0]->grid, dim3(THREADS), recs[0]->lds, recs[0]->stream, x...); }, a);
+    int rc = 0;
+    apply_host([&](auto... x) { rc = issue_entry<Body, THREADS, MINW, P...>(recs[0]->grid, recs[0]->lds, recs[0]->stream, x...); }, a);
+    if (rc != 0) return rc;
     const hipError_t lerr = hipGetLastError();
     if (lerr != hipSuccess) {
       set_error("launch (one record of a lock-step group) failed: %s", hipGetErrorString(lerr));
@@ -136,14 +164,7 @@ int fire_records(const LaunchRecord* const* recs, int n) {
   }
   size_t lds = 0;  // (dynamic LDS is an upper bound of what a body uses: the group gets the largest request)
   for (int k = 0; k < n; ++k) lds = recs[k]->lds > lds ? recs[k]->lds : lds;
-  if (lds > 32768) {  // (dynamic + static LDS beyond 64 KB needs the attribute on THIS instantiation, per device: set from 32 KB of dynamic LDS up)
-    static std::atomic<uint64_t> done{0};
-    const hipError_t err = set_max_dynamic_lds(reinterpret_cast<const void*>(grouped_kernel<Body, THREADS, MINW, P...>), 160 * 1024 - 4096, done);
-    if (err != hipSuccess) {
-      set_error("grouped launch: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(err));
-      return RDM_ERR_HIP;
-    }
-  }
+  if (int rc = raise_lds_limit<grouped_kernel<Body, THREADS, MINW, P...>>(lds)) return rc;
   hipLaunchKernelGGL((grouped_kernel<Body, THREADS, MINW, P...>), dim3(static_cast<unsigned>(g.first[n])), dim3(THREADS), lds,
                      recs[0]->stream, g);
   const hipError_t lerr = hipGetLastError();  // (taken here: the contexts of the group would otherwise pick it up in resume order)
@@ -153,26 +174,26 @@ int fire_records(const LaunchRecord* const* recs, int n) {
   }
   return 0;
 }
-template <auto Body, auto Kernel, int THREADS, int MINW, class... P>
+template <auto Body, int THREADS, int MINW, class... P>
 inline void launch_sig(Sig<P...>, dim3 grid, size_t lds, hipStream_t st, typename Ident<P>::type... a) {
   static_assert(sizeof(ArgPack<P...>) <= sizeof(LaunchRecord::args), "kernel arguments too large for a launch record");
   static_assert(sizeof(GroupArgs<P...>) <= 4000, "a grouped launch of these arguments exceeds the kernel-argument segment");
   if (grid.x == 0 || grid.y == 0 || grid.z == 0) return;
   if (!lockstep_active()) {
-    hipLaunchKernelGGL(Kernel, grid, dim3(THREADS), lds, st, a...);
+    if (issue_entry<Body, THREADS, MINW, P...>(grid, lds, st, a...) != 0) t_launch_failed = true;
     return;
   }
   LaunchRecord rec;
-  rec.fire = &fire_records<Body, Kernel, THREADS, MINW, P...>;
+  rec.fire = &fire_records<Body, THREADS, MINW, P...>;
   rec.grid = grid; rec.lds = lds; rec.stream = st;
   const ArgPack<P...> pack = make_pack<P...>(a...);
   std::memcpy(rec.args, &pack, sizeof(pack));
   if (lockstep_submit(rec) != 0) t_launch_failed = true;  // (launch_status of this context's caller reports it)
 }
 // The launch of a converted kernel: issued at once outside a lock-step group, recorded and grouped inside one.
-template <auto Body, auto Kernel, int THREADS, int MINW = 1, class... U>
+template <auto Body, int THREADS, int MINW = 1, class... U>
 inline void launch(dim3 grid, size_t lds, hipStream_t st, U... a) {
-  launch_sig<Body, Kernel, THREADS, MINW>(decltype(sig_of(Body)){}, grid, lds, st, a...);
+  launch_sig<Body, THREADS, MINW>(decltype(sig_of(Body)){}, grid, lds, st, a...);
 }
 #endif
 

@@ -13,8 +13,6 @@
 //   u = log_mu - logsumexp_j(Z + v)        logsumexp(x) = max + log(sum(exp(x - max)))
 //   v = log_nu - logsumexp_i(Z + u)
 //   out = ((Z + u) + v) - norm
-#include <atomic>
-
 #include "../../include/rdmnet_hip.h"
 #include "common.h"
 #include "lockstep.h"
@@ -221,11 +219,6 @@ __device__ __forceinline__ void sinkhorn_kernel_body(const dim3 blockIdx, const 
   else if (side <= 100) sinkhorn_iterate<25>(Z, ldz, nr, nc, norm, iters, u, v, rows, cols, m, n, O);
   else sinkhorn_iterate<33>(Z, ldz, nr, nc, norm, iters, u, v, rows, cols, m, n, O);
 }
-__global__ __launch_bounds__(256) void sinkhorn_kernel(const float* scores, int m, int n,
-                                                       const unsigned char* row_mask,
-                                                       const unsigned char* col_mask, const float* alpha_p,
-                                                       int iters, float* out) { sinkhorn_kernel_body(blockIdx, gridDim, scores, m, n, row_mask, col_mask, alpha_p, iters, out); }
-
 
 }  // namespace
 
@@ -237,11 +230,9 @@ extern "C" int rdm_sinkhorn(const float* scores, int64_t batch, int64_t m, int64
               "rdm_sinkhorn: bad sizes (m=%lld n=%lld, max %d)", (long long)m, (long long)n, kMaxSide);
   if (batch == 0) return RDM_OK;
   const size_t lds = sizeof(float) * (static_cast<size_t>(m + 1) * ((n + 1) | 1) + 8);
-  // the 129 x 129 fp32 tile (66.5 KB) needs more than the default 64 KB of dynamic LDS (set once per device)
-  static std::atomic<uint64_t> attr_set{0};
-  RDM_HIP_CHECK(set_max_dynamic_lds(reinterpret_cast<const void*>(sinkhorn_kernel), 160 * 1024 - 4096, attr_set));
+  // (the 129 x 129 fp32 tile, 66.5 KB, is more than the default 64 KB of dynamic LDS: the launch raises the limit)
   RDM_DUP_LOOP("sinkhorn")
-  ::rdm::launch<sinkhorn_kernel_body, sinkhorn_kernel, 256>(dim3(static_cast<unsigned>(batch)), lds, static_cast<hipStream_t>(stream), scores, static_cast<int>(m), static_cast<int>(n), row_mask,
+  ::rdm::launch<sinkhorn_kernel_body, 256>(dim3(static_cast<unsigned>(batch)), lds, static_cast<hipStream_t>(stream), scores, static_cast<int>(m), static_cast<int>(n), row_mask,
                      col_mask, alpha, iters, out);
   return launch_status("sinkhorn_kernel");
 }

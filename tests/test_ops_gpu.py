@@ -99,6 +99,22 @@ def test_patch_scores_gathers_inside_the_gemm(ops, B, k, n_r, n_s, d):
     assert torch.count_nonzero(got[0]) == 0
 
 
+@pytest.mark.parametrize('w', [1, 63, 64, 127, 128, 129, 255, 256, 320])
+def test_gather_rows_every_row_width(ops, w):
+    """rdm_gather_rows launches its body under 64, 128 or 256 threads by the row width (thresholds 128 and 256 words): rows of
+    w int32 words of random bits in a buffer whose row stride is w + 4, indices in and out of range ( -1 and n: zero rows),
+    bit for bit against torch indexing."""
+    g = torch.Generator().manual_seed(w)
+    n = 7
+    x = torch.randint(-2 ** 31, 2 ** 31, (n, w + 4), generator=g, dtype=torch.int64).to(torch.int32)
+    idx = torch.tensor([6, 0, 3, -1, 7])
+    want = x[:, :w][idx.clamp(0, n - 1)]
+    want[3:] = 0
+    got = ops.gather_rows(x.cuda()[:, :w], idx.cuda())
+    assert got.dtype == torch.int32 and got.shape == (5, w)
+    assert torch.equal(got.cpu(), want)
+
+
 @pytest.mark.parametrize('c,h,m,ns', [(1, 65, 500, 700), (32, 65, 400, 900), (64, 63, 300, 500), (128, 69, 200, 300),
                                       (256, 70, 150, 200), (512, 81, 90, 100), (32, 3, 50, 60),
                                       (96, 40, 120, 200), (160, 33, 70, 90), (1024, 20, 40, 60)])  # widths outside 32 * 2^k <= 512: the generic instance

@@ -1,7 +1,7 @@
-// Phase timing of gemm_kernel<64,64,2,2,32,false,2> (the path's main tile): compiles gemm.hip with shader-clock stamps and
+// Phase timing of gemm_kernel_body<64,64,2,2,32,false,2> (the path's main tile): compiles gemm.hip with shader-clock stamps and
 // prints, for workgroup 0, the clocks of prologue (first tiles in flight -> LDS), main loop and epilogue, plus the kernel time.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DRDM_GEMM_TIMING tools/gemm_phase_lab.hip rdmnet_amd/csrc/capi.cpp
-//         rdmnet_amd/csrc/norm.hip -o tools/bin/gemm_phase_lab;   ./tools/bin/gemm_phase_lab M K N splits [1 = with GroupNorm statistics and a row divisor]
+//         rdmnet_amd/csrc/lockstep.cpp rdmnet_amd/csrc/norm.hip -o tools/bin/gemm_phase_lab;   ./tools/bin/gemm_phase_lab M K N splits [1 = with GroupNorm statistics and a row divisor]
 #include "../rdmnet_amd/csrc/gemm.hip"
 #include <cstdio>
 #include <cstdlib>
@@ -24,7 +24,7 @@ int main(int argc, char** argv) {
   dim3 grid((N + 63) / 64, (M + 63) / 64, splits);
   for (int it = 0; it < 4; ++it) {
     (void)hipEventRecord(e0, 0);
-    hipLaunchKernelGGL((gemm_kernel<64, 64, 2, 2, 32, false, 2>), grid, dim3(256), 0, 0, g);
+    ::rdm::launch<gemm_kernel_body<64, 64, 2, 2, 32, false, 2>, 256, 4>(grid, 0, 0, g);  // (the product's bounds; no group here: launched at once)
     (void)hipEventRecord(e1, 0);
     (void)hipDeviceSynchronize();
     float ms; (void)hipEventElapsedTime(&ms, e0, e1);

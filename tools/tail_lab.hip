@@ -1,6 +1,6 @@
-// Phase timing of attention_tail128_kernel: compiles gemm.hip with shader-clock stamps (RDM_TAIL_TIMING) and prints the
+// Phase timing of attention_tail128_body: compiles gemm.hip with shader-clock stamps (RDM_TAIL_TIMING) and prints the
 // cycles workgroup 0 spends in each phase.   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DRDM_TAIL_TIMING tools/tail_lab.hip
-// rdmnet_amd/csrc/capi.cpp rdmnet_amd/csrc/norm.hip -o tools/bin/tail_lab
+// rdmnet_amd/csrc/capi.cpp rdmnet_amd/csrc/lockstep.cpp rdmnet_amd/csrc/norm.hip -o tools/bin/tail_lab
 #include "../rdmnet_amd/csrc/gemm.hip"
 #include <cstdio>
 #include <cstdlib>
@@ -22,8 +22,8 @@ int main(int argc, char** argv) {
   hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
   for (int it = 0; it < 4; ++it) {
     (void)hipEventRecord(e0, 0);
-    if (use_packed) hipLaunchKernelGGL(attention_tail128_kernel<true>, dim3((m + 15) / 16), dim3(512), 0, 0, a);
-    else hipLaunchKernelGGL(attention_tail128_kernel<false>, dim3((m + 15) / 16), dim3(512), 0, 0, a);
+    if (use_packed) ::rdm::launch<attention_tail128_body<true>, 512>(dim3((m + 15) / 16), 0, 0, a);  // (no group here: launched at once)
+    else ::rdm::launch<attention_tail128_body<false>, 512>(dim3((m + 15) / 16), 0, 0, a);
     (void)hipEventRecord(e1, 0);
     (void)hipDeviceSynchronize();
     float ms; (void)hipEventElapsedTime(&ms, e0, e1);

@@ -1,5 +1,5 @@
 """Developer aid (round 5): rewrites hipLaunchKernelGGL(K, grid, dim3(T), lds, st, args...) of the kernels named on the command line into
-::rdm::launch<K_body, K, T>(grid, lds, st, args...) (lockstep.h).   python tools/to_launch.py FILE NAME [NAME ...]"""
+::rdm::launch<K_body, T>(grid, lds, st, args...) (lockstep.h; a second launch bound, the minimum waves, is added by hand).   python tools/to_launch.py FILE NAME [NAME ...]"""
 import re, sys
 
 
@@ -51,7 +51,7 @@ def convert(src, names):
         assert m, (base, block)
         threads = m.group(1).strip()
         body = bare.replace(base, base + '_body', 1)
-        out += src[i:j] + f'::rdm::launch<{body}, {bare}, {threads}>({grid}, {lds}, {st},{args})'
+        out += src[i:j] + f'::rdm::launch<{body}, {threads}>({grid}, {lds}, {st},{args})'
         i = e
 
 

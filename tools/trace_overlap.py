@@ -7,10 +7,12 @@ import re
 
 
 def short(k):
-    """kernel name without the anonymous namespace, argument list and (for grouped launches) everything but the body's name"""
-    m = re.search(r'grouped_kernel.*?N_1\d+([a-z0-9_]+_(?:body|entry))((?:I(?:Li\d+E|Lb[01]E)+E)?)', k)
+    """kernel name without the anonymous namespace and argument list; of a kernel generated from a body (lockstep.h: entry_kernel
+    for a single launch, grouped_kernel for a group's) only the body's name and template arguments, mangled or demangled"""
+    m = (re.search(r'(grouped|entry)_kernelI.*?(?:N_1|L_Z)\d+([a-z0-9_]+_(?:body|entry))((?:I(?:Li\d+E|Lb[01]E)+E)?)', k) or
+         re.search(r'(grouped|entry)_kernel<&(?:\(anonymous namespace\)::)?([a-z0-9_]+_(?:body|entry))((?:<[^<>()]*>)?)', k))
     if m:
-        return 'grouped ' + m.group(1) + (m.group(2) or '')
+        return ('grouped ' if m.group(1) == 'grouped' else '') + m.group(2) + (m.group(3) or '')
     k = k.replace('(anonymous namespace)::', '').replace('void ', '')
     return k.split('(')[0][:80]
 
