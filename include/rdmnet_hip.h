@@ -876,6 +876,14 @@ int rdm_engine_collate_lockstep(rdm_engine* const* engines, int n_pairs, const f
 void rdm_lockstep_stats(long long* out, int reset);
 /* DIAGNOSTIC: self-test of the lock-step scheduler on scripted stand-in launches (no GPU needed; tests/test_lockstep.py). */
 int rdm_lockstep_selftest(int n_ctx, const int* script, int len, int* log, int cap, int* rcs);
+/* DIAGNOSTIC: self-test of the grouped launch on the GPU (tests/test_lockstep_gpu.py).  `n_ctx` (1 .. 8) contexts of a real
+ * lock-step group launch a probe kernel through the product path with scripted grids: script[(k * len + s) * 4 ..] = (gx, gy, gz,
+ * dynamic LDS bytes) of context k's step s (host memory); gx < 0 = a host wait, a grid with a zero dimension = nothing.  Every
+ * workgroup of every launch owns one slot of 10 int32 in `out` (device memory, zeroed by the caller, `cap_slots` slots):
+ * {threads seen, visits, tag = k * len + s, blockIdx.x/y/z, gridDim.x/y/z, LDS round trip ok}, slots in the order (context, step,
+ * linear workgroup id of the step's own grid).  threads = 64 | 256 selects one of the probe's two instantiations.  Waits for
+ * `stream`.  Returns the number of slots written, or a negative error code (rdm_last_error).                                    */
+int rdm_lockstep_selftest_gpu(int n_ctx, const int* script, int len, int threads, int32_t* out, int64_t cap_slots, void* stream);
 void rdm_lockstep_stats_dump(void);
 /* Stage intermediates by name (test/inspection aid): enable before a run, query after it. */
 /* Per-KPConv-layer HIP-event timing of the last run; get_profile returns the number of layers. */

@@ -231,6 +231,7 @@ SIGNATURES = {
     'rdm_lockstep_stats': (None, [c_void, c_int]),
     'rdm_lockstep_stats_dump': (None, []),
     'rdm_lockstep_selftest': (c_int, [c_int, c_void, c_int, c_void, c_int, c_void]),
+    'rdm_lockstep_selftest_gpu': (c_int, [c_int, c_void, c_int, c_int, c_void, c_i64, c_void]),
     'rdm_engine_reserve': (c_int, [c_void, c_size]),
     'rdm_engine_set_wait': (c_int, [c_void, c_int]),
     'rdm_engine_set_pairs_in_flight': (c_int, [c_void, c_int]),

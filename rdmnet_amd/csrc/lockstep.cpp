@@ -355,6 +355,114 @@ extern "C" int rdm_lockstep_selftest(int n_ctx, const int* script, int len, int*
   return rc != 0 ? -1 : t_log_n / 2;
 }
 
+// Self-test of the grouped launch ON the GPU (tests/test_lockstep_gpu.py): n contexts of a real lockstep_run launch a probe body
+// -- written and launched as every converted kernel is, so it goes launch_sig -> lockstep_submit -> fire_records -> grouped_kernel
+// (or entry_kernel for a record that found no partner) -- with scripted grids and dynamic-LDS sizes.  script[(k * len + s) * 4 ..]
+// = (gx, gy, gz, lds_bytes) of context k's step s: gx < 0 = a host wait (lockstep_sync); a grid with a zero dimension is not
+// launched (and does not yield), which also pads the shorter scripts.  Every workgroup of every launch owns one slot of
+// kProbeWords int32 in `out` (device): slot = base_slot + bx + gx * (by + gy * bz) with its OWN grid, where base_slot = the
+// volumes of the earlier contexts' whole scripts + the volumes of this context's earlier steps.  The slot holds
+//   [0] += 1 per thread, [1] += 1 per workgroup, [2..9] = {tag = k * len + s, bx, by, bz, gridDim.x, gridDim.y, gridDim.z, lds_ok};
+// lds_ok: every thread writes tag ^ threadIdx.x into the last THREADS words of its lds_bytes of dynamic LDS and reads its
+// neighbour's word back after a barrier (1 if lds_bytes == 0).  `out` must be zeroed by the caller; nothing outside the first
+// (returned count) slots is written.  threads = 64 or 256 selects the probe's instantiation (two different kernels).  Returns the
+// number of slots, or a negative error code.
+namespace rdm {
+namespace {
+constexpr int kProbeWords = 10;
+constexpr int kProbeMaxVolume = 1 << 16;  // workgroups per scripted launch
+
+template <int THREADS>
+__device__ __forceinline__ void lockstep_probe_body(const dim3 blockIdx, const dim3 gridDim, int32_t* out, int base_slot, int tag,
+                                                    int lds_bytes) {
+  extern __shared__ __align__(16) unsigned char s_probe[];
+  __shared__ int s_ok;
+  const int t = static_cast<int>(threadIdx.x);
+  if (t == 0) s_ok = 1;
+  __syncthreads();
+  if (lds_bytes > 0) {  // (the same for the whole workgroup)
+    int* w = reinterpret_cast<int*>(s_probe + lds_bytes) - THREADS;
+    w[t] = tag ^ t;
+    __syncthreads();
+    const int nb = (t + 1) % THREADS;
+    if (w[nb] != (tag ^ nb)) atomicAnd(&s_ok, 0);
+  }
+  __syncthreads();
+  const int b = static_cast<int>(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
+  int32_t* slot = out + static_cast<int64_t>(base_slot + b) * kProbeWords;
+  atomicAdd(&slot[0], 1);
+  if (t == 0) {
+    atomicAdd(&slot[1], 1);
+    slot[2] = tag;
+    slot[3] = static_cast<int>(blockIdx.x); slot[4] = static_cast<int>(blockIdx.y); slot[5] = static_cast<int>(blockIdx.z);
+    slot[6] = static_cast<int>(gridDim.x); slot[7] = static_cast<int>(gridDim.y); slot[8] = static_cast<int>(gridDim.z);
+    slot[9] = s_ok;
+  }
+}
+
+struct GpuSelfTest { const int* script; int len; int threads; int32_t* out; int region[kGroupMax]; hipStream_t st; };
+int selftest_gpu_ctx(int k, void* user) {
+  const GpuSelfTest& t = *static_cast<const GpuSelfTest*>(user);
+  int slot = t.region[k];
+  for (int s = 0; s < t.len; ++s) {
+    const int* e = t.script + (static_cast<size_t>(k) * t.len + s) * 4;
+    if (e[0] < 0) {
+      lockstep_sync();
+      continue;
+    }
+    const dim3 grid(static_cast<unsigned>(e[0]), static_cast<unsigned>(e[1]), static_cast<unsigned>(e[2]));
+    const size_t lds = static_cast<size_t>(e[3]);
+    if (t.threads == 64) launch<lockstep_probe_body<64>, 64>(grid, lds, t.st, t.out, slot, k * t.len + s, e[3]);
+    else launch<lockstep_probe_body<256>, 256, 2>(grid, lds, t.st, t.out, slot, k * t.len + s, e[3]);
+    if (int rc = launch_status("the lock-step probe")) return rc;
+    slot += e[0] * e[1] * e[2];
+  }
+  return 0;
+}
+int selftest_gpu_wait(hipStream_t st, void*) {  // (1: told apart from lockstep_run's own codes)
+  const hipError_t err = hipStreamSynchronize(st);
+  if (err != hipSuccess) set_error("rdm_lockstep_selftest_gpu: the group's wait failed: %s", hipGetErrorString(err));
+  return err == hipSuccess ? 0 : 1;
+}
+}  // namespace
+}  // namespace rdm
+extern "C" int rdm_lockstep_selftest_gpu(int n_ctx, const int* script, int len, int threads, int32_t* out, int64_t cap_slots,
+                                         void* stream) {
+  using namespace rdm;
+  RDM_REQUIRE(script && out, "rdm_lockstep_selftest_gpu: null pointer");
+  RDM_REQUIRE(n_ctx >= 1 && n_ctx <= kGroupMax && len >= 1 && len <= 4096, "rdm_lockstep_selftest_gpu: 1 .. %d contexts of 1 .. 4096 steps", kGroupMax);
+  RDM_REQUIRE(threads == 64 || threads == 256, "rdm_lockstep_selftest_gpu: the probe is built for 64 and for 256 threads");
+  GpuSelfTest t{script, len, threads, out, {}, static_cast<hipStream_t>(stream)};
+  int64_t total = 0;
+  for (int k = 0; k < n_ctx; ++k) {
+    t.region[k] = static_cast<int>(total);
+    for (int s = 0; s < len; ++s) {
+      const int* e = script + (static_cast<size_t>(k) * len + s) * 4;
+      if (e[0] < 0) continue;
+      RDM_REQUIRE(e[1] >= 0 && e[2] >= 0 && e[0] <= kProbeMaxVolume && e[1] <= kProbeMaxVolume && e[2] <= kProbeMaxVolume &&
+                      static_cast<int64_t>(e[0]) * e[1] * e[2] <= kProbeMaxVolume,
+                  "rdm_lockstep_selftest_gpu: context %d step %d: a grid of at most %d workgroups", k, s, kProbeMaxVolume);
+      RDM_REQUIRE(e[3] == 0 || (e[3] >= threads * 4 && e[3] <= kMaxDynamicLds && e[3] % 4 == 0),
+                  "rdm_lockstep_selftest_gpu: context %d step %d: 0 or %d .. %d bytes of dynamic LDS (whole words)", k, s,
+                  threads * 4, kMaxDynamicLds);
+      total += static_cast<int64_t>(e[0]) * e[1] * e[2];
+      RDM_REQUIRE(total <= cap_slots, "rdm_lockstep_selftest_gpu: the script needs more than the %lld slots of `out`",
+                  static_cast<long long>(cap_slots));
+    }
+  }
+  int rcs[kGroupMax] = {};
+  const int rc = lockstep_run(n_ctx, selftest_gpu_ctx, &t, t.st, selftest_gpu_wait, nullptr, rcs);
+  if (rc == -1 || rc == -3) {
+    set_error("rdm_lockstep_selftest_gpu: %s", rc == -1 ? "called from inside a lock-step group" : "no memory for the context stacks");
+    return RDM_ERR_ARG;
+  }
+  if (rc != 0) return RDM_ERR_HIP;
+  for (int k = 0; k < n_ctx; ++k)
+    if (rcs[k] != 0) return rcs[k];
+  RDM_HIP_CHECK(hipStreamSynchronize(t.st));
+  return static_cast<int>(total);
+}
+
 // Developer counters (tools/lockstep_lab.py): ns in lock-step runs, ns of them in host waits, waits, grouped launches, records, runs
 extern "C" void rdm_lockstep_stats_dump() {  // (RDM_LOCKSTEP_STATS=1: launches and records per kernel and dynamic LDS size)
   std::lock_guard<std::mutex> lk(rdm::g_by_kernel_mu);

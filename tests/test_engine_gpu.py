@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+import small_clouds
+
 pytestmark = pytest.mark.gpu
 
 
@@ -242,13 +244,11 @@ def test_plain_engine_run_equals_per_op_mirror_on_random_scenes(ctx, seed):
     assert np.array_equal(hc, out['corr_scores'].cpu().numpy())
 
 
-@pytest.mark.parametrize('n,scale', [(500, 20.0), (50, 5.0), (5, 1.0), (1, 1.0), (4000, 200.0)])
+@pytest.mark.parametrize('n,scale', small_clouds.DEGENERATE)
 def test_engine_handles_degenerate_clouds(ctx, n, scale):
     """Tiny, single-point and extremely sparse clouds (every point its own voxel at all levels) run through the whole
     path: no hang, no capacity error, a finite pose, sizes that shrink monotonically."""
-    rng = np.random.default_rng(n)
-    a = torch.from_numpy((rng.uniform(-1, 1, (n, 3)) * np.array([scale, scale, 2.0])).astype(np.float32)).cuda()
-    b = torch.from_numpy((rng.uniform(-1, 1, (max(n - 3, 1), 3)) * np.array([scale, scale, 2.0])).astype(np.float32)).cuda()
+    a, b = (torch.from_numpy(x).cuda() for x in small_clouds.degenerate_pair(n, scale))
     res = ctx['eng'].run(a, b)
     assert np.isfinite(ctx['eng'].transform()).all()
     assert res.level_sizes[0] == a.shape[0] + b.shape[0]
@@ -266,9 +266,7 @@ def test_latency_mode_on_degenerate_clouds_and_after_an_error(ctx):
     try:
         with torch.cuda.stream(st):
             for n, scale in ((500, 20.0), (5, 1.0), (1, 1.0), (4000, 200.0)):
-                rng = np.random.default_rng(n)
-                a = torch.from_numpy((rng.uniform(-1, 1, (n, 3)) * np.array([scale, scale, 2.0])).astype(np.float32)).cuda()
-                b = torch.from_numpy((rng.uniform(-1, 1, (max(n - 3, 1), 3)) * np.array([scale, scale, 2.0])).astype(np.float32)).cuda()
+                a, b = (torch.from_numpy(x).cuda() for x in small_clouds.degenerate_pair(n, scale))
                 st.synchronize()
                 outs = []
                 for mode in (0, 2):
@@ -300,10 +298,7 @@ def test_engine_deferred_large_buffer_pass_matches_per_op_searches(ctx):
     """6 000 points in a 6 x 6 x 4 m box: 300-500 points inside a level-0 search radius, more than the first pass's
     256-key buffer.  The engine defers the large-buffer pass of all 14 searches to one launch; the per-op path runs it
     right after each search: same neighbour tables."""
-    rng = np.random.default_rng(5)
-    box = np.array([3.0, 3.0, 2.0])
-    a = (rng.uniform(-1, 1, (6000, 3)) * box).astype(np.float32)
-    b = (rng.uniform(-1, 1, (5500, 3)) * box).astype(np.float32)
+    a, b = small_clouds.overflow_box_pair()
     data = ctx['collate'].collate_pair(a, b, ctx['cfg'])
     ctx['eng'].run(torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda())
     for i in range(5):

@@ -1,7 +1,9 @@
 """CPU: the lock-step scheduler (rdmnet_amd/csrc/lockstep.cpp) on scripted stand-in launches -- no GPU, no kernel.  Contexts run
 scripts of recorded launches of two stand-in kernels (1 = A, 2 = B), waits (3), layer boundaries (4) and deferred events (5); the
 library logs what the scheduler does: (1 | 2, n) = that kernel issued ONCE for n contexts, (3, i) = the i-th wait of the group,
-(4, k) = context k's event recorded.  The GPU half (every pair the bits of its own run) is tests/test_engine_gpu.py."""
+(4, k) = context k's event recorded.  The GPU half is tests/test_lockstep_gpu.py (the grouped launch itself on a probe kernel: every
+workgroup of every record once, with its own coordinates, arguments and LDS; groups of up to eight pairs, degenerate ones among
+them) and tests/test_engine_gpu.py (every pair the bits of its own run)."""
 import ctypes
 
 import numpy as np
