@@ -1219,6 +1219,50 @@ int rdm_voxel_map_register(const void* map, size_t map_bytes, int64_t capacity, 
                            int max_iteration, double rot_eps, double trans_eps, double* transforms, double* hessians, double* gradients,
                            double* costs, int64_t* stats, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- §7 voxel observations: in how many scans a voxel was seen, and a map without the voxels seen too rarely (voxel_map.hip) ------
+ * Not in the reference tree -> parity unpinned; the project's own definition, pinned to the NumPy restatement
+ * tests/voxel_observations_restatement.py.  Every integrated scan has an integer id in [0, 2^31 - 1).  A voxel OBSERVES scan s when at
+ * least one point of s is integrated into it -- the gates, the transform, the quantisation and the full-table rule are those of
+ * rdm_voxel_map_integrate; a skipped or dropped point observes nothing.  Per voxel: scans = the number of distinct ids observed,
+ * first = the smallest and last = the largest of them.  They are a function of the SET of (id, point) pairs under one condition: all
+ * points of an id come in ONE call.
+ * An observations block is a third caller-owned device block of rdm_voxel_observations_bytes(capacity) bytes (0 for a bad capacity)
+ * beside the map block and the (optional) moments block, addressed by the map's slot index: per slot a 64-bit scratch mask (bit s =
+ * scan s of the running call was seen) and three int32 {scans, first, last}.  rdm_voxel_observations_reset: no scan seen -- scans 0,
+ * first 2^31 - 1, last -1 (a fresh block must be reset, together with its map).  rdm_voxel_map_integrate_observed takes the arguments
+ * of rdm_voxel_map_integrate_moments plus the block and first_id: scan s of the batch has the id first_id + s.  `moments` may be null
+ * (moments_bytes is then not looked at): the one entry point of a map with and without moments.  A call carries at most
+ * RDM_VOXEL_OBSERVATIONS_MAX_SCANS scans; n_scans above that, first_id < 0 or first_id + n_scans > 2^31 - 1 are RDM_ERR_ARG, a short
+ * block RDM_ERR_WORKSPACE.  One sweep zeroes the masks at the start of the call, then ONE pass: the point is integrated as always, the
+ * slot's mask is loaded and, if the scan's bit is clear, set by an atomic or; the one thread that got the bit clear back adds 1 to
+ * scans and takes an atomic min / max on first / last.  Bits only go from 0 to 1 inside a call, so in a dense voxel almost every point
+ * costs one load and no atomic.  The six counters and the map are those of the other two integrates, bit for bit.  A map must be
+ * integrated through this function throughout.  rdm_voxel_observations_rehash is the counterpart of rdm_voxel_moments_rehash: AFTER
+ * the map's rehash (or prune) old_map -> new_map on the same stream it resets new_observations and, for every occupied slot of
+ * old_map, looks the key up in new_map (without claiming) and copies {scans, first, last}; a key that new_map lacks is passed over,
+ * and the masks are not copied.  rdm_voxel_moments_rehash passes over such a key in the same way, so both serve after a prune.
+ * rdm_voxel_map_extract_observations: selection, order, min_points, max_rows, *n_rows and the workspace are those of
+ * rdm_voxel_map_extract, so its rows are the rows of that call; outputs int32 [max_rows] each.  rdm_voxel_map_prune: resets new_map
+ * (another block, new_capacity >= old_capacity) and moves into it every occupied slot of old_map with count >= min_points and scans >=
+ * min_scans; occupied = the number kept, integrated = the sum of their counts, the other four counters are copied.  The moments and
+ * the observations of the kept keys follow through the two *_rehash functions.  Integer atomics only; no unbounded loop.            */
+#define RDM_VOXEL_OBSERVATIONS_MAX_SCANS 64
+size_t rdm_voxel_observations_bytes(int64_t capacity);
+int rdm_voxel_observations_reset(void* observations, size_t observations_bytes, int64_t capacity, void* stream);
+int rdm_voxel_map_integrate_observed(void* map, size_t map_bytes, int64_t capacity, int channels, double voxel, const float* points,
+                                     int64_t ld, int64_t total, const int64_t* offsets, const double* poses, int64_t n_scans,
+                                     double min_range, double max_range, void* moments, size_t moments_bytes, void* observations,
+                                     size_t observations_bytes, int64_t first_id, void* stream);
+int rdm_voxel_observations_rehash(const void* old_map, size_t old_bytes, int64_t old_capacity, const void* old_observations,
+                                  size_t old_observations_bytes, const void* new_map, size_t new_bytes, int64_t new_capacity,
+                                  void* new_observations, size_t new_observations_bytes, int channels, void* stream);
+int rdm_voxel_map_extract_observations(const void* map, size_t map_bytes, int64_t capacity, int channels, const void* observations,
+                                       size_t observations_bytes, double voxel, int64_t min_points, int32_t* scans, int32_t* first,
+                                       int32_t* last, int64_t max_rows, int64_t* n_rows, void* ws, size_t ws_bytes, void* stream);
+int rdm_voxel_map_prune(const void* old_map, size_t old_bytes, int64_t old_capacity, const void* old_observations,
+                        size_t old_observations_bytes, void* new_map, size_t new_bytes, int64_t new_capacity, int channels,
+                        int64_t min_points, int64_t min_scans, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,9 +20,15 @@
 //
 // Moments (include/rdmnet_hip.h, "voxel moments"; tests/voxel_moments_restatement.py): a second caller-owned block of nine int64
 // sums per slot, addressed by the map's slot index -- the first and second moments of the 12-bit local coordinates u_d, so every
-// voxel gets a mean, a covariance and a normal.  integrate_kernel<true> is the integrate kernel with nine more integer adds into
-// the slot that find_or_claim returned; integrate_kernel<false>, the plain one, is the same body with that block compiled out.  Extraction shares the
+// voxel gets a mean, a covariance and a normal.  integrate_kernel<true, .> is the integrate kernel with nine more integer adds into
+// the slot that find_or_claim returned; integrate_kernel<false, false>, the plain one, is the same body with that block compiled out.  Extraction shares the
 // selection and the sort and solves the 3 x 3 symmetric eigenproblem per row with a float64 cyclic Jacobi of kSweeps sweeps.
+//
+// Observations (include/rdmnet_hip.h, "voxel observations"; tests/voxel_observations_restatement.py): a third caller-owned block,
+// addressed by the map's slot index -- per slot a 64-bit scratch mask and the record {scans, first, last}: in how many distinct scans
+// the voxel was seen, and the smallest and the largest of their ids.  integrate_kernel<., true> is the integrate kernel plus, after the
+// point is counted, one load of the slot's mask and, where the scan's bit is still clear, one atomicOr; the one thread that got the
+// bit clear back updates the record.  Bits only go from 0 to 1 inside a call, so a set bit seen by the plain load is final.
 //
 // Three pinned definitions are written once: the point gate (gate_sensor, gate_world; integrate and register), the key (pack_key,
 // key_cell; integrate, register, extract) and the voxel Gaussian (voxel_gaussian; both extracts and register).  `#pragma clang fp
@@ -53,6 +59,9 @@ constexpr int kMomShift = RDM_VOXEL_MOMENTS_SHIFT;  // u_d = (Q_d - (cell_d << k
 constexpr double kMomSteps = 4096.0;                // 2^(kFrac - kMomShift) steps of u_d per voxel edge
 constexpr int kSweeps = 8;                          // cyclic Jacobi sweeps (a 3 x 3 symmetric matrix converges in 4 to 5)
 static_assert(kPlanes == 9 && kFrac - kMomShift == 12, "nine sums of 12-bit local coordinates");
+constexpr int kMaxObsScans = RDM_VOXEL_OBSERVATIONS_MAX_SCANS;  // scans of one integrate call: the bits of a slot's mask
+constexpr int64_t kMaxScanId = 0x7fffffffll;                    // ids lie below this: `first` of a slot that observed nothing
+static_assert(kMaxObsScans == 64, "one 64-bit mask per slot");
 
 enum { kOccupied = 0, kIntegrated, kNonfinite, kRange, kExtent, kDropped };
 
@@ -117,6 +126,24 @@ __device__ __forceinline__ long long moment_at(long long slot, int k, long long 
   return slot * kPlanes + k;
 #endif
 }
+
+// The observations block: the masks as one plane (the sweep before a call and the one load a point are dense in it), then the records.
+struct Observations {
+  unsigned long long* mask;  // [S] scratch: bit s = scan s of the running call was seen
+  int* record;               // [S] records, through observed_at only
+};
+enum { kObsScans = 0, kObsFirst, kObsLast, kObsFields };
+
+bool carve_observations(Arena& ar, int64_t capacity, Observations& o) {
+  const size_t s = static_cast<size_t>(capacity);
+  o.mask = ar.take<unsigned long long>(s);
+  o.record = ar.take<int>(s * kObsFields);
+  return ar.ok;
+}
+
+// Field k of a slot's record.  Slot-major: the three fields are 12 consecutive bytes, so a first sighting's three atomics fall into
+// one (at most two) 64-byte lines; nothing outside this function knows the layout.
+__device__ __forceinline__ long long observed_at(long long slot, int k) { return slot * kObsFields + k; }
 
 __global__ void __launch_bounds__(kBlock) reset_kernel(Table t, long long capacity, int channels) {
   const long long stride = static_cast<long long>(gridDim.x) * kBlock;
@@ -219,12 +246,15 @@ __device__ __forceinline__ long long scan_of(const int64_t* __restrict__ offsets
   return lo;
 }
 
-// Both integrate kernels.  kMoments = false is the plain integrate: `moments` is unused and every moments statement is compiled out.
-template <bool kMoments>
+// The integrate kernels.  kMoments = false: `moments` is unused and every moments statement is compiled out; kObserved = false: the
+// same for `obs` and `first_id` (the last arguments, so the plain kernels read theirs where they always did).  With kObserved the
+// scan's position in the batch is its bit, so n_scans <= kMaxObsScans, and its id is first_id + that position.
+template <bool kMoments, bool kObserved>
 __global__ void __launch_bounds__(kBlock) integrate_kernel(Table t, unsigned long long* __restrict__ moments, long long capacity,
                                                            int channels, double voxel, const float* __restrict__ points, long long ld,
                                                            long long total, const int64_t* __restrict__ offsets,
-                                                           const double* __restrict__ poses, long long n_scans, double lo2, double hi2) {
+                                                           const double* __restrict__ poses, long long n_scans, double lo2, double hi2,
+                                                           Observations obs, int first_id) {
 #pragma clang fp contract(off)
   __shared__ unsigned int tally[kStats];
   if (threadIdx.x < kStats) tally[threadIdx.x] = 0u;
@@ -237,10 +267,12 @@ __global__ void __launch_bounds__(kBlock) integrate_kernel(Table t, unsigned lon
     float v[kMaxC];
     double wd[3];
     long long q[kMaxC];
+    [[maybe_unused]] int bit = 0;  // kObserved: the scan's position in the batch
     int verdict = gate_sensor(points + i * ld, channels, lo2, hi2, v);
     if (verdict == kPass) {
       const long long scan = scan_of(offsets, n_scans, i);
       if (scan >= n_scans) continue;  // (offsets that do not ascend)
+      if constexpr (kObserved) bit = static_cast<int>(scan);
       verdict = gate_world(v, poses + scan * 16, voxel, wd, q);
     }
     if (verdict != kPass) {
@@ -265,6 +297,15 @@ __global__ void __launch_bounds__(kBlock) integrate_kernel(Table t, unsigned lon
       for (int d = 0; d < 3; ++d) atomicAdd(moments + moment_at(slot, k++, capacity), u[d]);
       for (int a = 0; a < 3; ++a)
         for (int b = a; b < 3; ++b) atomicAdd(moments + moment_at(slot, k++, capacity), u[a] * u[b]);
+    }
+    if constexpr (kObserved) {
+      const unsigned long long seen = 1ull << bit;  // (bit < n_scans <= 64)
+      if ((ld_agent(obs.mask + slot) & seen) == 0ull && (atomicOr(obs.mask + slot, seen) & seen) == 0ull) {
+        const int id = first_id + bit;  // this thread is the voxel's first sighting of the scan
+        atomicAdd(obs.record + observed_at(slot, kObsScans), 1);
+        atomicMin(obs.record + observed_at(slot, kObsFirst), id);
+        atomicMax(obs.record + observed_at(slot, kObsLast), id);
+      }
     }
   }
   __syncthreads();
@@ -304,21 +345,67 @@ __global__ void __launch_bounds__(kBlock) moments_rehash_kernel(Table a, const u
   }
 }
 
+// The sweep before an integrate call (records = false: the masks alone) and the reset: no scan seen, first = kMaxScanId, last = -1.
+__global__ void __launch_bounds__(kBlock) observations_reset_kernel(Observations o, long long capacity, bool records) {
+  const long long stride = static_cast<long long>(gridDim.x) * kBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < capacity; i += stride) {
+    o.mask[i] = 0ull;
+    if (records) {
+      o.record[observed_at(i, kObsScans)] = 0;
+      o.record[observed_at(i, kObsFirst)] = static_cast<int>(kMaxScanId);
+      o.record[observed_at(i, kObsLast)] = -1;
+    }
+  }
+}
+
+// moments_rehash_kernel's counterpart (`ob` reset before): the record of every occupied slot of `a` whose key `b` holds.  The mask is
+// scratch and stays behind.
+__global__ void __launch_bounds__(kBlock) observations_rehash_kernel(Table a, Observations oa, long long cap_a, Table b, Observations ob,
+                                                                     long long cap_b) {
+  const long long stride = static_cast<long long>(gridDim.x) * kBlock;
+  for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < cap_a; i += stride) {
+    const unsigned long long key = a.keys[i];
+    if (key == kEmpty) continue;
+    const long long slot = find(b.keys, cap_b, key);
+    if (slot < 0) continue;  // (a key that the map's rehash did not move: the voxels that rdm_voxel_map_prune left behind)
+    for (int k = 0; k < kObsFields; ++k) ob.record[observed_at(slot, k)] = oa.record[observed_at(i, k)];
+  }
+}
+
 // Every occupied slot of `a` into `b` (reset before): the keys are distinct, so a slot is claimed once and filled with plain stores.
-__global__ void __launch_bounds__(kBlock) rehash_kernel(Table a, long long cap_a, Table b, long long cap_b, int channels) {
+// kPrune (rdm_voxel_map_prune): only the slots with at least min_points points seen in at least min_scans scans (`oa`: the records of
+// `a`), and `occupied` and `integrated` are counted over those; the other arguments are unused without it.
+template <bool kPrune>
+__global__ void __launch_bounds__(kBlock) rehash_kernel(Table a, long long cap_a, Table b, long long cap_b, int channels, Observations oa,
+                                                        unsigned int min_points, int min_scans) {
+  __shared__ unsigned long long kept[2];  // voxels, points
+  if constexpr (kPrune) {
+    if (threadIdx.x < 2) kept[threadIdx.x] = 0ull;
+    __syncthreads();
+  }
   const long long stride = static_cast<long long>(gridDim.x) * kBlock;
   const long long first = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
-  if (first < kStats) b.counters[first] = a.counters[first];
+  if (first < kStats && !(kPrune && first <= kIntegrated)) b.counters[first] = a.counters[first];
   for (long long i = first; i < cap_a; i += stride) {
     const unsigned long long key = a.keys[i];
     if (key == kEmpty) continue;
+    if (kPrune && (a.counts[i] < min_points || oa.record[observed_at(i, kObsScans)] < min_scans)) continue;
     int claimed;
     const long long slot = find_or_claim(b.keys, cap_b, key, &claimed);
     if (slot < 0 || !claimed) continue;  // (cap_b >= cap_a and distinct keys: not reached)
     b.counts[slot] = a.counts[i];
     for (int c = 0; c < channels; ++c) b.sums[c * cap_b + slot] = a.sums[c * cap_a + i];
+    if constexpr (kPrune) {
+      atomicAdd(&kept[0], 1ull);
+      atomicAdd(&kept[1], static_cast<unsigned long long>(a.counts[i]));
+    }
+  }
+  if constexpr (kPrune) {  // (reset_kernel left both counters of `b` at zero)
+    __syncthreads();
+    if (threadIdx.x < 2 && kept[threadIdx.x] != 0ull) atomicAdd(b.counters + threadIdx.x, kept[threadIdx.x]);
   }
 }
+static_assert(kOccupied == 0 && kIntegrated == 1, "rehash_kernel<true> counts these two");
 
 __global__ void __launch_bounds__(kBlock) select_kernel(Table t, long long capacity, unsigned int min_points,
                                                         unsigned long long* __restrict__ keys, int* __restrict__ slots,
@@ -439,6 +526,23 @@ __global__ void __launch_bounds__(kBlock) emit_moments_kernel(Table t, const uns
   }
 }
 
+__global__ void __launch_bounds__(kBlock) emit_observations_kernel(Observations o, const int* __restrict__ slots,
+                                                                   const unsigned long long* __restrict__ n_sel, long long max_rows,
+                                                                   int32_t* __restrict__ scans, int32_t* __restrict__ first_seen,
+                                                                   int32_t* __restrict__ last_seen, int64_t* __restrict__ n_rows) {
+  const long long stride = static_cast<long long>(gridDim.x) * kBlock;
+  const long long first = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
+  const long long m = static_cast<long long>(*n_sel);
+  if (first == 0) *n_rows = m;
+  const long long rows = m < max_rows ? m : max_rows;
+  for (long long r = first; r < rows; r += stride) {
+    const long long slot = slots[r];
+    scans[r] = o.record[observed_at(slot, kObsScans)];
+    first_seen[r] = o.record[observed_at(slot, kObsFirst)];
+    last_seen[r] = o.record[observed_at(slot, kObsLast)];
+  }
+}
+
 unsigned blocks_for(int64_t n) {
   const int64_t b = (n + kBlock - 1) / kBlock;
   return static_cast<unsigned>(b < 1 ? 1 : (b > static_cast<int64_t>(kMaxBlocks) ? kMaxBlocks : b));
@@ -486,6 +590,17 @@ int open_moments(const char* what, const void* moments, size_t moments_bytes, in
   if (!ar.ok) {
     set_error("%s: the moments block is too small (%zu < %zu bytes)", what, moments_bytes, ar.off);
     return too_small;
+  }
+  return RDM_OK;
+}
+
+// the observations block of a caller, or the error code after set_error
+int open_observations(const char* what, const void* observations, size_t observations_bytes, int64_t capacity, Observations& o) {
+  RDM_REQUIRE(observations != nullptr, "%s: null observations block", what);
+  Arena ar(const_cast<void*>(observations), observations_bytes);
+  if (!carve_observations(ar, capacity, o)) {
+    set_error("%s: the observations block is too small (%zu < %zu bytes)", what, observations_bytes, ar.off);
+    return RDM_ERR_WORKSPACE;
   }
   return RDM_OK;
 }
@@ -754,21 +869,34 @@ int check_batch(const char* what, double voxel, int channels, const float* point
   return RDM_OK;
 }
 
-// rdm_voxel_map_integrate (want_moments = false: `moments` is not looked at) and rdm_voxel_map_integrate_moments
+// rdm_voxel_map_integrate (want_moments = false: `moments` is not looked at), rdm_voxel_map_integrate_moments and, with observed,
+// rdm_voxel_map_integrate_observed: the batch's scans have the ids first_id, first_id + 1, ...
 int integrate(const char* what, void* map, size_t map_bytes, int64_t capacity, int channels, double voxel, const float* points, int64_t ld,
               int64_t total, const int64_t* offsets, const double* poses, int64_t n_scans, double min_range, double max_range,
-              bool want_moments, void* moments, size_t moments_bytes, void* stream) {
+              bool want_moments, void* moments, size_t moments_bytes, bool observed, void* observations, size_t observations_bytes,
+              int64_t first_id, void* stream) {
   Table t;
   unsigned long long* m = nullptr;
+  Observations o{nullptr, nullptr};
   if (const int rc = open_table(what, map, map_bytes, capacity, channels, t)) return rc;
   if (want_moments)
     if (const int rc = open_moments(what, moments, moments_bytes, capacity, m)) return rc;
+  if (observed) {
+    if (const int rc = open_observations(what, observations, observations_bytes, capacity, o)) return rc;
+    RDM_REQUIRE(n_scans <= kMaxObsScans && first_id >= 0 && first_id <= kMaxScanId - (n_scans > 0 ? n_scans : 0),
+                "%s: a call takes at most %d scans and ids in [0, 2^31 - 1), got %lld scans from id %lld", what, kMaxObsScans,
+                static_cast<long long>(n_scans), static_cast<long long>(first_id));
+  }
   if (const int rc = check_batch(what, voxel, channels, points, ld, total, offsets, poses, n_scans, INT64_MAX, false, min_range, max_range))
     return rc;
   if (n_scans == 0 || total == 0) return RDM_OK;
-  hipLaunchKernelGGL(want_moments ? integrate_kernel<true> : integrate_kernel<false>, dim3(blocks_for(total)), dim3(kBlock), 0,
-                     static_cast<hipStream_t>(stream), t, m, capacity, channels, voxel, points, ld, total, offsets, poses, n_scans,
-                     min_range * min_range, max_range * max_range);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (observed)  // the masks of the call before
+    hipLaunchKernelGGL(observations_reset_kernel, dim3(blocks_for(capacity)), dim3(kBlock), 0, s, o, static_cast<long long>(capacity), false);
+  auto kernel = observed ? (want_moments ? integrate_kernel<true, true> : integrate_kernel<false, true>)
+                         : (want_moments ? integrate_kernel<true, false> : integrate_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(blocks_for(total)), dim3(kBlock), 0, s, t, m, capacity, channels, voxel, points, ld, total, offsets,
+                     poses, n_scans, min_range * min_range, max_range * max_range, o, static_cast<int>(first_id));
   return launch_status(what);
 }
 
@@ -822,7 +950,7 @@ extern "C" int rdm_voxel_map_integrate(void* map, size_t map_bytes, int64_t capa
                                        int64_t ld, int64_t total, const int64_t* offsets, const double* poses, int64_t n_scans,
                                        double min_range, double max_range, void* stream) {
   return rdm::integrate("rdm_voxel_map_integrate", map, map_bytes, capacity, channels, voxel, points, ld, total, offsets, poses, n_scans,
-                        min_range, max_range, false, nullptr, 0, stream);
+                        min_range, max_range, false, nullptr, 0, false, nullptr, 0, 0, stream);
 }
 
 extern "C" int rdm_voxel_map_rehash(const void* old_map, size_t old_bytes, int64_t old_capacity, void* new_map, size_t new_bytes,
@@ -834,8 +962,8 @@ extern "C" int rdm_voxel_map_rehash(const void* old_map, size_t old_bytes, int64
   RDM_REQUIRE(new_capacity >= old_capacity && new_map != old_map, "rdm_voxel_map_rehash: the new map must be another block of at least the old capacity");
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(reset_kernel, dim3(blocks_for(new_capacity)), dim3(kBlock), 0, s, b, static_cast<long long>(new_capacity), channels);
-  hipLaunchKernelGGL(rehash_kernel, dim3(blocks_for(old_capacity)), dim3(kBlock), 0, s, a, static_cast<long long>(old_capacity), b,
-                     static_cast<long long>(new_capacity), channels);
+  hipLaunchKernelGGL(rehash_kernel<false>, dim3(blocks_for(old_capacity)), dim3(kBlock), 0, s, a, static_cast<long long>(old_capacity), b,
+                     static_cast<long long>(new_capacity), channels, Observations{nullptr, nullptr}, 0u, 0);
   return launch_status("rdm_voxel_map_rehash");
 }
 
@@ -901,7 +1029,7 @@ extern "C" int rdm_voxel_map_integrate_moments(void* map, size_t map_bytes, int6
                                                const double* poses, int64_t n_scans, double min_range, double max_range, void* moments,
                                                size_t moments_bytes, void* stream) {
   return rdm::integrate("rdm_voxel_map_integrate_moments", map, map_bytes, capacity, channels, voxel, points, ld, total, offsets, poses,
-                        n_scans, min_range, max_range, true, moments, moments_bytes, stream);
+                        n_scans, min_range, max_range, true, moments, moments_bytes, false, nullptr, 0, 0, stream);
 }
 
 extern "C" int rdm_voxel_moments_rehash(const void* old_map, size_t old_bytes, int64_t old_capacity, const void* old_moments,
@@ -941,6 +1069,98 @@ extern "C" int rdm_voxel_map_extract_moments(const void* map, size_t map_bytes, 
   hipLaunchKernelGGL(emit_moments_kernel, dim3(blocks_for(max_rows)), dim3(kBlock), 0, s, t, m, static_cast<long long>(capacity), voxel,
                      w.slots, w.n_sel, static_cast<long long>(max_rows), sums, cov, eigenvalues, normals, n_rows);
   return launch_status("rdm_voxel_map_extract_moments");
+}
+
+// ---- voxel observations -------------------------------------------------------------------------------------------------------
+
+extern "C" size_t rdm_voxel_observations_bytes(int64_t capacity) {
+  using namespace rdm;
+  if (!shape_ok(capacity, 3)) return 0;
+  Arena ar(nullptr, 0);
+  Observations o;
+  carve_observations(ar, capacity, o);
+  return ar.off;
+}
+
+extern "C" int rdm_voxel_observations_reset(void* observations, size_t observations_bytes, int64_t capacity, void* stream) {
+  using namespace rdm;
+  RDM_REQUIRE(shape_ok(capacity, 3), "rdm_voxel_observations_reset: capacity must be a power of two in [64, 2^30], got %lld",
+              static_cast<long long>(capacity));
+  Observations o;
+  if (const int rc = open_observations("rdm_voxel_observations_reset", observations, observations_bytes, capacity, o)) return rc;
+  hipLaunchKernelGGL(observations_reset_kernel, dim3(blocks_for(capacity)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), o,
+                     static_cast<long long>(capacity), true);
+  return launch_status("rdm_voxel_observations_reset");
+}
+
+extern "C" int rdm_voxel_map_integrate_observed(void* map, size_t map_bytes, int64_t capacity, int channels, double voxel,
+                                                const float* points, int64_t ld, int64_t total, const int64_t* offsets,
+                                                const double* poses, int64_t n_scans, double min_range, double max_range, void* moments,
+                                                size_t moments_bytes, void* observations, size_t observations_bytes, int64_t first_id,
+                                                void* stream) {
+  return rdm::integrate("rdm_voxel_map_integrate_observed", map, map_bytes, capacity, channels, voxel, points, ld, total, offsets, poses,
+                        n_scans, min_range, max_range, moments != nullptr, moments, moments_bytes, true, observations, observations_bytes,
+                        first_id, stream);
+}
+
+extern "C" int rdm_voxel_observations_rehash(const void* old_map, size_t old_bytes, int64_t old_capacity, const void* old_observations,
+                                             size_t old_observations_bytes, const void* new_map, size_t new_bytes, int64_t new_capacity,
+                                             void* new_observations, size_t new_observations_bytes, int channels, void* stream) {
+  using namespace rdm;
+  const char* what = "rdm_voxel_observations_rehash";
+  Table a, b;
+  Observations oa, ob;
+  if (const int rc = open_table("rdm_voxel_observations_rehash (old)", const_cast<void*>(old_map), old_bytes, old_capacity, channels, a)) return rc;
+  if (const int rc = open_table("rdm_voxel_observations_rehash (new)", const_cast<void*>(new_map), new_bytes, new_capacity, channels, b)) return rc;
+  if (const int rc = open_observations("rdm_voxel_observations_rehash (old)", old_observations, old_observations_bytes, old_capacity, oa)) return rc;
+  if (const int rc = open_observations("rdm_voxel_observations_rehash (new)", new_observations, new_observations_bytes, new_capacity, ob)) return rc;
+  RDM_REQUIRE(new_capacity >= old_capacity && new_map != old_map && new_observations != old_observations,
+              "%s: the new map and observations must be other blocks of at least the old capacity", what);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(observations_reset_kernel, dim3(blocks_for(new_capacity)), dim3(kBlock), 0, s, ob, static_cast<long long>(new_capacity), true);
+  hipLaunchKernelGGL(observations_rehash_kernel, dim3(blocks_for(old_capacity)), dim3(kBlock), 0, s, a, oa, static_cast<long long>(old_capacity),
+                     b, ob, static_cast<long long>(new_capacity));
+  return launch_status(what);
+}
+
+extern "C" int rdm_voxel_map_extract_observations(const void* map, size_t map_bytes, int64_t capacity, int channels, const void* observations,
+                                                  size_t observations_bytes, double voxel, int64_t min_points, int32_t* scans,
+                                                  int32_t* first, int32_t* last, int64_t max_rows, int64_t* n_rows, void* ws,
+                                                  size_t ws_bytes, void* stream) {
+  using namespace rdm;
+  const char* what = "rdm_voxel_map_extract_observations";
+  Table t;
+  Observations o;
+  if (const int rc = open_table(what, const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
+  if (const int rc = open_observations(what, observations, observations_bytes, capacity, o)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ExtractWork w;
+  if (const int rc = select_sorted(what, t, capacity, voxel, min_points, max_rows, n_rows, max_rows == 0 || (scans && first && last), ws,
+                                   ws_bytes, s, w))
+    return rc;
+  hipLaunchKernelGGL(emit_observations_kernel, dim3(blocks_for(max_rows)), dim3(kBlock), 0, s, o, w.slots, w.n_sel,
+                     static_cast<long long>(max_rows), scans, first, last, n_rows);
+  return launch_status(what);
+}
+
+extern "C" int rdm_voxel_map_prune(const void* old_map, size_t old_bytes, int64_t old_capacity, const void* old_observations,
+                                   size_t old_observations_bytes, void* new_map, size_t new_bytes, int64_t new_capacity, int channels,
+                                   int64_t min_points, int64_t min_scans, void* stream) {
+  using namespace rdm;
+  const char* what = "rdm_voxel_map_prune";
+  Table a, b;
+  Observations oa;
+  if (const int rc = open_table("rdm_voxel_map_prune (old)", const_cast<void*>(old_map), old_bytes, old_capacity, channels, a)) return rc;
+  if (const int rc = open_table("rdm_voxel_map_prune (new)", new_map, new_bytes, new_capacity, channels, b)) return rc;
+  if (const int rc = open_observations(what, old_observations, old_observations_bytes, old_capacity, oa)) return rc;
+  RDM_REQUIRE(new_capacity >= old_capacity && new_map != old_map, "%s: the new map must be another block of at least the old capacity", what);
+  RDM_REQUIRE(min_points >= 0 && min_scans >= 0, "%s: min_points and min_scans must be >= 0", what);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(reset_kernel, dim3(blocks_for(new_capacity)), dim3(kBlock), 0, s, b, static_cast<long long>(new_capacity), channels);
+  hipLaunchKernelGGL(rehash_kernel<true>, dim3(blocks_for(old_capacity)), dim3(kBlock), 0, s, a, static_cast<long long>(old_capacity), b,
+                     static_cast<long long>(new_capacity), channels, oa, least_points(min_points),
+                     static_cast<int>(min_scans > kMaxScanId ? kMaxScanId : min_scans));
+  return launch_status(what);
 }
 
 // ---- voxel map registration ---------------------------------------------------------------------------------------------------

@@ -796,9 +796,13 @@ class VoxelMap:
     map depends on the set of integrated points only: the order of the scans, the batching and the run do not change one bit
     of what `extract` returns.  moments=True keeps nine more int64 sums per voxel in a second block (rdm_voxel_moments_*: the first
     and second moments of the 12-bit local coordinates), which give every voxel a mean, a covariance and a normal --
-    `extract_moments` -- and the map a sharpness report -- `sharpness`; `extract` and `stats` are the same bytes either way."""
+    `extract_moments` -- and the map a sharpness report -- `sharpness`; `extract` and `stats` are the same bytes either way.
+    observations=True keeps, in a third block (rdm_voxel_observations_*), in how many distinct scans every voxel was seen and the first and
+    the last of them -- `extract_observations` -- and gives the map without the voxels seen in too few scans -- `pruned`: a moving
+    object is in a voxel in one scan, a wall in many.  The scans are numbered from 0 as `integrate` is given them, empty ones included
+    (`num_scans`: the next id), so a scan must come whole in one `integrate` call.  Again `extract` and `stats` are the same bytes."""
 
-    def __init__(self, voxel, channels=4, capacity=1 << 20, device='cuda', moments=False):
+    def __init__(self, voxel, channels=4, capacity=1 << 20, device='cuda', moments=False, observations=False):
         voxel, channels, capacity = float(voxel), int(channels), int(capacity)
         if not (voxel > 0 and voxel < float('inf')):
             raise ValueError(f'voxel must be positive and finite, got {voxel}')
@@ -812,9 +816,10 @@ class VoxelMap:
             raise ValueError(f'VoxelMap needs a CUDA device, got {self.device}')
         if self.device.index is None:
             self.device = torch.device('cuda', torch.cuda.current_device())
-        self.moments = bool(moments)
+        self.moments, self.observations = bool(moments), bool(observations)
         self.capacity, self._buf = capacity, self._alloc(capacity)
         self._mom = self._alloc_moments(capacity) if self.moments else None
+        self._obs = self._alloc_observations(capacity) if self.observations else None
         self.reset()
 
     def _alloc(self, capacity):
@@ -822,6 +827,9 @@ class VoxelMap:
 
     def _alloc_moments(self, capacity):
         return torch.empty((_lib.lib().rdm_voxel_moments_bytes(capacity),), dtype=torch.uint8, device=self.device)
+
+    def _alloc_observations(self, capacity):
+        return torch.empty((_lib.lib().rdm_voxel_observations_bytes(capacity),), dtype=torch.uint8, device=self.device)
 
     def _head(self):
         return self._buf.data_ptr(), self._buf.numel(), self.capacity, self.channels
@@ -832,6 +840,10 @@ class VoxelMap:
             if self.moments:
                 _lib.check(_lib.lib().rdm_voxel_moments_reset(self._mom.data_ptr(), self._mom.numel(), self.capacity, _lib.stream_ptr()),
                            'rdm_voxel_moments_reset')
+            if self.observations:
+                _lib.check(_lib.lib().rdm_voxel_observations_reset(self._obs.data_ptr(), self._obs.numel(), self.capacity, _lib.stream_ptr()),
+                           'rdm_voxel_observations_reset')
+        self.num_scans = 0  # with observations: the id of the next scan
         self._bound = 0  # occupied <= _bound: spares the read-back of `occupied` while the table is certainly large enough
 
     def stats(self):
@@ -868,6 +880,13 @@ class VoxelMap:
                                                                        capacity, mom.data_ptr(), mom.numel(), self.channels,
                                                                        _lib.stream_ptr()), 'rdm_voxel_moments_rehash')
                         self._mom = mom
+                    if self.observations:
+                        obs = self._alloc_observations(capacity)
+                        _lib.check(_lib.lib().rdm_voxel_observations_rehash(self._buf.data_ptr(), self._buf.numel(), self.capacity,
+                                                                            self._obs.data_ptr(), self._obs.numel(), new.data_ptr(),
+                                                                            new.numel(), capacity, obs.data_ptr(), obs.numel(),
+                                                                            self.channels, _lib.stream_ptr()), 'rdm_voxel_observations_rehash')
+                        self._obs = obs
                 self.capacity, self._buf = capacity, new  # (the old block is freed in stream order by the caching allocator)
         self._bound += n_points
 
@@ -931,12 +950,26 @@ class VoxelMap:
         """clouds: a list of float32 CUDA tensors [N_i, >= C] (empty ones allowed), or a pair (points float32 CUDA [N, ld >= C],
         offsets int64 [n + 1], host or device: scan i is rows offsets[i] .. offsets[i + 1]).  poses: [n, 4, 4] finite, anything
         numpy or torch holds (world = pose @ point).  A point is integrated iff its C values are finite and min_range <= its range
-        in the sensor frame <= max_range.  -> self.  The list form concatenates the clouds' first C columns on the device."""
+        in the sensor frame <= max_range.  -> self.  The list form concatenates the clouds' first C columns on the device.  With
+        observations the scans get the ids num_scans, num_scans + 1, ... (an empty scan consumes one) and a longer batch goes in calls
+        of 64 scans, which read the same device arrays."""
         points, offsets, n, X, lo, hi = self._packed('integrate', clouds, poses, min_range, max_range)
         if n == 0 or points is None or points.shape[0] == 0:
+            self.num_scans += n if self.observations else 0
             return self
         points, ld, total, offsets, X = self._on_device(points, offsets, X)
         self._reserve(total)
+        if self.observations:
+            block = (self._mom.data_ptr(), self._mom.numel()) if self.moments else (0, 0)
+            with torch.cuda.device(self.device):
+                for lo_scan in range(0, n, _lib.VOXEL_OBSERVATIONS_MAX_SCANS):
+                    scans = min(n - lo_scan, _lib.VOXEL_OBSERVATIONS_MAX_SCANS)
+                    _lib.check(_lib.lib().rdm_voxel_map_integrate_observed(
+                        *self._head(), self.voxel, points.data_ptr(), ld, total, offsets.data_ptr() + 8 * lo_scan, X.data_ptr() + 128 * lo_scan,
+                        scans, lo, hi, *block, self._obs.data_ptr(), self._obs.numel(), self.num_scans + lo_scan, _lib.stream_ptr()),
+                        'rdm_voxel_map_integrate_observed')
+            self.num_scans += n
+            return self
         name = 'rdm_voxel_map_integrate' + ('_moments' if self.moments else '')
         block = (self._mom.data_ptr(), self._mom.numel()) if self.moments else ()
         with torch.cuda.device(self.device):
@@ -970,6 +1003,40 @@ class VoxelMap:
                                         n_rows.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), name)
         m = int(n_rows.item())
         return tuple(t[:m] for t in outs)
+
+    def _need_observations(self, what):
+        if not self.observations:
+            raise ValueError(f'VoxelMap.{what} needs a map created with observations=True')
+
+    def extract_observations(self, min_points=1):
+        """-> (scans, first, last), int32 [M] each on the device, row-aligned with extract(min_points): in how many distinct scans the
+        voxel was seen, and the smallest and the largest of their ids.  Two read-backs (sizes)."""
+        self._need_observations('extract_observations')
+        return tuple(t.view(-1) for t in self._extract('rdm_voxel_map_extract_observations', min_points, ((torch.int32, (1, 1, 1)),),
+                                                       self._obs.data_ptr(), self._obs.numel()))
+
+    def pruned(self, min_scans, min_points=1):
+        """-> a new VoxelMap of the same capacity and options that holds only the voxels with at least min_points points seen in at
+        least min_scans scans (rdm_voxel_map_prune), with their moments and observations where this map has them: `extract`,
+        `extract_moments`, `sharpness` and `register` work on it as on any map.  Its `occupied` and `integrated` count what was kept; the
+        other counters and num_scans are this map's.  This map is only read.  No read-back."""
+        self._need_observations('pruned')
+        min_scans, min_points = int(min_scans), int(min_points)
+        if min_scans < 0 or min_points < 0:
+            raise ValueError(f'min_scans and min_points must be >= 0, got {min_scans} and {min_points}')
+        L = _lib.lib()
+        out = VoxelMap(self.voxel, self.channels, self.capacity, self.device, self.moments, True)
+        old, new = (self._buf.data_ptr(), self._buf.numel(), self.capacity), (out._buf.data_ptr(), out._buf.numel(), out.capacity)
+        with torch.cuda.device(self.device):
+            _lib.check(L.rdm_voxel_map_prune(*old, self._obs.data_ptr(), self._obs.numel(), *new, self.channels, min_points, min_scans,
+                                             _lib.stream_ptr()), 'rdm_voxel_map_prune')
+            if self.moments:
+                _lib.check(L.rdm_voxel_moments_rehash(*old, self._mom.data_ptr(), self._mom.numel(), *new, out._mom.data_ptr(),
+                                                      out._mom.numel(), self.channels, _lib.stream_ptr()), 'rdm_voxel_moments_rehash')
+            _lib.check(L.rdm_voxel_observations_rehash(*old, self._obs.data_ptr(), self._obs.numel(), *new, out._obs.data_ptr(),
+                                                       out._obs.numel(), self.channels, _lib.stream_ptr()), 'rdm_voxel_observations_rehash')
+        out.num_scans, out._bound = self.num_scans, self._bound
+        return out
 
     def _need_moments(self, what):
         if not self.moments:

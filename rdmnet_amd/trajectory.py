@@ -4,7 +4,9 @@
                                   [--preconditioner {block_jacobi,chain}] [--linear-solver {pcg,direct}]
                                   [--map-scans DATASET_ROOT [--map-raw] [--map-voxel 0.3] [--map-min-points 1]
                                    [--map-range LO HI] [--map-batch 64] [--map-sharpness [--map-sharpness-min-points 4]]
-                                   [--map-refine [--map-refine-sigma 0.02] [--map-refine-neighbors {1,7}] [--map-refine-iterations 30]]]
+                                   [--map-min-scans 1]
+                                   [--map-refine [--map-refine-sigma 0.02] [--map-refine-neighbors {1,7}] [--map-refine-iterations 30]
+                                    [--map-refine-min-scans 1]]]
 
 reads the `{seq}_{src}_{ref}.npz` pair files that `python -m rdmnet_amd.infer` wrote into DIR (ordered and filtered as
 `python -m rdmnet_amd.eval` reads them) and, per sequence, chains the pair poses into a trajectory as
@@ -25,7 +27,11 @@ plane thickness (root of the mean smallest covariance eigenvalue) and the mean m
 --map-sharpness-min-points points; lower is sharper for both.  With --map-refine the per-voxel Gaussians are also used to improve
 the poses: every frame is registered against the map of the frames before it (`ops.VoxelMap.register`: point-to-distribution, the
 NDT / voxelised-GICP family) and then fused into that map -- `refine_against_map` -- from the optimised poses with --optimize, else
-the chained ones; the result is a third variant, `refined`, with its own error, pose file, map and sharpness lines."""
+the chained ones; the result is a third variant, `refined`, with its own error, pose file, map and sharpness lines.  With --map-min-scans N > 1 the map
+also keeps in how many scans every voxel was seen (`ops.VoxelMap(observations=True)`) and every variant's map is pruned to the voxels
+seen in at least N scans before anything is written or reported -- a moving object is in a voxel in one scan, static structure in
+many --; a `persistent:` line after every `map:` line says what was kept.  --map-refine-min-scans N registers frame k >= N against
+that pruned map instead of the full one."""
 import argparse
 import math
 import os
@@ -171,16 +177,17 @@ def write_kitti_poses(path, poses):
 
 # ---- the map of a run ------------------------------------------------------------------------------------------------------
 
-MAP_DEFAULTS = dict(voxel=0.3, min_points=1, batch=64, sharpness_min_points=4)
-REFINE_DEFAULTS = dict(sigma=0.02, neighbors=1, iterations=30, min_points=4)
+MAP_DEFAULTS = dict(voxel=0.3, min_points=1, batch=64, sharpness_min_points=4, min_scans=1)
+REFINE_DEFAULTS = dict(sigma=0.02, neighbors=1, iterations=30, min_points=4, min_scans=1)
 
 
 def build_map(paths, poses, voxel=MAP_DEFAULTS['voxel'], channels=None, min_range=0.0, max_range=math.inf, batch=MAP_DEFAULTS['batch'],
-              capacity=1 << 20, device='cuda', moments=False):
+              capacity=1 << 20, device='cuda', moments=False, observations=False):
     """The scans `paths` (.npy float32 [N, C] or KITTI .bin [N, 4], read by prepare.load_scan) under `poses` ([n, 4, 4], world =
     pose @ point) fused into an ops.VoxelMap.  channels None: the columns of the first scan (at most 8).  `batch` scans are read on
     a background thread while the previous batch is on the GPU; a batch is one host-to-device copy and one integrate call.
-    moments: keep the per-voxel second moments too (ops.VoxelMap(moments=True): extract_moments, sharpness).  A missing file is a TrajectoryError that names it (checked before anything is read)."""
+    moments: keep the per-voxel second moments too (ops.VoxelMap(moments=True): extract_moments, sharpness); observations: and in how
+    many scans every voxel was seen (ops.VoxelMap(observations=True): extract_observations, pruned; scan k has the id k).  A missing file is a TrajectoryError that names it (checked before anything is read)."""
     paths = list(paths)
     poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
     if len(paths) != len(poses):
@@ -206,13 +213,15 @@ def build_map(paths, poses, voxel=MAP_DEFAULTS['voxel'], channels=None, min_rang
     for group, (points, offsets) in prepare._read_ahead(load, groups):
         if vmap is None:
             width = points.shape[1] if channels is None else int(channels)
-            vmap = ops.VoxelMap(voxel, channels=min(width, 8), capacity=capacity, device=device, moments=moments)
+            vmap = ops.VoxelMap(voxel, channels=min(width, 8), capacity=capacity, device=device, moments=moments,
+                                observations=observations)
         if points.shape[1] < vmap.channels:
             raise TrajectoryError(f'{paths[group[0]]}: {points.shape[1]} columns, the map has {vmap.channels} channels')
         vmap.integrate((torch.from_numpy(points).to(vmap.device), torch.from_numpy(offsets)), poses[group[0]:group[1]], min_range,
                        max_range)
     if vmap is None:
-        vmap = ops.VoxelMap(voxel, channels=4 if channels is None else int(channels), capacity=capacity, device=device, moments=moments)
+        vmap = ops.VoxelMap(voxel, channels=4 if channels is None else int(channels), capacity=capacity, device=device, moments=moments,
+                            observations=observations)
     return vmap
 
 
@@ -227,19 +236,32 @@ def sharpness_line(seq, what, min_points, report):
             f"{report['plane_thickness'] * 1e3:.3f} mm, entropy {report['entropy']:.4f} ({report['degenerate']} degenerate)")
 
 
+def persistent_line(seq, what, min_scans, kept, full, scans):
+    """kept / full: the stats of the pruned and of the full map."""
+    return (f"seq {seq} {what} persistent: {kept['occupied']} of {full['occupied']} voxels seen in >= {min_scans} scans, "
+            f"{kept['integrated']} of {full['integrated']} points, {scans} scans")
+
+
 def refine_against_map(paths, poses, voxel=MAP_DEFAULTS['voxel'], channels=None, min_range=0.0, max_range=math.inf,
                        sigma=REFINE_DEFAULTS['sigma'], neighbors=REFINE_DEFAULTS['neighbors'], max_iteration=REFINE_DEFAULTS['iterations'],
-                       min_points=REFINE_DEFAULTS['min_points'], capacity=1 << 20, device='cuda'):
+                       min_points=REFINE_DEFAULTS['min_points'], capacity=1 << 20, device='cuda', min_scans=REFINE_DEFAULTS['min_scans'],
+                       observations=False):
     """Sequential scan-to-map refinement of the trajectory `poses` ([n, 4, 4]) of the scans `paths` (as build_map reads them): frame
     0 keeps its pose and is integrated into a map with moments; every later frame k starts from refined[k - 1] inv(poses[k - 1])
     poses[k] -- the previous frame's correction carried forward --, is registered against the map so far (ops.VoxelMap.register)
     and integrated under the result.  A degenerate frame (status 2: no correspondence, or a singular system) keeps its initial
-    pose.  The scans are read on a background thread, one ahead.  -> (refined float64 [n, 4, 4], the ops.VoxelMap of all frames
+    pose.  min_scans N > 1: frame k >= N is registered against vmap.pruned(N), the voxels seen in at least N of the frames before it
+    (earlier frames against the full map); every frame is still integrated into the full map, which then keeps observations, as it does
+    with observations=True.  The scans are read on a background thread, one ahead.  -> (refined float64 [n, 4, 4], the ops.VoxelMap of all frames
     under the refined poses, dict(frames, iterations [n], correspondences [n], status [n], degenerate)); frame 0 has status -1."""
     paths = list(paths)
     poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
     if len(paths) != len(poses):
         raise ValueError(f'refine_against_map: {len(paths)} scans and {len(poses)} poses')
+    min_scans = int(min_scans)
+    if min_scans < 1:
+        raise ValueError(f'refine_against_map: min_scans must be >= 1, got {min_scans}')
+    kind = dict(moments=True, observations=bool(observations) or min_scans > 1)
     for path in paths:
         if not osp.isfile(path):
             raise TrajectoryError(f'{path}: no such scan file')
@@ -254,19 +276,20 @@ def refine_against_map(paths, poses, voxel=MAP_DEFAULTS['voxel'], channels=None,
             raise TrajectoryError(f'{paths[k]}: shape {cloud.shape}, expected [N, >= 3]')
         if vmap is None:
             width = cloud.shape[1] if channels is None else int(channels)
-            vmap = ops.VoxelMap(voxel, channels=min(width, 8), capacity=capacity, device=device, moments=True)
+            vmap = ops.VoxelMap(voxel, channels=min(width, 8), capacity=capacity, device=device, **kind)
         if cloud.shape[1] < vmap.channels:
             raise TrajectoryError(f'{paths[k]}: {cloud.shape[1]} columns, the map has {vmap.channels} channels')
         points = torch.from_numpy(np.ascontiguousarray(cloud)).to(vmap.device)
         if k > 0:
             init = refined[k - 1] @ np.linalg.inv(poses[k - 1]) @ poses[k]
-            res = vmap.register([points], init[None], sigma=sigma, min_points=min_points, neighbors=neighbors, max_iteration=max_iteration,
+            target = vmap.pruned(min_scans) if min_scans > 1 and k >= min_scans else vmap
+            res = target.register([points], init[None], sigma=sigma, min_points=min_points, neighbors=neighbors, max_iteration=max_iteration,
                                 min_range=min_range, max_range=max_range)
             iterations[k], corr[k], status[k] = torch.stack([res.iterations, res.num_correspondences, res.status]).cpu().numpy()[:, 0]
             refined[k] = init if status[k] == 2 else res.transformations[0].cpu().numpy()
         vmap.integrate([points], refined[k][None], min_range, max_range)
     if vmap is None:
-        vmap = ops.VoxelMap(voxel, channels=4 if channels is None else int(channels), capacity=capacity, device=device, moments=True)
+        vmap = ops.VoxelMap(voxel, channels=4 if channels is None else int(channels), capacity=capacity, device=device, **kind)
     return refined, vmap, dict(frames=n, iterations=iterations, correspondences=corr, status=status, degenerate=int((status == 2).sum()))
 
 
@@ -280,12 +303,19 @@ def write_map(args, seq, what, paths, poses, emit, vmap=None):
     """vmap: the map of these scans under these poses when the caller has built it already (the refinement's)."""
     lo, hi = args.map_range if args.map_range else (0.0, math.inf)
     sharpness = bool(getattr(args, 'map_sharpness', False))
+    min_scans = getattr(args, 'map_min_scans', None) or MAP_DEFAULTS['min_scans']
     if vmap is None:
-        vmap = build_map(paths, poses, voxel=args.map_voxel, min_range=lo, max_range=hi, batch=args.map_batch, moments=sharpness)
+        vmap = build_map(paths, poses, voxel=args.map_voxel, min_range=lo, max_range=hi, batch=args.map_batch, moments=sharpness,
+                         observations=min_scans > 1)
+    if min_scans > 1:  # everything below describes the pruned map
+        full, scans = vmap.stats(), vmap.num_scans
+        vmap = vmap.pruned(min_scans)
     points, counts, _ = vmap.extract(args.map_min_points)
     points, counts = points.cpu().numpy(), counts.cpu().numpy()
     np.save(osp.join(args.out, f'{seq}_{what}_map.npy'), np.concatenate([points, counts[:, None].astype(np.float32)], 1))
     emit(map_line(seq, what, args.map_voxel, len(counts), int(counts.sum(dtype=np.int64)), vmap.stats()))
+    if min_scans > 1:
+        emit(persistent_line(seq, what, min_scans, vmap.stats(), full, scans))
     if sharpness:
         emit(sharpness_line(seq, what, args.map_sharpness_min_points, vmap.sharpness(args.map_sharpness_min_points)))
 
@@ -296,12 +326,17 @@ def map_paths(args, seqs):
     if refine and not (getattr(args, 'map_scans', None) and args.out):
         raise TrajectoryError('--map-refine needs --map-scans and --out (the frames are registered against the map of the scans)')
     if not refine:
-        for flag, key in (('--map-refine-sigma', 'sigma'), ('--map-refine-neighbors', 'neighbors'), ('--map-refine-iterations', 'iterations')):
+        for flag, key in (('--map-refine-sigma', 'sigma'), ('--map-refine-neighbors', 'neighbors'), ('--map-refine-iterations', 'iterations'),
+                          ('--map-refine-min-scans', 'min_scans')):
             if getattr(args, 'map_refine_' + key, None) not in (None, REFINE_DEFAULTS[key]):
                 raise TrajectoryError(f'{flag} needs --map-refine')
     elif not (args.map_refine_sigma > 0 and math.isfinite(args.map_refine_sigma)) or args.map_refine_iterations < 0:
         raise TrajectoryError('--map-refine-sigma must be > 0 and --map-refine-iterations >= 0')
+    elif getattr(args, 'map_refine_min_scans', REFINE_DEFAULTS['min_scans']) < 1:
+        raise TrajectoryError(f'--map-refine-min-scans must be >= 1, got {args.map_refine_min_scans}')
     if not getattr(args, 'map_scans', None):
+        if getattr(args, 'map_min_scans', None) not in (None, MAP_DEFAULTS['min_scans']):
+            raise TrajectoryError('--map-min-scans needs --map-scans (the voxels are counted over the scans of the map)')
         if getattr(args, 'map_sharpness', False):
             raise TrajectoryError('--map-sharpness needs --map-scans (the report is taken over the map of the scans)')
         if getattr(args, 'map_sharpness_min_points', None) not in (None, MAP_DEFAULTS['sharpness_min_points']):
@@ -309,6 +344,8 @@ def map_paths(args, seqs):
         return None
     if getattr(args, 'map_sharpness', False) and args.map_sharpness_min_points < 2:
         raise TrajectoryError(f'--map-sharpness-min-points must be >= 2 (a covariance needs two points), got {args.map_sharpness_min_points}')
+    if getattr(args, 'map_min_scans', MAP_DEFAULTS['min_scans']) < 1:
+        raise TrajectoryError(f'--map-min-scans must be >= 1, got {args.map_min_scans}')
     if not args.out:
         raise TrajectoryError('--map-scans needs --out (the directory the maps are written to)')
     if not (args.map_voxel > 0 and math.isfinite(args.map_voxel)) or args.map_min_points < 1 or args.map_batch < 1:
@@ -349,7 +386,9 @@ def run(args, emit=print):
         lo, hi = args.map_range if args.map_range else (0.0, math.inf)
         refined, vmap, stats = refine_against_map(scans[seq], base, voxel=args.map_voxel, min_range=lo, max_range=hi,
                                                   sigma=args.map_refine_sigma, neighbors=args.map_refine_neighbors,
-                                                  max_iteration=args.map_refine_iterations)
+                                                  max_iteration=args.map_refine_iterations,
+                                                  min_scans=getattr(args, 'map_refine_min_scans', None) or REFINE_DEFAULTS['min_scans'],
+                                                  observations=(getattr(args, 'map_min_scans', None) or 1) > 1)
         if seq in gts:
             emit(report_line(seq, 'refined', absolute_trajectory_error(refined[1:], gts[seq])))
         emit(refine_line(seq, stats))
@@ -418,6 +457,9 @@ def make_parser():
                          'entropy of that map (needs --map-scans); lower is sharper')
     ap.add_argument('--map-sharpness-min-points', type=int, default=MAP_DEFAULTS['sharpness_min_points'], metavar='N',
                     help='take the sharpness report over the voxels with at least N >= 2 points')
+    ap.add_argument('--map-min-scans', type=int, default=MAP_DEFAULTS['min_scans'], metavar='N',
+                    help='keep only the voxels seen in at least N scans in every map that is written or reported (needs --map-scans): '
+                         'removes what was in a voxel in fewer scans, such as a moving object; a `persistent:` line says what was kept')
     ap.add_argument('--map-refine', action='store_true',
                     help='register every frame against the voxel map of the frames before it and fuse it under the result: a third '
                          'variant, `refined`, from the optimised poses with --optimize, else the chained (needs --map-scans and --out)')
@@ -427,6 +469,8 @@ def make_parser():
                     help="a point is matched to its own voxel (1) or to it and its six face neighbours (7: a wider basin)")
     ap.add_argument('--map-refine-iterations', type=int, default=REFINE_DEFAULTS['iterations'], metavar='N',
                     help='at most N Gauss-Newton updates per frame')
+    ap.add_argument('--map-refine-min-scans', type=int, default=REFINE_DEFAULTS['min_scans'], metavar='N',
+                    help='register frame k >= N against the voxels seen in at least N of the frames before it (needs --map-refine)')
     return ap
 
 

@@ -1,7 +1,7 @@
 """Times the voxel map (ops.VoxelMap) on synthetic scans along a synthetic drive.
 
   python tools/map_bench.py [--frames 256] [--points 120000 | 18000] [--reps 3] [--batch 64] [--voxel 0.3] [--cpu] [--cpu-frames 8]
-                              [--moments] [--register] [--digest]
+                              [--moments] [--observations] [--register] [--digest]
 With --digest (and nothing else): no timing, one sha1 line per output of the voxel map on the bundled scans (see digest()), for
 comparing the bits of two builds of the library.  Otherwise prints one JSON line per case:
   * integrate: --frames scans of --points points (120 000: a raw scan; 18 000: a down-sampled one), xyz + intensity, integrated in
@@ -15,6 +15,11 @@ comparing the bits of two builds of the library.  Otherwise prints one JSON line
   * with --moments: the same integrate into a map with the nine second-moment sums beside it (ops.VoxelMap(moments=True): 14 integer
     atomic adds a point instead of 5, (8 C + 4 + 72) B), its points/s and the ratio to the plain integrate of the same run, and
     the ms of extract_moments (select, sort, covariance and the Jacobi eigen-solver per voxel);
+  * with --observations: the same integrate into a map with the observations block beside it (ops.VoxelMap(observations=True): per
+    point one load of the slot's mask more and, on a voxel's first sighting of a scan, four integer atomics), its points/s and the
+    ratio to the plain integrate of the same run; the ms of extract_observations and of one pruned(2); and what --map-refine-min-scans 2
+    adds to a frame of the refinement: one scan registered against a map with moments and observations of min(--frames, 64) scans
+    at the command line's capacity, and against its pruned(2), the prune included;
   * with --register (and nothing else of the above): the scan-to-map registration (ops.VoxelMap.register) at neighbors 1 and 7 for both
     scan shapes (120 000 and 18 000 points), against the map with moments of min(--frames, 64) scans, from poses 5 cm / 5 mrad off: ms
     per evaluation (max_iteration = 0, one scan), ms per full registration of one scan and of a batch of 64 scans (default
@@ -185,6 +190,8 @@ def main(argv=None):
     ap.add_argument('--batch', type=int, default=64, help='scans per integrate call')
     ap.add_argument('--voxel', type=float, default=0.3)
     ap.add_argument('--moments', action='store_true', help='also time integrate and extract with the per-voxel second moments')
+    ap.add_argument('--observations', action='store_true',
+                    help='also time integrate with the per-voxel scan observations, extract_observations, pruned and a refinement frame')
     ap.add_argument('--register', action='store_true', help='time the scan-to-map registration and nothing else')
     ap.add_argument('--digest', action='store_true', help='print the sha1 lines of the bundled scans\' maps and registrations and nothing else')
     ap.add_argument('--cpu', action='store_true', help='also time the NumPy restatement and compare the maps bit for bit')
@@ -253,6 +260,42 @@ def main(argv=None):
         print(json.dumps({'case': 'extract_moments', 'capacity': capacity, 'voxels': int(out_m[0].shape[0]), 'ms': round(ms_xm, 3),
                           'voxels_per_s': round(out_m[0].shape[0] / ms_xm * 1e3), 'sharpness': mmap.sharpness()}))
         del mmap, out_m
+
+    if a.observations:
+        omap = ops.VoxelMap(a.voxel, channels=C, capacity=capacity, observations=True)
+
+        def integrate_observed():
+            omap.reset()
+            for pts, off, X in batches:
+                omap.integrate((pts, off), X)
+            return omap
+
+        ms_oreset, _ = timed(omap.reset, a.reps)
+        ms_oall, _ = timed(integrate_observed, a.reps)
+        ms_o = ms_oall - ms_oreset
+        assert omap.capacity == capacity and omap.stats() == st and omap.num_scans == a.frames
+        pps_o = total / ms_o * 1e3
+        print(json.dumps({'case': 'integrate with observations', 'ms': round(ms_o, 3), 'ms_reset_excluded': round(ms_oreset, 3),
+                          'calls': sum(-(-(len(off) - 1) // _lib.VOXEL_OBSERVATIONS_MAX_SCANS) for _, off, _ in batches),
+                          'points_per_s': round(pps_o), 'over_plain_integrate': round(pps_o / pps, 3)}))
+        ms_xo, out_o = timed(lambda: omap.extract_observations(), a.reps)
+        seen = torch.bincount(out_o[0].long()).cpu().tolist()
+        print(json.dumps({'case': 'extract_observations', 'capacity': capacity, 'voxels': int(out_o[0].shape[0]), 'ms': round(ms_xo, 3),
+                          'voxels_per_s': round(out_o[0].shape[0] / ms_xo * 1e3), 'voxels_seen_once': seen[1] if len(seen) > 1 else 0}))
+        ms_p, kept = timed(lambda: omap.pruned(2), a.reps)
+        print(json.dumps({'case': 'pruned', 'min_scans': 2, 'capacity': capacity, 'voxels': st['occupied'], 'kept': len(kept), 'ms': round(ms_p, 3)}))
+        del omap, out_o, kept
+        m = max(min(a.frames, 64), 1)
+        rmap = ops.VoxelMap(a.voxel, channels=C, moments=True, observations=True)  # (the command line's capacity)
+        rmap.integrate([cloud[k * a.points:(k + 1) * a.points] for k in range(m)], poses[:m])
+        scan, X0 = [cloud[:a.points]], off_poses(poses[:1], np.random.default_rng(0))
+        ms_full, r_full = timed(lambda: rmap.register(scan, X0), a.reps)
+        ms_pruned, r_pruned = timed(lambda: rmap.pruned(2).register(scan, X0), a.reps)
+        print(json.dumps({'case': 'refine frame', 'map_frames': m, 'capacity': rmap.capacity, 'ms_register_full_map': round(ms_full, 3),
+                          'ms_prune_and_register': round(ms_pruned, 3), 'ms_added_by_min_scans_2': round(ms_pruned - ms_full, 3),
+                          'iterations': [int(r_full.iterations[0]), int(r_pruned.iterations[0])],
+                          'correspondences': [int(r_full.num_correspondences[0]), int(r_pruned.num_correspondences[0])]}))
+        del rmap
 
     host = cloud[:min(a.batch, a.frames) * a.points].cpu().numpy()
     pinned = torch.from_numpy(host).pin_memory()
