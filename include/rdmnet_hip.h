@@ -1263,6 +1263,47 @@ int rdm_voxel_map_prune(const void* old_map, size_t old_bytes, int64_t old_capac
                         size_t old_observations_bytes, void* new_map, size_t new_bytes, int64_t new_capacity, int channels,
                         int64_t min_points, int64_t min_scans, void* stream);
 
+/* ---- §7 voxel map queries: what the map says about every point of a scan (voxel_map.hip) ---------------------------------------
+ * Not in the reference tree -> parity unpinned; the project's own definition, pinned to the NumPy restatement
+ * tests/voxel_query_restatement.py.  The map, the moments block and the observations block are only read.  points / ld / total /
+ * offsets / poses / n_scans / min_range / max_range are those of rdm_voxel_map_register, without its limit on n_scans.  Parameters:
+ * sigma > 0, min_points >= 1, neighbors 1 or 7, min_scans >= 0, max_d2 >= 0 (+inf allowed, NaN is RDM_ERR_ARG).  `moments` may be null:
+ * every voxel's covariance is then zero, Sigma = sigma^2 I and d2 = |r|^2 / sigma^2.  `observations` may be null: then min_scans > 1 or
+ * a non-null `seen` is RDM_ERR_ARG.  Per row i of scan s at the pose X, everything in float64 without contraction:
+ *   gate      as rdm_voxel_map_integrate does: the labels RDM_VOXEL_POINT_NONFINITE, _RANGE and _EXTENT, for the rows it counts in
+ *             skipped_nonfinite, skipped_range and out_of_extent;
+ *   visit     the voxels cell + o, o = 0 ... neighbors - 1, in rdm_voxel_map_register's order and under its rule: a voxel takes part
+ *             if its key is in the table and its count >= min_points;
+ *   per voxel d2_o = r^T M r with r, Sigma = cov + sigma^2 I and M exactly as rdm_voxel_map_register forms them;
+ *   best      the voxel of the smallest d2_o, ties going to the smallest o;
+ *   label     no voxel took part -> _UNMAPPED; else the best voxel's scans < min_scans -> _TRANSIENT (a voxel of the table was seen
+ *             in at least one scan, so min_scans <= 1 never is and does not read the block); else d2 > max_d2 -> _OFF_SURFACE; else
+ *             _STATIC.
+ * Outputs, all on the device and indexed by row; ANY of them may be null and is then neither computed nor written: labels u8 [total];
+ * best i8 [total] (the winning o, or -1); counts i32 [total] (the best voxel's count, or 0); seen i32 [total, 3] (its {scans, first,
+ * last}, or the reset values {0, 2^31 - 1, -1}); d2 f64 [total] (the best, or +inf); d2_sum f64 [total] (the sum of d2_o in ascending o,
+ * or 0: its sum over a scan's rows is rdm_voxel_map_register's cost); pairs u8 [total] (how many voxels took part); tallies i64
+ * [n_scans, RDM_VOXEL_QUERY_TALLIES]: per scan the number of rows of each label 0 ... 6 and, in column 7, the sum of pairs -- the call
+ * zeroes it and adds one integer atomic per workgroup, scan and field after a reduction in the workgroup.  Rows outside every
+ * [offsets[s], offsets[s + 1]) are left untouched; n_scans = 0 (nothing is written) and empty scans are valid.  No workspace, no float
+ * atomics: a row's outputs are a function of the row, its pose and the map's contents -- not of the capacity, the order of
+ * integration, the row's place in the batch or the run.  With neighbors = 1, max_d2 = +inf and neither d2 nor d2_sum wanted no
+ * distance is formed: the lookup alone.                                                                                          */
+#define RDM_VOXEL_POINT_NONFINITE 0
+#define RDM_VOXEL_POINT_RANGE 1
+#define RDM_VOXEL_POINT_EXTENT 2
+#define RDM_VOXEL_POINT_UNMAPPED 3
+#define RDM_VOXEL_POINT_TRANSIENT 4
+#define RDM_VOXEL_POINT_OFF_SURFACE 5
+#define RDM_VOXEL_POINT_STATIC 6
+#define RDM_VOXEL_QUERY_TALLIES 8
+int rdm_voxel_map_query(const void* map, size_t map_bytes, int64_t capacity, int channels, const void* moments, size_t moments_bytes,
+                        const void* observations, size_t observations_bytes, double voxel, const float* points, int64_t ld,
+                        int64_t total, const int64_t* offsets, const double* poses, int64_t n_scans, double min_range, double max_range,
+                        double sigma, int64_t min_points, int neighbors, int64_t min_scans, double max_d2, uint8_t* labels,
+                        int8_t* best, int32_t* counts, int32_t* seen, double* d2, double* d2_sum, uint8_t* pairs, int64_t* tallies,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

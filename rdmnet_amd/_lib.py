@@ -57,6 +57,9 @@ VOXEL_MAP_MAX_CHANNELS = 8  # = RDM_VOXEL_MAP_MAX_CHANNELS
 VOXEL_MAP_STATS = ('occupied', 'integrated', 'skipped_nonfinite', 'skipped_range', 'out_of_extent', 'dropped_full')
 VOXEL_MOMENTS_PLANES = 9  # = RDM_VOXEL_MOMENTS_PLANES: u_x, u_y, u_z, then u_a u_b for ab = xx, xy, xz, yy, yz, zz
 VOXEL_OBSERVATIONS_MAX_SCANS = 64  # = RDM_VOXEL_OBSERVATIONS_MAX_SCANS: scans of one rdm_voxel_map_integrate_observed call
+# rdm_voxel_map_query's labels, in the order of their codes RDM_VOXEL_POINT_*
+VOXEL_POINT_LABELS = ('nonfinite', 'range', 'extent', 'unmapped', 'transient', 'off_surface', 'static')
+VOXEL_QUERY_TALLIES = 8  # = RDM_VOXEL_QUERY_TALLIES: a scan's rows per label, then its pairs
 
 EVAL_RECORD_WIDTH = 20 # = RDM_EVAL_RECORD_WIDTH
 # the fields of one record of rdm_eval_pairs, in order
@@ -299,6 +302,9 @@ SIGNATURES = {
     'rdm_voxel_map_extract_observations': (c_int, [c_void, c_size, c_i64, c_int, c_void, c_size, ctypes.c_double, c_i64, c_void, c_void,
                                                    c_void, c_i64, c_void, c_void, c_size, c_void]),
     'rdm_voxel_map_prune': (c_int, [c_void, c_size, c_i64, c_void, c_size, c_void, c_size, c_i64, c_int, c_i64, c_i64, c_void]),
+    'rdm_voxel_map_query': (c_int, [c_void, c_size, c_i64, c_int, c_void, c_size, c_void, c_size, ctypes.c_double, c_void, c_i64, c_i64,
+                                    c_void, c_void, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i64, c_int, c_i64,
+                                    ctypes.c_double, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
 }
 
 

@@ -30,8 +30,12 @@
 // point is counted, one load of the slot's mask and, where the scan's bit is still clear, one atomicOr; the one thread that got the
 // bit clear back updates the record.  Bits only go from 0 to 1 inside a call, so a set bit seen by the plain load is final.
 //
-// Three pinned definitions are written once: the point gate (gate_sensor, gate_world; integrate and register), the key (pack_key,
-// key_cell; integrate, register, extract) and the voxel Gaussian (voxel_gaussian; both extracts and register).  `#pragma clang fp
+// Queries (include/rdmnet_hip.h, "voxel map queries"; tests/voxel_query_restatement.py): register's per-point lookup and distance, kept
+// per point and not summed -- query_kernel, below the registration.  All three blocks are only read.
+//
+// Four pinned definitions are written once: the point gate (gate_sensor, gate_world; integrate, register and query), the key (pack_key,
+// key_cell; integrate, register, query, extract), the voxel Gaussian (voxel_gaussian; both extracts, register and query) and the weight
+// of a residual (voxel_precision; register and query).  `#pragma clang fp
 // contract(off)` is lexical and does not follow an inlined callee: every helper with pinned arithmetic opens with it itself, and
 // jacobi3 and rodrigues, which stand outside any such block, stay there.
 #include <cmath>
@@ -229,6 +233,24 @@ __device__ __forceinline__ Gaussian voxel_gaussian(const Table& t, const unsigne
       for (int b = a; b < 3; ++b, ++k) g.cov[k] = (S[3 + k] / n - m[a] * m[b]) * s2;
   }
   return g;
+}
+
+// What register and query weigh a residual with: M = (cov + sigma2 I)^-1, cofactors over the determinant, and Mr = M r.
+__device__ __forceinline__ void voxel_precision(const double (&cov)[6], double sigma2, const double (&r)[3], double (&M)[3][3],
+                                                double (&Mr)[3]) {
+#pragma clang fp contract(off)
+  const double a00 = cov[0] + sigma2, a01 = cov[1], a02 = cov[2], a11 = cov[3] + sigma2, a12 = cov[4], a22 = cov[5] + sigma2;
+  const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
+  const double c11 = a00 * a22 - a02 * a02, c12 = a01 * a02 - a00 * a12, c22 = a00 * a11 - a01 * a01;
+  const double det = (a00 * c00 + a01 * c01) + a02 * c02;
+  M[0][0] = c00 / det;
+  M[0][1] = M[1][0] = c01 / det;
+  M[0][2] = M[2][0] = c02 / det;
+  M[1][1] = c11 / det;
+  M[1][2] = M[2][1] = c12 / det;
+  M[2][2] = c22 / det;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) Mr[d] = (M[d][0] * r[0] + M[d][1] * r[1]) + M[d][2] * r[2];
 }
 
 // the number of offsets[1 .. n_scans] that are <= i: the scan of row i when offsets ascend (empty scans are passed over)
@@ -688,15 +710,8 @@ __global__ void __launch_bounds__(kBlock) register_accumulate_kernel(Table t, co
       if (slot < 0 || t.counts[slot] < min_points) continue;
       const Gaussian G = voxel_gaussian<true>(t, moments, capacity, voxel, slot);
       const double r[3] = {wd[0] - G.mean[0], wd[1] - G.mean[1], wd[2] - G.mean[2]};
-      const double a00 = G.cov[0] + sigma2, a01 = G.cov[1], a02 = G.cov[2], a11 = G.cov[3] + sigma2, a12 = G.cov[4], a22 = G.cov[5] + sigma2;
-      // M = the inverse of the symmetric matrix a: cofactors over the determinant
-      const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
-      const double c11 = a00 * a22 - a02 * a02, c12 = a01 * a02 - a00 * a12, c22 = a00 * a11 - a01 * a01;
-      const double det = (a00 * c00 + a01 * c01) + a02 * c02;
-      const double M[3][3] = {{c00 / det, c01 / det, c02 / det}, {c01 / det, c11 / det, c12 / det}, {c02 / det, c12 / det, c22 / det}};
-      double Mr[3];
-#pragma unroll
-      for (int d = 0; d < 3; ++d) Mr[d] = (M[d][0] * r[0] + M[d][1] * r[1]) + M[d][2] * r[2];
+      double M[3][3], Mr[3];
+      voxel_precision(G.cov, sigma2, r, M, Mr);
       // B = [q]x M = (J's rotation block)^T M; H = [[-B [q]x, B], [B^T, M]], g = (q x Mr, Mr)
       double B[3][3];
 #pragma unroll
@@ -852,6 +867,146 @@ __global__ void __launch_bounds__(kBlock) register_finalize_kernel(RegWork w, in
     st.done = 1;
     atomicSub(w.running, 1);
   }
+}
+
+// ---- per-point queries (include/rdmnet_hip.h, "voxel map queries"; tests/voxel_query_restatement.py) ----------------------------
+//
+// One launch, one thread per row, a read-only gather: the gates and the lookup of register, but what the lookup finds is kept per
+// row and not summed.  A workgroup takes a contiguous run of 256-row chunks, so the rows of one scan that it meets are tallied in LDS
+// (wave ballots, one LDS add per wave and field) and reach the scan's row of `tallies` as one integer atomic per field when the run
+// leaves the scan.  kDist = false is the labels-only form of neighbors = 1: no sums, no moments and no float64 beyond the gates.
+
+constexpr unsigned kQueryBlocks = 2048;  // 8 workgroups on each of 256 CUs; longer batches go to longer runs of chunks
+constexpr int kTallies = RDM_VOXEL_QUERY_TALLIES;
+constexpr int kNoLabel = kTallies;  // of a thread without a row
+static_assert(kTallies == 8 && RDM_VOXEL_POINT_STATIC == 6, "seven labels and the pairs in a row of tallies");
+static_assert(RDM_VOXEL_POINT_NONFINITE == 0 && kRange - kNonfinite == RDM_VOXEL_POINT_RANGE &&
+                  kExtent - kNonfinite == RDM_VOXEL_POINT_EXTENT,
+              "a gate's verdict is its label + kNonfinite");
+
+struct QueryOut {  // any of them null: not computed, not written
+  uint8_t* labels;
+  int8_t* best;
+  int32_t* counts;
+  int32_t* seen;
+  double* d2;
+  double* d2_sum;
+  uint8_t* pairs;
+  unsigned long long* tallies;
+};
+
+template <bool kDist, bool kCov>
+__global__ void __launch_bounds__(kBlock) query_kernel(Table t, const unsigned long long* __restrict__ moments,
+                                                       const int* __restrict__ records, long long capacity, int channels, double voxel,
+                                                       const float* __restrict__ points, long long ld, long long total,
+                                                       const int64_t* __restrict__ offsets, const double* __restrict__ poses,
+                                                       long long n_scans, double lo2, double hi2, double sigma2, unsigned int min_points,
+                                                       int neighbors, int min_scans, double max_d2, long long chunks, QueryOut out) {
+#pragma clang fp contract(off)
+  __shared__ unsigned long long tally[kTallies];
+  if (threadIdx.x < kTallies) tally[threadIdx.x] = 0ull;
+  long long tallied = -1;  // the scan that `tally` counts
+  // every thread of the workgroup calls it with the same `next`
+  auto turn_to = [&](long long next) {
+    __syncthreads();
+    if (threadIdx.x < kTallies && tally[threadIdx.x] != 0ull) {
+      atomicAdd(out.tallies + tallied * kTallies + threadIdx.x, tally[threadIdx.x]);  // (nothing was counted while tallied = -1)
+      tally[threadIdx.x] = 0ull;
+    }
+    __syncthreads();
+    tallied = next;
+  };
+  long long begin = offsets[0], end = offsets[n_scans];
+  begin = begin < 0 ? 0 : begin;
+  end = end > total ? total : end;  // (a bad offsets array reads and writes nothing outside the batch)
+  const int visits = kDist ? neighbors : 1;
+  for (long long c = 0; c < chunks; ++c) {
+    const long long row0 = begin + (static_cast<long long>(blockIdx.x) * chunks + c) * kBlock;
+    if (row0 >= end) break;
+    const long long i = row0 + threadIdx.x;
+    long long scan = -1;
+    int label = kNoLabel, pairs = 0;
+    if (i < end && (scan = scan_of(offsets, n_scans, i)) < n_scans) {
+      float v[kMaxC];
+      double wd[3];
+      long long q[kMaxC];
+      int verdict = gate_sensor(points + i * ld, channels, lo2, hi2, v);
+      if (verdict == kPass) verdict = gate_world(v, poses + scan * 16, voxel, wd, q);
+      int best = -1;
+      long long best_slot = -1;
+      uint32_t best_count = 0u;
+      [[maybe_unused]] double best_d2 = INFINITY, sum = 0.0;
+      int seen[kObsFields] = {0, static_cast<int>(kMaxScanId), -1};
+      if (verdict != kPass) {
+        label = verdict - kNonfinite;
+      } else {
+        const long long cell[3] = {q[0] >> kFrac, q[1] >> kFrac, q[2] >> kFrac};
+        for (int o = 0; o < visits; ++o) {  // register's order
+          long long n[3] = {cell[0], cell[1], cell[2]};
+          if (o > 0) n[(o - 1) >> 1] += (o & 1) ? -1 : 1;
+          if (n[0] < -kHalf || n[0] >= kHalf || n[1] < -kHalf || n[1] >= kHalf || n[2] < -kHalf || n[2] >= kHalf) continue;
+          const long long slot = find(t.keys, capacity, pack_key(n[0], n[1], n[2]));
+          if (slot < 0) continue;
+          const uint32_t count = t.counts[slot];
+          if (count < min_points) continue;
+          ++pairs;
+          if constexpr (kDist) {
+            Gaussian G = voxel_gaussian<kCov>(t, moments, capacity, voxel, slot);
+            if constexpr (!kCov)
+              for (int k = 0; k < 6; ++k) G.cov[k] = 0.0;
+            const double r[3] = {wd[0] - G.mean[0], wd[1] - G.mean[1], wd[2] - G.mean[2]};
+            double M[3][3], Mr[3];
+            voxel_precision(G.cov, sigma2, r, M, Mr);
+            const double d2 = (r[0] * Mr[0] + r[1] * Mr[1]) + r[2] * Mr[2];  // register's cost term
+            sum += d2;
+            if (best >= 0 && !(d2 < best_d2)) continue;  // ties go to the smallest o
+            best_d2 = d2;
+          }
+          best = o;
+          best_slot = slot;
+          best_count = count;
+        }
+        if (best >= 0 && records != nullptr)
+          for (int k = 0; k < kObsFields; ++k) seen[k] = records[observed_at(best_slot, k)];
+        if (best < 0)
+          label = RDM_VOXEL_POINT_UNMAPPED;
+        else if (records != nullptr && seen[kObsScans] < min_scans)
+          label = RDM_VOXEL_POINT_TRANSIENT;
+        else if (kDist && best_d2 > max_d2)
+          label = RDM_VOXEL_POINT_OFF_SURFACE;
+        else
+          label = RDM_VOXEL_POINT_STATIC;
+      }
+      if (out.labels != nullptr) out.labels[i] = static_cast<uint8_t>(label);
+      if (out.best != nullptr) out.best[i] = static_cast<int8_t>(best);
+      if (out.counts != nullptr) out.counts[i] = static_cast<int32_t>(best_count);
+      if (out.seen != nullptr)
+        for (int k = 0; k < kObsFields; ++k) out.seen[i * kObsFields + k] = seen[k];
+      if constexpr (kDist) {
+        if (out.d2 != nullptr) out.d2[i] = best_d2;
+        if (out.d2_sum != nullptr) out.d2_sum[i] = sum;
+      }
+      if (out.pairs != nullptr) out.pairs[i] = static_cast<uint8_t>(pairs);
+    }
+    if (out.tallies == nullptr) continue;
+    // the scans of this chunk's rows, one after the other (one, as a rule); an empty scan has no row to count
+    const long long last_row = (row0 + kBlock < end ? row0 + kBlock : end) - 1;
+    long long last = scan_of(offsets, n_scans, last_row);
+    last = last < n_scans ? last : n_scans - 1;
+    for (long long s = scan_of(offsets, n_scans, row0); s <= last; ++s) {
+      if (offsets[s + 1] <= offsets[s]) continue;
+      if (s != tallied) turn_to(s);
+      const bool mine = scan == s && label != kNoLabel;
+      unsigned long long add[kTallies];
+      for (int k = 0; k < kTallies - 1; ++k) add[k] = __popcll(__ballot(mine && label == k));
+      add[kTallies - 1] = 0ull;  // pairs <= 7: three bits
+      for (int b = 0; b < 3; ++b) add[kTallies - 1] += static_cast<unsigned long long>(__popcll(__ballot(mine && ((pairs >> b) & 1)))) << b;
+      if ((threadIdx.x & 63) == 0)
+        for (int k = 0; k < kTallies; ++k)
+          if (add[k] != 0ull) atomicAdd(&tally[k], add[k]);
+    }
+  }
+  if (out.tallies != nullptr && tallied >= 0) turn_to(-1);
 }
 
 // ---- what the entry points share -----------------------------------------------------------------------------------------------
@@ -1219,4 +1374,52 @@ extern "C" int rdm_voxel_map_register(const void* map, size_t map_bytes, int64_t
     RDM_HIP_CHECK(hipStreamSynchronize(s));
   }
   return RDM_OK;
+}
+
+// ---- voxel map queries --------------------------------------------------------------------------------------------------------
+
+extern "C" int rdm_voxel_map_query(const void* map, size_t map_bytes, int64_t capacity, int channels, const void* moments,
+                                   size_t moments_bytes, const void* observations, size_t observations_bytes, double voxel,
+                                   const float* points, int64_t ld, int64_t total, const int64_t* offsets, const double* poses,
+                                   int64_t n_scans, double min_range, double max_range, double sigma, int64_t min_points, int neighbors,
+                                   int64_t min_scans, double max_d2, uint8_t* labels, int8_t* best, int32_t* counts, int32_t* seen,
+                                   double* d2, double* d2_sum, uint8_t* pairs, int64_t* tallies, void* stream) {
+  using namespace rdm;
+  const char* what = "rdm_voxel_map_query";
+  Table t;
+  unsigned long long* m = nullptr;
+  Observations o{nullptr, nullptr};
+  if (const int rc = open_table(what, const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
+  if (moments != nullptr)
+    if (const int rc = open_moments(what, moments, moments_bytes, capacity, m, RDM_ERR_ARG)) return rc;
+  if (observations != nullptr)
+    if (const int rc = open_observations(what, observations, observations_bytes, capacity, o)) return rc;
+  if (const int rc = check_batch(what, voxel, channels, points, ld, total, offsets, poses, n_scans, INT64_MAX, false, min_range, max_range))
+    return rc;
+  RDM_REQUIRE(sigma > 0.0 && std::isfinite(sigma), "%s: sigma must be positive and finite (got %g)", what, sigma);
+  RDM_REQUIRE(neighbors == 1 || neighbors == 7, "%s: neighbors must be 1 or 7 (got %d)", what, neighbors);
+  RDM_REQUIRE(min_points >= 1 && min_scans >= 0, "%s: need min_points >= 1 and min_scans >= 0", what);
+  RDM_REQUIRE(max_d2 >= 0.0, "%s: max_d2 must be >= 0 or +inf (got %g)", what, max_d2);  // (NaN fails)
+  RDM_REQUIRE(observations != nullptr || (min_scans <= 1 && seen == nullptr),
+              "%s: min_scans > 1 and the seen output need an observations block", what);
+  if (n_scans == 0) return RDM_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (tallies != nullptr) fill_words<unsigned long long>(reinterpret_cast<unsigned long long*>(tallies), n_scans * kTallies, 0ull, s);
+  if (total > 0) {
+    // every voxel of the table was seen in at least one scan, so the records are read for min_scans > 1 or the seen output only; the
+    // distances are formed where a label, the choice among seven voxels or an output needs them
+    const int* records = min_scans > 1 || seen != nullptr ? o.record : nullptr;
+    const bool dist = neighbors == 7 || max_d2 < INFINITY || d2 != nullptr || d2_sum != nullptr;
+    const int64_t n_chunks = (total + kBlock - 1) / kBlock;
+    const int64_t blocks = n_chunks < kQueryBlocks ? n_chunks : kQueryBlocks;
+    const int64_t chunks = (n_chunks + blocks - 1) / blocks;
+    const QueryOut out{labels, best, counts, seen, d2, d2_sum, pairs, reinterpret_cast<unsigned long long*>(tallies)};
+    auto kernel = !dist ? query_kernel<false, false> : (m != nullptr ? query_kernel<true, true> : query_kernel<true, false>);
+    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, t, m, records, static_cast<long long>(capacity),
+                       channels, voxel, points, static_cast<long long>(ld), static_cast<long long>(total), offsets, poses,
+                       static_cast<long long>(n_scans), min_range * min_range, max_range * max_range, sigma * sigma,
+                       least_points(min_points), neighbors, static_cast<int>(min_scans > kMaxScanId ? kMaxScanId : min_scans), max_d2,
+                       static_cast<long long>(chunks), out);
+  }
+  return launch_status(what);
 }

@@ -1108,6 +1108,74 @@ class VoxelMap:
                            'rdm_voxel_map_register')
         return MapRegistrationResult(T.view(n, 4, 4), H.view(n, 6, 6), g, cost.view(n), stats[:, 0], stats[:, 1], stats[:, 2], stats[:, 3])
 
+    def query(self, clouds, poses, *, sigma=0.02, min_points=1, neighbors=1, min_scans=1, max_d2=float('inf'), min_range=0.0,
+              max_range=float('inf'), outputs=None):
+        """What the map says about every point of every scan (rdm_voxel_map_query).  clouds, poses, min_range,
+        max_range: as `integrate` takes them.  A point is gated as `integrate` gates it, looks up its voxel (neighbors = 7: and the six
+        face neighbours) under `register`'s rule -- a voxel takes part with at least min_points points -- and is judged by the voxel of
+        the smallest Mahalanobis distance d2 = r^T (cov + sigma^2 I)^-1 r (a map without moments: cov = 0): no voxel -> unmapped; that
+        voxel seen in fewer than min_scans scans -> transient; d2 > max_d2 -> off_surface; else static.  outputs: an iterable of
+        MapQueryResult.FIELDS; None: all that the map supports (`scans`, `first`, `last` need observations).  The others come back as
+        None and are not computed.  The map is only read.  -> MapQueryResult (device tensors).  No read-back."""
+        points, offsets, n, X, lo, hi = self._packed('query', clouds, poses, min_range, max_range)
+        sigma, max_d2 = float(sigma), float(max_d2)
+        min_points, neighbors, min_scans = int(min_points), int(neighbors), int(min_scans)
+        if not (sigma > 0 and sigma < float('inf')):
+            raise ValueError(f'sigma must be positive and finite, got {sigma}')
+        if neighbors not in (1, 7):
+            raise ValueError(f'neighbors must be 1 or 7, got {neighbors}')
+        if min_points < 1 or min_scans < 0:
+            raise ValueError(f'need min_points >= 1 and min_scans >= 0, got {min_points} and {min_scans}')
+        if not max_d2 >= 0:
+            raise ValueError(f'max_d2 must be >= 0 (inf: no test), got {max_d2}')
+        seen = ('scans', 'first', 'last')
+        if outputs is None:
+            want = set(MapQueryResult.FIELDS) - (set() if self.observations else set(seen))
+        else:
+            want = set(outputs)
+            if want - set(MapQueryResult.FIELDS):
+                raise ValueError(f'outputs must be among {MapQueryResult.FIELDS}, got {sorted(want - set(MapQueryResult.FIELDS))}')
+        if min_scans > 1 or want & set(seen):
+            self._need_observations('query (min_scans > 1, or the outputs scans, first and last)')
+        dev = self.device
+        rows = 0 if points is None else int(points.shape[0])
+        specs = dict(labels=(torch.uint8, ()), best=(torch.int8, ()), counts=(torch.int32, ()), d2=(torch.float64, ()),
+                     d2_sum=(torch.float64, ()), pairs=(torch.uint8, ()))
+        out = {k: torch.empty((rows,) + shape, dtype=dtype, device=dev) for k, (dtype, shape) in specs.items() if k in want}
+        rec = torch.empty((rows, 3), dtype=torch.int32, device=dev) if want & set(seen) else None
+        tallies = torch.zeros((n, _lib.VOXEL_QUERY_TALLIES), dtype=torch.int64, device=dev) if 'tallies' in want else None
+        if n > 0 and rows > 0:
+            points, ld, total, offsets, Xd = self._on_device(points, offsets, X)
+            mom = (self._mom.data_ptr(), self._mom.numel()) if self.moments else (0, 0)
+            obs = (self._obs.data_ptr(), self._obs.numel()) if self.observations else (0, 0)
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().rdm_voxel_map_query(
+                    *self._head(), *mom, *obs, self.voxel, points.data_ptr(), ld, total, offsets.data_ptr(), Xd.data_ptr(), n, lo, hi,
+                    sigma, min_points, neighbors, min_scans, max_d2, *(_lib.ptr(out.get(k)) for k in ('labels', 'best', 'counts')),
+                    _lib.ptr(rec), *(_lib.ptr(out.get(k)) for k in ('d2', 'd2_sum', 'pairs')), _lib.ptr(tallies), _lib.stream_ptr()),
+                    'rdm_voxel_map_query')
+        else:
+            offsets = offsets.to(dev)
+        for k, name in enumerate(seen):
+            out[name] = rec[:, k] if name in want else None
+        return MapQueryResult(tallies=tallies, offsets=offsets, **{k: out.get(k) for k in MapQueryResult.FIELDS if k != 'tallies'})
+
+    def clean(self, clouds, poses, **options):
+        """The scans without what the map does not call static: -> (list of tensors, tallies).  clouds: a list of tensors; poses and
+        the options: those of `query` (without `outputs`: the labels and the tallies alone are computed).  Tensor i holds the rows of
+        clouds[i] with the label `static`, all of its columns, in order; tallies int64 [n, 8] as MapQueryResult's.  One read-back
+        (the sizes of the result) per cloud."""
+        if not isinstance(clouds, (list, tuple)) or (len(clouds) == 2 and isinstance(clouds[1], torch.Tensor) and clouds[1].dtype == torch.int64):
+            raise ValueError('VoxelMap.clean: clouds must be a list of tensors')
+        if 'outputs' in options:
+            raise ValueError('VoxelMap.clean computes the labels and the tallies: it takes no `outputs`')
+        res = self.query(list(clouds), poses, outputs=('labels', 'tallies'), **options)
+        keep = res.labels == MapQueryResult.LABELS.index('static')
+        edges = [0]
+        for t in clouds:
+            edges.append(edges[-1] + int(t.shape[0]))
+        return [t[keep[a:b]] for t, a, b in zip(clouds, edges, edges[1:])], res.tallies
+
 
 class MapRegistrationResult:
     """What VoxelMap.register returns, device tensors with one row per scan: transformations float64 [n, 4, 4] (the refined poses),
@@ -1126,6 +1194,27 @@ class MapRegistrationResult:
         return 'MapRegistrationResult(' + '; '.join(
             f'{k}: {self.STATUS[s] if 0 <= s < 3 else s} after {i} updates, {c} correspondences of {p} points, cost {v:.6g}'
             for k, (i, c, p, s, v) in enumerate(zip(*rows, cost))) + ')'
+
+
+class MapQueryResult:
+    """What VoxelMap.query returns: device tensors indexed by the row of the packed batch (scan i is rows offsets[i] .. offsets[i + 1]),
+    None where not asked for.  labels uint8 (codes into LABELS); best int8 (which of the visited voxels won: 0 the point's own, 1 ... 6
+    its -x, +x, -y, +y, -z, +z neighbour, -1 none); counts int32 (that voxel's points, or 0); scans, first, last int32 (its
+    observations, or 0, 2^31 - 1, -1); d2 float64 (its Mahalanobis distance, or inf); d2_sum float64 (over all voxels that took part:
+    `register`'s cost term of the row); pairs uint8 (how many took part); tallies int64 [n, 8] (per scan the rows of each label, then
+    the sum of pairs); offsets int64 [n + 1]."""
+    LABELS = _lib.VOXEL_POINT_LABELS
+    FIELDS = ('labels', 'best', 'counts', 'scans', 'first', 'last', 'd2', 'd2_sum', 'pairs', 'tallies')
+
+    def __init__(self, labels, best, counts, scans, first, last, d2, d2_sum, pairs, tallies, offsets):
+        self.labels, self.best, self.counts, self.scans, self.first, self.last = labels, best, counts, scans, first, last
+        self.d2, self.d2_sum, self.pairs, self.tallies, self.offsets = d2, d2_sum, pairs, tallies, offsets
+
+    def __repr__(self):
+        if self.tallies is None:
+            return f'MapQueryResult({int(self.offsets.numel()) - 1} scans)'
+        return 'MapQueryResult(' + '; '.join(
+            f'{k}: ' + ', '.join(f'{v} {name}' for name, v in zip(self.LABELS, row) if v) for k, row in enumerate(self.tallies.cpu().tolist())) + ')'
 
 
 class RegistrationResult:

@@ -6,7 +6,8 @@
                                    [--map-range LO HI] [--map-batch 64] [--map-sharpness [--map-sharpness-min-points 4]]
                                    [--map-min-scans 1]
                                    [--map-refine [--map-refine-sigma 0.02] [--map-refine-neighbors {1,7}] [--map-refine-iterations 30]
-                                    [--map-refine-min-scans 1]]]
+                                    [--map-refine-min-scans 1]]
+                                   [--map-clean [--map-clean-max-d2 D] [--map-clean-sigma 0.02] [--map-clean-neighbors {1,7}]]]
 
 reads the `{seq}_{src}_{ref}.npz` pair files that `python -m rdmnet_amd.infer` wrote into DIR (ordered and filtered as
 `python -m rdmnet_amd.eval` reads them) and, per sequence, chains the pair poses into a trajectory as
@@ -31,7 +32,11 @@ the chained ones; the result is a third variant, `refined`, with its own error, 
 also keeps in how many scans every voxel was seen (`ops.VoxelMap(observations=True)`) and every variant's map is pruned to the voxels
 seen in at least N scans before anything is written or reported -- a moving object is in a voxel in one scan, static structure in
 many --; a `persistent:` line after every `map:` line says what was kept.  --map-refine-min-scans N registers frame k >= N against
-that pruned map instead of the full one."""
+that pruned map instead of the full one.  With --map-clean (and --map-min-scans N >= 2, a finite --map-clean-max-d2 D, or both) every
+point of every scan is judged by each variant's full map, before that prune (`clean_scans`, `ops.VoxelMap.query`): the scans are written
+to `{seq}_{variant}_clean/` under their own names without the points that have no voxel, whose voxel was seen in fewer than N scans or that
+lie further than D (squared Mahalanobis distance; the map then keeps second moments) from their voxel's Gaussian, and a `clean:` line after
+the map's lines says what was dropped."""
 import argparse
 import math
 import os
@@ -179,6 +184,24 @@ def write_kitti_poses(path, poses):
 
 MAP_DEFAULTS = dict(voxel=0.3, min_points=1, batch=64, sharpness_min_points=4, min_scans=1)
 REFINE_DEFAULTS = dict(sigma=0.02, neighbors=1, iterations=30, min_points=4, min_scans=1)
+CLEAN_DEFAULTS = dict(sigma=0.02, neighbors=1, max_d2=math.inf)
+
+
+def _read_batches(paths, batch):
+    """Yields ((lo, hi), (points float32 [N, C], offsets int64 [hi - lo + 1])) for the scans paths[lo:hi], `batch` at a time, read on a
+    background thread while the caller works on the batch before."""
+    from . import prepare
+    groups = [(i, min(i + int(batch), len(paths))) for i in range(0, len(paths), int(batch))]
+
+    def load(group):
+        clouds = [prepare.load_scan(paths[k]) for k in range(*group)]
+        for k, c in zip(range(*group), clouds):
+            if c.ndim != 2 or c.shape[1] != clouds[0].shape[-1]:
+                raise TrajectoryError(f'{paths[k]}: shape {c.shape}, expected [N, {clouds[0].shape[-1]}] as the scans of its batch')
+        offsets = np.concatenate([[0], np.cumsum([len(c) for c in clouds])]).astype(np.int64)
+        return np.concatenate(clouds), offsets
+
+    return prepare._read_ahead(load, groups)
 
 
 def build_map(paths, poses, voxel=MAP_DEFAULTS['voxel'], channels=None, min_range=0.0, max_range=math.inf, batch=MAP_DEFAULTS['batch'],
@@ -198,19 +221,9 @@ def build_map(paths, poses, voxel=MAP_DEFAULTS['voxel'], channels=None, min_rang
         if not osp.isfile(path):
             raise TrajectoryError(f'{path}: no such scan file')
     import torch
-    from . import ops, prepare
-    groups = [(i, min(i + int(batch), len(paths))) for i in range(0, len(paths), int(batch))]
-
-    def load(group):
-        clouds = [prepare.load_scan(paths[k]) for k in range(*group)]
-        for k, c in zip(range(*group), clouds):
-            if c.ndim != 2 or c.shape[1] != clouds[0].shape[-1]:
-                raise TrajectoryError(f'{paths[k]}: shape {c.shape}, expected [N, {clouds[0].shape[-1]}] as the scans of its batch')
-        offsets = np.concatenate([[0], np.cumsum([len(c) for c in clouds])]).astype(np.int64)
-        return np.concatenate(clouds), offsets
-
+    from . import ops
     vmap = None
-    for group, (points, offsets) in prepare._read_ahead(load, groups):
+    for group, (points, offsets) in _read_batches(paths, batch):
         if vmap is None:
             width = points.shape[1] if channels is None else int(channels)
             vmap = ops.VoxelMap(voxel, channels=min(width, 8), capacity=capacity, device=device, moments=moments,
@@ -240,6 +253,53 @@ def persistent_line(seq, what, min_scans, kept, full, scans):
     """kept / full: the stats of the pruned and of the full map."""
     return (f"seq {seq} {what} persistent: {kept['occupied']} of {full['occupied']} voxels seen in >= {min_scans} scans, "
             f"{kept['integrated']} of {full['integrated']} points, {scans} scans")
+
+
+def clean_scans(paths, poses, vmap, out_dir, *, min_scans=MAP_DEFAULTS['min_scans'], max_d2=math.inf, sigma=CLEAN_DEFAULTS['sigma'],
+                min_points=MAP_DEFAULTS['min_points'], neighbors=CLEAN_DEFAULTS['neighbors'], min_range=0.0, max_range=math.inf,
+                batch=MAP_DEFAULTS['batch']):
+    """The scans `paths` (read as build_map reads them) under `poses` without the points that the map `vmap` does not call static
+    (ops.VoxelMap.query: unmapped, in a voxel seen in fewer than min_scans scans, or further than max_d2 from its voxel's Gaussian):
+    every scan's static rows, all columns, are written to out_dir under the scan's own file name and format.  The map is only read.
+    -> the tallies int64 numpy [n, 8]: per scan the rows of each label of ops.MapQueryResult.LABELS, then the pairs."""
+    paths = list(paths)
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    if len(paths) != len(poses):
+        raise ValueError(f'clean_scans: {len(paths)} scans and {len(poses)} poses')
+    if int(batch) < 1:
+        raise ValueError(f'clean_scans: batch must be >= 1, got {batch}')
+    names = [osp.basename(p) for p in paths]
+    if len(set(names)) != len(names):
+        raise ValueError('clean_scans: two scans have the same file name')
+    for path in paths:
+        if not osp.isfile(path):
+            raise TrajectoryError(f'{path}: no such scan file')
+    import torch
+    from . import ops
+    os.makedirs(out_dir, exist_ok=True)
+    static = ops.MapQueryResult.LABELS.index('static')
+    tallies = np.zeros((len(paths), 8), np.int64)
+    for (lo, hi), (points, offsets) in _read_batches(paths, batch):
+        if points.shape[1] < vmap.channels:
+            raise TrajectoryError(f'{paths[lo]}: {points.shape[1]} columns, the map has {vmap.channels} channels')
+        res = vmap.query((torch.from_numpy(points).to(vmap.device), torch.from_numpy(offsets)), poses[lo:hi], sigma=sigma,
+                         min_points=min_points, neighbors=neighbors, min_scans=min_scans, max_d2=max_d2, min_range=min_range,
+                         max_range=max_range, outputs=('labels', 'tallies'))
+        tallies[lo:hi] = res.tallies.cpu().numpy()
+        keep = res.labels.cpu().numpy() == static
+        for k in range(lo, hi):
+            rows = points[offsets[k - lo]:offsets[k - lo + 1]][keep[offsets[k - lo]:offsets[k - lo + 1]]]
+            if names[k].endswith('.bin'):
+                rows.astype(np.float32).tofile(osp.join(out_dir, names[k]))
+            else:
+                np.save(osp.join(out_dir, names[k]), rows)
+    return tallies
+
+
+def clean_line(seq, what, tallies, min_scans, max_d2):
+    t = np.asarray(tallies, np.int64).reshape(-1, 8).sum(0)
+    return (f'seq {seq} {what} clean: {t[6]} of {t[:7].sum()} points kept in {len(tallies)} scans, dropped: {t[3]} unmapped, '
+            f'{t[4]} transient (< {min_scans} scans), {t[5]} off surface (d2 > {max_d2:g}), {t[:3].sum()} gated')
 
 
 def refine_against_map(paths, poses, voxel=MAP_DEFAULTS['voxel'], channels=None, min_range=0.0, max_range=math.inf,
@@ -304,9 +364,16 @@ def write_map(args, seq, what, paths, poses, emit, vmap=None):
     lo, hi = args.map_range if args.map_range else (0.0, math.inf)
     sharpness = bool(getattr(args, 'map_sharpness', False))
     min_scans = getattr(args, 'map_min_scans', None) or MAP_DEFAULTS['min_scans']
+    clean = bool(getattr(args, 'map_clean', False))
+    max_d2 = getattr(args, 'map_clean_max_d2', None) if clean else None
+    max_d2 = CLEAN_DEFAULTS['max_d2'] if max_d2 is None else max_d2
     if vmap is None:
-        vmap = build_map(paths, poses, voxel=args.map_voxel, min_range=lo, max_range=hi, batch=args.map_batch, moments=sharpness,
-                         observations=min_scans > 1)
+        vmap = build_map(paths, poses, voxel=args.map_voxel, min_range=lo, max_range=hi, batch=args.map_batch,
+                         moments=sharpness or math.isfinite(max_d2), observations=min_scans > 1)
+    if clean:  # the scans against the full map
+        tallies = clean_scans(paths, poses, vmap, osp.join(args.out, f'{seq}_{what}_clean'), min_scans=min_scans, max_d2=max_d2,
+                              sigma=args.map_clean_sigma, min_points=args.map_min_points, neighbors=args.map_clean_neighbors,
+                              min_range=lo, max_range=hi, batch=args.map_batch)
     if min_scans > 1:  # everything below describes the pruned map
         full, scans = vmap.stats(), vmap.num_scans
         vmap = vmap.pruned(min_scans)
@@ -318,6 +385,8 @@ def write_map(args, seq, what, paths, poses, emit, vmap=None):
         emit(persistent_line(seq, what, min_scans, vmap.stats(), full, scans))
     if sharpness:
         emit(sharpness_line(seq, what, args.map_sharpness_min_points, vmap.sharpness(args.map_sharpness_min_points)))
+    if clean:
+        emit(clean_line(seq, what, tallies, min_scans, max_d2))
 
 
 def map_paths(args, seqs):
@@ -334,6 +403,17 @@ def map_paths(args, seqs):
         raise TrajectoryError('--map-refine-sigma must be > 0 and --map-refine-iterations >= 0')
     elif getattr(args, 'map_refine_min_scans', REFINE_DEFAULTS['min_scans']) < 1:
         raise TrajectoryError(f'--map-refine-min-scans must be >= 1, got {args.map_refine_min_scans}')
+    if not getattr(args, 'map_clean', False):
+        for flag, key in (('--map-clean-max-d2', 'max_d2'), ('--map-clean-sigma', 'sigma'), ('--map-clean-neighbors', 'neighbors')):
+            if getattr(args, 'map_clean_' + key, None) not in (None, CLEAN_DEFAULTS[key]):
+                raise TrajectoryError(f'{flag} needs --map-clean')
+    elif not (getattr(args, 'map_scans', None) and args.out):
+        raise TrajectoryError('--map-clean needs --map-scans and --out (the scans are judged by their map and written to --out)')
+    elif not (args.map_clean_sigma > 0 and math.isfinite(args.map_clean_sigma)) or not args.map_clean_max_d2 >= 0:
+        raise TrajectoryError('--map-clean-sigma must be > 0 and --map-clean-max-d2 >= 0')
+    elif not (getattr(args, 'map_min_scans', MAP_DEFAULTS['min_scans']) >= 2 or math.isfinite(args.map_clean_max_d2)):
+        raise TrajectoryError('--map-clean needs a criterion: --map-min-scans N >= 2 (drop what was seen in fewer scans) or a finite '
+                              '--map-clean-max-d2 D (drop what lies off the surface)')
     if not getattr(args, 'map_scans', None):
         if getattr(args, 'map_min_scans', None) not in (None, MAP_DEFAULTS['min_scans']):
             raise TrajectoryError('--map-min-scans needs --map-scans (the voxels are counted over the scans of the map)')
@@ -471,6 +551,17 @@ def make_parser():
                     help='at most N Gauss-Newton updates per frame')
     ap.add_argument('--map-refine-min-scans', type=int, default=REFINE_DEFAULTS['min_scans'], metavar='N',
                     help='register frame k >= N against the voxels seen in at least N of the frames before it (needs --map-refine)')
+    ap.add_argument('--map-clean', action='store_true',
+                    help="judge every point of every scan by each variant's full map and write the scans without what is not static "
+                         'to --out as {seq}_{variant}_clean/ (needs --map-scans, --out and --map-min-scans N >= 2 or '
+                         '--map-clean-max-d2 D); a `clean:` line says what was dropped')
+    ap.add_argument('--map-clean-max-d2', type=float, default=CLEAN_DEFAULTS['max_d2'], metavar='D',
+                    help="drop a point whose squared Mahalanobis distance from its voxel's Gaussian exceeds D (the map then keeps "
+                         'second moments; default: no test)')
+    ap.add_argument('--map-clean-sigma', type=float, default=CLEAN_DEFAULTS['sigma'], metavar='S',
+                    help='the noise of a scan point in metres, added to every voxel covariance')
+    ap.add_argument('--map-clean-neighbors', type=int, choices=(1, 7), default=CLEAN_DEFAULTS['neighbors'],
+                    help='a point is judged by its own voxel (1) or by the best of it and its six face neighbours (7)')
     return ap
 
 

@@ -1,7 +1,7 @@
 """Times the voxel map (ops.VoxelMap) on synthetic scans along a synthetic drive.
 
   python tools/map_bench.py [--frames 256] [--points 120000 | 18000] [--reps 3] [--batch 64] [--voxel 0.3] [--cpu] [--cpu-frames 8]
-                              [--moments] [--observations] [--register] [--digest]
+                              [--moments] [--observations] [--register] [--query] [--digest]
 With --digest (and nothing else): no timing, one sha1 line per output of the voxel map on the bundled scans (see digest()), for
 comparing the bits of two builds of the library.  Otherwise prints one JSON line per case:
   * integrate: --frames scans of --points points (120 000: a raw scan; 18 000: a down-sampled one), xyz + intensity, integrated in
@@ -26,6 +26,15 @@ comparing the bits of two builds of the library.  Otherwise prints one JSON line
     tolerances), the point-voxel pairs per second of the evaluation, and ms per iteration (accumulate + finalize launches) from runs
     of 4 and 12 forced updates of the batch; with --cpu also the seconds of one evaluation by tests/voxel_register_restatement.py
     and whether its counts equal the GPU's;
+  * with --query (and nothing else of the above): the per-point queries (ops.VoxelMap.query) for both scan shapes, a batch of
+    min(--frames, 64) scans under their true poses against the map with moments and observations that holds them: points/s of a
+    labels-only query that is the lookup alone (neighbors 1, min_scans 1), with the scan count (min_scans 2), with the distance too
+    (max_d2 25) and at neighbors 7, and of a query with every output at neighbors 1 and 7; beside them the points/s of
+    rdm_voxel_map_integrate of the same batch into a plain map that already holds it, and of rdm_voxel_map_integrate_observed into the
+    queried map -- the same lookup plus the atomic adds --, both through the raw calls (no growth, no read-back); every figure is
+    the whole call between two device events (a query: the kernel, the zeroing of the tallies and the upload of poses and offsets),
+    ten calls a window; with --cpu also the
+    seconds of tests/voxel_query_restatement.py on the first --cpu-frames scans and whether the GPU's integer outputs equal it;
   * with --cpu: the NumPy restatement (tests/voxel_map_restatement.py) on the first --cpu-frames scans, its points/s, and whether the
     GPU's map of the same scans equals it bit for bit."""
 import argparse
@@ -182,6 +191,70 @@ def register_cases(a):
     return 0
 
 
+def query_cases(a):
+    import torch
+    from rdmnet_amd import _lib, ops
+    L = _lib.lib()
+    frames = max(min(a.frames, 64), 1)
+    for points in (120000, 18000):
+        cloud, poses = synthetic_scans(frames, points), drive(frames)
+        total = frames * points
+        clouds = [cloud[k * points:(k + 1) * points] for k in range(frames)]
+        packed = (cloud, (torch.arange(frames + 1, dtype=torch.int64) * points).cuda())
+        capacity = 1 << int(np.ceil(np.log2(4 * total)))  # no growth in any of the calls below
+        vmap = ops.VoxelMap(a.voxel, channels=4, capacity=capacity, moments=True, observations=True).integrate(packed, poses)
+        plain = ops.VoxelMap(a.voxel, channels=4, capacity=capacity).integrate(packed, poses)
+        assert vmap.capacity == plain.capacity == capacity
+        X = torch.from_numpy(poses).cuda()
+        batch = (cloud.data_ptr(), 4, total, packed[1].data_ptr(), X.data_ptr(), frames, 0.0, float('inf'))
+
+        def integrate_plain():
+            _lib.check(L.rdm_voxel_map_integrate(*plain._head(), a.voxel, *batch, _lib.stream_ptr()), 'integrate')
+
+        def integrate_full():
+            _lib.check(L.rdm_voxel_map_integrate_observed(*vmap._head(), a.voxel, *batch, vmap._mom.data_ptr(), vmap._mom.numel(),
+                                                          vmap._obs.data_ptr(), vmap._obs.numel(), frames, _lib.stream_ptr()), 'integrate_observed')
+
+        line = {'case': 'query', 'points_per_scan': points, 'scans': frames, 'points': total, 'voxel': a.voxel, 'capacity': capacity,
+                'voxels': len(vmap)}
+        inner = 10  # calls per timed window: one call of 18 000-point scans is a fraction of a millisecond
+        line['calls_per_window'] = inner
+        ms_plain = timed(lambda: [integrate_plain() for _ in range(inner)], a.reps)[0] / inner
+        line['integrate_plain_points_per_s'] = round(total / ms_plain * 1e3)
+        cases = (('labels_lookup_only_n1', dict(outputs=('labels',), neighbors=1, min_scans=1)),
+                 ('labels_min_scans_n1', dict(outputs=('labels',), neighbors=1, min_scans=2)),
+                 ('labels_min_scans_max_d2_n1', dict(outputs=('labels',), neighbors=1, min_scans=2, max_d2=25.0)),
+                 ('labels_min_scans_n7', dict(outputs=('labels',), neighbors=7, min_scans=2)),
+                 ('labels_tallies_min_scans_n1', dict(outputs=('labels', 'tallies'), neighbors=1, min_scans=2)),
+                 ('every_output_n1', dict(neighbors=1, min_scans=2, max_d2=25.0)),
+                 ('every_output_n7', dict(neighbors=7, min_scans=2, max_d2=25.0)))
+        for name, kw in cases:
+            ms, res = timed(lambda: [vmap.query(packed, poses, **kw) for _ in range(inner)][-1], a.reps)
+            ms /= inner
+            line[name + '_points_per_s'] = round(total / ms * 1e3)
+            line[name + '_over_integrate_plain'] = round(ms_plain / ms, 3)
+        line['tallies'] = res.tallies.sum(0).tolist()
+        ms_full = timed(lambda: [integrate_full() for _ in range(inner)], a.reps)[0] / inner  # (last: it adds to the queried map)
+        line['integrate_moments_observations_points_per_s'] = round(total / ms_full * 1e3)
+        if a.cpu:
+            import voxel_moments_restatement as MR
+            import voxel_observations_restatement as OR
+            import voxel_query_restatement as QR
+            m = min(a.cpu_frames, frames)
+            host = [c.cpu().numpy() for c in clouds[:m]]
+            table, observed = MR.build(host, poses[:m], a.voxel, 4), OR.build(host, poses[:m], a.voxel, 4)
+            small = ops.VoxelMap(a.voxel, channels=4, moments=True, observations=True).integrate(clouds[:m], poses[:m])
+            got = small.query(clouds[:m], poses[:m], neighbors=7, min_scans=2, max_d2=25.0)
+            t0 = time.perf_counter()
+            ref = QR.batch(table, observed, host, poses[:m], neighbors=7, min_scans=2, max_d2=25.0)
+            cpu_s = time.perf_counter() - t0
+            line.update(cpu_s=round(cpu_s, 3), cpu_frames=m, cpu_points_per_s=round(m * points / cpu_s),
+                        integers_equal=bool(all(np.array_equal(getattr(got, k).cpu().numpy(), ref[k]) for k in QR.INTEGERS + ('tallies',))))
+        print(json.dumps(line), flush=True)
+        del vmap, plain
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--frames', type=int, default=256)
@@ -193,6 +266,7 @@ def main(argv=None):
     ap.add_argument('--observations', action='store_true',
                     help='also time integrate with the per-voxel scan observations, extract_observations, pruned and a refinement frame')
     ap.add_argument('--register', action='store_true', help='time the scan-to-map registration and nothing else')
+    ap.add_argument('--query', action='store_true', help='time the per-point queries beside integrate and nothing else')
     ap.add_argument('--digest', action='store_true', help='print the sha1 lines of the bundled scans\' maps and registrations and nothing else')
     ap.add_argument('--cpu', action='store_true', help='also time the NumPy restatement and compare the maps bit for bit')
     ap.add_argument('--cpu-frames', type=int, default=8)
@@ -204,6 +278,8 @@ def main(argv=None):
         return digest()
     if a.register:
         return register_cases(a)
+    if a.query:
+        return query_cases(a)
     C = 4
     cloud, poses = synthetic_scans(a.frames, a.points), drive(a.frames)
     total = a.frames * a.points
