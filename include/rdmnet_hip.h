@@ -1304,6 +1304,47 @@ int rdm_voxel_map_query(const void* map, size_t map_bytes, int64_t capacity, int
                         int8_t* best, int32_t* counts, int32_t* seen, double* d2, double* d2_sum, uint8_t* pairs, int64_t* tallies,
                         void* stream);
 
+/* ---- §7 voxel map state: the raw sums of a map out of the table and into another one (voxel_map.hip) ---------------------------------
+ * Not in the reference tree -> parity unpinned; the project's own definition, pinned to the NumPy restatement
+ * tests/voxel_state_restatement.py.  The STATE of a voxel is what the integrates have added to it, as integers: its key, its uint32
+ * count, its C int64 sums and, where the map has the blocks, its nine int64 moment sums and its {scans, first, last}.  A map is a
+ * function of the SET of integrated points, and every one of these is a sum (a min, a max) over that set, so the states of two maps
+ * of different scans add, key by key, to the state of the map of all the scans -- bit for bit, at any capacity.
+ * rdm_voxel_map_export reads the state of the voxels with count >= min_points in ascending key order.  The map and the blocks are only
+ * read.  Selection, order, min_points, max_rows, *n_rows and the workspace (rdm_voxel_map_extract_workspace_bytes) are those of
+ * rdm_voxel_map_extract, so its rows are the rows of that call with the same min_points.  Outputs on the device, each of which may be
+ * null: keys u64 [max_rows]; counts u32 [max_rows]; sums i64 [max_rows, C] row-major; moment_sums i64 [max_rows, 9]; seen i32
+ * [max_rows, 3] = {scans, first, last}.  `moments` and `observations` may be null; moment_sums (seen) must then be null too, else
+ * RDM_ERR_ARG.
+ * rdm_voxel_map_import adds n_records records of that layout (device arrays) into a map.  moment_sums is required if and only if the
+ * map has a moments block (`moments` not null) -- records that carry moments go into a map without the block with moment_sums null --
+ * and seen if and only if it has an observations block; anything else is RDM_ERR_ARG, as are id_offset < 0 and a null n_rejected.
+ * n_records = 0 is valid.  One launch, one thread per record:
+ *   reject    a record whose key has bit 63 set (the empty marker included), whose count is 0 or, where seen is given, whose record
+ *             is not 1 <= scans <= last - first + 1 with 0 <= first <= last <= 2^31 - 2 - id_offset, changes nothing and is counted
+ *             in the device word *n_rejected (int64), which the call zeroes first;
+ *   claim     the slot of the key by integrate's bounded probe; a record that finds neither its key nor an empty slot in one full
+ *             cycle adds its count to dropped_full and nothing else -- a key is stored with all of its records or not at all, by
+ *             integrate's argument --; a fresh claim adds 1 to occupied;
+ *   add       count to the slot's count (it wraps at 2^32, as the map's counts do) and to integrated, the C sums, the nine moment
+ *             sums, scans to scans, and first + id_offset / last + id_offset by an atomic min / max.  Integer atomics throughout: two
+ *             records of one batch may hold the same key.  The observation masks are scratch of integrate and are not touched.
+ * skipped_host (HOST memory, may be null): four uint64 that are added to skipped_nonfinite, skipped_range, out_of_extent and
+ * dropped_full, so that the six counters of a merged map are those of the map built in one pass.
+ * Condition: the records' scans are scans other than those already in the map -- after id_offset their ids are disjoint from the
+ * map's; `scans` adds only then (count, the sums, first and last hold regardless).
+ * Property: without drops, the contents of the table as rdm_voxel_map_export shows them are a function of the contents before and of
+ * the multiset of records: not of their order, the batching, the capacity or the run.  No float anywhere, no unbounded loop and no
+ * workspace.                                                                                                                        */
+int rdm_voxel_map_export(const void* map, size_t map_bytes, int64_t capacity, int channels, const void* moments, size_t moments_bytes,
+                         const void* observations, size_t observations_bytes, int64_t min_points, uint64_t* keys, uint32_t* counts,
+                         int64_t* sums, int64_t* moment_sums, int32_t* seen, int64_t max_rows, int64_t* n_rows, void* ws, size_t ws_bytes,
+                         void* stream);
+int rdm_voxel_map_import(void* map, size_t map_bytes, int64_t capacity, int channels, void* moments, size_t moments_bytes,
+                         void* observations, size_t observations_bytes, const uint64_t* keys, const uint32_t* counts, const int64_t* sums,
+                         const int64_t* moment_sums, const int32_t* seen, int64_t n_records, int64_t id_offset,
+                         const uint64_t* skipped_host, int64_t* n_rejected, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,7 @@ VOXEL_MAP_MAX_CHANNELS = 8  # = RDM_VOXEL_MAP_MAX_CHANNELS
 # rdm_voxel_map_stats' counters, in order (RDM_VOXEL_MAP_STATS of them)
 VOXEL_MAP_STATS = ('occupied', 'integrated', 'skipped_nonfinite', 'skipped_range', 'out_of_extent', 'dropped_full')
 VOXEL_MOMENTS_PLANES = 9  # = RDM_VOXEL_MOMENTS_PLANES: u_x, u_y, u_z, then u_a u_b for ab = xx, xy, xz, yy, yz, zz
+VOXEL_MOMENTS_SHIFT = 8  # = RDM_VOXEL_MOMENTS_SHIFT
 VOXEL_OBSERVATIONS_MAX_SCANS = 64  # = RDM_VOXEL_OBSERVATIONS_MAX_SCANS: scans of one rdm_voxel_map_integrate_observed call
 # rdm_voxel_map_query's labels, in the order of their codes RDM_VOXEL_POINT_*
 VOXEL_POINT_LABELS = ('nonfinite', 'range', 'extent', 'unmapped', 'transient', 'off_surface', 'static')
@@ -305,6 +306,10 @@ SIGNATURES = {
     'rdm_voxel_map_query': (c_int, [c_void, c_size, c_i64, c_int, c_void, c_size, c_void, c_size, ctypes.c_double, c_void, c_i64, c_i64,
                                     c_void, c_void, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i64, c_int, c_i64,
                                     ctypes.c_double, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
+    'rdm_voxel_map_export': (c_int, [c_void, c_size, c_i64, c_int, c_void, c_size, c_void, c_size, c_i64, c_void, c_void, c_void, c_void,
+                                     c_void, c_i64, c_void, c_void, c_size, c_void]),
+    'rdm_voxel_map_import': (c_int, [c_void, c_size, c_i64, c_int, c_void, c_size, c_void, c_size, c_void, c_void, c_void, c_void, c_void,
+                                     c_i64, c_i64, c_void, c_void, c_void]),
 }
 
 

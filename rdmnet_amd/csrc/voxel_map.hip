@@ -33,6 +33,11 @@
 // Queries (include/rdmnet_hip.h, "voxel map queries"; tests/voxel_query_restatement.py): register's per-point lookup and distance, kept
 // per point and not summed -- query_kernel, below the registration.  All three blocks are only read.
 //
+// State (include/rdmnet_hip.h, "voxel map state"; tests/voxel_state_restatement.py): export is a third emit kernel behind the extract
+// driver that writes a row's integers as they stand in its slot; import is integrate with a record in the place of a point -- the same
+// find_or_claim, the same integer atomic adds, the block's tallies through shared memory -- so a saved map reloads, and two maps of
+// different scans add, to the bits of the map built in one pass.
+//
 // Four pinned definitions are written once: the point gate (gate_sensor, gate_world; integrate, register and query), the key (pack_key,
 // key_cell; integrate, register, query, extract), the voxel Gaussian (voxel_gaussian; both extracts, register and query) and the weight
 // of a residual (voxel_precision; register and query).  `#pragma clang fp
@@ -562,6 +567,95 @@ __global__ void __launch_bounds__(kBlock) emit_observations_kernel(Observations 
     scans[r] = o.record[observed_at(slot, kObsScans)];
     first_seen[r] = o.record[observed_at(slot, kObsFirst)];
     last_seen[r] = o.record[observed_at(slot, kObsLast)];
+  }
+}
+
+// The raw state of the selected rows (rdm_voxel_map_export): what integrate added, as it stands in the slot.  Any output may be null;
+// `moments` / `records` are null exactly when their output is.
+__global__ void __launch_bounds__(kBlock) emit_state_kernel(Table t, const unsigned long long* __restrict__ moments,
+                                                            const int* __restrict__ records, long long capacity, int channels,
+                                                            const unsigned long long* __restrict__ keys, const int* __restrict__ slots,
+                                                            const unsigned long long* __restrict__ n_sel, long long max_rows,
+                                                            unsigned long long* __restrict__ out_keys, uint32_t* __restrict__ counts,
+                                                            int64_t* __restrict__ sums, int64_t* __restrict__ moment_sums,
+                                                            int32_t* __restrict__ seen, int64_t* __restrict__ n_rows) {
+  const long long stride = static_cast<long long>(gridDim.x) * kBlock;
+  const long long first = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
+  const long long m = static_cast<long long>(*n_sel);
+  if (first == 0) *n_rows = m;
+  const long long rows = m < max_rows ? m : max_rows;
+  for (long long r = first; r < rows; r += stride) {
+    const long long slot = slots[r];
+    if (out_keys != nullptr) out_keys[r] = keys[r];
+    if (counts != nullptr) counts[r] = t.counts[slot];
+    if (sums != nullptr)
+      for (int c = 0; c < channels; ++c) sums[r * channels + c] = static_cast<long long>(t.sums[c * capacity + slot]);
+    if (moment_sums != nullptr)
+      for (int k = 0; k < kPlanes; ++k) moment_sums[r * kPlanes + k] = static_cast<long long>(moments[moment_at(slot, k, capacity)]);
+    if (seen != nullptr)
+      for (int k = 0; k < kObsFields; ++k) seen[r * kObsFields + k] = records[observed_at(slot, k)];
+  }
+}
+
+// rdm_voxel_map_import: one thread per record of the layout that emit_state_kernel writes.  A record is a voxel's worth of points that
+// integrate has summed already, so it goes where a point goes -- find_or_claim, then integer atomic adds (two records of a batch may
+// hold the same key) -- with `count` in the place of 1.  `moments` / `obs.record` are null when the map lacks the block; moment_sums /
+// seen are read only where the block is there.  skipped: the four skip counters of the map the records come from, added once.
+enum { kImpOccupied = 0, kImpIntegrated, kImpDropped, kImpRejected, kImpTallies };
+struct Skipped {
+  unsigned long long v[4];  // skipped_nonfinite, skipped_range, out_of_extent, dropped_full
+};
+static_assert(kNonfinite == 2 && kDropped == 5, "Skipped follows the counters from kNonfinite on");
+
+__global__ void __launch_bounds__(kBlock) import_kernel(Table t, unsigned long long* __restrict__ moments, Observations obs,
+                                                        long long capacity, int channels, const unsigned long long* __restrict__ keys,
+                                                        const uint32_t* __restrict__ counts, const int64_t* __restrict__ sums,
+                                                        const int64_t* __restrict__ moment_sums, const int32_t* __restrict__ seen,
+                                                        long long n_records, int id_offset, Skipped skipped,
+                                                        unsigned long long* __restrict__ n_rejected) {
+  __shared__ unsigned long long tally[kImpTallies];
+  if (threadIdx.x < kImpTallies) tally[threadIdx.x] = 0ull;
+  __syncthreads();
+  const long long stride = static_cast<long long>(gridDim.x) * kBlock;
+  const long long first = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
+  if (first < 4 && skipped.v[first] != 0ull) atomicAdd(t.counters + kNonfinite + first, skipped.v[first]);
+  for (long long i = first; i < n_records; i += stride) {
+    const unsigned long long key = keys[i];
+    const uint32_t count = counts[i];
+    bool valid = (key >> 63) == 0ull && count != 0u;
+    int rec[kObsFields] = {0, 0, 0};
+    if (seen != nullptr) {
+      for (int k = 0; k < kObsFields; ++k) rec[k] = seen[i * kObsFields + k];
+      const long long scans = rec[kObsScans], lo = rec[kObsFirst], hi = rec[kObsLast];
+      valid = valid && scans >= 1 && lo >= 0 && lo <= hi && scans <= hi - lo + 1 && hi <= kMaxScanId - 1 - id_offset;
+    }
+    if (!valid) {
+      atomicAdd(&tally[kImpRejected], 1ull);
+      continue;
+    }
+    int claimed;
+    const long long slot = find_or_claim(t.keys, capacity, key, &claimed);
+    if (slot < 0) {
+      atomicAdd(&tally[kImpDropped], static_cast<unsigned long long>(count));
+      continue;
+    }
+    if (claimed) atomicAdd(&tally[kImpOccupied], 1ull);
+    atomicAdd(&tally[kImpIntegrated], static_cast<unsigned long long>(count));
+    atomicAdd(t.counts + slot, count);  // (wraps at 2^32, as a count does)
+    for (int c = 0; c < channels; ++c) atomicAdd(t.sums + c * capacity + slot, static_cast<unsigned long long>(sums[i * channels + c]));
+    if (moments != nullptr)
+      for (int k = 0; k < kPlanes; ++k)
+        atomicAdd(moments + moment_at(slot, k, capacity), static_cast<unsigned long long>(moment_sums[i * kPlanes + k]));
+    if (obs.record != nullptr) {
+      atomicAdd(obs.record + observed_at(slot, kObsScans), rec[kObsScans]);
+      atomicMin(obs.record + observed_at(slot, kObsFirst), rec[kObsFirst] + id_offset);
+      atomicMax(obs.record + observed_at(slot, kObsLast), rec[kObsLast] + id_offset);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < kImpTallies && tally[threadIdx.x] != 0ull) {
+    const int k = threadIdx.x;
+    atomicAdd(k == kImpRejected ? n_rejected : t.counters + (k == kImpDropped ? kDropped : k), tally[k]);
   }
 }
 
@@ -1315,6 +1409,66 @@ extern "C" int rdm_voxel_map_prune(const void* old_map, size_t old_bytes, int64_
   hipLaunchKernelGGL(rehash_kernel<true>, dim3(blocks_for(old_capacity)), dim3(kBlock), 0, s, a, static_cast<long long>(old_capacity), b,
                      static_cast<long long>(new_capacity), channels, oa, least_points(min_points),
                      static_cast<int>(min_scans > kMaxScanId ? kMaxScanId : min_scans));
+  return launch_status(what);
+}
+
+// ---- voxel map state ----------------------------------------------------------------------------------------------------------
+
+extern "C" int rdm_voxel_map_export(const void* map, size_t map_bytes, int64_t capacity, int channels, const void* moments,
+                                    size_t moments_bytes, const void* observations, size_t observations_bytes, int64_t min_points,
+                                    uint64_t* keys, uint32_t* counts, int64_t* sums, int64_t* moment_sums, int32_t* seen, int64_t max_rows,
+                                    int64_t* n_rows, void* ws, size_t ws_bytes, void* stream) {
+  using namespace rdm;
+  const char* what = "rdm_voxel_map_export";
+  Table t;
+  unsigned long long* m = nullptr;
+  Observations o{nullptr, nullptr};
+  if (const int rc = open_table(what, const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
+  if (moments != nullptr)
+    if (const int rc = open_moments(what, moments, moments_bytes, capacity, m)) return rc;
+  if (observations != nullptr)
+    if (const int rc = open_observations(what, observations, observations_bytes, capacity, o)) return rc;
+  RDM_REQUIRE((m != nullptr || moment_sums == nullptr) && (o.record != nullptr || seen == nullptr),
+              "%s: moment_sums needs a moments block and seen an observations block", what);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ExtractWork w;
+  if (const int rc = select_sorted(what, t, capacity, 1.0, min_points, max_rows, n_rows, true, ws, ws_bytes, s, w)) return rc;
+  hipLaunchKernelGGL(emit_state_kernel, dim3(blocks_for(max_rows)), dim3(kBlock), 0, s, t, moment_sums != nullptr ? m : nullptr,
+                     seen != nullptr ? o.record : nullptr, static_cast<long long>(capacity), channels, w.keys, w.slots, w.n_sel,
+                     static_cast<long long>(max_rows), reinterpret_cast<unsigned long long*>(keys), counts, sums, moment_sums, seen, n_rows);
+  return launch_status(what);
+}
+
+extern "C" int rdm_voxel_map_import(void* map, size_t map_bytes, int64_t capacity, int channels, void* moments, size_t moments_bytes,
+                                    void* observations, size_t observations_bytes, const uint64_t* keys, const uint32_t* counts,
+                                    const int64_t* sums, const int64_t* moment_sums, const int32_t* seen, int64_t n_records,
+                                    int64_t id_offset, const uint64_t* skipped_host, int64_t* n_rejected, void* stream) {
+  using namespace rdm;
+  const char* what = "rdm_voxel_map_import";
+  Table t;
+  unsigned long long* m = nullptr;
+  Observations o{nullptr, nullptr};
+  if (const int rc = open_table(what, map, map_bytes, capacity, channels, t)) return rc;
+  if (moments != nullptr)
+    if (const int rc = open_moments(what, moments, moments_bytes, capacity, m)) return rc;
+  if (observations != nullptr)
+    if (const int rc = open_observations(what, observations, observations_bytes, capacity, o)) return rc;
+  RDM_REQUIRE(n_records >= 0 && n_rejected != nullptr, "%s: n_records must be >= 0 and n_rejected not null", what);
+  RDM_REQUIRE(id_offset >= 0 && id_offset <= kMaxScanId, "%s: id_offset must be in [0, 2^31 - 1], got %lld", what,
+              static_cast<long long>(id_offset));
+  RDM_REQUIRE(n_records == 0 || (keys && counts && sums), "%s: null keys, counts or sums", what);
+  RDM_REQUIRE((m != nullptr) == (moment_sums != nullptr) || (n_records == 0 && moment_sums == nullptr),
+              "%s: moment_sums is required if and only if the map has a moments block", what);
+  RDM_REQUIRE((o.record != nullptr) == (seen != nullptr) || (n_records == 0 && seen == nullptr),
+              "%s: seen is required if and only if the map has an observations block", what);
+  Skipped skipped{{0ull, 0ull, 0ull, 0ull}};
+  if (skipped_host != nullptr)
+    for (int k = 0; k < 4; ++k) skipped.v[k] = skipped_host[k];
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  fill_words<unsigned long long>(reinterpret_cast<unsigned long long*>(n_rejected), 1, 0ull, s);
+  hipLaunchKernelGGL(import_kernel, dim3(blocks_for(n_records)), dim3(kBlock), 0, s, t, m, o, static_cast<long long>(capacity), channels,
+                     reinterpret_cast<const unsigned long long*>(keys), counts, sums, moment_sums, seen, static_cast<long long>(n_records),
+                     static_cast<int>(id_offset), skipped, reinterpret_cast<unsigned long long*>(n_rejected));
   return launch_status(what);
 }
 

@@ -800,7 +800,9 @@ class VoxelMap:
     observations=True keeps, in a third block (rdm_voxel_observations_*), in how many distinct scans every voxel was seen and the first and
     the last of them -- `extract_observations` -- and gives the map without the voxels seen in too few scans -- `pruned`: a moving
     object is in a voxel in one scan, a wall in many.  The scans are numbered from 0 as `integrate` is given them, empty ones included
-    (`num_scans`: the next id), so a scan must come whole in one `integrate` call.  Again `extract` and `stats` are the same bytes."""
+    (`num_scans`: the next id), so a scan must come whole in one `integrate` call.  Again `extract` and `stats` are the same bytes.
+    The integers are all a map is: `state` reads them, `from_state` / `save` / `load` rebuild the map from them bit for bit at any
+    capacity, and `merge` adds the map of other scans into this one (rdm_voxel_map_export / rdm_voxel_map_import)."""
 
     def __init__(self, voxel, channels=4, capacity=1 << 20, device='cuda', moments=False, observations=False):
         voxel, channels, capacity = float(voxel), int(channels), int(capacity)
@@ -1175,6 +1177,219 @@ class VoxelMap:
         for t in clouds:
             edges.append(edges[-1] + int(t.shape[0]))
         return [t[keep[a:b]] for t, a, b in zip(clouds, edges, edges[1:])], res.tallies
+
+    # ---- the state: save, load, merge (rdm_voxel_map_export / rdm_voxel_map_import; DESIGN.md section 7, "voxel map state") ----
+
+    def state(self, min_points=1):
+        """The raw state of the voxels with at least min_points points, row-aligned with extract(min_points) (rdm_voxel_map_export) ->
+        dict: device tensors keys uint64 [M] (ascending), counts uint32 [M], sums int64 [M, C] and, where the map has the blocks,
+        moments int64 [M, 9] and observations int32 [M, 3] = {scans, first, last}; host values voxel, channels, num_scans and counters
+        (what `stats` returns).  These integers are all a map is: `from_state` rebuilds it from them at any capacity, bit for bit.
+        Two read-backs (sizes)."""
+        return self._export(min_points)
+
+    def _export(self, min_points, moments=True, observations=True):
+        """`state`, without a block that the caller leaves out."""
+        L, dev = _lib.lib(), self.device
+        counters = self.stats()
+        rows = counters['occupied']
+        R = max(rows, 1)
+        out = dict(keys=torch.empty((R,), dtype=torch.uint64, device=dev), counts=torch.empty((R,), dtype=torch.uint32, device=dev),
+                   sums=torch.empty((R, self.channels), dtype=torch.int64, device=dev))
+        if self.moments and moments:
+            out['moments'] = torch.empty((R, _lib.VOXEL_MOMENTS_PLANES), dtype=torch.int64, device=dev)
+        if self.observations and observations:
+            out['observations'] = torch.empty((R, 3), dtype=torch.int32, device=dev)
+        n_rows = torch.zeros((1,), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            ws = scratch(dev, L.rdm_voxel_map_extract_workspace_bytes(self.capacity))
+            _lib.check(L.rdm_voxel_map_export(*self._head(), *self._blocks(moments, observations), int(min_points), out['keys'].data_ptr(),
+                                              out['counts'].data_ptr(), out['sums'].data_ptr(), _lib.ptr(out.get('moments')),
+                                              _lib.ptr(out.get('observations')), rows, n_rows.data_ptr(), ws.data_ptr(), ws.numel(),
+                                              _lib.stream_ptr()), 'rdm_voxel_map_export')
+        m = int(n_rows.item())
+        out = {k: t[:m] for k, t in out.items()}
+        out.update(voxel=self.voxel, channels=self.channels, num_scans=self.num_scans, counters=counters)
+        return out
+
+    def _blocks(self, moments=True, observations=True):
+        """(moments, moments_bytes, observations, observations_bytes) as the state calls take them: zeros for a block that the map
+        lacks or that the caller leaves out."""
+        mom = (self._mom.data_ptr(), self._mom.numel()) if self.moments and moments else (0, 0)
+        obs = (self._obs.data_ptr(), self._obs.numel()) if self.observations and observations else (0, 0)
+        return mom + obs
+
+    def _import(self, what, state, id_offset, skipped):
+        """Adds the records of `state` (device tensors of this map's device) through rdm_voxel_map_import; raises if one was rejected.
+        The caller has reserved the room.  One read-back (the rejected records)."""
+        rows = int(state['keys'].shape[0])
+        host = (ctypes.c_uint64 * 4)(*(int(v) for v in skipped))
+        n_rejected = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().rdm_voxel_map_import(
+                *self._head(), *self._blocks(), state['keys'].data_ptr(), state['counts'].data_ptr(), state['sums'].data_ptr(),
+                state['moments'].data_ptr() if self.moments else 0, state['observations'].data_ptr() if self.observations else 0, rows,
+                int(id_offset), ctypes.addressof(host), n_rejected.data_ptr(), _lib.stream_ptr()), 'rdm_voxel_map_import')
+        bad = int(n_rejected.item())
+        if bad:
+            raise ValueError(f'VoxelMap.{what}: {bad} of {rows} records are not records of a voxel map (a key with bit 63 set, a count '
+                             'of 0, or observations that no set of scans gives)')
+
+    @classmethod
+    def from_state(cls, state, device='cuda', capacity=None, moments=None, observations=None):
+        """A map from what `state` or `read_state` returned (device tensors, host tensors or numpy arrays).  moments / observations
+        None: as the state has them; True for a block that the state lacks is a ValueError; False drops the block.  capacity None:
+        the smallest power of two >= max(64, 2 rows).  `extract`, `extract_moments`, `extract_observations`, `stats`, `num_scans`,
+        `register` and `query` of the result are, bit for bit, those of the map the state was taken from (with min_points = 1)."""
+        import numpy as np
+        have = {k: state.get(k) is not None for k in ('moments', 'observations')}
+        want = {}
+        for k, asked in (('moments', moments), ('observations', observations)):
+            if asked and not have[k]:
+                raise ValueError(f'VoxelMap.from_state: {k}=True, but the state holds no {k}')
+            want[k] = have[k] if asked is None else bool(asked)
+        channels = int(state['channels'])
+        rows = int(state['keys'].shape[0])
+        shapes = dict(keys=(torch.uint64, (rows,)), counts=(torch.uint32, (rows,)), sums=(torch.int64, (rows, channels)),
+                      moments=(torch.int64, (rows, _lib.VOXEL_MOMENTS_PLANES)), observations=(torch.int32, (rows, 3)))
+        if capacity is None:
+            capacity = 64
+            while capacity < 2 * rows:
+                capacity *= 2
+        out = cls(float(state['voxel']), channels, int(capacity), device, want['moments'], want['observations'])
+        dev_state = {}
+        for k, (dtype, shape) in shapes.items():
+            if k in want and not want[k]:
+                continue
+            t = state[k]
+            t = torch.from_numpy(np.ascontiguousarray(t)) if isinstance(t, np.ndarray) else t
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape:
+                raise ValueError(f'VoxelMap.from_state: {k} must be {dtype} {list(shape)}, got '
+                                 f'{getattr(t, "dtype", type(t).__name__)} {list(getattr(t, "shape", ()))}')
+            dev_state[k] = t.to(out.device).contiguous()
+        counters = state['counters']
+        if not isinstance(counters, dict):
+            counters = dict(zip(_lib.VOXEL_MAP_STATS, (int(v) for v in counters)))
+        out._reserve(rows)
+        out._import('from_state', dev_state, 0, [counters[k] for k in _lib.VOXEL_MAP_STATS[2:]])
+        out.num_scans = int(state['num_scans'])
+        return out
+
+    def save(self, path):
+        """The whole map into one .npz (`write_state`): `VoxelMap.load` gives it back bit for bit.  -> path."""
+        write_state(path, self.state())
+        return path
+
+    @classmethod
+    def load(cls, path, device='cuda', capacity=None, moments=None, observations=None):
+        """The map that `save` wrote to `path`: from_state(read_state(path), ...)."""
+        return cls.from_state(read_state(path), device, capacity, moments, observations)
+
+    def merge(self, other, id_offset=None):
+        """Adds the map `other` of OTHER scans into this one: afterwards this map is, bit for bit, the map of the scans of both --
+        every sum, all six counters, and with observations the scans of `other` numbered on from id_offset (None: num_scans; then
+        num_scans = max(num_scans, id_offset + other.num_scans)).  Both maps need the same voxel, channels and device, and `other` the
+        blocks that this map keeps (a block that only `other` has is left out).  `other` is exported on the device and imported
+        here (rdm_voxel_map_export / rdm_voxel_map_import): one record path.  `other` is only read.  -> self."""
+        if not isinstance(other, VoxelMap):
+            raise ValueError('VoxelMap.merge: other must be a VoxelMap')
+        if other.voxel != self.voxel:
+            raise ValueError(f'VoxelMap.merge: voxel differs ({other.voxel!r} against {self.voxel!r}); maps add only on the same grid')
+        if other.channels != self.channels:
+            raise ValueError(f'VoxelMap.merge: channels differ ({other.channels} against {self.channels})')
+        if other.device != self.device:
+            raise ValueError(f'VoxelMap.merge: device differs ({other.device} against {self.device})')
+        for k in ('moments', 'observations'):
+            if getattr(self, k) and not getattr(other, k):
+                raise ValueError(f'VoxelMap.merge: other has no {k}, which this map keeps')
+        id_offset = self.num_scans if id_offset is None else int(id_offset)
+        if id_offset < 0:
+            raise ValueError(f'VoxelMap.merge: id_offset must be >= 0, got {id_offset}')
+        if id_offset + other.num_scans > 2 ** 31 - 1:
+            raise ValueError(f'VoxelMap.merge: ids overflow ({id_offset} + {other.num_scans} scans; ids lie in [0, 2^31 - 1))')
+        st = other._export(1, self.moments, self.observations)
+        rows, counters = int(st['keys'].shape[0]), st['counters']
+        self._reserve(rows)
+        self._import('merge', st, id_offset, [counters[k] for k in _lib.VOXEL_MAP_STATS[2:]])
+        self.num_scans = max(self.num_scans, id_offset + other.num_scans)
+        return self
+
+
+_STATE_FORMAT, _STATE_VERSION = 'rdmnet_amd.voxel_map', 1
+_STATE_ARRAYS = dict(keys=('uint64', ()), counts=('uint32', ()), sums=('int64', (None,)), moments=('int64', (_lib.VOXEL_MOMENTS_PLANES,)),
+                     observations=('int32', (3,)))
+
+
+def write_state(path, state):
+    """What VoxelMap.state returned (tensors or numpy arrays) into the one .npz file `path`: format = 'rdmnet_amd.voxel_map', version
+    = 1, voxel (float64), channels, frac_bits, moments_shift, num_scans, counters (uint64 [6], VOXEL_MAP_STATS' order) and the
+    arrays keys, counts, sums and, where the state has them, moments and observations.  No GPU is needed."""
+    import numpy as np
+    counters = state['counters']
+    if isinstance(counters, dict):
+        counters = [counters[k] for k in _lib.VOXEL_MAP_STATS]
+    arrays = {}
+    for k, (dtype, _) in _STATE_ARRAYS.items():
+        t = state.get(k)
+        if t is not None:
+            arrays[k] = np.ascontiguousarray((t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(dtype, copy=False))
+    with open(path, 'wb') as f:
+        np.savez(f, format=np.array(_STATE_FORMAT), version=np.int64(_STATE_VERSION), voxel=np.float64(state['voxel']),
+                 channels=np.int64(state['channels']), frac_bits=np.int64(_lib.VOXEL_MAP_FRAC_BITS),
+                 moments_shift=np.int64(_lib.VOXEL_MOMENTS_SHIFT), num_scans=np.int64(state['num_scans']),
+                 counters=np.asarray(counters, np.uint64), **arrays)
+
+
+def read_state(path):
+    """The state that write_state wrote to `path` -> dict of numpy arrays and host values as VoxelMap.state's (counters: a dict), read
+    with allow_pickle=False and checked: a file that is not such a state, or whose records no map can hold, is a ValueError that says
+    what is wrong.  No GPU is needed."""
+    import numpy as np
+
+    def bad(why):
+        return ValueError(f'{path}: {why}')
+
+    with np.load(path, allow_pickle=False) as z:
+        data = {k: z[k] for k in z.files}
+    for k in ('format', 'version', 'voxel', 'channels', 'frac_bits', 'moments_shift', 'num_scans', 'counters', 'keys', 'counts', 'sums'):
+        if k not in data:
+            raise bad(f"not a voxel map state: no '{k}'")
+    if data['format'].shape != () or str(data['format']) != _STATE_FORMAT:
+        raise bad(f"not a voxel map state: format {str(data['format'])!r}, expected {_STATE_FORMAT!r}")
+    if int(data['version']) != _STATE_VERSION:
+        raise bad(f"version {int(data['version'])}, this library reads version {_STATE_VERSION}")
+    if int(data['frac_bits']) != _lib.VOXEL_MAP_FRAC_BITS:
+        raise bad(f"frac_bits {int(data['frac_bits'])}, the library has {_lib.VOXEL_MAP_FRAC_BITS}")
+    if int(data['moments_shift']) != _lib.VOXEL_MOMENTS_SHIFT:
+        raise bad(f"moments_shift {int(data['moments_shift'])}, the library has {_lib.VOXEL_MOMENTS_SHIFT}")
+    voxel, channels, num_scans = float(data['voxel']), int(data['channels']), int(data['num_scans'])
+    if not (voxel > 0 and voxel < float('inf')) or not 3 <= channels <= _lib.VOXEL_MAP_MAX_CHANNELS or not 0 <= num_scans <= 2 ** 31 - 1:
+        raise bad(f'voxel {voxel}, channels {channels}, num_scans {num_scans}: not those of a voxel map')
+    if data['counters'].dtype != np.uint64 or data['counters'].shape != (len(_lib.VOXEL_MAP_STATS),):
+        raise bad(f"counters must be uint64 [{len(_lib.VOXEL_MAP_STATS)}], got {data['counters'].dtype} {list(data['counters'].shape)}")
+    rows = data['keys'].shape[0] if data['keys'].ndim == 1 else -1
+    out = {}
+    for k, (dtype, tail) in _STATE_ARRAYS.items():
+        if k not in data:
+            continue
+        shape = (rows,) + tuple(channels if w is None else w for w in tail)
+        if data[k].dtype != np.dtype(dtype) or data[k].shape != shape:
+            raise bad(f'{k} must be {dtype} {list(shape) if rows >= 0 else "[M]"}, got {data[k].dtype} {list(data[k].shape)}')
+        out[k] = data[k]
+    keys = out['keys']
+    if (keys >> np.uint64(63)).any() or not (keys[1:] > keys[:-1]).all():
+        raise bad('keys must ascend strictly with bit 63 clear')
+    if not (out['counts'] >= 1).all():
+        raise bad('counts must be >= 1')
+    if 'moments' in out and not (out['moments'] >= 0).all():
+        raise bad('moments must be >= 0 (sums of non-negative local coordinates)')
+    if 'observations' in out:
+        scans, first, last = (out['observations'][:, k].astype(np.int64) for k in range(3))
+        if not ((1 <= scans) & (scans <= last - first + 1) & (0 <= first) & (first <= last) & (last <= 2 ** 31 - 2)).all():
+            raise bad('observations must hold 1 <= scans <= last - first + 1 and 0 <= first <= last <= 2^31 - 2')
+    out.update(voxel=voxel, channels=channels, num_scans=num_scans,
+               counters=dict(zip(_lib.VOXEL_MAP_STATS, (int(v) for v in data['counters']))))
+    return out
 
 
 class MapRegistrationResult:

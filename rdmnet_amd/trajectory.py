@@ -7,7 +7,8 @@
                                    [--map-min-scans 1]
                                    [--map-refine [--map-refine-sigma 0.02] [--map-refine-neighbors {1,7}] [--map-refine-iterations 30]
                                     [--map-refine-min-scans 1]]
-                                   [--map-clean [--map-clean-max-d2 D] [--map-clean-sigma 0.02] [--map-clean-neighbors {1,7}]]]
+                                   [--map-clean [--map-clean-max-d2 D] [--map-clean-sigma 0.02] [--map-clean-neighbors {1,7}]]
+                                   [--map-save] [--map-prior FILE [--map-localize]]]
 
 reads the `{seq}_{src}_{ref}.npz` pair files that `python -m rdmnet_amd.infer` wrote into DIR (ordered and filtered as
 `python -m rdmnet_amd.eval` reads them) and, per sequence, chains the pair poses into a trajectory as
@@ -36,7 +37,12 @@ that pruned map instead of the full one.  With --map-clean (and --map-min-scans 
 point of every scan is judged by each variant's full map, before that prune (`clean_scans`, `ops.VoxelMap.query`): the scans are written
 to `{seq}_{variant}_clean/` under their own names without the points that have no voxel, whose voxel was seen in fewer than N scans or that
 lie further than D (squared Mahalanobis distance; the map then keeps second moments) from their voxel's Gaussian, and a `clean:` line after
-the map's lines says what was dropped."""
+the map's lines says what was dropped.  With --map-save every variant's full map, before that prune, is also written as
+`{seq}_{variant}_map_state.npz` (`ops.VoxelMap.save`: the integers the map consists of; `ops.VoxelMap.load` gives the map back bit for
+bit).  --map-prior FILE names such a file in the trajectory's world frame -- an earlier --map-save of the same sequence is one -- and
+with it --map-clean judges the scans by that prior map instead of their own (--map-min-scans then counts the prior's scans; a scan that
+is not in the map is what the distance test is for), and --map-localize registers every frame, independently, against the fixed prior
+(`localize_against_map`): a variant `localized` with its own error, pose file and map lines."""
 import argparse
 import math
 import os
@@ -296,10 +302,18 @@ def clean_scans(paths, poses, vmap, out_dir, *, min_scans=MAP_DEFAULTS['min_scan
     return tallies
 
 
-def clean_line(seq, what, tallies, min_scans, max_d2):
+def prior_words(prior):
+    """prior: dict(name, voxels, voxel, scans, moments) of a --map-prior map, as the lines name it."""
+    return (f"the prior map {prior['name']} ({prior['voxels']} voxels at {prior['voxel']:g} m, {prior['scans']} scans"
+            + ('' if prior['moments'] else ', no moments: Sigma = sigma^2 I') + ')')
+
+
+def clean_line(seq, what, tallies, min_scans, max_d2, prior=None):
+    """prior: None when the scans were judged by their own map, else what prior_words takes."""
     t = np.asarray(tallies, np.int64).reshape(-1, 8).sum(0)
     return (f'seq {seq} {what} clean: {t[6]} of {t[:7].sum()} points kept in {len(tallies)} scans, dropped: {t[3]} unmapped, '
-            f'{t[4]} transient (< {min_scans} scans), {t[5]} off surface (d2 > {max_d2:g}), {t[:3].sum()} gated')
+            f'{t[4]} transient (< {min_scans} scans), {t[5]} off surface (d2 > {max_d2:g}), {t[:3].sum()} gated'
+            + ('' if prior is None else ', judged by ' + prior_words(prior)))
 
 
 def refine_against_map(paths, poses, voxel=MAP_DEFAULTS['voxel'], channels=None, min_range=0.0, max_range=math.inf,
@@ -359,6 +373,59 @@ def refine_line(seq, stats):
             f"{stats['correspondences'].sum() / moved:.0f} correspondences per frame, {stats['degenerate']} degenerate frames")
 
 
+def localize_against_map(paths, poses, vmap, *, sigma=REFINE_DEFAULTS['sigma'], neighbors=REFINE_DEFAULTS['neighbors'],
+                         max_iteration=REFINE_DEFAULTS['iterations'], min_points=REFINE_DEFAULTS['min_points'], min_range=0.0,
+                         max_range=math.inf, batch=MAP_DEFAULTS['batch']):
+    """Every scan of `paths` (as build_map reads them) registered from its pose in `poses` ([n, 4, 4]) against the fixed map `vmap` (an
+    ops.VoxelMap with moments, such as ops.VoxelMap.load gives; ops.VoxelMap.register).  The frames are independent: `batch` scans are
+    one register call, and nothing is integrated -- the map is only read.  A degenerate frame (status 2) keeps its pose.  -> (localized
+    float64 [n, 4, 4], dict(frames, iterations [n], correspondences [n], status [n], degenerate))."""
+    paths = list(paths)
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+    if len(paths) != len(poses):
+        raise ValueError(f'localize_against_map: {len(paths)} scans and {len(poses)} poses')
+    if int(batch) < 1:
+        raise ValueError(f'localize_against_map: batch must be >= 1, got {batch}')
+    if not vmap.moments:
+        raise ValueError('localize_against_map: the map has no moments')
+    for path in paths:
+        if not osp.isfile(path):
+            raise TrajectoryError(f'{path}: no such scan file')
+    import torch
+    n = len(paths)
+    localized = poses.copy()
+    iterations, corr, status = np.zeros(n, np.int64), np.zeros(n, np.int64), np.full(n, -1, np.int64)
+    for (lo, hi), (points, offsets) in _read_batches(paths, batch):
+        if points.shape[1] < vmap.channels:
+            raise TrajectoryError(f'{paths[lo]}: {points.shape[1]} columns, the map has {vmap.channels} channels')
+        res = vmap.register((torch.from_numpy(points).to(vmap.device), torch.from_numpy(offsets)), poses[lo:hi], sigma=sigma,
+                            min_points=min_points, neighbors=neighbors, max_iteration=max_iteration, min_range=min_range,
+                            max_range=max_range)
+        iterations[lo:hi], corr[lo:hi], status[lo:hi] = torch.stack([res.iterations, res.num_correspondences, res.status]).cpu().numpy()
+        moved = status[lo:hi] != 2
+        localized[lo:hi][moved] = res.transformations.cpu().numpy()[moved]
+    return localized, dict(frames=n, iterations=iterations, correspondences=corr, status=status, degenerate=int((status == 2).sum()))
+
+
+def localize_line(seq, stats, prior):
+    frames = max(stats['frames'], 1)
+    return (f"seq {seq} localized against {prior_words(prior)}: {stats['frames']} frames, {stats['iterations'].sum() / frames:.2f} "
+            f"iterations and {stats['correspondences'].sum() / frames:.0f} correspondences per frame, {stats['degenerate']} degenerate frames")
+
+
+def load_prior(args):
+    """(the ops.VoxelMap of --map-prior, what prior_words takes), loaded once per run from the state that map_paths read; (None, None)
+    without the flag."""
+    if getattr(args, 'map_prior', None) is None:
+        return None, None
+    if getattr(args, 'map_prior_loaded', None) is None:
+        from . import ops
+        vmap = ops.VoxelMap.from_state(args.map_prior_state)
+        args.map_prior_loaded = (vmap, dict(name=osp.basename(args.map_prior), voxels=len(args.map_prior_state['keys']), voxel=vmap.voxel,
+                                            scans=vmap.num_scans, moments=vmap.moments))
+    return args.map_prior_loaded
+
+
 def write_map(args, seq, what, paths, poses, emit, vmap=None):
     """vmap: the map of these scans under these poses when the caller has built it already (the refinement's)."""
     lo, hi = args.map_range if args.map_range else (0.0, math.inf)
@@ -367,11 +434,14 @@ def write_map(args, seq, what, paths, poses, emit, vmap=None):
     clean = bool(getattr(args, 'map_clean', False))
     max_d2 = getattr(args, 'map_clean_max_d2', None) if clean else None
     max_d2 = CLEAN_DEFAULTS['max_d2'] if max_d2 is None else max_d2
+    judge, prior = load_prior(args) if clean else (None, None)
     if vmap is None:
         vmap = build_map(paths, poses, voxel=args.map_voxel, min_range=lo, max_range=hi, batch=args.map_batch,
-                         moments=sharpness or math.isfinite(max_d2), observations=min_scans > 1)
-    if clean:  # the scans against the full map
-        tallies = clean_scans(paths, poses, vmap, osp.join(args.out, f'{seq}_{what}_clean'), min_scans=min_scans, max_d2=max_d2,
+                         moments=sharpness or (math.isfinite(max_d2) and judge is None), observations=min_scans > 1)
+    if getattr(args, 'map_save', False):  # the full map
+        vmap.save(osp.join(args.out, f'{seq}_{what}_map_state.npz'))
+    if clean:  # the scans against the full map, or against the prior
+        tallies = clean_scans(paths, poses, vmap if judge is None else judge, osp.join(args.out, f'{seq}_{what}_clean'), min_scans=min_scans, max_d2=max_d2,
                               sigma=args.map_clean_sigma, min_points=args.map_min_points, neighbors=args.map_clean_neighbors,
                               min_range=lo, max_range=hi, batch=args.map_batch)
     if min_scans > 1:  # everything below describes the pruned map
@@ -386,22 +456,29 @@ def write_map(args, seq, what, paths, poses, emit, vmap=None):
     if sharpness:
         emit(sharpness_line(seq, what, args.map_sharpness_min_points, vmap.sharpness(args.map_sharpness_min_points)))
     if clean:
-        emit(clean_line(seq, what, tallies, min_scans, max_d2))
+        emit(clean_line(seq, what, tallies, min_scans, max_d2, prior))
 
 
 def map_paths(args, seqs):
     """{seq: the scan file of every chain frame}, after the checks that need no GPU."""
-    refine = bool(getattr(args, 'map_refine', False))
+    refine, localize = bool(getattr(args, 'map_refine', False)), bool(getattr(args, 'map_localize', False))
+    prior = getattr(args, 'map_prior', None)
+    if getattr(args, 'map_save', False) and not (getattr(args, 'map_scans', None) and args.out):
+        raise TrajectoryError('--map-save needs --map-scans and --out (the maps of the scans are written to --out)')
+    if localize and not (prior and getattr(args, 'map_scans', None) and args.out):
+        raise TrajectoryError('--map-localize needs --map-prior, --map-scans and --out (the frames are registered against the prior map)')
+    if prior and not (localize or getattr(args, 'map_clean', False)):
+        raise TrajectoryError('--map-prior needs --map-clean or --map-localize (the prior judges the scans or localises the frames)')
     if refine and not (getattr(args, 'map_scans', None) and args.out):
         raise TrajectoryError('--map-refine needs --map-scans and --out (the frames are registered against the map of the scans)')
     if not refine:
         for flag, key in (('--map-refine-sigma', 'sigma'), ('--map-refine-neighbors', 'neighbors'), ('--map-refine-iterations', 'iterations'),
                           ('--map-refine-min-scans', 'min_scans')):
-            if getattr(args, 'map_refine_' + key, None) not in (None, REFINE_DEFAULTS[key]):
-                raise TrajectoryError(f'{flag} needs --map-refine')
-    elif not (args.map_refine_sigma > 0 and math.isfinite(args.map_refine_sigma)) or args.map_refine_iterations < 0:
+            if getattr(args, 'map_refine_' + key, None) not in (None, REFINE_DEFAULTS[key]) and not (localize and key != 'min_scans'):
+                raise TrajectoryError(f'{flag} needs --map-refine' + ('' if key == 'min_scans' else ' (or --map-localize)'))
+    if (refine or localize) and (not (args.map_refine_sigma > 0 and math.isfinite(args.map_refine_sigma)) or args.map_refine_iterations < 0):
         raise TrajectoryError('--map-refine-sigma must be > 0 and --map-refine-iterations >= 0')
-    elif getattr(args, 'map_refine_min_scans', REFINE_DEFAULTS['min_scans']) < 1:
+    if refine and getattr(args, 'map_refine_min_scans', REFINE_DEFAULTS['min_scans']) < 1:
         raise TrajectoryError(f'--map-refine-min-scans must be >= 1, got {args.map_refine_min_scans}')
     if not getattr(args, 'map_clean', False):
         for flag, key in (('--map-clean-max-d2', 'max_d2'), ('--map-clean-sigma', 'sigma'), ('--map-clean-neighbors', 'neighbors')):
@@ -422,6 +499,21 @@ def map_paths(args, seqs):
         if getattr(args, 'map_sharpness_min_points', None) not in (None, MAP_DEFAULTS['sharpness_min_points']):
             raise TrajectoryError('--map-sharpness-min-points needs --map-scans and --map-sharpness')
         return None
+    if prior:
+        from . import ops
+        try:
+            args.map_prior_state, args.map_prior_loaded = ops.read_state(prior), None
+        except FileNotFoundError:
+            raise TrajectoryError(f'--map-prior {prior}: no such file')
+        except Exception as e:  # (not a zip archive, not a state, records that no map holds: read_state says which)
+            raise TrajectoryError(f'--map-prior {prior}: cannot be read as a voxel map state ({e})')
+        if localize and args.map_prior_state.get('moments') is None:
+            raise TrajectoryError(f'--map-localize needs a prior with moments; --map-prior {prior} has none (save it from a run with '
+                                  '--map-sharpness or a finite --map-clean-max-d2)')
+        if getattr(args, 'map_clean', False) and getattr(args, 'map_min_scans', MAP_DEFAULTS['min_scans']) >= 2 \
+                and args.map_prior_state.get('observations') is None:
+            raise TrajectoryError(f'--map-min-scans {args.map_min_scans} with --map-clean counts the scans of the prior; --map-prior {prior} '
+                                  'has no observations (save it from a run with --map-min-scans N >= 2)')
     if getattr(args, 'map_sharpness', False) and args.map_sharpness_min_points < 2:
         raise TrajectoryError(f'--map-sharpness-min-points must be >= 2 (a covariance needs two points), got {args.map_sharpness_min_points}')
     if getattr(args, 'map_min_scans', MAP_DEFAULTS['min_scans']) < 1:
@@ -475,10 +567,24 @@ def run(args, emit=print):
         write_kitti_poses(osp.join(args.out, f'{seq}_refined.txt'), refined)
         write_map(args, seq, 'refined', scans[seq], refined, emit, vmap=vmap)
 
+    def localize(seq, base):
+        lo, hi = args.map_range if args.map_range else (0.0, math.inf)
+        vmap, prior = load_prior(args)
+        localized, stats = localize_against_map(scans[seq], base, vmap, sigma=args.map_refine_sigma, neighbors=args.map_refine_neighbors,
+                                                max_iteration=args.map_refine_iterations, min_range=lo, max_range=hi,
+                                                batch=args.map_batch)
+        if seq in gts:
+            emit(report_line(seq, 'localized', absolute_trajectory_error(localized[1:], gts[seq])))
+        emit(localize_line(seq, stats, prior))
+        write_kitti_poses(osp.join(args.out, f'{seq}_localized.txt'), localized)
+        write_map(args, seq, 'localized', scans[seq], localized, emit)
+
     if not args.optimize:
-        if getattr(args, 'map_refine', False):
-            for seq in seqs:
+        for seq in seqs:
+            if getattr(args, 'map_refine', False):
                 refine(seq, graphs[seq][0])
+            if getattr(args, 'map_localize', False):
+                localize(seq, graphs[seq][0])
         return None
     if not graphs:
         raise TrajectoryError(f'{args.features_root}: no pair files to optimise')
@@ -506,6 +612,8 @@ def run(args, emit=print):
             write_map(args, seq, 'optimized', scans[seq], nodes[noff[g]:noff[g + 1]], emit)
         if getattr(args, 'map_refine', False):
             refine(seq, nodes[noff[g]:noff[g + 1]])
+        if getattr(args, 'map_localize', False):
+            localize(seq, nodes[noff[g]:noff[g + 1]])
     return res
 
 
@@ -562,6 +670,16 @@ def make_parser():
                     help='the noise of a scan point in metres, added to every voxel covariance')
     ap.add_argument('--map-clean-neighbors', type=int, choices=(1, 7), default=CLEAN_DEFAULTS['neighbors'],
                     help='a point is judged by its own voxel (1) or by the best of it and its six face neighbours (7)')
+    ap.add_argument('--map-save', action='store_true',
+                    help="also write every variant's full map, before the --map-min-scans prune, to --out as {seq}_{variant}_map_state.npz: "
+                         'the integers the map consists of, from which it reloads bit for bit (needs --map-scans)')
+    ap.add_argument('--map-prior', default=None, metavar='FILE',
+                    help='a saved map state in the world frame of the trajectory, such as an earlier --map-save of the same sequence: with '
+                         '--map-clean the scans are judged by it instead of by their own map (--map-min-scans then counts its scans)')
+    ap.add_argument('--map-localize', action='store_true',
+                    help='register every frame, independently, against the fixed --map-prior (which needs moments): a variant `localized`, '
+                         'from the optimised poses with --optimize, else the chained; --map-batch frames per call, sigma, neighbours and '
+                         'iterations from the --map-refine-* options (needs --map-prior, --map-scans and --out)')
     return ap
 
 

@@ -1,7 +1,7 @@
 """Times the voxel map (ops.VoxelMap) on synthetic scans along a synthetic drive.
 
   python tools/map_bench.py [--frames 256] [--points 120000 | 18000] [--reps 3] [--batch 64] [--voxel 0.3] [--cpu] [--cpu-frames 8]
-                              [--moments] [--observations] [--register] [--query] [--digest]
+                              [--moments] [--observations] [--register] [--query] [--merge] [--digest]
 With --digest (and nothing else): no timing, one sha1 line per output of the voxel map on the bundled scans (see digest()), for
 comparing the bits of two builds of the library.  Otherwise prints one JSON line per case:
   * integrate: --frames scans of --points points (120 000: a raw scan; 18 000: a down-sampled one), xyz + intensity, integrated in
@@ -35,6 +35,11 @@ comparing the bits of two builds of the library.  Otherwise prints one JSON line
     the whole call between two device events (a query: the kernel, the zeroing of the tallies and the upload of poses and offsets),
     ten calls a window; with --cpu also the
     seconds of tests/voxel_query_restatement.py on the first --cpu-frames scans and whether the GPU's integer outputs equal it;
+  * with --merge (and nothing else of the above): the state calls behind save, load and merge on a map with moments and observations of
+    min(--frames, 64) scans: ms and records/s of rdm_voxel_map_export (select, sort, emit of the raw integers), ms and records/s of
+    rdm_voxel_map_import of those records into an empty map of the same capacity (C + 13 integer atomics a record; the reset before
+    it is timed alone and taken out), and beside them the rehash of the same map with both blocks into a table of the same capacity,
+    which moves the same slots with plain stores;
   * with --cpu: the NumPy restatement (tests/voxel_map_restatement.py) on the first --cpu-frames scans, its points/s, and whether the
     GPU's map of the same scans equals it bit for bit."""
 import argparse
@@ -255,6 +260,64 @@ def query_cases(a):
     return 0
 
 
+def merge_cases(a):
+    """--merge: the two state calls on a map with moments and observations of min(--frames, 64) scans, through the raw calls into
+    preallocated arrays (no growth, no read-back inside the timing), and the rehash of the same map as the yardstick."""
+    import torch
+    from rdmnet_amd import _lib, ops
+    L, C = _lib.lib(), 4
+    frames = min(a.frames, 64)
+    cloud, poses = synthetic_scans(frames, a.points), drive(frames)
+    capacity = min(1 << max(int(np.ceil(np.log2(2 * frames * a.points))), 6), 1 << 28)
+    vmap = ops.VoxelMap(a.voxel, channels=C, capacity=capacity, moments=True, observations=True)
+    vmap.integrate((cloud, (torch.arange(frames + 1, dtype=torch.int64) * a.points).cuda()), poses)
+    st = vmap.stats()
+    rows = st['occupied']
+    assert vmap.capacity == capacity and st['dropped_full'] == 0
+    rec = dict(keys=torch.empty((rows,), dtype=torch.uint64, device='cuda'), counts=torch.empty((rows,), dtype=torch.uint32, device='cuda'),
+               sums=torch.empty((rows, C), dtype=torch.int64, device='cuda'), moments=torch.empty((rows, 9), dtype=torch.int64, device='cuda'),
+               seen=torch.empty((rows, 3), dtype=torch.int32, device='cuda'))
+    n_rows = torch.zeros((1,), dtype=torch.int64, device='cuda')
+    ws = torch.empty((L.rdm_voxel_map_extract_workspace_bytes(capacity),), dtype=torch.uint8, device='cuda')
+    ptrs = [rec[k].data_ptr() for k in ('keys', 'counts', 'sums', 'moments', 'seen')]
+    ms_export, _ = timed(lambda: _lib.check(L.rdm_voxel_map_export(*vmap._head(), *vmap._blocks(), 1, *ptrs, rows, n_rows.data_ptr(),
+                                                                  ws.data_ptr(), ws.numel(), _lib.stream_ptr()), 'export'), a.reps)
+    assert int(n_rows.item()) == rows
+    record_bytes = 8 + 4 + 8 * C + 72 + 12
+    print(json.dumps({'case': 'export', 'capacity': capacity, 'voxels': rows, 'ms': round(ms_export, 3),
+                      'records_per_s': round(rows / ms_export * 1e3), 'bytes_per_record': record_bytes}))
+    into = ops.VoxelMap(a.voxel, channels=C, capacity=capacity, moments=True, observations=True)
+    n_rejected = torch.zeros((1,), dtype=torch.int64, device='cuda')
+
+    def load():
+        into.reset()
+        _lib.check(L.rdm_voxel_map_import(*into._head(), *into._blocks(), *ptrs, rows, 0, 0, n_rejected.data_ptr(), _lib.stream_ptr()),
+                   'import')
+
+    ms_reset, _ = timed(into.reset, a.reps)
+    ms_all, _ = timed(load, a.reps)
+    ms_import = ms_all - ms_reset
+    after = into.stats()
+    assert int(n_rejected.item()) == 0 and (after['occupied'], after['integrated']) == (rows, st['integrated'])
+    atomics = C + 13  # the count, C sums, nine moments, three observation fields
+    print(json.dumps({'case': 'import', 'capacity': capacity, 'records': rows, 'ms': round(ms_import, 3), 'ms_reset_excluded': round(ms_reset, 3),
+                      'records_per_s': round(rows / ms_import * 1e3), 'atomics_per_record': atomics,
+                      'atomic_bytes_per_s': round(rows / ms_import * 1e3 * (record_bytes - 8))}))
+    new, mom, obs = into._buf, into._mom, into._obs
+    old = (vmap._buf.data_ptr(), vmap._buf.numel(), capacity)
+
+    def rehash():
+        _lib.check(L.rdm_voxel_map_rehash(*old, new.data_ptr(), new.numel(), capacity, C, _lib.stream_ptr()), 'rehash')
+        _lib.check(L.rdm_voxel_moments_rehash(*old, vmap._mom.data_ptr(), vmap._mom.numel(), new.data_ptr(), new.numel(), capacity,
+                                              mom.data_ptr(), mom.numel(), C, _lib.stream_ptr()), 'moments rehash')
+        _lib.check(L.rdm_voxel_observations_rehash(*old, vmap._obs.data_ptr(), vmap._obs.numel(), new.data_ptr(), new.numel(), capacity,
+                                                   obs.data_ptr(), obs.numel(), C, _lib.stream_ptr()), 'observations rehash')
+
+    ms_rehash, _ = timed(rehash, a.reps)  # (its three resets are inside, as import's one reset is taken out: both move `rows` slots)
+    print(json.dumps({'case': 'rehash with both blocks', 'capacity': capacity, 'voxels': rows, 'ms': round(ms_rehash, 3),
+                      'ms_less_reset': round(ms_rehash - ms_reset, 3), 'import_over_rehash': round(ms_import / max(ms_rehash - ms_reset, 1e-6), 2)}))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--frames', type=int, default=256)
@@ -267,6 +330,7 @@ def main(argv=None):
                     help='also time integrate with the per-voxel scan observations, extract_observations, pruned and a refinement frame')
     ap.add_argument('--register', action='store_true', help='time the scan-to-map registration and nothing else')
     ap.add_argument('--query', action='store_true', help='time the per-point queries beside integrate and nothing else')
+    ap.add_argument('--merge', action='store_true', help='time the export and the import of a map state beside its rehash and nothing else')
     ap.add_argument('--digest', action='store_true', help='print the sha1 lines of the bundled scans\' maps and registrations and nothing else')
     ap.add_argument('--cpu', action='store_true', help='also time the NumPy restatement and compare the maps bit for bit')
     ap.add_argument('--cpu-frames', type=int, default=8)
@@ -280,6 +344,8 @@ def main(argv=None):
         return register_cases(a)
     if a.query:
         return query_cases(a)
+    if a.merge:
+        return merge_cases(a)
     C = 4
     cloud, poses = synthetic_scans(a.frames, a.points), drive(a.frames)
     total = a.frames * a.points
