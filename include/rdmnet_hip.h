@@ -1219,6 +1219,48 @@ int rdm_voxel_map_register(const void* map, size_t map_bytes, int64_t capacity, 
                            int max_iteration, double rot_eps, double trans_eps, double* transforms, double* hessians, double* gradients,
                            double* costs, int64_t* stats, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- §7 voxel map alignment: one map's voxel Gaussians against another's (voxel_map.hip) --------------------------------------------
+ * Distribution-to-distribution registration (voxelised GICP on both sides) of a packed batch of SETS of voxel records against a map
+ * with moments: what says where a map of one origin sits in the frame of another.  Not in the reference tree -> parity unpinned; the
+ * project's own definition, pinned to the NumPy restatement tests/voxel_align_restatement.py.  The target (map,
+ * moments block, voxel: the head of rdm_voxel_map_register) is only read.  The source is records as rdm_voxel_map_export writes
+ * them, on the device: counts u32 [total], sums i64 [total, sums_ld] (sums_ld >= 3; only the first three columns are read, so a
+ * state's [M, C] array is passed as it is), moment_sums i64 [total, 9], and source_voxel > 0, the edge of the grid the records were
+ * taken on, which may differ from the target's voxel.  Keys are no input: the sums are absolute fixed-point world coordinates, so a
+ * record's mean needs no cell.  offsets i64 [n_sets + 1] and poses f64 [n_sets, 16] are those of register's scans: set s is the
+ * rows offsets[s] .. offsets[s + 1], clamped to [0, total], and poses holds its initial pose X_s (target <- source).  Parameters:
+ * sigma > 0, min_points >= 1 (of a target voxel), source_min_points >= 1 (of a record), neighbors 1 or 7, max_iteration >= 0,
+ * rot_eps >= 0, trans_eps >= 0.  One evaluation of set s at X = (R, t), everything in float64 without contraction:
+ *   gate      a record with count < source_min_points is passed over and counted nowhere;
+ *   source    n = (double)count, mu_b,d = ((double)sum_d / n) / 2^F source_voxel; Sigma_b = the covariance of
+ *             rdm_voxel_map_extract_moments (its formula, from the nine sums) with source_voxel;
+ *   transform w_d = ((R[d][0] mu_x + R[d][1] mu_y) + R[d][2] mu_z) + t_d; Q_d = floor(w_d / voxel 2^F) and cell_d = Q_d >> F on the
+ *             TARGET's grid; a record whose w rdm_voxel_map_integrate would count in out_of_extent (non-finite included) is
+ *             dropped; the others are the records that passed;
+ *   visit     the 1 or 7 cells of rdm_voxel_map_register, in its order and under its rule (key present, count >= min_points);
+ *   per pair  mu_a and Sigma_a as register forms them; P = R Sigma_b, C = P R^T, every entry as ((x0 + x1) + x2) over the inner
+ *             index, only the six upper entries of C; cov_k = Sigma_a,k + C_k; M = (cov + sigma^2 I)^-1 (cofactors over the
+ *             determinant); r = w - mu_a, q = w - t, J = [-[q]x | I3];
+ *   totals    H += J^T M J, g += J^T M r, cost += r^T M r, n_corr += 1: every pair has weight one.
+ * M is held fixed in the linearisation -- its dependence on R through C is not differentiated (GICP's approximation).  Iteration,
+ * outputs and statuses are those of rdm_voxel_map_register, word for word: evaluate, Cholesky without pivoting, R <- Exp(omega) R,
+ * t <- t + v, the one more evaluation after convergence, statuses 0 / 1 / 2; transforms f64 [n, 16], hessians f64 [n, 36], gradients
+ * f64 [n, 6], costs f64 [n], stats int64 [n, 4] = {updates applied, n_corr, records that passed the gates, status}.  n_sets = 0
+ * (nothing is written) and empty sets are valid; n_sets <= 2^20.  Errors are register's: RDM_ERR_ARG, by name in rdm_last_error,
+ * for a null or short moments block, null counts, sums or moment_sums with total > 0, sums_ld < 3, a voxel or sigma that is not
+ * positive and finite, neighbors not 1 or 7 and negative tolerances or counts; a workspace below
+ * rdm_voxel_map_align_workspace_bytes(n_sets) is RDM_ERR_WORKSPACE.  The launches are register's with one other accumulate kernel
+ * (row j of a set goes to thread j mod (64 x 256) of the set's threads), so again no float atomics and no unbounded loop: two runs
+ * give the same bits, and a set's result does not depend on the rest of the batch, on the target's capacity or on the order in
+ * which either map was integrated.                                                                                                 */
+size_t rdm_voxel_map_align_workspace_bytes(int64_t n_sets);
+int rdm_voxel_map_align(const void* map, size_t map_bytes, int64_t capacity, int channels, const void* moments, size_t moments_bytes,
+                        double voxel, const uint32_t* counts, const int64_t* sums, int64_t sums_ld, const int64_t* moment_sums,
+                        double source_voxel, int64_t total, const int64_t* offsets, const double* poses, int64_t n_sets, double sigma,
+                        int64_t min_points, int64_t source_min_points, int neighbors, int max_iteration, double rot_eps,
+                        double trans_eps, double* transforms, double* hessians, double* gradients, double* costs, int64_t* stats,
+                        void* ws, size_t ws_bytes, void* stream);
+
 /* ---- §7 voxel observations: in how many scans a voxel was seen, and a map without the voxels seen too rarely (voxel_map.hip) ------
  * Not in the reference tree -> parity unpinned; the project's own definition, pinned to the NumPy restatement
  * tests/voxel_observations_restatement.py.  Every integrated scan has an integer id in [0, 2^31 - 1).  A voxel OBSERVES scan s when at

@@ -38,6 +38,9 @@
 // find_or_claim, the same integer atomic adds, the block's tallies through shared memory -- so a saved map reloads, and two maps of
 // different scans add, to the bits of the map built in one pass.
 //
+// Alignment (include/rdmnet_hip.h, "voxel map alignment"; tests/voxel_align_restatement.py): register with another map's voxel records
+// in the place of a scan's points -- align_accumulate_kernel, below register's, whose init and finalize kernels it shares.
+//
 // Four pinned definitions are written once: the point gate (gate_sensor, gate_world; integrate, register and query), the key (pack_key,
 // key_cell; integrate, register, query, extract), the voxel Gaussian (voxel_gaussian; both extracts, register and query) and the weight
 // of a residual (voxel_precision; register and query).  `#pragma clang fp
@@ -769,6 +772,70 @@ __global__ void __launch_bounds__(kBlock) register_init_kernel(const double* __r
   st.pad = 0;
 }
 
+// What both accumulate kernels do with one world point wd of the cell `cell` at the pose X: the visit and, per pair, H's upper triangle,
+// g and the cost into acc.  kExtra: `extra`, six covariance entries, is added to the voxel's own before the inverse (align: the
+// source's R Sigma_b R^T); else it is not looked at (register).  -> the number of pairs.
+template <bool kExtra>
+__device__ __forceinline__ int accumulate_pairs(const Table& t, const unsigned long long* __restrict__ moments, long long capacity,
+                                                double voxel, const double (&wd)[3], const long long (&cell)[3], const double (&X)[12],
+                                                const double* extra, double sigma2, unsigned int min_points, int neighbors,
+                                                double (&acc)[kRegSums]) {
+#pragma clang fp contract(off)
+  int n_corr = 0;
+  const double q0 = wd[0] - X[3], q1 = wd[1] - X[7], q2 = wd[2] - X[11];
+  for (int o = 0; o < neighbors; ++o) {  // (0,0,0), (-1,0,0), (+1,0,0), (0,-1,0), (0,+1,0), (0,0,-1), (0,0,+1)
+    long long c[3] = {cell[0], cell[1], cell[2]};
+    if (o > 0) c[(o - 1) >> 1] += (o & 1) ? -1 : 1;
+    if (c[0] < -kHalf || c[0] >= kHalf || c[1] < -kHalf || c[1] >= kHalf || c[2] < -kHalf || c[2] >= kHalf) continue;
+    const long long slot = find(t.keys, capacity, pack_key(c[0], c[1], c[2]));
+    if (slot < 0 || t.counts[slot] < min_points) continue;
+    Gaussian G = voxel_gaussian<true>(t, moments, capacity, voxel, slot);
+    if constexpr (kExtra) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) G.cov[k] = G.cov[k] + extra[k];
+    }
+    const double r[3] = {wd[0] - G.mean[0], wd[1] - G.mean[1], wd[2] - G.mean[2]};
+    double M[3][3], Mr[3];
+    voxel_precision(G.cov, sigma2, r, M, Mr);
+    // B = [q]x M = (J's rotation block)^T M; H = [[-B [q]x, B], [B^T, M]], g = (q x Mr, Mr)
+    double B[3][3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      B[0][j] = q1 * M[2][j] - q2 * M[1][j];
+      B[1][j] = q2 * M[0][j] - q0 * M[2][j];
+      B[2][j] = q0 * M[1][j] - q1 * M[0][j];
+    }
+    double Hrr[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      Hrr[a][0] = B[a][2] * q1 - B[a][1] * q2;
+      Hrr[a][1] = B[a][0] * q2 - B[a][2] * q0;
+      Hrr[a][2] = B[a][1] * q0 - B[a][0] * q1;
+    }
+    int k = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+      for (int b = a; b < 3; ++b) acc[k++] += Hrr[a][b];
+#pragma unroll
+      for (int b = 0; b < 3; ++b) acc[k++] += B[a][b];
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = a; b < 3; ++b) acc[k++] += M[a][b];
+    acc[21] += q1 * Mr[2] - q2 * Mr[1];
+    acc[22] += q2 * Mr[0] - q0 * Mr[2];
+    acc[23] += q0 * Mr[1] - q1 * Mr[0];
+    acc[24] += Mr[0];
+    acc[25] += Mr[1];
+    acc[26] += Mr[2];
+    acc[27] += (r[0] * Mr[0] + r[1] * Mr[1]) + r[2] * Mr[2];
+    ++n_corr;
+  }
+  return n_corr;
+}
+
 __global__ void __launch_bounds__(kBlock) register_accumulate_kernel(Table t, const unsigned long long* __restrict__ moments,
                                                                      long long capacity, int channels, double voxel,
                                                                      const float* __restrict__ points, long long ld, long long total,
@@ -795,58 +862,79 @@ __global__ void __launch_bounds__(kBlock) register_accumulate_kernel(Table t, co
     if (gate_sensor(points + i * ld, channels, lo2, hi2, v) != kPass || gate_world(v, X, voxel, wd, fixed) != kPass) continue;
     ++n_pass;
     const long long cell[3] = {fixed[0] >> kFrac, fixed[1] >> kFrac, fixed[2] >> kFrac};
-    const double q0 = wd[0] - X[3], q1 = wd[1] - X[7], q2 = wd[2] - X[11];
-    for (int o = 0; o < neighbors; ++o) {  // (0,0,0), (-1,0,0), (+1,0,0), (0,-1,0), (0,+1,0), (0,0,-1), (0,0,+1)
-      long long c[3] = {cell[0], cell[1], cell[2]};
-      if (o > 0) c[(o - 1) >> 1] += (o & 1) ? -1 : 1;
-      if (c[0] < -kHalf || c[0] >= kHalf || c[1] < -kHalf || c[1] >= kHalf || c[2] < -kHalf || c[2] >= kHalf) continue;
-      const long long slot = find(t.keys, capacity, pack_key(c[0], c[1], c[2]));
-      if (slot < 0 || t.counts[slot] < min_points) continue;
-      const Gaussian G = voxel_gaussian<true>(t, moments, capacity, voxel, slot);
-      const double r[3] = {wd[0] - G.mean[0], wd[1] - G.mean[1], wd[2] - G.mean[2]};
-      double M[3][3], Mr[3];
-      voxel_precision(G.cov, sigma2, r, M, Mr);
-      // B = [q]x M = (J's rotation block)^T M; H = [[-B [q]x, B], [B^T, M]], g = (q x Mr, Mr)
-      double B[3][3];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        B[0][j] = q1 * M[2][j] - q2 * M[1][j];
-        B[1][j] = q2 * M[0][j] - q0 * M[2][j];
-        B[2][j] = q0 * M[1][j] - q1 * M[0][j];
-      }
-      double Hrr[3][3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        Hrr[a][0] = B[a][2] * q1 - B[a][1] * q2;
-        Hrr[a][1] = B[a][0] * q2 - B[a][2] * q0;
-        Hrr[a][2] = B[a][1] * q0 - B[a][0] * q1;
-      }
-      int k = 0;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int b = a; b < 3; ++b) acc[k++] += Hrr[a][b];
-#pragma unroll
-        for (int b = 0; b < 3; ++b) acc[k++] += B[a][b];
-      }
-#pragma unroll
-      for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = a; b < 3; ++b) acc[k++] += M[a][b];
-      acc[21] += q1 * Mr[2] - q2 * Mr[1];
-      acc[22] += q2 * Mr[0] - q0 * Mr[2];
-      acc[23] += q0 * Mr[1] - q1 * Mr[0];
-      acc[24] += Mr[0];
-      acc[25] += Mr[1];
-      acc[26] += Mr[2];
-      acc[27] += (r[0] * Mr[0] + r[1] * Mr[1]) + r[2] * Mr[2];
-      ++n_corr;
-    }
+    n_corr += accumulate_pairs<false>(t, moments, capacity, voxel, wd, cell, X, nullptr, sigma2, min_points, neighbors, acc);
   }
   acc[28] = static_cast<double>(n_corr);
   acc[29] = static_cast<double>(n_pass);
   const double sum = block_sum<kRegSums, kBlock>(acc, threadIdx.x);
   if (threadIdx.x < kRegSums) w.slab[(scan * kRegGroups + group) * kRegRow + threadIdx.x] = sum;
+}
+
+// ---- map-to-map alignment (include/rdmnet_hip.h, "voxel map alignment"; tests/voxel_align_restatement.py) ------------------------
+//
+// register with a voxel record in the place of a point: the record's mean is the point and its covariance, turned by the pose, is added
+// to the target voxel's.  The launch geometry, the slab and the two other kernels are register's.  A thread holds register's 30 sums
+// plus the six entries of R Sigma_b R^T across the visit.
+__global__ void __launch_bounds__(kBlock) align_accumulate_kernel(Table t, const unsigned long long* __restrict__ moments,
+                                                                  long long capacity, double voxel, const uint32_t* __restrict__ counts,
+                                                                  const long long* __restrict__ sums, long long sums_ld,
+                                                                  const long long* __restrict__ moment_sums, double source_voxel,
+                                                                  long long total, const int64_t* __restrict__ offsets, double sigma2,
+                                                                  unsigned int min_points, unsigned int source_min_points, int neighbors,
+                                                                  RegWork w) {
+#pragma clang fp contract(off)
+  const long long set = blockIdx.x / kRegGroups;
+  const int group = blockIdx.x % kRegGroups;
+  const RegState& st = w.st[set];
+  if (st.done) return;
+  double X[12];
+  for (int k = 0; k < 12; ++k) X[k] = st.X[k];
+  long long begin = offsets[set], end = offsets[set + 1];
+  begin = begin < 0 ? 0 : begin;
+  end = end > total ? total : end;
+  const double s = source_voxel / kMomSteps, s2 = s * s;
+  double acc[kRegSums];
+#pragma unroll
+  for (int k = 0; k < kRegSums; ++k) acc[k] = 0.0;
+  int n_corr = 0, n_pass = 0;
+  for (long long i = begin + group * kBlock + threadIdx.x; i < end; i += static_cast<long long>(kRegGroups) * kBlock) {
+    const uint32_t count = counts[i];
+    if (count < source_min_points) continue;
+    const double n = static_cast<double>(count);
+    double mu[3], wd[3];
+    long long cell[3];
+    for (int d = 0; d < 3; ++d) mu[d] = static_cast<double>(sums[i * sums_ld + d]) / n / kScale * source_voxel;
+    bool inside = true;
+    for (int d = 0; d < 3; ++d) {  // gate_world's transform, quantisation and extent, on the target's grid
+      wd[d] = ((X[4 * d] * mu[0] + X[4 * d + 1] * mu[1]) + X[4 * d + 2] * mu[2]) + X[4 * d + 3];
+      const double f = floor(wd[d] / voxel * kScale);
+      const bool ok = f >= -kQLimit && f < kQLimit;  // (NaN and infinities fail)
+      inside = inside && ok;
+      cell[d] = (ok ? static_cast<long long>(f) : 0ll) >> kFrac;
+    }
+    if (!inside) continue;
+    ++n_pass;
+    // Sigma_b: voxel_gaussian's covariance from the record's nine sums, then C = (R Sigma_b) R^T, upper triangle
+    double S[kPlanes];
+    for (int k = 0; k < kPlanes; ++k) S[k] = static_cast<double>(moment_sums[i * kPlanes + k]);
+    const double m[3] = {S[0] / n, S[1] / n, S[2] / n};
+    double cb[6];
+    for (int a = 0, k = 0; a < 3; ++a)
+      for (int b = a; b < 3; ++b, ++k) cb[k] = (S[3 + k] / n - m[a] * m[b]) * s2;
+    const double Sb[3][3] = {{cb[0], cb[1], cb[2]}, {cb[1], cb[3], cb[4]}, {cb[2], cb[4], cb[5]}};
+    double P[3][3], C[6];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) P[a][b] = (X[4 * a] * Sb[0][b] + X[4 * a + 1] * Sb[1][b]) + X[4 * a + 2] * Sb[2][b];
+    for (int a = 0, k = 0; a < 3; ++a)
+      for (int b = a; b < 3; ++b, ++k) C[k] = (P[a][0] * X[4 * b] + P[a][1] * X[4 * b + 1]) + P[a][2] * X[4 * b + 2];
+    n_corr += accumulate_pairs<true>(t, moments, capacity, voxel, wd, cell, X, C, sigma2, min_points, neighbors, acc);
+  }
+  acc[28] = static_cast<double>(n_corr);
+  acc[29] = static_cast<double>(n_pass);
+  const double sum = block_sum<kRegSums, kBlock>(acc, threadIdx.x);
+  if (threadIdx.x < kRegSums) w.slab[(set * kRegGroups + group) * kRegRow + threadIdx.x] = sum;
 }
 
 // Exp(omega) by Rodrigues' formula: I + a [omega]x + b [omega]x^2, a = sin(th) / th, b = (1 - cos(th)) / th^2 (their series below 1e-4).
@@ -1524,6 +1612,66 @@ extern "C" int rdm_voxel_map_register(const void* map, size_t map_bytes, int64_t
                          trans_eps, transforms, hessians, gradients, costs, stats);
     }
     if (const int rc = launch_status("rdm_voxel_map_register")) return rc;
+    RDM_HIP_CHECK(hipMemcpyAsync(&running, w.running, sizeof(int), hipMemcpyDeviceToHost, s));  // one 4-byte read-back per chunk
+    RDM_HIP_CHECK(hipStreamSynchronize(s));
+  }
+  return RDM_OK;
+}
+
+// ---- voxel map alignment ------------------------------------------------------------------------------------------------------
+
+extern "C" size_t rdm_voxel_map_align_workspace_bytes(int64_t n_sets) { return rdm_voxel_map_register_workspace_bytes(n_sets); }
+
+extern "C" int rdm_voxel_map_align(const void* map, size_t map_bytes, int64_t capacity, int channels, const void* moments,
+                                   size_t moments_bytes, double voxel, const uint32_t* counts, const int64_t* sums, int64_t sums_ld,
+                                   const int64_t* moment_sums, double source_voxel, int64_t total, const int64_t* offsets,
+                                   const double* poses, int64_t n_sets, double sigma, int64_t min_points, int64_t source_min_points,
+                                   int neighbors, int max_iteration, double rot_eps, double trans_eps, double* transforms,
+                                   double* hessians, double* gradients, double* costs, int64_t* stats, void* ws, size_t ws_bytes,
+                                   void* stream) {
+  using namespace rdm;
+  const char* what = "rdm_voxel_map_align";
+  Table t;
+  unsigned long long* m;
+  if (const int rc = open_table(what, const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
+  if (const int rc = open_moments(what, moments, moments_bytes, capacity, m, RDM_ERR_ARG)) return rc;
+  RDM_REQUIRE(voxel > 0.0 && std::isfinite(voxel), "%s: voxel must be positive and finite", what);
+  RDM_REQUIRE(source_voxel > 0.0 && std::isfinite(source_voxel), "%s: source_voxel must be positive and finite", what);
+  RDM_REQUIRE(n_sets >= 0 && n_sets <= kMaxRegScans && total >= 0, "%s: bad sizes (need total >= 0 and 0 <= n_sets <= 2^20)", what);
+  RDM_REQUIRE(sums_ld >= 3, "%s: sums_ld must be >= 3 (got %lld)", what, static_cast<long long>(sums_ld));
+  if (n_sets > 0 && total > 0) {
+    RDM_REQUIRE(counts != nullptr, "%s: null counts", what);
+    RDM_REQUIRE(sums != nullptr, "%s: null sums", what);
+    RDM_REQUIRE(moment_sums != nullptr, "%s: null moment_sums", what);
+  }
+  RDM_REQUIRE(n_sets == 0 || (offsets && poses), "%s: null offsets or poses", what);
+  RDM_REQUIRE(sigma > 0.0 && std::isfinite(sigma), "%s: sigma must be positive and finite (got %g)", what, sigma);
+  RDM_REQUIRE(neighbors == 1 || neighbors == 7, "%s: neighbors must be 1 or 7 (got %d)", what, neighbors);
+  RDM_REQUIRE(min_points >= 1 && source_min_points >= 1 && max_iteration >= 0 && rot_eps >= 0.0 && trans_eps >= 0.0,
+              "%s: need min_points >= 1, source_min_points >= 1, max_iteration >= 0, rot_eps >= 0 and trans_eps >= 0", what);
+  Arena ar(ws, ws_bytes);
+  RegWork w;
+  if (!carve_register(ar, n_sets, w)) {
+    set_error("%s: workspace too small (%zu < %zu bytes)", what, ws_bytes, ar.off);
+    return RDM_ERR_WORKSPACE;
+  }
+  if (n_sets == 0) return RDM_OK;
+  RDM_REQUIRE(transforms && hessians && gradients && costs && stats, "%s: null output", what);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(register_init_kernel, dim3(blocks_for(n_sets)), dim3(kBlock), 0, s, poses, static_cast<long long>(n_sets), w);
+  int running = 1;
+  for (int k = 0; k <= max_iteration && running > 0;) {
+    const int end = max_iteration - k < kRegChunk ? max_iteration + 1 : k + kRegChunk;
+    for (; k < end; ++k) {
+      hipLaunchKernelGGL(align_accumulate_kernel, dim3(static_cast<unsigned>(n_sets * kRegGroups)), dim3(kBlock), 0, s, t, m,
+                         static_cast<long long>(capacity), voxel, counts, reinterpret_cast<const long long*>(sums),
+                         static_cast<long long>(sums_ld), reinterpret_cast<const long long*>(moment_sums), source_voxel,
+                         static_cast<long long>(total), offsets, sigma * sigma, least_points(min_points),
+                         least_points(source_min_points), neighbors, w);
+      hipLaunchKernelGGL(register_finalize_kernel, dim3(static_cast<unsigned>(n_sets)), dim3(kBlock), 0, s, w, max_iteration, rot_eps,
+                         trans_eps, transforms, hessians, gradients, costs, stats);
+    }
+    if (const int rc = launch_status(what)) return rc;
     RDM_HIP_CHECK(hipMemcpyAsync(&running, w.running, sizeof(int), hipMemcpyDeviceToHost, s));  // one 4-byte read-back per chunk
     RDM_HIP_CHECK(hipStreamSynchronize(s));
   }

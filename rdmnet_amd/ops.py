@@ -1110,6 +1110,93 @@ class VoxelMap:
                            'rdm_voxel_map_register')
         return MapRegistrationResult(T.view(n, 4, 4), H.view(n, 6, 6), g, cost.view(n), stats[:, 0], stats[:, 1], stats[:, 2], stats[:, 3])
 
+    def align(self, sources, poses, *, sigma=0.02, min_points=4, source_min_points=4, neighbors=7, max_iteration=30, rot_eps=1e-5,
+              trans_eps=1e-4):
+        """Map-to-map alignment on the per-voxel Gaussians of both sides (rdm_voxel_map_align): every source is
+        aligned, from its initial pose (this map's frame <- the source's), against this map -- distribution-to-distribution, voxelised
+        GICP.  sources: a list whose items are each a VoxelMap with moments or a state dict (`state` / `read_state`) that holds
+        `moments`, all of one voxel size, which may differ from this map's; a VoxelMap is exported on the device, a state's arrays are
+        copied to it.  The same source given twice with two poses is two hypotheses.  poses: [n, 4, 4] finite.  A source voxel takes
+        part with at least source_min_points points, a voxel of this map with at least min_points; sigma, neighbors, max_iteration,
+        rot_eps and trans_eps as `register` takes them.  The basin is about one voxel of this map with neighbors=7: the start must come
+        from elsewhere.  Both maps are only read.  -> MapRegistrationResult (num_points: the source records that passed)."""
+        import numpy as np
+        self._need_moments('align')
+        if not isinstance(sources, (list, tuple)):
+            raise ValueError('VoxelMap.align: sources must be a list of VoxelMaps or state dicts')
+        packed, source_voxel = [], None
+        for i, src in enumerate(sources):
+            if isinstance(src, VoxelMap):
+                if not src.moments:
+                    raise ValueError(f'sources[{i}] needs a map created with moments=True')
+                if src.device != self.device:
+                    raise ValueError(f'sources[{i}] is on {src.device}, the map on {self.device}')
+                voxel, st = src.voxel, src._export(1, moments=True, observations=False)
+            elif isinstance(src, dict):
+                if src.get('moments') is None:
+                    raise ValueError(f'sources[{i}] holds no moments')
+                voxel, st = float(src['voxel']), src
+            else:
+                raise ValueError(f'sources[{i}] must be a VoxelMap or a state dict, got {type(src).__name__}')
+            if source_voxel is None:
+                source_voxel = voxel
+            elif voxel != source_voxel:
+                raise ValueError(f'sources[{i}]: voxel differs ({voxel!r} against {source_voxel!r}); one call takes sources of one voxel size')
+            rows = int(st['counts'].shape[0])
+            arrays = []
+            for k, dtype, width in (('counts', torch.uint32, None), ('sums', torch.int64, 3), ('moments', torch.int64, _lib.VOXEL_MOMENTS_PLANES)):
+                t = st[k]
+                t = torch.from_numpy(np.ascontiguousarray(t)) if isinstance(t, np.ndarray) else t
+                good = isinstance(t, torch.Tensor) and t.dtype == dtype and t.shape[0] == rows and (
+                    t.dim() == 1 if width is None else t.dim() == 2 and (t.shape[1] >= 3 if k == 'sums' else t.shape[1] == width))
+                if not good:
+                    raise ValueError(f'sources[{i}]: {k} must be {dtype} [{rows}' + ('' if width is None else f', {width}') + '], got '
+                                     f'{getattr(t, "dtype", type(t).__name__)} {list(getattr(t, "shape", ()))}')
+                arrays.append(t.to(self.device)[:, :3] if k == 'sums' else t.to(self.device))
+            packed.append(arrays)
+        n = len(packed)
+        if isinstance(poses, torch.Tensor):
+            poses = poses.detach().cpu().numpy()
+        X = np.ascontiguousarray(np.asarray(poses, dtype=np.float64))
+        if X.shape == (4, 4) and n == 1:
+            X = X[None]
+        if X.size == 0 and n == 0:
+            X = X.reshape(0, 4, 4)
+        if X.shape != (n, 4, 4):
+            raise ValueError(f'poses must be [{n}, 4, 4] (one 4x4 per source), got {X.shape}')
+        if not np.isfinite(X).all():
+            raise ValueError('poses must be finite')
+        sigma, rot_eps, trans_eps = float(sigma), float(rot_eps), float(trans_eps)
+        min_points, source_min_points, neighbors, max_iteration = int(min_points), int(source_min_points), int(neighbors), int(max_iteration)
+        if not (sigma > 0 and sigma < float('inf')):
+            raise ValueError(f'sigma must be positive and finite, got {sigma}')
+        if neighbors not in (1, 7):
+            raise ValueError(f'neighbors must be 1 or 7, got {neighbors}')
+        if min_points < 1 or source_min_points < 1 or max_iteration < 0 or not rot_eps >= 0 or not trans_eps >= 0:
+            raise ValueError('need min_points >= 1, source_min_points >= 1, max_iteration >= 0, rot_eps >= 0 and trans_eps >= 0')
+        L, dev = _lib.lib(), self.device
+        real = torch.zeros((n, 59), dtype=torch.float64, device=dev)  # transforms, hessians, gradients, costs
+        stats = torch.zeros((n, 4), dtype=torch.int64, device=dev)
+        T, H, g, cost = (real.view(-1)[a * n:b * n].view(n, b - a) for a, b in ((0, 16), (16, 52), (52, 58), (58, 59)))
+        if n > 0:
+            offsets = torch.tensor([0] + [int(a[0].shape[0]) for a in packed], dtype=torch.int64).cumsum(0)
+            total = int(offsets[-1])
+            with torch.cuda.device(dev):
+                if total > 0:
+                    counts, sums, moments = (torch.cat([a[k] for a in packed]).contiguous() for k in range(3))
+                else:  # one placeholder record, never read
+                    counts = torch.zeros((1,), dtype=torch.uint32, device=dev)
+                    sums, moments = (torch.zeros((1, w), dtype=torch.int64, device=dev) for w in (3, _lib.VOXEL_MOMENTS_PLANES))
+                offsets, Xd = offsets.to(dev), torch.from_numpy(X).to(dev)
+                ws = scratch(dev, L.rdm_voxel_map_align_workspace_bytes(n))
+                _lib.check(L.rdm_voxel_map_align(*self._head(), self._mom.data_ptr(), self._mom.numel(), self.voxel, counts.data_ptr(),
+                                                 sums.data_ptr(), 3, moments.data_ptr(), source_voxel, total,
+                                                 offsets.data_ptr(), Xd.data_ptr(), n, sigma, min_points,
+                                                 source_min_points, neighbors, max_iteration, rot_eps, trans_eps, T.data_ptr(),
+                                                 H.data_ptr(), g.data_ptr(), cost.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                 _lib.stream_ptr()), 'rdm_voxel_map_align')
+        return MapRegistrationResult(T.view(n, 4, 4), H.view(n, 6, 6), g, cost.view(n), stats[:, 0], stats[:, 1], stats[:, 2], stats[:, 3])
+
     def query(self, clouds, poses, *, sigma=0.02, min_points=1, neighbors=1, min_scans=1, max_d2=float('inf'), min_range=0.0,
               max_range=float('inf'), outputs=None):
         """What the map says about every point of every scan (rdm_voxel_map_query).  clouds, poses, min_range,

@@ -8,7 +8,7 @@
                                    [--map-refine [--map-refine-sigma 0.02] [--map-refine-neighbors {1,7}] [--map-refine-iterations 30]
                                     [--map-refine-min-scans 1]]
                                    [--map-clean [--map-clean-max-d2 D] [--map-clean-sigma 0.02] [--map-clean-neighbors {1,7}]]
-                                   [--map-save] [--map-prior FILE [--map-localize]]]
+                                   [--map-save] [--map-prior FILE [--map-localize] [--map-prior-align [--map-prior-initial FILE]]]]
 
 reads the `{seq}_{src}_{ref}.npz` pair files that `python -m rdmnet_amd.infer` wrote into DIR (ordered and filtered as
 `python -m rdmnet_amd.eval` reads them) and, per sequence, chains the pair poses into a trajectory as
@@ -42,7 +42,12 @@ the map's lines says what was dropped.  With --map-save every variant's full map
 bit).  --map-prior FILE names such a file in the trajectory's world frame -- an earlier --map-save of the same sequence is one -- and
 with it --map-clean judges the scans by that prior map instead of their own (--map-min-scans then counts the prior's scans; a scan that
 is not in the map is what the distance test is for), and --map-localize registers every frame, independently, against the fixed prior
-(`localize_against_map`): a variant `localized` with its own error, pose file and map lines."""
+(`localize_against_map`): a variant `localized` with its own error, pose file and map lines.  With --map-prior-align the prior may
+live in any frame: the map of the base variant (optimised with --optimize, else chained) is aligned to the prior on the voxel Gaussians
+of both (`align_to_map`, `ops.VoxelMap.align`: voxelised GICP) from --map-prior-initial FILE (12 or 16 numbers, row-major: prior <-
+trajectory) or the identity, the result T is written as `{seq}_prior_alignment.txt` and reported in an `aligned to the prior map` line
+after the base variant's map lines, and T is applied only where the prior is touched: the prior is asked about T pose, and the poses
+--map-localize gets back are moved by inv(T).  Every pose file, map and report stays in the trajectory's own frame."""
 import argparse
 import math
 import os
@@ -413,6 +418,59 @@ def localize_line(seq, stats, prior):
             f"iterations and {stats['correspondences'].sum() / frames:.0f} correspondences per frame, {stats['degenerate']} degenerate frames")
 
 
+def read_transform(path):
+    """A text file of 12 or 16 numbers, row-major -> float64 [4, 4] (12: the last row is 0 0 0 1)."""
+    try:
+        with open(path) as f:
+            values = [float(v) for v in f.read().split()]
+    except FileNotFoundError:
+        raise TrajectoryError(f'{path}: no such file')
+    except ValueError as e:
+        raise TrajectoryError(f'{path}: not a text file of numbers ({e})')
+    if len(values) not in (12, 16) or not np.isfinite(values).all():
+        raise TrajectoryError(f'{path}: expected 12 or 16 finite numbers (a row-major 3x4 or 4x4 transform), got {len(values)}')
+    T = np.eye(4)
+    T.reshape(-1)[:len(values)] = values
+    if T[3].tolist() != [0.0, 0.0, 0.0, 1.0]:
+        raise TrajectoryError(f'{path}: the last row of a 4x4 transform must be 0 0 0 1')
+    return T
+
+
+def align_to_map(paths, poses, prior, initial=None, *, voxel=MAP_DEFAULTS['voxel'], sigma=REFINE_DEFAULTS['sigma'],
+                 neighbors=REFINE_DEFAULTS['neighbors'], max_iteration=REFINE_DEFAULTS['iterations'], min_points=REFINE_DEFAULTS['min_points'],
+                 source_min_points=REFINE_DEFAULTS['min_points'], min_range=0.0, max_range=math.inf, batch=MAP_DEFAULTS['batch']):
+    """Where the trajectory `poses` ([n, 4, 4]) of the scans `paths` sits in the frame of the map `prior` (an ops.VoxelMap with moments):
+    the scans are fused under the poses into a map with moments at `voxel` (build_map) and that map is aligned, as the source, to the
+    prior (ops.VoxelMap.align) from `initial` ([4, 4], prior <- trajectory; None: the identity).  Both maps are only read once built.
+    -> (T float64 [4, 4], dict(status, iterations, correspondences, cost, matched, voxels, moved_m, moved_deg)): matched / voxels are
+    the correspondences and the source voxels of one more evaluation at T with the voxel's own cell alone; moved: from `initial` to T.
+    A degenerate alignment (status 2) returns `initial`."""
+    if not prior.moments:
+        raise ValueError('align_to_map: the prior has no moments')
+    T0 = np.eye(4) if initial is None else np.asarray(initial, dtype=np.float64).reshape(4, 4)
+    source = build_map(paths, poses, voxel=voxel, channels=prior.channels, min_range=min_range, max_range=max_range, batch=batch,
+                       device=prior.device, moments=True)
+    res = prior.align([source], T0[None], sigma=sigma, min_points=min_points, source_min_points=source_min_points, neighbors=neighbors,
+                      max_iteration=max_iteration)
+    status, iterations, corr = (int(v[0]) for v in (res.status, res.iterations, res.num_correspondences))
+    T = T0.copy() if status == 2 else res.transformations[0].cpu().numpy()
+    own = prior.align([source], T[None], sigma=sigma, min_points=min_points, source_min_points=source_min_points, neighbors=1,
+                      max_iteration=0)
+    E = T[:3, :3] @ T0[:3, :3].T
+    return T, dict(status=status, iterations=iterations, correspondences=corr, cost=float(res.cost[0]),
+                   matched=int(own.num_correspondences[0]), voxels=int(own.num_points[0]),
+                   moved_m=float(np.linalg.norm(T[:3, 3] - T0[:3, 3])),
+                   moved_deg=float(np.degrees(np.arccos(np.clip((np.trace(E) - 1.0) / 2.0, -1.0, 1.0)))))
+
+
+def align_line(seq, what, prior, stats):
+    """prior: what prior_words takes; stats: align_to_map's."""
+    from .ops import MapRegistrationResult
+    return (f"seq {seq} {what} aligned to the prior map {prior['name']}: {stats['matched']} of {stats['voxels']} voxels matched, "
+            f"{stats['correspondences']} correspondences, {stats['iterations']} iterations, cost {stats['cost']:.6g}, moved "
+            f"{stats['moved_m']:.3f} m / {stats['moved_deg']:.3f} deg ({MapRegistrationResult.STATUS[stats['status']]})")
+
+
 def load_prior(args):
     """(the ops.VoxelMap of --map-prior, what prior_words takes), loaded once per run from the state that map_paths read; (None, None)
     without the flag."""
@@ -426,8 +484,9 @@ def load_prior(args):
     return args.map_prior_loaded
 
 
-def write_map(args, seq, what, paths, poses, emit, vmap=None):
-    """vmap: the map of these scans under these poses when the caller has built it already (the refinement's)."""
+def write_map(args, seq, what, paths, poses, emit, vmap=None, to_prior=None):
+    """vmap: the map of these scans under these poses when the caller has built it already (the refinement's); to_prior: the
+    --map-prior-align transform (prior <- trajectory), under which the prior judges the scans."""
     lo, hi = args.map_range if args.map_range else (0.0, math.inf)
     sharpness = bool(getattr(args, 'map_sharpness', False))
     min_scans = getattr(args, 'map_min_scans', None) or MAP_DEFAULTS['min_scans']
@@ -441,7 +500,8 @@ def write_map(args, seq, what, paths, poses, emit, vmap=None):
     if getattr(args, 'map_save', False):  # the full map
         vmap.save(osp.join(args.out, f'{seq}_{what}_map_state.npz'))
     if clean:  # the scans against the full map, or against the prior
-        tallies = clean_scans(paths, poses, vmap if judge is None else judge, osp.join(args.out, f'{seq}_{what}_clean'), min_scans=min_scans, max_d2=max_d2,
+        asked = poses if judge is None or to_prior is None else to_prior @ np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
+        tallies = clean_scans(paths, asked, vmap if judge is None else judge, osp.join(args.out, f'{seq}_{what}_clean'), min_scans=min_scans, max_d2=max_d2,
                               sigma=args.map_clean_sigma, min_points=args.map_min_points, neighbors=args.map_clean_neighbors,
                               min_range=lo, max_range=hi, batch=args.map_batch)
     if min_scans > 1:  # everything below describes the pruned map
@@ -463,20 +523,25 @@ def map_paths(args, seqs):
     """{seq: the scan file of every chain frame}, after the checks that need no GPU."""
     refine, localize = bool(getattr(args, 'map_refine', False)), bool(getattr(args, 'map_localize', False))
     prior = getattr(args, 'map_prior', None)
+    align, initial = bool(getattr(args, 'map_prior_align', False)), getattr(args, 'map_prior_initial', None)
+    if initial is not None and not align:
+        raise TrajectoryError('--map-prior-initial needs --map-prior-align (it is where the alignment to the prior map starts)')
+    if align and not (prior and getattr(args, 'map_scans', None) and args.out):
+        raise TrajectoryError("--map-prior-align needs --map-prior, --map-scans and --out (the map of the scans is aligned to the prior map)")
     if getattr(args, 'map_save', False) and not (getattr(args, 'map_scans', None) and args.out):
         raise TrajectoryError('--map-save needs --map-scans and --out (the maps of the scans are written to --out)')
     if localize and not (prior and getattr(args, 'map_scans', None) and args.out):
         raise TrajectoryError('--map-localize needs --map-prior, --map-scans and --out (the frames are registered against the prior map)')
-    if prior and not (localize or getattr(args, 'map_clean', False)):
+    if prior and not (localize or align or getattr(args, 'map_clean', False)):
         raise TrajectoryError('--map-prior needs --map-clean or --map-localize (the prior judges the scans or localises the frames)')
     if refine and not (getattr(args, 'map_scans', None) and args.out):
         raise TrajectoryError('--map-refine needs --map-scans and --out (the frames are registered against the map of the scans)')
     if not refine:
         for flag, key in (('--map-refine-sigma', 'sigma'), ('--map-refine-neighbors', 'neighbors'), ('--map-refine-iterations', 'iterations'),
                           ('--map-refine-min-scans', 'min_scans')):
-            if getattr(args, 'map_refine_' + key, None) not in (None, REFINE_DEFAULTS[key]) and not (localize and key != 'min_scans'):
+            if getattr(args, 'map_refine_' + key, None) not in (None, REFINE_DEFAULTS[key]) and not ((localize or align) and key != 'min_scans'):
                 raise TrajectoryError(f'{flag} needs --map-refine' + ('' if key == 'min_scans' else ' (or --map-localize)'))
-    if (refine or localize) and (not (args.map_refine_sigma > 0 and math.isfinite(args.map_refine_sigma)) or args.map_refine_iterations < 0):
+    if (refine or localize or align) and (not (args.map_refine_sigma > 0 and math.isfinite(args.map_refine_sigma)) or args.map_refine_iterations < 0):
         raise TrajectoryError('--map-refine-sigma must be > 0 and --map-refine-iterations >= 0')
     if refine and getattr(args, 'map_refine_min_scans', REFINE_DEFAULTS['min_scans']) < 1:
         raise TrajectoryError(f'--map-refine-min-scans must be >= 1, got {args.map_refine_min_scans}')
@@ -510,6 +575,10 @@ def map_paths(args, seqs):
         if localize and args.map_prior_state.get('moments') is None:
             raise TrajectoryError(f'--map-localize needs a prior with moments; --map-prior {prior} has none (save it from a run with '
                                   '--map-sharpness or a finite --map-clean-max-d2)')
+        if align and args.map_prior_state.get('moments') is None:
+            raise TrajectoryError(f'--map-prior-align needs a prior with moments; --map-prior {prior} has none (save it from a run with '
+                                  '--map-sharpness or a finite --map-clean-max-d2)')
+        args.map_prior_start = read_transform(initial) if initial is not None else None
         if getattr(args, 'map_clean', False) and getattr(args, 'map_min_scans', MAP_DEFAULTS['min_scans']) >= 2 \
                 and args.map_prior_state.get('observations') is None:
             raise TrajectoryError(f'--map-min-scans {args.map_min_scans} with --map-clean counts the scans of the prior; --map-prior {prior} '
@@ -542,6 +611,48 @@ def run(args, emit=print):
     if args.out:
         os.makedirs(args.out, exist_ok=True)
     gts = {}
+    align = bool(getattr(args, 'map_prior_align', False))
+    solved, aligned = [], {}
+
+    def optimised():
+        """The pose graphs of all sequences, optimised once -> (res, nodes, pruned, order, noff, eoff)."""
+        if not solved:
+            from . import ops
+            order = list(graphs)
+            noff = np.cumsum([0] + [len(graphs[q][0]) for q in order])
+            eoff = np.cumsum([0] + [len(graphs[q][1]) for q in order])
+            cat = lambda k, shape: np.concatenate([graphs[q][k].reshape(shape) for q in order]) if order else np.zeros(shape[1:])
+            res = ops.pose_graph_optimize(cat(0, (-1, 4, 4)), cat(1, (-1, 2)), cat(2, (-1, 4, 4)), cat(3, (-1, 6, 6)), cat(4, (-1,)),
+                                          line_process_weight=args.line_process_weight, edge_prune_threshold=args.edge_prune_threshold,
+                                          max_iterations=args.max_iterations, graph_node_offsets=noff, graph_edge_offsets=eoff,
+                                          preconditioner=getattr(args, 'preconditioner', 'block_jacobi'),
+                                          linear_solver=getattr(args, 'linear_solver', 'pcg'))
+            solved.append((res, res.nodes.cpu().numpy(), res.pruned.cpu().numpy(), order, noff, eoff))
+        return solved[0]
+
+    def to_prior(seq):
+        """--map-prior-align: (T, its line) of the sequence's base variant, found when the prior is first touched; else (None, None)."""
+        if not align:
+            return None, None
+        if seq not in aligned:
+            if args.optimize:
+                _, nodes, _, order, noff, _ = optimised()
+                g = order.index(seq)
+                base, what = nodes[noff[g]:noff[g + 1]], 'optimized'
+            else:
+                base, what = graphs[seq][0], 'chained'
+            lo, hi = args.map_range if args.map_range else (0.0, math.inf)
+            vmap, prior = load_prior(args)
+            T, stats = align_to_map(scans[seq], base, vmap, args.map_prior_start, voxel=args.map_voxel, sigma=args.map_refine_sigma,
+                                    neighbors=args.map_refine_neighbors, max_iteration=args.map_refine_iterations, min_range=lo,
+                                    max_range=hi, batch=args.map_batch)
+            if stats['status'] == 2:
+                raise TrajectoryError(f"seq {seq}: the alignment of the {what} map to the prior map {prior['name']} is degenerate "
+                                      f"({stats['correspondences']} correspondences): give a better start with --map-prior-initial")
+            np.savetxt(osp.join(args.out, f'{seq}_prior_alignment.txt'), T, fmt='%.9e')
+            aligned[seq] = (T, align_line(seq, what, prior, stats))
+        return aligned[seq]
+
     for seq, s in seqs.items():
         traj = graphs[seq][0][1:]
         if all(gt is not None for _, _, gt, _ in s['chain']):
@@ -552,7 +663,9 @@ def run(args, emit=print):
         if args.out:
             write_kitti_poses(osp.join(args.out, f'{seq}_chained.txt'), graphs[seq][0])
         if scans:
-            write_map(args, seq, 'chained', scans[seq], graphs[seq][0], emit)
+            write_map(args, seq, 'chained', scans[seq], graphs[seq][0], emit, to_prior=to_prior(seq)[0])
+            if align and not args.optimize:
+                emit(to_prior(seq)[1])
 
     def refine(seq, base):
         lo, hi = args.map_range if args.map_range else (0.0, math.inf)
@@ -565,19 +678,22 @@ def run(args, emit=print):
             emit(report_line(seq, 'refined', absolute_trajectory_error(refined[1:], gts[seq])))
         emit(refine_line(seq, stats))
         write_kitti_poses(osp.join(args.out, f'{seq}_refined.txt'), refined)
-        write_map(args, seq, 'refined', scans[seq], refined, emit, vmap=vmap)
+        write_map(args, seq, 'refined', scans[seq], refined, emit, vmap=vmap, to_prior=to_prior(seq)[0])
 
     def localize(seq, base):
         lo, hi = args.map_range if args.map_range else (0.0, math.inf)
         vmap, prior = load_prior(args)
-        localized, stats = localize_against_map(scans[seq], base, vmap, sigma=args.map_refine_sigma, neighbors=args.map_refine_neighbors,
+        T = to_prior(seq)[0]
+        localized, stats = localize_against_map(scans[seq], base if T is None else T @ base, vmap, sigma=args.map_refine_sigma, neighbors=args.map_refine_neighbors,
                                                 max_iteration=args.map_refine_iterations, min_range=lo, max_range=hi,
                                                 batch=args.map_batch)
+        if T is not None:  # back into the trajectory's frame; a degenerate frame keeps its pose
+            localized = np.where((stats['status'] == 2)[:, None, None], base, np.linalg.inv(T) @ localized)
         if seq in gts:
             emit(report_line(seq, 'localized', absolute_trajectory_error(localized[1:], gts[seq])))
         emit(localize_line(seq, stats, prior))
         write_kitti_poses(osp.join(args.out, f'{seq}_localized.txt'), localized)
-        write_map(args, seq, 'localized', scans[seq], localized, emit)
+        write_map(args, seq, 'localized', scans[seq], localized, emit, to_prior=T)
 
     if not args.optimize:
         for seq in seqs:
@@ -588,17 +704,7 @@ def run(args, emit=print):
         return None
     if not graphs:
         raise TrajectoryError(f'{args.features_root}: no pair files to optimise')
-    from . import ops
-    order = list(graphs)
-    noff = np.cumsum([0] + [len(graphs[q][0]) for q in order])
-    eoff = np.cumsum([0] + [len(graphs[q][1]) for q in order])
-    cat = lambda k, shape: np.concatenate([graphs[q][k].reshape(shape) for q in order]) if order else np.zeros(shape[1:])
-    res = ops.pose_graph_optimize(cat(0, (-1, 4, 4)), cat(1, (-1, 2)), cat(2, (-1, 4, 4)), cat(3, (-1, 6, 6)), cat(4, (-1,)),
-                                  line_process_weight=args.line_process_weight, edge_prune_threshold=args.edge_prune_threshold,
-                                  max_iterations=args.max_iterations, graph_node_offsets=noff, graph_edge_offsets=eoff,
-                                  preconditioner=getattr(args, 'preconditioner', 'block_jacobi'),
-                                  linear_solver=getattr(args, 'linear_solver', 'pcg'))
-    nodes, pruned = res.nodes.cpu().numpy(), res.pruned.cpu().numpy()
+    res, nodes, pruned, order, noff, eoff = optimised()
     for g, seq in enumerate(order):
         traj = nodes[noff[g] + 1:noff[g + 1]]
         if seq in gts:
@@ -609,7 +715,9 @@ def run(args, emit=print):
         if args.out:
             write_kitti_poses(osp.join(args.out, f'{seq}_optimized.txt'), nodes[noff[g]:noff[g + 1]])
         if scans:
-            write_map(args, seq, 'optimized', scans[seq], nodes[noff[g]:noff[g + 1]], emit)
+            write_map(args, seq, 'optimized', scans[seq], nodes[noff[g]:noff[g + 1]], emit, to_prior=to_prior(seq)[0])
+            if align:
+                emit(to_prior(seq)[1])
         if getattr(args, 'map_refine', False):
             refine(seq, nodes[noff[g]:noff[g + 1]])
         if getattr(args, 'map_localize', False):
@@ -680,6 +788,14 @@ def make_parser():
                     help='register every frame, independently, against the fixed --map-prior (which needs moments): a variant `localized`, '
                          'from the optimised poses with --optimize, else the chained; --map-batch frames per call, sigma, neighbours and '
                          'iterations from the --map-refine-* options (needs --map-prior, --map-scans and --out)')
+    ap.add_argument('--map-prior-align', action='store_true',
+                    help="the --map-prior may live in any frame: align the base variant's map (optimised with --optimize, else chained, "
+                         'with moments at --map-voxel) to it on the voxel Gaussians of both, write the transform T (prior <- trajectory) as '
+                         '{seq}_prior_alignment.txt and ask the prior about T pose; sigma, neighbours and iterations from the '
+                         '--map-refine-* options (needs --map-prior with moments, --map-scans and --out)')
+    ap.add_argument('--map-prior-initial', default=None, metavar='FILE',
+                    help='where --map-prior-align starts: a text file of 12 or 16 numbers, row-major, prior <- trajectory (default: the '
+                         'identity); the basin is about one voxel of the prior with --map-refine-neighbors 7')
     return ap
 
 

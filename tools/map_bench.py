@@ -1,7 +1,7 @@
 """Times the voxel map (ops.VoxelMap) on synthetic scans along a synthetic drive.
 
   python tools/map_bench.py [--frames 256] [--points 120000 | 18000] [--reps 3] [--batch 64] [--voxel 0.3] [--cpu] [--cpu-frames 8]
-                              [--moments] [--observations] [--register] [--query] [--merge] [--digest]
+                              [--moments] [--observations] [--register] [--align] [--query] [--merge] [--digest]
 With --digest (and nothing else): no timing, one sha1 line per output of the voxel map on the bundled scans (see digest()), for
 comparing the bits of two builds of the library.  Otherwise prints one JSON line per case:
   * integrate: --frames scans of --points points (120 000: a raw scan; 18 000: a down-sampled one), xyz + intensity, integrated in
@@ -26,6 +26,13 @@ comparing the bits of two builds of the library.  Otherwise prints one JSON line
     tolerances), the point-voxel pairs per second of the evaluation, and ms per iteration (accumulate + finalize launches) from runs
     of 4 and 12 forced updates of the batch; with --cpu also the seconds of one evaluation by tests/voxel_register_restatement.py
     and whether its counts equal the GPU's;
+  * with --align (and nothing else of the above): the map-to-map alignment (ops.VoxelMap.align) at neighbors 1 and 7 for both scan
+    shapes: the target is --register's map of min(--frames, 64) scans, the source the map with moments of the same scans built in a
+    frame turned by 0.3 rad and shifted by 3 m, the start 5 cm / 5 mrad off the transform between the two: ms per evaluation
+    (max_iteration = 0), the record-voxel pairs per second of the evaluation, ms per full alignment (default tolerances) and ms per
+    iteration from runs of 4 and 12 forced updates; beside them, from the same run and against the same target, ms per evaluation
+    and pairs per second of --register's one scan; with --cpu also the seconds of one evaluation by
+    tests/voxel_align_restatement.py on maps of the first --cpu-frames scans and whether its counts equal the GPU's;
   * with --query (and nothing else of the above): the per-point queries (ops.VoxelMap.query) for both scan shapes, a batch of
     min(--frames, 64) scans under their true poses against the map with moments and observations that holds them: points/s of a
     labels-only query that is the lookup alone (neighbors 1, min_scans 1), with the scan count (min_scans 2), with the distance too
@@ -196,6 +203,54 @@ def register_cases(a):
     return 0
 
 
+def align_cases(a):
+    from rdmnet_amd import ops
+    rng = np.random.default_rng(0)
+    frames = max(min(a.frames, 64), 1)
+    T = np.eye(4)
+    T[:3, :3] = [[np.cos(0.3), -np.sin(0.3), 0.0], [np.sin(0.3), np.cos(0.3), 0.0], [0.0, 0.0, 1.0]]
+    T[:3, 3] = [2.5, -1.5, 0.4]
+    start = off_poses(T[None], rng)
+    for points in (120000, 18000):
+        cloud, poses = synthetic_scans(frames, points), drive(frames)
+        clouds = [cloud[k * points:(k + 1) * points] for k in range(frames)]
+        vmap = ops.VoxelMap(a.voxel, channels=4, capacity=1 << 24, moments=True).integrate(clouds, poses)
+        moved = np.linalg.inv(T) @ poses
+        source = ops.VoxelMap(a.voxel, channels=4, capacity=1 << 24, moments=True).integrate(clouds, moved)
+        state = source.state()  # exported once: the timings are the alignment's own
+        off = off_poses(poses, rng)
+        for neighbors in (1, 7):
+            kw = dict(neighbors=neighbors)
+            ms_eval, ev = timed(lambda: vmap.align([state], start, max_iteration=0, **kw), a.reps)
+            ms_one, one = timed(lambda: vmap.align([state], start, **kw), a.reps)
+            ms_4, _ = timed(lambda: vmap.align([state], start, max_iteration=4, rot_eps=0.0, trans_eps=0.0, **kw), a.reps)
+            ms_12, _ = timed(lambda: vmap.align([state], start, max_iteration=12, rot_eps=0.0, trans_eps=0.0, **kw), a.reps)
+            ms_reg, reg = timed(lambda: vmap.register(clouds[:1], off[:1], max_iteration=0, **kw), a.reps)
+            pairs, reg_pairs = int(ev.num_correspondences[0]), int(reg.num_correspondences[0])
+            line = {'case': 'align', 'points_per_scan': points, 'neighbors': neighbors, 'voxel': a.voxel, 'map_frames': frames,
+                    'target_voxels': len(vmap), 'source_voxels': len(source), 'source_records_passed': int(ev.num_points[0]),
+                    'ms_per_evaluation': round(ms_eval, 3), 'pairs_per_evaluation': pairs, 'pairs_per_s': round(pairs / ms_eval * 1e3),
+                    'ms_per_alignment': round(ms_one, 3), 'iterations': int(one.iterations[0]), 'status': int(one.status[0]),
+                    'ms_per_iteration': round((ms_12 - ms_4) / 8.0, 4), 'register_ms_per_evaluation': round(ms_reg, 3),
+                    'register_pairs_per_evaluation': reg_pairs, 'register_pairs_per_s': round(reg_pairs / ms_reg * 1e3)}
+            if a.cpu:
+                import voxel_align_restatement as AR
+                import voxel_moments_restatement as MR
+                m = min(a.cpu_frames, frames)
+                host = [c.cpu().numpy() for c in clouds[:m]]
+                target, src = MR.build(host, poses[:m], a.voxel, 4), MR.build(host, moved[:m], a.voxel, 4)
+                small = ops.VoxelMap(a.voxel, channels=4, moments=True).integrate(clouds[:m], poses[:m])
+                small_src = ops.VoxelMap(a.voxel, channels=4, moments=True).integrate(clouds[:m], moved[:m])
+                got = small.align([small_src], start, max_iteration=0, **kw)
+                t0 = time.perf_counter()
+                e = AR.evaluate(target, src, start[0], 0.02, 4, 4, neighbors)
+                line.update(cpu_s_per_evaluation=round(time.perf_counter() - t0, 4), cpu_map_frames=m,
+                            counts_equal=bool(int(got.num_correspondences[0]) == e['n_corr'] and int(got.num_points[0]) == e['n_points']))
+            print(json.dumps(line), flush=True)
+        del vmap, source, state
+    return 0
+
+
 def query_cases(a):
     import torch
     from rdmnet_amd import _lib, ops
@@ -329,6 +384,7 @@ def main(argv=None):
     ap.add_argument('--observations', action='store_true',
                     help='also time integrate with the per-voxel scan observations, extract_observations, pruned and a refinement frame')
     ap.add_argument('--register', action='store_true', help='time the scan-to-map registration and nothing else')
+    ap.add_argument('--align', action='store_true', help='time the map-to-map alignment beside the registration and nothing else')
     ap.add_argument('--query', action='store_true', help='time the per-point queries beside integrate and nothing else')
     ap.add_argument('--merge', action='store_true', help='time the export and the import of a map state beside its rehash and nothing else')
     ap.add_argument('--digest', action='store_true', help='print the sha1 lines of the bundled scans\' maps and registrations and nothing else')
@@ -342,6 +398,8 @@ def main(argv=None):
         return digest()
     if a.register:
         return register_cases(a)
+    if a.align:
+        return align_cases(a)
     if a.query:
         return query_cases(a)
     if a.merge:
