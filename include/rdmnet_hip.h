@@ -1219,6 +1219,32 @@ int rdm_voxel_map_register(const void* map, size_t map_bytes, int64_t capacity, 
                            int max_iteration, double rot_eps, double trans_eps, double* transforms, double* hessians, double* gradients,
                            double* costs, int64_t* stats, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- §7 voxel map registration with robust weights (voxel_map.hip) -------------------------------------------------------------------
+ * rdm_voxel_map_register with one weight per point-voxel pair: the Geman-McClure weight of the pose graph's line process,
+ * l = (mu / (mu + d2))^2, mu = robust_scale in units of squared Mahalanobis distance (9, about the 97 % point of chi^2 with 3 degrees
+ * of freedom, is a value to start from; there is no default but off).  Not in the reference tree -> parity unpinned; the project's own
+ * definition, pinned to the NumPy restatement tests/voxel_register_robust_restatement.py.  Arguments: those of
+ * rdm_voxel_map_register in its order, with robust_scale after trans_eps and weight_sums (f64 [n], may be null) after costs.  Gates,
+ * visit, mu_d, Sigma, M, r, q and J are rdm_voxel_map_register's, word for word.  Per pair, in float64 without contraction:
+ *   d2 = r^T M r (the value the plain form adds to the cost); s = mu / (mu + d2); l = s s;
+ *   H += l (J^T M J): each of the pair's 21 upper-triangle terms is multiplied by l and then added;
+ *   g += l (J^T M r): each of the 6 terms is multiplied by l and then added;
+ *   cost += s d2 (= mu d2 / (mu + d2); its gradient with the associations held fixed is 2 g);
+ *   weight_sum += l; n_corr += 1 (every pair counts, whatever its weight).
+ * Iteration, update, convergence test, statuses and outputs are those of the plain form; H, now the weighted sum, discounts the
+ * outliers as the information of a scan-to-map edge too.  weight_sums[s] is the sum of l over the pairs of the returned pose: how
+ * many correspondences scan s has by weight.  robust_scale = 0 is rdm_voxel_map_register bit for bit (it runs the same kernels), and
+ * weight_sums, if given, then takes n_corr; rdm_voxel_map_register is this function with 0 and null.  A negative, NaN or infinite
+ * robust_scale is RDM_ERR_ARG; every other error is rdm_voxel_map_register's, under its name.  The workspace is
+ * rdm_voxel_map_register_workspace_bytes(n_scans).  weight_sum is one more sum of the same fixed-order reduction: no float atomics,
+ * and the bit-for-bit guarantees of the plain form hold. */
+int rdm_voxel_map_register_robust(const void* map, size_t map_bytes, int64_t capacity, int channels, const void* moments,
+                                  size_t moments_bytes, double voxel, const float* points, int64_t ld, int64_t total,
+                                  const int64_t* offsets, const double* poses, int64_t n_scans, double min_range, double max_range,
+                                  double sigma, int64_t min_points, int neighbors, int max_iteration, double rot_eps, double trans_eps,
+                                  double robust_scale, double* transforms, double* hessians, double* gradients, double* costs,
+                                  double* weight_sums, int64_t* stats, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- §7 voxel map alignment: one map's voxel Gaussians against another's (voxel_map.hip) --------------------------------------------
  * Distribution-to-distribution registration (voxelised GICP on both sides) of a packed batch of SETS of voxel records against a map
  * with moments: what says where a map of one origin sits in the frame of another.  Not in the reference tree -> parity unpinned; the

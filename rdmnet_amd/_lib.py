@@ -295,6 +295,10 @@ SIGNATURES = {
     'rdm_voxel_map_register': (c_int, [c_void, c_size, c_i64, c_int, c_void, c_size, ctypes.c_double, c_void, c_i64, c_i64, c_void, c_void,
                                        c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i64, c_int, c_int, ctypes.c_double,
                                        ctypes.c_double, c_void, c_void, c_void, c_void, c_void, c_void, c_size, c_void]),
+    'rdm_voxel_map_register_robust': (c_int, [c_void, c_size, c_i64, c_int, c_void, c_size, ctypes.c_double, c_void, c_i64, c_i64, c_void,
+                                              c_void, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i64, c_int, c_int,
+                                              ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void, c_void, c_void, c_void, c_void,
+                                              c_void, c_void, c_size, c_void]),
     'rdm_voxel_map_align_workspace_bytes': (c_size, [c_i64]),
     'rdm_voxel_map_align': (c_int, [c_void, c_size, c_i64, c_int, c_void, c_size, ctypes.c_double, c_void, c_void, c_i64, c_void,
                                     ctypes.c_double, c_i64, c_void, c_void, c_i64, ctypes.c_double, c_i64, c_i64, c_int, c_int,

@@ -731,10 +731,18 @@ int open_observations(const char* what, const void* observations, size_t observa
 // A thread keeps the upper triangle of H (21), g (6), the cost and two counts, block_sum adds them in a fixed order and one slab row
 // per workgroup is written.  register_finalize_kernel: one workgroup per scan adds the scan's slab rows in index order, thread 0
 // factors H, moves the pose, tests convergence and writes the outputs.  No float atomics; the table is only read.
+//
+// Robust weights (rdm_voxel_map_register_robust, robust_scale mu > 0; tests/voxel_register_robust_restatement.py) are a second
+// instantiation, kRobust, of accumulate_pairs and of both kernels: per pair d2 = r^T M r, s = mu / (mu + d2), l = s s; every term of
+// H and g is multiplied by l before it is added, the cost takes s d2, and a 31st sum, l itself, goes to slot 30 of the slab row and
+// from there to weight_sums.  The plain instantiation has none of this in it: it is the code it was, and it never writes or reads
+// slot 30.
 
 constexpr int kRegGroups = 64;   // workgroups per scan
 constexpr int kRegSums = 30;     // H upper triangle, g, cost, then n_corr and the gated points (integers, exact in a double)
+constexpr int kRegSumsRobust = kRegSums + 1;  // and the sum of the weights
 constexpr int kRegRow = 32;      // doubles per slab row
+static_assert(kRegSumsRobust <= kRegRow, "a slab row holds the sums of either form");
 constexpr int kRegChunk = 8;     // evaluations enqueued between two reads of `running`
 constexpr int64_t kMaxRegScans = int64_t(1) << 20;  // kRegGroups workgroups each in one grid
 
@@ -774,12 +782,13 @@ __global__ void __launch_bounds__(kBlock) register_init_kernel(const double* __r
 
 // What both accumulate kernels do with one world point wd of the cell `cell` at the pose X: the visit and, per pair, H's upper triangle,
 // g and the cost into acc.  kExtra: `extra`, six covariance entries, is added to the voxel's own before the inverse (align: the
-// source's R Sigma_b R^T); else it is not looked at (register).  -> the number of pairs.
-template <bool kExtra>
+// source's R Sigma_b R^T); else it is not looked at (register).  kRobust: every pair is weighted by l = (mu / (mu + d2))^2, d2 its
+// cost term, and acc[kRegSums] takes the sum of l; else mu is not looked at.  -> the number of pairs.
+template <bool kExtra, bool kRobust = false>
 __device__ __forceinline__ int accumulate_pairs(const Table& t, const unsigned long long* __restrict__ moments, long long capacity,
                                                 double voxel, const double (&wd)[3], const long long (&cell)[3], const double (&X)[12],
                                                 const double* extra, double sigma2, unsigned int min_points, int neighbors,
-                                                double (&acc)[kRegSums]) {
+                                                double (&acc)[kRobust ? kRegSumsRobust : kRegSums], double mu = 0.0) {
 #pragma clang fp contract(off)
   int n_corr = 0;
   const double q0 = wd[0] - X[3], q1 = wd[1] - X[7], q2 = wd[2] - X[11];
@@ -813,6 +822,31 @@ __device__ __forceinline__ int accumulate_pairs(const Table& t, const unsigned l
       Hrr[a][2] = B[a][1] * q0 - B[a][0] * q1;
     }
     int k = 0;
+    if constexpr (kRobust) {
+      const double d2 = (r[0] * Mr[0] + r[1] * Mr[1]) + r[2] * Mr[2];
+      const double s = mu / (mu + d2), l = s * s;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int b = a; b < 3; ++b) acc[k++] += l * Hrr[a][b];
+#pragma unroll
+        for (int b = 0; b < 3; ++b) acc[k++] += l * B[a][b];
+      }
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = a; b < 3; ++b) acc[k++] += l * M[a][b];
+      acc[21] += l * (q1 * Mr[2] - q2 * Mr[1]);
+      acc[22] += l * (q2 * Mr[0] - q0 * Mr[2]);
+      acc[23] += l * (q0 * Mr[1] - q1 * Mr[0]);
+      acc[24] += l * Mr[0];
+      acc[25] += l * Mr[1];
+      acc[26] += l * Mr[2];
+      acc[27] += s * d2;
+      acc[kRegSums] += l;
+      ++n_corr;
+      continue;
+    }
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
 #pragma unroll
@@ -836,12 +870,15 @@ __device__ __forceinline__ int accumulate_pairs(const Table& t, const unsigned l
   return n_corr;
 }
 
+template <bool kRobust>
 __global__ void __launch_bounds__(kBlock) register_accumulate_kernel(Table t, const unsigned long long* __restrict__ moments,
                                                                      long long capacity, int channels, double voxel,
                                                                      const float* __restrict__ points, long long ld, long long total,
                                                                      const int64_t* __restrict__ offsets, double lo2, double hi2,
-                                                                     double sigma2, unsigned int min_points, int neighbors, RegWork w) {
+                                                                     double sigma2, unsigned int min_points, int neighbors, RegWork w,
+                                                                     double mu) {
 #pragma clang fp contract(off)
+  constexpr int kSums = kRobust ? kRegSumsRobust : kRegSums;
   const long long scan = blockIdx.x / kRegGroups;
   const int group = blockIdx.x % kRegGroups;
   const RegState& st = w.st[scan];
@@ -851,9 +888,9 @@ __global__ void __launch_bounds__(kBlock) register_accumulate_kernel(Table t, co
   long long begin = offsets[scan], end = offsets[scan + 1];
   begin = begin < 0 ? 0 : begin;
   end = end > total ? total : end;
-  double acc[kRegSums];
+  double acc[kSums];
 #pragma unroll
-  for (int k = 0; k < kRegSums; ++k) acc[k] = 0.0;
+  for (int k = 0; k < kSums; ++k) acc[k] = 0.0;
   int n_corr = 0, n_pass = 0;
   for (long long i = begin + group * kBlock + threadIdx.x; i < end; i += static_cast<long long>(kRegGroups) * kBlock) {
     float v[kMaxC];
@@ -862,12 +899,12 @@ __global__ void __launch_bounds__(kBlock) register_accumulate_kernel(Table t, co
     if (gate_sensor(points + i * ld, channels, lo2, hi2, v) != kPass || gate_world(v, X, voxel, wd, fixed) != kPass) continue;
     ++n_pass;
     const long long cell[3] = {fixed[0] >> kFrac, fixed[1] >> kFrac, fixed[2] >> kFrac};
-    n_corr += accumulate_pairs<false>(t, moments, capacity, voxel, wd, cell, X, nullptr, sigma2, min_points, neighbors, acc);
+    n_corr += accumulate_pairs<false, kRobust>(t, moments, capacity, voxel, wd, cell, X, nullptr, sigma2, min_points, neighbors, acc, mu);
   }
   acc[28] = static_cast<double>(n_corr);
   acc[29] = static_cast<double>(n_pass);
-  const double sum = block_sum<kRegSums, kBlock>(acc, threadIdx.x);
-  if (threadIdx.x < kRegSums) w.slab[(scan * kRegGroups + group) * kRegRow + threadIdx.x] = sum;
+  const double sum = block_sum<kSums, kBlock>(acc, threadIdx.x);
+  if (threadIdx.x < kSums) w.slab[(scan * kRegGroups + group) * kRegRow + threadIdx.x] = sum;
 }
 
 // ---- map-to-map alignment (include/rdmnet_hip.h, "voxel map alignment"; tests/voxel_align_restatement.py) ------------------------
@@ -957,16 +994,20 @@ __device__ __forceinline__ void rodrigues(const double* __restrict__ om, double 
     }
 }
 
+// kRobust: the slab rows hold kRegSumsRobust sums and weight_sums takes the last; else they hold kRegSums, slot 30 is not read and
+// weight_sums takes n_corr, the sum of weights that are all one.  weight_sums may be null.
+template <bool kRobust>
 __global__ void __launch_bounds__(kBlock) register_finalize_kernel(RegWork w, int max_iteration, double rot_eps, double trans_eps,
                                                                    double* __restrict__ transforms, double* __restrict__ hessians,
                                                                    double* __restrict__ gradients, double* __restrict__ costs,
-                                                                   int64_t* __restrict__ stats) {
+                                                                   int64_t* __restrict__ stats, double* __restrict__ weight_sums) {
 #pragma clang fp contract(off)
+  constexpr int kSums = kRobust ? kRegSumsRobust : kRegSums;
   const long long scan = blockIdx.x;
   RegState& st = w.st[scan];
   if (st.done) return;
-  __shared__ double tot[kRegSums];
-  if (threadIdx.x < kRegSums) {
+  __shared__ double tot[kSums];
+  if (threadIdx.x < kSums) {
     const double* rows = w.slab + scan * kRegGroups * kRegRow + threadIdx.x;
     double sum = rows[0];
     for (int g = 1; g < kRegGroups; ++g) sum += rows[g * kRegRow];
@@ -991,6 +1032,7 @@ __global__ void __launch_bounds__(kBlock) register_finalize_kernel(RegWork w, in
     gradients[scan * 6 + a] = g[a];
   }
   costs[scan] = tot[27];
+  if (weight_sums != nullptr) weight_sums[scan] = kRobust ? tot[kSums - 1] : static_cast<double>(n_corr);
   int status = -1;  // running
   if (st.last) {
     status = 1;
@@ -1577,6 +1619,19 @@ extern "C" int rdm_voxel_map_register(const void* map, size_t map_bytes, int64_t
                                       double sigma, int64_t min_points, int neighbors, int max_iteration, double rot_eps,
                                       double trans_eps, double* transforms, double* hessians, double* gradients, double* costs,
                                       int64_t* stats, void* ws, size_t ws_bytes, void* stream) {
+  return rdm_voxel_map_register_robust(map, map_bytes, capacity, channels, moments, moments_bytes, voxel, points, ld, total, offsets, poses,
+                                       n_scans, min_range, max_range, sigma, min_points, neighbors, max_iteration, rot_eps, trans_eps, 0.0,
+                                       transforms, hessians, gradients, costs, nullptr, stats, ws, ws_bytes, stream);
+}
+
+// (the messages keep the name rdm_voxel_map_register: it is this function with robust_scale = 0)
+extern "C" int rdm_voxel_map_register_robust(const void* map, size_t map_bytes, int64_t capacity, int channels, const void* moments,
+                                             size_t moments_bytes, double voxel, const float* points, int64_t ld, int64_t total,
+                                             const int64_t* offsets, const double* poses, int64_t n_scans, double min_range,
+                                             double max_range, double sigma, int64_t min_points, int neighbors, int max_iteration,
+                                             double rot_eps, double trans_eps, double robust_scale, double* transforms, double* hessians,
+                                             double* gradients, double* costs, double* weight_sums, int64_t* stats, void* ws,
+                                             size_t ws_bytes, void* stream) {
   using namespace rdm;
   const char* what = "rdm_voxel_map_register";
   Table t;
@@ -1589,6 +1644,8 @@ extern "C" int rdm_voxel_map_register(const void* map, size_t map_bytes, int64_t
   RDM_REQUIRE(neighbors == 1 || neighbors == 7, "rdm_voxel_map_register: neighbors must be 1 or 7 (got %d)", neighbors);
   RDM_REQUIRE(min_points >= 1 && max_iteration >= 0 && rot_eps >= 0.0 && trans_eps >= 0.0,
               "rdm_voxel_map_register: need min_points >= 1, max_iteration >= 0, rot_eps >= 0 and trans_eps >= 0");
+  RDM_REQUIRE(robust_scale >= 0.0 && std::isfinite(robust_scale),
+              "rdm_voxel_map_register_robust: robust_scale must be finite and >= 0 (0: no weights; got %g)", robust_scale);
   Arena ar(ws, ws_bytes);
   RegWork w;
   if (!carve_register(ar, n_scans, w)) {
@@ -1599,17 +1656,19 @@ extern "C" int rdm_voxel_map_register(const void* map, size_t map_bytes, int64_t
   RDM_REQUIRE(transforms && hessians && gradients && costs && stats, "rdm_voxel_map_register: null output");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const unsigned int least = least_points(min_points);
+  const bool robust = robust_scale > 0.0;
   hipLaunchKernelGGL(register_init_kernel, dim3(blocks_for(n_scans)), dim3(kBlock), 0, s, poses, static_cast<long long>(n_scans), w);
   int running = 1;
   for (int k = 0; k <= max_iteration && running > 0;) {
     const int end = max_iteration - k < kRegChunk ? max_iteration + 1 : k + kRegChunk;
     for (; k < end; ++k) {
-      hipLaunchKernelGGL(register_accumulate_kernel, dim3(static_cast<unsigned>(n_scans * kRegGroups)), dim3(kBlock), 0, s, t, m,
-                         static_cast<long long>(capacity), channels, voxel, points, static_cast<long long>(ld),
-                         static_cast<long long>(total), offsets, min_range * min_range, max_range * max_range, sigma * sigma, least,
-                         neighbors, w);
-      hipLaunchKernelGGL(register_finalize_kernel, dim3(static_cast<unsigned>(n_scans)), dim3(kBlock), 0, s, w, max_iteration, rot_eps,
-                         trans_eps, transforms, hessians, gradients, costs, stats);
+      hipLaunchKernelGGL(robust ? register_accumulate_kernel<true> : register_accumulate_kernel<false>,
+                         dim3(static_cast<unsigned>(n_scans * kRegGroups)), dim3(kBlock), 0, s, t, m, static_cast<long long>(capacity),
+                         channels, voxel, points, static_cast<long long>(ld), static_cast<long long>(total), offsets,
+                         min_range * min_range, max_range * max_range, sigma * sigma, least, neighbors, w, robust_scale);
+      hipLaunchKernelGGL(robust ? register_finalize_kernel<true> : register_finalize_kernel<false>,
+                         dim3(static_cast<unsigned>(n_scans)), dim3(kBlock), 0, s, w, max_iteration, rot_eps, trans_eps, transforms,
+                         hessians, gradients, costs, stats, weight_sums);
     }
     if (const int rc = launch_status("rdm_voxel_map_register")) return rc;
     RDM_HIP_CHECK(hipMemcpyAsync(&running, w.running, sizeof(int), hipMemcpyDeviceToHost, s));  // one 4-byte read-back per chunk
@@ -1668,8 +1727,8 @@ extern "C" int rdm_voxel_map_align(const void* map, size_t map_bytes, int64_t ca
                          static_cast<long long>(sums_ld), reinterpret_cast<const long long*>(moment_sums), source_voxel,
                          static_cast<long long>(total), offsets, sigma * sigma, least_points(min_points),
                          least_points(source_min_points), neighbors, w);
-      hipLaunchKernelGGL(register_finalize_kernel, dim3(static_cast<unsigned>(n_sets)), dim3(kBlock), 0, s, w, max_iteration, rot_eps,
-                         trans_eps, transforms, hessians, gradients, costs, stats);
+      hipLaunchKernelGGL(register_finalize_kernel<false>, dim3(static_cast<unsigned>(n_sets)), dim3(kBlock), 0, s, w, max_iteration,
+                         rot_eps, trans_eps, transforms, hessians, gradients, costs, stats, static_cast<double*>(nullptr));
     }
     if (const int rc = launch_status(what)) return rc;
     RDM_HIP_CHECK(hipMemcpyAsync(&running, w.running, sizeof(int), hipMemcpyDeviceToHost, s));  // one 4-byte read-back per chunk

@@ -5,6 +5,7 @@ matrices are row-major with a row stride that is a multiple of 4 floats (`.strid
 widths are passed explicitly where they differ.  No function here falls back to torch math.
 """
 import ctypes
+import numbers
 
 import torch
 
@@ -1077,15 +1078,23 @@ class VoxelMap:
                     entropy=ent / n_full if n_full else float('nan'))
 
     def register(self, clouds, poses, *, sigma=0.02, min_points=4, neighbors=1, max_iteration=30, rot_eps=1e-5, trans_eps=1e-4,
-                 min_range=0.0, max_range=float('inf')):
+                 min_range=0.0, max_range=float('inf'), robust_scale=None):
         """Scan-to-map registration on the per-voxel Gaussians (rdm_voxel_map_register): every scan of the batch
         is registered, from its initial pose, against this map -- point-to-distribution, the NDT / voxelised-GICP family.  clouds,
         poses, min_range, max_range: as `integrate` takes them (poses: the initial poses).  sigma: the isotropic noise of a scan point
         in metres, added to every voxel's covariance; a voxel takes part with at least min_points points; neighbors 1 (the point's own
         voxel) or 7 (and its six face neighbours: a wider basin, less accurate from a small error); at most max_iteration Gauss-Newton
-        updates, until one is below rot_eps (rad) and trans_eps (m).  The map is only read.  -> MapRegistrationResult (device
-        tensors).  One 4-byte read-back per eight iterations."""
+        updates, until one is below rot_eps (rad) and trans_eps (m).  robust_scale mu: None (every pair has weight one) or a positive
+        finite number in units of squared Mahalanobis distance: a pair at the distance d2 = r^T M r is weighted by (mu / (mu + d2))^2
+        (Geman-McClure, rdm_voxel_map_register_robust), so that an object which stands elsewhere in the scan than in the map does not
+        pull the pose; 9 is a value to start from.  The result's weight_sum is then the correspondences by weight.  The map is only
+        read.  -> MapRegistrationResult (device tensors).  One 4-byte read-back per eight iterations."""
         self._need_moments('register')
+        if robust_scale is not None:
+            if isinstance(robust_scale, (str, bytes, bool)) or not isinstance(robust_scale, numbers.Real) or not (
+                    0 < float(robust_scale) < float('inf')):
+                raise ValueError(f'robust_scale must be None or a positive finite number, got {robust_scale!r}')
+            robust_scale = float(robust_scale)
         points, offsets, n, X, lo, hi = self._packed('register', clouds, poses, min_range, max_range)
         sigma, rot_eps, trans_eps = float(sigma), float(rot_eps), float(trans_eps)
         min_points, neighbors, max_iteration = int(min_points), int(neighbors), int(max_iteration)
@@ -1099,16 +1108,22 @@ class VoxelMap:
         real = torch.zeros((n, 59), dtype=torch.float64, device=dev)  # transforms, hessians, gradients, costs
         stats = torch.zeros((n, 4), dtype=torch.int64, device=dev)
         T, H, g, cost = (real.view(-1)[a * n:b * n].view(n, b - a) for a, b in ((0, 16), (16, 52), (52, 58), (58, 59)))
+        weight_sum = None if robust_scale is None else torch.zeros((n,), dtype=torch.float64, device=dev)
         if n > 0:
             points, ld, total, offsets, Xd = self._on_device(points, offsets, X)
             with torch.cuda.device(dev):
                 ws = scratch(dev, L.rdm_voxel_map_register_workspace_bytes(n))
-                _lib.check(L.rdm_voxel_map_register(*self._head(), self._mom.data_ptr(), self._mom.numel(), self.voxel, points.data_ptr(), ld,
-                                                    total, offsets.data_ptr(), Xd.data_ptr(), n, lo, hi, sigma, min_points, neighbors,
-                                                    max_iteration, rot_eps, trans_eps, T.data_ptr(), H.data_ptr(), g.data_ptr(),
-                                                    cost.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
-                           'rdm_voxel_map_register')
-        return MapRegistrationResult(T.view(n, 4, 4), H.view(n, 6, 6), g, cost.view(n), stats[:, 0], stats[:, 1], stats[:, 2], stats[:, 3])
+                head = (*self._head(), self._mom.data_ptr(), self._mom.numel(), self.voxel, points.data_ptr(), ld, total, offsets.data_ptr(),
+                        Xd.data_ptr(), n, lo, hi, sigma, min_points, neighbors, max_iteration, rot_eps, trans_eps)
+                tail = (stats.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr())
+                if robust_scale is None:
+                    _lib.check(L.rdm_voxel_map_register(*head, T.data_ptr(), H.data_ptr(), g.data_ptr(), cost.data_ptr(), *tail),
+                               'rdm_voxel_map_register')
+                else:
+                    _lib.check(L.rdm_voxel_map_register_robust(*head, robust_scale, T.data_ptr(), H.data_ptr(), g.data_ptr(), cost.data_ptr(),
+                                                               weight_sum.data_ptr(), *tail), 'rdm_voxel_map_register_robust')
+        return MapRegistrationResult(T.view(n, 4, 4), H.view(n, 6, 6), g, cost.view(n), stats[:, 0], stats[:, 1], stats[:, 2], stats[:, 3],
+                                     weight_sum)
 
     def align(self, sources, poses, *, sigma=0.02, min_points=4, source_min_points=4, neighbors=7, max_iteration=30, rot_eps=1e-5,
               trans_eps=1e-4):
@@ -1483,19 +1498,23 @@ class MapRegistrationResult:
     """What VoxelMap.register returns, device tensors with one row per scan: transformations float64 [n, 4, 4] (the refined poses),
     information float64 [n, 6, 6] (H = the sum of J^T M J at the returned pose, rotation first: usable as the weight of a scan-to-map
     edge), gradient float64 [n, 6], cost float64 [n] (the sum of r^T M r), and int64 [n] each: iterations (updates applied),
-    num_correspondences (point-voxel pairs of the last evaluation), num_points (rows that passed the gates) and status (STATUS)."""
+    num_correspondences (point-voxel pairs of the last evaluation), num_points (rows that passed the gates) and status (STATUS).
+    weight_sum: None, or with register's robust_scale float64 [n], the sum of the pairs' weights (num_correspondences by weight);
+    information, gradient and cost are then the weighted sums."""
     STATUS = ('max_iteration', 'converged', 'degenerate')
 
-    def __init__(self, transformations, information, gradient, cost, iterations, num_correspondences, num_points, status):
+    def __init__(self, transformations, information, gradient, cost, iterations, num_correspondences, num_points, status, weight_sum=None):
         self.transformations, self.information, self.gradient, self.cost = transformations, information, gradient, cost
         self.iterations, self.num_correspondences, self.num_points, self.status = iterations, num_correspondences, num_points, status
+        self.weight_sum = weight_sum
 
     def __repr__(self):
         rows = torch.stack([self.iterations, self.num_correspondences, self.num_points, self.status]).cpu().tolist()
         cost = self.cost.cpu().tolist()
+        by_weight = [''] * len(cost) if self.weight_sum is None else [f' ({w:.6g} by weight)' for w in self.weight_sum.cpu().tolist()]
         return 'MapRegistrationResult(' + '; '.join(
-            f'{k}: {self.STATUS[s] if 0 <= s < 3 else s} after {i} updates, {c} correspondences of {p} points, cost {v:.6g}'
-            for k, (i, c, p, s, v) in enumerate(zip(*rows, cost))) + ')'
+            f'{k}: {self.STATUS[s] if 0 <= s < 3 else s} after {i} updates, {c} correspondences{w} of {p} points, cost {v:.6g}'
+            for k, (i, c, p, s, v, w) in enumerate(zip(*rows, cost, by_weight))) + ')'
 
 
 class MapQueryResult:

@@ -6,7 +6,7 @@
                                    [--map-range LO HI] [--map-batch 64] [--map-sharpness [--map-sharpness-min-points 4]]
                                    [--map-min-scans 1]
                                    [--map-refine [--map-refine-sigma 0.02] [--map-refine-neighbors {1,7}] [--map-refine-iterations 30]
-                                    [--map-refine-min-scans 1]]
+                                    [--map-refine-min-scans 1] [--map-refine-robust MU]]
                                    [--map-clean [--map-clean-max-d2 D] [--map-clean-sigma 0.02] [--map-clean-neighbors {1,7}]]
                                    [--map-save] [--map-prior FILE [--map-localize] [--map-prior-align [--map-prior-initial FILE]]]]
 
@@ -33,7 +33,10 @@ the chained ones; the result is a third variant, `refined`, with its own error, 
 also keeps in how many scans every voxel was seen (`ops.VoxelMap(observations=True)`) and every variant's map is pruned to the voxels
 seen in at least N scans before anything is written or reported -- a moving object is in a voxel in one scan, static structure in
 many --; a `persistent:` line after every `map:` line says what was kept.  --map-refine-min-scans N registers frame k >= N against
-that pruned map instead of the full one.  With --map-clean (and --map-min-scans N >= 2, a finite --map-clean-max-d2 D, or both) every
+that pruned map instead of the full one.  --map-refine-robust MU (read by --map-refine and --map-localize; off by default) weights every
+point-voxel pair of those registrations by (MU / (MU + d2))^2, d2 its squared Mahalanobis distance (`ops.VoxelMap.register`'s
+robust_scale; 9 is a value to start from), so that an object which moved does not pull the poses, and a `robust weights:` line after the
+`refined against the map` / `localized against` line says how many correspondences a frame has by weight.  With --map-clean (and --map-min-scans N >= 2, a finite --map-clean-max-d2 D, or both) every
 point of every scan is judged by each variant's full map, before that prune (`clean_scans`, `ops.VoxelMap.query`): the scans are written
 to `{seq}_{variant}_clean/` under their own names without the points that have no voxel, whose voxel was seen in fewer than N scans or that
 lie further than D (squared Mahalanobis distance; the map then keeps second moments) from their voxel's Gaussian, and a `clean:` line after
@@ -324,14 +327,16 @@ def clean_line(seq, what, tallies, min_scans, max_d2, prior=None):
 def refine_against_map(paths, poses, voxel=MAP_DEFAULTS['voxel'], channels=None, min_range=0.0, max_range=math.inf,
                        sigma=REFINE_DEFAULTS['sigma'], neighbors=REFINE_DEFAULTS['neighbors'], max_iteration=REFINE_DEFAULTS['iterations'],
                        min_points=REFINE_DEFAULTS['min_points'], capacity=1 << 20, device='cuda', min_scans=REFINE_DEFAULTS['min_scans'],
-                       observations=False):
+                       observations=False, robust_scale=None):
     """Sequential scan-to-map refinement of the trajectory `poses` ([n, 4, 4]) of the scans `paths` (as build_map reads them): frame
     0 keeps its pose and is integrated into a map with moments; every later frame k starts from refined[k - 1] inv(poses[k - 1])
     poses[k] -- the previous frame's correction carried forward --, is registered against the map so far (ops.VoxelMap.register)
     and integrated under the result.  A degenerate frame (status 2: no correspondence, or a singular system) keeps its initial
     pose.  min_scans N > 1: frame k >= N is registered against vmap.pruned(N), the voxels seen in at least N of the frames before it
     (earlier frames against the full map); every frame is still integrated into the full map, which then keeps observations, as it does
-    with observations=True.  The scans are read on a background thread, one ahead.  -> (refined float64 [n, 4, 4], the ops.VoxelMap of all frames
+    with observations=True.  robust_scale: None, or ops.VoxelMap.register's (every pair weighted by its Mahalanobis distance, so that
+    what moves between the frames does not pull the poses); the dict then also holds weights [n], the correspondences by weight.  The
+    scans are read on a background thread, one ahead.  -> (refined float64 [n, 4, 4], the ops.VoxelMap of all frames
     under the refined poses, dict(frames, iterations [n], correspondences [n], status [n], degenerate)); frame 0 has status -1."""
     paths = list(paths)
     poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
@@ -349,6 +354,7 @@ def refine_against_map(paths, poses, voxel=MAP_DEFAULTS['voxel'], channels=None,
     refined = poses.copy()
     n = len(paths)
     iterations, corr, status = np.zeros(n, np.int64), np.zeros(n, np.int64), np.full(n, -1, np.int64)
+    weights = np.zeros(n, np.float64)
     vmap = None
     for k, cloud in prepare._read_ahead(lambda k: prepare.load_scan(paths[k]), list(range(n))):
         if cloud.ndim != 2 or cloud.shape[1] < 3:
@@ -363,13 +369,18 @@ def refine_against_map(paths, poses, voxel=MAP_DEFAULTS['voxel'], channels=None,
             init = refined[k - 1] @ np.linalg.inv(poses[k - 1]) @ poses[k]
             target = vmap.pruned(min_scans) if min_scans > 1 and k >= min_scans else vmap
             res = target.register([points], init[None], sigma=sigma, min_points=min_points, neighbors=neighbors, max_iteration=max_iteration,
-                                min_range=min_range, max_range=max_range)
+                                min_range=min_range, max_range=max_range, robust_scale=robust_scale)
             iterations[k], corr[k], status[k] = torch.stack([res.iterations, res.num_correspondences, res.status]).cpu().numpy()[:, 0]
+            if robust_scale is not None:
+                weights[k] = float(res.weight_sum[0])
             refined[k] = init if status[k] == 2 else res.transformations[0].cpu().numpy()
         vmap.integrate([points], refined[k][None], min_range, max_range)
     if vmap is None:
         vmap = ops.VoxelMap(voxel, channels=4 if channels is None else int(channels), capacity=capacity, device=device, **kind)
-    return refined, vmap, dict(frames=n, iterations=iterations, correspondences=corr, status=status, degenerate=int((status == 2).sum()))
+    stats = dict(frames=n, iterations=iterations, correspondences=corr, status=status, degenerate=int((status == 2).sum()))
+    if robust_scale is not None:
+        stats['weights'] = weights
+    return refined, vmap, stats
 
 
 def refine_line(seq, stats):
@@ -378,12 +389,20 @@ def refine_line(seq, stats):
             f"{stats['correspondences'].sum() / moved:.0f} correspondences per frame, {stats['degenerate']} degenerate frames")
 
 
+def robust_line(seq, what, scale, stats):
+    """what: 'refined' (per registered frame: all but the first) or 'localized' (per frame); stats: with `weights`."""
+    frames = max(stats['frames'] - 1 if what == 'refined' else stats['frames'], 1)
+    return (f"seq {seq} {what} robust weights: scale {scale:g}, {stats['weights'].sum() / frames:.1f} of "
+            f"{stats['correspondences'].sum() / frames:.0f} correspondences per frame by weight")
+
+
 def localize_against_map(paths, poses, vmap, *, sigma=REFINE_DEFAULTS['sigma'], neighbors=REFINE_DEFAULTS['neighbors'],
                          max_iteration=REFINE_DEFAULTS['iterations'], min_points=REFINE_DEFAULTS['min_points'], min_range=0.0,
-                         max_range=math.inf, batch=MAP_DEFAULTS['batch']):
+                         max_range=math.inf, batch=MAP_DEFAULTS['batch'], robust_scale=None):
     """Every scan of `paths` (as build_map reads them) registered from its pose in `poses` ([n, 4, 4]) against the fixed map `vmap` (an
     ops.VoxelMap with moments, such as ops.VoxelMap.load gives; ops.VoxelMap.register).  The frames are independent: `batch` scans are
-    one register call, and nothing is integrated -- the map is only read.  A degenerate frame (status 2) keeps its pose.  -> (localized
+    one register call, and nothing is integrated -- the map is only read.  A degenerate frame (status 2) keeps its pose.  robust_scale:
+    None, or ops.VoxelMap.register's; the dict then also holds weights [n], the correspondences by weight.  -> (localized
     float64 [n, 4, 4], dict(frames, iterations [n], correspondences [n], status [n], degenerate))."""
     paths = list(paths)
     poses = np.asarray(poses, dtype=np.float64).reshape(-1, 4, 4)
@@ -400,16 +419,22 @@ def localize_against_map(paths, poses, vmap, *, sigma=REFINE_DEFAULTS['sigma'], 
     n = len(paths)
     localized = poses.copy()
     iterations, corr, status = np.zeros(n, np.int64), np.zeros(n, np.int64), np.full(n, -1, np.int64)
+    weights = np.zeros(n, np.float64)
     for (lo, hi), (points, offsets) in _read_batches(paths, batch):
         if points.shape[1] < vmap.channels:
             raise TrajectoryError(f'{paths[lo]}: {points.shape[1]} columns, the map has {vmap.channels} channels')
         res = vmap.register((torch.from_numpy(points).to(vmap.device), torch.from_numpy(offsets)), poses[lo:hi], sigma=sigma,
                             min_points=min_points, neighbors=neighbors, max_iteration=max_iteration, min_range=min_range,
-                            max_range=max_range)
+                            max_range=max_range, robust_scale=robust_scale)
         iterations[lo:hi], corr[lo:hi], status[lo:hi] = torch.stack([res.iterations, res.num_correspondences, res.status]).cpu().numpy()
+        if robust_scale is not None:
+            weights[lo:hi] = res.weight_sum.cpu().numpy()
         moved = status[lo:hi] != 2
         localized[lo:hi][moved] = res.transformations.cpu().numpy()[moved]
-    return localized, dict(frames=n, iterations=iterations, correspondences=corr, status=status, degenerate=int((status == 2).sum()))
+    stats = dict(frames=n, iterations=iterations, correspondences=corr, status=status, degenerate=int((status == 2).sum()))
+    if robust_scale is not None:
+        stats['weights'] = weights
+    return localized, stats
 
 
 def localize_line(seq, stats, prior):
@@ -541,6 +566,8 @@ def map_paths(args, seqs):
                           ('--map-refine-min-scans', 'min_scans')):
             if getattr(args, 'map_refine_' + key, None) not in (None, REFINE_DEFAULTS[key]) and not ((localize or align) and key != 'min_scans'):
                 raise TrajectoryError(f'{flag} needs --map-refine' + ('' if key == 'min_scans' else ' (or --map-localize)'))
+        if getattr(args, 'map_refine_robust', None) is not None and not localize:
+            raise TrajectoryError('--map-refine-robust needs --map-refine (or --map-localize)')
     if (refine or localize or align) and (not (args.map_refine_sigma > 0 and math.isfinite(args.map_refine_sigma)) or args.map_refine_iterations < 0):
         raise TrajectoryError('--map-refine-sigma must be > 0 and --map-refine-iterations >= 0')
     if refine and getattr(args, 'map_refine_min_scans', REFINE_DEFAULTS['min_scans']) < 1:
@@ -673,10 +700,13 @@ def run(args, emit=print):
                                                   sigma=args.map_refine_sigma, neighbors=args.map_refine_neighbors,
                                                   max_iteration=args.map_refine_iterations,
                                                   min_scans=getattr(args, 'map_refine_min_scans', None) or REFINE_DEFAULTS['min_scans'],
-                                                  observations=(getattr(args, 'map_min_scans', None) or 1) > 1)
+                                                  observations=(getattr(args, 'map_min_scans', None) or 1) > 1,
+                                                  robust_scale=getattr(args, 'map_refine_robust', None))
         if seq in gts:
             emit(report_line(seq, 'refined', absolute_trajectory_error(refined[1:], gts[seq])))
         emit(refine_line(seq, stats))
+        if 'weights' in stats:
+            emit(robust_line(seq, 'refined', args.map_refine_robust, stats))
         write_kitti_poses(osp.join(args.out, f'{seq}_refined.txt'), refined)
         write_map(args, seq, 'refined', scans[seq], refined, emit, vmap=vmap, to_prior=to_prior(seq)[0])
 
@@ -686,12 +716,14 @@ def run(args, emit=print):
         T = to_prior(seq)[0]
         localized, stats = localize_against_map(scans[seq], base if T is None else T @ base, vmap, sigma=args.map_refine_sigma, neighbors=args.map_refine_neighbors,
                                                 max_iteration=args.map_refine_iterations, min_range=lo, max_range=hi,
-                                                batch=args.map_batch)
+                                                batch=args.map_batch, robust_scale=getattr(args, 'map_refine_robust', None))
         if T is not None:  # back into the trajectory's frame; a degenerate frame keeps its pose
             localized = np.where((stats['status'] == 2)[:, None, None], base, np.linalg.inv(T) @ localized)
         if seq in gts:
             emit(report_line(seq, 'localized', absolute_trajectory_error(localized[1:], gts[seq])))
         emit(localize_line(seq, stats, prior))
+        if 'weights' in stats:
+            emit(robust_line(seq, 'localized', args.map_refine_robust, stats))
         write_kitti_poses(osp.join(args.out, f'{seq}_localized.txt'), localized)
         write_map(args, seq, 'localized', scans[seq], localized, emit, to_prior=T)
 
@@ -723,6 +755,17 @@ def run(args, emit=print):
         if getattr(args, 'map_localize', False):
             localize(seq, nodes[noff[g]:noff[g + 1]])
     return res
+
+
+def positive_finite(text):
+    """argparse type: a float > 0 and finite."""
+    try:
+        value = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'{text!r} is not a number')
+    if not (value > 0 and math.isfinite(value)):
+        raise argparse.ArgumentTypeError(f'{text!r} is not positive and finite')
+    return value
 
 
 def make_parser():
@@ -765,6 +808,10 @@ def make_parser():
                     help="a point is matched to its own voxel (1) or to it and its six face neighbours (7: a wider basin)")
     ap.add_argument('--map-refine-iterations', type=int, default=REFINE_DEFAULTS['iterations'], metavar='N',
                     help='at most N Gauss-Newton updates per frame')
+    ap.add_argument('--map-refine-robust', type=positive_finite, default=None, metavar='MU',
+                    help='weight every point-voxel pair of --map-refine and --map-localize by (MU / (MU + d2))^2, d2 its squared '
+                         'Mahalanobis distance, so that what stands elsewhere in a scan than in the map does not pull the pose; 9 is a '
+                         'value to start from (default: off, every pair has weight one)')
     ap.add_argument('--map-refine-min-scans', type=int, default=REFINE_DEFAULTS['min_scans'], metavar='N',
                     help='register frame k >= N against the voxels seen in at least N of the frames before it (needs --map-refine)')
     ap.add_argument('--map-clean', action='store_true',

@@ -1,7 +1,7 @@
 """Times the voxel map (ops.VoxelMap) on synthetic scans along a synthetic drive.
 
   python tools/map_bench.py [--frames 256] [--points 120000 | 18000] [--reps 3] [--batch 64] [--voxel 0.3] [--cpu] [--cpu-frames 8]
-                              [--moments] [--observations] [--register] [--align] [--query] [--merge] [--digest]
+                              [--moments] [--observations] [--register [--robust MU]] [--align] [--query] [--merge] [--digest]
 With --digest (and nothing else): no timing, one sha1 line per output of the voxel map on the bundled scans (see digest()), for
 comparing the bits of two builds of the library.  Otherwise prints one JSON line per case:
   * integrate: --frames scans of --points points (120 000: a raw scan; 18 000: a down-sampled one), xyz + intensity, integrated in
@@ -25,7 +25,10 @@ comparing the bits of two builds of the library.  Otherwise prints one JSON line
     per evaluation (max_iteration = 0, one scan), ms per full registration of one scan and of a batch of 64 scans (default
     tolerances), the point-voxel pairs per second of the evaluation, and ms per iteration (accumulate + finalize launches) from runs
     of 4 and 12 forced updates of the batch; with --cpu also the seconds of one evaluation by tests/voxel_register_restatement.py
-    and whether its counts equal the GPU's;
+    and whether its counts equal the GPU's; with --robust MU also ms per evaluation and per registration of one scan with the robust
+    weights (robust_scale MU) beside the plain form's, and ms per iteration of the batch of 64 likewise, the two alternated call by
+    call in one process (`*_alternated`: the plain form's figures of that alternation), their ratios, and the scan's correspondences
+    by weight;
   * with --align (and nothing else of the above): the map-to-map alignment (ops.VoxelMap.align) at neighbors 1 and 7 for both scan
     shapes: the target is --register's map of min(--frames, 64) scans, the source the map with moments of the same scans built in a
     frame turned by 0.3 rad and shifted by 3 m, the start 5 cm / 5 mrad off the transform between the two: ms per evaluation
@@ -77,6 +80,25 @@ def timed(fn, reps):
         torch.cuda.synchronize()
         times.append(a.elapsed_time(b))
     return float(np.median(times)), out
+
+
+def timed_alternated(fn_a, fn_b, reps):
+    """Median device times in ms of fn_a() and fn_b(), called in turn (a, b, a, b, ...) after one warm-up call of each
+    -> (ms_a, ms_b, the last output of fn_a, of fn_b)."""
+    import torch
+    fn_a()
+    fn_b()
+    torch.cuda.synchronize()
+    times, out = ([], []), [None, None]
+    for _ in range(reps):
+        for k, fn in enumerate((fn_a, fn_b)):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            out[k] = fn()
+            b.record()
+            torch.cuda.synchronize()
+            times[k].append(a.elapsed_time(b))
+    return float(np.median(times[0])), float(np.median(times[1])), out[0], out[1]
 
 
 def synthetic_scans(frames, points, seed=0):
@@ -187,6 +209,25 @@ def register_cases(a):
                     'converged_in_batch': int((many.status == 1).sum()),
                     'ms_per_iteration_batch_of_64': round((ms_12 - ms_4) / 8.0, 4),
                     'pairs_per_s_batch': round(float(many.num_correspondences.sum()) / ((ms_12 - ms_4) / 8.0) * 1e3)}
+            if a.robust is not None:
+                rkw = dict(kw, robust_scale=a.robust)
+                ev_p, ev_w, _, wev = timed_alternated(lambda: vmap.register(clouds[:1], off[:1], max_iteration=0, **kw),
+                                                      lambda: vmap.register(clouds[:1], off[:1], max_iteration=0, **rkw), a.reps)
+                one_p, one_w, _, wone = timed_alternated(lambda: vmap.register(clouds[:1], off[:1], **kw),
+                                                         lambda: vmap.register(clouds[:1], off[:1], **rkw), a.reps)
+                forced = dict(rot_eps=0.0, trans_eps=0.0)
+                p4, w4, _, _ = timed_alternated(lambda: vmap.register(batch, Xb, max_iteration=4, **forced, **kw),
+                                                lambda: vmap.register(batch, Xb, max_iteration=4, **forced, **rkw), a.reps)
+                p12, w12, _, _ = timed_alternated(lambda: vmap.register(batch, Xb, max_iteration=12, **forced, **kw),
+                                                  lambda: vmap.register(batch, Xb, max_iteration=12, **forced, **rkw), a.reps)
+                line.update(ms_per_iteration_batch_of_64_alternated=round((p12 - p4) / 8.0, 4),
+                            ms_per_iteration_batch_of_64_weighted=round((w12 - w4) / 8.0, 4),
+                            weighted_over_plain_iteration_batch=round((w12 - w4) / (p12 - p4), 3))
+                line.update(robust_scale=a.robust, ms_per_evaluation_alternated=round(ev_p, 3), ms_per_evaluation_weighted=round(ev_w, 3),
+                            weighted_over_plain_evaluation=round(ev_w / ev_p, 3), ms_one_scan_alternated=round(one_p, 3),
+                            ms_one_scan_weighted=round(one_w, 3), weighted_over_plain_one_scan=round(one_w / one_p, 3),
+                            iterations_one_scan_weighted=int(wone.iterations[0]), status_one_scan_weighted=int(wone.status[0]),
+                            weight_sum_per_evaluation=round(float(wev.weight_sum[0]), 1))
             if a.cpu:
                 import voxel_moments_restatement as MR
                 import voxel_register_restatement as RR
@@ -384,6 +425,8 @@ def main(argv=None):
     ap.add_argument('--observations', action='store_true',
                     help='also time integrate with the per-voxel scan observations, extract_observations, pruned and a refinement frame')
     ap.add_argument('--register', action='store_true', help='time the scan-to-map registration and nothing else')
+    ap.add_argument('--robust', type=float, default=None, metavar='MU',
+                    help='with --register: also time the registration with robust weights of this scale, alternated with the plain form')
     ap.add_argument('--align', action='store_true', help='time the map-to-map alignment beside the registration and nothing else')
     ap.add_argument('--query', action='store_true', help='time the per-point queries beside integrate and nothing else')
     ap.add_argument('--merge', action='store_true', help='time the export and the import of a map state beside its rehash and nothing else')
@@ -391,6 +434,8 @@ def main(argv=None):
     ap.add_argument('--cpu', action='store_true', help='also time the NumPy restatement and compare the maps bit for bit')
     ap.add_argument('--cpu-frames', type=int, default=8)
     a = ap.parse_args(argv)
+    if a.robust is not None and not (a.register and a.robust > 0 and np.isfinite(a.robust)):
+        ap.error('--robust needs --register and a positive finite MU')
     import torch
     from rdmnet_amd import _lib, ops
     assert torch.cuda.is_available(), 'map_bench needs a GPU'
