@@ -329,6 +329,37 @@ int64_t rdm_pose_graph_separator_host(int64_t n_nodes, int64_t n_edges, const in
  * pivot and for a separator above the limit.                                                                                   */
 int rdm_pose_graph_direct_host(int64_t n_nodes, int64_t n_edges, const int64_t* edges_host, const double* diag, const double* off,
                                const double* rhs, double* out);
+/* Marginal covariances of a batch of graphs in rdm_pose_graph_optimize's layout: per graph, with
+ * H = sum_e w_e J_e^T L_e J_e over the free nodes 1 .. n - 1 -- the undamped Gauss-Newton matrix at `nodes` (normally the optimiser's
+ * output), linearised as the optimiser linearises, `weights` (device [E], >= 0; null: all 1 -- the optimiser's weights_out fits) in
+ * the line process's place -- covariances_out (device [N, 36], float64) row i is (H^-1)_ii: the covariance of node i's right
+ * perturbation X_i [Exp(dw) | dt], rotation first, conditioned on node 0, whose row is zero.  The factor is H^-1, not (2 H)^-1: the
+ * information matrices are inverse covariances of the residuals.  Every block is written exactly symmetric (an entry above the
+ * diagonal is a copy of the one below).  The blocks come from the direct solve's factors at lambda = 0 by a selected inversion --
+ * Sigma_SS = C^-1 on the separator and one backward recurrence per run -- so the separator limit above holds here too and nothing
+ * dense of size N is formed; no float atomics and every sum in an order the graph alone decides: a graph's rows are the same bits
+ * alone, anywhere in a batch and from run to run.  report_host [G, 2]: status (0, or 4: a pivot of a run or of the Schur complement
+ * is not positive -- zero weights that cut a node off, an indefinite information matrix, a graph of several nodes without edges;
+ * that graph's rows but row 0 are NaN, the call is still RDM_OK and the other graphs are unaffected) and the separator's size.
+ * RDM_ERR_ARG with every output untouched for what rdm_pose_graph_optimize refuses (non-finite entries, asymmetric information, an
+ * angle beyond the limit, a self edge, an edge outside its graph, the size limits), for a negative or non-finite weight and for a
+ * graph above the separator limit (the message names the graph, the count and the limit).  The workspace size is exact and reads
+ * the edges; 0 with rdm_last_error set for a graph above the limit or bad arguments.                                             */
+size_t rdm_pose_graph_marginals_workspace_bytes(int64_t n_graphs, const int64_t* graph_node_offsets_host,
+                                                const int64_t* graph_edge_offsets_host, const int64_t* edges_host);
+int rdm_pose_graph_marginals(int64_t n_graphs, const int64_t* graph_node_offsets_host, const int64_t* graph_edge_offsets_host,
+                             const double* nodes, const int64_t* edges_host, const double* transforms, const double* informations,
+                             const double* weights, double* covariances_out, double* report_host, void* ws, size_t ws_bytes,
+                             void* stream);
+/* The same functions as the kernels run them and in their order, on the host, on a system given as rdm_pose_graph_direct_host
+ * takes it (diag, off; all pointers host memory): out [n_nodes, 36], row 0 zero.  RDM_ERR_ARG ("not positive") for a failed pivot and
+ * for a separator above the limit.                                                                                              */
+int rdm_pose_graph_marginals_host(int64_t n_nodes, int64_t n_edges, const int64_t* edges_host, const double* diag, const double* off,
+                                  double* out);
+/* Measurement hook (tools/pose_graph_bench.py --marginals): with a device buffer of 3 long long per run of the next calls of this
+ * thread, the run sweep's lane 0 stores the 100 MHz clock ticks it spent in the columns' products, the butterflies and the nodes'
+ * steps; null (the default) turns it off.                                                                                       */
+int rdm_dbg_pose_graph_marginals_ticks(long long* device_ticks);
 
 /* ---- dense contraction ---------------------------------------------------------------------
  * C[b] = act((A[b] (m x k) * op(B[b])) / rowdiv[row] + bias[col]) in fp32 on the f32 MFMA.

@@ -147,6 +147,11 @@ SIGNATURES = {
     'rdm_pose_graph_direct_max_separator': (c_int, []),
     'rdm_pose_graph_separator_host': (c_i64, [c_i64, c_i64, c_void, c_void, c_i64]),
     'rdm_pose_graph_direct_host': (c_int, [c_i64, c_i64, c_void, c_void, c_void, c_void, c_void]),
+    'rdm_pose_graph_marginals_workspace_bytes': (c_size, [c_i64, c_void, c_void, c_void]),
+    'rdm_pose_graph_marginals': (c_int, [c_i64, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_size,
+                                         c_void]),
+    'rdm_pose_graph_marginals_host': (c_int, [c_i64, c_i64, c_void, c_void, c_void, c_void]),
+    'rdm_dbg_pose_graph_marginals_ticks': (c_int, [c_void]),
     'rdm_pose_graph_edge_terms_host': (c_int, [c_void, c_void, c_void, c_void, ctypes.c_double, c_int, c_void]),
     'rdm_pose_graph_retract_host': (c_int, [c_void, c_void, c_void]),
     'rdm_neighbor_histogram': (c_int, [c_void, c_i64, c_void, c_int, c_void]),

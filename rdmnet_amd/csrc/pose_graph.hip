@@ -20,7 +20,12 @@
 // Every sum has ONE place: assemble_nodes (node blocks, gradient and the chain's off-diagonal sums, for pg_solve_kernel and
 // pg_direct_blocks_kernel), add_block and block_mul (a sum of Hab blocks or their transposes; t = B z or B^T z), precondition<kPre>
 // (z = M^-1 r, before the conjugate-gradient loop and in it), direct_run_factor / direct_run_back (a run of the direct solve, and the
-// whole chain of rdm_pose_graph_chain_host).  The fixed order above holds because there is no second copy to edit another way.
+// whole chain of rdm_pose_graph_chain_host), dense_factor (the Schur complement's block Cholesky, for pg_direct_solve_kernel and
+// pg_marg_separator_kernel).  The fixed order above holds because there is no second copy to edit another way.
+//
+// rdm_pose_graph_marginals (the marginal covariance of every pose at given poses and weights) is a second, single-pass caller of the
+// same pieces: edge_terms with the given weight in the line process's place, assemble_nodes, the direct solve's factors at lambda = 0,
+// then a selected inversion (pg_marg_separator_kernel, pg_marg_sweep_kernel) under the same guarantee.
 #include "common.h"
 #include "../../include/rdmnet_hip.h"
 
@@ -55,7 +60,7 @@ constexpr double kLambdaMin = 1e-12;
 constexpr double kLambdaMax = 1e12;       // a rejection above it ends the solve (no decrease is left: stop reason `cost`)
 
 enum : int { STOP_NONE = 0, STOP_GRADIENT = 1, STOP_COST = 2, STOP_MAX_ITERATIONS = 3, STOP_EMPTY = 4 };
-enum : int { ST_OK = 0, ST_NONFINITE = 1, ST_ASYMMETRIC = 2, ST_ANGLE = 3, ST_SINGULAR = 4 };
+enum : int { ST_OK = 0, ST_NONFINITE = 1, ST_ASYMMETRIC = 2, ST_ANGLE = 3, ST_SINGULAR = 4, ST_WEIGHT = 5 };  // (5: the marginals' weights)
 
 struct GraphState {
   double lambda, cost, cost0, cand_cost, grad_max;
@@ -216,9 +221,10 @@ __host__ __device__ inline void put_block(double* H, int br, int bc, const M3& a
 // Everything one edge contributes: l, its cost term, and (times l) Haa = A^T L A, Hab = A^T L B, Hbb = B^T L B, ga = A^T L r,
 // gb = B^T L r (and r itself into r_out, also beyond the limit), where A = d r / d(source perturbation) = [[Jr^-1, 0], [0, R_E]] and B = d r / d(target perturbation) =
 // [[-Jr^-1 Rst^T, 0], [R_T^T [u]x, -R_T^T]] (right perturbations X <- X [Exp(dw) | dt]).  Returns false beyond the angle limit.
+// given_l: a weight that takes the line process's place (the marginal covariances' per-edge weights).
 __host__ __device__ inline bool edge_terms(const double* Xs, const double* Xt, const double* T, const double* L, double mu,
                                            bool uncertain, double* l_out, double* term, double* Haa, double* Hab, double* Hbb,
-                                           double* ga, double* gb, double* r_out = nullptr) {
+                                           double* ga, double* gb, double* r_out = nullptr, const double* given_l = nullptr) {
   Residual r;
   const bool ok = edge_residual(Xs, Xt, T, r);
   if (r_out)
@@ -229,7 +235,7 @@ __host__ __device__ inline bool edge_terms(const double* Xs, const double* Xt, c
   if (!ok) return false;
   double y[6];
   const double q = quad_form(L, r, y);
-  const double l = line_weight(q, mu, uncertain);
+  const double l = given_l != nullptr ? *given_l : line_weight(q, mu, uncertain);
   *l_out = l;
   *term = cost_term(q, l, mu, uncertain);
   M3 L11, L12, L21, L22;
@@ -1298,22 +1304,11 @@ __global__ __launch_bounds__(kBlock) void pg_direct_schur_kernel(Direct dp, Dire
   if (v <= u) direct_schur_block(dp, sy, 1.0 + gs[g].lambda, g, s, u, v);
 }
 
-// One workgroup per graph: C = L_S L_S^T in place (column after column: every thread factors the pivot for itself, a block row of
-// the panel per thread, the trailing blocks dealt out by number), x_S by substitution with the right-hand side in LDS, then the
-// graph's runs backwards, a run per thread.  A pivot that is not positive, here or in a run, ends the graph (ST_SINGULAR).
-__global__ __launch_bounds__(kBlock) void pg_direct_solve_kernel(Direct dp, DirectSystem sy, GraphState* __restrict__ gs,
-                                                                 const int* __restrict__ bad) {
-  __shared__ double rs[6 * kMaxSeparator];
-  __shared__ int fail;
-  const int g = blockIdx.x, tid = threadIdx.x;
-  if (skip(gs, g, bad)) return;  // (uniform over the workgroup)
-  const int s0 = dp.sep_off[g], s = dp.sep_off[g + 1] - s0;
-  double* C = dp.C + 36ll * dp.c_off[g];
-  if (tid == 0) fail = dp.fail[g];
-  for (int u = tid; u < s; u += kBlock)
-#pragma unroll
-    for (int k = 0; k < 6; ++k) rs[6 * u + k] = sy.xv[6ll * dp.sep_node[s0 + u] + k];
-  __syncthreads();
+// C = L_S L_S^T in place ([s, s] blocks, the lower triangle) by a whole workgroup, column after column: every thread factors the pivot
+// for itself, a block row of the panel per thread, the trailing blocks dealt out by number.  A pivot that is not positive sets
+// *fail (in LDS), which every thread may read after the call.
+__device__ __forceinline__ void dense_factor(double* C, int s, int* fail) {
+  const int tid = threadIdx.x;
   for (int k = 0; k < s; ++k) {
     double l[36];
     double* pivot = C + 36ll * (static_cast<long long>(k) * s + k);
@@ -1322,7 +1317,7 @@ __global__ __launch_bounds__(kBlock) void pg_direct_solve_kernel(Direct dp, Dire
     const bool ok = cholesky6(l);
     __syncthreads();  // every thread has read the pivot
     if (tid == 0) {
-      if (!ok) fail = 1;
+      if (!ok) *fail = 1;
 #pragma unroll
       for (int q = 0; q < 36; ++q) pivot[q] = l[q];
     }
@@ -1350,6 +1345,25 @@ __global__ __launch_bounds__(kBlock) void pg_direct_solve_kernel(Direct dp, Dire
     }
     __syncthreads();
   }
+}
+
+// One workgroup per graph: C = L_S L_S^T in place (column after column: every thread factors the pivot for itself, a block row of
+// the panel per thread, the trailing blocks dealt out by number), x_S by substitution with the right-hand side in LDS, then the
+// graph's runs backwards, a run per thread.  A pivot that is not positive, here or in a run, ends the graph (ST_SINGULAR).
+__global__ __launch_bounds__(kBlock) void pg_direct_solve_kernel(Direct dp, DirectSystem sy, GraphState* __restrict__ gs,
+                                                                 const int* __restrict__ bad) {
+  __shared__ double rs[6 * kMaxSeparator];
+  __shared__ int fail;
+  const int g = blockIdx.x, tid = threadIdx.x;
+  if (skip(gs, g, bad)) return;  // (uniform over the workgroup)
+  const int s0 = dp.sep_off[g], s = dp.sep_off[g + 1] - s0;
+  double* C = dp.C + 36ll * dp.c_off[g];
+  if (tid == 0) fail = dp.fail[g];
+  for (int u = tid; u < s; u += kBlock)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) rs[6 * u + k] = sy.xv[6ll * dp.sep_node[s0 + u] + k];
+  __syncthreads();
+  dense_factor(C, s, &fail);
   if (fail) {  // (uniform: written before barriers that every thread passed)
     end_graph(gs, g, ST_SINGULAR);
     return;
@@ -1371,6 +1385,325 @@ __global__ __launch_bounds__(kBlock) void pg_direct_solve_kernel(Direct dp, Dire
     for (int k = 0; k < 6; ++k) sy.xv[6ll * dp.sep_node[s0 + u] + k] = rs[6 * u + k];
   __syncthreads();
   for (int run = dp.run_off[g] + tid; run < dp.run_off[g + 1]; run += kBlock) direct_run_back(dp, sy, run);
+}
+
+// ---- marginal covariances --------------------------------------------------------------------------------
+// Sigma_i = (H^-1)_ii of every free node from the direct solve's factors at lambda = 0, by a selected inversion: no dense inverse and
+// no solves.  The separator part is Sigma_SS = C^-1 = Z^T Z with Z = L_S^-1.  Along a run, backwards from its last position, with
+// Omega_jj = L_jj^T Sigma_jj L_jj and Psi_j = L_jj^T Sigma_{j,S} (the columns of the run's couplings):
+//   Psi_j         = -W_{j+1}^T Psi_{j+1} - Y_j Sigma_SS
+//   Omega_{j,j+1} = -W_{j+1}^T Omega_{j+1,j+1} - Y_j Psi_{j+1}^T
+//   Omega_jj      = I - W_{j+1}^T Omega_{j,j+1}^T - Y_j Psi_j^T
+//   Sigma_jj      = G_j^T Omega_jj G_j
+// (no W terms at the last position; Y_j is zero for a coupling that begins behind j).  As above, one work item per function, for
+// the device and for the host (rdm_pose_graph_marginals_host).
+struct Marginals {
+  double* Z;  // L_S^-1, a graph's [s, s] blocks at c_off like C; C itself ends as Sigma_SS, both triangles
+  double* P;  // Psi: a coupling's 6 x 6 part at 36 * coupling, one column after the other (6 doubles each)
+  double* S;  // [N, 36] every node's block before the output's symmetrisation
+};
+
+// Scalar column `col` of block column j of Z = L_S^-1 (block rows j .. s - 1) by forward substitution, a row's terms in ascending
+// k.  The thread reads back only what it wrote.
+__host__ __device__ inline void marg_inverse_column(const double* C, double* Z, int s, int j, int col) {
+  for (int i = j; i < s; ++i) {
+    double r[6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) r[q] = (i == j && q == col) ? 1.0 : 0.0;
+    for (int k = j; k < i; ++k) {
+      const double* Zk = Z + 36ll * (static_cast<long long>(k) * s + j);
+      double z[6];
+#pragma unroll
+      for (int q = 0; q < 6; ++q) z[q] = Zk[6 * q + col];
+      dense_sub_mul(C + 36ll * (static_cast<long long>(i) * s + k), z, r, false);
+    }
+    dense_lower_solve(C + 36ll * (static_cast<long long>(i) * s + i), r);
+    double* Zi = Z + 36ll * (static_cast<long long>(i) * s + j);
+#pragma unroll
+    for (int q = 0; q < 6; ++q) Zi[6 * q + col] = r[q];
+  }
+}
+
+// Block (u, v), v <= u, of Sigma_SS = Z^T Z: the sum of Z_ku^T Z_kv over k = u .. s - 1 in ascending k, into block (u, v) of `out`
+// and transposed into block (v, u).
+__host__ __device__ inline void marg_sigma_block(const double* Z, double* out, int s, int u, int v) {
+  double acc[36];
+#pragma unroll
+  for (int k = 0; k < 36; ++k) acc[k] = 0.0;
+  for (int k = u; k < s; ++k) {
+    const double* Zu = Z + 36ll * (static_cast<long long>(k) * s + u);
+    const double* Zv = Z + 36ll * (static_cast<long long>(k) * s + v);
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        double t = 0.0;
+#pragma unroll
+        for (int m = 0; m < 6; ++m) t += Zu[6 * m + r] * Zv[6 * m + c];
+        acc[6 * r + c] += t;
+      }
+  }
+  double* low = out + 36ll * (static_cast<long long>(u) * s + v);
+#pragma unroll
+  for (int k = 0; k < 36; ++k) low[k] = acc[k];
+  if (u != v) {
+    double* up = out + 36ll * (static_cast<long long>(v) * s + u);
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) up[6 * c + r] = acc[6 * r + c];
+  }
+}
+
+// One scalar column (number col = 6 * (coupling inside the run) + column of the separator node) of a run's Psi at position pos:
+// psi <- -W_{pos+1}^T psi - Y_pos Sigma_SS[:, column] (the run's couplings that have begun, in ascending separator order), in place
+// in P; and the column's terms of the two 6 x 6 sums, a1 += y psi_old^T and a2 += y psi_new^T with y the column of Y_pos.  Sg: the
+// graph's Sigma_SS ([s, s] blocks), s0 its first separator number.  At the run's last position nothing is read from P.
+__host__ __device__ inline void marg_sweep_column(const Direct& dp, const DirectSystem& sy, const Marginals& mg, const double* Sg, int s,
+                                                  int s0, int run, int pos, int col, double* a1, double* a2) {
+  const int c0 = dp.cpl_off[run], c1 = dp.cpl_off[run + 1], len = dp.run_len[run];
+  const int cu = c0 + col / 6, q = col - 6 * (col / 6), su = dp.cpl_sep[cu] - s0;
+  double* p = mg.P + 36ll * cu + 6 * q;
+  double old[6], now[6];
+  if (pos + 1 < len) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) old[k] = p[k];
+    block_mul(sy.Wc + 36ll * (dp.run_begin[run] + pos + 1), old, true, now);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) now[k] = -now[k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) old[k] = now[k] = 0.0;
+  }
+  for (int c = c0; c < c1; ++c) {
+    const int pc = dp.cpl_pos[c];
+    if (pos < pc) continue;
+    const double* Sb = Sg + 36ll * (static_cast<long long>(dp.cpl_sep[c] - s0) * s + su);
+    double sv[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) sv[k] = Sb[6 * k + q];
+    dense_sub_mul(dp.Y + 36ll * (dp.cpl_y[c] + (pos - pc)), sv, now, false);
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) p[k] = now[k];
+  const int pu = dp.cpl_pos[cu];
+  if (pos >= pu) {
+    const double* Yu = dp.Y + 36ll * (dp.cpl_y[cu] + (pos - pu));
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      const double y = Yu[6 * r + q];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        a1[6 * r + k] += y * old[k];
+        a2[6 * r + k] += y * now[k];
+      }
+    }
+  }
+}
+
+// The node's step after the columns': om holds Omega_{j+1,j+1} (unused at the run's last position) and leaves as Omega_jj; a1 = Y_j
+// Psi_{j+1}^T and a2 = Y_j Psi_j^T summed over the columns (both are used up); out = G_j^T Omega_jj G_j.
+__host__ __device__ inline void marg_sweep_node(const DirectSystem& sy, long long node, bool last, double* a1, double* a2, double* om,
+                                                double* out) {
+  if (!last) {
+    const double* W = sy.Wc + 36 * (node + 1);
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        double t = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) t += W[6 * k + r] * om[6 * k + c];
+        a1[6 * r + c] = -t - a1[6 * r + c];  // Omega_{j,j+1}
+      }
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        double t = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) t += W[6 * k + r] * a1[6 * c + k];
+        om[6 * r + c] = ((r == c ? 1.0 : 0.0) - t) - a2[6 * r + c];
+      }
+  } else {
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) om[6 * r + c] = (r == c ? 1.0 : 0.0) - a2[6 * r + c];
+  }
+  const double* G = sy.F + 21 * node;
+  double g[21];
+#pragma unroll
+  for (int k = 0; k < 21; ++k) g[k] = G[k];
+#pragma unroll
+  for (int r = 0; r < 6; ++r)  // a2 <- Omega G
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+      double t = 0.0;
+#pragma unroll
+      for (int k = c; k < 6; ++k) t += om[6 * r + k] * g[k * (k + 1) / 2 + c];
+      a2[6 * r + c] = t;
+    }
+#pragma unroll
+  for (int r = 0; r < 6; ++r)  // out <- G^T (Omega G)
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+      double t = 0.0;
+#pragma unroll
+      for (int k = r; k < 6; ++k) t += g[k * (k + 1) / 2 + r] * a2[6 * k + c];
+      out[6 * r + c] = t;
+    }
+}
+
+// A node's block of the output: zeros for node 0, NaN for a graph whose factor failed, else the staged block with every entry above
+// the diagonal a copy of the one below it.
+__host__ __device__ inline void marg_write_block(const double* staged, bool first, bool failed, double* out) {
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int c = 0; c < 6; ++c) out[6 * r + c] = first ? 0.0 : failed ? NAN : staged[6 * (r > c ? r : c) + (r > c ? c : r)];
+}
+
+// One thread per graph: the state the direct solve's kernels read -- lambda = 0 (their diagonal scale 1 + lambda is exactly 1), not
+// done unless the graph has no free node.
+__global__ __launch_bounds__(kBlock) void pg_marg_init_kernel(GraphState* __restrict__ gs, int g, const int* __restrict__ node_off) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= g) return;
+  GraphState s;
+  s.lambda = s.cost = s.cost0 = s.cand_cost = s.grad_max = 0.0;
+  s.iterations = s.pcg_total = s.accepted = 0;
+  s.stop = STOP_NONE;
+  s.status = ST_OK;
+  s.done = node_off[i + 1] - node_off[i] <= 1 ? 1 : 0;
+  gs[i] = s;
+}
+
+// One thread per edge: the edge's blocks at the given poses through edge_terms, the given weight (null: 1) in the line process's
+// place.  A weight that is negative or not finite and a residual beyond the angle limit refuse the call through the graph's status;
+// such an edge's slots are zeros.
+__global__ __launch_bounds__(kBlock) void pg_marg_linearize_kernel(Graphs gr, int e_total, const double* __restrict__ X,
+                                                                   const double* __restrict__ T, const double* __restrict__ L,
+                                                                   const double* __restrict__ weights, GraphState* __restrict__ gs,
+                                                                   double* __restrict__ Haa, double* __restrict__ Hab,
+                                                                   double* __restrict__ Hbb, double* __restrict__ ga,
+                                                                   double* __restrict__ gb, const int* __restrict__ bad) {
+  const long long e = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
+  if (e >= e_total || *bad != 0) return;
+  const double l = weights != nullptr ? weights[e] : 1.0;
+  double l_out, term;
+  int status = ST_OK;
+  if (!(l >= 0.0) || !isfinite(l)) {
+    status = ST_WEIGHT;
+  } else if (!edge_terms(X + 16ll * gr.es[e], X + 16ll * gr.et[e], T + 16 * e, L + 36 * e, 0.0, false, &l_out, &term, Haa + 36 * e,
+                         Hab + 36 * e, Hbb + 36 * e, ga + 6 * e, gb + 6 * e, nullptr, &l)) {
+    status = ST_ANGLE;
+  }
+  if (status == ST_OK) return;
+  gs[gr.edge_graph[e]].status = status;  // (any writer's value names a cause that is present)
+  for (int k = 0; k < 36; ++k) Haa[36 * e + k] = Hab[36 * e + k] = Hbb[36 * e + k] = 0.0;
+  for (int k = 0; k < 6; ++k) ga[6 * e + k] = gb[6 * e + k] = 0.0;
+}
+
+// One workgroup per graph: C = L_S L_S^T (dense_factor), Z = L_S^-1 a scalar column per thread, Sigma_SS = Z^T Z a block per
+// thread into C, and the separator nodes' own blocks into S.
+__global__ __launch_bounds__(kBlock) void pg_marg_separator_kernel(Direct dp, Marginals mg, const GraphState* __restrict__ gs,
+                                                                   const int* __restrict__ bad) {
+  __shared__ int fail;
+  const int g = blockIdx.x, tid = threadIdx.x;
+  if (skip(gs, g, bad)) return;  // (uniform over the workgroup)
+  const int s0 = dp.sep_off[g], s = dp.sep_off[g + 1] - s0;
+  double* C = dp.C + 36ll * dp.c_off[g];
+  double* Z = mg.Z + 36ll * dp.c_off[g];
+  if (tid == 0) fail = dp.fail[g];
+  __syncthreads();
+  dense_factor(C, s, &fail);
+  if (fail) {  // (uniform: written before barriers that every thread passed)
+    if (tid == 0) dp.fail[g] = 1;
+    return;
+  }
+  for (int t = tid; t < 6 * s; t += kBlock) marg_inverse_column(C, Z, s, t / 6, t % 6);
+  __syncthreads();  // Z is whole, and L_S is read no more
+  for (int idx = tid; idx < s * s; idx += kBlock) {
+    const int u = idx / s, v = idx - u * s;
+    if (v <= u) marg_sigma_block(Z, C, s, u, v);
+  }
+  __syncthreads();
+  for (int u = tid; u < s; u += kBlock) {
+    const double* d = C + 36ll * (static_cast<long long>(u) * s + u);
+    double* o = mg.S + 36ll * dp.sep_node[s0 + u];
+#pragma unroll
+    for (int k = 0; k < 36; ++k) o[k] = d[k];
+  }
+}
+
+// One wavefront per run, backwards along it.  Lane l owns the scalar columns l, l + 64, ... of the run's Psi (marg_sweep_column: a
+// lane reads back only what it wrote); the two 6 x 6 sums over the columns are per-lane partial sums in ascending column, then
+// wave_sum's butterfly, which leaves the same bits in every lane; every lane then takes the node's step (marg_sweep_node) on those
+// wave-uniform values and lane 0 stores the block.  kTimed (the phase-timing build's entry): lane 0 adds the clock ticks spent in
+// the columns, the butterflies and the node steps to ticks[3 run ..].
+template <bool kTimed>
+__global__ __launch_bounds__(kWave) void pg_marg_sweep_kernel(Direct dp, DirectSystem sy, Marginals mg, const GraphState* __restrict__ gs,
+                                                              const int* __restrict__ bad, long long* __restrict__ ticks) {
+  const int run = blockIdx.x, lane = threadIdx.x;
+  if (*bad != 0) return;
+  const int g = dp.run_graph[run];
+  if (gs[g].done || dp.fail[g] != 0) return;  // (uniform over the wavefront)
+  const int s0 = dp.sep_off[g], s = dp.sep_off[g + 1] - s0, len = dp.run_len[run];
+  const int cols = 6 * (dp.cpl_off[run + 1] - dp.cpl_off[run]);
+  const long long first = dp.run_begin[run];
+  const double* Sg = dp.C + 36ll * dp.c_off[g];
+  double om[36];
+#pragma unroll
+  for (int k = 0; k < 36; ++k) om[k] = 0.0;
+  long long t_cols = 0, t_sum = 0, t_node = 0, t0 = 0;
+  for (int pos = len - 1; pos >= 0; --pos) {
+    double a1[36], a2[36], out[36];
+#pragma unroll
+    for (int k = 0; k < 36; ++k) a1[k] = a2[k] = 0.0;
+    if constexpr (kTimed) t0 = wall_clock64();
+    for (int col = lane; col < cols; col += kWave) marg_sweep_column(dp, sy, mg, Sg, s, s0, run, pos, col, a1, a2);
+    if constexpr (kTimed) {
+      const long long t = wall_clock64();
+      t_cols += t - t0;
+      t0 = t;
+    }
+    if (cols > 0) {
+#pragma unroll
+      for (int k = 0; k < 36; ++k) {
+        a1[k] = wave_sum(a1[k]);
+        a2[k] = wave_sum(a2[k]);
+      }
+    }
+    if constexpr (kTimed) {
+      const long long t = wall_clock64();
+      t_sum += t - t0;
+      t0 = t;
+    }
+    marg_sweep_node(sy, first + pos, pos + 1 == len, a1, a2, om, out);
+    if (lane == 0) {
+      double* o = mg.S + 36 * (first + pos);
+#pragma unroll
+      for (int k = 0; k < 36; ++k) o[k] = out[k];
+    }
+    if constexpr (kTimed) t_node += wall_clock64() - t0;
+  }
+  if constexpr (kTimed) {
+    if (lane == 0 && ticks != nullptr) {
+      ticks[3 * run] = t_cols;
+      ticks[3 * run + 1] = t_sum;
+      ticks[3 * run + 2] = t_node;
+    }
+  }
+}
+
+// One thread per node: the output (marg_write_block), only when the call is not refused.
+__global__ __launch_bounds__(kBlock) void pg_marg_finish_kernel(Graphs gr, int n_total, const int* __restrict__ fail,
+                                                                const int* __restrict__ failed, const double* __restrict__ S,
+                                                                double* __restrict__ out) {
+  const long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= n_total || *failed != 0) return;
+  const int g = gr.node_graph[i];
+  marg_write_block(S + 36 * i, i == gr.node_off[g], fail[g] != 0, out + 36 * i);
 }
 
 // One thread per node: candidate pose Xc = X [Exp(dw) | dt]; node 0 of a graph keeps its pose.
@@ -1612,7 +1945,7 @@ void for_each_direct_table(const DirectPlan& pl, Direct& d, Visit visit) {  // v
 // The plan of a call from its tables (global node numbers; inc in ascending edge order).  false, with the error set: a graph's
 // separator is above the cap, or Y is too large to index.
 bool build_direct_plan(int64_t G, const int* node_off, const int* edge_off, const int* es, const int* et, const int* inc_off,
-                       const int* inc, DirectPlan& pl, const char* who) {
+                       const int* inc, DirectPlan& pl, const char* who, const char* hint = " (use the conjugate gradients)") {
   pl = DirectPlan();
   pl.sep_off.push_back(0);
   pl.run_off.push_back(0);
@@ -1632,8 +1965,8 @@ bool build_direct_plan(int64_t G, const int* node_off, const int* edge_off, cons
     const int n0 = node_off[g], n = node_off[g + 1] - n0, e0 = edge_off[g], ne = edge_off[g + 1] - e0;
     choose_separator(n, ne, [&](int64_t e, int64_t& s, int64_t& t) { s = es[e0 + e] - n0; t = et[e0 + e] - n0; }, S);
     if (static_cast<int>(S.size()) > kMaxSeparator) {
-      set_error("%s: graph %lld needs %zu separator nodes for the direct solve; the limit is %d (use the conjugate gradients)", who,
-                static_cast<long long>(g), S.size(), kMaxSeparator);
+      set_error("%s: graph %lld needs %zu separator nodes for the direct solve; the limit is %d%s", who, static_cast<long long>(g),
+                S.size(), kMaxSeparator, hint);
       return false;
     }
     const int s = static_cast<int>(S.size()), sep0 = static_cast<int>(pl.sep_node.size()), run0 = static_cast<int>(pl.run_begin.size());
@@ -1832,11 +2165,12 @@ int fill_host_tables(int64_t G, const int64_t* graph_node_offsets_host, const in
 
 // The host-built tables of a call in one buffer laid out as the workspace's first part; with `plan`, the direct solve's behind them.
 int build_host_tables(int64_t G, const int64_t* graph_node_offsets_host, const int64_t* graph_edge_offsets_host,
-                      const int64_t* edges_host, const uint8_t* uncertain_host, std::vector<char>& host, DirectPlan* plan) {
+                      const int64_t* edges_host, const uint8_t* uncertain_host, std::vector<char>& host, DirectPlan* plan,
+                      const char* who = "rdm_pose_graph_optimize", const char* hint = " (use the conjugate gradients)") {
   Work t;
   const int rc = fill_host_tables(G, graph_node_offsets_host, graph_edge_offsets_host, edges_host, uncertain_host, host, t);
   if (rc != RDM_OK || plan == nullptr) return rc;
-  if (!build_direct_plan(G, t.node_off, t.edge_off, t.es, t.et, t.inc_off, t.inc, *plan, "rdm_pose_graph_optimize")) return RDM_ERR_ARG;
+  if (!build_direct_plan(G, t.node_off, t.edge_off, t.es, t.et, t.inc_off, t.inc, *plan, who, hint)) return RDM_ERR_ARG;
   const int64_t N = graph_node_offsets_host[G], E = graph_edge_offsets_host[G];
   Direct d;
   carve_host(host, [&](Arena& ar) {  // (the filled tables lie first and stay)
@@ -1846,6 +2180,146 @@ int build_host_tables(int64_t G, const int64_t* graph_node_offsets_host, const i
   fill_direct_tables(*plan, d);
   return RDM_OK;
 }
+
+// What a graph's status says, for the calls' messages.
+const char* status_text(int status) {
+  static const char* const what[] = {"", "a pose, transform or information entry is not finite", "an information matrix is not symmetric",
+                                     "a residual rotation of the given poses is beyond the supported angle (cos < -0.99)",
+                                     "a node's block is not positive definite (a node that no edge reaches, or an indefinite information matrix)",
+                                     "a weight is negative or not finite"};
+  return what[status >= 1 && status <= 5 ? status : 0];
+}
+
+// The workspace of rdm_pose_graph_marginals: the tables and the direct solve's, the per-edge and per-node arrays that its kernels
+// read and write (Work's other members stay null), then Z, Psi and the staged blocks.
+bool carve_marginals(Arena& ar, int64_t g, int64_t n, int64_t e, Work& w, const DirectPlan& plan, Direct& d, Marginals& m) {
+  const size_t G = static_cast<size_t>(g > 0 ? g : 1), N = static_cast<size_t>(n > 0 ? n : 1), E = static_cast<size_t>(e > 0 ? e : 1);
+  w = Work();
+  carve_tables(ar, g, n, e, w);
+  carve_direct_tables(ar, plan, w, d);
+  w.flags = ar.take<int>(4);
+  w.gs = ar.take<GraphState>(G);
+  w.Haa = ar.take<double>(36 * E);
+  w.Hab = ar.take<double>(36 * E);
+  w.Hbb = ar.take<double>(36 * E);
+  w.ga = ar.take<double>(6 * E);
+  w.gb = ar.take<double>(6 * E);
+  w.D = ar.take<double>(36 * N);
+  w.F = ar.take<double>(21 * N);
+  w.bv = ar.take<double>(6 * N);
+  w.xv = ar.take<double>(6 * N);
+  w.rv = ar.take<double>(6 * N);
+  w.zv = ar.take<double>(6 * N);
+  w.report = ar.take<double>(kReport * G);
+  w.Wc = ar.take<double>(36 * N);
+  carve_direct_arrays(ar, plan, G, d);
+  m.Z = ar.take<double>(36 * static_cast<size_t>(plan.c_off.back() > 0 ? plan.c_off.back() : 1));
+  m.P = ar.take<double>(36 * (plan.cpl_sep.empty() ? 1 : plan.cpl_sep.size()));
+  m.S = ar.take<double>(36 * N);
+  return ar.ok;
+}
+
+// The direct solve of one system on the host up to the factors: the plan, the runs' factors (and y = L^-1 rhs), the border, the Schur
+// complement and its dense factor, by the kernels' functions in their order.  RDM_ERR_ARG, with `who` in the message, for a failed
+// pivot and for a separator above the limit.
+struct HostDirect {
+  std::vector<char> host;
+  DirectPlan plan;
+  Work t;
+  std::vector<double> F, Wc, zv, xv, C, Y;
+  int fail = 0, runs = 0, couplings = 0, s = 0;
+  Direct dp = {};
+  DirectSystem sy = {};
+  double* block(int i, int j) { return C.data() + 36 * (static_cast<size_t>(i) * s + j); }
+};
+int host_direct_factor(HostDirect& h, int64_t n_nodes, int64_t n_edges, const int64_t* edges_host, const double* diag, const double* off,
+                       const double* rhs, const char* who, const char* hint) {
+  const int64_t noff[2] = {0, n_nodes}, eoff[2] = {0, n_edges};
+  Work& t = h.t;
+  const int rc = fill_host_tables(1, noff, eoff, edges_host, nullptr, h.host, t);
+  if (rc != RDM_OK) return rc;
+  {  // edges that touch node 0 stay out of the incidence lists (they hold no block of the system)
+    int kept = 0;
+    std::vector<int> inc_off(static_cast<size_t>(n_nodes) + 1, 0);
+    for (int64_t i = 0; i < n_nodes; ++i) {
+      inc_off[i] = kept;
+      for (int q = t.inc_off[i]; q < t.inc_off[i + 1]; ++q) {
+        const int e = t.inc[q] >> 1;
+        if (t.es[e] != 0 && t.et[e] != 0) t.inc[kept++] = t.inc[q];
+      }
+    }
+    inc_off[n_nodes] = kept;
+    for (int64_t i = 0; i <= n_nodes; ++i) t.inc_off[i] = inc_off[i];
+  }
+  DirectPlan& plan = h.plan;
+  if (!build_direct_plan(1, t.node_off, t.edge_off, t.es, t.et, t.inc_off, t.inc, plan, who, hint)) return RDM_ERR_ARG;
+  const size_t N = static_cast<size_t>(n_nodes);
+  h.F.assign(21 * N, 0.0);
+  h.Wc.assign(36 * N, 0.0);
+  h.zv.assign(6 * N, 0.0);
+  h.xv.assign(6 * N, 0.0);
+  h.C.assign(36 * static_cast<size_t>(plan.c_off.back()) + 36, 0.0);
+  h.Y.assign(36 * static_cast<size_t>(plan.y_blocks) + 36, 0.0);
+  Direct& dp = h.dp;
+  for_each_direct_table(plan, dp, [](const auto& v, auto& table) { table = v.empty() ? nullptr : v.data(); });
+  dp.C = h.C.data();
+  dp.Y = h.Y.data();
+  dp.fail = &h.fail;
+  h.sy = {t.es, t.et, t.inc_off, t.inc, diag, off, rhs, h.F.data(), h.Wc.data(), h.zv.data(), h.xv.data()};
+  const DirectSystem& sy = h.sy;
+  for (int64_t i = 2; i < n_nodes; ++i) chain_off_block(t.es, t.et, t.inc_off, t.inc, off, i, &h.Wc[36 * i]);
+  h.runs = static_cast<int>(plan.run_begin.size());
+  h.couplings = static_cast<int>(plan.cpl_sep.size());
+  h.s = plan.sep_off[1];
+  const int s = h.s;
+  for (int run = 0; run < h.runs; ++run)
+    if (!direct_run_factor(dp, sy, 1.0, run)) {
+      set_error("%s: a pivot of the run that begins at node %d is not positive definite", who, plan.run_begin[run]);
+      return RDM_ERR_ARG;
+    }
+  for (int c = 0; c < h.couplings; ++c)
+    for (int col = 0; col < 6; ++col) direct_border_column(dp, sy, c, col);
+  for (int u = 0; u < s; ++u)
+    for (int v = 0; v <= u; ++v) direct_schur_block(dp, sy, 1.0, 0, s, u, v);
+  for (int k = 0; k < s; ++k) {  // the dense factor, column after column
+    if (!cholesky6(h.block(k, k))) {
+      set_error("%s: the Schur complement's pivot of node %d is not positive definite", who, plan.sep_node[k]);
+      return RDM_ERR_ARG;
+    }
+    for (int i = k + 1; i < s; ++i) dense_panel_block(h.block(k, k), h.block(i, k));
+    for (int i = k + 1; i < s; ++i)
+      for (int j = k + 1; j <= i; ++j) dense_trailing_block(h.block(i, k), h.block(j, k), h.block(i, j));
+  }
+  return RDM_OK;
+}
+
+// pg_marg_sweep_kernel's run on the host: the 64 lanes' partial sums one lane after the other, then wave_sum's butterfly.
+void marg_sweep_run_host(const Direct& dp, const DirectSystem& sy, const Marginals& mg, int run) {
+  const int s = dp.sep_off[1], len = dp.run_len[run], cols = 6 * (dp.cpl_off[run + 1] - dp.cpl_off[run]);
+  const long long first = dp.run_begin[run];
+  double om[36] = {};
+  std::vector<double> a1(kWave * 36), a2(kWave * 36), b(kWave * 36);
+  auto butterfly = [&](std::vector<double>& a) {
+    for (int o = 32; o > 0; o >>= 1) {
+      for (int l = 0; l < kWave; ++l)
+        for (int k = 0; k < 36; ++k) b[36 * l + k] = a[36 * l + k] + a[36 * (l ^ o) + k];
+      a.swap(b);
+    }
+  };
+  for (int pos = len - 1; pos >= 0; --pos) {
+    std::fill(a1.begin(), a1.end(), 0.0);
+    std::fill(a2.begin(), a2.end(), 0.0);
+    for (int lane = 0; lane < kWave; ++lane)
+      for (int col = lane; col < cols; col += kWave) marg_sweep_column(dp, sy, mg, dp.C, s, 0, run, pos, col, &a1[36 * lane], &a2[36 * lane]);
+    if (cols > 0) {
+      butterfly(a1);
+      butterfly(a2);
+    }
+    marg_sweep_node(sy, first + pos, pos + 1 == len, a1.data(), a2.data(), om, mg.S + 36 * (first + pos));
+  }
+}
+
+thread_local long long* t_marg_ticks = nullptr;  // rdm_dbg_pose_graph_marginals_ticks
 
 }  // namespace
 }  // namespace rdm
@@ -1923,61 +2397,20 @@ extern "C" int rdm_pose_graph_direct_host(int64_t n_nodes, int64_t n_edges, cons
   RDM_REQUIRE(n_nodes >= 0 && n_nodes <= kMaxNodes && n_edges >= 0 && n_edges <= kMaxEdges, "rdm_pose_graph_direct_host: bad sizes");
   if (n_nodes == 0) return RDM_OK;
   RDM_REQUIRE(diag && rhs && out && ((edges_host && off) || n_edges == 0), "rdm_pose_graph_direct_host: null argument");
-  const int64_t noff[2] = {0, n_nodes}, eoff[2] = {0, n_edges};
-  std::vector<char> host;
-  DirectPlan plan;
-  Work t;
-  const int rc = fill_host_tables(1, noff, eoff, edges_host, nullptr, host, t);
+  HostDirect h;
+  const int rc = host_direct_factor(h, n_nodes, n_edges, edges_host, diag, off, rhs, "rdm_pose_graph_direct_host", " (use the conjugate gradients)");
   if (rc != RDM_OK) return rc;
-  {  // edges that touch node 0 stay out of the incidence lists (they hold no block of the system)
-    int kept = 0;
-    std::vector<int> inc_off(static_cast<size_t>(n_nodes) + 1, 0);
-    for (int64_t i = 0; i < n_nodes; ++i) {
-      inc_off[i] = kept;
-      for (int q = t.inc_off[i]; q < t.inc_off[i + 1]; ++q) {
-        const int e = t.inc[q] >> 1;
-        if (t.es[e] != 0 && t.et[e] != 0) t.inc[kept++] = t.inc[q];
-      }
-    }
-    inc_off[n_nodes] = kept;
-    for (int64_t i = 0; i <= n_nodes; ++i) t.inc_off[i] = inc_off[i];
-  }
-  if (!build_direct_plan(1, t.node_off, t.edge_off, t.es, t.et, t.inc_off, t.inc, plan, "rdm_pose_graph_direct_host")) return RDM_ERR_ARG;
   const size_t N = static_cast<size_t>(n_nodes);
-  std::vector<double> F(21 * N), Wc(36 * N, 0.0), zv(6 * N, 0.0), xv(6 * N, 0.0), C(36 * static_cast<size_t>(plan.c_off.back()) + 36),
-      Y(36 * static_cast<size_t>(plan.y_blocks) + 36);
-  int fail = 0;
-  Direct dp = {};
-  for_each_direct_table(plan, dp, [](const auto& v, auto& table) { table = v.empty() ? nullptr : v.data(); });
-  dp.C = C.data();
-  dp.Y = Y.data();
-  dp.fail = &fail;
-  const DirectSystem sy = {t.es, t.et, t.inc_off, t.inc, diag, off, rhs, F.data(), Wc.data(), zv.data(), xv.data()};
-  for (int64_t i = 2; i < n_nodes; ++i) chain_off_block(t.es, t.et, t.inc_off, t.inc, off, i, &Wc[36 * i]);
-  const int runs = static_cast<int>(plan.run_begin.size()), couplings = static_cast<int>(plan.cpl_sep.size()), s = plan.sep_off[1];
-  for (int run = 0; run < runs; ++run)
-    if (!direct_run_factor(dp, sy, 1.0, run)) {
-      set_error("rdm_pose_graph_direct_host: a pivot of the run that begins at node %d is not positive definite", plan.run_begin[run]);
-      return RDM_ERR_ARG;
-    }
-  for (int c = 0; c < couplings; ++c)
-    for (int col = 0; col < 6; ++col) direct_border_column(dp, sy, c, col);
-  for (int u = 0; u < s; ++u)
-    for (int v = 0; v <= u; ++v) direct_schur_block(dp, sy, 1.0, 0, s, u, v);
+  const Direct& dp = h.dp;
+  const DirectSystem& sy = h.sy;
+  const DirectPlan& plan = h.plan;
+  std::vector<double>& xv = h.xv;
+  const int runs = h.runs, s = h.s;
   for (int u = 0; u < s; ++u) direct_schur_rhs(dp, sy, 0, u);
   std::vector<double> rs(6 * static_cast<size_t>(s) + 6);
   for (int u = 0; u < s; ++u)
     for (int k = 0; k < 6; ++k) rs[6 * u + k] = xv[6 * plan.sep_node[u] + k];
-  auto block = [&](int i, int j) { return C.data() + 36 * (static_cast<size_t>(i) * s + j); };
-  for (int k = 0; k < s; ++k) {  // the dense factor, column after column
-    if (!cholesky6(block(k, k))) {
-      set_error("rdm_pose_graph_direct_host: the Schur complement's pivot of node %d is not positive definite", plan.sep_node[k]);
-      return RDM_ERR_ARG;
-    }
-    for (int i = k + 1; i < s; ++i) dense_panel_block(block(k, k), block(i, k));
-    for (int i = k + 1; i < s; ++i)
-      for (int j = k + 1; j <= i; ++j) dense_trailing_block(block(i, k), block(j, k), block(i, j));
-  }
+  auto block = [&](int i, int j) { return h.block(i, j); };
   for (int k = 0; k < s; ++k) {
     dense_lower_solve(block(k, k), &rs[6 * k]);
     for (int i = k + 1; i < s; ++i) dense_sub_mul(block(i, k), &rs[6 * k], &rs[6 * i], false);
@@ -1991,6 +2424,138 @@ extern "C" int rdm_pose_graph_direct_host(int64_t n_nodes, int64_t n_edges, cons
   for (int run = 0; run < runs; ++run) direct_run_back(dp, sy, run);
   for (int k = 0; k < 6; ++k) xv[k] = 0.0;
   memcpy(out, xv.data(), sizeof(double) * 6 * N);
+  return RDM_OK;
+}
+
+extern "C" int rdm_pose_graph_marginals_host(int64_t n_nodes, int64_t n_edges, const int64_t* edges_host, const double* diag,
+                                             const double* off, double* out) {
+  using namespace rdm;
+  RDM_REQUIRE(n_nodes >= 0 && n_nodes <= kMaxNodes && n_edges >= 0 && n_edges <= kMaxEdges, "rdm_pose_graph_marginals_host: bad sizes");
+  if (n_nodes == 0) return RDM_OK;
+  RDM_REQUIRE(diag && out && ((edges_host && off) || n_edges == 0), "rdm_pose_graph_marginals_host: null argument");
+  const size_t N = static_cast<size_t>(n_nodes);
+  const std::vector<double> rhs(6 * N, 0.0);  // (the runs' factor also sweeps a right-hand side)
+  HostDirect h;
+  const int rc = host_direct_factor(h, n_nodes, n_edges, edges_host, diag, off, rhs.data(), "rdm_pose_graph_marginals_host", "");
+  if (rc != RDM_OK) return rc;
+  const int s = h.s;
+  std::vector<double> Z(h.C.size(), 0.0), P(36 * static_cast<size_t>(h.couplings) + 36, 0.0), S(36 * N, 0.0);
+  const Marginals mg = {Z.data(), P.data(), S.data()};
+  for (int t = 0; t < 6 * s; ++t) marg_inverse_column(h.C.data(), mg.Z, s, t / 6, t % 6);
+  for (int u = 0; u < s; ++u)
+    for (int v = 0; v <= u; ++v) marg_sigma_block(mg.Z, h.C.data(), s, u, v);
+  for (int u = 0; u < s; ++u) memcpy(mg.S + 36 * static_cast<size_t>(h.plan.sep_node[u]), h.block(u, u), sizeof(double) * 36);
+  for (int run = 0; run < h.runs; ++run) marg_sweep_run_host(h.dp, h.sy, mg, run);
+  for (size_t i = 0; i < N; ++i) marg_write_block(mg.S + 36 * i, i == 0, false, out + 36 * i);
+  return RDM_OK;
+}
+
+extern "C" size_t rdm_pose_graph_marginals_workspace_bytes(int64_t n_graphs, const int64_t* graph_node_offsets_host,
+                                                           const int64_t* graph_edge_offsets_host, const int64_t* edges_host) {
+  using namespace rdm;
+  auto checked = [&]() -> int {
+    RDM_REQUIRE(n_graphs >= 0 && n_graphs < kMaxTotal && graph_node_offsets_host && graph_edge_offsets_host,
+                "rdm_pose_graph_marginals_workspace_bytes: bad number of graphs or null offsets");
+    const int rc = check_graphs(n_graphs, graph_node_offsets_host, graph_edge_offsets_host);
+    if (rc != RDM_OK) return rc;
+    RDM_REQUIRE(graph_edge_offsets_host[n_graphs] == 0 || edges_host, "rdm_pose_graph_marginals_workspace_bytes: null edges");
+    return RDM_OK;
+  };
+  if (checked() != RDM_OK) return 0;
+  std::vector<char> host;
+  DirectPlan plan;
+  if (build_host_tables(n_graphs, graph_node_offsets_host, graph_edge_offsets_host, edges_host, nullptr, host, &plan,
+                        "rdm_pose_graph_marginals", "") != RDM_OK)
+    return 0;
+  Arena ar(nullptr, 0);
+  Work w;
+  Direct dp;
+  Marginals mg;
+  carve_marginals(ar, n_graphs, graph_node_offsets_host[n_graphs], graph_edge_offsets_host[n_graphs], w, plan, dp, mg);
+  return ar.off;
+}
+
+extern "C" int rdm_dbg_pose_graph_marginals_ticks(long long* device_ticks) {
+  rdm::t_marg_ticks = device_ticks;
+  return rdm::RDM_OK;
+}
+
+extern "C" int rdm_pose_graph_marginals(int64_t n_graphs, const int64_t* graph_node_offsets_host, const int64_t* graph_edge_offsets_host,
+                                        const double* nodes, const int64_t* edges_host, const double* transforms,
+                                        const double* informations, const double* weights, double* covariances_out, double* report_host,
+                                        void* ws, size_t ws_bytes, void* stream) {
+  using namespace rdm;
+  const int64_t G = n_graphs;
+  RDM_REQUIRE(G >= 0 && G < kMaxTotal, "rdm_pose_graph_marginals: bad number of graphs");
+  RDM_REQUIRE(G == 0 || (graph_node_offsets_host && graph_edge_offsets_host && report_host), "rdm_pose_graph_marginals: null argument");
+  if (G == 0) return RDM_OK;
+  int rc = check_graphs(G, graph_node_offsets_host, graph_edge_offsets_host);
+  if (rc != RDM_OK) return rc;
+  const int64_t N = graph_node_offsets_host[G], E = graph_edge_offsets_host[G];
+  RDM_REQUIRE((nodes && covariances_out) || N == 0, "rdm_pose_graph_marginals: null nodes");
+  RDM_REQUIRE((edges_host && transforms && informations) || E == 0, "rdm_pose_graph_marginals: null edges");
+  std::vector<char> host;
+  DirectPlan plan;
+  rc = build_host_tables(G, graph_node_offsets_host, graph_edge_offsets_host, edges_host, nullptr, host, &plan, "rdm_pose_graph_marginals", "");
+  if (rc != RDM_OK) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Arena ar(ws, ws_bytes);
+  Work w;
+  Direct dp;
+  Marginals mg;
+  if (!carve_marginals(ar, G, N, E, w, plan, dp, mg)) {
+    set_error("rdm_pose_graph_marginals: workspace too small (%zu < %zu bytes)", ws_bytes, ar.off);
+    return RDM_ERR_WORKSPACE;
+  }
+  RDM_HIP_CHECK(hipMemcpyAsync(w.node_off, host.data(), host.size(), hipMemcpyHostToDevice, st));
+  RDM_HIP_CHECK(hipStreamSynchronize(st));  // (`host` is pageable and leaves scope)
+  const Graphs gr = {w.node_off, w.edge_off, w.edge_graph, w.node_graph, w.es, w.et, nullptr, w.inc_off, w.inc};
+  Params p = {};
+  p.gtol = -1.0;  // (pg_direct_blocks_kernel's gradient test never ends a graph: the blocks are wanted at a minimum too)
+  int *bad = w.flags, *failed = w.flags + 2;
+  const int n = static_cast<int>(N), e = static_cast<int>(E), g = static_cast<int>(G);
+  const DirectSystem sy = {w.es, w.et, w.inc_off, w.inc, w.D, w.Hab, w.rv, w.F, w.Wc, w.zv, w.xv};
+  const int runs = static_cast<int>(plan.run_begin.size()), couplings = static_cast<int>(plan.cpl_sep.size());
+  const long long items = plan.item_off.back();
+  fill_words<int>(w.flags, 4, 0, st);
+  fill_words<int>(dp.fail, G, 0, st);
+  hipLaunchKernelGGL(pg_marg_init_kernel, dim3(blocks_for(G)), dim3(kBlock), 0, st, w.gs, g, w.node_off);
+  hipLaunchKernelGGL(pg_check_kernel, dim3(blocks_for(std::max(N, E))), dim3(kBlock), 0, st, gr, nodes, n, transforms, informations, e,
+                     w.gs, bad);
+  hipLaunchKernelGGL(pg_marg_linearize_kernel, dim3(blocks_for(E)), dim3(kBlock), 0, st, gr, e, nodes, transforms, informations, weights,
+                     w.gs, w.Haa, w.Hab, w.Hbb, w.ga, w.gb, bad);
+  hipLaunchKernelGGL(pg_direct_blocks_kernel, dim3(static_cast<unsigned>(G)), dim3(kBlock), 0, st, gr, p, w.gs, w.Haa, w.Hab, w.Hbb, w.ga,
+                     w.gb, w.D, w.bv, w.xv, w.rv, w.Wc, dp.fail, bad);
+  if (runs > 0) hipLaunchKernelGGL(pg_direct_factor_kernel, dim3((runs + kWave - 1) / kWave), dim3(kWave), 0, st, dp, sy, runs, w.gs, bad);
+  if (couplings > 0)
+    hipLaunchKernelGGL(pg_direct_border_kernel, dim3(blocks_for(6ll * couplings)), dim3(kBlock), 0, st, dp, sy, couplings, w.gs, bad);
+  if (items > 0) hipLaunchKernelGGL(pg_direct_schur_kernel, dim3(blocks_for(items)), dim3(kBlock), 0, st, dp, sy, g, items, w.gs, bad);
+  hipLaunchKernelGGL(pg_marg_separator_kernel, dim3(static_cast<unsigned>(G)), dim3(kBlock), 0, st, dp, mg, w.gs, bad);
+  if (runs > 0) {
+    if (t_marg_ticks != nullptr)
+      hipLaunchKernelGGL(pg_marg_sweep_kernel<true>, dim3(runs), dim3(kWave), 0, st, dp, sy, mg, w.gs, bad, t_marg_ticks);
+    else
+      hipLaunchKernelGGL(pg_marg_sweep_kernel<false>, dim3(runs), dim3(kWave), 0, st, dp, sy, mg, w.gs, bad, static_cast<long long*>(nullptr));
+  }
+  hipLaunchKernelGGL(pg_report_kernel, dim3(1), dim3(64), 0, st, g, w.gs, bad, w.report, failed);
+  hipLaunchKernelGGL(pg_marg_finish_kernel, dim3(blocks_for(N)), dim3(kBlock), 0, st, gr, n, dp.fail, failed, mg.S, covariances_out);
+  rc = launch_status("rdm_pose_graph_marginals");
+  if (rc != RDM_OK) return rc;
+  std::vector<double> report(kReport * static_cast<size_t>(G));
+  std::vector<int> fail(static_cast<size_t>(G));
+  RDM_HIP_CHECK(hipMemcpyAsync(report.data(), w.report, sizeof(double) * kReport * G, hipMemcpyDeviceToHost, st));
+  RDM_HIP_CHECK(hipMemcpyAsync(fail.data(), dp.fail, sizeof(int) * G, hipMemcpyDeviceToHost, st));
+  RDM_HIP_CHECK(hipStreamSynchronize(st));
+  for (int64_t q = 0; q < G; ++q) {
+    const int status = static_cast<int>(report[q * kReport + 5]);
+    if (status == ST_OK) continue;
+    set_error("rdm_pose_graph_marginals: graph %lld: %s", static_cast<long long>(q), status_text(status));
+    return RDM_ERR_ARG;
+  }
+  for (int64_t q = 0; q < G; ++q) {
+    report_host[2 * q] = fail[q] != 0 ? ST_SINGULAR : ST_OK;
+    report_host[2 * q + 1] = plan.sep_off[q + 1] - plan.sep_off[q];
+  }
   return RDM_OK;
 }
 
@@ -2172,10 +2737,7 @@ extern "C" int rdm_pose_graph_optimize_ls(int64_t n_graphs, const int64_t* graph
   for (int64_t q = 0; q < G; ++q) {
     const int status = static_cast<int>(report_host[q * kReport + 5]);
     if (status == ST_OK) continue;
-    static const char* const what[] = {"", "a pose, transform or information entry is not finite", "an information matrix is not symmetric",
-                                       "a residual rotation of the given poses is beyond the supported angle (cos < -0.99)",
-                                       "a node's block is not positive definite (a node that no edge reaches, or an indefinite information matrix)"};
-    set_error("rdm_pose_graph_optimize: graph %lld: %s", static_cast<long long>(q), what[status >= 1 && status <= 4 ? status : 0]);
+    set_error("rdm_pose_graph_optimize: graph %lld: %s", static_cast<long long>(q), status_text(status));
     return RDM_ERR_ARG;
   }
   return RDM_OK;

@@ -1880,7 +1880,7 @@ class PoseGraphResult:
         self.damping, self.gradient_max = rep[:, 6].copy(), rep[:, 7].copy()
 
 
-def _pose_graph_connected(edges, node_offsets, edge_offsets):
+def _pose_graph_connected(edges, node_offsets, edge_offsets, who='pose_graph_optimize'):
     """Union-find over every graph's edges: ValueError naming the first node that no path connects to its graph's node 0.
     Edges whose ends are outside their graph are left to the library's own check.  Graphs without edges are returned as given
     and are not checked."""
@@ -1903,7 +1903,61 @@ def _pose_graph_connected(edges, node_offsets, edge_offsets):
                     parent[max(a, b)] = min(a, b)
         for i in range(n):
             if find(i) != 0:
-                raise ValueError(f'pose_graph_optimize: no path of edges connects node {i} of graph {g} to its node 0')
+                raise ValueError(f'{who}: no path of edges connects node {i} of graph {g} to its node 0')
+
+
+def _pose_graph_args(who, nodes, edges, transforms, informations, uncertain, graph_node_offsets, graph_edge_offsets, weights=None,
+                     before_connectivity=None):
+    """The arguments of a pose-graph call (pose_graph_optimize, pose_graph_marginals), checked and moved: nodes, transforms,
+    informations (and weights, when given) float64 on the device of the first of them that lies on one (else the current device),
+    edges / uncertain / offsets as host numpy arrays.  Every ValueError is raised before anything moves to a device: shapes, one row
+    per edge, the offsets, a weight that is negative or not finite, whatever before_connectivity() raises, a node without a path to
+    its graph's node 0.  -> (device, X, T, L, edges, uncertain, node offsets, edge offsets, G, weights)."""
+    import numpy as np
+
+    def f64(t, shape, name):
+        t = t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float64)))
+        if t.dim() != len(shape) + 1 or tuple(t.shape[1:]) != shape:
+            dims = ''.join(f', {d}' for d in shape)
+            raise ValueError(f'{who}: {name} must be [*{dims}], got {tuple(t.shape)}')
+        return t.detach()
+
+    def host(t, dtype):
+        if t is None:
+            return None
+        if isinstance(t, torch.Tensor):
+            t = t.detach().cpu().numpy()
+        return np.ascontiguousarray(np.asarray(t).astype(dtype, copy=False))
+
+    X, T, Lm = f64(nodes, (4, 4), 'nodes'), f64(transforms, (4, 4), 'transforms'), f64(informations, (6, 6), 'informations')
+    W = None if weights is None else f64(weights, (), 'weights')
+    ed = host(edges, np.int64).reshape(-1, 2)
+    unc = host(uncertain, np.uint8)
+    n, e = X.shape[0], ed.shape[0]
+    if T.shape[0] != e or Lm.shape[0] != e or (unc is not None and unc.shape != (e,)):
+        raise ValueError(f'{who}: edges, transforms, informations and uncertain must have one row per edge')
+    if W is not None and W.shape[0] != e:
+        raise ValueError(f'{who}: weights must have one entry per edge, got {tuple(W.shape)}')
+    if (graph_node_offsets is None) != (graph_edge_offsets is None):
+        raise ValueError(f'{who}: graph_node_offsets and graph_edge_offsets go together')
+    noff = np.array([0, n], np.int64) if graph_node_offsets is None else host(graph_node_offsets, np.int64)
+    eoff = np.array([0, e], np.int64) if graph_edge_offsets is None else host(graph_edge_offsets, np.int64)
+    if noff.ndim != 1 or noff.shape != eoff.shape or noff.shape[0] < 1 or noff[0] != 0 or eoff[0] != 0 or noff[-1] != n or eoff[-1] != e \
+            or np.any(np.diff(noff) < 0) or np.any(np.diff(eoff) < 0):
+        raise ValueError(f'{who}: offsets must be [G + 1], ascending, from 0 to the number of nodes / edges')
+    if W is not None and e > 0 and not bool((torch.isfinite(W) & (W >= 0)).all()):
+        raise ValueError(f'{who}: weights must be finite and >= 0')
+    if before_connectivity is not None:
+        before_connectivity()
+    g = noff.shape[0] - 1
+    if g > 0 and np.diff(noff).max() <= POSE_GRAPH_MAX_NODES and np.diff(eoff).max() <= POSE_GRAPH_MAX_EDGES:
+        _pose_graph_connected(ed, noff, eoff, who)
+    tensors = [t for t in (X, T, Lm) if t.is_cuda]
+    dev = tensors[0].device if tensors else torch.device('cuda', torch.cuda.current_device())
+    X, T, Lm = (t.to(device=dev, dtype=torch.float64).contiguous() for t in (X, T, Lm))
+    if W is not None:
+        W = W.to(device=dev, dtype=torch.float64).contiguous()
+    return dev, X, T, Lm, ed, unc, noff, eoff, g, W
 
 
 def pose_graph_optimize(nodes, edges, transforms, informations, uncertain=None, *, line_process_weight=None,
@@ -1940,41 +1994,14 @@ def pose_graph_optimize(nodes, edges, transforms, informations, uncertain=None, 
         raise ValueError(f'pose_graph_optimize: linear_solver must be one of {sorted(POSE_GRAPH_LINEAR_SOLVERS)}, got {linear_solver!r}')
     solver = POSE_GRAPH_LINEAR_SOLVERS[linear_solver]
     L = _lib.lib()
-    tensors = [t for t in (nodes, transforms, informations) if isinstance(t, torch.Tensor) and t.is_cuda]
-    dev = tensors[0].device if tensors else torch.device('cuda', torch.cuda.current_device())
 
-    def dev64(t, shape, name):
-        t = t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float64)))
-        t = t.detach().to(device=dev, dtype=torch.float64).contiguous()
-        if t.dim() != 3 or tuple(t.shape[1:]) != shape:
-            raise ValueError(f'pose_graph_optimize: {name} must be [*, {shape[0]}, {shape[1]}], got {tuple(t.shape)}')
-        return t
+    def check_weight():
+        if line_process_weight is not None and not line_process_weight > 0:
+            raise ValueError(f'pose_graph_optimize: line_process_weight must be > 0 or None, got {line_process_weight}')
 
-    def host(t, dtype):
-        if t is None:
-            return None
-        if isinstance(t, torch.Tensor):
-            t = t.detach().cpu().numpy()
-        return np.ascontiguousarray(np.asarray(t).astype(dtype, copy=False))
-
-    X, T, Lm = dev64(nodes, (4, 4), 'nodes'), dev64(transforms, (4, 4), 'transforms'), dev64(informations, (6, 6), 'informations')
-    ed = host(edges, np.int64).reshape(-1, 2)
-    unc = host(uncertain, np.uint8)
+    dev, X, T, Lm, ed, unc, noff, eoff, g, _ = _pose_graph_args('pose_graph_optimize', nodes, edges, transforms, informations, uncertain,
+                                                                graph_node_offsets, graph_edge_offsets, before_connectivity=check_weight)
     n, e = X.shape[0], ed.shape[0]
-    if T.shape[0] != e or Lm.shape[0] != e or (unc is not None and unc.shape != (e,)):
-        raise ValueError('pose_graph_optimize: edges, transforms, informations and uncertain must have one row per edge')
-    if (graph_node_offsets is None) != (graph_edge_offsets is None):
-        raise ValueError('pose_graph_optimize: graph_node_offsets and graph_edge_offsets go together')
-    noff = np.array([0, n], np.int64) if graph_node_offsets is None else host(graph_node_offsets, np.int64)
-    eoff = np.array([0, e], np.int64) if graph_edge_offsets is None else host(graph_edge_offsets, np.int64)
-    if noff.ndim != 1 or noff.shape != eoff.shape or noff.shape[0] < 1 or noff[0] != 0 or eoff[0] != 0 or noff[-1] != n or eoff[-1] != e \
-            or np.any(np.diff(noff) < 0) or np.any(np.diff(eoff) < 0):
-        raise ValueError('pose_graph_optimize: offsets must be [G + 1], ascending, from 0 to the number of nodes / edges')
-    if line_process_weight is not None and not line_process_weight > 0:
-        raise ValueError(f'pose_graph_optimize: line_process_weight must be > 0 or None, got {line_process_weight}')
-    g = noff.shape[0] - 1
-    if g > 0 and np.diff(noff).max() <= POSE_GRAPH_MAX_NODES and np.diff(eoff).max() <= POSE_GRAPH_MAX_EDGES:
-        _pose_graph_connected(ed, noff, eoff)
     if pcg_max_iterations is None:
         pcg_max_iterations = 60 * max(int(np.diff(noff).max()) - 1 if g > 0 else 0, 0) + 64
     out = torch.empty_like(X)
@@ -1996,6 +2023,46 @@ def pose_graph_optimize(nodes, edges, transforms, informations, uncertain=None, 
                                                 _lib.ptr(out), _lib.ptr(weights), _lib.ptr(pruned), report.ctypes.data,
                                                 ws.data_ptr(), ws.numel(), _lib.stream_ptr()), 'rdm_pose_graph_optimize')
     return PoseGraphResult(out, weights, pruned.bool(), report)
+
+
+class PoseGraphMarginals:
+    """What pose_graph_marginals returns.  covariances: float64 [N, 6, 6] on the device the call ran on -- row i is the covariance
+    of node i's right perturbation X_i [Exp(dw) | dt] (rotation first) given its graph's node 0, whose row is zero; every block is
+    exactly symmetric.  Per graph, host numpy [G]: status (0; 4: a pivot was not positive -- zero weights cut a node off, or an
+    information matrix is indefinite -- and the graph's rows but row 0 are NaN) and separator (the direct solve's separator size)."""
+
+    def __init__(self, covariances, report):
+        import numpy as np
+        self.covariances = covariances
+        rep = np.asarray(report, dtype=np.float64).reshape(-1, 2)
+        self.status, self.separator = rep[:, 0].astype(np.int64), rep[:, 1].astype(np.int64)
+
+
+def pose_graph_marginals(nodes, edges, transforms, informations, weights=None, *, graph_node_offsets=None, graph_edge_offsets=None):
+    """The marginal covariance of every pose of a pose graph on the GPU (rdm_pose_graph_marginals; g2o's computeMarginals, GTSAM's
+    Marginals): Sigma_i = (H^-1)_ii with H = sum_e w_e J_e^T L_e J_e over the free nodes, the undamped
+    Gauss-Newton matrix at `nodes` -- normally pose_graph_optimize's output, with its `weights` (float64 [E] >= 0, device or host;
+    None: every weight 1; set pruned edges' to 0 to leave them out).  The other arguments are pose_graph_optimize's.  The blocks come
+    from the direct solve's factors by a selected inversion (no dense inverse), so a graph may need at most 256 separator nodes:
+    above that the call is a RuntimeError naming the graph and the count.  -> PoseGraphMarginals.  ValueError, before any library
+    call, for shapes, offsets, a negative or non-finite weight and a node without a path to node 0; RuntimeError (the library's
+    argument error, nothing written) for what pose_graph_optimize refuses and for a residual beyond the angle limit."""
+    import numpy as np
+    dev, X, T, Lm, ed, _, noff, eoff, g, W = _pose_graph_args('pose_graph_marginals', nodes, edges, transforms, informations, None,
+                                                              graph_node_offsets, graph_edge_offsets, weights=weights)
+    L = _lib.lib()
+    n = X.shape[0]
+    out = torch.empty((n, 6, 6), dtype=torch.float64, device=dev)
+    report = np.zeros((g, 2), np.float64)
+    with torch.cuda.device(dev):
+        size = L.rdm_pose_graph_marginals_workspace_bytes(g, noff.ctypes.data, eoff.ctypes.data, ed.ctypes.data)
+        if size == 0:  # (an edge outside its graph, a graph above a limit: the library's message, before any GPU work)
+            _lib.check(-1, 'rdm_pose_graph_marginals')
+        ws = scratch(dev, size)
+        _lib.check(L.rdm_pose_graph_marginals(g, noff.ctypes.data, eoff.ctypes.data, _lib.ptr(X), ed.ctypes.data, _lib.ptr(T), _lib.ptr(Lm),
+                                              0 if W is None else _lib.ptr(W), _lib.ptr(out), report.ctypes.data, ws.data_ptr(), ws.numel(),
+                                              _lib.stream_ptr()), 'rdm_pose_graph_marginals')
+    return PoseGraphMarginals(out, report)
 
 
 def _gt_check(t, name, shape, dtype, device):

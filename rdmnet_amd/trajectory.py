@@ -1,7 +1,7 @@
 """Trajectories of a run over a sequence: the reference's chaining and absolute trajectory error, and the pose graph of a run.
 
     python -m rdmnet_amd.trajectory --features-root DIR [--optimize] [--line-process-weight MU] [--unit-information] [--out DIR]
-                                  [--preconditioner {block_jacobi,chain}] [--linear-solver {pcg,direct}]
+                                  [--preconditioner {block_jacobi,chain}] [--linear-solver {pcg,direct}] [--covariance]
                                   [--map-scans DATASET_ROOT [--map-raw] [--map-voxel 0.3] [--map-min-points 1]
                                    [--map-range LO HI] [--map-batch 64] [--map-sharpness [--map-sharpness-min-points 4]]
                                    [--map-min-scans 1]
@@ -18,7 +18,13 @@ pair's ref frame, and whose ref frame is new to the chain, continues the odometr
 several such pairs the first in file order); every other pair file of the sequence is an uncertain (loop-closure) edge between
 two frames of the chain.  With --optimize all sequences are optimised as one batch by
 `ops.pose_graph_optimize` (--preconditioner chain selects its odometry-chain preconditioner, which suits exactly
-these graphs; --linear-solver direct its direct sparse solve in place of the conjugate gradients) and the report is printed for the optimised trajectory too.  Without --optimize no
+these graphs; --linear-solver direct its direct sparse solve in place of the conjugate gradients) and the report is printed for the optimised trajectory too.  With --covariance
+(which needs --optimize) every sequence's `pose graph:` line is followed by an `optimized uncertainty:` line -- the marginal covariance
+of every optimised pose given frame 0 (`ops.pose_graph_marginals` at the optimised poses with the final line-process weights, pruned
+edges at 0; one call per sequence): the median and the largest position sigma (root of the trace of the translation block, metres) and
+rotation sigma (root of the trace of the rotation block, degrees) with the frames of the largest, or `not computed (K separator nodes,
+limit 256)` for a sequence with more loop structure than the selected inversion takes -- and --out gets `{seq}_optimized_covariance.txt`,
+one row of 36 numbers per frame of the chain (the 6 x 6 block of the right perturbation, rotation first; the first row zeros).  Without --optimize no
 GPU is needed.  Everything here is numpy float64 on the host.  With --map-scans (and --out) the scans of every sequence's chain
 frames are fused under the chained -- and with --optimize also the optimised -- poses into a voxel map on the GPU (`build_map`,
 `ops.VoxelMap`) and written as `{seq}_{variant}_map.npy`; a better trajectory puts the same surfaces into
@@ -180,6 +186,28 @@ def sequence_graph(s):
     pick = lambda v: [v[k] for k in keep]
     return (nodes, np.asarray(pick(edges), np.int64).reshape(-1, 2), np.asarray(pick(transforms)).reshape(-1, 4, 4),
             np.asarray(pick(infos)).reshape(-1, 6, 6), np.asarray(pick(uncertain), np.uint8), pick(names))
+
+
+def uncertainty(graph, nodes, weights, pruned):
+    """The marginal covariances [n, 6, 6] of one sequence's optimised poses (ops.pose_graph_marginals; pruned edges weigh 0), or the
+    number of separator nodes when the graph needs more than the library's limit."""
+    from . import _lib, ops
+    edges = np.ascontiguousarray(graph[1], dtype=np.int64)
+    limit = _lib.lib().rdm_pose_graph_direct_max_separator()
+    need = _lib.lib().rdm_pose_graph_separator_host(len(nodes), len(edges), edges.ctypes.data, 0, 0)
+    if need > limit:
+        return int(need)
+    res = ops.pose_graph_marginals(nodes, edges, graph[2], graph[3], np.where(pruned != 0, 0.0, weights))
+    return res.covariances.cpu().numpy()
+
+
+def uncertainty_line(seq, cov, limit=256):
+    if isinstance(cov, int):
+        return f'seq {seq} optimized uncertainty: not computed ({cov} separator nodes, limit {limit})'
+    pos = np.sqrt(np.trace(cov[:, 3:, 3:], axis1=1, axis2=2))
+    rot = np.degrees(np.sqrt(np.trace(cov[:, :3, :3], axis1=1, axis2=2)))
+    return (f'seq {seq} optimized uncertainty: position sigma median {np.median(pos):.6g} m, max {pos.max():.6g} m at frame '
+            f'{int(np.argmax(pos))}; rotation sigma median {np.median(rot):.6g} deg, max {rot.max():.6g} deg at frame {int(np.argmax(rot))}')
 
 
 def report_line(seq, what, err):
@@ -632,6 +660,9 @@ def map_paths(args, seqs):
 
 
 def run(args, emit=print):
+    covariance = bool(getattr(args, 'covariance', False))
+    if covariance and not args.optimize:
+        raise TrajectoryError('--covariance needs --optimize')
     seqs = read_sequences(args.features_root, args.unit_information)
     graphs = {seq: sequence_graph(s) for seq, s in seqs.items()}
     scans = map_paths(args, seqs)
@@ -744,6 +775,12 @@ def run(args, emit=print):
         names = [graphs[seq][5][int(e)] for e in np.nonzero(pruned[eoff[g]:eoff[g + 1]])[0]]
         emit(f'seq {seq} pose graph: {noff[g + 1] - noff[g]} nodes, {eoff[g + 1] - eoff[g]} edges, cost {res.initial_cost[g]:.6g} -> '
              f'{res.final_cost[g]:.6g}, {res.iterations[g]} iterations ({res.stop_reasons[g]}), pruned edges: {names}')
+        if covariance:
+            cov = uncertainty(graphs[seq], nodes[noff[g]:noff[g + 1]], res.weights[int(eoff[g]):int(eoff[g + 1])].cpu().numpy(),
+                              pruned[eoff[g]:eoff[g + 1]])
+            emit(uncertainty_line(seq, cov))
+            if args.out and not isinstance(cov, int):
+                np.savetxt(osp.join(args.out, f'{seq}_optimized_covariance.txt'), cov.reshape(-1, 36), fmt='%.9e')
         if args.out:
             write_kitti_poses(osp.join(args.out, f'{seq}_optimized.txt'), nodes[noff[g]:noff[g + 1]])
         if scans:
@@ -780,6 +817,9 @@ def make_parser():
                     help='of the conjugate gradients inside --optimize: the node blocks, or the odometry chain factored exactly')
     ap.add_argument('--linear-solver', choices=('pcg', 'direct'), default='pcg',
                     help='of --optimize: conjugate gradients, or the direct sparse solve for a chain with loop closures')
+    ap.add_argument('--covariance', action='store_true',
+                    help='after --optimize: the marginal covariance of every optimised pose given frame 0 -- an `optimized uncertainty:` '
+                         'line per sequence and, with --out, {seq}_optimized_covariance.txt (one 6 x 6 block per frame, rotation first)')
     ap.add_argument('--out', default=None, help='directory for one KITTI-format pose file per sequence and variant')
     ap.add_argument('--map-scans', default=None, metavar='DATASET_ROOT',
                     help='fuse the scans of every chain frame under each trajectory into a voxel map on the GPU, written to --out as '

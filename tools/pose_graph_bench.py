@@ -4,12 +4,16 @@ for comparison: the restatement's dense solve (tests/pose_graph_restatement.py, 
 and, where scipy is importable, the same damped Gauss-Newton iteration with a sparse direct solve (scipy.sparse.linalg.spsolve).
 
   python tools/pose_graph_bench.py [--nodes 500] [--loops 40] [--batch 11] [--reps 3] [--cpu] [--preconditioner chain]
-                                     [--linear-solver direct] [--digest host | gpu]
+                                     [--linear-solver direct] [--marginals] [--digest host | gpu]
 With --digest (and nothing else): no timing, one sha1 line per result of the library's host entry points (host: no GPU needed, see
 digest_host()) or of the GPU solves of the test graphs (gpu, see digest_gpu()), for comparing the bits of two builds of the library
 (RDM_LIB_PATH).  Otherwise prints one JSON line: sizes, GPU ms per call (median; a call ends with its read-back), outer iterations, PCG iterations per outer
 iteration, and the host's ms per solve.  --preconditioner (block_jacobi | chain) is passed to ops.pose_graph_optimize and named in
-the output; without the flag the call and the output are what they were.  --linear-solver (pcg | direct) likewise."""
+the output; without the flag the call and the output are what they were.  --linear-solver (pcg | direct) likewise.  --marginals
+also times ops.pose_graph_marginals (rdm_pose_graph_marginals) at the optimised poses with the final weights, pruned edges at 0,
+beside the optimise call of the same run -- ms per call, its ratio to the optimise call, and for the single graph how the run
+sweep's wavefronts spent their time (rdm_dbg_pose_graph_marginals_ticks: the columns' products, the butterflies, the nodes' steps) --
+and, with --cpu, np.linalg.inv on the same graph's dense H."""
 import argparse
 import hashlib
 import json
@@ -142,6 +146,15 @@ def digest_host():
                 for pre in (0, 1) for solver in (0, 1)]
         assert all(v > 0 for v in got), got
         sha1_line(f'workspace_bytes G {G} N {N} E {E}', [np.array(got, np.uint64)])
+    # (the marginals' lines come last: the lines above are what they were)
+    import test_pose_graph_marginals as tm
+    for name, (n, chords, _) in tm.SHAPES.items():
+        edges, diag, off, _ = td.random_system(n, chords, seed=300 + n + len(chords))
+        rc, out = tm.marginals_host(n, edges, diag, off)
+        sha1_line(f'marginals_host {name} rc {rc}', [out])
+    diag, off = tm.system(c, np.ones(len(c['edges'])))
+    rc, out = tm.marginals_host(len(c['nodes']), c['edges'], diag, off)
+    sha1_line(f'marginals_host noisy rc {rc}', [out])
 
 
 def digest_gpu():
@@ -184,6 +197,13 @@ def digest_gpu():
                 report = np.array([getattr(res, f)[k] for f in fields], np.float64)
                 sha1_line(f'{name} graph {k} {solver} steps {res.iterations[k]} pcg {res.pcg_iterations[k]}',
                           [nodes[noff[k]:noff[k + 1]], weights[eoff[k]:eoff[k + 1]], pruned[eoff[k]:eoff[k + 1]], report])
+    # (the marginals' lines come last: the lines above are what they were)
+    import pose_graph_marginals_restatement as M
+    for name in M.GRAPHS:
+        c, w, _ = M.graph(name)
+        res = ops.pose_graph_marginals(torch.from_numpy(c['nodes']).cuda(), c['edges'], torch.from_numpy(c['transforms']).cuda(),
+                                       torch.from_numpy(c['informations']).cuda(), torch.from_numpy(w).cuda())
+        sha1_line(f'marginals {name} status {res.status[0]} separator {res.separator[0]}', [res.covariances.cpu().numpy()])
 
 
 def main():
@@ -197,6 +217,7 @@ def main():
     ap.add_argument('--cpu', action='store_true', help='also time the host: the dense restatement and, with scipy, a sparse solve')
     ap.add_argument('--preconditioner', choices=('block_jacobi', 'chain'), default=None)
     ap.add_argument('--linear-solver', choices=('pcg', 'direct'), default=None)
+    ap.add_argument('--marginals', action='store_true', help='also time ops.pose_graph_marginals at the optimised poses')
     a = ap.parse_args()
     if a.digest is not None:
         return digest_host() if a.digest == 'host' else digest_gpu()
@@ -227,10 +248,40 @@ def main():
             t0 = time.perf_counter()
             res = call()
             times.append((time.perf_counter() - t0) * 1e3)
-        return {'gpu_ms': float(np.median(times)), 'gpu_ms_all': times, 'iterations': res.iterations.tolist(),
-                'pcg_per_iteration': (res.pcg_iterations / np.maximum(res.iterations, 1)).round(1).tolist(),
-                'stop': res.stop_reasons, 'cost': [res.initial_cost.tolist(), res.final_cost.tolist()],
-                'pruned': int(res.pruned.sum())}
+        row = {'gpu_ms': float(np.median(times)), 'gpu_ms_all': times, 'iterations': res.iterations.tolist(),
+               'pcg_per_iteration': (res.pcg_iterations / np.maximum(res.iterations, 1)).round(1).tolist(),
+               'stop': res.stop_reasons, 'cost': [res.initial_cost.tolist(), res.final_cost.tolist()],
+               'pruned': int(res.pruned.sum())}
+        if a.marginals:
+            w = torch.where(res.pruned, torch.zeros_like(res.weights), res.weights)
+            marg = lambda: ops.pose_graph_marginals(res.nodes, cat['edges'], dev['transforms'], dev['informations'], w,
+                                                    graph_node_offsets=noff, graph_edge_offsets=eoff)
+            m = marg()  # warm-up
+            torch.cuda.synchronize()
+            mt = []
+            for _ in range(a.reps):
+                t0 = time.perf_counter()
+                m = marg()
+                mt.append((time.perf_counter() - t0) * 1e3)
+            sigma = torch.sqrt(torch.diagonal(m.covariances[:, 3:, 3:], dim1=1, dim2=2).sum(1))
+            row.update({'marginals_ms': float(np.median(mt)), 'marginals_ms_all': mt, 'marginals_per_optimize': float(np.median(mt)) / row['gpu_ms'],
+                        'marginals_status': m.status.tolist(), 'separator': m.separator.tolist(),
+                        'position_sigma_max_m': float(sigma.max())})
+            if len(gs) == 1:  # the run sweep's phase clocks: 3 ticks of 10 ns per run
+                from rdmnet_amd import _lib
+                ticks = torch.zeros(3 * len(cat['nodes']), dtype=torch.int64, device='cuda')
+                _lib.lib().rdm_dbg_pose_graph_marginals_ticks(ticks.data_ptr())
+                try:
+                    marg()
+                    torch.cuda.synchronize()
+                finally:
+                    _lib.lib().rdm_dbg_pose_graph_marginals_ticks(0)
+                t = ticks.cpu().numpy().reshape(-1, 3)
+                t = t[t.sum(1) > 0] * 1e-2  # microseconds
+                row['sweep_runs'] = len(t)
+                row['sweep_us_longest_run'] = dict(zip(('columns', 'butterflies', 'node_steps'), t[np.argmax(t.sum(1))].round(1).tolist()))
+                row['sweep_us_all_runs'] = dict(zip(('columns', 'butterflies', 'node_steps'), t.sum(0).round(1).tolist()))
+        return row
 
     out['one_graph'] = run(graphs[:1])
     out['batch_of_graphs'] = run(graphs)
@@ -240,6 +291,15 @@ def main():
         res = R.optimize(c['nodes'], c['edges'], c['transforms'], c['informations'], c['uncertain'], MU, **TOL)
         out['host_dense'] = {'ms': (time.perf_counter() - t0) * 1e3, 'iterations': res['iterations'], 'cost': res['cost'],
                              'threads': os.environ.get('OMP_NUM_THREADS')}
+        if a.marginals:
+            H = R.normal_equations(res['nodes'], c['edges'], c['transforms'], c['informations'], c['uncertain'], MU)[0][6:, 6:]
+            inv_ms = []
+            for _ in range(a.reps):
+                t0 = time.perf_counter()
+                np.linalg.inv(H)
+                inv_ms.append((time.perf_counter() - t0) * 1e3)
+            out['host_dense_inverse'] = {'ms': float(np.median(inv_ms)), 'ms_all': inv_ms, 'unknowns': len(H),
+                                         'threads': os.environ.get('OMP_NUM_THREADS')}
         try:
             import scipy  # noqa: F401
         except ImportError:
