@@ -39,14 +39,17 @@
 // different scans add, to the bits of the map built in one pass.
 //
 // Alignment (include/rdmnet_hip.h, "voxel map alignment"; tests/voxel_align_restatement.py): register with another map's voxel records
-// in the place of a scan's points -- align_accumulate_kernel, below register's, whose init and finalize kernels it shares.
+// in the place of a scan's points -- accumulate_kernel with RecordRow where register has PointRow; the init and finalize kernels and
+// the host's gauss_newton driver are shared.
 //
-// Four pinned definitions are written once: the point gate (gate_sensor, gate_world; integrate, register and query), the key (pack_key,
-// key_cell; integrate, register, query, extract), the voxel Gaussian (voxel_gaussian; both extracts, register and query) and the weight
-// of a residual (voxel_precision; register and query).  `#pragma clang fp
-// contract(off)` is lexical and does not follow an inlined callee: every helper with pinned arithmetic opens with it itself, and
-// jacobi3 and rodrigues, which stand outside any such block, stay there.
+// The pinned definitions are written once: the point gate (gate_sensor, gate_world over world_fixed; integrate, register and query;
+// world_fixed alone: align's record), the key (pack_key, key_cell), the voxel Gaussian (voxel_gaussian over sum_mean and
+// sums_covariance; both extracts, register, query, and align's record through the two parts), the visit of a cell and its six face
+// neighbours (for_each_neighbor; register, align and query), the weight of a residual (voxel_precision) and a pair's sums (accumulate_pairs;
+// register and align).  `#pragma clang fp contract(off)` is lexical and does not follow an inlined callee: every helper with pinned
+// arithmetic opens with it itself, and jacobi3 and rodrigues, which stand outside any such block, stay there.
 #include <cmath>
+#include <string>
 
 #include "../../include/rdmnet_hip.h"
 #include "cell_index.h"
@@ -195,12 +198,11 @@ __device__ __forceinline__ int gate_sensor(const float* __restrict__ p, int chan
   return lo2 <= r2 && r2 <= hi2 ? kPass : kRange;
 }
 
-// World frame, after kPass above: wd = X v (X: the first 12 doubles of a row-major 4 x 4) with the restatement's association, q = the
-// fixed-point coordinates and attributes (meaningful on kPass) -> kExtent (a cell outside [-2^20, 2^20) or |attribute| >= 2^20) or kPass.
-__device__ __forceinline__ int gate_world(const float (&v)[kMaxC], const double* __restrict__ X, double voxel, double (&wd)[3],
-                                          long long (&q)[kMaxC]) {
+// wd = X (x, y, z) (X: the first 12 doubles of a row-major 4 x 4) with the restatement's association and q[0 .. 2] = its fixed-point
+// coordinates on the grid of `voxel` (0 for a coordinate outside) -> whether all three cells lie in [-2^20, 2^20).
+__device__ __forceinline__ bool world_fixed(const double* __restrict__ X, double x, double y, double z, double voxel, double (&wd)[3],
+                                            long long* __restrict__ q) {
 #pragma clang fp contract(off)
-  const double x = v[0], y = v[1], z = v[2];
   bool inside = true;
   for (int d = 0; d < 3; ++d) {
     wd[d] = ((X[4 * d] * x + X[4 * d + 1] * y) + X[4 * d + 2] * z) + X[4 * d + 3];
@@ -209,6 +211,15 @@ __device__ __forceinline__ int gate_world(const float (&v)[kMaxC], const double*
     inside = inside && ok;
     q[d] = ok ? static_cast<long long>(f) : 0ll;
   }
+  return inside;
+}
+
+// World frame, after kPass above: world_fixed of the row's xyz, then q[3 ..] = the fixed-point attributes (meaningful on kPass) ->
+// kExtent (a cell outside [-2^20, 2^20) or |attribute| >= 2^20) or kPass.
+__device__ __forceinline__ int gate_world(const float (&v)[kMaxC], const double* __restrict__ X, double voxel, double (&wd)[3],
+                                          long long (&q)[kMaxC]) {
+#pragma clang fp contract(off)
+  bool inside = world_fixed(X, v[0], v[1], v[2], voxel, wd, q);
   for (int c = 3; c < kMaxC; ++c) {
     const double a = v[c];
     inside = inside && fabs(a) < kScale;
@@ -224,21 +235,32 @@ struct Gaussian {
   double mean[3], cov[6];
 };
 
+// The two parts of it, which align also applies to a source record: a coordinate's mean in metres from its fixed-point sum over n
+// points, and the covariance from the nine sums S of the n points' 12-bit local coordinates, both on the grid of `voxel`.
+__device__ __forceinline__ double sum_mean(long long sum, double n, double voxel) {
+#pragma clang fp contract(off)
+  return static_cast<double>(sum) / n / kScale * voxel;
+}
+
+__device__ __forceinline__ void sums_covariance(const double (&S)[kPlanes], double n, double voxel, double (&cov)[6]) {
+#pragma clang fp contract(off)
+  const double s = voxel / kMomSteps, s2 = s * s;
+  const double m[3] = {S[0] / n, S[1] / n, S[2] / n};
+  for (int a = 0, k = 0; a < 3; ++a)
+    for (int b = a; b < 3; ++b, ++k) cov[k] = (S[3 + k] / n - m[a] * m[b]) * s2;
+}
+
 template <bool kCov>
 __device__ __forceinline__ Gaussian voxel_gaussian(const Table& t, const unsigned long long* __restrict__ moments, long long capacity,
                                                    double voxel, long long slot) {
-#pragma clang fp contract(off)
   Gaussian g;
   g.count = t.counts[slot];
   const double n = static_cast<double>(g.count);
-  for (int d = 0; d < 3; ++d) g.mean[d] = static_cast<double>(static_cast<long long>(t.sums[d * capacity + slot])) / n / kScale * voxel;
+  for (int d = 0; d < 3; ++d) g.mean[d] = sum_mean(static_cast<long long>(t.sums[d * capacity + slot]), n, voxel);
   if constexpr (kCov) {
-    const double s = voxel / kMomSteps, s2 = s * s;
     double S[kPlanes];
     for (int k = 0; k < kPlanes; ++k) S[k] = static_cast<double>(static_cast<long long>(moments[moment_at(slot, k, capacity)]));
-    const double m[3] = {S[0] / n, S[1] / n, S[2] / n};
-    for (int a = 0, k = 0; a < 3; ++a)
-      for (int b = a; b < 3; ++b, ++k) g.cov[k] = (S[3 + k] / n - m[a] * m[b]) * s2;
+    sums_covariance(S, n, voxel, g.cov);
   }
   return g;
 }
@@ -361,19 +383,30 @@ __device__ __forceinline__ long long find(const unsigned long long* __restrict__
   return -1;
 }
 
-// After rehash_kernel moved the table `a` into `b`: the nine sums of every occupied slot of `a` into the slot its key has in `b`
-// (`mb` zeroed before; the keys are distinct, so plain stores).
-__global__ void __launch_bounds__(kBlock) moments_rehash_kernel(Table a, const unsigned long long* __restrict__ ma, long long cap_a,
-                                                                Table b, unsigned long long* __restrict__ mb, long long cap_b) {
+// After rehash_kernel moved the table `a` into `b`: what a second block holds for every occupied slot of `a` into the slot its key has
+// in `b` (the new block reset before; the keys are distinct, so plain stores).  copy(i, slot): the block's payload, below.
+template <class Copy>
+__global__ void __launch_bounds__(kBlock) block_rehash_kernel(Table a, long long cap_a, Table b, long long cap_b, Copy copy) {
   const long long stride = static_cast<long long>(gridDim.x) * kBlock;
   for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < cap_a; i += stride) {
     const unsigned long long key = a.keys[i];
     if (key == kEmpty) continue;
     const long long slot = find(b.keys, cap_b, key);
-    if (slot < 0) continue;  // (a key that the map's rehash did not move: not reached after rdm_voxel_map_rehash)
-    for (int k = 0; k < kPlanes; ++k) mb[moment_at(slot, k, cap_b)] = ma[moment_at(i, k, cap_a)];
+    if (slot < 0) continue;  // (a key that the map's rehash did not move: the voxels that rdm_voxel_map_prune left behind)
+    copy(i, slot);
   }
 }
+
+struct MomentsCopy {  // the nine sums
+  const unsigned long long* __restrict__ from;
+  unsigned long long* __restrict__ to;
+  long long cap_a, cap_b;
+  __device__ void operator()(long long i, long long slot) const {
+    unsigned long long v[kPlanes];  // (nine loads in flight, then nine stores: `restrict` on a member does not license that)
+    for (int k = 0; k < kPlanes; ++k) v[k] = from[moment_at(i, k, cap_a)];
+    for (int k = 0; k < kPlanes; ++k) to[moment_at(slot, k, cap_b)] = v[k];
+  }
+};
 
 // The sweep before an integrate call (records = false: the masks alone) and the reset: no scan seen, first = kMaxScanId, last = -1.
 __global__ void __launch_bounds__(kBlock) observations_reset_kernel(Observations o, long long capacity, bool records) {
@@ -388,19 +421,13 @@ __global__ void __launch_bounds__(kBlock) observations_reset_kernel(Observations
   }
 }
 
-// moments_rehash_kernel's counterpart (`ob` reset before): the record of every occupied slot of `a` whose key `b` holds.  The mask is
-// scratch and stays behind.
-__global__ void __launch_bounds__(kBlock) observations_rehash_kernel(Table a, Observations oa, long long cap_a, Table b, Observations ob,
-                                                                     long long cap_b) {
-  const long long stride = static_cast<long long>(gridDim.x) * kBlock;
-  for (long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x; i < cap_a; i += stride) {
-    const unsigned long long key = a.keys[i];
-    if (key == kEmpty) continue;
-    const long long slot = find(b.keys, cap_b, key);
-    if (slot < 0) continue;  // (a key that the map's rehash did not move: the voxels that rdm_voxel_map_prune left behind)
-    for (int k = 0; k < kObsFields; ++k) ob.record[observed_at(slot, k)] = oa.record[observed_at(i, k)];
+struct RecordsCopy {  // block_rehash_kernel's payload of the observations: the record; the mask is scratch and stays behind
+  const int* __restrict__ from;
+  int* __restrict__ to;
+  __device__ void operator()(long long i, long long slot) const {
+    for (int k = 0; k < kObsFields; ++k) to[observed_at(slot, k)] = from[observed_at(i, k)];
   }
-}
+};
 
 // Every occupied slot of `a` into `b` (reset before): the keys are distinct, so a slot is claimed once and filled with plain stores.
 // kPrune (rdm_voxel_map_prune): only the slots with at least min_points points seen in at least min_scans scans (`oa`: the records of
@@ -724,9 +751,52 @@ int open_observations(const char* what, const void* observations, size_t observa
   return RDM_OK;
 }
 
+// A caller's map with the blocks beside it.  A block's pointer and size stand for how the entry point takes it: kAbsent (not looked
+// at), kOptional (opened when the pointer is not null) or kRequired (a null pointer is an error).
+struct Blocks {
+  Table t;
+  unsigned long long* m = nullptr;
+  Observations o{nullptr, nullptr};
+};
+enum Want { kAbsent, kOptional, kRequired };
+struct BlockArg {
+  Want want;
+  const void* p;
+  size_t bytes;
+};
+constexpr BlockArg kNoBlock{kAbsent, nullptr, 0};
+
+// the blocks of a caller, or the error code after set_error (moments_too_small: open_moments' too_small)
+int open_blocks(const char* what, const void* map, size_t map_bytes, int64_t capacity, int channels, BlockArg moments,
+                BlockArg observations, Blocks& b, int moments_too_small = RDM_ERR_WORKSPACE) {
+  if (const int rc = open_table(what, const_cast<void*>(map), map_bytes, capacity, channels, b.t)) return rc;
+  if (moments.want == kRequired || (moments.want == kOptional && moments.p != nullptr))
+    if (const int rc = open_moments(what, moments.p, moments.bytes, capacity, b.m, moments_too_small)) return rc;
+  if (observations.want == kRequired || (observations.want == kOptional && observations.p != nullptr))
+    if (const int rc = open_observations(what, observations.p, observations.bytes, capacity, b.o)) return rc;
+  return RDM_OK;
+}
+
+// The two sides of a rehash or a prune: the old blocks `a` and the new ones `b`, which must be other blocks of at least the old
+// capacity.  At most one of moments and observations moves with the map.
+int open_rehash(const char* what, const void* old_map, size_t old_bytes, int64_t old_capacity, BlockArg old_m, BlockArg old_o,
+                const void* new_map, size_t new_bytes, int64_t new_capacity, BlockArg new_m, BlockArg new_o, int channels, Blocks& a,
+                Blocks& b) {
+  const std::string name(what);
+  if (const int rc = open_blocks((name + " (old)").c_str(), old_map, old_bytes, old_capacity, channels, old_m, old_o, a)) return rc;
+  if (const int rc = open_blocks((name + " (new)").c_str(), new_map, new_bytes, new_capacity, channels, new_m, new_o, b)) return rc;
+  const bool mom = new_m.want != kAbsent, obs = new_o.want != kAbsent;
+  const bool other = new_capacity >= old_capacity && new_map != old_map && (!mom || new_m.p != old_m.p) && (!obs || new_o.p != old_o.p);
+  if (!mom && !obs)
+    RDM_REQUIRE(other, "%s: the new map must be another block of at least the old capacity", what);
+  else
+    RDM_REQUIRE(other, "%s: the new map and %s must be other blocks of at least the old capacity", what, mom ? "moments" : "observations");
+  return RDM_OK;
+}
+
 // ---- scan-to-map registration (include/rdmnet_hip.h, "voxel map registration"; tests/voxel_register_restatement.py) --------------
 //
-// An iteration is two launches.  register_accumulate_kernel: kRegGroups workgroups per scan; row j of a scan goes to thread
+// An iteration is two launches.  accumulate_kernel: kRegGroups workgroups per scan; row j of a scan goes to thread
 // j mod (kRegGroups kBlock) of the scan's threads, whatever else the batch holds, so a scan's sums are the same wherever it stands.
 // A thread keeps the upper triangle of H (21), g (6), the cost and two counts, block_sum adds them in a fixed order and one slab row
 // per workgroup is written.  register_finalize_kernel: one workgroup per scan adds the scan's slab rows in index order, thread 0
@@ -735,8 +805,8 @@ int open_observations(const char* what, const void* observations, size_t observa
 // Robust weights (rdm_voxel_map_register_robust, robust_scale mu > 0; tests/voxel_register_robust_restatement.py) are a second
 // instantiation, kRobust, of accumulate_pairs and of both kernels: per pair d2 = r^T M r, s = mu / (mu + d2), l = s s; every term of
 // H and g is multiplied by l before it is added, the cost takes s d2, and a 31st sum, l itself, goes to slot 30 of the slab row and
-// from there to weight_sums.  The plain instantiation has none of this in it: it is the code it was, and it never writes or reads
-// slot 30.
+// from there to weight_sums.  The plain instantiation has none of this in it -- weighted<false> is the identity, no multiply is
+// compiled -- and it never writes or reads slot 30.
 
 constexpr int kRegGroups = 64;   // workgroups per scan
 constexpr int kRegSums = 30;     // H upper triangle, g, cost, then n_corr and the gated points (integers, exact in a double)
@@ -780,24 +850,45 @@ __global__ void __launch_bounds__(kBlock) register_init_kernel(const double* __r
   st.pad = 0;
 }
 
-// What both accumulate kernels do with one world point wd of the cell `cell` at the pose X: the visit and, per pair, H's upper triangle,
-// g and the cost into acc.  kExtra: `extra`, six covariance entries, is added to the voxel's own before the inverse (align: the
-// source's R Sigma_b R^T); else it is not looked at (register).  kRobust: every pair is weighted by l = (mu / (mu + d2))^2, d2 its
-// cost term, and acc[kRegSums] takes the sum of l; else mu is not looked at.  -> the number of pairs.
-template <bool kExtra, bool kRobust = false>
-__device__ __forceinline__ int accumulate_pairs(const Table& t, const unsigned long long* __restrict__ moments, long long capacity,
-                                                double voxel, const double (&wd)[3], const long long (&cell)[3], const double (&X)[12],
-                                                const double* extra, double sigma2, unsigned int min_points, int neighbors,
-                                                double (&acc)[kRobust ? kRegSumsRobust : kRegSums], double mu = 0.0) {
-#pragma clang fp contract(off)
-  int n_corr = 0;
-  const double q0 = wd[0] - X[3], q1 = wd[1] - X[7], q2 = wd[2] - X[11];
-  for (int o = 0; o < neighbors; ++o) {  // (0,0,0), (-1,0,0), (+1,0,0), (0,-1,0), (0,+1,0), (0,0,-1), (0,0,+1)
+// The visit of register, align and query: pair(o, slot) for o = 0 ... visits - 1 -- the cell itself, then its -x, +x, -y, +y, -z, +z
+// neighbour -- wherever that cell lies in the extent and its slot holds at least min_points points.  (A loop around the body and no
+// function that returns a slot or -1: behind such a return the compiler reads the slot's count a second time.)
+template <class Pair>
+__device__ __forceinline__ void for_each_neighbor(const Table& t, long long capacity, const long long (&cell)[3], int visits,
+                                                  unsigned int min_points, Pair&& pair) {
+  for (int o = 0; o < visits; ++o) {
     long long c[3] = {cell[0], cell[1], cell[2]};
     if (o > 0) c[(o - 1) >> 1] += (o & 1) ? -1 : 1;
     if (c[0] < -kHalf || c[0] >= kHalf || c[1] < -kHalf || c[1] >= kHalf || c[2] < -kHalf || c[2] >= kHalf) continue;
     const long long slot = find(t.keys, capacity, pack_key(c[0], c[1], c[2]));
     if (slot < 0 || t.counts[slot] < min_points) continue;
+    pair(o, slot);
+  }
+}
+
+// A pair's term under its weight l: the term itself where the pairs are not weighted (no multiply is compiled).
+template <bool kRobust>
+__device__ __forceinline__ double weighted(double l, double x) {
+#pragma clang fp contract(off)
+  if constexpr (kRobust)
+    return l * x;
+  else
+    return x;
+}
+
+// What the accumulate kernel does with one world point wd of the cell `cell` at the pose X: the visit and, per pair, H's upper triangle,
+// g and the cost into acc.  kExtra: `extra`, six covariance entries, is added to the voxel's own before the inverse (align: the
+// source's R Sigma_b R^T); else it is not looked at (register).  kRobust: every pair is weighted by l = (mu / (mu + d2))^2, d2 its
+// cost term, and acc[kRegSums] takes the sum of l; else mu is not looked at and acc has no such slot.  -> the number of pairs.
+template <bool kExtra, bool kRobust>
+__device__ __forceinline__ int accumulate_pairs(const Table& t, const unsigned long long* __restrict__ moments, long long capacity,
+                                                double voxel, const double (&wd)[3], const long long (&cell)[3], const double (&X)[12],
+                                                const double* extra, double sigma2, unsigned int min_points, int neighbors,
+                                                double (&acc)[kRobust ? kRegSumsRobust : kRegSums], double mu) {
+#pragma clang fp contract(off)
+  int n_corr = 0;
+  const double q0 = wd[0] - X[3], q1 = wd[1] - X[7], q2 = wd[2] - X[11];
+  for_each_neighbor(t, capacity, cell, neighbors, min_points, [&](int, long long slot) {
     Gaussian G = voxel_gaussian<true>(t, moments, capacity, voxel, slot);
     if constexpr (kExtra) {
 #pragma unroll
@@ -821,63 +912,100 @@ __device__ __forceinline__ int accumulate_pairs(const Table& t, const unsigned l
       Hrr[a][1] = B[a][0] * q2 - B[a][2] * q0;
       Hrr[a][2] = B[a][1] * q0 - B[a][0] * q1;
     }
-    int k = 0;
+    const double d2 = (r[0] * Mr[0] + r[1] * Mr[1]) + r[2] * Mr[2];
+    [[maybe_unused]] double s = 1.0, l = 1.0;
     if constexpr (kRobust) {
-      const double d2 = (r[0] * Mr[0] + r[1] * Mr[1]) + r[2] * Mr[2];
-      const double s = mu / (mu + d2), l = s * s;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int b = a; b < 3; ++b) acc[k++] += l * Hrr[a][b];
-#pragma unroll
-        for (int b = 0; b < 3; ++b) acc[k++] += l * B[a][b];
-      }
-#pragma unroll
-      for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = a; b < 3; ++b) acc[k++] += l * M[a][b];
-      acc[21] += l * (q1 * Mr[2] - q2 * Mr[1]);
-      acc[22] += l * (q2 * Mr[0] - q0 * Mr[2]);
-      acc[23] += l * (q0 * Mr[1] - q1 * Mr[0]);
-      acc[24] += l * Mr[0];
-      acc[25] += l * Mr[1];
-      acc[26] += l * Mr[2];
-      acc[27] += s * d2;
+      s = mu / (mu + d2);
+      l = s * s;
       acc[kRegSums] += l;
-      ++n_corr;
-      continue;
     }
+    int k = 0;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
 #pragma unroll
-      for (int b = a; b < 3; ++b) acc[k++] += Hrr[a][b];
+      for (int b = a; b < 3; ++b) acc[k++] += weighted<kRobust>(l, Hrr[a][b]);
 #pragma unroll
-      for (int b = 0; b < 3; ++b) acc[k++] += B[a][b];
+      for (int b = 0; b < 3; ++b) acc[k++] += weighted<kRobust>(l, B[a][b]);
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a)
 #pragma unroll
-      for (int b = a; b < 3; ++b) acc[k++] += M[a][b];
-    acc[21] += q1 * Mr[2] - q2 * Mr[1];
-    acc[22] += q2 * Mr[0] - q0 * Mr[2];
-    acc[23] += q0 * Mr[1] - q1 * Mr[0];
-    acc[24] += Mr[0];
-    acc[25] += Mr[1];
-    acc[26] += Mr[2];
-    acc[27] += (r[0] * Mr[0] + r[1] * Mr[1]) + r[2] * Mr[2];
+      for (int b = a; b < 3; ++b) acc[k++] += weighted<kRobust>(l, M[a][b]);
+    acc[21] += weighted<kRobust>(l, q1 * Mr[2] - q2 * Mr[1]);
+    acc[22] += weighted<kRobust>(l, q2 * Mr[0] - q0 * Mr[2]);
+    acc[23] += weighted<kRobust>(l, q0 * Mr[1] - q1 * Mr[0]);
+    acc[24] += weighted<kRobust>(l, Mr[0]);
+    acc[25] += weighted<kRobust>(l, Mr[1]);
+    acc[26] += weighted<kRobust>(l, Mr[2]);
+    acc[27] += weighted<kRobust>(s, d2);
     ++n_corr;
-  }
+  });
   return n_corr;
 }
 
-template <bool kRobust>
-__global__ void __launch_bounds__(kBlock) register_accumulate_kernel(Table t, const unsigned long long* __restrict__ moments,
-                                                                     long long capacity, int channels, double voxel,
-                                                                     const float* __restrict__ points, long long ld, long long total,
-                                                                     const int64_t* __restrict__ offsets, double lo2, double hi2,
-                                                                     double sigma2, unsigned int min_points, int neighbors, RegWork w,
-                                                                     double mu) {
+// The rows that the accumulate kernel sums over.  row(i, X, voxel, wd, cell, extra) -> whether row i takes part at the pose X on the
+// target's grid of `voxel`: then wd is its world point and `cell` that point's cell; with kExtra, `extra` is what accumulate_pairs
+// adds to a voxel's covariance.
+//
+// register: a scan's point behind the point gate.
+struct PointRow {
+  static constexpr bool kExtra = false;
+  const float* __restrict__ points;
+  long long ld;
+  int channels;
+  double lo2, hi2;
+  __device__ __forceinline__ bool operator()(long long i, const double (&X)[12], double voxel, double (&wd)[3], long long (&cell)[3],
+                                             double*) const {
+    float v[kMaxC];
+    long long q[kMaxC];
+    if (gate_sensor(points + i * ld, channels, lo2, hi2, v) != kPass || gate_world(v, X, voxel, wd, q) != kPass) return false;
+    for (int d = 0; d < 3; ++d) cell[d] = q[d] >> kFrac;
+    return true;
+  }
+};
+
+// align (include/rdmnet_hip.h, "voxel map alignment"; tests/voxel_align_restatement.py): a voxel record of the source map in the place
+// of a point.  The record's mean is the point, under world_fixed on the target's grid, and its covariance Sigma_b, turned by the pose,
+// is the extra: C = (R Sigma_b) R^T, upper triangle.
+struct RecordRow {
+  static constexpr bool kExtra = true;
+  const uint32_t* __restrict__ counts;
+  const long long* __restrict__ sums;
+  long long sums_ld;
+  const long long* __restrict__ moment_sums;
+  double source_voxel;
+  unsigned int source_min_points;
+  __device__ __forceinline__ bool operator()(long long i, const double (&X)[12], double voxel, double (&wd)[3], long long (&cell)[3],
+                                             double* C) const {
 #pragma clang fp contract(off)
+    const uint32_t count = counts[i];
+    if (count < source_min_points) return false;
+    const double n = static_cast<double>(count);
+    double mu[3];
+    for (int d = 0; d < 3; ++d) mu[d] = sum_mean(sums[i * sums_ld + d], n, source_voxel);
+    long long q[3];
+    if (!world_fixed(X, mu[0], mu[1], mu[2], voxel, wd, q)) return false;
+    for (int d = 0; d < 3; ++d) cell[d] = q[d] >> kFrac;
+    double S[kPlanes], cb[6];
+    for (int k = 0; k < kPlanes; ++k) S[k] = static_cast<double>(moment_sums[i * kPlanes + k]);
+    sums_covariance(S, n, source_voxel, cb);
+    const double Sb[3][3] = {{cb[0], cb[1], cb[2]}, {cb[1], cb[3], cb[4]}, {cb[2], cb[4], cb[5]}};
+    double P[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) P[a][b] = (X[4 * a] * Sb[0][b] + X[4 * a + 1] * Sb[1][b]) + X[4 * a + 2] * Sb[2][b];
+    for (int a = 0, k = 0; a < 3; ++a)
+      for (int b = a; b < 3; ++b, ++k) C[k] = (P[a][0] * X[4 * b] + P[a][1] * X[4 * b + 1]) + P[a][2] * X[4 * b + 2];
+    return true;
+  }
+};
+
+// The accumulate launch of register (PointRow) and align (RecordRow): kRegGroups workgroups per scan or source, as described above.
+template <bool kRobust, class Row>
+__global__ void __launch_bounds__(kBlock) accumulate_kernel(Table t, const unsigned long long* __restrict__ moments, long long capacity,
+                                                            double voxel, Row row, long long total, const int64_t* __restrict__ offsets,
+                                                            double sigma2, unsigned int min_points, int neighbors, RegWork w, double mu) {
   constexpr int kSums = kRobust ? kRegSumsRobust : kRegSums;
   const long long scan = blockIdx.x / kRegGroups;
   const int group = blockIdx.x % kRegGroups;
@@ -893,85 +1021,17 @@ __global__ void __launch_bounds__(kBlock) register_accumulate_kernel(Table t, co
   for (int k = 0; k < kSums; ++k) acc[k] = 0.0;
   int n_corr = 0, n_pass = 0;
   for (long long i = begin + group * kBlock + threadIdx.x; i < end; i += static_cast<long long>(kRegGroups) * kBlock) {
-    float v[kMaxC];
     double wd[3];
-    long long fixed[kMaxC];
-    if (gate_sensor(points + i * ld, channels, lo2, hi2, v) != kPass || gate_world(v, X, voxel, wd, fixed) != kPass) continue;
+    long long cell[3];
+    [[maybe_unused]] double extra[6];
+    if (!row(i, X, voxel, wd, cell, extra)) continue;
     ++n_pass;
-    const long long cell[3] = {fixed[0] >> kFrac, fixed[1] >> kFrac, fixed[2] >> kFrac};
-    n_corr += accumulate_pairs<false, kRobust>(t, moments, capacity, voxel, wd, cell, X, nullptr, sigma2, min_points, neighbors, acc, mu);
+    n_corr += accumulate_pairs<Row::kExtra, kRobust>(t, moments, capacity, voxel, wd, cell, X, extra, sigma2, min_points, neighbors, acc, mu);
   }
   acc[28] = static_cast<double>(n_corr);
   acc[29] = static_cast<double>(n_pass);
   const double sum = block_sum<kSums, kBlock>(acc, threadIdx.x);
   if (threadIdx.x < kSums) w.slab[(scan * kRegGroups + group) * kRegRow + threadIdx.x] = sum;
-}
-
-// ---- map-to-map alignment (include/rdmnet_hip.h, "voxel map alignment"; tests/voxel_align_restatement.py) ------------------------
-//
-// register with a voxel record in the place of a point: the record's mean is the point and its covariance, turned by the pose, is added
-// to the target voxel's.  The launch geometry, the slab and the two other kernels are register's.  A thread holds register's 30 sums
-// plus the six entries of R Sigma_b R^T across the visit.
-__global__ void __launch_bounds__(kBlock) align_accumulate_kernel(Table t, const unsigned long long* __restrict__ moments,
-                                                                  long long capacity, double voxel, const uint32_t* __restrict__ counts,
-                                                                  const long long* __restrict__ sums, long long sums_ld,
-                                                                  const long long* __restrict__ moment_sums, double source_voxel,
-                                                                  long long total, const int64_t* __restrict__ offsets, double sigma2,
-                                                                  unsigned int min_points, unsigned int source_min_points, int neighbors,
-                                                                  RegWork w) {
-#pragma clang fp contract(off)
-  const long long set = blockIdx.x / kRegGroups;
-  const int group = blockIdx.x % kRegGroups;
-  const RegState& st = w.st[set];
-  if (st.done) return;
-  double X[12];
-  for (int k = 0; k < 12; ++k) X[k] = st.X[k];
-  long long begin = offsets[set], end = offsets[set + 1];
-  begin = begin < 0 ? 0 : begin;
-  end = end > total ? total : end;
-  const double s = source_voxel / kMomSteps, s2 = s * s;
-  double acc[kRegSums];
-#pragma unroll
-  for (int k = 0; k < kRegSums; ++k) acc[k] = 0.0;
-  int n_corr = 0, n_pass = 0;
-  for (long long i = begin + group * kBlock + threadIdx.x; i < end; i += static_cast<long long>(kRegGroups) * kBlock) {
-    const uint32_t count = counts[i];
-    if (count < source_min_points) continue;
-    const double n = static_cast<double>(count);
-    double mu[3], wd[3];
-    long long cell[3];
-    for (int d = 0; d < 3; ++d) mu[d] = static_cast<double>(sums[i * sums_ld + d]) / n / kScale * source_voxel;
-    bool inside = true;
-    for (int d = 0; d < 3; ++d) {  // gate_world's transform, quantisation and extent, on the target's grid
-      wd[d] = ((X[4 * d] * mu[0] + X[4 * d + 1] * mu[1]) + X[4 * d + 2] * mu[2]) + X[4 * d + 3];
-      const double f = floor(wd[d] / voxel * kScale);
-      const bool ok = f >= -kQLimit && f < kQLimit;  // (NaN and infinities fail)
-      inside = inside && ok;
-      cell[d] = (ok ? static_cast<long long>(f) : 0ll) >> kFrac;
-    }
-    if (!inside) continue;
-    ++n_pass;
-    // Sigma_b: voxel_gaussian's covariance from the record's nine sums, then C = (R Sigma_b) R^T, upper triangle
-    double S[kPlanes];
-    for (int k = 0; k < kPlanes; ++k) S[k] = static_cast<double>(moment_sums[i * kPlanes + k]);
-    const double m[3] = {S[0] / n, S[1] / n, S[2] / n};
-    double cb[6];
-    for (int a = 0, k = 0; a < 3; ++a)
-      for (int b = a; b < 3; ++b, ++k) cb[k] = (S[3 + k] / n - m[a] * m[b]) * s2;
-    const double Sb[3][3] = {{cb[0], cb[1], cb[2]}, {cb[1], cb[3], cb[4]}, {cb[2], cb[4], cb[5]}};
-    double P[3][3], C[6];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-      for (int b = 0; b < 3; ++b) P[a][b] = (X[4 * a] * Sb[0][b] + X[4 * a + 1] * Sb[1][b]) + X[4 * a + 2] * Sb[2][b];
-    for (int a = 0, k = 0; a < 3; ++a)
-      for (int b = a; b < 3; ++b, ++k) C[k] = (P[a][0] * X[4 * b] + P[a][1] * X[4 * b + 1]) + P[a][2] * X[4 * b + 2];
-    n_corr += accumulate_pairs<true>(t, moments, capacity, voxel, wd, cell, X, C, sigma2, min_points, neighbors, acc);
-  }
-  acc[28] = static_cast<double>(n_corr);
-  acc[29] = static_cast<double>(n_pass);
-  const double sum = block_sum<kRegSums, kBlock>(acc, threadIdx.x);
-  if (threadIdx.x < kRegSums) w.slab[(set * kRegGroups + group) * kRegRow + threadIdx.x] = sum;
 }
 
 // Exp(omega) by Rodrigues' formula: I + a [omega]x + b [omega]x^2, a = sin(th) / th, b = (1 - cos(th)) / th^2 (their series below 1e-4).
@@ -1165,14 +1225,8 @@ __global__ void __launch_bounds__(kBlock) query_kernel(Table t, const unsigned l
         label = verdict - kNonfinite;
       } else {
         const long long cell[3] = {q[0] >> kFrac, q[1] >> kFrac, q[2] >> kFrac};
-        for (int o = 0; o < visits; ++o) {  // register's order
-          long long n[3] = {cell[0], cell[1], cell[2]};
-          if (o > 0) n[(o - 1) >> 1] += (o & 1) ? -1 : 1;
-          if (n[0] < -kHalf || n[0] >= kHalf || n[1] < -kHalf || n[1] >= kHalf || n[2] < -kHalf || n[2] >= kHalf) continue;
-          const long long slot = find(t.keys, capacity, pack_key(n[0], n[1], n[2]));
-          if (slot < 0) continue;
+        for_each_neighbor(t, capacity, cell, visits, min_points, [&](int o, long long slot) {
           const uint32_t count = t.counts[slot];
-          if (count < min_points) continue;
           ++pairs;
           if constexpr (kDist) {
             Gaussian G = voxel_gaussian<kCov>(t, moments, capacity, voxel, slot);
@@ -1181,15 +1235,15 @@ __global__ void __launch_bounds__(kBlock) query_kernel(Table t, const unsigned l
             const double r[3] = {wd[0] - G.mean[0], wd[1] - G.mean[1], wd[2] - G.mean[2]};
             double M[3][3], Mr[3];
             voxel_precision(G.cov, sigma2, r, M, Mr);
-            const double d2 = (r[0] * Mr[0] + r[1] * Mr[1]) + r[2] * Mr[2];  // register's cost term
+            const double d2 = (r[0] * Mr[0] + r[1] * Mr[1]) + r[2] * Mr[2];  // (accumulate_pairs' d2)
             sum += d2;
-            if (best >= 0 && !(d2 < best_d2)) continue;  // ties go to the smallest o
+            if (best >= 0 && !(d2 < best_d2)) return;  // ties go to the smallest o
             best_d2 = d2;
           }
           best = o;
           best_slot = slot;
           best_count = count;
-        }
+        });
         if (best >= 0 && records != nullptr)
           for (int k = 0; k < kObsFields; ++k) seen[k] = records[observed_at(best_slot, k)];
         if (best < 0)
@@ -1254,33 +1308,68 @@ int integrate(const char* what, void* map, size_t map_bytes, int64_t capacity, i
               int64_t total, const int64_t* offsets, const double* poses, int64_t n_scans, double min_range, double max_range,
               bool want_moments, void* moments, size_t moments_bytes, bool observed, void* observations, size_t observations_bytes,
               int64_t first_id, void* stream) {
-  Table t;
-  unsigned long long* m = nullptr;
-  Observations o{nullptr, nullptr};
-  if (const int rc = open_table(what, map, map_bytes, capacity, channels, t)) return rc;
-  if (want_moments)
-    if (const int rc = open_moments(what, moments, moments_bytes, capacity, m)) return rc;
-  if (observed) {
-    if (const int rc = open_observations(what, observations, observations_bytes, capacity, o)) return rc;
-    RDM_REQUIRE(n_scans <= kMaxObsScans && first_id >= 0 && first_id <= kMaxScanId - (n_scans > 0 ? n_scans : 0),
-                "%s: a call takes at most %d scans and ids in [0, 2^31 - 1), got %lld scans from id %lld", what, kMaxObsScans,
-                static_cast<long long>(n_scans), static_cast<long long>(first_id));
-  }
+  Blocks b;
+  if (const int rc = open_blocks(what, map, map_bytes, capacity, channels, {want_moments ? kRequired : kAbsent, moments, moments_bytes},
+                                 {observed ? kRequired : kAbsent, observations, observations_bytes}, b))
+    return rc;
+  RDM_REQUIRE(!observed || (n_scans <= kMaxObsScans && first_id >= 0 && first_id <= kMaxScanId - (n_scans > 0 ? n_scans : 0)),
+              "%s: a call takes at most %d scans and ids in [0, 2^31 - 1), got %lld scans from id %lld", what, kMaxObsScans,
+              static_cast<long long>(n_scans), static_cast<long long>(first_id));
   if (const int rc = check_batch(what, voxel, channels, points, ld, total, offsets, poses, n_scans, INT64_MAX, false, min_range, max_range))
     return rc;
   if (n_scans == 0 || total == 0) return RDM_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (observed)  // the masks of the call before
-    hipLaunchKernelGGL(observations_reset_kernel, dim3(blocks_for(capacity)), dim3(kBlock), 0, s, o, static_cast<long long>(capacity), false);
+    hipLaunchKernelGGL(observations_reset_kernel, dim3(blocks_for(capacity)), dim3(kBlock), 0, s, b.o, static_cast<long long>(capacity), false);
   auto kernel = observed ? (want_moments ? integrate_kernel<true, true> : integrate_kernel<false, true>)
                          : (want_moments ? integrate_kernel<true, false> : integrate_kernel<false, false>);
-  hipLaunchKernelGGL(kernel, dim3(blocks_for(total)), dim3(kBlock), 0, s, t, m, capacity, channels, voxel, points, ld, total, offsets,
-                     poses, n_scans, min_range * min_range, max_range * max_range, o, static_cast<int>(first_id));
+  hipLaunchKernelGGL(kernel, dim3(blocks_for(total)), dim3(kBlock), 0, s, b.t, b.m, capacity, channels, voxel, points, ld, total, offsets,
+                     poses, n_scans, min_range * min_range, max_range * max_range, b.o, static_cast<int>(first_id));
   return launch_status(what);
 }
 
 unsigned int least_points(int64_t min_points) {  // (counts are uint32)
   return min_points > 0xffffffffll ? 0xffffffffu : static_cast<unsigned int>(min_points);
+}
+
+// The lookup options of register, align and query, or RDM_ERR_ARG after set_error.  rest_ok / rest: the entry point's own bounds and
+// their text ("min_points >= 1, ...").
+int check_options(const char* what, double sigma, int neighbors, bool rest_ok, const char* rest) {
+  RDM_REQUIRE(sigma > 0.0 && std::isfinite(sigma), "%s: sigma must be positive and finite (got %g)", what, sigma);
+  RDM_REQUIRE(neighbors == 1 || neighbors == 7, "%s: neighbors must be 1 or 7 (got %d)", what, neighbors);
+  RDM_REQUIRE(rest_ok, "%s: need %s", what, rest);
+  return RDM_OK;
+}
+
+// The Gauss-Newton iteration of register and align from the initial `poses` of n scans or sources: the workspace, the init launch,
+// then chunks of kRegChunk evaluations -- accumulate(w), the caller's accumulate launch on `s`, and the finalize launch -- with one
+// 4-byte read-back of `running` between two chunks.  robust: the slab rows hold the sum of the weights, which goes to weight_sums.
+template <class Accumulate>
+int gauss_newton(const char* what, const double* poses, int64_t n, int max_iteration, double rot_eps, double trans_eps, bool robust,
+                 double* transforms, double* hessians, double* gradients, double* costs, double* weight_sums, int64_t* stats, void* ws,
+                 size_t ws_bytes, hipStream_t s, Accumulate accumulate) {
+  Arena ar(ws, ws_bytes);
+  RegWork w;
+  if (!carve_register(ar, n, w)) {
+    set_error("%s: workspace too small (%zu < %zu bytes)", what, ws_bytes, ar.off);
+    return RDM_ERR_WORKSPACE;
+  }
+  if (n == 0) return RDM_OK;
+  RDM_REQUIRE(transforms && hessians && gradients && costs && stats, "%s: null output", what);
+  hipLaunchKernelGGL(register_init_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, s, poses, static_cast<long long>(n), w);
+  int running = 1;
+  for (int k = 0; k <= max_iteration && running > 0;) {
+    const int end = max_iteration - k < kRegChunk ? max_iteration + 1 : k + kRegChunk;
+    for (; k < end; ++k) {
+      accumulate(w);
+      hipLaunchKernelGGL(robust ? register_finalize_kernel<true> : register_finalize_kernel<false>, dim3(static_cast<unsigned>(n)),
+                         dim3(kBlock), 0, s, w, max_iteration, rot_eps, trans_eps, transforms, hessians, gradients, costs, stats, weight_sums);
+    }
+    if (const int rc = launch_status(what)) return rc;
+    RDM_HIP_CHECK(hipMemcpyAsync(&running, w.running, sizeof(int), hipMemcpyDeviceToHost, s));  // one 4-byte read-back per chunk
+    RDM_HIP_CHECK(hipStreamSynchronize(s));
+  }
+  return RDM_OK;
 }
 
 // What both extracts do before they emit: the argument checks (outputs_ok: the entry point's own outputs are there), then the slots
@@ -1318,9 +1407,9 @@ extern "C" size_t rdm_voxel_map_bytes(int64_t capacity, int channels) {
 
 extern "C" int rdm_voxel_map_reset(void* map, size_t map_bytes, int64_t capacity, int channels, void* stream) {
   using namespace rdm;
-  Table t;
-  if (const int rc = open_table("rdm_voxel_map_reset", map, map_bytes, capacity, channels, t)) return rc;
-  hipLaunchKernelGGL(reset_kernel, dim3(blocks_for(capacity)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), t,
+  Blocks b;
+  if (const int rc = open_blocks("rdm_voxel_map_reset", map, map_bytes, capacity, channels, kNoBlock, kNoBlock, b)) return rc;
+  hipLaunchKernelGGL(reset_kernel, dim3(blocks_for(capacity)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), b.t,
                      static_cast<long long>(capacity), channels);
   return launch_status("rdm_voxel_map_reset");
 }
@@ -1335,24 +1424,25 @@ extern "C" int rdm_voxel_map_integrate(void* map, size_t map_bytes, int64_t capa
 extern "C" int rdm_voxel_map_rehash(const void* old_map, size_t old_bytes, int64_t old_capacity, void* new_map, size_t new_bytes,
                                     int64_t new_capacity, int channels, void* stream) {
   using namespace rdm;
-  Table a, b;
-  if (const int rc = open_table("rdm_voxel_map_rehash (old)", const_cast<void*>(old_map), old_bytes, old_capacity, channels, a)) return rc;
-  if (const int rc = open_table("rdm_voxel_map_rehash (new)", new_map, new_bytes, new_capacity, channels, b)) return rc;
-  RDM_REQUIRE(new_capacity >= old_capacity && new_map != old_map, "rdm_voxel_map_rehash: the new map must be another block of at least the old capacity");
+  const char* what = "rdm_voxel_map_rehash";
+  Blocks a, b;
+  if (const int rc = open_rehash(what, old_map, old_bytes, old_capacity, kNoBlock, kNoBlock, new_map, new_bytes, new_capacity, kNoBlock, kNoBlock,
+                                 channels, a, b))
+    return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(reset_kernel, dim3(blocks_for(new_capacity)), dim3(kBlock), 0, s, b, static_cast<long long>(new_capacity), channels);
-  hipLaunchKernelGGL(rehash_kernel<false>, dim3(blocks_for(old_capacity)), dim3(kBlock), 0, s, a, static_cast<long long>(old_capacity), b,
-                     static_cast<long long>(new_capacity), channels, Observations{nullptr, nullptr}, 0u, 0);
-  return launch_status("rdm_voxel_map_rehash");
+  hipLaunchKernelGGL(reset_kernel, dim3(blocks_for(new_capacity)), dim3(kBlock), 0, s, b.t, static_cast<long long>(new_capacity), channels);
+  hipLaunchKernelGGL(rehash_kernel<false>, dim3(blocks_for(old_capacity)), dim3(kBlock), 0, s, a.t, static_cast<long long>(old_capacity),
+                     b.t, static_cast<long long>(new_capacity), channels, Observations{nullptr, nullptr}, 0u, 0);
+  return launch_status(what);
 }
 
 extern "C" int rdm_voxel_map_stats(const void* map, size_t map_bytes, int64_t capacity, int channels, uint64_t* stats, void* stream) {
   using namespace rdm;
-  Table t;
-  if (const int rc = open_table("rdm_voxel_map_stats", const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
+  Blocks b;
+  if (const int rc = open_blocks("rdm_voxel_map_stats", map, map_bytes, capacity, channels, kNoBlock, kNoBlock, b)) return rc;
   RDM_REQUIRE(stats != nullptr, "rdm_voxel_map_stats: null stats");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  RDM_HIP_CHECK(hipMemcpyAsync(stats, t.counters, kStats * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  RDM_HIP_CHECK(hipMemcpyAsync(stats, b.t.counters, kStats * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   RDM_HIP_CHECK(hipStreamSynchronize(s));
   return RDM_OK;
 }
@@ -1370,14 +1460,14 @@ extern "C" int rdm_voxel_map_extract(const void* map, size_t map_bytes, int64_t 
                                      int64_t min_points, float* points, int32_t* counts, int32_t* cells, int64_t max_rows,
                                      int64_t* n_rows, void* ws, size_t ws_bytes, void* stream) {
   using namespace rdm;
-  Table t;
-  if (const int rc = open_table("rdm_voxel_map_extract", const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
+  Blocks b;
+  if (const int rc = open_blocks("rdm_voxel_map_extract", map, map_bytes, capacity, channels, kNoBlock, kNoBlock, b)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   ExtractWork w;
-  if (const int rc = select_sorted("rdm_voxel_map_extract", t, capacity, voxel, min_points, max_rows, n_rows,
+  if (const int rc = select_sorted("rdm_voxel_map_extract", b.t, capacity, voxel, min_points, max_rows, n_rows,
                                    max_rows == 0 || (points && counts && cells), ws, ws_bytes, s, w))
     return rc;
-  hipLaunchKernelGGL(emit_kernel, dim3(blocks_for(max_rows)), dim3(kBlock), 0, s, t, static_cast<long long>(capacity), channels, voxel,
+  hipLaunchKernelGGL(emit_kernel, dim3(blocks_for(max_rows)), dim3(kBlock), 0, s, b.t, static_cast<long long>(capacity), channels, voxel,
                      w.keys, w.slots, w.n_sel, static_cast<long long>(max_rows), points, counts, cells, n_rows);
   return launch_status("rdm_voxel_map_extract");
 }
@@ -1415,20 +1505,18 @@ extern "C" int rdm_voxel_moments_rehash(const void* old_map, size_t old_bytes, i
                                         size_t old_moments_bytes, const void* new_map, size_t new_bytes, int64_t new_capacity,
                                         void* new_moments, size_t new_moments_bytes, int channels, void* stream) {
   using namespace rdm;
-  Table a, b;
-  unsigned long long *ma, *mb;
-  if (const int rc = open_table("rdm_voxel_moments_rehash (old)", const_cast<void*>(old_map), old_bytes, old_capacity, channels, a)) return rc;
-  if (const int rc = open_table("rdm_voxel_moments_rehash (new)", const_cast<void*>(new_map), new_bytes, new_capacity, channels, b)) return rc;
-  if (const int rc = open_moments("rdm_voxel_moments_rehash (old)", const_cast<void*>(old_moments), old_moments_bytes, old_capacity, ma)) return rc;
-  if (const int rc = open_moments("rdm_voxel_moments_rehash (new)", new_moments, new_moments_bytes, new_capacity, mb)) return rc;
-  RDM_REQUIRE(new_capacity >= old_capacity && new_map != old_map && new_moments != old_moments,
-              "rdm_voxel_moments_rehash: the new map and moments must be other blocks of at least the old capacity");
+  const char* what = "rdm_voxel_moments_rehash";
+  Blocks a, b;
+  if (const int rc = open_rehash(what, old_map, old_bytes, old_capacity, {kRequired, old_moments, old_moments_bytes}, kNoBlock, new_map, new_bytes,
+                                 new_capacity, {kRequired, new_moments, new_moments_bytes}, kNoBlock, channels, a, b))
+    return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(moments_reset_kernel, dim3(blocks_for(new_capacity * kPlanes)), dim3(kBlock), 0, s, mb,
+  hipLaunchKernelGGL(moments_reset_kernel, dim3(blocks_for(new_capacity * kPlanes)), dim3(kBlock), 0, s, b.m,
                      static_cast<long long>(new_capacity) * kPlanes);
-  hipLaunchKernelGGL(moments_rehash_kernel, dim3(blocks_for(old_capacity)), dim3(kBlock), 0, s, a, ma, static_cast<long long>(old_capacity),
-                     b, mb, static_cast<long long>(new_capacity));
-  return launch_status("rdm_voxel_moments_rehash");
+  hipLaunchKernelGGL(block_rehash_kernel<MomentsCopy>, dim3(blocks_for(old_capacity)), dim3(kBlock), 0, s, a.t,
+                     static_cast<long long>(old_capacity), b.t, static_cast<long long>(new_capacity),
+                     MomentsCopy{a.m, b.m, static_cast<long long>(old_capacity), static_cast<long long>(new_capacity)});
+  return launch_status(what);
 }
 
 extern "C" int rdm_voxel_map_extract_moments(const void* map, size_t map_bytes, int64_t capacity, int channels, const void* moments,
@@ -1436,16 +1524,16 @@ extern "C" int rdm_voxel_map_extract_moments(const void* map, size_t map_bytes, 
                                              double* eigenvalues, double* normals, int64_t max_rows, int64_t* n_rows, void* ws,
                                              size_t ws_bytes, void* stream) {
   using namespace rdm;
-  Table t;
-  unsigned long long* m;
-  if (const int rc = open_table("rdm_voxel_map_extract_moments", const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
-  if (const int rc = open_moments("rdm_voxel_map_extract_moments", moments, moments_bytes, capacity, m)) return rc;
+  Blocks b;
+  if (const int rc = open_blocks("rdm_voxel_map_extract_moments", map, map_bytes, capacity, channels, {kRequired, moments, moments_bytes},
+                                 kNoBlock, b))
+    return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   ExtractWork w;
-  if (const int rc = select_sorted("rdm_voxel_map_extract_moments", t, capacity, voxel, min_points, max_rows, n_rows,
+  if (const int rc = select_sorted("rdm_voxel_map_extract_moments", b.t, capacity, voxel, min_points, max_rows, n_rows,
                                    max_rows == 0 || (cov && eigenvalues && normals), ws, ws_bytes, s, w))
     return rc;
-  hipLaunchKernelGGL(emit_moments_kernel, dim3(blocks_for(max_rows)), dim3(kBlock), 0, s, t, m, static_cast<long long>(capacity), voxel,
+  hipLaunchKernelGGL(emit_moments_kernel, dim3(blocks_for(max_rows)), dim3(kBlock), 0, s, b.t, b.m, static_cast<long long>(capacity), voxel,
                      w.slots, w.n_sel, static_cast<long long>(max_rows), sums, cov, eigenvalues, normals, n_rows);
   return launch_status("rdm_voxel_map_extract_moments");
 }
@@ -1487,18 +1575,14 @@ extern "C" int rdm_voxel_observations_rehash(const void* old_map, size_t old_byt
                                              void* new_observations, size_t new_observations_bytes, int channels, void* stream) {
   using namespace rdm;
   const char* what = "rdm_voxel_observations_rehash";
-  Table a, b;
-  Observations oa, ob;
-  if (const int rc = open_table("rdm_voxel_observations_rehash (old)", const_cast<void*>(old_map), old_bytes, old_capacity, channels, a)) return rc;
-  if (const int rc = open_table("rdm_voxel_observations_rehash (new)", const_cast<void*>(new_map), new_bytes, new_capacity, channels, b)) return rc;
-  if (const int rc = open_observations("rdm_voxel_observations_rehash (old)", old_observations, old_observations_bytes, old_capacity, oa)) return rc;
-  if (const int rc = open_observations("rdm_voxel_observations_rehash (new)", new_observations, new_observations_bytes, new_capacity, ob)) return rc;
-  RDM_REQUIRE(new_capacity >= old_capacity && new_map != old_map && new_observations != old_observations,
-              "%s: the new map and observations must be other blocks of at least the old capacity", what);
+  Blocks a, b;
+  if (const int rc = open_rehash(what, old_map, old_bytes, old_capacity, kNoBlock, {kRequired, old_observations, old_observations_bytes}, new_map,
+                                 new_bytes, new_capacity, kNoBlock, {kRequired, new_observations, new_observations_bytes}, channels, a, b))
+    return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(observations_reset_kernel, dim3(blocks_for(new_capacity)), dim3(kBlock), 0, s, ob, static_cast<long long>(new_capacity), true);
-  hipLaunchKernelGGL(observations_rehash_kernel, dim3(blocks_for(old_capacity)), dim3(kBlock), 0, s, a, oa, static_cast<long long>(old_capacity),
-                     b, ob, static_cast<long long>(new_capacity));
+  hipLaunchKernelGGL(observations_reset_kernel, dim3(blocks_for(new_capacity)), dim3(kBlock), 0, s, b.o, static_cast<long long>(new_capacity), true);
+  hipLaunchKernelGGL(block_rehash_kernel<RecordsCopy>, dim3(blocks_for(old_capacity)), dim3(kBlock), 0, s, a.t,
+                     static_cast<long long>(old_capacity), b.t, static_cast<long long>(new_capacity), RecordsCopy{a.o.record, b.o.record});
   return launch_status(what);
 }
 
@@ -1508,16 +1592,14 @@ extern "C" int rdm_voxel_map_extract_observations(const void* map, size_t map_by
                                                   size_t ws_bytes, void* stream) {
   using namespace rdm;
   const char* what = "rdm_voxel_map_extract_observations";
-  Table t;
-  Observations o;
-  if (const int rc = open_table(what, const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
-  if (const int rc = open_observations(what, observations, observations_bytes, capacity, o)) return rc;
+  Blocks b;
+  if (const int rc = open_blocks(what, map, map_bytes, capacity, channels, kNoBlock, {kRequired, observations, observations_bytes}, b)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   ExtractWork w;
-  if (const int rc = select_sorted(what, t, capacity, voxel, min_points, max_rows, n_rows, max_rows == 0 || (scans && first && last), ws,
+  if (const int rc = select_sorted(what, b.t, capacity, voxel, min_points, max_rows, n_rows, max_rows == 0 || (scans && first && last), ws,
                                    ws_bytes, s, w))
     return rc;
-  hipLaunchKernelGGL(emit_observations_kernel, dim3(blocks_for(max_rows)), dim3(kBlock), 0, s, o, w.slots, w.n_sel,
+  hipLaunchKernelGGL(emit_observations_kernel, dim3(blocks_for(max_rows)), dim3(kBlock), 0, s, b.o, w.slots, w.n_sel,
                      static_cast<long long>(max_rows), scans, first, last, n_rows);
   return launch_status(what);
 }
@@ -1527,17 +1609,16 @@ extern "C" int rdm_voxel_map_prune(const void* old_map, size_t old_bytes, int64_
                                    int64_t min_points, int64_t min_scans, void* stream) {
   using namespace rdm;
   const char* what = "rdm_voxel_map_prune";
-  Table a, b;
-  Observations oa;
-  if (const int rc = open_table("rdm_voxel_map_prune (old)", const_cast<void*>(old_map), old_bytes, old_capacity, channels, a)) return rc;
-  if (const int rc = open_table("rdm_voxel_map_prune (new)", new_map, new_bytes, new_capacity, channels, b)) return rc;
-  if (const int rc = open_observations(what, old_observations, old_observations_bytes, old_capacity, oa)) return rc;
-  RDM_REQUIRE(new_capacity >= old_capacity && new_map != old_map, "%s: the new map must be another block of at least the old capacity", what);
+  Blocks a, b;
+  if (const int rc = open_rehash(what, old_map, old_bytes, old_capacity, kNoBlock, kNoBlock, new_map, new_bytes, new_capacity, kNoBlock, kNoBlock,
+                                 channels, a, b))
+    return rc;
+  if (const int rc = open_observations(what, old_observations, old_observations_bytes, old_capacity, a.o)) return rc;  // (no " (old)")
   RDM_REQUIRE(min_points >= 0 && min_scans >= 0, "%s: min_points and min_scans must be >= 0", what);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(reset_kernel, dim3(blocks_for(new_capacity)), dim3(kBlock), 0, s, b, static_cast<long long>(new_capacity), channels);
-  hipLaunchKernelGGL(rehash_kernel<true>, dim3(blocks_for(old_capacity)), dim3(kBlock), 0, s, a, static_cast<long long>(old_capacity), b,
-                     static_cast<long long>(new_capacity), channels, oa, least_points(min_points),
+  hipLaunchKernelGGL(reset_kernel, dim3(blocks_for(new_capacity)), dim3(kBlock), 0, s, b.t, static_cast<long long>(new_capacity), channels);
+  hipLaunchKernelGGL(rehash_kernel<true>, dim3(blocks_for(old_capacity)), dim3(kBlock), 0, s, a.t, static_cast<long long>(old_capacity), b.t,
+                     static_cast<long long>(new_capacity), channels, a.o, least_points(min_points),
                      static_cast<int>(min_scans > kMaxScanId ? kMaxScanId : min_scans));
   return launch_status(what);
 }
@@ -1550,21 +1631,17 @@ extern "C" int rdm_voxel_map_export(const void* map, size_t map_bytes, int64_t c
                                     int64_t* n_rows, void* ws, size_t ws_bytes, void* stream) {
   using namespace rdm;
   const char* what = "rdm_voxel_map_export";
-  Table t;
-  unsigned long long* m = nullptr;
-  Observations o{nullptr, nullptr};
-  if (const int rc = open_table(what, const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
-  if (moments != nullptr)
-    if (const int rc = open_moments(what, moments, moments_bytes, capacity, m)) return rc;
-  if (observations != nullptr)
-    if (const int rc = open_observations(what, observations, observations_bytes, capacity, o)) return rc;
-  RDM_REQUIRE((m != nullptr || moment_sums == nullptr) && (o.record != nullptr || seen == nullptr),
+  Blocks b;
+  if (const int rc = open_blocks(what, map, map_bytes, capacity, channels, {kOptional, moments, moments_bytes},
+                                 {kOptional, observations, observations_bytes}, b))
+    return rc;
+  RDM_REQUIRE((b.m != nullptr || moment_sums == nullptr) && (b.o.record != nullptr || seen == nullptr),
               "%s: moment_sums needs a moments block and seen an observations block", what);
   hipStream_t s = static_cast<hipStream_t>(stream);
   ExtractWork w;
-  if (const int rc = select_sorted(what, t, capacity, 1.0, min_points, max_rows, n_rows, true, ws, ws_bytes, s, w)) return rc;
-  hipLaunchKernelGGL(emit_state_kernel, dim3(blocks_for(max_rows)), dim3(kBlock), 0, s, t, moment_sums != nullptr ? m : nullptr,
-                     seen != nullptr ? o.record : nullptr, static_cast<long long>(capacity), channels, w.keys, w.slots, w.n_sel,
+  if (const int rc = select_sorted(what, b.t, capacity, 1.0, min_points, max_rows, n_rows, true, ws, ws_bytes, s, w)) return rc;
+  hipLaunchKernelGGL(emit_state_kernel, dim3(blocks_for(max_rows)), dim3(kBlock), 0, s, b.t, moment_sums != nullptr ? b.m : nullptr,
+                     seen != nullptr ? b.o.record : nullptr, static_cast<long long>(capacity), channels, w.keys, w.slots, w.n_sel,
                      static_cast<long long>(max_rows), reinterpret_cast<unsigned long long*>(keys), counts, sums, moment_sums, seen, n_rows);
   return launch_status(what);
 }
@@ -1575,28 +1652,24 @@ extern "C" int rdm_voxel_map_import(void* map, size_t map_bytes, int64_t capacit
                                     int64_t id_offset, const uint64_t* skipped_host, int64_t* n_rejected, void* stream) {
   using namespace rdm;
   const char* what = "rdm_voxel_map_import";
-  Table t;
-  unsigned long long* m = nullptr;
-  Observations o{nullptr, nullptr};
-  if (const int rc = open_table(what, map, map_bytes, capacity, channels, t)) return rc;
-  if (moments != nullptr)
-    if (const int rc = open_moments(what, moments, moments_bytes, capacity, m)) return rc;
-  if (observations != nullptr)
-    if (const int rc = open_observations(what, observations, observations_bytes, capacity, o)) return rc;
+  Blocks b;
+  if (const int rc = open_blocks(what, map, map_bytes, capacity, channels, {kOptional, moments, moments_bytes},
+                                 {kOptional, observations, observations_bytes}, b))
+    return rc;
   RDM_REQUIRE(n_records >= 0 && n_rejected != nullptr, "%s: n_records must be >= 0 and n_rejected not null", what);
   RDM_REQUIRE(id_offset >= 0 && id_offset <= kMaxScanId, "%s: id_offset must be in [0, 2^31 - 1], got %lld", what,
               static_cast<long long>(id_offset));
   RDM_REQUIRE(n_records == 0 || (keys && counts && sums), "%s: null keys, counts or sums", what);
-  RDM_REQUIRE((m != nullptr) == (moment_sums != nullptr) || (n_records == 0 && moment_sums == nullptr),
+  RDM_REQUIRE((b.m != nullptr) == (moment_sums != nullptr) || (n_records == 0 && moment_sums == nullptr),
               "%s: moment_sums is required if and only if the map has a moments block", what);
-  RDM_REQUIRE((o.record != nullptr) == (seen != nullptr) || (n_records == 0 && seen == nullptr),
+  RDM_REQUIRE((b.o.record != nullptr) == (seen != nullptr) || (n_records == 0 && seen == nullptr),
               "%s: seen is required if and only if the map has an observations block", what);
   Skipped skipped{{0ull, 0ull, 0ull, 0ull}};
   if (skipped_host != nullptr)
     for (int k = 0; k < 4; ++k) skipped.v[k] = skipped_host[k];
   hipStream_t s = static_cast<hipStream_t>(stream);
   fill_words<unsigned long long>(reinterpret_cast<unsigned long long*>(n_rejected), 1, 0ull, s);
-  hipLaunchKernelGGL(import_kernel, dim3(blocks_for(n_records)), dim3(kBlock), 0, s, t, m, o, static_cast<long long>(capacity), channels,
+  hipLaunchKernelGGL(import_kernel, dim3(blocks_for(n_records)), dim3(kBlock), 0, s, b.t, b.m, b.o, static_cast<long long>(capacity), channels,
                      reinterpret_cast<const unsigned long long*>(keys), counts, sums, moment_sums, seen, static_cast<long long>(n_records),
                      static_cast<int>(id_offset), skipped, reinterpret_cast<unsigned long long*>(n_rejected));
   return launch_status(what);
@@ -1634,47 +1707,26 @@ extern "C" int rdm_voxel_map_register_robust(const void* map, size_t map_bytes, 
                                              size_t ws_bytes, void* stream) {
   using namespace rdm;
   const char* what = "rdm_voxel_map_register";
-  Table t;
-  unsigned long long* m;
-  if (const int rc = open_table(what, const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
-  if (const int rc = open_moments(what, moments, moments_bytes, capacity, m, RDM_ERR_ARG)) return rc;
+  Blocks b;
+  if (const int rc = open_blocks(what, map, map_bytes, capacity, channels, {kRequired, moments, moments_bytes}, kNoBlock, b, RDM_ERR_ARG))
+    return rc;
   if (const int rc = check_batch(what, voxel, channels, points, ld, total, offsets, poses, n_scans, kMaxRegScans, true, min_range, max_range))
     return rc;
-  RDM_REQUIRE(sigma > 0.0 && std::isfinite(sigma), "rdm_voxel_map_register: sigma must be positive and finite (got %g)", sigma);
-  RDM_REQUIRE(neighbors == 1 || neighbors == 7, "rdm_voxel_map_register: neighbors must be 1 or 7 (got %d)", neighbors);
-  RDM_REQUIRE(min_points >= 1 && max_iteration >= 0 && rot_eps >= 0.0 && trans_eps >= 0.0,
-              "rdm_voxel_map_register: need min_points >= 1, max_iteration >= 0, rot_eps >= 0 and trans_eps >= 0");
+  if (const int rc = check_options(what, sigma, neighbors, min_points >= 1 && max_iteration >= 0 && rot_eps >= 0.0 && trans_eps >= 0.0,
+                                   "min_points >= 1, max_iteration >= 0, rot_eps >= 0 and trans_eps >= 0"))
+    return rc;
   RDM_REQUIRE(robust_scale >= 0.0 && std::isfinite(robust_scale),
               "rdm_voxel_map_register_robust: robust_scale must be finite and >= 0 (0: no weights; got %g)", robust_scale);
-  Arena ar(ws, ws_bytes);
-  RegWork w;
-  if (!carve_register(ar, n_scans, w)) {
-    set_error("rdm_voxel_map_register: workspace too small (%zu < %zu bytes)", ws_bytes, ar.off);
-    return RDM_ERR_WORKSPACE;
-  }
-  if (n_scans == 0) return RDM_OK;
-  RDM_REQUIRE(transforms && hessians && gradients && costs && stats, "rdm_voxel_map_register: null output");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const unsigned int least = least_points(min_points);
   const bool robust = robust_scale > 0.0;
-  hipLaunchKernelGGL(register_init_kernel, dim3(blocks_for(n_scans)), dim3(kBlock), 0, s, poses, static_cast<long long>(n_scans), w);
-  int running = 1;
-  for (int k = 0; k <= max_iteration && running > 0;) {
-    const int end = max_iteration - k < kRegChunk ? max_iteration + 1 : k + kRegChunk;
-    for (; k < end; ++k) {
-      hipLaunchKernelGGL(robust ? register_accumulate_kernel<true> : register_accumulate_kernel<false>,
-                         dim3(static_cast<unsigned>(n_scans * kRegGroups)), dim3(kBlock), 0, s, t, m, static_cast<long long>(capacity),
-                         channels, voxel, points, static_cast<long long>(ld), static_cast<long long>(total), offsets,
-                         min_range * min_range, max_range * max_range, sigma * sigma, least, neighbors, w, robust_scale);
-      hipLaunchKernelGGL(robust ? register_finalize_kernel<true> : register_finalize_kernel<false>,
-                         dim3(static_cast<unsigned>(n_scans)), dim3(kBlock), 0, s, w, max_iteration, rot_eps, trans_eps, transforms,
-                         hessians, gradients, costs, stats, weight_sums);
-    }
-    if (const int rc = launch_status("rdm_voxel_map_register")) return rc;
-    RDM_HIP_CHECK(hipMemcpyAsync(&running, w.running, sizeof(int), hipMemcpyDeviceToHost, s));  // one 4-byte read-back per chunk
-    RDM_HIP_CHECK(hipStreamSynchronize(s));
-  }
-  return RDM_OK;
+  const PointRow row{points, static_cast<long long>(ld), channels, min_range * min_range, max_range * max_range};
+  auto kernel = robust ? accumulate_kernel<true, PointRow> : accumulate_kernel<false, PointRow>;
+  return gauss_newton(what, poses, n_scans, max_iteration, rot_eps, trans_eps, robust, transforms, hessians, gradients, costs, weight_sums,
+                      stats, ws, ws_bytes, s, [&](const RegWork& w) {
+                        hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(n_scans * kRegGroups)), dim3(kBlock), 0, s, b.t, b.m,
+                                           static_cast<long long>(capacity), voxel, row, static_cast<long long>(total), offsets,
+                                           sigma * sigma, least_points(min_points), neighbors, w, robust_scale);
+                      });
 }
 
 // ---- voxel map alignment ------------------------------------------------------------------------------------------------------
@@ -1690,10 +1742,9 @@ extern "C" int rdm_voxel_map_align(const void* map, size_t map_bytes, int64_t ca
                                    void* stream) {
   using namespace rdm;
   const char* what = "rdm_voxel_map_align";
-  Table t;
-  unsigned long long* m;
-  if (const int rc = open_table(what, const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
-  if (const int rc = open_moments(what, moments, moments_bytes, capacity, m, RDM_ERR_ARG)) return rc;
+  Blocks b;
+  if (const int rc = open_blocks(what, map, map_bytes, capacity, channels, {kRequired, moments, moments_bytes}, kNoBlock, b, RDM_ERR_ARG))
+    return rc;
   RDM_REQUIRE(voxel > 0.0 && std::isfinite(voxel), "%s: voxel must be positive and finite", what);
   RDM_REQUIRE(source_voxel > 0.0 && std::isfinite(source_voxel), "%s: source_voxel must be positive and finite", what);
   RDM_REQUIRE(n_sets >= 0 && n_sets <= kMaxRegScans && total >= 0, "%s: bad sizes (need total >= 0 and 0 <= n_sets <= 2^20)", what);
@@ -1704,37 +1755,19 @@ extern "C" int rdm_voxel_map_align(const void* map, size_t map_bytes, int64_t ca
     RDM_REQUIRE(moment_sums != nullptr, "%s: null moment_sums", what);
   }
   RDM_REQUIRE(n_sets == 0 || (offsets && poses), "%s: null offsets or poses", what);
-  RDM_REQUIRE(sigma > 0.0 && std::isfinite(sigma), "%s: sigma must be positive and finite (got %g)", what, sigma);
-  RDM_REQUIRE(neighbors == 1 || neighbors == 7, "%s: neighbors must be 1 or 7 (got %d)", what, neighbors);
-  RDM_REQUIRE(min_points >= 1 && source_min_points >= 1 && max_iteration >= 0 && rot_eps >= 0.0 && trans_eps >= 0.0,
-              "%s: need min_points >= 1, source_min_points >= 1, max_iteration >= 0, rot_eps >= 0 and trans_eps >= 0", what);
-  Arena ar(ws, ws_bytes);
-  RegWork w;
-  if (!carve_register(ar, n_sets, w)) {
-    set_error("%s: workspace too small (%zu < %zu bytes)", what, ws_bytes, ar.off);
-    return RDM_ERR_WORKSPACE;
-  }
-  if (n_sets == 0) return RDM_OK;
-  RDM_REQUIRE(transforms && hessians && gradients && costs && stats, "%s: null output", what);
+  if (const int rc = check_options(what, sigma, neighbors,
+                                   min_points >= 1 && source_min_points >= 1 && max_iteration >= 0 && rot_eps >= 0.0 && trans_eps >= 0.0,
+                                   "min_points >= 1, source_min_points >= 1, max_iteration >= 0, rot_eps >= 0 and trans_eps >= 0"))
+    return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(register_init_kernel, dim3(blocks_for(n_sets)), dim3(kBlock), 0, s, poses, static_cast<long long>(n_sets), w);
-  int running = 1;
-  for (int k = 0; k <= max_iteration && running > 0;) {
-    const int end = max_iteration - k < kRegChunk ? max_iteration + 1 : k + kRegChunk;
-    for (; k < end; ++k) {
-      hipLaunchKernelGGL(align_accumulate_kernel, dim3(static_cast<unsigned>(n_sets * kRegGroups)), dim3(kBlock), 0, s, t, m,
-                         static_cast<long long>(capacity), voxel, counts, reinterpret_cast<const long long*>(sums),
-                         static_cast<long long>(sums_ld), reinterpret_cast<const long long*>(moment_sums), source_voxel,
-                         static_cast<long long>(total), offsets, sigma * sigma, least_points(min_points),
-                         least_points(source_min_points), neighbors, w);
-      hipLaunchKernelGGL(register_finalize_kernel<false>, dim3(static_cast<unsigned>(n_sets)), dim3(kBlock), 0, s, w, max_iteration,
-                         rot_eps, trans_eps, transforms, hessians, gradients, costs, stats, static_cast<double*>(nullptr));
-    }
-    if (const int rc = launch_status(what)) return rc;
-    RDM_HIP_CHECK(hipMemcpyAsync(&running, w.running, sizeof(int), hipMemcpyDeviceToHost, s));  // one 4-byte read-back per chunk
-    RDM_HIP_CHECK(hipStreamSynchronize(s));
-  }
-  return RDM_OK;
+  const RecordRow row{counts, reinterpret_cast<const long long*>(sums), static_cast<long long>(sums_ld),
+                      reinterpret_cast<const long long*>(moment_sums), source_voxel, least_points(source_min_points)};
+  return gauss_newton(what, poses, n_sets, max_iteration, rot_eps, trans_eps, false, transforms, hessians, gradients, costs, nullptr, stats,
+                      ws, ws_bytes, s, [&](const RegWork& w) {
+                        hipLaunchKernelGGL((accumulate_kernel<false, RecordRow>), dim3(static_cast<unsigned>(n_sets * kRegGroups)),
+                                           dim3(kBlock), 0, s, b.t, b.m, static_cast<long long>(capacity), voxel, row,
+                                           static_cast<long long>(total), offsets, sigma * sigma, least_points(min_points), neighbors, w, 0.0);
+                      });
 }
 
 // ---- voxel map queries --------------------------------------------------------------------------------------------------------
@@ -1747,19 +1780,13 @@ extern "C" int rdm_voxel_map_query(const void* map, size_t map_bytes, int64_t ca
                                    double* d2, double* d2_sum, uint8_t* pairs, int64_t* tallies, void* stream) {
   using namespace rdm;
   const char* what = "rdm_voxel_map_query";
-  Table t;
-  unsigned long long* m = nullptr;
-  Observations o{nullptr, nullptr};
-  if (const int rc = open_table(what, const_cast<void*>(map), map_bytes, capacity, channels, t)) return rc;
-  if (moments != nullptr)
-    if (const int rc = open_moments(what, moments, moments_bytes, capacity, m, RDM_ERR_ARG)) return rc;
-  if (observations != nullptr)
-    if (const int rc = open_observations(what, observations, observations_bytes, capacity, o)) return rc;
+  Blocks b;
+  if (const int rc = open_blocks(what, map, map_bytes, capacity, channels, {kOptional, moments, moments_bytes},
+                                 {kOptional, observations, observations_bytes}, b, RDM_ERR_ARG))
+    return rc;
   if (const int rc = check_batch(what, voxel, channels, points, ld, total, offsets, poses, n_scans, INT64_MAX, false, min_range, max_range))
     return rc;
-  RDM_REQUIRE(sigma > 0.0 && std::isfinite(sigma), "%s: sigma must be positive and finite (got %g)", what, sigma);
-  RDM_REQUIRE(neighbors == 1 || neighbors == 7, "%s: neighbors must be 1 or 7 (got %d)", what, neighbors);
-  RDM_REQUIRE(min_points >= 1 && min_scans >= 0, "%s: need min_points >= 1 and min_scans >= 0", what);
+  if (const int rc = check_options(what, sigma, neighbors, min_points >= 1 && min_scans >= 0, "min_points >= 1 and min_scans >= 0")) return rc;
   RDM_REQUIRE(max_d2 >= 0.0, "%s: max_d2 must be >= 0 or +inf (got %g)", what, max_d2);  // (NaN fails)
   RDM_REQUIRE(observations != nullptr || (min_scans <= 1 && seen == nullptr),
               "%s: min_scans > 1 and the seen output need an observations block", what);
@@ -1769,14 +1796,14 @@ extern "C" int rdm_voxel_map_query(const void* map, size_t map_bytes, int64_t ca
   if (total > 0) {
     // every voxel of the table was seen in at least one scan, so the records are read for min_scans > 1 or the seen output only; the
     // distances are formed where a label, the choice among seven voxels or an output needs them
-    const int* records = min_scans > 1 || seen != nullptr ? o.record : nullptr;
+    const int* records = min_scans > 1 || seen != nullptr ? b.o.record : nullptr;
     const bool dist = neighbors == 7 || max_d2 < INFINITY || d2 != nullptr || d2_sum != nullptr;
     const int64_t n_chunks = (total + kBlock - 1) / kBlock;
     const int64_t blocks = n_chunks < kQueryBlocks ? n_chunks : kQueryBlocks;
     const int64_t chunks = (n_chunks + blocks - 1) / blocks;
     const QueryOut out{labels, best, counts, seen, d2, d2_sum, pairs, reinterpret_cast<unsigned long long*>(tallies)};
-    auto kernel = !dist ? query_kernel<false, false> : (m != nullptr ? query_kernel<true, true> : query_kernel<true, false>);
-    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, t, m, records, static_cast<long long>(capacity),
+    auto kernel = !dist ? query_kernel<false, false> : (b.m != nullptr ? query_kernel<true, true> : query_kernel<true, false>);
+    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, b.t, b.m, records, static_cast<long long>(capacity),
                        channels, voxel, points, static_cast<long long>(ld), static_cast<long long>(total), offsets, poses,
                        static_cast<long long>(n_scans), min_range * min_range, max_range * max_range, sigma * sigma,
                        least_points(min_points), neighbors, static_cast<int>(min_scans > kMaxScanId ? kMaxScanId : min_scans), max_d2,

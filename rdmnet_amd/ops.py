@@ -820,32 +820,39 @@ class VoxelMap:
         if self.device.index is None:
             self.device = torch.device('cuda', torch.cuda.current_device())
         self.moments, self.observations = bool(moments), bool(observations)
-        self.capacity, self._buf = capacity, self._alloc(capacity)
-        self._mom = self._alloc_moments(capacity) if self.moments else None
-        self._obs = self._alloc_observations(capacity) if self.observations else None
+        self.capacity, self._mom, self._obs = capacity, None, None
+        for attr, kind in self._owned():
+            setattr(self, attr, self._alloc(kind, capacity))
         self.reset()
 
-    def _alloc(self, capacity):
-        return torch.empty((_lib.lib().rdm_voxel_map_bytes(capacity, self.channels),), dtype=torch.uint8, device=self.device)
+    def _owned(self):
+        """The blocks this map keeps, in the order of their launches on the stream: (attribute, kind), kind being what stands behind
+        `rdm_voxel_` in the names of the block's bytes, reset and rehash entry points."""
+        return [('_buf', 'map')] + [('_mom', 'moments')] * self.moments + [('_obs', 'observations')] * self.observations
 
-    def _alloc_moments(self, capacity):
-        return torch.empty((_lib.lib().rdm_voxel_moments_bytes(capacity),), dtype=torch.uint8, device=self.device)
+    def _shape(self, kind, capacity):
+        """What the bytes and reset entry points of a block take as its shape."""
+        return (capacity, self.channels) if kind == 'map' else (capacity,)
 
-    def _alloc_observations(self, capacity):
-        return torch.empty((_lib.lib().rdm_voxel_observations_bytes(capacity),), dtype=torch.uint8, device=self.device)
+    def _alloc(self, kind, capacity):
+        nbytes = getattr(_lib.lib(), f'rdm_voxel_{kind}_bytes')(*self._shape(kind, capacity))
+        return torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
 
     def _head(self):
         return self._buf.data_ptr(), self._buf.numel(), self.capacity, self.channels
 
+    def _rehash_beside(self, kind, old, was, new, now):
+        """rdm_voxel_{kind}_rehash: the moments or observations `was` beside the map old = (pointer, bytes, capacity) into `now` beside
+        the map `new`, which holds the keys already."""
+        name = f'rdm_voxel_{kind}_rehash'
+        _lib.check(getattr(_lib.lib(), name)(*old, was.data_ptr(), was.numel(), *new, now.data_ptr(), now.numel(), self.channels,
+                                             _lib.stream_ptr()), name)
+
     def reset(self):
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().rdm_voxel_map_reset(*self._head(), _lib.stream_ptr()), 'rdm_voxel_map_reset')
-            if self.moments:
-                _lib.check(_lib.lib().rdm_voxel_moments_reset(self._mom.data_ptr(), self._mom.numel(), self.capacity, _lib.stream_ptr()),
-                           'rdm_voxel_moments_reset')
-            if self.observations:
-                _lib.check(_lib.lib().rdm_voxel_observations_reset(self._obs.data_ptr(), self._obs.numel(), self.capacity, _lib.stream_ptr()),
-                           'rdm_voxel_observations_reset')
+            for attr, kind in self._owned():
+                t, name = getattr(self, attr), f'rdm_voxel_{kind}_reset'
+                _lib.check(getattr(_lib.lib(), name)(t.data_ptr(), t.numel(), *self._shape(kind, self.capacity), _lib.stream_ptr()), name)
         self.num_scans = 0  # with observations: the id of the next scan
         self._bound = 0  # occupied <= _bound: spares the read-back of `occupied` while the table is certainly large enough
 
@@ -871,26 +878,14 @@ class VoxelMap:
                     capacity *= 2
                 if _lib.lib().rdm_voxel_map_bytes(capacity, self.channels) == 0:
                     raise RuntimeError(f'VoxelMap: {need // 2} voxels need more than 2^30 slots')
-                new = self._alloc(capacity)
+                grown = {attr: self._alloc(kind, capacity) for attr, kind in self._owned()}
+                old, new = (self._buf.data_ptr(), self._buf.numel(), self.capacity), (grown['_buf'].data_ptr(), grown['_buf'].numel(), capacity)
                 with torch.cuda.device(self.device):
-                    _lib.check(_lib.lib().rdm_voxel_map_rehash(self._buf.data_ptr(), self._buf.numel(), self.capacity, new.data_ptr(),
-                                                               new.numel(), capacity, self.channels, _lib.stream_ptr()),
-                               'rdm_voxel_map_rehash')
-                    if self.moments:
-                        mom = self._alloc_moments(capacity)
-                        _lib.check(_lib.lib().rdm_voxel_moments_rehash(self._buf.data_ptr(), self._buf.numel(), self.capacity,
-                                                                       self._mom.data_ptr(), self._mom.numel(), new.data_ptr(), new.numel(),
-                                                                       capacity, mom.data_ptr(), mom.numel(), self.channels,
-                                                                       _lib.stream_ptr()), 'rdm_voxel_moments_rehash')
-                        self._mom = mom
-                    if self.observations:
-                        obs = self._alloc_observations(capacity)
-                        _lib.check(_lib.lib().rdm_voxel_observations_rehash(self._buf.data_ptr(), self._buf.numel(), self.capacity,
-                                                                            self._obs.data_ptr(), self._obs.numel(), new.data_ptr(),
-                                                                            new.numel(), capacity, obs.data_ptr(), obs.numel(),
-                                                                            self.channels, _lib.stream_ptr()), 'rdm_voxel_observations_rehash')
-                        self._obs = obs
-                self.capacity, self._buf = capacity, new  # (the old block is freed in stream order by the caching allocator)
+                    _lib.check(_lib.lib().rdm_voxel_map_rehash(*old, *new, self.channels, _lib.stream_ptr()), 'rdm_voxel_map_rehash')
+                    for attr, kind in self._owned()[1:]:
+                        self._rehash_beside(kind, old, getattr(self, attr), new, grown[attr])
+                self.capacity = capacity
+                self.__dict__.update(grown)  # (the old blocks are freed in stream order by the caching allocator)
         self._bound += n_points
 
     def _packed(self, what, clouds, poses, min_range, max_range):
@@ -922,6 +917,16 @@ class VoxelMap:
             elif named:
                 points = torch.cat([t[:, :C] for t, _ in named])
         n = offsets.numel() - 1
+        X = self._poses_arg(poses, n, 'scan')
+        lo, hi = float(min_range), float(max_range)
+        if not 0.0 <= lo <= hi:
+            raise ValueError(f'need 0 <= min_range <= max_range, got {min_range} and {max_range}')
+        return points, offsets, n, X, lo, hi
+
+    @staticmethod
+    def _poses_arg(poses, n, per):
+        """poses, anything numpy or torch holds -> float64 numpy [n, 4, 4], finite (per: what a pose belongs to, for the message)."""
+        import numpy as np
         if isinstance(poses, torch.Tensor):
             poses = poses.detach().cpu().numpy()
         X = np.ascontiguousarray(np.asarray(poses, dtype=np.float64))
@@ -930,13 +935,37 @@ class VoxelMap:
         if X.size == 0 and n == 0:
             X = X.reshape(0, 4, 4)
         if X.shape != (n, 4, 4):
-            raise ValueError(f'poses must be [{n}, 4, 4] (one 4x4 per scan), got {X.shape}')
+            raise ValueError(f'poses must be [{n}, 4, 4] (one 4x4 per {per}), got {X.shape}')
         if not np.isfinite(X).all():
             raise ValueError('poses must be finite')
-        lo, hi = float(min_range), float(max_range)
-        if not 0.0 <= lo <= hi:
-            raise ValueError(f'need 0 <= min_range <= max_range, got {min_range} and {max_range}')
-        return points, offsets, n, X, lo, hi
+        return X
+
+    @staticmethod
+    def _options(sigma, neighbors, rest_ok, rest):
+        """The checks of sigma and neighbors that register, align and query share, then the caller's own bounds (rest: their text)."""
+        if not (sigma > 0 and sigma < float('inf')):
+            raise ValueError(f'sigma must be positive and finite, got {sigma}')
+        if neighbors not in (1, 7):
+            raise ValueError(f'neighbors must be 1 or 7, got {neighbors}')
+        if not rest_ok:
+            raise ValueError('need ' + rest)
+
+    def _gauss_newton(self, n, weighted, workspace_bytes, call):
+        """The outputs of register and align for n scans or sources: allocates them and, for n > 0, the workspace of the size that the
+        entry point `workspace_bytes` names, lets call((transforms, hessians, gradients, costs pointers), weight_sum pointer or None,
+        (stats, workspace, its size, stream)) make the C call, and wraps them -> MapRegistrationResult."""
+        L, dev = _lib.lib(), self.device
+        real = torch.zeros((n, 59), dtype=torch.float64, device=dev)  # transforms, hessians, gradients, costs
+        stats = torch.zeros((n, 4), dtype=torch.int64, device=dev)
+        T, H, g, cost = (real.view(-1)[a * n:b * n].view(n, b - a) for a, b in ((0, 16), (16, 52), (52, 58), (58, 59)))
+        weight_sum = torch.zeros((n,), dtype=torch.float64, device=dev) if weighted else None
+        if n > 0:
+            with torch.cuda.device(dev):
+                ws = scratch(dev, getattr(L, workspace_bytes)(n))
+                call((T.data_ptr(), H.data_ptr(), g.data_ptr(), cost.data_ptr()), _lib.ptr(weight_sum),
+                     (stats.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()))
+        return MapRegistrationResult(T.view(n, 4, 4), H.view(n, 6, 6), g, cost.view(n), stats[:, 0], stats[:, 1], stats[:, 2], stats[:, 3],
+                                     weight_sum)
 
     def _on_device(self, points, offsets, X):
         """_packed's points, offsets and poses as the C calls take them -> (points, ld, total, offsets and poses on the device).  A batch
@@ -1033,11 +1062,8 @@ class VoxelMap:
         with torch.cuda.device(self.device):
             _lib.check(L.rdm_voxel_map_prune(*old, self._obs.data_ptr(), self._obs.numel(), *new, self.channels, min_points, min_scans,
                                              _lib.stream_ptr()), 'rdm_voxel_map_prune')
-            if self.moments:
-                _lib.check(L.rdm_voxel_moments_rehash(*old, self._mom.data_ptr(), self._mom.numel(), *new, out._mom.data_ptr(),
-                                                      out._mom.numel(), self.channels, _lib.stream_ptr()), 'rdm_voxel_moments_rehash')
-            _lib.check(L.rdm_voxel_observations_rehash(*old, self._obs.data_ptr(), self._obs.numel(), *new, out._obs.data_ptr(),
-                                                       out._obs.numel(), self.channels, _lib.stream_ptr()), 'rdm_voxel_observations_rehash')
+            for attr, kind in self._owned()[1:]:
+                self._rehash_beside(kind, old, getattr(self, attr), new, getattr(out, attr))
         out.num_scans, out._bound = self.num_scans, self._bound
         return out
 
@@ -1098,32 +1124,20 @@ class VoxelMap:
         points, offsets, n, X, lo, hi = self._packed('register', clouds, poses, min_range, max_range)
         sigma, rot_eps, trans_eps = float(sigma), float(rot_eps), float(trans_eps)
         min_points, neighbors, max_iteration = int(min_points), int(neighbors), int(max_iteration)
-        if not (sigma > 0 and sigma < float('inf')):
-            raise ValueError(f'sigma must be positive and finite, got {sigma}')
-        if neighbors not in (1, 7):
-            raise ValueError(f'neighbors must be 1 or 7, got {neighbors}')
-        if min_points < 1 or max_iteration < 0 or not rot_eps >= 0 or not trans_eps >= 0:
-            raise ValueError('need min_points >= 1, max_iteration >= 0, rot_eps >= 0 and trans_eps >= 0')
-        L, dev = _lib.lib(), self.device
-        real = torch.zeros((n, 59), dtype=torch.float64, device=dev)  # transforms, hessians, gradients, costs
-        stats = torch.zeros((n, 4), dtype=torch.int64, device=dev)
-        T, H, g, cost = (real.view(-1)[a * n:b * n].view(n, b - a) for a, b in ((0, 16), (16, 52), (52, 58), (58, 59)))
-        weight_sum = None if robust_scale is None else torch.zeros((n,), dtype=torch.float64, device=dev)
-        if n > 0:
-            points, ld, total, offsets, Xd = self._on_device(points, offsets, X)
-            with torch.cuda.device(dev):
-                ws = scratch(dev, L.rdm_voxel_map_register_workspace_bytes(n))
-                head = (*self._head(), self._mom.data_ptr(), self._mom.numel(), self.voxel, points.data_ptr(), ld, total, offsets.data_ptr(),
-                        Xd.data_ptr(), n, lo, hi, sigma, min_points, neighbors, max_iteration, rot_eps, trans_eps)
-                tail = (stats.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr())
-                if robust_scale is None:
-                    _lib.check(L.rdm_voxel_map_register(*head, T.data_ptr(), H.data_ptr(), g.data_ptr(), cost.data_ptr(), *tail),
-                               'rdm_voxel_map_register')
-                else:
-                    _lib.check(L.rdm_voxel_map_register_robust(*head, robust_scale, T.data_ptr(), H.data_ptr(), g.data_ptr(), cost.data_ptr(),
-                                                               weight_sum.data_ptr(), *tail), 'rdm_voxel_map_register_robust')
-        return MapRegistrationResult(T.view(n, 4, 4), H.view(n, 6, 6), g, cost.view(n), stats[:, 0], stats[:, 1], stats[:, 2], stats[:, 3],
-                                     weight_sum)
+        self._options(sigma, neighbors, min_points >= 1 and max_iteration >= 0 and rot_eps >= 0 and trans_eps >= 0,
+                      'min_points >= 1, max_iteration >= 0, rot_eps >= 0 and trans_eps >= 0')
+
+        def call(outs, weight_sum, tail):
+            pts, ld, total, off, Xd = self._on_device(points, offsets, X)
+            head = (*self._head(), self._mom.data_ptr(), self._mom.numel(), self.voxel, pts.data_ptr(), ld, total, off.data_ptr(),
+                    Xd.data_ptr(), n, lo, hi, sigma, min_points, neighbors, max_iteration, rot_eps, trans_eps)
+            if robust_scale is None:
+                _lib.check(_lib.lib().rdm_voxel_map_register(*head, *outs, *tail), 'rdm_voxel_map_register')
+            else:
+                _lib.check(_lib.lib().rdm_voxel_map_register_robust(*head, robust_scale, *outs, weight_sum, *tail),
+                           'rdm_voxel_map_register_robust')
+
+        return self._gauss_newton(n, robust_scale is not None, 'rdm_voxel_map_register_workspace_bytes', call)
 
     def align(self, sources, poses, *, sigma=0.02, min_points=4, source_min_points=4, neighbors=7, max_iteration=30, rot_eps=1e-5,
               trans_eps=1e-4):
@@ -1170,47 +1184,28 @@ class VoxelMap:
                 arrays.append(t.to(self.device)[:, :3] if k == 'sums' else t.to(self.device))
             packed.append(arrays)
         n = len(packed)
-        if isinstance(poses, torch.Tensor):
-            poses = poses.detach().cpu().numpy()
-        X = np.ascontiguousarray(np.asarray(poses, dtype=np.float64))
-        if X.shape == (4, 4) and n == 1:
-            X = X[None]
-        if X.size == 0 and n == 0:
-            X = X.reshape(0, 4, 4)
-        if X.shape != (n, 4, 4):
-            raise ValueError(f'poses must be [{n}, 4, 4] (one 4x4 per source), got {X.shape}')
-        if not np.isfinite(X).all():
-            raise ValueError('poses must be finite')
+        X = self._poses_arg(poses, n, 'source')
         sigma, rot_eps, trans_eps = float(sigma), float(rot_eps), float(trans_eps)
         min_points, source_min_points, neighbors, max_iteration = int(min_points), int(source_min_points), int(neighbors), int(max_iteration)
-        if not (sigma > 0 and sigma < float('inf')):
-            raise ValueError(f'sigma must be positive and finite, got {sigma}')
-        if neighbors not in (1, 7):
-            raise ValueError(f'neighbors must be 1 or 7, got {neighbors}')
-        if min_points < 1 or source_min_points < 1 or max_iteration < 0 or not rot_eps >= 0 or not trans_eps >= 0:
-            raise ValueError('need min_points >= 1, source_min_points >= 1, max_iteration >= 0, rot_eps >= 0 and trans_eps >= 0')
-        L, dev = _lib.lib(), self.device
-        real = torch.zeros((n, 59), dtype=torch.float64, device=dev)  # transforms, hessians, gradients, costs
-        stats = torch.zeros((n, 4), dtype=torch.int64, device=dev)
-        T, H, g, cost = (real.view(-1)[a * n:b * n].view(n, b - a) for a, b in ((0, 16), (16, 52), (52, 58), (58, 59)))
-        if n > 0:
+        self._options(sigma, neighbors, min_points >= 1 and source_min_points >= 1 and max_iteration >= 0 and rot_eps >= 0 and trans_eps >= 0,
+                      'min_points >= 1, source_min_points >= 1, max_iteration >= 0, rot_eps >= 0 and trans_eps >= 0')
+
+        def call(outs, _, tail):
+            dev = self.device
             offsets = torch.tensor([0] + [int(a[0].shape[0]) for a in packed], dtype=torch.int64).cumsum(0)
             total = int(offsets[-1])
-            with torch.cuda.device(dev):
-                if total > 0:
-                    counts, sums, moments = (torch.cat([a[k] for a in packed]).contiguous() for k in range(3))
-                else:  # one placeholder record, never read
-                    counts = torch.zeros((1,), dtype=torch.uint32, device=dev)
-                    sums, moments = (torch.zeros((1, w), dtype=torch.int64, device=dev) for w in (3, _lib.VOXEL_MOMENTS_PLANES))
-                offsets, Xd = offsets.to(dev), torch.from_numpy(X).to(dev)
-                ws = scratch(dev, L.rdm_voxel_map_align_workspace_bytes(n))
-                _lib.check(L.rdm_voxel_map_align(*self._head(), self._mom.data_ptr(), self._mom.numel(), self.voxel, counts.data_ptr(),
-                                                 sums.data_ptr(), 3, moments.data_ptr(), source_voxel, total,
-                                                 offsets.data_ptr(), Xd.data_ptr(), n, sigma, min_points,
-                                                 source_min_points, neighbors, max_iteration, rot_eps, trans_eps, T.data_ptr(),
-                                                 H.data_ptr(), g.data_ptr(), cost.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                 _lib.stream_ptr()), 'rdm_voxel_map_align')
-        return MapRegistrationResult(T.view(n, 4, 4), H.view(n, 6, 6), g, cost.view(n), stats[:, 0], stats[:, 1], stats[:, 2], stats[:, 3])
+            if total > 0:
+                counts, sums, moments = (torch.cat([a[k] for a in packed]).contiguous() for k in range(3))
+            else:  # one placeholder record, never read
+                counts = torch.zeros((1,), dtype=torch.uint32, device=dev)
+                sums, moments = (torch.zeros((1, w), dtype=torch.int64, device=dev) for w in (3, _lib.VOXEL_MOMENTS_PLANES))
+            offsets, Xd = offsets.to(dev), torch.from_numpy(X).to(dev)
+            _lib.check(_lib.lib().rdm_voxel_map_align(*self._head(), self._mom.data_ptr(), self._mom.numel(), self.voxel, counts.data_ptr(),
+                                                      sums.data_ptr(), 3, moments.data_ptr(), source_voxel, total, offsets.data_ptr(),
+                                                      Xd.data_ptr(), n, sigma, min_points, source_min_points, neighbors, max_iteration,
+                                                      rot_eps, trans_eps, *outs, *tail), 'rdm_voxel_map_align')
+
+        return self._gauss_newton(n, False, 'rdm_voxel_map_align_workspace_bytes', call)
 
     def query(self, clouds, poses, *, sigma=0.02, min_points=1, neighbors=1, min_scans=1, max_d2=float('inf'), min_range=0.0,
               max_range=float('inf'), outputs=None):
@@ -1224,12 +1219,8 @@ class VoxelMap:
         points, offsets, n, X, lo, hi = self._packed('query', clouds, poses, min_range, max_range)
         sigma, max_d2 = float(sigma), float(max_d2)
         min_points, neighbors, min_scans = int(min_points), int(neighbors), int(min_scans)
-        if not (sigma > 0 and sigma < float('inf')):
-            raise ValueError(f'sigma must be positive and finite, got {sigma}')
-        if neighbors not in (1, 7):
-            raise ValueError(f'neighbors must be 1 or 7, got {neighbors}')
-        if min_points < 1 or min_scans < 0:
-            raise ValueError(f'need min_points >= 1 and min_scans >= 0, got {min_points} and {min_scans}')
+        self._options(sigma, neighbors, min_points >= 1 and min_scans >= 0,
+                      f'min_points >= 1 and min_scans >= 0, got {min_points} and {min_scans}')
         if not max_d2 >= 0:
             raise ValueError(f'max_d2 must be >= 0 (inf: no test), got {max_d2}')
         seen = ('scans', 'first', 'last')

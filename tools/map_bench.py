@@ -146,7 +146,10 @@ def digest():
     """One `sha1  what` line over the raw bytes of everything the voxel map returns for the three bundled scans (tests/golden/scans.npz
     with the intensity column of the tests) under three seeded poses: stats, extract and extract_moments of maps that grow from 1024
     slots at voxel 0.3 and 0.05, with and without moments, and every field of register at neighbors 1 and 7, as one batch of three
-    and as three calls of one.  Two libraries (RDM_LIB_PATH) compute the same bits iff they print the same lines."""
+    and as three calls of one; then the same registrations with robust_scale = 9, align of a map of voxel 0.5 onto the map of voxel
+    0.3, query with every output on a map with moments and observations grown scan by scan from 64 slots, that map's
+    extract_observations, the state of its pruned(min_scans=2), its own state, and the state of two halves merged.  Two libraries
+    (RDM_LIB_PATH) compute the same bits iff they print the same lines."""
     import hashlib
     import torch
     from rdmnet_amd import ops
@@ -178,6 +181,37 @@ def digest():
         for what, res in zip(('batch of 3', 'scan 0', 'scan 1', 'scan 2'), runs):
             line(f'register neighbors {neighbors} {what}', [res.transformations, res.information, res.gradient, res.cost, res.iterations,
                                                             res.num_correspondences, res.num_points, res.status])
+
+    def fields(res):
+        return [res.transformations, res.information, res.gradient, res.cost, res.iterations, res.num_correspondences, res.num_points,
+                res.status] + ([] if res.weight_sum is None else [res.weight_sum])
+
+    def state_line(what, st):
+        host = torch.tensor(list(st['counters'].values()) + [st['num_scans']], dtype=torch.int64)
+        line(what, [st[k] for k in ('keys', 'counts', 'sums', 'moments', 'observations') if k in st] + [host])
+
+    for neighbors in (1, 7):
+        kw = dict(neighbors=neighbors, max_iteration=5, robust_scale=9)
+        runs = [vmap.register(clouds, off, **kw)] + [vmap.register(clouds[k:k + 1], off[k:k + 1], **kw) for k in range(3)]
+        for what, res in zip(('batch of 3', 'scan 0', 'scan 1', 'scan 2'), runs):
+            line(f'register robust 9 neighbors {neighbors} {what}', fields(res))
+    source = ops.VoxelMap(0.5, channels=4, capacity=1024, moments=True).integrate(clouds, poses)
+    start = off_poses(np.eye(4)[None], np.random.default_rng(1))
+    for neighbors in (1, 7):  # (the bundled scans are sparse: two points make a voxel here, or hardly a pair is left)
+        kw = dict(neighbors=neighbors, max_iteration=5, min_points=2, source_min_points=2)
+        line(f'align voxel 0.5 onto 0.3 neighbors {neighbors}', fields(vmap.align([source], start, **kw)))
+    full = ops.VoxelMap(0.3, channels=4, capacity=64, moments=True, observations=True)
+    for k in range(3):
+        full.integrate(clouds[k:k + 1], poses[k:k + 1])
+    for neighbors in (1, 7):
+        res = full.query(clouds, off, neighbors=neighbors, min_scans=2, max_d2=25.0)
+        line(f'query every output neighbors {neighbors}', [getattr(res, k) for k in res.FIELDS])
+    line('extract_observations', full.extract_observations())
+    state_line('pruned(min_scans=2) state', full.pruned(min_scans=2).state())
+    state_line('state of a map grown from 64 slots', full.state())
+    halves = [ops.VoxelMap(0.3, channels=4, capacity=1024, moments=True, observations=True).integrate(clouds[a:b], poses[a:b])
+              for a, b in ((0, 2), (2, 3))]
+    state_line('merge of two halves state', halves[0].merge(halves[1]).state())
     return 0
 
 
