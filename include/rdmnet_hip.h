@@ -356,6 +356,46 @@ int rdm_pose_graph_marginals(int64_t n_graphs, const int64_t* graph_node_offsets
  * for a separator above the limit.                                                                                              */
 int rdm_pose_graph_marginals_host(int64_t n_nodes, int64_t n_edges, const int64_t* edges_host, const double* diag, const double* off,
                                   double* out);
+/* Cross covariances and the consistency of candidate (loop) edges with a graph (g2o's computeMarginals with
+ * block pairs, GTSAM's jointMarginalCovariance): the marginals call above, with the same arguments and the same kernels in the same
+ * order -- covariances_out is bit for bit what rdm_pose_graph_marginals writes --, and then, for a list of P pairs in the edges' layout
+ * (pairs_host int64 [P, 2] rows (s, t) numbered inside their graph, graph_pair_offsets_host int64 [G + 1]; pair_transforms device
+ * [P, 16] with an edge's convention X_s = X_t T; pair_informations device [P, 36] or null for the whole call), per pair:
+ *   cross_out [P, 36]         Sigma_st = (H^-1)_st, rows belonging to s; zero when s or t is node 0
+ *   residual_cov_out [P, 36]  M = A Sigma_ss A^T + A Sigma_st B^T + B Sigma_ts A^T + B Sigma_tt B^T with the Jacobians A, B of the
+ *                             residual r of (X_s, X_t, T) as an edge's are formed: the covariance of that residual under the graph (at
+ *                             T = X_t^-1 X_s: of the relative pose); exactly symmetric
+ *   d2_out [P]                r^T (M + L^-1)^-1 r (without informations r^T M^-1 r) by a 6 x 6 Cholesky
+ *   pair_status_out [P]       uint8: 0, or 1: L or M + L^-1 is not positive definite -- d2 is NaN, the blocks are written
+ * Every output pointer may be null.  The six columns of H^-1 of a pair's column node t are solved for from the factors the marginals
+ * leave (forwards along t's run, through Sigma_SS, backwards along s's run), a thread per scalar column, kColumnsInFlight = 128 column
+ * nodes at a time on the stream; nothing of size N x N or N x P is formed, no float atomics, and every sum in an order the graph and
+ * the pair decide: a pair's rows are the same bits alone, with any other pairs, anywhere in a batch and from run to run.  report_host
+ * [G, 2] as above; a graph with status 4 has NaN in its pairs' rows (pair status 0).  RDM_ERR_ARG with every output untouched, the
+ * message naming the first offender: whatever the marginals call refuses, a pair with s = t or outside its graph, a non-finite pair
+ * transform or information, an asymmetric information (the edges' rule), a pair residual beyond the angle limit.  The workspace size
+ * is exact and reads edges and pairs: the marginals' plus O(P) and 128 x (the longest forward pass + the largest separator) blocks;
+ * 0 with rdm_last_error set for what the host can refuse.                                                                          */
+size_t rdm_pose_graph_consistency_workspace_bytes(int64_t n_graphs, const int64_t* graph_node_offsets_host,
+                                                  const int64_t* graph_edge_offsets_host, const int64_t* edges_host,
+                                                  const int64_t* graph_pair_offsets_host, const int64_t* pairs_host);
+int rdm_pose_graph_consistency(int64_t n_graphs, const int64_t* graph_node_offsets_host, const int64_t* graph_edge_offsets_host,
+                               const double* nodes, const int64_t* edges_host, const double* transforms, const double* informations,
+                               const double* weights, const int64_t* graph_pair_offsets_host, const int64_t* pairs_host,
+                               const double* pair_transforms, const double* pair_informations, double* covariances_out,
+                               double* cross_out, double* residual_cov_out, double* d2_out, uint8_t* pair_status_out,
+                               double* report_host, void* ws, size_t ws_bytes, void* stream);
+/* The pairs' work items as the kernels run them and in their order, on the host, on a system given as rdm_pose_graph_marginals_host
+ * takes it: out [n_pairs, 36] is Sigma_st of pairs_host's rows (s, t).  RDM_ERR_ARG as there, and for a pair with s = t or outside
+ * the graph.                                                                                                                      */
+int rdm_pose_graph_pair_covariances_host(int64_t n_nodes, int64_t n_edges, const int64_t* edges_host, const double* diag,
+                                         const double* off, int64_t n_pairs, const int64_t* pairs_host, double* out);
+/* One pair as the pair kernel's thread computes it (host pointers): poses and transform [16], information [36] or null, Sigma_ss and
+ * Sigma_tt (their lower triangles are read) and Sigma_st [36] -> out [44]: r [6], M [36], d2, status (0 or 1).  RDM_ERR_ARG beyond
+ * the angle limit.                                                                                                                */
+int rdm_pose_graph_pair_terms_host(const double* source_pose, const double* target_pose, const double* transform,
+                                   const double* information, const double* cov_ss, const double* cov_tt, const double* cov_st,
+                                   double* out);
 /* Measurement hook (tools/pose_graph_bench.py --marginals): with a device buffer of 3 long long per run of the next calls of this
  * thread, the run sweep's lane 0 stores the 100 MHz clock ticks it spent in the columns' products, the butterflies and the nodes'
  * steps; null (the default) turns it off.                                                                                       */

@@ -152,6 +152,11 @@ SIGNATURES = {
                                          c_void]),
     'rdm_pose_graph_marginals_host': (c_int, [c_i64, c_i64, c_void, c_void, c_void, c_void]),
     'rdm_dbg_pose_graph_marginals_ticks': (c_int, [c_void]),
+    'rdm_pose_graph_consistency_workspace_bytes': (c_size, [c_i64, c_void, c_void, c_void, c_void, c_void]),
+    'rdm_pose_graph_consistency': (c_int, [c_i64, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void,
+                                           c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_size, c_void]),
+    'rdm_pose_graph_pair_covariances_host': (c_int, [c_i64, c_i64, c_void, c_void, c_void, c_i64, c_void, c_void]),
+    'rdm_pose_graph_pair_terms_host': (c_int, [c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
     'rdm_pose_graph_edge_terms_host': (c_int, [c_void, c_void, c_void, c_void, ctypes.c_double, c_int, c_void]),
     'rdm_pose_graph_retract_host': (c_int, [c_void, c_void, c_void]),
     'rdm_neighbor_histogram': (c_int, [c_void, c_i64, c_void, c_int, c_void]),

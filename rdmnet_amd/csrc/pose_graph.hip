@@ -25,7 +25,10 @@
 //
 // rdm_pose_graph_marginals (the marginal covariance of every pose at given poses and weights) is a second, single-pass caller of the
 // same pieces: edge_terms with the given weight in the line process's place, assemble_nodes, the direct solve's factors at lambda = 0,
-// then a selected inversion (pg_marg_separator_kernel, pg_marg_sweep_kernel) under the same guarantee.
+// then a selected inversion (pg_marg_separator_kernel, pg_marg_sweep_kernel) under the same guarantee.  rdm_pose_graph_consistency
+// launches exactly that (enqueue_marginals) and then, for a list of pairs of nodes, solves for the columns of H^-1 that the pairs
+// need from the same factors (pg_cons_*_kernel): cross covariances, the covariance of a candidate edge's residual and its squared
+// Mahalanobis distance, a pair's rows the same bits whatever else the call holds.
 #include "common.h"
 #include "../../include/rdmnet_hip.h"
 
@@ -218,6 +221,21 @@ __host__ __device__ inline void put_block(double* H, int br, int bc, const M3& a
     for (int j = 0; j < 3; ++j) H[6 * (3 * br + i) + 3 * bc + j] = l * a.m[3 * i + j];
 }
 
+// The non-zero 3 x 3 blocks of an edge's Jacobians (below): A = [[Ja, 0], [0, Ra]], B = [[B11, 0], [B21, B22]].
+struct EdgeJacobians {
+  M3 Ja, Ra, B11, B21, B22;
+};
+__host__ __device__ inline EdgeJacobians edge_jacobians(const Residual& r, const double* T) {
+  EdgeJacobians j;
+  j.Ja = jr_inv(r.w, r.theta2);
+  j.Ra = r.Re;
+  const M3 RT = rot_of(T);
+  j.B11 = neg(mul(j.Ja, transpose(r.Rst)));
+  j.B21 = tmul(RT, skew(r.u));
+  j.B22 = neg(transpose(RT));
+  return j;
+}
+
 // Everything one edge contributes: l, its cost term, and (times l) Haa = A^T L A, Hab = A^T L B, Hbb = B^T L B, ga = A^T L r,
 // gb = B^T L r (and r itself into r_out, also beyond the limit), where A = d r / d(source perturbation) = [[Jr^-1, 0], [0, R_E]] and B = d r / d(target perturbation) =
 // [[-Jr^-1 Rst^T, 0], [R_T^T [u]x, -R_T^T]] (right perturbations X <- X [Exp(dw) | dt]).  Returns false beyond the angle limit.
@@ -246,9 +264,8 @@ __host__ __device__ inline bool edge_terms(const double* Xs, const double* Xt, c
       L22.m[3 * i + j] = 0.5 * (L[6 * (3 + i) + 3 + j] + L[6 * (3 + j) + 3 + i]);
     }
   L21 = transpose(L12);
-  const M3 Ja = jr_inv(r.w, r.theta2), Ra = r.Re;
-  const M3 RT = rot_of(T);
-  const M3 B11 = neg(mul(Ja, transpose(r.Rst))), B21 = tmul(RT, skew(r.u)), B22 = neg(transpose(RT));
+  const EdgeJacobians J = edge_jacobians(r, T);
+  const M3 &Ja = J.Ja, &Ra = J.Ra, &B11 = J.B11, &B21 = J.B21, &B22 = J.B22;
   // L A and L B by blocks
   const M3 LA11 = mul(L11, Ja), LA12 = mul(L12, Ra), LA21 = mul(L21, Ja), LA22 = mul(L22, Ra);
   const M3 LB11 = add(mul(L11, B11), mul(L12, B21)), LB12 = mul(L12, B22);
@@ -1706,6 +1723,363 @@ __global__ __launch_bounds__(kBlock) void pg_marg_finish_kernel(Graphs gr, int n
   marg_write_block(S + 36 * i, i == gr.node_off[g], fail[g] != 0, out + 36 * i);
 }
 
+// ---- cross covariances and loop-edge consistency -------------------------------------------------------------
+// Sigma_st = (H^-1)_st for a list of pairs (s, t), from the same factors and Sigma_SS: the six columns of H^-1 that belong to the
+// pair's COLUMN NODE t are solved for -- forwards along t's run (y = L^-1 e, then u_S = -Y^T y), through the separator
+// (x_S = Sigma_SS u_S), backwards along the run of every row node asked for (x = L^-T (y - Y x_S)) -- and the rows of s are read off.
+// A thread owns ONE of the six scalar columns of one column node: its recurrences need nothing from another thread, and every sum
+// it forms has an order that the graph and the pair decide.  The columns of a call are taken kColumnsInFlight at a time; their y,
+// u_S and x_S live in the workspace.  As above, one work item per function, for the device and for the host
+// (rdm_pose_graph_pair_covariances_host).
+constexpr int kColumnsInFlight = 128;  // column nodes whose forward vectors the workspace holds at a time
+
+struct Pairs {             // the host-built plan of a call's pairs (global node, run, separator and coupling numbers) and its arrays
+  const int* pair_s;       // [P] the pair's nodes
+  const int* pair_t;       // [P]
+  const int* col_node;     // [K] the distinct column nodes, ascending
+  const int* col_run;      // [K] the column node's run, or -1: it is a separator node
+  const int* col_pos;      // [K] its position in the run, or its separator number
+  const int* grp_off;      // [R + 1] a group's items; a group is a column and a run that holds row nodes (or -1: rows in the separator)
+  const int* grp_col;      // [R] ascending, so a chunk of columns is a range of groups
+  const int* grp_run;      // [R]
+  const int* item_pos;     // [I] the row node's position in the run, descending inside a group, or its separator number
+  const int* item_pair;    // [I] the pair whose block the item is
+  int y_stride, u_stride, x_stride;  // 6 x 6 blocks per column in flight: forward positions, couplings of its run, separator nodes
+  double* yf;              // [kColumnsInFlight, y_stride, 36] a block is six scalar columns of 6 doubles each
+  double* us;              // [kColumnsInFlight, u_stride, 36]
+  double* xs;              // [kColumnsInFlight, x_stride, 36]
+  double* cross;           // [P + 1, 36] Sigma_st of every pair, staged; block P is zeros (node 0's rows)
+  unsigned long long* bad_pair;  // 8 * (the first refused pair) + its cause, or all ones
+};
+
+// Scalar column c of column k (in slot `slot` of the chunk), forwards: y_p = G_p e_c at the node's position, y_j = -W_j y_{j-1} to the
+// run's end, as direct_run_factor carries its y; then the column's part of u_S = -Y^T y, a coupling of the run after the other, the
+// positions in ascending order as direct_schur_rhs takes them.  The thread reads back only what it wrote.
+__host__ __device__ inline void cons_forward_column(const Direct& dp, const DirectSystem& sy, const Pairs& pp, int k, int slot, int c) {
+  const int run = pp.col_run[k];
+  if (run < 0) return;
+  const int p = pp.col_pos[k], len = dp.run_len[run];
+  const long long first = dp.run_begin[run];
+  double* yf = pp.yf + 36ll * slot * pp.y_stride + 6 * c;
+  const double* G = sy.F + 21 * (first + p);
+  double y[6];
+#pragma unroll
+  for (int r = 0; r < 6; ++r) yf[r] = y[r] = r >= c ? G[r * (r + 1) / 2 + c] : 0.0;
+  for (int pos = p + 1; pos < len; ++pos) {
+    const double* W = sy.Wc + 36 * (first + pos);
+    double t[6];
+#pragma unroll
+    for (int r = 0; r < 6; ++r) t[r] = chain_row(0.0, W + 6 * r, y);
+#pragma unroll
+    for (int r = 0; r < 6; ++r) yf[36ll * (pos - p) + r] = y[r] = t[r];
+  }
+  const int c0 = dp.cpl_off[run], c1 = dp.cpl_off[run + 1];
+  for (int cu = c0; cu < c1; ++cu) {
+    const int pc = dp.cpl_pos[cu], b = pc > p ? pc : p;
+    const double* Yc = dp.Y + 36ll * (dp.cpl_y[cu] + (b - pc));
+    const double* yy = yf + 36ll * (b - p);
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int pos = b; pos < len; ++pos, Yc += 36, yy += 36) dense_sub_mul(Yc, yy, acc, true);
+    double* u = pp.us + 36ll * (static_cast<long long>(slot) * pp.u_stride + (cu - c0)) + 6 * c;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) u[r] = acc[r];
+  }
+}
+
+// Scalar column c of block v of x_S = Sigma_SS u_S of column k: the sum over the couplings of the column node's run, which are in
+// ascending separator order; for a column node that is itself separator node number col_pos, column c of block (v, col_pos) of
+// Sigma_SS.  Sg: the graph's Sigma_SS ([s, s] blocks, both triangles), s0 its first separator number.
+__host__ __device__ inline void cons_separator_column(const Direct& dp, const Pairs& pp, const double* Sg, int s, int s0, int k, int slot,
+                                                      int v, int c) {
+  const int run = pp.col_run[k];
+  double x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (run < 0) {
+    const double* Sb = Sg + 36ll * (static_cast<long long>(v) * s + (pp.col_pos[k] - s0));
+#pragma unroll
+    for (int r = 0; r < 6; ++r) x[r] = Sb[6 * r + c];
+  } else {
+    const int c0 = dp.cpl_off[run], c1 = dp.cpl_off[run + 1];
+    for (int cu = c0; cu < c1; ++cu) {
+      const double* u = pp.us + 36ll * (static_cast<long long>(slot) * pp.u_stride + (cu - c0)) + 6 * c;
+      double t[6];
+      block_mul(Sg + 36ll * (static_cast<long long>(v) * s + (dp.cpl_sep[cu] - s0)), u, false, t);
+#pragma unroll
+      for (int r = 0; r < 6; ++r) x[r] += t[r];
+    }
+  }
+  double* o = pp.xs + 36ll * (static_cast<long long>(slot) * pp.x_stride + v) + 6 * c;
+#pragma unroll
+  for (int r = 0; r < 6; ++r) o[r] = x[r];
+}
+
+// Scalar column c of group `group` (column k in slot `slot`, row run `run`): x = L^-T (y [the column's own run] - Y x_S) backwards from
+// the run's last position down to the lowest one asked for, as direct_run_back goes (a position's couplings that have begun in
+// ascending separator order); column c of the block of every item on the way is written.  Row nodes in the separator (run -1) read x_S.
+__host__ __device__ inline void cons_back_column(const Direct& dp, const DirectSystem& sy, const Pairs& pp, int s0, int group, int slot,
+                                                 int c) {
+  const int k = pp.grp_col[group], run = pp.grp_run[group];
+  int it = pp.grp_off[group];
+  const int ie = pp.grp_off[group + 1];
+  const double* xs = pp.xs + 36ll * slot * pp.x_stride + 6 * c;
+  if (run < 0) {
+    for (; it < ie; ++it) {
+      const double* x = xs + 36ll * (pp.item_pos[it] - s0);
+      double* o = pp.cross + 36ll * pp.item_pair[it] + c;
+#pragma unroll
+      for (int r = 0; r < 6; ++r) o[6 * r] = x[r];
+    }
+    return;
+  }
+  const bool same = pp.col_run[k] == run;
+  const int p = same ? pp.col_pos[k] : 0, len = dp.run_len[run], low = pp.item_pos[ie - 1];
+  const long long first = dp.run_begin[run];
+  const double* yf = pp.yf + 36ll * slot * pp.y_stride + 6 * c;
+  const int c0 = dp.cpl_off[run], c1 = dp.cpl_off[run + 1];
+  double y[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int pos = len - 1; pos >= low; --pos) {
+    const long long node = first + pos;
+    double t[6], q[6];
+#pragma unroll
+    for (int r = 0; r < 6; ++r) t[r] = same && pos >= p ? yf[36ll * (pos - p) + r] : 0.0;
+    for (int cu = c0; cu < c1; ++cu) {
+      const int pc = dp.cpl_pos[cu];
+      if (pos < pc) continue;
+      dense_sub_mul(dp.Y + 36ll * (dp.cpl_y[cu] + (pos - pc)), xs + 36ll * (dp.cpl_sep[cu] - s0), t, false);
+    }
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      double col[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+      if (pos + 1 < len) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) col[j] = sy.Wc[36 * (node + 1) + 6 * j + r];
+      }
+      q[r] = chain_row(t[r], col, y);
+    }
+#pragma unroll
+    for (int r = 0; r < 6; ++r) y[r] = q[r];
+    if (it < ie && pp.item_pos[it] == pos) {
+      chain_gt_mul(sy.F + 21 * node, q, t);
+      for (; it < ie && pp.item_pos[it] == pos; ++it) {
+        double* o = pp.cross + 36ll * pp.item_pair[it] + c;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) o[6 * r] = t[r];
+      }
+    }
+  }
+}
+
+// Entry (r, c) of a node's covariance block whose lower triangle holds it (a staged block, or an exactly symmetric one).
+__host__ __device__ __forceinline__ double sym_entry(const double* S, int r, int c) { return S[6 * (r > c ? r : c) + (r > c ? c : r)]; }
+
+// One pair from (X_s, X_t, T, L or null) and the blocks Sigma_ss, Sigma_tt (their lower triangles are read) and Sigma_st (rows: s): the
+// residual r (as edge_terms gives it), M = A Sigma_ss A^T + A Sigma_st B^T + B Sigma_ts A^T + B Sigma_tt B^T with edge_terms'
+// Jacobians -- its lower triangle is computed and copied above the diagonal -- and d2 = r^T (M + L^-1)^-1 r by cholesky6 (L^-1 from
+// chain_factor_node's G = F^-1 of L = F F^T; L symmetrised as the edges' are).  -> 0; 1: L or M + L^-1 is not positive definite (d2
+// is NaN); -1: the residual is beyond the angle limit (nothing but r is written).
+__host__ __device__ inline int pair_terms(const double* Xs, const double* Xt, const double* T, const double* L, const double* Sss,
+                                          const double* Stt, const double* Sst, double* r_out, double* M_out, double* d2_out) {
+  Residual res;
+  const bool ok = edge_residual(Xs, Xt, T, res);
+  double r[6];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    r_out[i] = r[i] = res.w.v[i];
+    r_out[3 + i] = r[3 + i] = res.v.v[i];
+  }
+  if (!ok) return -1;
+  double A[36], B[36], m[36];
+#pragma unroll
+  for (int k = 0; k < 36; ++k) A[k] = B[k] = m[k] = 0.0;
+  {
+    const EdgeJacobians J = edge_jacobians(res, T);
+    put_block(A, 0, 0, J.Ja, 1.0);
+    put_block(A, 1, 1, J.Ra, 1.0);
+    put_block(B, 0, 0, J.B11, 1.0);
+    put_block(B, 1, 0, J.B21, 1.0);
+    put_block(B, 1, 1, J.B22, 1.0);
+  }
+  {  // U = A Sigma_ss + B Sigma_ts, then the lower triangle of U A^T
+    double U[36];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        double a = 0.0, b = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          a += A[6 * i + k] * sym_entry(Sss, k, j);
+          b += B[6 * i + k] * Sst[6 * j + k];
+        }
+        U[6 * i + j] = a + b;
+      }
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j <= i; ++j) {
+        double a = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) a += U[6 * i + k] * A[6 * j + k];
+        m[6 * i + j] = a;
+      }
+  }
+  {  // V = A Sigma_st + B Sigma_tt, then the lower triangle of V B^T on top
+    double V[36];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        double a = 0.0, b = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          a += A[6 * i + k] * Sst[6 * k + j];
+          b += B[6 * i + k] * sym_entry(Stt, k, j);
+        }
+        V[6 * i + j] = a + b;
+      }
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j <= i; ++j) {
+        double a = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) a += V[6 * i + k] * B[6 * j + k];
+        m[6 * i + j] += a;
+      }
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) M_out[6 * i + j] = m[6 * (i > j ? i : j) + (i > j ? j : i)];
+  bool pd = true;
+  if (L != nullptr) {  // the lower triangle of L^-1 = G^T G on top of M's
+    double d[36], g[21], x[36];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) d[6 * i + j] = 0.5 * (L[6 * i + j] + L[6 * j + i]);
+    pd = chain_factor_node(d, nullptr, nullptr, g, x);
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j <= i; ++j) {
+        double a = 0.0;
+#pragma unroll
+        for (int k = i; k < 6; ++k) a += g[k * (k + 1) / 2 + i] * g[k * (k + 1) / 2 + j];
+        m[6 * i + j] += a;
+      }
+  }
+  if (!cholesky6(m)) pd = false;
+  dense_lower_solve(m, r);
+  double d2 = 0.0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) d2 += r[i] * r[i];
+  *d2_out = pd ? d2 : NAN;
+  return pd ? 0 : 1;
+}
+
+// One thread per pair: its transform and information as pg_check_kernel holds an edge's, and the angle limit of its residual at the
+// given poses.  The first refused pair and its cause go to *bad_pair (an integer minimum), and the call is refused through *failed.
+__global__ __launch_bounds__(kBlock) void pg_cons_check_kernel(Pairs pp, int p_total, const double* __restrict__ X,
+                                                               const double* __restrict__ T, const double* __restrict__ L,
+                                                               const int* __restrict__ bad, int* __restrict__ failed) {
+  const long long i = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= p_total || *bad != 0) return;
+  int b = 0;
+  const double* Ti = T + 16 * i;
+  for (int k = 0; k < 16; ++k)
+    if (!isfinite(Ti[k])) b = ST_NONFINITE;
+  if (L != nullptr) {
+    const double* M = L + 36 * i;
+    double big = 0.0;
+    for (int k = 0; k < 36; ++k) {
+      if (!isfinite(M[k])) b = ST_NONFINITE;
+      big = fmax(big, fabs(M[k]));
+    }
+    if (b == 0)
+      for (int r = 0; r < 6; ++r)
+        for (int c = r + 1; c < 6; ++c)
+          if (fabs(M[6 * r + c] - M[6 * c + r]) > kSymTol * big) b = ST_ASYMMETRIC;
+  }
+  if (b == 0) {
+    Residual r;
+    if (!edge_residual(X + 16ll * pp.pair_s[i], X + 16ll * pp.pair_t[i], Ti, r)) b = ST_ANGLE;
+  }
+  if (b == 0) return;
+  atomicMin(pp.bad_pair, 8ull * static_cast<unsigned long long>(i) + static_cast<unsigned long long>(b));
+  *failed = b;  // (any writer's value names a cause that is present)
+}
+
+// The graph of column k takes no part: the input check refused the call, or the graph has no free node or a failed pivot.
+__device__ __forceinline__ bool cons_skip(const Graphs& gr, const Direct& dp, const Pairs& pp, const GraphState* gs, const int* bad, int k,
+                                          int* g_out) {
+  if (*bad != 0) return true;
+  const int g = gr.node_graph[pp.col_node[k]];
+  *g_out = g;
+  return gs[g].done || dp.fail[g] != 0;
+}
+
+// One thread per scalar column of the chunk's columns k0 .. k0 + cols - 1.
+__global__ __launch_bounds__(kBlock) void pg_cons_forward_kernel(Graphs gr, Direct dp, DirectSystem sy, Pairs pp, int k0, int cols,
+                                                                 const GraphState* __restrict__ gs, const int* __restrict__ bad) {
+  const int t = blockIdx.x * kBlock + threadIdx.x, slot = t / 6;
+  int g;
+  if (slot >= cols || cons_skip(gr, dp, pp, gs, bad, k0 + slot, &g)) return;
+  cons_forward_column(dp, sy, pp, k0 + slot, slot, t - 6 * slot);
+}
+
+// One thread per scalar column of every block of x_S of the chunk's columns (x_stride blocks each; a graph uses its first s).
+__global__ __launch_bounds__(kBlock) void pg_cons_separator_kernel(Graphs gr, Direct dp, Pairs pp, int k0, int cols,
+                                                                   const GraphState* __restrict__ gs, const int* __restrict__ bad) {
+  const long long t = static_cast<long long>(blockIdx.x) * kBlock + threadIdx.x;
+  const int slot = static_cast<int>(t / (6ll * pp.x_stride));
+  int g;
+  if (slot >= cols || cons_skip(gr, dp, pp, gs, bad, k0 + slot, &g)) return;
+  const int q = static_cast<int>(t - 6ll * pp.x_stride * slot), v = q / 6;
+  const int s0 = dp.sep_off[g], s = dp.sep_off[g + 1] - s0;
+  if (v >= s) return;
+  cons_separator_column(dp, pp, dp.C + 36ll * dp.c_off[g], s, s0, k0 + slot, slot, v, q - 6 * v);
+}
+
+// One thread per scalar column of the chunk's groups r0 .. r0 + groups - 1.
+__global__ __launch_bounds__(kBlock) void pg_cons_back_kernel(Graphs gr, Direct dp, DirectSystem sy, Pairs pp, int k0, int r0, int groups,
+                                                              const GraphState* __restrict__ gs, const int* __restrict__ bad) {
+  const int t = blockIdx.x * kBlock + threadIdx.x, q = t / 6;
+  if (q >= groups) return;
+  const int k = pp.grp_col[r0 + q];
+  int g;
+  if (cons_skip(gr, dp, pp, gs, bad, k, &g)) return;
+  cons_back_column(dp, sy, pp, dp.sep_off[g], r0 + q, k - k0, t - 6 * q);
+}
+
+// One thread per pair, only when the call is not refused: the pair's outputs (each may be null) from the staged blocks through
+// pair_terms; NaN for a graph whose factor failed; a pair with node 0 has a zero cross block.
+__global__ __launch_bounds__(kWave) void pg_cons_pair_kernel(Graphs gr, Pairs pp, int p_total, const double* __restrict__ X,
+                                                             const double* __restrict__ T, const double* __restrict__ L,
+                                                             const int* __restrict__ fail, const int* __restrict__ failed,
+                                                             const double* __restrict__ S, double* __restrict__ cross_out,
+                                                             double* __restrict__ m_out, double* __restrict__ d2_out,
+                                                             uint8_t* __restrict__ status_out) {
+  const int i = blockIdx.x * kWave + threadIdx.x;
+  if (i >= p_total || *failed != 0) return;
+  const long long a = pp.pair_s[i], b = pp.pair_t[i];
+  const int g = gr.node_graph[a];
+  const long long node0 = gr.node_off[g];
+  const double* zero = pp.cross + 36ll * p_total;
+  const double* Sst = a == node0 || b == node0 ? zero : pp.cross + 36ll * i;
+  double r[6], m[36], d2 = NAN;
+  int status = 0;
+  const bool dead = fail[g] != 0;
+  if (!dead)
+    status = pair_terms(X + 16 * a, X + 16 * b, T + 16ll * i, L != nullptr ? L + 36ll * i : nullptr, a == node0 ? zero : S + 36 * a,
+                        b == node0 ? zero : S + 36 * b, Sst, r, m, &d2);
+  if (cross_out != nullptr)
+    for (int k = 0; k < 36; ++k) cross_out[36ll * i + k] = dead ? NAN : Sst[k];
+  if (m_out != nullptr)
+    for (int k = 0; k < 36; ++k) m_out[36ll * i + k] = dead ? NAN : m[k];
+  if (d2_out != nullptr) d2_out[i] = dead ? NAN : d2;
+  if (status_out != nullptr) status_out[i] = static_cast<uint8_t>(status > 0 ? status : 0);
+}
+
 // One thread per node: candidate pose Xc = X [Exp(dw) | dt]; node 0 of a graph keeps its pose.
 __global__ __launch_bounds__(kBlock) void pg_update_kernel(Graphs gr, int n_total, const GraphState* __restrict__ gs,
                                                            const double* __restrict__ X, const double* __restrict__ xv,
@@ -2319,7 +2693,205 @@ void marg_sweep_run_host(const Direct& dp, const DirectSystem& sy, const Margina
   }
 }
 
+// ---- the pairs' plan (host) ------------------------------------------------------------------------------------------------------
+
+struct PairPlan {  // Pairs' tables on the host, and what the host alone needs: a chunk's first group, the strides
+  std::vector<int> pair_s, pair_t, col_node, col_run, col_pos, grp_off, grp_col, grp_run, item_pos, item_pair;
+  std::vector<int> chunk_grp;  // [chunks + 1] the first group of every chunk of kColumnsInFlight columns
+  int y_stride = 1, u_stride = 1, x_stride = 1;
+};
+// The ONE list of Pairs' tables, as kDirectInts is the direct solve's.
+struct PairTable {
+  std::vector<int> PairPlan::*plan;
+  const int* Pairs::*table;
+};
+constexpr PairTable kPairInts[] = {{&PairPlan::pair_s, &Pairs::pair_s},     {&PairPlan::pair_t, &Pairs::pair_t},
+                                   {&PairPlan::col_node, &Pairs::col_node}, {&PairPlan::col_run, &Pairs::col_run},
+                                   {&PairPlan::col_pos, &Pairs::col_pos},   {&PairPlan::grp_off, &Pairs::grp_off},
+                                   {&PairPlan::grp_col, &Pairs::grp_col},   {&PairPlan::grp_run, &Pairs::grp_run},
+                                   {&PairPlan::item_pos, &Pairs::item_pos}, {&PairPlan::item_pair, &Pairs::item_pair}};
+
+// The plan of a call's pairs over the direct solve's plan: the pairs checked (inside their graph, s != t), grouped by column node t,
+// then by the run of the row node s, positions descending -- so a column's forward pass runs once and a run's backward pass once,
+// down to the lowest position asked for.  Pairs with node 0 hold no block and stay out of the groups.  false, with the error set.
+bool build_pair_plan(int64_t G, const int* node_off, const DirectPlan& pl, const int64_t* pair_off, const int64_t* pairs_host,
+                     PairPlan& pp, const char* who) {
+  pp = PairPlan();
+  const int64_t N = node_off[G], P = pair_off[G];
+  std::vector<int> node_run(static_cast<size_t>(N > 0 ? N : 1), -1), node_at(static_cast<size_t>(N > 0 ? N : 1), -1);
+  for (size_t r = 0; r < pl.run_begin.size(); ++r)
+    for (int i = 0; i < pl.run_len[r]; ++i) {
+      node_run[pl.run_begin[r] + i] = static_cast<int>(r);
+      node_at[pl.run_begin[r] + i] = i;
+    }
+  for (size_t u = 0; u < pl.sep_node.size(); ++u) node_at[pl.sep_node[u]] = static_cast<int>(u);
+  struct Item {
+    int col, run, pos, pair;
+    bool operator<(const Item& o) const {
+      return col != o.col ? col < o.col : run != o.run ? run < o.run : pos != o.pos ? pos > o.pos : pair < o.pair;
+    }
+  };
+  std::vector<Item> items;
+  pp.pair_s.resize(static_cast<size_t>(P));
+  pp.pair_t.resize(static_cast<size_t>(P));
+  for (int64_t g = 0; g < G; ++g) {
+    const int64_t n = node_off[g + 1] - node_off[g];
+    for (int64_t k = pair_off[g]; k < pair_off[g + 1]; ++k) {
+      const int64_t s = pairs_host[2 * k], t = pairs_host[2 * k + 1];
+      if (s < 0 || s >= n || t < 0 || t >= n) {
+        set_error("%s: pair %lld (%lld, %lld) is outside graph %lld of %lld nodes", who, static_cast<long long>(k), static_cast<long long>(s),
+                  static_cast<long long>(t), static_cast<long long>(g), static_cast<long long>(n));
+        return false;
+      }
+      if (s == t) {
+        set_error("%s: pair %lld joins node %lld to itself", who, static_cast<long long>(k), static_cast<long long>(s));
+        return false;
+      }
+      pp.pair_s[k] = static_cast<int>(node_off[g] + s);
+      pp.pair_t[k] = static_cast<int>(node_off[g] + t);
+      if (s == 0 || t == 0) continue;
+      items.push_back({pp.pair_t[k], node_run[pp.pair_s[k]], node_at[pp.pair_s[k]], static_cast<int>(k)});  // (col: the node, for now)
+    }
+  }
+  std::sort(items.begin(), items.end());
+  std::vector<int> run_couplings(pl.run_begin.size(), 0);
+  for (size_t r = 0; r < pl.run_begin.size(); ++r) run_couplings[r] = pl.cpl_off[r + 1] - pl.cpl_off[r];
+  int graph = 0;
+  for (size_t i = 0; i < items.size(); ++i) {
+    const Item& it = items[i];
+    const bool new_col = i == 0 || items[i - 1].col != it.col;
+    if (new_col) {
+      const int node = it.col, run = node_run[node];
+      if (pp.col_node.size() % kColumnsInFlight == 0) pp.chunk_grp.push_back(static_cast<int>(pp.grp_col.size()));
+      pp.col_node.push_back(node);
+      pp.col_run.push_back(run);
+      pp.col_pos.push_back(node_at[node]);
+      while (node >= node_off[graph + 1]) ++graph;
+      pp.x_stride = std::max(pp.x_stride, pl.sep_off[graph + 1] - pl.sep_off[graph]);
+      if (run >= 0) {
+        pp.y_stride = std::max(pp.y_stride, pl.run_len[run] - node_at[node]);
+        pp.u_stride = std::max(pp.u_stride, run_couplings[run]);
+      }
+    }
+    if (new_col || items[i - 1].run != it.run) {
+      pp.grp_off.push_back(static_cast<int>(i));
+      pp.grp_col.push_back(static_cast<int>(pp.col_node.size()) - 1);
+      pp.grp_run.push_back(it.run);
+    }
+    pp.item_pos.push_back(it.pos);
+    pp.item_pair.push_back(it.pair);
+  }
+  pp.grp_off.push_back(static_cast<int>(items.size()));
+  pp.chunk_grp.push_back(static_cast<int>(pp.grp_col.size()));
+  return true;
+}
+
+template <typename Visit>
+void for_each_pair_table(const PairPlan& pl, Pairs& d, Visit visit) {
+  for (const auto& t : kPairInts) visit(pl.*t.plan, d.*t.table);
+}
+
+// The pairs' part of the workspace, behind the marginals': the tables (one upload, from *tables_begin for *tables_bytes), the
+// forward vectors, u_S and x_S of the columns in flight, the staged cross blocks and the refusal word.
+bool carve_pairs(Arena& ar, const PairPlan& pl, Pairs& d, void** tables_begin, size_t* tables_bytes) {
+  const size_t begin = ar.off;
+  *tables_begin = ar.base != nullptr ? ar.base + begin : nullptr;
+  for_each_pair_table(pl, d, [&](const std::vector<int>& v, const int*& table) { table = ar.take<int>(v.size() > 0 ? v.size() : 1); });
+  *tables_bytes = ar.off - begin;
+  const size_t cols = std::min<size_t>(pl.col_node.size() > 0 ? pl.col_node.size() : 1, kColumnsInFlight);
+  d.y_stride = pl.y_stride;
+  d.u_stride = pl.u_stride;
+  d.x_stride = pl.x_stride;
+  d.yf = ar.take<double>(36 * cols * static_cast<size_t>(pl.y_stride));
+  d.us = ar.take<double>(36 * cols * static_cast<size_t>(pl.u_stride));
+  d.xs = ar.take<double>(36 * cols * static_cast<size_t>(pl.x_stride));
+  d.cross = ar.take<double>(36 * (pl.pair_s.size() + 1));
+  d.bad_pair = ar.take<unsigned long long>(1);
+  return ar.ok;
+}
+
+// The checks of a consistency call's host arguments, then the two plans; the marginals' refusals come first.
+int build_consistency_plans(const char* who, int64_t G, const int64_t* graph_node_offsets_host, const int64_t* graph_edge_offsets_host,
+                            const int64_t* edges_host, const int64_t* graph_pair_offsets_host, const int64_t* pairs_host,
+                            std::vector<char>& host, DirectPlan& plan, PairPlan& pairs) {
+  RDM_REQUIRE(G >= 0 && G < kMaxTotal && graph_node_offsets_host && graph_edge_offsets_host && graph_pair_offsets_host,
+              "%s: bad number of graphs or null offsets", who);
+  int rc = check_graphs(G, graph_node_offsets_host, graph_edge_offsets_host);
+  if (rc != RDM_OK) return rc;
+  RDM_REQUIRE(graph_edge_offsets_host[G] == 0 || edges_host, "%s: null edges", who);
+  RDM_REQUIRE(graph_pair_offsets_host[0] == 0, "%s: pair offsets must begin at 0", who);
+  for (int64_t g = 0; g < G; ++g)
+    RDM_REQUIRE(graph_pair_offsets_host[g + 1] >= graph_pair_offsets_host[g], "%s: pair offsets of graph %lld decrease", who,
+                static_cast<long long>(g));
+  RDM_REQUIRE(graph_pair_offsets_host[G] < kMaxTotal / 36, "%s: too many pairs in one call", who);
+  RDM_REQUIRE(graph_pair_offsets_host[G] == 0 || pairs_host, "%s: null pairs", who);
+  rc = build_host_tables(G, graph_node_offsets_host, graph_edge_offsets_host, edges_host, nullptr, host, &plan, who, "");
+  if (rc != RDM_OK) return rc;
+  Work t;
+  Arena ar(host.data(), host.size());
+  carve_tables(ar, G, graph_node_offsets_host[G], graph_edge_offsets_host[G], t);
+  return build_pair_plan(G, t.node_off, plan, graph_pair_offsets_host, pairs_host, pairs, who) ? RDM_OK : RDM_ERR_ARG;
+}
+
 thread_local long long* t_marg_ticks = nullptr;  // rdm_dbg_pose_graph_marginals_ticks
+
+// The marginals' kernels on the stream, from the state's initialisation to the run sweep and the report (which sets *failed): the
+// staged blocks lie in mg.S, Sigma_SS in dp.C.  rdm_pose_graph_marginals and rdm_pose_graph_consistency both launch exactly this.
+void enqueue_marginals(hipStream_t st, const Graphs& gr, const Work& w, const Direct& dp, const Marginals& mg, const DirectPlan& plan,
+                       int64_t G, int64_t N, int64_t E, const double* nodes, const double* transforms, const double* informations,
+                       const double* weights) {
+  Params p = {};
+  p.gtol = -1.0;  // (pg_direct_blocks_kernel's gradient test never ends a graph: the blocks are wanted at a minimum too)
+  int *bad = w.flags, *failed = w.flags + 2;
+  const int n = static_cast<int>(N), e = static_cast<int>(E), g = static_cast<int>(G);
+  const DirectSystem sy = {w.es, w.et, w.inc_off, w.inc, w.D, w.Hab, w.rv, w.F, w.Wc, w.zv, w.xv};
+  const int runs = static_cast<int>(plan.run_begin.size()), couplings = static_cast<int>(plan.cpl_sep.size());
+  const long long items = plan.item_off.back();
+  fill_words<int>(w.flags, 4, 0, st);
+  fill_words<int>(dp.fail, G, 0, st);
+  hipLaunchKernelGGL(pg_marg_init_kernel, dim3(blocks_for(G)), dim3(kBlock), 0, st, w.gs, g, w.node_off);
+  hipLaunchKernelGGL(pg_check_kernel, dim3(blocks_for(std::max(N, E))), dim3(kBlock), 0, st, gr, nodes, n, transforms, informations, e,
+                     w.gs, bad);
+  hipLaunchKernelGGL(pg_marg_linearize_kernel, dim3(blocks_for(E)), dim3(kBlock), 0, st, gr, e, nodes, transforms, informations, weights,
+                     w.gs, w.Haa, w.Hab, w.Hbb, w.ga, w.gb, bad);
+  hipLaunchKernelGGL(pg_direct_blocks_kernel, dim3(static_cast<unsigned>(G)), dim3(kBlock), 0, st, gr, p, w.gs, w.Haa, w.Hab, w.Hbb, w.ga,
+                     w.gb, w.D, w.bv, w.xv, w.rv, w.Wc, dp.fail, bad);
+  if (runs > 0) hipLaunchKernelGGL(pg_direct_factor_kernel, dim3((runs + kWave - 1) / kWave), dim3(kWave), 0, st, dp, sy, runs, w.gs, bad);
+  if (couplings > 0)
+    hipLaunchKernelGGL(pg_direct_border_kernel, dim3(blocks_for(6ll * couplings)), dim3(kBlock), 0, st, dp, sy, couplings, w.gs, bad);
+  if (items > 0) hipLaunchKernelGGL(pg_direct_schur_kernel, dim3(blocks_for(items)), dim3(kBlock), 0, st, dp, sy, g, items, w.gs, bad);
+  hipLaunchKernelGGL(pg_marg_separator_kernel, dim3(static_cast<unsigned>(G)), dim3(kBlock), 0, st, dp, mg, w.gs, bad);
+  if (runs > 0) {
+    if (t_marg_ticks != nullptr)
+      hipLaunchKernelGGL(pg_marg_sweep_kernel<true>, dim3(runs), dim3(kWave), 0, st, dp, sy, mg, w.gs, bad, t_marg_ticks);
+    else
+      hipLaunchKernelGGL(pg_marg_sweep_kernel<false>, dim3(runs), dim3(kWave), 0, st, dp, sy, mg, w.gs, bad, static_cast<long long*>(nullptr));
+  }
+  hipLaunchKernelGGL(pg_report_kernel, dim3(1), dim3(64), 0, st, g, w.gs, bad, w.report, failed);
+}
+
+// The end of both calls: the report and the runs' failure words read back; RDM_ERR_ARG for the first graph with a status, else
+// `out` [G, 2] for report_host.
+int read_marginals_report(const char* who, hipStream_t st, const Work& w, const Direct& dp, const DirectPlan& plan, int64_t G,
+                          std::vector<double>& out) {
+  std::vector<double> report(kReport * static_cast<size_t>(G));
+  std::vector<int> fail(static_cast<size_t>(G));
+  RDM_HIP_CHECK(hipMemcpyAsync(report.data(), w.report, sizeof(double) * kReport * G, hipMemcpyDeviceToHost, st));
+  RDM_HIP_CHECK(hipMemcpyAsync(fail.data(), dp.fail, sizeof(int) * G, hipMemcpyDeviceToHost, st));
+  RDM_HIP_CHECK(hipStreamSynchronize(st));
+  for (int64_t q = 0; q < G; ++q) {
+    const int status = static_cast<int>(report[q * kReport + 5]);
+    if (status == ST_OK) continue;
+    set_error("%s: graph %lld: %s", who, static_cast<long long>(q), status_text(status));
+    return RDM_ERR_ARG;
+  }
+  out.resize(2 * static_cast<size_t>(G));
+  for (int64_t q = 0; q < G; ++q) {
+    out[2 * q] = fail[q] != 0 ? ST_SINGULAR : ST_OK;
+    out[2 * q + 1] = plan.sep_off[q + 1] - plan.sep_off[q];
+  }
+  return RDM_OK;
+}
 
 }  // namespace
 }  // namespace rdm
@@ -2510,52 +3082,198 @@ extern "C" int rdm_pose_graph_marginals(int64_t n_graphs, const int64_t* graph_n
   RDM_HIP_CHECK(hipMemcpyAsync(w.node_off, host.data(), host.size(), hipMemcpyHostToDevice, st));
   RDM_HIP_CHECK(hipStreamSynchronize(st));  // (`host` is pageable and leaves scope)
   const Graphs gr = {w.node_off, w.edge_off, w.edge_graph, w.node_graph, w.es, w.et, nullptr, w.inc_off, w.inc};
-  Params p = {};
-  p.gtol = -1.0;  // (pg_direct_blocks_kernel's gradient test never ends a graph: the blocks are wanted at a minimum too)
-  int *bad = w.flags, *failed = w.flags + 2;
-  const int n = static_cast<int>(N), e = static_cast<int>(E), g = static_cast<int>(G);
-  const DirectSystem sy = {w.es, w.et, w.inc_off, w.inc, w.D, w.Hab, w.rv, w.F, w.Wc, w.zv, w.xv};
-  const int runs = static_cast<int>(plan.run_begin.size()), couplings = static_cast<int>(plan.cpl_sep.size());
-  const long long items = plan.item_off.back();
-  fill_words<int>(w.flags, 4, 0, st);
-  fill_words<int>(dp.fail, G, 0, st);
-  hipLaunchKernelGGL(pg_marg_init_kernel, dim3(blocks_for(G)), dim3(kBlock), 0, st, w.gs, g, w.node_off);
-  hipLaunchKernelGGL(pg_check_kernel, dim3(blocks_for(std::max(N, E))), dim3(kBlock), 0, st, gr, nodes, n, transforms, informations, e,
-                     w.gs, bad);
-  hipLaunchKernelGGL(pg_marg_linearize_kernel, dim3(blocks_for(E)), dim3(kBlock), 0, st, gr, e, nodes, transforms, informations, weights,
-                     w.gs, w.Haa, w.Hab, w.Hbb, w.ga, w.gb, bad);
-  hipLaunchKernelGGL(pg_direct_blocks_kernel, dim3(static_cast<unsigned>(G)), dim3(kBlock), 0, st, gr, p, w.gs, w.Haa, w.Hab, w.Hbb, w.ga,
-                     w.gb, w.D, w.bv, w.xv, w.rv, w.Wc, dp.fail, bad);
-  if (runs > 0) hipLaunchKernelGGL(pg_direct_factor_kernel, dim3((runs + kWave - 1) / kWave), dim3(kWave), 0, st, dp, sy, runs, w.gs, bad);
-  if (couplings > 0)
-    hipLaunchKernelGGL(pg_direct_border_kernel, dim3(blocks_for(6ll * couplings)), dim3(kBlock), 0, st, dp, sy, couplings, w.gs, bad);
-  if (items > 0) hipLaunchKernelGGL(pg_direct_schur_kernel, dim3(blocks_for(items)), dim3(kBlock), 0, st, dp, sy, g, items, w.gs, bad);
-  hipLaunchKernelGGL(pg_marg_separator_kernel, dim3(static_cast<unsigned>(G)), dim3(kBlock), 0, st, dp, mg, w.gs, bad);
-  if (runs > 0) {
-    if (t_marg_ticks != nullptr)
-      hipLaunchKernelGGL(pg_marg_sweep_kernel<true>, dim3(runs), dim3(kWave), 0, st, dp, sy, mg, w.gs, bad, t_marg_ticks);
-    else
-      hipLaunchKernelGGL(pg_marg_sweep_kernel<false>, dim3(runs), dim3(kWave), 0, st, dp, sy, mg, w.gs, bad, static_cast<long long*>(nullptr));
-  }
-  hipLaunchKernelGGL(pg_report_kernel, dim3(1), dim3(64), 0, st, g, w.gs, bad, w.report, failed);
-  hipLaunchKernelGGL(pg_marg_finish_kernel, dim3(blocks_for(N)), dim3(kBlock), 0, st, gr, n, dp.fail, failed, mg.S, covariances_out);
+  enqueue_marginals(st, gr, w, dp, mg, plan, G, N, E, nodes, transforms, informations, weights);
+  hipLaunchKernelGGL(pg_marg_finish_kernel, dim3(blocks_for(N)), dim3(kBlock), 0, st, gr, static_cast<int>(N), dp.fail, w.flags + 2, mg.S,
+                     covariances_out);
   rc = launch_status("rdm_pose_graph_marginals");
   if (rc != RDM_OK) return rc;
-  std::vector<double> report(kReport * static_cast<size_t>(G));
-  std::vector<int> fail(static_cast<size_t>(G));
-  RDM_HIP_CHECK(hipMemcpyAsync(report.data(), w.report, sizeof(double) * kReport * G, hipMemcpyDeviceToHost, st));
-  RDM_HIP_CHECK(hipMemcpyAsync(fail.data(), dp.fail, sizeof(int) * G, hipMemcpyDeviceToHost, st));
-  RDM_HIP_CHECK(hipStreamSynchronize(st));
-  for (int64_t q = 0; q < G; ++q) {
-    const int status = static_cast<int>(report[q * kReport + 5]);
-    if (status == ST_OK) continue;
-    set_error("rdm_pose_graph_marginals: graph %lld: %s", static_cast<long long>(q), status_text(status));
+  std::vector<double> report;
+  rc = read_marginals_report("rdm_pose_graph_marginals", st, w, dp, plan, G, report);
+  if (rc != RDM_OK) return rc;
+  memcpy(report_host, report.data(), sizeof(double) * report.size());
+  return RDM_OK;
+}
+
+extern "C" int rdm_pose_graph_pair_terms_host(const double* source_pose, const double* target_pose, const double* transform,
+                                              const double* information, const double* cov_ss, const double* cov_tt, const double* cov_st,
+                                              double* out) {
+  using namespace rdm;
+  RDM_REQUIRE(source_pose && target_pose && transform && cov_ss && cov_tt && cov_st && out, "rdm_pose_graph_pair_terms_host: null argument");
+  double d2 = NAN;
+  const int status = pair_terms(source_pose, target_pose, transform, information, cov_ss, cov_tt, cov_st, out, out + 6, &d2);
+  if (status < 0) {
+    set_error("rdm_pose_graph_pair_terms_host: the residual rotation is beyond the supported angle");
     return RDM_ERR_ARG;
   }
-  for (int64_t q = 0; q < G; ++q) {
-    report_host[2 * q] = fail[q] != 0 ? ST_SINGULAR : ST_OK;
-    report_host[2 * q + 1] = plan.sep_off[q + 1] - plan.sep_off[q];
+  out[42] = d2;
+  out[43] = status;
+  return RDM_OK;
+}
+
+extern "C" int rdm_pose_graph_pair_covariances_host(int64_t n_nodes, int64_t n_edges, const int64_t* edges_host, const double* diag,
+                                                    const double* off, int64_t n_pairs, const int64_t* pairs_host, double* out) {
+  using namespace rdm;
+  const char* who = "rdm_pose_graph_pair_covariances_host";
+  RDM_REQUIRE(n_nodes >= 0 && n_nodes <= kMaxNodes && n_edges >= 0 && n_edges <= kMaxEdges && n_pairs >= 0 && n_pairs < kMaxTotal / 36,
+              "%s: bad sizes", who);
+  if (n_pairs == 0) return RDM_OK;
+  RDM_REQUIRE(diag && out && pairs_host && ((edges_host && off) || n_edges == 0), "%s: null argument", who);
+  const size_t N = static_cast<size_t>(n_nodes), P = static_cast<size_t>(n_pairs);
+  const std::vector<double> rhs(6 * (N > 0 ? N : 1), 0.0);
+  HostDirect h;
+  PairPlan pl;
+  const int64_t poff[2] = {0, n_pairs};
+  int rc = RDM_OK;
+  if (n_nodes > 0) rc = host_direct_factor(h, n_nodes, n_edges, edges_host, diag, off, rhs.data(), who, "");
+  if (rc != RDM_OK) return rc;
+  const int noff[2] = {0, static_cast<int>(n_nodes)};
+  if (n_nodes == 0) {
+    h.plan = DirectPlan();
+    h.plan.sep_off = {0, 0};
+    h.plan.cpl_off = {0};
   }
+  if (!build_pair_plan(1, noff, h.plan, poff, pairs_host, pl, who)) return RDM_ERR_ARG;
+  const int s = h.s;
+  std::vector<double> Z(h.C.size(), 0.0);
+  for (int t = 0; t < 6 * s; ++t) marg_inverse_column(h.C.data(), Z.data(), s, t / 6, t % 6);
+  for (int u = 0; u < s; ++u)
+    for (int v = 0; v <= u; ++v) marg_sigma_block(Z.data(), h.C.data(), s, u, v);
+  const size_t cols = std::min<size_t>(pl.col_node.size() > 0 ? pl.col_node.size() : 1, kColumnsInFlight);
+  std::vector<double> yf(36 * cols * pl.y_stride), us(36 * cols * pl.u_stride), xs(36 * cols * pl.x_stride), cross(36 * (P + 1), 0.0);
+  Pairs pp = {};
+  for_each_pair_table(pl, pp, [](const std::vector<int>& v, const int*& table) { table = v.empty() ? nullptr : v.data(); });
+  pp.y_stride = pl.y_stride;
+  pp.u_stride = pl.u_stride;
+  pp.x_stride = pl.x_stride;
+  pp.yf = yf.data();
+  pp.us = us.data();
+  pp.xs = xs.data();
+  pp.cross = cross.data();
+  const int K = static_cast<int>(pl.col_node.size());
+  for (int chunk = 0; chunk + 1 < static_cast<int>(pl.chunk_grp.size()); ++chunk) {  // a chunk's items in the kernels' order
+    const int k0 = chunk * kColumnsInFlight, n = std::min(K - k0, kColumnsInFlight);
+    for (int q = 0; q < n; ++q)
+      for (int c = 0; c < 6; ++c) cons_forward_column(h.dp, h.sy, pp, k0 + q, q, c);
+    for (int q = 0; q < n; ++q)
+      for (int v = 0; v < s; ++v)
+        for (int c = 0; c < 6; ++c) cons_separator_column(h.dp, pp, h.C.data(), s, 0, k0 + q, q, v, c);
+    for (int r = pl.chunk_grp[chunk]; r < pl.chunk_grp[chunk + 1]; ++r)
+      for (int c = 0; c < 6; ++c) cons_back_column(h.dp, h.sy, pp, 0, r, pl.grp_col[r] - k0, c);
+  }
+  for (size_t k = 0; k < P; ++k) {
+    const bool zero = pl.pair_s[k] == 0 || pl.pair_t[k] == 0;
+    for (int q = 0; q < 36; ++q) out[36 * k + q] = zero ? 0.0 : cross[36 * k + q];
+  }
+  return RDM_OK;
+}
+
+extern "C" size_t rdm_pose_graph_consistency_workspace_bytes(int64_t n_graphs, const int64_t* graph_node_offsets_host,
+                                                             const int64_t* graph_edge_offsets_host, const int64_t* edges_host,
+                                                             const int64_t* graph_pair_offsets_host, const int64_t* pairs_host) {
+  using namespace rdm;
+  std::vector<char> host;
+  DirectPlan plan;
+  PairPlan pairs;
+  if (build_consistency_plans("rdm_pose_graph_consistency", n_graphs, graph_node_offsets_host, graph_edge_offsets_host, edges_host,
+                              graph_pair_offsets_host, pairs_host, host, plan, pairs) != RDM_OK)
+    return 0;
+  Arena ar(nullptr, 0);
+  Work w;
+  Direct dp;
+  Marginals mg;
+  Pairs pp;
+  void* tables;
+  size_t tables_bytes;
+  carve_marginals(ar, n_graphs, graph_node_offsets_host[n_graphs], graph_edge_offsets_host[n_graphs], w, plan, dp, mg);
+  carve_pairs(ar, pairs, pp, &tables, &tables_bytes);
+  return ar.off;
+}
+
+extern "C" int rdm_pose_graph_consistency(int64_t n_graphs, const int64_t* graph_node_offsets_host, const int64_t* graph_edge_offsets_host,
+                                          const double* nodes, const int64_t* edges_host, const double* transforms,
+                                          const double* informations, const double* weights, const int64_t* graph_pair_offsets_host,
+                                          const int64_t* pairs_host, const double* pair_transforms, const double* pair_informations,
+                                          double* covariances_out, double* cross_out, double* residual_cov_out, double* d2_out,
+                                          uint8_t* pair_status_out, double* report_host, void* ws, size_t ws_bytes, void* stream) {
+  using namespace rdm;
+  const char* who = "rdm_pose_graph_consistency";
+  const int64_t G = n_graphs;
+  RDM_REQUIRE(G >= 0 && G < kMaxTotal, "%s: bad number of graphs", who);
+  if (G == 0) return RDM_OK;
+  RDM_REQUIRE(report_host, "%s: null argument", who);
+  std::vector<char> host;
+  DirectPlan plan;
+  PairPlan pairs;
+  int rc = build_consistency_plans(who, G, graph_node_offsets_host, graph_edge_offsets_host, edges_host, graph_pair_offsets_host, pairs_host,
+                                   host, plan, pairs);
+  if (rc != RDM_OK) return rc;
+  const int64_t N = graph_node_offsets_host[G], E = graph_edge_offsets_host[G], P = graph_pair_offsets_host[G];
+  RDM_REQUIRE(nodes || N == 0, "%s: null nodes", who);
+  RDM_REQUIRE((transforms && informations) || E == 0, "%s: null edges", who);
+  RDM_REQUIRE(pair_transforms || P == 0, "%s: null pair transforms", who);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  Arena ar(ws, ws_bytes);
+  Work w;
+  Direct dp;
+  Marginals mg;
+  Pairs pp;
+  void* tables = nullptr;
+  size_t tables_bytes = 0;
+  const bool fits = carve_marginals(ar, G, N, E, w, plan, dp, mg);
+  if (!carve_pairs(ar, pairs, pp, &tables, &tables_bytes) || !fits) {
+    set_error("%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, ar.off);
+    return RDM_ERR_WORKSPACE;
+  }
+  std::vector<char> pair_host(tables_bytes, 0);
+  {  // the pairs' tables in a host buffer laid out as the workspace's part
+    Arena hs(pair_host.data(), pair_host.size());
+    Pairs hp;
+    for_each_pair_table(pairs, hp, [&](const std::vector<int>& v, const int*& table) {
+      int* dst = hs.take<int>(v.size() > 0 ? v.size() : 1);
+      if (!v.empty()) memcpy(dst, v.data(), v.size() * sizeof(int));
+      table = dst;
+    });
+  }
+  RDM_HIP_CHECK(hipMemcpyAsync(w.node_off, host.data(), host.size(), hipMemcpyHostToDevice, st));
+  RDM_HIP_CHECK(hipMemcpyAsync(tables, pair_host.data(), pair_host.size(), hipMemcpyHostToDevice, st));
+  RDM_HIP_CHECK(hipStreamSynchronize(st));  // (the host buffers are pageable and leave scope)
+  const Graphs gr = {w.node_off, w.edge_off, w.edge_graph, w.node_graph, w.es, w.et, nullptr, w.inc_off, w.inc};
+  const DirectSystem sy = {w.es, w.et, w.inc_off, w.inc, w.D, w.Hab, w.rv, w.F, w.Wc, w.zv, w.xv};
+  int *bad = w.flags, *failed = w.flags + 2;
+  const int p_total = static_cast<int>(P);
+  enqueue_marginals(st, gr, w, dp, mg, plan, G, N, E, nodes, transforms, informations, weights);
+  fill_words<unsigned long long>(pp.bad_pair, 1, ~0ull, st);
+  fill_words<double>(pp.cross + 36 * P, 36, 0.0, st);
+  if (P > 0)
+    hipLaunchKernelGGL(pg_cons_check_kernel, dim3(blocks_for(P)), dim3(kBlock), 0, st, pp, p_total, nodes, pair_transforms, pair_informations,
+                       bad, failed);
+  if (covariances_out != nullptr)
+    hipLaunchKernelGGL(pg_marg_finish_kernel, dim3(blocks_for(N)), dim3(kBlock), 0, st, gr, static_cast<int>(N), dp.fail, failed, mg.S,
+                       covariances_out);
+  const int K = static_cast<int>(pairs.col_node.size());
+  for (int chunk = 0; chunk + 1 < static_cast<int>(pairs.chunk_grp.size()); ++chunk) {  // (on the stream: no read-back between chunks)
+    const int k0 = chunk * kColumnsInFlight, cols = std::min(K - k0, kColumnsInFlight);
+    const int r0 = pairs.chunk_grp[chunk], groups = pairs.chunk_grp[chunk + 1] - r0;
+    hipLaunchKernelGGL(pg_cons_forward_kernel, dim3(blocks_for(6ll * cols)), dim3(kBlock), 0, st, gr, dp, sy, pp, k0, cols, w.gs, bad);
+    hipLaunchKernelGGL(pg_cons_separator_kernel, dim3(blocks_for(6ll * cols * pp.x_stride)), dim3(kBlock), 0, st, gr, dp, pp, k0, cols, w.gs,
+                       bad);
+    hipLaunchKernelGGL(pg_cons_back_kernel, dim3(blocks_for(6ll * groups)), dim3(kBlock), 0, st, gr, dp, sy, pp, k0, r0, groups, w.gs, bad);
+  }
+  if (P > 0)
+    hipLaunchKernelGGL(pg_cons_pair_kernel, dim3(static_cast<unsigned>((P + kWave - 1) / kWave)), dim3(kWave), 0, st, gr, pp, p_total, nodes,
+                       pair_transforms, pair_informations, dp.fail, failed, mg.S, cross_out, residual_cov_out, d2_out, pair_status_out);
+  rc = launch_status(who);
+  if (rc != RDM_OK) return rc;
+  unsigned long long bad_pair = ~0ull;
+  RDM_HIP_CHECK(hipMemcpyAsync(&bad_pair, pp.bad_pair, sizeof(bad_pair), hipMemcpyDeviceToHost, st));
+  std::vector<double> report;
+  rc = read_marginals_report(who, st, w, dp, plan, G, report);
+  if (rc != RDM_OK) return rc;
+  if (bad_pair != ~0ull) {
+    set_error("%s: pair %llu: %s", who, bad_pair >> 3, status_text(static_cast<int>(bad_pair & 7)));
+    return RDM_ERR_ARG;
+  }
+  memcpy(report_host, report.data(), sizeof(double) * report.size());
   return RDM_OK;
 }
 

@@ -2056,6 +2056,107 @@ def pose_graph_marginals(nodes, edges, transforms, informations, weights=None, *
     return PoseGraphMarginals(out, report)
 
 
+class PoseGraphConsistency:
+    """What pose_graph_consistency returns, float64 on the device the call ran on.  covariances [N, 6, 6]: pose_graph_marginals' output,
+    bit for bit.  Per pair (s, t): cross [P, 6, 6] = Sigma_st (rows: s; zero with node 0), residual_covariances [P, 6, 6] = the
+    covariance M of the pair's residual under the graph (exactly symmetric), d2 [P] = r^T (M + L^-1)^-1 r, pair_status uint8 [P] (0; 1: L
+    or M + L^-1 is not positive definite, d2 is NaN).  Per graph, host numpy [G]: status (0; 4: the graph's rows and its pairs' are NaN)
+    and separator, as PoseGraphMarginals'."""
+
+    def __init__(self, covariances, cross, residual_covariances, d2, pair_status, report):
+        import numpy as np
+        self.covariances, self.cross, self.residual_covariances, self.d2, self.pair_status = covariances, cross, residual_covariances, d2, \
+            pair_status
+        rep = np.asarray(report, dtype=np.float64).reshape(-1, 2)
+        self.status, self.separator = rep[:, 0].astype(np.int64), rep[:, 1].astype(np.int64)
+
+
+def pose_graph_consistency(nodes, edges, transforms, informations, weights=None, *, pairs, pair_transforms=None, pair_informations=None,
+                           graph_node_offsets=None, graph_edge_offsets=None, graph_pair_offsets=None):
+    """Cross covariances of pairs of poses and the consistency of candidate edges with a pose graph on the GPU
+    (rdm_pose_graph_consistency; g2o's computeMarginals with block pairs, GTSAM's jointMarginalCovariance).  The
+    first five arguments and the node / edge offsets are pose_graph_marginals'.  pairs int64 [P, 2] rows (s, t) numbered inside their
+    graph (graph_pair_offsets int64 [G + 1]; None: one graph), pair_transforms float64 [P, 4, 4] with an edge's convention X_s = X_t T
+    (None: the current relative poses X_t^-1 X_s, formed in float64 on the device -- the result is then the covariance of the relative
+    pose and d2 is 0 up to rounding), pair_informations float64 [P, 6, 6] or None (d2 = r^T M^-1 r).  d2 is the squared Mahalanobis
+    distance of a measured edge from the graph's relative pose under the graph's uncertainty plus its own; it is only as calibrated as
+    the information matrices are.  -> PoseGraphConsistency.  ValueError, before any library call, for what pose_graph_marginals raises
+    and for the pairs' shape, offsets, s = t and a node outside its graph; RuntimeError (nothing written) for what the library
+    refuses: pose_graph_marginals' cases, a non-finite pair transform or information, an asymmetric information, a pair residual
+    beyond the angle limit."""
+    import numpy as np
+    who = 'pose_graph_consistency'
+
+    def check_pairs():
+        pr = np.asarray(pairs.detach().cpu().numpy() if isinstance(pairs, torch.Tensor) else pairs)
+        if pr.ndim != 2 or pr.shape[1] != 2 or pr.dtype.kind not in 'iu':
+            raise ValueError(f'{who}: pairs must be integers [*, 2], got {pr.dtype} {tuple(pr.shape)}')
+        state['pairs'] = pr = np.ascontiguousarray(pr.astype(np.int64, copy=False))
+        p = pr.shape[0]
+        for t, shape, name in ((pair_transforms, (4, 4), 'pair_transforms'), (pair_informations, (6, 6), 'pair_informations')):
+            got = None if t is None else tuple(t.shape) if hasattr(t, 'shape') else np.shape(t)
+            if t is not None and got != (p,) + shape:
+                raise ValueError(f'{who}: {name} must be [{p}, {shape[0]}, {shape[1]}] (one per pair), got {got}')
+        n = np.asarray(nodes).shape[0] if not isinstance(nodes, torch.Tensor) else nodes.shape[0]
+        if (graph_pair_offsets is None) != (graph_node_offsets is None):
+            raise ValueError(f'{who}: graph_pair_offsets goes with graph_node_offsets and graph_edge_offsets')
+        noff = np.array([0, n], np.int64) if graph_node_offsets is None else np.asarray(
+            graph_node_offsets.cpu() if isinstance(graph_node_offsets, torch.Tensor) else graph_node_offsets, dtype=np.int64)
+        poff = np.array([0, p], np.int64) if graph_pair_offsets is None else np.ascontiguousarray(np.asarray(
+            graph_pair_offsets.cpu() if isinstance(graph_pair_offsets, torch.Tensor) else graph_pair_offsets, dtype=np.int64))
+        if poff.ndim != 1 or poff.shape != noff.shape or poff[0] != 0 or poff[-1] != p or np.any(np.diff(poff) < 0):
+            raise ValueError(f'{who}: graph_pair_offsets must be [G + 1], ascending, from 0 to the number of pairs')
+        state['poff'] = poff
+        size = np.repeat(np.diff(noff), np.diff(poff))
+        same = np.nonzero(pr[:, 0] == pr[:, 1])[0]
+        if len(same):
+            raise ValueError(f'{who}: pair {same[0]} joins node {pr[same[0], 0]} to itself')
+        out = np.nonzero((pr < 0).any(1) | (pr >= size[:, None]).any(1))[0]
+        if len(out):
+            k = out[0]
+            raise ValueError(f'{who}: pair {k} ({pr[k, 0]}, {pr[k, 1]}) is outside its graph of {size[k]} nodes')
+
+    state = {}
+    dev, X, T, Lm, ed, _, noff, eoff, g, W = _pose_graph_args(who, nodes, edges, transforms, informations, None, graph_node_offsets,
+                                                              graph_edge_offsets, weights=weights, before_connectivity=check_pairs)
+    pr, poff = state['pairs'], state['poff']
+    n, p = X.shape[0], pr.shape[0]
+
+    def moved(t):
+        t = t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float64)))
+        return t.detach().to(device=dev, dtype=torch.float64).contiguous()
+
+    if pair_transforms is None:  # X_t^-1 X_s with the closed-form inverse [R^T | -R^T t]
+        glob = torch.from_numpy(pr + np.repeat(noff[:-1], np.diff(poff))[:, None]).to(dev)
+        Xs, Xt = X[glob[:, 0]], X[glob[:, 1]]
+        Rt = Xt[:, :3, :3].transpose(1, 2)
+        PT = torch.zeros((p, 4, 4), dtype=torch.float64, device=dev)
+        PT[:, :3, :3] = Rt @ Xs[:, :3, :3]
+        PT[:, :3, 3] = (Rt @ (Xs[:, :3, 3] - Xt[:, :3, 3]).unsqueeze(2)).squeeze(2)
+        PT[:, 3, 3] = 1.0
+    else:
+        PT = moved(pair_transforms)
+    PL = None if pair_informations is None else moved(pair_informations)
+    L = _lib.lib()
+    cov = torch.empty((n, 6, 6), dtype=torch.float64, device=dev)
+    cross, resid = (torch.empty((p, 6, 6), dtype=torch.float64, device=dev) for _ in range(2))
+    d2 = torch.empty(p, dtype=torch.float64, device=dev)
+    pstat = torch.empty(p, dtype=torch.uint8, device=dev)
+    report = np.zeros((g, 2), np.float64)
+    with torch.cuda.device(dev):
+        size = L.rdm_pose_graph_consistency_workspace_bytes(g, noff.ctypes.data, eoff.ctypes.data, ed.ctypes.data, poff.ctypes.data,
+                                                            pr.ctypes.data)
+        if size == 0:  # (an edge outside its graph, a graph above a limit: the library's message, before any GPU work)
+            _lib.check(-1, 'rdm_pose_graph_consistency')
+        ws = scratch(dev, size)
+        _lib.check(L.rdm_pose_graph_consistency(g, noff.ctypes.data, eoff.ctypes.data, _lib.ptr(X), ed.ctypes.data, _lib.ptr(T), _lib.ptr(Lm),
+                                                0 if W is None else _lib.ptr(W), poff.ctypes.data, pr.ctypes.data, _lib.ptr(PT),
+                                                0 if PL is None else _lib.ptr(PL), _lib.ptr(cov), _lib.ptr(cross), _lib.ptr(resid),
+                                                _lib.ptr(d2), _lib.ptr(pstat), report.ctypes.data, ws.data_ptr(), ws.numel(),
+                                                _lib.stream_ptr()), 'rdm_pose_graph_consistency')
+    return PoseGraphConsistency(cov, cross, resid, d2, pstat, report)
+
+
 def _gt_check(t, name, shape, dtype, device):
     if not isinstance(t, torch.Tensor):
         raise RuntimeError(f'gt_node_correspondences: {name} must be a tensor')

@@ -2,6 +2,7 @@
 
     python -m rdmnet_amd.trajectory --features-root DIR [--optimize] [--line-process-weight MU] [--unit-information] [--out DIR]
                                   [--preconditioner {block_jacobi,chain}] [--linear-solver {pcg,direct}] [--covariance]
+                                  [--loop-consistency] [--loop-gate D2]
                                   [--map-scans DATASET_ROOT [--map-raw] [--map-voxel 0.3] [--map-min-points 1]
                                    [--map-range LO HI] [--map-batch 64] [--map-sharpness [--map-sharpness-min-points 4]]
                                    [--map-min-scans 1]
@@ -24,8 +25,16 @@ of every optimised pose given frame 0 (`ops.pose_graph_marginals` at the optimis
 edges at 0; one call per sequence): the median and the largest position sigma (root of the trace of the translation block, metres) and
 rotation sigma (root of the trace of the rotation block, degrees) with the frames of the largest, or `not computed (K separator nodes,
 limit 256)` for a sequence with more loop structure than the selected inversion takes -- and --out gets `{seq}_optimized_covariance.txt`,
-one row of 36 numbers per frame of the chain (the 6 x 6 block of the right perturbation, rotation first; the first row zeros).  Without --optimize no
-GPU is needed.  Everything here is numpy float64 on the host.  With --map-scans (and --out) the scans of every sequence's chain
+one row of 36 numbers per frame of the chain (the 6 x 6 block of the right perturbation, rotation first; the first row zeros).  With
+--loop-consistency (which needs the GPU but not --optimize) every sequence's `chained:` line is followed by a `loop consistency:` line:
+the graph of the certain edges alone (the odometry chain) at the chained poses is asked how far every loop edge lies from the relative
+pose it gives -- d2 = r^T (M + L^-1)^-1 r with M the covariance of the edge's residual under the chain (`ops.pose_graph_consistency`) and
+L the edge's information -- and the line names the number of loop edges, the median and the largest d2 with its pair file; --out gets
+`{seq}_loop_consistency.txt` (file name, s, t, d2 per loop edge).  --loop-gate D2 (needs --optimize, implies --loop-consistency, has no
+default) leaves the loop edges with d2 > D2 (or without a d2) out of the optimised graph, the line ends with `, G above the gate D2`, and
+the pose graph, uncertainty and map lines describe the graph that was optimised.  d2 is only as calibrated as the information matrices
+are -- Open3D's scales with the number of correspondences -- so the gate is the user's number, not a chi-square quantile.  Without
+--optimize and --loop-consistency no GPU is needed.  Everything here is numpy float64 on the host.  With --map-scans (and --out) the scans of every sequence's chain
 frames are fused under the chained -- and with --optimize also the optimised -- poses into a voxel map on the GPU (`build_map`,
 `ops.VoxelMap`) and written as `{seq}_{variant}_map.npy`; a better trajectory puts the same surfaces into
 fewer voxels, so voxels and points per voxel of the two variants are a check of --optimize that needs no ground truth.  The
@@ -208,6 +217,38 @@ def uncertainty_line(seq, cov, limit=256):
     rot = np.degrees(np.sqrt(np.trace(cov[:, :3, :3], axis1=1, axis2=2)))
     return (f'seq {seq} optimized uncertainty: position sigma median {np.median(pos):.6g} m, max {pos.max():.6g} m at frame '
             f'{int(np.argmax(pos))}; rotation sigma median {np.median(rot):.6g} deg, max {rot.max():.6g} deg at frame {int(np.argmax(rot))}')
+
+
+def loop_consistency(graph):
+    """The squared Mahalanobis distance d2 [K] of every loop (uncertain) edge of one sequence's graph from the relative pose that the
+    odometry chain alone gives, under the chain's uncertainty plus the edge's own (ops.pose_graph_consistency on the graph of the
+    certain edges at the chained poses, every loop edge a pair with its transform and information), and the loop edges' numbers in the
+    graph.  An edge whose d2 cannot be formed (an information matrix that is not positive definite) has NaN."""
+    from . import ops
+    nodes, edges, transforms, infos, uncertain = graph[:5]
+    loops, chain = np.nonzero(uncertain != 0)[0], np.nonzero(uncertain == 0)[0]
+    if len(loops) == 0:
+        return np.zeros(0), loops
+    res = ops.pose_graph_consistency(nodes, edges[chain], transforms[chain], infos[chain], pairs=edges[loops],
+                                     pair_transforms=transforms[loops], pair_informations=infos[loops])
+    return res.d2.cpu().numpy(), loops
+
+
+def loop_consistency_line(seq, graph, d2, loops, gate=None):
+    if len(loops) == 0:
+        return f'seq {seq} loop consistency: 0 loop edges'
+    worst = int(np.argmax(np.where(np.isnan(d2), np.inf, d2)))
+    line = (f'seq {seq} loop consistency: {len(loops)} loop edges, d2 median {np.median(d2):.6g}, max {d2[worst]:.6g} '
+            f'({graph[5][int(loops[worst])]})')
+    if gate is not None:
+        line += f', {int(np.count_nonzero(~(d2 <= gate)))} above the gate {gate:g}'
+    return line
+
+
+def without_edges(graph, drop):
+    """The sequence graph without the edges numbered `drop`."""
+    keep = np.setdiff1d(np.arange(len(graph[1])), drop)
+    return (graph[0], graph[1][keep], graph[2][keep], graph[3][keep], graph[4][keep], [graph[5][int(k)] for k in keep])
 
 
 def report_line(seq, what, err):
@@ -663,8 +704,19 @@ def run(args, emit=print):
     covariance = bool(getattr(args, 'covariance', False))
     if covariance and not args.optimize:
         raise TrajectoryError('--covariance needs --optimize')
+    gate = getattr(args, 'loop_gate', None)
+    if gate is not None and not args.optimize:
+        raise TrajectoryError('--loop-gate needs --optimize')
     seqs = read_sequences(args.features_root, args.unit_information)
     graphs = {seq: sequence_graph(s) for seq, s in seqs.items()}
+    consistency = {}
+    if getattr(args, 'loop_consistency', False) or gate is not None:
+        for seq in graphs:  # (before anything is optimised: the gate decides what is)
+            d2, loops = loop_consistency(graphs[seq])
+            consistency[seq] = (loop_consistency_line(seq, graphs[seq], d2, loops, gate),
+                                [(graphs[seq][5][int(e)], *graphs[seq][1][int(e)], v) for e, v in zip(loops, d2)])
+            if gate is not None:
+                graphs[seq] = without_edges(graphs[seq], loops[~(d2 <= gate)])
     scans = map_paths(args, seqs)
     if args.out:
         os.makedirs(args.out, exist_ok=True)
@@ -718,6 +770,12 @@ def run(args, emit=print):
             emit(report_line(seq, 'chained', absolute_trajectory_error(traj, gts[seq])))
         else:
             emit(f'seq {seq} chained: no ground truth in the pair files')
+        if seq in consistency:
+            emit(consistency[seq][0])
+            if args.out:
+                with open(osp.join(args.out, f'{seq}_loop_consistency.txt'), 'w') as f:
+                    for name, a, b, v in consistency[seq][1]:
+                        f.write(f'{name} {a} {b} {v:.9e}\n')
         if args.out:
             write_kitti_poses(osp.join(args.out, f'{seq}_chained.txt'), graphs[seq][0])
         if scans:
@@ -820,6 +878,14 @@ def make_parser():
     ap.add_argument('--covariance', action='store_true',
                     help='after --optimize: the marginal covariance of every optimised pose given frame 0 -- an `optimized uncertainty:` '
                          'line per sequence and, with --out, {seq}_optimized_covariance.txt (one 6 x 6 block per frame, rotation first)')
+    ap.add_argument('--loop-consistency', action='store_true',
+                    help='per sequence, the squared Mahalanobis distance d2 of every loop edge from the relative pose the odometry chain '
+                         'gives, under the chain\'s uncertainty plus the edge\'s own (GPU; works without --optimize): a `loop consistency:` '
+                         'line and, with --out, {seq}_loop_consistency.txt (file, s, t, d2 per loop edge).  d2 is only as calibrated as '
+                         'the information matrices are: Open3D\'s scales with the number of correspondences, so it is no chi-square value')
+    ap.add_argument('--loop-gate', type=positive_finite, default=None, metavar='D2',
+                    help='with --optimize (implies --loop-consistency; no default): loop edges with d2 > D2 are left out of the optimised '
+                         'graph.  The threshold is yours to choose from the d2 of your runs, not a chi-square quantile (see above)')
     ap.add_argument('--out', default=None, help='directory for one KITTI-format pose file per sequence and variant')
     ap.add_argument('--map-scans', default=None, metavar='DATASET_ROOT',
                     help='fuse the scans of every chain frame under each trajectory into a voxel map on the GPU, written to --out as '

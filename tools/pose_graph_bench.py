@@ -4,7 +4,7 @@ for comparison: the restatement's dense solve (tests/pose_graph_restatement.py, 
 and, where scipy is importable, the same damped Gauss-Newton iteration with a sparse direct solve (scipy.sparse.linalg.spsolve).
 
   python tools/pose_graph_bench.py [--nodes 500] [--loops 40] [--batch 11] [--reps 3] [--cpu] [--preconditioner chain]
-                                     [--linear-solver direct] [--marginals] [--digest host | gpu]
+                                     [--linear-solver direct] [--marginals] [--consistency] [--digest host | gpu]
 With --digest (and nothing else): no timing, one sha1 line per result of the library's host entry points (host: no GPU needed, see
 digest_host()) or of the GPU solves of the test graphs (gpu, see digest_gpu()), for comparing the bits of two builds of the library
 (RDM_LIB_PATH).  Otherwise prints one JSON line: sizes, GPU ms per call (median; a call ends with its read-back), outer iterations, PCG iterations per outer
@@ -13,7 +13,11 @@ the output; without the flag the call and the output are what they were.  --line
 also times ops.pose_graph_marginals (rdm_pose_graph_marginals) at the optimised poses with the final weights, pruned edges at 0,
 beside the optimise call of the same run -- ms per call, its ratio to the optimise call, and for the single graph how the run
 sweep's wavefronts spent their time (rdm_dbg_pose_graph_marginals_ticks: the columns' products, the butterflies, the nodes' steps) --
-and, with --cpu, np.linalg.inv on the same graph's dense H."""
+and, with --cpu, np.linalg.inv on the same graph's dense H.  --consistency (which implies --marginals, whose figures stay beside it)
+also times ops.pose_graph_consistency (rdm_pose_graph_consistency) on the same graph, poses and weights, once with every graph's loop
+edges as the pairs (their own transforms and informations) and once with 4096 seeded random pairs per graph (the current relative
+poses, no informations) -- ms per call, its ratio to the marginals call, the distinct column nodes -- and, with --cpu, the dense
+route beside it: np.linalg.inv of H (the figure above) plus reading the pairs' blocks out of it."""
 import argparse
 import hashlib
 import json
@@ -218,7 +222,10 @@ def main():
     ap.add_argument('--preconditioner', choices=('block_jacobi', 'chain'), default=None)
     ap.add_argument('--linear-solver', choices=('pcg', 'direct'), default=None)
     ap.add_argument('--marginals', action='store_true', help='also time ops.pose_graph_marginals at the optimised poses')
+    ap.add_argument('--consistency', action='store_true',
+                    help='also time ops.pose_graph_consistency there: the loop edges as pairs, and 4096 random pairs per graph')
     a = ap.parse_args()
+    a.marginals = a.marginals or a.consistency
     if a.digest is not None:
         return digest_host() if a.digest == 'host' else digest_gpu()
     import torch
@@ -281,10 +288,47 @@ def main():
                 row['sweep_runs'] = len(t)
                 row['sweep_us_longest_run'] = dict(zip(('columns', 'butterflies', 'node_steps'), t[np.argmax(t.sum(1))].round(1).tolist()))
                 row['sweep_us_all_runs'] = dict(zip(('columns', 'butterflies', 'node_steps'), t.sum(0).round(1).tolist()))
+        if a.consistency:
+            import pose_graph_consistency_restatement as C
+            X = res.nodes.cpu().numpy()
+            rng = np.random.default_rng(7)
+            loops, rand = [], []
+            for k, g in enumerate(gs):
+                unc = np.nonzero(g['uncertain'])[0]
+                loops.append((g['edges'][unc], g['transforms'][unc], g['informations'][unc]))
+                pr = rng.integers(0, len(g['nodes']), size=(3 * 4096, 2))
+                pr = pr[pr[:, 0] != pr[:, 1]][:4096]
+                Xg = X[noff[k]:noff[k + 1]]
+                rand.append((pr, np.stack([C.current_transform(Xg[s], Xg[t]) for s, t in pr]), None))
+            for name, sets in (('loop_edges', loops), ('random_4096', rand)):
+                poff = np.cumsum([0] + [len(p[0]) for p in sets])
+                pairs = np.concatenate([p[0] for p in sets])
+                PT = torch.from_numpy(np.concatenate([p[1] for p in sets])).cuda()
+                PL = None if sets[0][2] is None else torch.from_numpy(np.concatenate([p[2] for p in sets])).cuda()
+                cons = lambda: ops.pose_graph_consistency(res.nodes, cat['edges'], dev['transforms'], dev['informations'], w, pairs=pairs,
+                                                          pair_transforms=PT, pair_informations=PL, graph_node_offsets=noff,
+                                                          graph_edge_offsets=eoff, graph_pair_offsets=poff)
+                r = cons()  # warm-up
+                torch.cuda.synchronize()
+                ct = []
+                for _ in range(a.reps):
+                    t0 = time.perf_counter()
+                    r = cons()
+                    ct.append((time.perf_counter() - t0) * 1e3)
+                assert torch.equal(r.covariances, m.covariances)
+                d2 = r.d2[torch.isfinite(r.d2)]
+                row['consistency_' + name] = {
+                    'pairs': int(len(pairs)), 'columns': int(len(np.unique(pairs[:, 1] + np.repeat(noff[:-1], np.diff(poff))))),
+                    'ms': float(np.median(ct)), 'ms_all': ct, 'per_marginals': float(np.median(ct)) / row['marginals_ms'],
+                    'pair_status_1': int((r.pair_status != 0).sum()), 'd2_median': float(d2.median()) if len(d2) else None,
+                    'd2_max': float(d2.max()) if len(d2) else None}
+            row['_pairs_for_host'] = rand[0][0]
         return row
 
     out['one_graph'] = run(graphs[:1])
     out['batch_of_graphs'] = run(graphs)
+    host_pairs = out['one_graph'].pop('_pairs_for_host', None)
+    out['batch_of_graphs'].pop('_pairs_for_host', None)
     if a.cpu:
         c = graphs[0]
         t0 = time.perf_counter()
@@ -300,6 +344,13 @@ def main():
                 inv_ms.append((time.perf_counter() - t0) * 1e3)
             out['host_dense_inverse'] = {'ms': float(np.median(inv_ms)), 'ms_all': inv_ms, 'unknowns': len(H),
                                          'threads': os.environ.get('OMP_NUM_THREADS')}
+            if a.consistency:  # the dense route to the same pairs' blocks: the inverse, then 3 blocks per pair read out of it
+                t0 = time.perf_counter()
+                S = np.zeros((len(H) + 6, len(H) + 6))
+                S[6:, 6:] = np.linalg.inv(H)
+                blocks = [(S[6 * s:6 * s + 6, 6 * s:6 * s + 6], S[6 * t:6 * t + 6, 6 * t:6 * t + 6], S[6 * s:6 * s + 6, 6 * t:6 * t + 6])
+                          for s, t in host_pairs.tolist()]
+                out['host_dense_pair_blocks'] = {'ms': (time.perf_counter() - t0) * 1e3, 'pairs': len(blocks)}
         try:
             import scipy  # noqa: F401
         except ImportError:
